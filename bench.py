@@ -1,7 +1,11 @@
 #!/usr/bin/env python3
 """Headline benchmark: images/sec at 256x256, 50 DDIM steps, k=4 retrieval (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W [--config {2,3,4}]
+    python bench.py --gpus N --steps K --warmup W [--config {2,3,4,5}] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times K steps, writes the last timed step's outputs if --dump-outputs is given, and prints the result
+line (metric, value, unit, ms_per_step, ...).  Everything else the benchmark measures (box calibration, roofline objects, extras, CPU
+baseline) runs only with --full.
 
 A "step" is one pass of the whole hot path over one batch of synthetic inputs that are already resident in HBM.
   --config 3 (default, the configuration the metric is quoted on): exact kNN of B=64 query embeddings over the
@@ -26,7 +30,11 @@ with the product's helpers (rdm_amd.parallel: shard_range / per_sample_noise / a
 rows — inputs are a function of the GLOBAL row index — weights and DB are replicated, the only collective is the all-gather of
 the finished images (weak scaling).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with
+--dump-outputs DIR: rank 0 writes the images of the last timed step (what a caller of the path receives) as DIR/images.npy in float32;
+above 64 MB a fixed, seeded sample of rows is kept, their indices in DIR/images_rows.npy.  Inputs are seeded: the same arguments give the
+same inputs on every run.
+
+Prints ONE JSON line on rank 0 (contract in the task statement); with --full it also carries
   roofline      dominant kernel = the 3x3 convolution (63 % of all FLOPs), MFMA-bound: achieved = algorithmic FLOPs
                 (2*M*N*9*Cin per launch) / HIP-event time of those launches, recorded live INSIDE the timed region on the
                 library's stream; peak 2.5 PFLOP/s dense bf16.  `traffic` = HBM bytes per launch from the committed rocprofv3
@@ -34,6 +42,8 @@ Prints ONE JSON line on rank 0 (contract in the task statement) with
                 kernel classes: linear GEMMs, flash attention, GroupNorm, LayerNorm, and `knn` (HBM-bound: bytes of the
                 database pass / ms, against 8 TB/s).
   cpu_baseline  the fp32 PyTorch oracle (kind "port") on this box's host cores on a bounded sample of config #1.
+  calibration   fixed MFMA / HBM probes before the warm-up and the shader clock through the timed region (value_at_reference_box).
+  extras        the untimed profiled step's time and, for configs 2 and 3, images/s at guidance scale 1.0.
 """
 import argparse
 import json
@@ -58,9 +68,15 @@ def parse():
     p.add_argument("--k", type=int, default=None, help="neighbours (default 4; 1 for --config 2; 16 for --config 4)")
     p.add_argument("--scale", type=float, default=2.0)
     p.add_argument("--db-rows", type=int, default=20_927_907, help="OpenImages DB rows (SURVEY §8 a-13)")
+    p.add_argument("--full", action="store_true",
+                   help="also measure what the headline does not need: box calibration, roofline objects (HIP events on the last timed step, one untimed "
+                        "profiled step), the guidance-scale-1.0 step and the CPU baseline; --no-calibration / --no-extras / --no-cpu-baseline trim it")
+    p.add_argument("--dump-outputs", default=None, metavar="DIR",
+                   help="rank 0 writes the last timed step's images to DIR/images.npy (float32, at most 64 MB: a fixed, seeded sample of rows above that)")
     p.add_argument("--no-cpu-baseline", action="store_true")
     p.add_argument("--full-cpu-baseline", action="store_true",
-                   help="SURVEY 8d's protocol instead of the bounded sample: 1 warm-up + 3 FULL config-#1 runs (50 DDIM steps + decode), median; ~5 min on 32 cores")
+                   help="SURVEY 8d's protocol instead of the bounded sample: 1 warm-up + 3 FULL config-#1 runs (50 DDIM steps + decode), median; ~5 min on 32 cores; "
+                        "implies --full")
     p.add_argument("--no-extras", action="store_true", help="skip the untimed extras (per-class roofline step, guidance-scale-1.0 step)")
     p.add_argument("--gather", choices=("f32", "uint8"), default="f32",
                    help="N > 1: what the one collective moves -- the decoded fp32 images [B,3,256,256] (50 MB per rank at B = 64, default) or their "
@@ -73,7 +89,33 @@ def parse():
     a.ddim_steps_given = a.ddim_steps is not None
     a.ddim_steps = a.ddim_steps if a.ddim_steps is not None else (250 if a.config == 4 else 50)
     a.steps = a.steps if a.steps is not None else (1 if a.config == 4 else 3)
+    a.full = a.full or a.full_cpu_baseline
+    if a.steps < 1 or a.warmup < 0:
+        p.error("--steps must be >= 1 and --warmup >= 0")
     return a
+
+
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(out_dir, arrays, limit=DUMP_LIMIT_BYTES):
+    """Writes every tensor of `arrays` ({name: tensor}) as out_dir/<name>.npy in float32 (float64 stays float64).  If they would
+    take more than `limit` bytes together, each keeps the same fixed, seeded sample of its leading-axis rows (the budget shared
+    in proportion to size), sorted, with the row indices beside it as <name>_rows.npy (float64)."""
+    import numpy as np
+    import torch
+    os.makedirs(out_dir, exist_ok=True)
+    width = {n: 8 if t.dtype == torch.float64 else 4 for n, t in arrays.items()}
+    total = sum(width[n] * t.numel() for n, t in arrays.items())
+    for name, t in arrays.items():
+        if total > limit:
+            share = width[name] * t.numel() / total
+            keep = max(1, int(limit * share - 256) // (width[name] * t[0].numel() + 8))        # + 8: its float64 row index; 256: .npy headers
+            rows = np.sort(np.random.default_rng(0).choice(t.shape[0], size=min(keep, t.shape[0]), replace=False))
+            t = t.index_select(0, torch.from_numpy(rows).to(t.device))
+            np.save(os.path.join(out_dir, f"{name}_rows.npy"), rows.astype(np.float64))
+        t = t if t.dtype == torch.float64 else t.float()
+        np.save(os.path.join(out_dir, f"{name}.npy"), t.cpu().numpy())
 
 
 def cpu_baseline_full(scale):
@@ -325,7 +367,7 @@ def main():
     # ---- box calibration (untimed, < 3 s): fixed MFMA and HBM-stream probes that do not change with the product kernels -- boxes of the
     # pool differ by +-4..5 % under the power cap and the headline moves with them; `value_at_reference_box` rescales by these readings
     calib = None
-    if not a.no_calibration:
+    if a.full and not a.no_calibration:
         try:
             tf_, gb_ = ctx.calib_probe(mfma_ms=800.0, stream_bytes=1 << 30, stream_reps=6)
             calib = {"mfma_probe_tflops": tf_, "hbm_stream_gbps": gb_}
@@ -339,22 +381,24 @@ def main():
     for i in range(a.warmup):
         step(i)
     fence()
-    ctx.prof_reset()
+    if a.full:
+        ctx.prof_reset()
     box_sampler = BoxSampler() if (calib is not None and rank == 0) else None
     if box_sampler:
         box_sampler.start()
-    # dominant kernel: HIP events (on the library's stream) around its launches INSIDE the timed region, on the LAST timed step only --
+    # --full, dominant kernel: HIP events (on the library's stream) around its launches INSIDE the timed region, on the LAST timed step only --
     # 2 524 event pairs per step on every step cost the headline what a sampled step measures just as well (a host-side flag: no sync)
     t0 = time.perf_counter()
     for i in range(a.warmup, total_steps):
-        if i == total_steps - 1:
+        if a.full and i == total_steps - 1:
             ctx.prof_enable((_lib.PROF_CONV3X3,))
         img = step(i)
     fence()
     dt = time.perf_counter() - t0
     if box_sampler:
         calib.update(box_sampler.stop())
-    ctx.prof_enable(())
+    if a.full:
+        ctx.prof_enable(())
     rank_ms = None
     if world > 1:
         # max over ranks is the job's time (contract); every rank's own time rides along so that a straggler is visible in the line
@@ -366,13 +410,15 @@ def main():
     assert img.shape[0] == world * B and bool(torch.isfinite(img.float()).all()), "non-finite images"
     if a.dump_images and rank == 0:
         np.save(a.dump_images, img.cpu().numpy())
-    n_conv, ms_conv, fl_conv = ctx.prof_collect(_lib.PROF_CONV3X3)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(a.dump_outputs, {"images": img})
+    n_conv, ms_conv, fl_conv = ctx.prof_collect(_lib.PROF_CONV3X3) if a.full else (0, 0.0, 0.0)
 
     # ---- one extra UNTIMED step with events around every other kernel class (their event records would otherwise sit in
     # the timed region: ~25 k launches per step)
     classes = {}
     extras = {}
-    if not a.no_extras:
+    if a.full and not a.no_extras:
         ctx.prof_reset()
         ctx.prof_enable((_lib.PROF_LINEAR, _lib.PROF_KNN, _lib.PROF_ATTENTION, _lib.PROF_GROUPNORM, _lib.PROF_LAYERNORM, _lib.PROF_UPSCONV))
         torch.cuda.synchronize(); t1 = time.perf_counter()
@@ -404,114 +450,117 @@ def main():
     # HBM traffic of the dominant kernel: PMC counters cannot be read from inside the process -- taken from the committed
     # rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE passes of this command (gfx950 corrections applied; profiles/README.md)
     traffic, traffic_src, pmc = None, None, {}
-    for name in ("r06_pmc.json", "r05_pmc.json", "r04_pmc.json", "r03_pmc.json", "r02_pmc.json", "r01_pmc_v4.json"):
-        try:
-            with open(os.path.join(ROOT, "profiles", name)) as f:
-                pmc = json.load(f)
-            traffic = pmc["hbm_bytes_per_launch"]; traffic_src = name
-            break
-        except Exception:
-            pmc = {}
+    if a.full:
+        for name in ("r06_pmc.json", "r05_pmc.json", "r04_pmc.json", "r03_pmc.json", "r02_pmc.json", "r01_pmc_v4.json"):
+            try:
+                with open(os.path.join(ROOT, "profiles", name)) as f:
+                    pmc = json.load(f)
+                traffic = pmc["hbm_bytes_per_launch"]; traffic_src = name
+                break
+            except Exception:
+                pmc = {}
 
     if rank == 0:
         images = world * B * a.steps
-        achieved = fl_conv / (ms_conv * 1e-3) / 1e12 if ms_conv > 0 else 0.0
         sampler = (f"{a.ddim_steps}-step ancestral DDPM (p_sample_loop, no CFG)" if a.config == 4
                    else "256 autoregressive tokens (RARM transformer 18 x 768 with K/V cache, top-k 256, guidance 1.0)" if a.config == 5
                    else f"{a.ddim_steps}-step DDIM (eta 0, CFG scale {a.scale:.1f})")
         front = ("CLIP ViT-B/32 text tower on 64 captions (no retrieval, k=1)" if a.config == 2
                  else f"exact kNN (k={k}) over a synthetic {N} x 512 fp16 CLIP DB")
-        roof = {"kernel": "conv3x3_halo4_kernel<3> + igemm_kernel<..,conv> (3x3 conv, bf16 MFMA, fp32 accumulate)", "bound": "mfma",
-                "achieved": achieved, "peak": 2500.0, "unit": "TFLOP/s", "frac": achieved / 2500.0, "traffic": traffic,
-                "traffic_note": f"bytes per launch of the dominant conv kernel from the committed rocprofv3 PMC passes (profiles/{traffic_src}), not collected in this run",
-                "launches": n_conv, "avg_launch_ms": ms_conv / max(n_conv, 1),
-                "algorithmic_tflop_per_launch": fl_conv / max(n_conv, 1) / 1e12, "conv_time_frac_of_step": ms_conv * 1e-3 / (dt / a.steps)}      # events cover the LAST timed step only
-        for name, (n_, ms_, w_) in classes.items():
-            if n_ == 0:
-                continue
-            if name == "upsample_conv_by_phase":
-                # Upsample's nearest-2x + conv3x3 as four 2x2-tap convs at source resolution (igemm_kernel<.., 3>): EXECUTED FLOPs = 4/9 of the
-                # nine-tap count the reference's F.interpolate + conv2d performs
-                ach = w_ / (ms_ * 1e-3) / 1e12
-                roof[name] = {"kernel": "igemm_kernel<BM, BN, W, 3> (pre-summed phase weights)", "bound": "mfma", "achieved": ach, "peak": 2500.0, "unit": "TFLOP/s",
-                              "frac": ach / 2500.0, "launches": n_, "time_ms_per_step": ms_, "nine_tap_equivalent_tflops": ach * 2.25}
-                continue
-            if name in ("linear_gemm", "flash_attention"):
-                roof[name] = {"bound": "mfma", "achieved": w_ / (ms_ * 1e-3) / 1e12, "peak": 2500.0, "unit": "TFLOP/s",
-                              "frac": w_ / (ms_ * 1e-3) / 1e12 / 2500.0, "launches": n_, "time_ms_per_step": ms_}
-                if name == "linear_gemm":
-                    roof[name]["kernel"] = "lin4_kernel<GEGLU, WM> (big-M projections) + igemm_kernel / sgemm_kernel (the rest)"
-                # HBM bytes per launch and MFMA-busy share per kernel of the class, from the same committed PMC passes as `traffic`
-                per_kernel = pmc.get("linear" if name == "linear_gemm" else "flash_attention", {})
-                if per_kernel and a.config != 5:          # (the passes are of the default config: not the RARM decode's kernels)
-                    roof[name]["traffic"] = {k_: {"hbm_bytes_per_launch": v_.get("hbm_bytes_per_launch"), "mfma_busy_frac": v_.get("mfma_busy_frac")}
-                                             for k_, v_ in per_kernel.items()}
-                    roof[name]["traffic_note"] = f"per kernel, profiles/{traffic_src}"
-            else:
-                roof[name] = {"bound": "hbm", "achieved": w_ / (ms_ * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                              "frac": w_ / (ms_ * 1e-3) / 1e9 / 8000.0, "launches": n_, "time_ms_per_step": ms_,
-                              "algorithmic_bytes_per_launch": w_ / n_}
-        if a.config != 5:
-            # end to end: ALGORITHMIC FLOPs per image (g S F_unet(k) + F_dec + F_vq) x images/s against the dense bf16 peak
-            g_ = 2 if (a.config != 4 and a.scale > 1) else 1
-            flop_img = g_ * a.ddim_steps * (208.56e9 + (k - 4) * 0.034e9) + 670.58e9 + 0.20e9
-            roof["end_to_end_tflops"] = flop_img * images / dt / 1e12
-            roof["end_to_end_frac"] = roof["end_to_end_tflops"] / 2500.0
-            roof["algorithmic_tflop_per_image"] = flop_img / 1e12
-            # SpatialTransformer block (attention.py:122-196) as one class: its GEMMs (incl. the fused cross-attention and, not separable
-            # by the event kinds, the ResBlocks' 1x1 skip_connection GEMMs), self-attention and LayerNorms; its entry GroupNorm sits in `groupnorm`
-            st = [classes.get(n_) for n_ in ("linear_gemm", "flash_attention", "layernorm")]
-            if all(c_ is not None and c_[0] > 0 for c_ in st):
-                st_ms = sum(c_[1] for c_ in st)
-                st_fl = st[0][2] + st[1][2]
-                roof["spatial_transformer_block"] = {"bound": "mfma", "achieved": st_fl / (st_ms * 1e-3) / 1e12, "peak": 2500.0, "unit": "TFLOP/s",
-                                                     "frac": st_fl / (st_ms * 1e-3) / 1e12 / 2500.0, "time_ms_per_step": st_ms,
-                                                     "classes": ["linear_gemm", "flash_attention", "layernorm"]}
-        if a.config == 5 and "linear_gemm" in roof:
-            # RARM: a token step is ~110 dependent launches: the decode GEMMs (M = batch rows against 768..6144-row weight matrices: weight streaming;
-            # bound HBM: N K 2 bytes per launch) and the K/V-cache attention (bound HBM: the cache rows 0..pos of every sequence).  The top-level object
-            # describes whichever takes more of the step (at 64 sequences the GEMMs, latency-bound; at 512 the attention, bandwidth-bound); the
-            # other sits beside it.  Measured on the extra UNTIMED step (one event pair per launch for ~28 k launches would otherwise sit in the timed region).
-            n_, ms_, w_ = classes["linear_gemm"]
-            wbytes = w_ / B                                  # 2 M N K FLOP / M rows = 2 N K bytes of bf16 weights
-            step_s = dt / a.steps
-            conv_roof = {k_: roof[k_] for k_ in ("kernel", "bound", "achieved", "peak", "unit", "frac", "launches", "avg_launch_ms", "conv_time_frac_of_step")}
-            lin = {"kernel": "sgemm_kernel<MA,NB,U> (decode-step linear layers: M = batch rows, weights streamed once per launch)",
-                   "bound": "hbm", "achieved": wbytes / (ms_ * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
-                   "frac": wbytes / (ms_ * 1e-3) / 1e9 / 8000.0, "traffic": None, "launches": n_, "avg_launch_ms": ms_ / max(n_, 1),
-                   "algorithmic_bytes_per_launch": wbytes / max(n_, 1), "time_frac_of_step": ms_ * 1e-3 / step_s,
-                   "note": "weight bytes only: at big batches these launches are bound by latency and MFMA work per launch, not by the weight stream"}
-            att = None
-            if classes.get("flash_attention", (0, 0, 0))[0] > 0:
-                na_, msa_, wa_ = classes["flash_attention"]
-                att = {"kernel": "rarm_decode_attention_kernel (one query row per sequence against its K/V cache rows 0..pos, 18 layers x 256 steps)",
-                       "bound": "hbm", "achieved": wa_ / (msa_ * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": wa_ / (msa_ * 1e-3) / 1e9 / 8000.0,
-                       "traffic": None, "launches": na_, "avg_launch_ms": msa_ / max(na_, 1), "algorithmic_bytes_per_launch": wa_ / max(na_, 1),
-                       "time_frac_of_step": msa_ * 1e-3 / step_s}
-            # The dominant KERNEL (contract: "the dominant kernel"): the linear class is several kernels (sgemm tile instantiations, the tiled GEGLU
-            # GEMM) over five shapes per layer; its largest launch group (one shape) is compared with the attention kernel.  A GEMM of M rows
-            # against an [N, K] weight has ~M FLOP per weight byte: weight-stream (HBM) bound below the ridge (2500 / 8 = 312 rows), MFMA above.
-            big = None
-            lin_shapes = {k_: v_ for k_, v_ in lin_shapes.items() if k_[0] > 0 and k_[1] > 0 and k_[2] > 0}
-            if lin_shapes:
-                (m_, n2_, k_), (cnt_, gms_, gfl_) = max(lin_shapes.items(), key=lambda kv: kv[1][1])
-                hbm_ = m_ < 312
-                ach_ = (cnt_ * 2.0 * n2_ * k_ / (gms_ * 1e-3) / 1e9) if hbm_ else gfl_ / (gms_ * 1e-3) / 1e12
-                big = {"kernel": f"sgemm_kernel / lin4_kernel, decode GEMM [{m_} x {k_}] x [{n2_} x {k_}]^T (largest launch group of the linear class)",
-                       "bound": "hbm" if hbm_ else "mfma", "achieved": ach_, "peak": 8000.0 if hbm_ else 2500.0, "unit": "GB/s" if hbm_ else "TFLOP/s",
-                       "frac": ach_ / (8000.0 if hbm_ else 2500.0), "traffic": None, "launches": cnt_, "avg_launch_ms": gms_ / max(cnt_, 1),
-                       "time_frac_of_step": gms_ * 1e-3 / step_s}
-                lin["largest_shape"] = big
-            for k_ in list(roof):
-                roof.pop(k_)
-            lin_top = big["time_frac_of_step"] if big else lin["time_frac_of_step"]
-            if att and att["time_frac_of_step"] > lin_top:
-                roof.update(att); roof["decode_linear"] = lin
-            else:
-                roof.update(big or lin); roof["decode_linear"] = lin
-                if att:
-                    roof["kv_cache_attention"] = att
-            roof["vqgan_conv"] = conv_roof
+        roof = None
+        if a.full:
+            achieved = fl_conv / (ms_conv * 1e-3) / 1e12 if ms_conv > 0 else 0.0
+            roof = {"kernel": "conv3x3_halo4_kernel<3> + igemm_kernel<..,conv> (3x3 conv, bf16 MFMA, fp32 accumulate)", "bound": "mfma",
+                    "achieved": achieved, "peak": 2500.0, "unit": "TFLOP/s", "frac": achieved / 2500.0, "traffic": traffic,
+                    "traffic_note": f"bytes per launch of the dominant conv kernel from the committed rocprofv3 PMC passes (profiles/{traffic_src}), not collected in this run",
+                    "launches": n_conv, "avg_launch_ms": ms_conv / max(n_conv, 1),
+                    "algorithmic_tflop_per_launch": fl_conv / max(n_conv, 1) / 1e12, "conv_time_frac_of_step": ms_conv * 1e-3 / (dt / a.steps)}      # events cover the LAST timed step only
+            for name, (n_, ms_, w_) in classes.items():
+                if n_ == 0:
+                    continue
+                if name == "upsample_conv_by_phase":
+                    # Upsample's nearest-2x + conv3x3 as four 2x2-tap convs at source resolution (igemm_kernel<.., 3>): EXECUTED FLOPs = 4/9 of the
+                    # nine-tap count the reference's F.interpolate + conv2d performs
+                    ach = w_ / (ms_ * 1e-3) / 1e12
+                    roof[name] = {"kernel": "igemm_kernel<BM, BN, W, 3> (pre-summed phase weights)", "bound": "mfma", "achieved": ach, "peak": 2500.0, "unit": "TFLOP/s",
+                                  "frac": ach / 2500.0, "launches": n_, "time_ms_per_step": ms_, "nine_tap_equivalent_tflops": ach * 2.25}
+                    continue
+                if name in ("linear_gemm", "flash_attention"):
+                    roof[name] = {"bound": "mfma", "achieved": w_ / (ms_ * 1e-3) / 1e12, "peak": 2500.0, "unit": "TFLOP/s",
+                                  "frac": w_ / (ms_ * 1e-3) / 1e12 / 2500.0, "launches": n_, "time_ms_per_step": ms_}
+                    if name == "linear_gemm":
+                        roof[name]["kernel"] = "lin4_kernel<GEGLU, WM> (big-M projections) + igemm_kernel / sgemm_kernel (the rest)"
+                    # HBM bytes per launch and MFMA-busy share per kernel of the class, from the same committed PMC passes as `traffic`
+                    per_kernel = pmc.get("linear" if name == "linear_gemm" else "flash_attention", {})
+                    if per_kernel and a.config != 5:          # (the passes are of the default config: not the RARM decode's kernels)
+                        roof[name]["traffic"] = {k_: {"hbm_bytes_per_launch": v_.get("hbm_bytes_per_launch"), "mfma_busy_frac": v_.get("mfma_busy_frac")}
+                                                 for k_, v_ in per_kernel.items()}
+                        roof[name]["traffic_note"] = f"per kernel, profiles/{traffic_src}"
+                else:
+                    roof[name] = {"bound": "hbm", "achieved": w_ / (ms_ * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                                  "frac": w_ / (ms_ * 1e-3) / 1e9 / 8000.0, "launches": n_, "time_ms_per_step": ms_,
+                                  "algorithmic_bytes_per_launch": w_ / n_}
+            if a.config != 5:
+                # end to end: ALGORITHMIC FLOPs per image (g S F_unet(k) + F_dec + F_vq) x images/s against the dense bf16 peak
+                g_ = 2 if (a.config != 4 and a.scale > 1) else 1
+                flop_img = g_ * a.ddim_steps * (208.56e9 + (k - 4) * 0.034e9) + 670.58e9 + 0.20e9
+                roof["end_to_end_tflops"] = flop_img * images / dt / 1e12
+                roof["end_to_end_frac"] = roof["end_to_end_tflops"] / 2500.0
+                roof["algorithmic_tflop_per_image"] = flop_img / 1e12
+                # SpatialTransformer block (attention.py:122-196) as one class: its GEMMs (incl. the fused cross-attention and, not separable
+                # by the event kinds, the ResBlocks' 1x1 skip_connection GEMMs), self-attention and LayerNorms; its entry GroupNorm sits in `groupnorm`
+                st = [classes.get(n_) for n_ in ("linear_gemm", "flash_attention", "layernorm")]
+                if all(c_ is not None and c_[0] > 0 for c_ in st):
+                    st_ms = sum(c_[1] for c_ in st)
+                    st_fl = st[0][2] + st[1][2]
+                    roof["spatial_transformer_block"] = {"bound": "mfma", "achieved": st_fl / (st_ms * 1e-3) / 1e12, "peak": 2500.0, "unit": "TFLOP/s",
+                                                         "frac": st_fl / (st_ms * 1e-3) / 1e12 / 2500.0, "time_ms_per_step": st_ms,
+                                                         "classes": ["linear_gemm", "flash_attention", "layernorm"]}
+            if a.config == 5 and "linear_gemm" in roof:
+                # RARM: a token step is ~110 dependent launches: the decode GEMMs (M = batch rows against 768..6144-row weight matrices: weight streaming;
+                # bound HBM: N K 2 bytes per launch) and the K/V-cache attention (bound HBM: the cache rows 0..pos of every sequence).  The top-level object
+                # describes whichever takes more of the step (at 64 sequences the GEMMs, latency-bound; at 512 the attention, bandwidth-bound); the
+                # other sits beside it.  Measured on the extra UNTIMED step (one event pair per launch for ~28 k launches would otherwise sit in the timed region).
+                n_, ms_, w_ = classes["linear_gemm"]
+                wbytes = w_ / B                                  # 2 M N K FLOP / M rows = 2 N K bytes of bf16 weights
+                step_s = dt / a.steps
+                conv_roof = {k_: roof[k_] for k_ in ("kernel", "bound", "achieved", "peak", "unit", "frac", "launches", "avg_launch_ms", "conv_time_frac_of_step")}
+                lin = {"kernel": "sgemm_kernel<MA,NB,U> (decode-step linear layers: M = batch rows, weights streamed once per launch)",
+                       "bound": "hbm", "achieved": wbytes / (ms_ * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s",
+                       "frac": wbytes / (ms_ * 1e-3) / 1e9 / 8000.0, "traffic": None, "launches": n_, "avg_launch_ms": ms_ / max(n_, 1),
+                       "algorithmic_bytes_per_launch": wbytes / max(n_, 1), "time_frac_of_step": ms_ * 1e-3 / step_s,
+                       "note": "weight bytes only: at big batches these launches are bound by latency and MFMA work per launch, not by the weight stream"}
+                att = None
+                if classes.get("flash_attention", (0, 0, 0))[0] > 0:
+                    na_, msa_, wa_ = classes["flash_attention"]
+                    att = {"kernel": "rarm_decode_attention_kernel (one query row per sequence against its K/V cache rows 0..pos, 18 layers x 256 steps)",
+                           "bound": "hbm", "achieved": wa_ / (msa_ * 1e-3) / 1e9, "peak": 8000.0, "unit": "GB/s", "frac": wa_ / (msa_ * 1e-3) / 1e9 / 8000.0,
+                           "traffic": None, "launches": na_, "avg_launch_ms": msa_ / max(na_, 1), "algorithmic_bytes_per_launch": wa_ / max(na_, 1),
+                           "time_frac_of_step": msa_ * 1e-3 / step_s}
+                # The dominant KERNEL (contract: "the dominant kernel"): the linear class is several kernels (sgemm tile instantiations, the tiled GEGLU
+                # GEMM) over five shapes per layer; its largest launch group (one shape) is compared with the attention kernel.  A GEMM of M rows
+                # against an [N, K] weight has ~M FLOP per weight byte: weight-stream (HBM) bound below the ridge (2500 / 8 = 312 rows), MFMA above.
+                big = None
+                lin_shapes = {k_: v_ for k_, v_ in lin_shapes.items() if k_[0] > 0 and k_[1] > 0 and k_[2] > 0}
+                if lin_shapes:
+                    (m_, n2_, k_), (cnt_, gms_, gfl_) = max(lin_shapes.items(), key=lambda kv: kv[1][1])
+                    hbm_ = m_ < 312
+                    ach_ = (cnt_ * 2.0 * n2_ * k_ / (gms_ * 1e-3) / 1e9) if hbm_ else gfl_ / (gms_ * 1e-3) / 1e12
+                    big = {"kernel": f"sgemm_kernel / lin4_kernel, decode GEMM [{m_} x {k_}] x [{n2_} x {k_}]^T (largest launch group of the linear class)",
+                           "bound": "hbm" if hbm_ else "mfma", "achieved": ach_, "peak": 8000.0 if hbm_ else 2500.0, "unit": "GB/s" if hbm_ else "TFLOP/s",
+                           "frac": ach_ / (8000.0 if hbm_ else 2500.0), "traffic": None, "launches": cnt_, "avg_launch_ms": gms_ / max(cnt_, 1),
+                           "time_frac_of_step": gms_ * 1e-3 / step_s}
+                    lin["largest_shape"] = big
+                for k_ in list(roof):
+                    roof.pop(k_)
+                lin_top = big["time_frac_of_step"] if big else lin["time_frac_of_step"]
+                if att and att["time_frac_of_step"] > lin_top:
+                    roof.update(att); roof["decode_linear"] = lin
+                else:
+                    roof.update(big or lin); roof["decode_linear"] = lin
+                    if att:
+                        roof["kv_cache_attention"] = att
+                roof["vqgan_conv"] = conv_roof
         out = {
             "metric": "images/sec at 256x256, 50 DDIM steps, k=4 OpenImages retrieval",
             "value": images / dt, "unit": "images/s", "n_gpus": world, "steps": a.steps, "warmup": a.warmup,
@@ -525,8 +574,9 @@ def main():
                        "parallelism": f"dp{world} (batch-sharded, weights + DB replicated, all-gather of images only)",
                        "collective": collective, "gathered": None if world == 1 else f"{a.gather} images, {img.element_size() * img[0].numel() * B} bytes per rank",
                        "deterministic_mode": bool(ctx.deterministic)},
-            "roofline": roof,
         }
+        if roof is not None:
+            out["roofline"] = roof
         if rank_ms is not None:
             out["config"]["rank_ms_per_step"] = {"min": min(rank_ms), "max": max(rank_ms), "per_rank": rank_ms}
         if calib is not None:
@@ -548,7 +598,7 @@ def main():
             out["calibration"] = calib
         if extras:
             out["extras"] = extras
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline_full(a.scale) if a.full_cpu_baseline else cpu_baseline(a.scale)
             if not a.full_cpu_baseline:
                 # the bounded sample above is an extrapolation; the full SURVEY-8d protocol (--full-cpu-baseline, ~5 min) as last committed

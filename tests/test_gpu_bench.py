@@ -5,7 +5,7 @@ refuses two ranks on one device, so the collective here is torch.distributed's; 
 the library's RCCL communicator, `config.collective` says which one ran).  In deterministic (batch-invariant) mode the gathered
 images of a global batch of 8 must be BIT-IDENTICAL for 1 x 8, 2 x 4, 4 x 2 and 8 x 1 rows per rank.
 
-SURVEY.md 8e; /root/reference/scripts/rdm_sample.py:181-185 is single-GPU: everything here is new functionality."""
+SURVEY.md 8e; the reference's scripts/rdm_sample.py:181-185 is single-GPU: everything here is new functionality."""
 import json
 import os
 import subprocess
@@ -19,14 +19,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GLOBAL_BATCH = 8
 
 
-def _run_bench(n, tmp_path, tag, extra=(), port=29700):
+def _run_bench(n, tmp_path, tag, extra=(), port=29700, full=True, steps=1):
     dump = tmp_path / f"img_{tag}.npy"
     env = dict(os.environ, RDM_DIST_BACKEND="gloo", RDM_DIST_DEVICE="0", RDM_DETERMINISTIC="1", HSA_ENABLE_IPC_MODE_LEGACY="0",
                MASTER_PORT=str(port))
     for k in ("RANK", "WORLD_SIZE", "LOCAL_RANK"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", str(n), "--batch", str(GLOBAL_BATCH // n), "--db-rows", "200000",
-           "--ddim-steps", "2", "--steps", "1", "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--dump-images", str(dump)] + list(extra)
+           "--ddim-steps", "2", "--steps", str(steps), "--warmup", "1", "--no-cpu-baseline", "--no-extras", "--dump-images", str(dump)] + list(extra)
+    if full:
+        cmd.append("--full")
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=1500)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-4000:]
     lines = [ln for ln in r.stdout.splitlines() if ln.startswith("{") and '"metric"' in ln]
@@ -82,3 +84,20 @@ def test_bench_gpus_2_4_and_8_on_one_gpu_match_the_single_rank_run(tmp_path):
     v = np.clip(img1, np.float32(-1), np.float32(1))
     ref = (np.float32(255.0) * ((v + np.float32(1.0)) / np.float32(2.0))).astype(np.uint8).transpose(0, 2, 3, 1)
     assert np.array_equal(img_u, ref), "2 ranks, uint8 gather: bytes differ from the conversion of the 1-rank fp32 images"
+
+
+def test_bench_plain_run_times_its_steps_and_dumps_the_last_step(tmp_path):
+    """A plain run (no --full) prints the headline fields only, times exactly --steps steps, and --dump-outputs writes the last timed
+    step's images in float32: equal to the --dump-images array of the same run and, inputs being seeded, of a second run."""
+    out = tmp_path / "out"
+    line, img = _run_bench(1, tmp_path, "plain", extra=("--dump-outputs", str(out)), full=False, steps=2)
+    assert line["steps"] == 2 and line["warmup"] == 1 and line["n_gpus"] == 1 and line["unit"] == "images/s" and line["higher_is_better"] is True
+    assert line["dtype"] == "bf16" and line["ms_per_step"] > 0
+    assert abs(line["value"] - GLOBAL_BATCH / (line["ms_per_step"] * 1e-3)) < 1e-6 * line["value"]
+    assert not {"roofline", "calibration", "extras", "cpu_baseline", "value_at_reference_box"} & set(line), sorted(line)
+    assert sorted(os.listdir(out)) == ["images.npy"]
+    dumped = np.load(out / "images.npy")
+    assert dumped.dtype == np.float32 and dumped.shape == (GLOBAL_BATCH, 3, 256, 256) and np.array_equal(dumped, img)
+    out2 = tmp_path / "out2"
+    _run_bench(1, tmp_path, "plain2", extra=("--dump-outputs", str(out2)), full=False, steps=2)
+    assert np.array_equal(np.load(out2 / "images.npy"), dumped), "same arguments, deterministic mode: the dumped images differ between runs"

@@ -355,7 +355,7 @@ class _MockProductCtx:
     comm_init = comm_all_gather = comm_destroy = comm_unique_id
 
 
-def _worker_lib_comm_never_returns(rank, world, port, q):
+def _worker_lib_comm_never_returns(rank, world, port, q, go):
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank),
                       RDM_LIB_COMM_TIMEOUT="1")
     import time
@@ -377,6 +377,7 @@ def _worker_lib_comm_never_returns(rank, world, port, q):
     parallel.shutdown()
     q.put((rank, got, getattr(ctx, "lib_comm_agreed", None), getattr(ctx, "lib_comm", "unset"), len(parallel._abandoned_comm_contexts), t_attach,
            time.time() - t0, out[:, 0].tolist()))
+    go.wait(120)                                     # exit when the parent says so (see the test)
 
 
 def test_library_comm_rendezvous_that_never_returns_world2_gloo():
@@ -385,10 +386,14 @@ def test_library_comm_rendezvous_that_never_returns_world2_gloo():
     context is never used for communicator work, the gather still works through torch, shutdown() returns and the processes exit."""
     ctx = mp.get_context("spawn")
     q = ctx.Queue()
-    procs = [ctx.Process(target=_worker_lib_comm_never_returns, args=(r, 2, 29633, q)) for r in range(2)]
+    go = [ctx.Event() for _ in range(2)]
+    procs = [ctx.Process(target=_worker_lib_comm_never_returns, args=(r, 2, 29633, q, go[r])) for r in range(2)]
     for p in procs: p.start()
     got = {r[0]: r[1:] for r in (q.get(timeout=120), q.get(timeout=120))}
-    for p in procs:
+    # one rank after the other: rank 0's helper is still inside the mock's gloo probe gather, and rank 1 closing its gloo connections
+    # while rank 0's interpreter is being torn down aborts rank 0 inside gloo (a race of the two mock processes, not of the hand-shake)
+    for r, p in enumerate(procs):
+        go[r].set()
         p.join(timeout=60)
         assert p.exitcode == 0
     for rank in (0, 1):
@@ -811,3 +816,29 @@ def test_bench_box_sampler_without_sensors_and_calibration_reference():
     assert set(out) >= {"sclk_mhz_mean", "sclk_mhz_min", "power_w_mean", "samples", "sampler"}
     ref = b.load_calibration_reference()
     assert ref and ref["sclk_mhz_mean"] > 1000 and 0 < ref["clock_bound_share"] <= 1 and ref["mfma_probe_tflops"] > 1000 and ref["hbm_stream_gbps"] > 1000
+
+
+def test_bench_dump_outputs_writes_float32_and_samples_rows_over_the_limit(tmp_path):
+    """bench.py --dump-outputs: arrays under the limit are written whole in float32 (float64 kept); over it, a fixed seeded sample of
+    rows (the same in every run) is written, with the row indices beside it, and the files stay within the limit."""
+    import importlib.util
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    spec = importlib.util.spec_from_file_location("bench_mod", os.path.join(root, "bench.py"))
+    b = importlib.util.module_from_spec(spec); spec.loader.exec_module(b)
+    img = torch.arange(64 * 3 * 8 * 8, dtype=torch.bfloat16).reshape(64, 3, 8, 8)
+    sc = torch.linspace(0, 1, 10, dtype=torch.float64)
+    b.dump_outputs(str(tmp_path / "whole"), {"images": img, "scores": sc})
+    assert sorted(os.listdir(tmp_path / "whole")) == ["images.npy", "scores.npy"]
+    w = np.load(tmp_path / "whole" / "images.npy")
+    assert w.dtype == np.float32 and np.array_equal(w, img.float().numpy())
+    assert np.load(tmp_path / "whole" / "scores.npy").dtype == np.float64
+    u8 = torch.randint(0, 256, (300, 16, 16, 3), dtype=torch.uint8)
+    limit = 40 * (16 * 16 * 3 * 4 + 8) + 256
+    for d in ("s1", "s2"):
+        b.dump_outputs(str(tmp_path / d), {"images": u8}, limit=limit)
+    rows = np.load(tmp_path / "s1" / "images_rows.npy")
+    got = np.load(tmp_path / "s1" / "images.npy")
+    assert rows.dtype == np.float64 and len(rows) == 40 and np.all(np.diff(rows) > 0)
+    assert got.dtype == np.float32 and np.array_equal(got, u8.numpy()[rows.astype(np.int64)].astype(np.float32))
+    assert np.array_equal(np.load(tmp_path / "s2" / "images_rows.npy"), rows) and np.array_equal(np.load(tmp_path / "s2" / "images.npy"), got)
+    assert sum(os.path.getsize(tmp_path / "s1" / f) for f in os.listdir(tmp_path / "s1")) <= limit

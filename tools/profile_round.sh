@@ -8,7 +8,7 @@ REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
-python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench.json 2> $OUT/bench.err
+python3 $REPO/bench.py --steps 2 --warmup 1 --no-cpu-baseline --full > $OUT/bench.json 2> $OUT/bench.err
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/stats -- python3 $REPO/bench.py --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/stats.log 2>&1
 python3 $REPO/tools/pmc_sum.py stats $OUT/stats.csv $OUT/stats
 SHORT="--steps 1 --warmup 0 --ddim-steps 4 --no-cpu-baseline --no-extras"
@@ -36,7 +36,7 @@ python3 $REPO/tools/pmc_sum.py json $OUT/pmc.json $OUT/sq.csv $OUT/fetch.csv $OU
 rm -rf $OUT/stats $OUT/sq1 $OUT/sq2 $OUT/fetch $OUT/write
 # RARM decode (config #5): bench line + kernel stats at 64 / 256 / 512 / 1024 / 2048 sequences, one SQ pass at the default batch (2048) on a short run (32 tokens)
 for b in ${RARM_BATCHES:-64 256 512 1024 2048}; do
-  python3 $REPO/bench.py --config 5 --batch $b --db-rows 2000000 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/rarm_bench_b$b.json 2> $OUT/rarm_bench_b$b.err
+  python3 $REPO/bench.py --config 5 --batch $b --db-rows 2000000 --steps 2 --warmup 1 --no-cpu-baseline --full > $OUT/rarm_bench_b$b.json 2> $OUT/rarm_bench_b$b.err
   rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/rstats_b$b -- python3 $REPO/bench.py --config 5 --batch $b --db-rows 2000000 --steps 1 --warmup 1 --no-cpu-baseline --no-extras > $OUT/rstats_b$b.log 2>&1
   python3 $REPO/tools/pmc_sum.py stats $OUT/rarm_b${b}_kernel_stats.csv $OUT/rstats_b$b
   rm -rf $OUT/rstats_b$b
@@ -45,8 +45,8 @@ rocprofv3 --kernel-trace --output-format csv --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_B
 python3 $REPO/tools/pmc_sum.py counters $OUT/rarm_b2048_sq.csv $OUT/rsq
 rm -rf $OUT/rsq
 # the other single-GPU configurations on the same box
-python3 $REPO/bench.py --config 2 --steps 2 --warmup 1 --no-cpu-baseline > $OUT/bench_config2.json 2> $OUT/bench_config2.err
-python3 $REPO/bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline > $OUT/bench_config4.json 2> $OUT/bench_config4.err
+python3 $REPO/bench.py --config 2 --steps 2 --warmup 1 --no-cpu-baseline --full > $OUT/bench_config2.json 2> $OUT/bench_config2.err
+python3 $REPO/bench.py --config 4 --steps 1 --warmup 1 --no-cpu-baseline --full > $OUT/bench_config4.json 2> $OUT/bench_config4.err
 # per-op table of one guided UNet forward (tools/op_trace.py)
 python3 $REPO/tools/op_trace.py --out $OUT/op_trace.csv > $OUT/op_trace.log 2>&1
 ls -la $OUT
