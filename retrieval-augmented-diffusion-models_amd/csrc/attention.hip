@@ -115,7 +115,7 @@ __global__ __launch_bounds__(256, 2) void flash_d32_lds_kernel(FlashParams p) {
     int xb = blockIdx.x, h = blockIdx.y, b = blockIdx.z;
     {
         const int gx = gridDim.x, G = gridDim.y * gridDim.z;
-        if ((G & 7) == 0 && p.xcd_remap) {
+        if ((G & 7) == 0) {
             const int lin = blockIdx.x + gx * (blockIdx.y + gridDim.y * blockIdx.z);
             const int xcd = lin & 7, slot = lin >> 3;
             const int grp = (slot / gx) * 8 + xcd;
@@ -240,10 +240,8 @@ hipError_t launch_flash_d32(const FlashParams& p, int heads, int batch, hipStrea
     if (!p.vt && (!p.v || p.n % 64 != 0)) return hipErrorInvalidValue;          // token-major V: LDS-shared kernel only
     if (p.n % 64 == 0) {
         dim3 grid((p.n / 32 + 3) / 4, heads, batch);
-        static const int old = getenv("RDM_FLASH_OLD") ? atoi(getenv("RDM_FLASH_OLD")) : 0;
-        FlashParams q = p; q.xcd_remap = old ? 0 : 1;          // RDM_FLASH_OLD=1: plain blockIdx mapping (A/B)
-        if (q.v && !q.vt) flash_d32_lds_kernel<true><<<grid, 256, 0, st>>>(q);
-        else flash_d32_lds_kernel<false><<<grid, 256, 0, st>>>(q);
+        if (p.v && !p.vt) flash_d32_lds_kernel<true><<<grid, 256, 0, st>>>(p);
+        else flash_d32_lds_kernel<false><<<grid, 256, 0, st>>>(p);
         return hipGetLastError();
     }
     int nw = p.n / 32; if (nw > 4) nw = 4;

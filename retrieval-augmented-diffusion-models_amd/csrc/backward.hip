@@ -478,8 +478,7 @@ __global__ void gn_bwd_apply2_kernel(GnBwd2 p) {
 }
 static int gn_bwd_nchunk(int B, int HW) { int n = 2048 / (B > 0 ? B : 1); if (n > HW / 32) n = HW / 32; if (n < 1) n = 1; if (n > 64) n = 64; return n; }
 static bool gn_bwd_vec_ok(int C, int groups) {
-    static const bool off = getenv("RDM_NO_GN_BWD_VEC") != nullptr;
-    return !off && C % 8 == 0 && C <= 2048 && groups <= 64 && C % groups == 0;
+    return C % 8 == 0 && C <= 2048 && groups <= 64 && C % groups == 0;
 }
 size_t groupnorm_bwd_scratch_bytes(int B, int HW, int C, int groups) {
     const size_t nch = gn_bwd_nchunk(B, HW);
@@ -646,8 +645,7 @@ hipError_t launch_layernorm_bwd(const bf16_t* x, const bf16_t* dy, const float* 
     const int nb = (M + rows_per_block - 1) / rows_per_block;
     if (nb_out) *nb_out = nb;
     float* pg = scratch; float* pb = scratch + (size_t)nb * C;
-    static const bool novec = getenv("RDM_NO_LN_BWD_VEC") != nullptr;
-    if (!novec && C % 8 == 0 && C <= 1024) {
+    if (C % 8 == 0 && C <= 1024) {
         if (C <= 512) ln_bwd_vec_kernel<1><<<nb, 256, (size_t)8 * C * sizeof(float), st>>>(x, dy, gamma, M, C, eps, dx, pg, pb, rows_per_block, residual);
         else ln_bwd_vec_kernel<2><<<nb, 256, (size_t)8 * C * sizeof(float), st>>>(x, dy, gamma, M, C, eps, dx, pg, pb, rows_per_block, residual);
         ln_bwd_affine4_kernel<<<(C + 15) / 16, 256, 0, st>>>(pg, pb, nb, C, dgamma, dbeta);

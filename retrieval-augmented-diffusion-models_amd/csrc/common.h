@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <stdlib.h>
 
 typedef uint16_t bf16_t;   // raw bfloat16 bits
 typedef __attribute__((ext_vector_type(8))) short bf16x8;
@@ -74,6 +75,11 @@ constexpr int RDM_EYE_OFFSET = 4096, RDM_EYE_N = 256;
 constexpr int RDM_MAX_DEVICES = 32;
 inline int rdm_cur_device() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 && d < RDM_MAX_DEVICES) ? d : 0; }
 
+// The library's only environment switches are read through this, as rdm_env_int(getenv("RDM_..."), def) (unset: def):
+// RDM_DETERMINISTIC (= rdm_set_deterministic), and the test / tool hooks RDM_MGEMM_ANY, RDM_MGEMM_FROM, RDM_VQ_RANGE and
+// RDM_OP_FRAG_CACHE (model.hip).  tests/test_library_cpu.py keeps the list from growing.
+inline int rdm_env_int(const char* value, int def) { return value ? atoi(value) : def; }
+
 struct IgemmParams {
     // A operand: logical [M, K].  Two channel-concatenated sources (A1 may be null, C1 = 0).
     const bf16_t* A0; const bf16_t* A1;
@@ -109,5 +115,5 @@ struct IgemmParams {
     // lin4 only: LayerNorm folded into the GEMM.  A0 holds the RAW rows, Wfrag the gamma-scaled fragment copy, ln_sb[n] = (s[n], b'[n]) per
     // stored weight row (launch_lin_ln_sb); the kernel takes the row statistics itself: out = rstd (A Wg^T - mean s) + b'
     const float* ln_sb; float ln_inv_c, ln_eps;      // ln_inv_c = 1 / (logical row width): zero padding beyond it adds nothing to the sums
-    int dbg;                    // debug ablation bits (env RDM_IGEMM_DBG): 1 no MFMA, 2 no in-loop staging, 4 no stores
+    int dbg;                    // always 0: read only by conv3x3_halo4_kernel's phase-clock code, kept for its code generation (conv_halo4.hip)
 };

@@ -21,13 +21,13 @@
 //     every wait counted (vmcnt retires in order); one s_barrier per 64-channel slice (9 taps, 432 MFMAs per wave).
 // Same persistent XCD-aware tile walk, split-K planes and epilogue scheme (DPP pair swap -> wave-private LDS transpose -> 16-byte
 // row stores) as conv_halo.hip.
-#include <stdio.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
 #include "kernels.h"
 
+// Phase-clock counters of the kernel below.  IgemmParams::dbg is always 0 now (nothing sets it): the clock code stays because removing
+// it changes hipcc's schedule of the FN = 3 main loop (measured 265 -> 303 us per launch, - 4.8 % on the headline).
 __device__ unsigned long long g_halo4_prof[4];
 
 // fragment-ordered weight copy: dst[((nb * 9 + tap) * KQ + kq) * 512 + lane * 8 + e] = W[nb * 32 + (lane & 31)][tap][kq * 16 + (lane >> 5) * 8 + e]
@@ -81,7 +81,7 @@ constexpr int H4_HALO_MAX = 66560;                 // largest HBYTES admitted (W
 // strips' real pixels (zero only at the image border), rows of a tile are WI pixels apart in memory, and tile index -> (sample, row
 // group, strip).  Costs three VALU per halo piece (column = strip origin + halo column, its validity, the source column), so it is a
 // template variant: the UNet's kernels (W <= 64) are unchanged.
-template <int FN, int VAR, bool STRIP = false>      // VAR: dev-only ablations (RDM_H4_VAR): 1 = no halo-piece address work (wrong results)
+template <int FN, bool STRIP = false>
 __global__ __launch_bounds__(256, 1) void conv3x3_halo4_kernel(IgemmParams p) {
     constexpr int BM = 256, BK = 64, FM = 4, WN = FN * 32, BN = 2 * WN;
     extern __shared__ __attribute__((aligned(16))) char smem[];   // [halo0][halo1][dump: 1 KB per wave]
@@ -371,8 +371,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4_kernel(IgemmParams p) {
 #pragma unroll
         for (int m = 0; m < FM * FN; m++) {
             mfma(0, m);
-            if constexpr (VAR == 3) H4_GLOADB(fb[P ^ 1][m / FN][m % FN], voffj[0], Wf, 0);      // ablation: every weight request hits the same KiB (wrong results)
-            else H4_GLOADB(fb[P ^ 1][m / FN][m % FN], voffj[m % FN], sbn, (m / FN) * 1024);
+            H4_GLOADB(fb[P ^ 1][m / FN][m % FN], voffj[m % FN], sbn, (m / FN) * 1024);
             if (m == 3) {
 #pragma unroll
                 for (int i = 0; i < FM; i++) H4_LDSR(fa[1][i], va[i], 32);
@@ -385,7 +384,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4_kernel(IgemmParams p) {
             asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
             if (ks < 3) H4_LDSW(hdst[P][ks], hreg[P][ks]);
             const int q = q0 + ks - 1;
-            const bool live = (VAR != 1) && q < hnp;                       // uniform
+            const bool live = q < hnp;                       // uniform
             unsigned pe;                                                  // the piece's table entry (pieces past the wave's share: entry 20, unused)
             asm volatile("ds_read_b32 %0, %1" : "=v"(pe) : "v"(tbl + (unsigned)((q < 20 ? q : 20) * 256)));
             mfma(ks, 0); mfma(ks, 1); mfma(ks, 2); mfma(ks, 3);
@@ -427,7 +426,6 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4_kernel(IgemmParams p) {
             hd = (live & (((pe >> 28) & 1u) != 0)) ? hd : dump;
             H4_PIN1(hd);
             const char* hg = (const char*)(((unsigned long long)ghi << 32) | glo);
-            if constexpr (VAR == 2) hg = zl;                              // all the address work, no HBM request
             if constexpr (FN >= 3) mfma(ks, 10);
             H4_GLOADH(hreg[P][ks - 1], hg); hdst[P][ks - 1] = hd;
             if constexpr (FN >= 3) mfma(ks, 11);
@@ -606,14 +604,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_halo4_kernel(IgemmParams p) {
     }
 }
 
-template <int FN, int VAR, bool STRIP = false>
+template <int FN, bool STRIP = false>
 static hipError_t launch_halo4_cfg(const IgemmParams& p, hipStream_t st) {
     constexpr int smem = 2 * H4_HALO_MAX + 4096 + 4 * 21 * 256;       // halo x 2, dump, piece tables
     constexpr int BN = FN * 64;
     static int ncu_dev[RDM_MAX_DEVICES] = {0};
     const int dev = rdm_cur_device();
     if (!ncu_dev[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_halo4_kernel<FN, VAR, STRIP>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
+        hipError_t e = hipFuncSetAttribute((const void*)conv3x3_halo4_kernel<FN, STRIP>, hipFuncAttributeMaxDynamicSharedMemorySize, smem);
         if (e != hipSuccess) return e;
         hipDeviceGetAttribute(&ncu_dev[dev], hipDeviceAttributeMultiprocessorCount, dev);
     }
@@ -621,26 +619,12 @@ static hipError_t launch_halo4_cfg(const IgemmParams& p, hipStream_t st) {
     const long long ntiles = (long long)(p.M / 256) * (p.N / BN) * (p.ksplit > 1 ? p.ksplit : 1);
     long long g = (ncu + 7) & ~7;
     if (g > ntiles) g = ntiles;
-    static const int prof = getenv("RDM_HALO_PROF") ? atoi(getenv("RDM_HALO_PROF")) : 0;
-    if (prof) {
-        IgemmParams q = p; q.dbg |= 16;
-        unsigned long long z[4] = {0, 0, 0, 0}, r[4];
-        hipMemcpyToSymbol(HIP_SYMBOL(g_halo4_prof), z, sizeof(z));
-        conv3x3_halo4_kernel<FN, VAR, STRIP><<<dim3((unsigned)g), 256, smem, st>>>(q);
-        hipStreamSynchronize(st);
-        hipMemcpyFromSymbol(r, HIP_SYMBOL(g_halo4_prof), sizeof(r));
-        fprintf(stderr, "[halo4<%d> M=%d N=%d K=%d] blocks=%llu per-block cycles: main %.0f epilogue %.0f (tiles/block %.2f)\n", BN, p.M, p.N, p.K,
-                r[3], (double)r[0] / r[3], (double)r[1] / r[3], (double)ntiles / g);
-        return hipGetLastError();
-    }
-    conv3x3_halo4_kernel<FN, VAR, STRIP><<<dim3((unsigned)g), 256, smem, st>>>(p);
+    conv3x3_halo4_kernel<FN, STRIP><<<dim3((unsigned)g), 256, smem, st>>>(p);
     return hipGetLastError();
 }
 
 // images wider than 64 pixels as 64-column strips (conv3x3_halo4_kernel<.., STRIP>): the first-stage decoder's 128- / 256-pixel levels
 bool conv_halo4_strip_supported(const IgemmParams& p) {
-    static const int off = getenv("RDM_NO_HALO4_STRIP") ? atoi(getenv("RDM_NO_HALO4_STRIP")) : 0;
-    if (off || getenv("RDM_NO_HALO4") || getenv("RDM_NO_HALO")) return false;
     const int W = p.Wout, H = p.Hout;
     if (p.stride != 1 || W <= 64 || W % 64 || H % 4 || W > 4096 || H > 4096) return false;
     if (p.ups ? (p.Hout != 2 * p.Hin || p.Wout != 2 * p.Win) : (p.Hout != p.Hin || p.Wout != p.Win)) return false;
@@ -654,8 +638,7 @@ bool conv_halo4_strip_supported(const IgemmParams& p) {
 
 // the one-wave-per-SIMD kernel takes every conv the halo geometry admits once a fragment-ordered weight copy exists
 bool conv_halo4_supported(const IgemmParams& p) {
-    static const int off = getenv("RDM_NO_HALO4") ? atoi(getenv("RDM_NO_HALO4")) : 0;
-    if (off || !p.Wfrag) return false;
+    if (!p.Wfrag) return false;
     if (!conv_halo_supported(p)) return false;
     if (p.rowvec && p.rows_per_sample % 32 != 0) return false;
     if ((p.C0 + p.C1) % 64 != 0 || p.N % 32 != 0) return false;
@@ -669,16 +652,10 @@ bool conv_halo4_supported(const IgemmParams& p) {
 }
 
 hipError_t launch_conv_halo4(const IgemmParams& p, hipStream_t st) {
-    static const int var = getenv("RDM_H4_VAR") ? atoi(getenv("RDM_H4_VAR")) : 0;
     if (p.Wout > 64) {
         if (!p.Wfrag || !conv_halo4_strip_supported(p)) return hipErrorInvalidValue;
-        return launch_halo4_cfg<2, 0, true>(p, st);
+        return launch_halo4_cfg<2, true>(p, st);
     }
-    if (p.N % 192 == 0) {
-        if (var == 1) return launch_halo4_cfg<3, 1>(p, st);
-        if (var == 3) return launch_halo4_cfg<3, 3>(p, st);
-        if (var == 2) return launch_halo4_cfg<3, 2>(p, st);
-        return launch_halo4_cfg<3, 0>(p, st);
-    }
-    return launch_halo4_cfg<2, 0>(p, st);
+    if (p.N % 192 == 0) return launch_halo4_cfg<3>(p, st);
+    return launch_halo4_cfg<2>(p, st);
 }

@@ -16,8 +16,6 @@
 // Zero padding of the 3x3 halo (and M/N tails) is done by pointing the lane at a zero page.
 // The skip-concat of the UNet decoder (th.cat([h, hs.pop()]), openaimodel.py:365) is never
 // materialised: the loader switches source tensor per K-slice (dual-source A).
-#include <stdio.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -38,9 +36,6 @@ __device__ __forceinline__ void softmax_group16(float (&v)[16], int g) {
         v[r] = e / sum;
     }
 }
-
-// dev-only phase clock (env RDM_IGEMM_PROF=1): shader cycles spent by wave 0 of every block in [K loop, epilogue, wait at tile start]
-__device__ unsigned long long g_igemm_prof[5];
 
 // CONV: 0 linear, 1 conv3x3, 2 conv3x3 on a 2x nearest-upsampled input, 3 the same conv by OUTPUT PHASE: output pixel (2y + a, 2x + b) of
 // conv3x3(nearest2x(src)) reads only the 2 x 2 source window rows {y - 1 + a, y + a} x columns {x - 1 + b, x + b} -- the taps that land
@@ -267,10 +262,7 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
     int c_g = 0;                        // compute stream position
     int pending_stores = 0;             // stores issued after the most recent B request (previous tile's epilogue)
 
-    unsigned long long tprof[4] = {0, 0, 0, 0};
     while (true) {
-        unsigned long long tp0 = 0, tp1 = 0;
-        if (p.dbg & 16) tp0 = __builtin_readcyclecounter();
         const int em0 = (tile / nbn) * BM, en0 = (tile % nbn) * BN;
         // bias (+ time-embedding row) into registers now; consumed in the epilogue, latency hides under the K loop
         const bool full = (em0 + BM <= p.M) && (en0 + BN <= p.N);
@@ -306,20 +298,14 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
         for (int kt = 0; kt < nk; kt++, c_g++) {
             // needed now: A(c_g) [requested two slices ago] and B(c_g).  Younger than B(c_g): the A slice requested right
             // after it (if any) and, at a tile start, the previous epilogue's stores.
-            unsigned long long tw0 = 0;
-            if ((p.dbg & 16) && kt == 0) tw0 = __builtin_readcyclecounter();
             wait_vm((a_ahead ? AP : 0) + pending_stores);
             pending_stores = 0;
             __syncthreads();                       // slices landed for every wave; ring slots of slice c_g-1 are free
-            if ((p.dbg & 16) && kt == 0) tprof[2] += __builtin_readcyclecounter() - tw0;
-            if (!(p.dbg & 2)) {
-                if (b_live) issue_b();             // B(c_g+1)
-                a_ahead = (A_SLOTS == 3) && a_live;
-                if (a_live) issue_a();             // A(c_g+2), or A(c_g+1) with the 2-slot ring
-            } else a_ahead = false;
+            if (b_live) issue_b();                 // B(c_g+1)
+            a_ahead = (A_SLOTS == 3) && a_live;
+            if (a_live) issue_a();                 // A(c_g+2), or A(c_g+1) with the 2-slot ring
             const char* As = a_ring + (c_g % A_SLOTS) * A_BYTES;
             const char* Bs = b_ring + (c_g & 1) * B_BYTES;
-            if (p.dbg & 1) continue;
             // Hand-pipelined LDS->MFMA loop: the fragments of k-step kk+1 are requested (inline-asm ds_read_b128,
             // invisible to hipcc's waitcnt bookkeeping) before the MFMAs of k-step kk; a COUNTED lgkmcnt leaves
             // them in flight behind the matrix pipe.  All fragments of a lane share one swizzle term, so one
@@ -373,13 +359,12 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
         // are written with conflict-free ds_write_b32, read back as whole rows, and leave as 16-byte-per-lane stores
         // (4x fewer store instructions; the residual arrives as 16-byte loads of the same rows).  The staging area is
         // the ring slots of the K-slice just consumed (free until the next request), so it costs one barrier per tile.
-        if (p.dbg & 16) { tp1 = __builtin_readcyclecounter(); tprof[0] += tp1 - tp0; }
         constexpr int WNO = GEGLU ? WN / 2 : WN;                        // output columns per wave
         const int No = GEGLU ? p.N / 2 : p.N;
         // (a plain bf16 residual -- not the K-column form -- takes the direct epilogue, which adds it in fp32 BEFORE the one rounding: the LDS
         //  transpose below packs to bf16 first, and the rest of the library (conv_halo4 / lin4 read-outs, the split-K finisher, the
         //  residual-as-K-columns GEMMs) rounds once.  Reached by the generic-path convs of small batches / deterministic mode only.)
-        const bool lds_epi = ob && !of && !rf && !rb && (No % 8 == 0) && (p.ldo % 8 == 0) && !(p.dbg & 4);
+        const bool lds_epi = ob && !of && !rf && !rb && (No % 8 == 0) && (p.ldo % 8 == 0);
         // PLAIN = no activation, alpha 1, no per-row time-embedding lookup: every UNet projection except the GEGLU one.  The flag is
         // a compile-time parameter of the body: as run-time tests inside the unrolled element loops hipcc kept a compare + branch
         // (+ hazard nops) per ELEMENT, and the epilogue took twice as long as the halo kernel's for the same tile.
@@ -389,7 +374,6 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
             constexpr int ROWB = WNO * 2, CPR = WNO / 8, NIT = (32 * CPR) / 64;
             static_assert((32 * CPR) % 64 == 0 && 32 * ROWB * 4 <= B_BYTES, "epilogue staging geometry");
             __syncthreads();                                            // every wave is done reading slice c_g-1
-            if (p.dbg & 16) tprof[3] += __builtin_readcyclecounter() - tp1;
             char* stg = (wave < 4) ? (char*)b_ring + ((c_g - 1) & 1) * B_BYTES + wave * (32 * ROWB)
                                    : (char*)a_ring + ((c_g - 1) % A_SLOTS) * A_BYTES + (wave - 4) * (32 * ROWB);
             const int eno = (GEGLU ? en0 / 2 : en0) + wn * WNO;         // first output column of this wave
@@ -460,7 +444,6 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
                                                     __uint_as_float(uu[e] & 0xffff0000u) + __uint_as_float(rr[e] & 0xffff0000u));
                             u = make_uint4(oo[0], oo[1], oo[2], oo[3]);
                         }
-                        if (p.dbg & 8) o &= 0xfff8;
                         *(uint4*)(ob + o) = u;
                     }
                 }
@@ -475,7 +458,7 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
                 if (simple && p.act == ACT_SOFTMAXG) { lds_epilogue(std::integral_constant<int, 2>{}); done = true; }
             }
             if (!done) { if (plain) lds_epilogue(std::integral_constant<int, 1>{}); else lds_epilogue(std::integral_constant<int, 0>{}); }
-        } else if (!(p.dbg & 4)) {
+        } else {
 #pragma unroll
             for (int i = 0; i < FM; i++) {
                 const int mf = em0 + wm * WM + i * 32;                 // first row of this fragment
@@ -545,7 +528,6 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
                         float hi = odd ? v[2 * t + 1] : got;
                         if (full || (pair_ok && mrow + roff < p.M)) {
                             long long o = base + (long long)roff * p.ldo;
-                            if (p.dbg & 8) o &= 0xfffe;            // ablation: all stores land in one 64 KB window (no HBM write stream)
                             if constexpr (BATCH_RES) { if (rb) { const uint32_t u = rw[j & 1][t]; lo += __uint_as_float(u << 16); hi += __uint_as_float(u & 0xffff0000u); } }
                             else { if (rb) { const uint32_t u = *(const uint32_t*)(rb + o); lo += __uint_as_float(u << 16); hi += __uint_as_float(u & 0xffff0000u); } }
                             if (rf) { const float2 f = *(const float2*)(rf + o); lo += f.x; hi += f.y; }
@@ -556,21 +538,15 @@ __global__ __launch_bounds__(WAVES_M * 128, 2) void igemm_kernel(IgemmParams p) 
                 }
             }
         }
-        if (p.dbg & 16) tprof[1] += __builtin_readcyclecounter() - tp1;
         if (!has_next) break;
         tile = next;
         {
             constexpr int NFRAG = GEGLU ? FM * FN / 2 : FM * FN;
             const int nout = (ob ? 1 : 0) + (of ? 1 : 0);
             if (lds_epi) pending_stores = full ? FM * ((32 * (WNO / 8)) / 64) : 0;     // 16-byte row stores per lane
-            else pending_stores = (full && nout == 1 && !(p.dbg & 4)) ? NFRAG * 8 : 0;      // exact only for full tiles
+            else pending_stores = (full && nout == 1) ? NFRAG * 8 : 0;      // exact only for full tiles
             if (pending_stores == 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // unknown count: drain now
         }
-    }
-    if ((p.dbg & 16) && tid == 0) {
-        atomicAdd(&g_igemm_prof[0], tprof[0]); atomicAdd(&g_igemm_prof[1], tprof[1]); atomicAdd(&g_igemm_prof[2], tprof[2]);
-        atomicAdd(&g_igemm_prof[4], tprof[3]);
-        atomicAdd(&g_igemm_prof[3], 1ull);
     }
 }
 
@@ -599,18 +575,6 @@ static hipError_t launch_cfg(const IgemmParams& p, int batch, hipStream_t st) {
     if (g > ntiles) g = ntiles;
     if (g < 1) g = 1;
     dim3 grid((unsigned)g, 1, batch);
-    static const int prof = getenv("RDM_IGEMM_PROF") ? atoi(getenv("RDM_IGEMM_PROF")) : 0;
-    if (prof) {      // dev-only: synchronous launch, prints wave-0 shader cycles per block
-        IgemmParams q = p; q.dbg |= 16;
-        unsigned long long z[5] = {0, 0, 0, 0, 0}, r[5];
-        hipMemcpyToSymbol(HIP_SYMBOL(g_igemm_prof), z, sizeof(z));
-        igemm_kernel<BM, BN, WAVES_M, CONV, GEGLU><<<grid, NT, smem, st>>>(q);
-        hipStreamSynchronize(st);
-        hipMemcpyFromSymbol(r, HIP_SYMBOL(g_igemm_prof), sizeof(r));
-        fprintf(stderr, "[igemm<%d,%d,%d,%d> M=%d N=%d K=%d] blocks=%llu per-block cycles: kloop %.0f (of which tile-start wait %.0f) epilogue %.0f (of which waiting for the other waves %.0f) (tiles/block %.2f)\n",
-                BM, BN, CONV, (int)GEGLU, p.M, p.N, p.K, r[3], (double)r[0] / r[3], (double)r[2] / r[3], (double)r[1] / r[3], (double)r[4] / r[3], (double)ntiles / g);
-        return hipGetLastError();
-    }
     igemm_kernel<BM, BN, WAVES_M, CONV, GEGLU><<<grid, NT, smem, st>>>(p);
     return hipGetLastError();
 }
@@ -639,9 +603,7 @@ hipError_t launch_conv_phase_weights(const bf16_t* W, bf16_t* Wp, int N, int C, 
 }
 
 hipError_t launch_igemm(const IgemmParams& p_in, bool conv, int batch, hipStream_t st) {
-    static const int dbg = getenv("RDM_IGEMM_DBG") ? atoi(getenv("RDM_IGEMM_DBG")) : 0;
-    IgemmParams p = p_in; p.dbg = dbg;
-    static const int no_resk = getenv("RDM_NO_RESK") ? atoi(getenv("RDM_NO_RESK")) : 0;
+    IgemmParams p = p_in;
     p.res_k = 0;
     if (p.K % 64 != 0 || p.C0 % 64 != 0 || p.C1 % 64 != 0) return hipErrorInvalidValue;
     if (p.N % 2 != 0 || p.ldo % 2 != 0 || p.sO % 2 != 0) return hipErrorInvalidValue;   // paired-column epilogue
@@ -651,21 +613,17 @@ hipError_t launch_igemm(const IgemmParams& p_in, bool conv, int batch, hipStream
         return hipErrorInvalidValue;                        // the column-group softmax lives in the 128-wide bf16 epilogue only
     // tall 256-row tiles (8 waves, 1 block/CU) cut the L2->LDS operand traffic per FLOP by 1.44x; use them
     // whenever there are enough row tiles to fill the chip, else the 128-row tile (4 waves, 2 blocks/CU).
-    static const int force_bm = getenv("RDM_IGEMM_BM") ? atoi(getenv("RDM_IGEMM_BM")) : 0;
     const bool wide = (p.N % 192 == 0);
     const long long tiles256 = (long long)((p.M + 255) / 256) * ((p.N + (wide ? 191 : 127)) / (wide ? 192 : 128)) * batch;
-    bool tall = tiles256 >= 256 && p.M > 128;      // 8 waves, 3-deep A ring: the HBM latency of the activation stream is covered
+    const bool tall = tiles256 >= 256 && p.M > 128;      // 8 waves, 3-deep A ring: the HBM latency of the activation stream is covered
                                                    // (M <= 128 rows per batch item: a 256-row tile would be mostly padding)
-    if (force_bm == 128) tall = false;
-    if (force_bm == 256) tall = true;
     if (!conv && p.Wfrag && lin4_supported(p, batch)) return launch_lin4(p, st);       // lin4.hip
     if (p.a1_wrap_rows > 0 || p.res_wrap_rows > 0) return hipErrorInvalidValue;                               // a wrapped second source is read by lin4 only
     if (p.act == ACT_GEGLU) {
         if (conv) return hipErrorInvalidValue;
         // 256-wide tile (x and gate interleaved: 128 outputs): the A tile is re-read once per column tile, and the
         // L2->LDS path (1 KiB per ~20 cycles per CU), not the MFMA pipe, bounds the 128-wide tile's K loop
-        static const int geglu_bn = getenv("RDM_GEGLU_BN") ? atoi(getenv("RDM_GEGLU_BN")) : 256;
-        if (tall && geglu_bn == 256 && p.N % 256 == 0 && (long long)((p.M + 255) / 256) * (p.N / 256) * batch >= 256)
+        if (tall && p.N % 256 == 0 && (long long)((p.M + 255) / 256) * (p.N / 256) * batch >= 256)
             return launch_cfg<256, 256, 4, 0, true>(p, batch, st);
         return tall ? launch_cfg<256, 128, 4, 0, true>(p, batch, st) : launch_cfg<128, 128, 2, 0, true>(p, batch, st);
     }
@@ -686,7 +644,7 @@ hipError_t launch_igemm(const IgemmParams& p_in, bool conv, int batch, hipStream
         return tall ? launch_cfg<256, 128, 4, 1, false>(p, batch, st) : launch_cfg<128, 128, 2, 1, false>(p, batch, st);
     }
     // linear with a bf16 residual: feed the residual tile through the A stream against an identity block (see the kernel)
-    if (!no_resk && p.res_bf16 && !p.res_f32 && p.out_bf16 && !p.out_f32 && p.alpha == 1.0f && p.act == ACT_NONE &&
+    if (p.res_bf16 && !p.res_f32 && p.out_bf16 && !p.out_f32 && p.alpha == 1.0f && p.act == ACT_NONE &&
         p.N % (wide ? 192 : 128) == 0 && p.ldo % 8 == 0 && p.ldo >= p.N)
         p.res_k = 1;
     if (wide) return tall ? launch_cfg<256, 192, 4, 0, false>(p, batch, st) : launch_cfg<128, 192, 2, 0, false>(p, batch, st);

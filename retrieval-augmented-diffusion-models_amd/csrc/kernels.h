@@ -12,7 +12,6 @@ struct GnParams {
     float eps; int silu;
     bf16_t* out;                          // [B, HW, C0+C1]
     int x1_bmod;                          // > 0: x1 holds only x1_bmod samples and sample b reads b % x1_bmod (a shared-prefix skip tensor whose second half was never materialised)
-    int b0;                               // first sample of this launch (launch_groupnorm walks big tensors in sample ranges: blockIdx.y + b0)
     int x0_bmod;                          // the same for x0 (round 5: the activation leaving the shared guidance prefix is not duplicated either)
 };
 
@@ -39,7 +38,6 @@ struct FlashParams {
     bf16_t* out; int ldo;            // out[(b*n + i)*ldo + h*32 + d]
     int n, C;                        // tokens, channels (= heads*32)
     float scale_log2e;               // d^-0.5 * log2(e)
-    int xcd_remap;                   // set by the launcher: XCD-aware (sample, head) grouping of the query blocks
 };
 
 // cross-attention over k retrieved neighbours in the re-associated form (model.hip: unet_compute_xattn): per sample b
@@ -100,11 +98,7 @@ struct RarmXattnParams {
     const float* bias;                         // [C]
     int B2, Bc, C, NP, heads, k;
     const float* ln3_g; const float* ln3_b; bf16_t* ln3_out;   // given: LayerNorm (gamma, beta) of the FINISHED rows leaves with them as bf16 [B2][C] (norm3: the operand of the feed-forward's first GEMM)
-    float* ws; int* ws_count;                  // four-blocks-per-sequence form: partial output rows [B2][4][C] as 8-byte {fp32, epoch tag} granules (zeroed once) and one monotonic arrival counter per sequence; null = one block per sequence
-    unsigned epoch;                            // four-blocks form: this launch's tag, unique per launch over the buffer's lifetime, never 0 (rarm.hip: self-validating hand-over)
-    int no_split;                              // deterministic mode: the form must not follow the batch -- always one block per sequence
 };
-unsigned long long rarm_xsplit_stale_count();     // granules the four-blocks form's last arrivers had to re-read since library load (debug counter 0)
 hipError_t launch_rarm_xattn_decode(const RarmXattnParams& p, hipStream_t st);
 
 struct RarmSampleParams {
@@ -237,9 +231,3 @@ hipError_t launch_to_uint8_hwc(const float* x, unsigned char* out, int B, int C,
 
 // box calibration probes (calib.hip): a fixed MFMA stream on random bf16 operands and a fixed HBM copy, timed on `st`
 hipError_t run_calib_probes(void* buf, double mfma_ms, size_t stream_bytes, int stream_reps, double* mfma_tflops, double* stream_gbps, hipStream_t st);
-
-// fused feed-forward (ffn.hip, round 6: a measurement vehicle, C = 384 only): out = [x gelu(g) | t2] Wf^T + bf + xin, [x | g] = l3 W1^T + b1
-size_t ffn_fused_scratch_bytes(int C);
-bool ffn_fused_supported(int M, int C);
-hipError_t launch_ffn_fused(const bf16_t* l3, const bf16_t* t2, const bf16_t* xin, const bf16_t* w1, const float* b1, const bf16_t* wf, const float* bf,
-                            bf16_t* out, int M, int C, char* scratch, bool repack, hipStream_t st);

@@ -107,7 +107,6 @@ struct ScanParams {
     const _Float16* qh; const _Float16* ql;
     float* cand_s; uint32_t* cand_i;      // [64][nlists][KSEL]
     int nlists; const void* zero_page;
-    int hi_only;                          // score with the hi word of the query only (certificate bound KNN_EPS_BULK)
 };
 
 template <int KSEL>
@@ -323,8 +322,9 @@ __global__ __launch_bounds__(256, 1) void knn_scan512_kernel(ScanParams p) {
 // queries (128 registers of hi / lo fragments) x 128 rows, so 8 waves = 2 row halves x 4 query groups fit two per SIMD (256
 // registers each) and one wave's LDS-DMA issue, LDS latency and list insertion hide behind its SIMD partner's MFMAs.
 // D layout 16x16: col (query) = lane & 15, row = (lane >> 4) * 4 + reg -> still one query, one private top-k list per lane.
-template <int KSEL, bool HI_ONLY>    // HI_ONLY: score with the hi fp16 word of the query (certificate bound KNN_EPS_BULK); halves the MFMA work, and the
-                                      // lighter loop holds a higher clock: 4.99 -> 4.48 ms per 64 queries over 20.9 M rows
+// Scores with the hi fp16 word of the query only (certificate bound KNN_EPS_BULK): that halves the MFMA work, and the lighter loop
+// holds a higher clock: 4.99 -> 4.48 ms per 64 queries over 20.9 M rows.
+template <int KSEL>
 __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
     constexpr int DB_BYTES = KNN_ROWS * 128, NKC = 8, DIM = 512;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -334,12 +334,11 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
     const int rh = wave >> 2, qg = wave & 3;
     const char* zero = (const char*)p.zero_page;
 
-    f16x8 qh[16], ql[HI_ONLY ? 1 : 16];                       // B fragments of my 16 queries, all 16 k-steps of 32
+    f16x8 qh[16];                                             // B fragments of my 16 queries, all 16 k-steps of 32
     {
         const _Float16* qhp = p.qh + (long long)(qg * 16 + l15) * DIM + kq * 8;
-        const _Float16* qlp = p.ql + (long long)(qg * 16 + l15) * DIM + kq * 8;
 #pragma unroll
-        for (int s = 0; s < 16; s++) { qh[s] = *(const f16x8*)(qhp + s * 32); if constexpr (!HI_ONLY) ql[s] = *(const f16x8*)(qlp + s * 32); }
+        for (int s = 0; s < 16; s++) qh[s] = *(const f16x8*)(qhp + s * 32);
     }
     float ls[KSEL]; uint32_t li[KSEL];
 #pragma unroll
@@ -385,10 +384,6 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
                 for (int rf = 0; rf < 8; rf++) {
                     const int row = rh * 128 + rf * 16 + l15;
                     a[rf] = *(const f16x8*)(Ds + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-                }
-                if constexpr (!HI_ONLY) {
-#pragma unroll
-                    for (int rf = 0; rf < 8; rf++) acc[rf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rf], ql[s], acc[rf], 0, 0, 0);
                 }
 #pragma unroll
                 for (int rf = 0; rf < 8; rf++) acc[rf] = __builtin_amdgcn_mfma_f32_16x16x32_f16(a[rf], qh[s], acc[rf], 0, 0, 0);
@@ -441,7 +436,7 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
 // 8-entry lists, the ascending insertion and the 16-candidate pre-compare below); an idle sleep in place of the MFMAs hides completely
 // behind the requests (62 ms), the real MFMA + LDS-read stream does not (96 ms without insertion): what is left is contention between
 // the LDS-DMA stream (48 KB per stage and block at ~26 B/clk) and the scoring waves, not the ring depth.
-struct BulkParams { ScanParams s; int groups; int dbg; };      // s.qh: [groups*128][dim]; s.cand_*: [groups*128][nlists][KSEL]; dbg: ablation bits (RDM_KNN_BULK_DBG)
+struct BulkParams { ScanParams s; int groups; };      // s.qh: [groups*128][dim]; s.cand_*: [groups*128][nlists][KSEL]
 
 template <int KSEL>
 __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
@@ -504,7 +499,7 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
             if (it + 1 < iters) asm volatile("s_waitcnt vmcnt(12)" ::: "memory");    // stage `it` landed; the 12 requests of stage it+1 may fly
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();                 // everyone is done reading the slot of stage it-1
-            if (it + 2 < iters && !(bp.dbg & 1)) stage_next();
+            if (it + 2 < iters) stage_next();
         }
         return;
     }
@@ -538,8 +533,7 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
         __builtin_amdgcn_sched_barrier(0);
         const unsigned sb = (unsigned)(cslot * STAGE);
         cslot = cslot == NSLOT - 1 ? 0 : cslot + 1;
-        if (bp.dbg & 16) __builtin_amdgcn_s_sleep(16);    // ~1024 idle cycles per stage in place of the MFMAs (with bit 2)
-        if (!(bp.dbg & 2)) {
+        {
             // One scoring wave per SIMD: nobody else hides its LDS latency, so the fragments of k-step kk+1 are requested before the
             // MFMAs of k-step kk are issued.  Left to the scheduler the loop came out as read-6 / wait / 8 MFMAs (2.1 k cycles per
             // stage for 1 k cycles of MFMA), hence explicit reads with counted lgkmcnt waits.
@@ -582,7 +576,6 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
                     }
             }
             const uint32_t rb = (uint32_t)rbase;
-            const bool ins = !(bp.dbg & 4);
             auto insert_half = [&](auto F) {               // compile-time query fragment: the lists must stay in registers
                 constexpr int f = decltype(F)::value;
 #pragma unroll
@@ -591,7 +584,7 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
                     float m = acc[rf][f][0];
 #pragma unroll
                     for (int r = 1; r < 16; r++) m = fmaxf(m, acc[rf][f][r]);
-                    if (ins && m > ls[f][KSEL - 1]) {
+                    if (m > ls[f][KSEL - 1]) {
 #pragma unroll
                         for (int r = 0; r < 16; r++) list_insert_ascending<KSEL>(ls[f], li[f], acc[rf][f][r], rb + rf * 32 + (r & 3) + 8 * (r >> 2));
                     }
@@ -876,14 +869,6 @@ static const char* search_impl(KnnDb& db, const float* q, int b, int k, uint32_t
             knn_prep_queries_kernel<<<groups * 128, 64, 0, st>>>(q + (size_t)q0 * db.dim, bq, db.dim, qn, qh, ql);
             KNN_TRY(hipGetLastError());
             BulkParams bp{}; bp.groups = groups;
-            // scan-only ablation (tools/bulk_pmc.sh): compiled in only with -DRDM_DEBUG_ABLATION -- a leaked environment variable must
-            // never make the production search return success with uninitialised neighbours
-#ifdef RDM_DEBUG_ABLATION
-            static const int bdbg = getenv("RDM_KNN_BULK_DBG") ? atoi(getenv("RDM_KNN_BULK_DBG")) : 0;
-#else
-            constexpr int bdbg = 0;
-#endif
-            bp.dbg = bdbg;
             bp.s.dbn = (const _Float16*)db.dbn; bp.s.n = db.n; bp.s.dim = db.dim; bp.s.ntiles = ntiles; bp.s.qh = qh; bp.s.ql = ql;
             bp.s.cand_s = cs; bp.s.cand_i = ci; bp.s.zero_page = zero_page;
             int walkers = bgrid / groups; if ((long long)walkers > ntiles) walkers = (int)ntiles;
@@ -894,7 +879,6 @@ static const char* search_impl(KnnDb& db, const float* q, int b, int k, uint32_t
             KNN_TRY(hipGetLastError());
             MergeParams mp{}; mp.cand_s = cs; mp.cand_i = ci; mp.nlists = bp.s.nlists; mp.dbn = (const _Float16*)db.dbn; mp.qn = qn;
             mp.dim = db.dim; mp.n = db.n; mp.k = k; mp.idx_out = idx_out; mp.score_out = score_out; mp.score64_out = score64_out; mp.qbase = q0; mp.cert = cert; mp.eps = KNN_EPS_BULK;
-            if (bdbg) continue;                                            // ablation timing of the scan alone: results are garbage
             knn_merge_kernel<KSEL, R><<<bq, 256, merge_smem, st>>>(mp);
             KNN_TRY(hipGetLastError());
             knn_exact_collect_kernel<<<ncu * 4, 256, 0, st>>>(cert, (const _Float16*)db.dbn, qn, db.n, db.dim, bq);
@@ -909,25 +893,21 @@ static const char* search_impl(KnnDb& db, const float* q, int b, int k, uint32_t
         KNN_TRY(hipGetLastError());
         ScanParams sp{}; sp.dbn = (const _Float16*)db.dbn; sp.n = db.n; sp.dim = db.dim; sp.ntiles = ntiles; sp.qh = qh; sp.ql = ql;
         sp.cand_s = cs; sp.cand_i = ci; sp.nlists = nlists; sp.zero_page = zero_page;
-        static const int w8 = getenv("RDM_KNN_W8") ? atoi(getenv("RDM_KNN_W8")) : 1;
-        static const int hi_only = getenv("RDM_KNN_HI_ONLY") ? atoi(getenv("RDM_KNN_HI_ONLY")) : 1;
-        sp.hi_only = (d512 && KSEL == 8 && w8) ? hi_only : 0;
-        if (d512 && KSEL == 8 && w8) {
+        const bool w8 = d512 && KSEL == 8;                               // hi-word scoring: certificate bound KNN_EPS_BULK
+        if (w8) {
             static bool attr8_dev[RDM_MAX_DEVICES] = {false};
             bool& attr8 = attr8_dev[rdm_cur_device()];
             if (!attr8) {
-                KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<8, true>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
-                KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<8, false>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
+                KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
                 attr8 = true;
             }
             sp.nlists = grid * 8;
-            if (sp.hi_only) knn_scan512w8_kernel<8, true><<<grid, 512, scan512_smem, st>>>(sp);
-            else knn_scan512w8_kernel<8, false><<<grid, 512, scan512_smem, st>>>(sp);
+            knn_scan512w8_kernel<8><<<grid, 512, scan512_smem, st>>>(sp);
         } else if (d512) knn_scan512_kernel<KSEL><<<grid, 256, scan512_smem, st>>>(sp);
         else knn_scan_kernel<KSEL><<<grid, 256, scan_smem, st>>>(sp);
         KNN_TRY(hipGetLastError());
         MergeParams mp{}; mp.cand_s = cs; mp.cand_i = ci; mp.nlists = sp.nlists; mp.dbn = (const _Float16*)db.dbn; mp.qn = qn;
-        mp.dim = db.dim; mp.n = db.n; mp.k = k; mp.idx_out = idx_out; mp.score_out = score_out; mp.score64_out = score64_out; mp.qbase = q0; mp.cert = cert; mp.eps = sp.hi_only ? KNN_EPS_BULK : KNN_EPS;
+        mp.dim = db.dim; mp.n = db.n; mp.k = k; mp.idx_out = idx_out; mp.score_out = score_out; mp.score64_out = score64_out; mp.qbase = q0; mp.cert = cert; mp.eps = w8 ? KNN_EPS_BULK : KNN_EPS;
         knn_merge_kernel<KSEL, R><<<bq, 256, merge_smem, st>>>(mp);
         KNN_TRY(hipGetLastError());
         // exact fallback for the flagged queries of this group (both kernels return at once when nothing is flagged)

@@ -15,15 +15,11 @@
 //     consecutive channels of ONE row of the output; a v_permlane32_swap per register pair makes that 8 consecutive channels =
 //     one 16-byte store, with no LDS transpose, no DPP and no LDS wait in the epilogue; the bias is the accumulators' initial
 //     value (written when the previous tile's results are read out), so the epilogue adds nothing but the residual.
-#include <stdio.h>
-#include <stdlib.h>
 
 #include <type_traits>
 
 #include "kernels.h"
 #include "h4_asm.h"
-
-__device__ unsigned long long g_lin4_prof[4];
 
 // fragment-ordered weight copy: dst[(nb * KQ + kq) * 512 + lane * 8 + e] = W[nb * 32 + (lane & 31)][kq * 16 + (lane >> 5) * 8 + e]
 // GEGLU (W rows stored as [32 x | 32 gates] blocks, packing.py _geglu_perm): fragment nb = rows {16 x, then their 16 gates} of block
@@ -109,7 +105,7 @@ __device__ __forceinline__ ASrc l4_asrc(bool dead, int row0, int kc, int C0, con
 // 8 lanes per row reduced by DPP once per tile), meet in LDS as (mean, rstd) one step before the tile's read-out, and the read-out
 // forms  rstd * (acc - mean * s[n]) + b'[n]  in fp32 (no bias in the accumulators, no residual).  The separate LayerNorm pass (one
 // read + one write of the tensor, 2.3 % of a sampling step) is gone; the statistics cost VALU slots beside the MFMAs.
-template <int VAR, bool GEGLU, int WM, bool LN>       // VAR: dev-only ablations (RDM_L4_VAR): 1 = activation pieces from the zero page, 2 = no stores
+template <bool GEGLU, int WM, bool LN>
 __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
     constexpr int BM = 128 * WM, BK = 64, FM = 4, FN = 3, WN = FN * 32, BN = (4 / WM) * WN;
     constexpr int L4_ABUF = BM * 144;          // one staged K-slice: BM rows x (128 bytes of channels + 16 of padding)
@@ -173,7 +169,7 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
         return (const char*)l4_uni64((unsigned long long)(Wf + off));
     };
     auto a_src = [&](const Cur& c) __attribute__((always_inline)) {
-        return l4_asrc(VAR == 1 || c.tile >= t_end, c.bm * BM, c.sl * BK, C0, A0p, A1p, ld0, ld1, zero, voffA0, voffA1, lane16, wrap1);
+        return l4_asrc(c.tile >= t_end, c.bm * BM, c.sl * BK, C0, A0p, A1p, ld0, ld1, zero, voffA0, voffA1, lane16, wrap1);
     };
 
     asm volatile("" ::: H4_ACC_CLOBBERS);                    // the kernel descriptor must allocate the accumulator AGPRs
@@ -289,10 +285,6 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
     }
     acc_init(cc.bn, cc.bm);
 
-    unsigned long long tprof[2] = {0, 0};
-    unsigned long long tp0 = 0, tp1 = 0;
-    if (p.dbg & 16) tp0 = __builtin_readcyclecounter();
-
     // ---- main stream: one step = one 64-deep K-slice = 4 k-steps x 12 MFMAs.  Outstanding vector-memory requests at a step's
     // start, oldest first: [NPC pieces of step X-2][12 weight fragments requested in step X-1][NPC pieces of step X-1]: vmcnt(NPC).
     int epi_stores = 0;
@@ -392,7 +384,6 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
         // considers dead: drain them before anything else may be allocated there
         if (!has_next) asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
         asm volatile("s_nop 15\n\ts_nop 15" ::: "memory");      // last MFMA -> v_accvgpr_read: 18 wait states (hipcc does not pad around asm)
-        if (p.dbg & 16) { tp1 = __builtin_readcyclecounter(); tprof[0] += tp1 - tp0; }
 
         int lane_e = lane;
         asm volatile("" : "+v"(lane_e));
@@ -475,7 +466,7 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
                     // algorithmic bytes, verdict round 4 item 7).  Same box: GEGLU 415.6 -> 400.8 us, its consumer ff.net.2 x proj_out 210.4 -> 203.0,
                     // headline + 0.45 .. 0.6 % (profiles/r05c_nt_stores_ab.log).  The same modifier on the other read-outs (plain lin4,
                     // conv_halo4) and on the GroupNorm outputs measured neutral to slightly negative: their consumers re-read them at once.
-                    if constexpr (VAR == 2) { asm volatile("" :: "v"(dv), "v"(voffs[it])); } else H4_GSTORES_NT(voffs[it], dv, op);
+                    H4_GSTORES_NT(voffs[it], dv, op);
                 }
             };
             stage_row(0); store_row(0);
@@ -528,10 +519,10 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
                         a1.z += __uint_as_float(r4.w << 16); a1.w += __uint_as_float(r4.w & 0xffff0000u);
                     }
                     const h4_u32x4 dv = {cvt_pk_bf16(a0.x, a0.y), cvt_pk_bf16(a0.z, a0.w), cvt_pk_bf16(a1.x, a1.y), cvt_pk_bf16(a1.z, a1.w)};
-                    if constexpr (VAR == 2) { asm volatile("" :: "v"(dv), "v"(voffs[it])); } else H4_GSTORES(voffs[it], dv, op);
+                    H4_GSTORES(voffs[it], dv, op);
                 }
             };
-            constexpr int NST = VAR == 2 ? 0 : 6;              // stores per fragment row
+            constexpr int NST = 6;                             // stores per fragment row
             if (!LN && rb) {
                 res_request(0, rr4[0]); res_request(1, rr4[1]);
                 stage_row(0);
@@ -555,25 +546,19 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
                 stage_row(3); store_row(3);
             }
         }
-        epi_stores = (VAR == 2) ? 0 : (GEGLU ? FM * FN : 2 * FM * FN);
-        if (p.dbg & 16) tprof[1] += __builtin_readcyclecounter() - tp1;
+        epi_stores = GEGLU ? FM * FN : 2 * FM * FN;
         if (!has_next) return true;
         cc = nx;
-        if (p.dbg & 16) tp0 = __builtin_readcyclecounter();
         return false;
     };
     while (true) {
         describe(); step(std::integral_constant<int, 0>{}); if (advance()) break;
         describe(); step(std::integral_constant<int, 1>{}); if (advance()) break;
     }
-    if ((p.dbg & 16) && tid == 0) {
-        atomicAdd(&g_lin4_prof[0], tprof[0]); atomicAdd(&g_lin4_prof[1], tprof[1]); atomicAdd(&g_lin4_prof[3], 1ull);
-    }
 }
 
 static int lin4_wm(const IgemmParams& p) {        // wave arrangement: 1 x 4 waves (128 x 384 tiles) whenever N allows, else 2 x 2 (256 x 192)
-    static const int force = getenv("RDM_L4_WM") ? atoi(getenv("RDM_L4_WM")) : 0;
-    if (p.N % 384 == 0 && p.M % 128 == 0 && force != 2) return 1;
+    if (p.N % 384 == 0 && p.M % 128 == 0) return 1;
     if (p.N % 192 == 0 && p.M % 256 == 0) return 2;
     return 0;
 }
@@ -581,8 +566,7 @@ static int lin4_smem_bytes(const IgemmParams& p, int wm) {
     return 2 * (128 * wm * 144) + 4 * 32 * 400 + (p.ln_sb ? p.N * 8 + 128 * wm * 8 : p.N * 4 + (p.rowvec ? 2 * p.N * 4 : 0));
 }
 bool lin4_supported(const IgemmParams& p, int batch) {
-    static const int off = getenv("RDM_NO_LIN4") ? atoi(getenv("RDM_NO_LIN4")) : 0;
-    if ((off & 1) || !p.Wfrag || batch != 1) return false;
+    if (!p.Wfrag || batch != 1) return false;
     const int wm = lin4_wm(p);
     if (!wm || p.K % 64 || p.C0 % 64 || p.C1 % 64 || p.K != p.C0 + p.C1) return false;
     if (p.alpha != 1.0f || p.res_f32 || p.out_f32 || !p.out_bf16) return false;
@@ -590,7 +574,7 @@ bool lin4_supported(const IgemmParams& p, int batch) {
     if (p.rowvec && (p.ln_sb || p.rows_per_sample <= 0 || p.rows_per_sample % (128 * wm) != 0 || 2LL * p.rows_per_sample < p.M || p.rowvec_ld < p.N)) return false;
     const bool geglu = p.act == ACT_GEGLU;
     if (p.act != ACT_NONE && !geglu) return false;
-    if (geglu && (p.res_bf16 || (off & 2))) return false;
+    if (geglu && p.res_bf16) return false;
     const int No = geglu ? p.N / 2 : p.N;
     if (p.N > 8192 || p.ldo % 8 || p.ldo < No || (p.ldw > 0 && p.ldw != p.K)) return false;
     if (p.C1 > 0 && p.lda > 0) return false;
@@ -598,51 +582,34 @@ bool lin4_supported(const IgemmParams& p, int batch) {
     if (p.a1_wrap_rows > 0 && (p.C1 == 0 || p.a1_wrap_rows % (128 * wm) != 0 || 2LL * p.a1_wrap_rows < p.M)) return false;     // whole tiles, at most two copies
     // LayerNorm folded in: one source of >= 2 slices, no residual (the bias rides in ln_sb), everything in 160 KiB of LDS
     if (p.ln_sb && (p.C1 > 0 || p.K < 128 || p.res_bf16 || p.bias || lin4_smem_bytes(p, wm) > 160 * 1024 || !(p.ln_inv_c > 0.f))) return false;
-    static const int min_tiles = getenv("RDM_L4_MIN_TILES") ? atoi(getenv("RDM_L4_MIN_TILES")) : 128;
-    if (!p.l4_any_tiles && (long long)(p.M / (128 * wm)) * (p.N / (wm == 1 ? 384 : 192)) < min_tiles) return false;     // far fewer tiles than CUs: the 128-row tiles of igemm.hip (160 tiles -- the 8x8-level projections -- still win here: 28 vs 32 us)
+    // far fewer tiles than CUs: the 128-row tiles of igemm.hip (160 tiles -- the 8x8-level projections -- still win here: 28 vs 32 us)
+    constexpr int L4_MIN_TILES = 128;
+    if (!p.l4_any_tiles && (long long)(p.M / (128 * wm)) * (p.N / (wm == 1 ? 384 : 192)) < L4_MIN_TILES) return false;
     return true;
 }
 
-template <int VAR, bool GEGLU, int WM, bool LN>
+template <bool GEGLU, int WM, bool LN>
 static hipError_t launch_lin4_cfg(const IgemmParams& p, hipStream_t st) {
     const int smem = lin4_smem_bytes(p, WM);
     static int ncu_dev[RDM_MAX_DEVICES] = {0};
     const int dev = rdm_cur_device();
     if (!ncu_dev[dev]) {
-        hipError_t e = hipFuncSetAttribute((const void*)lin4_kernel<VAR, GEGLU, WM, LN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)lin4_kernel<GEGLU, WM, LN>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
         if (e != hipSuccess) return e;
         hipDeviceGetAttribute(&ncu_dev[dev], hipDeviceAttributeMultiprocessorCount, dev);
     }
     const long long ntiles = (long long)(p.M / (128 * WM)) * (p.N / (WM == 1 ? 384 : 192));
     long long g = (ncu_dev[dev] + 7) & ~7;
     if (g > ntiles) g = ntiles;
-    static const int prof = getenv("RDM_LIN4_PROF") ? atoi(getenv("RDM_LIN4_PROF")) : 0;
-    if (prof) {
-        IgemmParams q = p; q.dbg |= 16;
-        unsigned long long z[4] = {0, 0, 0, 0}, r[4];
-        hipMemcpyToSymbol(HIP_SYMBOL(g_lin4_prof), z, sizeof(z));
-        lin4_kernel<VAR, GEGLU, WM, LN><<<dim3((unsigned)g), 256, smem, st>>>(q);
-        hipStreamSynchronize(st);
-        hipMemcpyFromSymbol(r, HIP_SYMBOL(g_lin4_prof), sizeof(r));
-        fprintf(stderr, "[lin4<%d,%d,%d> M=%d N=%d K=%d] blocks=%llu per-block cycles: main %.0f epilogue %.0f (tiles/block %.2f)\n", (int)GEGLU, WM, (int)LN, p.M, p.N, p.K,
-                r[3], (double)r[0] / r[3], (double)r[1] / r[3], (double)ntiles / g);
-        return hipGetLastError();
-    }
-    lin4_kernel<VAR, GEGLU, WM, LN><<<dim3((unsigned)g), 256, smem, st>>>(p);
+    lin4_kernel<GEGLU, WM, LN><<<dim3((unsigned)g), 256, smem, st>>>(p);
     return hipGetLastError();
 }
-template <int VAR>
-static hipError_t launch_lin4_var(const IgemmParams& p, hipStream_t st) {
-    const int wm = lin4_wm(p);
-    if (p.act == ACT_GEGLU) return wm == 1 ? launch_lin4_cfg<VAR, true, 1, false>(p, st) : launch_lin4_cfg<VAR, true, 2, false>(p, st);
-    return wm == 1 ? launch_lin4_cfg<VAR, false, 1, false>(p, st) : launch_lin4_cfg<VAR, false, 2, false>(p, st);
-}
 hipError_t launch_lin4(const IgemmParams& p, hipStream_t st) {
-    static const int var = getenv("RDM_L4_VAR") ? atoi(getenv("RDM_L4_VAR")) : 0;
-    if (p.ln_sb) {                                   // LayerNorm folded in (no dev ablations of these)
-        const int wm = lin4_wm(p);
-        if (p.act == ACT_GEGLU) return wm == 1 ? launch_lin4_cfg<0, true, 1, true>(p, st) : launch_lin4_cfg<0, true, 2, true>(p, st);
-        return wm == 1 ? launch_lin4_cfg<0, false, 1, true>(p, st) : launch_lin4_cfg<0, false, 2, true>(p, st);
+    const int wm = lin4_wm(p);
+    if (p.ln_sb) {                                   // LayerNorm folded in
+        if (p.act == ACT_GEGLU) return wm == 1 ? launch_lin4_cfg<true, 1, true>(p, st) : launch_lin4_cfg<true, 2, true>(p, st);
+        return wm == 1 ? launch_lin4_cfg<false, 1, true>(p, st) : launch_lin4_cfg<false, 2, true>(p, st);
     }
-    return var == 2 ? launch_lin4_var<2>(p, st) : var == 1 ? launch_lin4_var<1>(p, st) : launch_lin4_var<0>(p, st);
+    if (p.act == ACT_GEGLU) return wm == 1 ? launch_lin4_cfg<true, 1, false>(p, st) : launch_lin4_cfg<true, 2, false>(p, st);
+    return wm == 1 ? launch_lin4_cfg<false, 1, false>(p, st) : launch_lin4_cfg<false, 2, false>(p, st);
 }

@@ -15,13 +15,12 @@
 // [2048 x 2304] 23.8, K = 3072 39.6; at 4096 rows 17.8 / 37.5 / 45.7 us.  RARM decode: 2048 sequences 776 -> 850 img/s, 4096: 844 -> 960;
 // at 1024 sequences the skinny kernel is still ahead (675 vs 660): used from 1536 rows on.  (Those figures: two stages, two barriers per
 // step; the three-stage ring with one barrier: 2048 sequences 840 -> 865 img/s, 4096: 960 -> 978.)  128-row tiles, 128-column tiles with
-// the waves 2 x 2 (fewer, bigger blocks) and a fourth stage (fewer blocks per CU) measured slower: what paces a block is its chain of
+// the waves 2 x 2 (fewer, bigger blocks) and a fourth stage (fewer blocks per CU) measured slower and are removed: what paces a block is its chain of
 // barrier -> fragment reads -> MFMAs per K step (77 % of the wave cycles wait, MFMA busy 6.5 %), hidden only by the other blocks of the CU.
 // Reading the fragments of stage k + 1 under the MFMAs of stage k (current stage in registers, three buffers, lgkmcnt(0) before the one
 // barrier): built and measured, 876 -> 868 img/s at 2048 sequences (profiles/r05e_rarm_mgemm_fragment_prefetch_sweep.log) -- removed.
 // LDS rows are 128 bytes (64 k); the 16-byte piece p of row r sits at piece p ^ ((r >> 1) & 7): the 16 lanes of a fragment read
 // (consecutive rows, one piece index) land on 16 different 16-byte bank groups.
-#include <stdlib.h>
 
 #include "kernels.h"
 
@@ -170,13 +169,13 @@ __global__ __launch_bounds__(256) void mgemm_kernel(SgemmParams p) {
 }
 
 bool mgemm_supported(const SgemmParams& p) {
-    static const int off = getenv("RDM_NO_MGEMM") ? atoi(getenv("RDM_NO_MGEMM")) : 0;
-    if (off || p.ln_x || p.M < 64 || p.N % 64 != 0 || p.K % 64 != 0 || p.K < 128 || p.lda % 8 != 0) return false;
+    if (p.ln_x || p.M < 64 || p.N % 64 != 0 || p.K % 64 != 0 || p.K < 128 || p.lda % 8 != 0) return false;
     return p.act == ACT_NONE || p.act == ACT_SILU || p.act == ACT_QUICKGELU;
 }
 
-template <int BM, int NS, int BN = 64>
-static hipError_t mgemm_launch_one(const SgemmParams& p, hipStream_t st) {
+hipError_t launch_mgemm(const SgemmParams& p, hipStream_t st) {
+    if (!mgemm_supported(p)) return hipErrorInvalidValue;
+    constexpr int BM = 64, NS = 3, BN = 64;                  // 64 x 64 tiles, 3-stage ring
     constexpr int sm = NS * (BM * 64 * 2 + BN * 64 * 2);
     static bool attr[RDM_MAX_DEVICES] = {false};
     bool& done = attr[rdm_cur_device()];
@@ -187,14 +186,4 @@ static hipError_t mgemm_launch_one(const SgemmParams& p, hipStream_t st) {
     }
     mgemm_kernel<BM, NS, BN><<<dim3(p.N / BN, (p.M + BM - 1) / BM), 256, sm, st>>>(p);
     return hipGetLastError();
-}
-
-hipError_t launch_mgemm(const SgemmParams& p, hipStream_t st) {
-    if (!mgemm_supported(p)) return hipErrorInvalidValue;
-    static const int bm = getenv("RDM_MGEMM_BM") ? atoi(getenv("RDM_MGEMM_BM")) : 64;
-    static const int ns = getenv("RDM_MGEMM_NS") ? atoi(getenv("RDM_MGEMM_NS")) : 3;          // (dev switches: tile rows 64 / 128, ring stages 2 .. 4, tile columns 64 / 128)
-    static const int bn = getenv("RDM_MGEMM_BN") ? atoi(getenv("RDM_MGEMM_BN")) : 64;
-    if (bn == 128 && p.N % 128 == 0) return bm == 128 ? mgemm_launch_one<128, 2, 128>(p, st) : mgemm_launch_one<64, 2, 128>(p, st);
-    if (bm == 128) return ns >= 3 ? mgemm_launch_one<128, 3>(p, st) : mgemm_launch_one<128, 2>(p, st);
-    return ns >= 4 ? mgemm_launch_one<64, 4>(p, st) : ns == 3 ? mgemm_launch_one<64, 3>(p, st) : mgemm_launch_one<64, 2>(p, st);
 }

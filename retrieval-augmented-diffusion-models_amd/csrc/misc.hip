@@ -125,7 +125,6 @@ hipError_t launch_conv_in(const float* x, const float* w, const float* bias, bf1
     const size_t sm = (size_t)(cin_t * 9 + 1) * Cout * sizeof(float);
     if (sm > 96 * 1024) return hipErrorInvalidValue;
     int grid = (H * W + 511) / 512; const int cap_in = (2048 + B - 1) / B; if (grid > cap_in) grid = cap_in; if (grid < 1) grid = 1;
-    static const int oct_env = getenv("RDM_CONVIN_OCT") ? atoi(getenv("RDM_CONVIN_OCT")) : 4;     // 0: direct 16-byte stores
     static bool attr_dev[RDM_MAX_DEVICES] = {false};           // per device, like every other launcher (one process may hold contexts on several GPUs)
     bool& attr_set = attr_dev[rdm_cur_device()];
     if (!attr_set) {
@@ -135,7 +134,7 @@ hipError_t launch_conv_in(const float* x, const float* w, const float* bias, bf1
     }
     const dim3 g(grid, B);
     const size_t sm4 = sm + 2 * 4 * 64 * 80;
-    if (oct_env >= 4 && Cout % 32 == 0) {
+    if (Cout % 32 == 0) {                                   // else direct 16-byte stores (OCT = 0)
         if (cin_t == 3) conv_in_kernel<4, 3><<<g, 256, sm4, st>>>(x, w, bias, out, B, Cin, H, W, Cout);
         else            conv_in_kernel<4, 4><<<g, 256, sm4, st>>>(x, w, bias, out, B, Cin, H, W, Cout);
     } else {

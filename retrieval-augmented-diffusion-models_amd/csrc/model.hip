@@ -446,8 +446,6 @@ struct RarmModel {
     char* state = nullptr; size_t state_bytes = 0;
     // decode-step cross-attention operands per layer (rarm_prepare): [depth][2][Bc][128][C] bf16 (G, UT), valid for xa_B conditional sequences and xa_k neighbours
     char* xa = nullptr; size_t xa_bytes = 0; int xa_B = 0, xa_k = 0;
-    char* xws = nullptr; size_t xws_bytes = 0;          // split decode cross-attention: [B2][4][C] {fp32, epoch} granules, then B2 arrival counters
-    unsigned xepoch = 0;                                // its launch tag (rarm.hip): incremented per launch
 };
 static void build_rarm(RarmModel& m, const rdm_rarm_cfg& c, Manifest& mf) {
     m.cfg = c; m.blk.clear(); m.C = c.n_heads * c.d_head;
@@ -482,8 +480,6 @@ static void build_rarm(RarmModel& m, const rdm_rarm_cfg& c, Manifest& mf) {
 // ------------------------------------------------------------------------------------ context
 struct rdm_ctx {
     int device = 0; hipStream_t stream = nullptr; char err[512] = {0};
-    // side stream for work that is independent of the main chain (the ResBlocks' skip_connection GEMM, round 6): forked / joined by events
-    hipStream_t side = nullptr; hipEvent_t ev_fork = nullptr, ev_join = nullptr; hipStream_t side_saved = nullptr;
     void* zero_page = nullptr; float* eye3 = nullptr;
     UNet unet; VqModel vq; VqEncModel vqenc; ClipModel clip; RarmModel rarm; KnnDb db;
     float* gn_partial = nullptr; size_t gn_partial_bytes = 0;
@@ -554,25 +550,10 @@ struct rdm_ctx {
         wfrag[key] = FragVal{nullptr, t};
         return t;
     }
-    // ... with LayerNorm(gamma, beta) folded in: the copy holds bf16(gamma[k] W[n][k]), *sb the (s, b') table (lin4.hip: lin_ln_sb_kernel)
-    const bf16_t* frag_for_lin_ln(const bf16_t* W, int N, int K, int geglu, const float* gamma, const float* beta, const float* bias, const float** sb) {
-        const FragKey key{W, N, K, geglu ? 4 : 3, gamma};
-        auto it = wfrag.find(key);
-        if (it != wfrag.end()) { *sb = it->second.sb; return it->second.frag; }
-        bf16_t* d = nullptr; float* t = nullptr;
-        if (hipMalloc((void**)&d, (size_t)N * K * 2) != hipSuccess) return nullptr;
-        if (hipMalloc((void**)&t, (size_t)N * 2 * sizeof(float)) != hipSuccess) { (void)hipFree(d); return nullptr; }
-        if (launch_lin_w_fragpack(W, d, N, K, K, geglu, stream, gamma) != hipSuccess || launch_lin_ln_sb(W, gamma, beta, bias, t, N, K, stream) != hipSuccess) {
-            (void)hipFree(d); (void)hipFree(t); return nullptr;
-        }
-        wfrag[key] = FragVal{d, t};
-        *sb = t;
-        return d;
-    }
     // batch-invariant execution (rdm_set_deterministic / env RDM_DETERMINISTIC): every kernel-selection decision (skinny vs tiled GEMM,
     // halo vs generic conv, conv split-K, the zero-context shortcut) is a function of the PER-SAMPLE layer shape only, so a row's
     // result is bitwise independent of the batch it sits in and of the number of ranks the batch is sharded over
-    bool deterministic = getenv("RDM_DETERMINISTIC") ? atoi(getenv("RDM_DETERMINISTIC")) != 0 : false;
+    bool deterministic = rdm_env_int(getenv("RDM_DETERMINISTIC"), 0) != 0;
     // debug tap (rdm_debug_tap): the output activation of top-level UNet block `tap_block` (NHWC bf16) is copied into tap_buf by the next forward
     void* tap_buf = nullptr; size_t tap_bytes = 0; int tap_block = -1, tap_sub = 0;      // tap_sub: 0 = the block's output, else 16 * layer-in-block + stage (unet_body)
     // RCCL communicator (rdm_comm_*): library handle from dlopen, function table, communicator
@@ -606,30 +587,6 @@ struct Ops {
     void check(hipError_t e, const char* what) {
         if (e != hipSuccess && rc == 0) rc = c->fail(-3, "%s: %s", what, hipGetErrorString(e));
     }
-    // ---- side stream (round 6).  A ResBlock's skip_connection 1x1 conv depends on the block's INPUT only, while the main chain runs
-    // GroupNorm -> conv1 -> GroupNorm before conv2 consumes it as the residual.  Issued on a second (non-blocking) stream at the top of the
-    // block it fills the CUs the persistent conv kernels leave idle in their last, partial round of tiles (16 x 16 level: 384 tiles on
-    // 256 CUs) instead of taking its own slot in the serial chain.  Same kernels, same arithmetic: only the issue order changes.
-    // Opt-in, RDM_SKIP_OVERLAP=1 (resblock): two same-box A/Bs disagree in sign.  side_begin(): launches that follow go to the side stream (ordered after everything issued so far).
-    bool side_begin() {
-        // (not while kernel classes other than the conv are bracketed with events: concurrent side work would be billed to whatever runs beside it)
-        if (plan || (c->prof & ~(1u << RDM_PROF_CONV3X3))) return false;
-        if (!c->side) {
-            if (hipStreamCreateWithFlags(&c->side, hipStreamNonBlocking) != hipSuccess) { c->side = nullptr; return false; }     // (a low-priority stream measured the same: profiles/r06_conv_tail_split_normal_priority_ab.log)
-            if (hipEventCreateWithFlags(&c->ev_fork, hipEventDisableTiming) != hipSuccess || hipEventCreateWithFlags(&c->ev_join, hipEventDisableTiming) != hipSuccess) {
-                (void)hipStreamDestroy(c->side); c->side = nullptr; return false;
-            }
-        }
-        check(hipEventRecord(c->ev_fork, c->stream), "side stream fork");
-        check(hipStreamWaitEvent(c->side, c->ev_fork, 0), "side stream fork");
-        c->side_saved = c->stream; c->stream = c->side;
-        return true;
-    }
-    void side_end() {                                           // back to the main stream; the side work is still in flight
-        check(hipEventRecord(c->ev_join, c->stream), "side stream join");
-        c->stream = c->side_saved;
-    }
-    void side_join() { check(hipStreamWaitEvent(c->stream, c->ev_join, 0), "side stream join"); }     // main stream: wait for the side work
     IgemmParams base(int M, int N, int K) {
         IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.ldo = N; p.zero_page = c->zero_page;
         p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1; return p;
@@ -652,19 +609,19 @@ struct Ops {
         // the ops with ONE row per sample (`single_row`: time embedding, RARM decode step, CLIP projection), at any batch
         // (one-row-per-sample operands of bigger batches -- RARM decode at 128+ sequences per GPU -- keep the skinny kernel: its row
         //  blocks scale with M, while the tiled kernels would run a dozen 256-row tiles)
-        // RDM_SGEMM_MAX_ROWS / RDM_SGEMM_GEGLU_MAX_ROWS (dev): one-row-per-sample operands beyond these row counts take the tiled kernels
-        static const int sg_max = getenv("RDM_SGEMM_MAX_ROWS") ? atoi(getenv("RDM_SGEMM_MAX_ROWS")) : 4096;      // (2048 sequences: 716 -> 780 img/s against the tiled kernels, round 5)
+        // one-row-per-sample operands beyond these row counts take the tiled kernels
+        constexpr int SGEMM_MAX_ROWS = 4096;          // (2048 sequences: 716 -> 780 img/s against the tiled kernels, round 5)
         // (round 5, same box: the GEGLU projection of the RARM decode step through the tiled kernel from ~200 rows on: 397.8 -> 409.5 img/s at 256
         //  sequences, 487.0 -> 514.8 at 512; the plain projections through it: 221 / 305 -- their N = 768 gives the tiled kernel 16-24 tiles)
-        static const int sg_geglu_max = getenv("RDM_SGEMM_GEGLU_MAX_ROWS") ? atoi(getenv("RDM_SGEMM_GEGLU_MAX_ROWS")) : 192;
-        const bool skinny = c->deterministic ? single_row : (M <= 128 || (single_row && M <= (act == ACT_GEGLU ? sg_geglu_max : sg_max)));
+        constexpr int SGEMM_GEGLU_MAX_ROWS = 192;
+        const bool skinny = c->deterministic ? single_row : (M <= 128 || (single_row && M <= (act == ACT_GEGLU ? SGEMM_GEGLU_MAX_ROWS : SGEMM_MAX_ROWS)));
         if (skinny && !A1 && C1 == 0 && !rowvec) {         // N/32 x ceil(M/32) blocks (sgemm.hip)
             SgemmParams q{}; q.A = A0; q.lda = C0; q.W = w<bf16_t>(woff); q.M = M; q.N = N; q.K = C0; q.bias = has_bias ? w<float>(boff) : nullptr;
             q.act = act; q.res_f32 = res_f32; q.res_bf16 = res; q.out_f32 = out_f32; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
             q.fixed_split = c->deterministic ? 1 : 0;
             // 1536+ rows: LDS-staged 64 x 64 tiles (mgemm.hip) -- the skinny kernel's per-wave operand fetch is 75 MB through the L2 -> CU
             // fabric for a [2048 x 768] x [768 x 768] product (33.6 us; 15.5 there).  Not in deterministic mode (the kernel choice would follow the batch).
-            static const int mg_from = getenv("RDM_MGEMM_FROM") ? atoi(getenv("RDM_MGEMM_FROM")) : 1536;
+            static const int mg_from = rdm_env_int(getenv("RDM_MGEMM_FROM"), 1536);     // (tests move it)
             if (!c->deterministic && single_row && mg_from > 0 && M >= mg_from && act != ACT_GEGLU && mgemm_supported(q)) {
                 prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
                 check(launch_mgemm(q, c->stream), "mid-size linear");
@@ -701,44 +658,17 @@ struct Ops {
     // out = act(LayerNorm(x) W^T + bias) with the LayerNorm formed inside the skinny GEMM (sgemm.hip): decode-sized operands only.
     // false = not available for this shape (the caller runs layernorm + linear)
     bool linear_ln(const float* x, size_t g, size_t b, int C, size_t woff, size_t boff, bool has_bias, int M, int N, int act, bf16_t* out) {
-        static const int off = getenv("RDM_NO_LNFUSE") ? atoi(getenv("RDM_NO_LNFUSE")) : 0;
-        static const int ln_max_rows = getenv("RDM_SGEMM_LN_MAX_ROWS") ? atoi(getenv("RDM_SGEMM_LN_MAX_ROWS")) : 192;
         // (from ~200 rows on a separate LayerNorm pass + the 64 x 64-tile GEMM beats the LayerNorm-fused 32-row tiles: sgemm.hip)
-        // (RDM_SGEMM_LN8_FROM=m: the eight-wave 64-row tiles take the LayerNorm themselves from m rows on -- measured slower, off: sgemm.hip)
-        static const int ln8_from = getenv("RDM_SGEMM_LN8_FROM") ? atoi(getenv("RDM_SGEMM_LN8_FROM")) : 0;
-        const bool ln8 = ln8_from > 0 && M >= ln8_from && act != ACT_GEGLU && C == 768;
-        if (!c->deterministic && M > ln_max_rows && !ln8) return false;
+        constexpr int SGEMM_LN_MAX_ROWS = 192;
+        if (!c->deterministic && M > SGEMM_LN_MAX_ROWS) return false;
         const bool skinny = c->deterministic ? single_row : (M <= 128 || (single_row && M <= 1024));
         SgemmParams q{}; q.ln_x = x; q.ln_g = w<float>(g); q.ln_b = w<float>(b); q.ln_eps = 1e-5f; q.W = w<bf16_t>(woff); q.M = M; q.N = N; q.K = C;
         q.bias = has_bias ? w<float>(boff) : nullptr; q.act = act; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
         q.fixed_split = c->deterministic ? 1 : 0;
-        if (off || !skinny || !sgemm_supported(q)) return false;
+        if (!skinny || !sgemm_supported(q)) return false;
         if (plan) return true;
         prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C, M, N, C);
         check(launch_sgemm(q, c->stream), "skinny linear on a LayerNorm");
-        prof_end();
-        return true;
-    }
-    // out = act(LayerNorm(x) W^T + bias) for the big-M projections, with the LayerNorm folded into lin4's GEMM (lin4.hip, <.., LN>): x is
-    // the RAW bf16 tensor, the row statistics are taken inside the kernel.  false = not available for this shape / mode (the caller
-    // runs layernorm + linear).  Clog: logical row width (zero padding beyond it).
-    bool linear_ln_big(const bf16_t* x, size_t g, size_t b, int C, int Clog, size_t woff, size_t boff, bool has_bias, int M, int N, int act, bf16_t* out) {
-        // OFF by default (round 4, measured on the headline bench, same box): 38.50 img/s with the fold against 38.75 without.  The
-        // separate LayerNorm passes it removes are 42 ms of a 1650 ms step; the folded GEMMs cost 52 ms more -- every column block of a
-        // row block repeats the row statistics (64 v_dot2_f32_bf16 per K-slice at ~11 cycles each beside the MFMAs: K loop + 30 %), and
-        // the read-out gains 4 LDS reads + 16 FMAs per 8 outputs (GEGLU read-out + 50 %).  DESIGN.md section 8.  RDM_LNFOLD=1 enables it.
-        static const int on = getenv("RDM_LNFOLD") ? atoi(getenv("RDM_LNFOLD")) : 0;
-        if (!on || c->deterministic) return false;
-        IgemmParams p = base(M, N, C);
-        p.A0 = x; p.C0 = C; p.W = w<bf16_t>(woff); p.act = act; p.out_bf16 = out; if (act == ACT_GEGLU) p.ldo = N / 2;
-        p.ln_inv_c = 1.0f / (float)Clog; p.ln_eps = 1e-5f;
-        IgemmParams t = p; t.Wfrag = p.W; t.ln_sb = (const float*)blob;          // shape check only
-        if (!lin4_supported(t, 1)) return false;
-        if (plan) return true;
-        p.Wfrag = c->frag_for_lin_ln(p.W, N, C, act == ACT_GEGLU, w<float>(g), w<float>(b), has_bias ? w<float>(boff) : nullptr, &p.ln_sb);
-        if (!p.Wfrag) { if (rc == 0) rc = c->fail(-2, "out of memory for a LayerNorm-folded weight copy"); return true; }
-        prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C, M, N, C);
-        check(launch_lin4(p, c->stream), "linear on a folded LayerNorm");
         prof_end();
         return true;
     }
@@ -755,9 +685,8 @@ struct Ops {
         // that are multiples of 256 / HW -- there the generic implicit GEMM (another summation order) runs for EVERY batch; and no
         // split-K (its factor follows the tile count, i.e. the batch)
         // Upsample's conv by output phase: four 2 x 2-tap convs at source resolution on pre-summed weights, 2.25 x fewer FLOPs than the
-        // nine taps at output resolution (igemm.hip CONV == 3).  RDM_NO_UPS_PHASE=1: the fused-upsample halo kernel as before.
-        static const bool no_phase = getenv("RDM_NO_UPS_PHASE") != nullptr;
-        if (ups && !no_phase && !A1 && C1 == 0 && C0 % 64 == 0 && N % 8 == 0 && !rowvec && !res && stride == 1) {
+        // nine taps at output resolution (igemm.hip CONV == 3)
+        if (ups && !A1 && C1 == 0 && C0 % 64 == 0 && N % 8 == 0 && !rowvec && !res && stride == 1) {
             const bf16_t* wp = c->phase_weights_for(p.W, N, C0);
             if (wp) {
                 IgemmParams q = base(B * Hin * Win, N, 4 * C0);
@@ -819,12 +748,11 @@ struct Ops {
     void head(const bf16_t* x, int B, int H, int W, int C, int Clog, size_t g, size_t b, float eps, size_t woff, size_t boff, int Cout,
               float* out, bf16_t* tmp, bf16_t* wp) {
         if (plan) return;
-        static const int off = getenv("RDM_NO_HEADFUSE") ? atoi(getenv("RDM_NO_HEADFUSE")) : 0;
         HeadParams hp{}; hp.x = x; hp.B = B; hp.H = H; hp.W = W; hp.C = C; hp.groups = 32; hp.gamma = w<float>(g); hp.beta = w<float>(b); hp.eps = eps;
         hp.w = w<float>(woff); hp.wp = wp; hp.bias = w<float>(boff); hp.out = out; hp.Cout = Cout;
         int nchunk = H * W / 64; if (nchunk < 1) nchunk = 1; if (nchunk > 32) nchunk = 32;
         hp.partial = c->gn_partial; hp.nchunk = nchunk;
-        if (!off && Clog == C && head_conv_supported(hp)) {
+        if (Clog == C && head_conv_supported(hp)) {
             GnParams p{}; p.x0 = x; p.C0 = C; p.HW = H * W; p.B = B; p.groups = 32; p.L0 = C; p.nchunk = nchunk; p.partial = c->gn_partial;
             prof_begin(RDM_PROF_GROUPNORM, (double)B * H * W * C * 2.0, B * H * W, C, 2);
             check(launch_gn_stats(p, c->stream), "head groupnorm statistics");
@@ -864,8 +792,7 @@ static void unet_compute_kv(Ops& o, UNet& u, const float* context, int B, int k,
 // drops from two C x C projections + an attention kernel (9 tensor passes) to N = 128 / K = 128 GEMMs (3.3 passes); identical
 // in exact arithmetic to rdm/modules/attention.py:52-72 (CrossAttention.forward).
 static bool xattn_skinny_ok(const UNet& u, int k) {
-    static const int off = getenv("RDM_NO_XSKINNY") ? atoi(getenv("RDM_NO_XSKINNY")) : 0;
-    if (off || !(k == 1 || k == 2 || k == 4)) return false;
+    if (!(k == 1 || k == 2 || k == 4)) return false;
     for (const StW& s : u.st) if (s.heads * k > XA_NP || s.c != s.heads * 32) return false;
     return !u.st.empty();
 }
@@ -948,7 +875,6 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
     };
     // Skip tensors pushed inside the prefix are NOT duplicated when their readers can wrap the batch index instead (GroupNorm's and the
     // skip_connection GEMM's second source: 4 of the 5 copies, 0.24 ms of a 34.5 ms forward); resblock() materialises one on demand.
-    static const int no_wrap = getenv("RDM_NO_SKIPWRAP") ? atoi(getenv("RDM_NO_SKIPWRAP")) : 0;
 
     auto resblock = [&](const ResW& r, const Act& a, Act* skip) -> Act {
         const int C0 = a.C, C1 = skip ? skip->C : 0, HW = a.H * a.W, M = B * HW;
@@ -959,16 +885,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
             else expand(*skip);
         }
         const bf16_t* x1 = skip ? skip->p : nullptr;
-        // skip_connection first, on the side stream (Ops::side_begin): it needs the block's input only
+        // skip_connection first: it needs the block's input only.  (Issuing it on a second stream, to fill the CUs the conv kernels leave
+        // idle in their last round, measured + 0.45 % on one box and - 0.25 % on another in round 6 (profiles/r06_skip_overlap_ab*.log): removed.)
         const bf16_t* res = a.p;
-        bf16_t* sk = nullptr; bool forked = false;
+        bf16_t* sk = nullptr;
         if (r.skip) {
             sk = o.abf((size_t)M * r.cout);
             o.tag = "res.skip";
-            static const int skip_on = getenv("RDM_SKIP_OVERLAP") ? atoi(getenv("RDM_SKIP_OVERLAP")) : 0;     // opt-in: + 0.45 % on one box, - 0.25 % on another (profiles/r06_skip_overlap_ab*.log)
-            forked = skip_on && o.side_begin();
             o.linear(a.p, x1, C0, C1, r.wsk, r.bsk, true, M, r.cout, ACT_NONE, nullptr, sk, nullptr, nullptr, wrap_b * HW);
-            if (forked) o.side_end();
             res = sk;
         }
         bf16_t* n1 = o.abf((size_t)M * r.cin);
@@ -983,7 +907,6 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         o.tag = "res.gn2";
         o.groupnorm(h1, nullptr, r.cout, 0, B, HW, r.gn2g, r.gn2b, 1e-5f, 1, n2, r.lout, 0);
         o.tap(3, n2, (size_t)M * r.cout * 2);
-        if (forked) o.side_join();
         if (r.skip) o.tap(4, sk, (size_t)M * r.cout * 2);
         bf16_t* out = o.abf((size_t)Bfull * HW * r.cout);           // Bfull: see expand()
         o.tag = "res.conv2";
@@ -1010,17 +933,13 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         // n % 64 == 0: q | k | v in ONE projection (to_v's rows follow to_q | to_k in the blob, asserted in build_unet); the flash kernel
         // reads the token-major V block through transpose reads, so no per-layer V^T GEMM (6.8 % of the forward as a batched
         // weights-as-A GEMM at 380 TFLOP/s)
-        static const int no_vrow = getenv("RDM_NO_VROW") ? atoi(getenv("RDM_NO_VROW")) : 0;
-        const bool vrow = (n % 64 == 0) && !no_vrow && s.v_follows;
+        const bool vrow = (n % 64 == 0) && s.v_follows;
         const int QW = vrow ? 3 * C : 2 * C;
         bf16_t* qk = o.abf((size_t)M * QW);
         o.tag = "st.norm1+qkv";
-        // norm1 folded into the q | k | v projection where lin4 takes it (only the fused form: the other paths read l1 again)
-        if (!(vrow && o.linear_ln_big(t0, s.ln1g, s.ln1b, C, s.lc, s.wqk, 0, false, M, QW, ACT_NONE, qk))) {
-            o.layernorm(t0, 0, s.ln1g, s.ln1b, l1, 0, M, C, s.lc);
-            o.tap(3, l1, (size_t)M * C * 2);
-            o.linear(l1, nullptr, C, 0, s.wqk, 0, false, M, QW, ACT_NONE, nullptr, qk);
-        }
+        o.layernorm(t0, 0, s.ln1g, s.ln1b, l1, 0, M, C, s.lc);
+        o.tap(3, l1, (size_t)M * C * 2);
+        o.linear(l1, nullptr, C, 0, s.wqk, 0, false, M, QW, ACT_NONE, nullptr, qk);
         o.tap(4, qk, (size_t)M * QW * 2);
         bf16_t* ao = o.abf((size_t)M * C);
         o.tag = "st.self_attention";
@@ -1063,11 +982,8 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         //     values of those rows: Ops::linear's rowvec; one rounding less than t1 -> + b_o2), no add_bias_rows pass;
         //   * the cross-attention kernel runs IN PLACE on the conditional rows (t2 aliases t1) and emits norm3 of its finished rows, so
         //     the separate LayerNorm-3 pass only covers the unconditional rows.
-        // RDM_NO_XFOLD=1: the separate passes as before.
-        static const int no_xfold = getenv("RDM_NO_XFOLD") ? atoi(getenv("RDM_NO_XFOLD")) : 0;
-        static const int no_xfused_env = getenv("RDM_NO_XFUSED") ? atoi(getenv("RDM_NO_XFUSED")) : 0;
         XattnParams xq{}; xq.rows = Mx; xq.n = n; xq.C = C; xq.NP = XA_NP; xq.ncols = s.heads * k; xq.group = k;
-        const bool xfold_shape = xa && Mx > 0 && !no_xfused_env && s.lc == C && C <= 2048 && xattn_fused_supported(xq) && !no_xfold && !o.c->deterministic;       // => xfused && xln below
+        const bool xfold_shape = xa && Mx > 0 && s.lc == C && C <= 2048 && xattn_fused_supported(xq) && !o.c->deterministic;       // => xfused && xln below
         const bool bias_fold = xfold_shape && Bx * 2 == B;             // the unconditional half exists and is exactly the second half
         o.tag = "st.attn1.to_out";
         if (bias_fold) {
@@ -1081,15 +997,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         o.tag = "st.norm2+attn2";
         bf16_t* l2 = o.abf((size_t)M * C);
         // norm2 + attn2 + residual in one kernel when the neighbours' operands are cached (xa) and no channel is padding
-        static const int no_xfused = getenv("RDM_NO_XFUSED") ? atoi(getenv("RDM_NO_XFUSED")) : 0;       // 1: two GEMMs; 2: fused without the LayerNorm
         XattnParams xp{};
         if (xa && Mx > 0) {
             const bf16_t* G = xa + (size_t)B * s.xa_unit; const bf16_t* U = G + (size_t)B * XA_NP * C;
             xp.x = l2; xp.G = U + (size_t)B * C * XA_NP; xp.U = xp.G + (size_t)B * XA_NP * C; xp.bias = o.w<float>(s.bo2); xp.res = t1; xp.out = nullptr;
             xp.rows = Mx; xp.n = n; xp.C = C; xp.NP = XA_NP; xp.ncols = s.heads * k; xp.group = k;
         }
-        const bool xfused = xa && Mx > 0 && no_xfused != 1 && xattn_fused_supported(xp);
-        const bool xln = xfused && no_xfused != 2 && s.lc == C && C <= 2048;
+        const bool xfused = xa && Mx > 0 && xattn_fused_supported(xp);
+        const bool xln = xfused && s.lc == C && C <= 2048;
         if (Mx > 0 && !xln) o.layernorm(t1, 0, s.ln2g, s.ln2b, l2, 0, Mx, C, s.lc);
         bf16_t* t2 = xfold_shape ? t1 : o.abf((size_t)M * C);
         bf16_t* l3 = o.abf((size_t)M * C);
@@ -1141,24 +1056,17 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         if (xfold_shape) {       // norm3 of the conditional rows left the cross-attention kernel; the unconditional rows' here
             if (M > Mx) o.layernorm(t2 + (size_t)Mx * C, 0, s.ln3g, s.ln3b, l3 + (size_t)Mx * C, 0, M - Mx, C, s.lc);
             o.linear(l3, nullptr, C, 0, s.wff1, s.bff1, true, M, 2 * FI, ACT_GEGLU, nullptr, ff);
-        } else if (!o.linear_ln_big(t2, s.ln3g, s.ln3b, C, s.lc, s.wff1, s.bff1, true, M, 2 * FI, ACT_GEGLU, ff)) {       // norm3 folded into the GEGLU projection
+        } else {
             o.layernorm(t2, 0, s.ln3g, s.ln3b, l3, 0, M, C, s.lc);
             o.linear(l3, nullptr, C, 0, s.wff1, s.bff1, true, M, 2 * FI, ACT_GEGLU, nullptr, ff);
         }
-        o.tap(8, l3, (size_t)M * C * 2);          // (only where a separate norm3 tensor exists: not with RDM_LNFOLD)
+        o.tap(8, l3, (size_t)M * C * 2);
         o.tap(9, ff, (size_t)M * FI * 2);
         bf16_t* out = o.abf((size_t)M * C);
         o.tag = "st.ff2*proj_out";
-        static const int no_ffout = getenv("RDM_NO_FFOUT") ? atoi(getenv("RDM_NO_FFOUT")) : 0;
-        if (!no_ffout) {
-            // t3 = ff W_2^T + b_2 + t2 and out = t3 W_out^T + b_out + x are one GEMM over the K-concatenated operand [ff | t2]
-            // (dual-source A) with the product weights built by the packer: t3 never exists (2 of 9 tensor passes, one launch)
-            o.linear(ff, t2, FI, C, s.wfo, s.bfo, true, M, C, ACT_NONE, a.p, out, nullptr, nullptr, 0, nullptr, 0, 1, in_wrap * n);
-        } else {
-            bf16_t* t3 = o.abf((size_t)M * C);
-            o.linear(ff, nullptr, FI, 0, s.wff2, s.bff2, true, M, C, ACT_NONE, t2, t3);
-            o.linear(t3, nullptr, C, 0, s.wout, s.bout, true, M, C, ACT_NONE, a.p, out);
-        }
+        // t3 = ff W_2^T + b_2 + t2 and out = t3 W_out^T + b_out + x are one GEMM over the K-concatenated operand [ff | t2]
+        // (dual-source A) with the product weights built by the packer: t3 never exists (2 of 9 tensor passes, one launch)
+        o.linear(ff, t2, FI, C, s.wfo, s.bfo, true, M, C, ACT_NONE, a.p, out, nullptr, nullptr, 0, nullptr, 0, 1, in_wrap * n);
         o.tap(10, out, (size_t)M * C * 2);
         return Act{out, C, a.H, a.W, s.lc};
     };
@@ -1180,14 +1088,11 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                     if (B < Bfull) {       // first context-dependent layer: leave the shared prefix
                         {   // the activation itself is duplicated only where its readers cannot wrap the batch index instead (transformer())
                             const StW& s0 = u.st[L.idx];
-                            static const int no_inwrap = getenv("RDM_NO_INWRAP") ? atoi(getenv("RDM_NO_INWRAP")) : 0;
-                            static const int no_ffout_env = getenv("RDM_NO_FFOUT") ? atoi(getenv("RDM_NO_FFOUT")) : 0;
                             const int n0 = h.H * h.W, Mfull = Bfull * n0;
-                            if (!no_inwrap && !no_wrap && !no_ffout_env && !o.c->deterministic &&
-                                o.lin4_takes(Mfull, s0.c, 4 * s0.lc, s0.c, 0, (Bfull / 2) * n0)) h.half = true;
+                            if (!o.c->deterministic && o.lin4_takes(Mfull, s0.c, 4 * s0.lc, s0.c, 0, (Bfull / 2) * n0)) h.half = true;
                             else expand(h);
                         }
-                        for (Act& a : hs) { if (no_wrap || o.c->deterministic) expand(a); else a.half = true; }
+                        for (Act& a : hs) { if (o.c->deterministic) expand(a); else a.half = true; }
                         B = Bfull;
                     }
                     h = transformer(u.st[L.idx], h); break;
@@ -1524,11 +1429,9 @@ void rdm_ctx_destroy(rdm_ctx* c) {
     if (c->comm) rdm_comm_destroy(c);
     DevGuard guard(c->device);
     hipDeviceSynchronize();
-    // (the side stream and its two events are left to the runtime: a context may be destroyed from a finaliser at interpreter shutdown, and tearing
-    //  streams down there is not worth one lost handle per context)
     void* ptrs[] = {c->zero_page, c->unet.blob, c->unet.arena.base, c->unet.kv_cache, c->vq.blob, c->vq.arena.base,
                     c->clip.blob, c->clip.arena.base, c->gn_partial, c->samp, c->splitk_ws, c->unet.xa_cache,
-                    c->rarm.blob, c->rarm.arena.base, c->rarm.cache, c->rarm.ctxkv, c->rarm.state, c->rarm.xa, c->rarm.xws, c->wfrag_tmp, c->bwd_tmp,
+                    c->rarm.blob, c->rarm.arena.base, c->rarm.cache, c->rarm.ctxkv, c->rarm.state, c->rarm.xa, c->wfrag_tmp, c->bwd_tmp,
                     c->vqenc.blob, c->vqenc.arena.base, c->eye3, c->unet.emb_table};
     for (void* p : ptrs) if (p) hipFree(p);
     c->drop_frags();
@@ -1682,7 +1585,6 @@ static int prepare_kv(rdm_ctx* c, const float* cond, const float* uncond, int B,
     if (skinny) RDM_TRY(ensure_bytes(c, (char**)&u.xa_cache, &u.xa_cache_bytes, (size_t)nb * u.xa_total * 2));
     u.ctx_rows = nb;
     if (uncond) {      // how many trailing samples have all-zero neighbours?  (one small kernel + one 4*nb-byte read per sampling call)
-        static const int off = getenv("RDM_NO_ZEROCTX") ? atoi(getenv("RDM_NO_ZEROCTX")) : 0;
         std::vector<int> flags(nb, 1);
         int* dflags = (int*)c->gn_partial;             // scratch: >= 16 KB once any forward ran; make sure it exists
         RDM_TRY(ensure_gn_partial(c, nb));
@@ -1692,7 +1594,7 @@ static int prepare_kv(rdm_ctx* c, const float* cond, const float* uncond, int B,
         RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
         int rows = nb;
         while (rows > 0 && flags[rows - 1] == 0) rows--;
-        if (!off && !c->deterministic) u.ctx_rows = rows;     // (which rows are "trailing" depends on the batch)
+        if (!c->deterministic) u.ctx_rows = rows;     // (which rows are "trailing" depends on the batch)
     }
     return run_with_arena(c, u.arena, u.blob, [&](Ops& o) {
         unet_compute_kv(o, u, cat, nb, k, u.kv_cache);
@@ -1746,13 +1648,11 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
     }
     RDM_CHECK_HIP(c, hipMemcpyAsync(x2, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
     int n_logged = 0;
-    static const int share_prefix = getenv("RDM_NO_SHARED_PREFIX") ? !atoi(getenv("RDM_NO_SHARED_PREFIX")) : 1;
     // Every sample of a step shares the step's timestep, and the S timesteps are known now: their time-embedding rows (MLP + the 22 emb_layers)
     // are computed ONCE per call as S-row GEMMs into a table, instead of three B-row GEMMs per forward (72 us of a 29 ms forward).  Not in
     // deterministic mode (the rows must come out of the same kernel configuration as rdm_unet_forward's).
-    static const int no_emb_table = getenv("RDM_NO_EMB_TABLE") ? atoi(getenv("RDM_NO_EMB_TABLE")) : 0;
     const float* emb_table = nullptr;
-    if (!no_emb_table && !c->deterministic) {
+    if (!c->deterministic) {
         RDM_TRY(ensure_bytes(c, (char**)&u.emb_table, &u.emb_table_bytes, (size_t)total * u.emb_total * 4 + (size_t)total * 8 + 256));
         long long* tuniq = (long long*)((char*)u.emb_table + (((size_t)total * u.emb_total * 4 + 255) & ~(size_t)255));
         std::vector<long long> th(ts.begin(), ts.end());
@@ -1765,7 +1665,7 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
         const int index = total - i - 1;
         if (cfg && i == 0) RDM_CHECK_HIP(c, hipMemcpyAsync(x2 + n1, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));   // later steps: ddim_step writes both halves
         RDM_TRY(unet_forward_impl(c, x2, (const int64_t*)(tdev + (size_t)index * nb), nullptr, u.kv_cache, nb, k, a->height, a->width, eps, u.ctx_rows,
-                                  share_prefix && cfg ? B : 0, emb_table ? emb_table + (size_t)index * u.emb_total : nullptr));     // [x | x], same t: the context-independent prefix runs once
+                                  cfg ? B : 0, emb_table ? emb_table + (size_t)index * u.emb_total : nullptr));     // [x | x], same t: the context-independent prefix runs once
         const bool log = (index % a->log_every_t == 0) || (index == total - 1);
         DdimStepParams p{};
         p.x = x2; p.eps = eps; p.noise = (noise && a->eta != 0.f) ? noise + (size_t)i * n1 : nullptr;
@@ -1806,9 +1706,8 @@ int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const 
     }
     RDM_CHECK_HIP(c, hipMemcpyAsync(x, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
     // the T timesteps' time-embedding rows once per call (as rdm_ddim_sample: every sample of a step shares the step's timestep)
-    static const int no_emb_table = getenv("RDM_NO_EMB_TABLE") ? atoi(getenv("RDM_NO_EMB_TABLE")) : 0;
     const float* emb_table = nullptr;
-    if (!no_emb_table && !c->deterministic) {
+    if (!c->deterministic) {
         RDM_TRY(ensure_bytes(c, (char**)&u.emb_table, &u.emb_table_bytes, (size_t)T * u.emb_total * 4 + (size_t)T * 8 + 256));
         long long* tuniq = (long long*)((char*)u.emb_table + (((size_t)T * u.emb_total * 4 + 255) & ~(size_t)255));
         std::vector<long long> th((size_t)T);
@@ -1835,9 +1734,9 @@ int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const 
 // Samples per decoder pass.  Decoding is per sample (GroupNorm statistics included), so a batch may be walked in ranges; a range is
 // sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo convs address an operand through
 // 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the seven 128-channel convs of
-// the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).  RDM_VQ_RANGE overrides.
+// the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).  RDM_VQ_RANGE overrides (tests).
 static int vq_range(const VqModel& v, int b) {
-    static const int env = getenv("RDM_VQ_RANGE") ? atoi(getenv("RDM_VQ_RANGE")) : 0;
+    static const int env = rdm_env_int(getenv("RDM_VQ_RANGE"), 0);
     if (env > 0) return env < b ? env : b;
     const rdm_vq_cfg& c = v.cfg;
     long long per = 1;
@@ -1954,22 +1853,16 @@ static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,c
     // neighbours' keys / values of every layer in one GEMM; the unconditional half of a guided batch attends to ZERO neighbours
     // (transformer.py:237-239), whose projections are zero (to_k / to_v have no bias)
     RDM_CHECK_HIP(c, hipMemsetAsync(m.ctxkv, 0, (size_t)B2 * k * m.kv_total * 2, c->stream));
-    static const int no_xf = getenv("RDM_NO_RARM_XFUSED") ? atoi(getenv("RDM_NO_RARM_XFUSED")) : 0;
     // Round 5: the per-sequence re-association pays per-sequence operands (G and U^T: 2 x 128 x C bf16 = 393 KB per sequence and layer
     // where the projections' weights are 2.4 MB per layer for ALL sequences): the one-launch form wins while launches are the cost
-    // (<= 128 sequences); from RDM_RARM_XGEMM_FROM sequences on (default 384) the decode step takes norm2 + to_q as a GEMM, the k-key attention
-    // and to_out + residual as a GEMM (same box, profiles/r05_rarm_sweep.log: 256 sequences 399 img/s fused vs 378 as GEMMs, 512 sequences 484 vs 489).
-    static const int xgemm_from = getenv("RDM_RARM_XGEMM_FROM") ? atoi(getenv("RDM_RARM_XGEMM_FROM")) : 384;
-    const bool fuse = !no_xf && g.n_heads * k <= 128 && C <= 1024 && C % 64 == 0 && (c->deterministic || B2 < xgemm_from);
+    // (<= 128 sequences); from RARM_XGEMM_FROM sequences on the decode step takes norm2 + to_q as a GEMM, the k-key attention and to_out +
+    // residual as a GEMM (same box, profiles/r05_rarm_sweep.log: 256 sequences 399 img/s fused vs 378 as GEMMs, 512 sequences 484 vs 489).
+    constexpr int RARM_XGEMM_FROM = 384;
+    const bool fuse = g.n_heads * k <= 128 && C <= 1024 && C % 64 == 0 && (c->deterministic || B2 < RARM_XGEMM_FROM);
     m.xa_B = 0; m.xa_k = 0;
     if (fuse) {
         RDM_TRY(ensure_bytes(c, &m.xa, &m.xa_bytes, (size_t)g.depth * 2 * B * 128 * C * 2));
         m.xa_B = B; m.xa_k = k;
-        // partial rows as 8-byte {value, epoch} granules + one monotonic arrival counter per sequence; zeroed per sampling call (tag 0 = never
-        // written; counters restart at a multiple of four)
-        const size_t pbytes = ((size_t)B2 * 4 * C * 8 + 255) & ~(size_t)255;
-        RDM_TRY(ensure_bytes(c, &m.xws, &m.xws_bytes, pbytes + (size_t)B2 * 4));
-        RDM_CHECK_HIP(c, hipMemsetAsync(m.xws, 0, pbytes + (size_t)B2 * 4, c->stream));
     }
     return run_with_arena(c, m.arena, m.blob, [&](Ops& o) {
         bf16_t* cb = o.abf((size_t)B * k * g.context_dim);
@@ -2010,8 +1903,7 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
         bf16_t* q2 = o.abf((size_t)B2 * C); bf16_t* ff = o.abf((size_t)B2 * 4 * C);
         if (!o.plan) o.check(launch_rarm_embed(st.tokens, o.w<float>(m.emb), o.w<float>(m.pos), st.pos, x, B2, C, g.vocab_in, c->stream), "rarm embed");
         const float scale = 1.0f / sqrtf((float)g.d_head);
-        static const int no_ln3 = getenv("RDM_NO_RARM_LN3") ? atoi(getenv("RDM_NO_RARM_LN3")) : 0;
-        const bool ln3_fused = !no_ln3 && m.xa_B > 0 && m.xa_k == k;      // the fused cross-attention kernel also emits norm3 of its output rows
+        const bool ln3_fused = m.xa_B > 0 && m.xa_k == k;      // the fused cross-attention kernel also emits norm3 of its output rows
         for (int l = 0; l < g.depth; l++) {
             const RarmBlk& b = m.blk[l];
             if (!o.linear_ln(x, b.ln1g, b.ln1b, C, b.wqkv, 0, false, B2, 3 * C, ACT_NONE, qkv)) {
@@ -2021,11 +1913,10 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
             if (!o.plan) {
                 RarmAttnParams p{}; p.q = qkv; p.ldq = 3 * C; p.k_new = qkv + C; p.v_new = qkv + 2 * C;
                 p.Kc = (bf16_t*)m.cache + ((size_t)l * 2) * B2 * L * C; p.Vc = (bf16_t*)m.cache + ((size_t)l * 2 + 1) * B2 * L * C;
-                p.batch_stride = (long long)L * C; p.row_stride = C; p.nkv = L; p.pos = st.pos; p.scale = scale; p.out = ao; p.ldo = C;
+                p.batch_stride = (long long)L * C; p.nkv = L; p.pos = st.pos; p.scale = scale; p.out = ao; p.ldo = C;
                 // Head-major cache [B][head][L][64] (round 5): a (head, sequence) block reads ONE contiguous run of (pos + 1) x 128 bytes
                 // instead of 128-byte pieces 2 C bytes apart.  The cache is private to this kernel (it appends the new row itself).
-                static const int rowmajor = getenv("RDM_RARM_CACHE_ROWMAJOR") ? atoi(getenv("RDM_RARM_CACHE_ROWMAJOR")) : 0;
-                if (!rowmajor) { p.row_stride = g.d_head; p.head_stride = (long long)L * g.d_head; }
+                p.row_stride = g.d_head; p.head_stride = (long long)L * g.d_head;
                 // bytes of the K / V cache rows this step reads (positions 0 .. pos): what bounds the launch at big batches
                 o.tag = "rarm.cache_attention";
                 o.prof_begin(RDM_PROF_ATTENTION, pos_hint >= 0 ? (double)B2 * (pos_hint + 1) * C * 4.0 : 0.0, B2, pos_hint + 1, C);
@@ -2038,9 +1929,6 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
                     RarmXattnParams xp{}; xp.x = x; xp.ln_g = o.w<float>(b.ln2g); xp.ln_b = o.w<float>(b.ln2b); xp.ln_eps = 1e-5f;
                     xp.G = (const bf16_t*)m.xa + ((size_t)l * 2) * m.xa_B * 128 * C; xp.UT = xp.G + (size_t)m.xa_B * 128 * C;
                     xp.bias = o.w<float>(b.bo2); xp.B2 = B2; xp.Bc = m.xa_B; xp.C = C; xp.NP = 128; xp.heads = g.n_heads; xp.k = k;
-                    xp.ws = (float*)m.xws; xp.ws_count = (int*)(m.xws + ((((size_t)B2 * 4 * C * 8) + 255) & ~(size_t)255));
-                    if (++m.xepoch == 0u) m.xepoch = 1u;                 // unique per launch, never 0
-                    xp.epoch = m.xepoch; xp.no_split = c->deterministic ? 1 : 0;
                     if (ln3_fused) { xp.ln3_g = o.w<float>(b.ln3g); xp.ln3_b = o.w<float>(b.ln3b); xp.ln3_out = ln; }
                     o.check(launch_rarm_xattn_decode(xp, c->stream), "rarm fused cross attention");
                 }
@@ -2282,27 +2170,6 @@ int rdm_prof_dump(rdm_ctx* c, const char* path) {
     fclose(f);
     return 0;
 }
-int rdm_op_ffn_fused(rdm_ctx* c, const void* l3, const void* t2, const void* xin, const void* w1, const float* b1, const void* wf, const float* bf,
-                     void* out, int M, int C) {
-    RDM_ENTER(c);
-    if (!l3 || !t2 || !xin || !w1 || !b1 || !wf || !bf || !out) return c->fail(-1, "rdm_op_ffn_fused: null argument");
-    if (!ffn_fused_supported(M, C)) return c->fail(-5, "rdm_op_ffn_fused: C = 384 and M %% 128 == 0 only (M = %d, C = %d)", M, C);
-    RDM_TRY(ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, ffn_fused_scratch_bytes(C)));
-    static const int op_cache = getenv("RDM_OP_FRAG_CACHE") ? atoi(getenv("RDM_OP_FRAG_CACHE")) : 0;     // dev-only (tools/ffn_bench.py): the caller promises constant weights
-    static const void* last_w1 = nullptr; static const void* last_wf = nullptr; static const void* last_buf = nullptr;
-    const bool repack = !(op_cache && last_w1 == w1 && last_wf == wf && last_buf == c->wfrag_tmp);
-    RDM_CHECK_HIP(c, launch_ffn_fused((const bf16_t*)l3, (const bf16_t*)t2, (const bf16_t*)xin, (const bf16_t*)w1, b1, (const bf16_t*)wf, bf, (bf16_t*)out, M, C,
-                                      c->wfrag_tmp, repack, c->stream));
-    last_w1 = w1; last_wf = wf; last_buf = c->wfrag_tmp;
-    return 0;
-}
-int rdm_debug_counter(rdm_ctx* c, int which, unsigned long long* value) {
-    RDM_ENTER(c);
-    if (!value) return c->fail(-1, "rdm_debug_counter: null argument");
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    if (which == 0) { *value = rarm_xsplit_stale_count(); return 0; }
-    return c->fail(-2, "rdm_debug_counter: unknown counter %d", which);
-}
 // Box calibration (calib.hip): fixed probes, independent of every product kernel.  buf: caller's device scratch.
 int rdm_calib_probe(rdm_ctx* c, void* buf, size_t buf_bytes, double mfma_ms, size_t stream_bytes, int stream_reps, double* mfma_tflops, double* stream_gbps) {
     RDM_ENTER(c);
@@ -2343,7 +2210,7 @@ static int op_linear_impl(rdm_ctx* c, const void* a, const void* w, const float*
         q.res_bf16 = (const bf16_t*)res; q.out_f32 = out_f32; q.out_bf16 = (bf16_t*)out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
         if (sgemm_supported(q)) { RDM_CHECK_HIP(c, launch_sgemm(q, c->stream)); return 0; }
     }
-    static const int mg_any = getenv("RDM_MGEMM_ANY") ? atoi(getenv("RDM_MGEMM_ANY")) : 0;      // dev / tests: plain ops of >= mg_any rows on the mid-size GEMM (mgemm.hip)
+    static const int mg_any = rdm_env_int(getenv("RDM_MGEMM_ANY"), 0);      // tests: plain ops of >= mg_any rows on the mid-size GEMM (mgemm.hip)
     if (mg_any > 0 && M >= mg_any && alpha == 1.0f && !rowvec && act != ACT_GEGLU) {
         SgemmParams q{}; q.A = (const bf16_t*)a; q.lda = K; q.W = (const bf16_t*)w; q.M = M; q.N = N; q.K = K; q.bias = bias; q.act = act;
         q.res_bf16 = (const bf16_t*)res; q.out_f32 = out_f32; q.out_bf16 = (bf16_t*)out; q.ldo = N;
@@ -2357,7 +2224,7 @@ static int op_linear_impl(rdm_ctx* c, const void* a, const void* w, const float*
     {
         IgemmParams t = p; t.Wfrag = p.W;
         if (!c->deterministic && lin4_supported(t, 1)) {
-            static const int op_cache = getenv("RDM_OP_FRAG_CACHE") ? atoi(getenv("RDM_OP_FRAG_CACHE")) : 0;   // dev-only: the caller promises constant weights
+            static const int op_cache = rdm_env_int(getenv("RDM_OP_FRAG_CACHE"), 0);   // op benchmarks (tools/lin_bench.py): the caller promises constant weights
             if (op_cache) p.Wfrag = c->frag_for_lin(p.W, N, K, act == ACT_GEGLU);
             else {
                 RDM_TRY(ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, (size_t)N * K * 2));
@@ -2400,8 +2267,7 @@ int rdm_op_conv3x3(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, c
     p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.stride = stride; p.ups = ups;
     p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = Hout * Wout; p.res_bf16 = (const bf16_t*)res; p.out_bf16 = (bf16_t*)out;
     {   // the fused-upsample conv by output phase (as Ops::conv3 runs it inside the models); the phase weights are rebuilt per call
-        static const bool no_phase = getenv("RDM_NO_UPS_PHASE") != nullptr;
-        if (ups && !no_phase && !x1 && C1 == 0 && C0 % 64 == 0 && N % 8 == 0 && !rowvec && !res && stride == 1) {
+        if (ups && !x1 && C1 == 0 && C0 % 64 == 0 && N % 8 == 0 && !rowvec && !res && stride == 1) {
             RDM_TRY(ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, (size_t)16 * N * C0 * 2));
             RDM_CHECK_HIP(c, launch_conv_phase_weights(p.W, (bf16_t*)c->wfrag_tmp, N, C0, c->stream));
             IgemmParams q{}; q.M = B * Hin * Win; q.N = N; q.K = 4 * C0; q.alpha = 1.f; q.ldo = N; q.zero_page = c->zero_page;
@@ -2415,7 +2281,7 @@ int rdm_op_conv3x3(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, c
     if (det_generic) { RDM_CHECK_HIP(c, launch_igemm(p, true, 1, c->stream)); return 0; }
     const int ks = c->deterministic ? 1 : conv_halo_ksplit(p);
     if (ks > 1) { RDM_TRY(ensure_bytes(c, &c->splitk_ws, &c->splitk_ws_bytes, (size_t)ks * p.M * N * 4)); p.ksplit = ks; p.ws = (float*)c->splitk_ws; }
-    static const int op_cache = getenv("RDM_OP_FRAG_CACHE") ? atoi(getenv("RDM_OP_FRAG_CACHE")) : 0;     // dev-only (tools/conv_bench.py): the caller promises constant weights
+    static const int op_cache = rdm_env_int(getenv("RDM_OP_FRAG_CACHE"), 0);     // op benchmarks (tools/conv_bench.py): the caller promises constant weights
     const bool halo = conv_halo_supported(p) || conv_halo4_strip_supported(p);
     if (halo && op_cache) p.Wfrag = c->frag_for(p.W, N, C0 + C1);
     else if (halo) {

@@ -9,7 +9,6 @@
 // depend on scheduling, so batch sharding over GPUs is bit-reproducible); (2) an elementwise
 // normalise+affine(+SiLU) pass that folds (mean, rstd, gamma, beta) into one per-channel FMA held in
 // LDS.  Both passes read the decoder's skip-concat as two source tensors (never materialised).
-#include <stdlib.h>
 
 #include <type_traits>
 
@@ -36,7 +35,7 @@ __global__ void gn_stats_kernel(GnParams p) {
     const int C = p.C0 + p.C1, VC = C >> 3;
     const int R = blockDim.x / VC;
     const int v = threadIdx.x % VC, rr = threadIdx.x / VC;
-    const int b = blockIdx.y + p.b0, chunk = blockIdx.x;
+    const int b = blockIdx.y, chunk = blockIdx.x;
     const int rows_per = (p.HW + p.nchunk - 1) / p.nchunk;
     const int r0 = chunk * rows_per, r1 = min(p.HW, r0 + rows_per);
     float s[8], q[8];
@@ -91,7 +90,7 @@ __global__ void gn_apply_kernel(GnParams p) {
     const int C = p.C0 + p.C1, VC = C >> 3, cg = (p.L0 + p.L1) / p.groups;
     const int R = blockDim.x / VC;
     const int v = threadIdx.x % VC, rr = threadIdx.x / VC;
-    const int b = blockIdx.y + p.b0;
+    const int b = blockIdx.y;
     __shared__ float gstat[64][2];
     if (threadIdx.x < p.groups) {
         double a = 0.0, q = 0.0;
@@ -246,11 +245,10 @@ __global__ __launch_bounds__(T) void gn_onepass_kernel(GnParams p, int gpb, int 
 
 // slice geometry of the one-pass form for this shape, or false (the two-pass kernels run)
 static bool gn_onepass_plan(const GnParams& p, int& gpb, int& T, int& nv) {
-    static const int off = getenv("RDM_NO_GN1PASS") ? atoi(getenv("RDM_NO_GN1PASS")) : 0;
-    static const int max_hw = getenv("RDM_GN1PASS_MAXHW") ? atoi(getenv("RDM_GN1PASS_MAXHW")) : 1024;
-    static const int min_seg = getenv("RDM_GN1PASS_MINSEG") ? atoi(getenv("RDM_GN1PASS_MINSEG")) : 96;      // bytes of a pixel row per slice
+    constexpr int GN1PASS_MAXHW = 1024;
+    constexpr int GN1PASS_MINSEG = 96;         // bytes of a pixel row per slice
     const int C = p.C0 + p.C1;
-    if (off || p.L0 != p.C0 || p.L1 != p.C1 || C % p.groups || p.HW > max_hw || p.HW < 1) return false;      // (padded widths: two-pass)
+    if (p.L0 != p.C0 || p.L1 != p.C1 || C % p.groups || p.HW > GN1PASS_MAXHW || p.HW < 1) return false;      // (padded widths: two-pass)
     const int cg = C / p.groups;
     // groups per block: slices of whole 16-byte vectors (C0 % 8 == 0, so no vector straddles the x0 | x1 boundary), at least min_seg bytes
     // of every pixel row, and registers for it: T / VS pixel lanes x NV <= 32 (16 at 1024 threads) vectors each.  Among the feasible
@@ -259,20 +257,17 @@ static bool gn_onepass_plan(const GnParams& p, int& gpb, int& T, int& nv) {
     const long long want = (long long)p.HW * C / 4;
     long long best_d = -1;
     for (int g = 1; g <= p.groups; g++) {
-        if (p.groups % g || (g * cg) % 8 || g * cg * 2 < min_seg) continue;
+        if (p.groups % g || (g * cg) % 8 || g * cg * 2 < GN1PASS_MINSEG) continue;
         const int VS = g * cg / 8;
         int t_ok = 0, n_ok = 0;
         for (int t : {256, 512, 1024}) {
             if (VS > t) continue;
             const int R = t / VS, n = (p.HW + R - 1) / R;
-            // (1024 threads: 128 registers each; 512 threads: 256 each -- RDM_GN1PASS_NV512=52 admits 52 vectors per thread there: the 64 x 64
-            //  level's 8-group slices of 192 / 384-channel tensors, 96-byte row segments, with RDM_GN1PASS_MAXHW=4096; round 6 experiment)
-            static const int nv512 = getenv("RDM_GN1PASS_NV512") ? atoi(getenv("RDM_GN1PASS_NV512")) : 32;
-            if (n <= (t == 1024 ? 16 : t == 512 ? nv512 : 32)) { t_ok = t; n_ok = n; break; }
+            if (n <= (t == 1024 ? 16 : 32)) { t_ok = t; n_ok = n; break; }      // 1024 threads: 128 registers each
         }
         if (!t_ok) continue;
         const long long el = (long long)g * cg * p.HW, dist = el > want ? el - want : want - el;
-        if (best_d < 0 || dist < best_d) { best_d = dist; gpb = g; T = t_ok; nv = n_ok <= 4 ? 4 : n_ok <= 8 ? 8 : n_ok <= 16 ? 16 : n_ok <= 32 ? 32 : 52; }
+        if (best_d < 0 || dist < best_d) { best_d = dist; gpb = g; T = t_ok; nv = n_ok <= 4 ? 4 : n_ok <= 8 ? 8 : n_ok <= 16 ? 16 : 32; }
     }
     return best_d >= 0;
 }
@@ -304,7 +299,7 @@ static hipError_t launch_gn_onepass(const GnParams& p, int gpb, int T, int nv, h
         case 8: return by_t(std::integral_constant<int, 8>{});
         case 16: return by_t(std::integral_constant<int, 16>{});
         case 32: return by_t(std::integral_constant<int, 32>{});
-        default: return T == 512 ? go(std::integral_constant<int, 52>{}, std::integral_constant<int, 512>{}) : hipErrorInvalidValue;
+        default: return hipErrorInvalidValue;
     }
 }
 
@@ -336,27 +331,18 @@ hipError_t launch_groupnorm(GnParams p, hipStream_t st) {
         int gpb, T, nv;
         if (p.out && gn_onepass_plan(p, gpb, T, nv)) return launch_gn_onepass(p, gpb, T, nv, st);
     }
-    // RDM_GN_RANGE_MB = n (default 0 = off): walk a tensor larger than 2n MB in sample ranges of n MB, statistics then apply per range, so
-    // that the apply pass could re-read from the 256 MB memory-side cache what the statistics pass of the SAME range pulled in (64 x 64
-    // level at B' = 128: 200 .. 600 MB per GroupNorm).  Measured round 5 (profiles/r05e_gn_sample_ranges_ab.log): 24 / 48 / 96 MB ranges
-    // = -7.6 % / -2.9 % / -1.0 % on the headline -- the under-filled launches and their tails cost more than any reuse returns.  Off.
-    static const long long range_mb = getenv("RDM_GN_RANGE_MB") ? atoll(getenv("RDM_GN_RANGE_MB")) : 0;
-    const long long per_sample = (long long)p.HW * (p.C0 + p.C1) * 2;
-    int nb = p.B;
-    if (range_mb > 0 && per_sample * p.B > 2 * range_mb * (1 << 20)) { nb = (int)(range_mb * (1 << 20) / per_sample); if (nb < 1) nb = 1; }
+    // (Walking a big tensor in sample ranges, so that the apply pass re-reads from the memory-side cache what the statistics pass of the
+    // same range pulled in, measured round 5 (profiles/r05e_gn_sample_ranges_ab.log): 24 / 48 / 96 MB ranges = -7.6 % / -2.9 % / -1.0 %
+    // on the headline -- the under-filled launches and their tails cost more than any reuse returns.  Removed.)
     const size_t sm1 = (size_t)(R + 1) * (p.C0 + p.C1) * 2 * sizeof(float);
-    for (int b0 = 0; b0 < p.B; b0 += nb) {
-        GnParams q = p; q.b0 = p.b0 + b0;
-        const int n = p.B - b0 < nb ? p.B - b0 : nb;
-        gn_stats_kernel<<<dim3(q.nchunk, n), threads, sm1, st>>>(q);
-        // apply: ~64 rows per thread-row, at least ~2k blocks across the range
-        int nblk = (p.HW + 64 * R - 1) / (64 * R);
-        const int min_blocks = (2048 + n - 1) / n;
-        if (nblk < min_blocks) nblk = min_blocks;
-        if (nblk > p.HW) nblk = p.HW;
-        if (nblk < 1) nblk = 1;
-        gn_apply_kernel<<<dim3(nblk, n), threads, 0, st>>>(q);
-    }
+    gn_stats_kernel<<<dim3(p.nchunk, p.B), threads, sm1, st>>>(p);
+    // apply: ~64 rows per thread-row, at least ~2k blocks
+    int nblk = (p.HW + 64 * R - 1) / (64 * R);
+    const int min_blocks = (2048 + p.B - 1) / p.B;
+    if (nblk < min_blocks) nblk = min_blocks;
+    if (nblk > p.HW) nblk = p.HW;
+    if (nblk < 1) nblk = 1;
+    gn_apply_kernel<<<dim3(nblk, p.B), threads, 0, st>>>(p);
     return hipGetLastError();
 }
 
@@ -490,9 +476,8 @@ hipError_t launch_layernorm(const void* x, int in_is_f32, const float* gamma, co
     if (C % 2 || C > 4096) return hipErrorInvalidValue;
     if (Clog < 0) Clog = C;
     if (Clog > C || Clog % 8 || (Clog != C && (in_is_f32 || out_is_f32 || C % 8 || C > 1024))) return hipErrorInvalidValue;   // padded rows: the bf16 vector kernel only
-    static const int no_vec = getenv("RDM_LN_NOVEC") ? atoi(getenv("RDM_LN_NOVEC")) : 0;
-    if (Clog != C && (no_vec || ((size_t)x % 16) || ((size_t)out % 16) || ((size_t)gamma % 16) || ((size_t)beta % 16))) return hipErrorInvalidValue;
-    if (!no_vec && !in_is_f32 && !out_is_f32 && C % 8 == 0 && C <= 1024 && ((size_t)x % 16 == 0) && ((size_t)out % 16 == 0) &&
+    if (Clog != C && (((size_t)x % 16) || ((size_t)out % 16) || ((size_t)gamma % 16) || ((size_t)beta % 16))) return hipErrorInvalidValue;
+    if (!in_is_f32 && !out_is_f32 && C % 8 == 0 && C <= 1024 && ((size_t)x % 16 == 0) && ((size_t)out % 16 == 0) &&
         ((size_t)gamma % 16 == 0) && ((size_t)beta % 16 == 0)) {
         const int grid = (M + 3) / 4;
         if (C <= 512) layernorm_bf16x8_kernel<1><<<grid, 256, 0, st>>>((const bf16_t*)x, gamma, beta, (bf16_t*)out, M, C, eps, Clog);

@@ -35,9 +35,9 @@ hipError_t launch_rarm_embed(const long long* tokens, const float* emb, const fl
 // wave's chunks of sum_j p_j V[j][:], the four partial rows meet in LDS and are added in wave order.  CrossAttention.forward,
 // attention.py:42-74.
 // NW: waves per block = 32-row chunks in flight at once.  Eight waves (all 256 cached rows of a (head, sequence) requested in ONE round
-// trip; RDM_RARM_ATTN_NW8_FROM=<sequences>) measured SLOWER, round 5: 419 / 578 / 683 -> 406 / 552 / 644 img/s at 256 / 512 / 1024 sequences
+// trip) measured SLOWER, round 5: 419 / 578 / 683 -> 406 / 552 / 644 img/s at 256 / 512 / 1024 sequences
 // (profiles/r05e_rarm_attn_8wave_sweep.log) -- averaged over the 256 positions the launch is a fixed ~6.5 us + the cache bytes at ~5.5 TB/s
-// already; the bigger blocks raise the fixed part (idle waves at short prefixes, wider barriers).  Four waves stay the default.
+// already; the bigger blocks raise the fixed part (idle waves at short prefixes, wider barriers).  Four waves; the eight-wave path is removed.
 template <int NW>
 __global__ __launch_bounds__(64 * NW) void rarm_decode_attention_kernel(RarmAttnParams p) {
     // Eight lanes per cache row (16 bytes each), eight rows per load instruction: an instruction touches 8 cache lines.  (One lane
@@ -193,14 +193,11 @@ __global__ __launch_bounds__(256) void rarm_fewkey_attention_kernel(RarmAttnPara
 }
 hipError_t launch_rarm_decode_attention(const RarmAttnParams& p, int heads, int batch, hipStream_t st) {
     if (p.nkv > 1024) return hipErrorInvalidValue;
-    static const int no_fewkey = getenv("RDM_NO_RARM_FEWKEY") ? atoi(getenv("RDM_NO_RARM_FEWKEY")) : 0;
-    if (!no_fewkey && !p.k_new && !p.pos && p.nkv >= 1 && p.nkv <= 8 && batch >= 128) {       // cross-attention over few keys at big batches
+    if (!p.k_new && !p.pos && p.nkv >= 1 && p.nkv <= 8 && batch >= 128) {       // cross-attention over few keys at big batches
         rarm_fewkey_attention_kernel<<<batch, 256, 0, st>>>(p, heads);
         return hipGetLastError();
     }
-    static const int nw8_from = getenv("RDM_RARM_ATTN_NW8_FROM") ? atoi(getenv("RDM_RARM_ATTN_NW8_FROM")) : 0;
-    if (p.k_new && nw8_from > 0 && batch >= nw8_from) rarm_decode_attention_kernel<8><<<dim3(heads, batch), 512, 0, st>>>(p);
-    else rarm_decode_attention_kernel<4><<<dim3(heads, batch), 256, 0, st>>>(p);
+    rarm_decode_attention_kernel<4><<<dim3(heads, batch), 256, 0, st>>>(p);
     return hipGetLastError();
 }
 
@@ -354,209 +351,11 @@ __global__ __launch_bounds__(1024) void rarm_xattn_decode_kernel(RarmXattnParams
         rarm_emit_ln<16>(tid < C ? xn[tid] : 0.f, tid < C, tid, C, p.ln3_g, p.ln3_b, p.ln_eps, p.ln3_out + (long long)b * C, red);
     }
 }
-// Four blocks per sequence (round 4).  The one-block form asks ONE CU for a sequence's whole operand pair (heads k rows of G and of
-// UT: 295 KB at 12 heads x 8 neighbours x 768 channels) on 64 of 256 CUs: 16.4 us per layer.  The softmax is per head, so a block
-// that owns a QUARTER of the heads needs only their rows of G and UT (74 KB): scores, softmax and the partial output row of its
-// heads; the four partial rows meet in global memory -- written through to the coherence point (agent-scope stores), one
-// agent-scope arrival counter per sequence -- and the block that arrives last adds them IN BLOCK ORDER to bias and residual
-// (deterministic).  heads % 4 == 0.
-// LayerNorm of one row held as channels tid + 256 i (i < 4) by a 256-thread block, rounded to bf16 (every thread calls it)
-__device__ __forceinline__ void rarm_emit_ln4(const float (&xv)[4], int tid, int C, const float* g, const float* bta, float eps, bf16_t* y, float* red) {
-    const int lane = tid & 63, w = tid >> 6;
-    float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) s += (tid + 256 * i < C) ? xv[i] : 0.f;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    __syncthreads();
-    if (lane == 0) red[w] = s;
-    __syncthreads();
-    const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / C;
-    float q = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const float d = (tid + 256 * i < C) ? xv[i] - mean : 0.f; q += d * d; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) q += __shfl_xor(q, o);
-    if (lane == 0) red[4 + w] = q;
-    __syncthreads();
-    const float rstd = rsqrtf(((red[4] + red[5]) + (red[6] + red[7])) / C + eps);
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const int c = tid + 256 * i; if (c < C) y[c] = f2bf((xv[i] - mean) * rstd * g[c] + bta[c]); }
-}
-// HAND-OVER OF THE PARTIAL ROWS (round 6: self-validating granules instead of an ordering assumption).  Round 4's form wrote the partial
-// rows with agent-scope write-through stores, drained them (vmcnt(0) + workgroup barrier), arrived on a relaxed agent-scope counter, and the
-// last arriver read the rows back with agent-scope loads: correct only if "store completed" means "visible to every other XCD" -- gfx950
-// behaviour outside the C++ memory model, and round 5's stress test saw ONE bitwise mismatch in ~6 800 repeated decodes (~2.9 M launches)
-// whose only possible source was this hand-over (everything else in the step is block-local): a last arriver reading one partial value of
-// the PREVIOUS layer, which sits in the same buffer.  Now every value travels as ONE naturally aligned 8-byte granule {fp32 bits, tag},
-// tag = this launch's epoch (host-incremented per launch, never 0; the buffer is zeroed when it is allocated), written by ONE agent-scope
-// 8-byte store.  The last arriver checks the tag of every granule it reads and re-reads (agent-scope load, bounded spin) until the tag
-// is this launch's: a value of an earlier launch can no longer be consumed, whatever the visibility delay -- no release / acquire edge and
-// no assumption about write-through completion is needed, on any target.  Re-reads are counted (g_rarm_xsplit_stale, rdm_debug_counter(0)):
-// tools/rarm_stress.py reports them, a non-zero count is the round-5 mismatch caught in the act.  The arrival counter is monotonic
-// (last = every fourth arrival), nothing is re-armed.
-__device__ unsigned long long g_rarm_xsplit_stale = 0ull;
-unsigned long long rarm_xsplit_stale_count() {
-    unsigned long long v = 0ull;
-    (void)hipMemcpyFromSymbol(&v, HIP_SYMBOL(g_rarm_xsplit_stale), sizeof(v));
-    return v;
-}
-__global__ __launch_bounds__(256) void rarm_xattn_decode_split_kernel(RarmXattnParams p) {
-    __shared__ float xn[1024];
-    __shared__ float sc[32];
-    __shared__ float red[8];
-    __shared__ int s_last;
-    const int b = blockIdx.x >> 2, q = blockIdx.x & 3, tid = threadIdx.x, lane = tid & 63, w = tid >> 6, C = p.C;
-    float* xr = p.x + (long long)b * C;
-    if (b >= p.Bc) {                      // zero neighbours: the attention output is 0, to_out leaves its bias (block 0 of the sequence)
-        if (q != 0) return;
-        float xv[4];
-#pragma unroll
-        for (int i = 0; i < 4; i++) { const int c = tid + 256 * i; xv[i] = 0.f; if (c < C) { xv[i] = xr[c] + p.bias[c]; xr[c] = xv[i]; } }
-        if (p.ln3_out) rarm_emit_ln4(xv, tid, C, p.ln3_g, p.ln3_b, p.ln_eps, p.ln3_out + (long long)b * C, red);
-        return;
-    }
-    // ---- every operand row this block will read, requested NOW: neither G nor UT depends on the LayerNorm or the scores, and the launch
-    // is a chain of dependent round trips -- wave w takes score rows w, w + 4, ... (<= 8 each; a row = C/8 16-byte pieces: two rounds of
-    // lanes), thread t the 4 output channels 4 t of all nr rows of UT
-    const int nr = (p.heads >> 2) * p.k, r0 = q * nr, npc = C >> 3;
-    const bf16_t* Gb = p.G + ((long long)b * p.NP + r0) * C;
-    const bf16_t* Ub = p.UT + ((long long)b * p.NP + r0) * C;
-    const int nc4 = C >> 2;
-    bf16x8 g[8][2];
-#pragma unroll
-    for (int u = 0; u < 8; u++) {
-        const int j = w + 4 * u;
-#pragma unroll
-        for (int h = 0; h < 2; h++) {
-            const int pc = lane + 64 * h;
-            g[u][h] = (j < nr && pc < npc) ? *(const bf16x8*)(Gb + (long long)j * C + pc * 8) : bf16x8{0, 0, 0, 0, 0, 0, 0, 0};
-        }
-    }
-    uint2 u[32];
-    if (tid < nc4) {
-#pragma unroll
-        for (int i = 0; i < 32; i++) u[i] = i < nr ? *(const uint2*)(Ub + (long long)i * C + tid * 4) : make_uint2(0u, 0u);
-    }
-    // ---- LayerNorm (two-pass; up to 4 channels per thread), rounded to bf16 as the GEMM operand was
-    float v[4]; float s = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const int c = tid + 256 * i; v[i] = c < C ? xr[c] : 0.f; s += v[i]; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
-    if (lane == 0) red[w] = s;
-    __syncthreads();
-    const float mean = ((red[0] + red[1]) + (red[2] + red[3])) / C;
-    float qq = 0.f;
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const int c = tid + 256 * i; const float d = c < C ? v[i] - mean : 0.f; v[i] = d; qq += d * d; }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) qq += __shfl_xor(qq, o);
-    if (lane == 0) red[4 + w] = qq;
-    __syncthreads();
-    const float rstd = rsqrtf(((red[4] + red[5]) + (red[6] + red[7])) / C + p.ln_eps);
-#pragma unroll
-    for (int i = 0; i < 4; i++) { const int c = tid + 256 * i; if (c < C) xn[c] = bf2f(f2bf(v[i] * rstd * p.ln_g[c] + p.ln_b[c])); }
-    __syncthreads();
-    // ---- scores of this block's rows [r0, r0 + nr)
-    {
-#pragma unroll
-        for (int u = 0; u < 8; u++) {
-            const int j = w + 4 * u;
-            float a = 0.f;
-#pragma unroll
-            for (int h = 0; h < 2; h++) {
-                const int pc = lane + 64 * h;
-                if (pc < npc) {
-#pragma unroll
-                    for (int e = 0; e < 8; e++) a += bf2f((bf16_t)g[u][h][e]) * xn[pc * 8 + e];
-                }
-            }
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) a += __shfl_xor(a, o);
-            if (lane == 0 && j < nr) sc[j] = a;
-        }
-    }
-    __syncthreads();
-    float pr = 0.f;
-    if (tid < nr) {
-        const int h0 = (tid / p.k) * p.k;
-        float m = -INFINITY;
-        for (int i = 0; i < p.k; i++) m = fmaxf(m, sc[h0 + i]);
-        float sum = 0.f;
-        for (int i = 0; i < p.k; i++) sum += __expf(sc[h0 + i] - m);
-        pr = __expf(sc[tid] - m) / sum;
-    }
-    __syncthreads();
-    if (tid < nr) sc[tid] = pr;
-    __syncthreads();
-    // ---- partial output row of this block's heads: thread = 4 channels over the nr rows requested above
-    unsigned long long* const pw = (unsigned long long*)p.ws + ((long long)b * 4 + q) * C;
-    const unsigned long long etag = (unsigned long long)p.epoch << 32;
-    if (tid < nc4) {
-        float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
-#pragma unroll
-        for (int i = 0; i < 32; i++) {
-            const float pj = i < nr ? sc[i] : 0.f;
-            a0 += pj * __uint_as_float(u[i].x << 16); a1 += pj * __uint_as_float(u[i].x & 0xffff0000u);
-            a2 += pj * __uint_as_float(u[i].y << 16); a3 += pj * __uint_as_float(u[i].y & 0xffff0000u);
-        }
-        __hip_atomic_store(pw + tid * 4 + 0, etag | __float_as_uint(a0), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pw + tid * 4 + 1, etag | __float_as_uint(a1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pw + tid * 4 + 2, etag | __float_as_uint(a2), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        __hip_atomic_store(pw + tid * 4 + 3, etag | __float_as_uint(a3), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    // Drain this block's granule stores, then ONE relaxed agent-scope arrival per block (monotonic counter: every fourth arrival is a
-    // sequence's last).  The drain makes the common case -- granules visible before the arrival -- the only case seen so far; the tag check
-    // below is what makes the uncommon one harmless.
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    __syncthreads();
-    if (tid == 0) s_last = ((__hip_atomic_fetch_add(p.ws_count + b, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) & 3) == 3) ? 1 : 0;
-    __syncthreads();
-    if (!s_last) return;
-    const unsigned long long* const pb = (const unsigned long long*)p.ws + (long long)b * 4 * C;
-    auto granule = [&](const unsigned long long* g) -> float {
-        unsigned long long v = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        if ((unsigned)(v >> 32) != p.epoch) {              // a value of an earlier launch: not yet this launch's -- count it, wait for ours
-            atomicAdd(&g_rarm_xsplit_stale, 1ull);
-            for (int spin = 0; spin < (1 << 24) && (unsigned)(v >> 32) != p.epoch; spin++) {
-                __builtin_amdgcn_s_sleep(2);
-                v = __hip_atomic_load(g, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-            }
-            if ((unsigned)(v >> 32) != p.epoch) return __uint_as_float(0x7fc00000u);      // never arrived (cannot happen: all four blocks have): poison, do not guess
-        }
-        return __uint_as_float((unsigned)v);
-    };
-    float xv[4];
-#pragma unroll
-    for (int i = 0; i < 4; i++) {
-        const int c = tid + 256 * i;
-        xv[i] = 0.f;
-        if (c < C) {
-            const float t0 = granule(pb + c), t1 = granule(pb + C + c), t2 = granule(pb + 2 * C + c), t3 = granule(pb + 3 * C + c);
-            xv[i] = xr[c] + (p.bias[c] + ((t0 + t1) + (t2 + t3)));
-            xr[c] = xv[i];
-        }
-    }
-    // the last arriver holds the finished row: norm3 of the feed-forward that follows leaves with it (bf16 GEMM operand)
-    if (p.ln3_out) rarm_emit_ln4(xv, tid, C, p.ln3_g, p.ln3_b, p.ln_eps, p.ln3_out + (long long)b * C, red);
-}
-#ifndef RARM_XSPLIT_DEFAULT
-#define RARM_XSPLIT_DEFAULT 0
-#endif
 hipError_t launch_rarm_xattn_decode(const RarmXattnParams& p, hipStream_t st) {
     if (p.C % 8 || p.C > 1024 || p.heads * p.k > 128 || p.heads * p.k > p.NP || p.k < 1) return hipErrorInvalidValue;
-    // The four-blocks-per-sequence form: OPT-IN (RDM_RARM_XSPLIT=1).  Round 5 made it opt-in after one unexplained bitwise mismatch in ~6 800
-    // repeated decodes; round 6 replaced the hand-over's ordering assumption by self-validating granules (note above), stress-ran both forms clean
-    // (profiles/r06_rarm_stress.log) -- and then measured the granule form SLOWER than one block per sequence (64 sequences 199.4 vs 198.0 img/s,
-    // 128: 290.6 vs 284.5; profiles/r06_rarm_split_ab.log): the 8-byte granules and the tag checks cost more than the 1 us the split bought.
-    // Never in deterministic mode (p.no_split: the choice follows the batch; the two forms add the heads in different orders).
-    static const int split_on = getenv("RDM_RARM_XSPLIT") ? atoi(getenv("RDM_RARM_XSPLIT")) : RARM_XSPLIT_DEFAULT;
-    // (from 128 sequences on the one-block form already fills the chip: measured equal at 256)
-    if (split_on && !p.no_split && p.epoch && p.ws && p.ws_count && p.B2 <= 128 && p.heads % 4 == 0 && (p.heads / 4) * p.k <= 32 && p.C % 4 == 0) {
-        rarm_xattn_decode_split_kernel<<<p.B2 * 4, 256, 0, st>>>(p);
-        return hipGetLastError();
-    }
+    // (A four-blocks-per-sequence form -- a quarter of the heads per block, the partial rows handed over in global memory -- was
+    // measured SLOWER than one block per sequence in round 6 (64 sequences 198.0 vs 199.4 img/s, 128: 284.5 vs 290.6;
+    // profiles/r06_rarm_split_ab.log) and removed.)
     rarm_xattn_decode_kernel<<<p.B2, 1024, 0, st>>>(p);
     return hipGetLastError();
 }

@@ -10,7 +10,6 @@
 // and the four partial tiles meet in LDS for a fused bias / activation / residual epilogue.  GEGLU: the packed weight rows interleave
 // 32 x-rows with their 32 gate rows (packing._geglu_perm); a block owns a whole 64-row strip (NB = 4: 32 outputs) or one half of it
 // (NB = 2: x rows [16 h, 16 h + 16) and their gates, 16 outputs) and emits x * gelu(gate).
-#include <stdlib.h>
 
 #include "kernels.h"
 
@@ -249,8 +248,7 @@ __global__ __launch_bounds__(64 * NW) void sgemm_kernel(SgemmParams p) {
 }
 
 bool sgemm_supported(const SgemmParams& p) {
-    static const int off = getenv("RDM_NO_SGEMM") ? atoi(getenv("RDM_NO_SGEMM")) : 0;
-    if (off || p.M < 1 || p.K % 256 != 0 || (!p.ln_x && p.lda % 8 != 0)) return false;      // any M: 16 MA-row blocks on grid.y
+    if (p.M < 1 || p.K % 256 != 0 || (!p.ln_x && p.lda % 8 != 0)) return false;      // any M: 16 MA-row blocks on grid.y
     if (p.ln_x && (p.K != 768 || !p.ln_g || !p.ln_b)) return false;                          // LayerNorm-fused A: a K quarter = one batch of 6 k-steps
     if (p.act == ACT_GEGLU) return p.N % 64 == 0;
     return p.N % 32 == 0 && (p.act == ACT_NONE || p.act == ACT_SILU || p.act == ACT_QUICKGELU);
@@ -277,7 +275,6 @@ static hipError_t launch_one(const SgemmParams& p, hipStream_t st) {
 // fetch is what a launch lasts; rounds = how many blocks a CU gets).  Depends on (M, N, K, kind) only.
 template <bool GEGLU, bool LN>
 static void pick_tile(const SgemmParams& p, int& ma, int& nb) {
-    static const int force_ma = getenv("RDM_SGEMM_MA") ? atoi(getenv("RDM_SGEMM_MA")) : 0, force_nb = getenv("RDM_SGEMM_NB") ? atoi(getenv("RDM_SGEMM_NB")) : 0;
     const int mas[3] = {1, 2, 4}, nbs[3] = {GEGLU ? 2 : 1, GEGLU ? 4 : 2, GEGLU ? 8 : 4};
     double best = 1e30; ma = 2; nb = nbs[1];
     for (int a : mas) for (int b : nbs) {
@@ -290,7 +287,7 @@ static void pick_tile(const SgemmParams& p, int& ma, int& nb) {
         (void)rounds;
         const double per_cu = blocks > 256 ? (double)blocks / 256.0 : 1.0;                      // blocks a CU's ingest path is shared by
         const double cost = per_cu * (bytes + 8192.0);                                          // + a fixed per-block latency term
-        if ((force_ma == 0 || force_ma == a) && (force_nb == 0 || force_nb == b) && cost < best) { best = cost; ma = a; nb = b; }
+        if (cost < best) { best = cost; ma = a; nb = b; }
     }
 }
 
@@ -300,27 +297,18 @@ static hipError_t launch_nf(const SgemmParams& p, hipStream_t st) {
     constexpr int N1 = GEGLU ? 2 : 1, N2 = GEGLU ? 4 : 2, N3 = GEGLU ? 8 : 4;
     int ma, nb;
     if (p.ln_x) {
-        // RDM_SGEMM_LN8_FROM = m (default 0 = off): from m rows on, plain projections take the LayerNorm inside the 64-row tiles on eight
-        // waves (a wave's K / 8 = 96 fp32 columns of 64 rows in registers) -- the separate LayerNorm launch is 5.4 us of a decode layer's
-        // 150 at 512 sequences, three times per layer.  Measured round 5 (profiles/r05e_rarm_ln8_sweep.log): 512 sequences 564 -> 524
-        // img/s, 256 sequences 419 -> 395: every column tile re-reads its 64 rows as fp32 (196 KB instead of 98 KB per block, 64 x 32
-        // outputs only: 64 x 64 is 41 registers over an eight-wave block's budget) and repeats the statistics; the two launches saved
-        // (10.8 us per layer) come back as + 26 us of GEMM.  Off.
-        static const int ln8_from = getenv("RDM_SGEMM_LN8_FROM") ? atoi(getenv("RDM_SGEMM_LN8_FROM")) : 0;
-        if constexpr (!GEGLU) {
-            if (!p.fixed_split && ln8_from > 0 && p.M >= ln8_from && p.K == 768)
-                return launch_one<4, N2, false, 3, true, 8>(p, st);      // (64 x 64 outputs: 41 registers over the budget of an eight-wave block)
-        }
+        // (The LayerNorm inside 64-row tiles on eight waves, for the plain projections from some row count on, measured round 5
+        // (profiles/r05e_rarm_ln8_sweep.log): 512 sequences 564 -> 524 img/s, 256 sequences 419 -> 395: every column tile re-reads its
+        // 64 rows as fp32 (196 KB instead of 98 KB per block) and repeats the statistics; the two LayerNorm launches saved (10.8 us per
+        // layer) come back as + 26 us of GEMM.  Removed.)
         pick_tile<GEGLU, true>(p, ma, nb);
         if (ma == 1) return nb == N1 ? launch_one<1, N1, GEGLU, 6, true>(p, st) : launch_one<1, N2, GEGLU, 6, true>(p, st);
         return nb == N1 ? launch_one<2, N1, GEGLU, 6, true>(p, st) : launch_one<2, N2, GEGLU, 6, true>(p, st);
     }
     if constexpr (!GEGLU) {
         // 64 x 96 outputs for wide projections at 384+ rows (q | k | v, N = 2304, at 512 rows: 8 x 24 = 192 blocks in ONE round of the 256 CUs;
-        // as 64 x 64 tiles it is 288 blocks of 128 KB LDS each, one per CU: two rounds).  RDM_SGEMM_N96=0: off
-        static const int n96 = getenv("RDM_SGEMM_N96") ? atoi(getenv("RDM_SGEMM_N96")) : 1;
-        static const int nw8_off2 = getenv("RDM_SGEMM_NW4") ? atoi(getenv("RDM_SGEMM_NW4")) : 0;
-        if (!p.fixed_split && n96 && !nw8_off2 && p.M >= 384 && p.N % 96 == 0 && p.N >= 1536 && p.K == 768) {
+        // as 64 x 64 tiles it is 288 blocks of 128 KB LDS each, one per CU: two rounds)
+        if (!p.fixed_split && p.M >= 384 && p.N % 96 == 0 && p.N >= 1536 && p.K == 768) {
             const long long b64 = (long long)((p.M + 63) / 64) * (p.N / 64), b96 = (long long)((p.M + 63) / 64) * (p.N / 96);
             if ((b64 + 255) / 256 > (b96 + 255) / 256) return launch_one<4, 6, false, 3, false, 8>(p, st);
         }
@@ -329,8 +317,7 @@ static hipError_t launch_nf(const SgemmParams& p, hipStream_t st) {
     if (nb == N3) {       // 64 x 64 outputs: two (GEGLU) / three k-steps per batch of loads keep the operand registers under the budget
         if constexpr (GEGLU) return launch_one<4, N3, true, 2>(p, st);
         else {
-            static const int nw8_off = getenv("RDM_SGEMM_NW4") ? atoi(getenv("RDM_SGEMM_NW4")) : 0;
-            if (!p.fixed_split && !nw8_off && p.M >= 384 && (p.K >> 3) % 96 == 0) return launch_one<4, N3, false, 3, false, 8>(p, st);      // eight waves: K / 8 in batches of three k-steps
+            if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 96 == 0) return launch_one<4, N3, false, 3, false, 8>(p, st);      // eight waves: K / 8 in batches of three k-steps
             return ((p.K >> 2) % 96) == 0 ? launch_one<4, N3, false, 3>(p, st) : launch_one<4, N3, false, 2>(p, st);
         }
     }
@@ -345,12 +332,10 @@ static hipError_t launch_nf(const SgemmParams& p, hipStream_t st) {
         case 1: return deep ? launch_one<1, N2, GEGLU, 6>(p, st) : launch_one<1, N2, GEGLU, 2>(p, st);
         case 2: return deep ? launch_one<2, N2, GEGLU, 6>(p, st) : launch_one<2, N2, GEGLU, 2>(p, st);
         default: {
-            static const int nw8_off = getenv("RDM_SGEMM_NW4") ? atoi(getenv("RDM_SGEMM_NW4")) : 0;
             if constexpr (!GEGLU) {
-                // deep K (3072: a wave's share is 12 k-steps): six per batch of loads = two dependent round trips instead of four (RDM_SGEMM_U6=0: three)
-                static const int u6 = getenv("RDM_SGEMM_U6") ? atoi(getenv("RDM_SGEMM_U6")) : 1;
-                if (!p.fixed_split && !nw8_off && u6 && p.M >= 384 && (p.K >> 3) % 192 == 0) return launch_one<4, N2, false, 6, false, 8>(p, st);
-                if (!p.fixed_split && !nw8_off && p.M >= 384 && (p.K >> 3) % 96 == 0) return launch_one<4, N2, false, 3, false, 8>(p, st);
+                // deep K (3072: a wave's share is 12 k-steps): six per batch of loads = two dependent round trips instead of four
+                if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 192 == 0) return launch_one<4, N2, false, 6, false, 8>(p, st);
+                if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 96 == 0) return launch_one<4, N2, false, 3, false, 8>(p, st);
             }      // (same box: 512 rows 511.6 -> 519.5 img/s, 256 rows 407.8 -> 404.3: from 384 rows on)
             return deep ? launch_one<4, N2, GEGLU, 6>(p, st) : launch_one<4, N2, GEGLU, 2>(p, st);
         }

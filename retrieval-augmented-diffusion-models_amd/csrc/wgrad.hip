@@ -293,8 +293,7 @@ void wgrad_geom(long long M, int N, int K, int taps, int* pZ, int* pmz) {
 }  // namespace
 
 bool wgrad_tn_supported(long long M, int N, int K, int lda, int ldb) {
-    static const bool off = getenv("RDM_NO_WGRAD_TN") != nullptr;
-    return !off && M >= 256 && M < (1LL << 30) && N % 32 == 0 && K % 32 == 0 && lda % 8 == 0 && ldb % 8 == 0;
+    return M >= 256 && M < (1LL << 30) && N % 32 == 0 && K % 32 == 0 && lda % 8 == 0 && ldb % 8 == 0;
 }
 bool conv_wgrad_tn_supported(int B, int H, int W, int C, int N) {
     return (H & (H - 1)) == 0 && (W & (W - 1)) == 0 && wgrad_tn_supported((long long)B * H * W, N, C, N, C);
@@ -306,8 +305,7 @@ size_t wgrad_tn_scratch_bytes(long long M, int N, int K, int taps) {
 
 // nine-tap kernel: W in {16, 32, 64}, H a power of two, channel counts multiples of 64
 static bool conv9_ok(int B, int H, int W, int C, int N) {
-    static const bool off = getenv("RDM_NO_WGRAD_CONV9") != nullptr;
-    return !off && (W == 16 || W == 32 || W == 64) && (H & (H - 1)) == 0 && H >= 2 && C % 64 == 0 && N % 64 == 0 && (long long)B * H * W < (1LL << 30) &&
+    return (W == 16 || W == 32 || W == 64) && (H & (H - 1)) == 0 && H >= 2 && C % 64 == 0 && N % 64 == 0 && (long long)B * H * W < (1LL << 30) &&
            ((long long)B * H * W) % (W > 32 ? W : 32) == 0;
 }
 static void conv9_geom(int B, int H, int W, int C, int N, int* pZ, int* pcz) {

@@ -109,9 +109,9 @@ def test_linear_rowvec(ctx, M, N, K, rows, res):
 
 
 def test_linear_mid_size_gemm(tmp_path):
-    """mgemm.hip (LDS-staged 64 x 64 / 128 x 64 tiles: the RARM decode step's plain projections from 1536 sequences on) on its own, through
-    rdm_op_linear in a child process with RDM_MGEMM_ANY=64 (dev switch: plain ops of >= 64 rows take it): ragged row counts, fp32 and bf16
-    outputs, bias, bf16 residual, SiLU / QuickGELU, both tile heights and two ring depths -- against fp32 products of the same bf16 operands
+    """mgemm.hip (LDS-staged 64 x 64 tiles: the RARM decode step's plain projections from 1536 sequences on) on its own, through
+    rdm_op_linear in a child process with RDM_MGEMM_ANY=64 (test hook: plain ops of >= 64 rows take it): ragged row counts, fp32 and bf16
+    outputs, bias, bf16 residual, SiLU / QuickGELU -- against fp32 products of the same bf16 operands
     (bound: the fp32-accumulation level for fp32 outputs, one bf16 rounding for bf16 outputs)."""
     import os
     import subprocess
@@ -139,10 +139,9 @@ def test_linear_mid_size_gemm(tmp_path):
         "    assert e <= (2e-5 if f32 else 6e-3), (M, N, K, e)\n"
         "    worst = max(worst, e)\n"
         "print('OK', worst)\n")
-    for extra in ({}, {"RDM_MGEMM_NS": "3"}, {"RDM_MGEMM_NS": "2"}, {"RDM_MGEMM_BM": "128", "RDM_MGEMM_NS": "3"}, {"RDM_MGEMM_BN": "128"}, {"RDM_MGEMM_BN": "128", "RDM_MGEMM_BM": "128"}):
-        r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RDM_MGEMM_ANY="64", **extra), capture_output=True, text=True, timeout=600)
-        print(r.stdout[-1500:])
-        assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-1500:] + r.stderr[-2500:]
+    r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RDM_MGEMM_ANY="64"), capture_output=True, text=True, timeout=600)
+    print(r.stdout[-1500:])
+    assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-1500:] + r.stderr[-2500:]
 
 
 @pytest.mark.parametrize("M,C", [(49152, 192), (32768, 384)])
@@ -313,7 +312,7 @@ def test_conv3x3_wide_images_as_strips(ctx, B, H, W, C0, C1, N, ups):
                           x1=None if x1 is None else x1.to(d, torch.bfloat16), rowvec=temb.to(d), residual=res.to(d, torch.bfloat16), ups=ups)
     _close(out2, ref + temb[:, None, None, :] + res, what="wide conv3x3 + row + residual")
     # bitwise the same as the generic implicit GEMM?  No (other summation order): but both must sit within the tolerance of the reference,
-    # and the strip kernel must be the one that ran when it applies (env RDM_NO_HALO4_STRIP=1 switches it off for A/B)
+    # and the strip kernel is the one that runs when it applies
 
 
 def test_conv3x3_dual_source_rowvec_residual(ctx):
@@ -542,35 +541,3 @@ def test_cross_attention_reference_golden(ctx):
     e = rel_l2(y, torch.from_numpy(g["ca_y"]))
     print("CrossAttention vs reference golden rel L2:", e)
     assert e <= 2e-2
-
-
-def test_ffn_fused_matches_the_two_kernel_feed_forward(ctx):
-    """Round 6 (verdict item 2): csrc/ffn.hip's fused GEGLU -> ff.net.2 x proj_out kernel (the hidden tensor never in HBM; a measurement vehicle, not used
-    by the executors) against an fp32 torch reference on bf16-rounded operands -- [x | g] = l3 W1^T + b1, ff = bf16(x gelu(g)), out = bf16([ff | t2] Wf^T +
-    bf + x_in) (rdm/modules/attention.py:77-96; ldm GEGLU) -- and against the two-kernel path of the executors (same roundings: flips only)."""
-    from rdm_amd import _lib
-    from rdm_amd.packing import _geglu_perm
-    from _util import rel_l2
-    d = ctx.device
-    g = torch.Generator().manual_seed(9)
-    M, C = 512, 384
-    bf = lambda t: t.to(torch.bfloat16)
-    R = lambda *s, sc=1.0: torch.randn(*s, generator=g) * sc
-    l3, t2, xin = bf(R(M, C)), bf(R(M, C)), bf(R(M, C))
-    w1, b1 = bf(R(8 * C, C, sc=C ** -0.5)), R(8 * C, sc=0.3)
-    wf, bfb = bf(R(C, 5 * C, sc=(5 * C) ** -0.5)), R(C, sc=0.3)
-    pp = l3.float() @ w1.float().t() + b1
-    x, gate = pp.chunk(2, dim=-1)
-    ff = bf(x * F.gelu(gate)).float()
-    ref = bf(torch.cat([ff, t2.float()], dim=1) @ wf.float().t() + bfb + xin.float()).float()
-    perm = torch.as_tensor(_geglu_perm(8 * C))
-    dev = lambda t: t.to(d).contiguous()
-    out = ctx.op_ffn_fused(dev(l3), dev(t2), dev(xin), dev(w1[perm]), dev(b1[perm]), dev(wf), dev(bfb))
-    hid = ctx.op_linear(dev(l3), dev(w1[perm]), dev(b1[perm]), act=_lib.ACT_GEGLU)
-    pair = ctx.op_linear(torch.cat([hid, dev(t2)], dim=1).contiguous(), dev(wf), dev(bfb), residual=dev(xin))
-    torch.cuda.synchronize()
-    e, e2 = rel_l2(out, ref), rel_l2(out, pair.float())
-    print(f"fused feed-forward vs fp32 reference {e:.3e}, vs the two-kernel path {e2:.3e}")
-    assert e <= 3e-3 and e2 <= 3e-3
-    with pytest.raises(_lib.RdmError):
-        ctx.op_ffn_fused(dev(l3[:100]), dev(t2[:100]), dev(xin[:100]), dev(w1[perm]), dev(b1[perm]), dev(wf), dev(bfb))      # M % 128

@@ -162,16 +162,9 @@ def test_rarm_forward_shipped_deep_golden_batch64(ctx):
             assert e <= 2.5e-2
 
 
-def test_rarm_decode_repeats_bitwise(ctx, tmp_path):
+def test_rarm_decode_repeats_bitwise(ctx):
     """The decode step must behave like a deterministic function: 40 repeated 24-token decodes of a 64-sequence batch at the shipped size are
-    compared BIT FOR BIT with the first one (every kernel of the default step is block-local: fixed summation orders, no atomics).
-    The four-blocks-per-sequence cross-attention (RDM_RARM_XSPLIT=1: partial rows handed over as self-validating {value, epoch} granules and
-    one monotonic arrival counter, rarm.hip's hand-over note -- round 6) runs the same repeats in a child process: its result must agree with
-    the one-block form (another summation order: a bound, not bits) and EVERY repeat must equal its own first run (round 5's form, which
-    trusted store completion to mean visibility, showed one differing repeat in ~6 800; tools/rarm_stress.py is the long version)."""
-    import os
-    import subprocess
-    import sys
+    compared BIT FOR BIT with the first one (every kernel of the default step is block-local: fixed summation orders, no atomics)."""
     spec = orarm.shipped_rarm_spec()
     _load(ctx, spec, 77)
     gen = torch.Generator().manual_seed(5)
@@ -182,26 +175,6 @@ def test_rarm_decode_repeats_bitwise(ctx, tmp_path):
     for rep in range(39):
         again = ctx.rarm_forward(tokens, context).cpu()
         assert torch.equal(again, first), f"repeat {rep + 1}: the decode step gave different bits"
-    out = tmp_path / "split.npz"
-    code = (
-        "import sys, numpy as np, torch\n"
-        f"sys.path.insert(0, {os.path.dirname(os.path.dirname(os.path.abspath(__file__)))!r}); sys.path.insert(0, {os.path.dirname(os.path.abspath(__file__))!r})\n"
-        "import rdm_amd\nfrom rdm_amd import _lib, packing\nfrom oracle import rarm as orarm, unet as ounet\n"
-        "import test_gpu_rarm as T\n"
-        "torch.set_grad_enabled(False)\nctx = _lib.Context(0)\nspec = orarm.shipped_rarm_spec()\nT._load(ctx, spec, 77)\n"
-        "gen = torch.Generator().manual_seed(5)\ntokens = torch.randint(0, spec.vocab_out, (64, 24), generator=gen)\n"
-        "context = torch.randn((64, 8, spec.context_dim), generator=gen) * 0.45\n"
-        "first = ctx.rarm_forward(tokens, context).cpu()\n"
-        "bad = sum(0 if torch.equal(ctx.rarm_forward(tokens, context).cpu(), first) else 1 for _ in range(39))\n"
-        f"np.savez({str(out)!r}, first=first.numpy(), bad=np.int64(bad))\n")
-    env = dict(os.environ, RDM_RARM_XSPLIT="1")
-    r = subprocess.run([sys.executable, "-c", code], env=env, capture_output=True, text=True, timeout=600)
-    assert r.returncode == 0, r.stderr[-2000:]
-    got = np.load(out)
-    e = rel_l2(torch.from_numpy(got["first"]), first)
-    print(f"four-block cross-attention vs the one-block form, rel L2: {e:.3e}; its repeats differing from its first run: {int(got['bad'])} of 39")
-    assert e <= 1.5e-2          # (the parity bound against the reference is 2.5e-2: tests above)
-    assert int(got["bad"]) == 0
 
 
 def test_rarm_sampler_kernel_exact_at_vocab_16384(ctx):

@@ -33,6 +33,17 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in _lib.lib.rdm_version()
 
 
+def test_native_library_reads_only_the_kept_environment_switches():
+    """The library's environment switches are a closed list: the deterministic mode and four test / tool hooks (csrc/common.h, rdm_env_int).
+    A new `getenv("RDM_...")` in csrc/ must be driven by a test or not be added."""
+    import glob
+    csrc = os.path.join(ROOT, "retrieval-augmented-diffusion-models_amd", "csrc")
+    names = set()
+    for path in glob.glob(os.path.join(csrc, "*.hip")) + glob.glob(os.path.join(csrc, "*.h")):
+        names |= set(re.findall(r'getenv\("(RDM_[A-Z0-9_]+)', open(path).read()))
+    assert names == {"RDM_DETERMINISTIC", "RDM_MGEMM_ANY", "RDM_MGEMM_FROM", "RDM_VQ_RANGE", "RDM_OP_FRAG_CACHE"}, sorted(names)
+
+
 @pytest.mark.skipif(torch.cuda.is_available(), reason="checks the no-GPU failure mode")
 def test_no_cpu_fallback():
     import rdm_amd  # noqa: F401

@@ -1,5 +1,5 @@
 #!/bin/bash
-# Same-box comparison of several builds / switch settings of the headline bench: tools/ab_multi.sh TAG "ENV.." "ENV.." ...  (two rounds, interleaved)
+# Same-box comparison of several builds of the headline bench: tools/ab_multi.sh TAG "RDM_HIP_LIB=.." "" ...  (two rounds, interleaved)
 TAG=$1; shift
 OUT=gpurun_out/abm_$TAG.log; mkdir -p gpurun_out; : > $OUT
 for rep in 1 2; do

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """Self-attention (d_head = 32) kernel timing at the UNet's three token counts, fused q | k | v operand (token-major V) as the sampler
-runs it.  usage: attn_bench.py   env: RDM_FLASH_VAR (inner-loop variant bits, attention.hip), RDM_FLASH_OLD"""
+runs it.  usage: attn_bench.py"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
 """3x3-conv kernel bench over the UNet's conv shapes through the C ABI (GPU box only), plus multi-tile parity checks.
-usage: conv_bench.py [check] [bench]      env: RDM_NO_HALO4=1 -> the 8-wave ping-pong kernel, RDM_HALO_PROF=1 -> cycle breakdown"""
+usage: conv_bench.py [check] [bench]"""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,5 @@
 #!/usr/bin/env python3
-"""Timing of single linear GEMM shapes through the C ABI (GPU box only).  usage: lin_bench.py M,N,K[,res] ...   env: RDM_NO_LIN4, RDM_L4_VAR, RDM_LIN4_PROF"""
+"""Timing of single linear GEMM shapes through the C ABI (GPU box only).  usage: lin_bench.py M,N,K[,res] ..."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,6 @@
 #!/bin/bash
-# RARM decode (config #5) img/s at several batch sizes under dev-switch settings given as "ENV=.. ENV=.." strings (A/B on one box)
+# RARM decode (config #5) img/s at several batch sizes under environment settings given as "ENV=.. ENV=.." strings (A/B on one box,
+# e.g. "RDM_HIP_LIB=<other build>" "")
 OUT=gpurun_out/rarm_sweep.log; mkdir -p gpurun_out; : > $OUT
 BATCHES=${BATCHES:-"64 128 256 512"}
 for v in "$@"; do

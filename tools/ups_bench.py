@@ -1,6 +1,6 @@
 #!/usr/bin/env python3
-"""The UNet's three Upsample convs (nearest 2x + conv3x3) at the benchmark batch: time per call.  RDM_NO_UPS_PHASE=1 times the fused-upsample
-halo kernel (nine taps at output resolution) instead of the four-phase form (2 x 2 taps at source resolution).  GPU box only."""
+"""The UNet's three Upsample convs (nearest 2x + conv3x3, run as four 2 x 2-tap phases at source resolution) at the benchmark batch: time
+per call.  GPU box only."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)

@@ -1,5 +1,5 @@
 """Weight-gradient kernels at the shipped UNet's training shapes (batch 64): time per call and MFMA rate of op_conv3x3_wgrad /
-op_linear_wgrad.  RDM_NO_WGRAD_TN=1 in the environment times the round-3 path (transposes + K-major GEMM + plane sums) instead.
+op_linear_wgrad.
     python tools/wgrad_bench.py [--batch 64]"""
 import argparse
 import os
