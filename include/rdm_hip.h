@@ -148,6 +148,13 @@ int rdm_unet_forward(rdm_ctx* ctx, const float* x, const int64_t* t, const float
 int rdm_ddim_num_intermediates(int S, int log_every_t);
 int rdm_ddim_sample(rdm_ctx* ctx, const rdm_ddim_args* args, const float* x_T, const float* cond, const float* uncond,
                     const float* noise, float* z_out, float* x_inter, float* pred_x0_inter);
+/* ldm PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py): pseudo linear multistep sampling on DDIM's
+ * schedule with eta = 0 (args->eta != 0 is an error, as make_schedule's ValueError; temperature has no effect there).  The first step is
+ * the pseudo improved Euler step (two forwards), later steps combine the guided eps with up to three earlier ones: S' + 1 forwards for
+ * S' sampler timesteps.  Arguments as rdm_ddim_sample without the noise stack; the intermediates follow the DDIM rule
+ * (n_inter = rdm_ddim_num_intermediates), pred_x0_inter holding the pred_x0 of the combined eps. */
+int rdm_plms_sample(rdm_ctx* ctx, const rdm_ddim_args* args, const float* x_T, const float* cond, const float* uncond,
+                    float* z_out, float* x_inter, float* pred_x0_inter);
 /* ldm LatentDiffusion.p_sample_loop / p_sample (no CFG on this path).
  * noise [dev] f32 [timesteps,B,C,H,W], consumed in loop order. */
 int rdm_ddpm_sample(rdm_ctx* ctx, const rdm_ddpm_args* args, const float* x_T, const float* cond, const float* noise,

@@ -85,6 +85,7 @@ SIGNATURES = {
     "rdm_unet_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_ddim_num_intermediates": (C.c_int, [C.c_int, C.c_int]),
     "rdm_ddim_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, _P, _P, _P, _P]),
+    "rdm_plms_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, _P, _P, _P]),
     "rdm_ddpm_sample": (C.c_int, [_P, C.POINTER(DdpmArgs), _P, _P, _P, _P]),
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
@@ -469,6 +470,30 @@ class Context:
             pi = torch.empty_like(xi)
         self._check(lib.rdm_ddim_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(noise), _ptr(z),
                                         _ptr(xi), _ptr(pi)))
+        return z, xi, pi
+
+    def plms_sample(self, S, x_T, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False):
+        """ldm PLMSSampler's loop (eta = 0) on DDIM's schedule: S' + 1 UNet forwards for S' sampler timesteps.  Returns
+        (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
+        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
+        uncond = None if uncond is None else self._dev(uncond, torch.float32)
+        ac = np.ascontiguousarray(alphas_cumprod.detach().cpu().numpy() if isinstance(alphas_cumprod, torch.Tensor)
+                                  else alphas_cumprod, dtype=np.float32)
+        self._check_sampler_shapes("plms_sample", x_T, cond, uncond)
+        if scale > 1.0 and uncond is None:
+            raise RdmError("plms_sample: unconditional_conditioning is required when unconditional_guidance_scale > 1")
+        B, Cc, H, W = x_T.shape
+        a = DdimArgs(S=S, batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, eta=0.0, temperature=1.0,
+                     unconditional_guidance_scale=scale, log_every_t=log_every_t, T=ac.shape[0],
+                     alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)))
+        z = torch.empty_like(x_T)
+        xi = pi = None
+        if want_intermediates:
+            total = len(range(0, ac.shape[0], max(ac.shape[0] // max(int(S), 1), 1)))
+            n = lib.rdm_ddim_num_intermediates(total, log_every_t)
+            xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
+            pi = torch.empty_like(xi)
+        self._check(lib.rdm_plms_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
         return z, xi, pi
 
     def ddpm_sample(self, timesteps, x_T, cond, noise, sched, clip_denoised=True, temperature=1.0):

@@ -73,6 +73,21 @@ struct DdimStepParams {
     int cfg;
 };
 
+// One PLMS step (ldm PLMSSampler.p_sample_plms, eta = 0).  mode PLMS_STEP: e_t = CFG(eps) -> e_store, e' from `order` history
+// tensors (h1 = o[-1], h2 = o[-2], h3 = o[-3]; e_store may alias h3: each element is read before it is written), x_out = update(x, e').
+// mode PLMS_EULER_A (first step, before the t_next forward): e_t -> e_store, x_out = update(x, e_t) (x_tmp; no pred_x0).
+// mode PLMS_EULER_B (after it): e' = (e_prev + CFG(eps)) / 2, x_out = update(x, e').  x_dup: second half of the CFG-doubled batch or null.
+enum { PLMS_STEP = 0, PLMS_EULER_A = 1, PLMS_EULER_B = 2 };
+struct PlmsStepParams {
+    const float* x; const float* eps;                        // eps: [n] rows (scale == 1) or [2n] (cond | uncond)
+    const float* e_prev;                                     // PLMS_EULER_B: the step's stored e_t
+    const float* h1; const float* h2; const float* h3;       // PLMS_STEP history (order of them are read)
+    float* e_store; float* x_out; float* x_dup; float* pred_x0;
+    long long n;                                             // B*C*H*W
+    float a_t, a_prev, sqrt_one_minus_at, scale;
+    int cfg, mode, order;
+};
+
 struct DdpmStepParams {
     const float* x; const float* eps; const float* noise; float* x_prev; long long n;
     float sqrt_recip, sqrt_recipm1, coef1, coef2, log_var; int clip, nonzero; float temperature;
@@ -215,6 +230,7 @@ hipError_t launch_add_bias_rows(const bf16_t* x, const float* bias, bf16_t* out,
 hipError_t launch_row_nonzero(const float* x, int rows, long long n, int* flag, hipStream_t st);   // flag[r] = row r has a non-zero element
 hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st);
 hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st);
+hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
 hipError_t launch_vq_quantize(const float* z, const float* codebook, int n_embed, const float* pq_w, const float* pq_b,
                               float* out, int* idx_out, int B, int HW, int quantize, hipStream_t st);
 hipError_t launch_softmax_rows(const float* s, bf16_t* p, long long rows, int n, hipStream_t st, int n_valid = 0);   // columns >= n_valid: probability 0

@@ -515,6 +515,79 @@ hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ PLMS update (fp32, eta = 0)
+// ldm PLMSSampler.p_sample_plms: CFG combine, the linear-multistep combination of e_t with up to three earlier e_t, and the DDIM
+// update (get_x_prev_and_pred_x0 with sigma_t = 0), one pass per step.  Same association, true divisions and no FMA contraction as the
+// torch expressions, so a torch restatement agrees to rounding.  V = 4: float4 accesses (the launcher checks n % 4 and alignment).
+template <int V> __device__ __forceinline__ void plms_ld(const float* p, long long i, float (&v)[V]) {
+    if constexpr (V == 4) { const float4 t = *(const float4*)(p + i); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    else v[0] = p[i];
+}
+template <int V> __device__ __forceinline__ void plms_st(float* p, long long i, const float (&v)[V]) {
+    if constexpr (V == 4) *(float4*)(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+    else p[i] = v[0];
+}
+template <int V>
+__global__ __launch_bounds__(256) void plms_step_kernel(PlmsStepParams p) {
+#pragma clang fp contract(off)
+    const float sa = sqrtf(p.a_t), sap = sqrtf(p.a_prev), s1p = sqrtf(1.0f - p.a_prev);
+    const long long nv = p.n / V;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * V;
+        float e[V], x[V], o[V];
+        plms_ld<V>(p.eps, i, e);
+        if (p.cfg) {
+            float u[V]; plms_ld<V>(p.eps + p.n, i, u);
+#pragma unroll
+            for (int k = 0; k < V; k++) e[k] = u[k] + p.scale * (e[k] - u[k]);
+        }
+        plms_ld<V>(p.x, i, x);
+        if (p.mode == PLMS_EULER_B) {
+            float q[V]; plms_ld<V>(p.e_prev, i, q);
+#pragma unroll
+            for (int k = 0; k < V; k++) o[k] = (q[k] + e[k]) / 2.0f;
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; k++) o[k] = e[k];
+            if (p.mode == PLMS_STEP && p.order >= 1) {
+                float a[V]; plms_ld<V>(p.h1, i, a);
+                if (p.order == 1) {
+#pragma unroll
+                    for (int k = 0; k < V; k++) o[k] = (3.0f * e[k] - a[k]) / 2.0f;
+                } else {
+                    float b[V]; plms_ld<V>(p.h2, i, b);
+                    if (p.order == 2) {
+#pragma unroll
+                        for (int k = 0; k < V; k++) o[k] = (23.0f * e[k] - 16.0f * a[k] + 5.0f * b[k]) / 12.0f;
+                    } else {
+                        float c[V]; plms_ld<V>(p.h3, i, c);
+#pragma unroll
+                        for (int k = 0; k < V; k++) o[k] = (55.0f * e[k] - 59.0f * a[k] + 37.0f * b[k] - 9.0f * c[k]) / 24.0f;
+                    }
+                }
+            }
+            plms_st<V>(p.e_store, i, e);          // after the history reads: e_store may be h3's slot
+        }
+        float xo[V], x0[V];
+#pragma unroll
+        for (int k = 0; k < V; k++) { x0[k] = (x[k] - p.sqrt_one_minus_at * o[k]) / sa; xo[k] = sap * x0[k] + s1p * o[k]; }
+        plms_st<V>(p.x_out, i, xo);
+        if (p.x_dup) plms_st<V>(p.x_dup, i, xo);
+        if (p.pred_x0) plms_st<V>(p.pred_x0, i, x0);
+    }
+}
+hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st) {
+    if (p.n <= 0) return hipSuccess;
+    const void* ptrs[] = {p.x, p.eps, p.e_prev, p.h1, p.h2, p.h3, p.e_store, p.x_out, p.x_dup, p.pred_x0};
+    bool vec = p.n % 4 == 0;
+    for (const void* q : ptrs) vec = vec && ((uintptr_t)q % 16 == 0);        // (null is aligned)
+    const long long nv = vec ? p.n / 4 : p.n;
+    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
+    if (vec) plms_step_kernel<4><<<grid, 256, 0, st>>>(p);
+    else plms_step_kernel<1><<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
+}
+
 // out[r, :] = x[r, :] + bias[:]   (bf16 rows, 8 columns per thread).  Cross-attention of a sample whose neighbours are all-zero
 // vectors -- the unconditional half of a guided batch, rdm/models/diffusion/ddpm.py:673-680 -- is exactly to_out.bias: K = V = 0
 // gives uniform attention over zero values (rdm/modules/attention.py:52-72), so t2 = t1 + b_o without any GEMM.

@@ -1602,6 +1602,44 @@ static int prepare_kv(rdm_ctx* c, const float* cond, const float* uncond, int B,
     });
 }
 
+// DDIM schedule (ldm make_ddim_timesteps 'uniform' + make_ddim_sampling_parameters): the timesteps ts, the fp32 alphas a_t,
+// alphas_prev a_prev and np.sqrt(1 - a_t) of every step (shared by the DDIM and PLMS loops; sigma is the DDIM loop's own)
+static int ddim_schedule(rdm_ctx* c, const rdm_ddim_args* a, std::vector<int>& ts, std::vector<float>& at, std::vector<float>& ap,
+                         std::vector<float>& s1m) {
+    if (a->S < 1 || a->S > a->T || !a->alphas_cumprod) return c->fail(-1, "bad schedule");
+    const int step = a->T / a->S;
+    ts.clear();
+    for (int i = 0; i < a->T && (int)ts.size() < (a->T + step - 1) / step; i += step) ts.push_back(i + 1);
+    const int total = (int)ts.size();
+    for (int v : ts) if (v >= a->T) return c->fail(-1, "ddim timestep %d out of range for T=%d (S must divide the schedule like the reference)", v, a->T);
+    at.resize(total); ap.resize(total); s1m.resize(total);
+    for (int i = 0; i < total; i++) {
+        at[i] = a->alphas_cumprod[ts[i]];
+        ap[i] = (i == 0) ? a->alphas_cumprod[0] : a->alphas_cumprod[ts[i - 1]];
+        s1m[i] = std::sqrt(1.0f - at[i]);         // np.sqrt on the fp32 tensor (ddim.py:52)
+    }
+    return 0;
+}
+
+// Every sample of a step shares the step's timestep, and the sampler's timesteps are known before the loop: their time-embedding rows
+// (MLP + the 22 emb_layers) are computed ONCE per call as row GEMMs into a table (row i <-> ts[i]), instead of three B-row GEMMs per
+// forward (72 us of a 29 ms forward).  Not in deterministic mode (the rows must come out of the same kernel configuration as
+// rdm_unet_forward's): *table stays null there.
+static int sampler_emb_table(rdm_ctx* c, const std::vector<int>& ts, const float** table) {
+    *table = nullptr;
+    if (c->deterministic) return 0;
+    UNet& u = c->unet;
+    const size_t total = ts.size();
+    RDM_TRY(ensure_bytes(c, (char**)&u.emb_table, &u.emb_table_bytes, total * u.emb_total * 4 + total * 8 + 256));
+    long long* tuniq = (long long*)((char*)u.emb_table + ((total * u.emb_total * 4 + 255) & ~(size_t)255));
+    std::vector<long long> th(ts.begin(), ts.end());
+    RDM_CHECK_HIP(c, hipMemcpyAsync(tuniq, th.data(), total * 8, hipMemcpyHostToDevice, c->stream));
+    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
+    RDM_TRY(run_with_arena(c, u.arena, u.blob, [&](Ops& o) { unet_time_rows(o, u, tuniq, (int)total, u.emb_table); }));
+    *table = u.emb_table;
+    return 0;
+}
+
 int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
                     const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
@@ -1612,23 +1650,16 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
     const bool cfg = a->unconditional_guidance_scale > 1.0f;
     if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1 (ddim.py:231)");
     if (a->eta != 0.f && !noise) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
-    if (a->S < 1 || a->S > a->T || !a->alphas_cumprod) return c->fail(-1, "bad schedule");
-    const int B = a->batch, k = a->k, S = a->S;
+    const int B = a->batch, k = a->k;
     const long long n1 = (long long)B * a->channels * a->height * a->width;
-    // schedule (ldm make_ddim_timesteps 'uniform' + make_ddim_sampling_parameters)
-    const int step = a->T / S;
-    std::vector<int> ts; for (int i = 0; i < a->T && (int)ts.size() < (a->T + step - 1) / step; i += step) ts.push_back(i + 1);
+    std::vector<int> ts; std::vector<float> at, ap, s1m;
+    RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
     const int total = (int)ts.size();
-    for (int v : ts) if (v >= a->T) return c->fail(-1, "ddim timestep %d out of range for T=%d (S must divide the schedule like the reference)", v, a->T);
-    std::vector<float> at(total), ap(total), sg(total), s1m(total);
+    std::vector<float> sg(total);
     for (int i = 0; i < total; i++) {
-        at[i] = a->alphas_cumprod[ts[i]];
-        const double apd = (i == 0) ? (double)a->alphas_cumprod[0] : (double)a->alphas_cumprod[ts[i - 1]];
-        ap[i] = (float)apd;
         // sigma computed in float64 from the fp32 alphas like numpy does with a float64 alphas_prev array
-        const double atd = (double)at[i];
+        const double atd = (double)at[i], apd = (double)ap[i];
         sg[i] = (float)((double)a->eta * std::sqrt((1.0 - apd) / (1.0 - atd) * (1.0 - atd / apd)));
-        s1m[i] = std::sqrt(1.0f - at[i]);         // np.sqrt on the fp32 tensor (ddim.py:52)
     }
     // scratch: [cond|uncond] f32, x2 [2B], t [total][2B] int64, eps [2B]
     const int nb = cfg ? 2 * B : B;
@@ -1648,19 +1679,8 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
     }
     RDM_CHECK_HIP(c, hipMemcpyAsync(x2, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
     int n_logged = 0;
-    // Every sample of a step shares the step's timestep, and the S timesteps are known now: their time-embedding rows (MLP + the 22 emb_layers)
-    // are computed ONCE per call as S-row GEMMs into a table, instead of three B-row GEMMs per forward (72 us of a 29 ms forward).  Not in
-    // deterministic mode (the rows must come out of the same kernel configuration as rdm_unet_forward's).
     const float* emb_table = nullptr;
-    if (!c->deterministic) {
-        RDM_TRY(ensure_bytes(c, (char**)&u.emb_table, &u.emb_table_bytes, (size_t)total * u.emb_total * 4 + (size_t)total * 8 + 256));
-        long long* tuniq = (long long*)((char*)u.emb_table + (((size_t)total * u.emb_total * 4 + 255) & ~(size_t)255));
-        std::vector<long long> th(ts.begin(), ts.end());
-        RDM_CHECK_HIP(c, hipMemcpyAsync(tuniq, th.data(), (size_t)total * 8, hipMemcpyHostToDevice, c->stream));
-        RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-        RDM_TRY(run_with_arena(c, u.arena, u.blob, [&](Ops& o) { unet_time_rows(o, u, tuniq, total, u.emb_table); }));
-        emb_table = u.emb_table;
-    }
+    RDM_TRY(sampler_emb_table(c, ts, &emb_table));
     for (int i = 0; i < total; i++) {
         const int index = total - i - 1;
         if (cfg && i == 0) RDM_CHECK_HIP(c, hipMemcpyAsync(x2 + n1, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));   // later steps: ddim_step writes both halves
@@ -1673,6 +1693,87 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
         p.n_per_batch = n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sigma_t = sg[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.temperature = a->temperature; p.cfg = cfg ? 1 : 0;
         RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
+        if (log) {
+            if (x_inter) RDM_CHECK_HIP(c, hipMemcpyAsync(x_inter + (size_t)n_logged * n1, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+            n_logged++;
+        }
+    }
+    RDM_CHECK_HIP(c, hipMemcpyAsync(z_out, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+// ldm PLMSSampler.plms_sampling / p_sample_plms (eta = 0): DDIM's schedule, timesteps and intermediates, total + 1 forwards.  The
+// first step is the pseudo improved Euler step: phase A stores e_t and writes x_tmp = update(x, e_t) into the UNet input, a forward at
+// t_next (one of the table's rows) follows, phase B updates the kept x with (e_t + e_next) / 2.  Later steps combine e_t with up to
+// three earlier e_t held in a ring of three slots, rotated by pointer (the newest e_t takes the oldest slot in the same pass).
+int rdm_plms_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
+                    float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    UNet& u = c->unet;
+    if (!u.loaded) return c->fail(-1, "unet weights not loaded");
+    if (a->eta != 0.f) return c->fail(-1, "ddim_eta must be 0 for PLMS");
+    if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1");
+    const bool cfg = a->unconditional_guidance_scale > 1.0f;
+    if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1");
+    const int B = a->batch, k = a->k;
+    const long long n1 = (long long)B * a->channels * a->height * a->width;
+    std::vector<int> ts; std::vector<float> at, ap, s1m;
+    RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
+    const int total = (int)ts.size();
+    // scratch: [cond|uncond] f32, x2 [2B], t [total][2B] int64, eps [2B], the kept x [B], 3 history slots [B]
+    const int nb = cfg ? 2 * B : B;
+    const size_t cd_bytes = (size_t)nb * k * u.cfg.context_dim * 4;
+    const size_t x2_bytes = (size_t)nb * (n1 / B) * 4, t_bytes = (size_t)total * nb * 8, eps_bytes = x2_bytes, x1_bytes = (size_t)n1 * 4;
+    const auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
+    const size_t off_x2 = al(cd_bytes), off_t = al(off_x2 + x2_bytes), off_eps = al(off_t + t_bytes), off_xk = al(off_eps + eps_bytes),
+                 off_h = al(off_xk + x1_bytes), h_stride = al(x1_bytes);
+    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, off_h + 3 * h_stride));
+    int nbe = 0;
+    RDM_TRY(prepare_kv(c, cond, cfg ? uncond : nullptr, B, k, &nbe));
+    float* x2 = (float*)(c->samp + off_x2); long long* tdev = (long long*)(c->samp + off_t); float* eps = (float*)(c->samp + off_eps);
+    float* xk = (float*)(c->samp + off_xk);
+    float* slot[3] = {(float*)(c->samp + off_h), (float*)(c->samp + off_h + h_stride), (float*)(c->samp + off_h + 2 * h_stride)};
+    {
+        std::vector<long long> th((size_t)total * nb);
+        for (int i = 0; i < total; i++) for (int j = 0; j < nb; j++) th[(size_t)i * nb + j] = ts[i];
+        RDM_CHECK_HIP(c, hipMemcpyAsync(tdev, th.data(), t_bytes, hipMemcpyHostToDevice, c->stream));
+        RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));   // th goes out of scope
+    }
+    RDM_CHECK_HIP(c, hipMemcpyAsync(x2, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+    if (cfg) RDM_CHECK_HIP(c, hipMemcpyAsync(x2 + n1, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));   // later: the step kernel writes both halves
+    RDM_CHECK_HIP(c, hipMemcpyAsync(xk, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));                 // the first step's x, kept beside x_tmp
+    const float* emb_table = nullptr;
+    RDM_TRY(sampler_emb_table(c, ts, &emb_table));
+    const auto forward = [&](int idx) {      // UNet on x2 = [x | x] at ts[idx], [cond | uncond]: the context-independent prefix runs once
+        return unet_forward_impl(c, x2, (const int64_t*)(tdev + (size_t)idx * nb), nullptr, u.kv_cache, nb, k, a->height, a->width, eps,
+                                 u.ctx_rows, cfg ? B : 0, emb_table ? emb_table + (size_t)idx * u.emb_total : nullptr);
+    };
+    int n_logged = 0, n_hist = 0;            // slot[0 .. n_hist) = o[-1], o[-2], o[-3]
+    for (int i = 0; i < total; i++) {
+        const int index = total - i - 1;
+        const bool log = (index % a->log_every_t == 0) || (index == total - 1);
+        PlmsStepParams p{};
+        p.eps = eps; p.n = n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sqrt_one_minus_at = s1m[index];
+        p.scale = a->unconditional_guidance_scale; p.cfg = cfg ? 1 : 0;
+        p.x_out = x2; p.x_dup = cfg ? x2 + n1 : nullptr;
+        float* e_new = slot[n_hist < 3 ? n_hist : 2];         // a free slot, or the oldest e_t (read before it is overwritten)
+        p.e_store = e_new;
+        RDM_TRY(forward(index));
+        if (n_hist == 0) {
+            p.x = xk; p.mode = PLMS_EULER_A;                   // x_tmp -> x2 (both halves); x stays in xk
+            RDM_CHECK_HIP(c, launch_plms_step(p, c->stream));
+            RDM_TRY(forward(index > 0 ? index - 1 : 0));      // t_next = time_range[min(i + 1, total - 1)]
+            p.mode = PLMS_EULER_B; p.e_prev = e_new; p.e_store = nullptr;
+        } else {
+            p.x = x2; p.mode = PLMS_STEP; p.order = n_hist;
+            p.h1 = slot[0]; p.h2 = n_hist > 1 ? slot[1] : nullptr; p.h3 = n_hist > 2 ? slot[2] : nullptr;
+        }
+        p.pred_x0 = (log && pred_x0_inter) ? pred_x0_inter + (size_t)n_logged * n1 : nullptr;
+        RDM_CHECK_HIP(c, launch_plms_step(p, c->stream));
+        for (int j = n_hist < 3 ? n_hist : 2; j > 0; j--) slot[j] = slot[j - 1];
+        slot[0] = e_new;
+        if (n_hist < 3) n_hist++;
         if (log) {
             if (x_inter) RDM_CHECK_HIP(c, hipMemcpyAsync(x_inter + (size_t)n_logged * n1, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
             n_logged++;

@@ -17,7 +17,8 @@ Deliberate differences:
 Additions (not in the reference, all optional): `--clip_ckpt` (CLIP ViT-B/32 state_dict; the reference downloads it),
 `--synthetic` (seeded random weights and database: the 6.2 GB checkpoint / 18 GB database are unreachable without a
 network), `--gpus N` (batch-sharded multi-GPU sampling, one process per GPU via torch.distributed.run, RCCL all-gather of
-the finished images; `--gpu` is then ignored and each rank uses its LOCAL_RANK).
+the finished images; `--gpu` is then ignored and each rank uses its LOCAL_RANK), `--plms` (sample with ldm's PLMSSampler on
+`--steps` instead of DDIM: same schedule, about half the steps for the same accuracy; works with `--gpus N`).
 """
 import argparse
 import datetime
@@ -62,6 +63,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--gpus", type=int, default=1, help="[native] shard each batch over this many GPUs (RCCL)")
     parser.add_argument("--shard_db", action="store_true", help="[native] with --gpus N: shard the database ROWS over the GPUs instead of "
                         "replicating them (databases beyond one GPU's memory); neighbours are merged in one exchange per search")
+    parser.add_argument("--plms", default=False, action="store_true", help="[native] sample with PLMS (ldm PLMSSampler) instead of DDIM")
     return parser
 
 
@@ -173,6 +175,11 @@ def _save_logs(logs, keys, opt, sampling_start, n):
                 raise NotImplementedError("image grids (batched_nns) belong to --save_nns")
 
 
+def _sampler_kwargs(opt: argparse.Namespace) -> dict:
+    """--plms reaches MinimalRETRODiffusion.sample_log; without it the calls are the reference's."""
+    return {"plms": True} if getattr(opt, "plms", False) else {}
+
+
 def sample_unconditional(model, opt: argparse.Namespace, is_writer=True):
     """rdm_sample.py:225-266."""
     qids = model.get_qids(opt.top_m, opt.batch_size, use_weights=opt.use_weights) if opt.keep_qids else None
@@ -183,7 +190,7 @@ def sample_unconditional(model, opt: argparse.Namespace, is_writer=True):
         print("Sampling query and neighbors (wait for the sampling to start)")
         logs = model.sample_from_rdata(opt.batch_size, qids=qids, k_nn=opt.k_nn, return_nns=opt.save_nns, use_weights=opt.use_weights,
                                        memsize=opt.top_m, unconditional_guidance_scale=opt.guidance_scale, ddim_steps=opt.steps,
-                                       ddim=True, unconditional_retro_guidance_label=0.)
+                                       ddim=True, unconditional_retro_guidance_label=0., **_sampler_kwargs(opt))
         if is_writer:
             _save_logs(logs, ["samples_with_sampled_nns", "batched_nns"], opt, sampling_start, n)
         if opt.increase_guidance:
@@ -209,7 +216,8 @@ def sample_conditional(model, opt: argparse.Namespace, is_writer=True):
         logs = model.sample_with_query(query=query_embeddings, query_embedded=True, k_nn=opt.k_nn if not opt.only_caption else 1,
                                        return_nns=opt.save_nns and not opt.only_caption, visualize_nns=opt.save_nns and not opt.only_caption,
                                        use_weights=opt.use_weights, unconditional_guidance_scale=opt.guidance_scale, ddim_steps=opt.steps,
-                                       ddim=True, unconditional_retro_guidance_label=0., omit_query=opt.omit_query and not opt.only_caption)
+                                       ddim=True, unconditional_retro_guidance_label=0., omit_query=opt.omit_query and not opt.only_caption,
+                                       **_sampler_kwargs(opt))
         print(f"Run {n + 1}/{opt.n_runs}")
         if is_writer:
             _save_logs(logs, None, opt, sampling_start, n)
