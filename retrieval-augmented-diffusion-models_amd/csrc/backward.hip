@@ -275,10 +275,16 @@ __global__ __launch_bounds__(256) void gn_bwd_stats_kernel(GnBwdParams p) {
     const int cg = p.C / p.groups; const long long n = (long long)p.HW * cg;
     const bf16_t* xb = p.x + (long long)b * p.HW * p.C + g * cg;
     const bf16_t* db = p.dy + (long long)b * p.HW * p.C + g * cg;
-    float s = 0.f, ss = 0.f;
-    for (long long i = threadIdx.x; i < n; i += 256) { const float v = bf2f(xb[(i / cg) * p.C + (i % cg)]); s += v; ss += v * v; }
-    s = block_sum_256(s, red); ss = block_sum_256(ss, red);
-    const float mean = s / (float)n, var = fmaxf(ss / (float)n - mean * mean, 0.f), rstd = rsqrtf(var + p.eps);
+    // two passes (mean, then the squared deviations), like ln_bwd_kernel: a one-pass E[x^2] - mean^2 in fp32 loses the variance of
+    // groups whose mean is large against their spread
+    float s = 0.f;
+    for (long long i = threadIdx.x; i < n; i += 256) s += bf2f(xb[(i / cg) * p.C + (i % cg)]);
+    s = block_sum_256(s, red);
+    const float mean = s / (float)n;
+    float ss = 0.f;
+    for (long long i = threadIdx.x; i < n; i += 256) { const float dv = bf2f(xb[(i / cg) * p.C + (i % cg)]) - mean; ss += dv * dv; }
+    ss = block_sum_256(ss, red);
+    const float rstd = rsqrtf(ss / (float)n + p.eps);
     float s1 = 0.f, s2 = 0.f;
     for (long long i = threadIdx.x; i < n; i += 256) {
         const int c = (int)(i % cg); const long long o = (i / cg) * p.C + c;
@@ -525,10 +531,16 @@ __global__ __launch_bounds__(256) void ln_bwd_kernel(const bf16_t* __restrict__ 
     const int r0 = blockIdx.x * rows_per_block;
     for (int r = r0 + wave; r < r0 + rows_per_block && r < M; r += 4) {
         const bf16_t* xr = x + (long long)r * C; const bf16_t* dr = dy + (long long)r * C;
-        float s = 0.f, ss = 0.f;
-        for (int c = lane; c < C; c += 64) { const float v = bf2f(xr[c]); s += v; ss += v * v; }
-        for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
-        const float mean = s / C, rstd = rsqrtf(fmaxf(ss / C - mean * mean, 0.f) + eps);
+        // exact two-pass statistics, like the forward (layernorm_kernel): a one-pass E[x^2] - mean^2 loses the variance of rows whose
+        // mean is large against their spread, and the gradient would use another rstd than the forward applied
+        float s = 0.f;
+        for (int c = lane; c < C; c += 64) s += bf2f(xr[c]);
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const float mean = s / C;
+        float ss = 0.f;
+        for (int c = lane; c < C; c += 64) { const float dv = bf2f(xr[c]) - mean; ss += dv * dv; }
+        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        const float rstd = rsqrtf(ss / C + eps);
         float s1 = 0.f, s2 = 0.f;
         for (int c = lane; c < C; c += 64) { const float xh = (bf2f(xr[c]) - mean) * rstd, dxh = bf2f(dr[c]) * gamma[c]; s1 += dxh; s2 += dxh * xh; }
         for (int o = 32; o > 0; o >>= 1) { s1 += __shfl_xor(s1, o); s2 += __shfl_xor(s2, o); }
@@ -573,7 +585,7 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const bf16_t* __restric
     const int r0 = blockIdx.x * rows_per_block, r1 = min(M, r0 + rows_per_block);
     for (int r = r0 + wave; r < r1; r += 4) {
         float xf[NV][8], df[NV][8];
-        float s = 0.f, ss = 0.f;
+        float s = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; j++) {
             if (on[j]) {
@@ -584,10 +596,18 @@ __global__ __launch_bounds__(256) void ln_bwd_vec_kernel(const bf16_t* __restric
                 for (int e = 0; e < 8; e++) { xf[j][e] = 0.f; df[j][e] = 0.f; }
             }
 #pragma unroll
-            for (int e = 0; e < 8; e++) { s += xf[j][e]; ss += xf[j][e] * xf[j][e]; }
+            for (int e = 0; e < 8; e++) s += xf[j][e];
         }
-        for (int o = 32; o > 0; o >>= 1) { s += __shfl_xor(s, o); ss += __shfl_xor(ss, o); }
-        const float mean = s * invC, rstd = rsqrtf(fmaxf(ss * invC - mean * mean, 0.f) + eps);
+        for (int o = 32; o > 0; o >>= 1) s += __shfl_xor(s, o);
+        const float mean = s * invC;
+        float ss = 0.f;                                  // second pass over the registers (exact two-pass variance, as in ln_bwd_kernel)
+#pragma unroll
+        for (int j = 0; j < NV; j++)
+            if (on[j])
+#pragma unroll
+                for (int e = 0; e < 8; e++) { const float dv = xf[j][e] - mean; ss += dv * dv; }
+        for (int o = 32; o > 0; o >>= 1) ss += __shfl_xor(ss, o);
+        const float rstd = rsqrtf(ss * invC + eps);
         float s1 = 0.f, s2 = 0.f;
 #pragma unroll
         for (int j = 0; j < NV; j++)

@@ -2447,6 +2447,7 @@ int rdm_op_layernorm_bwd_add(rdm_ctx* c, const void* x, const void* dy, const fl
                              float* dgamma, float* dbeta) {
     RDM_ENTER(c);
     if (!x || !dy || !gamma || !dx || !dgamma || !dbeta) return c->fail(-1, "rdm_op_layernorm_bwd: null argument");
+    if (M < 1 || C < 1) return c->fail(-1, "rdm_op_layernorm_bwd: M and C must be positive");
     RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, (size_t)2 * ((M + 15) / 16) * C * 4));
     RDM_CHECK_HIP(c, launch_layernorm_bwd((const bf16_t*)x, (const bf16_t*)dy, gamma, M, C, eps, (float*)c->bwd_tmp, nullptr, (bf16_t*)dx, dgamma, dbeta,
                                           c->stream, (const bf16_t*)residual));
@@ -2470,6 +2471,7 @@ int rdm_op_linear_wgrad(rdm_ctx* c, const void* dy, const void* a, float* dw, lo
 int rdm_op_colsum(rdm_ctx* c, const void* x, float* out, long long M, int N) {
     RDM_ENTER(c);
     if (!x || !out) return c->fail(-1, "rdm_op_colsum: null argument");
+    if (M < 1 || N < 1) return c->fail(-1, "rdm_op_colsum: M and N must be positive");
     RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, colsum_scratch_bytes(M, N) + 256));
     RDM_CHECK_HIP(c, launch_colsum((const bf16_t*)x, out, M, N, c->stream, (float*)c->bwd_tmp));
     return 0;
@@ -2477,12 +2479,14 @@ int rdm_op_colsum(rdm_ctx* c, const void* x, float* out, long long M, int N) {
 int rdm_op_transpose(rdm_ctx* c, const void* x, void* y, int rows, int cols) {
     RDM_ENTER(c);
     if (!x || !y) return c->fail(-1, "rdm_op_transpose: null argument");
+    if (rows < 1 || cols < 1) return c->fail(-1, "rdm_op_transpose: rows and cols must be positive");
     RDM_CHECK_HIP(c, launch_transpose_bf16((const bf16_t*)x, (bf16_t*)y, rows, cols, c->stream));
     return 0;
 }
 int rdm_op_add(rdm_ctx* c, const void* a, const void* b, void* out, long long n) {
     RDM_ENTER(c);
     if (!a || !b || !out) return c->fail(-1, "rdm_op_add: null argument");
+    if (n < 1) return c->fail(-1, "rdm_op_add: n must be positive");
     RDM_CHECK_HIP(c, launch_add_bf16((const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n, c->stream));
     return 0;
 }
@@ -2598,18 +2602,24 @@ int rdm_op_bmm(rdm_ctx* c, const void* a, const void* w, void* out_bf16, float* 
 int rdm_op_heads(rdm_ctx* c, const void* x, void* out, int B, int n, int H, int D, int ldx, int mode) {
     RDM_ENTER(c);
     if (!x || !out || B < 1 || n < 1 || H < 1) return c->fail(-1, "rdm_op_heads: bad argument");
+    if (D < 1 || D > 64) return c->fail(-1, "rdm_op_heads: D must be in 1..64");
+    if (mode < 0 || mode > 2) return c->fail(-1, "rdm_op_heads: mode must be 0, 1 or 2");
+    if (mode != 2 && (long long)ldx < (long long)H * D) return c->fail(-1, "rdm_op_heads: ldx must be at least H * D");
     RDM_CHECK_HIP(c, launch_heads((const bf16_t*)x, (bf16_t*)out, B, n, H, D, ldx, mode, c->stream));
     return 0;
 }
 int rdm_op_transpose_batched(rdm_ctx* c, const void* x, void* y, int batch, int rows, int cols) {
     RDM_ENTER(c);
     if (!x || !y || batch < 1 || batch > 65535) return c->fail(-1, "rdm_op_transpose_batched: bad argument");
+    if (rows < 1 || cols < 1) return c->fail(-1, "rdm_op_transpose_batched: rows and cols must be positive");
     RDM_CHECK_HIP(c, launch_transpose_bf16((const bf16_t*)x, (bf16_t*)y, rows, cols, c->stream, batch));
     return 0;
 }
 int rdm_op_softmax(rdm_ctx* c, const float* s, void* p_bf16, long long rows, int n, int n_valid) {
     RDM_ENTER(c);
     if (!s || !p_bf16 || n % 4) return c->fail(-1, "rdm_op_softmax: bad argument (n must be a multiple of 4)");
+    if (rows < 1 || n < 4) return c->fail(-1, "rdm_op_softmax: rows and n must be positive");
+    if (n_valid < 0 || n_valid > n) return c->fail(-1, "rdm_op_softmax: n_valid must be in 0..n (0: all columns valid)");
     RDM_CHECK_HIP(c, launch_softmax_rows(s, (bf16_t*)p_bf16, rows, n, c->stream, n_valid));
     return 0;
 }

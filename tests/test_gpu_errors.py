@@ -162,3 +162,37 @@ def test_single_op_entry_points_reject_unsupported_shapes(fresh):
     # and the context still works
     out = fresh.op_head_conv(bf(1, 8, 32, 64), torch.zeros(3, 64, 3, 3, device=d), None)
     assert out.shape == (1, 3, 8, 32) and float(out.abs().max()) == 0.0
+
+
+def test_training_primitives_refuse_bad_sizes(fresh):
+    """The backward primitives check their sizes at the C ABI instead of launching a zero-size grid or returning a bare HIP error: each
+    refusal names the op, and the context keeps working afterwards."""
+    from rdm_amd import _lib
+    d = fresh.device
+    L = _lib.lib
+    bf = torch.zeros(4096, device=d, dtype=torch.bfloat16); f = torch.zeros(4096, device=d)
+    x, y, o = bf.data_ptr(), torch.zeros_like(bf).data_ptr(), torch.zeros_like(bf).data_ptr()
+    g, g2, g3 = f.data_ptr(), torch.zeros_like(f).data_ptr(), torch.zeros_like(f).data_ptr()
+    call = lambda rc: fresh._check(rc)
+    assert "rdm_op_layernorm_bwd" in _err(lambda: call(L.rdm_op_layernorm_bwd(fresh._h, x, y, g, 0, 64, 1e-5, o, g2, g3)))      # M = 0
+    assert "rdm_op_layernorm_bwd" in _err(lambda: call(L.rdm_op_layernorm_bwd(fresh._h, x, y, g, 4, 0, 1e-5, o, g2, g3)))      # C = 0
+    assert "rdm_op_transpose" in _err(lambda: call(L.rdm_op_transpose(fresh._h, x, y, 0, 8)))                                   # rows = 0
+    assert "rdm_op_transpose" in _err(lambda: call(L.rdm_op_transpose(fresh._h, x, y, 8, -1)))                                  # cols < 0
+    assert "rdm_op_transpose_batched" in _err(lambda: call(L.rdm_op_transpose_batched(fresh._h, x, y, 2, 0, 8)))                # rows = 0
+    assert "rdm_op_transpose_batched" in _err(lambda: call(L.rdm_op_transpose_batched(fresh._h, x, y, 2, 8, 0)))                # cols = 0
+    assert "rdm_op_softmax" in _err(lambda: call(L.rdm_op_softmax(fresh._h, g, x, 0, 8, 0)))                                    # rows = 0
+    assert "n_valid" in _err(lambda: call(L.rdm_op_softmax(fresh._h, g, x, 4, 8, -1)))                                          # n_valid < 0
+    assert "n_valid" in _err(lambda: call(L.rdm_op_softmax(fresh._h, g, x, 4, 8, 9)))                                           # n_valid > n
+    assert "rdm_op_heads" in _err(lambda: call(L.rdm_op_heads(fresh._h, x, y, 1, 4, 2, 0, 64, 0)))                              # D = 0
+    assert "rdm_op_heads" in _err(lambda: call(L.rdm_op_heads(fresh._h, x, y, 1, 4, 2, 65, 130, 0)))                            # D > 64
+    assert "rdm_op_heads" in _err(lambda: call(L.rdm_op_heads(fresh._h, x, y, 1, 4, 2, 32, 63, 1)))                             # ldx < H D
+    assert "rdm_op_heads" in _err(lambda: call(L.rdm_op_heads(fresh._h, x, y, 1, 4, 2, 32, 64, 3)))                             # mode 3
+    assert "rdm_op_colsum" in _err(lambda: call(L.rdm_op_colsum(fresh._h, x, g, 0, 8)))                                         # M = 0
+    assert "rdm_op_colsum" in _err(lambda: call(L.rdm_op_colsum(fresh._h, x, g, 8, 0)))                                         # N = 0
+    assert "rdm_op_add" in _err(lambda: call(L.rdm_op_add(fresh._h, x, y, o, 0)))                                               # n = 0
+    # the context still works, and each of these ops still runs at a valid size
+    a = torch.arange(24, device=d, dtype=torch.float32).reshape(3, 8).to(torch.bfloat16)
+    assert torch.equal(fresh.op_transpose(a), a.t())
+    assert torch.equal(fresh.op_add(a, a), (a.float() * 2).to(torch.bfloat16))
+    assert torch.equal(fresh.op_colsum(a), a.float().sum(0))
+    assert torch.equal(fresh.op_softmax(torch.zeros(2, 8, device=d), n_valid=8), torch.full((2, 8), 0.125, device=d, dtype=torch.bfloat16))
