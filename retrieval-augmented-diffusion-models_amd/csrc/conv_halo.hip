@@ -246,8 +246,8 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(IgemmParams p) {
 
         // ---- epilogue (same scheme as igemm.hip): per-column bias / time-embedding add in registers, DPP lane-pair swap
         // to packed column pairs, wave-private LDS transpose (staged in the halo buffer just consumed: its successor
-        // was prefetched into the other buffer), whole rows leave as 16-byte stores, the residual arrives as 16-byte
-        // loads.  Vector-memory instruction count, not bytes, is what an epilogue pays for.
+        // was prefetched into the other buffer), whole rows leave as 16-byte stores; the residual is read in the accumulator
+        // layout and joins in fp32 before the one rounding.  Vector-memory instruction count, not bytes, is what an epilogue pays for.
         if (S > 1) {
             // split-K: this part's raw fp32 accumulators go to its plane of the workspace (bias, time-embedding row, residual and
             // the bf16 rounding happen once, in splitk_finish_kernel).  One 32x32 fragment at a time through a wave-private 4 KB
@@ -287,6 +287,9 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(IgemmParams p) {
                     for (int r = 0; r < 16; r++) {
                         v[r] = acc[i][j][r] + pbias[i][j];    // (a time-embedding row never changes inside a 32-row fragment here:
                                                               //  conv_halo_supported; run-time tests per ELEMENT are expensive, igemm.hip)
+                        // the residual joins in fp32 before the one bf16 rounding, as in conv_halo4's read-out and the K-split finisher
+                        // (added after the packed rounding it cost a second rounding: up to 2.7x the one-rounding bound)
+                        if (rb) v[r] += bf2f(rb[(long long)(mf + (r & 3) + 8 * (r >> 2) + 4 * fhalf) * p.ldo + ncol]);
                     }
                     char* wp = stg + (4 * fhalf + odd) * ROWB + (j * 32 + frow - odd) * 2;
 #pragma unroll
@@ -304,16 +307,6 @@ __global__ __launch_bounds__(512, 2) void conv3x3_halo_kernel(IgemmParams p) {
                     const int idx = it * 64 + lane, row = idx / CPR, ch = idx - row * CPR;
                     uint4 u = *(const uint4*)(stg + row * ROWB + ch * 16);
                     const long long o = (long long)(mf + row) * p.ldo + eno + ch * 8;
-                    if (rb) {
-                        const uint4 r4 = *(const uint4*)(rb + o);
-                        const uint32_t uu[4] = {u.x, u.y, u.z, u.w}, rr[4] = {r4.x, r4.y, r4.z, r4.w};
-                        uint32_t oo[4];
-#pragma unroll
-                        for (int e = 0; e < 4; e++)
-                            oo[e] = cvt_pk_bf16(__uint_as_float(uu[e] << 16) + __uint_as_float(rr[e] << 16),
-                                                __uint_as_float(uu[e] & 0xffff0000u) + __uint_as_float(rr[e] & 0xffff0000u));
-                        u = make_uint4(oo[0], oo[1], oo[2], oo[3]);
-                    }
                     *(uint4*)(ob + o) = u;
                 }
                 asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");

@@ -825,12 +825,17 @@ BF16_OUT = {"add", "sumpool2", "colsum_samples", "softmax", "softmax_bwd", "gegl
             "transpose", "heads", "expand2"}
 
 
-def standin(case, inp):
-    """the fp32 torch restatement standing in for the kernel (CPU test): fp32 arithmetic, outputs rounded like the kernel's"""
+def _bf16_out(case, inp, k):
+    return (case.name in BF16_OUT) or k == "dx" or (case.name == "silu" and not inp["grad"]) or (case.name == "bmm" and not inp["f32"])
+
+
+def standin(case, inp, bf16_out=_bf16_out):
+    """the fp32 torch restatement standing in for the kernel (CPU test): fp32 arithmetic, outputs rounded like the kernel's
+    (bf16_out(case, inp, key): which outputs the kernel writes as bf16 -- the forward ops pass their own rule)"""
     out = case.ref(inp, torch.float32)
     res = {}
     for k, v in out.items():
-        bf_out = (case.name in BF16_OUT) or k == "dx" or (case.name == "silu" and not inp["grad"]) or (case.name == "bmm" and not inp["f32"])
+        bf_out = bf16_out(case, inp, k)
         res[k] = bfr(v) if bf_out else v
     return res
 

@@ -1,0 +1,56 @@
+"""CPU check of the forward-op references (tests/_fwd_ref.py) that tests/test_gpu_forward_ops.py holds the HIP kernels to: an fp32 torch
+restatement of each op stands in for the kernel.  It must pass every per-element bound and fall outside the bound against every near
+miss -- so the bounds are wide enough for honest fp32 arithmetic and narrow enough to catch the bugs the near misses encode."""
+import pytest
+import torch
+
+import _fwd_ref as R
+from _train_ref import check, standin
+
+torch.set_num_threads(min(16, torch.get_num_threads()))
+
+# the largest shapes exist for the GPU launch geometry (lin4 tile counts, M > 16384 rows); on the CPU their smaller siblings carry the
+# same checks
+_CPU_CASES = [e for e in R.CASES if not (e[0] in (R.Linear, R.LinearLN) and e[1]["M"] * e[1]["N"] > 20_000_000)]
+
+
+@pytest.mark.parametrize("entry", _CPU_CASES, ids=[R.case_id(e) for e in _CPU_CASES])
+def test_fp32_restatement_within_bound_and_near_misses_outside(entry):
+    case, kw, path = entry
+    inp = case.make(**kw)
+    worst, margin = check(case, inp, standin(case, inp, R.bf16_out))
+    print(f"{path}: worst error / bound {worst:.3g}, closest near miss {margin:.3g}")
+
+
+def test_every_forward_op_is_parametrised():
+    names = {e[0].name for e in R.CASES}
+    assert names == {"linear", "linear_ln", "conv3x3", "groupnorm", "layernorm", "self_attention", "small_attention", "xattn_fused", "head_conv"}
+
+
+def test_case_ids_name_every_launch_path():
+    paths = " | ".join(e[2] for e in R.CASES)
+    for kernel in ("halo<128>", "halo<192>", "halo4<2>", "halo4<3>", "halo4<2, STRIP>", "K-split 2", "K-split 3", "igemm phase2", "igemm conv",
+                   "igemm ups", "igemm<128, 128", "igemm<256, 192", "igemm<128, 192", "igemm<256, 128", "res_k", "igemm<256, 256, GEGLU>",
+                   "igemm<128, 128, GEGLU>", "igemm<256, 128, GEGLU>", "lin4<plain, WM1>", "lin4<plain, WM2>", "lin4<GEGLU, WM1>",
+                   "lin4<GEGLU, WM2>", "rowvec", "sgemm", "mgemm", "LN>", "gn_onepass<NV", ", 512>", ", 1024>", "gn_stats + gn_apply",
+                   "XCD block order", "layernorm_bf16x8<1>", "layernorm_bf16x8<2>", "layernorm_kernel<f32>", "layernorm_kernel<bf16>",
+                   "flash_d32_lds_kernel<false>", "flash_d32_lds_kernel<true>", "flash_d32_kernel", "small_attention_kernel<32>",
+                   "small_attention_kernel<64>", "xattn_fused_kernel", "xattn_ln_fused_kernel", "head_conv_kernel"):
+        assert kernel in paths, kernel
+
+
+def test_bf16_ksplit_planes_fall_outside_the_bound():
+    """A plausible precision regression of the K-split: the fp32 partial planes rounded to bf16 before the finisher adds them.  An
+    fp32 emulation of it must fail the conv bound on a K-split case (the planes cancel, so each is large while the sum is small)."""
+    entry = next(e for e in R.CASES if e[0] is R.Conv3x3 and "K-split 2" in e[2])
+    inp = R.Conv3x3.make(**entry[1])
+    S, C = inp["S"], inp["x"].shape[3]
+    ns = C // 64
+    y = 0
+    for s in range(S):
+        lo, hi = s * ns // S * 64, (s + 1) * ns // S * 64
+        y = y + R.bfr(R.Conv3x3.conv(inp, torch.float32, x=inp["x"][..., lo:hi], w=inp["w"][:, lo:hi]))
+    out = {"out": R.bfr(R.Conv3x3.epilogue(inp, torch.float32, y))}
+    with pytest.raises(AssertionError, match="worst error / bound"):
+        check(R.Conv3x3, inp, out)
+
