@@ -503,37 +503,26 @@ struct rdm_ctx {
     struct FragVal { bf16_t* frag; float* sb; };
     std::unordered_map<FragKey, FragVal, FragKeyHash> wfrag;
     char* bwd_tmp = nullptr; size_t bwd_tmp_bytes = 0;          // scratch of the backward ops (backward.hip)
-    char* wfrag_tmp = nullptr; size_t wfrag_tmp_bytes = 0;      // rdm_op_conv3x3 / rdm_op_linear: caller-owned weights are re-packed per call
+    char* wfrag_tmp = nullptr; size_t wfrag_tmp_bytes = 0;      // derived copies of caller-owned weights, re-packed per call (Ops::derived)
     void drop_frags() { for (auto& kv : wfrag) { (void)hipFree(kv.second.frag); if (kv.second.sb) (void)hipFree(kv.second.sb); } wfrag.clear(); }
+    // derived copy of kind `kind` of the weight W [N][K] (conv kinds: K = input channels): 0 = fragment-ordered 3x3 conv weights
+    // (conv_halo4.hip), 1 / 2 = fragment-ordered Linear / 1x1 weights (lin4.hip; 2: GEGLU-ordered), 5 = [4][N][2][2][Cin] phase weights of
+    // a fused-upsample conv (igemm.hip CONV == 3)
+    static size_t derived_bytes(int kind, int N, int K) { return (size_t)N * K * 2 * (kind == 0 ? 9 : kind == 5 ? 16 : 1); }
+    hipError_t pack_derived(int kind, const bf16_t* W, bf16_t* d, int N, int K) {
+        return kind == 0 ? launch_conv_w_fragpack(W, d, N, K, stream)
+             : kind == 5 ? launch_conv_phase_weights(W, d, N, K, stream)
+                         : launch_lin_w_fragpack(W, d, N, K, K, kind == 2, stream);
+    }
     // (the copies are packed on `stream`; rdm_set_stream synchronises the old stream before it installs another one, so a copy is
     //  complete before any other stream can launch a kernel that reads it)
-    const bf16_t* frag_for(const bf16_t* W, int N, int Cin) {
-        const FragKey key{W, N, Cin, 0, nullptr};
+    const bf16_t* cached_derived(const bf16_t* W, int N, int K, int kind) {
+        const FragKey key{W, N, K, kind, nullptr};
         auto it = wfrag.find(key);
         if (it != wfrag.end()) return it->second.frag;
         bf16_t* d = nullptr;
-        if (hipMalloc((void**)&d, (size_t)N * 9 * Cin * 2) != hipSuccess) return nullptr;
-        if (launch_conv_w_fragpack(W, d, N, Cin, stream) != hipSuccess) { (void)hipFree(d); return nullptr; }
-        wfrag[key] = FragVal{d, nullptr};
-        return d;
-    }
-    const bf16_t* phase_weights_for(const bf16_t* W, int N, int Cin) {           // [4][N][2][2][Cin] of a fused-upsample conv (igemm.hip CONV == 3)
-        const FragKey key{W, N, Cin, 5, nullptr};
-        auto it = wfrag.find(key);
-        if (it != wfrag.end()) return it->second.frag;
-        bf16_t* d = nullptr;
-        if (hipMalloc((void**)&d, (size_t)16 * N * Cin * 2) != hipSuccess) return nullptr;
-        if (launch_conv_phase_weights(W, d, N, Cin, stream) != hipSuccess) { (void)hipFree(d); return nullptr; }
-        wfrag[key] = FragVal{d, nullptr};
-        return d;
-    }
-    const bf16_t* frag_for_lin(const bf16_t* W, int N, int K, int geglu) {       // fragment-ordered copy of a Linear / 1x1 weight (lin4.hip)
-        const FragKey key{W, N, K, geglu ? 2 : 1, nullptr};
-        auto it = wfrag.find(key);
-        if (it != wfrag.end()) return it->second.frag;
-        bf16_t* d = nullptr;
-        if (hipMalloc((void**)&d, (size_t)N * K * 2) != hipSuccess) return nullptr;
-        if (launch_lin_w_fragpack(W, d, N, K, K, geglu, stream) != hipSuccess) { (void)hipFree(d); return nullptr; }
+        if (hipMalloc((void**)&d, derived_bytes(kind, N, K)) != hipSuccess) return nullptr;
+        if (pack_derived(kind, W, d, N, K) != hipSuccess) { (void)hipFree(d); return nullptr; }
         wfrag[key] = FragVal{d, nullptr};
         return d;
     }
@@ -579,6 +568,10 @@ static int ensure_bytes(rdm_ctx* c, char** p, size_t* have, size_t need) {
 }
 
 // ------------------------------------------------------------------------------------ op helpers
+static int gn_chunks(int HW) { const int n = HW / 64; return n < 1 ? 1 : n > 32 ? 32 : n; }      // GroupNorm statistics: pixel chunks per sample
+
+// The kernel dispatch of the model executors and of the operator-level entries (rdm_op_*): which kernel runs an op, with which
+// parameters.  Weight and bias arguments are device pointers (executors: o.w<T>(offset) into the model blob).
 struct Ops {
     rdm_ctx* c; Arena* ar; const char* blob; bool plan; int rc = 0;
     template <typename T> const T* w(size_t off) const { return (const T*)(blob + off); }
@@ -591,6 +584,23 @@ struct Ops {
         IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.ldo = N; p.zero_page = c->zero_page;
         p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1; return p;
     }
+    // Derived weight copies (rdm_ctx::derived_bytes): with constant weights (the executors' blobs; the op entries when their caller promises
+    // constant weights) built once per weight and cached in the context, otherwise packed per call into wfrag_tmp.
+    // null: the copy could not be made, and the op runs a kernel that reads W itself.
+    bool const_weights = true;
+    const bf16_t* derived(const bf16_t* W, int N, int K, int kind) {
+        if (const_weights) return c->cached_derived(W, N, K, kind);
+        if (ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, rdm_ctx::derived_bytes(kind, N, K)) != 0) return nullptr;
+        bf16_t* d = (bf16_t*)c->wfrag_tmp;
+        return c->pack_derived(kind, W, d, N, K) == hipSuccess ? d : nullptr;
+    }
+    bool single_row = false;     // set by callers around ops whose operand has one row per sample (see linear)
+    int rows_hint = 0;           // rows per sample of the operand of the linear ops that follow (0 = unknown); set by the UNet block executors
+    // skinny (weight-streaming) kernel for decode-sized operands.  Fast mode: whenever M <= 128, and for `single_row` operands up to
+    // single_max rows.  Deterministic mode: exactly for the ops with ONE row per sample (`single_row`: time embedding, RARM decode step,
+    // CLIP projection), at any batch (one-row-per-sample operands of bigger batches -- RARM decode at 128+ sequences per GPU -- keep the
+    // skinny kernel: its row blocks scale with M, while the tiled kernels would run a dozen 256-row tiles)
+    bool skinny(int M, int single_max) const { return c->deterministic ? single_row : (M <= 128 || (single_row && M <= single_max)); }
     // out[M,N] = act(A[M,K] W^T + bias) (+res)
     // a1_wrap_rows > 0: A1 holds that many rows only, row m reads m % a1_wrap_rows (lin4 only: callers check lin4_takes first)
     bool lin4_takes(int M, int N, int C0, int C1, int a1_wrap_rows, int res_wrap_rows = 0) {
@@ -601,42 +611,47 @@ struct Ops {
         return lin4_supported(t, 1);
     }
     // rowvec / rowvec_ld / rv_rows: a per-row-group per-column add (IgemmParams::rowvec with rows_per_sample = rv_rows)
-    void linear(const bf16_t* A0, const bf16_t* A1, int C0, int C1, size_t woff, size_t boff, bool has_bias, int M, int N,
+    // alpha: scale of the product (the skinny and mid-size kernels take alpha == 1 only)
+    void linear(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int M, int N,
                 int act, const bf16_t* res, bf16_t* out, float* out_f32 = nullptr, const float* res_f32 = nullptr, int a1_wrap_rows = 0,
-                const float* rowvec = nullptr, int rowvec_ld = 0, int rv_rows = 1, int res_wrap_rows = 0) {
+                const float* rowvec = nullptr, int rowvec_ld = 0, int rv_rows = 1, int res_wrap_rows = 0, float alpha = 1.f) {
         if (plan) return;
-        // skinny (weight-streaming) kernel for decode-sized operands.  Fast mode: whenever M <= 128.  Deterministic mode: exactly for
-        // the ops with ONE row per sample (`single_row`: time embedding, RARM decode step, CLIP projection), at any batch
-        // (one-row-per-sample operands of bigger batches -- RARM decode at 128+ sequences per GPU -- keep the skinny kernel: its row
-        //  blocks scale with M, while the tiled kernels would run a dozen 256-row tiles)
         // one-row-per-sample operands beyond these row counts take the tiled kernels
         constexpr int SGEMM_MAX_ROWS = 4096;          // (2048 sequences: 716 -> 780 img/s against the tiled kernels, round 5)
         // (round 5, same box: the GEGLU projection of the RARM decode step through the tiled kernel from ~200 rows on: 397.8 -> 409.5 img/s at 256
         //  sequences, 487.0 -> 514.8 at 512; the plain projections through it: 221 / 305 -- their N = 768 gives the tiled kernel 16-24 tiles)
         constexpr int SGEMM_GEGLU_MAX_ROWS = 192;
-        const bool skinny = c->deterministic ? single_row : (M <= 128 || (single_row && M <= (act == ACT_GEGLU ? SGEMM_GEGLU_MAX_ROWS : SGEMM_MAX_ROWS)));
-        if (skinny && !A1 && C1 == 0 && !rowvec) {         // N/32 x ceil(M/32) blocks (sgemm.hip)
-            SgemmParams q{}; q.A = A0; q.lda = C0; q.W = w<bf16_t>(woff); q.M = M; q.N = N; q.K = C0; q.bias = has_bias ? w<float>(boff) : nullptr;
+        if (!A1 && C1 == 0 && !rowvec && alpha == 1.f) {         // N/32 x ceil(M/32) blocks (sgemm.hip), 64 x 64 tiles (mgemm.hip)
+            SgemmParams q{}; q.A = A0; q.lda = C0; q.W = W; q.M = M; q.N = N; q.K = C0; q.bias = bias;
             q.act = act; q.res_f32 = res_f32; q.res_bf16 = res; q.out_f32 = out_f32; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-            q.fixed_split = c->deterministic ? 1 : 0;
-            // 1536+ rows: LDS-staged 64 x 64 tiles (mgemm.hip) -- the skinny kernel's per-wave operand fetch is 75 MB through the L2 -> CU
-            // fabric for a [2048 x 768] x [768 x 768] product (33.6 us; 15.5 there).  Not in deterministic mode (the kernel choice would follow the batch).
-            static const int mg_from = rdm_env_int(getenv("RDM_MGEMM_FROM"), 1536);     // (tests move it)
-            if (!c->deterministic && single_row && mg_from > 0 && M >= mg_from && act != ACT_GEGLU && mgemm_supported(q)) {
+            if (skinny(M, act == ACT_GEGLU ? SGEMM_GEGLU_MAX_ROWS : SGEMM_MAX_ROWS)) {
+                // 1536+ rows: LDS-staged 64 x 64 tiles (mgemm.hip) -- the skinny kernel's per-wave operand fetch is 75 MB through the L2 -> CU
+                // fabric for a [2048 x 768] x [768 x 768] product (33.6 us; 15.5 there).  Not in deterministic mode (the kernel choice would follow the batch).
+                static const int mg_from = rdm_env_int(getenv("RDM_MGEMM_FROM"), 1536);     // (tests move it)
+                if (!c->deterministic && single_row && mg_from > 0 && M >= mg_from && act != ACT_GEGLU && mgemm_supported(q)) {
+                    prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
+                    check(launch_mgemm(q, c->stream), "mid-size linear");
+                    prof_end();
+                    return;
+                }
+                q.fixed_split = c->deterministic ? 1 : 0;
+                if (sgemm_supported(q)) {
+                    prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
+                    check(launch_sgemm(q, c->stream), "skinny linear");
+                    prof_end();
+                    return;
+                }
+            }
+            static const int mg_any = rdm_env_int(getenv("RDM_MGEMM_ANY"), 0);      // tests: operands of >= mg_any rows that are not single_row
+            if (!single_row && mg_any > 0 && M >= mg_any && act != ACT_GEGLU && mgemm_supported(q)) {
                 prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
                 check(launch_mgemm(q, c->stream), "mid-size linear");
                 prof_end();
                 return;
             }
-            if (sgemm_supported(q)) {
-                prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
-                check(launch_sgemm(q, c->stream), "skinny linear");
-                prof_end();
-                return;
-            }
         }
         IgemmParams p = base(M, N, C0 + C1);
-        p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = w<bf16_t>(woff); p.bias = has_bias ? w<float>(boff) : nullptr;
+        p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = W; p.bias = bias; p.alpha = alpha;
         p.act = act; p.res_bf16 = res; p.res_f32 = res_f32; p.out_bf16 = out; p.out_f32 = out_f32; p.a1_wrap_rows = a1_wrap_rows;
         p.res_wrap_rows = res_wrap_rows;
         if (rowvec) { p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = rv_rows; }
@@ -649,7 +664,7 @@ struct Ops {
             const int tile_rows = (N % 384 == 0) ? 128 : 256;
             const bool det_ok = rows_hint > 0 && rows_hint % tile_rows == 0;
             if (c->deterministic) t.l4_any_tiles = p.l4_any_tiles = 1;
-            if ((!c->deterministic || det_ok) && lin4_supported(t, 1)) p.Wfrag = c->frag_for_lin(p.W, N, C0 + C1, act == ACT_GEGLU);
+            if ((!c->deterministic || det_ok) && lin4_supported(t, 1)) p.Wfrag = derived(p.W, N, C0 + C1, act == ACT_GEGLU ? 2 : 1);
         }
         prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)(C0 + C1), M, N, C0 + C1);
         check(launch_igemm(p, false, 1, c->stream), "linear");
@@ -657,28 +672,27 @@ struct Ops {
     }
     // out = act(LayerNorm(x) W^T + bias) with the LayerNorm formed inside the skinny GEMM (sgemm.hip): decode-sized operands only.
     // false = not available for this shape (the caller runs layernorm + linear)
-    bool linear_ln(const float* x, size_t g, size_t b, int C, size_t woff, size_t boff, bool has_bias, int M, int N, int act, bf16_t* out) {
+    bool linear_ln(const float* x, const float* g, const float* b, int C, const bf16_t* W, const float* bias, int M, int N, int act, bf16_t* out) {
         // (from ~200 rows on a separate LayerNorm pass + the 64 x 64-tile GEMM beats the LayerNorm-fused 32-row tiles: sgemm.hip)
         constexpr int SGEMM_LN_MAX_ROWS = 192;
         if (!c->deterministic && M > SGEMM_LN_MAX_ROWS) return false;
-        const bool skinny = c->deterministic ? single_row : (M <= 128 || (single_row && M <= 1024));
-        SgemmParams q{}; q.ln_x = x; q.ln_g = w<float>(g); q.ln_b = w<float>(b); q.ln_eps = 1e-5f; q.W = w<bf16_t>(woff); q.M = M; q.N = N; q.K = C;
-        q.bias = has_bias ? w<float>(boff) : nullptr; q.act = act; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
+        SgemmParams q{}; q.ln_x = x; q.ln_g = g; q.ln_b = b; q.ln_eps = 1e-5f; q.W = W; q.M = M; q.N = N; q.K = C;
+        q.bias = bias; q.act = act; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
         q.fixed_split = c->deterministic ? 1 : 0;
-        if (!skinny || !sgemm_supported(q)) return false;
+        if (!skinny(M, 1024) || !sgemm_supported(q)) return false;
         if (plan) return true;
         prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C, M, N, C);
         check(launch_sgemm(q, c->stream), "skinny linear on a LayerNorm");
         prof_end();
         return true;
     }
-    void conv3(const bf16_t* A0, const bf16_t* A1, int C0, int C1, size_t woff, size_t boff, int B, int Hin, int Win, int N,
+    void conv3(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int B, int Hin, int Win, int N,
                int stride, int ups, const float* rowvec, int rowvec_ld, const bf16_t* res, bf16_t* out, int asym = 0) {
         if (plan) return;
         const int Hout = ups ? Hin * 2 : (stride == 2 ? Hin / 2 : Hin), Wout = ups ? Win * 2 : (stride == 2 ? Win / 2 : Win);
         IgemmParams p = base(B * Hout * Wout, N, 9 * (C0 + C1));
         p.asym = asym;
-        p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = w<bf16_t>(woff); p.bias = w<float>(boff);
+        p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = W; p.bias = bias;
         p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.stride = stride; p.ups = ups;
         p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = Hout * Wout; p.res_bf16 = res; p.out_bf16 = out;
         // deterministic mode: the halo kernels need whole 256-pixel tiles, which at < 256 pixels per sample exist only for batches
@@ -687,10 +701,10 @@ struct Ops {
         // Upsample's conv by output phase: four 2 x 2-tap convs at source resolution on pre-summed weights, 2.25 x fewer FLOPs than the
         // nine taps at output resolution (igemm.hip CONV == 3)
         if (ups && !A1 && C1 == 0 && C0 % 64 == 0 && N % 8 == 0 && !rowvec && !res && stride == 1) {
-            const bf16_t* wp = c->phase_weights_for(p.W, N, C0);
+            const bf16_t* wp = derived(W, N, C0, 5);
             if (wp) {
                 IgemmParams q = base(B * Hin * Win, N, 4 * C0);
-                q.A0 = A0; q.C0 = C0; q.W = wp; q.bias = w<float>(boff); q.out_bf16 = out; q.phase2 = 1;
+                q.A0 = A0; q.C0 = C0; q.W = wp; q.bias = bias; q.out_bf16 = out; q.phase2 = 1;
                 q.Hin = Hin; q.Win = Win; q.Hout = Hout; q.Wout = Wout; q.stride = 1; q.rows_per_sample = Hin * Win;
                 q.sA = 0; q.sW = (long long)N * 4 * C0; q.sO = 0;
                 prof_begin(RDM_PROF_UPSCONV, 2.0 * 4.0 * q.M * N * (double)q.K, 4 * q.M, N, q.K);
@@ -702,7 +716,7 @@ struct Ops {
         const bool det_generic = c->deterministic && ((Hout * Wout) % 256 != 0);
         const int ks = c->deterministic ? 1 : conv_halo_ksplit(p);
         if (ks > 1 && ensure_bytes(c, &c->splitk_ws, &c->splitk_ws_bytes, (size_t)ks * p.M * N * 4) == 0) { p.ksplit = ks; p.ws = (float*)c->splitk_ws; }
-        if (!det_generic && (conv_halo_supported(p) || conv_halo4_strip_supported(p))) p.Wfrag = c->frag_for(p.W, N, C0 + C1);
+        if (!det_generic && (conv_halo_supported(p) || conv_halo4_strip_supported(p))) p.Wfrag = derived(W, N, C0 + C1, 0);
         prof_begin(RDM_PROF_CONV3X3, 2.0 * p.M * N * (double)p.K, p.M, N, p.K);
         check(det_generic ? launch_igemm(p, true, 1, c->stream) : launch_conv3x3(p, c->stream), "conv3x3");
         prof_end();
@@ -720,8 +734,6 @@ struct Ops {
         if (nbytes > c->tap_bytes) nbytes = c->tap_bytes;
         check(hipMemcpyAsync(c->tap_buf, ptr, nbytes, hipMemcpyDeviceToDevice, c->stream), "debug tap");
     }
-    bool single_row = false;     // set by callers around ops whose operand has one row per sample (see linear)
-    int rows_hint = 0;           // rows per sample of the operand of the linear ops that follow (0 = unknown); set by the UNet block executors
     bool prof_open = false;
     const char* tag = "";        // role of the ops that follow in the graph ("st.proj_in", "res.conv1", ...): rdm_prof_dump groups by it
     void prof_begin(int kind, double work, int d0 = 0, int d1 = 0, int d2 = 0) {       // work: FLOPs (GEMM-class kinds) or bytes (bandwidth-class kinds)
@@ -731,42 +743,85 @@ struct Ops {
         hipEventRecord(r.a, c->stream); c->prof_recs.push_back(r);
     }
     void prof_end() { if (prof_open) hipEventRecord(c->prof_recs.back().b, c->stream); prof_open = false; }
-    void groupnorm(const bf16_t* x0, const bf16_t* x1, int C0, int C1, int B, int HW, size_t g, size_t b, float eps, int silu,
+    // (gn_partial must hold B samples' statistics: ensure_gn_partial)
+    void groupnorm(const bf16_t* x0, const bf16_t* x1, int C0, int C1, int B, int HW, const float* g, const float* b, float eps, int silu,
                    bf16_t* out, int L0 = -1, int L1 = -1, int x1_bmod = 0, int x0_bmod = 0) {      // L0 / L1: logical channels of the (zero-padded) sources, default = all
         if (plan) return;
         GnParams p{}; p.x0 = x0; p.x1 = x1; p.C0 = C0; p.C1 = C1; p.HW = HW; p.B = B; p.groups = 32; p.x1_bmod = x1_bmod; p.x0_bmod = x0_bmod;
         p.L0 = L0 < 0 ? C0 : L0; p.L1 = L1 < 0 ? C1 : L1;
-        int nchunk = HW / 64; if (nchunk < 1) nchunk = 1; if (nchunk > 32) nchunk = 32;
-        p.nchunk = nchunk; p.partial = c->gn_partial; p.gamma = w<float>(g); p.beta = w<float>(b); p.eps = eps; p.silu = silu;
+        p.nchunk = gn_chunks(HW); p.partial = c->gn_partial; p.gamma = g; p.beta = b; p.eps = eps; p.silu = silu;
         p.out = out;
         prof_begin(RDM_PROF_GROUPNORM, (double)B * HW * (C0 + C1) * 4.0, B * HW, C0 + C1, silu);       // ALGORITHMIC bytes: one read + one write of the bf16 tensor (round 5: the one-pass kernel moves exactly these; the two-pass form of the 64 x 64 level reads twice)
         check(launch_groupnorm(p, c->stream), "groupnorm");
         prof_end();
     }
     // GroupNorm + SiLU + 3x3 conv to a few channels (UNet `out`, VQ decoder conv_out): one statistics pass + the fused MFMA head kernel
-    // (misc.hip), or GroupNorm-apply into `tmp` + the VALU head conv where the fused kernel does not apply
-    void head(const bf16_t* x, int B, int H, int W, int C, int Clog, size_t g, size_t b, float eps, size_t woff, size_t boff, int Cout,
+    // (misc.hip), or GroupNorm-apply into `tmp` + the VALU head conv where the fused kernel does not apply.  g == null: no GroupNorm
+    // (the fused kernel only)
+    HeadParams head_params(const bf16_t* x, int B, int H, int W, int C, const float* g, const float* b, float eps, const float* wt, const float* bias,
+                           int Cout, float* out, bf16_t* wp) const {
+        HeadParams hp{}; hp.x = x; hp.B = B; hp.H = H; hp.W = W; hp.C = C; hp.groups = 32; hp.gamma = g; hp.beta = b; hp.eps = eps;
+        hp.w = wt; hp.wp = wp; hp.bias = bias; hp.out = out; hp.Cout = Cout;
+        if (g) { hp.partial = c->gn_partial; hp.nchunk = gn_chunks(H * W); }
+        return hp;
+    }
+    void head(const bf16_t* x, int B, int H, int W, int C, int Clog, const float* g, const float* b, float eps, const float* wt, const float* bias, int Cout,
               float* out, bf16_t* tmp, bf16_t* wp) {
         if (plan) return;
-        HeadParams hp{}; hp.x = x; hp.B = B; hp.H = H; hp.W = W; hp.C = C; hp.groups = 32; hp.gamma = w<float>(g); hp.beta = w<float>(b); hp.eps = eps;
-        hp.w = w<float>(woff); hp.wp = wp; hp.bias = w<float>(boff); hp.out = out; hp.Cout = Cout;
-        int nchunk = H * W / 64; if (nchunk < 1) nchunk = 1; if (nchunk > 32) nchunk = 32;
-        hp.partial = c->gn_partial; hp.nchunk = nchunk;
+        const HeadParams hp = head_params(x, B, H, W, C, g, b, eps, wt, bias, Cout, out, wp);
         if (Clog == C && head_conv_supported(hp)) {
-            GnParams p{}; p.x0 = x; p.C0 = C; p.HW = H * W; p.B = B; p.groups = 32; p.L0 = C; p.nchunk = nchunk; p.partial = c->gn_partial;
-            prof_begin(RDM_PROF_GROUPNORM, (double)B * H * W * C * 2.0, B * H * W, C, 2);
-            check(launch_gn_stats(p, c->stream), "head groupnorm statistics");
-            prof_end();
+            if (g) {
+                GnParams p{}; p.x0 = x; p.C0 = C; p.HW = H * W; p.B = B; p.groups = 32; p.L0 = C; p.nchunk = hp.nchunk; p.partial = c->gn_partial;
+                prof_begin(RDM_PROF_GROUPNORM, (double)B * H * W * C * 2.0, B * H * W, C, 2);
+                check(launch_gn_stats(p, c->stream), "head groupnorm statistics");
+                prof_end();
+            }
             check(launch_head_conv(hp, c->stream), "head conv");
             return;
         }
         groupnorm(x, nullptr, C, 0, B, H * W, g, b, eps, 1, tmp, Clog, 0);
-        check(launch_conv_out(tmp, w<float>(woff), w<float>(boff), out, B, H, W, C, Cout, c->stream), "conv_out");
+        check(launch_conv_out(tmp, wt, bias, out, B, H, W, C, Cout, c->stream), "conv_out");
     }
-    void layernorm(const void* x, int in_f32, size_t g, size_t b, void* out, int out_f32, int M, int C, int Clog = -1) {
+    void layernorm(const void* x, int in_f32, const float* g, const float* b, void* out, int out_f32, int M, int C, int Clog = -1, float eps = 1e-5f) {
         if (plan) return;
         prof_begin(RDM_PROF_LAYERNORM, (double)M * C * ((in_f32 ? 4.0 : 2.0) + (out_f32 ? 4.0 : 2.0)), M, C, 0);
-        check(launch_layernorm(x, in_f32, w<float>(g), w<float>(b), out, out_f32, M, C, 1e-5f, c->stream, Clog < 0 ? C : Clog), "layernorm");
+        check(launch_layernorm(x, in_f32, g, b, out, out_f32, M, C, eps, c->stream, Clog < 0 ? C : Clog), "layernorm");
+        prof_end();
+    }
+    // d = 32 flash attention over n tokens (attention.hip): q / k (= q + C) token-major at row stride ldq; V either token-major at the
+    // same stride (v: the fused q | k | v projection, n % 64 == 0) or V^T per sample [B][C][n] (vt)
+    void flash_d32(const bf16_t* q, int ldq, const bf16_t* v, const bf16_t* vt, bf16_t* out, int B, int n, int heads) {
+        if (plan) return;
+        const int C = heads * 32;
+        FlashParams f{}; f.q = q; f.ldq = ldq; f.k = q + C; f.ldk = ldq; f.v = v; f.ldv = v ? ldq : 0; f.vt = vt; f.out = out; f.ldo = C;
+        f.n = n; f.C = C; f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
+        prof_begin(RDM_PROF_ATTENTION, 4.0 * B * heads * (double)n * n * 32, B, n, C);
+        check(launch_flash_d32(f, heads, B, c->stream), "flash attention");
+        prof_end();
+    }
+    // attention over a few keys / short sequences (attention.hip): head dim D, nq queries and nkv keys per sample
+    void small_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, bf16_t* out, int ldo, int B, int nq, int nkv,
+                         int heads, int D, int causal, float scale, const char* what) {
+        if (plan) return;
+        SmallAttnParams p{}; p.q = q; p.ldq = ldq; p.k = k; p.ldk = ldk; p.v = v; p.ldv = ldv; p.out = out;
+        p.ldo = ldo; p.nq = nq; p.nkv = nkv; p.causal = causal; p.scale = scale;
+        check(launch_small_attention(p, D, heads, B, c->stream), what);
+    }
+    // cross-attention over k neighbours in one launch (attention.hip): scores against G, softmax, P U, bias and residual; G / U are the
+    // fragment-ordered images of launch_xattn_pack.  ln_g given: x holds the raw rows, the scores are taken on LayerNorm(x) and the residual
+    // is x itself (res null); ln3_out given: LayerNorm(out rows; ln3_g, ln3_b) leaves with the finished rows
+    static XattnParams xattn_params(int rows, int n, int C, int NP, int ncols, int group) {
+        XattnParams q{}; q.rows = rows; q.n = n; q.C = C; q.NP = NP; q.ncols = ncols; q.group = group; return q;
+    }
+    void xattn_fused(const bf16_t* x, const float* ln_g, const float* ln_b, float ln_eps, const bf16_t* G, const bf16_t* U, const float* bias,
+                     const bf16_t* res, bf16_t* out, int rows, int n, int C, int NP, int ncols, int group,
+                     const float* ln3_g = nullptr, const float* ln3_b = nullptr, bf16_t* ln3_out = nullptr) {
+        if (plan) return;
+        XattnParams q = xattn_params(rows, n, C, NP, ncols, group);
+        q.x = x; q.G = G; q.U = U; q.bias = bias; q.res = res; q.out = out; q.ln_g = ln_g; q.ln_b = ln_b; q.ln_eps = ln_eps;
+        q.ln3_g = ln3_g; q.ln3_b = ln3_b; q.ln3_out = ln3_out;
+        prof_begin(RDM_PROF_LINEAR, 4.0 * rows * NP * (double)C, rows, NP, C);
+        check(launch_xattn_fused(q, c->stream), "fused cross attention");
         prof_end();
     }
 };
@@ -782,7 +837,7 @@ static void unet_compute_kv(Ops& o, UNet& u, const float* context, int B, int k,
     const int cd = u.cfg.context_dim;
     bf16_t* cb = o.abf((size_t)B * k * cd);
     if (!o.plan) o.check(launch_cast_f32_bf16(context, cb, (long long)B * k * cd, o.c->stream), "cast ctx");
-    o.linear(cb, nullptr, cd, 0, u.kvw, 0, false, B * k, u.kv_total, ACT_NONE, nullptr, kv_out);
+    o.linear(cb, nullptr, cd, 0, o.w<bf16_t>(u.kvw), nullptr, B * k, u.kv_total, ACT_NONE, nullptr, kv_out);
 }
 
 // ---- cross-attention over k neighbours as two skinny GEMMs.  softmax(q K^T / sqrt d) V W_o^T with q = x W_q^T is re-associated
@@ -834,10 +889,10 @@ static void unet_time_rows(Ops& o, UNet& u, const long long* t, int B, float* em
     bf16_t* e1 = o.abf((size_t)B * ted);
     o.single_row = true;                                  // one row per sample (see Ops::linear)
     o.tag = "time_embed";
-    o.linear(temb, nullptr, mc, 0, u.te0w, u.te0b, true, B, ted, ACT_SILU, nullptr, e1);
+    o.linear(temb, nullptr, mc, 0, o.w<bf16_t>(u.te0w), o.w<float>(u.te0b), B, ted, ACT_SILU, nullptr, e1);
     bf16_t* semb = o.abf((size_t)B * ted);
-    o.linear(e1, nullptr, ted, 0, u.te2w, u.te2b, true, B, ted, ACT_SILU, nullptr, semb);
-    o.linear(semb, nullptr, ted, 0, u.embw, u.embb, true, B, u.emb_total, ACT_NONE, nullptr, nullptr, emb_all);      // all 22 emb_layers in one GEMM
+    o.linear(e1, nullptr, ted, 0, o.w<bf16_t>(u.te2w), o.w<float>(u.te2b), B, ted, ACT_SILU, nullptr, semb);
+    o.linear(semb, nullptr, ted, 0, o.w<bf16_t>(u.embw), o.w<float>(u.embb), B, u.emb_total, ACT_NONE, nullptr, nullptr, emb_all);      // all 22 emb_layers in one GEMM
     o.single_row = false;
 }
 
@@ -892,25 +947,25 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         if (r.skip) {
             sk = o.abf((size_t)M * r.cout);
             o.tag = "res.skip";
-            o.linear(a.p, x1, C0, C1, r.wsk, r.bsk, true, M, r.cout, ACT_NONE, nullptr, sk, nullptr, nullptr, wrap_b * HW);
+            o.linear(a.p, x1, C0, C1, o.w<bf16_t>(r.wsk), o.w<float>(r.bsk), M, r.cout, ACT_NONE, nullptr, sk, nullptr, nullptr, wrap_b * HW);
             res = sk;
         }
         bf16_t* n1 = o.abf((size_t)M * r.cin);
         o.tag = "res.gn1";
-        o.groupnorm(a.p, x1, C0, C1, B, HW, r.gn1g, r.gn1b, 1e-5f, 1, n1, a.L, skip ? skip->L : 0, wrap_b);
+        o.groupnorm(a.p, x1, C0, C1, B, HW, o.w<float>(r.gn1g), o.w<float>(r.gn1b), 1e-5f, 1, n1, a.L, skip ? skip->L : 0, wrap_b);
         o.tap(1, n1, (size_t)M * r.cin * 2);
         bf16_t* h1 = o.abf((size_t)M * r.cout);
         o.tag = "res.conv1";
-        o.conv3(n1, nullptr, r.cin, 0, r.w1, r.b1, B, a.H, a.W, r.cout, 1, 0, emb_all + r.emb_off, emb_ld, nullptr, h1);
+        o.conv3(n1, nullptr, r.cin, 0, o.w<bf16_t>(r.w1), o.w<float>(r.b1), B, a.H, a.W, r.cout, 1, 0, emb_all + r.emb_off, emb_ld, nullptr, h1);
         o.tap(2, h1, (size_t)M * r.cout * 2);
         bf16_t* n2 = o.abf((size_t)M * r.cout);
         o.tag = "res.gn2";
-        o.groupnorm(h1, nullptr, r.cout, 0, B, HW, r.gn2g, r.gn2b, 1e-5f, 1, n2, r.lout, 0);
+        o.groupnorm(h1, nullptr, r.cout, 0, B, HW, o.w<float>(r.gn2g), o.w<float>(r.gn2b), 1e-5f, 1, n2, r.lout, 0);
         o.tap(3, n2, (size_t)M * r.cout * 2);
         if (r.skip) o.tap(4, sk, (size_t)M * r.cout * 2);
         bf16_t* out = o.abf((size_t)Bfull * HW * r.cout);           // Bfull: see expand()
         o.tag = "res.conv2";
-        o.conv3(n2, nullptr, r.cout, 0, r.w2, r.b2, B, a.H, a.W, r.cout, 1, 0, nullptr, 0, res, out);
+        o.conv3(n2, nullptr, r.cout, 0, o.w<bf16_t>(r.w2), o.w<float>(r.b2), B, a.H, a.W, r.cout, 1, 0, nullptr, 0, res, out);
         o.tap(5, out, (size_t)M * r.cout * 2);
         return Act{out, r.cout, a.H, a.W, r.lout};
     };
@@ -922,11 +977,11 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         const int in_wrap = a.half ? Bfull / 2 : 0;
         bf16_t* xn = o.abf((size_t)M * C);
         o.tag = "st.gn";
-        o.groupnorm(a.p, nullptr, C, 0, B, n, s.gng, s.gnb, 1e-6f, 0, xn, s.lc, 0, 0, in_wrap);
+        o.groupnorm(a.p, nullptr, C, 0, B, n, o.w<float>(s.gng), o.w<float>(s.gnb), 1e-6f, 0, xn, s.lc, 0, 0, in_wrap);
         o.tap(1, xn, (size_t)M * C * 2);
         bf16_t* t0 = o.abf((size_t)M * C);
         o.tag = "st.proj_in";
-        o.linear(xn, nullptr, C, 0, s.win, s.bin, true, M, C, ACT_NONE, nullptr, t0);
+        o.linear(xn, nullptr, C, 0, o.w<bf16_t>(s.win), o.w<float>(s.bin), M, C, ACT_NONE, nullptr, t0);
         o.tap(2, t0, (size_t)M * C * 2);
         // --- attn1 (self)
         bf16_t* l1 = o.abf((size_t)M * C);
@@ -937,20 +992,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         const int QW = vrow ? 3 * C : 2 * C;
         bf16_t* qk = o.abf((size_t)M * QW);
         o.tag = "st.norm1+qkv";
-        o.layernorm(t0, 0, s.ln1g, s.ln1b, l1, 0, M, C, s.lc);
+        o.layernorm(t0, 0, o.w<float>(s.ln1g), o.w<float>(s.ln1b), l1, 0, M, C, s.lc);
         o.tap(3, l1, (size_t)M * C * 2);
-        o.linear(l1, nullptr, C, 0, s.wqk, 0, false, M, QW, ACT_NONE, nullptr, qk);
+        o.linear(l1, nullptr, C, 0, o.w<bf16_t>(s.wqk), nullptr, M, QW, ACT_NONE, nullptr, qk);
         o.tap(4, qk, (size_t)M * QW * 2);
         bf16_t* ao = o.abf((size_t)M * C);
         o.tag = "st.self_attention";
         if (vrow) {
-            if (!o.plan) {
-                FlashParams f{}; f.q = qk; f.ldq = QW; f.k = qk + C; f.ldk = QW; f.v = qk + 2 * C; f.ldv = QW; f.out = ao; f.ldo = C;
-                f.n = n; f.C = C; f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
-                o.prof_begin(RDM_PROF_ATTENTION, 4.0 * B * s.heads * (double)n * n * 32, B, n, C);
-                o.check(launch_flash_d32(f, s.heads, B, o.c->stream), "flash attention");
-                o.prof_end();
-            }
+            o.flash_d32(qk, QW, qk + 2 * C, nullptr, ao, B, n, s.heads);
         } else if (n % 32 == 0) {
             bf16_t* vt = o.abf((size_t)M * C);      // V^T per sample: [B][C][n] via swapped-operand GEMM
             if (!o.plan) {
@@ -958,54 +1007,39 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                 p.A0 = o.w<bf16_t>(s.wv); p.C0 = C; p.W = l1; p.sA = 0; p.sW = (long long)n * C; p.sO = (long long)C * n;
                 p.out_bf16 = vt; p.ldo = n;
                 o.check(launch_igemm(p, false, B, o.c->stream), "v^T gemm");
-                FlashParams f{}; f.q = qk; f.ldq = 2 * C; f.k = qk + C; f.ldk = 2 * C; f.vt = vt; f.out = ao; f.ldo = C;
-                f.n = n; f.C = C; f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
-                o.prof_begin(RDM_PROF_ATTENTION, 4.0 * B * s.heads * (double)n * n * 32, B, n, C);
-                o.check(launch_flash_d32(f, s.heads, B, o.c->stream), "flash attention");
-                o.prof_end();
             }
+            o.flash_d32(qk, 2 * C, nullptr, vt, ao, B, n, s.heads);
         } else {
             bf16_t* v = o.abf((size_t)M * C);
-            o.linear(l1, nullptr, C, 0, s.wv, 0, false, M, C, ACT_NONE, nullptr, v);
-            if (!o.plan) {
-                SmallAttnParams p{}; p.q = qk; p.ldq = 2 * C; p.k = qk + C; p.ldk = 2 * C; p.v = v; p.ldv = C; p.out = ao;
-                p.ldo = C; p.nq = n; p.nkv = n; p.causal = 0; p.scale = 1.0f / sqrtf(32.f);
-                o.check(launch_small_attention(p, 32, s.heads, B, o.c->stream), "small self attention");
-            }
+            o.linear(l1, nullptr, C, 0, o.w<bf16_t>(s.wv), nullptr, M, C, ACT_NONE, nullptr, v);
+            o.small_attention(qk, 2 * C, qk + C, 2 * C, v, C, ao, C, B, n, n, s.heads, 32, 0, 1.0f / sqrtf(32.f), "small self attention");
         }
         o.tap(5, ao, (size_t)M * C * 2);
         bf16_t* t1 = o.abf((size_t)M * C);
         // --- attn2 (cross over the k neighbours); samples >= Bx have all-zero neighbours: t2 = t1 + b_o exactly (see add_bias_rows_kernel)
         const int Mx = Bx * n;
+        // norm2 + attn2 + residual in one kernel when the neighbours' operands are cached (xa), norm2 too when no channel is padding
+        const bool xfused = xa && Mx > 0 && xattn_fused_supported(Ops::xattn_params(Mx, n, C, XA_NP, s.heads * k, k));
+        const bool xln = xfused && s.lc == C && C <= 2048;
         // Round 5: in a guided batch [conditional | unconditional] (Bx = B / 2) with the LayerNorm-fused cross-attention kernel,
         //   * the unconditional rows' t2 = attn1.to_out(...) + t0 + b_o2 leaves attn1.to_out's GEMM directly (b_o2 rides in the start
         //     values of those rows: Ops::linear's rowvec; one rounding less than t1 -> + b_o2), no add_bias_rows pass;
         //   * the cross-attention kernel runs IN PLACE on the conditional rows (t2 aliases t1) and emits norm3 of its finished rows, so
         //     the separate LayerNorm-3 pass only covers the unconditional rows.
-        XattnParams xq{}; xq.rows = Mx; xq.n = n; xq.C = C; xq.NP = XA_NP; xq.ncols = s.heads * k; xq.group = k;
-        const bool xfold_shape = xa && Mx > 0 && s.lc == C && C <= 2048 && xattn_fused_supported(xq) && !o.c->deterministic;       // => xfused && xln below
+        const bool xfold_shape = xln && !o.c->deterministic;
         const bool bias_fold = xfold_shape && Bx * 2 == B;             // the unconditional half exists and is exactly the second half
         o.tag = "st.attn1.to_out";
         if (bias_fold) {
             const float* zb = o.plan ? nullptr : o.c->zero_bias_pair(o.w<float>(s.bo2), C);
             if (!o.plan && !zb && o.rc == 0) o.rc = o.c->fail(-2, "out of memory for a bias table");
-            o.linear(ao, nullptr, C, 0, s.wo1, s.bo1, true, M, C, ACT_NONE, t0, t1, nullptr, nullptr, 0, zb, C, Mx);
+            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(s.wo1), o.w<float>(s.bo1), M, C, ACT_NONE, t0, t1, nullptr, nullptr, 0, zb, C, Mx);
         } else {
-            o.linear(ao, nullptr, C, 0, s.wo1, s.bo1, true, M, C, ACT_NONE, t0, t1);
+            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(s.wo1), o.w<float>(s.bo1), M, C, ACT_NONE, t0, t1);
         }
         o.tap(6, t1, (size_t)M * C * 2);          // (with the bias fold: the unconditional rows already hold t2)
         o.tag = "st.norm2+attn2";
         bf16_t* l2 = o.abf((size_t)M * C);
-        // norm2 + attn2 + residual in one kernel when the neighbours' operands are cached (xa) and no channel is padding
-        XattnParams xp{};
-        if (xa && Mx > 0) {
-            const bf16_t* G = xa + (size_t)B * s.xa_unit; const bf16_t* U = G + (size_t)B * XA_NP * C;
-            xp.x = l2; xp.G = U + (size_t)B * C * XA_NP; xp.U = xp.G + (size_t)B * XA_NP * C; xp.bias = o.w<float>(s.bo2); xp.res = t1; xp.out = nullptr;
-            xp.rows = Mx; xp.n = n; xp.C = C; xp.NP = XA_NP; xp.ncols = s.heads * k; xp.group = k;
-        }
-        const bool xfused = xa && Mx > 0 && xattn_fused_supported(xp);
-        const bool xln = xfused && s.lc == C && C <= 2048;
-        if (Mx > 0 && !xln) o.layernorm(t1, 0, s.ln2g, s.ln2b, l2, 0, Mx, C, s.lc);
+        if (Mx > 0 && !xln) o.layernorm(t1, 0, o.w<float>(s.ln2g), o.w<float>(s.ln2b), l2, 0, Mx, C, s.lc);
         bf16_t* t2 = xfold_shape ? t1 : o.abf((size_t)M * C);
         bf16_t* l3 = o.abf((size_t)M * C);
         if (Bx < B && !bias_fold && !o.plan)
@@ -1013,16 +1047,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         if (Mx == 0) {
         } else if (xa) {       // two skinny per-sample GEMMs (see unet_compute_xattn)
             bf16_t* P = o.abf((size_t)M * XA_NP);
-            if (!o.plan) {
-                const bf16_t* G = xa + (size_t)B * s.xa_unit; const bf16_t* U = G + (size_t)B * XA_NP * C;
-                xp.out = t2;
-                if (xln) { xp.x = t1; xp.res = nullptr; xp.ln_g = o.w<float>(s.ln2g); xp.ln_b = o.w<float>(s.ln2b); xp.ln_eps = 1e-5f; }
-                if (xfold_shape && xln && xfused) { xp.ln3_g = o.w<float>(s.ln3g); xp.ln3_b = o.w<float>(s.ln3b); xp.ln3_out = l3; }
-                if (xfused) {       // both GEMMs, the softmax and the residual (and norm2) in one launch (attention.hip)
-                    o.prof_begin(RDM_PROF_LINEAR, 4.0 * Mx * XA_NP * (double)C, Mx, XA_NP, C);
-                    o.check(launch_xattn_fused(xp, o.c->stream), "fused cross attention");
-                    o.prof_end();
-                } else {
+            const bf16_t* G = xa + (size_t)B * s.xa_unit; const bf16_t* U = G + (size_t)B * XA_NP * C;
+            const bf16_t* Gp = U + (size_t)B * C * XA_NP; const bf16_t* Up = Gp + (size_t)B * XA_NP * C;     // their packed images
+            if (xln)            // both GEMMs, the softmax, the residual and norm2 (and norm3) in one launch
+                o.xattn_fused(t1, o.w<float>(s.ln2g), o.w<float>(s.ln2b), 1e-5f, Gp, Up, o.w<float>(s.bo2), nullptr, t2, Mx, n, C, XA_NP, s.heads * k, k,
+                              xfold_shape ? o.w<float>(s.ln3g) : nullptr, xfold_shape ? o.w<float>(s.ln3b) : nullptr, xfold_shape ? l3 : nullptr);
+            else if (xfused)    // on the LayerNorm'd rows
+                o.xattn_fused(l2, nullptr, nullptr, 0.f, Gp, Up, o.w<float>(s.bo2), t1, t2, Mx, n, C, XA_NP, s.heads * k, k);
+            else if (!o.plan) {
                 IgemmParams p = o.base(n, XA_NP, C);
                 p.A0 = l2; p.C0 = C; p.sA = (long long)n * C; p.W = G; p.sW = (long long)XA_NP * C; p.out_bf16 = P; p.sO = (long long)n * XA_NP;
                 p.act = ACT_SOFTMAXG; p.sm_group = k;
@@ -1035,18 +1067,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                 o.prof_begin(RDM_PROF_LINEAR, 2.0 * Mx * C * (double)XA_NP);
                 o.check(launch_igemm(q, false, Bx, o.c->stream), "xattn out");
                 o.prof_end();
-                }
             }
         } else {
             bf16_t* q2 = o.abf((size_t)M * C);
-            o.linear(l2, nullptr, C, 0, s.wq2, 0, false, Mx, C, ACT_NONE, nullptr, q2);
+            o.linear(l2, nullptr, C, 0, o.w<bf16_t>(s.wq2), nullptr, Mx, C, ACT_NONE, nullptr, q2);
             bf16_t* ao2 = o.abf((size_t)M * C);
-            if (!o.plan) {
-                SmallAttnParams p{}; p.q = q2; p.ldq = C; p.k = kv + s.kv_off; p.ldk = u.kv_total; p.v = kv + s.kv_off + C;
-                p.ldv = u.kv_total; p.out = ao2; p.ldo = C; p.nq = n; p.nkv = k; p.causal = 0; p.scale = 1.0f / sqrtf(32.f);
-                o.check(launch_small_attention(p, 32, s.heads, Bx, o.c->stream), "cross attention");
-            }
-            o.linear(ao2, nullptr, C, 0, s.wo2, s.bo2, true, Mx, C, ACT_NONE, t1, t2);
+            o.small_attention(q2, C, kv + s.kv_off, u.kv_total, kv + s.kv_off + C, u.kv_total, ao2, C, Bx, n, k, s.heads, 32, 0, 1.0f / sqrtf(32.f),
+                              "cross attention");
+            o.linear(ao2, nullptr, C, 0, o.w<bf16_t>(s.wo2), o.w<float>(s.bo2), Mx, C, ACT_NONE, t1, t2);
         }
         o.tap(7, t2, (size_t)M * C * 2);
         // --- GEGLU feed-forward
@@ -1054,11 +1082,11 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         const int FI = 4 * s.lc;                     // GEGLU hidden width: 4 x the LOGICAL channels (a multiple of 128, never padded)
         bf16_t* ff = o.abf((size_t)M * FI);
         if (xfold_shape) {       // norm3 of the conditional rows left the cross-attention kernel; the unconditional rows' here
-            if (M > Mx) o.layernorm(t2 + (size_t)Mx * C, 0, s.ln3g, s.ln3b, l3 + (size_t)Mx * C, 0, M - Mx, C, s.lc);
-            o.linear(l3, nullptr, C, 0, s.wff1, s.bff1, true, M, 2 * FI, ACT_GEGLU, nullptr, ff);
+            if (M > Mx) o.layernorm(t2 + (size_t)Mx * C, 0, o.w<float>(s.ln3g), o.w<float>(s.ln3b), l3 + (size_t)Mx * C, 0, M - Mx, C, s.lc);
+            o.linear(l3, nullptr, C, 0, o.w<bf16_t>(s.wff1), o.w<float>(s.bff1), M, 2 * FI, ACT_GEGLU, nullptr, ff);
         } else {
-            o.layernorm(t2, 0, s.ln3g, s.ln3b, l3, 0, M, C, s.lc);
-            o.linear(l3, nullptr, C, 0, s.wff1, s.bff1, true, M, 2 * FI, ACT_GEGLU, nullptr, ff);
+            o.layernorm(t2, 0, o.w<float>(s.ln3g), o.w<float>(s.ln3b), l3, 0, M, C, s.lc);
+            o.linear(l3, nullptr, C, 0, o.w<bf16_t>(s.wff1), o.w<float>(s.bff1), M, 2 * FI, ACT_GEGLU, nullptr, ff);
         }
         o.tap(8, l3, (size_t)M * C * 2);
         o.tap(9, ff, (size_t)M * FI * 2);
@@ -1066,7 +1094,7 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         o.tag = "st.ff2*proj_out";
         // t3 = ff W_2^T + b_2 + t2 and out = t3 W_out^T + b_out + x are one GEMM over the K-concatenated operand [ff | t2]
         // (dual-source A) with the product weights built by the packer: t3 never exists (2 of 9 tensor passes, one launch)
-        o.linear(ff, t2, FI, C, s.wfo, s.bfo, true, M, C, ACT_NONE, a.p, out, nullptr, nullptr, 0, nullptr, 0, 1, in_wrap * n);
+        o.linear(ff, t2, FI, C, o.w<bf16_t>(s.wfo), o.w<float>(s.bfo), M, C, ACT_NONE, a.p, out, nullptr, nullptr, 0, nullptr, 0, 1, in_wrap * n);
         o.tap(10, out, (size_t)M * C * 2);
         return Act{out, C, a.H, a.W, s.lc};
     };
@@ -1100,14 +1128,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                     const ConvW& d = u.down[L.idx];
                     bf16_t* out = o.abf((size_t)Bfull * (h.H / 2) * (h.W / 2) * d.c);
                     o.tag = "downsample";
-                    o.conv3(h.p, nullptr, d.c, 0, d.w, d.b, B, h.H, h.W, d.c, 2, 0, nullptr, 0, nullptr, out);
+                    o.conv3(h.p, nullptr, d.c, 0, o.w<bf16_t>(d.w), o.w<float>(d.b), B, h.H, h.W, d.c, 2, 0, nullptr, 0, nullptr, out);
                     h = Act{out, d.c, h.H / 2, h.W / 2, d.lc};
                 } break;
                 case 4: {
                     const ConvW& d = u.up[L.idx];
                     bf16_t* out = o.abf((size_t)Bfull * (h.H * 2) * (h.W * 2) * d.c);
                     o.tag = "upsample";
-                    o.conv3(h.p, nullptr, d.c, 0, d.w, d.b, B, h.H, h.W, d.c, 1, 1, nullptr, 0, nullptr, out);
+                    o.conv3(h.p, nullptr, d.c, 0, o.w<bf16_t>(d.w), o.w<float>(d.b), B, h.H, h.W, d.c, 1, 1, nullptr, 0, nullptr, out);
                     h = Act{out, d.c, h.H * 2, h.W * 2, d.lc};
                 } break;
             }
@@ -1124,7 +1152,7 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
     bf16_t* no = o.abf((size_t)B * H * W * mc);
     bf16_t* hwp = o.abf(head_conv_wp_bytes(mc) / 2);
     o.tag = "out_head";
-    o.head(h.p, B, H, W, mc, mcl, u.outg, u.outb, 1e-5f, u.outw, u.outbias, c.out_channels, eps_out, no, hwp);
+    o.head(h.p, B, H, W, mc, mcl, o.w<float>(u.outg), o.w<float>(u.outb), 1e-5f, o.w<float>(u.outw), o.w<float>(u.outbias), c.out_channels, eps_out, no, hwp);
 }
 
 // plan (count bytes) -> ensure arena -> run
@@ -1169,51 +1197,54 @@ static int load_blob(rdm_ctx* c, M& m, const Manifest& mf, const void* packed, s
     return 0;
 }
 
-// ------------------------------------------------------------------------------------ VQ decode
+// ------------------------------------------------------------------------------------ VQ decode / encode
+// ldm / taming ResnetBlock (no time embedding): GroupNorm + SiLU + 3x3 conv twice, 1x1 skip when the width changes
+static bf16_t* vq_res(Ops& o, const VqRes& r, bf16_t* x, int B, int H, int W) {
+    const int HW = H * W, M = B * HW;
+    bf16_t* n1 = o.abf((size_t)M * r.cin);
+    o.groupnorm(x, nullptr, r.cin, 0, B, HW, o.w<float>(r.n1g), o.w<float>(r.n1b), 1e-6f, 1, n1);
+    bf16_t* h1 = o.abf((size_t)M * r.cout);
+    o.conv3(n1, nullptr, r.cin, 0, o.w<bf16_t>(r.w1), o.w<float>(r.b1), B, H, W, r.cout, 1, 0, nullptr, 0, nullptr, h1);
+    bf16_t* n2 = o.abf((size_t)M * r.cout);
+    o.groupnorm(h1, nullptr, r.cout, 0, B, HW, o.w<float>(r.n2g), o.w<float>(r.n2b), 1e-6f, 1, n2);
+    const bf16_t* rs = x;
+    if (r.skip) { bf16_t* s = o.abf((size_t)M * r.cout); o.linear(x, nullptr, r.cin, 0, o.w<bf16_t>(r.wsk), o.w<float>(r.bsk), M, r.cout, ACT_NONE, nullptr, s); rs = s; }
+    bf16_t* out = o.abf((size_t)M * r.cout);
+    o.conv3(n2, nullptr, r.cout, 0, o.w<bf16_t>(r.w2), o.w<float>(r.b2), B, H, W, r.cout, 1, 0, nullptr, 0, rs, out);
+    return out;
+}
+// ldm / taming AttnBlock: single head over H*W tokens, scale C^-1/2
+static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) {
+    const int C = a.c, n = H * W, M = B * n;
+    bf16_t* hn = o.abf((size_t)M * C);
+    o.groupnorm(x, nullptr, C, 0, B, n, o.w<float>(a.ng), o.w<float>(a.nb), 1e-6f, 0, hn);
+    bf16_t* q = o.abf((size_t)M * C); bf16_t* kk = o.abf((size_t)M * C); bf16_t* vt = o.abf((size_t)M * C);
+    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wq), o.w<float>(a.bq), M, C, ACT_NONE, nullptr, q);
+    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wk), o.w<float>(a.bk), M, C, ACT_NONE, nullptr, kk);
+    float* S = o.af32((size_t)B * n * n); bf16_t* P = o.abf((size_t)B * n * n); bf16_t* ao = o.abf((size_t)M * C);
+    if (!o.plan) {
+        IgemmParams p = o.base(C, n, C);     // V^T[b] = Wv . hn[b]^T   (bias b_v folded in after P.V: rows of P sum to 1)
+        p.A0 = o.w<bf16_t>(a.wv); p.C0 = C; p.W = hn; p.sW = (long long)n * C; p.sO = (long long)C * n; p.out_bf16 = vt; p.ldo = n;
+        o.check(launch_igemm(p, false, B, o.c->stream), "vq v^T");
+        IgemmParams s = o.base(n, n, C);     // S[b] = q[b] k[b]^T * C^-1/2  (fp32 scores)
+        s.A0 = q; s.C0 = C; s.W = kk; s.sA = (long long)n * C; s.sW = (long long)n * C; s.sO = (long long)n * n; s.out_f32 = S; s.ldo = n;
+        s.alpha = 1.0f / sqrtf((float)C);
+        o.check(launch_igemm(s, false, B, o.c->stream), "vq qk^T");
+        o.check(launch_softmax_rows(S, P, (long long)B * n, n, o.c->stream), "vq softmax");
+        IgemmParams pv = o.base(n, C, n);    // O[b] = P[b] V[b] + b_v
+        pv.A0 = P; pv.C0 = n; pv.W = vt; pv.sA = (long long)n * n; pv.sW = (long long)C * n; pv.sO = (long long)n * C; pv.out_bf16 = ao; pv.ldo = C;
+        pv.bias = o.w<float>(a.bv);
+        o.check(launch_igemm(pv, false, B, o.c->stream), "vq pv");
+    }
+    bf16_t* out = o.abf((size_t)M * C);
+    o.linear(ao, nullptr, C, 0, o.w<bf16_t>(a.wo), o.w<float>(a.bo), M, C, ACT_NONE, x, out);
+    return out;
+}
+
 // decoder trunk shared by the VQ-f4 (ldm) and VQGAN-f16 (taming) first stages: ResnetBlocks, AttnBlocks, nearest-2x upsample convs
 static void vq_trunk(Ops& o, VqModel& v, bf16_t* h, int B, int H, int W, float* img) {
     const rdm_vq_cfg& c = v.cfg;
     int bin = c.ch * c.ch_mult[c.n_ch_mult - 1];
-    auto res = [&](const VqRes& r, bf16_t* x) -> bf16_t* {
-        const int HW = H * W, M = B * HW;
-        bf16_t* n1 = o.abf((size_t)M * r.cin);
-        o.groupnorm(x, nullptr, r.cin, 0, B, HW, r.n1g, r.n1b, 1e-6f, 1, n1);
-        bf16_t* h1 = o.abf((size_t)M * r.cout);
-        o.conv3(n1, nullptr, r.cin, 0, r.w1, r.b1, B, H, W, r.cout, 1, 0, nullptr, 0, nullptr, h1);
-        bf16_t* n2 = o.abf((size_t)M * r.cout);
-        o.groupnorm(h1, nullptr, r.cout, 0, B, HW, r.n2g, r.n2b, 1e-6f, 1, n2);
-        const bf16_t* rs = x;
-        if (r.skip) { bf16_t* s = o.abf((size_t)M * r.cout); o.linear(x, nullptr, r.cin, 0, r.wsk, r.bsk, true, M, r.cout, ACT_NONE, nullptr, s); rs = s; }
-        bf16_t* out = o.abf((size_t)M * r.cout);
-        o.conv3(n2, nullptr, r.cout, 0, r.w2, r.b2, B, H, W, r.cout, 1, 0, nullptr, 0, rs, out);
-        return out;
-    };
-    auto attn = [&](const VqAttn& a, bf16_t* x) -> bf16_t* {   // ldm / taming AttnBlock: single head over H*W tokens, scale C^-1/2
-        const int C = a.c, n = H * W, M = B * n;
-        bf16_t* hn = o.abf((size_t)M * C);
-        o.groupnorm(x, nullptr, C, 0, B, n, a.ng, a.nb, 1e-6f, 0, hn);
-        bf16_t* q = o.abf((size_t)M * C); bf16_t* kk = o.abf((size_t)M * C); bf16_t* vt = o.abf((size_t)M * C);
-        o.linear(hn, nullptr, C, 0, a.wq, a.bq, true, M, C, ACT_NONE, nullptr, q);
-        o.linear(hn, nullptr, C, 0, a.wk, a.bk, true, M, C, ACT_NONE, nullptr, kk);
-        float* S = o.af32((size_t)B * n * n); bf16_t* P = o.abf((size_t)B * n * n); bf16_t* ao = o.abf((size_t)M * C);
-        if (!o.plan) {
-            IgemmParams p = o.base(C, n, C);     // V^T[b] = Wv . hn[b]^T   (bias b_v folded in after P.V: rows of P sum to 1)
-            p.A0 = o.w<bf16_t>(a.wv); p.C0 = C; p.W = hn; p.sW = (long long)n * C; p.sO = (long long)C * n; p.out_bf16 = vt; p.ldo = n;
-            o.check(launch_igemm(p, false, B, o.c->stream), "vq v^T");
-            IgemmParams s = o.base(n, n, C);     // S[b] = q[b] k[b]^T * C^-1/2  (fp32 scores)
-            s.A0 = q; s.C0 = C; s.W = kk; s.sA = (long long)n * C; s.sW = (long long)n * C; s.sO = (long long)n * n; s.out_f32 = S; s.ldo = n;
-            s.alpha = 1.0f / sqrtf((float)C);
-            o.check(launch_igemm(s, false, B, o.c->stream), "vq qk^T");
-            o.check(launch_softmax_rows(S, P, (long long)B * n, n, o.c->stream), "vq softmax");
-            IgemmParams pv = o.base(n, C, n);    // O[b] = P[b] V[b] + b_v
-            pv.A0 = P; pv.C0 = n; pv.W = vt; pv.sA = (long long)n * n; pv.sW = (long long)C * n; pv.sO = (long long)n * C; pv.out_bf16 = ao; pv.ldo = C;
-            pv.bias = o.w<float>(a.bv);
-            o.check(launch_igemm(pv, false, B, o.c->stream), "vq pv");
-        }
-        bf16_t* out = o.abf((size_t)M * C);
-        o.linear(ao, nullptr, C, 0, a.wo, a.bo, true, M, C, ACT_NONE, x, out);
-        return out;
-    };
     // debug tap (rdm_debug_tap): first-stage decoder layers are blocks 1000, 1001, ... in execution order (conv_in's output = 1000)
     int tapi = 1000;
     auto vtap = [&](const bf16_t* t, int ch) {
@@ -1224,25 +1255,25 @@ static void vq_trunk(Ops& o, VqModel& v, bf16_t* h, int B, int H, int W, float* 
         }
     };
     vtap(h, bin);
-    h = res(v.mid1, h); vtap(h, bin);
-    if (c.mid_attn) { h = attn(v.attn, h); vtap(h, bin); }
-    h = res(v.mid2, h); vtap(h, bin);
+    h = vq_res(o, v.mid1, h, B, H, W); vtap(h, bin);
+    if (c.mid_attn) { h = vq_attn(o, v.attn, h, B, H, W); vtap(h, bin); }
+    h = vq_res(o, v.mid2, h, B, H, W); vtap(h, bin);
     for (int lvl = c.n_ch_mult - 1; lvl >= 0; lvl--) {
         for (size_t i = 0; i < v.up_blocks[lvl].size(); i++) {
-            h = res(v.up_blocks[lvl][i], h); bin = v.up_blocks[lvl][i].cout; vtap(h, bin);
-            if (i < v.up_attn[lvl].size()) { h = attn(v.up_attn[lvl][i], h); vtap(h, bin); }
+            h = vq_res(o, v.up_blocks[lvl][i], h, B, H, W); bin = v.up_blocks[lvl][i].cout; vtap(h, bin);
+            if (i < v.up_attn[lvl].size()) { h = vq_attn(o, v.up_attn[lvl][i], h, B, H, W); vtap(h, bin); }
         }
         if (lvl != 0) {
             const ConvW& u = v.upsample[lvl];
             bf16_t* out = o.abf((size_t)B * (H * 2) * (W * 2) * u.c);
-            o.conv3(h, nullptr, u.c, 0, u.w, u.b, B, H, W, u.c, 1, 1, nullptr, 0, nullptr, out);
+            o.conv3(h, nullptr, u.c, 0, o.w<bf16_t>(u.w), o.w<float>(u.b), B, H, W, u.c, 1, 1, nullptr, 0, nullptr, out);
             h = out; H *= 2; W *= 2;
             vtap(h, u.c);
         }
     }
     bf16_t* no = o.abf((size_t)B * H * W * bin);
     bf16_t* hwp = o.abf(head_conv_wp_bytes(bin) / 2);
-    o.head(h, B, H, W, bin, bin, v.noutg, v.noutb, 1e-6f, v.coutw, v.coutb, c.out_ch, img, no, hwp);
+    o.head(h, B, H, W, bin, bin, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, o.w<float>(v.coutw), o.w<float>(v.coutb), c.out_ch, img, no, hwp);
 }
 
 // VQ-f4 (3-channel latent): quantise (or not) + post_quant_conv + conv_in as tiny fp32 stem kernels, then the trunk
@@ -1270,10 +1301,10 @@ static void vq_wide_body(Ops& o, VqModel& v, const long long* indices, int B, fl
     bf16_t* zq = o.abf((size_t)M * c.embed_dim);
     if (!o.plan) o.check(launch_codebook_gather(indices, o.w<float>(v.codebook), c.n_embed, c.embed_dim, M, zq, o.c->stream), "codebook gather");
     bf16_t* h0 = o.abf((size_t)M * c.z_channels);
-    o.linear(zq, nullptr, c.embed_dim, 0, v.pqw, v.pqb, true, M, c.z_channels, ACT_NONE, nullptr, h0);
+    o.linear(zq, nullptr, c.embed_dim, 0, o.w<bf16_t>(v.pqw), o.w<float>(v.pqb), M, c.z_channels, ACT_NONE, nullptr, h0);
     const int bin = c.ch * c.ch_mult[c.n_ch_mult - 1];
     bf16_t* h = o.abf((size_t)M * bin);
-    o.conv3(h0, nullptr, c.z_channels, 0, v.cinw, v.cinb, B, zr, zr, bin, 1, 0, nullptr, 0, nullptr, h);
+    o.conv3(h0, nullptr, c.z_channels, 0, o.w<bf16_t>(v.cinw), o.w<float>(v.cinb), B, zr, zr, bin, 1, 0, nullptr, 0, nullptr, h);
     vq_trunk(o, v, h, B, zr, zr, img);
 }
 
@@ -1283,66 +1314,26 @@ static void vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* z)
     int H = c.resolution, W = c.resolution;
     bf16_t* h = o.abf((size_t)B * H * W * c.ch);
     if (!o.plan) o.check(launch_conv_in(img, o.w<float>(v.cinw), o.w<float>(v.cinb), h, B, c.out_ch, H, W, c.ch, o.c->stream), "encoder conv_in");
-    auto res = [&](const VqRes& r, bf16_t* x) -> bf16_t* {
-        const int HW = H * W, M = B * HW;
-        bf16_t* n1 = o.abf((size_t)M * r.cin);
-        o.groupnorm(x, nullptr, r.cin, 0, B, HW, r.n1g, r.n1b, 1e-6f, 1, n1);
-        bf16_t* h1 = o.abf((size_t)M * r.cout);
-        o.conv3(n1, nullptr, r.cin, 0, r.w1, r.b1, B, H, W, r.cout, 1, 0, nullptr, 0, nullptr, h1);
-        bf16_t* n2 = o.abf((size_t)M * r.cout);
-        o.groupnorm(h1, nullptr, r.cout, 0, B, HW, r.n2g, r.n2b, 1e-6f, 1, n2);
-        const bf16_t* rs = x;
-        if (r.skip) { bf16_t* sk = o.abf((size_t)M * r.cout); o.linear(x, nullptr, r.cin, 0, r.wsk, r.bsk, true, M, r.cout, ACT_NONE, nullptr, sk); rs = sk; }
-        bf16_t* out = o.abf((size_t)M * r.cout);
-        o.conv3(n2, nullptr, r.cout, 0, r.w2, r.b2, B, H, W, r.cout, 1, 0, nullptr, 0, rs, out);
-        return out;
-    };
-    auto attn = [&](const VqAttn& a, bf16_t* x) -> bf16_t* {       // as vq_trunk's AttnBlock
-        const int C = a.c, n = H * W, M = B * n;
-        bf16_t* hn = o.abf((size_t)M * C);
-        o.groupnorm(x, nullptr, C, 0, B, n, a.ng, a.nb, 1e-6f, 0, hn);
-        bf16_t* q = o.abf((size_t)M * C); bf16_t* kk = o.abf((size_t)M * C); bf16_t* vt = o.abf((size_t)M * C);
-        o.linear(hn, nullptr, C, 0, a.wq, a.bq, true, M, C, ACT_NONE, nullptr, q);
-        o.linear(hn, nullptr, C, 0, a.wk, a.bk, true, M, C, ACT_NONE, nullptr, kk);
-        float* S = o.af32((size_t)B * n * n); bf16_t* P = o.abf((size_t)B * n * n); bf16_t* ao = o.abf((size_t)M * C);
-        if (!o.plan) {
-            IgemmParams p = o.base(C, n, C);
-            p.A0 = o.w<bf16_t>(a.wv); p.C0 = C; p.W = hn; p.sW = (long long)n * C; p.sO = (long long)C * n; p.out_bf16 = vt; p.ldo = n;
-            o.check(launch_igemm(p, false, B, o.c->stream), "enc v^T");
-            IgemmParams sc = o.base(n, n, C);
-            sc.A0 = q; sc.C0 = C; sc.W = kk; sc.sA = (long long)n * C; sc.sW = (long long)n * C; sc.sO = (long long)n * n; sc.out_f32 = S; sc.ldo = n;
-            sc.alpha = 1.0f / sqrtf((float)C);
-            o.check(launch_igemm(sc, false, B, o.c->stream), "enc qk^T");
-            o.check(launch_softmax_rows(S, P, (long long)B * n, n, o.c->stream), "enc softmax");
-            IgemmParams pv = o.base(n, C, n);
-            pv.A0 = P; pv.C0 = n; pv.W = vt; pv.sA = (long long)n * n; pv.sW = (long long)C * n; pv.sO = (long long)n * C; pv.out_bf16 = ao; pv.ldo = C;
-            pv.bias = o.w<float>(a.bv);
-            o.check(launch_igemm(pv, false, B, o.c->stream), "enc pv");
-        }
-        bf16_t* out = o.abf((size_t)M * C);
-        o.linear(ao, nullptr, C, 0, a.wo, a.bo, true, M, C, ACT_NONE, x, out);
-        return out;
-    };
     int bin = c.ch;
     for (int lvl = 0; lvl < c.n_ch_mult; lvl++) {
         for (size_t i = 0; i < v.down[lvl].size(); i++) {
-            h = res(v.down[lvl][i], h); bin = v.down[lvl][i].cout;
-            if (i < v.down_attn[lvl].size()) h = attn(v.down_attn[lvl][i], h);
+            h = vq_res(o, v.down[lvl][i], h, B, H, W); bin = v.down[lvl][i].cout;
+            if (i < v.down_attn[lvl].size()) h = vq_attn(o, v.down_attn[lvl][i], h, B, H, W);
         }
         if (lvl != c.n_ch_mult - 1) {      // F.pad(x, (0, 1, 0, 1)) + Conv2d(stride 2, padding 0): window rows 2 oy .. 2 oy + 2, zero beyond the last row / column
             const ConvW& d = v.downsample[lvl];
             bf16_t* out = o.abf((size_t)B * (H / 2) * (W / 2) * d.c);
-            o.conv3(h, nullptr, d.c, 0, d.w, d.b, B, H, W, d.c, 2, 0, nullptr, 0, nullptr, out, /*asym=*/1);
+            o.conv3(h, nullptr, d.c, 0, o.w<bf16_t>(d.w), o.w<float>(d.b), B, H, W, d.c, 2, 0, nullptr, 0, nullptr, out, /*asym=*/1);
             h = out; H /= 2; W /= 2;
         }
     }
-    h = res(v.mid1, h);
-    if (c.mid_attn) h = attn(v.attn, h);
-    h = res(v.mid2, h);
+    h = vq_res(o, v.mid1, h, B, H, W);
+    if (c.mid_attn) h = vq_attn(o, v.attn, h, B, H, W);
+    h = vq_res(o, v.mid2, h, B, H, W);
     bf16_t* no = o.abf((size_t)B * H * W * bin);
     bf16_t* hwp = o.abf(head_conv_wp_bytes(bin) / 2);
     float* ze = o.af32((size_t)B * c.z_channels * H * W);
-    o.head(h, B, H, W, bin, bin, v.noutg, v.noutb, 1e-6f, v.coutw, v.coutb, c.z_channels, ze, no, hwp);
+    o.head(h, B, H, W, bin, bin, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, o.w<float>(v.coutw), o.w<float>(v.coutb), c.z_channels, ze, no, hwp);
     if (!o.plan) o.check(launch_vq_quantize(ze, nullptr, 0, o.w<float>(v.qw), o.w<float>(v.qb), z, nullptr, B, H * W, 0, o.c->stream), "quant_conv");
 }
 
@@ -1352,17 +1343,14 @@ static void clip_tower(Ops& o, const std::vector<ClipBlk>& blks, float* x, int B
     bf16_t* ln = o.abf((size_t)M * Wd); bf16_t* qkv = o.abf((size_t)M * 3 * Wd); bf16_t* ao = o.abf((size_t)M * Wd);
     bf16_t* hid = o.abf((size_t)M * 4 * Wd);
     for (const ClipBlk& k : blks) {
-        o.layernorm(x, 1, k.ln1g, k.ln1b, ln, 0, M, Wd);
-        o.linear(ln, nullptr, Wd, 0, k.wqkv, k.bqkv, true, M, 3 * Wd, ACT_NONE, nullptr, qkv);
-        if (!o.plan) {
-            SmallAttnParams p{}; p.q = qkv; p.ldq = 3 * Wd; p.k = qkv + Wd; p.ldk = 3 * Wd; p.v = qkv + 2 * Wd; p.ldv = 3 * Wd;
-            p.out = ao; p.ldo = Wd; p.nq = L; p.nkv = L; p.causal = causal; p.scale = 1.0f / sqrtf((float)(Wd / heads));
-            o.check(launch_small_attention(p, Wd / heads, heads, B, o.c->stream), "clip attention");
-        }
-        o.linear(ao, nullptr, Wd, 0, k.wo, k.bo, true, M, Wd, ACT_NONE, nullptr, nullptr, x, x);        // x += out_proj(attn)
-        o.layernorm(x, 1, k.ln2g, k.ln2b, ln, 0, M, Wd);
-        o.linear(ln, nullptr, Wd, 0, k.wfc, k.bfc, true, M, 4 * Wd, ACT_QUICKGELU, nullptr, hid);
-        o.linear(hid, nullptr, 4 * Wd, 0, k.wpj, k.bpj, true, M, Wd, ACT_NONE, nullptr, nullptr, x, x);  // x += mlp
+        o.layernorm(x, 1, o.w<float>(k.ln1g), o.w<float>(k.ln1b), ln, 0, M, Wd);
+        o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(k.wqkv), o.w<float>(k.bqkv), M, 3 * Wd, ACT_NONE, nullptr, qkv);
+        o.small_attention(qkv, 3 * Wd, qkv + Wd, 3 * Wd, qkv + 2 * Wd, 3 * Wd, ao, Wd, B, L, L, heads, Wd / heads, causal, 1.0f / sqrtf((float)(Wd / heads)),
+                          "clip attention");
+        o.linear(ao, nullptr, Wd, 0, o.w<bf16_t>(k.wo), o.w<float>(k.bo), M, Wd, ACT_NONE, nullptr, nullptr, x, x);        // x += out_proj(attn)
+        o.layernorm(x, 1, o.w<float>(k.ln2g), o.w<float>(k.ln2b), ln, 0, M, Wd);
+        o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(k.wfc), o.w<float>(k.bfc), M, 4 * Wd, ACT_QUICKGELU, nullptr, hid);
+        o.linear(hid, nullptr, 4 * Wd, 0, o.w<bf16_t>(k.wpj), o.w<float>(k.bpj), M, Wd, ACT_NONE, nullptr, nullptr, x, x);  // x += mlp
     }
 }
 static void clip_text_body(Ops& o, ClipModel& m, const long long* tokens, int B, float* out) {
@@ -1372,9 +1360,9 @@ static void clip_text_body(Ops& o, ClipModel& m, const long long* tokens, int B,
     clip_tower(o, m.text, x, B, L, Wd, c.transformer_heads, 1);
     float* eot = o.af32((size_t)B * Wd); bf16_t* ln = o.abf((size_t)B * Wd);
     if (!o.plan) o.check(launch_clip_gather_eot(tokens, x, eot, B, L, Wd, o.c->stream), "gather eot");
-    o.layernorm(eot, 1, m.lnfg, m.lnfb, ln, 0, B, Wd);
+    o.layernorm(eot, 1, o.w<float>(m.lnfg), o.w<float>(m.lnfb), ln, 0, B, Wd);
     o.single_row = true;                                  // the pooled token: one row per sample
-    o.linear(ln, nullptr, Wd, 0, m.tproj, 0, false, B, c.embed_dim, ACT_NONE, nullptr, nullptr, out);
+    o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(m.tproj), nullptr, B, c.embed_dim, ACT_NONE, nullptr, nullptr, out);
     o.single_row = false;
 }
 // raw_h > 0: `img` is the un-preprocessed [B,3,raw_h,raw_w] image in [-1,1]; the bicubic resize + normalisation of
@@ -1387,16 +1375,16 @@ static void clip_image_body(Ops& o, ClipModel& m, const float* img, int B, float
         if (raw_h > 0) o.check(launch_clip_preprocess(img, B, raw_h, raw_w, c.image_resolution, P, nullptr, patches, o.c->stream), "preprocess+patchify");
         else o.check(launch_clip_patchify(img, patches, B, c.image_resolution, P, o.c->stream), "patchify");
     }
-    o.linear(patches, nullptr, K, 0, m.conv1, 0, false, B * G * G, Wd, ACT_NONE, nullptr, nullptr, pe);
+    o.linear(patches, nullptr, K, 0, o.w<bf16_t>(m.conv1), nullptr, B * G * G, Wd, ACT_NONE, nullptr, nullptr, pe);
     float* x0 = o.af32((size_t)B * L * Wd); float* x = o.af32((size_t)B * L * Wd);
     if (!o.plan) o.check(launch_clip_vit_assemble(pe, o.w<float>(m.cls), o.w<float>(m.vpos), x0, B, G * G, Wd, o.c->stream), "vit assemble");
-    o.layernorm(x0, 1, m.lnpreg, m.lnpreb, x, 1, B * L, Wd);
+    o.layernorm(x0, 1, o.w<float>(m.lnpreg), o.w<float>(m.lnpreb), x, 1, B * L, Wd);
     clip_tower(o, m.vis, x, B, L, Wd, Wd / 64, 0);
     float* cls = o.af32((size_t)B * Wd); bf16_t* ln = o.abf((size_t)B * Wd);
     if (!o.plan) o.check(launch_gather_rows_f32(x, cls, B, L, Wd, o.c->stream), "gather cls");
-    o.layernorm(cls, 1, m.lnpostg, m.lnpostb, ln, 0, B, Wd);
+    o.layernorm(cls, 1, o.w<float>(m.lnpostg), o.w<float>(m.lnpostb), ln, 0, B, Wd);
     o.single_row = true;                                  // the pooled token: one row per sample
-    o.linear(ln, nullptr, Wd, 0, m.vproj, 0, false, B, c.embed_dim, ACT_NONE, nullptr, nullptr, out);
+    o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(m.vproj), nullptr, B, c.embed_dim, ACT_NONE, nullptr, nullptr, out);
     o.single_row = false;
 }
 
@@ -1968,7 +1956,7 @@ static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,c
     return run_with_arena(c, m.arena, m.blob, [&](Ops& o) {
         bf16_t* cb = o.abf((size_t)B * k * g.context_dim);
         if (!o.plan) o.check(launch_cast_f32_bf16(context, cb, (long long)B * k * g.context_dim, c->stream), "cast ctx");
-        o.linear(cb, nullptr, g.context_dim, 0, m.kvw, 0, false, B * k, m.kv_total, ACT_NONE, nullptr, (bf16_t*)m.ctxkv);
+        o.linear(cb, nullptr, g.context_dim, 0, o.w<bf16_t>(m.kvw), nullptr, B * k, m.kv_total, ACT_NONE, nullptr, (bf16_t*)m.ctxkv);
         // the decode step's cross-attention re-associated per sequence (rarm.hip: rarm_xattn_decode_kernel):
         //   G_l[b][(h,j)][:] = (K_bj restricted to head h) W_q / sqrt(d),   UT_l[b][(h,j)][:] = W_o (V_bj restricted to head h)
         if (fuse) {
@@ -2007,9 +1995,9 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
         const bool ln3_fused = m.xa_B > 0 && m.xa_k == k;      // the fused cross-attention kernel also emits norm3 of its output rows
         for (int l = 0; l < g.depth; l++) {
             const RarmBlk& b = m.blk[l];
-            if (!o.linear_ln(x, b.ln1g, b.ln1b, C, b.wqkv, 0, false, B2, 3 * C, ACT_NONE, qkv)) {
-                o.layernorm(x, 1, b.ln1g, b.ln1b, ln, 0, B2, C);
-                o.linear(ln, nullptr, C, 0, b.wqkv, 0, false, B2, 3 * C, ACT_NONE, nullptr, qkv);
+            if (!o.linear_ln(x, o.w<float>(b.ln1g), o.w<float>(b.ln1b), C, o.w<bf16_t>(b.wqkv), nullptr, B2, 3 * C, ACT_NONE, qkv)) {
+                o.layernorm(x, 1, o.w<float>(b.ln1g), o.w<float>(b.ln1b), ln, 0, B2, C);
+                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wqkv), nullptr, B2, 3 * C, ACT_NONE, nullptr, qkv);
             }
             if (!o.plan) {
                 RarmAttnParams p{}; p.q = qkv; p.ldq = 3 * C; p.k_new = qkv + C; p.v_new = qkv + 2 * C;
@@ -2024,7 +2012,7 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
                 o.check(launch_rarm_decode_attention(p, g.n_heads, B2, c->stream), "rarm self attention");
                 o.prof_end();
             }
-            o.linear(ao, nullptr, C, 0, b.wo1, b.bo1, true, B2, C, ACT_NONE, nullptr, nullptr, x, x);
+            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo1), o.w<float>(b.bo1), B2, C, ACT_NONE, nullptr, nullptr, x, x);
             if (m.xa_B > 0 && m.xa_k == k) {      // norm2 + to_q + attention over the neighbours + to_out + residual in one launch
                 if (!o.plan) {
                     RarmXattnParams xp{}; xp.x = x; xp.ln_g = o.w<float>(b.ln2g); xp.ln_b = o.w<float>(b.ln2b); xp.ln_eps = 1e-5f;
@@ -2034,27 +2022,27 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
                     o.check(launch_rarm_xattn_decode(xp, c->stream), "rarm fused cross attention");
                 }
             } else {
-            if (!o.linear_ln(x, b.ln2g, b.ln2b, C, b.wq2, 0, false, B2, C, ACT_NONE, q2)) {
-                o.layernorm(x, 1, b.ln2g, b.ln2b, ln, 0, B2, C);
-                o.linear(ln, nullptr, C, 0, b.wq2, 0, false, B2, C, ACT_NONE, nullptr, q2);
+            if (!o.linear_ln(x, o.w<float>(b.ln2g), o.w<float>(b.ln2b), C, o.w<bf16_t>(b.wq2), nullptr, B2, C, ACT_NONE, q2)) {
+                o.layernorm(x, 1, o.w<float>(b.ln2g), o.w<float>(b.ln2b), ln, 0, B2, C);
+                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wq2), nullptr, B2, C, ACT_NONE, nullptr, q2);
             }
             if (!o.plan) {
                 RarmAttnParams p{}; p.q = q2; p.ldq = C; p.Kc = (bf16_t*)m.ctxkv + (size_t)l * 2 * C; p.Vc = (bf16_t*)m.ctxkv + (size_t)l * 2 * C + C;
                 p.batch_stride = (long long)k * m.kv_total; p.row_stride = m.kv_total; p.nkv = k; p.scale = scale; p.out = ao; p.ldo = C;
                 o.check(launch_rarm_decode_attention(p, g.n_heads, B2, c->stream), "rarm cross attention");
             }
-            o.linear(ao, nullptr, C, 0, b.wo2, b.bo2, true, B2, C, ACT_NONE, nullptr, nullptr, x, x);
+            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo2), o.w<float>(b.bo2), B2, C, ACT_NONE, nullptr, nullptr, x, x);
             }
             if (ln3_fused) {      // norm3 left the cross-attention kernel with the finished rows: a plain GEGLU GEMM on the bf16 operand
-                o.linear(ln, nullptr, C, 0, b.wff1, b.bff1, true, B2, 8 * C, ACT_GEGLU, nullptr, ff);
-            } else if (!o.linear_ln(x, b.ln3g, b.ln3b, C, b.wff1, b.bff1, true, B2, 8 * C, ACT_GEGLU, ff)) {
-                o.layernorm(x, 1, b.ln3g, b.ln3b, ln, 0, B2, C);
-                o.linear(ln, nullptr, C, 0, b.wff1, b.bff1, true, B2, 8 * C, ACT_GEGLU, nullptr, ff);
+                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), B2, 8 * C, ACT_GEGLU, nullptr, ff);
+            } else if (!o.linear_ln(x, o.w<float>(b.ln3g), o.w<float>(b.ln3b), C, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), B2, 8 * C, ACT_GEGLU, ff)) {
+                o.layernorm(x, 1, o.w<float>(b.ln3g), o.w<float>(b.ln3b), ln, 0, B2, C);
+                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), B2, 8 * C, ACT_GEGLU, nullptr, ff);
             }
-            o.linear(ff, nullptr, 4 * C, 0, b.wff2, b.bff2, true, B2, C, ACT_NONE, nullptr, nullptr, x, x);
+            o.linear(ff, nullptr, 4 * C, 0, o.w<bf16_t>(b.wff2), o.w<float>(b.bff2), B2, C, ACT_NONE, nullptr, nullptr, x, x);
         }
         if (!o.plan) o.check(launch_cast_f32_bf16(x, ln, (long long)B2 * C, c->stream), "cast x");
-        o.linear(ln, nullptr, C, 0, m.wpo, m.bpo, true, B2, g.vocab_out, ACT_NONE, nullptr, nullptr, st.logits);
+        o.linear(ln, nullptr, C, 0, o.w<bf16_t>(m.wpo), o.w<float>(m.bpo), B2, g.vocab_out, ACT_NONE, nullptr, nullptr, st.logits);
     });
 }
 static int rarm_check(rdm_ctx* c, int b, int k, int positions) {
@@ -2289,53 +2277,31 @@ int rdm_prof_reset(rdm_ctx* c) {
     return 0;
 }
 
-// ---- operator-level wrappers for the parity tests
-static int op_linear_impl(rdm_ctx* c, const void* a, const void* w, const float* bias, const void* res, void* out, float* out_f32,
-                          int M, int N, int K, int act, float alpha, const float* rowvec, int rows_per_group);
+// ---- operator-level entries (parity tests, op benchmarks, the training path): argument checks, then the executors' dispatch (Ops) on
+// caller-owned weights.  Their derived copies are packed per call, unless RDM_OP_FRAG_CACHE=1: the caller promises constant weights (op benchmarks).
+static Ops op_exec(rdm_ctx* c) {
+    static const bool cache = rdm_env_int(getenv("RDM_OP_FRAG_CACHE"), 0) != 0;
+    Ops o{c, nullptr, nullptr, /*plan=*/false};
+    o.const_weights = cache;
+    return o;
+}
+static int op_linear(rdm_ctx* c, const void* a, const void* w, const float* bias, const void* res, void* out, float* out_f32,
+                     int M, int N, int K, int act, float alpha, const float* rowvec, int rows_per_group) {
+    Ops o = op_exec(c);
+    o.linear((const bf16_t*)a, nullptr, K, 0, (const bf16_t*)w, bias, M, N, act, (const bf16_t*)res, (bf16_t*)out, out_f32, nullptr, 0,
+             rowvec, N, rows_per_group, 0, alpha);
+    return o.rc;
+}
 int rdm_op_linear(rdm_ctx* c, const void* a, const void* w, const float* bias, const void* res, void* out, float* out_f32,
                   int M, int N, int K, int act, float alpha) {
-    return op_linear_impl(c, a, w, bias, res, out, out_f32, M, N, K, act, alpha, nullptr, 1);
+    RDM_ENTER(c);
+    return op_linear(c, a, w, bias, res, out, out_f32, M, N, K, act, alpha, nullptr, 1);
 }
 int rdm_op_linear_rowvec(rdm_ctx* c, const void* a, const void* w, const float* bias, const float* rowvec, int rows_per_group, const void* res,
                          void* out, int M, int N, int K) {
-    if (c && (!rowvec || rows_per_group < 1)) return c->fail(-1, "rdm_op_linear_rowvec: rowvec and rows_per_group >= 1 required");
-    return op_linear_impl(c, a, w, bias, res, out, nullptr, M, N, K, ACT_NONE, 1.0f, rowvec, rows_per_group);
-}
-static int op_linear_impl(rdm_ctx* c, const void* a, const void* w, const float* bias, const void* res, void* out, float* out_f32,
-                          int M, int N, int K, int act, float alpha, const float* rowvec, int rows_per_group) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    if (M <= 128 && alpha == 1.0f && !c->deterministic && !rowvec) {       // same dispatch as the executors (Ops::linear): decode-sized batches take the skinny kernel.  Deterministic mode: the
-                                                                // op has no notion of "one row per sample", so it never takes the batch-dependent shortcut (the tiled kernel for every M)
-        SgemmParams q{}; q.A = (const bf16_t*)a; q.lda = K; q.W = (const bf16_t*)w; q.M = M; q.N = N; q.K = K; q.bias = bias; q.act = act;
-        q.res_bf16 = (const bf16_t*)res; q.out_f32 = out_f32; q.out_bf16 = (bf16_t*)out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-        if (sgemm_supported(q)) { RDM_CHECK_HIP(c, launch_sgemm(q, c->stream)); return 0; }
-    }
-    static const int mg_any = rdm_env_int(getenv("RDM_MGEMM_ANY"), 0);      // tests: plain ops of >= mg_any rows on the mid-size GEMM (mgemm.hip)
-    if (mg_any > 0 && M >= mg_any && alpha == 1.0f && !rowvec && act != ACT_GEGLU) {
-        SgemmParams q{}; q.A = (const bf16_t*)a; q.lda = K; q.W = (const bf16_t*)w; q.M = M; q.N = N; q.K = K; q.bias = bias; q.act = act;
-        q.res_bf16 = (const bf16_t*)res; q.out_f32 = out_f32; q.out_bf16 = (bf16_t*)out; q.ldo = N;
-        if (mgemm_supported(q)) { RDM_CHECK_HIP(c, launch_mgemm(q, c->stream)); return 0; }
-    }
-    IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.ldo = (act == ACT_GEGLU) ? N / 2 : N; p.zero_page = c->zero_page;
-    p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1;
-    p.A0 = (const bf16_t*)a; p.C0 = K; p.W = (const bf16_t*)w; p.bias = bias; p.res_bf16 = (const bf16_t*)res;
-    p.out_bf16 = (bf16_t*)out; p.out_f32 = out_f32; p.act = act;
-    if (rowvec) { p.rowvec = rowvec; p.rowvec_ld = N; p.rows_per_sample = rows_per_group; }
-    {
-        IgemmParams t = p; t.Wfrag = p.W;
-        if (!c->deterministic && lin4_supported(t, 1)) {
-            static const int op_cache = rdm_env_int(getenv("RDM_OP_FRAG_CACHE"), 0);   // op benchmarks (tools/lin_bench.py): the caller promises constant weights
-            if (op_cache) p.Wfrag = c->frag_for_lin(p.W, N, K, act == ACT_GEGLU);
-            else {
-                RDM_TRY(ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, (size_t)N * K * 2));
-                RDM_CHECK_HIP(c, launch_lin_w_fragpack(p.W, (bf16_t*)c->wfrag_tmp, N, K, K, act == ACT_GEGLU, c->stream));
-                p.Wfrag = (const bf16_t*)c->wfrag_tmp;
-            }
-        }
-    }
-    RDM_CHECK_HIP(c, launch_igemm(p, false, 1, c->stream));
-    return 0;
+    if (!rowvec || rows_per_group < 1) return c->fail(-1, "rdm_op_linear_rowvec: rowvec and rows_per_group >= 1 required");
+    return op_linear(c, a, w, bias, res, out, nullptr, M, N, K, ACT_NONE, 1.0f, rowvec, rows_per_group);
 }
 int rdm_op_linear_ln(rdm_ctx* c, const void* x, const void* w, const float* bias, const float* gamma, const float* beta, void* out,
                      int M, int N, int K, int act, float eps) {
@@ -2361,37 +2327,10 @@ int rdm_op_conv3x3(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, c
                    const float* rowvec, int rowvec_ld, const void* res, void* out, int B, int Hin, int Win, int N, int stride,
                    int ups) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    const int Hout = ups ? Hin * 2 : (stride == 2 ? Hin / 2 : Hin), Wout = ups ? Win * 2 : (stride == 2 ? Win / 2 : Win);
-    IgemmParams p{}; p.M = B * Hout * Wout; p.N = N; p.K = 9 * (C0 + C1); p.alpha = 1.f; p.ldo = N; p.zero_page = c->zero_page;
-    p.A0 = (const bf16_t*)x0; p.A1 = (const bf16_t*)x1; p.C0 = C0; p.C1 = C1; p.W = (const bf16_t*)w; p.bias = bias;
-    p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.stride = stride; p.ups = ups;
-    p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = Hout * Wout; p.res_bf16 = (const bf16_t*)res; p.out_bf16 = (bf16_t*)out;
-    {   // the fused-upsample conv by output phase (as Ops::conv3 runs it inside the models); the phase weights are rebuilt per call
-        if (ups && !x1 && C1 == 0 && C0 % 64 == 0 && N % 8 == 0 && !rowvec && !res && stride == 1) {
-            RDM_TRY(ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, (size_t)16 * N * C0 * 2));
-            RDM_CHECK_HIP(c, launch_conv_phase_weights(p.W, (bf16_t*)c->wfrag_tmp, N, C0, c->stream));
-            IgemmParams q{}; q.M = B * Hin * Win; q.N = N; q.K = 4 * C0; q.alpha = 1.f; q.ldo = N; q.zero_page = c->zero_page;
-            q.A0 = p.A0; q.C0 = C0; q.W = (const bf16_t*)c->wfrag_tmp; q.bias = bias; q.out_bf16 = (bf16_t*)out; q.phase2 = 1;
-            q.Hin = Hin; q.Win = Win; q.Hout = Hout; q.Wout = Wout; q.stride = 1; q.rows_per_sample = Hin * Win; q.sW = (long long)N * 4 * C0;
-            RDM_CHECK_HIP(c, launch_igemm(q, true, 4, c->stream));
-            return 0;
-        }
-    }
-    const bool det_generic = c->deterministic && ((Hout * Wout) % 256 != 0);
-    if (det_generic) { RDM_CHECK_HIP(c, launch_igemm(p, true, 1, c->stream)); return 0; }
-    const int ks = c->deterministic ? 1 : conv_halo_ksplit(p);
-    if (ks > 1) { RDM_TRY(ensure_bytes(c, &c->splitk_ws, &c->splitk_ws_bytes, (size_t)ks * p.M * N * 4)); p.ksplit = ks; p.ws = (float*)c->splitk_ws; }
-    static const int op_cache = rdm_env_int(getenv("RDM_OP_FRAG_CACHE"), 0);     // op benchmarks (tools/conv_bench.py): the caller promises constant weights
-    const bool halo = conv_halo_supported(p) || conv_halo4_strip_supported(p);
-    if (halo && op_cache) p.Wfrag = c->frag_for(p.W, N, C0 + C1);
-    else if (halo) {
-        RDM_TRY(ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, (size_t)N * p.K * 2));
-        RDM_CHECK_HIP(c, launch_conv_w_fragpack(p.W, (bf16_t*)c->wfrag_tmp, N, C0 + C1, c->stream));
-        p.Wfrag = (const bf16_t*)c->wfrag_tmp;
-    }
-    RDM_CHECK_HIP(c, launch_conv3x3(p, c->stream));
-    return 0;
+    Ops o = op_exec(c);
+    o.conv3((const bf16_t*)x0, (const bf16_t*)x1, C0, C1, (const bf16_t*)w, bias, B, Hin, Win, N, stride, ups, rowvec, rowvec_ld,
+            (const bf16_t*)res, (bf16_t*)out);
+    return o.rc;
 }
 int rdm_op_rarm_sampler(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
                         const float* uniforms, int64_t* tokens_out) {
@@ -2638,101 +2577,77 @@ int rdm_op_geglu(rdm_ctx* c, const void* pre, const void* dh, void* out, long lo
 int rdm_op_groupnorm(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, int B, int HW, const float* gamma,
                      const float* beta, float eps, int silu, void* out) {
     RDM_ENTER(c);
-    if (!c) return -1;
     RDM_TRY(ensure_gn_partial(c, B));
-    GnParams p{}; p.x0 = (const bf16_t*)x0; p.x1 = (const bf16_t*)x1; p.C0 = C0; p.C1 = C1; p.HW = HW; p.B = B; p.groups = 32;
-    int nchunk = HW / 64; if (nchunk < 1) nchunk = 1; if (nchunk > 32) nchunk = 32;
-    p.nchunk = nchunk; p.partial = c->gn_partial; p.gamma = gamma; p.beta = beta; p.eps = eps; p.silu = silu; p.out = (bf16_t*)out;
-    RDM_CHECK_HIP(c, launch_groupnorm(p, c->stream));
-    return 0;
+    Ops o = op_exec(c);
+    o.groupnorm((const bf16_t*)x0, (const bf16_t*)x1, C0, C1, B, HW, gamma, beta, eps, silu, (bf16_t*)out);
+    return o.rc;
 }
 int rdm_op_layernorm(rdm_ctx* c, const void* x, int in_is_f32, const float* gamma, const float* beta, int M, int C, float eps,
                      void* out) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    RDM_CHECK_HIP(c, launch_layernorm(x, in_is_f32, gamma, beta, out, 0, M, C, eps, c->stream));
-    return 0;
+    Ops o = op_exec(c);
+    o.layernorm(x, in_is_f32, gamma, beta, out, 0, M, C, -1, eps);
+    return o.rc;
 }
 int rdm_op_self_attention(rdm_ctx* c, const void* qk, const void* vt, int B, int n, int heads, void* out) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    const int C = heads * 32;
-    FlashParams f{}; f.q = (const bf16_t*)qk; f.ldq = 2 * C; f.k = (const bf16_t*)qk + C; f.ldk = 2 * C; f.vt = (const bf16_t*)vt;
-    f.out = (bf16_t*)out; f.ldo = C; f.n = n; f.C = C; f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
-    RDM_CHECK_HIP(c, launch_flash_d32(f, heads, B, c->stream));
-    return 0;
+    Ops o = op_exec(c);
+    o.flash_d32((const bf16_t*)qk, 2 * heads * 32, nullptr, (const bf16_t*)vt, (bf16_t*)out, B, n, heads);
+    return o.rc;
 }
 int rdm_op_self_attention_qkv(rdm_ctx* c, const void* qkv, int B, int n, int heads, void* out) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    const int C = heads * 32;
     if (n % 64 != 0) return c->fail(-3, "rdm_op_self_attention_qkv: n = %d must be a multiple of 64 (token-major V is read by the LDS-shared kernel only)", n);
-    FlashParams f{}; f.q = (const bf16_t*)qkv; f.ldq = 3 * C; f.k = f.q + C; f.ldk = 3 * C; f.v = f.q + 2 * C; f.ldv = 3 * C;
-    f.out = (bf16_t*)out; f.ldo = C; f.n = n; f.C = C; f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
-    RDM_CHECK_HIP(c, launch_flash_d32(f, heads, B, c->stream));
-    return 0;
+    Ops o = op_exec(c);
+    o.flash_d32((const bf16_t*)qkv, 3 * heads * 32, (const bf16_t*)qkv + 2 * heads * 32, nullptr, (bf16_t*)out, B, n, heads);
+    return o.rc;
+}
+// G / U arrive in their natural layout: their fragment-ordered images are packed per call into bwd_tmp
+static int op_xattn_fused(rdm_ctx* c, const void* x, const float* ln_g, const float* ln_b, float ln_eps, const void* G, const void* U,
+                          const float* bias, const void* res, void* out, int B, int n, int C, int NP, int ncols, int group,
+                          const float* ln3_g, const float* ln3_b, void* ln3_out) {
+    const size_t img = (size_t)B * NP * C;
+    RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, 2 * img * 2));
+    bf16_t* Gp = (bf16_t*)c->bwd_tmp; bf16_t* Up = Gp + img;
+    Ops o = op_exec(c);
+    o.check(launch_xattn_pack((const bf16_t*)G, (const bf16_t*)U, Gp, Up, B, NP, C, c->stream), "xattn pack");
+    o.xattn_fused((const bf16_t*)x, ln_g, ln_b, ln_eps, Gp, Up, bias, (const bf16_t*)res, (bf16_t*)out, B * n, n, C, NP, ncols, group,
+                  ln3_g, ln3_b, (bf16_t*)ln3_out);
+    return o.rc;
 }
 int rdm_op_xattn_fused(rdm_ctx* c, const void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G, const void* U,
                        const float* bias, const void* res, int B, int n, int C, int NP, int ncols, int group, void* out) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    XattnParams q{}; q.x = (const bf16_t*)x; q.G = (const bf16_t*)G; q.U = (const bf16_t*)U; q.bias = bias; q.res = (const bf16_t*)res;
-    q.out = (bf16_t*)out; q.rows = B * n; q.n = n; q.C = C; q.NP = NP; q.ncols = ncols; q.group = group;
-    q.ln_g = ln_gamma; q.ln_b = ln_beta; q.ln_eps = ln_eps;
     if ((ln_gamma != nullptr) != (ln_beta != nullptr) || (ln_gamma && res)) return c->fail(-3, "rdm_op_xattn_fused: LayerNorm needs gamma and beta, and then the residual is x itself (res must be null)");
-    if (!xattn_fused_supported(q)) return c->fail(-3, "rdm_op_xattn_fused: unsupported shape (n %% 32, C %% 64, NP %% 32, ncols <= min(NP, 128), group 1 / 2 / 4): n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
-    const size_t img = (size_t)B * NP * C * 2;          // the kernel reads fragment-ordered images of G and U
-    RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, 2 * img));
-    bf16_t* Gp = (bf16_t*)c->bwd_tmp; bf16_t* Up = Gp + (size_t)B * NP * C;
-    RDM_CHECK_HIP(c, launch_xattn_pack(q.G, q.U, Gp, Up, B, NP, C, c->stream));
-    q.G = Gp; q.U = Up;
-    RDM_CHECK_HIP(c, launch_xattn_fused(q, c->stream));
-    return 0;
+    if (!xattn_fused_supported(Ops::xattn_params(B * n, n, C, NP, ncols, group))) return c->fail(-3, "rdm_op_xattn_fused: unsupported shape (n %% 32, C %% 64, NP %% 32, ncols <= min(NP, 128), group 1 / 2 / 4): n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
+    return op_xattn_fused(c, x, ln_gamma, ln_beta, ln_eps, G, U, bias, res, out, B, n, C, NP, ncols, group, nullptr, nullptr, nullptr);
 }
 int rdm_op_xattn_fused_ln3(rdm_ctx* c, void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G, const void* U,
                            const float* bias, int B, int n, int C, int NP, int ncols, int group, const float* ln3_gamma, const float* ln3_beta, void* ln3_out) {
     RDM_ENTER(c);
-    if (!c) return -1;
     if (!x || !ln_gamma || !ln_beta || !ln3_gamma || !ln3_beta || !ln3_out) return c->fail(-1, "rdm_op_xattn_fused_ln3: null argument");
-    XattnParams q{}; q.x = (const bf16_t*)x; q.G = (const bf16_t*)G; q.U = (const bf16_t*)U; q.bias = bias; q.res = nullptr;
-    q.out = (bf16_t*)x; q.rows = B * n; q.n = n; q.C = C; q.NP = NP; q.ncols = ncols; q.group = group;
-    q.ln_g = ln_gamma; q.ln_b = ln_beta; q.ln_eps = ln_eps; q.ln3_g = ln3_gamma; q.ln3_b = ln3_beta; q.ln3_out = (bf16_t*)ln3_out;
-    if (!xattn_fused_supported(q)) return c->fail(-3, "rdm_op_xattn_fused_ln3: unsupported shape: n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
-    const size_t img = (size_t)B * NP * C * 2;
-    RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, 2 * img));
-    bf16_t* Gp = (bf16_t*)c->bwd_tmp; bf16_t* Up = Gp + (size_t)B * NP * C;
-    RDM_CHECK_HIP(c, launch_xattn_pack(q.G, q.U, Gp, Up, B, NP, C, c->stream));
-    q.G = Gp; q.U = Up;
-    RDM_CHECK_HIP(c, launch_xattn_fused(q, c->stream));
-    return 0;
+    if (!xattn_fused_supported(Ops::xattn_params(B * n, n, C, NP, ncols, group))) return c->fail(-3, "rdm_op_xattn_fused_ln3: unsupported shape: n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
+    return op_xattn_fused(c, x, ln_gamma, ln_beta, ln_eps, G, U, bias, nullptr, x, B, n, C, NP, ncols, group, ln3_gamma, ln3_beta, ln3_out);
 }
 int rdm_op_head_conv(rdm_ctx* c, const void* x, const float* gn_gamma, const float* gn_beta, float gn_eps, const float* w, const float* bias,
                      int B, int H, int W, int C, int Cout, float* out) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    HeadParams hp{}; hp.x = (const bf16_t*)x; hp.B = B; hp.H = H; hp.W = W; hp.C = C; hp.groups = 32; hp.gamma = gn_gamma; hp.beta = gn_beta; hp.eps = gn_eps;
-    hp.w = w; hp.bias = bias; hp.out = out; hp.Cout = Cout;
     if ((gn_gamma != nullptr) != (gn_beta != nullptr)) return c->fail(-3, "rdm_op_head_conv: GroupNorm needs gamma and beta");
-    int nchunk = H * W / 64; if (nchunk < 1) nchunk = 1; if (nchunk > 32) nchunk = 32;
-    if (gn_gamma) { RDM_TRY(ensure_gn_partial(c, B)); hp.partial = c->gn_partial; hp.nchunk = nchunk; }
-    if (!head_conv_supported(hp)) return c->fail(-3, "rdm_op_head_conv: unsupported shape (C %% 32, C <= 240, W %% 32, H %% 2, Cout <= 8, C %% 32 groups): C %d H %d W %d Cout %d", C, H, W, Cout);
+    if (gn_gamma) RDM_TRY(ensure_gn_partial(c, B));
+    Ops o = op_exec(c);
+    if (!head_conv_supported(o.head_params((const bf16_t*)x, B, H, W, C, gn_gamma, gn_beta, gn_eps, w, bias, Cout, out, nullptr)))
+        return c->fail(-3, "rdm_op_head_conv: unsupported shape (C %% 32, C <= 240, W %% 32, H %% 2, Cout <= 8, C %% 32 groups): C %d H %d W %d Cout %d", C, H, W, Cout);
     RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, head_conv_wp_bytes(C)));
-    hp.wp = (bf16_t*)c->bwd_tmp;
-    if (gn_gamma) {
-        GnParams p{}; p.x0 = hp.x; p.C0 = C; p.HW = H * W; p.B = B; p.groups = 32; p.L0 = C; p.nchunk = nchunk; p.partial = c->gn_partial;
-        RDM_CHECK_HIP(c, launch_gn_stats(p, c->stream));
-    }
-    RDM_CHECK_HIP(c, launch_head_conv(hp, c->stream));
-    return 0;
+    o.head((const bf16_t*)x, B, H, W, C, C, gn_gamma, gn_beta, gn_eps, w, bias, Cout, out, nullptr, (bf16_t*)c->bwd_tmp);
+    return o.rc;
 }
 int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int nq, int nkv,
                            int heads, int D, int causal, float scale, void* out, int ldo) {
     RDM_ENTER(c);
-    if (!c) return -1;
-    SmallAttnParams p{}; p.q = (const bf16_t*)q; p.ldq = ldq; p.k = (const bf16_t*)k; p.ldk = ldkv; p.v = (const bf16_t*)v; p.ldv = ldkv;
-    p.out = (bf16_t*)out; p.ldo = ldo; p.nq = nq; p.nkv = nkv; p.causal = causal; p.scale = scale;
-    RDM_CHECK_HIP(c, launch_small_attention(p, D, heads, B, c->stream));
-    return 0;
+    Ops o = op_exec(c);
+    o.small_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldkv, (const bf16_t*)v, ldkv, (bf16_t*)out, ldo, B, nq, nkv, heads, D, causal, scale,
+                      "small attention");
+    return o.rc;
 }
 
 }  // extern "C"

@@ -63,7 +63,7 @@ def lin4_wm(M, N):
 
 
 def linear_path(M, N, K, act=ACT_NONE, alpha=1.0, f32=False, res=False, rows=None, mgemm=False):
-    """the kernel rdm_op_linear / rdm_op_linear_rowvec launches for this call (model.hip op_linear_impl, lin4_supported, launch_igemm)"""
+    """the kernel rdm_op_linear / rdm_op_linear_rowvec launches for this call (model.hip Ops::linear, lin4_supported, launch_igemm)"""
     if M <= 128 and alpha == 1.0 and rows is None and K % 256 == 0 and (N % 64 == 0 if act == ACT_GEGLU else N % 32 == 0):
         return "sgemm"
     if mgemm:
