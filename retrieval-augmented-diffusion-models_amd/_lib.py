@@ -445,17 +445,19 @@ class Context:
         self._check(lib.rdm_unet_forward(self._h, _ptr(x), _ptr(t), _ptr(context), b, context.shape[1], H, W, _ptr(out)))
         return out
 
-    def ddim_sample(self, S, x_T, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
-                    temperature=1.0, want_intermediates=False):
+    def _ddim_call(self, what, fn, S, x_T, cond, uncond, alphas_cumprod, eta, scale, noise, log_every_t, temperature, want_intermediates):
+        """The set-up that ddim_sample and plms_sample share (both run on DDIM's schedule through DdimArgs): device casts, checks,
+        the fp32 alphas_cumprod array, the outputs.  fn(handle, args, x_T, cond, uncond, noise, z, x_inter, pred_x0_inter) is the
+        library call."""
         x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
         uncond = None if uncond is None else self._dev(uncond, torch.float32)
         noise = None if noise is None else self._dev(noise, torch.float32)
         ac = np.ascontiguousarray(alphas_cumprod.detach().cpu().numpy() if isinstance(alphas_cumprod, torch.Tensor)
                                   else alphas_cumprod, dtype=np.float32)
         total = len(range(0, ac.shape[0], max(ac.shape[0] // max(int(S), 1), 1)))
-        self._check_sampler_shapes("ddim_sample", x_T, cond, uncond, noise if eta != 0.0 else None, total)
+        self._check_sampler_shapes(what, x_T, cond, uncond, noise if eta != 0.0 else None, total)
         if scale > 1.0 and uncond is None:
-            raise RdmError("ddim_sample: unconditional_conditioning is required when unconditional_guidance_scale > 1")
+            raise RdmError(f"{what}: unconditional_conditioning is required when unconditional_guidance_scale > 1")
         B, Cc, H, W = x_T.shape
         a = DdimArgs(S=S, batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, eta=eta, temperature=temperature,
                      unconditional_guidance_scale=scale, log_every_t=log_every_t, T=ac.shape[0],
@@ -463,38 +465,22 @@ class Context:
         z = torch.empty_like(x_T)
         xi = pi = None
         if want_intermediates:
-            T_ = ac.shape[0]; c_ = T_ // S
-            total = len(range(0, T_, c_))
             n = lib.rdm_ddim_num_intermediates(total, log_every_t)
             xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
             pi = torch.empty_like(xi)
-        self._check(lib.rdm_ddim_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(noise), _ptr(z),
-                                        _ptr(xi), _ptr(pi)))
+        self._check(fn(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(noise), _ptr(z), _ptr(xi), _ptr(pi)))
         return z, xi, pi
+
+    def ddim_sample(self, S, x_T, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
+                    temperature=1.0, want_intermediates=False):
+        return self._ddim_call("ddim_sample", lib.rdm_ddim_sample, S, x_T, cond, uncond, alphas_cumprod, eta, scale, noise,
+                               log_every_t, temperature, want_intermediates)
 
     def plms_sample(self, S, x_T, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False):
         """ldm PLMSSampler's loop (eta = 0) on DDIM's schedule: S' + 1 UNet forwards for S' sampler timesteps.  Returns
         (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
-        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
-        uncond = None if uncond is None else self._dev(uncond, torch.float32)
-        ac = np.ascontiguousarray(alphas_cumprod.detach().cpu().numpy() if isinstance(alphas_cumprod, torch.Tensor)
-                                  else alphas_cumprod, dtype=np.float32)
-        self._check_sampler_shapes("plms_sample", x_T, cond, uncond)
-        if scale > 1.0 and uncond is None:
-            raise RdmError("plms_sample: unconditional_conditioning is required when unconditional_guidance_scale > 1")
-        B, Cc, H, W = x_T.shape
-        a = DdimArgs(S=S, batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, eta=0.0, temperature=1.0,
-                     unconditional_guidance_scale=scale, log_every_t=log_every_t, T=ac.shape[0],
-                     alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)))
-        z = torch.empty_like(x_T)
-        xi = pi = None
-        if want_intermediates:
-            total = len(range(0, ac.shape[0], max(ac.shape[0] // max(int(S), 1), 1)))
-            n = lib.rdm_ddim_num_intermediates(total, log_every_t)
-            xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
-            pi = torch.empty_like(xi)
-        self._check(lib.rdm_plms_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
-        return z, xi, pi
+        return self._ddim_call("plms_sample", lambda h, a, x, c, u, noise, *out: lib.rdm_plms_sample(h, a, x, c, u, *out),
+                               S, x_T, cond, uncond, alphas_cumprod, 0.0, scale, None, log_every_t, 1.0, want_intermediates)
 
     def ddpm_sample(self, timesteps, x_T, cond, noise, sched, clip_denoised=True, temperature=1.0):
         x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32); noise = self._dev(noise, torch.float32)

@@ -832,7 +832,7 @@ static int ensure_gn_partial(rdm_ctx* c, int B) {
 }
 
 // ------------------------------------------------------------------------------------ UNet forward
-// kv: bf16 [B*k, kv_total] cross-attention keys/values for every SpatialTransformer (computed by unet_prepare_kv)
+// kv: bf16 [B*k, kv_total] cross-attention keys/values for every SpatialTransformer (rdm_unet_forward: per call; the samplers: prepare_kv)
 static void unet_compute_kv(Ops& o, UNet& u, const float* context, int B, int k, bf16_t* kv_out) {
     const int cd = u.cfg.context_dim;
     bf16_t* cb = o.abf((size_t)B * k * cd);
@@ -1558,15 +1558,13 @@ int rdm_ddim_num_intermediates(int S, int log_every_t) {
     return n;
 }
 
-// precompute K/V of the conditioning once per sample() call (reference recomputes S*16 times)
-static int prepare_kv(rdm_ctx* c, const float* cond, const float* uncond, int B, int k, int* Beff) {
+// precompute K/V of the conditioning once per sample() call (reference recomputes S*16 times).  cat: fp32 staging for [cond | uncond],
+// nb * k * context_dim floats (SamplerRun::begin reserves it at the front of the sampler scratch)
+static int prepare_kv(rdm_ctx* c, float* cat, const float* cond, const float* uncond, int B, int k) {
     UNet& u = c->unet;
     const int nb = uncond ? 2 * B : B;
-    *Beff = nb;
     const size_t cd = u.cfg.context_dim;
     RDM_TRY(ensure_bytes(c, (char**)&u.kv_cache, &u.kv_cache_bytes, (size_t)nb * k * u.kv_total * 2));
-    // stage [cond | uncond] contiguous in the sampler scratch (fp32)
-    float* cat = (float*)c->samp;
     RDM_CHECK_HIP(c, hipMemcpyAsync(cat, cond, (size_t)B * k * cd * 4, hipMemcpyDeviceToDevice, c->stream));
     if (uncond) RDM_CHECK_HIP(c, hipMemcpyAsync(cat + (size_t)B * k * cd, uncond, (size_t)B * k * cd * 4, hipMemcpyDeviceToDevice, c->stream));
     const bool skinny = xattn_skinny_ok(u, k);
@@ -1628,18 +1626,63 @@ static int sampler_emb_table(rdm_ctx* c, const std::vector<int>& ts, const float
     return 0;
 }
 
+// One sampling call of the DDIM, PLMS and DDPM loops.  begin() lays out the scratch in c->samp ([cond | uncond] staging, the UNet input
+// x of nb rows, the [steps][nb] int64 timestep table, eps, `extra` bytes of the sampler's own), projects the conditioning's K/V, uploads
+// the timestep table and the time-embedding table of ts, and copies x_T into x (both halves of a guided batch: nb = 2B, [x | x] against
+// [cond | uncond]; later steps' kernels write both halves through x_dup).  forward(idx) is then the UNet at ts[idx] on x into eps.
+struct SamplerRun {
+    rdm_ctx* c; int B, nb, k, H, W, total; long long n1;           // n1: elements of x for B rows; total: ts.size()
+    float *x, *x_dup, *eps; char* extra; long long* tdev; const float* emb_table;
+    int log_every_t = 0, n_logged = 0; float *x_inter = nullptr, *pred_x0_inter = nullptr;     // intermediates: set by DDIM and PLMS
+    static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
+    // batch, k, C, H, W: of the entry's args; uncond: null for an unguided call.  The caller has checked that the UNet is loaded.
+    int begin(rdm_ctx* ctx, int batch, int k_, int C, int H_, int W_, const std::vector<int>& ts, const float* x_T, const float* cond,
+              const float* uncond, size_t extra_bytes) {
+        c = ctx; B = batch; nb = uncond ? 2 * B : B; k = k_; H = H_; W = W_; total = (int)ts.size();
+        n1 = (long long)B * C * H * W;
+        const size_t x_bytes = (size_t)n1 * 4 * (nb / B), t_bytes = (size_t)total * nb * 8;
+        const size_t off_x = al((size_t)nb * k * c->unet.cfg.context_dim * 4), off_t = al(off_x + x_bytes), off_eps = al(off_t + t_bytes),
+                     off_extra = al(off_eps + x_bytes);
+        RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, off_extra + extra_bytes));
+        RDM_TRY(prepare_kv(c, (float*)c->samp, cond, uncond, B, k));
+        x = (float*)(c->samp + off_x); x_dup = uncond ? x + n1 : nullptr; eps = (float*)(c->samp + off_eps); extra = c->samp + off_extra;
+        tdev = (long long*)(c->samp + off_t);
+        {
+            std::vector<long long> th((size_t)total * nb);
+            for (int i = 0; i < total; i++) for (int j = 0; j < nb; j++) th[(size_t)i * nb + j] = ts[i];
+            RDM_CHECK_HIP(c, hipMemcpyAsync(tdev, th.data(), t_bytes, hipMemcpyHostToDevice, c->stream));
+            RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));   // th goes out of scope
+        }
+        RDM_CHECK_HIP(c, hipMemcpyAsync(x, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (x_dup) RDM_CHECK_HIP(c, hipMemcpyAsync(x_dup, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+        return sampler_emb_table(c, ts, &emb_table);
+    }
+    int forward(int idx) {        // guided: [x | x] at the same t, so the context-independent prefix runs once (shared half = B)
+        UNet& u = c->unet;
+        return unet_forward_impl(c, x, (const int64_t*)(tdev + (size_t)idx * nb), nullptr, u.kv_cache, nb, k, H, W, eps, u.ctx_rows,
+                                 x_dup ? B : 0, emb_table ? emb_table + (size_t)idx * u.emb_total : nullptr);
+    }
+    // intermediates of step `index` (counting down from total - 1): where the step kernel writes pred_x0, then the copy of the new x
+    bool logs(int index) const { return (index % log_every_t == 0) || (index == total - 1); }
+    float* pred_x0_slot(int index) const { return (logs(index) && pred_x0_inter) ? pred_x0_inter + (size_t)n_logged * n1 : nullptr; }
+    int log_x(int index) {
+        if (!logs(index)) return 0;
+        if (x_inter) RDM_CHECK_HIP(c, hipMemcpyAsync(x_inter + (size_t)n_logged * n1, x, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+        n_logged++;
+        return 0;
+    }
+    int finish(float* z_out) { RDM_CHECK_HIP(c, hipMemcpyAsync(z_out, x, n1 * 4, hipMemcpyDeviceToDevice, c->stream)); return 0; }
+};
+
 int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
                     const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    UNet& u = c->unet;
-    if (!u.loaded) return c->fail(-1, "unet weights not loaded");
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1 (ddim.py:223)");
     const bool cfg = a->unconditional_guidance_scale > 1.0f;
     if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1 (ddim.py:231)");
     if (a->eta != 0.f && !noise) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
-    const int B = a->batch, k = a->k;
-    const long long n1 = (long long)B * a->channels * a->height * a->width;
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
     const int total = (int)ts.size();
@@ -1649,45 +1692,21 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
         const double atd = (double)at[i], apd = (double)ap[i];
         sg[i] = (float)((double)a->eta * std::sqrt((1.0 - apd) / (1.0 - atd) * (1.0 - atd / apd)));
     }
-    // scratch: [cond|uncond] f32, x2 [2B], t [total][2B] int64, eps [2B]
-    const int nb = cfg ? 2 * B : B;
-    const size_t cd_bytes = (size_t)nb * k * u.cfg.context_dim * 4;
-    const size_t x2_bytes = (size_t)nb * (n1 / B) * 4, t_bytes = (size_t)total * nb * 8, eps_bytes = x2_bytes;
-    const size_t off_x2 = (cd_bytes + 255) & ~(size_t)255, off_t = (off_x2 + x2_bytes + 255) & ~(size_t)255,
-                 off_eps = (off_t + t_bytes + 255) & ~(size_t)255;
-    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, off_eps + eps_bytes));
-    int nbe = 0;
-    RDM_TRY(prepare_kv(c, cond, cfg ? uncond : nullptr, B, k, &nbe));
-    float* x2 = (float*)(c->samp + off_x2); long long* tdev = (long long*)(c->samp + off_t); float* eps = (float*)(c->samp + off_eps);
-    {
-        std::vector<long long> th((size_t)total * nb);
-        for (int i = 0; i < total; i++) for (int j = 0; j < nb; j++) th[(size_t)i * nb + j] = ts[i];
-        RDM_CHECK_HIP(c, hipMemcpyAsync(tdev, th.data(), t_bytes, hipMemcpyHostToDevice, c->stream));
-        RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));   // th goes out of scope
-    }
-    RDM_CHECK_HIP(c, hipMemcpyAsync(x2, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-    int n_logged = 0;
-    const float* emb_table = nullptr;
-    RDM_TRY(sampler_emb_table(c, ts, &emb_table));
+    SamplerRun run;
+    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr, 0));
+    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
     for (int i = 0; i < total; i++) {
         const int index = total - i - 1;
-        if (cfg && i == 0) RDM_CHECK_HIP(c, hipMemcpyAsync(x2 + n1, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));   // later steps: ddim_step writes both halves
-        RDM_TRY(unet_forward_impl(c, x2, (const int64_t*)(tdev + (size_t)index * nb), nullptr, u.kv_cache, nb, k, a->height, a->width, eps, u.ctx_rows,
-                                  cfg ? B : 0, emb_table ? emb_table + (size_t)index * u.emb_total : nullptr));     // [x | x], same t: the context-independent prefix runs once
-        const bool log = (index % a->log_every_t == 0) || (index == total - 1);
+        RDM_TRY(run.forward(index));
         DdimStepParams p{};
-        p.x = x2; p.eps = eps; p.noise = (noise && a->eta != 0.f) ? noise + (size_t)i * n1 : nullptr;
-        p.x_prev = x2; p.x_dup = cfg ? x2 + n1 : nullptr; p.pred_x0 = (log && pred_x0_inter) ? pred_x0_inter + (size_t)n_logged * n1 : nullptr;
-        p.n_per_batch = n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sigma_t = sg[index]; p.sqrt_one_minus_at = s1m[index];
+        p.x = run.x; p.eps = run.eps; p.noise = (noise && a->eta != 0.f) ? noise + (size_t)i * run.n1 : nullptr;
+        p.x_prev = run.x; p.x_dup = run.x_dup; p.pred_x0 = run.pred_x0_slot(index);
+        p.n_per_batch = run.n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sigma_t = sg[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.temperature = a->temperature; p.cfg = cfg ? 1 : 0;
         RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
-        if (log) {
-            if (x_inter) RDM_CHECK_HIP(c, hipMemcpyAsync(x_inter + (size_t)n_logged * n1, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-            n_logged++;
-        }
+        RDM_TRY(run.log_x(index));
     }
-    RDM_CHECK_HIP(c, hipMemcpyAsync(z_out, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
+    return run.finish(z_out);
 }
 
 // ldm PLMSSampler.plms_sampling / p_sample_plms (eta = 0): DDIM's schedule, timesteps and intermediates, total + 1 forwards.  The
@@ -1698,126 +1717,72 @@ int rdm_plms_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
                     float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    UNet& u = c->unet;
-    if (!u.loaded) return c->fail(-1, "unet weights not loaded");
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->eta != 0.f) return c->fail(-1, "ddim_eta must be 0 for PLMS");
     if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1");
     const bool cfg = a->unconditional_guidance_scale > 1.0f;
     if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1");
-    const int B = a->batch, k = a->k;
-    const long long n1 = (long long)B * a->channels * a->height * a->width;
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
     const int total = (int)ts.size();
-    // scratch: [cond|uncond] f32, x2 [2B], t [total][2B] int64, eps [2B], the kept x [B], 3 history slots [B]
-    const int nb = cfg ? 2 * B : B;
-    const size_t cd_bytes = (size_t)nb * k * u.cfg.context_dim * 4;
-    const size_t x2_bytes = (size_t)nb * (n1 / B) * 4, t_bytes = (size_t)total * nb * 8, eps_bytes = x2_bytes, x1_bytes = (size_t)n1 * 4;
-    const auto al = [](size_t v) { return (v + 255) & ~(size_t)255; };
-    const size_t off_x2 = al(cd_bytes), off_t = al(off_x2 + x2_bytes), off_eps = al(off_t + t_bytes), off_xk = al(off_eps + eps_bytes),
-                 off_h = al(off_xk + x1_bytes), h_stride = al(x1_bytes);
-    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, off_h + 3 * h_stride));
-    int nbe = 0;
-    RDM_TRY(prepare_kv(c, cond, cfg ? uncond : nullptr, B, k, &nbe));
-    float* x2 = (float*)(c->samp + off_x2); long long* tdev = (long long*)(c->samp + off_t); float* eps = (float*)(c->samp + off_eps);
-    float* xk = (float*)(c->samp + off_xk);
-    float* slot[3] = {(float*)(c->samp + off_h), (float*)(c->samp + off_h + h_stride), (float*)(c->samp + off_h + 2 * h_stride)};
-    {
-        std::vector<long long> th((size_t)total * nb);
-        for (int i = 0; i < total; i++) for (int j = 0; j < nb; j++) th[(size_t)i * nb + j] = ts[i];
-        RDM_CHECK_HIP(c, hipMemcpyAsync(tdev, th.data(), t_bytes, hipMemcpyHostToDevice, c->stream));
-        RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));   // th goes out of scope
-    }
-    RDM_CHECK_HIP(c, hipMemcpyAsync(x2, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-    if (cfg) RDM_CHECK_HIP(c, hipMemcpyAsync(x2 + n1, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));   // later: the step kernel writes both halves
-    RDM_CHECK_HIP(c, hipMemcpyAsync(xk, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));                 // the first step's x, kept beside x_tmp
-    const float* emb_table = nullptr;
-    RDM_TRY(sampler_emb_table(c, ts, &emb_table));
-    const auto forward = [&](int idx) {      // UNet on x2 = [x | x] at ts[idx], [cond | uncond]: the context-independent prefix runs once
-        return unet_forward_impl(c, x2, (const int64_t*)(tdev + (size_t)idx * nb), nullptr, u.kv_cache, nb, k, a->height, a->width, eps,
-                                 u.ctx_rows, cfg ? B : 0, emb_table ? emb_table + (size_t)idx * u.emb_total : nullptr);
-    };
-    int n_logged = 0, n_hist = 0;            // slot[0 .. n_hist) = o[-1], o[-2], o[-3]
+    // the sampler's own scratch: the kept x [B], 3 history slots [B]
+    const size_t h_stride = SamplerRun::al((size_t)a->batch * a->channels * a->height * a->width * 4);
+    SamplerRun run;
+    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr, 4 * h_stride));
+    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
+    float* xk = (float*)run.extra;
+    float* slot[3] = {(float*)(run.extra + h_stride), (float*)(run.extra + 2 * h_stride), (float*)(run.extra + 3 * h_stride)};
+    RDM_CHECK_HIP(c, hipMemcpyAsync(xk, x_T, run.n1 * 4, hipMemcpyDeviceToDevice, c->stream));             // the first step's x, kept beside x_tmp
+    int n_hist = 0;                          // slot[0 .. n_hist) = o[-1], o[-2], o[-3]
     for (int i = 0; i < total; i++) {
         const int index = total - i - 1;
-        const bool log = (index % a->log_every_t == 0) || (index == total - 1);
         PlmsStepParams p{};
-        p.eps = eps; p.n = n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sqrt_one_minus_at = s1m[index];
+        p.eps = run.eps; p.n = run.n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.cfg = cfg ? 1 : 0;
-        p.x_out = x2; p.x_dup = cfg ? x2 + n1 : nullptr;
+        p.x_out = run.x; p.x_dup = run.x_dup;
         float* e_new = slot[n_hist < 3 ? n_hist : 2];         // a free slot, or the oldest e_t (read before it is overwritten)
         p.e_store = e_new;
-        RDM_TRY(forward(index));
+        RDM_TRY(run.forward(index));
         if (n_hist == 0) {
-            p.x = xk; p.mode = PLMS_EULER_A;                   // x_tmp -> x2 (both halves); x stays in xk
+            p.x = xk; p.mode = PLMS_EULER_A;                   // x_tmp -> run.x (both halves); x stays in xk
             RDM_CHECK_HIP(c, launch_plms_step(p, c->stream));
-            RDM_TRY(forward(index > 0 ? index - 1 : 0));      // t_next = time_range[min(i + 1, total - 1)]
+            RDM_TRY(run.forward(index > 0 ? index - 1 : 0));  // t_next = time_range[min(i + 1, total - 1)]
             p.mode = PLMS_EULER_B; p.e_prev = e_new; p.e_store = nullptr;
         } else {
-            p.x = x2; p.mode = PLMS_STEP; p.order = n_hist;
+            p.x = run.x; p.mode = PLMS_STEP; p.order = n_hist;
             p.h1 = slot[0]; p.h2 = n_hist > 1 ? slot[1] : nullptr; p.h3 = n_hist > 2 ? slot[2] : nullptr;
         }
-        p.pred_x0 = (log && pred_x0_inter) ? pred_x0_inter + (size_t)n_logged * n1 : nullptr;
+        p.pred_x0 = run.pred_x0_slot(index);
         RDM_CHECK_HIP(c, launch_plms_step(p, c->stream));
         for (int j = n_hist < 3 ? n_hist : 2; j > 0; j--) slot[j] = slot[j - 1];
         slot[0] = e_new;
         if (n_hist < 3) n_hist++;
-        if (log) {
-            if (x_inter) RDM_CHECK_HIP(c, hipMemcpyAsync(x_inter + (size_t)n_logged * n1, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-            n_logged++;
-        }
+        RDM_TRY(run.log_x(index));
     }
-    RDM_CHECK_HIP(c, hipMemcpyAsync(z_out, x2, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
+    return run.finish(z_out);
 }
 
 int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const float* noise,
                     float* z_out) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !noise || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    UNet& u = c->unet;
-    if (!u.loaded) return c->fail(-1, "unet weights not loaded");
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->timesteps < 1 || a->timesteps > a->T) return c->fail(-1, "bad timesteps");
-    const int B = a->batch, k = a->k, T = a->timesteps;
-    const long long n1 = (long long)B * a->channels * a->height * a->width;
-    const size_t cd_bytes = (size_t)B * k * u.cfg.context_dim * 4;
-    const size_t off_x = (cd_bytes + 255) & ~(size_t)255, off_t = (off_x + n1 * 4 + 255) & ~(size_t)255,
-                 off_eps = (off_t + (size_t)T * B * 8 + 255) & ~(size_t)255;
-    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, off_eps + n1 * 4));
-    int nbe = 0;
-    RDM_TRY(prepare_kv(c, cond, nullptr, B, k, &nbe));
-    float* x = (float*)(c->samp + off_x); long long* tdev = (long long*)(c->samp + off_t); float* eps = (float*)(c->samp + off_eps);
-    {
-        std::vector<long long> th((size_t)T * B);
-        for (int i = 0; i < T; i++) for (int j = 0; j < B; j++) th[(size_t)i * B + j] = i;
-        RDM_CHECK_HIP(c, hipMemcpyAsync(tdev, th.data(), th.size() * 8, hipMemcpyHostToDevice, c->stream));
-        RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    }
-    RDM_CHECK_HIP(c, hipMemcpyAsync(x, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-    // the T timesteps' time-embedding rows once per call (as rdm_ddim_sample: every sample of a step shares the step's timestep)
-    const float* emb_table = nullptr;
-    if (!c->deterministic) {
-        RDM_TRY(ensure_bytes(c, (char**)&u.emb_table, &u.emb_table_bytes, (size_t)T * u.emb_total * 4 + (size_t)T * 8 + 256));
-        long long* tuniq = (long long*)((char*)u.emb_table + (((size_t)T * u.emb_total * 4 + 255) & ~(size_t)255));
-        std::vector<long long> th((size_t)T);
-        for (int i = 0; i < T; i++) th[i] = i;
-        RDM_CHECK_HIP(c, hipMemcpyAsync(tuniq, th.data(), (size_t)T * 8, hipMemcpyHostToDevice, c->stream));
-        RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-        RDM_TRY(run_with_arena(c, u.arena, u.blob, [&](Ops& o) { unet_time_rows(o, u, tuniq, T, u.emb_table); }));
-        emb_table = u.emb_table;
-    }
+    const int T = a->timesteps;
+    std::vector<int> ts(T);
+    for (int i = 0; i < T; i++) ts[i] = i;
+    SamplerRun run;
+    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, nullptr, 0));
     for (int n = 0, i = T - 1; i >= 0; i--, n++) {
-        RDM_TRY(unet_forward_impl(c, x, (const int64_t*)(tdev + (size_t)i * B), nullptr, u.kv_cache, B, k, a->height, a->width, eps, B, 0,
-                                  emb_table ? emb_table + (size_t)i * u.emb_total : nullptr));
+        RDM_TRY(run.forward(i));
         DdpmStepParams p{};
-        p.x = x; p.eps = eps; p.noise = noise + (size_t)n * n1; p.x_prev = x; p.n = n1;
+        p.x = run.x; p.eps = run.eps; p.noise = noise + (size_t)n * run.n1; p.x_prev = run.x; p.n = run.n1;
         p.sqrt_recip = a->sqrt_recip_alphas_cumprod[i]; p.sqrt_recipm1 = a->sqrt_recipm1_alphas_cumprod[i];
         p.coef1 = a->posterior_mean_coef1[i]; p.coef2 = a->posterior_mean_coef2[i]; p.log_var = a->posterior_log_variance_clipped[i];
         p.clip = a->clip_denoised; p.nonzero = (i != 0); p.temperature = a->temperature;
         RDM_CHECK_HIP(c, launch_ddpm_step(p, c->stream));
     }
-    RDM_CHECK_HIP(c, hipMemcpyAsync(z_out, x, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-    return 0;
+    return run.finish(z_out);
 }
 
 // Samples per decoder pass.  Decoding is per sample (GroupNorm statistics included), so a batch may be walked in ranges; a range is

@@ -33,7 +33,9 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
     return sigmas, alphas, alphas_prev
 
 
-class DDIMSampler(object):
+class _SamplerBase(object):
+    """What DDIMSampler and PLMSSampler share: the constructor, DDIM's schedule, and the rules both loops apply around a step."""
+
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
         self.model = model
@@ -53,6 +55,53 @@ class DDIMSampler(object):
         self.register_buffer('ddim_alphas', al)
         self.register_buffer('ddim_alphas_prev', alp)
         self.register_buffer('ddim_sqrt_one_minus_alphas', np.sqrt(1. - al))
+
+    @staticmethod
+    def _unwrap(c, single=None):
+        """A conditioning given as a dict (its first value) or a list (its first entry).  `single` names the loop that takes one
+        cross-attention tensor only and refuses a longer list."""
+        if isinstance(c, dict):
+            c = c[list(c.keys())[0]]
+        if isinstance(c, (list, tuple)):
+            if single is not None and len(c) != 1:
+                raise NotImplementedError(f"native {single} loop takes a single cross-attention conditioning tensor")
+            c = c[0]
+        return c
+
+    @staticmethod
+    def _refuse_original_steps(ddim_use_original_steps):
+        if ddim_use_original_steps:
+            raise NotImplementedError("ddim_use_original_steps: dead in the reference (ddim.py:249 reads a buffer that lives on the sampler, "
+                                      "not on the model: AttributeError)")
+
+    def _timestep_subset(self, timesteps):
+        if timesteps is None:
+            return self.ddim_timesteps
+        subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1     # ddim.py:158-160
+        return self.ddim_timesteps[:subset_end]
+
+    @staticmethod
+    def _logs(index, log_every_t, total_steps):
+        return index % log_every_t == 0 or index == total_steps - 1
+
+    def _masked_blend(self, img, mask, x0, ts, q_noise):
+        """Inpainting: outside the mask keep the sample, inside take x0 noised to the step's timestep."""
+        assert x0 is not None
+        img_orig = self._q_sample(x0, ts, q_noise)
+        return img_orig * mask + (1. - mask) * img
+
+    def _q_sample(self, x_start, t, noise=None):
+        """The model's q_sample; a model without one (a stand-in) gets it restated from its alphas_cumprod."""
+        if hasattr(self.model, "q_sample"):
+            return self.model.q_sample(x_start, t, noise=noise)
+        noise = torch.randn_like(x_start) if noise is None else noise
+        ac = self.model.alphas_cumprod.detach().double().cpu()
+        sa = torch.sqrt(ac).float().to(x_start.device)[t].reshape(-1, 1, 1, 1)
+        s1m = torch.sqrt(1. - ac).float().to(x_start.device)[t].reshape(-1, 1, 1, 1)
+        return sa * x_start + s1m * noise
+
+
+class DDIMSampler(_SamplerBase):
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
@@ -81,20 +130,12 @@ class DDIMSampler(object):
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, random_guiding='none', content_cond=None, style_cond=None,
                       intermediates_to_cpu=False, S=None, eta=0., **kwargs):
-        if ddim_use_original_steps:
-            raise NotImplementedError("ddim_use_original_steps: dead in the reference (ddim.py:249 reads a buffer that lives on the sampler, "
-                                      "not on the model: AttributeError)")
+        self._refuse_original_steps(ddim_use_original_steps)
         # options that change the loop body step by step run through the per-step path (native UNet forward per step)
         per_step = (quantize_denoised or mask is not None or x0 is not None or noise_dropout > 0. or score_corrector is not None or
                     content_cond is not None or style_cond is not None or random_guiding != 'none' or timesteps is not None)
-        if isinstance(cond, dict):
-            cond = cond[list(cond.keys())[0]]
-        if isinstance(cond, list):
-            if len(cond) != 1:
-                raise NotImplementedError("native DDIM loop takes a single cross-attention conditioning tensor")
-            cond = cond[0]
-        if isinstance(unconditional_conditioning, list):
-            unconditional_conditioning = unconditional_conditioning[0]
+        cond = self._unwrap(cond, single="DDIM")
+        unconditional_conditioning = self._unwrap(unconditional_conditioning)
         assert unconditional_guidance_scale >= 1.
         if unconditional_guidance_scale > 1.:
             assert unconditional_conditioning is not None
@@ -103,13 +144,11 @@ class DDIMSampler(object):
         total_steps = self.ddim_timesteps.shape[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
         if callback is not None or img_callback is not None or per_step:
-            unwrap = lambda c: c[0] if isinstance(c, (list, tuple)) else (c[list(c.keys())[0]] if isinstance(c, dict) else c)
             return self._python_loop(cond, img, callback, img_callback, log_every_t, temperature, eta,
                                      unconditional_guidance_scale, unconditional_conditioning, intermediates_to_cpu,
                                      mask=mask, x0=x0, noise_dropout=noise_dropout, score_corrector=score_corrector,
                                      corrector_kwargs=corrector_kwargs, random_guiding=random_guiding, timesteps=timesteps,
-                                     content_cond=None if content_cond is None else unwrap(content_cond),
-                                     style_cond=None if style_cond is None else unwrap(style_cond),
+                                     content_cond=self._unwrap(content_cond), style_cond=self._unwrap(style_cond),
                                      noise=kwargs.get("noise"), q_noise=kwargs.get("q_noise"), quantize_denoised=quantize_denoised)
         noise = kwargs.get("noise")             # [native] optional explicit per-step noise stack [S, B, C, H, W] (consumed in loop order)
         if eta != 0. and noise is None:
@@ -127,10 +166,7 @@ class DDIMSampler(object):
         """Per-step path of ddim.py:143-209 (callbacks, inpainting mask, style / content conditioning by SNR band, timestep
         subset, noise dropout, score corrector): native UNet forward per step, torch elementwise update.  `noise` / `q_noise`
         [native]: optional explicit stacks [steps, B, C, H, W] for the update noise and for q_sample of the masked region."""
-        ts_all = self.ddim_timesteps
-        if timesteps is not None:                                   # ddim.py:158-160
-            subset_end = int(min(timesteps / ts_all.shape[0], 1) * ts_all.shape[0]) - 1
-            ts_all = ts_all[:subset_end]
+        ts_all = self._timestep_subset(timesteps)
         total_steps = ts_all.shape[0]
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         b = img.shape[0]
@@ -147,9 +183,7 @@ class DDIMSampler(object):
             if content_cond is not None and snr >= 5.e-2 and snr < 1.:
                 input_cond = content_cond
             if mask is not None:
-                assert x0 is not None
-                img_orig = self.model.q_sample(x0, ts, noise=None if q_noise is None else q_noise[i])
-                img = img_orig * mask + (1. - mask) * img
+                img = self._masked_blend(img, mask, x0, ts, None if q_noise is None else q_noise[i])
             if random_guiding == 'sampled':
                 random_guider = torch.clamp(torch.randn(img.shape, device=img.device), -1., 1.)
             img, pred_x0 = self.p_sample_ddim(img, input_cond, ts, index=index, temperature=temperature, quantize_denoised=quantize_denoised,
@@ -159,7 +193,7 @@ class DDIMSampler(object):
                                               random_guider=random_guider)
             if callback: callback(i)
             if img_callback: img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total_steps - 1:
+            if self._logs(index, log_every_t, total_steps):
                 intermediates['x_inter'].append(img.cpu() if to_cpu else img)
                 intermediates['pred_x0'].append(pred_x0.cpu() if to_cpu else pred_x0)
         return img, intermediates

@@ -14,32 +14,15 @@ NotImplementedError, for the reason given in ddim.py.
 import numpy as np
 import torch
 
-from .ddim import make_ddim_sampling_parameters, make_ddim_timesteps
+from .ddim import _SamplerBase
 
 
-class PLMSSampler(object):
-    def __init__(self, model, schedule="linear", **kwargs):
-        super().__init__()
-        self.model = model
-        self.ddpm_num_timesteps = model.num_timesteps
-        self.schedule = schedule
-
-    def register_buffer(self, name, attr):
-        setattr(self, name, attr)
-
+class PLMSSampler(_SamplerBase):
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
         if ddim_eta != 0:
             raise ValueError('ddim_eta must be 0 for PLMS')
         self.ddim_num_steps = ddim_num_steps            # [native] the S the library rebuilds this schedule from
-        self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
-        ac = self.model.alphas_cumprod.detach().float().cpu()
-        assert ac.shape[0] == self.ddpm_num_timesteps, 'alphas have to be defined for each timestep'
-        self.register_buffer('alphas_cumprod', ac)
-        sig, al, alp = make_ddim_sampling_parameters(ac.numpy(), self.ddim_timesteps, ddim_eta, verbose)
-        self.register_buffer('ddim_sigmas', sig)
-        self.register_buffer('ddim_alphas', al)
-        self.register_buffer('ddim_alphas_prev', alp)
-        self.register_buffer('ddim_sqrt_one_minus_alphas', np.sqrt(1. - al))
+        super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose)
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
@@ -64,17 +47,9 @@ class PLMSSampler(object):
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, q_noise=None):
         """`q_noise` [native]: optional explicit stack [steps, B, C, H, W] for q_sample of the masked region (per-step path)."""
-        if ddim_use_original_steps:
-            raise NotImplementedError("ddim_use_original_steps: dead in the reference (ddim.py:249 reads a buffer that lives on the sampler, "
-                                      "not on the model: AttributeError)")
-        if isinstance(cond, dict):
-            cond = cond[list(cond.keys())[0]]
-        if isinstance(cond, list):
-            if len(cond) != 1:
-                raise NotImplementedError("native PLMS loop takes a single cross-attention conditioning tensor")
-            cond = cond[0]
-        if isinstance(unconditional_conditioning, list):
-            unconditional_conditioning = unconditional_conditioning[0]
+        self._refuse_original_steps(ddim_use_original_steps)
+        cond = self._unwrap(cond, single="PLMS")
+        unconditional_conditioning = self._unwrap(unconditional_conditioning)
         device = self.model.device
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
         per_step = (callback is not None or img_callback is not None or quantize_denoised or mask is not None or x0 is not None or
@@ -95,11 +70,7 @@ class PLMSSampler(object):
     def _python_loop(self, cond, img, callback, img_callback, log_every_t, timesteps, quantize_denoised, mask, x0, score_corrector,
                      corrector_kwargs, scale, uc, q_noise):
         """Per-step path of plms_sampling: native apply_model per forward, torch fp32 update."""
-        if timesteps is None:
-            timesteps = self.ddim_timesteps
-        else:
-            subset_end = int(min(timesteps / self.ddim_timesteps.shape[0], 1) * self.ddim_timesteps.shape[0]) - 1
-            timesteps = self.ddim_timesteps[:subset_end]
+        timesteps = self._timestep_subset(timesteps)
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         time_range = np.flip(timesteps)
         total_steps = timesteps.shape[0]
@@ -111,9 +82,7 @@ class PLMSSampler(object):
             ts = torch.full((b,), int(step), device=img.device, dtype=torch.long)
             ts_next = torch.full((b,), int(time_range[min(i + 1, len(time_range) - 1)]), device=img.device, dtype=torch.long)
             if mask is not None:
-                assert x0 is not None
-                img_orig = self._q_sample(x0, ts, None if q_noise is None else q_noise[i])
-                img = img_orig * mask + (1. - mask) * img
+                img = self._masked_blend(img, mask, x0, ts, None if q_noise is None else q_noise[i])
             img, pred_x0, e_t = self.p_sample_plms(img, cond, ts, index=index, quantize_denoised=quantize_denoised,
                                                    score_corrector=score_corrector, corrector_kwargs=corrector_kwargs,
                                                    unconditional_guidance_scale=scale, unconditional_conditioning=uc,
@@ -123,20 +92,10 @@ class PLMSSampler(object):
                 old_eps.pop(0)
             if callback: callback(i)
             if img_callback: img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == total_steps - 1:
+            if self._logs(index, log_every_t, total_steps):
                 intermediates['x_inter'].append(img)
                 intermediates['pred_x0'].append(pred_x0)
         return img, intermediates
-
-    def _q_sample(self, x_start, t, noise=None):
-        """The model's q_sample; a model without one (a stand-in) gets it restated from its alphas_cumprod."""
-        if hasattr(self.model, "q_sample"):
-            return self.model.q_sample(x_start, t, noise=noise)
-        noise = torch.randn_like(x_start) if noise is None else noise
-        ac = self.model.alphas_cumprod.detach().double().cpu()
-        sa = torch.sqrt(ac).float().to(x_start.device)[t].reshape(-1, 1, 1, 1)
-        s1m = torch.sqrt(1. - ac).float().to(x_start.device)[t].reshape(-1, 1, 1, 1)
-        return sa * x_start + s1m * noise
 
     @torch.no_grad()
     def p_sample_plms(self, x, c, t, index, repeat_noise=False, use_original_steps=False, quantize_denoised=False,

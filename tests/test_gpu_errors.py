@@ -80,6 +80,7 @@ def test_blob_and_shape_mismatches(fresh):
     ac = torch.linspace(0.999, 0.005, 1000)
     _err(lambda: fresh.ddim_sample(4, x, c, c[:, :2], ac, scale=2.0))      # unconditional conditioning with another k
     _err(lambda: fresh.ddim_sample(4, x, c, None, ac, eta=1.0, noise=torch.zeros(3, B, 3, 16, 16, device=d)))   # noise stack shorter than the loop
+    assert "bad schedule" in _err(lambda: fresh.ddim_sample(0, x, c, None, ac, want_intermediates=True))   # S = 0 reaches the library
     z, _, _ = fresh.ddim_sample(4, x, c, None, ac)                         # and the context is still alive
     assert torch.isfinite(z).all()
 
