@@ -191,6 +191,14 @@ int rdm_to_uint8(rdm_ctx* ctx, const float* img, int b, int c, int h, int w, uin
 int rdm_rarm_forward(rdm_ctx* ctx, const int64_t* tokens, int b, int t, const float* context, int k, float* logits_out);
 int rdm_rarm_sample(rdm_ctx* ctx, const rdm_rarm_sample_args* args, const int64_t* cond_tokens, const float* context,
                     const float* uniforms, int64_t* tokens_out);
+/* rdm_rarm_sample with the nucleus (top-p) filter that `sample`, `sampling_util` and `log_images` name as `top_p` and the reference
+ * refuses (rdm/models/autoregression/transformer.py:279-280 `assert top_p==1., 'not yet implemented'`, :427, :454-472).  top_p in
+ * (0, 1], anything else (NaN included) is an argument error; 1 is rdm_rarm_sample itself.  Below 1, per sequence and step, AFTER the
+ * top-k rule (survivors K, ties with the k-th kept): p_i = softmax over K; the nucleus is { i in K : g_i >= theta } for the LARGEST
+ * logit value theta present in K whose mass M(theta) = sum of p_i over g_i >= theta reaches top_p -- the smallest descending prefix
+ * that reaches top_p, the crossing token kept, every token tied with the last kept one kept too.  The draw is unchanged. */
+int rdm_rarm_sample_top_p(rdm_ctx* ctx, const rdm_rarm_sample_args* args, float top_p, const int64_t* cond_tokens, const float* context,
+                          const float* uniforms, int64_t* tokens_out);
 
 /* ---- CLIP: CLIP.encode_text / encode_image (rdm/modules/custom_clip/model.py:304-320), used by
  *      ClipImageRetriever / CLIPTextEmbedder (rdm/modules/retrievers.py:67-117).
@@ -296,6 +304,10 @@ int rdm_op_conv3x3(rdm_ctx* ctx, const void* x0_bf16, const void* x1_bf16, int C
  * (conditional rows first), uniforms [dev] f32 [b], tokens_out [dev] int64 [b].  top_k <= 0: no filter. */
 int rdm_op_rarm_sampler(rdm_ctx* ctx, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature,
                         int top_k, const float* uniforms, int64_t* tokens_out);
+/* the same kernel with the nucleus filter of rdm_rarm_sample_top_p (the `top_p` of transformer.py:279-280, unbuilt there): top_p in
+ * (0, 1], 1 = no nucleus filter.  kept_out: optional [dev] int32 [b], receives the number of tokens each row kept (after top-k and top-p). */
+int rdm_op_rarm_sampler_top_p(rdm_ctx* ctx, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature,
+                              int top_k, float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out);
 /* ---- backward building blocks of the training step (reference rdm/models/diffusion/ddpm.py:390-443 shared_step -> ldm
  * p_losses -> autograd through UNetModel): gradients of the ResBlock's ops.  bf16 activations / activation gradients, fp32 weight
  * gradients.  conv3x3: stride 1, pad 1, weights [N][3][3][C].  Tested against torch autograd (tests/test_gpu_backward.py). */

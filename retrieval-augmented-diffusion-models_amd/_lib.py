@@ -81,6 +81,7 @@ SIGNATURES = {
     "rdm_load_rarm": (C.c_int, [_P, C.POINTER(RarmCfg), _P, C.c_size_t]),
     "rdm_rarm_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "rdm_rarm_sample": (C.c_int, [_P, C.POINTER(RarmSampleArgs), _P, _P, _P, _P]),
+    "rdm_rarm_sample_top_p": (C.c_int, [_P, C.POINTER(RarmSampleArgs), C.c_float, _P, _P, _P, _P]),
     "rdm_vq_decode_indices": (C.c_int, [_P, _P, C.c_int, _P]),
     "rdm_unet_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_ddim_num_intermediates": (C.c_int, [C.c_int, C.c_int]),
@@ -127,6 +128,7 @@ SIGNATURES = {
     "rdm_op_conv3x3": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int]),
     "rdm_op_rarm_sampler": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
+    "rdm_op_rarm_sampler_top_p": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P]),
     "rdm_op_conv3x3_dgrad": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_conv3x3_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_groupnorm_bwd": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_int, _P, _P, _P]),
@@ -286,6 +288,19 @@ class RdmError(RuntimeError):
     pass
 
 
+def check_top_p(what, top_p):
+    """The nucleus mass of the RARM sampler: None or 1.0 -> None (no nucleus filter, the entry without one); a number in (0, 1) -> float."""
+    if top_p is None:
+        return None
+    try:
+        v = float(top_p)
+    except (TypeError, ValueError):
+        raise RdmError(f"{what}: top_p must be a number in (0, 1], got {top_p!r}") from None
+    if not (0.0 < v <= 1.0):                                   # NaN fails both comparisons
+        raise RdmError(f"{what}: top_p must lie in (0, 1], got {top_p!r}")
+    return None if v == 1.0 else v
+
+
 class Context:
     """One library context per HIP device (include/rdm_hip.h: rdm_ctx)."""
 
@@ -381,8 +396,10 @@ class Context:
         self._check(lib.rdm_rarm_forward(self._h, _ptr(tokens), b, t, _ptr(context), context.shape[1], _ptr(out)))
         return out
 
-    def rarm_sample(self, cond_tokens, context, steps, uniforms, temperature=1.0, top_k=None, guidance_scale=1.0):
-        """LatentImageRETRO.sample with sample=True: -> tokens int64 [b,steps].  uniforms f32 [steps,b] in [0,1)."""
+    def rarm_sample(self, cond_tokens, context, steps, uniforms, temperature=1.0, top_k=None, guidance_scale=1.0, top_p=None):
+        """LatentImageRETRO.sample with sample=True: -> tokens int64 [b,steps].  uniforms f32 [steps,b] in [0,1).
+        top_p in (0, 1]: nucleus filter after top-k (include/rdm_hip.h rdm_rarm_sample_top_p); None or 1.0: none, today's entry."""
+        top_p = check_top_p("rarm_sample", top_p)
         cond_tokens = self._dev(cond_tokens, torch.int64); context = self._dev(context, torch.float32)
         uniforms = self._dev(uniforms, torch.float32)
         b, tc = cond_tokens.shape
@@ -393,7 +410,10 @@ class Context:
         a = RarmSampleArgs(batch=b, k=context.shape[1], cond_len=tc, steps=steps, temperature=temperature,
                            top_k=int(top_k) if top_k is not None else 0, guidance_scale=guidance_scale)
         out = torch.empty((b, steps), device=self.device, dtype=torch.int64)
-        self._check(lib.rdm_rarm_sample(self._h, C.byref(a), _ptr(cond_tokens), _ptr(context), _ptr(uniforms), _ptr(out)))
+        if top_p is None:
+            self._check(lib.rdm_rarm_sample(self._h, C.byref(a), _ptr(cond_tokens), _ptr(context), _ptr(uniforms), _ptr(out)))
+        else:
+            self._check(lib.rdm_rarm_sample_top_p(self._h, C.byref(a), top_p, _ptr(cond_tokens), _ptr(context), _ptr(uniforms), _ptr(out)))
         return out
 
     def vq_decode_indices(self, indices):
@@ -722,17 +742,25 @@ class Context:
                                        stride, ups))
         return out
 
-    def op_rarm_sampler(self, logits, uniforms, guidance_scale=1.0, temperature=1.0, top_k=None):
-        """The sampler kernel alone: logits f32 [(2 if guided else 1) * b, vocab] (conditional rows first), uniforms f32 [b] -> int64 [b]."""
+    def op_rarm_sampler(self, logits, uniforms, guidance_scale=1.0, temperature=1.0, top_k=None, top_p=None, return_kept=False):
+        """The sampler kernel alone: logits f32 [(2 if guided else 1) * b, vocab] (conditional rows first), uniforms f32 [b] -> int64 [b].
+        top_p in (0, 1]: nucleus filter after top-k; None or 1.0: none.  return_kept: -> (tokens, int32 [b] tokens each row kept)."""
+        top_p = check_top_p("op_rarm_sampler", top_p)
         logits = self._dev(logits, torch.float32); uniforms = self._dev(uniforms, torch.float32)
         b = uniforms.shape[0]
         cfg = guidance_scale > 1.0
         if logits.ndim != 2 or logits.shape[0] != (2 * b if cfg else b):
             raise RdmError(f"op_rarm_sampler: logits must be [{2 * b if cfg else b}, vocab], got {tuple(logits.shape)}")
         out = torch.empty((b,), device=self.device, dtype=torch.int64)
-        self._check(lib.rdm_op_rarm_sampler(self._h, _ptr(logits), b, logits.shape[1], int(cfg), float(guidance_scale), float(temperature),
-                                            int(top_k) if top_k is not None else 0, _ptr(uniforms), _ptr(out)))
-        return out
+        k = int(top_k) if top_k is not None else 0
+        if top_p is None and not return_kept:
+            self._check(lib.rdm_op_rarm_sampler(self._h, _ptr(logits), b, logits.shape[1], int(cfg), float(guidance_scale), float(temperature),
+                                                k, _ptr(uniforms), _ptr(out)))
+            return out
+        kept = torch.empty((b,), device=self.device, dtype=torch.int32) if return_kept else None
+        self._check(lib.rdm_op_rarm_sampler_top_p(self._h, _ptr(logits), b, logits.shape[1], int(cfg), float(guidance_scale), float(temperature),
+                                                  k, 1.0 if top_p is None else top_p, _ptr(uniforms), _ptr(out), _ptr(kept)))
+        return (out, kept) if return_kept else out
 
     # ---- backward building blocks (include/rdm_hip.h "backward"; composed in rdm_amd/training.py)
     def op_conv3x3_dgrad(self, dy, w):

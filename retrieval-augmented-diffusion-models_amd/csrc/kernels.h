@@ -121,6 +121,8 @@ struct RarmSampleParams {
     const float* uniforms;                    // [steps][B], row = *pos - pos0
     int* pos; int pos0; int steps;            // tokens_out[b*steps + (*pos - pos0)]
     long long* tokens_out; long long* next_tokens; int* done;
+    float top_p = 1.0f;                       // in (0, 1]; < 1: nucleus filter among the top-k survivors (the nucleus instantiation)
+    int* kept_out = nullptr;                  // optional [B]: tokens each row kept
 };
 hipError_t launch_rarm_embed(const long long* tokens, const float* emb, const float* pos_t, const int* pos, float* x, int B, int C,
                              int vocab, hipStream_t st);

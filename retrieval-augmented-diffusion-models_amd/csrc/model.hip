@@ -2053,8 +2053,20 @@ int rdm_rarm_forward(rdm_ctx* c, const int64_t* tokens, int b, int t, const floa
     }
     return 0;
 }
+static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
+                           const float* uniforms, int64_t* tokens_out);
 int rdm_rarm_sample(rdm_ctx* c, const rdm_rarm_sample_args* a, const int64_t* cond_tokens, const float* context, const float* uniforms,
                     int64_t* tokens_out) {
+    return rarm_sample_run(c, a, 1.0f, cond_tokens, context, uniforms, tokens_out);
+}
+int rdm_rarm_sample_top_p(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
+                          const float* uniforms, int64_t* tokens_out) {
+    RDM_ENTER(c);
+    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_rarm_sample_top_p: top_p must lie in (0, 1], got %g", (double)top_p);
+    return rarm_sample_run(c, a, top_p, cond_tokens, context, uniforms, tokens_out);
+}
+static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
+                           const float* uniforms, int64_t* tokens_out) {
     RDM_ENTER(c);
     if (!a || !cond_tokens || !context || !uniforms || !tokens_out) return c->fail(-1, "null argument");
     if (a->cond_len < 1 || a->steps < 1 || a->temperature <= 0.f) return c->fail(-1, "bad sampling arguments");
@@ -2072,6 +2084,7 @@ int rdm_rarm_sample(rdm_ctx* c, const rdm_rarm_sample_args* a, const int64_t* co
     RarmSampleParams sp{}; sp.logits = st.logits; sp.vocab = m.cfg.vocab_out; sp.B = B; sp.cfg = cfg ? 1 : 0; sp.scale = a->guidance_scale;
     sp.temperature = a->temperature; sp.top_k = a->top_k > 0 ? a->top_k : m.cfg.vocab_out; sp.uniforms = uniforms; sp.pos = st.pos;
     sp.pos0 = a->cond_len - 1; sp.steps = a->steps; sp.tokens_out = (long long*)tokens_out; sp.next_tokens = st.tokens; sp.done = st.done;
+    sp.top_p = top_p;
     for (int s_ = 0; s_ < a->steps; s_++) {                    // every step: the same launches (the step counter lives on the device)
         RDM_TRY(rarm_step(c, B2, k, a->cond_len - 1 + s_));
         RDM_CHECK_HIP(c, launch_rarm_sample(sp, c->stream));
@@ -2297,8 +2310,20 @@ int rdm_op_conv3x3(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, c
             (const bf16_t*)res, (bf16_t*)out);
     return o.rc;
 }
+static int op_rarm_sampler_run(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
+                               float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out);
 int rdm_op_rarm_sampler(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
                         const float* uniforms, int64_t* tokens_out) {
+    return op_rarm_sampler_run(c, logits, b, vocab, cfg, guidance_scale, temperature, top_k, 1.0f, uniforms, tokens_out, nullptr);
+}
+int rdm_op_rarm_sampler_top_p(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
+                              float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out) {
+    RDM_ENTER(c);
+    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_op_rarm_sampler_top_p: top_p must lie in (0, 1], got %g", (double)top_p);
+    return op_rarm_sampler_run(c, logits, b, vocab, cfg, guidance_scale, temperature, top_k, top_p, uniforms, tokens_out, kept_out);
+}
+static int op_rarm_sampler_run(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
+                               float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out) {
     RDM_ENTER(c);
     if (!logits || !uniforms || !tokens_out || b < 1 || vocab < 1) return c->fail(-1, "rdm_op_rarm_sampler: bad arguments");
     if (!(temperature > 0.f)) return c->fail(-1, "rdm_op_rarm_sampler: temperature must be positive");
@@ -2308,7 +2333,7 @@ int rdm_op_rarm_sampler(rdm_ctx* c, const float* logits, int b, int vocab, int c
     RDM_CHECK_HIP(c, launch_set_int(done, 0, c->stream));
     RarmSampleParams sp{}; sp.logits = logits; sp.vocab = vocab; sp.B = b; sp.cfg = cfg ? 1 : 0; sp.scale = guidance_scale; sp.temperature = temperature;
     sp.top_k = top_k > 0 ? top_k : vocab; sp.uniforms = uniforms; sp.pos = pos; sp.pos0 = 0; sp.steps = 1; sp.tokens_out = (long long*)tokens_out;
-    sp.next_tokens = next; sp.done = done;
+    sp.next_tokens = next; sp.done = done; sp.top_p = top_p; sp.kept_out = kept_out;
     RDM_CHECK_HIP(c, launch_rarm_sample(sp, c->stream));
     return 0;
 }

@@ -370,6 +370,19 @@ hipError_t launch_rarm_xattn_decode(const RarmXattnParams& p, hipStream_t st) {
 // halves), and — last block — advances *pos.
 __device__ __forceinline__ uint32_t f2ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 
+// Sum of one value per thread over the block of 256 in a FIXED order: xor butterfly inside each wave (every lane ends with the same
+// bits), then (w0 + w1) + (w2 + w3) of the four wave sums.  `slot` is four floats the caller alternates between rounds: one barrier.
+__device__ __forceinline__ float rarm_block_sum_fixed(float v, float* slot, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((tid & 63) == 0) slot[tid >> 6] = v;
+    __syncthreads();
+    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
+}
+
+// NUCLEUS: the top-p filter after the top-k one (below).  COUNT: p.kept_out[b] receives the number of kept tokens.  Both are
+// compile-time variants: rarm_sample_kernel<false, false>, the top_p == 1 path of every older entry, carries none of their code.
+template <bool NUCLEUS, bool COUNT>
 __global__ __launch_bounds__(256) void rarm_sample_kernel(RarmSampleParams p) {
     __shared__ uint32_t hist[256];
     __shared__ float red[256];
@@ -399,6 +412,7 @@ __global__ __launch_bounds__(256) void rarm_sample_kernel(RarmSampleParams p) {
     const int remaining0 = p.top_k < V ? p.top_k : V;
     constexpr int KPT = 64;                                   // keys per thread: vocabularies up to 16 384; longer ones loop below
     uint32_t prefix = 0;
+    [[maybe_unused]] uint32_t theta = 0;                      // NUCLEUS: order image of the smallest logit of the nucleus
     if (V <= 256 * KPT) {
         uint32_t key[KPT];
 #pragma unroll
@@ -420,6 +434,47 @@ __global__ __launch_bounds__(256) void rarm_sample_kernel(RarmSampleParams p) {
             const int tot1 = (int)(t12 & 0xffffu), tot2 = (int)(t12 >> 16);
             if (tot3 >= remaining0) prefix = c3; else if (tot2 >= remaining0) prefix = c2; else if (tot1 >= remaining0) prefix = c1;
         }
+        if constexpr (NUCLEUS) {
+            // ---- top-p among the top-k survivors K = {key >= prefix}: M(theta) = sum over K of exp(g - max) with key >= theta never grows
+            // with theta, so the largest threshold whose mass still reaches top_p * M(k-th) is found by the same bit-wise search, a round
+            // SUMMING the exponentials at or above the candidates where the top-k round counted keys.  The 64 exponentials sit in
+            // registers beside the keys (0 for the tokens top-k dropped).  Every mass is added in one fixed order -- four chains of 16
+            // per thread, (a0 + a1) + (a2 + a3), the wave butterfly, (w0 + w1) + (w2 + w3): 26 additions deep -- and dropping a term
+            // only replaces it by 0, so the rounded M is still monotone and depends on neither the batch nor the launch.
+            float ex[KPT];
+            float m = -INFINITY;
+#pragma unroll
+            for (int u = 0; u < KPT; u++) { const int i = tid + u * 256; ex[u] = i < V ? logit(i) : -INFINITY; m = fmaxf(m, ex[u]); }
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+            if ((tid & 63) == 0) red[40 + (tid >> 6)] = m;
+            __syncthreads();
+            m = fmaxf(fmaxf(red[40], red[41]), fmaxf(red[42], red[43]));           // the arg-max always survives top-k: the max of K
+#pragma unroll
+            for (int u = 0; u < KPT; u++) ex[u] = key[u] >= prefix ? __expf(ex[u] - m) : 0.f;
+            float a[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+            for (int u = 0; u < KPT; u++) a[u & 3] += ex[u];
+            const float need = p.top_p * rarm_block_sum_fixed((a[0] + a[1]) + (a[2] + a[3]), red + 32, tid);
+            uint32_t th = 0;
+            for (int bit = 30; bit >= 0; bit -= 2) {
+                const uint32_t c1 = th | (1u << bit), c2 = th | (2u << bit), c3 = th | (3u << bit);
+                float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, s3[4] = {0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int u = 0; u < KPT; u++) {
+                    s1[u & 3] += key[u] >= c1 ? ex[u] : 0.f; s2[u & 3] += key[u] >= c2 ? ex[u] : 0.f; s3[u & 3] += key[u] >= c3 ? ex[u] : 0.f;
+                }
+                float m1 = (s1[0] + s1[1]) + (s1[2] + s1[3]), m2 = (s2[0] + s2[1]) + (s2[2] + s2[3]), m3 = (s3[0] + s3[1]) + (s3[2] + s3[3]);
+#pragma unroll
+                for (int o = 32; o > 0; o >>= 1) { m1 += __shfl_xor(m1, o); m2 += __shfl_xor(m2, o); m3 += __shfl_xor(m3, o); }
+                float* slot = red + ((bit >> 1) & 1) * 16;                                   // two alternating slots: one barrier per round
+                if ((tid & 63) == 0) { slot[tid >> 6] = m1; slot[4 + (tid >> 6)] = m2; slot[8 + (tid >> 6)] = m3; }
+                __syncthreads();
+                m1 = (slot[0] + slot[1]) + (slot[2] + slot[3]); m2 = (slot[4] + slot[5]) + (slot[6] + slot[7]); m3 = (slot[8] + slot[9]) + (slot[10] + slot[11]);
+                if (m3 >= need) th = c3; else if (m2 >= need) th = c2; else if (m1 >= need) th = c1;
+            }
+            theta = th;
+        }
     } else {
         for (int bit = 31; bit >= 0; bit--) {
             const uint32_t cand = prefix | (1u << bit);
@@ -432,15 +487,48 @@ __global__ __launch_bounds__(256) void rarm_sample_kernel(RarmSampleParams p) {
             const int tot = (int)(hist[(bit & 1) * 4] + hist[(bit & 1) * 4 + 1] + hist[(bit & 1) * 4 + 2] + hist[(bit & 1) * 4 + 3]);
             if (tot >= remaining0) prefix = cand;
         }
+        if constexpr (NUCLEUS) {          // the same search from LDS, one bit a round, the exponentials formed again every round: slow, as the loop above
+            float m = -INFINITY;
+            for (int i = tid; i < V; i += 256) m = fmaxf(m, logit(i));
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+            if ((tid & 63) == 0) red[40 + (tid >> 6)] = m;
+            __syncthreads();
+            m = fmaxf(fmaxf(red[40], red[41]), fmaxf(red[42], red[43]));
+            auto mass = [&](uint32_t cand, float* slot) {        // per thread: four chains over its strided elements, then the fixed reduction
+                float a[4] = {0.f, 0.f, 0.f, 0.f};
+                int j = 0;
+                for (int i = tid; i < V; i += 256, j++) { const float v = logit(i); const uint32_t o = f2ord(v); a[j & 3] += (o >= prefix && o >= cand) ? __expf(v - m) : 0.f; }
+                return rarm_block_sum_fixed((a[0] + a[1]) + (a[2] + a[3]), slot, tid);
+            };
+            const float need = p.top_p * mass(prefix, red + 32);
+            uint32_t th = 0;
+            for (int bit = 31; bit >= 0; bit--) {
+                const uint32_t cand = th | (1u << bit);
+                if (mass(cand, red + (bit & 1) * 16) >= need) th = cand;
+            }
+            theta = th;
+        }
     }
     __syncthreads();
-    const uint32_t kth = prefix;                          // order image of the k-th largest logit: keep o >= kth
+    const uint32_t kth = NUCLEUS ? (theta > prefix ? theta : prefix) : prefix;     // order image of the k-th largest logit (of the nucleus edge, if higher): keep o >= kth
     // ---- max, then per-thread partial sums over a CONTIGUOUS chunk (vocabulary order), block scan, locate the draw
     float mx = -INFINITY;
     for (int i = tid; i < V; i += 256) { const float v = logit(i); if (f2ord(v) >= kth) mx = fmaxf(mx, v); }
     red[tid] = mx; __syncthreads();
     for (int o = 128; o > 0; o >>= 1) { if (tid < o) red[tid] = fmaxf(red[tid], red[tid + o]); __syncthreads(); }
     mx = red[0]; __syncthreads();
+    if constexpr (COUNT) {                                    // the kept-token count of the row (a read-out for callers and tests)
+        if (p.kept_out) {
+            int cnt = 0;
+            for (int i = tid; i < V; i += 256) cnt += f2ord(logit(i)) >= kth ? 1 : 0;
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) cnt += __shfl_xor(cnt, o);
+            if ((tid & 63) == 0) hist[32 + (tid >> 6)] = (uint32_t)cnt;
+            __syncthreads();
+            if (tid == 0) p.kept_out[b] = (int)(hist[32] + hist[33] + hist[34] + hist[35]);
+        }
+    }
     const int chunk = (V + 255) / 256, i0 = tid * chunk, i1 = min(V, i0 + chunk);
     // (round 4) the three scans below add in EXACTLY the order they always did -- the draw is defined by it -- but no longer wait for one
     // LDS read / one exponential per addition: loads and exponentials are issued in batches of 16, the additions then run out of registers
@@ -501,14 +589,18 @@ __global__ __launch_bounds__(256) void rarm_sample_kernel(RarmSampleParams p) {
 hipError_t launch_rarm_sample(const RarmSampleParams& p, hipStream_t st) {
     const size_t sm = ((size_t)p.vocab + (p.vocab >> 6) + 64) * sizeof(float);
     if (sm > 150 * 1024) return hipErrorInvalidValue;          // vocabulary beyond ~37 k entries: not an RARM configuration
-    static bool attr_dev[RDM_MAX_DEVICES] = {false};
-    bool& attr = attr_dev[rdm_cur_device()];
+    if (!(p.top_p > 0.f && p.top_p <= 1.f)) return hipErrorInvalidValue;
+    // top_p == 1 is the kernel without a nucleus (a nucleus of mass 1 would not be the same thing: in fp32 the tail's mass can round away)
+    const int which = p.top_p < 1.f ? 2 : (p.kept_out ? 1 : 0);
+    void (*const kern[3])(RarmSampleParams) = {rarm_sample_kernel<false, false>, rarm_sample_kernel<false, true>, rarm_sample_kernel<true, true>};
+    static bool attr_dev[RDM_MAX_DEVICES][3] = {};
+    bool& attr = attr_dev[rdm_cur_device()][which];
     if (!attr && sm > 32 * 1024) {
-        hipError_t e = hipFuncSetAttribute((const void*)rarm_sample_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+        hipError_t e = hipFuncSetAttribute((const void*)kern[which], hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
         if (e != hipSuccess) return e;
         attr = true;
     }
-    rarm_sample_kernel<<<p.B, 256, sm, st>>>(p);
+    kern[which]<<<p.B, 256, sm, st>>>(p);
     return hipGetLastError();
 }
 

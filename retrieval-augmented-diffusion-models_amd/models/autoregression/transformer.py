@@ -87,22 +87,26 @@ class LatentImageRETRO(object):
     # ---- transformer.py:224-294
     @torch.no_grad()
     def sample(self, x, r, c, steps, temperature=1.0, sample=False, top_k=None, guidance_scale=1.0, callback=lambda k: None,
-               uniforms=None, **kwargs):
+               uniforms=None, top_p=None, **kwargs):
+        """`top_p` (:279-280 names it and asserts it away): the nucleus filter after top-k, in (0, 1]; None and 1.0 are the call
+        without one.  With sample=False (arg-max) it has no effect, as top_k has none."""
+        top_p = _lib.check_top_p("LatentImageRETRO.sample", top_p)
         x = torch.cat((c.to(self.device), x.to(self.device)), 1)           # conditioning tokens, then any given prefix
         for k_ in range(steps):
             callback(k_)                                                    # the loop itself runs inside the library
         if uniforms is None:
             uniforms = torch.rand((steps, x.shape[0]), device=self.device)
         if not sample:
-            top_k = 1                                                       # torch.topk(probs, 1): the arg-max token (:266-267)
-        return self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale)
+            top_k, top_p = 1, None                                          # torch.topk(probs, 1): the arg-max token (:266-267)
+        if top_p is None:
+            return self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale)
+        return self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale, top_p=top_p)
 
     # ---- transformer.py:296-312
     @torch.no_grad()
     def sampling_util(self, steps, z_start, r, c, temperature, top_k, zshape, callback=None, top_p=1., **kwargs):
-        assert top_p == 1., 'not yet implemented'
         index_sample = self.sample(z_start, r, c, steps=steps, temperature=temperature if temperature is not None else 1.0,
-                                   sample=True, top_k=top_k if top_k is not None else 100,
+                                   sample=True, top_k=top_k if top_k is not None else 100, top_p=top_p,
                                    callback=callback if callback is not None else lambda k: None, **kwargs)
         return self.decode_to_img(index_sample, zshape)
 
@@ -110,7 +114,7 @@ class LatentImageRETRO(object):
     @torch.no_grad()
     def sample_from_rdata(self, N, cond=None, return_nns=False, use_weights=False, qids=None, k_nn=None, memsize=100, verbose=False,
                           top_k=256, temperature=1.0, code_side_len=16, z_dimensionality=256, pre_loaded_patches=None,
-                          nn_embeddings=None, query_embeddings=None, **kwargs):
+                          nn_embeddings=None, query_embeddings=None, top_p=None, **kwargs):
         if return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("return_nns / pre_loaded_patches need the raw OpenImages patches (out of scope, SURVEY.md §2 #8)")
         if cond is not None:
@@ -135,7 +139,7 @@ class LatentImageRETRO(object):
         z_shape = (N, z_dimensionality, code_side_len, code_side_len)
         steps = code_side_len ** 2
         z_start = torch.zeros((N, 0), dtype=torch.long)
-        out["samples_with_sampled_nns"] = self.sampling_util(steps, z_start, retro_cond, cond, temperature, top_k, z_shape, **kwargs)
+        out["samples_with_sampled_nns"] = self.sampling_util(steps, z_start, retro_cond, cond, temperature, top_k, z_shape, top_p=top_p, **kwargs)
         return out
 
     # ---- transformer.py:407-430

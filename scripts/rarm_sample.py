@@ -6,7 +6,7 @@ Same flags, defaults and run loop as scripts/rarm_sample.py:100-293: -s/--savepa
 --temperature (1.0), --top_m (0.01), --k_nn (4), -c/--caption, --only_caption, --unconditional, --use_weights; 256 tokens
 (f16 first stage), `seed_everything` before every run, files `{start}-{key}-run{n}-sample{i}.png`.
 Deliberate differences: as scripts/rdm_sample.py (no CPU path, --save_nns unsupported, --seed works).  Additions:
---clip_ckpt, --synthetic.
+--clip_ckpt, --synthetic, --top_p (1.0: nucleus sampling after top-k, the `top_p` the reference's sampling_util names and asserts away).
 """
 import argparse
 import datetime
@@ -35,6 +35,7 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--keep_qids", default=False, action="store_true", help="Keep same queries for each run")
     parser.add_argument("--guidance_scale", type=float, default=1., help="classifier free (transformer) guidance")
     parser.add_argument("--top_k", type=int, default=256, help="top-k sampling")
+    parser.add_argument("--top_p", type=float, default=1.0, help="[native] top-p (nucleus) sampling after top-k, in (0, 1] (default: 1.0, off)")
     parser.add_argument("--temperature", type=float, default=1., help="temperature sampling")
     parser.add_argument("--top_m", type=float, default=0.01, help="top-m sampling")
     parser.add_argument("--k_nn", type=int, default=4, help="number of neighbors drawn for sampling")
@@ -129,7 +130,7 @@ def sample(model, opt):
         print("Sampling query and neighbors (wait for the sampling to start)")
         logs = model.sample_from_rdata(opt.batch_size, qids=qids, query_embeddings=query_embeddings, nn_embeddings=nn_embeddings,
                                        k_nn=opt.k_nn, return_nns=opt.save_nns, use_weights=opt.use_weights, memsize=opt.top_m,
-                                       top_k=opt.top_k, temperature=opt.temperature, guidance_scale=opt.guidance_scale)
+                                       top_k=opt.top_k, temperature=opt.temperature, guidance_scale=opt.guidance_scale, top_p=opt.top_p)
         if opt.keep_qids:
             assert "qids" in logs
             qids = logs["qids"]
