@@ -105,15 +105,41 @@ struct IgemmParams {
     // batching over blockIdx.z (element strides)
     long long sA, sW, sO;
     const void* zero_page;      // 4 KiB of zeros, followed by a 256 x 256 bf16 identity matrix (RDM_EYE_OFFSET)
-    int ksplit; float* ws;      // halo conv split-K (conv_halo.hip): ksplit fp32 partial tiles [ksplit][M][N] in ws, summed by a finisher
+    int ksplit; float* ws;      // conv3x3_halo4_kernel only (never its strip form, never the implicit GEMM: launch_conv3x3): split-K into ksplit fp32
+                                // partial planes [ksplit][M][N] in ws, summed by splitk_finish_kernel (conv_halo.hip); <= 1: none
     int res_k;                  // set by launch_igemm: the bf16 residual enters as BN extra K columns against that identity
     int lda, ldw;               // linear only: row strides of A0 and W in elements when they are views into wider matrices (0 = K); backward.hip
     int l4_any_tiles;           // lin4: take the GEMM whatever its tile count (deterministic mode: the choice must not follow the batch)
     int res_wrap_rows;          // lin4 only: > 0: the bf16 residual holds only that many rows and row m adds row m % res_wrap_rows (whole tiles, at most two copies)
     int a1_wrap_rows;           // lin4 only: > 0: A1 holds only that many rows and row m reads m % a1_wrap_rows (a multiple of the block tile's rows)
-    const bf16_t* Wfrag;        // conv3x3: fragment-ordered copy of W (conv_halo4.hip, built by launch_conv_w_fragpack) or null
+    const bf16_t* Wfrag;        // conv3x3: fragment-ordered copy of W (built by launch_conv_w_fragpack, read by conv_halo4.hip), or null: the conv runs on the
+                                // implicit GEMM whatever its geometry (launch_conv3x3).  Linear: lin4.hip's copy (launch_lin_w_fragpack) or null
     // lin4 only: LayerNorm folded into the GEMM.  A0 holds the RAW rows, Wfrag the gamma-scaled fragment copy, ln_sb[n] = (s[n], b'[n]) per
     // stored weight row (launch_lin_ln_sb); the kernel takes the row statistics itself: out = rstd (A Wg^T - mean s) + b'
     const float* ln_sb; float ln_inv_c, ln_eps;      // ln_inv_c = 1 / (logical row width): zero padding beyond it adds nothing to the sums
     int dbg;                    // always 0: read only by conv3x3_halo4_kernel's phase-clock code, kept for its code generation (conv_halo4.hip)
 };
+
+// host + device: halo geometry of a conv (output H x W) in the one-wave-per-SIMD kernel.  A tile is 256 consecutive output pixels =
+// NS sample parts of RS whole image rows; its halo is NROW = NS (RS + 2) rows of HPW = W + 2 positions.  LDS image (per 64-channel
+// slice): row R at R * RSTR, position hx at + 144 hx (128 bytes of channels + 16 of padding), 16-byte channel chunk c at + 16 c.
+// The layout is ADDITIVE -- a tap (dy, dx) is the constant offset dy RSTR + 144 dx, a k-step 32 bytes -- so the A-fragment
+// addresses of a tap cost one add each, and the 144-byte position stride (9 x 16: odd) together with the row padding
+// (RSTR = 144 HPW + 224 at W <= 16, making consecutive rows differ by 0 resp. 8 sixteen-byte slots mod 16) keeps every
+// ds_read_b128 of a 32-pixel fragment conflict-free at all four resolutions (brute-forced over the instruction's lane groups;
+// the XOR-swizzled 128-byte layout of the 8-wave kernel was 3-way conflicted at 16x16 and 7-way at 8x8).
+struct Halo4Geom { int RS, NS, HPW, NROW, RSTR, NPR, NPT, HBYTES; };
+__host__ __device__ inline Halo4Geom halo4_geom(int H, int W) {
+    Halo4Geom g;
+    const int HW = H * W;
+    g.RS = (HW >= 256) ? 256 / W : H;
+    g.NS = 256 / (g.RS * W);
+    g.HPW = W + 2;
+    g.NROW = g.NS * (g.RS + 2);
+    g.RSTR = g.HPW * 144 + (W <= 16 ? 224 : 0);
+    g.NPR = (g.HPW + 7) >> 3;                     // 8-position pieces per halo row
+    g.NPT = g.NROW * g.NPR;
+    g.HBYTES = (g.NROW * g.RSTR + 255) & ~255;
+    return g;
+}
+constexpr int H4_HALO_MAX = 66560;                 // largest HBYTES admitted (W = 8: 40 rows x 1664 bytes)

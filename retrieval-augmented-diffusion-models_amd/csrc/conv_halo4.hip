@@ -1,5 +1,5 @@
 // Input-stationary 3x3 convolution (stride 1, pad 1, optional fused nearest-2x upsample) for NHWC bf16 on gfx950,
-// ONE WAVE PER SIMD: the round-3 successor of conv_halo.hip's 8-wave ping-pong kernel for the UNet's dominant op
+// ONE WAVE PER SIMD: the round-3 successor of the 8-wave ping-pong kernel of rounds 1-2 (retired) for the UNet's dominant op
 // (conv_nd(2, C, C', 3, padding=1) inside ResBlock in_layers / out_layers and Upsample, ldm, reached from
 // rdm/modules/diffusionmodules/openaimodel.py:144-305).
 //
@@ -14,13 +14,13 @@
 //     (48 MFMAs, ~1.5 k cycles) ahead into the registers its predecessor has just been consumed from;
 //   * LDS holds only the halo (2 buffers, double-buffered per 64-channel slice), staged THROUGH REGISTERS (global_load ->
 //     ds_write_b128 three k-steps later) instead of LDS-DMA: no parked issue, and the LDS image need not be lane-linear: it is
-//     an ADDITIVE layout (halo4_geom below: 144-byte positions, padded rows) in which a tap is a constant offset and every
+//     an ADDITIVE layout (halo4_geom, common.h: 144-byte positions, padded rows) in which a tap is a constant offset and every
 //     A-fragment ds_read_b128 is conflict-free at all four resolutions -- no per-tap swizzle arithmetic at all;
 //   * the instruction stream is hand-placed: MFMAs, fragment loads and waits are asm volatile statements in program order
 //     (hipcc keeps their order and only allocates registers), 4 ds_read_b128 + <= 4 global loads + <= 1 ds_write per 12 MFMAs,
 //     every wait counted (vmcnt retires in order); one s_barrier per 64-channel slice (9 taps, 432 MFMAs per wave).
-// Same persistent XCD-aware tile walk, split-K planes and epilogue scheme (DPP pair swap -> wave-private LDS transpose -> 16-byte
-// row stores) as conv_halo.hip.
+// Same persistent XCD-aware tile walk and epilogue scheme (DPP pair swap -> wave-private LDS transpose -> 16-byte row stores) as
+// igemm.hip; a K-split part leaves its fp32 plane for splitk_finish_kernel (conv_halo.hip, with the host rules of which conv runs here).
 
 #include <type_traits>
 
@@ -51,30 +51,6 @@ hipError_t launch_conv_w_fragpack(const bf16_t* W, bf16_t* dst, int N, int Cin, 
 }
 
 #include "h4_asm.h"
-
-// host + device: halo geometry of a conv (output H x W) in the one-wave-per-SIMD kernel.  A tile is 256 consecutive output pixels =
-// NS sample parts of RS whole image rows; its halo is NROW = NS (RS + 2) rows of HPW = W + 2 positions.  LDS image (per 64-channel
-// slice): row R at R * RSTR, position hx at + 144 hx (128 bytes of channels + 16 of padding), 16-byte channel chunk c at + 16 c.
-// The layout is ADDITIVE -- a tap (dy, dx) is the constant offset dy RSTR + 144 dx, a k-step 32 bytes -- so the A-fragment
-// addresses of a tap cost one add each, and the 144-byte position stride (9 x 16: odd) together with the row padding
-// (RSTR = 144 HPW + 224 at W <= 16, making consecutive rows differ by 0 resp. 8 sixteen-byte slots mod 16) keeps every
-// ds_read_b128 of a 32-pixel fragment conflict-free at all four resolutions (brute-forced over the instruction's lane groups;
-// the XOR-swizzled 128-byte layout of the 8-wave kernel was 3-way conflicted at 16x16 and 7-way at 8x8).
-struct Halo4Geom { int RS, NS, HPW, NROW, RSTR, NPR, NPT, HBYTES; };
-__host__ __device__ inline Halo4Geom halo4_geom(int H, int W) {
-    Halo4Geom g;
-    const int HW = H * W;
-    g.RS = (HW >= 256) ? 256 / W : H;
-    g.NS = 256 / (g.RS * W);
-    g.HPW = W + 2;
-    g.NROW = g.NS * (g.RS + 2);
-    g.RSTR = g.HPW * 144 + (W <= 16 ? 224 : 0);
-    g.NPR = (g.HPW + 7) >> 3;                     // 8-position pieces per halo row
-    g.NPT = g.NROW * g.NPR;
-    g.HBYTES = (g.NROW * g.RSTR + 255) & ~255;
-    return g;
-}
-constexpr int H4_HALO_MAX = 66560;                 // largest HBYTES admitted (W = 8: 40 rows x 1664 bytes)
 
 // STRIP (round 4): images wider than 64 pixels (the first-stage decoder's 128- and 256-pixel levels).  A tile is still 256 output pixels
 // with the W = 64 halo geometry -- 4 rows of a 64-COLUMN STRIP -- but the strip's left / right halo columns are the neighbouring
@@ -623,39 +599,9 @@ static hipError_t launch_halo4_cfg(const IgemmParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
-// images wider than 64 pixels as 64-column strips (conv3x3_halo4_kernel<.., STRIP>): the first-stage decoder's 128- / 256-pixel levels
-bool conv_halo4_strip_supported(const IgemmParams& p) {
-    const int W = p.Wout, H = p.Hout;
-    if (p.stride != 1 || W <= 64 || W % 64 || H % 4 || W > 4096 || H > 4096) return false;
-    if (p.ups ? (p.Hout != 2 * p.Hin || p.Wout != 2 * p.Win) : (p.Hout != p.Hin || p.Wout != p.Win)) return false;
-    if (p.M % 256 != 0 || p.N % 128 != 0 || p.ksplit > 1) return false;
-    if (p.C0 % 64 || p.C1 % 64 || p.alpha != 1.0f || p.act != ACT_NONE || !p.out_bf16 || p.out_f32 || p.res_f32) return false;
-    if (p.ldo % 8 || p.K != 9 * (p.C0 + p.C1)) return false;
-    if (p.rowvec && p.rows_per_sample % 32 != 0) return false;
-    if ((long long)p.M * (p.C0 > p.C1 ? p.C0 : p.C1) >= 0x7fffffffLL || (long long)p.M * p.ldo >= 0x7fffffffLL) return false;
-    return true;
-}
-
-// the one-wave-per-SIMD kernel takes every conv the halo geometry admits once a fragment-ordered weight copy exists
-bool conv_halo4_supported(const IgemmParams& p) {
-    if (!p.Wfrag) return false;
-    if (!conv_halo_supported(p)) return false;
-    if (p.rowvec && p.rows_per_sample % 32 != 0) return false;
-    if ((p.C0 + p.C1) % 64 != 0 || p.N % 32 != 0) return false;
-    const Halo4Geom g = halo4_geom(p.Hout, p.Wout);
-    if (g.HBYTES > H4_HALO_MAX || g.NPT > 4 * 21) return false;          // three pieces per wave per tap-step, staged during taps 0..6
-    // the kernel's multiply-shift divisions by NPR and RS + 2 must be exact over the ranges met
-    const int mNPR = 65536 / g.NPR + 1, mRS2 = 65536 / (g.RS + 2) + 1;
-    for (int x = 0; x < 4 * 36 + 4; x++) if (((x * mNPR) >> 16) != x / g.NPR) return false;
-    for (int x = 0; x <= g.NROW + 36; x++) if (((x * mRS2) >> 16) != x / (g.RS + 2)) return false;
-    return true;
-}
-
-hipError_t launch_conv_halo4(const IgemmParams& p, hipStream_t st) {
-    if (p.Wout > 64) {
-        if (!p.Wfrag || !conv_halo4_strip_supported(p)) return hipErrorInvalidValue;
-        return launch_halo4_cfg<2, true>(p, st);
-    }
+// which conv runs here, and in which form, is conv3x3_kernel's answer (conv_halo.hip): launch_conv3x3 is the only caller
+hipError_t launch_conv_halo4(const IgemmParams& p, bool strip, hipStream_t st) {
+    if (strip) return launch_halo4_cfg<2, true>(p, st);
     if (p.N % 192 == 0) return launch_halo4_cfg<3>(p, st);
     return launch_halo4_cfg<2>(p, st);
 }

@@ -145,25 +145,20 @@ hipError_t launch_sgemm(const SgemmParams& p, hipStream_t st);
 bool mgemm_supported(const SgemmParams& p);
 hipError_t launch_mgemm(const SgemmParams& p, hipStream_t st);
 hipError_t launch_igemm(const IgemmParams& p, bool conv, int batch, hipStream_t st);
-bool conv_halo_supported(const IgemmParams& p);
-int conv_halo_ksplit(const IgemmParams& p);                // K-split factor worth using for this conv (1 = none); needs p.ws of ksplit*M*N floats
-hipError_t launch_conv_halo(const IgemmParams& p, hipStream_t st);
-// one-wave-per-SIMD halo kernel (conv_halo4.hip): needs p.Wfrag, the fragment-ordered weight copy
-bool conv_halo4_supported(const IgemmParams& p);
-bool conv_halo4_strip_supported(const IgemmParams& p);     // output wider than 64 pixels: 64-column strips (N % 128 == 0, no K-split); needs p.Wfrag
-hipError_t launch_conv_halo4(const IgemmParams& p, hipStream_t st);
+// 3x3 conv (conv_halo.hip): the one statement of which kernel takes a conv -- geometry and epilogue only, not whether p.Wfrag exists
+enum ConvKernel { CONV_IGEMM, CONV_HALO4, CONV_HALO4_STRIP };     // igemm.hip | conv_halo4.hip | its 64-column strip form (output wider than 64 pixels)
+ConvKernel conv3x3_kernel(const IgemmParams& p);
+int conv_halo_ksplit(const IgemmParams& p);                // K-split factor worth using for this conv (1 = none, and always unless CONV_HALO4); needs p.ws of ksplit*M*N floats
+// launches conv3x3_kernel's choice when p.Wfrag (the fragment-ordered weight copy) is given, plus the K-split finisher when p.ksplit > 1; without p.Wfrag the implicit GEMM
+hipError_t launch_conv3x3(const IgemmParams& p, hipStream_t st);
+hipError_t launch_conv_halo4(const IgemmParams& p, bool strip, hipStream_t st);      // conv_halo4.hip; launch_conv3x3 is its caller
 // one-wave-per-SIMD linear GEMM (lin4.hip): needs p.Wfrag = the fragment-ordered copy of W built by launch_lin_w_fragpack
 bool lin4_supported(const IgemmParams& p, int batch);
 hipError_t launch_lin4(const IgemmParams& p, hipStream_t st);
 hipError_t launch_lin_w_fragpack(const bf16_t* W, bf16_t* dst, int N, int K, int ldw, int geglu, hipStream_t st, const float* gamma = nullptr);       // dst: N*K elements; geglu: W rows in packing.py's _geglu_perm order; gamma: dst = bf16(gamma[k] W[n][k]) (LayerNorm fold)
 hipError_t launch_lin_ln_sb(const bf16_t* W, const float* gamma, const float* beta, const float* bias, float* sb, int N, int K, hipStream_t st);   // sb[n] = (sum_k bf16(gamma W), bias + sum_k beta W), n = stored row
 hipError_t launch_conv_w_fragpack(const bf16_t* W, bf16_t* dst, int N, int Cin, hipStream_t st);   // dst: N*9*Cin elements
-// 3x3 conv dispatcher: input-stationary halo kernels when the geometry allows, else the generic implicit GEMM
 hipError_t launch_conv_phase_weights(const bf16_t* W, bf16_t* Wp, int N, int C, hipStream_t st);     // igemm.hip: [N][3][3][C] -> [4 phases][N][2][2][C]
-inline hipError_t launch_conv3x3(const IgemmParams& p, hipStream_t st) {
-    if (p.Wfrag && p.Wout > 64 && conv_halo4_strip_supported(p)) return launch_conv_halo4(p, st);
-    return conv_halo_supported(p) ? launch_conv_halo(p, st) : launch_igemm(p, true, 1, st);
-}
 // ---- backward pieces (backward.hip)
 hipError_t launch_conv_w_dgrad(const bf16_t* w, bf16_t* wd, int N, int C, hipStream_t st);             // [N][9][C] -> flipped [C][9][N]
 size_t conv_wgrad_scratch_bytes(int B, int H, int W, int C, int N, int* WP, int* PR, int* Kc, int* Z, int* margin);

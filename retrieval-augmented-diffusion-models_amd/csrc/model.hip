@@ -714,11 +714,12 @@ struct Ops {
             }
         }
         const bool det_generic = c->deterministic && ((Hout * Wout) % 256 != 0);
-        const int ks = c->deterministic ? 1 : conv_halo_ksplit(p);
+        if (!det_generic && conv3x3_kernel(p) != CONV_IGEMM) p.Wfrag = derived(W, N, C0 + C1, 0);
+        // the K-split is chosen only with the fragment copy in hand: without one the conv runs on the implicit GEMM, which knows nothing of ksplit / ws
+        const int ks = (p.Wfrag && !c->deterministic) ? conv_halo_ksplit(p) : 1;
         if (ks > 1 && ensure_bytes(c, &c->splitk_ws, &c->splitk_ws_bytes, (size_t)ks * p.M * N * 4) == 0) { p.ksplit = ks; p.ws = (float*)c->splitk_ws; }
-        if (!det_generic && (conv_halo_supported(p) || conv_halo4_strip_supported(p))) p.Wfrag = derived(W, N, C0 + C1, 0);
         prof_begin(RDM_PROF_CONV3X3, 2.0 * p.M * N * (double)p.K, p.M, N, p.K);
-        check(det_generic ? launch_igemm(p, true, 1, c->stream) : launch_conv3x3(p, c->stream), "conv3x3");
+        check(launch_conv3x3(p, c->stream), "conv3x3");      // no p.Wfrag (det_generic, no halo geometry, no memory for the copy): the implicit GEMM
         prof_end();
     }
     // (Round 6, wave quantisation: a conv of q full rounds of the CUs plus a partial round -- the 16 x 16 level of a guided batch of 64 is 384

@@ -9,7 +9,7 @@ Bound conventions (u = 2^-24): r = 2^-8 for a bf16 output, 0 for an fp32 output;
 of the terms of the element and c the chain of the launch geometry, stated per op.  The bf16 MFMAs are taken as one fp32 rounding per
 product, accumulated in k order (c = K for a K-long dot product; a K-split part and its finisher add at most 3 more).  Every rounding
 a kernel adds by design has its own term:
-  * bias / time-embedding start values carried as bf16 (hi, lo) pairs (lin4, halo, halo4): 2^-16 |b|;
+  * bias / time-embedding start values carried as bf16 (hi, lo) pairs (lin4, halo4): 2^-16 |b|;
   * the phase-upsample conv's pre-summed 2 x 2 weights stored as bf16: 2^-9 sum |x| |w| over the original taps;
   * the LayerNorm-folded weights bf16(gamma o W): 2^-9 rstd sum |x - mu| |gamma w|;
   * the attention probabilities rounded to bf16 before the PV MFMA (flash, fused cross-attention): 2^-8 P;
@@ -85,32 +85,23 @@ def linear_path(M, N, K, act=ACT_NONE, alpha=1.0, f32=False, res=False, rows=Non
     return f"igemm<{256 if tall else 128}, {192 if wide else 128}{', res_k' if resk else ''}>"
 
 
-def halo4_geom(H, W):
+def conv3x3_kernel(B, H, W, C, N, stride, rowvec):
+    """conv3x3_kernel (conv_halo.hip) for a conv whose OUTPUT is H x W: the halo4 form that takes it, or None: the implicit GEMM"""
     HW = H * W
-    RS = 256 // W if HW >= 256 else H
-    NS = 256 // (RS * W)
-    HPW = W + 2
-    NROW = NS * (RS + 2)
-    RSTR = HPW * 144 + (224 if W <= 16 else 0)
-    NPR = (HPW + 7) >> 3
-    return dict(RS=RS, NS=NS, NPT=NROW * NPR, HBYTES=(NROW * RSTR + 255) & ~255)
-
-
-def conv_halo_supported(B, H, W, C, N, stride, rowvec):
-    if stride != 1 or W < 4 or W > 64 or 256 % W:
-        return False
-    HW = H * W
-    if HW >= 256:
-        if HW % 256 or H % (256 // W):
-            return False
-    elif 256 % HW:
-        return False
-    if (B * HW) % 256 or (N % 192 and N % 128) or C % 64:
-        return False
-    if rowvec and HW % 32:
-        return False
-    RS = 256 // W if HW >= 256 else H
-    return (256 // (RS * W)) * (RS + 2) * (W + 2) <= 400
+    if stride != 1 or (B * HW) % 256 or C % 64 or (rowvec and HW % 32):
+        return None
+    if W > 64:
+        return "halo4<2, STRIP>" if W % 64 == 0 and H % 4 == 0 and max(H, W) <= 4096 and N % 128 == 0 else None
+    if W < 4 or 256 % W or (N % 192 and N % 128):
+        return None
+    if (HW % 256 or H % (256 // W)) if HW >= 256 else 256 % HW:
+        return None
+    RS = 256 // W if HW >= 256 else H                  # halo4_geom (common.h)
+    HPW, NROW = W + 2, 256 // (RS * W) * (RS + 2)
+    HBYTES = (NROW * (HPW * 144 + (224 if W <= 16 else 0)) + 255) & ~255
+    if HBYTES > 66560 or NROW * ((HPW + 7) >> 3) > 84 or NROW * HPW > 400:
+        return None
+    return f"halo4<{3 if N % 192 == 0 else 2}>"
 
 
 def conv_ksplit(B, H, W, C, N):
@@ -129,19 +120,14 @@ def conv_ksplit(B, H, W, C, N):
 
 
 def conv_path(B, H, W, C, N, stride=1, ups=0, dual=False, rowvec=False, res=False):
-    """(kernel, K-split planes) rdm_op_conv3x3 launches (model.hip, conv_halo.hip, conv_halo4.hip, igemm.hip); H, W: the input"""
+    """(kernel, K-split planes) rdm_op_conv3x3 launches (model.hip Ops::conv3, conv_halo.hip launch_conv3x3); H, W: the input"""
     Ho, Wo = (2 * H, 2 * W) if ups else ((H // 2, W // 2) if stride == 2 else (H, W))
     if ups and not dual and C % 64 == 0 and N % 8 == 0 and not rowvec and not res and stride == 1:
         return "igemm phase2", 1
-    if conv_halo_supported(B, Ho, Wo, C, N, stride, rowvec):
-        S = conv_ksplit(B, Ho, Wo, C, N)
-        g = halo4_geom(Ho, Wo)
-        if g["HBYTES"] <= 66560 and g["NPT"] <= 84:
-            return f"halo4<{3 if N % 192 == 0 else 2}>", S
-        return f"halo<{192 if N % 192 == 0 else 128}>", S
-    if stride == 1 and Wo > 64 and Wo % 64 == 0 and Ho % 4 == 0 and (B * Ho * Wo) % 256 == 0 and N % 128 == 0 and C % 64 == 0:
-        return "halo4<2, STRIP>", 1
-    return ("igemm ups" if ups else "igemm conv"), 1
+    kernel = conv3x3_kernel(B, Ho, Wo, C, N, stride, rowvec)
+    if kernel is None:
+        return ("igemm ups" if ups else "igemm conv"), 1
+    return kernel, (1 if "STRIP" in kernel else conv_ksplit(B, Ho, Wo, C, N))
 
 
 def gn_onepass_plan(HW, C):
@@ -939,6 +925,7 @@ CASES = [
     # conv3x3
     _conv(B=1, H=64, W=4, C0=128, N=128, res=True),
     _conv(B=2, H=64, W=4, C0=64, N=192, rowvec=True),
+    _conv(B=1, H=64, W=4, C0=256, N=128, res=True),      # few tiles and four slices, but no halo4 geometry: no K-split may be chosen for it
     _conv(B=4, H=8, W=8, C0=128, N=192),
     _conv(B=4, H=8, W=8, C0=64, C1=64, N=128, rowvec=True, ld_pad=7, res=True),
     _conv(B=1, H=16, W=16, C0=128, N=192, rowvec=True, res=True),

@@ -29,7 +29,7 @@ def test_every_forward_op_is_parametrised():
 
 def test_case_ids_name_every_launch_path():
     paths = " | ".join(e[2] for e in R.CASES)
-    for kernel in ("halo<128>", "halo<192>", "halo4<2>", "halo4<3>", "halo4<2, STRIP>", "K-split 2", "K-split 3", "igemm phase2", "igemm conv",
+    for kernel in ("halo4<2>", "halo4<3>", "halo4<2, STRIP>", "K-split 2", "K-split 3", "igemm phase2", "igemm conv",
                    "igemm ups", "igemm<128, 128", "igemm<256, 192", "igemm<128, 192", "igemm<256, 128", "res_k", "igemm<256, 256, GEGLU>",
                    "igemm<128, 128, GEGLU>", "igemm<256, 128, GEGLU>", "lin4<plain, WM1>", "lin4<plain, WM2>", "lin4<GEGLU, WM1>",
                    "lin4<GEGLU, WM2>", "rowvec", "sgemm", "mgemm", "LN>", "gn_onepass<NV", ", 512>", ", 1024>", "gn_stats + gn_apply",
