@@ -179,6 +179,16 @@ int rdm_vq_decode_indices(rdm_ctx* ctx, const int64_t* indices, int b, float* im
 long long rdm_vqenc_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes);
 int rdm_load_vqenc(rdm_ctx* ctx, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes);
 int rdm_vq_encode(rdm_ctx* ctx, const float* img, int b, float* z_out);
+/* Wide latents (taming VQGAN-f16: embed_dim % 64 == 0 && z_channels % 64 == 0, the condition under which rdm_load_vq takes a wide
+ * decoder) are accepted by the three entries above as well; rdm_vq_encode then returns z_out [b,embed_dim,h,w] = quant_conv(encoder(x)).
+ *
+ * rdm_vq_encode_indices: taming VQModel.encode as reached from Net2NetTransformer.encode_to_z (un-vendored, parity unpinned):
+ *   quant_z, _, info = first_stage_model.encode(x); indices = info[2].view(b, -1)
+ * i.e. the nearest codebook row (first minimum on ties) of every latent token; the image-completion path of LatentImageRETRO.log_images
+ * (rdm/models/autoregression/transformer.py:448, :457-462).  Needs rdm_load_vqenc AND rdm_load_vq (the codebook is the decoder blob's
+ * quantize.embedding.weight) with the same wide cfg.  Batches beyond the first stage's activation range are walked in ranges. */
+int rdm_vq_encode_indices(rdm_ctx* ctx, const float* img /*[dev] f32 [b,out_ch,R,R]*/, int b, int64_t* indices_out /*[dev] [b, h*w]*/,
+                          float* quant_out_or_null /*[dev] f32 [b,embed_dim,h,w] = codebook rows*/);
 /* scripts/rdm_sample.py:203-214 custom_to_np/custom_to_pil: f32 NCHW [-1,1] -> uint8 NHWC (truncating). */
 int rdm_to_uint8(rdm_ctx* ctx, const float* img, int b, int c, int h, int w, uint8_t* out);
 
@@ -299,6 +309,11 @@ int rdm_op_linear_ln(rdm_ctx* ctx, const void* x_bf16, const void* w_bf16, const
 int rdm_op_conv3x3(rdm_ctx* ctx, const void* x0_bf16, const void* x1_bf16, int C0, int C1, const void* w_bf16,
                    const float* bias, const float* rowvec, int rowvec_ld, const void* residual_bf16, void* out_bf16,
                    int B, int Hin, int Win, int N, int stride, int ups);
+/* the nearest-code kernel of rdm_vq_encode_indices alone, on caller-given operands: idx_out[m] = argmin_j |e_j|^2 - 2 z_m . e_j, evaluated
+ * in fp32 on fp32-input MFMAs, first minimum on ties (taming VectorQuantizer2: torch.argmin); bitwise independent of M.  Any M, N >= 1;
+ * E % 64 == 0 and E <= 512, otherwise an argument error and no launch.  Every index lies in [0, N), also for non-finite z. */
+int rdm_op_vq_nearest_code(rdm_ctx* ctx, const float* z /*[dev] [M,E]*/, const float* codebook /*[dev] [N,E]*/, long long M, int N, int E,
+                           int32_t* idx_out /*[dev] [M]*/);
 /* the RARM sampler kernel alone (taming top_k_logits + softmax + multinomial as an inverse CDF in vocabulary order, after the
  * classifier-free combine lu + scale (lc - lu) and the temperature; transformer.py:237-263): logits [dev] f32 [(cfg ? 2 : 1) * b, vocab]
  * (conditional rows first), uniforms [dev] f32 [b], tokens_out [dev] int64 [b].  top_k <= 0: no filter. */

@@ -118,6 +118,7 @@ SIGNATURES = {
     "rdm_vqenc_manifest": (C.c_longlong, [_P, _P, C.c_size_t, _P]),
     "rdm_load_vqenc": (C.c_int, [_P, _P, _P, C.c_size_t]),
     "rdm_vq_encode": (C.c_int, [_P, _P, C.c_int, _P]),
+    "rdm_vq_encode_indices": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "rdm_op_q_sample": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_mse_loss": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_where_rows": (C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_longlong]),
@@ -127,6 +128,7 @@ SIGNATURES = {
     "rdm_op_linear": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "rdm_op_conv3x3": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int]),
+    "rdm_op_vq_nearest_code": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int, _P]),
     "rdm_op_rarm_sampler": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "rdm_op_rarm_sampler_top_p": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P]),
     "rdm_op_conv3x3_dgrad": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -364,6 +366,35 @@ class Context:
         z = torch.empty((img.shape[0], cfg.embed_dim, zr, zr), device=self.device, dtype=torch.float32)
         self._check(lib.rdm_vq_encode(self._h, _ptr(img), img.shape[0], _ptr(z)))
         return z
+
+    def vq_encode_indices(self, img, return_quant=False):
+        """taming VQModel.encode as Net2NetTransformer.encode_to_z reaches it: image f32 [b,out_ch,R,R] in [-1,1] -> code indices
+        int64 [b, h*w] (nearest codebook row of quant_conv(encoder(x)), first minimum on ties); return_quant: -> (quant f32
+        [b,embed_dim,h,w] = the chosen codebook rows, indices).  Needs the encoder AND the decoder (it holds the codebook) of a
+        first stage with a wide latent (VQGAN-f16)."""
+        img = self._dev(img, torch.float32)
+        cfg = self._need("vq_encode_indices", "vqenc")
+        self._need("vq_encode_indices", "vq")
+        if img.ndim != 4 or tuple(img.shape[1:]) != (cfg.out_ch, cfg.resolution, cfg.resolution):
+            raise RdmError(f"vq_encode_indices: image must be [b,{cfg.out_ch},{cfg.resolution},{cfg.resolution}], got {tuple(img.shape)}")
+        b = img.shape[0]
+        if b < 1:
+            raise RdmError("vq_encode_indices: empty batch")
+        zr = cfg.resolution >> (cfg.n_ch_mult - 1)
+        idx = torch.empty((b, zr * zr), device=self.device, dtype=torch.int64)
+        quant = torch.empty((b, cfg.embed_dim, zr, zr), device=self.device, dtype=torch.float32) if return_quant else None
+        self._check(lib.rdm_vq_encode_indices(self._h, _ptr(img), b, _ptr(idx), _ptr(quant)))
+        return (quant, idx) if return_quant else idx
+
+    def vq_nearest_code(self, z, codebook):
+        """The nearest-code kernel alone: z f32 [M, E], codebook f32 [N, E] -> int32 [M] = argmin_j |e_j|^2 - 2 z . e_j in fp32, first
+        minimum on ties.  E: multiples of 64 up to 512 (the library rejects others)."""
+        z = self._dev(z, torch.float32); codebook = self._dev(codebook, torch.float32)
+        if z.ndim != 2 or codebook.ndim != 2 or z.shape[1] != codebook.shape[1] or z.shape[0] < 1 or codebook.shape[0] < 1:
+            raise RdmError(f"vq_nearest_code: z must be [M,E] and codebook [N,E], got {tuple(z.shape)} and {tuple(codebook.shape)}")
+        out = torch.empty((z.shape[0],), device=self.device, dtype=torch.int32)
+        self._check(lib.rdm_op_vq_nearest_code(self._h, _ptr(z), _ptr(codebook), z.shape[0], codebook.shape[0], z.shape[1], _ptr(out)))
+        return out
 
     def load_clip(self, cfg: ClipCfg, blob: np.ndarray):
         self._check(lib.rdm_load_clip(self._h, C.byref(cfg), blob.ctypes.data_as(_P), blob.nbytes)); self.clip_cfg = cfg

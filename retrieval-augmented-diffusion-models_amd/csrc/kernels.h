@@ -230,6 +230,13 @@ hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
 hipError_t launch_vq_quantize(const float* z, const float* codebook, int n_embed, const float* pq_w, const float* pq_b,
                               float* out, int* idx_out, int B, int HW, int quantize, hipStream_t st);
+// nearest-code search of a wide-latent VQ first stage (vqcode.hip): idx[m] = argmin_j |e_j|^2 - 2 z_m . e_j on fp32-input MFMAs, first minimum on ties
+bool vq_nearest_supported(int E);                         // E % 64 == 0, E <= 512
+size_t vq_nearest_ws_bytes(long long M, int N);           // per-split (score, index) planes
+hipError_t launch_vq_code_norms(const float* codebook, float* norms, int N, int E, hipStream_t st);
+hipError_t launch_vq_nearest(const float* z, const float* codebook, const float* norms, long long M, int N, int E, char* ws, int* idx32,
+                             long long* idx64, hipStream_t st);       // idx32 / idx64: either may be null
+hipError_t launch_vq_rows_to_nchw(const float* src, const int* idx, float* out, int B, int HW, int E, hipStream_t st);      // out [B,E,HW] = rows idx[token] (null: token) of src [.,E]; E % 32 == 0
 hipError_t launch_softmax_rows(const float* s, bf16_t* p, long long rows, int n, hipStream_t st, int n_valid = 0);   // columns >= n_valid: probability 0
 hipError_t launch_clip_embed(const long long* tokens, const float* tok_emb, const float* pos_emb, float* out, int B, int L,
                              int Wd, hipStream_t st);

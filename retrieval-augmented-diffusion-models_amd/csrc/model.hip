@@ -331,13 +331,16 @@ static void build_vq(VqModel& v, const rdm_vq_cfg& c, Manifest& mf) {
     v.coutw = f32("decoder.conv_out.weight", (size_t)c.out_ch * bin * 9); v.coutb = f32("decoder.conv_out.bias", c.out_ch);
 }
 
-// ------------------------------------------------------------------------------------ VQ-f4 first-stage ENCODER description (training input)
+// ------------------------------------------------------------------------------------ first-stage ENCODER description (VQ-f4: training input; VQGAN-f16: image -> codes)
 // ldm Encoder (ldm/modules/diffusionmodules/model.py; un-vendored: restated from the published code, parity unpinned) as reached from
 // MinimalRETRODiffusion.get_input -> encode_first_stage -> VQModelInterface.encode = quant_conv(encoder(x)) under torch.no_grad()
 // (rdm/models/diffusion/ddpm.py:390-391): conv_in, per level num_res_blocks ResnetBlocks (+ AttnBlocks at attn_resolutions) and a
 // stride-2 Downsample conv with (0, 1, 0, 1) zero padding, mid res-attn-res, GroupNorm + swish + conv_out, quant_conv (1x1).
+// The taming VQGAN-f16 encoder (wide latent; un-vendored, parity unpinned) is the same graph: only the tail's weights are stored otherwise
+// (conv_out as conv3 bf16, quant_conv as a bf16 GEMM operand: vqenc_body).
 struct VqEncModel {
     rdm_vq_cfg cfg{}; bool loaded = false;
+    bool wide = false;                             // z_channels > 4 (taming VQGAN-f16): conv_out is an ordinary 3x3 conv, quant_conv a GEMM with an fp32 token-major output
     size_t cinw, cinb, noutg, noutb, coutw, coutb, qw, qb;
     std::vector<std::vector<VqRes>> down; std::vector<std::vector<VqAttn>> down_attn; std::vector<ConvW> downsample;   // indexed by level
     VqRes mid1, mid2; VqAttn attn;
@@ -388,8 +391,14 @@ static void build_vqenc(VqEncModel& v, const rdm_vq_cfg& c, Manifest& mf) {
     if (c.mid_attn) v.attn = add_attn("encoder.mid.attn_1", bin);
     v.mid2 = add_res("encoder.mid.block_2", bin, bin);
     v.noutg = f32("encoder.norm_out.weight", bin); v.noutb = f32("encoder.norm_out.bias", bin);
-    v.coutw = f32("encoder.conv_out.weight", (size_t)c.z_channels * bin * 9); v.coutb = f32("encoder.conv_out.bias", c.z_channels);
-    v.qw = f32("quant_conv.weight", (size_t)c.embed_dim * c.z_channels); v.qb = f32("quant_conv.bias", c.embed_dim);
+    v.wide = c.z_channels > 4;
+    if (v.wide) {
+        v.coutw = mf.add("conv3", "encoder.conv_out.weight", (size_t)c.z_channels * bin * 9 * 2); v.coutb = f32("encoder.conv_out.bias", c.z_channels);
+        v.qw = bf("quant_conv.weight", (size_t)c.embed_dim * c.z_channels); v.qb = f32("quant_conv.bias", c.embed_dim);
+    } else {
+        v.coutw = f32("encoder.conv_out.weight", (size_t)c.z_channels * bin * 9); v.coutb = f32("encoder.conv_out.bias", c.z_channels);
+        v.qw = f32("quant_conv.weight", (size_t)c.embed_dim * c.z_channels); v.qb = f32("quant_conv.bias", c.embed_dim);
+    }
 }
 
 // ------------------------------------------------------------------------------------ CLIP description
@@ -485,6 +494,7 @@ struct rdm_ctx {
     float* gn_partial = nullptr; size_t gn_partial_bytes = 0;
     char* splitk_ws = nullptr; size_t splitk_ws_bytes = 0;   // fp32 partial planes of the K-split halo convs
     char* samp = nullptr; size_t samp_bytes = 0;     // sampler scratch
+    float* code_norms = nullptr;                     // |e_j|^2 of the loaded first stage's codebook (vqcode.hip), made on first use, dropped by rdm_load_vq
     // derived weight layouts, built on first use per weight and dropped when a model is reloaded: fragment-ordered copies of the 3x3 conv
     // weights (conv_halo4.hip) and of the Linear / 1x1 weights (lin4.hip; optionally scaled by a LayerNorm's gamma, with the (s, b') table
     // of the folded LayerNorm beside it).  Keyed on everything the copy depends on -- the entry is the copy of exactly that
@@ -782,6 +792,12 @@ struct Ops {
         }
         groupnorm(x, nullptr, C, 0, B, H * W, g, b, eps, 1, tmp, Clog, 0);
         check(launch_conv_out(tmp, wt, bias, out, B, H, W, C, Cout, c->stream), "conv_out");
+    }
+    // nearest codebook row of every token (vqcode.hip): z f32 [M, E], cb f32 [N, E], norms = |e_j|^2 (launch_vq_code_norms), ws of
+    // vq_nearest_ws_bytes(M, N); first minimum on ties, indices as int32 and / or int64
+    void vq_nearest(const float* z, const float* cb, const float* norms, long long M, int N, int E, char* ws, int* idx32, long long* idx64) {
+        if (plan) return;
+        check(launch_vq_nearest(z, cb, norms, M, N, E, ws, idx32, idx64, c->stream), "vq nearest code");
     }
     void layernorm(const void* x, int in_f32, const float* g, const float* b, void* out, int out_f32, int M, int C, int Clog = -1, float eps = 1e-5f) {
         if (plan) return;
@@ -1309,8 +1325,10 @@ static void vq_wide_body(Ops& o, VqModel& v, const long long* indices, int B, fl
     vq_trunk(o, v, h, B, zr, zr, img);
 }
 
-// VQ-f4 encode: image f32 [B, out_ch, R, R] -> z f32 [B, embed_dim, R / 2^(levels-1), ...]  (VQModelInterface.encode: no quantisation here)
-static void vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* z) {
+// first-stage encode: image f32 [B, out_ch, R, R] -> z f32 [B, embed_dim, R / 2^(levels-1), ...]  (VQModelInterface.encode: no quantisation here).
+// Wide latents (taming VQGAN-f16; un-vendored, parity unpinned): norm_out + swish as a GroupNorm pass, conv_out as a 3x3 conv, quant_conv as
+// a GEMM whose fp32 output stays token-major [B h w, embed_dim] (returned; what the nearest-code search reads); z (NCHW) may then be null.
+static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* z) {
     const rdm_vq_cfg& c = v.cfg;
     int H = c.resolution, W = c.resolution;
     bf16_t* h = o.abf((size_t)B * H * W * c.ch);
@@ -1332,10 +1350,21 @@ static void vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* z)
     if (c.mid_attn) h = vq_attn(o, v.attn, h, B, H, W);
     h = vq_res(o, v.mid2, h, B, H, W);
     bf16_t* no = o.abf((size_t)B * H * W * bin);
+    if (v.wide) {
+        const int M = B * H * W;
+        o.groupnorm(h, nullptr, bin, 0, B, H * W, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, 1, no);
+        bf16_t* ze = o.abf((size_t)M * c.z_channels);
+        o.conv3(no, nullptr, bin, 0, o.w<bf16_t>(v.coutw), o.w<float>(v.coutb), B, H, W, c.z_channels, 1, 0, nullptr, 0, nullptr, ze);
+        float* zt = o.af32((size_t)M * c.embed_dim);
+        o.linear(ze, nullptr, c.z_channels, 0, o.w<bf16_t>(v.qw), o.w<float>(v.qb), M, c.embed_dim, ACT_NONE, nullptr, nullptr, zt);
+        if (z && !o.plan) o.check(launch_vq_rows_to_nchw(zt, nullptr, z, B, H * W, c.embed_dim, o.c->stream), "latent to NCHW");
+        return zt;
+    }
     bf16_t* hwp = o.abf(head_conv_wp_bytes(bin) / 2);
     float* ze = o.af32((size_t)B * c.z_channels * H * W);
     o.head(h, B, H, W, bin, bin, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, o.w<float>(v.coutw), o.w<float>(v.coutb), c.z_channels, ze, no, hwp);
     if (!o.plan) o.check(launch_vq_quantize(ze, nullptr, 0, o.w<float>(v.qw), o.w<float>(v.qb), z, nullptr, B, H * W, 0, o.c->stream), "quant_conv");
+    return nullptr;
 }
 
 // ------------------------------------------------------------------------------------ CLIP
@@ -1421,7 +1450,7 @@ void rdm_ctx_destroy(rdm_ctx* c) {
     void* ptrs[] = {c->zero_page, c->unet.blob, c->unet.arena.base, c->unet.kv_cache, c->vq.blob, c->vq.arena.base,
                     c->clip.blob, c->clip.arena.base, c->gn_partial, c->samp, c->splitk_ws, c->unet.xa_cache,
                     c->rarm.blob, c->rarm.arena.base, c->rarm.cache, c->rarm.ctxkv, c->rarm.state, c->rarm.xa, c->wfrag_tmp, c->bwd_tmp,
-                    c->vqenc.blob, c->vqenc.arena.base, c->eye3, c->unet.emb_table};
+                    c->vqenc.blob, c->vqenc.arena.base, c->eye3, c->unet.emb_table, c->code_norms};
     for (void* p : ptrs) if (p) hipFree(p);
     c->drop_frags();
     knn_free(c->db);
@@ -1482,13 +1511,15 @@ int rdm_load_vq(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nb
     if (cfg->ch % 64 || cfg->out_ch > 4 || cfg->n_attn_resolutions < 0 || cfg->n_attn_resolutions > RDM_MAX_LEVELS ||
         !((cfg->embed_dim == 3 && cfg->z_channels == 3) || (cfg->embed_dim % 64 == 0 && cfg->z_channels % 64 == 0 && !cfg->kl)))
         return c->fail(-1, "unsupported vq cfg: ch %% 64 == 0 and either embed_dim == z_channels == 3 (VQ-f4 / KL-f4) or both multiples of 64 (VQGAN-f16)");
+    if (c->code_norms) { RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->code_norms); c->code_norms = nullptr; }
     Manifest mf; build_vq(c->vq, *cfg, mf);
     return load_blob(c, c->vq, mf, packed, nbytes);
 }
 static int cfg_check_vqenc(rdm_ctx* c, const rdm_vq_cfg* g) {
     const bool ok = g && g->n_ch_mult >= 1 && g->n_ch_mult <= RDM_MAX_LEVELS && g->n_attn_resolutions >= 0 && g->n_attn_resolutions <= RDM_MAX_LEVELS &&
-                    g->ch % 64 == 0 && g->out_ch <= 4 && g->embed_dim == 3 && g->z_channels == 3 && !g->kl && g->resolution % (1 << (g->n_ch_mult - 1)) == 0;
-    if (!ok) return c ? c->fail(-1, "unsupported first-stage encoder cfg: VQ interface (kl = 0) with embed_dim == z_channels == 3, ch %% 64 == 0") : -1;
+                    g->ch % 64 == 0 && g->out_ch <= 4 && !g->kl && g->resolution % (1 << (g->n_ch_mult - 1)) == 0 &&
+                    ((g->embed_dim == 3 && g->z_channels == 3) || (g->embed_dim > 0 && g->z_channels > 0 && g->embed_dim % 64 == 0 && g->z_channels % 64 == 0));
+    if (!ok) return c ? c->fail(-1, "unsupported first-stage encoder cfg: VQ interface (kl = 0), ch %% 64 == 0 and either embed_dim == z_channels == 3 (VQ-f4) or both multiples of 64 (VQGAN-f16)") : -1;
     return 0;
 }
 long long rdm_vqenc_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) {
@@ -1503,12 +1534,75 @@ int rdm_load_vqenc(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t
     Manifest mf; build_vqenc(c->vqenc, *cfg, mf);
     return load_blob(c, c->vqenc, mf, packed, nbytes);
 }
+// Samples per decoder (or wide-latent encoder: the same levels, mirrored) pass.  Decoding is per sample (GroupNorm statistics included), so a batch may be walked in ranges; a range is
+// sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo convs address an operand through
+// 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the seven 128-channel convs of
+// the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).  RDM_VQ_RANGE overrides (tests).
+static int vq_range(const rdm_vq_cfg& c, int b) {
+    static const int env = rdm_env_int(getenv("RDM_VQ_RANGE"), 0);
+    if (env > 0) return env < b ? env : b;
+    long long per = 1;
+    for (int l = 0; l < c.n_ch_mult; l++) {
+        const long long r = c.resolution >> l, e = r * r * c.ch * c.ch_mult[l];
+        if (e > per) per = e;
+        // the level's Upsample output (and the first convs' input at the next finer level) keeps THIS level's channel count at twice the
+        // resolution -- the decoder's largest activation (VQ-f4: 256 x 256 x 256 per image, twice the level maximum): a range sized without
+        // it reached exactly 2^31 elements and pushed those convs off the 32-bit-offset halo kernels (advisor, round 5)
+        if (l >= 1) { const long long u = 4 * r * r * c.ch * c.ch_mult[l]; if (u > per) per = u; }
+    }
+    long long n = (1LL << 30) / per;
+    if (n < 1) n = 1;
+    return n < b ? (int)n : b;
+}
 int rdm_vq_encode(rdm_ctx* c, const float* img, int b, float* z_out) {
     RDM_ENTER(c);
     if (!img || !z_out || b < 1) return c->fail(-1, "rdm_vq_encode: bad argument");
     if (!c->vqenc.loaded) return c->fail(-1, "first-stage encoder weights not loaded (rdm_load_vqenc)");
-    RDM_TRY(ensure_gn_partial(c, b));
-    return run_with_arena(c, c->vqenc.arena, c->vqenc.blob, [&](Ops& o) { vqenc_body(o, c->vqenc, img, b, z_out); });
+    const rdm_vq_cfg& q = c->vqenc.cfg;
+    const int nb = c->vqenc.wide ? vq_range(q, b) : b, zr = q.resolution >> (q.n_ch_mult - 1);      // wide latents: walked in ranges as rdm_vq_decode* is
+    RDM_TRY(ensure_gn_partial(c, nb));
+    for (int b0 = 0; b0 < b; b0 += nb) {
+        const int n = b - b0 < nb ? b - b0 : nb;
+        RDM_TRY(run_with_arena(c, c->vqenc.arena, c->vqenc.blob, [&](Ops& o) {
+            vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, z_out + (size_t)b0 * q.embed_dim * zr * zr);
+        }));
+    }
+    return 0;
+}
+// taming VQModel.encode as reached from Net2NetTransformer.encode_to_z (un-vendored, parity unpinned): quant_z, _, info =
+// first_stage_model.encode(x); indices = info[2].view(b, -1).  The token-major fp32 latent of the encoder goes straight into the
+// nearest-code search; quant_out = the chosen codebook rows as [b, embed_dim, h, w].
+int rdm_vq_encode_indices(rdm_ctx* c, const float* img, int b, int64_t* indices_out, float* quant_out) {
+    RDM_ENTER(c);
+    if (!img || !indices_out || b < 1) return c->fail(-1, "rdm_vq_encode_indices: bad argument");
+    if (!c->vqenc.loaded) return c->fail(-1, "first-stage encoder weights not loaded (rdm_load_vqenc)");
+    if (!c->vq.loaded) return c->fail(-1, "rdm_vq_encode_indices: the codebook comes with the first-stage decoder weights (rdm_load_vq), which are not loaded");
+    const rdm_vq_cfg& q = c->vqenc.cfg; const rdm_vq_cfg& d = c->vq.cfg;
+    if (!c->vqenc.wide || !c->vq.wide || d.kl) return c->fail(-1, "rdm_vq_encode_indices needs a VQGAN first stage with a wide latent (embed_dim %% 64 == 0); VQ-f4 latents are quantised by rdm_vq_quantize");
+    if (q.embed_dim != d.embed_dim || q.z_channels != d.z_channels || q.resolution != d.resolution || q.n_ch_mult != d.n_ch_mult || q.out_ch != d.out_ch)
+        return c->fail(-1, "rdm_vq_encode_indices: encoder and decoder were loaded with different cfgs (embed_dim %d / %d, resolution %d / %d)", q.embed_dim, d.embed_dim, q.resolution, d.resolution);
+    if (!vq_nearest_supported(q.embed_dim)) return c->fail(-1, "rdm_vq_encode_indices: embed_dim %d not taken by the nearest-code kernel (multiples of 64 up to 512)", q.embed_dim);
+    const float* cb = (const float*)(c->vq.blob + c->vq.codebook);
+    if (!c->code_norms) {
+        RDM_CHECK_HIP(c, hipMalloc((void**)&c->code_norms, (size_t)d.n_embed * sizeof(float)));
+        const hipError_t e = launch_vq_code_norms(cb, c->code_norms, d.n_embed, d.embed_dim, c->stream);
+        if (e != hipSuccess) { (void)hipFree(c->code_norms); c->code_norms = nullptr; return c->fail(-2, "codebook norms: %s", hipGetErrorString(e)); }
+    }
+    const int nb = vq_range(q, b), zr = q.resolution >> (q.n_ch_mult - 1), HW = zr * zr;
+    RDM_TRY(ensure_gn_partial(c, nb));
+    for (int b0 = 0; b0 < b; b0 += nb) {
+        const int n = b - b0 < nb ? b - b0 : nb;
+        RDM_TRY(run_with_arena(c, c->vqenc.arena, c->vqenc.blob, [&](Ops& o) {
+            const float* zt = vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, nullptr);
+            const long long M = (long long)n * HW;
+            char* ws = (char*)o.ar->alloc(vq_nearest_ws_bytes(M, d.n_embed));
+            int* idx32 = (int*)o.ar->alloc((size_t)M * 4);
+            o.vq_nearest(zt, cb, c->code_norms, M, d.n_embed, d.embed_dim, ws, idx32, (long long*)indices_out + (size_t)b0 * HW);
+            if (quant_out && !o.plan)
+                o.check(launch_vq_rows_to_nchw(cb, idx32, quant_out + (size_t)b0 * d.embed_dim * HW, n, HW, d.embed_dim, o.c->stream), "codebook rows to NCHW");
+        }));
+    }
+    return 0;
 }
 int rdm_load_clip(rdm_ctx* c, const rdm_clip_cfg* cfg, const void* packed, size_t nbytes) {
     RDM_ENTER(c);
@@ -1786,27 +1880,6 @@ int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const 
     return run.finish(z_out);
 }
 
-// Samples per decoder pass.  Decoding is per sample (GroupNorm statistics included), so a batch may be walked in ranges; a range is
-// sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo convs address an operand through
-// 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the seven 128-channel convs of
-// the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).  RDM_VQ_RANGE overrides (tests).
-static int vq_range(const VqModel& v, int b) {
-    static const int env = rdm_env_int(getenv("RDM_VQ_RANGE"), 0);
-    if (env > 0) return env < b ? env : b;
-    const rdm_vq_cfg& c = v.cfg;
-    long long per = 1;
-    for (int l = 0; l < c.n_ch_mult; l++) {
-        const long long r = c.resolution >> l, e = r * r * c.ch * c.ch_mult[l];
-        if (e > per) per = e;
-        // the level's Upsample output (and the first convs' input at the next finer level) keeps THIS level's channel count at twice the
-        // resolution -- the decoder's largest activation (VQ-f4: 256 x 256 x 256 per image, twice the level maximum): a range sized without
-        // it reached exactly 2^31 elements and pushed those convs off the 32-bit-offset halo kernels (advisor, round 5)
-        if (l >= 1) { const long long u = 4 * r * r * c.ch * c.ch_mult[l]; if (u > per) per = u; }
-    }
-    long long n = (1LL << 30) / per;
-    if (n < 1) n = 1;
-    return n < b ? (int)n : b;
-}
 
 int rdm_vq_decode(rdm_ctx* c, const float* z, int b, int force_not_quantize, float* img_out, int32_t* indices_out) {
     RDM_ENTER(c);
@@ -1814,7 +1887,7 @@ int rdm_vq_decode(rdm_ctx* c, const float* z, int b, int force_not_quantize, flo
     if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
     if (c->vq.wide) return c->fail(-1, "this first stage has a wide latent (VQGAN-f16): decode from code indices with rdm_vq_decode_indices");
     const rdm_vq_cfg& q = c->vq.cfg;
-    const int nb = vq_range(c->vq, b), zr = q.resolution >> (q.n_ch_mult - 1);
+    const int nb = vq_range(c->vq.cfg, b), zr = q.resolution >> (q.n_ch_mult - 1);
     RDM_TRY(ensure_gn_partial(c, nb));
     for (int b0 = 0; b0 < b; b0 += nb) {
         const int n = b - b0 < nb ? b - b0 : nb;
@@ -1846,7 +1919,7 @@ int rdm_vq_decode_indices(rdm_ctx* c, const int64_t* indices, int b, float* img_
     if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
     if (!c->vq.wide || c->vq.cfg.kl) return c->fail(-1, "rdm_vq_decode_indices needs a VQGAN first stage with a wide latent (z_channels %% 64 == 0)");
     const rdm_vq_cfg& q = c->vq.cfg;
-    const int nb = vq_range(c->vq, b), zr = q.resolution >> (q.n_ch_mult - 1);
+    const int nb = vq_range(c->vq.cfg, b), zr = q.resolution >> (q.n_ch_mult - 1);
     RDM_TRY(ensure_gn_partial(c, nb));
     for (int b0 = 0; b0 < b; b0 += nb) {
         const int n = b - b0 < nb ? b - b0 : nb;
@@ -2309,6 +2382,19 @@ int rdm_op_conv3x3(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, c
     Ops o = op_exec(c);
     o.conv3((const bf16_t*)x0, (const bf16_t*)x1, C0, C1, (const bf16_t*)w, bias, B, Hin, Win, N, stride, ups, rowvec, rowvec_ld,
             (const bf16_t*)res, (bf16_t*)out);
+    return o.rc;
+}
+// the nearest-code kernel alone on caller-given operands (vqcode.hip): |e|^2 and the split planes live in the sampler scratch
+int rdm_op_vq_nearest_code(rdm_ctx* c, const float* z, const float* codebook, long long M, int N, int E, int32_t* idx_out) {
+    RDM_ENTER(c);
+    if (!z || !codebook || !idx_out || M < 1 || N < 1) return c->fail(-1, "rdm_op_vq_nearest_code: null argument or M, N < 1");
+    if (!vq_nearest_supported(E)) return c->fail(-1, "rdm_op_vq_nearest_code: E = %d; the kernel takes multiples of 64 up to 512", E);
+    const size_t nbytes = ((size_t)N * 4 + 255) & ~(size_t)255;
+    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, nbytes + vq_nearest_ws_bytes(M, N)));
+    float* norms = (float*)c->samp;
+    RDM_CHECK_HIP(c, launch_vq_code_norms(codebook, norms, N, E, c->stream));
+    Ops o = op_exec(c);
+    o.vq_nearest(z, codebook, norms, M, N, E, c->samp + nbytes, idx_out, nullptr);
     return o.rc;
 }
 static int op_rarm_sampler_run(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,

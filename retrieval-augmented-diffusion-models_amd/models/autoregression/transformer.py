@@ -1,11 +1,13 @@
 """Native counterpart of the SAMPLING methods of rdm/models/autoregression/transformer.py::LatentImageRETRO (RARM):
-`sample` (:224-294), `sampling_util` (:296-312), `sample_from_rdata` (:314-404), `get_qids` (:407-430), and of the taming
-Net2NetTransformer pieces it inherits for sampling (`encode_to_c` with the SOSProvider, `decode_to_img`, `top_k_logits`).
-Training, logging and image-patch neighbour encoders are out of scope (the shipped configs use
-IdentityEncoder on CLIP embeddings, models/rarm/imagenet/dogs/config.yaml:10-13).
+`sample` (:224-294), `sampling_util` (:296-312), `sample_from_rdata` (:314-404), `get_qids` (:407-430), `get_r` (:191-205),
+`log_images` (:422-478: full samples, image completion from the first half of an image's codes, samples under masked neighbours,
+reconstructions), and of the taming Net2NetTransformer pieces it inherits for them (`encode_to_z`, `encode_to_c` with the
+SOSProvider, `decode_to_img`, `top_k_logits`).
+Training, the patch plotter of log_images and image-patch neighbour encoders are out of scope (the shipped
+configs use IdentityEncoder on CLIP embeddings, models/rarm/imagenet/dogs/config.yaml:10-13).
 
 The transformer (rdm.modules.attention.RetrievalPatchTransformer, 18 x 768, causal self-attention + cross-attention to the k
-retrieved neighbours) and the VQGAN-f16 decoder run inside librdm_hip; the 256-step loop is ONE library call
+retrieved neighbours), the VQGAN-f16 decoder and its encoder + nearest-code search run inside librdm_hip; the 256-step loop is ONE library call
 (rdm_rarm_sample) that decodes against a K/V cache — the reference re-runs the whole prefix for every token (:241-248).
 The multinomial draw uses uniforms taken from torch's global generator on the model's device (so `seed_everything`
 makes a run repeatable) and the inverse-CDF rule documented in include/rdm_hip.h.
@@ -67,7 +69,10 @@ class LatentImageRETRO(object):
         self.ctx.load_rarm(self.rarm_cfg, packing.pack("rarm", self.rarm_cfg, tsd))
 
     def load_first_stage_state_dict(self, fsd):
+        """Decoder + codebook always; the encoder (`encoder.*`, `quant_conv.*`: encode_to_z, log_images) when the dict carries it."""
         self.ctx.load_vq(self.vq_cfg, packing.pack("vq", self.vq_cfg, fsd))
+        if any(k.startswith("encoder.") for k in fsd):
+            self.ctx.load_vq_encoder(self.vq_cfg, packing.pack("vqenc", self.vq_cfg, fsd))
 
     # ---- taming pieces
     def encode_to_c(self, c):
@@ -77,7 +82,36 @@ class LatentImageRETRO(object):
         return idx, idx
 
     @torch.no_grad()
-    def decode_to_img(self, index, zshape):
+    def encode_to_z(self, x):
+        """Net2NetTransformer.encode_to_z: image [b,3,R,R] in [-1,1] -> (quant_z [b,embed_dim,h,w], indices int64 [b, h*w])."""
+        quant_z, indices = self.ctx.vq_encode_indices(x, return_quant=True)
+        return quant_z, indices
+
+    def get_xc(self, batch, N=None):
+        """taming get_input on the `image` key ([N,H,W,3] -> [N,3,H,W] float); the conditioning is the SOS provider's: unused."""
+        x = torch.as_tensor(batch["image"])
+        if x.ndim == 3:
+            x = x[..., None]
+        x = x.permute(0, 3, 1, 2).to(dtype=torch.float32).contiguous()
+        if N is not None:
+            x = x[:N]
+        return x, torch.zeros((x.shape[0], 0))
+
+    # ---- transformer.py:191-205 (IdentityEncoder on [N,k,d] embeddings); the masking is host-side torch, as written there
+    @torch.no_grad()
+    def get_r(self, batch, N=None, p_mask=0.):
+        nns = torch.as_tensor(batch[self.nn_key])
+        if N is not None:
+            nns = nns[:N]
+        r = nns.to(torch.float32)
+        if p_mask > 0.:
+            mask = torch.bernoulli(torch.ones_like(r) * p_mask)
+            mask = mask.round().to(dtype=torch.int64)
+            r = r * (1 - mask) + mask * torch.ones_like(r) * self.mask_token
+        return r
+
+    @torch.no_grad()
+    def decode_to_img(self, index, zshape=None):
         """Net2NetTransformer.decode_to_img: indices [b, h*w] -> image [b,3,256,256]."""
         return self.ctx.vq_decode_indices(index.reshape(index.shape[0], -1))
 
@@ -99,8 +133,12 @@ class LatentImageRETRO(object):
         if not sample:
             top_k, top_p = 1, None                                          # torch.topk(probs, 1): the arg-max token (:266-267)
         if top_p is None:
-            return self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale)
-        return self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale, top_p=top_p)
+            new = self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale)
+        else:
+            new = self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale, top_p=top_p)
+        if x.shape[1] == c.shape[1]:
+            return new
+        return torch.cat((x[:, c.shape[1]:].to(torch.int64), new), 1)      # the given prefix, then the new tokens (:268-269)
 
     # ---- transformer.py:296-312
     @torch.no_grad()
@@ -141,6 +179,36 @@ class LatentImageRETRO(object):
         z_start = torch.zeros((N, 0), dtype=torch.long)
         out["samples_with_sampled_nns"] = self.sampling_util(steps, z_start, retro_cond, cond, temperature, top_k, z_shape, top_p=top_p, **kwargs)
         return out
+
+    # ---- transformer.py:422-478.  plot_cond_stage is a no-op for the SOS provider; the patch plotter needs the raw patches (out of scope)
+    @torch.no_grad()
+    def log_images(self, batch, temperature=None, top_k=256, top_p=1.0, callback=None, N=4, half_sample=True, sample=True, p_sample=True,
+                   masking_probs=[0.5, 1.0], **kwargs):
+        log = dict()
+        x, c = self.get_xc(batch, N)
+        r = self.get_r(batch, N, p_mask=0.)
+        x = x.to(device=self.device)
+        r = r.to(device=self.device)
+        quant_z, z_indices = self.encode_to_z(x)
+        _, c_indices = self.encode_to_c(c)
+        n = z_indices.shape[1]
+        if sample:
+            log["samples_full"] = self.sampling_util(n, z_indices[:, :0], r, c_indices, zshape=quant_z.shape, temperature=temperature,
+                                                     top_k=top_k, top_p=top_p, callback=callback)
+        if half_sample:
+            z_start_indices = z_indices[:, :n // 2]
+            log["samples_half"] = self.sampling_util(n - z_start_indices.shape[1], z_start_indices, r, c_indices, temperature=temperature,
+                                                     top_k=top_k, top_p=top_p, callback=callback, zshape=quant_z.shape)
+        if p_sample:
+            if masking_probs[0] >= self.p_mask_max and self.p_mask_max != 0.:
+                masking_probs = [self.p_mask_max] + masking_probs
+            for p_mask in masking_probs:
+                r = self.get_r(batch, N, p_mask=p_mask).to(device=self.device)
+                log[f"samples_full_p_{p_mask:.2f}"] = self.sampling_util(n, z_indices[:, :0], r, c_indices, zshape=quant_z.shape,
+                                                                         temperature=temperature, top_k=top_k, top_p=top_p, callback=callback)
+        log["inputs"] = x
+        log["reconstructions"] = self.decode_to_img(z_indices, quant_z.shape)
+        return log
 
     # ---- transformer.py:407-430
     def get_qids(self, memsize, N, qids=None, use_weights=False, verbose=False):

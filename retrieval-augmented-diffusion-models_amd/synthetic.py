@@ -133,6 +133,47 @@ def vq_param_shapes(cfg) -> Dict[str, tuple]:
     return p
 
 
+def vq_encoder_param_shapes(cfg) -> Dict[str, tuple]:
+    """`encoder.*` and `quant_conv.*` of the first-stage state dict (ldm / taming Encoder with in_channels = out_ch, double_z = False;
+    un-vendored like the decoder): the mirror image of vq_param_shapes."""
+    mults = [cfg.ch_mult[i] for i in range(cfg.n_ch_mult)]
+    attn_res = {cfg.attn_resolutions[i] for i in range(cfg.n_attn_resolutions)}
+    p: Dict[str, tuple] = {}
+
+    def res(pre, cin, cout):
+        p[pre + ".norm1.weight"] = (cin,); p[pre + ".norm1.bias"] = (cin,)
+        p[pre + ".conv1.weight"] = (cout, cin, 3, 3); p[pre + ".conv1.bias"] = (cout,)
+        p[pre + ".norm2.weight"] = (cout,); p[pre + ".norm2.bias"] = (cout,)
+        p[pre + ".conv2.weight"] = (cout, cout, 3, 3); p[pre + ".conv2.bias"] = (cout,)
+        if cin != cout:
+            p[pre + ".nin_shortcut.weight"] = (cout, cin, 1, 1); p[pre + ".nin_shortcut.bias"] = (cout,)
+
+    def attn(a, ch):
+        p[a + ".norm.weight"] = (ch,); p[a + ".norm.bias"] = (ch,)
+        for n in ("q", "k", "v", "proj_out"):
+            p[f"{a}.{n}.weight"] = (ch, ch, 1, 1); p[f"{a}.{n}.bias"] = (ch,)
+
+    p["encoder.conv_in.weight"] = (cfg.ch, cfg.out_ch, 3, 3); p["encoder.conv_in.bias"] = (cfg.ch,)
+    bin_, curr_res = cfg.ch, cfg.resolution
+    for lvl, mult in enumerate(mults):
+        bout = cfg.ch * mult
+        for i in range(cfg.num_res_blocks):
+            res(f"encoder.down.{lvl}.block.{i}", bin_, bout); bin_ = bout
+            if curr_res in attn_res:
+                attn(f"encoder.down.{lvl}.attn.{i}", bin_)
+        if lvl != len(mults) - 1:
+            p[f"encoder.down.{lvl}.downsample.conv.weight"] = (bin_, bin_, 3, 3); p[f"encoder.down.{lvl}.downsample.conv.bias"] = (bin_,)
+            curr_res //= 2
+    res("encoder.mid.block_1", bin_, bin_)
+    if cfg.mid_attn:
+        attn("encoder.mid.attn_1", bin_)
+    res("encoder.mid.block_2", bin_, bin_)
+    p["encoder.norm_out.weight"] = (bin_,); p["encoder.norm_out.bias"] = (bin_,)
+    p["encoder.conv_out.weight"] = (cfg.z_channels, bin_, 3, 3); p["encoder.conv_out.bias"] = (cfg.z_channels,)
+    p["quant_conv.weight"] = (cfg.embed_dim, cfg.z_channels, 1, 1); p["quant_conv.bias"] = (cfg.embed_dim,)
+    return p
+
+
 def clip_param_shapes(cfg) -> Dict[str, tuple]:
     p: Dict[str, tuple] = {}
 
@@ -181,6 +222,7 @@ def rarm_param_shapes(cfg) -> Dict[str, tuple]:
 
 
 UNET_SEED, VQ_SEED, CLIP_SEED, RARM_SEED, VQGAN_SEED = 1234, 4321, 99, 777, 888   # seeds of the committed golden fixtures
+VQENC_SEED = 889          # the first-stage encoder is drawn on its own: the decoder draws above stay what the fixtures hold
 
 
 def rarm_state_dict(cfg, seed=RARM_SEED):
@@ -193,6 +235,10 @@ def unet_state_dict(cfg, seed=UNET_SEED):
 
 def vq_state_dict(cfg, seed=VQ_SEED):
     return synth_state_dict(vq_param_shapes(cfg), seed)
+
+
+def vq_encoder_state_dict(cfg, seed=VQENC_SEED):
+    return synth_state_dict(vq_encoder_param_shapes(cfg), seed)
 
 
 def clip_state_dict(cfg, seed=CLIP_SEED):

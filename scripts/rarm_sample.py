@@ -6,7 +6,12 @@ Same flags, defaults and run loop as scripts/rarm_sample.py:100-293: -s/--savepa
 --temperature (1.0), --top_m (0.01), --k_nn (4), -c/--caption, --only_caption, --unconditional, --use_weights; 256 tokens
 (f16 first stage), `seed_everything` before every run, files `{start}-{key}-run{n}-sample{i}.png`.
 Deliberate differences: as scripts/rdm_sample.py (no CPU path, --save_nns unsupported, --seed works).  Additions:
---clip_ckpt, --synthetic, --top_p (1.0: nucleus sampling after top-k, the `top_p` the reference's sampling_util names and asserts away).
+--clip_ckpt, --synthetic, --top_p (1.0: nucleus sampling after top-k, the `top_p` the reference's sampling_util names and asserts away),
+--complete_from PATH [--keep_rows R]: image completion as LatentImageRETRO.log_images does it (`samples_half`, transformer.py:457-462) --
+every image of PATH (a file or a directory) is centre-cropped, resized to the first-stage resolution and encoded to its VQGAN codes, the
+first R code rows (default: half the grid) are kept and the rest is sampled with the flags above; neighbours come from the image's own
+CLIP embedding unless -c / --only_caption / --unconditional say otherwise.  Writes `{start}-samples_half-run{n}-sample{i}.png` and
+`{start}-reconstructions-run{n}-sample{i}.png`.
 """
 import argparse
 import datetime
@@ -48,6 +53,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--clip_ckpt", type=Path, default=None, help="[native] CLIP ViT-B/32 state_dict (.pt)")
     parser.add_argument("--synthetic", default=False, action="store_true", help="[native] seeded random weights + synthetic database")
     parser.add_argument("--synthetic_db_rows", type=int, default=200_000, help="[native] rows of the --synthetic database")
+    parser.add_argument("--complete_from", type=Path, default=None,
+                        help="[native] image file or directory: keep the first code rows of each image and sample the rest")
+    parser.add_argument("--keep_rows", type=int, default=None, help="[native] code rows kept by --complete_from (default: half the grid)")
     return parser
 
 
@@ -76,7 +84,10 @@ def load_model(opt):
         model = LatentImageRETRO(transformer_config={"params": {}}, first_stage_config={"params": {"ddconfig": {}}}, k_nn=opt.k_nn, device=opt.gpu,
                                  nn_memory=np.arange(min(10_000, opt.synthetic_db_rows)))
         model.load_transformer_state_dict(synthetic.rarm_state_dict(model.rarm_cfg))
-        model.load_first_stage_state_dict(synthetic.vq_state_dict(model.vq_cfg, synthetic.VQGAN_SEED))
+        fsd = synthetic.vq_state_dict(model.vq_cfg, synthetic.VQGAN_SEED)
+        if opt.complete_from is not None:
+            fsd.update(synthetic.vq_encoder_state_dict(model.vq_cfg))
+        model.load_first_stage_state_dict(fsd)
         n = opt.synthetic_db_rows
         pool = {"embedding": synthetic.clip_like_rows(n), "img_id": np.arange(n), "patch_coords": np.zeros((n, 4), np.int64)}
         retr = ClipImageRetriever(state_dict=synthetic.clip_state_dict(_lib.make_clip_cfg()), ctx=model.ctx)
@@ -108,8 +119,84 @@ def load_model(opt):
     return model.eval()
 
 
+IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp", ".webp")
+
+
+def load_images(path, resolution):
+    """Image file or directory (sorted) -> f32 [n,3,R,R] in [-1,1]: centre crop to a square, bicubic resize to the first-stage resolution."""
+    import torch
+    from PIL import Image
+    path = Path(path)
+    files = sorted(f for f in path.iterdir() if f.suffix.lower() in IMAGE_SUFFIXES) if path.is_dir() else [path]
+    if not files:
+        raise SystemExit(f"--complete_from: no image found at {path}")
+    out = []
+    for f in files:
+        im = Image.open(f).convert("RGB")
+        w, h = im.size
+        side = min(w, h)
+        left, top = (w - side) // 2, (h - side) // 2
+        im = im.crop((left, top, left + side, top + side)).resize((resolution, resolution), Image.BICUBIC)
+        out.append(torch.from_numpy(np.asarray(im, dtype=np.uint8).copy()).permute(2, 0, 1).float() / 127.5 - 1.0)
+    return torch.stack(out)
+
+
+def complete(model, opt):
+    """[native] --complete_from: the `samples_half` / `reconstructions` entries of LatentImageRETRO.log_images (transformer.py:448-479) with
+    a selectable split row, batch by batch over the given images."""
+    import torch
+    from rdm_amd.modules.custom_clip.tokenizer import tokenize
+    sampling_start = datetime.datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
+    cfg = model.vq_cfg
+    side = cfg.resolution >> (cfg.n_ch_mult - 1)
+    keep = side // 2 if opt.keep_rows is None else opt.keep_rows
+    if not 0 <= keep < side:
+        raise SystemExit(f"--keep_rows must lie in [0, {side}), got {keep}")
+    images = load_images(opt.complete_from, cfg.resolution)
+    if model.retriever is not None and model.retriever.searcher is None:
+        model.train_searcher()
+    for n in range(opt.n_runs):
+        if opt.seed is not None:
+            seed_everything(opt.seed)
+        print(f"Run {n + 1}/{opt.n_runs}")
+        for b0 in range(0, images.shape[0], opt.batch_size):
+            x = images[b0:b0 + opt.batch_size].to(model.device)
+            bs = x.shape[0]
+            if opt.unconditional:
+                r = torch.zeros((bs, 1, 512), dtype=torch.float, device=model.device)
+            else:
+                if opt.caption != "":
+                    q = model.retriever.retriever.model.encode_text(torch.from_numpy(tokenize([opt.caption] * bs)))
+                else:
+                    q = model.retriever.retriever(x)                     # the image's own CLIP embedding
+                q = q.float()
+                if opt.only_caption:
+                    assert opt.caption != "", "Need a caption"
+                    r = q.unsqueeze(1).to(model.device)
+                else:
+                    qe = q.cpu().numpy().astype(np.float32)
+                    nns, _ = model.retriever.searcher.search_batched(qe / np.linalg.norm(qe, axis=1)[:, np.newaxis], final_num_neighbors=opt.k_nn)
+                    r = torch.from_numpy(np.asarray(model.retriever.data_pool["embedding"][nns])).to(model.device).to(torch.float)
+            quant_z, z_indices = model.encode_to_z(x)
+            _, c_indices = model.encode_to_c(torch.zeros((bs, 0)))
+            z_start = z_indices[:, :keep * side]
+            logs = {"samples_half": model.sampling_util(z_indices.shape[1] - z_start.shape[1], z_start, r, c_indices, opt.temperature, opt.top_k,
+                                                        quant_z.shape, top_p=opt.top_p, guidance_scale=opt.guidance_scale),
+                    "reconstructions": model.decode_to_img(z_indices, quant_z.shape)}
+            for key, imgs in logs.items():
+                for bi, be in enumerate(imgs):
+                    save_image(be, os.path.join(opt.savepath, f"{sampling_start}-{key}-run{n}-sample{b0 + bi}.png"))
+        if opt.increase_guidance:
+            opt.guidance_scale += 1.0
+            print(f"New guidance scale: {opt.guidance_scale}")
+    print("Done")
+    return sampling_start
+
+
 def sample(model, opt):
     """rarm_sample.py:225-293."""
+    if getattr(opt, "complete_from", None) is not None:
+        return complete(model, opt)
     import torch
     from rdm_amd.modules.custom_clip.tokenizer import tokenize
     qids = None
