@@ -209,6 +209,22 @@ int rdm_rarm_sample(rdm_ctx* ctx, const rdm_rarm_sample_args* args, const int64_
  * that reaches top_p, the crossing token kept, every token tied with the last kept one kept too.  The draw is unchanged. */
 int rdm_rarm_sample_top_p(rdm_ctx* ctx, const rdm_rarm_sample_args* args, float top_p, const int64_t* cond_tokens, const float* context,
                           const float* uniforms, int64_t* tokens_out);
+/* ---- RARM over whole sequences: one transformer pass over all t positions (causal self-attention at d_head 64 on the MFMA units,
+ *      csrc/attention.hip: causal_d64_kernel) instead of t decode steps.  Sequences are walked in ranges of at most 32 768 rows
+ *      (RARM_SEQ_ROWS, csrc/model.hip), so the scratch does not grow with b * t.  At most 128 neighbours per sequence (k <= 128).
+ * rdm_rarm_forward_seq: RetrievalPatchTransformer.forward(x, context) (rdm/modules/attention.py:252-272): the contract of
+ *      rdm_rarm_forward -- tokens [dev] int64 [b,t], context [dev] f32 [b,k,context_dim], logits_out [dev] f32 [b,t,vocab_out]. */
+int rdm_rarm_forward_seq(rdm_ctx* ctx, const int64_t* tokens, int b, int t, const float* context, int k, float* logits_out);
+/* LatentImageRETRO.forward + compute_loss without the mean (rdm/models/autoregression/transformer.py:62-70, 213-222):
+ *      nll_out[i,j] = -log softmax(logits[i,j,:])[targets[i,j]], F.cross_entropy(reduction='none').  tokens, targets [dev] int64 [b,t],
+ *      targets in [0, vocab_out) (outside: NaN); nll_out [dev] f32 [b,t].  The head GEMM runs in row pieces into bounded scratch:
+ *      [b*t, vocab_out] logits are never formed. */
+int rdm_rarm_nll(rdm_ctx* ctx, const int64_t* tokens, const int64_t* targets, int b, int t, const float* context, int k, float* nll_out);
+/* rdm_rarm_sample_top_p (top_p = 1: rdm_rarm_sample) whose conditioning prefix -- `c_indices` and the kept codes of an image completion,
+ *      transformer.py:232-248 -- is fed in ONE whole-sequence pass over positions 0 .. cond_len-2 that fills the decode step's K/V cache;
+ *      the token-by-token loop then starts at position cond_len-1.  cond_len == 1: nothing to prefill, the very launches of rdm_rarm_sample. */
+int rdm_rarm_sample_prefill(rdm_ctx* ctx, const rdm_rarm_sample_args* args, float top_p, const int64_t* cond_tokens, const float* context,
+                            const float* uniforms, int64_t* tokens_out);
 
 /* ---- CLIP: CLIP.encode_text / encode_image (rdm/modules/custom_clip/model.py:304-320), used by
  *      ClipImageRetriever / CLIPTextEmbedder (rdm/modules/retrievers.py:67-117).
@@ -428,6 +444,15 @@ int rdm_op_xattn_fused(rdm_ctx* ctx, const void* x_bf16, const float* ln_gamma, 
 int rdm_op_xattn_fused_ln3(rdm_ctx* ctx, void* x_bf16_inout, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G_bf16,
                            const void* U_bf16, const float* bias, int B, int n, int C, int NP, int ncols, int group,
                            const float* ln3_gamma, const float* ln3_beta, void* ln3_out_bf16);
+/* Causal self-attention at d_head 64 over all n positions (CrossAttention.forward with RetrievalPatchTransformer's causal mask,
+ * rdm/modules/attention.py:42-74, 199-272): qkv bf16 [B*n rows at stride ldq] = q | k | v thirds of heads*64 columns each, head h in columns
+ * h*64..h*64+63 of its third; out bf16 [B*n, heads*64] at stride ldo; 1 <= n <= 1024.  kcache / vcache (both or neither) [B][heads][L][64]
+ * bf16: rows 0..n-1 receive the K / V columns of qkv bit for bit (the decode step's cache layout), rows >= n are not touched. */
+int rdm_op_causal_attention_d64(rdm_ctx* ctx, const void* qkv_bf16, int ldq, int B, int n, int heads, float scale, void* out_bf16, int ldo,
+                                void* kcache_bf16_or_null, void* vcache_bf16_or_null, int L);
+/* nll_out[r] = logsumexp(logits[r,:]) - logits[r, targets[r]] in fp32 (F.cross_entropy(reduction='none'), transformer.py:62-70):
+ * logits f32 [rows, vocab] (vocab even), targets int64 [rows]; a target outside [0, vocab) gives NaN. */
+int rdm_op_rarm_nll(rdm_ctx* ctx, const float* logits, long long rows, int vocab, const int64_t* targets, float* nll_out);
 /* The UNet's `out` head (openaimodel.py:307-311: GroupNorm32 + SiLU + 3x3 conv to out_channels) and the VQ decoder's norm_out + swish +
  * conv_out as one statistics pass + one kernel: x bf16 NHWC [B, H, W, C] raw, 32 groups; gn_gamma / gn_beta null: no norm, x is convolved
  * as is.  w fp32 [Cout, C, 3, 3], bias fp32 [Cout] or null, out fp32 NCHW [B, Cout, H, W].  C % 32 == 0, C <= 240, W % 32 == 0, H even,

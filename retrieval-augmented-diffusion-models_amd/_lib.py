@@ -82,6 +82,9 @@ SIGNATURES = {
     "rdm_rarm_forward": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
     "rdm_rarm_sample": (C.c_int, [_P, C.POINTER(RarmSampleArgs), _P, _P, _P, _P]),
     "rdm_rarm_sample_top_p": (C.c_int, [_P, C.POINTER(RarmSampleArgs), C.c_float, _P, _P, _P, _P]),
+    "rdm_rarm_forward_seq": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "rdm_rarm_nll": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, C.c_int, _P]),
+    "rdm_rarm_sample_prefill": (C.c_int, [_P, C.POINTER(RarmSampleArgs), C.c_float, _P, _P, _P, _P]),
     "rdm_vq_decode_indices": (C.c_int, [_P, _P, C.c_int, _P]),
     "rdm_unet_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_ddim_num_intermediates": (C.c_int, [C.c_int, C.c_int]),
@@ -161,6 +164,8 @@ SIGNATURES = {
     "rdm_op_linear_rowvec": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]),
     "rdm_op_xattn_fused_ln3": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdm_op_xattn_fused": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "rdm_op_causal_attention_d64": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P, _P, C.c_int]),
+    "rdm_op_rarm_nll": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
     "rdm_op_small_attention": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_float, _P, C.c_int]),
     "rdm_op_adamw_multi": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
@@ -427,9 +432,46 @@ class Context:
         self._check(lib.rdm_rarm_forward(self._h, _ptr(tokens), b, t, _ptr(context), context.shape[1], _ptr(out)))
         return out
 
-    def rarm_sample(self, cond_tokens, context, steps, uniforms, temperature=1.0, top_k=None, guidance_scale=1.0, top_p=None):
+    RARM_SEQ_MAX_K = 128      # neighbours per sequence of the whole-sequence entries (small_attention's LDS limit)
+
+    def _check_rarm_seq(self, what, tokens, context):
+        b, t = tokens.shape
+        self._check_rarm(what, context, b)
+        self._check_ids(what, tokens, self.rarm_cfg.vocab_in, "tokens")
+        if t < 1 or t > self.rarm_cfg.sequence_length:
+            raise RdmError(f"{what}: {t} positions exceed the positional encoding (sequence_length {self.rarm_cfg.sequence_length})")
+        if context.shape[1] > self.RARM_SEQ_MAX_K:
+            raise RdmError(f"{what}: at most {self.RARM_SEQ_MAX_K} neighbours per sequence, got k={context.shape[1]}")
+        return b, t
+
+    def rarm_forward_seq(self, tokens, context):
+        """rarm_forward in ONE pass over all positions (include/rdm_hip.h rdm_rarm_forward_seq): -> logits f32 [b,t,vocab_out]."""
+        tokens = self._dev(tokens, torch.int64); context = self._dev(context, torch.float32)
+        if self.rarm_cfg is None:
+            raise RdmError("rarm_forward_seq: rarm weights not loaded")
+        b, t = self._check_rarm_seq("rarm_forward_seq", tokens, context)
+        out = torch.empty((b, t, self.rarm_cfg.vocab_out), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_rarm_forward_seq(self._h, _ptr(tokens), b, t, _ptr(context), context.shape[1], _ptr(out)))
+        return out
+
+    def rarm_nll(self, tokens, targets, context):
+        """F.cross_entropy(RetrievalPatchTransformer.forward(tokens, context), targets, reduction='none') without the [b,t,vocab] logits
+        (rdm_rarm_nll): tokens, targets int64 [b,t] -> f32 [b,t]."""
+        tokens = self._dev(tokens, torch.int64); targets = self._dev(targets, torch.int64); context = self._dev(context, torch.float32)
+        if self.rarm_cfg is None:
+            raise RdmError("rarm_nll: rarm weights not loaded")
+        b, t = self._check_rarm_seq("rarm_nll", tokens, context)
+        if tuple(targets.shape) != (b, t):
+            raise RdmError(f"rarm_nll: targets must be [{b},{t}], got {tuple(targets.shape)}")
+        self._check_ids("rarm_nll", targets, self.rarm_cfg.vocab_out, "targets")
+        out = torch.empty((b, t), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_rarm_nll(self._h, _ptr(tokens), _ptr(targets), b, t, _ptr(context), context.shape[1], _ptr(out)))
+        return out
+
+    def rarm_sample(self, cond_tokens, context, steps, uniforms, temperature=1.0, top_k=None, guidance_scale=1.0, top_p=None, prefill=False):
         """LatentImageRETRO.sample with sample=True: -> tokens int64 [b,steps].  uniforms f32 [steps,b] in [0,1).
-        top_p in (0, 1]: nucleus filter after top-k (include/rdm_hip.h rdm_rarm_sample_top_p); None or 1.0: none, today's entry."""
+        top_p in (0, 1]: nucleus filter after top-k (include/rdm_hip.h rdm_rarm_sample_top_p); None or 1.0: none, today's entry.
+        prefill: the conditioning prefix runs in one whole-sequence pass instead of token by token (rdm_rarm_sample_prefill)."""
         top_p = check_top_p("rarm_sample", top_p)
         cond_tokens = self._dev(cond_tokens, torch.int64); context = self._dev(context, torch.float32)
         uniforms = self._dev(uniforms, torch.float32)
@@ -441,7 +483,14 @@ class Context:
         a = RarmSampleArgs(batch=b, k=context.shape[1], cond_len=tc, steps=steps, temperature=temperature,
                            top_k=int(top_k) if top_k is not None else 0, guidance_scale=guidance_scale)
         out = torch.empty((b, steps), device=self.device, dtype=torch.int64)
-        if top_p is None:
+        if prefill:
+            if tc + steps - 1 > self.rarm_cfg.sequence_length:
+                raise RdmError(f"rarm_sample: {tc + steps - 1} positions exceed the positional encoding (sequence_length {self.rarm_cfg.sequence_length})")
+            if context.shape[1] > self.RARM_SEQ_MAX_K:
+                raise RdmError(f"rarm_sample: prefill takes at most {self.RARM_SEQ_MAX_K} neighbours per sequence, got k={context.shape[1]}")
+            self._check(lib.rdm_rarm_sample_prefill(self._h, C.byref(a), 1.0 if top_p is None else top_p, _ptr(cond_tokens), _ptr(context),
+                                                    _ptr(uniforms), _ptr(out)))
+        elif top_p is None:
             self._check(lib.rdm_rarm_sample(self._h, C.byref(a), _ptr(cond_tokens), _ptr(context), _ptr(uniforms), _ptr(out)))
         else:
             self._check(lib.rdm_rarm_sample_top_p(self._h, C.byref(a), top_p, _ptr(cond_tokens), _ptr(context), _ptr(uniforms), _ptr(out)))
@@ -1059,6 +1108,36 @@ class Context:
         self._check(lib.rdm_op_small_attention_bwd(self._h, _ptr(q), Cc, _ptr(k), _ptr(v), k.shape[2], _ptr(dout), dout.shape[2], B, nq, m, heads, float(scale),
                                                    _ptr(dq), _ptr(dk), _ptr(dv)))
         return dq, dk, dv
+
+    def op_causal_attention_d64(self, qkv, heads, scale, kcache=None, vcache=None):
+        """Causal self-attention at d_head 64 over all positions: qkv bf16 [B,n,3*heads*64] (q | k | v) -> bf16 [B,n,heads*64].
+        kcache / vcache bf16 [B,heads,L,64]: rows 0..n-1 receive the K / V columns of qkv."""
+        B, n, C3 = qkv.shape
+        assert qkv.is_contiguous() and qkv.dtype == torch.bfloat16 and C3 == 3 * heads * 64
+        if n < 1 or n > 1024:
+            raise RdmError(f"op_causal_attention_d64: 1 <= n <= 1024 required, got {n}")
+        if (kcache is None) != (vcache is None):
+            raise RdmError("op_causal_attention_d64: kcache and vcache come together")
+        L = 0
+        if kcache is not None:
+            L = kcache.shape[2]
+            if tuple(kcache.shape) != (B, heads, L, 64) or kcache.shape != vcache.shape or L < n:
+                raise RdmError(f"op_causal_attention_d64: caches must be [{B},{heads},L>={n},64], got {tuple(kcache.shape)} / {tuple(vcache.shape)}")
+            assert kcache.is_contiguous() and vcache.is_contiguous() and kcache.dtype == vcache.dtype == torch.bfloat16
+        out = torch.empty((B, n, heads * 64), device=self.device, dtype=torch.bfloat16)
+        opt = lambda t: _ptr(t) if t is not None else None
+        self._check(lib.rdm_op_causal_attention_d64(self._h, _ptr(qkv), C3, B, n, heads, float(scale), _ptr(out), heads * 64, opt(kcache), opt(vcache), L))
+        return out
+
+    def op_rarm_nll(self, logits, targets):
+        """logsumexp(logits) - logits[target] per row in fp32: logits f32 [rows,V] (V even), targets int64 [rows] -> f32 [rows]."""
+        logits = self._dev(logits, torch.float32); targets = self._dev(targets, torch.int64)
+        if logits.ndim != 2 or logits.shape[1] % 2 or tuple(targets.shape) != (logits.shape[0],):
+            raise RdmError(f"op_rarm_nll: logits [rows, even V] and targets [rows] required, got {tuple(logits.shape)} / {tuple(targets.shape)}")
+        self._check_ids("op_rarm_nll", targets, logits.shape[1], "targets")
+        out = torch.empty((logits.shape[0],), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_op_rarm_nll(self._h, _ptr(logits), logits.shape[0], logits.shape[1], _ptr(targets), _ptr(out)))
+        return out
 
     def op_small_attention(self, q, k, v, heads, D, causal, scale):
         B, nq, Cc = q.shape

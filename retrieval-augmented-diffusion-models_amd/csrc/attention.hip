@@ -16,6 +16,8 @@
 //    projection GEMM (swapped operands), K/V tiles are L2-resident (<= 64 KB per head).
 // 2) small_attention<D>: generic VALU kernel for short key sequences (cross-attention over the k
 //    retrieved neighbours, n_kv = k <= 16; CLIP n = 77/50 with optional causal mask; odd sizes).
+// 3) causal_d64: causal self-attention, d_head = 64, any n <= 1024, over all query positions (the RARM
+//    transformer's whole-sequence pass); flash_d32's scheme with a causal tile walk, at the end of the file.
 #include "kernels.h"
 
 
@@ -795,5 +797,144 @@ hipError_t launch_small_attention(const SmallAttnParams& p, int D, int heads, in
     if (D == 32) small_attention_kernel<32><<<grid, threads, sm, st>>>(p);
     else if (D == 64) small_attention_kernel<64><<<grid, threads, sm, st>>>(p);
     else return hipErrorInvalidValue;
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------ causal attention, d_head = 64
+// CrossAttention.forward with the causal mask of RetrievalPatchTransformer (rdm/modules/attention.py:42-74, 199-272) over ALL query
+// positions of a sequence: the whole-sequence counterpart of rarm_decode_attention (rarm.hip), which takes one query row per launch.
+// flash_d32_kernel's scheme: one wave owns 32 query rows, S^T = K . Q^T (four 32x32x16 k-steps over d = 64) leaves a lane with 16 scores of
+// ONE query, the softmax statistics are lane-local, P is rounded to bf16 in registers and is the B operand of O^T = V^T . P^T, held as
+// two 32 x 32 accumulators (d 0..31, 32..63).  The same in-tile key permutation makes the 8 scores of a k-step 8 consecutive keys.
+// V is token-major here (a column block of the fused q | k | v projection), so the V^T operand -- 8 consecutive keys of one channel per
+// lane -- is gathered by 2-byte loads (the 32 lanes of a half-wave read 64 contiguous bytes of a row); K and V of a (sequence, head) are
+// <= 128 KB and stay in L2.  Measured at 64 x 256 tokens, shipped size: 49 us per layer, 7.2 % of the pass (DESIGN 3,
+// profiles/rarm_seq_kernel_stats.csv) against under 2 % of its FLOPs -- small enough that the waves of a block share nothing through LDS.
+// Causal: the wave of query tile q0 walks key tiles 0 .. q0 only; the diagonal tile is masked per element (key > query), which also
+// covers the ragged last tile (keys >= n lie above every live query); loads of rows >= n are redirected to row n - 1, stores are
+// guarded.  Key i = query i is always present, so no row ends with an empty softmax.
+// kcache / vcache given: the wave also copies the K and V rows of its 32 positions into the decode step's head-major cache
+// [B][head][L][64] (rarm_step), bit for bit; rows >= n are not touched.
+__global__ __launch_bounds__(256) void causal_d64_kernel(CausalD64Params p) {
+    constexpr int D = 64;
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    const int ntile = (p.n + 31) >> 5;
+    const int tile = ntile - 1 - (blockIdx.x * 4 + wave);      // long rows first
+    if (tile < 0) return;
+    const int q0 = tile * 32;
+    const int h = blockIdx.y, b = blockIdx.z, heads = p.C / D;
+    const int l31 = lane & 31, hf = lane >> 5;
+    const long long tok0 = (long long)b * p.n;
+    const int nlast = p.n - 1;
+    const bf16_t* qb = p.qkv + h * D;
+    const bf16_t* kb = qb + p.C;
+    const bf16_t* vb = qb + 2 * p.C;
+
+    if (p.kcache) {      // rows q0 .. q0+31 of this head: 32 rows x 8 16-byte pieces each for K and V, four of each per lane
+        bf16_t* kc = p.kcache + ((long long)b * heads + h) * p.L * D;
+        bf16_t* vc = p.vcache + ((long long)b * heads + h) * p.L * D;
+#pragma unroll
+        for (int u = 0; u < 4; u++) {
+            const int r = q0 + u * 8 + (lane >> 3), c8 = (lane & 7) * 8;
+            if (r < p.n) {
+                *(bf16x8*)(kc + (long long)r * D + c8) = *(const bf16x8*)(kb + (tok0 + r) * p.ldq + c8);
+                *(bf16x8*)(vc + (long long)r * D + c8) = *(const bf16x8*)(vb + (tok0 + r) * p.ldq + c8);
+            }
+        }
+    }
+
+    // Q as the B operand of S^T = K . Q^T: lane (q = l31) holds d = ks*16 + hf*8 .. +8
+    const int qi = q0 + l31;
+    bf16x8 qf[4];
+    {
+        const bf16_t* qp = qb + (tok0 + (qi < p.n ? qi : nlast)) * p.ldq + hf * 8;
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) qf[ks] = *(const bf16x8*)(qp + ks * 16);
+    }
+    // in-tile key permutation: position l31 holds key pi = l31 with bits 2 and 3 swapped
+    const int pi = (l31 & ~0xc) | ((l31 & 4) << 1) | ((l31 & 8) >> 1);
+
+    f32x16 o0, o1;
+#pragma unroll
+    for (int r = 0; r < 16; r++) { o0[r] = 0.f; o1[r] = 0.f; }
+    float m = -INFINITY, l = 0.f;
+
+    for (int kv0 = 0; kv0 <= q0; kv0 += 32) {
+        const int kr = kv0 + pi;
+        const bf16_t* kp = kb + (tok0 + (kr < p.n ? kr : nlast)) * p.ldq + hf * 8;
+        bf16x8 kf[4];
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) kf[ks] = *(const bf16x8*)(kp + ks * 16);
+        // V^T operand: lane (d = db*32 + l31) holds keys kv0 + ks*16 + hf*8 .. +8 of channel d
+        union { bf16x8 v; unsigned short s[8]; } vf[2][2];
+#pragma unroll
+        for (int ks = 0; ks < 2; ks++) {
+#pragma unroll
+            for (int e = 0; e < 8; e++) {
+                const int j = kv0 + ks * 16 + hf * 8 + e;
+                const unsigned short* vp = (const unsigned short*)(vb + (tok0 + (j < p.n ? j : nlast)) * p.ldq + l31);
+                vf[0][ks].s[e] = vp[0];
+                vf[1][ks].s[e] = vp[32];
+            }
+        }
+        f32x16 s;
+#pragma unroll
+        for (int r = 0; r < 16; r++) s[r] = 0.f;
+#pragma unroll
+        for (int ks = 0; ks < 4; ks++) s = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[ks], qf[ks], s, 0, 0, 0);
+        if (kv0 == q0) {          // the diagonal tile: s[r] is key kv0 + (r < 8 ? hf*8 + r : 16 + hf*8 + r - 8)
+#pragma unroll
+            for (int r = 0; r < 16; r++) {
+                const int j = kv0 + (r < 8 ? hf * 8 + r : 8 + hf * 8 + r);
+                if (j > qi) s[r] = -INFINITY;
+            }
+        }
+        float mx = s[0];
+#pragma unroll
+        for (int r = 1; r < 16; r++) mx = fmaxf(mx, s[r]);
+        mx = fmaxf(mx, __shfl_xor(mx, 32));                 // finite: key kv0 <= q0 <= qi is never masked
+        const float mnew = fmaxf(m, mx * p.scale_log2e);
+        const float alpha = __builtin_amdgcn_exp2f(m - mnew);
+        float ps = 0.f;
+        float pr[16];
+#pragma unroll
+        for (int r = 0; r < 16; r++) { pr[r] = __builtin_amdgcn_exp2f(s[r] * p.scale_log2e - mnew); ps += pr[r]; }
+        l = l * alpha + ps;
+        m = mnew;
+#pragma unroll
+        for (int r = 0; r < 16; r++) { o0[r] *= alpha; o1[r] *= alpha; }
+        union { bf16x8 v; uint32_t u[4]; } pb0, pb1;
+#pragma unroll
+        for (int i = 0; i < 4; i++) {
+            pb0.u[i] = pack2bf(pr[2 * i], pr[2 * i + 1]);
+            pb1.u[i] = pack2bf(pr[8 + 2 * i], pr[8 + 2 * i + 1]);
+        }
+        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[0][0].v, pb0.v, o0, 0, 0, 0);
+        o0 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[0][1].v, pb1.v, o0, 0, 0, 0);
+        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[1][0].v, pb0.v, o1, 0, 0, 0);
+        o1 = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf[1][1].v, pb1.v, o1, 0, 0, 0);
+    }
+    l += __shfl_xor(l, 32);
+    if (qi >= p.n) return;
+    const float inv = 1.f / l;
+    bf16_t* op = p.out + (tok0 + qi) * p.ldo + h * D + 4 * hf;
+#pragma unroll
+    for (int g = 0; g < 4; g++) {
+        uint2 w0, w1;
+        w0.x = pack2bf(o0[g * 4 + 0] * inv, o0[g * 4 + 1] * inv);
+        w0.y = pack2bf(o0[g * 4 + 2] * inv, o0[g * 4 + 3] * inv);
+        w1.x = pack2bf(o1[g * 4 + 0] * inv, o1[g * 4 + 1] * inv);
+        w1.y = pack2bf(o1[g * 4 + 2] * inv, o1[g * 4 + 3] * inv);
+        *(uint2*)(op + 8 * g) = w0;
+        *(uint2*)(op + 32 + 8 * g) = w1;
+    }
+}
+
+hipError_t launch_causal_d64(const CausalD64Params& p, int heads, int batch, hipStream_t st) {
+    if (p.n < 1 || p.n > 1024 || heads < 1 || batch < 1 || batch > 65535 || p.C != heads * 64 || p.ldq % 8 || p.ldq < 3 * p.C || p.ldo % 4 || p.ldo < p.C)
+        return hipErrorInvalidValue;
+    if ((p.kcache != nullptr) != (p.vcache != nullptr) || (p.kcache && p.L < p.n)) return hipErrorInvalidValue;
+    const int ntile = (p.n + 31) / 32;
+    causal_d64_kernel<<<dim3((ntile + 3) / 4, heads, batch), 256, 0, st>>>(p);
     return hipGetLastError();
 }

@@ -64,6 +64,17 @@ struct SmallAttnParams {
     float scale;
 };
 
+// causal self-attention over all query positions, d_head = 64 (attention.hip: causal_d64_kernel); q | k | v are the thirds of the fused
+// projection output, head h in columns h*64 .. h*64+63 of each third
+struct CausalD64Params {
+    const bf16_t* qkv; int ldq;      // q[(b*n + i)*ldq + h*64 + d], k at + C, v at + 2C  (C = heads*64)
+    bf16_t* out; int ldo;            // out[(b*n + i)*ldo + h*64 + d]
+    int n, C;                        // tokens per sequence (any 1 <= n <= 1024), channels
+    float scale_log2e;               // scale * log2(e)
+    bf16_t* kcache; bf16_t* vcache;  // optional (both or neither): head-major decode caches [B][heads][L][64]; rows 0 .. n-1 receive the K / V columns of qkv
+    int L;
+};
+
 struct DdimStepParams {
     const float* x; const float* eps; const float* noise;   // noise may be null (eta == 0)
     float* x_prev; float* pred_x0;                           // pred_x0 may be null
@@ -128,6 +139,10 @@ hipError_t launch_rarm_embed(const long long* tokens, const float* emb, const fl
                              int vocab, hipStream_t st);
 hipError_t launch_rarm_decode_attention(const RarmAttnParams& p, int heads, int batch, hipStream_t st);
 hipError_t launch_rarm_sample(const RarmSampleParams& p, hipStream_t st);
+// whole-sequence pass (rarm.hip): row r of x is position r % t of sequence r / t, whose tokens are row (seq0 + r / t) % tok_rows of tokens [tok_rows][tok_ld]
+hipError_t launch_rarm_embed_seq(const long long* tokens, int tok_ld, int tok_rows, int seq0, const float* emb, const float* pos_t, float* x, long long rows,
+                                 int t, int C, int vocab, hipStream_t st);
+hipError_t launch_rarm_nll(const float* logits, long long rows, int vocab, const long long* targets, float* nll_out, hipStream_t st);
 hipError_t launch_codebook_gather(const long long* idx, const float* codebook, int n_embed, int E, long long n, bf16_t* out, hipStream_t st);
 hipError_t launch_set_int(int* p, int v, hipStream_t st);
 
@@ -190,6 +205,7 @@ hipError_t launch_layernorm(const void* x, int in_is_f32, const float* gamma, co
                             int M, int C, float eps, hipStream_t st, int Clog = -1);   // Clog: logical width of zero-padded rows (statistics over Clog)
 hipError_t launch_flash_d32(const FlashParams& p, int heads, int batch, hipStream_t st);
 hipError_t launch_small_attention(const SmallAttnParams& p, int D, int heads, int batch, hipStream_t st);
+hipError_t launch_causal_d64(const CausalD64Params& p, int heads, int batch, hipStream_t st);
 size_t small_attention_bwd_scratch_bytes(int B, int heads, int nq, int nkv);
 hipError_t launch_small_attention_bwd(const bf16_t* q, int ldq, const bf16_t* k, const bf16_t* v, int ldkv, const bf16_t* dout, int ldo, int B, int nq, int nkv,
                                       int heads, float scale, bf16_t* dq, bf16_t* dk, bf16_t* dv, char* scratch, hipStream_t st);    // backward.hip: d_head 32, nkv <= 32

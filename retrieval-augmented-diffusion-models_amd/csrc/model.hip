@@ -816,6 +816,16 @@ struct Ops {
         check(launch_flash_d32(f, heads, B, c->stream), "flash attention");
         prof_end();
     }
+    // causal self-attention at d_head 64 over all n positions of B sequences (attention.hip): qkv = the fused q | k | v projection rows;
+    // kc / vc: optional head-major decode caches [B][heads][L][64] that receive rows 0 .. n-1
+    void causal_d64(const bf16_t* qkv, int ldq, bf16_t* out, int ldo, int B, int n, int heads, float scale, bf16_t* kc, bf16_t* vc, int L) {
+        if (plan) return;
+        CausalD64Params f{}; f.qkv = qkv; f.ldq = ldq; f.out = out; f.ldo = ldo; f.n = n; f.C = heads * 64;
+        f.scale_log2e = scale * 1.4426950408889634f; f.kcache = kc; f.vcache = vc; f.L = L;
+        prof_begin(RDM_PROF_ATTENTION, 2.0 * B * heads * (double)n * n * 64, B, n, f.C);
+        check(launch_causal_d64(f, heads, B, c->stream), "causal attention");
+        prof_end();
+    }
     // attention over a few keys / short sequences (attention.hip): head dim D, nq queries and nkv keys per sample
     void small_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, bf16_t* out, int ldo, int B, int nq, int nkv,
                          int heads, int D, int causal, float scale, const char* what) {
@@ -1969,14 +1979,17 @@ struct RarmState { int* pos; int* done; long long* tokens; float* logits; };
 static RarmState rarm_state(RarmModel& m, int B2) {
     RarmState st{};
     st.pos = (int*)m.state; st.done = (int*)(m.state + 64); st.tokens = (long long*)(m.state + 256);
+    // (the logits exist only after rarm_prepare(decode = true): the whole-sequence entries size the buffer without them and must not touch st.logits)
     st.logits = (float*)(m.state + 256 + (((size_t)B2 * 8 + 255) & ~(size_t)255));
     return st;
 }
-static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,cd] dev*/, int B, bool cfg) {
+// decode = false: the call runs no decode step (rdm_rarm_forward_seq, rdm_rarm_nll) -- neither the K/V cache, nor the step's logits buffer,
+// nor the re-associated cross-attention operands are made
+static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,cd] dev*/, int B, bool cfg, bool decode = true) {
     RarmModel& m = c->rarm; const rdm_rarm_cfg& g = m.cfg; const int C = m.C, L = g.sequence_length;
-    RDM_TRY(ensure_bytes(c, &m.cache, &m.cache_bytes, (size_t)g.depth * 2 * B2 * L * C * 2));
+    if (decode) RDM_TRY(ensure_bytes(c, &m.cache, &m.cache_bytes, (size_t)g.depth * 2 * B2 * L * C * 2));
     RDM_TRY(ensure_bytes(c, &m.ctxkv, &m.ctxkv_bytes, (size_t)B2 * k * m.kv_total * 2));
-    RDM_TRY(ensure_bytes(c, &m.state, &m.state_bytes, 256 + (((size_t)B2 * 8 + 255) & ~(size_t)255) + (size_t)B2 * g.vocab_out * 4));
+    RDM_TRY(ensure_bytes(c, &m.state, &m.state_bytes, 256 + (((size_t)B2 * 8 + 255) & ~(size_t)255) + (decode ? (size_t)B2 * g.vocab_out * 4 : 0)));      // counters, tokens, the step's logits
     RDM_CHECK_HIP(c, hipMemsetAsync(m.state, 0, 256, c->stream));
     // neighbours' keys / values of every layer in one GEMM; the unconditional half of a guided batch attends to ZERO neighbours
     // (transformer.py:237-239), whose projections are zero (to_k / to_v have no bias)
@@ -1986,7 +1999,7 @@ static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,c
     // (<= 128 sequences); from RARM_XGEMM_FROM sequences on the decode step takes norm2 + to_q as a GEMM, the k-key attention and to_out +
     // residual as a GEMM (same box, profiles/r05_rarm_sweep.log: 256 sequences 399 img/s fused vs 378 as GEMMs, 512 sequences 484 vs 489).
     constexpr int RARM_XGEMM_FROM = 384;
-    const bool fuse = g.n_heads * k <= 128 && C <= 1024 && C % 64 == 0 && (c->deterministic || B2 < RARM_XGEMM_FROM);
+    const bool fuse = decode && g.n_heads * k <= 128 && C <= 1024 && C % 64 == 0 && (c->deterministic || B2 < RARM_XGEMM_FROM);
     m.xa_B = 0; m.xa_k = 0;
     if (fuse) {
         RDM_TRY(ensure_bytes(c, &m.xa, &m.xa_bytes, (size_t)g.depth * 2 * B * 128 * C * 2));
@@ -2098,6 +2111,72 @@ static int rarm_set_tokens(rdm_ctx* c, RarmState& st, const int64_t* tokens, int
     if (dup) RDM_CHECK_HIP(c, hipMemcpy2DAsync(st.tokens + b, 8, tokens + i, (size_t)t * 8, 8, b, hipMemcpyDeviceToDevice, c->stream));
     return 0;
 }
+// ---- the whole-sequence pass: RetrievalPatchTransformer.forward over all t positions of B2 sequences at once (attention.py:252-272),
+// the transformer of rarm_step with t rows per sequence -- tiled GEMMs (single_row stays false: no kernel on this path is chosen by the
+// row count in deterministic mode), the causal d_head-64 kernel over the sequence itself, small_attention over its k neighbour rows of
+// ctxkv (rarm_prepare; the zeroed rows of a guided batch's unconditional half give zero attention output, as in the decode step).
+// Sequences are independent, so they are walked in ranges of whole sequences of at most RARM_SEQ_ROWS rows: that bounds the [rows, 4C]
+// hidden tensor (201 MB at C = 768) whatever b * t is.  What leaves a range:
+//   logits_out  : the head GEMM's rows, [B2, t, V] fp32 (rdm_rarm_forward_seq)
+//   nll_out     : -log softmax(logits)[target] per row; the head GEMM runs in pieces of RARM_NLL_ROWS rows into scratch, [b * t, V] never exists
+//   fill_cache  : the K / V rows of positions 0 .. t-1 into the decode step's cache (rdm_rarm_sample_prefill); no head at all
+// tokens: [tok_rows][tok_ld] int64, sequence s reads row s % tok_rows.
+constexpr int RARM_SEQ_ROWS = 32768;
+constexpr int RARM_NLL_ROWS = 2048;
+static int rarm_seq_body(rdm_ctx* c, const int64_t* tokens, int tok_ld, int tok_rows, int B2, int t, int k, float* logits_out, const int64_t* targets,
+                         float* nll_out, bool fill_cache) {
+    RarmModel& m = c->rarm; const rdm_rarm_cfg& g = m.cfg; const int C = m.C, L = g.sequence_length, V = g.vocab_out;
+    const int per = t >= RARM_SEQ_ROWS ? 1 : RARM_SEQ_ROWS / t;          // sequences per range
+    const int nbmax = B2 < per ? B2 : per;
+    return run_with_arena(c, m.arena, m.blob, [&](Ops& o) {
+        const size_t Mmax = (size_t)nbmax * t;
+        float* x = o.af32(Mmax * C);
+        bf16_t* ln = o.abf(Mmax * C); bf16_t* qkv = o.abf(Mmax * 3 * C); bf16_t* ao = o.abf(Mmax * C);
+        bf16_t* q2 = o.abf(Mmax * C); bf16_t* ff = o.abf(Mmax * 4 * C);
+        float* lg = nll_out ? o.af32((size_t)(Mmax < (size_t)RARM_NLL_ROWS ? Mmax : (size_t)RARM_NLL_ROWS) * V) : nullptr;
+        if (o.plan) return;
+        const float scale = 1.0f / sqrtf((float)g.d_head);
+        for (int s0 = 0; s0 < B2 && o.rc == 0; s0 += per) {
+            const int nb = B2 - s0 < per ? B2 - s0 : per, M = nb * t;
+            o.check(launch_rarm_embed_seq((const long long*)tokens, tok_ld, tok_rows, s0, o.w<float>(m.emb), o.w<float>(m.pos), x, M, t, C, g.vocab_in, c->stream),
+                    "rarm embed");
+            for (int l = 0; l < g.depth; l++) {
+                const RarmBlk& b = m.blk[l];
+                o.layernorm(x, 1, o.w<float>(b.ln1g), o.w<float>(b.ln1b), ln, 0, M, C);
+                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wqkv), nullptr, M, 3 * C, ACT_NONE, nullptr, qkv);
+                bf16_t* kc = fill_cache ? (bf16_t*)m.cache + (((size_t)l * 2) * B2 + s0) * L * C : nullptr;
+                bf16_t* vc = fill_cache ? (bf16_t*)m.cache + (((size_t)l * 2 + 1) * B2 + s0) * L * C : nullptr;
+                o.tag = "rarm.causal_attention";
+                o.causal_d64(qkv, 3 * C, ao, C, nb, t, g.n_heads, scale, kc, vc, L);
+                o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo1), o.w<float>(b.bo1), M, C, ACT_NONE, nullptr, nullptr, x, x);
+                o.layernorm(x, 1, o.w<float>(b.ln2g), o.w<float>(b.ln2b), ln, 0, M, C);
+                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wq2), nullptr, M, C, ACT_NONE, nullptr, q2);
+                const bf16_t* kv = (const bf16_t*)m.ctxkv + (size_t)s0 * k * m.kv_total + (size_t)l * 2 * C;
+                o.small_attention(q2, C, kv, m.kv_total, kv + C, m.kv_total, ao, C, nb, t, k, g.n_heads, g.d_head, 0, scale, "rarm cross attention");
+                o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo2), o.w<float>(b.bo2), M, C, ACT_NONE, nullptr, nullptr, x, x);
+                o.layernorm(x, 1, o.w<float>(b.ln3g), o.w<float>(b.ln3b), ln, 0, M, C);
+                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), M, 8 * C, ACT_GEGLU, nullptr, ff);
+                o.linear(ff, nullptr, 4 * C, 0, o.w<bf16_t>(b.wff2), o.w<float>(b.bff2), M, C, ACT_NONE, nullptr, nullptr, x, x);
+            }
+            if (!logits_out && !nll_out) continue;
+            o.check(launch_cast_f32_bf16(x, ln, (long long)M * C, c->stream), "cast x");
+            const size_t row0 = (size_t)s0 * t;
+            if (logits_out) o.linear(ln, nullptr, C, 0, o.w<bf16_t>(m.wpo), o.w<float>(m.bpo), M, V, ACT_NONE, nullptr, nullptr, logits_out + row0 * V);
+            if (nll_out) {
+                for (int r0 = 0; r0 < M && o.rc == 0; r0 += RARM_NLL_ROWS) {
+                    const int nr = M - r0 < RARM_NLL_ROWS ? M - r0 : RARM_NLL_ROWS;
+                    o.linear(ln + (size_t)r0 * C, nullptr, C, 0, o.w<bf16_t>(m.wpo), o.w<float>(m.bpo), nr, V, ACT_NONE, nullptr, nullptr, lg);
+                    o.check(launch_rarm_nll(lg, nr, V, (const long long*)targets + row0 + r0, nll_out + row0 + r0, c->stream), "rarm nll");
+                }
+            }
+        }
+    });
+}
+static int rarm_seq_check(rdm_ctx* c, int b, int k, int positions) {
+    RDM_TRY(rarm_check(c, b, k, positions));
+    if (k > 128) return c->fail(-1, "the whole-sequence pass attends at most 128 neighbours per sequence, got k=%d", k);
+    return 0;
+}
 long long rdm_rarm_manifest(const rdm_rarm_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) {
     if (!cfg || cfg->depth < 1 || cfg->n_heads < 1) return -1;
     RarmModel m; Manifest mf; build_rarm(m, *cfg, mf);
@@ -2127,8 +2206,29 @@ int rdm_rarm_forward(rdm_ctx* c, const int64_t* tokens, int b, int t, const floa
     }
     return 0;
 }
+int rdm_rarm_forward_seq(rdm_ctx* c, const int64_t* tokens, int b, int t, const float* context, int k, float* logits_out) {
+    RDM_ENTER(c);
+    if (!tokens || !context || !logits_out) return c->fail(-1, "null argument");
+    RDM_TRY(rarm_seq_check(c, b, k, t));
+    RDM_TRY(rarm_prepare(c, b, k, context, b, false, false));
+    return rarm_seq_body(c, tokens, t, b, b, t, k, logits_out, nullptr, nullptr, false);
+}
+int rdm_rarm_nll(rdm_ctx* c, const int64_t* tokens, const int64_t* targets, int b, int t, const float* context, int k, float* nll_out) {
+    RDM_ENTER(c);
+    if (!tokens || !targets || !context || !nll_out) return c->fail(-1, "null argument");
+    RDM_TRY(rarm_seq_check(c, b, k, t));
+    RDM_TRY(rarm_prepare(c, b, k, context, b, false, false));
+    return rarm_seq_body(c, tokens, t, b, b, t, k, nullptr, targets, nll_out, false);
+}
 static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
-                           const float* uniforms, int64_t* tokens_out);
+                           const float* uniforms, int64_t* tokens_out, bool prefill = false);
+int rdm_rarm_sample_prefill(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
+                            const float* uniforms, int64_t* tokens_out) {
+    RDM_ENTER(c);
+    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_rarm_sample_prefill: top_p must lie in (0, 1], got %g", (double)top_p);
+    if (a && a->k > 128) return c->fail(-1, "the whole-sequence pass attends at most 128 neighbours per sequence, got k=%d", a->k);
+    return rarm_sample_run(c, a, top_p, cond_tokens, context, uniforms, tokens_out, true);
+}
 int rdm_rarm_sample(rdm_ctx* c, const rdm_rarm_sample_args* a, const int64_t* cond_tokens, const float* context, const float* uniforms,
                     int64_t* tokens_out) {
     return rarm_sample_run(c, a, 1.0f, cond_tokens, context, uniforms, tokens_out);
@@ -2140,7 +2240,7 @@ int rdm_rarm_sample_top_p(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p
     return rarm_sample_run(c, a, top_p, cond_tokens, context, uniforms, tokens_out);
 }
 static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
-                           const float* uniforms, int64_t* tokens_out) {
+                           const float* uniforms, int64_t* tokens_out, bool prefill) {
     RDM_ENTER(c);
     if (!a || !cond_tokens || !context || !uniforms || !tokens_out) return c->fail(-1, "null argument");
     if (a->cond_len < 1 || a->steps < 1 || a->temperature <= 0.f) return c->fail(-1, "bad sampling arguments");
@@ -2150,7 +2250,12 @@ static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_
     const int B = a->batch, B2 = cfg ? 2 * B : B, k = a->k;
     RDM_TRY(rarm_prepare(c, B2, k, context, B, cfg));
     RarmState st = rarm_state(m, B2);
-    for (int i = 0; i < a->cond_len; i++) {                    // prefill the conditioning tokens (the sos token)
+    int i0 = 0;
+    if (prefill && a->cond_len > 1) {      // positions 0 .. cond_len-2 in one whole-sequence pass that fills the K/V cache; the loop below starts at the last one
+        i0 = a->cond_len - 1;
+        RDM_TRY(rarm_seq_body(c, cond_tokens, a->cond_len, B, B2, i0, k, nullptr, nullptr, nullptr, true));
+    }
+    for (int i = i0; i < a->cond_len; i++) {                   // feed the conditioning tokens (the sos token)
         RDM_TRY(rarm_set_tokens(c, st, cond_tokens, B, a->cond_len, i, cfg));
         RDM_CHECK_HIP(c, launch_set_int(st.pos, i, c->stream));
         if (i + 1 < a->cond_len) RDM_TRY(rarm_step(c, B2, k, i));
@@ -2717,6 +2822,24 @@ int rdm_op_head_conv(rdm_ctx* c, const void* x, const float* gn_gamma, const flo
     RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, head_conv_wp_bytes(C)));
     o.head((const bf16_t*)x, B, H, W, C, C, gn_gamma, gn_beta, gn_eps, w, bias, Cout, out, nullptr, (bf16_t*)c->bwd_tmp);
     return o.rc;
+}
+int rdm_op_causal_attention_d64(rdm_ctx* c, const void* qkv, int ldq, int B, int n, int heads, float scale, void* out, int ldo, void* kcache,
+                                void* vcache, int L) {
+    RDM_ENTER(c);
+    if (!qkv || !out) return c->fail(-1, "rdm_op_causal_attention_d64: null argument");
+    if (B < 1 || n < 1 || n > 1024 || heads < 1) return c->fail(-1, "rdm_op_causal_attention_d64: bad shape B=%d n=%d heads=%d (1 <= n <= 1024)", B, n, heads);
+    if ((kcache != nullptr) != (vcache != nullptr) || (kcache && L < n))
+        return c->fail(-1, "rdm_op_causal_attention_d64: kcache and vcache come together, with L >= n (L=%d, n=%d)", L, n);
+    Ops o = op_exec(c);
+    o.causal_d64((const bf16_t*)qkv, ldq, (bf16_t*)out, ldo, B, n, heads, scale, (bf16_t*)kcache, (bf16_t*)vcache, L);
+    return o.rc;
+}
+int rdm_op_rarm_nll(rdm_ctx* c, const float* logits, long long rows, int vocab, const int64_t* targets, float* nll_out) {
+    RDM_ENTER(c);
+    if (!logits || !targets || !nll_out) return c->fail(-1, "rdm_op_rarm_nll: null argument");
+    if (rows < 1 || vocab < 2 || vocab % 2) return c->fail(-1, "rdm_op_rarm_nll: rows >= 1 and an even vocabulary required (rows=%lld, vocab=%d)", rows, vocab);
+    RDM_CHECK_HIP(c, launch_rarm_nll(logits, rows, vocab, (const long long*)targets, nll_out, c->stream));
+    return 0;
 }
 int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int nq, int nkv,
                            int heads, int D, int causal, float scale, void* out, int ldo) {

@@ -11,6 +11,16 @@
 // of all steps are identical and nothing on the host depends on the step.
 #include "kernels.h"
 
+// Sum of one value per thread over the block of 256 in a FIXED order: xor butterfly inside each wave (every lane ends with the same
+// bits), then (w0 + w1) + (w2 + w3) of the four wave sums.  `slot` is four floats the caller alternates between rounds: one barrier.
+__device__ __forceinline__ float rarm_block_sum_fixed(float v, float* slot, int tid) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
+    if ((tid & 63) == 0) slot[tid >> 6] = v;
+    __syncthreads();
+    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
+}
+
 // ---------------------------------------------------------------- token embedding + positional encoding
 // x[b, :] = proj_in.weight[token[b]] + positional_encoding[:, pos]   (attention.py:252-258), fp32 residual stream
 __global__ __launch_bounds__(256) void rarm_embed_kernel(const long long* tokens, const float* emb, const float* pos_t /*[L][C]*/,
@@ -23,6 +33,64 @@ __global__ __launch_bounds__(256) void rarm_embed_kernel(const long long* tokens
 hipError_t launch_rarm_embed(const long long* tokens, const float* emb, const float* pos_t, const int* pos, float* x, int B, int C,
                              int vocab, hipStream_t st) {
     rarm_embed_kernel<<<B, 256, 0, st>>>(tokens, emb, pos_t, pos, x, B, C, vocab);
+    return hipGetLastError();
+}
+
+// The same for ALL positions of a range of sequences (the whole-sequence pass, model.hip: rarm_seq_body): row r of x is position r % t
+// of sequence r / t.  Token rows wrap at tok_rows: the unconditional half of a guided batch reads the conditional half's tokens.
+__global__ __launch_bounds__(256) void rarm_embed_seq_kernel(const long long* tokens, int tok_ld, int tok_rows, int seq0, const float* emb,
+                                                             const float* pos_t /*[L][C]*/, float* x, int t, int C, int vocab) {
+    const long long r = blockIdx.x;
+    const int s = (int)(r / t), i = (int)(r - (long long)s * t);
+    long long tok = tokens[(long long)((seq0 + s) % tok_rows) * tok_ld + i];
+    if (tok < 0 || tok >= vocab) tok = 0;
+    for (int c = threadIdx.x; c < C; c += blockDim.x) x[r * C + c] = emb[tok * C + c] + pos_t[(long long)i * C + c];
+}
+hipError_t launch_rarm_embed_seq(const long long* tokens, int tok_ld, int tok_rows, int seq0, const float* emb, const float* pos_t, float* x, long long rows,
+                                 int t, int C, int vocab, hipStream_t st) {
+    if (rows < 1 || rows > 0x7fffffffLL || t < 1 || tok_rows < 1) return hipErrorInvalidValue;
+    rarm_embed_seq_kernel<<<(unsigned)rows, 256, 0, st>>>(tokens, tok_ld, tok_rows, seq0, emb, pos_t, x, t, C, vocab);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- token negative log-likelihood from logits
+// nll[r] = logsumexp(logits[r, :]) - logits[r, target[r]]: F.cross_entropy(reduction='none') of LatentImageRETRO.compute_loss
+// (rdm/models/autoregression/transformer.py:62-70), all in fp32.  One block per row, two passes over the row (maximum, then the sum of
+// exponentials; the second pass finds the row in L2).  16-byte loads: V is even, so a row starts 0 or 8 bytes past a 16-byte boundary and
+// the (at most two) elements before the first boundary and after the last are taken one by one.  Fixed order, no atomics: a thread adds
+// its elements in index order, the wave sums by butterfly, the four wave sums are added as (w0 + w1) + (w2 + w3).
+// A target outside [0, V) gives NaN (the callers check the ids first).
+__global__ __launch_bounds__(256) void rarm_nll_kernel(const float* logits, int V, const long long* targets, float* nll_out) {
+    __shared__ float red[8];
+    const long long r = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* row = logits + r * V;
+    int head = (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 2);        // elements before the first 16-byte boundary
+    if (head > V) head = V;
+    const int nv = (V - head) >> 2, tail0 = head + nv * 4;
+    const float4* rv = (const float4*)(row + head);
+    float m = -INFINITY;
+    for (int i = tid; i < nv; i += 256) { const float4 v = rv[i]; m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w)); }
+    if (tid < head) m = fmaxf(m, row[tid]);
+    if (tail0 + tid < V) m = fmaxf(m, row[tail0 + tid]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((tid & 63) == 0) red[tid >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float s = 0.f;
+    for (int i = tid; i < nv; i += 256) { const float4 v = rv[i]; s += (expf(v.x - m) + expf(v.y - m)) + (expf(v.z - m) + expf(v.w - m)); }
+    if (tid < head) s += expf(row[tid] - m);
+    if (tail0 + tid < V) s += expf(row[tail0 + tid] - m);
+    s = rarm_block_sum_fixed(s, red + 4, tid);
+    if (tid == 0) {
+        const long long tg = targets[r];
+        nll_out[r] = (tg >= 0 && tg < V) ? (m + logf(s)) - row[tg] : NAN;
+    }
+}
+hipError_t launch_rarm_nll(const float* logits, long long rows, int vocab, const long long* targets, float* nll_out, hipStream_t st) {
+    if (rows < 1 || rows > 0x7fffffffLL || vocab < 1 || ((uintptr_t)logits & 7)) return hipErrorInvalidValue;
+    rarm_nll_kernel<<<(unsigned)rows, 256, 0, st>>>(logits, vocab, targets, nll_out);
     return hipGetLastError();
 }
 
@@ -370,15 +438,6 @@ hipError_t launch_rarm_xattn_decode(const RarmXattnParams& p, hipStream_t st) {
 // halves), and — last block — advances *pos.
 __device__ __forceinline__ uint32_t f2ord(float f) { const uint32_t u = __float_as_uint(f); return (u & 0x80000000u) ? ~u : (u | 0x80000000u); }
 
-// Sum of one value per thread over the block of 256 in a FIXED order: xor butterfly inside each wave (every lane ends with the same
-// bits), then (w0 + w1) + (w2 + w3) of the four wave sums.  `slot` is four floats the caller alternates between rounds: one barrier.
-__device__ __forceinline__ float rarm_block_sum_fixed(float v, float* slot, int tid) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-    if ((tid & 63) == 0) slot[tid >> 6] = v;
-    __syncthreads();
-    return (slot[0] + slot[1]) + (slot[2] + slot[3]);
-}
 
 // NUCLEUS: the top-p filter after the top-k one (below).  COUNT: p.kept_out[b] receives the number of kept tokens.  Both are
 // compile-time variants: rarm_sample_kernel<false, false>, the top_p == 1 path of every older entry, carries none of their code.

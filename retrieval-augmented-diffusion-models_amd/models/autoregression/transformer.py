@@ -1,19 +1,23 @@
-"""Native counterpart of the SAMPLING methods of rdm/models/autoregression/transformer.py::LatentImageRETRO (RARM):
-`sample` (:224-294), `sampling_util` (:296-312), `sample_from_rdata` (:314-404), `get_qids` (:407-430), `get_r` (:191-205),
+"""Native counterpart of the SAMPLING and VALIDATION methods of rdm/models/autoregression/transformer.py::LatentImageRETRO (RARM):
+`forward` (:213-222), `shared_step` (:207-211), `get_mask_prob` (:186-189), `compute_loss` / `validation_step` (:46-48, :65-70: the
+teacher-forced cross-entropy of an image's codes under its neighbours, one whole-sequence transformer pass), `sample` (:224-294), `sampling_util` (:296-312), `sample_from_rdata` (:314-404), `get_qids` (:407-430), `get_r` (:191-205),
 `log_images` (:422-478: full samples, image completion from the first half of an image's codes, samples under masked neighbours,
 reconstructions), and of the taming Net2NetTransformer pieces it inherits for them (`encode_to_z`, `encode_to_c` with the
 SOSProvider, `decode_to_img`, `top_k_logits`).
-Training, the patch plotter of log_images and image-patch neighbour encoders are out of scope (the shipped
+Training (`training_step`: there is no backward of the transformer), the patch plotter of log_images and image-patch neighbour encoders are out of scope (the shipped
 configs use IdentityEncoder on CLIP embeddings, models/rarm/imagenet/dogs/config.yaml:10-13).
 
 The transformer (rdm.modules.attention.RetrievalPatchTransformer, 18 x 768, causal self-attention + cross-attention to the k
 retrieved neighbours), the VQGAN-f16 decoder and its encoder + nearest-code search run inside librdm_hip; the 256-step loop is ONE library call
 (rdm_rarm_sample) that decodes against a K/V cache — the reference re-runs the whole prefix for every token (:241-248).
+`prefill=True` (sample / sampling_util / log_images / sample_from_rdata) feeds a given prefix in one whole-sequence pass instead of token
+by token (rdm_rarm_sample_prefill); the default stays the token-by-token feed.
 The multinomial draw uses uniforms taken from torch's global generator on the model's device (so `seed_everything`
 makes a run repeatable) and the inverse-CDF rule documented in include/rdm_hip.h.
 """
 import numpy as np
 import torch
+import torch.nn.functional as F
 
 from ... import _lib, packing
 
@@ -118,12 +122,60 @@ class LatentImageRETRO(object):
     def train_searcher(self):
         self.retriever.train_searcher()
 
+    # ---- transformer.py:186-189, 207-222, 46-70: the teacher-forced pass (validation; no backward, so no training_step)
+    def get_mask_prob(self):
+        return np.random.uniform(0., self.p_mask_max)
+
+    def _teacher_tokens(self, x, c):
+        """-> (transformer input [cond | z][:, :-1], target z, cond length): :217-220"""
+        _, z_indices = self.encode_to_z(x.to(self.device))
+        _, cond = self.encode_to_c(c)
+        cond = cond.to(z_indices.device)
+        return torch.cat((cond, z_indices), 1)[:, :-1], z_indices, cond.shape[1]
+
+    @torch.no_grad()
+    def forward(self, x, c, r):
+        """:213-222: logits of every code of x under the neighbours r (one whole-sequence pass) and the codes themselves."""
+        tokens, target, nc = self._teacher_tokens(x, c)
+        logits = self.ctx.rarm_forward_seq(tokens, r)
+        return logits[:, nc - 1:], target
+
+    __call__ = forward
+
+    @torch.no_grad()
+    def nll(self, x, r):
+        """-log p(code) per token, f32 [b, h*w]: cross_entropy(reduction='none') of `forward`, without its [b, h*w, vocab] logits."""
+        tokens, target, nc = self._teacher_tokens(x, torch.zeros((x.shape[0], 0)))
+        assert nc == 1                                                      # the SOS provider: one conditioning token (encode_to_c)
+        return self.ctx.rarm_nll(tokens, target, r)
+
+    def shared_step(self, batch, batch_idx):
+        x, c = self.get_xc(batch)
+        r = self.get_r(batch, p_mask=self.get_mask_prob())
+        return self.forward(x, c, r)
+
+    def compute_loss(self, logits, targets, split="train"):
+        loss = F.cross_entropy(logits.reshape(-1, logits.size(-1)), targets.reshape(-1))
+        return loss, {f"{split}/loss": loss.detach()}
+
+    @torch.no_grad()
+    def validation_step(self, batch, batch_idx):
+        """:65-70 -> {"val/loss": mean NLL}; through rdm_rarm_nll, so no [b, 256, 16384] logits tensor is formed."""
+        x, c = self.get_xc(batch)
+        r = self.get_r(batch, p_mask=self.get_mask_prob())
+        return {"val/loss": self.nll(x, r).mean()}
+
+    def training_step(self, batch, batch_idx):
+        raise NotImplementedError("LatentImageRETRO.training_step: the RARM transformer has no native backward pass (validation_step, nll and "
+                                  "forward are available)")
+
     # ---- transformer.py:224-294
     @torch.no_grad()
     def sample(self, x, r, c, steps, temperature=1.0, sample=False, top_k=None, guidance_scale=1.0, callback=lambda k: None,
-               uniforms=None, top_p=None, **kwargs):
+               uniforms=None, top_p=None, prefill=None, **kwargs):
         """`top_p` (:279-280 names it and asserts it away): the nucleus filter after top-k, in (0, 1]; None and 1.0 are the call
-        without one.  With sample=False (arg-max) it has no effect, as top_k has none."""
+        without one.  With sample=False (arg-max) it has no effect, as top_k has none.
+        `prefill`: feed [c | x] in one whole-sequence pass (rdm_rarm_sample_prefill) instead of token by token; None / False: token by token."""
         top_p = _lib.check_top_p("LatentImageRETRO.sample", top_p)
         x = torch.cat((c.to(self.device), x.to(self.device)), 1)           # conditioning tokens, then any given prefix
         for k_ in range(steps):
@@ -132,10 +184,12 @@ class LatentImageRETRO(object):
             uniforms = torch.rand((steps, x.shape[0]), device=self.device)
         if not sample:
             top_k, top_p = 1, None                                          # torch.topk(probs, 1): the arg-max token (:266-267)
-        if top_p is None:
-            new = self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale)
-        else:
-            new = self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale, top_p=top_p)
+        extra = {}
+        if top_p is not None:
+            extra["top_p"] = top_p
+        if prefill:
+            extra["prefill"] = True
+        new = self.ctx.rarm_sample(x, r, steps, uniforms, temperature=temperature, top_k=top_k, guidance_scale=guidance_scale, **extra)
         if x.shape[1] == c.shape[1]:
             return new
         return torch.cat((x[:, c.shape[1]:].to(torch.int64), new), 1)      # the given prefix, then the new tokens (:268-269)
@@ -194,18 +248,18 @@ class LatentImageRETRO(object):
         n = z_indices.shape[1]
         if sample:
             log["samples_full"] = self.sampling_util(n, z_indices[:, :0], r, c_indices, zshape=quant_z.shape, temperature=temperature,
-                                                     top_k=top_k, top_p=top_p, callback=callback)
+                                                     top_k=top_k, top_p=top_p, callback=callback, **kwargs)
         if half_sample:
             z_start_indices = z_indices[:, :n // 2]
             log["samples_half"] = self.sampling_util(n - z_start_indices.shape[1], z_start_indices, r, c_indices, temperature=temperature,
-                                                     top_k=top_k, top_p=top_p, callback=callback, zshape=quant_z.shape)
+                                                     top_k=top_k, top_p=top_p, callback=callback, zshape=quant_z.shape, **kwargs)
         if p_sample:
             if masking_probs[0] >= self.p_mask_max and self.p_mask_max != 0.:
                 masking_probs = [self.p_mask_max] + masking_probs
             for p_mask in masking_probs:
                 r = self.get_r(batch, N, p_mask=p_mask).to(device=self.device)
                 log[f"samples_full_p_{p_mask:.2f}"] = self.sampling_util(n, z_indices[:, :0], r, c_indices, zshape=quant_z.shape,
-                                                                         temperature=temperature, top_k=top_k, top_p=top_p, callback=callback)
+                                                                         temperature=temperature, top_k=top_k, top_p=top_p, callback=callback, **kwargs)
         log["inputs"] = x
         log["reconstructions"] = self.decode_to_img(z_indices, quant_z.shape)
         return log

@@ -12,6 +12,10 @@ every image of PATH (a file or a directory) is centre-cropped, resized to the fi
 first R code rows (default: half the grid) are kept and the rest is sampled with the flags above; neighbours come from the image's own
 CLIP embedding unless -c / --only_caption / --unconditional say otherwise.  Writes `{start}-samples_half-run{n}-sample{i}.png` and
 `{start}-reconstructions-run{n}-sample{i}.png`.
+--prefill (with --complete_from only): the kept codes are fed to the transformer in one whole-sequence pass instead of token by token.
+--score PATH: no sampling -- every image of PATH is encoded, its neighbours retrieved as --complete_from does, and its teacher-forced
+negative log-likelihood under them (LatentImageRETRO.validation_step, transformer.py:65-70) is printed: one line per image with the mean
+in nats and bits per code, then the mean over all images as the reference's `val/loss`.
 """
 import argparse
 import datetime
@@ -56,6 +60,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--complete_from", type=Path, default=None,
                         help="[native] image file or directory: keep the first code rows of each image and sample the rest")
     parser.add_argument("--keep_rows", type=int, default=None, help="[native] code rows kept by --complete_from (default: half the grid)")
+    parser.add_argument("--prefill", default=False, action="store_true",
+                        help="[native] feed the codes kept by --complete_from in one whole-sequence pass instead of token by token")
+    parser.add_argument("--score", type=Path, default=None,
+                        help="[native] image file or directory: print each image's mean negative log-likelihood per code, sample nothing")
     return parser
 
 
@@ -63,6 +71,8 @@ def parse_args(argv=None) -> argparse.Namespace:
     opt = build_parser().parse_args(argv)
     if opt.top_m > 1.0:
         opt.top_m = int(opt.top_m)
+    if opt.prefill and opt.complete_from is None:
+        print("Warning: --prefill only has an effect with --complete_from")
     if opt.seed is not None and (not opt.increase_guidance) and opt.n_runs > 1:
         print("Warning: You will get the same images each run")
     return opt
@@ -85,7 +95,7 @@ def load_model(opt):
                                  nn_memory=np.arange(min(10_000, opt.synthetic_db_rows)))
         model.load_transformer_state_dict(synthetic.rarm_state_dict(model.rarm_cfg))
         fsd = synthetic.vq_state_dict(model.vq_cfg, synthetic.VQGAN_SEED)
-        if opt.complete_from is not None:
+        if opt.complete_from is not None or opt.score is not None:
             fsd.update(synthetic.vq_encoder_state_dict(model.vq_cfg))
         model.load_first_stage_state_dict(fsd)
         n = opt.synthetic_db_rows
@@ -129,7 +139,7 @@ def load_images(path, resolution):
     path = Path(path)
     files = sorted(f for f in path.iterdir() if f.suffix.lower() in IMAGE_SUFFIXES) if path.is_dir() else [path]
     if not files:
-        raise SystemExit(f"--complete_from: no image found at {path}")
+        raise SystemExit(f"no image found at {path}")
     out = []
     for f in files:
         im = Image.open(f).convert("RGB")
@@ -141,11 +151,30 @@ def load_images(path, resolution):
     return torch.stack(out)
 
 
+def neighbours_of(model, opt, x):
+    """The neighbour embeddings [bs,k,512] of an image batch: by its own CLIP embedding, or as -c / --only_caption / --unconditional say."""
+    import torch
+    from rdm_amd.modules.custom_clip.tokenizer import tokenize
+    bs = x.shape[0]
+    if opt.unconditional:
+        return torch.zeros((bs, 1, 512), dtype=torch.float, device=model.device)
+    if opt.caption != "":
+        q = model.retriever.retriever.model.encode_text(torch.from_numpy(tokenize([opt.caption] * bs)))
+    else:
+        q = model.retriever.retriever(x)                     # the image's own CLIP embedding
+    q = q.float()
+    if opt.only_caption:
+        assert opt.caption != "", "Need a caption"
+        return q.unsqueeze(1).to(model.device)
+    qe = q.cpu().numpy().astype(np.float32)
+    nns, _ = model.retriever.searcher.search_batched(qe / np.linalg.norm(qe, axis=1)[:, np.newaxis], final_num_neighbors=opt.k_nn)
+    return torch.from_numpy(np.asarray(model.retriever.data_pool["embedding"][nns])).to(model.device).to(torch.float)
+
+
 def complete(model, opt):
     """[native] --complete_from: the `samples_half` / `reconstructions` entries of LatentImageRETRO.log_images (transformer.py:448-479) with
     a selectable split row, batch by batch over the given images."""
     import torch
-    from rdm_amd.modules.custom_clip.tokenizer import tokenize
     sampling_start = datetime.datetime.now().strftime("%Y-%m-%d-%H-%M-%S")
     cfg = model.vq_cfg
     side = cfg.resolution >> (cfg.n_ch_mult - 1)
@@ -162,26 +191,13 @@ def complete(model, opt):
         for b0 in range(0, images.shape[0], opt.batch_size):
             x = images[b0:b0 + opt.batch_size].to(model.device)
             bs = x.shape[0]
-            if opt.unconditional:
-                r = torch.zeros((bs, 1, 512), dtype=torch.float, device=model.device)
-            else:
-                if opt.caption != "":
-                    q = model.retriever.retriever.model.encode_text(torch.from_numpy(tokenize([opt.caption] * bs)))
-                else:
-                    q = model.retriever.retriever(x)                     # the image's own CLIP embedding
-                q = q.float()
-                if opt.only_caption:
-                    assert opt.caption != "", "Need a caption"
-                    r = q.unsqueeze(1).to(model.device)
-                else:
-                    qe = q.cpu().numpy().astype(np.float32)
-                    nns, _ = model.retriever.searcher.search_batched(qe / np.linalg.norm(qe, axis=1)[:, np.newaxis], final_num_neighbors=opt.k_nn)
-                    r = torch.from_numpy(np.asarray(model.retriever.data_pool["embedding"][nns])).to(model.device).to(torch.float)
+            r = neighbours_of(model, opt, x)
             quant_z, z_indices = model.encode_to_z(x)
             _, c_indices = model.encode_to_c(torch.zeros((bs, 0)))
             z_start = z_indices[:, :keep * side]
             logs = {"samples_half": model.sampling_util(z_indices.shape[1] - z_start.shape[1], z_start, r, c_indices, opt.temperature, opt.top_k,
-                                                        quant_z.shape, top_p=opt.top_p, guidance_scale=opt.guidance_scale),
+                                                        quant_z.shape, top_p=opt.top_p, guidance_scale=opt.guidance_scale,
+                                                        prefill=opt.prefill),
                     "reconstructions": model.decode_to_img(z_indices, quant_z.shape)}
             for key, imgs in logs.items():
                 for bi, be in enumerate(imgs):
@@ -193,8 +209,31 @@ def complete(model, opt):
     return sampling_start
 
 
+def score(model, opt):
+    """[native] --score: LatentImageRETRO.validation_step (transformer.py:65-70) image by image -> the per-token NLL tensor [n, codes]."""
+    import torch
+    images = load_images(opt.score, model.vq_cfg.resolution)
+    if model.retriever is not None and model.retriever.searcher is None:
+        model.train_searcher()
+    if opt.seed is not None:
+        seed_everything(opt.seed)
+    rows = []
+    for b0 in range(0, images.shape[0], opt.batch_size):
+        x = images[b0:b0 + opt.batch_size].to(model.device)
+        nll = model.nll(x, neighbours_of(model, opt, x)).cpu()
+        for bi, row in enumerate(nll):
+            m = float(row.mean())
+            print(f"image {b0 + bi}: nll {m:.4f} nats/code, {m / np.log(2.0):.4f} bits/code")
+        rows.append(nll)
+    nll = torch.cat(rows)
+    print(f"val/loss {float(nll.mean()):.4f}")
+    return nll
+
+
 def sample(model, opt):
     """rarm_sample.py:225-293."""
+    if opt.score is not None:
+        return score(model, opt)
     if getattr(opt, "complete_from", None) is not None:
         return complete(model, opt)
     import torch
