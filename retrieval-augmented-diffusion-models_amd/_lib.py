@@ -274,8 +274,8 @@ def make_clip_cfg(embed_dim=512, image_resolution=224, vision_layers=12, vision_
     return c
 
 
-def manifest(kind: str, cfg):
-    """-> (list of (offset, nbytes, kind, [src...]), blob_bytes)"""
+def manifest_text(kind: str, cfg):
+    """-> (the manifest as the library writes it: one "offset nbytes kind src,src,..." line per entry, blob_bytes)"""
     fn = {"unet": lib.rdm_unet_manifest, "vq": lib.rdm_vq_manifest, "vqenc": lib.rdm_vqenc_manifest, "clip": lib.rdm_clip_manifest,
           "rarm": lib.rdm_rarm_manifest}[kind]
     blob = C.c_size_t(0)
@@ -284,11 +284,17 @@ def manifest(kind: str, cfg):
         raise ValueError(f"unsupported {kind} config")
     buf = C.create_string_buffer(int(n) + 1)
     fn(C.byref(cfg), buf, int(n) + 1, C.byref(blob))
+    return buf.value.decode(), int(blob.value)
+
+
+def manifest(kind: str, cfg):
+    """-> (list of (offset, nbytes, kind, [src...]), blob_bytes)"""
+    text, blob_bytes = manifest_text(kind, cfg)
     out = []
-    for line in buf.value.decode().splitlines():
+    for line in text.splitlines():
         off, nb, kd, srcs = line.split(" ")
         out.append((int(off), int(nb), kd, srcs.split(",")))
-    return out, int(blob.value)
+    return out, blob_bytes
 
 
 class RdmError(RuntimeError):

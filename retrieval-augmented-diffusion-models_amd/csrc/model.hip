@@ -63,6 +63,10 @@ struct Manifest {
         total += nbytes;
         return off;
     }
+    // the unpadded kinds every builder uses, by element count
+    size_t f32(const std::string& n, size_t numel) { return add("f32", n, numel * 4); }
+    size_t bf16(const std::string& n, size_t numel) { return add("bf16", n, numel * 2); }
+    size_t conv3(const std::string& n, size_t cout, size_t cin) { return add("conv3", n, cout * cin * 9 * 2); }      // bf16 [cout][3][3][cin]
 };
 
 // ------------------------------------------------------------------------------------ arena
@@ -76,6 +80,15 @@ struct Arena {
         if (off > peak) peak = off;
         return p;
     }
+};
+
+// ------------------------------------------------------------------------------------ what every model owns
+template <typename T> static void free_dev(T*& p, size_t& bytes) { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
+// A model is a description (cfg, layer graph, blob offsets: filled by its build_* function, which allocates nothing) plus the
+// device memory behind it.  A description without memory may be copied (load_model builds one aside and assigns it).
+struct ModelBase {
+    char* blob = nullptr; size_t blob_bytes = 0; Arena arena; bool loaded = false;
+    void release() { free_dev(blob, blob_bytes); free_dev(arena.base, arena.cap); loaded = false; }      // (the caller has synchronised)
 };
 
 // ------------------------------------------------------------------------------------ UNet description
@@ -109,26 +122,22 @@ struct ConvW { int c; size_t w, b; int lc; };
 struct ULayer { int kind; int idx; };            // 0 conv_in, 1 res, 2 st, 3 down, 4 up
 struct UBlock { int where; std::vector<ULayer> layers; };   // where: 0 input, 1 middle, 2 output
 
-struct UNet {
+struct UNet : ModelBase {
     rdm_unet_cfg cfg{};
-    bool loaded = false;
     std::vector<UBlock> blocks; std::vector<ResW> res; std::vector<StW> st; std::vector<ConvW> down, up;
     size_t te0w, te0b, te2w, te2b, embw, embb, kvw, cinw, cinb, outg, outb, outw, outbias;
     int emb_total = 0, kv_total = 0; long long xa_total = 0;         // xa_total: per-sample elements of all (G, U) pairs
     bf16_t* xa_cache = nullptr; size_t xa_cache_bytes = 0;
-    char* blob = nullptr; size_t blob_bytes = 0;
-    Arena arena;
     // cached cross-attention K/V for the current conditioning
     bf16_t* kv_cache = nullptr; size_t kv_cache_bytes = 0;
     float* emb_table = nullptr; size_t emb_table_bytes = 0;      // rdm_ddim_sample: one row of emb_total floats per sampler timestep
     int ctx_rows = 0;            // samples [ctx_rows, B') of the cached conditioning have ALL-ZERO neighbours (the unconditional half of
                                  // a guided batch): their cross-attention is the output bias, no GEMM runs for them
+    void release() { free_dev(xa_cache, xa_cache_bytes); free_dev(kv_cache, kv_cache_bytes); free_dev(emb_table, emb_table_bytes); ModelBase::release(); }
 };
 
-static std::string key(const std::string& pre, const char* s) { return pre + s; }
-
 static void build_unet(UNet& u, const rdm_unet_cfg& c, Manifest& mf) {
-    u.cfg = c; u.blocks.clear(); u.res.clear(); u.st.clear(); u.down.clear(); u.up.clear();
+    u.cfg = c;
     const int mc = c.model_channels, ted = mc * 4, mcp = pad64(mc);       // ted = 4 mc: a multiple of 64 whenever mc % 32 == 0... (128-aligned)
     // vec: fp32 vector(s) over channel segments; mat: bf16 [rows][cols]; both padded per segment
     auto vec = [&](const std::string& n, std::initializer_list<Seg> segs) {
@@ -259,195 +268,164 @@ static void build_unet(UNet& u, const rdm_unet_cfg& c, Manifest& mf) {
     u.kvw = mf.add(std::string("bf16") + (kv_padded ? "|R=" + kv_rspec : ""), kv_srcs, (size_t)u.kv_total * c.context_dim * 2);
 }
 
-// ------------------------------------------------------------------------------------ VQ decoder description
+// ------------------------------------------------------------------------------------ first-stage description (decoder and encoder)
+// ldm / taming Decoder and Encoder are built from the same pieces: ResnetBlocks (+ one AttnBlock per block at attn_resolutions) per
+// level, a resampling conv between levels, and a res - attn - res middle.
 struct VqRes { int cin, cout; size_t n1g, n1b, w1, b1, n2g, n2b, w2, b2, wsk, bsk; bool skip; };
 struct VqAttn { int c; size_t ng, nb, wq, bq, wk, bk, wv, bv, wo, bo; };
-struct VqModel {
-    rdm_vq_cfg cfg{}; bool loaded = false;
+struct VqLevel {
+    std::vector<VqRes> blocks;
+    std::vector<VqAttn> attn;          // one per block, or none
+    ConvW resample{};                  // the level's Upsample / stride-2 Downsample conv (the last level walked has none)
+};
+struct VqMid { VqRes res1, res2; VqAttn attn; bool has_attn; };
+
+static VqRes add_vq_res(Manifest& mf, const std::string& pre, int cin, int cout) {
+    VqRes r{}; r.cin = cin; r.cout = cout; r.skip = cin != cout;
+    r.n1g = mf.f32(pre + ".norm1.weight", cin); r.n1b = mf.f32(pre + ".norm1.bias", cin);
+    r.w1 = mf.conv3(pre + ".conv1.weight", cout, cin); r.b1 = mf.f32(pre + ".conv1.bias", cout);
+    r.n2g = mf.f32(pre + ".norm2.weight", cout); r.n2b = mf.f32(pre + ".norm2.bias", cout);
+    r.w2 = mf.conv3(pre + ".conv2.weight", cout, cout); r.b2 = mf.f32(pre + ".conv2.bias", cout);
+    if (r.skip) { r.wsk = mf.bf16(pre + ".nin_shortcut.weight", (size_t)cout * cin); r.bsk = mf.f32(pre + ".nin_shortcut.bias", cout); }
+    return r;
+}
+static VqAttn add_vq_attn(Manifest& mf, const std::string& p, int ch) {
+    VqAttn a{}; a.c = ch;
+    a.ng = mf.f32(p + ".norm.weight", ch); a.nb = mf.f32(p + ".norm.bias", ch);
+    a.wq = mf.bf16(p + ".q.weight", (size_t)ch * ch); a.bq = mf.f32(p + ".q.bias", ch);
+    a.wk = mf.bf16(p + ".k.weight", (size_t)ch * ch); a.bk = mf.f32(p + ".k.bias", ch);
+    a.wv = mf.bf16(p + ".v.weight", (size_t)ch * ch); a.bv = mf.f32(p + ".v.bias", ch);
+    a.wo = mf.bf16(p + ".proj_out.weight", (size_t)ch * ch); a.bo = mf.f32(p + ".proj_out.bias", ch);
+    return a;
+}
+// pre: "decoder.mid" / "encoder.mid"
+static VqMid add_vq_mid(Manifest& mf, const std::string& pre, int ch, bool attn) {
+    VqMid m{}; m.has_attn = attn;
+    m.res1 = add_vq_res(mf, pre + ".block_1", ch, ch);
+    if (attn) m.attn = add_vq_attn(mf, pre + ".attn_1", ch);
+    m.res2 = add_vq_res(mf, pre + ".block_2", ch, ch);
+    return m;
+}
+// pre: "decoder.up.<lvl>" / "encoder.down.<lvl>"; n_blocks ResnetBlocks ch -> bout (AttnBlocks behind them when the level's resolution
+// `res` is in attn_resolutions), then the conv of `resample` ("upsample" / "downsample"; null: none).  ch leaves as the level's width.
+static VqLevel add_vq_level(Manifest& mf, const rdm_vq_cfg& c, const std::string& pre, int n_blocks, int& ch, int bout, int res, const char* resample) {
+    VqLevel L;
+    bool at = false;
+    for (int i = 0; i < c.n_attn_resolutions; i++) at = at || c.attn_resolutions[i] == res;
+    for (int i = 0; i < n_blocks; i++) {
+        L.blocks.push_back(add_vq_res(mf, pre + ".block." + std::to_string(i), ch, bout)); ch = bout;
+        if (at) L.attn.push_back(add_vq_attn(mf, pre + ".attn." + std::to_string(i), ch));
+    }
+    if (resample) {
+        const std::string p = pre + "." + resample + ".conv";
+        L.resample.c = ch; L.resample.w = mf.conv3(p + ".weight", ch, ch); L.resample.b = mf.f32(p + ".bias", ch);
+    }
+    return L;
+}
+
+struct VqModel : ModelBase {
+    rdm_vq_cfg cfg{};
     bool wide = false;                             // z_channels > 4 (taming VQGAN-f16: 256): latent handled as bf16 NHWC tokens, GEMM-class
                                                    // post_quant_conv / conv_in; else the 3-channel VQ-f4 path (tiny fp32 stem kernels)
     size_t codebook, pqw, pqb, cinw, cinb, noutg, noutb, coutw, coutb;
-    VqRes mid1, mid2; VqAttn attn;
-    std::vector<std::vector<VqRes>> up_blocks;     // indexed by level
-    std::vector<std::vector<VqAttn>> up_attn;      // indexed by level: one AttnBlock per res block when the level's resolution is in attn_resolutions
-    std::vector<ConvW> upsample;                   // indexed by level (level 0 unused)
-    char* blob = nullptr; size_t blob_bytes = 0; Arena arena;
+    VqMid mid;
+    std::vector<VqLevel> levels;                   // indexed by level (walked high to low; level 0 has no upsample)
+    float* code_norms = nullptr;                   // |e_j|^2 of the codebook (vqcode.hip), made on first use by rdm_vq_encode_indices
+    void release() { if (code_norms) (void)hipFree(code_norms); code_norms = nullptr; ModelBase::release(); }
 };
 
 static void build_vq(VqModel& v, const rdm_vq_cfg& c, Manifest& mf) {
     v.cfg = c;
-    auto f32 = [&](const std::string& n, size_t numel) { return mf.add("f32", n, numel * 4); };
-    auto bf = [&](const std::string& n, size_t numel) { return mf.add("bf16", n, numel * 2); };
-    auto add_res = [&](const std::string& pre, int cin, int cout) {
-        VqRes r{}; r.cin = cin; r.cout = cout; r.skip = cin != cout;
-        r.n1g = f32(pre + ".norm1.weight", cin); r.n1b = f32(pre + ".norm1.bias", cin);
-        r.w1 = mf.add("conv3", pre + ".conv1.weight", (size_t)cout * cin * 9 * 2); r.b1 = f32(pre + ".conv1.bias", cout);
-        r.n2g = f32(pre + ".norm2.weight", cout); r.n2b = f32(pre + ".norm2.bias", cout);
-        r.w2 = mf.add("conv3", pre + ".conv2.weight", (size_t)cout * cout * 9 * 2); r.b2 = f32(pre + ".conv2.bias", cout);
-        if (r.skip) { r.wsk = bf(pre + ".nin_shortcut.weight", (size_t)cout * cin); r.bsk = f32(pre + ".nin_shortcut.bias", cout); }
-        return r;
-    };
-    auto add_attn = [&](const std::string& p, int ch) {
-        VqAttn a{}; a.c = ch;
-        a.ng = f32(p + ".norm.weight", ch); a.nb = f32(p + ".norm.bias", ch);
-        a.wq = bf(p + ".q.weight", (size_t)ch * ch); a.bq = f32(p + ".q.bias", ch);
-        a.wk = bf(p + ".k.weight", (size_t)ch * ch); a.bk = f32(p + ".k.bias", ch);
-        a.wv = bf(p + ".v.weight", (size_t)ch * ch); a.bv = f32(p + ".v.bias", ch);
-        a.wo = bf(p + ".proj_out.weight", (size_t)ch * ch); a.bo = f32(p + ".proj_out.bias", ch);
-        return a;
-    };
     v.wide = c.z_channels > 4;
-    if (!c.kl) v.codebook = f32("quantize.embedding.weight", (size_t)c.n_embed * c.embed_dim);
+    if (!c.kl) v.codebook = mf.f32("quantize.embedding.weight", (size_t)c.n_embed * c.embed_dim);
     int bin = c.ch * c.ch_mult[c.n_ch_mult - 1];
-    if (v.wide) {
-        v.pqw = bf("post_quant_conv.weight", (size_t)c.z_channels * c.embed_dim); v.pqb = f32("post_quant_conv.bias", c.z_channels);
-        v.cinw = mf.add("conv3", "decoder.conv_in.weight", (size_t)bin * c.z_channels * 9 * 2); v.cinb = f32("decoder.conv_in.bias", bin);
-    } else {
-        v.pqw = f32("post_quant_conv.weight", (size_t)c.z_channels * c.embed_dim); v.pqb = f32("post_quant_conv.bias", c.z_channels);
-        v.cinw = f32("decoder.conv_in.weight", (size_t)bin * c.z_channels * 9); v.cinb = f32("decoder.conv_in.bias", bin);
-    }
-    v.mid1 = add_res("decoder.mid.block_1", bin, bin);
-    if (c.mid_attn) v.attn = add_attn("decoder.mid.attn_1", bin);
-    v.mid2 = add_res("decoder.mid.block_2", bin, bin);
-    v.up_blocks.assign(c.n_ch_mult, {}); v.upsample.assign(c.n_ch_mult, ConvW{}); v.up_attn.assign(c.n_ch_mult, {});
+    const size_t pq = (size_t)c.z_channels * c.embed_dim;      // wide: post_quant_conv a bf16 GEMM operand, conv_in a conv3 entry; else fp32 for the stem kernels
+    v.pqw = v.wide ? mf.bf16("post_quant_conv.weight", pq) : mf.f32("post_quant_conv.weight", pq); v.pqb = mf.f32("post_quant_conv.bias", c.z_channels);
+    v.cinw = v.wide ? mf.conv3("decoder.conv_in.weight", bin, c.z_channels) : mf.f32("decoder.conv_in.weight", (size_t)bin * c.z_channels * 9);
+    v.cinb = mf.f32("decoder.conv_in.bias", bin);
+    v.mid = add_vq_mid(mf, "decoder.mid", bin, c.mid_attn);
+    v.levels.assign(c.n_ch_mult, {});
     int curr_res = c.resolution >> (c.n_ch_mult - 1);
-    for (int lvl = c.n_ch_mult - 1; lvl >= 0; lvl--) {
-        const int bout = c.ch * c.ch_mult[lvl];
-        bool at = false;
-        for (int i = 0; i < c.n_attn_resolutions; i++) at = at || c.attn_resolutions[i] == curr_res;
-        for (int i = 0; i <= c.num_res_blocks; i++) {
-            char pre[64]; snprintf(pre, sizeof pre, "decoder.up.%d.block.%d", lvl, i);
-            v.up_blocks[lvl].push_back(add_res(pre, bin, bout)); bin = bout;
-            if (at) { snprintf(pre, sizeof pre, "decoder.up.%d.attn.%d", lvl, i); v.up_attn[lvl].push_back(add_attn(pre, bin)); }
-        }
-        if (lvl != 0) {
-            char pre[64]; snprintf(pre, sizeof pre, "decoder.up.%d.upsample.conv", lvl);
-            ConvW u{}; u.c = bin; u.w = mf.add("conv3", std::string(pre) + ".weight", (size_t)bin * bin * 9 * 2);
-            u.b = f32(std::string(pre) + ".bias", bin); v.upsample[lvl] = u;
-            curr_res *= 2;
-        }
-    }
-    v.noutg = f32("decoder.norm_out.weight", bin); v.noutb = f32("decoder.norm_out.bias", bin);
-    v.coutw = f32("decoder.conv_out.weight", (size_t)c.out_ch * bin * 9); v.coutb = f32("decoder.conv_out.bias", c.out_ch);
+    for (int lvl = c.n_ch_mult - 1; lvl >= 0; lvl--, curr_res *= 2)
+        v.levels[lvl] = add_vq_level(mf, c, "decoder.up." + std::to_string(lvl), c.num_res_blocks + 1, bin, c.ch * c.ch_mult[lvl], curr_res, lvl ? "upsample" : nullptr);
+    v.noutg = mf.f32("decoder.norm_out.weight", bin); v.noutb = mf.f32("decoder.norm_out.bias", bin);
+    v.coutw = mf.f32("decoder.conv_out.weight", (size_t)c.out_ch * bin * 9); v.coutb = mf.f32("decoder.conv_out.bias", c.out_ch);
 }
 
-// ------------------------------------------------------------------------------------ first-stage ENCODER description (VQ-f4: training input; VQGAN-f16: image -> codes)
+// First-stage ENCODER (VQ-f4: training input; VQGAN-f16: image -> codes).
 // ldm Encoder (ldm/modules/diffusionmodules/model.py; un-vendored: restated from the published code, parity unpinned) as reached from
 // MinimalRETRODiffusion.get_input -> encode_first_stage -> VQModelInterface.encode = quant_conv(encoder(x)) under torch.no_grad()
 // (rdm/models/diffusion/ddpm.py:390-391): conv_in, per level num_res_blocks ResnetBlocks (+ AttnBlocks at attn_resolutions) and a
 // stride-2 Downsample conv with (0, 1, 0, 1) zero padding, mid res-attn-res, GroupNorm + swish + conv_out, quant_conv (1x1).
 // The taming VQGAN-f16 encoder (wide latent; un-vendored, parity unpinned) is the same graph: only the tail's weights are stored otherwise
 // (conv_out as conv3 bf16, quant_conv as a bf16 GEMM operand: vqenc_body).
-struct VqEncModel {
-    rdm_vq_cfg cfg{}; bool loaded = false;
+struct VqEncModel : ModelBase {
+    rdm_vq_cfg cfg{};
     bool wide = false;                             // z_channels > 4 (taming VQGAN-f16): conv_out is an ordinary 3x3 conv, quant_conv a GEMM with an fp32 token-major output
     size_t cinw, cinb, noutg, noutb, coutw, coutb, qw, qb;
-    std::vector<std::vector<VqRes>> down; std::vector<std::vector<VqAttn>> down_attn; std::vector<ConvW> downsample;   // indexed by level
-    VqRes mid1, mid2; VqAttn attn;
-    char* blob = nullptr; size_t blob_bytes = 0; Arena arena;
+    std::vector<VqLevel> levels;                   // indexed by level (walked low to high; the last level has no downsample)
+    VqMid mid;
 };
 static void build_vqenc(VqEncModel& v, const rdm_vq_cfg& c, Manifest& mf) {
     v.cfg = c;
-    auto f32 = [&](const std::string& n, size_t numel) { return mf.add("f32", n, numel * 4); };
-    auto bf = [&](const std::string& n, size_t numel) { return mf.add("bf16", n, numel * 2); };
-    auto add_res = [&](const std::string& pre, int cin, int cout) {
-        VqRes r{}; r.cin = cin; r.cout = cout; r.skip = cin != cout;
-        r.n1g = f32(pre + ".norm1.weight", cin); r.n1b = f32(pre + ".norm1.bias", cin);
-        r.w1 = mf.add("conv3", pre + ".conv1.weight", (size_t)cout * cin * 9 * 2); r.b1 = f32(pre + ".conv1.bias", cout);
-        r.n2g = f32(pre + ".norm2.weight", cout); r.n2b = f32(pre + ".norm2.bias", cout);
-        r.w2 = mf.add("conv3", pre + ".conv2.weight", (size_t)cout * cout * 9 * 2); r.b2 = f32(pre + ".conv2.bias", cout);
-        if (r.skip) { r.wsk = bf(pre + ".nin_shortcut.weight", (size_t)cout * cin); r.bsk = f32(pre + ".nin_shortcut.bias", cout); }
-        return r;
-    };
-    auto add_attn = [&](const std::string& p, int ch) {
-        VqAttn a{}; a.c = ch;
-        a.ng = f32(p + ".norm.weight", ch); a.nb = f32(p + ".norm.bias", ch);
-        a.wq = bf(p + ".q.weight", (size_t)ch * ch); a.bq = f32(p + ".q.bias", ch);
-        a.wk = bf(p + ".k.weight", (size_t)ch * ch); a.bk = f32(p + ".k.bias", ch);
-        a.wv = bf(p + ".v.weight", (size_t)ch * ch); a.bv = f32(p + ".v.bias", ch);
-        a.wo = bf(p + ".proj_out.weight", (size_t)ch * ch); a.bo = f32(p + ".proj_out.bias", ch);
-        return a;
-    };
-    v.cinw = f32("encoder.conv_in.weight", (size_t)c.ch * c.out_ch * 9); v.cinb = f32("encoder.conv_in.bias", c.ch);
-    v.down.assign(c.n_ch_mult, {}); v.down_attn.assign(c.n_ch_mult, {}); v.downsample.assign(c.n_ch_mult, ConvW{});
+    v.cinw = mf.f32("encoder.conv_in.weight", (size_t)c.ch * c.out_ch * 9); v.cinb = mf.f32("encoder.conv_in.bias", c.ch);
+    v.levels.assign(c.n_ch_mult, {});
     int bin = c.ch, curr_res = c.resolution;
-    for (int lvl = 0; lvl < c.n_ch_mult; lvl++) {
-        const int bout = c.ch * c.ch_mult[lvl];
-        bool at = false;
-        for (int i = 0; i < c.n_attn_resolutions; i++) at = at || c.attn_resolutions[i] == curr_res;
-        for (int i = 0; i < c.num_res_blocks; i++) {
-            char pre[64]; snprintf(pre, sizeof pre, "encoder.down.%d.block.%d", lvl, i);
-            v.down[lvl].push_back(add_res(pre, bin, bout)); bin = bout;
-            if (at) { snprintf(pre, sizeof pre, "encoder.down.%d.attn.%d", lvl, i); v.down_attn[lvl].push_back(add_attn(pre, bin)); }
-        }
-        if (lvl != c.n_ch_mult - 1) {
-            char pre[64]; snprintf(pre, sizeof pre, "encoder.down.%d.downsample.conv", lvl);
-            ConvW d{}; d.c = bin; d.w = mf.add("conv3", std::string(pre) + ".weight", (size_t)bin * bin * 9 * 2);
-            d.b = f32(std::string(pre) + ".bias", bin); v.downsample[lvl] = d;
-            curr_res /= 2;
-        }
-    }
-    v.mid1 = add_res("encoder.mid.block_1", bin, bin);
-    if (c.mid_attn) v.attn = add_attn("encoder.mid.attn_1", bin);
-    v.mid2 = add_res("encoder.mid.block_2", bin, bin);
-    v.noutg = f32("encoder.norm_out.weight", bin); v.noutb = f32("encoder.norm_out.bias", bin);
+    for (int lvl = 0; lvl < c.n_ch_mult; lvl++, curr_res /= 2)
+        v.levels[lvl] = add_vq_level(mf, c, "encoder.down." + std::to_string(lvl), c.num_res_blocks, bin, c.ch * c.ch_mult[lvl], curr_res,
+                                     lvl != c.n_ch_mult - 1 ? "downsample" : nullptr);
+    v.mid = add_vq_mid(mf, "encoder.mid", bin, c.mid_attn);
+    v.noutg = mf.f32("encoder.norm_out.weight", bin); v.noutb = mf.f32("encoder.norm_out.bias", bin);
     v.wide = c.z_channels > 4;
-    if (v.wide) {
-        v.coutw = mf.add("conv3", "encoder.conv_out.weight", (size_t)c.z_channels * bin * 9 * 2); v.coutb = f32("encoder.conv_out.bias", c.z_channels);
-        v.qw = bf("quant_conv.weight", (size_t)c.embed_dim * c.z_channels); v.qb = f32("quant_conv.bias", c.embed_dim);
-    } else {
-        v.coutw = f32("encoder.conv_out.weight", (size_t)c.z_channels * bin * 9); v.coutb = f32("encoder.conv_out.bias", c.z_channels);
-        v.qw = f32("quant_conv.weight", (size_t)c.embed_dim * c.z_channels); v.qb = f32("quant_conv.bias", c.embed_dim);
-    }
+    const size_t qc = (size_t)c.embed_dim * c.z_channels;      // wide: conv_out a conv3 entry, quant_conv a bf16 GEMM operand; else fp32 for the head / quantiser kernels
+    v.coutw = v.wide ? mf.conv3("encoder.conv_out.weight", c.z_channels, bin) : mf.f32("encoder.conv_out.weight", (size_t)c.z_channels * bin * 9);
+    v.coutb = mf.f32("encoder.conv_out.bias", c.z_channels);
+    v.qw = v.wide ? mf.bf16("quant_conv.weight", qc) : mf.f32("quant_conv.weight", qc); v.qb = mf.f32("quant_conv.bias", c.embed_dim);
 }
 
 // ------------------------------------------------------------------------------------ CLIP description
 struct ClipBlk { size_t ln1g, ln1b, wqkv, bqkv, wo, bo, ln2g, ln2b, wfc, bfc, wpj, bpj; };
-struct ClipModel {
-    rdm_clip_cfg cfg{}; bool loaded = false;
+struct ClipModel : ModelBase {
+    rdm_clip_cfg cfg{};
     std::vector<ClipBlk> text, vis;
     size_t tok, pos, lnfg, lnfb, tproj;                               // text
     size_t conv1, cls, vpos, lnpreg, lnpreb, lnpostg, lnpostb, vproj;  // vision
-    char* blob = nullptr; size_t blob_bytes = 0; Arena arena;
 };
 static void build_clip(ClipModel& m, const rdm_clip_cfg& c, Manifest& mf) {
-    m.cfg = c; m.text.clear(); m.vis.clear();
-    auto f32 = [&](const std::string& n, size_t numel) { return mf.add("f32", n, numel * 4); };
-    auto bf = [&](const std::string& n, size_t numel) { return mf.add("bf16", n, numel * 2); };
+    m.cfg = c;
     auto tower = [&](std::vector<ClipBlk>& out, const std::string& pre, int w, int layers) {
         for (int i = 0; i < layers; i++) {
             char b[96]; snprintf(b, sizeof b, "%s.resblocks.%d", pre.c_str(), i); const std::string p = b;
             ClipBlk k{};
-            k.ln1g = f32(p + ".ln_1.weight", w); k.ln1b = f32(p + ".ln_1.bias", w);
-            k.wqkv = bf(p + ".attn.in_proj_weight", (size_t)3 * w * w); k.bqkv = f32(p + ".attn.in_proj_bias", 3 * w);
-            k.wo = bf(p + ".attn.out_proj.weight", (size_t)w * w); k.bo = f32(p + ".attn.out_proj.bias", w);
-            k.ln2g = f32(p + ".ln_2.weight", w); k.ln2b = f32(p + ".ln_2.bias", w);
-            k.wfc = bf(p + ".mlp.c_fc.weight", (size_t)4 * w * w); k.bfc = f32(p + ".mlp.c_fc.bias", 4 * w);
-            k.wpj = bf(p + ".mlp.c_proj.weight", (size_t)4 * w * w); k.bpj = f32(p + ".mlp.c_proj.bias", w);
+            k.ln1g = mf.f32(p + ".ln_1.weight", w); k.ln1b = mf.f32(p + ".ln_1.bias", w);
+            k.wqkv = mf.bf16(p + ".attn.in_proj_weight", (size_t)3 * w * w); k.bqkv = mf.f32(p + ".attn.in_proj_bias", 3 * w);
+            k.wo = mf.bf16(p + ".attn.out_proj.weight", (size_t)w * w); k.bo = mf.f32(p + ".attn.out_proj.bias", w);
+            k.ln2g = mf.f32(p + ".ln_2.weight", w); k.ln2b = mf.f32(p + ".ln_2.bias", w);
+            k.wfc = mf.bf16(p + ".mlp.c_fc.weight", (size_t)4 * w * w); k.bfc = mf.f32(p + ".mlp.c_fc.bias", 4 * w);
+            k.wpj = mf.bf16(p + ".mlp.c_proj.weight", (size_t)4 * w * w); k.bpj = mf.f32(p + ".mlp.c_proj.bias", w);
             out.push_back(k);
         }
     };
     const int vw = c.vision_width, g = c.image_resolution / c.vision_patch_size, tw = c.transformer_width;
-    m.conv1 = bf("visual.conv1.weight", (size_t)vw * 3 * c.vision_patch_size * c.vision_patch_size);
-    m.cls = f32("visual.class_embedding", vw); m.vpos = f32("visual.positional_embedding", (size_t)(g * g + 1) * vw);
-    m.lnpreg = f32("visual.ln_pre.weight", vw); m.lnpreb = f32("visual.ln_pre.bias", vw);
+    m.conv1 = mf.bf16("visual.conv1.weight", (size_t)vw * 3 * c.vision_patch_size * c.vision_patch_size);
+    m.cls = mf.f32("visual.class_embedding", vw); m.vpos = mf.f32("visual.positional_embedding", (size_t)(g * g + 1) * vw);
+    m.lnpreg = mf.f32("visual.ln_pre.weight", vw); m.lnpreb = mf.f32("visual.ln_pre.bias", vw);
     tower(m.vis, "visual.transformer", vw, c.vision_layers);
-    m.lnpostg = f32("visual.ln_post.weight", vw); m.lnpostb = f32("visual.ln_post.bias", vw);
+    m.lnpostg = mf.f32("visual.ln_post.weight", vw); m.lnpostb = mf.f32("visual.ln_post.bias", vw);
     m.vproj = mf.add("bf16_t", "visual.proj", (size_t)vw * c.embed_dim * 2);
     tower(m.text, "transformer", tw, c.transformer_layers);
-    m.tok = f32("token_embedding.weight", (size_t)c.vocab_size * tw);
-    m.pos = f32("positional_embedding", (size_t)c.context_length * tw);
-    m.lnfg = f32("ln_final.weight", tw); m.lnfb = f32("ln_final.bias", tw);
+    m.tok = mf.f32("token_embedding.weight", (size_t)c.vocab_size * tw);
+    m.pos = mf.f32("positional_embedding", (size_t)c.context_length * tw);
+    m.lnfg = mf.f32("ln_final.weight", tw); m.lnfb = mf.f32("ln_final.bias", tw);
     m.tproj = mf.add("bf16_t", "text_projection", (size_t)tw * c.embed_dim * 2);
 }
 
 // ------------------------------------------------------------------------------------ RARM transformer description
 struct RarmBlk { size_t ln1g, ln1b, wqkv, wo1, bo1, ln2g, ln2b, wq2, wo2, bo2, ln3g, ln3b, wff1, bff1, wff2, bff2; };
-struct RarmModel {
-    rdm_rarm_cfg cfg{}; bool loaded = false; int C = 0, kv_total = 0;
+struct RarmModel : ModelBase {
+    rdm_rarm_cfg cfg{}; int C = 0, kv_total = 0;
     std::vector<RarmBlk> blk;
     size_t emb, pos, kvw, wpo, bpo;
-    char* blob = nullptr; size_t blob_bytes = 0; Arena arena;
     // sampling state: per-layer self-attention K/V cache [depth][2][B'][L][C], projected neighbours [B'*k][depth*2*C],
     // device step counter / completion counter / current tokens, logits of the current step
     char* cache = nullptr; size_t cache_bytes = 0;
@@ -455,35 +433,34 @@ struct RarmModel {
     char* state = nullptr; size_t state_bytes = 0;
     // decode-step cross-attention operands per layer (rarm_prepare): [depth][2][Bc][128][C] bf16 (G, UT), valid for xa_B conditional sequences and xa_k neighbours
     char* xa = nullptr; size_t xa_bytes = 0; int xa_B = 0, xa_k = 0;
+    void release() { free_dev(cache, cache_bytes); free_dev(ctxkv, ctxkv_bytes); free_dev(state, state_bytes); free_dev(xa, xa_bytes); xa_B = xa_k = 0; ModelBase::release(); }
 };
 static void build_rarm(RarmModel& m, const rdm_rarm_cfg& c, Manifest& mf) {
-    m.cfg = c; m.blk.clear(); m.C = c.n_heads * c.d_head;
+    m.cfg = c; m.C = c.n_heads * c.d_head;
     const int C = m.C;
-    auto f32 = [&](const std::string& n, size_t numel) { return mf.add("f32", n, numel * 4); };
-    auto bf = [&](const std::string& n, size_t numel) { return mf.add("bf16", n, numel * 2); };
-    m.emb = f32("proj_in.weight", (size_t)c.vocab_in * C);
+    m.emb = mf.f32("proj_in.weight", (size_t)c.vocab_in * C);
     m.pos = mf.add("f32_t", "positional_encoding", (size_t)C * c.sequence_length * 4);
     std::string kv_srcs;
     for (int i = 0; i < c.depth; i++) {
         char b[64]; snprintf(b, sizeof b, "transformer_blocks.%d", i); const std::string p = b;
         RarmBlk k{};
-        k.ln1g = f32(p + ".norm1.weight", C); k.ln1b = f32(p + ".norm1.bias", C);
-        k.wqkv = bf(p + ".attn1.to_q.weight," + p + ".attn1.to_k.weight," + p + ".attn1.to_v.weight", (size_t)3 * C * C);
-        k.wo1 = bf(p + ".attn1.to_out.0.weight", (size_t)C * C); k.bo1 = f32(p + ".attn1.to_out.0.bias", C);
-        k.ln2g = f32(p + ".norm2.weight", C); k.ln2b = f32(p + ".norm2.bias", C);
-        k.wq2 = bf(p + ".attn2.to_q.weight", (size_t)C * C);
-        k.wo2 = bf(p + ".attn2.to_out.0.weight", (size_t)C * C); k.bo2 = f32(p + ".attn2.to_out.0.bias", C);
-        k.ln3g = f32(p + ".norm3.weight", C); k.ln3b = f32(p + ".norm3.bias", C);
+        k.ln1g = mf.f32(p + ".norm1.weight", C); k.ln1b = mf.f32(p + ".norm1.bias", C);
+        k.wqkv = mf.bf16(p + ".attn1.to_q.weight," + p + ".attn1.to_k.weight," + p + ".attn1.to_v.weight", (size_t)3 * C * C);
+        k.wo1 = mf.bf16(p + ".attn1.to_out.0.weight", (size_t)C * C); k.bo1 = mf.f32(p + ".attn1.to_out.0.bias", C);
+        k.ln2g = mf.f32(p + ".norm2.weight", C); k.ln2b = mf.f32(p + ".norm2.bias", C);
+        k.wq2 = mf.bf16(p + ".attn2.to_q.weight", (size_t)C * C);
+        k.wo2 = mf.bf16(p + ".attn2.to_out.0.weight", (size_t)C * C); k.bo2 = mf.f32(p + ".attn2.to_out.0.bias", C);
+        k.ln3g = mf.f32(p + ".norm3.weight", C); k.ln3b = mf.f32(p + ".norm3.bias", C);
         k.wff1 = mf.add("geglu_w", p + ".ff.net.0.proj.weight", (size_t)8 * C * C * 2);
         k.bff1 = mf.add("geglu_b", p + ".ff.net.0.proj.bias", (size_t)8 * C * 4);
-        k.wff2 = bf(p + ".ff.net.2.weight", (size_t)C * 4 * C); k.bff2 = f32(p + ".ff.net.2.bias", C);
+        k.wff2 = mf.bf16(p + ".ff.net.2.weight", (size_t)C * 4 * C); k.bff2 = mf.f32(p + ".ff.net.2.bias", C);
         if (!kv_srcs.empty()) kv_srcs += ",";
         kv_srcs += p + ".attn2.to_k.weight," + p + ".attn2.to_v.weight";
         m.blk.push_back(k);
     }
     m.kv_total = c.depth * 2 * C;
     m.kvw = mf.add("bf16", kv_srcs, (size_t)m.kv_total * c.context_dim * 2);      // the neighbours' K/V of ALL layers: one GEMM per sampling call
-    m.wpo = bf("proj_out.weight", (size_t)c.vocab_out * C); m.bpo = f32("proj_out.bias", c.vocab_out);
+    m.wpo = mf.bf16("proj_out.weight", (size_t)c.vocab_out * C); m.bpo = mf.f32("proj_out.bias", c.vocab_out);
 }
 
 // ------------------------------------------------------------------------------------ context
@@ -494,7 +471,6 @@ struct rdm_ctx {
     float* gn_partial = nullptr; size_t gn_partial_bytes = 0;
     char* splitk_ws = nullptr; size_t splitk_ws_bytes = 0;   // fp32 partial planes of the K-split halo convs
     char* samp = nullptr; size_t samp_bytes = 0;     // sampler scratch
-    float* code_norms = nullptr;                     // |e_j|^2 of the loaded first stage's codebook (vqcode.hip), made on first use, dropped by rdm_load_vq
     // derived weight layouts, built on first use per weight and dropped when a model is reloaded: fragment-ordered copies of the 3x3 conv
     // weights (conv_halo4.hip) and of the Linear / 1x1 weights (lin4.hip; optionally scaled by a LayerNorm's gamma, with the (s, b') table
     // of the folded LayerNorm beside it).  Keyed on everything the copy depends on -- the entry is the copy of exactly that
@@ -1197,30 +1173,73 @@ static int run_with_arena(rdm_ctx* c, Arena& ar, const char* blob, F&& body) {
     return run.rc;
 }
 
-static int cfg_check_unet(rdm_ctx* c, const rdm_unet_cfg* g) {
-    if (!g || g->n_channel_mult < 1 || g->n_channel_mult > RDM_MAX_LEVELS || g->n_attention_resolutions > RDM_MAX_LEVELS)
-        return c ? c->fail(-1, "bad unet cfg") : -1;
+// One cfg check per model, called by its manifest entry (c null, load false) and by its load entry.  First what the builder walks --
+// array extents, divisors: refused by both entries --, then, for `load`, what the executors and kernels take.
+static int cfg_refuse(rdm_ctx* c, const char* msg) { return c ? c->fail(-1, "%s", msg) : -1; }
+static int cfg_check_unet(rdm_ctx* c, const rdm_unet_cfg* g, bool /*load*/) {
+    if (!g || g->n_channel_mult < 1 || g->n_channel_mult > RDM_MAX_LEVELS || g->n_attention_resolutions > RDM_MAX_LEVELS) return cfg_refuse(c, "bad unet cfg");
     if (g->model_channels % 32 || g->num_head_channels != 32 || g->context_dim % 64 || g->in_channels > 4 || g->out_channels > 4)
-        return c ? c->fail(-1, "unsupported unet cfg: model_channels %% 32 == 0 (GroupNorm32; widths that are not multiples of 64 run zero-padded), num_head_channels == 32, context_dim %% 64 == 0 required") : -1;
+        return cfg_refuse(c, "unsupported unet cfg: model_channels % 32 == 0 (GroupNorm32; widths that are not multiples of 64 run zero-padded), num_head_channels == 32, context_dim % 64 == 0 required");
+    return 0;
+}
+// first stage, decoder and encoder.  `exec`: also what the executors take (the decoder's manifest entry describes any cfg that can be walked)
+static int cfg_check_first_stage(rdm_ctx* c, const rdm_vq_cfg* g, bool encoder, bool exec) {
+    bool ok = g && g->n_ch_mult >= 1 && g->n_ch_mult <= RDM_MAX_LEVELS && g->n_attn_resolutions >= 0 && g->n_attn_resolutions <= RDM_MAX_LEVELS;
+    if (ok && exec) {
+        const bool narrow = g->embed_dim == 3 && g->z_channels == 3;      // VQ-f4; the decoder also as KL-f4
+        const bool wide = g->embed_dim > 0 && g->z_channels > 0 && g->embed_dim % 64 == 0 && g->z_channels % 64 == 0 && !g->kl;      // VQGAN-f16
+        ok = g->ch % 64 == 0 && g->out_ch <= 4 && (narrow || wide);
+        if (encoder) ok = ok && !g->kl && g->resolution % (1 << (g->n_ch_mult - 1)) == 0;      // the VQ interface only; every Downsample halves exactly
+    }
+    if (ok) return 0;
+    return cfg_refuse(c, encoder ? "unsupported first-stage encoder cfg: n_ch_mult in [1, RDM_MAX_LEVELS], n_attn_resolutions in [0, RDM_MAX_LEVELS], VQ interface (kl = 0), resolution a multiple of 2^(levels - 1), "
+                                   "ch % 64 == 0, out_ch <= 4 and either embed_dim == z_channels == 3 (VQ-f4) or both multiples of 64 (VQGAN-f16)"
+                                 : "unsupported vq cfg: n_ch_mult in [1, RDM_MAX_LEVELS], n_attn_resolutions in [0, RDM_MAX_LEVELS], ch % 64 == 0, out_ch <= 4 and either embed_dim == z_channels == 3 "
+                                   "(VQ-f4 / KL-f4) or both multiples of 64 (VQGAN-f16, kl = 0)");
+}
+static int cfg_check_vq(rdm_ctx* c, const rdm_vq_cfg* g, bool load) { return cfg_check_first_stage(c, g, false, load); }
+static int cfg_check_vqenc(rdm_ctx* c, const rdm_vq_cfg* g, bool /*load*/) { return cfg_check_first_stage(c, g, true, true); }
+static int cfg_check_clip(rdm_ctx* c, const rdm_clip_cfg* g, bool load) {
+    if (!g || g->vision_patch_size < 1) return cfg_refuse(c, "bad clip cfg: vision_patch_size >= 1 required");
+    if (load && (g->transformer_width % 64 || g->vision_width % 64 || g->embed_dim % 8 || g->transformer_heads < 1 || g->transformer_width / g->transformer_heads != 64))
+        return cfg_refuse(c, "unsupported clip cfg: widths % 64 == 0 and 64-d heads required");
+    return 0;
+}
+static int cfg_check_rarm(rdm_ctx* c, const rdm_rarm_cfg* g, bool load) {
+    if (!g || g->depth < 1 || g->n_heads < 1) return cfg_refuse(c, "bad rarm cfg: depth >= 1 and n_heads >= 1 required");
+    if (load && (g->d_head != 64 || g->context_dim % 64 || g->sequence_length > 1024 || g->vocab_out % 2))
+        return cfg_refuse(c, "unsupported rarm cfg: d_head == 64, context_dim % 64 == 0, sequence_length <= 1024, even vocab_out required");
     return 0;
 }
 
-static long long write_manifest(const Manifest& mf, char* buf, size_t buflen, size_t* blob_bytes) {
+// rdm_*_manifest: the description is built into a model of its own, nothing is allocated
+template <typename M, typename Cfg>
+static long long model_manifest(int (*check)(rdm_ctx*, const Cfg*, bool), void (*build)(M&, const Cfg&, Manifest&), const Cfg* cfg,
+                                char* buf, size_t buflen, size_t* blob_bytes) {
+    if (check(nullptr, cfg, false)) return -1;
+    M m{}; Manifest mf; build(m, *cfg, mf);
     if (blob_bytes) *blob_bytes = (mf.total + 255) & ~(size_t)255;
     if (buf && buflen > mf.text.size()) { memcpy(buf, mf.text.c_str(), mf.text.size() + 1); }
     return (long long)mf.text.size();
 }
 
-template <typename M>
-static int load_blob(rdm_ctx* c, M& m, const Manifest& mf, const void* packed, size_t nbytes) {
+// rdm_load_*: everything that can refuse the load comes before the first change to `live` -- a refused load leaves the model that was
+// loaded before fully usable
+template <typename M, typename Cfg>
+static int load_model(rdm_ctx* c, M& live, int (*check)(rdm_ctx*, const Cfg*, bool), void (*build)(M&, const Cfg&, Manifest&), const Cfg* cfg,
+                      const void* packed, size_t nbytes) {
+    RDM_TRY(check(c, cfg, true));
+    if (!packed) return c->fail(-1, "null blob");
+    M next{}; Manifest mf; build(next, *cfg, mf);
     const size_t need = (mf.total + 255) & ~(size_t)255;
     if (nbytes != need) return c->fail(-1, "packed blob is %zu bytes, manifest needs %zu", nbytes, need);
     RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
     c->drop_frags();                                  // derived weight layouts refer to blob addresses that may be reused
-    if (m.blob) { RDM_CHECK_HIP(c, hipFree(m.blob)); m.blob = nullptr; }
-    RDM_CHECK_HIP(c, hipMalloc((void**)&m.blob, need));
-    RDM_CHECK_HIP(c, hipMemcpy(m.blob, packed, need, hipMemcpyHostToDevice));
-    m.blob_bytes = need; m.loaded = true;
+    live.release();                                   // the old weights, and the arena and everything else made for or from them
+    live = next;                                      // (a description only: owns no device memory)
+    RDM_CHECK_HIP(c, hipMalloc((void**)&live.blob, need));
+    RDM_CHECK_HIP(c, hipMemcpy(live.blob, packed, need, hipMemcpyHostToDevice));
+    live.blob_bytes = need; live.loaded = true;
     return 0;
 }
 
@@ -1268,34 +1287,46 @@ static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) 
     return out;
 }
 
+// debug tap (rdm_debug_tap): first-stage decoder layers are blocks 1000, 1001, ... in execution order (conv_in's output = 1000).
+// tapi: the decoder's running block number; null (the encoder): no taps
+static void vq_tap(Ops& o, int* tapi, const bf16_t* t, int B, int H, int W, int ch) {
+    if (!tapi) return;
+    o.cur_block = (*tapi)++; o.cur_layer = 0;
+    if (!o.plan && o.c->tap_buf && o.c->tap_sub == 0 && o.c->tap_block == o.cur_block) {
+        size_t nb = (size_t)B * H * W * ch * 2; if (nb > o.c->tap_bytes) nb = o.c->tap_bytes;
+        o.check(hipMemcpyAsync(o.c->tap_buf, t, nb, hipMemcpyDeviceToDevice, o.c->stream), "debug tap");
+    }
+}
+// the ResnetBlocks (+ AttnBlocks) of one level (ch: the running width) and the middle, for the decoder and the encoder
+static bf16_t* vq_blocks(Ops& o, const VqLevel& L, bf16_t* h, int B, int H, int W, int& ch, int* tapi) {
+    for (size_t i = 0; i < L.blocks.size(); i++) {
+        h = vq_res(o, L.blocks[i], h, B, H, W); ch = L.blocks[i].cout; vq_tap(o, tapi, h, B, H, W, ch);
+        if (i < L.attn.size()) { h = vq_attn(o, L.attn[i], h, B, H, W); vq_tap(o, tapi, h, B, H, W, ch); }
+    }
+    return h;
+}
+static bf16_t* vq_mid(Ops& o, const VqMid& m, bf16_t* h, int B, int H, int W, int* tapi) {
+    const int ch = m.res1.cout;
+    h = vq_res(o, m.res1, h, B, H, W); vq_tap(o, tapi, h, B, H, W, ch);
+    if (m.has_attn) { h = vq_attn(o, m.attn, h, B, H, W); vq_tap(o, tapi, h, B, H, W, ch); }
+    h = vq_res(o, m.res2, h, B, H, W); vq_tap(o, tapi, h, B, H, W, ch);
+    return h;
+}
+
 // decoder trunk shared by the VQ-f4 (ldm) and VQGAN-f16 (taming) first stages: ResnetBlocks, AttnBlocks, nearest-2x upsample convs
 static void vq_trunk(Ops& o, VqModel& v, bf16_t* h, int B, int H, int W, float* img) {
     const rdm_vq_cfg& c = v.cfg;
-    int bin = c.ch * c.ch_mult[c.n_ch_mult - 1];
-    // debug tap (rdm_debug_tap): first-stage decoder layers are blocks 1000, 1001, ... in execution order (conv_in's output = 1000)
-    int tapi = 1000;
-    auto vtap = [&](const bf16_t* t, int ch) {
-        o.cur_block = tapi++; o.cur_layer = 0;
-        if (!o.plan && o.c->tap_buf && o.c->tap_sub == 0 && o.c->tap_block == o.cur_block) {
-            size_t nb = (size_t)B * H * W * ch * 2; if (nb > o.c->tap_bytes) nb = o.c->tap_bytes;
-            o.check(hipMemcpyAsync(o.c->tap_buf, t, nb, hipMemcpyDeviceToDevice, o.c->stream), "debug tap");
-        }
-    };
-    vtap(h, bin);
-    h = vq_res(o, v.mid1, h, B, H, W); vtap(h, bin);
-    if (c.mid_attn) { h = vq_attn(o, v.attn, h, B, H, W); vtap(h, bin); }
-    h = vq_res(o, v.mid2, h, B, H, W); vtap(h, bin);
+    int bin = c.ch * c.ch_mult[c.n_ch_mult - 1], tapi = 1000;
+    vq_tap(o, &tapi, h, B, H, W, bin);
+    h = vq_mid(o, v.mid, h, B, H, W, &tapi);
     for (int lvl = c.n_ch_mult - 1; lvl >= 0; lvl--) {
-        for (size_t i = 0; i < v.up_blocks[lvl].size(); i++) {
-            h = vq_res(o, v.up_blocks[lvl][i], h, B, H, W); bin = v.up_blocks[lvl][i].cout; vtap(h, bin);
-            if (i < v.up_attn[lvl].size()) { h = vq_attn(o, v.up_attn[lvl][i], h, B, H, W); vtap(h, bin); }
-        }
+        h = vq_blocks(o, v.levels[lvl], h, B, H, W, bin, &tapi);
         if (lvl != 0) {
-            const ConvW& u = v.upsample[lvl];
+            const ConvW& u = v.levels[lvl].resample;
             bf16_t* out = o.abf((size_t)B * (H * 2) * (W * 2) * u.c);
             o.conv3(h, nullptr, u.c, 0, o.w<bf16_t>(u.w), o.w<float>(u.b), B, H, W, u.c, 1, 1, nullptr, 0, nullptr, out);
             h = out; H *= 2; W *= 2;
-            vtap(h, u.c);
+            vq_tap(o, &tapi, h, B, H, W, u.c);
         }
     }
     bf16_t* no = o.abf((size_t)B * H * W * bin);
@@ -1345,20 +1376,15 @@ static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* 
     if (!o.plan) o.check(launch_conv_in(img, o.w<float>(v.cinw), o.w<float>(v.cinb), h, B, c.out_ch, H, W, c.ch, o.c->stream), "encoder conv_in");
     int bin = c.ch;
     for (int lvl = 0; lvl < c.n_ch_mult; lvl++) {
-        for (size_t i = 0; i < v.down[lvl].size(); i++) {
-            h = vq_res(o, v.down[lvl][i], h, B, H, W); bin = v.down[lvl][i].cout;
-            if (i < v.down_attn[lvl].size()) h = vq_attn(o, v.down_attn[lvl][i], h, B, H, W);
-        }
+        h = vq_blocks(o, v.levels[lvl], h, B, H, W, bin, nullptr);
         if (lvl != c.n_ch_mult - 1) {      // F.pad(x, (0, 1, 0, 1)) + Conv2d(stride 2, padding 0): window rows 2 oy .. 2 oy + 2, zero beyond the last row / column
-            const ConvW& d = v.downsample[lvl];
+            const ConvW& d = v.levels[lvl].resample;
             bf16_t* out = o.abf((size_t)B * (H / 2) * (W / 2) * d.c);
             o.conv3(h, nullptr, d.c, 0, o.w<bf16_t>(d.w), o.w<float>(d.b), B, H, W, d.c, 2, 0, nullptr, 0, nullptr, out, /*asym=*/1);
             h = out; H /= 2; W /= 2;
         }
     }
-    h = vq_res(o, v.mid1, h, B, H, W);
-    if (c.mid_attn) h = vq_attn(o, v.attn, h, B, H, W);
-    h = vq_res(o, v.mid2, h, B, H, W);
+    h = vq_mid(o, v.mid, h, B, H, W, nullptr);
     bf16_t* no = o.abf((size_t)B * H * W * bin);
     if (v.wide) {
         const int M = B * H * W;
@@ -1375,6 +1401,36 @@ static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* 
     o.head(h, B, H, W, bin, bin, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, o.w<float>(v.coutw), o.w<float>(v.coutb), c.z_channels, ze, no, hwp);
     if (!o.plan) o.check(launch_vq_quantize(ze, nullptr, 0, o.w<float>(v.qw), o.w<float>(v.qb), z, nullptr, B, H * W, 0, o.c->stream), "quant_conv");
     return nullptr;
+}
+
+// Samples per decoder (or wide-latent encoder: the same levels, mirrored) pass.  Decoding is per sample (GroupNorm statistics included), so a batch may be walked in ranges; a range is
+// sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo convs address an operand through
+// 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the seven 128-channel convs of
+// the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).  RDM_VQ_RANGE overrides (tests).
+static int vq_range(const rdm_vq_cfg& c, int b) {
+    static const int env = rdm_env_int(getenv("RDM_VQ_RANGE"), 0);
+    if (env > 0) return env < b ? env : b;
+    long long per = 1;
+    for (int l = 0; l < c.n_ch_mult; l++) {
+        const long long r = c.resolution >> l, e = r * r * c.ch * c.ch_mult[l];
+        if (e > per) per = e;
+        // the level's Upsample output (and the first convs' input at the next finer level) keeps THIS level's channel count at twice the
+        // resolution -- the decoder's largest activation (VQ-f4: 256 x 256 x 256 per image, twice the level maximum): a range sized without
+        // it reached exactly 2^31 elements and pushed those convs off the 32-bit-offset halo kernels (advisor, round 5)
+        if (l >= 1) { const long long u = 4 * r * r * c.ch * c.ch_mult[l]; if (u > per) per = u; }
+    }
+    long long n = (1LL << 30) / per;
+    if (n < 1) n = 1;
+    return n < b ? (int)n : b;
+}
+// a first-stage pass over a batch: body(o, b0, n) runs samples [b0, b0 + n) -- in ranges of vq_range(), or the whole batch at once
+template <typename M, typename F>
+static int vq_walk(rdm_ctx* c, M& m, int b, bool in_ranges, F&& body) {
+    const int nb = in_ranges ? vq_range(m.cfg, b) : b;
+    RDM_TRY(ensure_gn_partial(c, nb));
+    for (int b0 = 0; b0 < b; b0 += nb)
+        RDM_TRY(run_with_arena(c, m.arena, m.blob, [&](Ops& o) { body(o, b0, b - b0 < nb ? b - b0 : nb); }));
+    return 0;
 }
 
 // ------------------------------------------------------------------------------------ CLIP
@@ -1457,10 +1513,8 @@ void rdm_ctx_destroy(rdm_ctx* c) {
     if (c->comm) rdm_comm_destroy(c);
     DevGuard guard(c->device);
     hipDeviceSynchronize();
-    void* ptrs[] = {c->zero_page, c->unet.blob, c->unet.arena.base, c->unet.kv_cache, c->vq.blob, c->vq.arena.base,
-                    c->clip.blob, c->clip.arena.base, c->gn_partial, c->samp, c->splitk_ws, c->unet.xa_cache,
-                    c->rarm.blob, c->rarm.arena.base, c->rarm.cache, c->rarm.ctxkv, c->rarm.state, c->rarm.xa, c->wfrag_tmp, c->bwd_tmp,
-                    c->vqenc.blob, c->vqenc.arena.base, c->eye3, c->unet.emb_table, c->code_norms};
+    c->unet.release(); c->vq.release(); c->vqenc.release(); c->clip.release(); c->rarm.release();
+    void* ptrs[] = {c->zero_page, c->eye3, c->gn_partial, c->samp, c->splitk_ws, c->wfrag_tmp, c->bwd_tmp};      // the context's own buffers
     for (void* p : ptrs) if (p) hipFree(p);
     c->drop_frags();
     knn_free(c->db);
@@ -1492,92 +1546,26 @@ int rdm_set_stream(rdm_ctx* c, void* s) {
     return 0;
 }
 
-long long rdm_unet_manifest(const rdm_unet_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) {
-    if (cfg_check_unet(nullptr, cfg)) return -1;
-    UNet u; Manifest mf; build_unet(u, *cfg, mf);
-    return write_manifest(mf, buf, buflen, blob_bytes);
-}
-long long rdm_vq_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) {
-    if (!cfg || cfg->n_ch_mult < 1 || cfg->n_ch_mult > RDM_MAX_LEVELS || cfg->n_attn_resolutions < 0 || cfg->n_attn_resolutions > RDM_MAX_LEVELS) return -1;
-    VqModel v; Manifest mf; build_vq(v, *cfg, mf);
-    return write_manifest(mf, buf, buflen, blob_bytes);
-}
-long long rdm_clip_manifest(const rdm_clip_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) {
-    if (!cfg) return -1;
-    ClipModel m; Manifest mf; build_clip(m, *cfg, mf);
-    return write_manifest(mf, buf, buflen, blob_bytes);
-}
+long long rdm_unet_manifest(const rdm_unet_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_unet, build_unet, cfg, buf, buflen, blob_bytes); }
+long long rdm_vq_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_vq, build_vq, cfg, buf, buflen, blob_bytes); }
+long long rdm_vqenc_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_vqenc, build_vqenc, cfg, buf, buflen, blob_bytes); }
+long long rdm_clip_manifest(const rdm_clip_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_clip, build_clip, cfg, buf, buflen, blob_bytes); }
+long long rdm_rarm_manifest(const rdm_rarm_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_rarm, build_rarm, cfg, buf, buflen, blob_bytes); }
 
-int rdm_load_unet(rdm_ctx* c, const rdm_unet_cfg* cfg, const void* packed, size_t nbytes) {
-    RDM_ENTER(c);
-    if (!c) return -1;
-    RDM_TRY(cfg_check_unet(c, cfg));
-    Manifest mf; build_unet(c->unet, *cfg, mf);
-    return load_blob(c, c->unet, mf, packed, nbytes);
-}
-int rdm_load_vq(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes) {
-    RDM_ENTER(c);
-    if (!c || !cfg) return -1;
-    if (cfg->ch % 64 || cfg->out_ch > 4 || cfg->n_attn_resolutions < 0 || cfg->n_attn_resolutions > RDM_MAX_LEVELS ||
-        !((cfg->embed_dim == 3 && cfg->z_channels == 3) || (cfg->embed_dim % 64 == 0 && cfg->z_channels % 64 == 0 && !cfg->kl)))
-        return c->fail(-1, "unsupported vq cfg: ch %% 64 == 0 and either embed_dim == z_channels == 3 (VQ-f4 / KL-f4) or both multiples of 64 (VQGAN-f16)");
-    if (c->code_norms) { RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream)); (void)hipFree(c->code_norms); c->code_norms = nullptr; }
-    Manifest mf; build_vq(c->vq, *cfg, mf);
-    return load_blob(c, c->vq, mf, packed, nbytes);
-}
-static int cfg_check_vqenc(rdm_ctx* c, const rdm_vq_cfg* g) {
-    const bool ok = g && g->n_ch_mult >= 1 && g->n_ch_mult <= RDM_MAX_LEVELS && g->n_attn_resolutions >= 0 && g->n_attn_resolutions <= RDM_MAX_LEVELS &&
-                    g->ch % 64 == 0 && g->out_ch <= 4 && !g->kl && g->resolution % (1 << (g->n_ch_mult - 1)) == 0 &&
-                    ((g->embed_dim == 3 && g->z_channels == 3) || (g->embed_dim > 0 && g->z_channels > 0 && g->embed_dim % 64 == 0 && g->z_channels % 64 == 0));
-    if (!ok) return c ? c->fail(-1, "unsupported first-stage encoder cfg: VQ interface (kl = 0), ch %% 64 == 0 and either embed_dim == z_channels == 3 (VQ-f4) or both multiples of 64 (VQGAN-f16)") : -1;
-    return 0;
-}
-long long rdm_vqenc_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) {
-    if (cfg_check_vqenc(nullptr, cfg)) return -1;
-    VqEncModel v; Manifest mf; build_vqenc(v, *cfg, mf);
-    return write_manifest(mf, buf, buflen, blob_bytes);
-}
-int rdm_load_vqenc(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes) {
-    RDM_ENTER(c);
-    if (!packed) return c->fail(-1, "null blob");
-    RDM_TRY(cfg_check_vqenc(c, cfg));
-    Manifest mf; build_vqenc(c->vqenc, *cfg, mf);
-    return load_blob(c, c->vqenc, mf, packed, nbytes);
-}
-// Samples per decoder (or wide-latent encoder: the same levels, mirrored) pass.  Decoding is per sample (GroupNorm statistics included), so a batch may be walked in ranges; a range is
-// sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo convs address an operand through
-// 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the seven 128-channel convs of
-// the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).  RDM_VQ_RANGE overrides (tests).
-static int vq_range(const rdm_vq_cfg& c, int b) {
-    static const int env = rdm_env_int(getenv("RDM_VQ_RANGE"), 0);
-    if (env > 0) return env < b ? env : b;
-    long long per = 1;
-    for (int l = 0; l < c.n_ch_mult; l++) {
-        const long long r = c.resolution >> l, e = r * r * c.ch * c.ch_mult[l];
-        if (e > per) per = e;
-        // the level's Upsample output (and the first convs' input at the next finer level) keeps THIS level's channel count at twice the
-        // resolution -- the decoder's largest activation (VQ-f4: 256 x 256 x 256 per image, twice the level maximum): a range sized without
-        // it reached exactly 2^31 elements and pushed those convs off the 32-bit-offset halo kernels (advisor, round 5)
-        if (l >= 1) { const long long u = 4 * r * r * c.ch * c.ch_mult[l]; if (u > per) per = u; }
-    }
-    long long n = (1LL << 30) / per;
-    if (n < 1) n = 1;
-    return n < b ? (int)n : b;
-}
+int rdm_load_unet(rdm_ctx* c, const rdm_unet_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->unet, cfg_check_unet, build_unet, cfg, packed, nbytes); }
+int rdm_load_vq(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->vq, cfg_check_vq, build_vq, cfg, packed, nbytes); }
+int rdm_load_vqenc(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->vqenc, cfg_check_vqenc, build_vqenc, cfg, packed, nbytes); }
+int rdm_load_clip(rdm_ctx* c, const rdm_clip_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->clip, cfg_check_clip, build_clip, cfg, packed, nbytes); }
+int rdm_load_rarm(rdm_ctx* c, const rdm_rarm_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->rarm, cfg_check_rarm, build_rarm, cfg, packed, nbytes); }
 int rdm_vq_encode(rdm_ctx* c, const float* img, int b, float* z_out) {
     RDM_ENTER(c);
     if (!img || !z_out || b < 1) return c->fail(-1, "rdm_vq_encode: bad argument");
     if (!c->vqenc.loaded) return c->fail(-1, "first-stage encoder weights not loaded (rdm_load_vqenc)");
     const rdm_vq_cfg& q = c->vqenc.cfg;
-    const int nb = c->vqenc.wide ? vq_range(q, b) : b, zr = q.resolution >> (q.n_ch_mult - 1);      // wide latents: walked in ranges as rdm_vq_decode* is
-    RDM_TRY(ensure_gn_partial(c, nb));
-    for (int b0 = 0; b0 < b; b0 += nb) {
-        const int n = b - b0 < nb ? b - b0 : nb;
-        RDM_TRY(run_with_arena(c, c->vqenc.arena, c->vqenc.blob, [&](Ops& o) {
-            vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, z_out + (size_t)b0 * q.embed_dim * zr * zr);
-        }));
-    }
-    return 0;
+    const int zr = q.resolution >> (q.n_ch_mult - 1);
+    return vq_walk(c, c->vqenc, b, c->vqenc.wide, [&](Ops& o, int b0, int n) {      // wide latents: walked in ranges as rdm_vq_decode* is
+        vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, z_out + (size_t)b0 * q.embed_dim * zr * zr);
+    });
 }
 // taming VQModel.encode as reached from Net2NetTransformer.encode_to_z (un-vendored, parity unpinned): quant_z, _, info =
 // first_stage_model.encode(x); indices = info[2].view(b, -1).  The token-major fp32 latent of the encoder goes straight into the
@@ -1593,35 +1581,21 @@ int rdm_vq_encode_indices(rdm_ctx* c, const float* img, int b, int64_t* indices_
         return c->fail(-1, "rdm_vq_encode_indices: encoder and decoder were loaded with different cfgs (embed_dim %d / %d, resolution %d / %d)", q.embed_dim, d.embed_dim, q.resolution, d.resolution);
     if (!vq_nearest_supported(q.embed_dim)) return c->fail(-1, "rdm_vq_encode_indices: embed_dim %d not taken by the nearest-code kernel (multiples of 64 up to 512)", q.embed_dim);
     const float* cb = (const float*)(c->vq.blob + c->vq.codebook);
-    if (!c->code_norms) {
-        RDM_CHECK_HIP(c, hipMalloc((void**)&c->code_norms, (size_t)d.n_embed * sizeof(float)));
-        const hipError_t e = launch_vq_code_norms(cb, c->code_norms, d.n_embed, d.embed_dim, c->stream);
-        if (e != hipSuccess) { (void)hipFree(c->code_norms); c->code_norms = nullptr; return c->fail(-2, "codebook norms: %s", hipGetErrorString(e)); }
+    if (!c->vq.code_norms) {
+        RDM_CHECK_HIP(c, hipMalloc((void**)&c->vq.code_norms, (size_t)d.n_embed * sizeof(float)));
+        const hipError_t e = launch_vq_code_norms(cb, c->vq.code_norms, d.n_embed, d.embed_dim, c->stream);
+        if (e != hipSuccess) { (void)hipFree(c->vq.code_norms); c->vq.code_norms = nullptr; return c->fail(-2, "codebook norms: %s", hipGetErrorString(e)); }
     }
-    const int nb = vq_range(q, b), zr = q.resolution >> (q.n_ch_mult - 1), HW = zr * zr;
-    RDM_TRY(ensure_gn_partial(c, nb));
-    for (int b0 = 0; b0 < b; b0 += nb) {
-        const int n = b - b0 < nb ? b - b0 : nb;
-        RDM_TRY(run_with_arena(c, c->vqenc.arena, c->vqenc.blob, [&](Ops& o) {
-            const float* zt = vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, nullptr);
-            const long long M = (long long)n * HW;
-            char* ws = (char*)o.ar->alloc(vq_nearest_ws_bytes(M, d.n_embed));
-            int* idx32 = (int*)o.ar->alloc((size_t)M * 4);
-            o.vq_nearest(zt, cb, c->code_norms, M, d.n_embed, d.embed_dim, ws, idx32, (long long*)indices_out + (size_t)b0 * HW);
-            if (quant_out && !o.plan)
-                o.check(launch_vq_rows_to_nchw(cb, idx32, quant_out + (size_t)b0 * d.embed_dim * HW, n, HW, d.embed_dim, o.c->stream), "codebook rows to NCHW");
-        }));
-    }
-    return 0;
-}
-int rdm_load_clip(rdm_ctx* c, const rdm_clip_cfg* cfg, const void* packed, size_t nbytes) {
-    RDM_ENTER(c);
-    if (!c || !cfg) return -1;
-    if (cfg->transformer_width % 64 || cfg->vision_width % 64 || cfg->embed_dim % 8 ||
-        cfg->transformer_width / cfg->transformer_heads != 64)
-        return c->fail(-1, "unsupported clip cfg: widths %% 64 == 0 and 64-d heads required");
-    Manifest mf; build_clip(c->clip, *cfg, mf);
-    return load_blob(c, c->clip, mf, packed, nbytes);
+    const int zr = q.resolution >> (q.n_ch_mult - 1), HW = zr * zr;
+    return vq_walk(c, c->vqenc, b, true, [&](Ops& o, int b0, int n) {
+        const float* zt = vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, nullptr);
+        const long long M = (long long)n * HW;
+        char* ws = (char*)o.ar->alloc(vq_nearest_ws_bytes(M, d.n_embed));
+        int* idx32 = (int*)o.ar->alloc((size_t)M * 4);
+        o.vq_nearest(zt, cb, c->vq.code_norms, M, d.n_embed, d.embed_dim, ws, idx32, (long long*)indices_out + (size_t)b0 * HW);
+        if (quant_out && !o.plan)
+            o.check(launch_vq_rows_to_nchw(cb, idx32, quant_out + (size_t)b0 * d.embed_dim * HW, n, HW, d.embed_dim, o.c->stream), "codebook rows to NCHW");
+    });
 }
 
 static int unet_forward_impl(rdm_ctx* c, const float* x, const int64_t* t, const float* context, const bf16_t* kv_cached,
@@ -1897,16 +1871,11 @@ int rdm_vq_decode(rdm_ctx* c, const float* z, int b, int force_not_quantize, flo
     if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
     if (c->vq.wide) return c->fail(-1, "this first stage has a wide latent (VQGAN-f16): decode from code indices with rdm_vq_decode_indices");
     const rdm_vq_cfg& q = c->vq.cfg;
-    const int nb = vq_range(c->vq.cfg, b), zr = q.resolution >> (q.n_ch_mult - 1);
-    RDM_TRY(ensure_gn_partial(c, nb));
-    for (int b0 = 0; b0 < b; b0 += nb) {
-        const int n = b - b0 < nb ? b - b0 : nb;
-        RDM_TRY(run_with_arena(c, c->vq.arena, c->vq.blob, [&](Ops& o) {
-            vq_body(o, c->vq, z + (size_t)b0 * q.z_channels * zr * zr, n, force_not_quantize, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution,
-                    indices_out ? indices_out + (size_t)b0 * zr * zr : nullptr);
-        }));
-    }
-    return 0;
+    const int zr = q.resolution >> (q.n_ch_mult - 1);
+    return vq_walk(c, c->vq, b, true, [&](Ops& o, int b0, int n) {
+        vq_body(o, c->vq, z + (size_t)b0 * q.z_channels * zr * zr, n, force_not_quantize, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution,
+                indices_out ? indices_out + (size_t)b0 * zr * zr : nullptr);
+    });
 }
 int rdm_vq_quantize(rdm_ctx* c, const float* z, int b, float* zq_out, int32_t* indices_out) {
     RDM_ENTER(c);
@@ -1929,15 +1898,10 @@ int rdm_vq_decode_indices(rdm_ctx* c, const int64_t* indices, int b, float* img_
     if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
     if (!c->vq.wide || c->vq.cfg.kl) return c->fail(-1, "rdm_vq_decode_indices needs a VQGAN first stage with a wide latent (z_channels %% 64 == 0)");
     const rdm_vq_cfg& q = c->vq.cfg;
-    const int nb = vq_range(c->vq.cfg, b), zr = q.resolution >> (q.n_ch_mult - 1);
-    RDM_TRY(ensure_gn_partial(c, nb));
-    for (int b0 = 0; b0 < b; b0 += nb) {
-        const int n = b - b0 < nb ? b - b0 : nb;
-        RDM_TRY(run_with_arena(c, c->vq.arena, c->vq.blob, [&](Ops& o) {
-            vq_wide_body(o, c->vq, (const long long*)indices + (size_t)b0 * zr * zr, n, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution);
-        }));
-    }
-    return 0;
+    const int zr = q.resolution >> (q.n_ch_mult - 1);
+    return vq_walk(c, c->vq, b, true, [&](Ops& o, int b0, int n) {
+        vq_wide_body(o, c->vq, (const long long*)indices + (size_t)b0 * zr * zr, n, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution);
+    });
 }
 
 int rdm_to_uint8(rdm_ctx* c, const float* img, int b, int ch, int h, int w, uint8_t* out) {
@@ -2176,19 +2140,6 @@ static int rarm_seq_check(rdm_ctx* c, int b, int k, int positions) {
     RDM_TRY(rarm_check(c, b, k, positions));
     if (k > 128) return c->fail(-1, "the whole-sequence pass attends at most 128 neighbours per sequence, got k=%d", k);
     return 0;
-}
-long long rdm_rarm_manifest(const rdm_rarm_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) {
-    if (!cfg || cfg->depth < 1 || cfg->n_heads < 1) return -1;
-    RarmModel m; Manifest mf; build_rarm(m, *cfg, mf);
-    return write_manifest(mf, buf, buflen, blob_bytes);
-}
-int rdm_load_rarm(rdm_ctx* c, const rdm_rarm_cfg* cfg, const void* packed, size_t nbytes) {
-    RDM_ENTER(c);
-    if (!cfg) return c->fail(-1, "null cfg");
-    if (cfg->d_head != 64 || cfg->context_dim % 64 || cfg->sequence_length > 1024 || cfg->vocab_out % 2 || cfg->depth < 1)
-        return c->fail(-1, "unsupported rarm cfg: d_head == 64, context_dim %% 64 == 0, sequence_length <= 1024, even vocab_out required");
-    Manifest mf; build_rarm(c->rarm, *cfg, mf);
-    return load_blob(c, c->rarm, mf, packed, nbytes);
 }
 int rdm_rarm_forward(rdm_ctx* c, const int64_t* tokens, int b, int t, const float* context, int k, float* logits_out) {
     RDM_ENTER(c);

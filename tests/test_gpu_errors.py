@@ -85,6 +85,53 @@ def test_blob_and_shape_mismatches(fresh):
     assert torch.isfinite(z).all()
 
 
+def test_refused_load_leaves_the_loaded_model_usable(fresh):
+    """A load that is refused -- here for its blob size -- changes nothing: the model loaded before gives the same bits afterwards.
+    The refused cfg is the loaded one with one res block fewer per level, so a library that mixed the new layer graph with the old
+    blob would still read inside the blob and write the same output sizes: it shows as unequal outputs."""
+    from dataclasses import replace
+    from rdm_amd import packing
+    d = fresh.device
+    g = torch.Generator().manual_seed(11)
+    small = replace(ovq.tiny_vq_spec(), resolution=32); big = replace(small, num_res_blocks=small.num_res_blocks + 1)
+    blob = packing.pack("vq", spec_to_vq_cfg(big), ounet.synth_state_dict(ovq.vq_param_shapes(big), seed=5))
+    fresh.load_vq(spec_to_vq_cfg(big), blob)
+    z = (torch.randn(2, 3, big.z_res, big.z_res, generator=g) * 0.6).to(d)
+    img1 = fresh.vq_decode(z)
+    assert "manifest" in _err(lambda: fresh.load_vq(spec_to_vq_cfg(small), blob))
+    img2 = fresh.vq_decode(z)
+    assert img1.shape == (2, 3, 32, 32) and torch.isfinite(img1).all() and float(img1.abs().max()) > 0
+    assert torch.equal(img1, img2)
+
+    small = ounet.tiny_spec(); big = replace(small, num_res_blocks=small.num_res_blocks + 1)
+    blob = packing.pack("unet", spec_to_unet_cfg(big), ounet.synth_state_dict(ounet.param_shapes(big), seed=3))
+    fresh.load_unet(spec_to_unet_cfg(big), blob)
+    x = torch.randn(2, big.in_channels, 16, 16, generator=g).to(d); t = torch.tensor([10, 500], device=d)
+    c = (torch.randn(2, 4, big.context_dim, generator=g) * 0.45).to(d)
+    eps1 = fresh.unet_forward(x, t, c)
+    assert "manifest" in _err(lambda: fresh.load_unet(spec_to_unet_cfg(small), blob))
+    eps2 = fresh.unet_forward(x, t, c)
+    assert torch.isfinite(eps1).all() and float(eps1.abs().max()) > 0
+    assert torch.equal(eps1, eps2)
+
+
+def test_cfgs_the_builders_cannot_walk_are_refused_by_the_load_entries(fresh):
+    """Level counts outside the cfg's arrays and a zero head count are refused on the host with a message (no kernel runs): the
+    builders would index past ch_mult / divide by zero."""
+    from oracle import clip as oclip
+    from rdm_amd import _lib
+    from _util import spec_to_clip_cfg
+    blob = np.zeros(256, np.uint8)
+    for n in (0, _lib.RDM_MAX_LEVELS + 1):
+        for load in (fresh.load_vq, fresh.load_vq_encoder):
+            cfg = spec_to_vq_cfg(ovq.tiny_vq_spec()); cfg.n_ch_mult = n
+            assert "unsupported" in _err(lambda: load(cfg, blob))
+    cfg = spec_to_clip_cfg(oclip.tiny_clip_spec()); cfg.transformer_heads = 0
+    assert "unsupported clip cfg" in _err(lambda: fresh.load_clip(cfg, blob))
+    assert fresh.vq_cfg is None and fresh.vqenc_cfg is None and fresh.clip_cfg is None
+    assert "not loaded" in _err(lambda: fresh.vq_decode(torch.zeros(1, 3, 16, 16, device=fresh.device)))
+
+
 def test_no_device_memory_growth_across_calls_and_contexts():
     """hipMemGetInfo at the same point of three context lifetimes and over twelve rounds of every sampling entry (DDIM, VQ decode, online
     and bulk kNN, RARM sampling): the library's scratch is sized once and reused, and rdm_ctx_destroy gives everything back."""

@@ -144,6 +144,29 @@ def test_rarm_and_vqgan_manifests():
     assert sorted(s for e in e3 for s in e[3]) == sorted(ovq.vq_param_shapes(ovq.vqgan_f16_spec()))
 
 
+def test_manifests_are_byte_for_byte_the_recorded_ones():
+    """tests/golden/manifest_digests.json (tools/manifest_digests.py) holds, for all five model kinds and every cfg the suite loads,
+    the sha256 of the manifest text and blob_bytes: entry order, offsets, sizes, kinds and source keys of every blob layout stay
+    what packed checkpoints were written against."""
+    import hashlib
+    import json
+    import rdm_amd  # noqa: F401
+    from rdm_amd import _lib
+    rows = json.load(open(os.path.join(ROOT, "tests", "golden", "manifest_digests.json")))
+    assert {r["kind"] for r in rows} == {"unet", "vq", "vqenc", "clip", "rarm"} and len(rows) >= 25
+    types = {"unet": _lib.UNetCfg, "vq": _lib.VqCfg, "vqenc": _lib.VqCfg, "clip": _lib.ClipCfg, "rarm": _lib.RarmCfg}
+    for r in rows:
+        cfg = types[r["kind"]]()
+        assert sorted(r["cfg"]) == sorted(n for n, _ in cfg._fields_)
+        for name, v in r["cfg"].items():
+            if isinstance(v, list):
+                getattr(cfg, name)[:] = v
+            else:
+                setattr(cfg, name, v)
+        text, blob_bytes = _lib.manifest_text(r["kind"], cfg)
+        assert (hashlib.sha256(text.encode()).hexdigest(), blob_bytes) == (r["sha256"], r["blob_bytes"]), (r["kind"], r["cfg"])
+
+
 def test_ema_key_mapping():
     import rdm_amd  # noqa: F401
     from rdm_amd import packing
