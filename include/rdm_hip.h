@@ -453,6 +453,21 @@ int rdm_op_causal_attention_d64(rdm_ctx* ctx, const void* qkv_bf16, int ldq, int
 /* nll_out[r] = logsumexp(logits[r,:]) - logits[r, targets[r]] in fp32 (F.cross_entropy(reduction='none'), transformer.py:62-70):
  * logits f32 [rows, vocab] (vocab even), targets int64 [rows]; a target outside [0, vocab) gives NaN. */
 int rdm_op_rarm_nll(rdm_ctx* ctx, const float* logits, long long rows, int vocab, const int64_t* targets, float* nll_out);
+/* ---- RARM training (the backward of LatentImageRETRO.training_step, rdm/models/autoregression/transformer.py:46-57)
+ * Gradient of rdm_op_causal_attention_d64: the same qkv (stride ldq, a multiple of 8), out = the forward's bf16 output (stride ldo, a
+ * multiple of 4), dout bf16 [B*n, heads*64] (stride lddo, a multiple of 8) -> dqkv bf16 = dq | dk | dv in the layout of qkv (stride ldd, a
+ * multiple of 4; columns beyond 3*heads*64 are not touched).  1 <= n <= 1024; no n x n matrix in memory; fp32 accumulation; every element
+ * written once, so two calls agree bitwise.  Scratch: the context's backward scratch (rdm_release_scratch returns it). */
+int rdm_op_causal_attention_d64_bwd(rdm_ctx* ctx, const void* qkv_bf16, int ldq, const void* out_bf16, int ldo, const void* dout_bf16, int lddo,
+                                    int B, int n, int heads, float scale, void* dqkv_bf16, int ldd);
+/* dlogits[r,:] = gscale * (softmax(logits[r,:]) - onehot(targets[r])) (gscale = 1/rows: the gradient of the mean cross-entropy): fp32
+ * arithmetic, one rounding to bf16 [rows, vocab].  nll_out f32 [rows] or null: bitwise what rdm_op_rarm_nll gives.  vocab even; a target
+ * outside [0, vocab) gives NaN in its row. */
+int rdm_op_rarm_nll_bwd(rdm_ctx* ctx, const float* logits, long long rows, int vocab, const int64_t* targets, float gscale, void* dlogits_bf16,
+                        float* nll_out_or_null);
+/* Gradient of an embedding lookup: dw f32 [V, C], dw[v,:] = sum of dy[m,:] (bf16 [M, C]) over tokens[m] == v in ascending m; rows of unused
+ * ids are written as zero (no pre-clear), ids outside [0, V) are ignored.  No atomics: two calls agree bitwise.  C <= 12288. */
+int rdm_op_embedding_grad(rdm_ctx* ctx, const int64_t* tokens, const void* dy_bf16, int M, int C, int V, float* dw_f32);
 /* The UNet's `out` head (openaimodel.py:307-311: GroupNorm32 + SiLU + 3x3 conv to out_channels) and the VQ decoder's norm_out + swish +
  * conv_out as one statistics pass + one kernel: x bf16 NHWC [B, H, W, C] raw, 32 groups; gn_gamma / gn_beta null: no norm, x is convolved
  * as is.  w fp32 [Cout, C, 3, 3], bias fp32 [Cout] or null, out fp32 NCHW [B, Cout, H, W].  C % 32 == 0, C <= 240, W % 32 == 0, H even,

@@ -166,6 +166,9 @@ SIGNATURES = {
     "rdm_op_xattn_fused": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_causal_attention_d64": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P, _P, C.c_int]),
     "rdm_op_rarm_nll": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
+    "rdm_op_causal_attention_d64_bwd": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int]),
+    "rdm_op_rarm_nll_bwd": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, C.c_float, _P, _P]),
+    "rdm_op_embedding_grad": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_small_attention": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_float, _P, C.c_int]),
     "rdm_op_adamw_multi": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
@@ -1143,6 +1146,48 @@ class Context:
         self._check_ids("op_rarm_nll", targets, logits.shape[1], "targets")
         out = torch.empty((logits.shape[0],), device=self.device, dtype=torch.float32)
         self._check(lib.rdm_op_rarm_nll(self._h, _ptr(logits), logits.shape[0], logits.shape[1], _ptr(targets), _ptr(out)))
+        return out
+
+    def op_causal_attention_d64_bwd(self, qkv, out, dout, heads, scale):
+        """Gradient of op_causal_attention_d64: qkv bf16 [B,n,3*heads*64], out (the forward's output) and dout bf16 [B,n,heads*64] ->
+        dqkv bf16 [B,n,3*heads*64] = dq | dk | dv."""
+        B, n, C3 = qkv.shape
+        Cc = heads * 64
+        assert qkv.dtype == out.dtype == dout.dtype == torch.bfloat16 and C3 == 3 * Cc
+        if n < 1 or n > 1024:
+            raise RdmError(f"op_causal_attention_d64_bwd: 1 <= n <= 1024 required, got {n}")
+        if tuple(out.shape) != (B, n, Cc) or tuple(dout.shape) != (B, n, Cc):
+            raise RdmError(f"op_causal_attention_d64_bwd: out and dout must be [{B},{n},{Cc}], got {tuple(out.shape)} / {tuple(dout.shape)}")
+        dqkv = torch.empty((B, n, C3), device=self.device, dtype=torch.bfloat16)
+        self._check(lib.rdm_op_causal_attention_d64_bwd(self._h, _ptr(qkv), C3, _ptr(out), Cc, _ptr(dout), Cc, B, n, heads, float(scale), _ptr(dqkv), C3))
+        return dqkv
+
+    def op_rarm_nll_bwd(self, logits, targets, gscale, want_nll=False, out=None, nll_out=None):
+        """gscale * (softmax(logits) - onehot(targets)) as bf16 [rows,V]: logits f32 [rows,V] (V even), targets int64 [rows].
+        want_nll: -> (dlogits, nll f32 [rows]), the second bitwise op_rarm_nll's.  out / nll_out: contiguous tensors to write into."""
+        logits = self._dev(logits, torch.float32); targets = self._dev(targets, torch.int64)
+        if logits.ndim != 2 or logits.shape[1] % 2 or tuple(targets.shape) != (logits.shape[0],):
+            raise RdmError(f"op_rarm_nll_bwd: logits [rows, even V] and targets [rows] required, got {tuple(logits.shape)} / {tuple(targets.shape)}")
+        self._check_ids("op_rarm_nll_bwd", targets, logits.shape[1], "targets")
+        dl = out if out is not None else torch.empty(logits.shape, device=self.device, dtype=torch.bfloat16)
+        nll = nll_out if nll_out is not None else (torch.empty((logits.shape[0],), device=self.device, dtype=torch.float32) if want_nll else None)
+        assert dl.shape == logits.shape and dl.dtype == torch.bfloat16 and (nll is None or (nll.numel() == logits.shape[0] and nll.dtype == torch.float32))
+        want_nll = want_nll or nll_out is not None
+        self._check(lib.rdm_op_rarm_nll_bwd(self._h, _ptr(logits), logits.shape[0], logits.shape[1], _ptr(targets), float(gscale), _ptr(dl), _ptr(nll)))
+        return (dl, nll) if want_nll else dl
+
+    def op_embedding_grad(self, tokens, dy, V, out=None):
+        """Gradient of an embedding lookup: tokens int64 [M], dy bf16 [M,C] -> f32 [V,C], row v the sum of dy[m] over tokens[m] == v
+        (zero where the id is unused; `out` is overwritten whole)."""
+        tokens = self._dev(tokens, torch.int64).reshape(-1)
+        M, Cc = dy.shape
+        if tokens.numel() != M or dy.dtype != torch.bfloat16:
+            raise RdmError(f"op_embedding_grad: tokens [{M}] and dy bf16 [{M},{Cc}] required, got {tuple(tokens.shape)} / {dy.dtype}")
+        self._check_ids("op_embedding_grad", tokens, V, "tokens")
+        if out is None:
+            out = torch.empty((V, Cc), device=self.device, dtype=torch.float32)
+        assert tuple(out.shape) == (V, Cc) and out.dtype == torch.float32
+        self._check(lib.rdm_op_embedding_grad(self._h, _ptr(tokens), _ptr(dy), M, Cc, V, _ptr(out)))
         return out
 
     def op_small_attention(self, q, k, v, heads, D, causal, scale):

@@ -143,6 +143,10 @@ hipError_t launch_rarm_sample(const RarmSampleParams& p, hipStream_t st);
 hipError_t launch_rarm_embed_seq(const long long* tokens, int tok_ld, int tok_rows, int seq0, const float* emb, const float* pos_t, float* x, long long rows,
                                  int t, int C, int vocab, hipStream_t st);
 hipError_t launch_rarm_nll(const float* logits, long long rows, int vocab, const long long* targets, float* nll_out, hipStream_t st);
+// training (rarm.hip): gradient of the mean NLL w.r.t. the logits (bf16; nll_out optional, bitwise launch_rarm_nll's), gradient of the token embedding
+hipError_t launch_rarm_nll_bwd(const float* logits, long long rows, int vocab, const long long* targets, float gscale, bf16_t* dlogits, float* nll_out,
+                               hipStream_t st);
+hipError_t launch_embedding_grad(const long long* tokens, const bf16_t* dy, int M, int C, int V, float* dw, hipStream_t st);
 hipError_t launch_codebook_gather(const long long* idx, const float* codebook, int n_embed, int E, long long n, bf16_t* out, hipStream_t st);
 hipError_t launch_set_int(int* p, int v, hipStream_t st);
 
@@ -235,6 +239,10 @@ hipError_t launch_sumpool2(const bf16_t* x, bf16_t* out, int B, int H, int W, in
 size_t attn_bwd_scratch_bytes(int B, int H, int n, int m);
 hipError_t launch_attention_bwd(const bf16_t* q, const bf16_t* k, const bf16_t* v, const bf16_t* o, const bf16_t* dout, int B, int n, int m, int H,
                                 bf16_t* dq, bf16_t* dk, bf16_t* dv, char* scratch, hipStream_t st);
+// fused backward of the causal d_head = 64 attention (backward.hip) on the fused q | k | v projection: dqkv = dq | dk | dv
+size_t causal_attention_d64_bwd_scratch_bytes(int B, int H, int n);
+hipError_t launch_causal_attention_d64_bwd(const bf16_t* qkv, int ldq, const bf16_t* o, int ldo, const bf16_t* dout, int lddo, int B, int n, int H, float scale,
+                                           bf16_t* dqkv, int ldd, char* scratch, hipStream_t st);
 // attention backward helpers (backward.hip)
 hipError_t launch_heads(const bf16_t* x, bf16_t* out, int B, int n, int H, int D, int ldx, int mode, hipStream_t st);
 hipError_t launch_softmax_bwd(const bf16_t* P, const float* dP, bf16_t* dS, long long rows, int n, hipStream_t st);

@@ -2792,6 +2792,34 @@ int rdm_op_rarm_nll(rdm_ctx* c, const float* logits, long long rows, int vocab, 
     RDM_CHECK_HIP(c, launch_rarm_nll(logits, rows, vocab, (const long long*)targets, nll_out, c->stream));
     return 0;
 }
+int rdm_op_causal_attention_d64_bwd(rdm_ctx* c, const void* qkv, int ldq, const void* out, int ldo, const void* dout, int lddo, int B, int n, int heads,
+                                    float scale, void* dqkv, int ldd) {
+    RDM_ENTER(c);
+    if (!qkv || !out || !dout || !dqkv) return c->fail(-1, "rdm_op_causal_attention_d64_bwd: null argument");
+    if (B < 1 || n < 1 || n > 1024 || heads < 1) return c->fail(-1, "rdm_op_causal_attention_d64_bwd: bad shape B=%d n=%d heads=%d (1 <= n <= 1024)", B, n, heads);
+    const int C = heads * 64;
+    if (ldq % 8 || ldq < 3 * C || lddo % 8 || lddo < C || ldo % 4 || ldo < C || ldd % 4 || ldd < 3 * C)
+        return c->fail(-1, "rdm_op_causal_attention_d64_bwd: bad row pitch (ldq=%d, lddo=%d: multiples of 8; ldo=%d, ldd=%d: multiples of 4; each at least its %d or %d columns)",
+                       ldq, lddo, ldo, ldd, C, 3 * C);
+    RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, causal_attention_d64_bwd_scratch_bytes(B, heads, n)));
+    RDM_CHECK_HIP(c, launch_causal_attention_d64_bwd((const bf16_t*)qkv, ldq, (const bf16_t*)out, ldo, (const bf16_t*)dout, lddo, B, n, heads, scale, (bf16_t*)dqkv, ldd,
+                                                     c->bwd_tmp, c->stream));
+    return 0;
+}
+int rdm_op_rarm_nll_bwd(rdm_ctx* c, const float* logits, long long rows, int vocab, const int64_t* targets, float gscale, void* dlogits, float* nll_out) {
+    RDM_ENTER(c);
+    if (!logits || !targets || !dlogits) return c->fail(-1, "rdm_op_rarm_nll_bwd: null argument");
+    if (rows < 1 || vocab < 2 || vocab % 2) return c->fail(-1, "rdm_op_rarm_nll_bwd: rows >= 1 and an even vocabulary required (rows=%lld, vocab=%d)", rows, vocab);
+    RDM_CHECK_HIP(c, launch_rarm_nll_bwd(logits, rows, vocab, (const long long*)targets, gscale, (bf16_t*)dlogits, nll_out, c->stream));
+    return 0;
+}
+int rdm_op_embedding_grad(rdm_ctx* c, const int64_t* tokens, const void* dy, int M, int C, int V, float* dw) {
+    RDM_ENTER(c);
+    if (!tokens || !dy || !dw) return c->fail(-1, "rdm_op_embedding_grad: null argument");
+    if (M < 1 || C < 1 || C > 12288 || V < 1) return c->fail(-1, "rdm_op_embedding_grad: bad shape M=%d C=%d V=%d (M, V >= 1; 1 <= C <= 12288)", M, C, V);
+    RDM_CHECK_HIP(c, launch_embedding_grad((const long long*)tokens, (const bf16_t*)dy, M, C, V, dw, c->stream));
+    return 0;
+}
 int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int nq, int nkv,
                            int heads, int D, int causal, float scale, void* out, int ldo) {
     RDM_ENTER(c);

@@ -94,7 +94,111 @@ hipError_t launch_rarm_nll(const float* logits, long long rows, int vocab, const
     return hipGetLastError();
 }
 
-// ---------------------------------------------------------------- decode-step attention against a K/V cache (d_head = 64)
+// ---------------------------------------------------------------- gradient of the mean token NLL w.r.t. the logits
+// dlogits[r, j] = gscale (softmax(logits[r])[j] - [j == target[r]]): the backward of F.cross_entropy in LatentImageRETRO.compute_loss
+// (transformer.py:46-48; gscale = 1 / rows for its mean).  The maximum and the sum of exponentials are formed exactly as in
+// rarm_nll_kernel (same loads, same order), so the optional nll_out is bit for bit that kernel's.  The third pass walks the row in pairs
+// (V is even: 8-byte loads, 4-byte bf16x2 stores at any row): exp(x - max) / sum and the subtraction in fp32, one rounding to bf16.
+// A target outside [0, V) gives NaN in the whole row.
+__global__ __launch_bounds__(256) void rarm_nll_bwd_kernel(const float* logits, int V, const long long* targets, float gscale, bf16_t* dlogits, float* nll_out) {
+    __shared__ float red[8];
+    const long long r = blockIdx.x;
+    const int tid = threadIdx.x;
+    const float* row = logits + r * V;
+    int head = (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 2);
+    if (head > V) head = V;
+    const int nv = (V - head) >> 2, tail0 = head + nv * 4;
+    const float4* rv = (const float4*)(row + head);
+    float m = -INFINITY;
+    for (int i = tid; i < nv; i += 256) { const float4 v = rv[i]; m = fmaxf(fmaxf(m, fmaxf(v.x, v.y)), fmaxf(v.z, v.w)); }
+    if (tid < head) m = fmaxf(m, row[tid]);
+    if (tail0 + tid < V) m = fmaxf(m, row[tail0 + tid]);
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o));
+    if ((tid & 63) == 0) red[tid >> 6] = m;
+    __syncthreads();
+    m = fmaxf(fmaxf(red[0], red[1]), fmaxf(red[2], red[3]));
+    float s = 0.f;
+    for (int i = tid; i < nv; i += 256) { const float4 v = rv[i]; s += (expf(v.x - m) + expf(v.y - m)) + (expf(v.z - m) + expf(v.w - m)); }
+    if (tid < head) s += expf(row[tid] - m);
+    if (tail0 + tid < V) s += expf(row[tail0 + tid] - m);
+    s = rarm_block_sum_fixed(s, red + 4, tid);
+    const long long tg = targets[r];
+    const bool ok = tg >= 0 && tg < V;
+    if (tid == 0 && nll_out) nll_out[r] = ok ? (m + logf(s)) - row[tg] : NAN;
+    const float inv = ok ? 1.f / s : NAN;
+    const float2* rp = (const float2*)row;
+    uint32_t* dp = (uint32_t*)(dlogits + r * V);
+    const int tpair = ok ? (int)(tg >> 1) : -1;
+    for (int i = tid; i < (V >> 1); i += 256) {
+        const float2 v = rp[i];
+        float p0 = expf(v.x - m) * inv, p1 = expf(v.y - m) * inv;
+        if (i == tpair) { if (tg & 1) p1 -= 1.f; else p0 -= 1.f; }
+        dp[i] = pack2bf(p0 * gscale, p1 * gscale);
+    }
+}
+hipError_t launch_rarm_nll_bwd(const float* logits, long long rows, int vocab, const long long* targets, float gscale, bf16_t* dlogits, float* nll_out,
+                               hipStream_t st) {
+    if (rows < 1 || rows > 0x7fffffffLL || vocab < 2 || vocab % 2 || ((uintptr_t)logits & 7) || ((uintptr_t)dlogits & 3)) return hipErrorInvalidValue;
+    rarm_nll_bwd_kernel<<<(unsigned)rows, 256, 0, st>>>(logits, vocab, targets, gscale, dlogits, nll_out);
+    return hipGetLastError();
+}
+
+// ---------------------------------------------------------------- gradient of the token embedding
+// dw[v, :] = sum over m with tokens[m] == v of dy[m, :] (the backward of nn.Embedding proj_in, attention.py:252): fp32 [V, C], every row
+// written -- zero where no token has the id -- so the caller does not clear dw.  No atomics and a fixed order: a block owns VB consecutive
+// ids and keeps their fp32 rows in LDS, each (row, column) touched by ONE thread; it walks the tokens in chunks of 2048, a thread looking
+// at 8 consecutive ones, and adds the matching dy rows in ascending m (thread order through the waves' match masks, then the thread's
+// own positions in order).  Almost every chunk has no token of the block's ids and costs one barrier.  Ids outside [0, V) match no row.
+__global__ __launch_bounds__(256) void embedding_grad_kernel(const long long* __restrict__ tokens, const bf16_t* __restrict__ dy, int M, int C, int V, int VB,
+                                                             float* __restrict__ dw) {
+    extern __shared__ float eg_acc[];                       // [VB][C]
+    __shared__ unsigned long long hit[4];
+    __shared__ int found[256][8], nfound[256];
+    const int tid = threadIdx.x, v0 = blockIdx.x * VB, nv = min(VB, V - v0);
+    for (int i = tid; i < VB * C; i += 256) eg_acc[i] = 0.f;
+    for (int m0 = 0; m0 < M; m0 += 2048) {
+        int cnt = 0;
+#pragma unroll
+        for (int e = 0; e < 8; e++) {
+            const int m = m0 + tid * 8 + e;
+            if (m < M) {
+                const long long d = tokens[m] - v0;
+                if (d >= 0 && d < nv) found[tid][cnt++] = (e << 8) | (int)d;
+            }
+        }
+        nfound[tid] = cnt;
+        const unsigned long long mask = __ballot(cnt > 0);
+        if (__syncthreads_or(cnt) == 0) continue;           // also orders the LDS clear before the first accumulation
+        if ((tid & 63) == 0) hit[tid >> 6] = mask;
+        __syncthreads();
+        for (int w = 0; w < 4; w++) {
+            unsigned long long left = hit[w];
+            while (left) {
+                const int t = w * 64 + __ffsll((long long)left) - 1;
+                left &= left - 1;
+                const int nf = nfound[t];
+                for (int i = 0; i < nf; i++) {
+                    const int f = found[t][i];
+                    const int e = f >> 8, d = f & 255;
+                    const bf16_t* src = dy + (long long)(m0 + t * 8 + e) * C;
+                    for (int c = tid; c < C; c += 256) eg_acc[d * C + c] += bf2f(src[c]);
+                }
+            }
+        }
+        __syncthreads();                                    // found / nfound / hit are rewritten by the next chunk
+    }
+    __syncthreads();
+    for (int i = tid; i < nv * C; i += 256) dw[(long long)v0 * C + i] = eg_acc[i];
+}
+static int embedding_grad_vb(int C) { int vb = 12288 / C; return vb > 16 ? 16 : vb; }      // <= 48 KB of fp32 rows per block
+hipError_t launch_embedding_grad(const long long* tokens, const bf16_t* dy, int M, int C, int V, float* dw, hipStream_t st) {
+    if (M < 1 || C < 1 || C > 12288 || V < 1) return hipErrorInvalidValue;
+    const int VB = embedding_grad_vb(C);
+    embedding_grad_kernel<<<(V + VB - 1) / VB, 256, (size_t)VB * C * sizeof(float), st>>>(tokens, dy, M, C, V, VB, dw);
+    return hipGetLastError();
+}
+
 // One BLOCK of four waves per (head, sequence) (round 4; one wave before: its 2 x 8 chunk loops were 16 serialised round trips to
 // the cache, 12.8 us at 256 cached rows -- four waves take every fourth 32-row chunk, and a wave's first K and V chunks are requested
 // together before anything is computed).  Self-attention (attn1, causal): the new token's k / v rows are appended to the cache at

@@ -1,10 +1,14 @@
-"""Native counterpart of the SAMPLING and VALIDATION methods of rdm/models/autoregression/transformer.py::LatentImageRETRO (RARM):
+"""Native counterpart of the SAMPLING, VALIDATION and TRAINING methods of rdm/models/autoregression/transformer.py::LatentImageRETRO (RARM):
 `forward` (:213-222), `shared_step` (:207-211), `get_mask_prob` (:186-189), `compute_loss` / `validation_step` (:46-48, :65-70: the
 teacher-forced cross-entropy of an image's codes under its neighbours, one whole-sequence transformer pass), `sample` (:224-294), `sampling_util` (:296-312), `sample_from_rdata` (:314-404), `get_qids` (:407-430), `get_r` (:191-205),
 `log_images` (:422-478: full samples, image completion from the first half of an image's codes, samples under masked neighbours,
 reconstructions), and of the taming Net2NetTransformer pieces it inherits for them (`encode_to_z`, `encode_to_c` with the
 SOSProvider, `decode_to_img`, `top_k_logits`).
-Training (`training_step`: there is no backward of the transformer), the patch plotter of log_images and image-patch neighbour encoders are out of scope (the shipped
+`configure_optimizers` (:106-119) and `training_step` (:50-57) run one optimisation step on the native path (rdm_amd.training_rarm: the
+transformer's forward with saved activations, the mean cross-entropy, the backward to every parameter, AdamW(betas=(0.9, 0.95)) on fp32
+masters); `sync_sampling_weights` hands the trained weights to the sampling / validation kernels, `state_dict` returns them in the
+reference's layout.  The LambdaLR scheduler of :109-118 and the Lightning loop stay with the caller (`training_step(..., lr=)`).
+The patch plotter of log_images and image-patch neighbour encoders are out of scope (the shipped
 configs use IdentityEncoder on CLIP embeddings, models/rarm/imagenet/dogs/config.yaml:10-13).
 
 The transformer (rdm.modules.attention.RetrievalPatchTransformer, 18 x 768, causal self-attention + cross-attention to the k
@@ -19,7 +23,7 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-from ... import _lib, packing
+from ... import _lib, packing, training_rarm
 
 
 class LatentImageRETRO(object):
@@ -50,6 +54,8 @@ class LatentImageRETRO(object):
         if self.use_memory:
             self.nn_memory = torch.as_tensor(np.asarray(nn_memory))
         self.id_count = id_count
+        self._transformer_sd = None                    # the state dict last loaded (a reference, not a copy): configure_optimizers' default
+        self._train = None                             # (TrainState, shapes, optimiser settings) once configure_optimizers has run
 
     @property
     def ctx(self):
@@ -71,6 +77,7 @@ class LatentImageRETRO(object):
 
     def load_transformer_state_dict(self, tsd):
         self.ctx.load_rarm(self.rarm_cfg, packing.pack("rarm", self.rarm_cfg, tsd))
+        self._transformer_sd = tsd
 
     def load_first_stage_state_dict(self, fsd):
         """Decoder + codebook always; the encoder (`encoder.*`, `quant_conv.*`: encode_to_z, log_images) when the dict carries it."""
@@ -122,7 +129,7 @@ class LatentImageRETRO(object):
     def train_searcher(self):
         self.retriever.train_searcher()
 
-    # ---- transformer.py:186-189, 207-222, 46-70: the teacher-forced pass (validation; no backward, so no training_step)
+    # ---- transformer.py:186-189, 207-222, 46-70: the teacher-forced pass (validation)
     def get_mask_prob(self):
         return np.random.uniform(0., self.p_mask_max)
 
@@ -165,9 +172,54 @@ class LatentImageRETRO(object):
         r = self.get_r(batch, p_mask=self.get_mask_prob())
         return {"val/loss": self.nll(x, r).mean()}
 
-    def training_step(self, batch, batch_idx):
-        raise NotImplementedError("LatentImageRETRO.training_step: the RARM transformer has no native backward pass (validation_step, nll and "
-                                  "forward are available)")
+    # ---- transformer.py:106-119, 50-57: the optimisation step (rdm_amd.training_rarm)
+    def configure_optimizers(self, transformer_sd=None, lr=None, betas=(0.9, 0.95), eps=1e-8, weight_decay=1e-2):
+        """:106-107: AdamW(self.transformer.parameters(), lr=self.learning_rate, betas=(0.9, 0.95)) with torch's eps and weight decay,
+        on every transformer parameter.  Builds the train state -- fp32 masters and moments, bf16 working copies -- from `transformer_sd`
+        (default: the state dict last loaded).  `lr` (default 1e-4) is what a step uses when it is not given one; the LambdaLR scheduler
+        of :109-118 is the caller's."""
+        sd = transformer_sd if transformer_sd is not None else self._transformer_sd
+        if sd is None:
+            raise RuntimeError("LatentImageRETRO.configure_optimizers: no transformer weights (load_state_dict / load_transformer_state_dict first, "
+                               "or pass transformer_sd)")
+        sd = packing.strip_prefix(sd, "transformer.") or sd
+        shapes = {k: tuple(torch.as_tensor(v).shape) for k, v in sd.items()}
+        state = training_rarm.TrainState(training_rarm.params_from_state_dict(sd, self.device))
+        self._train = {"state": state, "shapes": shapes, "lr": 1e-4 if lr is None else float(lr), "betas": tuple(betas), "eps": float(eps),
+                       "weight_decay": float(weight_decay)}
+        return state
+
+    def training_step(self, batch, batch_idx, lr=None):
+        """:50-57 with the optimiser step of the training loop: shared_step's inputs (get_xc, encode_to_z, get_r under get_mask_prob()),
+        the transformer input sos + codes[:, :-1], the mean cross-entropy, backward, AdamW.  -> the loss BEFORE the update (a float).
+        The sampling / validation kernels keep the weights they were loaded with until sync_sampling_weights()."""
+        if self._train is None:
+            raise NotImplementedError("LatentImageRETRO.training_step: the native backward pass is set up by configure_optimizers() -- call it "
+                                      "first (validation_step, nll and forward need no set-up)")
+        x, c = self.get_xc(batch)
+        r = self.get_r(batch, p_mask=self.get_mask_prob())
+        tokens, target, nc = self._teacher_tokens(x, c)
+        assert nc == 1                                                      # the SOS provider: one conditioning token (encode_to_c)
+        tr = self._train
+        return training_rarm.rarm_training_step(self.ctx, tr["state"], self.rarm_cfg, tokens, target, r, lr=tr["lr"] if lr is None else float(lr),
+                                                betas=tr["betas"], eps=tr["eps"], weight_decay=tr["weight_decay"])
+
+    def state_dict(self):
+        """The trained `transformer.*` tensors in the reference's layout (host fp32); before configure_optimizers: the loaded ones."""
+        if self._train is None:
+            if self._transformer_sd is None:
+                raise RuntimeError("LatentImageRETRO.state_dict: no transformer weights loaded")
+            return {"transformer." + k: torch.as_tensor(v) for k, v in self._transformer_sd.items()}
+        sd = training_rarm.state_dict_from_params(self._train["state"].P, self._train["shapes"])
+        return {"transformer." + k: v for k, v in sd.items()}
+
+    def sync_sampling_weights(self):
+        """Re-pack the live (trained) weights and load them into the library: validation_step, nll, forward and sample see the trained model."""
+        if self._train is None:
+            raise RuntimeError("LatentImageRETRO.sync_sampling_weights: configure_optimizers() has not run")
+        tsd = training_rarm.state_dict_from_params(self._train["state"].P, self._train["shapes"])
+        self.ctx.load_rarm(self.rarm_cfg, packing.pack("rarm", self.rarm_cfg, tsd))
+        self._transformer_sd = tsd
 
     # ---- transformer.py:224-294
     @torch.no_grad()

@@ -122,13 +122,20 @@ def ff_backward(ctx, p, x, saved, dout):
     return g
 
 
-def attention_forward(ctx, q, k, v, heads):
+def attention_forward(ctx, q, k, v, heads, causal=False):
     """ldm CrossAttention core (attention.py:52-72): per head softmax(q k^T / sqrt(d)) v.  q [B, n, C], k / v [B, m, C] bf16 (already
-    projected), C = heads * d, d <= 64, n and m multiples of 4 -> (out [B, n, C] bf16, saved)."""
+    projected), C = heads * d, d <= 64 -> (out [B, n, C] bf16, saved).  causal=True (RetrievalPatchTransformer's self-attention,
+    rdm/modules/attention.py:58-65; d = 64, m = n <= 1024): the fused causal kernel on [q | k | v], no score matrix."""
     B, n, C = q.shape
     d = C // heads
     scale = d ** -0.5
     m = k.shape[1]
+    if causal:
+        if d != 64 or m != n:
+            raise NotImplementedError(f"causal attention: d_head = 64 self-attention only (d_head {d}, n {n}, m {m})")
+        qkv = torch.cat([q, k, v], dim=-1)
+        out = ctx.op_causal_attention_d64(qkv, heads, scale)
+        return out, {"causal": True, "qkv": qkv, "o": out}
     if d == 32 and m == n and n % 64 == 0 and not _UNFUSED_ATTENTION_BWD:
         # self-attention at the UNet's head width: the sampling path's flash kernel on [q | k | v] (V token-major, transposed inside
         # the kernel's LDS reads); the fused backward needs only q, k, v, the output and its gradient
@@ -140,12 +147,15 @@ def attention_forward(ctx, q, k, v, heads):
         out = ctx.op_small_attention(q.contiguous(), k.contiguous(), v.contiguous(), heads, 32, False, scale)
         return out, {"small": True}
     k, v = _pad_keys(k), _pad_keys(v)                                                   # key count -> multiple of 64 (a GEMM K unit); padding gets probability 0
+    q = _pad_keys(q)                                                                    # query count too (the K unit of dV / dK); zero rows, sliced off below
     qp, kp = ctx.op_heads(q, heads, d, 0), ctx.op_heads(k, heads, d, 0)                # [BH, n|mp, 64]
     vt = ctx.op_heads(v, heads, d, 1)                                                   # [BH, 64, mp]
     s = ctx.op_bmm(qp, kp, alpha=scale, out_f32=True)                                   # [BH, n, mp] fp32
     p = ctx.op_softmax(s, n_valid=m)
     o = ctx.op_bmm(p, vt)                                                               # [BH, n, 64]
     out = ctx.op_heads(o, heads, d, 2)
+    if out.shape[1] != n:
+        out = out[:, :n].contiguous()
     return out, {"p": p, "kpad": k, "vpad": v, "m": m, "o": out}
 
 
@@ -154,6 +164,9 @@ def attention_backward(ctx, q, k, v, heads, saved, dout):
     B, n, C = q.shape
     d = C // heads
     scale = d ** -0.5
+    if saved.get("causal"):
+        dqkv = ctx.op_causal_attention_d64_bwd(saved["qkv"], saved["o"], dout.contiguous(), heads, scale)
+        return {"q": dqkv[..., :C].contiguous(), "k": dqkv[..., C:2 * C].contiguous(), "v": dqkv[..., 2 * C:].contiguous()}
     if d == 32 and n % 32 == 0 and k.shape[1] % 32 == 0 and "o" in saved and not _UNFUSED_ATTENTION_BWD:
         dq, dk, dv = ctx.op_attention_bwd(q.contiguous(), k.contiguous(), v.contiguous(), saved["o"], dout.contiguous(), heads)     # fused: no score matrix
         return {"q": dq, "k": dk, "v": dv}
@@ -161,6 +174,7 @@ def attention_backward(ctx, q, k, v, heads, saved, dout):
         dq, dk, dv = ctx.op_small_attention_bwd(q.contiguous(), k.contiguous(), v.contiguous(), dout.contiguous(), heads, scale)
         return {"q": dq, "k": dk, "v": dv}
     p, k, v, m = saved["p"], saved["kpad"], saved["vpad"], saved["m"]
+    q, dout = _pad_keys(q), _pad_keys(dout)                                             # zero query rows: P^T dO, dS = P (0 - 0) add nothing
     dop, dot_ = ctx.op_heads(dout, heads, d, 0), ctx.op_heads(dout, heads, d, 1)        # [BH, n, 64], [BH, 64, n]
     vp = ctx.op_heads(v, heads, d, 0)                                                   # [BH, m, 64]
     dv = ctx.op_bmm(ctx.op_transpose_batched(p), dot_)                                  # [BH, m, 64]
@@ -169,15 +183,26 @@ def attention_backward(ctx, q, k, v, heads, saved, dout):
     kt, qt = ctx.op_heads(k, heads, d, 1), ctx.op_heads(q, heads, d, 1)                 # [BH, 64, m], [BH, 64, n]
     dq = ctx.op_bmm(ds, kt, alpha=scale)                                                # [BH, n, 64]
     dk = ctx.op_bmm(ctx.op_transpose_batched(ds), qt, alpha=scale)                      # [BH, m, 64]
-    return {"q": ctx.op_heads(dq, heads, d, 2), "k": ctx.op_heads(dk, heads, d, 2)[:, :m].contiguous(), "v": ctx.op_heads(dv, heads, d, 2)[:, :m].contiguous()}
+    return {"q": ctx.op_heads(dq, heads, d, 2)[:, :n].contiguous(), "k": ctx.op_heads(dk, heads, d, 2)[:, :m].contiguous(), "v": ctx.op_heads(dv, heads, d, 2)[:, :m].contiguous()}
 
 
-def attn_block_forward(ctx, p, x, context=None):
+def attn_block_forward(ctx, p, x, context=None, causal=False):
     """One attention residual branch of BasicTransformerBlock: out = x + to_out(attention(to_q(norm(x)), to_k(c), to_v(c))) with
     c = norm(x) (self-attention, attn1) or the conditioning `context` [B, m, Cc] (cross-attention, attn2); attention.py:84-96, 52-72.
-    x bf16 [B, n, C]; p: ln_g / ln_b f32, wq [C, C], wk / wv [C, Cc] bf16 (no bias), wo [C, C] bf16, bo f32, heads."""
+    x bf16 [B, n, C]; p: ln_g / ln_b f32, wq [C, C], wk / wv [C, Cc] bf16 (no bias), wo [C, C] bf16, bo f32, heads.
+    causal=True (self-attention at d_head 64 under the causal mask): ONE projection with the fused [3C, C] weight rows q | k | v, whose
+    output the causal kernel and its backward read in place; the backward splits the fused weight gradient into wq / wk / wv."""
     B, n, C = x.shape
     ln = ctx.op_layernorm(x.reshape(B * n, C), p["ln_g"], p["ln_b"])
+    if causal:
+        heads = p["heads"]
+        if context is not None or C != heads * 64:
+            raise NotImplementedError(f"causal attention block: self-attention at d_head = 64 only (C {C}, heads {heads})")
+        wqkv = torch.cat([p["wq"], p["wk"], p["wv"]], dim=0)
+        qkv = ctx.op_linear(ln, wqkv).reshape(B, n, 3 * C)
+        att = ctx.op_causal_attention_d64(qkv, heads, 64 ** -0.5)
+        out = ctx.op_linear(att.reshape(B * n, C), p["wo"], p["bo"], residual=x.reshape(B * n, C)).reshape(B, n, C)
+        return out, {"causal": True, "ln": ln, "qkv": qkv, "att": att, "wqkv": wqkv}
     c = ln if context is None else context.reshape(-1, context.shape[-1])
     m = n if context is None else context.shape[1]
     q = ctx.op_linear(ln, p["wq"]).reshape(B, n, C)
@@ -195,6 +220,13 @@ def attn_block_backward(ctx, p, x, saved, dout, context=None):
     g = {}
     dflat = dout.reshape(B * n, C)
     datt, g["wo"], g["bo"] = linear_backward(ctx, saved["att"].reshape(B * n, C), p["wo"], dflat)
+    if saved.get("causal"):
+        dqkv = ctx.op_causal_attention_d64_bwd(saved["qkv"], saved["att"], datt.reshape(B, n, C), p["heads"], 64 ** -0.5)
+        dln, dw, _ = linear_backward(ctx, saved["ln"], saved["wqkv"], dqkv.reshape(B * n, 3 * C), bias=False)
+        g["wq"], g["wk"], g["wv"] = dw[:C], dw[C:2 * C], dw[2 * C:]
+        dx, g["ln_g"], g["ln_b"] = ctx.op_layernorm_bwd(x.reshape(B * n, C), dln, p["ln_g"], residual=dflat.contiguous())
+        g["x"] = dx.reshape(B, n, C)
+        return g
     d = attention_backward(ctx, saved["q"], saved["k"], saved["v"], p["heads"], saved, datt.reshape(B, n, C))
     c = saved["ln"] if context is None else context.reshape(-1, context.shape[-1])
     m = saved["k"].shape[1]
