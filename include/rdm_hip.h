@@ -82,6 +82,18 @@ typedef struct {
     int T; const float* alphas_cumprod; /* [host] */
 } rdm_ddim_args;
 
+/* DPM-Solver++(2M) arguments (Lu et al. 2022, "DPM-Solver++: Fast Solver for Guided Sampling of Diffusion Probabilistic Models";
+ * ldm models/diffusion/dpm_solver/sampler.py): the multistep data-prediction solver on an explicit list of integer timesteps. */
+typedef struct {
+    int batch, k, channels, height, width;
+    float unconditional_guidance_scale;   /* >= 1; > 1 enables CFG batch doubling */
+    int order;             /* 1 (= DDIM with eta 0) | 2 (2M) */
+    int lower_order_final; /* the last step is first order (recommended below 15 steps) */
+    int log_every_t;       /* intermediates rule of the DDIM loop over n_nodes - 1 steps */
+    int T; const float* alphas_cumprod; /* [host] the model's fp32 buffer [T] */
+    int n_nodes; const int* nodes;      /* [host] strictly decreasing timesteps in [0, T-1]; the UNet runs at nodes[0 .. n_nodes-2] */
+} rdm_dpmpp_args;
+
 /* ldm LatentDiffusion.p_sample_loop arguments (reached from rdm/models/diffusion/ddpm.py:1008). */
 typedef struct {
     int timesteps;         /* loop runs reversed(range(timesteps)) */
@@ -155,6 +167,21 @@ int rdm_ddim_sample(rdm_ctx* ctx, const rdm_ddim_args* args, const float* x_T, c
  * (n_inter = rdm_ddim_num_intermediates), pred_x0_inter holding the pred_x0 of the combined eps. */
 int rdm_plms_sample(rdm_ctx* ctx, const rdm_ddim_args* args, const float* x_T, const float* cond, const float* uncond,
                     float* z_out, float* x_inter, float* pred_x0_inter);
+/* DPM-Solver++(2M) (Lu et al. 2022; ldm models/diffusion/dpm_solver/sampler.py, multistep "dpmsolver++") on integer timesteps.  With
+ * a = alphas_cumprod[t] in float64, alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(a / (1 - a)) / 2, step j goes from
+ * s = nodes[j] to t = nodes[j+1]: m_j = (x - sigma_s eps) / alpha_s with the guided eps, h_j = lambda_t - lambda_s,
+ * D = (1 + 1/(2r)) m_j - (1/(2r)) m_{j-1} with r = h_{j-1} / h_j when order == 2, j >= 1 and not (lower_order_final and the last step),
+ * else D = m_j; x <- (sigma_t / sigma_s) x - alpha_t expm1(-h_j) D.  n_nodes - 1 UNet forwards; the result lives at the noise level of
+ * nodes[n_nodes-1].  Order 1 is DDIM with eta = 0.  pred_x0_inter holds m_j; the intermediates follow the DDIM rule over
+ * n_nodes - 1 steps (n_inter = rdm_ddim_num_intermediates(n_nodes - 1, log_every_t)).  Other arguments as rdm_plms_sample. */
+int rdm_dpmpp_sample(rdm_ctx* ctx, const rdm_dpmpp_args* args, const float* x_T, const float* cond, const float* uncond,
+                     float* z_out, float* x_inter, float* pred_x0_inter);
+/* Node lists for rdm_dpmpp_sample, host code only (ctx-free).  skip_type 0 (time_uniform): DDIM's S-step timesteps descending, then 0
+ * (S / T as rdm_ddim_sample).  skip_type 1 (logSNR): S + 1 targets uniform in lambda from lambda(T-1) to lambda(0), each rounded to the
+ * timestep of nearest lambda (ties to the smaller t), duplicates dropped, 0 appended when missing -- fewer than S steps when targets
+ * collide.  nodes_out holds S + 1 entries (time_uniform with an S that does not divide T: ceil(T / (T / S)) + 1); returns the number of
+ * nodes written, or a negative value for bad arguments. */
+int rdm_dpmpp_timesteps(const float* alphas_cumprod, int T, int S, int skip_type, int* nodes_out);
 /* ldm LatentDiffusion.p_sample_loop / p_sample (no CFG on this path).
  * noise [dev] f32 [timesteps,B,C,H,W], consumed in loop order. */
 int rdm_ddpm_sample(rdm_ctx* ctx, const rdm_ddpm_args* args, const float* x_T, const float* cond, const float* noise,
@@ -362,6 +389,12 @@ int rdm_op_linear_wgrad(rdm_ctx* ctx, const void* dy_bf16, const void* a_bf16, f
 int rdm_op_colsum(rdm_ctx* ctx, const void* x_bf16 /*[M,N]*/, float* out /*[N]*/, long long M, int N);
 int rdm_op_transpose(rdm_ctx* ctx, const void* x_bf16 /*[rows,cols]*/, void* y_bf16 /*[cols,rows]*/, int rows, int cols);
 int rdm_op_add(rdm_ctx* ctx, const void* a_bf16, const void* b_bf16, void* out_bf16, long long n);
+/* One DPM-Solver++ update, the kernel of rdm_dpmpp_sample alone (fp32, n elements): e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i])
+ * : eps[i]; m0 = (x - sqrt_one_minus_a_s e) / sqrt_a_s; x_out = c_x x + c_0 m0 + c_1 m_prev (no m_prev: the last term is absent);
+ * x_dup <- x_out, m_store <- m0, pred_x0 <- m0.  m_store may be m_prev itself. */
+int rdm_op_dpmpp_step(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, long long n, int cfg, float scale,
+                      float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup_or_null,
+                      float* m_store_or_null, float* pred_x0_or_null);
 /* Elementwise pieces of the UNet's training graph: SiLU of the time-embedding MLP (`nn.SiLU()` in
  * openaimodel.py time_embed / emb_layers) -- dy null: out bf16 = silu(x), else out fp32 = dy * silu'(x) -- and the 2 x 2 sum pooling
  * that is the gradient of Upsample's nearest-neighbour F.interpolate: x bf16 [B, 2H, 2W, C] -> out bf16 [B, H, W, C]. */

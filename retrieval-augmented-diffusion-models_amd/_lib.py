@@ -55,6 +55,16 @@ class DdimArgs(C.Structure):
                 ("alphas_cumprod", C.POINTER(C.c_float))]
 
 
+class DpmppArgs(C.Structure):
+    _fields_ = [("batch", C.c_int), ("k", C.c_int), ("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
+                ("unconditional_guidance_scale", C.c_float), ("order", C.c_int), ("lower_order_final", C.c_int),
+                ("log_every_t", C.c_int), ("T", C.c_int), ("alphas_cumprod", C.POINTER(C.c_float)), ("n_nodes", C.c_int),
+                ("nodes", C.POINTER(C.c_int))]
+
+
+DPMPP_SKIP_TYPES = {"time_uniform": 0, "logSNR": 1}
+
+
 class DdpmArgs(C.Structure):
     _fields_ = [("timesteps", C.c_int), ("batch", C.c_int), ("k", C.c_int), ("channels", C.c_int), ("height", C.c_int),
                 ("width", C.c_int), ("clip_denoised", C.c_int), ("temperature", C.c_float), ("T", C.c_int),
@@ -90,6 +100,8 @@ SIGNATURES = {
     "rdm_ddim_num_intermediates": (C.c_int, [C.c_int, C.c_int]),
     "rdm_ddim_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, _P, _P, _P, _P]),
     "rdm_plms_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, _P, _P, _P]),
+    "rdm_dpmpp_sample": (C.c_int, [_P, C.POINTER(DpmppArgs), _P, _P, _P, _P, _P, _P]),
+    "rdm_dpmpp_timesteps": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rdm_ddpm_sample": (C.c_int, [_P, C.POINTER(DdpmArgs), _P, _P, _P, _P]),
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
@@ -143,6 +155,8 @@ SIGNATURES = {
     "rdm_op_colsum": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int]),
     "rdm_op_transpose": (C.c_int, [_P, _P, _P, C.c_int, C.c_int]),
     "rdm_op_add": (C.c_int, [_P, _P, _P, _P, C.c_longlong]),
+    "rdm_op_dpmpp_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                    _P, _P, _P, _P]),
     "rdm_op_geglu": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int]),
     "rdm_op_linear_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "rdm_op_linear_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
@@ -315,6 +329,27 @@ def check_top_p(what, top_p):
     if not (0.0 < v <= 1.0):                                   # NaN fails both comparisons
         raise RdmError(f"{what}: top_p must lie in (0, 1], got {top_p!r}")
     return None if v == 1.0 else v
+
+
+def _acp_array(alphas_cumprod):
+    return np.ascontiguousarray(alphas_cumprod.detach().cpu().numpy() if isinstance(alphas_cumprod, torch.Tensor) else alphas_cumprod,
+                                dtype=np.float32)
+
+
+def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):
+    """Node list for Context.dpmpp_sample (rdm_dpmpp_timesteps; host code, no context needed): "time_uniform" = DDIM's S-step
+    timesteps descending, then 0; "logSNR" = uniform in logSNR from T - 1 to 0, rounded to integer timesteps (may come out shorter
+    than S steps when targets collide).  -> int32 numpy array, strictly decreasing, ending in 0."""
+    if skip_type not in DPMPP_SKIP_TYPES:
+        raise RdmError(f"dpmpp_timesteps: skip_type must be one of {sorted(DPMPP_SKIP_TYPES)}, got {skip_type!r}")
+    ac = _acp_array(alphas_cumprod)
+    T, S = ac.shape[0], int(S)
+    out = np.empty((max(S, len(range(0, T, max(T // max(S, 1), 1)))) + 1,), dtype=np.int32)
+    n = lib.rdm_dpmpp_timesteps(ac.ctypes.data_as(C.POINTER(C.c_float)), T, S, DPMPP_SKIP_TYPES[skip_type],
+                                out.ctypes.data_as(C.POINTER(C.c_int)))
+    if n < 2:
+        raise RdmError(f"dpmpp_timesteps: bad arguments (S={S}, T={T}, skip_type={skip_type!r})")
+    return out[:n].copy()
 
 
 class Context:
@@ -561,8 +596,7 @@ class Context:
         x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
         uncond = None if uncond is None else self._dev(uncond, torch.float32)
         noise = None if noise is None else self._dev(noise, torch.float32)
-        ac = np.ascontiguousarray(alphas_cumprod.detach().cpu().numpy() if isinstance(alphas_cumprod, torch.Tensor)
-                                  else alphas_cumprod, dtype=np.float32)
+        ac = _acp_array(alphas_cumprod)
         total = len(range(0, ac.shape[0], max(ac.shape[0] // max(int(S), 1), 1)))
         self._check_sampler_shapes(what, x_T, cond, uncond, noise if eta != 0.0 else None, total)
         if scale > 1.0 and uncond is None:
@@ -590,6 +624,50 @@ class Context:
         (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
         return self._ddim_call("plms_sample", lambda h, a, x, c, u, noise, *out: lib.rdm_plms_sample(h, a, x, c, u, *out),
                                S, x_T, cond, uncond, alphas_cumprod, 0.0, scale, None, log_every_t, 1.0, want_intermediates)
+
+    @staticmethod
+    def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):
+        return dpmpp_timesteps(S, alphas_cumprod, skip_type)
+
+    def dpmpp_sample(self, nodes, x_T, cond, uncond, alphas_cumprod, scale=1.0, order=2, lower_order_final=None, log_every_t=100,
+                     want_intermediates=False):
+        """DPM-Solver++(2M) (order 1: DDIM with eta = 0) over the strictly decreasing integer timesteps `nodes` (dpmpp_timesteps builds
+        the two grids): len(nodes) - 1 UNet forwards, the result at the noise level of nodes[-1].  lower_order_final None: on below 15
+        steps.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
+        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
+        uncond = None if uncond is None else self._dev(uncond, torch.float32)
+        ac = _acp_array(alphas_cumprod)
+        nd = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
+        n_steps = nd.shape[0] - 1
+        self._check_sampler_shapes("dpmpp_sample", x_T, cond, uncond)
+        if scale > 1.0 and uncond is None:
+            raise RdmError("dpmpp_sample: unconditional_conditioning is required when unconditional_guidance_scale > 1")
+        if lower_order_final is None:
+            lower_order_final = n_steps < 15
+        B, Cc, H, W = x_T.shape
+        a = DpmppArgs(batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, unconditional_guidance_scale=scale, order=int(order),
+                      lower_order_final=int(bool(lower_order_final)), log_every_t=log_every_t, T=ac.shape[0],
+                      alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)), n_nodes=nd.shape[0],
+                      nodes=nd.ctypes.data_as(C.POINTER(C.c_int)))
+        z = torch.empty_like(x_T)
+        xi = pi = None
+        if want_intermediates:
+            n = lib.rdm_ddim_num_intermediates(n_steps, log_every_t)
+            xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
+            pi = torch.empty_like(xi)
+        self._check(lib.rdm_dpmpp_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
+        return z, xi, pi
+
+    def op_dpmpp_step(self, x, eps, m_prev, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, x_out, x_dup=None, m_store=None,
+                      pred_x0=None):
+        """The DPM-Solver++ update kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
+        [cond | uncond]); m_prev / x_dup / m_store / pred_x0 may be None, m_store may be m_prev.  Writes into the given outputs."""
+        n = x.numel()
+        if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in (m_prev, x_out, x_dup, m_store, pred_x0)):
+            raise RdmError("op_dpmpp_step: operand sizes do not match x")
+        self._check(lib.rdm_op_dpmpp_step(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), n, int(bool(cfg)), float(scale), float(sqrt_a_s),
+                                          float(sqrt_one_minus_a_s), float(c_x), float(c_0), float(c_1), _ptr(x_out), _ptr(x_dup),
+                                          _ptr(m_store), _ptr(pred_x0)))
 
     def ddpm_sample(self, timesteps, x_T, cond, noise, sched, clip_denoised=True, temperature=1.0):
         x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32); noise = self._dev(noise, torch.float32)

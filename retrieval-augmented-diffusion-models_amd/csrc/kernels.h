@@ -99,6 +99,19 @@ struct PlmsStepParams {
     int cfg, mode, order;
 };
 
+// One DPM-Solver++ step (Lu et al. 2022, multistep data prediction; ldm models/diffusion/dpm_solver): e = CFG(eps),
+// m0 = (x - sqrt_one_minus_a_s e) / sqrt_a_s -> m_store, pred_x0; x_out = c_x x + c_0 m0 + c_1 m_prev.  The host flattens the solver's
+// D = (1 + 1/(2r)) m0 - (1/(2r)) m_prev into c_0, c_1 (first-order step: m_prev null, c_1 unused).  m_store may be the very slot m_prev
+// points to: each thread reads its elements of m_prev before it writes m_store, so ONE history slot serves the whole loop.
+struct DpmppStepParams {
+    const float* x; const float* eps;                        // eps: [n] rows (cfg == 0) or [2n] (cond | uncond)
+    const float* m_prev;                                     // the previous step's m0, or null
+    float* x_out; float* x_dup; float* m_store; float* pred_x0;     // x_dup, m_store, pred_x0 may be null
+    long long n;                                             // B*C*H*W
+    float sqrt_a_s, sqrt_one_minus_a_s, scale, c_x, c_0, c_1;
+    int cfg;
+};
+
 struct DdpmStepParams {
     const float* x; const float* eps; const float* noise; float* x_prev; long long n;
     float sqrt_recip, sqrt_recipm1, coef1, coef2, log_var; int clip, nonzero; float temperature;
@@ -252,6 +265,7 @@ hipError_t launch_row_nonzero(const float* x, int rows, long long n, int* flag, 
 hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st);
 hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
+hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);
 hipError_t launch_vq_quantize(const float* z, const float* codebook, int n_embed, const float* pq_w, const float* pq_b,
                               float* out, int* idx_out, int B, int HW, int quantize, hipStream_t st);
 // nearest-code search of a wide-latent VQ first stage (vqcode.hip): idx[m] = argmin_j |e_j|^2 - 2 z_m . e_j on fp32-input MFMAs, first minimum on ties

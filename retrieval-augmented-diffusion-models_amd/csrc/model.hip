@@ -1667,16 +1667,25 @@ static int prepare_kv(rdm_ctx* c, float* cat, const float* cond, const float* un
     });
 }
 
+// ldm make_ddim_timesteps 'uniform', ascending (ddim_schedule and rdm_dpmpp_timesteps' time_uniform grid both take their list from
+// here).  Returns 0, -1 for an S outside [1, T], or the first timestep that falls outside the schedule (>= T, so positive).
+static int ddim_timesteps(int T, int S, std::vector<int>& ts) {
+    ts.clear();
+    if (S < 1 || S > T) return -1;
+    const int step = T / S;
+    for (int i = 0; i < T && (int)ts.size() < (T + step - 1) / step; i += step) ts.push_back(i + 1);
+    for (int v : ts) if (v >= T) return v;
+    return 0;
+}
+
 // DDIM schedule (ldm make_ddim_timesteps 'uniform' + make_ddim_sampling_parameters): the timesteps ts, the fp32 alphas a_t,
 // alphas_prev a_prev and np.sqrt(1 - a_t) of every step (shared by the DDIM and PLMS loops; sigma is the DDIM loop's own)
 static int ddim_schedule(rdm_ctx* c, const rdm_ddim_args* a, std::vector<int>& ts, std::vector<float>& at, std::vector<float>& ap,
                          std::vector<float>& s1m) {
-    if (a->S < 1 || a->S > a->T || !a->alphas_cumprod) return c->fail(-1, "bad schedule");
-    const int step = a->T / a->S;
-    ts.clear();
-    for (int i = 0; i < a->T && (int)ts.size() < (a->T + step - 1) / step; i += step) ts.push_back(i + 1);
+    const int bad = a->alphas_cumprod ? ddim_timesteps(a->T, a->S, ts) : -1;
+    if (bad < 0) return c->fail(-1, "bad schedule");
+    if (bad > 0) return c->fail(-1, "ddim timestep %d out of range for T=%d (S must divide the schedule like the reference)", bad, a->T);
     const int total = (int)ts.size();
-    for (int v : ts) if (v >= a->T) return c->fail(-1, "ddim timestep %d out of range for T=%d (S must divide the schedule like the reference)", v, a->T);
     at.resize(total); ap.resize(total); s1m.resize(total);
     for (int i = 0; i < total; i++) {
         at[i] = a->alphas_cumprod[ts[i]];
@@ -1836,6 +1845,88 @@ int rdm_plms_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
         for (int j = n_hist < 3 ? n_hist : 2; j > 0; j--) slot[j] = slot[j - 1];
         slot[0] = e_new;
         if (n_hist < 3) n_hist++;
+        RDM_TRY(run.log_x(index));
+    }
+    return run.finish(z_out);
+}
+
+// DPM-Solver++ (Lu et al. 2022; ldm models/diffusion/dpm_solver/sampler.py): alpha, sigma and the half logSNR lambda of a timestep, in
+// float64 from the model's fp32 alphas_cumprod
+struct DpmppNode { double alpha, sigma, lambda; };
+static DpmppNode dpmpp_node(const float* acp, int t) {
+    const double a = (double)acp[t];
+    return {std::sqrt(a), std::sqrt(1.0 - a), 0.5 * std::log(a / (1.0 - a))};
+}
+
+int rdm_dpmpp_timesteps(const float* alphas_cumprod, int T, int S, int skip_type, int* nodes_out) {
+    if (!alphas_cumprod || !nodes_out || T < 2 || S < 1 || S > T || (skip_type != 0 && skip_type != 1)) return -1;
+    int n = 0;
+    if (skip_type == 0) {                 // time_uniform: DDIM's timesteps descending, then 0 (they start at 1)
+        std::vector<int> ts;
+        if (ddim_timesteps(T, S, ts) != 0) return -1;
+        for (int i = (int)ts.size() - 1; i >= 0; i--) nodes_out[n++] = ts[i];
+        nodes_out[n++] = 0;
+        return n;
+    }
+    std::vector<double> lam(T);
+    for (int t = 0; t < T; t++) {
+        if (!(alphas_cumprod[t] > 0.f && alphas_cumprod[t] < 1.f)) return -1;
+        lam[t] = dpmpp_node(alphas_cumprod, t).lambda;
+    }
+    for (int i = 0; i <= S; i++) {        // logSNR: S + 1 targets uniform in lambda, each to the timestep of nearest lambda
+        const double target = lam[T - 1] + (lam[0] - lam[T - 1]) * ((double)i / (double)S);
+        int best = 0;
+        for (int t = 1; t < T; t++) if (std::fabs(lam[t] - target) < std::fabs(lam[best] - target)) best = t;     // a tie keeps the smaller t
+        if (n == 0 || best < nodes_out[n - 1]) nodes_out[n++] = best;
+    }
+    if (nodes_out[n - 1] != 0) nodes_out[n++] = 0;
+    return n;
+}
+
+// The loop of rdm_dpmpp_sample's header comment: one forward and one dpmpp_step_kernel launch per step, the solver's coefficients computed
+// here in float64.  The history is ONE slot: the kernel reads m_{j-1} from it and writes m_j to it in the same pass.
+int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond,
+                     float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_T || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
+    if (a->order != 1 && a->order != 2) return c->fail(-1, "dpm-solver++ order must be 1 or 2, got %d", a->order);
+    if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1");
+    const bool cfg = a->unconditional_guidance_scale > 1.0f;
+    if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1");
+    if (a->n_nodes < 2) return c->fail(-1, "dpm-solver++ needs at least 2 nodes, got %d", a->n_nodes);
+    for (int j = 0; j < a->n_nodes; j++) {
+        if (a->nodes[j] < 0 || a->nodes[j] >= a->T) return c->fail(-1, "dpm-solver++ node %d = %d outside [0, %d]", j, a->nodes[j], a->T - 1);
+        if (j > 0 && a->nodes[j] >= a->nodes[j - 1]) return c->fail(-1, "dpm-solver++ nodes must be strictly decreasing (node %d = %d after %d)", j, a->nodes[j], a->nodes[j - 1]);
+        const float ac = a->alphas_cumprod[a->nodes[j]];
+        if (!(ac > 0.f && ac < 1.f)) return c->fail(-1, "alphas_cumprod[%d] = %g outside (0, 1)", a->nodes[j], (double)ac);
+    }
+    const int n_steps = a->n_nodes - 1;
+    const std::vector<int> ts(a->nodes, a->nodes + n_steps);
+    SamplerRun run;
+    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr,
+                      SamplerRun::al((size_t)a->batch * a->channels * a->height * a->width * 4)));
+    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
+    float* m_slot = (float*)run.extra;
+    double h_prev = 0.0;
+    for (int j = 0; j < n_steps; j++) {
+        const int index = n_steps - 1 - j;
+        const DpmppNode s = dpmpp_node(a->alphas_cumprod, a->nodes[j]), t = dpmpp_node(a->alphas_cumprod, a->nodes[j + 1]);
+        const double h = t.lambda - s.lambda, g = -t.alpha * std::expm1(-h);       // x <- (sigma_t / sigma_s) x + g D
+        const bool second = a->order == 2 && j >= 1 && !(a->lower_order_final && j == n_steps - 1);
+        RDM_TRY(run.forward(j));
+        DpmppStepParams p{};
+        p.x = run.x; p.eps = run.eps; p.n = run.n1; p.cfg = cfg ? 1 : 0; p.scale = a->unconditional_guidance_scale;
+        p.sqrt_a_s = (float)s.alpha; p.sqrt_one_minus_a_s = (float)s.sigma; p.c_x = (float)(t.sigma / s.sigma);
+        if (second) {
+            const double r = h_prev / h;
+            p.m_prev = m_slot; p.c_0 = (float)(g * (1.0 + 1.0 / (2.0 * r))); p.c_1 = (float)(-g / (2.0 * r));
+        } else {
+            p.c_0 = (float)g;
+        }
+        p.x_out = run.x; p.x_dup = run.x_dup; p.m_store = m_slot; p.pred_x0 = run.pred_x0_slot(index);
+        RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
+        h_prev = h;
         RDM_TRY(run.log_x(index));
     }
     return run.finish(z_out);
@@ -2560,6 +2651,17 @@ int rdm_op_add(rdm_ctx* c, const void* a, const void* b, void* out, long long n)
     if (!a || !b || !out) return c->fail(-1, "rdm_op_add: null argument");
     if (n < 1) return c->fail(-1, "rdm_op_add: n must be positive");
     RDM_CHECK_HIP(c, launch_add_bf16((const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n, c->stream));
+    return 0;
+}
+int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int cfg, float scale, float sqrt_a_s,
+                      float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup, float* m_store, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_step: bad argument");
+    DpmppStepParams p{};
+    p.x = x; p.eps = eps; p.m_prev = m_prev; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale; p.sqrt_a_s = sqrt_a_s;
+    p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1;
+    p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
+    RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
     return 0;
 }
 int rdm_op_ema(rdm_ctx* c, float* shadow, const float* p, long long n, float one_minus_decay) {

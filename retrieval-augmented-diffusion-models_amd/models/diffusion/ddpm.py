@@ -20,6 +20,7 @@ import torch
 from ... import _lib, packing, parallel
 from ...util import ischannellastimage
 from .ddim import DDIMSampler
+from .dpm_solver import DPMSolverSampler
 from .plms import PLMSSampler
 
 
@@ -176,10 +177,10 @@ class MinimalRETRODiffusion(object):
             base = parallel.shared_seed(self.device, getattr(self, "_group", None))
             kwargs["x_T"] = parallel.per_sample_noise(base, range(lo, hi), shape, device=self.device)
             steps = None
-            plms = kwargs.get("plms", False)                            # PLMS draws no per-step noise
-            if not plms and kwargs.get("ddim", True) and kwargs.get("eta", 0.) != 0.:
+            noiseless = kwargs.get("plms", False) or kwargs.get("dpm_solver", False)      # PLMS and DPM-Solver++ draw no per-step noise
+            if not noiseless and kwargs.get("ddim", True) and kwargs.get("eta", 0.) != 0.:
                 steps = len(range(0, self.num_timesteps, self.num_timesteps // kwargs.get("S", kwargs.get("ddim_steps"))))
-            elif not plms and not kwargs.get("ddim", True):
+            elif not noiseless and not kwargs.get("ddim", True):
                 steps = int(kwargs.get("timesteps") or self.num_timesteps)
             if steps is not None and kwargs.get("noise") is None:      # per-step noise: [steps, b, C, H, W], row streams as above
                 nz = parallel.per_sample_noise(base + 1, range(lo, hi), (steps,) + shape, device=self.device)
@@ -372,10 +373,13 @@ class MinimalRETRODiffusion(object):
 
     # ---- samplers
     @torch.no_grad()
-    def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, **kwargs):
-        """ddpm.py:988-1011.  [native] plms=True samples with PLMSSampler (ldm) on S = ddim_steps instead of DDIM / DDPM."""
-        if ddim or plms:
-            sampler = PLMSSampler(self) if plms else DDIMSampler(self)
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, dpm_solver=False, **kwargs):
+        """ddpm.py:988-1011.  [native] plms=True samples with PLMSSampler (ldm), dpm_solver=True with DPMSolverSampler (DPM-Solver++ 2M
+        on the logSNR grid) on S = ddim_steps instead of DDIM / DDPM."""
+        if plms and dpm_solver:
+            raise ValueError("plms and dpm_solver select different samplers: give one of them")
+        if ddim or plms or dpm_solver:
+            sampler = PLMSSampler(self) if plms else DPMSolverSampler(self) if dpm_solver else DDIMSampler(self)
             shape = custom_shape if custom_shape is not None else (self.channels, self.image_size, self.image_size)
             ddim_steps = kwargs.pop('S', ddim_steps)
             verbose = kwargs.pop('verbose', False)

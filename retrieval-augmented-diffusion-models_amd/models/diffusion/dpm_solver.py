@@ -1,0 +1,138 @@
+"""SAMPLING ONLY — native counterpart of ldm's DPMSolverSampler (ldm/models/diffusion/dpm_solver/sampler.py; `--dpm_solver` in
+ldm's txt2img script): DPM-Solver++(2M), the multistep data-prediction solver of Lu et al. 2022 ("DPM-Solver++: Fast Solver for
+Guided Sampling of Diffusion Probabilistic Models"), here on INTEGER timesteps.
+
+`sample` has ldm's signature and returns `(z, intermediates)` like PLMSSampler here.  The solver walks a strictly decreasing node list
+nodes[0] > ... > nodes[n-1] of model timesteps with n - 1 UNet forwards (at nodes[0 .. n-2]) and ends at the noise level of
+nodes[n-1].  With a = alphas_cumprod[t] in float64, alpha = sqrt(a), sigma = sqrt(1 - a), lambda = log(a / (1 - a)) / 2, step j from
+s = nodes[j] to t = nodes[j+1] is
+
+    m_j = (x - sigma_s eps) / alpha_s                 (eps guided: e_u + scale (e_c - e_u)),       h_j = lambda_t - lambda_s
+    D   = (1 + 1/(2r)) m_j - (1/(2r)) m_{j-1},  r = h_{j-1} / h_j      when order == 2, j >= 1, not (lower_order_final and last step)
+    D   = m_j                                                          otherwise
+    x  <- (sigma_t / sigma_s) x - alpha_t expm1(-h_j) D
+
+and order 1 is DDIM with eta = 0.  The node list comes from the library (rdm_dpmpp_timesteps): `skip_type="logSNR"` (uniform in
+lambda from T - 1 to 0, rounded to timesteps; the grid this solver needs: on DDIM's grid it is barely better than DDIM) or
+"time_uniform" (DDIM's S timesteps, then 0), or from `timesteps=`.  The logSNR grid may hold fewer than S steps when targets round to
+the same timestep.  The loop runs inside librdm_hip (rdm_dpmpp_sample): K/V of the neighbours projected once per call, the
+time-embedding table, the shared guidance prefix and the zero-context shortcut as in the DDIM loop, one fused update kernel per step.
+Options that change the loop body per step (callbacks, mask / x0 inpainting, quantize_x0 through the native quantiser applied to m_j,
+score_corrector) take the per-step path: native `apply_model`, torch fp32 update; it reads only `model.num_timesteps`,
+`model.alphas_cumprod`, `model.device` and `model.apply_model` (and `model.q_sample` under a mask, when the model has one).  The solver
+is deterministic: eta != 0 raises ValueError; `temperature` and `noise_dropout` have no effect.
+"""
+import math
+
+import numpy as np
+import torch
+
+from ... import _lib
+from .ddim import _SamplerBase
+
+
+def dpmpp_coefficients(alphas_cumprod, s, t, h_prev=None):
+    """Step s -> t in float64 from the fp32 alphas_cumprod: (alpha_s, sigma_s, c_x, c_0, c_1, h) with x_t = c_x x + c_0 m + c_1 m_prev.
+    h_prev None: first-order step (c_1 = 0)."""
+    a_s, a_t = float(alphas_cumprod[s]), float(alphas_cumprod[t])
+    lam = lambda a: 0.5 * math.log(a / (1.0 - a))
+    h = lam(a_t) - lam(a_s)
+    g = -math.sqrt(a_t) * math.expm1(-h)
+    c_x = math.sqrt(1.0 - a_t) / math.sqrt(1.0 - a_s)
+    if h_prev is None:
+        return math.sqrt(a_s), math.sqrt(1.0 - a_s), c_x, g, 0.0, h
+    r = h_prev / h
+    return math.sqrt(a_s), math.sqrt(1.0 - a_s), c_x, g * (1.0 + 1.0 / (2.0 * r)), -g / (2.0 * r), h
+
+
+class DPMSolverSampler(_SamplerBase):
+    def __init__(self, model, **kwargs):
+        super().__init__(model, **kwargs)
+        ac = model.alphas_cumprod.detach().float().cpu()
+        assert ac.shape[0] == self.ddpm_num_timesteps, 'alphas have to be defined for each timestep'
+        self.register_buffer('alphas_cumprod', ac)
+
+    def make_nodes(self, S, skip_type="logSNR", timesteps=None):
+        """[native] the node list: `timesteps` as given, or the library's grid of S steps."""
+        if timesteps is not None:
+            return np.asarray(timesteps, dtype=np.int64).reshape(-1)
+        return _lib.dpmpp_timesteps(S, self.alphas_cumprod, skip_type).astype(np.int64)
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
+               unconditional_conditioning=None, order=2, skip_type="logSNR", lower_order_final=None, timesteps=None, **kwargs):
+        """`order` (1 | 2), `skip_type` ("logSNR" | "time_uniform"), `lower_order_final` (None: on below 15 steps), `timesteps` (an
+        explicit node list, strictly decreasing) and `q_noise` (explicit stack [steps, B, C, H, W] for q_sample of the masked region,
+        per-step path) are [native]."""
+        if eta != 0:
+            raise ValueError('eta must be 0 for DPM-Solver++ (the solver is deterministic)')
+        if order not in (1, 2):
+            raise ValueError(f'DPM-Solver++ order must be 1 or 2, got {order!r}')
+        if unconditional_guidance_scale < 1.:
+            raise ValueError('unconditional_guidance_scale must be >= 1')
+        if conditioning is not None and not isinstance(conditioning, (dict, list)):
+            if conditioning.shape[0] != batch_size:
+                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        cond = self._unwrap(conditioning, single="DPM-Solver++")
+        uc = self._unwrap(unconditional_conditioning)
+        nodes = self.make_nodes(S, skip_type, timesteps)
+        n_steps = len(nodes) - 1
+        if lower_order_final is None:
+            lower_order_final = n_steps < 15
+        device = self.model.device
+        size = (batch_size,) + tuple(shape)
+        img = torch.randn(size, device=device) if x_T is None else x_T.to(device)
+        print(f"Running DPM-Solver++ Sampling (order {order}) with {n_steps} timesteps")
+        guided = uc is not None and unconditional_guidance_scale != 1.
+        scale = unconditional_guidance_scale if guided else 1.0
+        per_step = (callback is not None or img_callback is not None or quantize_x0 or mask is not None or x0 is not None or
+                    score_corrector is not None)
+        if per_step:
+            return self._python_loop(nodes, cond, img, callback, img_callback, log_every_t, order, lower_order_final, quantize_x0, mask,
+                                     x0, score_corrector, corrector_kwargs, scale, uc if guided else None, kwargs.get("q_noise"))
+        z, xi, pi = self.model.ctx.dpmpp_sample(nodes, img, cond, uc if guided else None, self.alphas_cumprod, scale=scale, order=order,
+                                                lower_order_final=lower_order_final, log_every_t=log_every_t, want_intermediates=True)
+        intermediates = {'x_inter': [img] + list(xi), 'pred_x0': [img] + list(pi)}
+        return z.detach(), intermediates
+
+    def _python_loop(self, nodes, cond, img, callback, img_callback, log_every_t, order, lower_order_final, quantize_denoised, mask, x0,
+                     score_corrector, corrector_kwargs, scale, uc, q_noise):
+        """Per-step path of sample: native apply_model per forward, torch fp32 update with the library's coefficients."""
+        ac = self.alphas_cumprod.numpy()
+        n_steps = len(nodes) - 1
+        if n_steps < 1 or np.any(np.diff(nodes) >= 0) or nodes[0] >= ac.shape[0] or nodes[-1] < 0:
+            raise ValueError(f"DPM-Solver++ nodes must be strictly decreasing timesteps in [0, {ac.shape[0] - 1}], at least two")
+        intermediates = {'x_inter': [img], 'pred_x0': [img]}
+        b = img.shape[0]
+        f32 = lambda v: float(np.float32(v))
+        m_prev, h_prev = None, None
+        for j in range(n_steps):
+            index = n_steps - 1 - j
+            ts = torch.full((b,), int(nodes[j]), device=img.device, dtype=torch.long)
+            if mask is not None:
+                img = self._masked_blend(img, mask, x0, ts, None if q_noise is None else q_noise[j])
+            if uc is None:
+                e = self.model.apply_model(img, ts, cond)
+            else:
+                out = self.model.apply_model(torch.cat([img] * 2), torch.cat([ts] * 2), torch.cat([cond, uc]))
+                e = out[b:] + scale * (out[:b] - out[b:])
+            if score_corrector is not None:
+                assert getattr(self.model, "parameterization", "eps") == "eps"
+                e = score_corrector.modify_score(self.model, e, img, ts, cond, **(corrector_kwargs or {}))
+            second = order == 2 and j >= 1 and not (lower_order_final and j == n_steps - 1)
+            alpha_s, sigma_s, c_x, c_0, c_1, h_prev = dpmpp_coefficients(ac, int(nodes[j]), int(nodes[j + 1]), h_prev if second else None)
+            m = (img - f32(sigma_s) * e) / f32(alpha_s)
+            if quantize_denoised:
+                m = self.model.quantize_first_stage(m)
+            img = f32(c_x) * img + f32(c_0) * m
+            if second:
+                img = img + f32(c_1) * m_prev
+            m_prev = m
+            if callback: callback(j)
+            if img_callback: img_callback(m, j)
+            if self._logs(index, log_every_t, n_steps):
+                intermediates['x_inter'].append(img)
+                intermediates['pred_x0'].append(m)
+        return img, intermediates

@@ -18,7 +18,9 @@ Additions (not in the reference, all optional): `--clip_ckpt` (CLIP ViT-B/32 sta
 `--synthetic` (seeded random weights and database: the 6.2 GB checkpoint / 18 GB database are unreachable without a
 network), `--gpus N` (batch-sharded multi-GPU sampling, one process per GPU via torch.distributed.run, RCCL all-gather of
 the finished images; `--gpu` is then ignored and each rank uses its LOCAL_RANK), `--plms` (sample with ldm's PLMSSampler on
-`--steps` instead of DDIM: same schedule, about half the steps for the same accuracy; works with `--gpus N`).
+`--steps` instead of DDIM: same schedule, about half the steps for the same accuracy; works with `--gpus N`), `--dpm_solver`
+(sample with DPM-Solver++(2M), ldm's DPMSolverSampler, on a logSNR grid of at most `--steps` steps: 15-25 steps under guidance;
+works with `--gpus N`; not together with `--plms`).
 """
 import argparse
 import datetime
@@ -64,6 +66,8 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--shard_db", action="store_true", help="[native] with --gpus N: shard the database ROWS over the GPUs instead of "
                         "replicating them (databases beyond one GPU's memory); neighbours are merged in one exchange per search")
     parser.add_argument("--plms", default=False, action="store_true", help="[native] sample with PLMS (ldm PLMSSampler) instead of DDIM")
+    parser.add_argument("--dpm_solver", default=False, action="store_true",
+                        help="[native] sample with DPM-Solver++(2M) (ldm DPMSolverSampler) on a logSNR grid instead of DDIM")
     return parser
 
 
@@ -176,8 +180,8 @@ def _save_logs(logs, keys, opt, sampling_start, n):
 
 
 def _sampler_kwargs(opt: argparse.Namespace) -> dict:
-    """--plms reaches MinimalRETRODiffusion.sample_log; without it the calls are the reference's."""
-    return {"plms": True} if getattr(opt, "plms", False) else {}
+    """--plms / --dpm_solver reach MinimalRETRODiffusion.sample_log; without them the calls are the reference's."""
+    return {name: True for name in ("plms", "dpm_solver") if getattr(opt, name, False)}
 
 
 def sample_unconditional(model, opt: argparse.Namespace, is_writer=True):

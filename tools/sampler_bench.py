@@ -1,9 +1,10 @@
 #!/usr/bin/env python3
-"""DDIM against PLMS, native loops on the shipped synthetic UNet + VQ-f4 decoder at B = 64 (CFG 2.0, k = 4 neighbours; the UNet
-batch is the guided B' = 128): ms per image, VQ decode included, for each `name:S` given (default ddim:50 plms:50 plms:25).  PLMS
-with S timesteps runs S + 1 forwards.  Prints one JSON line.
+"""DDIM against PLMS and DPM-Solver++, native loops on the shipped synthetic UNet + VQ-f4 decoder at B = 64 (CFG 2.0, k = 4
+neighbours; the UNet batch is the guided B' = 128): ms per image, VQ decode included, for each `name:S` given (default ddim:50 plms:50
+plms:25).  PLMS with S timesteps runs S + 1 forwards; dpmpp:S is DPM-Solver++(2M) on the logSNR grid of S targets, whose real step
+count (reported under "forwards") can come out below S.  Prints one JSON line.
 
-    python tools/sampler_bench.py [--reps N] [--batch B] [ddim:50 plms:50 plms:25 ...]
+    python tools/sampler_bench.py [--reps N] [--batch B] [ddim:50 plms:50 plms:25 dpmpp:20 ...]
 """
 import argparse
 import json
@@ -44,9 +45,16 @@ def main():
             z, _, _ = ctx.ddim_sample(S, x_T, cond, uncond, model.alphas_cumprod, eta=0.0, scale=2.0)
         elif name == "plms":
             z, _, _ = ctx.plms_sample(S, x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
+        elif name == "dpmpp":
+            z, _, _ = ctx.dpmpp_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         else:
-            raise SystemExit(f"unknown sampler {name!r} (ddim | plms)")
+            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp)")
         return ctx.vq_decode(z)
+
+    def forwards(name, S):
+        if name == "dpmpp":
+            return len(ctx.dpmpp_timesteps(S, model.alphas_cumprod)) - 1
+        return S + (1 if name == "plms" else 0)
 
     out = {"batch": B, "scale": 2.0, "k": 4, "reps": a.reps, "ms_per_image": {}, "forwards": {}}
     for run in a.runs:
@@ -61,11 +69,13 @@ def main():
         dt = (time.perf_counter() - t0) / a.reps
         assert torch.isfinite(img).all()
         out["ms_per_image"][run] = round(dt * 1e3 / B, 3)
-        out["forwards"][run] = S + (1 if name == "plms" else 0)
+        out["forwards"][run] = forwards(name, S)
         print(f"{run}: {dt * 1e3:.1f} ms per call, {dt * 1e3 / B:.3f} ms per image", file=sys.stderr, flush=True)
     ms = out["ms_per_image"]
     if "ddim:50" in ms and "plms:25" in ms:
         out["speedup_plms25_over_ddim50"] = round(ms["ddim:50"] / ms["plms:25"], 3)
+    if "ddim:50" in ms and "dpmpp:20" in ms:
+        out["speedup_dpmpp20_over_ddim50"] = round(ms["ddim:50"] / ms["dpmpp:20"], 3)
     print(json.dumps(out))
     ctx.close()
 
