@@ -199,6 +199,18 @@ int rdm_vq_quantize(rdm_ctx* ctx, const float* z, int b, float* zq_out, int32_t*
  * [dev] int64 [b, h*w] -> quantize.get_codebook_entry -> post_quant_conv -> Decoder -> img_out [dev] f32 [b,3,R,R].
  * For first stages with a wide latent (VQGAN-f16, z_channels % 64 == 0). */
 int rdm_vq_decode_indices(rdm_ctx* ctx, const int64_t* indices, int b, float* img_out);
+/* The first stage at any size (ldm's "convolutional sampling": decode_first_stage / VQModelInterface.decode on a conv-only autoencoder,
+ * rdm/models/diffusion/ddpm.py:840 behind sample_log(custom_shape=) at ddpm.py:988-1011).  rdm_vq_decode and rdm_vq_quantize above are
+ * these two at the cfg's own latent size h = w = resolution / f, f = 2^(levels - 1).
+ *   rdm_vq_decode_hw:   z [dev] f32 [b,z_channels,h,w] -> img_out [dev] f32 [b,out_ch,f*h,f*w]; indices_out [dev] int32 [b,h*w] or NULL
+ *   rdm_vq_quantize_hw: z [dev] f32 [b,3,h,w] -> zq_out [dev] f32 [b,3,h,w]; indices_out as above
+ * Any h, w >= 1.  What runs where: 3x3 convs of levels whose width is at most 64 with 256 % width == 0, or a multiple of 64 with
+ * height % 4 == 0, on the halo kernels, every other width on the generic implicit GEMM; the mid AttnBlock materialises its n x n scores
+ * (n = h*w, padded to a multiple of 64), so a batch is walked in ranges of at most 8 GiB of them, and a latent of more than 46336 pixels
+ * -- or one whose largest activation passes 2^30 elements -- is refused (-1); work buffers that cannot be allocated: -2.  Not for wide
+ * latents (VQGAN-f16: its 256-token sequence fixes its size) -- rdm_vq_decode_indices / rdm_vq_encode_indices stay square. */
+int rdm_vq_decode_hw(rdm_ctx* ctx, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out);
+int rdm_vq_quantize_hw(rdm_ctx* ctx, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out);
 /* ---- first stage, encoder side (training input): LatentDiffusion.encode_first_stage -> VQModelInterface.encode = quant_conv(encoder(x))
  *      under torch.no_grad(), reached from MinimalRETRODiffusion.shared_step -> get_input (rdm/models/diffusion/ddpm.py:390-391).
  * Same rdm_vq_cfg as the decoder (the encoder mirrors it: ddconfig is shared); state_dict keys `encoder.*`, `quant_conv.*`.
@@ -216,6 +228,9 @@ int rdm_vq_encode(rdm_ctx* ctx, const float* img, int b, float* z_out);
  * quantize.embedding.weight) with the same wide cfg.  Batches beyond the first stage's activation range are walked in ranges. */
 int rdm_vq_encode_indices(rdm_ctx* ctx, const float* img /*[dev] f32 [b,out_ch,R,R]*/, int b, int64_t* indices_out /*[dev] [b, h*w]*/,
                           float* quant_out_or_null /*[dev] f32 [b,embed_dim,h,w] = codebook rows*/);
+/* VQModelInterface.encode at any image size: img [dev] f32 [b,out_ch,H,W], H and W positive multiples of f -> z_out [dev] f32
+ * [b,embed_dim,H/f,W/f].  rdm_vq_encode is this at H = W = resolution.  VQ-f4 (3-channel latent) only. */
+int rdm_vq_encode_hw(rdm_ctx* ctx, const float* img, int b, int H, int W, float* z_out);
 /* scripts/rdm_sample.py:203-214 custom_to_np/custom_to_pil: f32 NCHW [-1,1] -> uint8 NHWC (truncating). */
 int rdm_to_uint8(rdm_ctx* ctx, const float* img, int b, int c, int h, int w, uint8_t* out);
 

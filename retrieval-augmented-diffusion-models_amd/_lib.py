@@ -106,6 +106,8 @@ SIGNATURES = {
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
     "rdm_vq_quantize": (C.c_int, [_P, _P, C.c_int, _P, _P]),
+    "rdm_vq_decode_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P]),
+    "rdm_vq_quantize_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P]),
     "rdm_to_uint8": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_clip_encode_text": (C.c_int, [_P, _P, C.c_int, _P]),
     "rdm_clip_encode_image": (C.c_int, [_P, _P, C.c_int, _P]),
@@ -133,6 +135,7 @@ SIGNATURES = {
     "rdm_vqenc_manifest": (C.c_longlong, [_P, _P, C.c_size_t, _P]),
     "rdm_load_vqenc": (C.c_int, [_P, _P, _P, C.c_size_t]),
     "rdm_vq_encode": (C.c_int, [_P, _P, C.c_int, _P]),
+    "rdm_vq_encode_hw": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_vq_encode_indices": (C.c_int, [_P, _P, C.c_int, _P, _P]),
     "rdm_op_q_sample": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_mse_loss": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -406,14 +409,24 @@ class Context:
         self._check(lib.rdm_load_vqenc(self._h, C.byref(cfg), blob.ctypes.data_as(_P), blob.nbytes)); self.vqenc_cfg = cfg
 
     def vq_encode(self, img):
-        """VQModelInterface.encode: image f32 [b,out_ch,R,R] in [-1,1] -> latent f32 [b,embed_dim,R/f,R/f] (not quantised)."""
+        """VQModelInterface.encode: image f32 [b,out_ch,H,W] in [-1,1], H and W multiples of f = 2^(levels-1) -> latent f32
+        [b,embed_dim,H/f,W/f] (not quantised).  The encoder is conv-only, so any such size runs (rdm_vq_encode_hw); a first stage with a
+        wide latent (VQGAN-f16) runs at its own resolution only."""
         img = self._dev(img, torch.float32)
         cfg = self._need("vq_encode", "vqenc")
-        if img.ndim != 4 or tuple(img.shape[1:]) != (cfg.out_ch, cfg.resolution, cfg.resolution):
-            raise RdmError(f"vq_encode: image must be [b,{cfg.out_ch},{cfg.resolution},{cfg.resolution}], got {tuple(img.shape)}")
-        zr = cfg.resolution >> (cfg.n_ch_mult - 1)
-        z = torch.empty((img.shape[0], cfg.embed_dim, zr, zr), device=self.device, dtype=torch.float32)
-        self._check(lib.rdm_vq_encode(self._h, _ptr(img), img.shape[0], _ptr(z)))
+        f = 1 << (cfg.n_ch_mult - 1)
+        if img.ndim != 4 or img.shape[1] != cfg.out_ch:
+            raise RdmError(f"vq_encode: image must be [b,{cfg.out_ch},H,W], got {tuple(img.shape)}")
+        b, _, H, W = img.shape
+        if b < 1 or H < f or W < f or H % f or W % f:
+            raise RdmError(f"vq_encode: image height and width must be positive multiples of {f}, got {tuple(img.shape)}")
+        if cfg.embed_dim > 4 and (H, W) != (cfg.resolution, cfg.resolution):
+            raise RdmError(f"vq_encode: a first stage with a wide latent takes [b,{cfg.out_ch},{cfg.resolution},{cfg.resolution}] only, got {tuple(img.shape)}")
+        z = torch.empty((b, cfg.embed_dim, H // f, W // f), device=self.device, dtype=torch.float32)
+        if cfg.embed_dim > 4:
+            self._check(lib.rdm_vq_encode(self._h, _ptr(img), b, _ptr(z)))
+        else:
+            self._check(lib.rdm_vq_encode_hw(self._h, _ptr(img), b, H, W, _ptr(z)))
         return z
 
     def vq_encode_indices(self, img, return_quant=False):
@@ -686,27 +699,28 @@ class Context:
         return z
 
     def vq_decode(self, z, force_not_quantize=False, return_indices=False):
+        """decode_first_stage: latent f32 [b,embed_dim,h,w] -> image f32 [b,out_ch,f*h,f*w], f = 2^(levels-1); any h, w (the decoder is
+        conv-only: rdm_vq_decode_hw), optionally the code indices int32 [b*h*w]."""
         z = self._dev(z, torch.float32)
         cfg = self._need("vq_decode", "vq")
-        zr = cfg.resolution >> (cfg.n_ch_mult - 1)
-        if z.ndim != 4 or tuple(z.shape[1:]) != (cfg.embed_dim, zr, zr):
-            raise RdmError(f"vq_decode: latent must be [b,{cfg.embed_dim},{zr},{zr}], got {tuple(z.shape)}")
-        b = z.shape[0]; r = self.vq_cfg.resolution
-        img = torch.empty((b, self.vq_cfg.out_ch, r, r), device=self.device, dtype=torch.float32)
-        idx = torch.empty((b * z.shape[2] * z.shape[3],), device=self.device, dtype=torch.int32) if return_indices else None
-        self._check(lib.rdm_vq_decode(self._h, _ptr(z), b, int(force_not_quantize), _ptr(img), _ptr(idx)))
+        if z.ndim != 4 or z.shape[1] != cfg.embed_dim or min(z.shape) < 1:
+            raise RdmError(f"vq_decode: latent must be [b,{cfg.embed_dim},h,w], got {tuple(z.shape)}")
+        b, _, h, w = z.shape; f = 1 << (cfg.n_ch_mult - 1)
+        img = torch.empty((b, cfg.out_ch, f * h, f * w), device=self.device, dtype=torch.float32)
+        idx = torch.empty((b * h * w,), device=self.device, dtype=torch.int32) if return_indices else None
+        self._check(lib.rdm_vq_decode_hw(self._h, _ptr(z), b, h, w, int(force_not_quantize), _ptr(img), _ptr(idx)))
         return (img, idx) if return_indices else img
 
     def vq_quantize(self, z, return_indices=False):
-        """first_stage_model.quantize(z): z f32 [b,3,h,w] -> z_q (straight-through form), optionally the code indices."""
+        """first_stage_model.quantize(z): z f32 [b,3,h,w] (any h, w) -> z_q (straight-through form), optionally the code indices."""
         z = self._dev(z, torch.float32)
         cfg = self._need("vq_quantize", "vq")
-        zr = cfg.resolution >> (cfg.n_ch_mult - 1)
-        if z.ndim != 4 or tuple(z.shape[1:]) != (cfg.embed_dim, zr, zr):
-            raise RdmError(f"vq_quantize: latent must be [b,{cfg.embed_dim},{zr},{zr}], got {tuple(z.shape)}")
+        if z.ndim != 4 or z.shape[1] != cfg.embed_dim or min(z.shape) < 1:
+            raise RdmError(f"vq_quantize: latent must be [b,{cfg.embed_dim},h,w], got {tuple(z.shape)}")
+        b, _, h, w = z.shape
         zq = torch.empty_like(z)
-        idx = torch.empty((z.shape[0] * zr * zr,), device=self.device, dtype=torch.int32) if return_indices else None
-        self._check(lib.rdm_vq_quantize(self._h, _ptr(z), z.shape[0], _ptr(zq), _ptr(idx)))
+        idx = torch.empty((b * h * w,), device=self.device, dtype=torch.int32) if return_indices else None
+        self._check(lib.rdm_vq_quantize_hw(self._h, _ptr(z), b, h, w, _ptr(zq), _ptr(idx)))
         return (zq, idx) if return_indices else zq
 
     def to_uint8(self, img):

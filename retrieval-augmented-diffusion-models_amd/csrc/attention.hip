@@ -743,30 +743,39 @@ hipError_t launch_xattn_fused(const XattnParams& p, hipStream_t st) {
 // ------------------------------------------------------------------------------ small attention
 
 template <int D>
-__global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p) {
-    extern __shared__ float kv[];            // K [nkv][D] then V [nkv][D]  (f32)
+__global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p, int kc) {
+    extern __shared__ float kv[];            // K [kc][D] then V [kc][D]  (f32): the keys pass through LDS in chunks of kc (>= nkv: one chunk)
     const int h = blockIdx.y, b = blockIdx.z;
-    float* Ks = kv; float* Vs = kv + p.nkv * D;
-    for (int i = threadIdx.x; i < p.nkv * (D / 8); i += blockDim.x) {
-        const int j = i / (D / 8), c = (i % (D / 8)) * 8;
-        const bf16x8 kk = *(const bf16x8*)(p.k + ((long long)b * p.nkv + j) * p.ldk + h * D + c);
-        const bf16x8 vv = *(const bf16x8*)(p.v + ((long long)b * p.nkv + j) * p.ldv + h * D + c);
+    float* Ks = kv; float* Vs = kv + kc * D;
+    const int qi = blockIdx.x * blockDim.x + threadIdx.x;      // one query per thread (the grid covers nq)
+    const bool live = qi < p.nq;
+    float qr[D], acc[D];
 #pragma unroll
-        for (int e = 0; e < 8; e++) { Ks[j * D + c + e] = bf2f((bf16_t)kk[e]); Vs[j * D + c + e] = bf2f((bf16_t)vv[e]); }
-    }
-    __syncthreads();
-    for (int qi = blockIdx.x * blockDim.x + threadIdx.x; qi < p.nq; qi += gridDim.x * blockDim.x) {
-        float qr[D], acc[D];
+    for (int c = 0; c < D; c++) { qr[c] = 0.f; acc[c] = 0.f; }
+    if (live) {
         const bf16_t* qp = p.q + ((long long)b * p.nq + qi) * p.ldq + h * D;
 #pragma unroll
         for (int c = 0; c < D; c += 8) {
             const bf16x8 t = *(const bf16x8*)(qp + c);
 #pragma unroll
-            for (int e = 0; e < 8; e++) { qr[c + e] = bf2f((bf16_t)t[e]) * p.scale; acc[c + e] = 0.f; }
+            for (int e = 0; e < 8; e++) qr[c + e] = bf2f((bf16_t)t[e]) * p.scale;
         }
-        float m = -INFINITY, l = 0.f;
-        const int jend = p.causal ? min(p.nkv, qi + 1) : p.nkv;
-        for (int j = 0; j < jend; j++) {
+    }
+    float m = -INFINITY, l = 0.f;
+    const int jend = !live ? 0 : p.causal ? min(p.nkv, qi + 1) : p.nkv;
+    for (int j0 = 0; j0 < p.nkv; j0 += kc) {
+        if (j0) __syncthreads();                             // every thread has left the previous chunk
+        const int nj = min(kc, p.nkv - j0);
+        for (int i = threadIdx.x; i < nj * (D / 8); i += blockDim.x) {
+            const int j = i / (D / 8), c = (i % (D / 8)) * 8;
+            const bf16x8 kk = *(const bf16x8*)(p.k + ((long long)b * p.nkv + j0 + j) * p.ldk + h * D + c);
+            const bf16x8 vv = *(const bf16x8*)(p.v + ((long long)b * p.nkv + j0 + j) * p.ldv + h * D + c);
+#pragma unroll
+            for (int e = 0; e < 8; e++) { Ks[j * D + c + e] = bf2f((bf16_t)kk[e]); Vs[j * D + c + e] = bf2f((bf16_t)vv[e]); }
+        }
+        __syncthreads();
+        const int je = min(jend - j0, nj);
+        for (int j = 0; j < je; j++) {
             float s = 0.f;
 #pragma unroll
             for (int d = 0; d < D; d++) s += qr[d] * Ks[j * D + d];
@@ -776,27 +785,31 @@ __global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p)
 #pragma unroll
             for (int d = 0; d < D; d++) acc[d] = acc[d] * a + pj * Vs[j * D + d];
         }
-        const float inv = 1.f / l;
-        bf16_t* op = p.out + ((long long)b * p.nq + qi) * p.ldo + h * D;
+    }
+    if (!live) return;
+    const float inv = 1.f / l;
+    bf16_t* op = p.out + ((long long)b * p.nq + qi) * p.ldo + h * D;
 #pragma unroll
-        for (int c = 0; c < D; c += 8) {
-            uint4 w;
-            w.x = pack2bf(acc[c] * inv, acc[c + 1] * inv); w.y = pack2bf(acc[c + 2] * inv, acc[c + 3] * inv);
-            w.z = pack2bf(acc[c + 4] * inv, acc[c + 5] * inv); w.w = pack2bf(acc[c + 6] * inv, acc[c + 7] * inv);
-            *(uint4*)(op + c) = w;
-        }
+    for (int c = 0; c < D; c += 8) {
+        uint4 w;
+        w.x = pack2bf(acc[c] * inv, acc[c + 1] * inv); w.y = pack2bf(acc[c + 2] * inv, acc[c + 3] * inv);
+        w.z = pack2bf(acc[c + 4] * inv, acc[c + 5] * inv); w.w = pack2bf(acc[c + 6] * inv, acc[c + 7] * inv);
+        *(uint4*)(op + c) = w;
     }
 }
 
 hipError_t launch_small_attention(const SmallAttnParams& p, int D, int heads, int batch, hipStream_t st) {
-    const size_t sm = (size_t)p.nkv * D * 2 * sizeof(float);
-    if (sm > 64 * 1024) return hipErrorInvalidValue;
+    if ((D != 32 && D != 64) || p.nq < 1 || p.nkv < 1) return hipErrorInvalidValue;
+    // keys beyond 64 KiB of fp32 K | V (256 at d = 32: the self-attention of a level whose pixel count is no multiple of 32, above 256
+    // pixels) pass through LDS in chunks, the running maximum / sum / output kept per query across them
+    const int kmax = (64 * 1024) / (D * 2 * (int)sizeof(float));
+    const int kc = p.nkv < kmax ? p.nkv : kmax;
+    const size_t sm = (size_t)kc * D * 2 * sizeof(float);
     int threads = p.nq >= 256 ? 256 : ((p.nq + 63) / 64) * 64;
     int gx = (p.nq + threads - 1) / threads;
     dim3 grid(gx, heads, batch);
-    if (D == 32) small_attention_kernel<32><<<grid, threads, sm, st>>>(p);
-    else if (D == 64) small_attention_kernel<64><<<grid, threads, sm, st>>>(p);
-    else return hipErrorInvalidValue;
+    if (D == 32) small_attention_kernel<32><<<grid, threads, sm, st>>>(p, kc);
+    else small_attention_kernel<64><<<grid, threads, sm, st>>>(p, kc);
     return hipGetLastError();
 }
 

@@ -48,8 +48,8 @@ ConvKernel conv3x3_kernel(const IgemmParams& p) {
     if (p.alpha != 1.0f || p.act != ACT_NONE || !p.out_bf16 || p.out_f32 || p.res_f32) return CONV_IGEMM;
     if (p.rowvec && p.rows_per_sample % 32 != 0) return CONV_IGEMM;      // the read-out folds the per-sample row per 32-row fragment
     if ((long long)p.M * (p.C0 > p.C1 ? p.C0 : p.C1) >= 0x7fffffffLL) return CONV_IGEMM;
-    if (W > 64) {      // 64-column strips (conv3x3_halo4_kernel<2, STRIP>): the first-stage decoder's 128- / 256-pixel levels
-        if (W % 64 || H % 4 || W > 4096 || H > 4096 || p.N % 128 != 0 || (long long)p.M * p.ldo >= 0x7fffffffLL) return CONV_IGEMM;
+    if (W > 64) {      // 64-column strips (conv3x3_halo4_kernel<FN, STRIP>): the first-stage decoder's 128- / 256-pixel levels, the UNet's at latents wider than 64
+        if (W % 64 || H % 4 || W > 4096 || H > 4096 || (p.N % 192 != 0 && p.N % 128 != 0) || (long long)p.M * p.ldo >= 0x7fffffffLL) return CONV_IGEMM;
         return CONV_HALO4_STRIP;
     }
     // a tile is 256 consecutive output pixels: whole rows of one image, or whole images

@@ -601,7 +601,7 @@ static hipError_t launch_halo4_cfg(const IgemmParams& p, hipStream_t st) {
 
 // which conv runs here, and in which form, is conv3x3_kernel's answer (conv_halo.hip): launch_conv3x3 is the only caller
 hipError_t launch_conv_halo4(const IgemmParams& p, bool strip, hipStream_t st) {
-    if (strip) return launch_halo4_cfg<2, true>(p, st);
+    if (strip) return p.N % 192 == 0 ? launch_halo4_cfg<3, true>(p, st) : launch_halo4_cfg<2, true>(p, st);
     if (p.N % 192 == 0) return launch_halo4_cfg<3>(p, st);
     return launch_halo4_cfg<2>(p, st);
 }

@@ -39,7 +39,10 @@ __global__ __launch_bounds__(256) void conv_in_kernel(const float* x, const floa
     const int b = blockIdx.y, npix = H * W;
     // two pixels per thread: every broadcast weight read from LDS feeds 16 FMAs instead of 8 (the LDS reads, not the FMAs, bound
     // the one-pixel version)
-    for (int lp0 = blockIdx.x * 512 + threadIdx.x; lp0 < npix; lp0 += gridDim.x * 512) {
+    // (the trip count is the WAVE's: with a pixel count that is no multiple of 64 the lanes past the last pixel stay in the loop -- their loads
+    //  and stores are masked by `inb` / the bounds below -- because the staged stores of the OCT form are issued by ALL 64 lanes of a wave: a lane
+    //  that left the loop took the pixels it would have stored with it)
+    for (int lp0 = blockIdx.x * 512 + threadIdx.x; lp0 - lane < npix; lp0 += gridDim.x * 512) {
         f2_t patch[2][(K + 1) / 2];                   // tap k of pixel q: half k & 1 of patch[q][k / 2]
         const float* xb = x + (long long)b * Cin * npix;       // uniform base + 32-bit lane offsets: one address register per load
 #pragma unroll

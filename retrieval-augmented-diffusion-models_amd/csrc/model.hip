@@ -1262,25 +1262,46 @@ static bf16_t* vq_res(Ops& o, const VqRes& r, bf16_t* x, int B, int H, int W) {
 // ldm / taming AttnBlock: single head over H*W tokens, scale C^-1/2
 static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) {
     const int C = a.c, n = H * W, M = B * n;
+    // The score and P.V GEMMs contract over tokens in 64-slices and write column pairs: a token count that is no multiple of 64 (a 5 x 7
+    // latent) runs on np = n rounded up to 64 tokens per sample -- the normalised rows are copied into a zeroed [B][np][C] image, the padding
+    // KEYS get probability 0 in the softmax (n_valid), the padding QUERIES' rows are computed and never read -- and the real rows copied back.
+    // A correctness fallback for small odd sizes, not a fast path: one memset, two strided copies and the padding queries' q / k / scores per
+    // AttnBlock on top of the materialised n x n matrix -- a size that matters (40 x 40 latents of the shipped decoder) wants its own kernel.
+    const int np = (n + 63) & ~63, Mp = B * np;
+    const bool padn = np != n;
+    const size_t rowb = (size_t)n * C * 2, prowb = (size_t)np * C * 2;
     bf16_t* hn = o.abf((size_t)M * C);
     o.groupnorm(x, nullptr, C, 0, B, n, o.w<float>(a.ng), o.w<float>(a.nb), 1e-6f, 0, hn);
-    bf16_t* q = o.abf((size_t)M * C); bf16_t* kk = o.abf((size_t)M * C); bf16_t* vt = o.abf((size_t)M * C);
-    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wq), o.w<float>(a.bq), M, C, ACT_NONE, nullptr, q);
-    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wk), o.w<float>(a.bk), M, C, ACT_NONE, nullptr, kk);
-    float* S = o.af32((size_t)B * n * n); bf16_t* P = o.abf((size_t)B * n * n); bf16_t* ao = o.abf((size_t)M * C);
+    if (padn) {
+        bf16_t* hp = o.abf((size_t)Mp * C);
+        if (!o.plan) {
+            o.check(hipMemsetAsync(hp, 0, (size_t)Mp * C * 2, o.c->stream), "vq attention padding");
+            o.check(hipMemcpy2DAsync(hp, prowb, hn, rowb, rowb, B, hipMemcpyDeviceToDevice, o.c->stream), "vq attention padding");
+        }
+        hn = hp;
+    }
+    bf16_t* q = o.abf((size_t)Mp * C); bf16_t* kk = o.abf((size_t)Mp * C); bf16_t* vt = o.abf((size_t)Mp * C);
+    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wq), o.w<float>(a.bq), Mp, C, ACT_NONE, nullptr, q);
+    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wk), o.w<float>(a.bk), Mp, C, ACT_NONE, nullptr, kk);
+    float* S = o.af32((size_t)B * np * np); bf16_t* P = o.abf((size_t)B * np * np); bf16_t* ao = o.abf((size_t)Mp * C);
     if (!o.plan) {
-        IgemmParams p = o.base(C, n, C);     // V^T[b] = Wv . hn[b]^T   (bias b_v folded in after P.V: rows of P sum to 1)
-        p.A0 = o.w<bf16_t>(a.wv); p.C0 = C; p.W = hn; p.sW = (long long)n * C; p.sO = (long long)C * n; p.out_bf16 = vt; p.ldo = n;
+        IgemmParams p = o.base(C, np, C);    // V^T[b] = Wv . hn[b]^T   (bias b_v folded in after P.V: rows of P sum to 1)
+        p.A0 = o.w<bf16_t>(a.wv); p.C0 = C; p.W = hn; p.sW = (long long)np * C; p.sO = (long long)C * np; p.out_bf16 = vt; p.ldo = np;
         o.check(launch_igemm(p, false, B, o.c->stream), "vq v^T");
-        IgemmParams s = o.base(n, n, C);     // S[b] = q[b] k[b]^T * C^-1/2  (fp32 scores)
-        s.A0 = q; s.C0 = C; s.W = kk; s.sA = (long long)n * C; s.sW = (long long)n * C; s.sO = (long long)n * n; s.out_f32 = S; s.ldo = n;
+        IgemmParams s = o.base(np, np, C);   // S[b] = q[b] k[b]^T * C^-1/2  (fp32 scores)
+        s.A0 = q; s.C0 = C; s.W = kk; s.sA = (long long)np * C; s.sW = (long long)np * C; s.sO = (long long)np * np; s.out_f32 = S; s.ldo = np;
         s.alpha = 1.0f / sqrtf((float)C);
         o.check(launch_igemm(s, false, B, o.c->stream), "vq qk^T");
-        o.check(launch_softmax_rows(S, P, (long long)B * n, n, o.c->stream), "vq softmax");
-        IgemmParams pv = o.base(n, C, n);    // O[b] = P[b] V[b] + b_v
-        pv.A0 = P; pv.C0 = n; pv.W = vt; pv.sA = (long long)n * n; pv.sW = (long long)C * n; pv.sO = (long long)n * C; pv.out_bf16 = ao; pv.ldo = C;
+        o.check(launch_softmax_rows(S, P, (long long)B * np, np, o.c->stream, n), "vq softmax");
+        IgemmParams pv = o.base(np, C, np);  // O[b] = P[b] V[b] + b_v
+        pv.A0 = P; pv.C0 = np; pv.W = vt; pv.sA = (long long)np * np; pv.sW = (long long)C * np; pv.sO = (long long)np * C; pv.out_bf16 = ao; pv.ldo = C;
         pv.bias = o.w<float>(a.bv);
         o.check(launch_igemm(pv, false, B, o.c->stream), "vq pv");
+    }
+    if (padn) {
+        bf16_t* aoc = o.abf((size_t)M * C);
+        if (!o.plan) o.check(hipMemcpy2DAsync(aoc, rowb, ao, prowb, rowb, B, hipMemcpyDeviceToDevice, o.c->stream), "vq attention padding");
+        ao = aoc;
     }
     bf16_t* out = o.abf((size_t)M * C);
     o.linear(ao, nullptr, C, 0, o.w<bf16_t>(a.wo), o.w<float>(a.bo), M, C, ACT_NONE, x, out);
@@ -1334,11 +1355,11 @@ static void vq_trunk(Ops& o, VqModel& v, bf16_t* h, int B, int H, int W, float* 
     o.head(h, B, H, W, bin, bin, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, o.w<float>(v.coutw), o.w<float>(v.coutb), c.out_ch, img, no, hwp);
 }
 
-// VQ-f4 (3-channel latent): quantise (or not) + post_quant_conv + conv_in as tiny fp32 stem kernels, then the trunk
-static void vq_body(Ops& o, VqModel& v, const float* z, int B, int force_not_quantize, float* img, int* idx_out) {
+// VQ-f4 (3-channel latent [B, 3, h0, w0]: any size, the decoder is conv-only): quantise (or not) + post_quant_conv + conv_in as tiny fp32 stem
+// kernels, then the trunk
+static void vq_body(Ops& o, VqModel& v, const float* z, int B, int h0, int w0, int force_not_quantize, float* img, int* idx_out) {
     const rdm_vq_cfg& c = v.cfg;
-    const int zr = c.resolution >> (c.n_ch_mult - 1);
-    const int HW0 = zr * zr;
+    const int HW0 = h0 * w0;
     float* zq = o.af32((size_t)B * c.z_channels * HW0);
     const int quant = (!c.kl && !force_not_quantize) ? 1 : 0;
     if (!o.plan)
@@ -1346,8 +1367,8 @@ static void vq_body(Ops& o, VqModel& v, const float* z, int B, int force_not_qua
                                    zq, idx_out, B, HW0, quant, o.c->stream), "vq_quantize");
     const int bin = c.ch * c.ch_mult[c.n_ch_mult - 1];
     bf16_t* h = o.abf((size_t)B * HW0 * bin);
-    if (!o.plan) o.check(launch_conv_in(zq, o.w<float>(v.cinw), o.w<float>(v.cinb), h, B, c.z_channels, zr, zr, bin, o.c->stream), "vq conv_in");
-    vq_trunk(o, v, h, B, zr, zr, img);
+    if (!o.plan) o.check(launch_conv_in(zq, o.w<float>(v.cinw), o.w<float>(v.cinb), h, B, c.z_channels, h0, w0, bin, o.c->stream), "vq conv_in");
+    vq_trunk(o, v, h, B, h0, w0, img);
 }
 
 // VQGAN-f16 (wide latent): decode_to_img from code indices (taming Net2NetTransformer.decode_to_img -> quantize.get_codebook_entry ->
@@ -1366,12 +1387,12 @@ static void vq_wide_body(Ops& o, VqModel& v, const long long* indices, int B, fl
     vq_trunk(o, v, h, B, zr, zr, img);
 }
 
-// first-stage encode: image f32 [B, out_ch, R, R] -> z f32 [B, embed_dim, R / 2^(levels-1), ...]  (VQModelInterface.encode: no quantisation here).
+// first-stage encode: image f32 [B, out_ch, H, W] (H, W multiples of f = 2^(levels-1)) -> z f32 [B, embed_dim, H / f, W / f]  (VQModelInterface.encode:
+// no quantisation here).
 // Wide latents (taming VQGAN-f16; un-vendored, parity unpinned): norm_out + swish as a GroupNorm pass, conv_out as a 3x3 conv, quant_conv as
 // a GEMM whose fp32 output stays token-major [B h w, embed_dim] (returned; what the nearest-code search reads); z (NCHW) may then be null.
-static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* z) {
+static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, int H, int W, float* z) {
     const rdm_vq_cfg& c = v.cfg;
-    int H = c.resolution, W = c.resolution;
     bf16_t* h = o.abf((size_t)B * H * W * c.ch);
     if (!o.plan) o.check(launch_conv_in(img, o.w<float>(v.cinw), o.w<float>(v.cinb), h, B, c.out_ch, H, W, c.ch, o.c->stream), "encoder conv_in");
     int bin = c.ch;
@@ -1403,30 +1424,46 @@ static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, float* 
     return nullptr;
 }
 
-// Samples per decoder (or wide-latent encoder: the same levels, mirrored) pass.  Decoding is per sample (GroupNorm statistics included), so a batch may be walked in ranges; a range is
-// sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo convs address an operand through
-// 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the seven 128-channel convs of
-// the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).  RDM_VQ_RANGE overrides (tests).
-static int vq_range(const rdm_vq_cfg& c, int b) {
+// Samples per decoder (or encoder: the same levels, mirrored) pass at an h x w latent.  Decoding is per sample (GroupNorm statistics included), so a
+// batch may be walked in ranges; a range is sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo
+// convs address an operand through 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the
+// seven 128-channel convs of the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).
+// An AttnBlock materialises its scores and probabilities, n^2 fp32 + n^2 bf16 per sample over the n pixels of its level: they are bounded in
+// BYTES, VQ_SCORE_BYTES per pass -- 8 GiB, which the shipped batch of 64 at the training size (n = 4096: 6.4 GB) stays under, so that size
+// is walked as it always was, while a 128 x 128 latent (n = 16384: 1.6 GB per image, which the activation count alone would have run 16 at a
+// time) goes 5 images per pass.  Returns 0 when ONE sample is beyond what the kernels index (an activation of 2^30 elements, a score matrix of
+// 2^31).  RDM_VQ_RANGE overrides the range (tests).
+constexpr long long VQ_SCORE_BYTES = 8LL << 30;
+template <typename M>
+static int vq_range(const M& m, int b, int h, int w) {
     static const int env = rdm_env_int(getenv("RDM_VQ_RANGE"), 0);
-    if (env > 0) return env < b ? env : b;
-    long long per = 1;
-    for (int l = 0; l < c.n_ch_mult; l++) {
-        const long long r = c.resolution >> l, e = r * r * c.ch * c.ch_mult[l];
+    const rdm_vq_cfg& c = m.cfg;
+    const int top = c.n_ch_mult - 1;
+    long long per = 1, score = 0;
+    for (int l = 0; l <= top; l++) {
+        const long long px = ((long long)h << (top - l)) * ((long long)w << (top - l)), e = px * c.ch * c.ch_mult[l];
         if (e > per) per = e;
         // the level's Upsample output (and the first convs' input at the next finer level) keeps THIS level's channel count at twice the
         // resolution -- the decoder's largest activation (VQ-f4: 256 x 256 x 256 per image, twice the level maximum): a range sized without
         // it reached exactly 2^31 elements and pushed those convs off the 32-bit-offset halo kernels (advisor, round 5)
-        if (l >= 1) { const long long u = 4 * r * r * c.ch * c.ch_mult[l]; if (u > per) per = u; }
+        if (l >= 1 && 4 * e > per) per = 4 * e;
+        const bool attn = !m.levels[l].attn.empty() || (l == top && m.mid.has_attn);
+        const long long np = (px + 63) & ~63LL;
+        if (attn && np * np > score) score = np * np;
     }
+    if (per > (1LL << 30) || score >= (1LL << 31)) return 0;
+    if (env > 0) return env < b ? env : b;
     long long n = (1LL << 30) / per;
+    if (score > 0 && VQ_SCORE_BYTES / (6 * score) < n) n = VQ_SCORE_BYTES / (6 * score);
     if (n < 1) n = 1;
     return n < b ? (int)n : b;
 }
-// a first-stage pass over a batch: body(o, b0, n) runs samples [b0, b0 + n) -- in ranges of vq_range(), or the whole batch at once
+// a first-stage pass over a batch of h x w latents: body(o, b0, n) runs samples [b0, b0 + n) -- in ranges of vq_range(), or the whole batch at once
 template <typename M, typename F>
-static int vq_walk(rdm_ctx* c, M& m, int b, bool in_ranges, F&& body) {
-    const int nb = in_ranges ? vq_range(m.cfg, b) : b;
+static int vq_walk(rdm_ctx* c, M& m, int b, int h, int w, bool in_ranges, F&& body) {
+    const int nr = vq_range(m, b, h, w);
+    if (nr < 1) return c->fail(-1, "first stage: a %d x %d latent is beyond what one pass can index (largest activation 2^30 elements, attention over 46336 pixels)", h, w);
+    const int nb = in_ranges ? nr : b;
     RDM_TRY(ensure_gn_partial(c, nb));
     for (int b0 = 0; b0 < b; b0 += nb)
         RDM_TRY(run_with_arena(c, m.arena, m.blob, [&](Ops& o) { body(o, b0, b - b0 < nb ? b - b0 : nb); }));
@@ -1557,15 +1594,27 @@ int rdm_load_vq(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nb
 int rdm_load_vqenc(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->vqenc, cfg_check_vqenc, build_vqenc, cfg, packed, nbytes); }
 int rdm_load_clip(rdm_ctx* c, const rdm_clip_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->clip, cfg_check_clip, build_clip, cfg, packed, nbytes); }
 int rdm_load_rarm(rdm_ctx* c, const rdm_rarm_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->rarm, cfg_check_rarm, build_rarm, cfg, packed, nbytes); }
-int rdm_vq_encode(rdm_ctx* c, const float* img, int b, float* z_out) {
-    RDM_ENTER(c);
-    if (!img || !z_out || b < 1) return c->fail(-1, "rdm_vq_encode: bad argument");
+// img [b, out_ch, H, W] -> z_out [b, embed_dim, H / f, W / f]; `what`: the entry's name in messages
+static int vq_encode_impl(rdm_ctx* c, const char* what, const float* img, int b, int H, int W, float* z_out) {
+    if (!img || !z_out || b < 1) return c->fail(-1, "%s: bad argument", what);
     if (!c->vqenc.loaded) return c->fail(-1, "first-stage encoder weights not loaded (rdm_load_vqenc)");
     const rdm_vq_cfg& q = c->vqenc.cfg;
-    const int zr = q.resolution >> (q.n_ch_mult - 1);
-    return vq_walk(c, c->vqenc, b, c->vqenc.wide, [&](Ops& o, int b0, int n) {      // wide latents: walked in ranges as rdm_vq_decode* is
-        vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, z_out + (size_t)b0 * q.embed_dim * zr * zr);
+    const int f = 1 << (q.n_ch_mult - 1);
+    if (H < f || W < f || H % f || W % f) return c->fail(-1, "%s: image height and width must be positive multiples of %d (every Downsample halves exactly), got %d x %d", what, f, H, W);
+    const int h = H / f, w = W / f;
+    return vq_walk(c, c->vqenc, b, h, w, c->vqenc.wide, [&](Ops& o, int b0, int n) {      // wide latents: walked in ranges as rdm_vq_decode* is
+        vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * H * W, n, H, W, z_out + (size_t)b0 * q.embed_dim * h * w);
     });
+}
+int rdm_vq_encode(rdm_ctx* c, const float* img, int b, float* z_out) {
+    RDM_ENTER(c);
+    const int R = c->vqenc.loaded ? c->vqenc.cfg.resolution : 1;      // (not loaded: refused before R is used)
+    return vq_encode_impl(c, "rdm_vq_encode", img, b, R, R, z_out);
+}
+int rdm_vq_encode_hw(rdm_ctx* c, const float* img, int b, int H, int W, float* z_out) {
+    RDM_ENTER(c);
+    if (c->vqenc.loaded && c->vqenc.wide) return c->fail(-1, "rdm_vq_encode_hw: a first stage with a wide latent (VQGAN-f16) runs at its own resolution only (rdm_vq_encode)");
+    return vq_encode_impl(c, "rdm_vq_encode_hw", img, b, H, W, z_out);
 }
 // taming VQModel.encode as reached from Net2NetTransformer.encode_to_z (un-vendored, parity unpinned): quant_z, _, info =
 // first_stage_model.encode(x); indices = info[2].view(b, -1).  The token-major fp32 latent of the encoder goes straight into the
@@ -1587,8 +1636,8 @@ int rdm_vq_encode_indices(rdm_ctx* c, const float* img, int b, int64_t* indices_
         if (e != hipSuccess) { (void)hipFree(c->vq.code_norms); c->vq.code_norms = nullptr; return c->fail(-2, "codebook norms: %s", hipGetErrorString(e)); }
     }
     const int zr = q.resolution >> (q.n_ch_mult - 1), HW = zr * zr;
-    return vq_walk(c, c->vqenc, b, true, [&](Ops& o, int b0, int n) {
-        const float* zt = vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, nullptr);
+    return vq_walk(c, c->vqenc, b, zr, zr, true, [&](Ops& o, int b0, int n) {
+        const float* zt = vqenc_body(o, c->vqenc, img + (size_t)b0 * q.out_ch * q.resolution * q.resolution, n, q.resolution, q.resolution, nullptr);
         const long long M = (long long)n * HW;
         char* ws = (char*)o.ar->alloc(vq_nearest_ws_bytes(M, d.n_embed));
         int* idx32 = (int*)o.ar->alloc((size_t)M * 4);
@@ -1956,32 +2005,49 @@ int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const 
 }
 
 
-int rdm_vq_decode(rdm_ctx* c, const float* z, int b, int force_not_quantize, float* img_out, int32_t* indices_out) {
-    RDM_ENTER(c);
-    if (!c || !z || !img_out) return c ? c->fail(-1, "null argument") : -1;
+// z [b, z_channels, h, w] -> img_out [b, out_ch, f h, f w], indices_out [b, h w] or null
+static int vq_decode_impl(rdm_ctx* c, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out) {
+    if (!z || !img_out) return c->fail(-1, "null argument");
     if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
     if (c->vq.wide) return c->fail(-1, "this first stage has a wide latent (VQGAN-f16): decode from code indices with rdm_vq_decode_indices");
+    if (b < 1 || h < 1 || w < 1) return c->fail(-1, "vq decode: bad shape b=%d h=%d w=%d", b, h, w);
     const rdm_vq_cfg& q = c->vq.cfg;
-    const int zr = q.resolution >> (q.n_ch_mult - 1);
-    return vq_walk(c, c->vq, b, true, [&](Ops& o, int b0, int n) {
-        vq_body(o, c->vq, z + (size_t)b0 * q.z_channels * zr * zr, n, force_not_quantize, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution,
-                indices_out ? indices_out + (size_t)b0 * zr * zr : nullptr);
+    const int f = 1 << (q.n_ch_mult - 1);
+    const size_t zper = (size_t)q.z_channels * h * w, iper = (size_t)q.out_ch * (f * h) * ((size_t)f * w);
+    return vq_walk(c, c->vq, b, h, w, true, [&](Ops& o, int b0, int n) {
+        vq_body(o, c->vq, z + b0 * zper, n, h, w, force_not_quantize, img_out + b0 * iper, indices_out ? indices_out + (size_t)b0 * h * w : nullptr);
     });
+}
+int rdm_vq_decode(rdm_ctx* c, const float* z, int b, int force_not_quantize, float* img_out, int32_t* indices_out) {
+    RDM_ENTER(c);
+    const int zr = c->vq.loaded ? c->vq.cfg.resolution >> (c->vq.cfg.n_ch_mult - 1) : 1;      // (not loaded: refused before zr is used)
+    return vq_decode_impl(c, z, b, zr, zr, force_not_quantize, img_out, indices_out);
+}
+int rdm_vq_decode_hw(rdm_ctx* c, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out) {
+    RDM_ENTER(c);
+    return vq_decode_impl(c, z, b, h, w, force_not_quantize, img_out, indices_out);
+}
+static int vq_quantize_impl(rdm_ctx* c, const char* what, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out) {
+    if (!z || !zq_out || b < 1 || h < 1 || w < 1 || (long long)h * w > 0x7fffffffLL / b) return c->fail(-1, "%s: bad argument", what);
+    VqModel& v = c->vq;
+    if (!v.loaded) return c->fail(-1, "vq weights not loaded");
+    if (v.wide || v.cfg.kl || v.cfg.embed_dim != 3) return c->fail(-1, "%s: needs a VQ first stage with a 3-channel latent (VQ-f4)", what);
+    if (!c->eye3) {       // the quantiser kernel ends in a 3 x 3 map (post_quant_conv in decode): identity + zero bias here
+        const float e[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+        RDM_CHECK_HIP(c, hipMalloc((void**)&c->eye3, sizeof e));
+        RDM_CHECK_HIP(c, hipMemcpy(c->eye3, e, sizeof e, hipMemcpyHostToDevice));
+    }
+    RDM_CHECK_HIP(c, launch_vq_quantize(z, (const float*)(v.blob + v.codebook), v.cfg.n_embed, c->eye3, c->eye3 + 9, zq_out, indices_out, b, h * w, 1, c->stream));
+    return 0;
 }
 int rdm_vq_quantize(rdm_ctx* c, const float* z, int b, float* zq_out, int32_t* indices_out) {
     RDM_ENTER(c);
-    if (!z || !zq_out || b < 1) return c->fail(-1, "rdm_vq_quantize: bad argument");
-    VqModel& v = c->vq;
-    if (!v.loaded) return c->fail(-1, "vq weights not loaded");
-    if (v.wide || v.cfg.kl || v.cfg.embed_dim != 3) return c->fail(-1, "rdm_vq_quantize: needs a VQ first stage with a 3-channel latent (VQ-f4)");
-    if (!c->eye3) {       // the quantiser kernel ends in a 3 x 3 map (post_quant_conv in decode): identity + zero bias here
-        const float h[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-        RDM_CHECK_HIP(c, hipMalloc((void**)&c->eye3, sizeof h));
-        RDM_CHECK_HIP(c, hipMemcpy(c->eye3, h, sizeof h, hipMemcpyHostToDevice));
-    }
-    const int zr = v.cfg.resolution >> (v.cfg.n_ch_mult - 1);
-    RDM_CHECK_HIP(c, launch_vq_quantize(z, (const float*)(v.blob + v.codebook), v.cfg.n_embed, c->eye3, c->eye3 + 9, zq_out, indices_out, b, zr * zr, 1, c->stream));
-    return 0;
+    const int zr = c->vq.loaded ? c->vq.cfg.resolution >> (c->vq.cfg.n_ch_mult - 1) : 1;
+    return vq_quantize_impl(c, "rdm_vq_quantize", z, b, zr, zr, zq_out, indices_out);
+}
+int rdm_vq_quantize_hw(rdm_ctx* c, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out) {
+    RDM_ENTER(c);
+    return vq_quantize_impl(c, "rdm_vq_quantize_hw", z, b, h, w, zq_out, indices_out);
 }
 int rdm_vq_decode_indices(rdm_ctx* c, const int64_t* indices, int b, float* img_out) {
     RDM_ENTER(c);
@@ -1990,7 +2056,7 @@ int rdm_vq_decode_indices(rdm_ctx* c, const int64_t* indices, int b, float* img_
     if (!c->vq.wide || c->vq.cfg.kl) return c->fail(-1, "rdm_vq_decode_indices needs a VQGAN first stage with a wide latent (z_channels %% 64 == 0)");
     const rdm_vq_cfg& q = c->vq.cfg;
     const int zr = q.resolution >> (q.n_ch_mult - 1);
-    return vq_walk(c, c->vq, b, true, [&](Ops& o, int b0, int n) {
+    return vq_walk(c, c->vq, b, zr, zr, true, [&](Ops& o, int b0, int n) {
         vq_wide_body(o, c->vq, (const long long*)indices + (size_t)b0 * zr * zr, n, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution);
     });
 }

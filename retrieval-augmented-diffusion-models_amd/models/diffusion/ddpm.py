@@ -168,9 +168,22 @@ class MinimalRETRODiffusion(object):
             raise ValueError(f"batch of {n_total} cannot be sharded over {world} ranks")
         return parallel.shard_range(n_total, world, rank)
 
+    def _latent_shape(self, custom_shape=None):
+        """(C, H, W) of the latents a sampling call runs on: `custom_shape` (sample_log's argument, ddpm.py:988-1011: the UNet and
+        the first stage are convolutional, so a model samples at sizes other than its training resolution) or the model's own.
+        H and W must be multiples of the UNet's down factor (every Downsample halves exactly): checked here, before any GPU work."""
+        if custom_shape is None:
+            return (self.channels, self.image_size, self.image_size)
+        shape = tuple(int(v) for v in custom_shape)
+        down = 1 << (self.unet_cfg.n_channel_mult - 1)
+        if len(shape) != 3 or shape[0] != self.channels or shape[1] < down or shape[2] < down or shape[1] % down or shape[2] % down:
+            raise ValueError(f"custom_shape must be ({self.channels}, H, W) with H and W positive multiples of the UNet's down factor {down}, got {tuple(custom_shape)}")
+        return shape
+
     def _sample_shard(self, c, c_uncond, lo, hi, n_total, scale, kwargs):
-        """sample_log + decode_first_stage on rows [lo, hi) of a global batch of n_total, then the all-gather."""
-        shape = (self.channels, self.image_size, self.image_size)
+        """sample_log + decode_first_stage on rows [lo, hi) of a global batch of n_total, then the all-gather.  The starting noise and
+        the per-step noise stack are drawn at the latent shape of the call (custom_shape when given)."""
+        shape = self._latent_shape(kwargs.get("custom_shape"))
         if kwargs.get("x_T") is not None:
             kwargs["x_T"] = kwargs["x_T"][lo:hi]
         else:
@@ -208,11 +221,12 @@ class MinimalRETRODiffusion(object):
 
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
+        """z [b,C,h,w] at any h, w (the first stage is conv-only) -> images [b,out_ch,f*h,f*w]."""
         return self.ctx.vq_decode(z / self.scale_factor if self.scale_factor != 1.0 else z, force_not_quantize=force_not_quantize)
 
     @torch.no_grad()
     def quantize_first_stage(self, z):
-        """first_stage_model.quantize(z)[0] (taming VectorQuantizer2.forward) on the native quantiser."""
+        """first_stage_model.quantize(z)[0] (taming VectorQuantizer2.forward) on the native quantiser; z [b,C,h,w] at any h, w."""
         return self.ctx.vq_quantize(z)
 
     @torch.no_grad()
@@ -225,7 +239,8 @@ class MinimalRETRODiffusion(object):
     # ---- training surface.  ldm DDPM.get_input / LatentDiffusion.get_input, encode_first_stage, get_first_stage_encoding
     @torch.no_grad()
     def encode_first_stage(self, x):
-        """ldm LatentDiffusion.encode_first_stage -> VQModelInterface.encode (no quantisation), on the native encoder."""
+        """ldm LatentDiffusion.encode_first_stage -> VQModelInterface.encode (no quantisation), on the native encoder; x [b,out_ch,H,W]
+        with H, W multiples of the first stage's factor f -> [b,C,H/f,W/f]."""
         return self.ctx.vq_encode(x)
 
     def get_first_stage_encoding(self, encoder_posterior):
@@ -378,19 +393,28 @@ class MinimalRETRODiffusion(object):
         on the logSNR grid) on S = ddim_steps instead of DDIM / DDPM."""
         if plms and dpm_solver:
             raise ValueError("plms and dpm_solver select different samplers: give one of them")
+        shape = (self.channels, self.image_size, self.image_size) if custom_shape is None else self._latent_shape(custom_shape)
         if ddim or plms or dpm_solver:
             sampler = PLMSSampler(self) if plms else DPMSolverSampler(self) if dpm_solver else DDIMSampler(self)
-            shape = custom_shape if custom_shape is not None else (self.channels, self.image_size, self.image_size)
             ddim_steps = kwargs.pop('S', ddim_steps)
             verbose = kwargs.pop('verbose', False)
             return sampler.sample(S=ddim_steps, batch_size=batch_size, shape=shape, conditioning=cond, verbose=verbose, **kwargs)
-        return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True, **kwargs)
+        return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True,
+                           shape=None if custom_shape is None else (batch_size,) + shape, **kwargs)
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, timesteps=None, noise=None,
-               temperature=1., **kwargs):
-        """ldm LatentDiffusion.sample -> p_sample_loop (ancestral DDPM; CFG kwargs are swallowed like in ldm)."""
-        shape = (batch_size, self.channels, self.image_size, self.image_size)
+               temperature=1., shape=None, **kwargs):
+        """ldm LatentDiffusion.sample -> p_sample_loop (ancestral DDPM; CFG kwargs are swallowed like in ldm).  shape: ldm's argument,
+        (batch_size, C, H, W) of the latents; default the model's own size."""
+        if shape is None:
+            shape = (batch_size, self.channels, self.image_size, self.image_size)
+        else:
+            shape = tuple(int(v) for v in shape)
+            if len(shape) != 4:
+                raise ValueError(f"shape must be (batch_size, {self.channels}, H, W), got {shape}")
+            shape = (shape[0],) + self._latent_shape(shape[1:])
+            batch_size = shape[0]
         if isinstance(cond, (list, tuple)):
             cond = cond[0]
         cond = cond[:batch_size]
@@ -422,6 +446,7 @@ class MinimalRETRODiffusion(object):
         """ddpm.py:689-844 (nn_encoder is None, retrieval_encoder = Identity — every shipped config)."""
         if cond is not None or return_nns:
             raise NotImplementedError("cond (a second conditioning) / return_nns (neighbour image grids) are not part of the native sampling path")
+        self._latent_shape(kwargs.get("custom_shape"))      # a bad custom_shape fails here, not after the retrieval
         # (the reference asserts `query.ndim` first, which makes its own `isinstance(query, str)` branch unreachable: a caption only
         #  works pre-embedded there, scripts/rdm_sample.py:275-277; here str / list-of-str queries take the CLIP text tower)
         if not query_embedded and not isinstance(query, (str, list)):
@@ -519,6 +544,7 @@ class MinimalRETRODiffusion(object):
         """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921)."""
         if cond is not None or return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("cond / return_nns / pre_loaded_patches are not part of the native sampling path")
+        self._latent_shape(kwargs.get("custom_shape"))
         self._sync_retriever_sharding()
         if self.retriever.searcher is None:
             self.train_searcher()

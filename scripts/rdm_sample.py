@@ -20,7 +20,10 @@ network), `--gpus N` (batch-sharded multi-GPU sampling, one process per GPU via 
 the finished images; `--gpu` is then ignored and each rank uses its LOCAL_RANK), `--plms` (sample with ldm's PLMSSampler on
 `--steps` instead of DDIM: same schedule, about half the steps for the same accuracy; works with `--gpus N`), `--dpm_solver`
 (sample with DPM-Solver++(2M), ldm's DPMSolverSampler, on a logSNR grid of at most `--steps` steps: 15-25 steps under guidance;
-works with `--gpus N`; not together with `--plms`).
+works with `--gpus N`; not together with `--plms`), `--height PX` / `--width PX` (image size in pixels, default the model's own: the UNet and
+the first stage are convolutional, so a model samples at other sizes -- the reference reaches this through `sample_log(custom_shape=)`
+only, its script has no flag; multiples of 32 = first-stage factor 4 x UNet down factor 8 of the shipped models; every sampler, and
+`--gpus N`).
 """
 import argparse
 import datetime
@@ -68,11 +71,21 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--plms", default=False, action="store_true", help="[native] sample with PLMS (ldm PLMSSampler) instead of DDIM")
     parser.add_argument("--dpm_solver", default=False, action="store_true",
                         help="[native] sample with DPM-Solver++(2M) (ldm DPMSolverSampler) on a logSNR grid instead of DDIM")
+    parser.add_argument("--height", type=int, default=None, help="[native] image height in pixels (default: the model's own size); a multiple of 32")
+    parser.add_argument("--width", type=int, default=None, help="[native] image width in pixels (default: the model's own size); a multiple of 32")
     return parser
 
 
+SIZE_MULTIPLE = 32          # first-stage factor (VQ-f4: 4) x UNet down factor (8) of the shipped models
+
+
 def parse_args(argv=None) -> argparse.Namespace:
-    opt = build_parser().parse_args(argv)
+    parser = build_parser()
+    opt = parser.parse_args(argv)
+    for name in ("height", "width"):
+        v = getattr(opt, name)
+        if v is not None and (v < SIZE_MULTIPLE or v % SIZE_MULTIPLE):
+            parser.error(f"--{name} must be a positive multiple of {SIZE_MULTIPLE} (first-stage factor x UNet down factor), got {v}")
     if opt.top_m > 1.0:
         opt.top_m = int(opt.top_m)          # top_m should be int if a fixed number of images is given (:138-140)
     if opt.seed is not None and (not opt.increase_guidance) and opt.n_runs > 1:
@@ -179,9 +192,19 @@ def _save_logs(logs, keys, opt, sampling_start, n):
                 raise NotImplementedError("image grids (batched_nns) belong to --save_nns")
 
 
-def _sampler_kwargs(opt: argparse.Namespace) -> dict:
-    """--plms / --dpm_solver reach MinimalRETRODiffusion.sample_log; without them the calls are the reference's."""
-    return {name: True for name in ("plms", "dpm_solver") if getattr(opt, name, False)}
+def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
+    """--plms / --dpm_solver / --height / --width reach MinimalRETRODiffusion.sample_log (the sizes as its custom_shape, in latent
+    pixels); without them the calls are the reference's."""
+    kw = {name: True for name in ("plms", "dpm_solver") if getattr(opt, name, False)}
+    height, width = getattr(opt, "height", None), getattr(opt, "width", None)
+    if height is not None or width is not None:
+        f = 1 << (model.vq_cfg.n_ch_mult - 1)                       # pixels per latent pixel
+        own = model.image_size * f
+        height, width = (own if height is None else height), (own if width is None else width)
+        if height % f or width % f:
+            raise SystemExit(f"rdm_sample.py (native): --height / --width must be multiples of the first stage's factor {f}")
+        kw["custom_shape"] = (model.channels, height // f, width // f)       # checked against the UNet's down factor by the model
+    return kw
 
 
 def sample_unconditional(model, opt: argparse.Namespace, is_writer=True):
@@ -194,7 +217,7 @@ def sample_unconditional(model, opt: argparse.Namespace, is_writer=True):
         print("Sampling query and neighbors (wait for the sampling to start)")
         logs = model.sample_from_rdata(opt.batch_size, qids=qids, k_nn=opt.k_nn, return_nns=opt.save_nns, use_weights=opt.use_weights,
                                        memsize=opt.top_m, unconditional_guidance_scale=opt.guidance_scale, ddim_steps=opt.steps,
-                                       ddim=True, unconditional_retro_guidance_label=0., **_sampler_kwargs(opt))
+                                       ddim=True, unconditional_retro_guidance_label=0., **_sampler_kwargs(opt, model))
         if is_writer:
             _save_logs(logs, ["samples_with_sampled_nns", "batched_nns"], opt, sampling_start, n)
         if opt.increase_guidance:
@@ -221,7 +244,7 @@ def sample_conditional(model, opt: argparse.Namespace, is_writer=True):
                                        return_nns=opt.save_nns and not opt.only_caption, visualize_nns=opt.save_nns and not opt.only_caption,
                                        use_weights=opt.use_weights, unconditional_guidance_scale=opt.guidance_scale, ddim_steps=opt.steps,
                                        ddim=True, unconditional_retro_guidance_label=0., omit_query=opt.omit_query and not opt.only_caption,
-                                       **_sampler_kwargs(opt))
+                                       **_sampler_kwargs(opt, model))
         print(f"Run {n + 1}/{opt.n_runs}")
         if is_writer:
             _save_logs(logs, None, opt, sampling_start, n)

@@ -1,11 +1,14 @@
 #!/usr/bin/env python3
 """3x3-conv kernel bench over the UNet's conv shapes through the C ABI (GPU box only), plus multi-tile parity checks.
-usage: conv_bench.py [check] [bench]"""
+usage: conv_bench.py [check] [bench] [wide]
+wide: the widest UNet level (192 channels) at latents wider than 64 -- 64 x 128 and 128 x 128, UNet batch 8 and 32, 192 -> 192 with the
+time-embedding row and residual (ResBlock conv2 / conv1) and (192 + 192) -> 192 (the first conv behind a skip concat) -- for A/B runs of
+two builds through RDM_HIP_LIB: the 64-column strip form of conv_halo4 against the generic implicit GEMM."""
 import os, sys, time
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 what = sys.argv[1:] or ["check"]
-if "bench" in what: os.environ.setdefault("RDM_OP_FRAG_CACHE", "1")     # constant weights: keep the fragment-ordered copy between calls
+if "bench" in what or "wide" in what: os.environ.setdefault("RDM_OP_FRAG_CACHE", "1")     # constant weights: keep the fragment-ordered copy between calls
 import torch
 import torch.nn.functional as F
 import rdm_amd
@@ -59,3 +62,20 @@ if "bench" in what:
         tot_t += dt; tot_f += fl
         print(f"conv B={B} {H}x{H} C={C}->{N} res={r}: {dt * 1e3:8.3f} ms {fl / dt / 1e12:8.1f} TF", flush=True)
     print(f"TOTAL {tot_t * 1e3:.3f} ms  {tot_f / tot_t / 1e12:.1f} TF")
+
+if "wide" in what:
+    tot_t = tot_f = 0.0
+    for (B, H, W) in [(8, 64, 128), (8, 128, 128), (32, 64, 128), (32, 128, 128)]:
+        for (C0, C1, r) in [(192, 0, 1), (192, 192, 0)]:
+            N = 192
+            x0 = torch.randn(B, H, W, C0, device=d).bfloat16()
+            x1 = torch.randn(B, H, W, C1, device=d).bfloat16() if C1 else None
+            w = (torch.randn(N, 3, 3, C0 + C1, device=d) * (9 * (C0 + C1)) ** -0.5).bfloat16()
+            b = torch.zeros(N, device=d)
+            temb = torch.randn(B, N, device=d) if r else None
+            res = torch.randn(B, H, W, N, device=d).bfloat16() if r else None
+            dt = bench(lambda: ctx.op_conv3x3(x0, w, b, x1=x1, rowvec=temb, residual=res))
+            fl = 2.0 * B * H * W * N * 9 * (C0 + C1)
+            tot_t += dt; tot_f += fl
+            print(f"wide conv B={B} {H}x{W} C={C0}+{C1}->{N} res={r}: {dt * 1e3:8.3f} ms {fl / dt / 1e12:8.1f} TF", flush=True)
+    print(f"WIDE TOTAL {os.path.basename(os.environ.get('RDM_HIP_LIB') or 'default')}: {tot_t * 1e3:.3f} ms  {tot_f / tot_t / 1e12:.1f} TF")
