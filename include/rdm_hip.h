@@ -529,6 +529,16 @@ int rdm_op_small_attention(rdm_ctx* ctx, const void* q_bf16, int ldq, const void
  * (head h = columns [32 h, 32 h + 32)) -> dq [B, nq, 32 heads], dk / dv [B, nkv, 32 heads], all bf16; sums in a fixed order. */
 int rdm_op_small_attention_bwd(rdm_ctx* ctx, const void* q_bf16, int ldq, const void* k_bf16, const void* v_bf16, int ldkv, const void* dout_bf16, int ldo,
                                int B, int nq, int nkv, int heads, float scale, void* dq_bf16, void* dk_bf16, void* dv_bf16);
+/* The stem conv in front of the UNet, the VQ decoder and the encoder (conv_in_kernel): 3x3, pad 1, x fp32 NCHW [B, Cin, H, W], w fp32
+ * [Cout, Cin, 3, 3], bias fp32 [Cout] -> out bf16 NHWC [B, H, W, Cout]; one fp32 FMA chain per element, one rounding.  1 <= Cin <= 4,
+ * Cout % 8 == 0, any H x W. */
+int rdm_op_conv_in(rdm_ctx* ctx, const float* x_f32, const float* w_f32, const float* bias_f32, int B, int Cin, int H, int W, int Cout,
+                   void* out_bf16);
+/* The VALU head conv (conv_out_kernel), the one the models fall back to where rdm_op_head_conv's fused kernel refuses a shape (W % 32,
+ * odd H): 3x3, pad 1, x bf16 NHWC [B, H, W, Cin], w fp32 [Cout, Cin, 3, 3], bias fp32 [Cout] -> out fp32 NCHW [B, Cout, H, W].
+ * Cin % 64 == 0, 1 <= Cout <= 4, Cout * Cin <= 1820, any H x W. */
+int rdm_op_conv_out(rdm_ctx* ctx, const void* x_bf16, const float* w_f32, const float* bias_f32, int B, int H, int W, int Cin, int Cout,
+                    float* out_f32);
 
 #ifdef __cplusplus
 }

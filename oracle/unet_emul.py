@@ -10,7 +10,9 @@ re-associations done the library's way (each cites its site):
   * time embedding: bf16 sinusoid, SiLU folded into the two MLP outputs (only SiLU(emb) is ever consumed), emb rows in fp32;
   * GroupNorm / LayerNorm statistics in fp32 on the bf16 values, outputs rounded once;
   * conv: fp32 accumulate + bias + emb row (+ residual), one rounding;
-  * self-attention: fp32 scores and row sums, probabilities rounded to bf16 for the P.V product (flash_d32_lds_kernel);
+  * self-attention: fp32 scores and row sums, probabilities rounded to bf16 for the P.V product (flash_d32_lds_kernel, and flash_d32_kernel
+    at token counts with n % 64 == 32: the same 32-key tiles); at a level whose token count is no multiple of 32 small_attention_kernel
+    runs instead, which keeps the probabilities in fp32 (`small_attention` below);
   * cross-attention over the k neighbours re-associated per sample (unet_compute_xattn): G = bf16(bf16(K / sqrt d) W_q), U = bf16(W_o V^T),
     scores on bf16(LayerNorm-2), group softmax in fp32, bf16 probabilities, + bias + residual, one rounding;
     rows >= ctx_rows (all-zero neighbours: the unconditional half of a guided batch) get t2 = to_out1(...) + b_o1 + b_o2 + t0 in ONE rounding;
@@ -63,6 +65,15 @@ def flash_attention(q, k, v, scale, R, tile=32):
     wgt = torch.exp2(m_key - m_run[..., -1:])
     o = torch.einsum("bhij,bhjd->bhid", R.bf(p) * wgt, v)
     return o / (p * wgt).sum(dim=-1, keepdim=True)
+
+
+def small_attention(q, k, v, scale):
+    """softmax(q k^T scale) v as small_attention_kernel forms it (csrc/attention.hip): the scale goes into the query first (one fp32
+    rounding per element), scores, probabilities and the P.V product stay in fp32 -- nothing is rounded to bf16 before the output.
+    q, k, v [B, heads, n, d] (bf16 values).  (The kernel's running maximum across keys / key chunks is plain fp32 re-association.)"""
+    s = torch.einsum("bhid,bhjd->bhij", q * torch.tensor(scale, dtype=torch.float32), k)
+    p = torch.exp(s - s.amax(dim=-1, keepdim=True))
+    return torch.einsum("bhij,bhjd->bhid", p, v) / p.sum(dim=-1, keepdim=True)
 
 
 def _phase_weights(w, R):
@@ -166,12 +177,19 @@ def unet_forward_emulated(sd, spec: UNetSpec, x, timesteps, context, ctx_rows=No
         xn = stage(1, to_tok(bf(group_norm(xin, sd[pre + ".norm.weight"], sd[pre + ".norm.bias"], 1e-6))))
         t0 = stage(2, bf(F.linear(xn, Wb(pre + ".proj_in.weight").reshape(c, c), sd[pre + ".proj_in.bias"])))
         ln = lambda t, nm: bf(F.layer_norm(t, (c,), sd[f"{tb}.{nm}.weight"], sd[f"{tb}.{nm}.bias"], 1e-5))
-        # --- attn1: q | k | v in one projection, flash attention with bf16 probabilities
+        # --- attn1: q | k | v in one projection, flash attention with bf16 probabilities (n % 32 == 0) or the fp32 small attention
         l1 = stage(3, ln(t0, "norm1"))
-        qkv = stage(4, torch.cat([bf(F.linear(l1, Wb(f"{tb}.attn1.{nm}.weight"))) for nm in ("to_q", "to_k", "to_v")], dim=-1))
-        q, k_, v = qkv.split(c, dim=-1)
+        # (n % 64 == 0: one fused q | k | v projection, shown whole; otherwise the library projects q | k -- its stage 4 is 2 c wide -- and
+        # forms V in a GEMM of its own, which no tap shows)
+        proj = lambda nm: bf(F.linear(l1, Wb(f"{tb}.attn1.{nm}.weight")))
+        if n % 64 == 0:
+            q, k_, v = stage(4, torch.cat([proj("to_q"), proj("to_k"), proj("to_v")], dim=-1)).split(c, dim=-1)
+        else:
+            q, k_ = stage(4, torch.cat([proj("to_q"), proj("to_k")], dim=-1)).split(c, dim=-1)
+            v = proj("to_v")
         sp = lambda t: t.reshape(b, n, heads, d).permute(0, 2, 1, 3)
-        ao = stage(5, bf(flash_attention(sp(q), sp(k_), sp(v), scale, R).permute(0, 2, 1, 3).reshape(b, n, c)))
+        attn1 = flash_attention(sp(q), sp(k_), sp(v), scale, R) if n % 32 == 0 else small_attention(sp(q), sp(k_), sp(v), scale)      # unet_body's dispatch
+        ao = stage(5, bf(attn1.permute(0, 2, 1, 3).reshape(b, n, c)))
         acc1 = F.linear(ao, Wb(f"{tb}.attn1.to_out.0.weight"))
         bo1, bo2 = sd[f"{tb}.attn1.to_out.0.bias"], sd[f"{tb}.attn2.to_out.0.bias"]
         t1 = bf(acc1 + bo1 + t0)

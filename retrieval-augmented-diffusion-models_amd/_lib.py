@@ -178,6 +178,8 @@ SIGNATURES = {
     "rdm_op_self_attention": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_self_attention_qkv": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_head_conv": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "rdm_op_conv_in": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "rdm_op_conv_out": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_linear_rowvec": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int]),
     "rdm_op_xattn_fused_ln3": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdm_op_xattn_fused": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -1175,6 +1177,23 @@ class Context:
         g, b_, eps = gn if gn is not None else (None, None, 0.0)
         opt = lambda t: _ptr(t) if t is not None else None
         self._check(lib.rdm_op_head_conv(self._h, _ptr(x), opt(g), opt(b_), float(eps), _ptr(w), opt(bias), B, H, W, Cc, Cout, _ptr(out)))
+        return out
+
+    def op_conv_in(self, x, w, bias):
+        """the stem conv (conv_in_kernel): x fp32 [B, Cin, H, W] (Cin <= 4), w fp32 [Cout, Cin, 3, 3], bias fp32 [Cout] -> bf16 [B, H, W, Cout]."""
+        B, Cin, H, W = x.shape
+        Cout = w.shape[0]
+        out = torch.empty((B, H, W, Cout), device=self.device, dtype=torch.bfloat16)
+        self._check(lib.rdm_op_conv_in(self._h, _ptr(x), _ptr(w), _ptr(bias), B, Cin, H, W, Cout, _ptr(out)))
+        return out
+
+    def op_conv_out(self, x, w, bias):
+        """the VALU head conv (conv_out_kernel, the models' fallback where op_head_conv refuses a shape): x bf16 [B, H, W, Cin], w fp32
+        [Cout, Cin, 3, 3] (Cout <= 4), bias fp32 [Cout] -> fp32 [B, Cout, H, W]."""
+        B, H, W, Cin = x.shape
+        Cout = w.shape[0]
+        out = torch.empty((B, Cout, H, W), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_op_conv_out(self._h, _ptr(x), _ptr(w), _ptr(bias), B, H, W, Cin, Cout, _ptr(out)))
         return out
 
     def op_xattn_fused(self, x, G, U, bias, res, ncols, group, ln=None):

@@ -2996,5 +2996,21 @@ int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, co
                       "small attention");
     return o.rc;
 }
+int rdm_op_conv_in(rdm_ctx* c, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, void* out) {
+    RDM_ENTER(c);
+    if (!x || !w || !bias || !out) return c->fail(-1, "rdm_op_conv_in: null argument");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W * 5 >= (1ll << 30) || Cin < 1 || Cin > 4 || Cout < 8 || Cout % 8 || ((Cin <= 3 ? 3 : 4) * 9 + 1) * (long long)Cout * 4 > 96 * 1024)
+        return c->fail(-3, "rdm_op_conv_in: unsupported shape (1 <= Cin <= 4, Cout %% 8, weights + bias within 96 KB of LDS): B %d Cin %d H %d W %d Cout %d", B, Cin, H, W, Cout);
+    RDM_CHECK_HIP(c, launch_conv_in(x, w, bias, (bf16_t*)out, B, Cin, H, W, Cout, c->stream));
+    return 0;
+}
+int rdm_op_conv_out(rdm_ctx* c, const void* x, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout, float* out) {
+    RDM_ENTER(c);
+    if (!x || !w || !bias || !out) return c->fail(-1, "rdm_op_conv_out: null argument");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W >= (1ll << 31) || Cin < 64 || Cin % 64 || Cout < 1 || Cout > 4 || (long long)Cout * 9 * Cin * 4 > 64 * 1024)
+        return c->fail(-3, "rdm_op_conv_out: unsupported shape (Cin %% 64, 1 <= Cout <= 4, weights within 64 KB of LDS): B %d H %d W %d Cin %d Cout %d", B, H, W, Cin, Cout);
+    RDM_CHECK_HIP(c, launch_conv_out((const bf16_t*)x, w, bias, (float*)out, B, H, W, Cin, Cout, c->stream));
+    return 0;
+}
 
 }  // extern "C"

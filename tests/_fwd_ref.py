@@ -1,6 +1,6 @@
 """Float64 restatements of the inference forward ops (linear / lin4 / sgemm / mgemm, the LayerNorm-folded projection, conv3x3 on every
-launch path, GroupNorm, LayerNorm, flash and small attention, the fused cross-attention and the head conv), their per-element error
-bounds and their near misses.  Shared by tests/test_gpu_forward_ops.py (the HIP kernels through the C ABI) and
+launch path, the stem conv, GroupNorm, LayerNorm, flash and small attention, the fused cross-attention, the head conv and its VALU
+fallback), their per-element error bounds and their near misses.  Shared by tests/test_gpu_forward_ops.py (the HIP kernels through the C ABI) and
 tests/test_forward_ops_cpu.py (an fp32 torch restatement standing in for the kernels).  Same CASE contract as tests/_train_ref.py:
 `make(**shape)`, `ref(inp, dt)`, `bound(inp, ref)` -> per output (r, a), `misses(inp)`; `check()` asserts |out - ref| <= r |ref| + a
 element by element and that the output falls outside the bound against every near miss.
@@ -91,7 +91,9 @@ def conv3x3_kernel(B, H, W, C, N, stride, rowvec):
     if stride != 1 or (B * HW) % 256 or C % 64 or (rowvec and HW % 32):
         return None
     if W > 64:
-        return "halo4<2, STRIP>" if W % 64 == 0 and H % 4 == 0 and max(H, W) <= 4096 and N % 128 == 0 else None
+        if W % 64 or H % 4 or max(H, W) > 4096 or (N % 192 and N % 128):
+            return None
+        return f"halo4<{3 if N % 192 == 0 else 2}, STRIP>"
     if W < 4 or 256 % W or (N % 192 and N % 128):
         return None
     if (HW % 256 or H % (256 // W)) if HW >= 256 else 256 % HW:
@@ -645,9 +647,17 @@ class SelfAttention:
                 ("heads reversed", SelfAttention.ref(inp, F64, reverse=True)), ("k and v swapped", SelfAttention.ref(inp, F64, swap=True))]
 
 
+def small_attention_chunk(nkv, D):
+    """keys per LDS chunk of small_attention_kernel<D> (attention.hip launch_small_attention: 64 KiB of fp32 K | V)"""
+    return min(nkv, 64 * 1024 // (D * 8))
+
+
 class SmallAttention:
-    """few-key attention (small_attention_kernel<D>, D = 32 / 64, fp32 inside: b = 0 in _attn_bound), optional causal mask.  Near
-    misses: the scale applied twice; the diagonal masked (causal); the head order reversed; k and v swapped."""
+    """few-key attention (small_attention_kernel<D>, D = 32 / 64, fp32 inside: b = 0 in _attn_bound), optional causal mask.  More than
+    64 KiB / (8 D) keys (256 at D = 32, 128 at D = 64) pass through LDS in chunks, the running maximum / sum / output carried per query
+    from one chunk to the next: the same key-ordered chain as one chunk, so the bound does not change.  Near misses: the scale applied
+    twice; the diagonal masked (causal); the head order reversed; k and v swapped; and where more than one chunk runs: the keys beyond
+    the first chunk dropped; the last chunk alone; the per-chunk softmaxes averaged (no rescale from chunk to chunk)."""
     name = "small_attention"
     exact = False
 
@@ -658,13 +668,22 @@ class SmallAttention:
                 "v": bfr(torch.randn(B, nkv, H * D, generator=g)), "H": H, "D": D, "causal": causal, "scale": D ** -0.5}
 
     @staticmethod
-    def ref(inp, dt, scale=None, swap=False, reverse=False, diag=False):
+    def ref(inp, dt, scale=None, swap=False, reverse=False, diag=False, keys=None, per_chunk=False):
         k, v = (inp["v"], inp["k"]) if swap else (inp["k"], inp["v"])
         H, D = inp["H"], inp["D"]
         s = _heads(inp["q"].to(dt), H, D) @ _heads(k.to(dt), H, D).transpose(-1, -2) * (inp["scale"] if scale is None else scale)
         if inp["causal"]:
             s = s.masked_fill(torch.ones(s.shape[-2:], dtype=torch.bool).triu(0 if diag else 1), float("-inf"))
-        o = _unheads(torch.nan_to_num(torch.softmax(s, -1)) @ _heads(v.to(dt), H, D))
+        if keys is not None:                                 # only the keys [lo, hi) are seen
+            s = s.clone(); s[..., : keys[0]] = float("-inf"); s[..., keys[1]:] = float("-inf")
+        vh = _heads(v.to(dt), H, D)
+        if per_chunk:                                        # every chunk's own softmax, the chunks that hold a key averaged
+            kc, nkv = small_attention_chunk(s.shape[-1], D), s.shape[-1]
+            parts = [torch.nan_to_num(torch.softmax(s[..., j:j + kc], -1)) @ vh[..., j:j + kc, :] for j in range(0, nkv, kc)]
+            seen = sum((torch.isfinite(s[..., j:j + kc]).any(-1, keepdim=True)).to(dt) for j in range(0, nkv, kc))
+            o = _unheads(sum(parts) / seen.clamp(min=1))
+        else:
+            o = _unheads(torch.nan_to_num(torch.softmax(s, -1)) @ vh)
         if reverse:
             o = _unheads(_heads(o, H, D).flip(1))
         return {"out": o}
@@ -679,6 +698,13 @@ class SmallAttention:
              ("k and v swapped", SmallAttention.ref(inp, F64, swap=True))]
         if inp["causal"]:
             m.append(("diagonal masked", SmallAttention.ref(inp, F64, diag=True)))
+        nkv = inp["k"].shape[1]
+        kc = small_attention_chunk(nkv, inp["D"])
+        if nkv > kc:
+            last = (nkv - 1) // kc * kc
+            m += [("keys beyond the first chunk dropped", SmallAttention.ref(inp, F64, keys=(0, kc))),
+                  ("the last chunk alone", SmallAttention.ref(inp, F64, keys=(last, nkv))),
+                  ("per-chunk softmaxes averaged", SmallAttention.ref(inp, F64, per_chunk=True))]
         return m
 
 
@@ -846,10 +872,121 @@ class HeadConv:
         return m
 
 
+# ============================================================================================================ stem conv / VALU head conv
+def _conv_rowwrap(x, w):
+    """3x3 conv of x [B, C, H, W] with the ROWS zero-padded but the columns taken at the flat index p + dx: at x = 0 / x = W - 1 the
+    left / right tap is the last / first pixel of the neighbouring row (zero only in front of the first and behind the last padded row)"""
+    B, C, H, W = x.shape
+    flat = F.pad(F.pad(x, (0, 0, 1, 1)).reshape(B, C, (H + 2) * W), (1, 1))
+    y = 0
+    for t in range(9):
+        start = (t // 3) * W + (t % 3)                       # (1 + dy) W + dx + 1
+        y = y + torch.einsum("bcp,nc->bnp", flat[..., start:start + H * W], w[:, :, t // 3, t % 3])
+    return y.reshape(B, -1, H, W)
+
+
+def _conv_stacked(x, w):
+    """the samples stacked vertically: each one's top / bottom pad row is its neighbour's edge row"""
+    B, C, H, W = x.shape
+    return F.conv2d(x.permute(1, 0, 2, 3).reshape(1, C, B * H, W), w, padding=1).reshape(-1, B, H, W).permute(1, 0, 2, 3)
+
+
+class ConvIn:
+    """The stem conv (rdm_op_conv_in: conv_in_kernel<OCT, CIN>, OCT = 4 when Cout % 32 == 0 else 0, CIN = 3 for Cin <= 3 else 4): 3x3,
+    pad 1, x fp32 NCHW [B, Cin, H, W], w fp32 [Cout, Cin, 3, 3], bias fp32 -> bf16 NHWC.  A thread owns a pixel: its accumulator starts
+    from the bias and takes one fp32 FMA per (channel, tap) -- a chain of 9 CIN = 9 Cin terms for Cin = 3 or 4 -- then one bf16 rounding:
+    r = 2^-8, a = (9 Cin + 2) u S, S = sum |x| |w| + |b|.  Inputs: every channel plane carries its own offset.  Near misses: the taps
+    flipped; the neighbouring sample's rows instead of the zero padding; row wrap (the flat-index neighbour p +- 1 at x = 0 / W - 1
+    instead of zero); the channel planes rotated; the bias missing on the last 8 channels; the pixels behind the last whole 64 of a
+    sample written as zero (a lane that leaves the pixel loop takes the staged stores of its wave with it)."""
+    name = "conv_in"
+    exact = False
+
+    @staticmethod
+    def make(B, Cin, H, W, Cout, seed=121):
+        g = torch.Generator().manual_seed(seed)
+        off = torch.tensor([1.5, -2.0, 0.7, 3.0])[:Cin]
+        return {"x": torch.randn(B, Cin, H, W, generator=g) + off[None, :, None, None],
+                "w": torch.randn(Cout, Cin, 3, 3, generator=g) / math.sqrt(9 * Cin), "b": 0.5 * torch.randn(Cout, generator=g)}
+
+    @staticmethod
+    def ref(inp, dt, conv=None, x=None, w=None, bias_cut=False, tail_zero=False):
+        x = (inp["x"] if x is None else x).to(dt)
+        w = (inp["w"] if w is None else w).to(dt)
+        b = inp["b"].to(dt).clone()
+        if bias_cut:
+            b[-8:] = 0
+        y = (F.conv2d(x, w, padding=1) if conv is None else conv(x, w)) + b[None, :, None, None]
+        y = y.permute(0, 2, 3, 1).contiguous()
+        if tail_zero:
+            B, H, W, N = y.shape
+            y.view(B, H * W, N)[:, H * W // 64 * 64:] = 0
+        return {"out": y}
+
+    @staticmethod
+    def bound(inp, ref):
+        Cin = inp["x"].shape[1]
+        S = F.conv2d(inp["x"].double().abs(), inp["w"].double().abs(), inp["b"].double().abs(), padding=1).permute(0, 2, 3, 1)
+        return {"out": (BF, (9 * Cin + 2) * U * S)}
+
+    @staticmethod
+    def misses(inp):
+        m = [("taps flipped", ConvIn.ref(inp, F64, w=inp["w"].flip(2, 3))), ("row wrap", ConvIn.ref(inp, F64, conv=_conv_rowwrap)),
+             ("channel planes rotated", ConvIn.ref(inp, F64, x=inp["x"].roll(1, 1))),
+             ("bias missing on the last 8 channels", ConvIn.ref(inp, F64, bias_cut=True)),
+             ("pixels behind the last whole 64 written as zero", ConvIn.ref(inp, F64, tail_zero=True))]
+        if inp["x"].shape[0] > 1:
+            m.append(("neighbouring sample instead of zero padding", ConvIn.ref(inp, F64, conv=_conv_stacked)))
+        return m
+
+
+class ConvOut:
+    """The VALU head conv (rdm_op_conv_out: conv_out_kernel, what Ops::head falls back to where W % 32 or an odd H rules out the fused
+    head conv): 3x3, pad 1, x bf16 NHWC, w fp32 [Cout, Cin, 3, 3], bias fp32 -> fp32 NCHW.  Eight lanes share a pixel: a lane takes every
+    eighth 16-byte piece of each tap's channel row, i.e. 9 Cin / 8 products summed in order in fp32, then three shuffle adds combine the
+    eight lanes and the bias is added: r = 0, a = (9 Cin / 8 + 8) u S, S = sum |x| |w| + |b|.  Near misses: the taps flipped; the
+    neighbouring sample's rows instead of the zero padding; row wrap; the bias missing; the output channels swapped; the last 64-channel
+    slice dropped."""
+    name = "conv_out"
+    exact = False
+
+    @staticmethod
+    def make(B, H, W, Cin, Cout, seed=131):
+        g = torch.Generator().manual_seed(seed)
+        x = bfr(torch.randn(B, H, W, Cin, generator=g) + 0.5 * torch.randn(1, 1, 1, Cin, generator=g))
+        return {"x": x, "w": torch.randn(Cout, Cin, 3, 3, generator=g) / (3 * Cin ** 0.5), "b": torch.randn(Cout, generator=g)}
+
+    @staticmethod
+    def ref(inp, dt, conv=None, w=None, no_bias=False, swap=False):
+        x = inp["x"].to(dt).permute(0, 3, 1, 2)
+        w = (inp["w"] if w is None else w).to(dt)
+        y = F.conv2d(x, w, padding=1) if conv is None else conv(x, w)
+        if not no_bias:
+            y = y + inp["b"].to(dt)[None, :, None, None]
+        return {"out": y.flip(1) if swap else y}
+
+    @staticmethod
+    def bound(inp, ref):
+        Cin = inp["x"].shape[3]
+        S = F.conv2d(inp["x"].double().abs().permute(0, 3, 1, 2), inp["w"].double().abs(), inp["b"].double().abs(), padding=1)
+        return {"out": (0.0, (9 * Cin // 8 + 8) * U * S)}
+
+    @staticmethod
+    def misses(inp):
+        w = inp["w"].clone(); w[:, -64:] = 0
+        m = [("taps flipped", ConvOut.ref(inp, F64, w=inp["w"].flip(2, 3))), ("row wrap", ConvOut.ref(inp, F64, conv=_conv_rowwrap)),
+             ("bias missing", ConvOut.ref(inp, F64, no_bias=True)), ("output channels swapped", ConvOut.ref(inp, F64, swap=True)),
+             ("last 64-channel slice dropped", ConvOut.ref(inp, F64, w=w))]
+        if inp["x"].shape[0] > 1:
+            m.append(("neighbouring sample instead of zero padding", ConvOut.ref(inp, F64, conv=_conv_stacked)))
+        return m
+
+
 # ============================================================================================================ the parametrisations
 # (case, shape kwargs, the launch path it reaches); the path strings come from the host-side launch rules above where they exist, so a
 # test id names the kernel instantiation it exercises
 _L, _LN, _CV, _GN, _LY, _SA, _SM, _XA, _HC = Linear, LinearLN, Conv3x3, GroupNorm, LayerNorm, SelfAttention, SmallAttention, XattnFused, HeadConv
+_CI, _CO = ConvIn, ConvOut
 
 
 def _lin(**kw):
@@ -872,7 +1009,23 @@ def _gn(**kw):
     B, HW, C = kw["B"], kw["HW"], kw["C0"] + kw.get("C1", 0)
     plan = gn_onepass_plan(HW, C)
     path = f"gn_onepass<NV{plan[2]}, {plan[1]}>" if plan else "gn_stats + gn_apply"
+    if plan is None:                                         # model.hip gn_chunks: the pixel chunks of the statistics pass
+        nchunk = min(32, max(1, HW // 64))
+        if HW % nchunk:
+            path += f": {nchunk} chunks of {_cdiv(HW, nchunk)} rows, the last one short"
     return (_GN, kw, path + (" (XCD block order)" if plan and B % 8 == 0 else ""))
+
+
+def _cin(**kw):
+    npix, grid = kw["H"] * kw["W"], min(_cdiv(kw["H"] * kw["W"], 512), _cdiv(2048, kw["B"]))      # misc.hip launch_conv_in
+    path = f"conv_in_kernel<{4 if kw['Cout'] % 32 == 0 else 0}, {3 if kw['Cin'] <= 3 else 4}>: {npix} pixels"
+    return (_CI, kw, path + (f", {grid} blocks x {_cdiv(npix, 512 * grid)} trips" if npix > 512 * grid else ""))
+
+
+def _sm(**kw):
+    kc = small_attention_chunk(kw["nkv"], kw["D"])
+    path = f"small_attention_kernel<{kw['D']}>: " + ("causal, " if kw.get("causal") else "") + f"{_cdiv(kw['nkv'], kc)} key chunks"
+    return (_SM, kw, path)
 
 
 def _ly(**kw):
@@ -942,6 +1095,25 @@ CASES = [
     _conv(B=5, H=4, W=4, C0=64, N=128, res=True),
     _conv(B=3, H=4, W=4, C0=64, N=128, ups=1, res=True),
     _conv(B=2, H=16, W=16, C0=64, N=64, stride=2),
+    # 192-wide strip tiles; odd widths, M a multiple of neither 256 nor 64, HW % 32 != 0 under a per-sample row, stride 2 on a non-square
+    # input, the phase and dual-source upsample forms at odd widths (implicit GEMM)
+    _conv(B=1, H=4, W=128, C0=64, N=192),
+    _conv(B=2, H=8, W=192, C0=64, C1=64, N=192, rowvec=True, res=True),
+    _conv(B=1, H=2, W=64, C0=64, N=192, ups=1, rowvec=True),
+    _conv(B=2, H=5, W=7, C0=64, N=64),
+    _conv(B=1, H=10, W=14, C0=64, C1=64, N=128, rowvec=True, ld_pad=5, res=True),
+    _conv(B=3, H=6, W=10, C0=64, N=64, stride=2),
+    _conv(B=2, H=5, W=7, C0=64, N=64, ups=1),
+    _conv(B=1, H=5, W=7, C0=64, C1=64, N=72, ups=1),
+    # stem conv, all four instantiations: one partial wave; direct stores, four input channels; a short second block; one pixel; a ragged
+    # second grid-stride trip
+    _cin(B=2, Cin=3, H=5, W=7, Cout=64),
+    _cin(B=1, Cin=4, H=9, W=8, Cout=40),
+    _cin(B=1, Cin=4, H=9, W=8, Cout=32),
+    _cin(B=2, Cin=3, H=5, W=7, Cout=40),
+    _cin(B=3, Cin=3, H=20, W=28, Cout=128),
+    _cin(B=1, Cin=3, H=1, W=1, Cout=32),
+    _cin(B=64, Cin=3, H=130, W=130, Cout=32),
     # GroupNorm
     _gn(B=8, HW=1024, C0=384, silu=1, offset=True),
     _gn(B=3, HW=1024, C0=384, silu=0, small_var=True),
@@ -951,6 +1123,12 @@ CASES = [
     _gn(B=2, HW=816, C0=640, silu=1, offset=True),
     _gn(B=2, HW=4096, C0=64, silu=1, offset=True),
     _gn(B=2, HW=4096, C0=192, C1=192, silu=0, small_var=True),
+    _gn(B=2, HW=1100, C0=64, silu=1, offset=True),
+    _gn(B=2, HW=1100, C0=192, C1=192, silu=0, small_var=True),
+    _gn(B=3, HW=35, C0=256, silu=1, offset=True),
+    _gn(B=2, HW=50, C0=192, silu=0),
+    _gn(B=2, HW=200, C0=128, C1=64, silu=1, offset=True),
+    _gn(B=4, HW=2, C0=64, silu=0),
     # LayerNorm
     _ly(M=100, C=384, offset=True),
     _ly(M=77, C=512, f32=True, small_var=True),
@@ -965,10 +1143,16 @@ CASES = [
     (_SA, dict(B=1, n=256, H=3, mode="qkv"), "flash_d32_lds_kernel<true>"),
     (_SA, dict(B=2, n=96, H=2, mode="vt"), "flash_d32_kernel (n % 64 != 0)"),
     (_SA, dict(B=1, n=1024, H=2, mode="vt"), "flash_d32_lds_kernel<false>: n = 1024"),
+    (_SA, dict(B=1, n=32, H=1, mode="vt"), "flash_d32_kernel: one 32-row tile"),
+    (_SA, dict(B=2, n=160, H=2, mode="vt"), "flash_d32_kernel: n = 160"),
+    (_SA, dict(B=1, n=800, H=1, mode="vt"), "flash_d32_kernel: n = 800"),
     (_SM, dict(B=2, nq=64, nkv=4, H=4, D=32), "small_attention_kernel<32>"),
     (_SM, dict(B=2, nq=77, nkv=77, H=2, D=64, causal=1), "small_attention_kernel<64>: causal"),
     (_SM, dict(B=2, nq=300, nkv=1, H=2, D=32), "small_attention_kernel<32>: one key"),
     (_SM, dict(B=1, nq=1024, nkv=16, H=6, D=32), "small_attention_kernel<32>: many queries, few keys"),
+    _sm(B=2, nq=70, nkv=257, H=2, D=32),
+    _sm(B=1, nq=600, nkv=600, H=1, D=32),
+    _sm(B=2, nq=200, nkv=200, H=1, D=64, causal=1),
     (_XA, dict(B=2, n=64, heads=4, k=4), "xattn_fused_kernel: bias + residual"),
     (_XA, dict(B=2, n=32, heads=2, k=1, bias=False, res=False), "xattn_fused_kernel: no bias / residual"),
     (_XA, dict(B=8, n=64, heads=4, k=2), "xattn_fused_kernel: XCD block order"),
@@ -978,6 +1162,10 @@ CASES = [
     (_HC, dict(B=2, H=34, W=64, C=224, Cout=4), "head_conv_kernel: band split (H = 34)"),
     (_HC, dict(B=3, H=16, W=32, C=64, Cout=4, norm=False), "head_conv_kernel: no norm"),
     (_HC, dict(B=6, H=8, W=32, C=32, Cout=1), "head_conv_kernel: Cout = 1"),
+    # the VALU head conv: odd sizes, a latent width of 28, one output channel
+    (_CO, dict(B=2, H=5, W=7, Cin=64, Cout=3), "conv_out_kernel: 35 pixels"),
+    (_CO, dict(B=1, H=20, W=28, Cin=128, Cout=4), "conv_out_kernel: 560 pixels, Cout = 4"),
+    (_CO, dict(B=3, H=3, W=50, Cin=192, Cout=1), "conv_out_kernel: Cout = 1"),
 ]
 
 
@@ -990,4 +1178,4 @@ def bf16_out(case, inp, key):
     """does the kernel write this output as bf16 (the stand-in rounds it the same way)"""
     if case is Linear:
         return not inp["f32"]
-    return case is not HeadConv
+    return case not in (HeadConv, ConvOut)

@@ -24,12 +24,16 @@ def test_fp32_restatement_within_bound_and_near_misses_outside(entry):
 
 def test_every_forward_op_is_parametrised():
     names = {e[0].name for e in R.CASES}
-    assert names == {"linear", "linear_ln", "conv3x3", "groupnorm", "layernorm", "self_attention", "small_attention", "xattn_fused", "head_conv"}
+    assert names == {"linear", "linear_ln", "conv3x3", "groupnorm", "layernorm", "self_attention", "small_attention", "xattn_fused", "head_conv",
+                     "conv_in", "conv_out"}
 
 
 def test_case_ids_name_every_launch_path():
     paths = " | ".join(e[2] for e in R.CASES)
-    for kernel in ("halo4<2>", "halo4<3>", "halo4<2, STRIP>", "K-split 2", "K-split 3", "igemm phase2", "igemm conv",
+    for kernel in ("halo4<2>", "halo4<3>", "halo4<2, STRIP>", "halo4<3, STRIP>", "conv_in_kernel<4, 3>", "conv_in_kernel<4, 4>", "conv_in_kernel<0, 3>", "conv_in_kernel<0, 4>",
+                   "conv_out_kernel", "small_attention_kernel<32>: 2 key chunks", "small_attention_kernel<32>: 3 key chunks",
+                   "small_attention_kernel<64>: causal, 2 key chunks", "gn_stats + gn_apply: 17 chunks of 65 rows, the last one short",
+                   "blocks x 2 trips", "K-split 2", "K-split 3", "igemm phase2", "igemm conv",
                    "igemm ups", "igemm<128, 128", "igemm<256, 192", "igemm<128, 192", "igemm<256, 128", "res_k", "igemm<256, 256, GEGLU>",
                    "igemm<128, 128, GEGLU>", "igemm<256, 128, GEGLU>", "lin4<plain, WM1>", "lin4<plain, WM2>", "lin4<GEGLU, WM1>",
                    "lin4<GEGLU, WM2>", "rowvec", "sgemm", "mgemm", "LN>", "gn_onepass<NV", ", 512>", ", 1024>", "gn_stats + gn_apply",

@@ -17,7 +17,8 @@ What this can and cannot bound (measured, tools/emul_probe.py):
 Covered: (1) the direct forward of the shipped 400.9 M-parameter UNet, (2) the forward inside rdm_ddim_sample on a guided batch (shared
 guidance prefix, zero-neighbour rows with attn2's bias folded into attn1.to_out, in-place cross-attention + norm3) and the CFG combine /
 DDIM update that follows it, (3) the VQ-f4 decoder layer by layer, (4) tight op-level checks incl. the exact-erf GELU, (5) the free-running
-distances with the statement above as assertions.  The emulators are pinned on the CPU: rounding off, they equal the fp32 oracle to 2e-5
+distances with the statement above as assertions, (6) the same stage-by-stage comparison at sizes that are not the training size: the tiny UNet at
+latent 36 x 40 and the tiny VQ-f4 decoder at latents 5 x 7 / 9 x 8 (the kernel paths only such sizes reach).  The emulators are pinned on the CPU: rounding off, they equal the fp32 oracle to 2e-5
 (tests/test_oracle_cpu.py), and the fp32 oracle equals the reference's classes bit for bit (tools/gen_golden*.py).
 
 Reference: rdm/modules/diffusionmodules/openaimodel.py:129 (fp32 compute), :335-371; rdm/modules/attention.py:77-196; ddim.py:217-268."""
@@ -220,3 +221,74 @@ def test_ops_against_their_own_arithmetic(ctx):
     print(f"[emul] (the GEGLU output against a tanh-approximated GELU: {e_tanh:.3e})")
     assert max(res.values()) <= OP_TOL, res
     assert e_tanh > 2 * OP_TOL, "the GEGLU check would not tell erf from tanh"
+
+
+# ------------------------------------------------------------------------------------------------ sizes that are not the training size
+def _teacher_forced_unet(ctx, spec, sd, x, t, c):
+    """-> ({stage: error}, error of eps from the library's last block): every tap of one direct forward against the restatement run on
+    the library's own value of the previous stage"""
+    B = x.shape[0]
+    free = {}
+    unet_forward_emulated(sd, spec, x, t, c, taps=free)
+    lib = _library_stages(ctx, lambda: ctx.unet_forward(x, t, c), {k: v.shape for k, v in free.items()}, lambda key: B)
+    own = {}
+    emu_tf = unet_forward_emulated(sd, spec, x, t, c, taps=own, forced=lib)
+    eps = ctx.unet_forward(x, t, c)
+    torch.cuda.synchronize()
+    return {k: rel_l2(lib[k], own[k]) for k in lib}, rel_l2(eps, emu_tf)
+
+
+def test_unet_stage_by_stage_at_latent_36x40(ctx):
+    """The tiny UNet with self-attention at every level, latent 36 x 40, B = 2 with one zero-context row, k = 4, direct forward.  Its levels:
+    1440 pixels (flash_d32_kernel at n % 64 == 32, two-pass GroupNorm whose 22 chunks of 66 rows do not divide 1440, 40-wide generic convs),
+    360 pixels (small self-attention with its keys in two LDS chunks, cross-attention as two skinny GEMMs), 90 pixels (small attention in
+    one chunk, 10-wide convs); the 40-wide `out` conv falls to conv_out_kernel.  Every tap teacher-forced at STAGE_TOL, and eps from the
+    library's last block."""
+    from dataclasses import replace
+    from rdm_amd import packing
+    spec = replace(ounet.tiny_spec(), attention_resolutions=(1, 2, 4))
+    sd = ounet.synth_state_dict(ounet.param_shapes(spec), seed=4321)
+    cfg = spec_to_unet_cfg(spec)
+    ctx.load_unet(cfg, packing.pack("unet", cfg, sd))
+    g = torch.Generator().manual_seed(3640)
+    x, t = torch.randn(2, 3, 36, 40, generator=g), torch.tensor([917, 12])
+    c = torch.randn(2, 4, 512, generator=g) * 0.45
+    c[1] = 0
+    errs, e_eps = _teacher_forced_unet(ctx, spec, sd, x, t, c)
+    worst = max(errs, key=errs.get)
+    print(f"[emul] tiny UNet at latent 36x40, {len(errs)} stages teacher-forced: worst {errs[worst]:.3e} at {_stage_name(spec, worst)}; eps (conv_out_kernel head on the library's last block) {e_eps:.3e}")
+    for k, e in errs.items():
+        assert e <= STAGE_TOL, f"{_stage_name(spec, k)}: library vs its restatement on the library's own inputs {e:.3e}"
+    assert e_eps <= STAGE_TOL
+
+
+@pytest.mark.parametrize("h,w", [(5, 7), (9, 8)])
+def test_vq_decoder_layer_by_layer_on_padded_tokens(ctx, h, w):
+    """The tiny VQ-f4 decoder (force_not_quantize) at latents whose mid AttnBlock runs on padded tokens: 5 x 7 = 35 tokens in np = 64, 9 x 8 =
+    72 tokens in np = 128 (two key tiles, the second mostly padding); odd widths on the generic conv, conv_in on a partial wave and the
+    head on conv_out_kernel (image widths 28 / 32 x heights 20 / 36).  Every layer tap teacher-forced at 2 STAGE_TOL per block, the image
+    from the library's last layer at STAGE_TOL."""
+    from rdm_amd import packing
+    vs = ovq.tiny_vq_spec()
+    sd = ounet.synth_state_dict(ovq.vq_param_shapes(vs), seed=5)
+    cfg = spec_to_vq_cfg(vs)
+    ctx.load_vq(cfg, packing.pack("vq", cfg, sd))
+    z = torch.randn(2, 3, h, w, generator=torch.Generator().manual_seed(100 * h + w))
+    free = []
+    vq_decode_emulated(sd, vs, z, force_not_quantize=True, taps=free)
+    lib = {}
+    for i, tp in enumerate(free):
+        buf = torch.empty(tuple(tp.shape), device=ctx.device, dtype=torch.bfloat16)
+        ctx.debug_tap(buf, 1000 + i, 0)
+        img = ctx.vq_decode(z, force_not_quantize=True)
+        torch.cuda.synchronize()
+        lib[i] = buf.float().cpu()
+    ctx.debug_tap(None, -1)
+    own = []
+    emu_tf = vq_decode_emulated(sd, vs, z, force_not_quantize=True, taps=own, forced=lib)
+    errs = [rel_l2(lib[i], own[i]) for i in range(len(own))]
+    e_img = rel_l2(img, emu_tf)
+    print(f"[emul] tiny vq-f4 decoder at latent {h}x{w}, {len(own)} layers teacher-forced: worst {max(errs):.3e} (layer {int(np.argmax(errs))}); image from the library's last layer {e_img:.3e}")
+    assert tuple(img.shape) == (2, 3, 4 * h, 4 * w)
+    assert max(errs) <= 2 * STAGE_TOL, errs
+    assert e_img <= STAGE_TOL

@@ -212,6 +212,28 @@ def test_single_op_entry_points_reject_unsupported_shapes(fresh):
     assert out.shape == (1, 3, 8, 32) and float(out.abs().max()) == 0.0
 
 
+def test_stem_and_valu_head_conv_entries_state_their_shape_contract(fresh):
+    """rdm_op_conv_in / rdm_op_conv_out answer what their launchers would refuse with a message, not a bare HIP error code, and the context
+    keeps working after each refusal."""
+    d = fresh.device
+    f32 = lambda *s: torch.zeros(*s, device=d)
+    bf = lambda *s: torch.zeros(*s, device=d, dtype=torch.bfloat16)
+    ok_in = lambda: fresh.op_conv_in(f32(1, 3, 4, 5) + 1, f32(8, 3, 3, 3), f32(8) + 2)
+    ok_out = lambda: fresh.op_conv_out(bf(1, 4, 5, 64), f32(2, 64, 3, 3), f32(2) + 3)
+    msg = _err(lambda: fresh.op_conv_in(f32(1, 5, 4, 4), f32(8, 5, 3, 3), f32(8)))                   # Cin = 5
+    assert "rdm_op_conv_in" in msg and "unsupported shape" in msg and "Cin 5" in msg
+    assert tuple(ok_in().shape) == (1, 4, 5, 8) and float((ok_in().float() - 2).abs().max()) == 0.0
+    msg = _err(lambda: fresh.op_conv_in(f32(1, 3, 4, 4), f32(12, 3, 3, 3), f32(12)))                 # Cout % 8
+    assert "rdm_op_conv_in" in msg and "unsupported shape" in msg and "Cout 12" in msg
+    assert float((ok_in().float() - 2).abs().max()) == 0.0
+    msg = _err(lambda: fresh.op_conv_out(bf(1, 4, 4, 96), f32(3, 96, 3, 3), f32(3)))                 # Cin % 64
+    assert "rdm_op_conv_out" in msg and "unsupported shape" in msg and "Cin 96" in msg
+    assert tuple(ok_out().shape) == (1, 2, 4, 5) and float((ok_out() - 3).abs().max()) == 0.0
+    msg = _err(lambda: fresh.op_conv_out(bf(1, 4, 4, 64), f32(5, 64, 3, 3), f32(5)))                 # Cout = 5
+    assert "rdm_op_conv_out" in msg and "unsupported shape" in msg and "Cout 5" in msg
+    assert float((ok_out() - 3).abs().max()) == 0.0
+
+
 def test_training_primitives_refuse_bad_sizes(fresh):
     """The backward primitives check their sizes at the C ABI instead of launching a zero-size grid or returning a bare HIP error: each
     refusal names the op, and the context keeps working afterwards."""

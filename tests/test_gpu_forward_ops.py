@@ -1,5 +1,5 @@
-"""The inference forward kernels (linear / lin4 / sgemm / mgemm, the LayerNorm-folded projection, conv3x3 on every launch path,
-GroupNorm, LayerNorm, flash and small attention, the fused cross-attention, the head conv) called through the C ABI and held to a
+"""The inference forward kernels (linear / lin4 / sgemm / mgemm, the LayerNorm-folded projection, conv3x3 on every launch path, the
+stem conv, GroupNorm, LayerNorm, flash and small attention, the fused cross-attention, the head conv and its VALU fallback) called through the C ABI and held to a
 float64 CPU restatement of the same operation, element by element (tests/_fwd_ref.py states each bound and near miss).  Every case
 also shows that its bound discriminates: the kernel output must fall outside the bound against each near-miss reference.  Kernels that
 sum in a fixed order are called twice and must agree bitwise; for the batched tile geometries, changing one sample's input must leave
@@ -69,6 +69,10 @@ def _run(ctx, case, inp):
     if case is R.HeadConv:
         gn = (f(inp["gamma"]), f(inp["beta"]), inp["eps"]) if inp["norm"] else None
         return {"out": ctx.op_head_conv(b(inp["x"]), f(inp["w"]), f(inp["bias"]), gn=gn)}
+    if case is R.ConvIn:
+        return {"out": ctx.op_conv_in(f(inp["x"]), f(inp["w"]), f(inp["b"]))}
+    if case is R.ConvOut:
+        return {"out": ctx.op_conv_out(b(inp["x"]), f(inp["w"]), f(inp["b"]))}
     raise AssertionError(case.name)
 
 

@@ -225,6 +225,44 @@ def test_emulated_unet_is_exact_algebra_without_rounding():
     assert 1e-4 < e <= 2.5e-2, e
 
 
+def test_emulated_unet_is_exact_algebra_at_a_non_square_size():
+    """The same pin at latent 12 x 20 with self-attention at every level (240 / 60 / 15 tokens): 240 and 60 are no multiples of 32, where
+    the restatement follows small_attention_kernel (fp32 probabilities), and every level is non-square with an odd width at the bottom --
+    what tests/test_gpu_emul.py trusts the emulator for at sizes other than the training size."""
+    from dataclasses import replace
+    from oracle import unet as ounet
+    from oracle.unet_emul import unet_forward_emulated
+    spec = replace(ounet.tiny_spec(), attention_resolutions=(1, 2, 4))
+    sd = ounet.synth_state_dict(ounet.param_shapes(spec), seed=12)
+    g = torch.Generator().manual_seed(4)
+    x = torch.randn(2, 3, 12, 20, generator=g)
+    t = torch.tensor([700, 33])
+    ctx = torch.randn(2, 4, 512, generator=g) * 0.45
+    ctx[1] = 0
+    ref = ounet.unet_forward(sd, spec, x, t, ctx)
+    taps = {}
+    got = unet_forward_emulated(sd, spec, x, t, ctx, rounding=False, taps=taps)
+    e = float((got - ref).norm() / ref.norm())
+    assert e <= 2e-5, e
+    assert {v.shape[1] for v in taps.values()} == {240, 60, 15}
+    e = float((unet_forward_emulated(sd, spec, x, t, ctx) - ref).norm() / ref.norm())
+    assert 1e-4 < e <= 2.5e-2, e
+
+
+def test_emulated_vq_decoder_is_exact_algebra_at_a_non_square_size():
+    """The decoder restatement at a 5 x 7 latent (35 tokens in the mid AttnBlock, odd widths 7 / 14 / 28), rounding off, against the fp32 oracle."""
+    from oracle import unet as ounet, vqdecoder as ovq
+    from oracle.vq_emul import vq_decode_emulated
+    spec = ovq.tiny_vq_spec()
+    sd = ounet.synth_state_dict(ovq.vq_param_shapes(spec), seed=5)
+    z = torch.randn(2, 3, 5, 7, generator=torch.Generator().manual_seed(6))
+    ref = ovq.vq_decode(sd, spec, z, force_not_quantize=True)
+    assert tuple(ref.shape) == (2, 3, 20, 28)
+    got = vq_decode_emulated(sd, spec, z, force_not_quantize=True, rounding=False)
+    e = float((got - ref).norm() / ref.norm())
+    assert e <= 2e-5, e
+
+
 def test_emulated_vq_decoder_is_exact_algebra_without_rounding():
     from oracle import unet as ounet, vqdecoder as ovq
     from oracle.vq_emul import vq_decode_emulated
