@@ -205,9 +205,10 @@ int rdm_vq_decode_indices(rdm_ctx* ctx, const int64_t* indices, int b, float* im
  *   rdm_vq_decode_hw:   z [dev] f32 [b,z_channels,h,w] -> img_out [dev] f32 [b,out_ch,f*h,f*w]; indices_out [dev] int32 [b,h*w] or NULL
  *   rdm_vq_quantize_hw: z [dev] f32 [b,3,h,w] -> zq_out [dev] f32 [b,3,h,w]; indices_out as above
  * Any h, w >= 1.  What runs where: 3x3 convs of levels whose width is at most 64 with 256 % width == 0, or a multiple of 64 with
- * height % 4 == 0, on the halo kernels, every other width on the generic implicit GEMM; the mid AttnBlock materialises its n x n scores
- * (n = h*w, padded to a multiple of 64), so a batch is walked in ranges of at most 8 GiB of them, and a latent of more than 46336 pixels
- * -- or one whose largest activation passes 2^30 elements -- is refused (-1); work buffers that cannot be allocated: -2.  Not for wide
+ * height % 4 == 0, on the halo kernels, every other width on the generic implicit GEMM; an AttnBlock over at most 4096 pixels materialises
+ * its n x n scores (n = h*w, padded to a multiple of 64; a batch is walked in ranges of at most 8 GiB of them), beyond that it streams them
+ * (rdm_op_vq_attention; widths that are multiples of 128 up to 512 -- any other width keeps materialising, up to 46336 pixels).  A latent
+ * whose largest activation passes 2^30 elements per sample is refused (-1); work buffers that cannot be allocated: -2.  Not for wide
  * latents (VQGAN-f16: its 256-token sequence fixes its size) -- rdm_vq_decode_indices / rdm_vq_encode_indices stay square. */
 int rdm_vq_decode_hw(rdm_ctx* ctx, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out);
 int rdm_vq_quantize_hw(rdm_ctx* ctx, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out);
@@ -498,6 +499,16 @@ int rdm_op_xattn_fused_ln3(rdm_ctx* ctx, void* x_bf16_inout, const float* ln_gam
  * bf16: rows 0..n-1 receive the K / V columns of qkv bit for bit (the decode step's cache layout), rows >= n are not touched. */
 int rdm_op_causal_attention_d64(rdm_ctx* ctx, const void* qkv_bf16, int ldq, int B, int n, int heads, float scale, void* out_bf16, int ldo,
                                 void* kcache_bf16_or_null, void* vcache_bf16_or_null, int L);
+/* The first stage's AttnBlock without its n x n scores (ldm/modules/diffusionmodules/model.py AttnBlock.forward: q k^T * C^-1/2 -> softmax ->
+ * . v over the h*w pixels, one head of C channels; what rdm_vq_decode_hw / rdm_vq_encode_hw run beyond 4096 pixels):
+ *   out[b] = softmax(q[b] k[b]^T * scale) v[b] + bias_v
+ * q, k, v bf16 token-major [B*n rows at strides ldq / ldk / ldv, multiples of 8, 16-byte aligned] (column blocks of one fused q | k | v
+ * projection may be passed), bias_v f32 [C] or NULL, out bf16 [B*n, C] at stride ldo (a multiple of 4).  Any n >= 1; C a multiple of 128,
+ * at most 512.  The arithmetic of rdm_op_bmm(alpha) -> rdm_op_softmax -> rdm_op_bmm: fp32 scores, the normalised probability rounded to
+ * bf16, fp32 accumulation, one rounding of the result; two sweeps over the keys per 64 query rows, nothing of size n x n in memory, and a
+ * sample's result does not depend on B. */
+int rdm_op_vq_attention(rdm_ctx* ctx, const void* q_bf16, int ldq, const void* k_bf16, int ldk, const void* v_bf16, int ldv,
+                        const float* bias_v_or_null, int B, int n, int C, float scale, void* out_bf16, int ldo);
 /* nll_out[r] = logsumexp(logits[r,:]) - logits[r, targets[r]] in fp32 (F.cross_entropy(reduction='none'), transformer.py:62-70):
  * logits f32 [rows, vocab] (vocab even), targets int64 [rows]; a target outside [0, vocab) gives NaN. */
 int rdm_op_rarm_nll(rdm_ctx* ctx, const float* logits, long long rows, int vocab, const int64_t* targets, float* nll_out);

@@ -185,6 +185,7 @@ SIGNATURES = {
     "rdm_op_xattn_fused": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_causal_attention_d64": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P, _P, C.c_int]),
     "rdm_op_rarm_nll": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
+    "rdm_op_vq_attention": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int]),
     "rdm_op_causal_attention_d64_bwd": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int]),
     "rdm_op_rarm_nll_bwd": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, C.c_float, _P, _P]),
     "rdm_op_embedding_grad": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -1247,6 +1248,28 @@ class Context:
         out = torch.empty((B, n, heads * 64), device=self.device, dtype=torch.bfloat16)
         opt = lambda t: _ptr(t) if t is not None else None
         self._check(lib.rdm_op_causal_attention_d64(self._h, _ptr(qkv), C3, B, n, heads, float(scale), _ptr(out), heads * 64, opt(kcache), opt(vcache), L))
+        return out
+
+    def op_vq_attention(self, q, k, v, bias_v=None, scale=None):
+        """The first stage's AttnBlock attention without its n x n scores: softmax(q k^T scale) v + bias_v over one head of C channels.
+        q, k, v bf16 [B,n,C], each rows of C contiguous channels at one row stride (column blocks of a fused [B,n,3C] projection are fine);
+        bias_v f32 [C] or None; scale defaults to C ** -0.5.  Any n >= 1, C a multiple of 128 up to 512 -> bf16 [B,n,C]."""
+        B, n, Cc = q.shape
+        if tuple(k.shape) != (B, n, Cc) or tuple(v.shape) != (B, n, Cc):
+            raise RdmError(f"op_vq_attention: q, k, v must share one shape [B,n,C], got {tuple(q.shape)} / {tuple(k.shape)} / {tuple(v.shape)}")
+        for t in (q, k, v):
+            assert t.dtype == torch.bfloat16 and t.is_cuda
+            if n > 0 and (t.stride(2) != 1 or (B > 1 and t.stride(0) != n * t.stride(1))):
+                raise RdmError(f"op_vq_attention: rows of contiguous channels at one row stride required, got strides {t.stride()}")
+        if bias_v is not None:
+            bias_v = self._dev(bias_v, torch.float32).contiguous()
+            if tuple(bias_v.shape) != (Cc,):
+                raise RdmError(f"op_vq_attention: bias_v must be [{Cc}], got {tuple(bias_v.shape)}")
+        out = torch.empty((B, n, Cc), device=self.device, dtype=torch.bfloat16)
+        ld = lambda t: t.stride(1) if n > 0 else Cc
+        raw = lambda t: C.c_void_p(t.data_ptr())           # views: _ptr() takes contiguous tensors only
+        self._check(lib.rdm_op_vq_attention(self._h, raw(q), ld(q), raw(k), ld(k), raw(v), ld(v), _ptr(bias_v) if bias_v is not None else None, B, n, Cc,
+                                            float(Cc ** -0.5 if scale is None else scale), _ptr(out), Cc))
         return out
 
     def op_rarm_nll(self, logits, targets):

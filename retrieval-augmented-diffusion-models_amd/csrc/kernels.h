@@ -75,6 +75,17 @@ struct CausalD64Params {
     int L;
 };
 
+// streaming single-head attention of the first stage's AttnBlock (vq_attn.hip): out[b] = softmax(q[b] k[b]^T scale) v[b] + bias
+struct VqAttnParams {
+    const bf16_t* q; int ldq;        // q[(b*n + i)*ldq + d]   (row strides in elements, multiples of 8)
+    const bf16_t* k; int ldk;        // k[(b*n + j)*ldk + d]
+    const bf16_t* v; int ldv;        // v[(b*n + j)*ldv + d]   (token-major)
+    const float* bias;               // [C] added after P.V (rows of P sum to 1), or null
+    bf16_t* out; int ldo;            // out[(b*n + i)*ldo + d]  (ldo a multiple of 4)
+    int n, C;                        // tokens per sample (any n >= 1), channels (a multiple of 128, <= 512)
+    float scale;
+};
+
 struct DdimStepParams {
     const float* x; const float* eps; const float* noise;   // noise may be null (eta == 0)
     float* x_prev; float* pred_x0;                           // pred_x0 may be null
@@ -223,6 +234,8 @@ hipError_t launch_layernorm(const void* x, int in_is_f32, const float* gamma, co
 hipError_t launch_flash_d32(const FlashParams& p, int heads, int batch, hipStream_t st);
 hipError_t launch_small_attention(const SmallAttnParams& p, int D, int heads, int batch, hipStream_t st);
 hipError_t launch_causal_d64(const CausalD64Params& p, int heads, int batch, hipStream_t st);
+bool vq_attn_stream_supported(int C);                     // C % 128 == 0, C <= 512
+hipError_t launch_vq_attn_stream(const VqAttnParams& p, int batch, hipStream_t st);
 size_t small_attention_bwd_scratch_bytes(int B, int heads, int nq, int nkv);
 hipError_t launch_small_attention_bwd(const bf16_t* q, int ldq, const bf16_t* k, const bf16_t* v, int ldkv, const bf16_t* dout, int ldo, int B, int nq, int nkv,
                                       int heads, float scale, bf16_t* dq, bf16_t* dk, bf16_t* dv, char* scratch, hipStream_t st);    // backward.hip: d_head 32, nkv <= 32

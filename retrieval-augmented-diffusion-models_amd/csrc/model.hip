@@ -802,6 +802,15 @@ struct Ops {
         check(launch_causal_d64(f, heads, B, c->stream), "causal attention");
         prof_end();
     }
+    // the first stage's AttnBlock without its n x n scores (vq_attn.hip): one head of C channels over n tokens, any n
+    void vq_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, const float* bias_v, bf16_t* out, int ldo, int B, int n, int C,
+                      float scale) {
+        if (plan) return;
+        VqAttnParams f{}; f.q = q; f.ldq = ldq; f.k = k; f.ldk = ldk; f.v = v; f.ldv = ldv; f.bias = bias_v; f.out = out; f.ldo = ldo; f.n = n; f.C = C; f.scale = scale;
+        prof_begin(RDM_PROF_ATTENTION, 6.0 * B * (double)n * n * C, B, n, C);      // the scores twice (vq_attn.hip) and P.V
+        check(launch_vq_attn_stream(f, B, c->stream), "vq attention");
+        prof_end();
+    }
     // attention over a few keys / short sequences (attention.hip): head dim D, nq queries and nkv keys per sample
     void small_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, bf16_t* out, int ldo, int B, int nq, int nkv,
                          int heads, int D, int causal, float scale, const char* what) {
@@ -1259,14 +1268,33 @@ static bf16_t* vq_res(Ops& o, const VqRes& r, bf16_t* x, int B, int H, int W) {
     o.conv3(n2, nullptr, r.cout, 0, o.w<bf16_t>(r.w2), o.w<float>(r.b2), B, H, W, r.cout, 1, 0, nullptr, 0, rs, out);
     return out;
 }
+// An AttnBlock over more than VQ_ATTN_STREAM_N tokens runs on the streaming kernel (vq_attn.hip) when that kernel takes its width; up to there
+// -- the shipped 64 x 64 decode, VQGAN-f16's 256 tokens, the padded small sizes -- and at every other width it materialises its scores.
+constexpr int VQ_ATTN_STREAM_N = 4096;
+static bool vq_attn_streams(long long n, int C) { return n > VQ_ATTN_STREAM_N && vq_attn_stream_supported(C); }
 // ldm / taming AttnBlock: single head over H*W tokens, scale C^-1/2
 static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) {
     const int C = a.c, n = H * W, M = B * n;
+    if (vq_attn_streams(n, C)) {
+        // beyond VQ_ATTN_STREAM_N tokens: token-major q, k, v (b_v after P.V, as below) and the two-sweep kernel of vq_attn.hip -- the chain's
+        // arithmetic with no scores, no probabilities and no padded copies in memory, at any n
+        bf16_t* hn = o.abf((size_t)M * C);
+        o.groupnorm(x, nullptr, C, 0, B, n, o.w<float>(a.ng), o.w<float>(a.nb), 1e-6f, 0, hn);
+        bf16_t* q = o.abf((size_t)M * C); bf16_t* kk = o.abf((size_t)M * C); bf16_t* v = o.abf((size_t)M * C);
+        o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wq), o.w<float>(a.bq), M, C, ACT_NONE, nullptr, q);
+        o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wk), o.w<float>(a.bk), M, C, ACT_NONE, nullptr, kk);
+        o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wv), nullptr, M, C, ACT_NONE, nullptr, v);
+        bf16_t* ao = o.abf((size_t)M * C);
+        o.vq_attention(q, C, kk, C, v, C, o.w<float>(a.bv), ao, C, B, n, C, 1.0f / sqrtf((float)C));
+        bf16_t* out = o.abf((size_t)M * C);
+        o.linear(ao, nullptr, C, 0, o.w<bf16_t>(a.wo), o.w<float>(a.bo), M, C, ACT_NONE, x, out);
+        return out;
+    }
     // The score and P.V GEMMs contract over tokens in 64-slices and write column pairs: a token count that is no multiple of 64 (a 5 x 7
     // latent) runs on np = n rounded up to 64 tokens per sample -- the normalised rows are copied into a zeroed [B][np][C] image, the padding
     // KEYS get probability 0 in the softmax (n_valid), the padding QUERIES' rows are computed and never read -- and the real rows copied back.
     // A correctness fallback for small odd sizes, not a fast path: one memset, two strided copies and the padding queries' q / k / scores per
-    // AttnBlock on top of the materialised n x n matrix -- a size that matters (40 x 40 latents of the shipped decoder) wants its own kernel.
+    // AttnBlock on top of the materialised n x n matrix.
     const int np = (n + 63) & ~63, Mp = B * np;
     const bool padn = np != n;
     const size_t rowb = (size_t)n * C * 2, prowb = (size_t)np * C * 2;
@@ -1428,11 +1456,12 @@ static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, int H, 
 // batch may be walked in ranges; a range is sized so that the decoder's largest activation stays below 2^30 elements (2 GiB of bf16): the halo
 // convs address an operand through 32-bit offsets and leave bigger tensors to the generic implicit GEMM (RARM at 512 sequences per GPU: the
 // seven 128-channel convs of the 256 x 256 level on an 8.6 GB activation ran there at 0.30 of peak, 94 of the step's 933 ms).
-// An AttnBlock materialises its scores and probabilities, n^2 fp32 + n^2 bf16 per sample over the n pixels of its level: they are bounded in
-// BYTES, VQ_SCORE_BYTES per pass -- 8 GiB, which the shipped batch of 64 at the training size (n = 4096: 6.4 GB) stays under, so that size
-// is walked as it always was, while a 128 x 128 latent (n = 16384: 1.6 GB per image, which the activation count alone would have run 16 at a
-// time) goes 5 images per pass.  Returns 0 when ONE sample is beyond what the kernels index (an activation of 2^30 elements, a score matrix of
-// 2^31).  RDM_VQ_RANGE overrides the range (tests).
+// An AttnBlock of at most VQ_ATTN_STREAM_N pixels (or of a width the streaming kernel does not take) materialises its scores and probabilities,
+// n^2 fp32 + n^2 bf16 per sample over the n pixels of its level: they are bounded in BYTES, VQ_SCORE_BYTES per pass -- 8 GiB, which the shipped
+// batch of 64 at the training size (n = 4096: 6.4 GB) stays under, so that size is walked as it always was.  Larger levels stream (vq_attn.hip)
+// and count for nothing here: a 128 x 128 latent goes 16 images per pass, what the activation count allows.  Returns 0 when ONE sample is beyond
+// what the kernels index (an activation of 2^30 elements; a materialised score matrix of 2^31, which only a width outside the streaming kernel's
+// can still reach).  RDM_VQ_RANGE overrides the range (tests).
 constexpr long long VQ_SCORE_BYTES = 8LL << 30;
 template <typename M>
 static int vq_range(const M& m, int b, int h, int w) {
@@ -1449,7 +1478,7 @@ static int vq_range(const M& m, int b, int h, int w) {
         if (l >= 1 && 4 * e > per) per = 4 * e;
         const bool attn = !m.levels[l].attn.empty() || (l == top && m.mid.has_attn);
         const long long np = (px + 63) & ~63LL;
-        if (attn && np * np > score) score = np * np;
+        if (attn && !vq_attn_streams(px, c.ch * c.ch_mult[l]) && np * np > score) score = np * np;
     }
     if (per > (1LL << 30) || score >= (1LL << 31)) return 0;
     if (env > 0) return env < b ? env : b;
@@ -1462,7 +1491,7 @@ static int vq_range(const M& m, int b, int h, int w) {
 template <typename M, typename F>
 static int vq_walk(rdm_ctx* c, M& m, int b, int h, int w, bool in_ranges, F&& body) {
     const int nr = vq_range(m, b, h, w);
-    if (nr < 1) return c->fail(-1, "first stage: a %d x %d latent is beyond what one pass can index (largest activation 2^30 elements, attention over 46336 pixels)", h, w);
+    if (nr < 1) return c->fail(-1, "first stage: a %d x %d latent is beyond what one pass can index (largest activation of one sample 2^30 elements; an AttnBlock whose width is not a multiple of 128 up to 512 materialises its scores: 46336 pixels)", h, w);
     const int nb = in_ranges ? nr : b;
     RDM_TRY(ensure_gn_partial(c, nb));
     for (int b0 = 0; b0 < b; b0 += nb)
@@ -2951,6 +2980,21 @@ int rdm_op_causal_attention_d64(rdm_ctx* c, const void* qkv, int ldq, int B, int
         return c->fail(-1, "rdm_op_causal_attention_d64: kcache and vcache come together, with L >= n (L=%d, n=%d)", L, n);
     Ops o = op_exec(c);
     o.causal_d64((const bf16_t*)qkv, ldq, (bf16_t*)out, ldo, B, n, heads, scale, (bf16_t*)kcache, (bf16_t*)vcache, L);
+    return o.rc;
+}
+int rdm_op_vq_attention(rdm_ctx* c, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias_v, int B, int n, int C, float scale,
+                        void* out, int ldo) {
+    RDM_ENTER(c);
+    if (B < 1 || n < 1) return c->fail(-1, "rdm_op_vq_attention: bad shape B=%d n=%d (B >= 1, n >= 1)", B, n);
+    if (!q || !k || !v || !out) return c->fail(-1, "rdm_op_vq_attention: null argument");
+    if (!vq_attn_stream_supported(C)) return c->fail(-1, "rdm_op_vq_attention: C=%d must be a multiple of 128, at most 512", C);
+    if (ldq % 8 || ldq < C || ldk % 8 || ldk < C || ldv % 8 || ldv < C || ldo % 4 || ldo < C)
+        return c->fail(-1, "rdm_op_vq_attention: bad row pitch (ldq=%d, ldk=%d, ldv=%d: multiples of 8; ldo=%d: a multiple of 4; each at least C=%d)", ldq, ldk, ldv, ldo, C);
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (uintptr_t)out % 8)
+        return c->fail(-1, "rdm_op_vq_attention: q, k and v must be 16-byte aligned, out 8-byte aligned");
+    if ((long long)B * ((n + 63) / 64) > 0x7fffffffLL) return c->fail(-1, "rdm_op_vq_attention: B=%d x n=%d is more than one launch takes", B, n);
+    Ops o = op_exec(c);
+    o.vq_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, bias_v, (bf16_t*)out, ldo, B, n, C, scale);
     return o.rc;
 }
 int rdm_op_rarm_nll(rdm_ctx* c, const float* logits, long long rows, int vocab, const int64_t* targets, float* nll_out) {
