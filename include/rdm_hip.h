@@ -499,6 +499,46 @@ int rdm_op_xattn_fused_ln3(rdm_ctx* ctx, void* x_bf16_inout, const float* ln_gam
  * bf16: rows 0..n-1 receive the K / V columns of qkv bit for bit (the decode step's cache layout), rows >= n are not touched. */
 int rdm_op_causal_attention_d64(rdm_ctx* ctx, const void* qkv_bf16, int ldq, int B, int n, int heads, float scale, void* out_bf16, int ldo,
                                 void* kcache_bf16_or_null, void* vcache_bf16_or_null, int L);
+/* ---- the RARM decode step's kernels, one at a time (rarm_step of rdm_rarm_forward / rdm_rarm_sample: one row per sequence)
+ * Which kernel a one-row-per-sequence linear op runs, host only (no device call): kernel = one of RDM_LINEAR_ROWS_*; for the skinny kernel
+ * (sgemm.hip) also its instantiation: 16*ma rows x 16*nb weight rows per block, u k-steps of 32 per batch of loads, nw waves splitting K,
+ * ln = the LayerNorm formed in the kernel, geglu.  The library's own dispatch asks this same function. */
+enum { RDM_LINEAR_ROWS_REFUSED = 0, RDM_LINEAR_ROWS_SGEMM = 1, RDM_LINEAR_ROWS_MGEMM = 2, RDM_LINEAR_ROWS_TILED = 3 };
+typedef struct rdm_linear_rows_form { int kernel, ma, nb, u, nw, ln, geglu; } rdm_linear_rows_form;
+/* The kernel rdm_op_linear_rows launches for (M, N, K, act) with a LayerNorm operand (ln != 0) or a bf16 one, in fast (deterministic = 0) or
+ * deterministic mode.  RDM_LINEAR_ROWS_REFUSED: the LayerNorm form declines the shape (the executor then runs LayerNorm and the plain op). */
+int rdm_linear_rows_select(int M, int N, int K, int act, int ln, int deterministic, rdm_linear_rows_form* form_out);
+/* A linear op of the decode step, as the executor calls it (one row per sequence, in the context's current mode):
+ *   out[M, N (N/2: GEGLU)] = act(A W^T + bias) (+ res_f32),  A = a_bf16 [M, K], or LayerNorm(ln_x_f32 [M, K]; gamma, beta, eps 1e-5) formed in
+ * the kernel (exactly one of a_bf16 / ln_x_f32; the LayerNorm form: K = 768, bf16 output only, no residual).  w bf16 [N, K] (GEGLU: rows in
+ * the packed order of the model blob), bias f32 [N] or NULL, res_f32 [M, N] or NULL, out_bf16 and / or out_f32; out_f32 == res_f32 is allowed
+ * (the residual stream updated in place).  Where the LayerNorm form declines the shape the call fails with -5: it does not fall back. */
+int rdm_op_linear_rows(rdm_ctx* ctx, const void* a_bf16_or_null, const float* ln_x_f32_or_null, const float* ln_gamma, const float* ln_beta,
+                       const void* w_bf16, const float* bias_or_null, const float* res_f32_or_null, void* out_bf16_or_null, float* out_f32_or_null,
+                       int M, int N, int K, int act);
+/* The decode step's attention over a K/V cache at d_head 64 (rarm.hip): q bf16 [batch rows at stride ldq], head h in columns h*64..h*64+63;
+ * cache element (b, j, h, d) at b*batch_stride + j*row_stride + h*head_stride + d (head_stride 0 = 64: the heads side by side in a row).
+ * Self mode (k_new / v_new given, same stride ldq): the new rows are stored at cache row pos and rows 0..pos are attended (0 <= pos < nkv =
+ * the cache's capacity <= 1024).  Cross mode (k_new = v_new = NULL): rows 0..nkv-1 are attended; pos = -1, or >= 0 to hold the call to the
+ * block-per-(head, sequence) kernel (otherwise 1..8 keys at batch >= 128 take the few-key kernel).  out bf16 [batch rows at stride ldo].
+ * Strides are multiples of 8 elements, pointers 16-byte aligned. */
+int rdm_op_rarm_decode_attention(rdm_ctx* ctx, const void* q_bf16, int ldq, const void* k_new_bf16_or_null, const void* v_new_bf16_or_null,
+                                 void* kcache_bf16, void* vcache_bf16, long long batch_stride, int row_stride, long long head_stride, int nkv, int pos,
+                                 float scale, void* out_bf16, int ldo, int heads, int batch);
+/* The decode step's cross-attention over k neighbours in one launch, on operands re-associated per sequence:
+ *   x[b] += softmax_per_head(LayerNorm(x[b]; ln) G[b]^T) UT[b] + bias  (b < Bc);   x[b] += bias  (Bc <= b < B2: zero neighbours)
+ * x f32 [B2, C] in place; G, UT bf16 [Bc][NP][C], row h*k + j for head h, neighbour j; the softmax runs over each head's k columns.
+ * ln3_gamma / ln3_beta / ln3_out (all or none): ln3_out bf16 [B2, C] = LayerNorm of the finished rows.  C % 8 == 0, C <= 1024,
+ * heads * k <= min(128, NP). */
+int rdm_op_rarm_xattn_decode(rdm_ctx* ctx, float* x_f32_inout, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G_bf16,
+                             const void* UT_bf16, const float* bias, int B2, int Bc, int C, int NP, int heads, int k, const float* ln3_gamma_or_null,
+                             const float* ln3_beta_or_null, void* ln3_out_bf16_or_null);
+/* Token embedding + positional encoding into the fp32 residual stream: x[r] = emb[token(r)] + pos_t[position(r)], emb f32 [vocab, C], pos_t
+ * f32 [L, C]; a token id outside [0, vocab) reads row 0.  pos >= 0: the decode step (t = 1): token(r) = tokens[r], position pos < L.
+ * pos = -1: the whole-sequence pass: row r is position r % t (t <= L) of sequence r / t, token(r) = tokens[((seq0 + r / t) % tok_rows) *
+ * tok_ld + r % t], tokens int64 [tok_rows, tok_ld >= t]. */
+int rdm_op_rarm_embed(rdm_ctx* ctx, const int64_t* tokens, int tok_ld, int tok_rows, int seq0, const float* emb_f32, const float* pos_t_f32,
+                      float* x_f32, long long rows, int t, int C, int vocab, int L, int pos);
 /* The first stage's AttnBlock without its n x n scores (ldm/modules/diffusionmodules/model.py AttnBlock.forward: q k^T * C^-1/2 -> softmax ->
  * . v over the h*w pixels, one head of C channels; what rdm_vq_decode_hw / rdm_vq_encode_hw run beyond 4096 pixels):
  *   out[b] = softmax(q[b] k[b]^T * scale) v[b] + bias_v

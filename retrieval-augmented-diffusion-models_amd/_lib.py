@@ -41,6 +41,13 @@ class RarmSampleArgs(C.Structure):
                 ("top_k", C.c_int), ("guidance_scale", C.c_float)]
 
 
+class LinearRowsForm(C.Structure):
+    _fields_ = [("kernel", C.c_int), ("ma", C.c_int), ("nb", C.c_int), ("u", C.c_int), ("nw", C.c_int), ("ln", C.c_int), ("geglu", C.c_int)]
+
+
+LINEAR_ROWS_REFUSED, LINEAR_ROWS_SGEMM, LINEAR_ROWS_MGEMM, LINEAR_ROWS_TILED = range(4)
+
+
 class ClipCfg(C.Structure):
     _fields_ = [("embed_dim", C.c_int), ("image_resolution", C.c_int), ("vision_layers", C.c_int),
                 ("vision_width", C.c_int), ("vision_patch_size", C.c_int), ("context_length", C.c_int),
@@ -185,6 +192,12 @@ SIGNATURES = {
     "rdm_op_xattn_fused": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_causal_attention_d64": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int, _P, _P, C.c_int]),
     "rdm_op_rarm_nll": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
+    "rdm_linear_rows_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LinearRowsForm)]),
+    "rdm_op_linear_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rdm_op_rarm_decode_attention": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_float, _P,
+                                               C.c_int, C.c_int, C.c_int]),
+    "rdm_op_rarm_xattn_decode": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
+    "rdm_op_rarm_embed": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P, _P, _P, C.c_longlong, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_vq_attention": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int]),
     "rdm_op_causal_attention_d64_bwd": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, C.c_int]),
     "rdm_op_rarm_nll_bwd": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, C.c_float, _P, _P]),
@@ -210,6 +223,18 @@ def load_library(path: str = LIB_PATH):
 
 
 lib = load_library()
+
+
+def linear_rows_select(M, N, K, act=ACT_NONE, ln=False, deterministic=False):
+    """The kernel Context.op_linear_rows launches for this shape (host only, no device): a tuple ("sgemm", MA, NB, U, NW, LN, GEGLU) with
+    the skinny kernel's instantiation, ("mgemm",), ("tiled",), or ("refused",) where the LayerNorm-in-kernel form declines the shape."""
+    f = LinearRowsForm()
+    rc = lib.rdm_linear_rows_select(int(M), int(N), int(K), int(act), int(bool(ln)), int(bool(deterministic)), C.byref(f))
+    if rc != 0:
+        raise RdmError(f"rdm_linear_rows_select({M}, {N}, {K}, act={act}, ln={ln}, deterministic={deterministic}) failed ({rc})")
+    if f.kernel == LINEAR_ROWS_SGEMM:
+        return ("sgemm", f.ma, f.nb, f.u, f.nw, bool(f.ln), bool(f.geglu))
+    return (("refused", "sgemm", "mgemm", "tiled")[f.kernel],)
 
 
 def _ptr(t):
@@ -1249,6 +1274,122 @@ class Context:
         opt = lambda t: _ptr(t) if t is not None else None
         self._check(lib.rdm_op_causal_attention_d64(self._h, _ptr(qkv), C3, B, n, heads, float(scale), _ptr(out), heads * 64, opt(kcache), opt(vcache), L))
         return out
+
+    # ---- the RARM decode step's kernels one at a time
+    def op_linear_rows(self, w, a=None, ln=None, bias=None, res_f32=None, out_bf16=None, out_f32=None, act=ACT_NONE, rows=None):
+        """A linear op as the decode step calls it (one row per sequence, the context's current mode): act(A w^T + bias) (+ res_f32) with A =
+        a (bf16 [M,K]) or LayerNorm(x; gamma, beta) for ln = (x f32 [M,K], gamma, beta).  out_bf16 / out_f32: tensors of at least `rows`
+        rows to write into (out_f32 may BE res_f32: in place); neither given: a bf16 output is made.  -> (out_bf16, out_f32)."""
+        if (a is None) == (ln is None):
+            raise RdmError("op_linear_rows: exactly one of a (bf16 rows) and ln = (x, gamma, beta) required")
+        src = a if a is not None else ln[0]
+        M = src.shape[0] if rows is None else int(rows)
+        K, N = src.shape[1], w.shape[0]
+        No = N // 2 if act == ACT_GEGLU else N
+        if tuple(w.shape) != (N, K) or w.dtype != torch.bfloat16 or src.dtype != (torch.bfloat16 if a is not None else torch.float32) or M < 1 or M > src.shape[0]:
+            raise RdmError(f"op_linear_rows: operand [M >= {M},{K}] ({'bf16' if a is not None else 'f32'}) and w bf16 [{N},{K}] required, got {tuple(src.shape)} {src.dtype} / {tuple(w.shape)} {w.dtype}")
+        if ln is not None:
+            if res_f32 is not None or out_f32 is not None:
+                raise RdmError("op_linear_rows: the LayerNorm form writes bf16 and takes no residual")
+            if any(tuple(t.shape) != (K,) or t.dtype != torch.float32 for t in ln[1:]):
+                raise RdmError(f"op_linear_rows: gamma and beta must be f32 [{K}]")
+        if out_bf16 is None and out_f32 is None:
+            out_bf16 = torch.empty((M, No), device=self.device, dtype=torch.bfloat16)
+        for name, t, dt in (("out_bf16", out_bf16, torch.bfloat16), ("out_f32", out_f32, torch.float32), ("res_f32", res_f32, torch.float32)):
+            if t is not None and (t.ndim != 2 or t.shape[0] < M or t.shape[1] != No or t.dtype != dt or not t.is_contiguous()):
+                raise RdmError(f"op_linear_rows: {name} must be a contiguous {dt} [rows >= {M},{No}], got {tuple(t.shape)} {t.dtype}")
+        if bias is not None and (tuple(bias.shape) != (N,) or bias.dtype != torch.float32):
+            raise RdmError(f"op_linear_rows: bias must be f32 [{N}]")
+        g, b = (ln[1], ln[2]) if ln is not None else (None, None)
+        self._check(lib.rdm_op_linear_rows(self._h, _ptr(a), _ptr(ln[0]) if ln is not None else None, _ptr(g), _ptr(b), _ptr(w), _ptr(bias), _ptr(res_f32),
+                                           _ptr(out_bf16), _ptr(out_f32), M, N, K, int(act)))
+        return out_bf16, out_f32
+
+    def op_rarm_decode_attention(self, q, kcache, vcache, heads, scale, pos=-1, k_new=None, v_new=None, nkv=None, out=None):
+        """The decode step's attention at d_head 64 over a K/V cache.  q (and k_new / v_new) bf16 [B, heads*64] rows at one row stride (columns of
+        a fused q | k | v projection are fine).  Caches bf16: [B, heads, L, 64] (head-major, the self-attention cache) or [B, rows, ld] views with
+        the heads side by side in a row (the projected neighbours).  With k_new / v_new: they are stored at cache row pos and rows 0..pos
+        attended; without: rows 0..nkv-1 (default: all of the cache's).  -> bf16 [B, heads*64]."""
+        B, Cc = q.shape
+        if Cc != heads * 64 or q.dtype != torch.bfloat16 or q.stride(1) != 1:
+            raise RdmError(f"op_rarm_decode_attention: q must be bf16 [B,{heads * 64}] rows, got {tuple(q.shape)} {q.dtype}")
+        if (k_new is None) != (v_new is None):
+            raise RdmError("op_rarm_decode_attention: k_new and v_new come together")
+        for t in (k_new, v_new):
+            if t is not None and (tuple(t.shape) != (B, Cc) or t.dtype != torch.bfloat16 or t.stride(1) != 1 or t.stride(0) != q.stride(0)):
+                raise RdmError(f"op_rarm_decode_attention: k_new / v_new must be bf16 [{B},{Cc}] rows at q's row stride")
+        if kcache.shape != vcache.shape or kcache.stride() != vcache.stride() or kcache.dtype != torch.bfloat16 or vcache.dtype != torch.bfloat16 or kcache.ndim not in (3, 4):
+            raise RdmError(f"op_rarm_decode_attention: caches must be two bf16 tensors of one shape, [B,heads,L,64] or [B,rows,ld], got {tuple(kcache.shape)} / {tuple(vcache.shape)}")
+        if kcache.ndim == 4:
+            if tuple(kcache.shape) != (B, heads, kcache.shape[2], 64) or not kcache.is_contiguous():
+                raise RdmError(f"op_rarm_decode_attention: a head-major cache must be contiguous [{B},{heads},L,64], got {tuple(kcache.shape)}")
+            cap, bs, rs, hs = kcache.shape[2], heads * kcache.shape[2] * 64, 64, kcache.shape[2] * 64
+        else:
+            if kcache.shape[0] != B or kcache.shape[2] != Cc or kcache.stride(2) != 1:
+                raise RdmError(f"op_rarm_decode_attention: a row-major cache must be [{B},rows,{Cc}] rows, got {tuple(kcache.shape)}")
+            cap, bs, rs, hs = kcache.shape[1], kcache.stride(0), kcache.stride(1), 0
+        n = cap if nkv is None else int(nkv)
+        if n < 1 or n > cap or n > 1024:
+            raise RdmError(f"op_rarm_decode_attention: 1 <= nkv <= min(1024, the cache's {cap} rows) required, got {n}")
+        pos = int(pos)
+        if k_new is not None and not 0 <= pos < n:
+            raise RdmError(f"op_rarm_decode_attention: 0 <= pos < {n} required with k_new / v_new, got {pos}")
+        if k_new is None and pos < -1:
+            raise RdmError(f"op_rarm_decode_attention: pos must be -1 (none) or a position, got {pos}")
+        if out is None:
+            out = torch.empty((B, Cc), device=self.device, dtype=torch.bfloat16)
+        if tuple(out.shape) != (B, Cc) or out.dtype != torch.bfloat16 or not out.is_contiguous():
+            raise RdmError(f"op_rarm_decode_attention: out must be a contiguous bf16 [{B},{Cc}]")
+        raw = lambda t: None if t is None else C.c_void_p(t.data_ptr())
+        self._check(lib.rdm_op_rarm_decode_attention(self._h, raw(q), q.stride(0), raw(k_new), raw(v_new), raw(kcache), raw(vcache), bs, rs, hs, n, pos,
+                                                     float(scale), raw(out), Cc, heads, B))
+        return out
+
+    def op_rarm_xattn_decode(self, x, ln, G, UT, bias, heads, k, ln3=None, eps=1e-5):
+        """The decode step's one-launch cross-attention, IN PLACE on x f32 [B2,C]: rows b < Bc get softmax_per_head(LayerNorm(x[b]; ln) G[b]^T) UT[b]
+        + bias added, the others bias.  ln = (gamma, beta); G, UT bf16 [Bc,NP,C] (row h*k + j: head h, neighbour j); ln3 = (gamma, beta):
+        -> bf16 [B2,C], LayerNorm of the finished rows (else None)."""
+        if x.ndim != 2 or x.dtype != torch.float32 or not x.is_contiguous():
+            raise RdmError(f"op_rarm_xattn_decode: x must be a contiguous f32 [B2,C], got {tuple(x.shape)} {x.dtype}")
+        B2, Cc = x.shape
+        if G.ndim != 3 or G.shape != UT.shape or G.shape[2] != Cc or G.dtype != torch.bfloat16 or UT.dtype != torch.bfloat16 or G.shape[0] > B2:
+            raise RdmError(f"op_rarm_xattn_decode: G and UT must be bf16 [Bc <= {B2},NP,{Cc}], got {tuple(G.shape)} / {tuple(UT.shape)}")
+        Bc, NP = G.shape[0], G.shape[1]
+        if Cc % 8 or Cc > 1024 or heads < 1 or k < 1 or heads * k > min(128, NP):
+            raise RdmError(f"op_rarm_xattn_decode: C a multiple of 8 up to 1024 and heads * k <= min(128, NP = {NP}) required, got C={Cc} heads={heads} k={k}")
+        vecs = [ln[0], ln[1], bias] + (list(ln3) if ln3 is not None else [])
+        if any(tuple(t.shape) != (Cc,) or t.dtype != torch.float32 for t in vecs):
+            raise RdmError(f"op_rarm_xattn_decode: gamma, beta and bias must be f32 [{Cc}]")
+        l3 = torch.empty((B2, Cc), device=self.device, dtype=torch.bfloat16) if ln3 is not None else None
+        self._check(lib.rdm_op_rarm_xattn_decode(self._h, _ptr(x), _ptr(ln[0]), _ptr(ln[1]), float(eps), _ptr(G), _ptr(UT), _ptr(bias), B2, Bc, Cc, NP, heads, k,
+                                                 _ptr(ln3[0]) if ln3 is not None else None, _ptr(ln3[1]) if ln3 is not None else None, _ptr(l3)))
+        return l3
+
+    def op_rarm_embed(self, tokens, emb, pos_t, pos=None, t=None, seq0=0, n_seq=None):
+        """Token embedding + positional encoding -> f32 rows.  emb f32 [vocab,C], pos_t f32 [L,C]; ids outside [0, vocab) read row 0.
+        pos given: the decode step, tokens int64 [B] -> [B,C] at position pos.  t given: the whole-sequence pass, tokens int64 [tok_rows,
+        tok_ld >= t] -> [n_seq*t,C], sequence s reading token row (seq0 + s) % tok_rows (n_seq defaults to tok_rows)."""
+        if (pos is None) == (t is None):
+            raise RdmError("op_rarm_embed: exactly one of pos (decode step) and t (whole sequences) required")
+        if emb.ndim != 2 or pos_t.ndim != 2 or emb.shape[1] != pos_t.shape[1] or emb.dtype != torch.float32 or pos_t.dtype != torch.float32 or tokens.dtype != torch.int64:
+            raise RdmError("op_rarm_embed: emb f32 [vocab,C], pos_t f32 [L,C] and int64 tokens required")
+        vocab, Cc = emb.shape
+        L = pos_t.shape[0]
+        if pos is not None:
+            if tokens.ndim != 1 or not 0 <= int(pos) < L:
+                raise RdmError(f"op_rarm_embed: tokens [B] and 0 <= pos < {L} required, got {tuple(tokens.shape)} / {pos}")
+            rows, tt, ld, tr, p = tokens.shape[0], 1, 1, tokens.shape[0], int(pos)
+        else:
+            if tokens.ndim != 2 or not 1 <= int(t) <= min(L, tokens.shape[1]) or seq0 < 0:
+                raise RdmError(f"op_rarm_embed: tokens [tok_rows, tok_ld >= t], 1 <= t <= {L} and seq0 >= 0 required, got {tuple(tokens.shape)} / t={t} seq0={seq0}")
+            tr, ld = tokens.shape
+            tt, p = int(t), -1
+            rows = (tr if n_seq is None else int(n_seq)) * tt
+        if rows < 1:
+            raise RdmError("op_rarm_embed: no rows")
+        x = torch.empty((rows, Cc), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_op_rarm_embed(self._h, _ptr(tokens), ld, tr, int(seq0), _ptr(emb), _ptr(pos_t), _ptr(x), rows, tt, Cc, vocab, L, p))
+        return x
 
     def op_vq_attention(self, q, k, v, bias_v=None, scale=None):
         """The first stage's AttnBlock attention without its n x n scores: softmax(q k^T scale) v + bias_v over one head of C channels.

@@ -183,6 +183,10 @@ struct SgemmParams {
                               // (K / 4 per wave, partial tiles added in wave order), never the eight-wave / folded / LayerNorm-in-tile forms that start at 384 rows
 };
 bool sgemm_supported(const SgemmParams& p);
+// the sgemm_kernel<MA, NB, GEGLU, U, LN, NW> instantiation launch_sgemm runs for a supported p (host only: reads M, N, K, act, ln_x, fixed_split)
+struct SgemmForm { int ma, nb, u, nw, ln, geglu; };
+SgemmForm sgemm_form(const SgemmParams& p);
+bool sgemm_form_compiled(const SgemmForm& f);
 hipError_t launch_sgemm(const SgemmParams& p, hipStream_t st);
 // mid-size GEMM (mgemm.hip): one-row-per-sequence operands at 1024+ rows, LDS-staged BM x 64 tiles, fp32 / bf16 residual and output
 bool mgemm_supported(const SgemmParams& p);

@@ -556,6 +556,38 @@ static int ensure_bytes(rdm_ctx* c, char** p, size_t* have, size_t need) {
 // ------------------------------------------------------------------------------------ op helpers
 static int gn_chunks(int HW) { const int n = HW / 64; return n < 1 ? 1 : n > 32 ? 32 : n; }      // GroupNorm statistics: pixel chunks per sample
 
+// Which kernel takes a linear op that the skinny kernels may run (one bf16 operand, no row vector, alpha 1), and whether the LayerNorm-in-
+// kernel form takes a LayerNorm + projection: the ONE statement of both choices, shared by Ops::linear / Ops::linear_ln (every executor
+// and op entry) and by rdm_linear_rows_select, which reports it.  Host only: reads q's shape, activation and which pointers are set.
+static bool skinny_rows(bool deterministic, bool single_row, int M, int single_max) {
+    return deterministic ? single_row : (M <= 128 || (single_row && M <= single_max));
+}
+static int linear_kernel(SgemmParams& q, bool deterministic, bool single_row) {
+    // one-row-per-sample operands beyond these row counts take the tiled kernels
+    constexpr int SGEMM_MAX_ROWS = 4096;          // (2048 sequences: 716 -> 780 img/s against the tiled kernels, round 5)
+    // (round 5, same box: the GEGLU projection of the RARM decode step through the tiled kernel from ~200 rows on: 397.8 -> 409.5 img/s at 256
+    //  sequences, 487.0 -> 514.8 at 512; the plain projections through it: 221 / 305 -- their N = 768 gives the tiled kernel 16-24 tiles)
+    constexpr int SGEMM_GEGLU_MAX_ROWS = 192;
+    if (skinny_rows(deterministic, single_row, q.M, q.act == ACT_GEGLU ? SGEMM_GEGLU_MAX_ROWS : SGEMM_MAX_ROWS)) {
+        // 1536+ rows: LDS-staged 64 x 64 tiles (mgemm.hip) -- the skinny kernel's per-wave operand fetch is 75 MB through the L2 -> CU
+        // fabric for a [2048 x 768] x [768 x 768] product (33.6 us; 15.5 there).  Not in deterministic mode (the kernel choice would follow the batch).
+        static const int mg_from = rdm_env_int(getenv("RDM_MGEMM_FROM"), 1536);     // (tests move it)
+        if (!deterministic && single_row && mg_from > 0 && q.M >= mg_from && q.act != ACT_GEGLU && mgemm_supported(q)) return RDM_LINEAR_ROWS_MGEMM;
+        q.fixed_split = deterministic ? 1 : 0;
+        if (sgemm_supported(q)) return RDM_LINEAR_ROWS_SGEMM;
+    }
+    static const int mg_any = rdm_env_int(getenv("RDM_MGEMM_ANY"), 0);      // tests: operands of >= mg_any rows that are not single_row
+    if (!single_row && mg_any > 0 && q.M >= mg_any && q.act != ACT_GEGLU && mgemm_supported(q)) return RDM_LINEAR_ROWS_MGEMM;
+    return RDM_LINEAR_ROWS_TILED;
+}
+static bool linear_ln_takes(SgemmParams& q, bool deterministic, bool single_row) {
+    // (from ~200 rows on a separate LayerNorm pass + the 64 x 64-tile GEMM beats the LayerNorm-fused 32-row tiles: sgemm.hip)
+    constexpr int SGEMM_LN_MAX_ROWS = 192;
+    if (!deterministic && q.M > SGEMM_LN_MAX_ROWS) return false;
+    q.fixed_split = deterministic ? 1 : 0;
+    return skinny_rows(deterministic, single_row, q.M, 1024) && sgemm_supported(q);
+}
+
 // The kernel dispatch of the model executors and of the operator-level entries (rdm_op_*): which kernel runs an op, with which
 // parameters.  Weight and bias arguments are device pointers (executors: o.w<T>(offset) into the model blob).
 struct Ops {
@@ -586,7 +618,7 @@ struct Ops {
     // single_max rows.  Deterministic mode: exactly for the ops with ONE row per sample (`single_row`: time embedding, RARM decode step,
     // CLIP projection), at any batch (one-row-per-sample operands of bigger batches -- RARM decode at 128+ sequences per GPU -- keep the
     // skinny kernel: its row blocks scale with M, while the tiled kernels would run a dozen 256-row tiles)
-    bool skinny(int M, int single_max) const { return c->deterministic ? single_row : (M <= 128 || (single_row && M <= single_max)); }
+    bool skinny(int M, int single_max) const { return skinny_rows(c->deterministic, single_row, M, single_max); }
     // out[M,N] = act(A[M,K] W^T + bias) (+res)
     // a1_wrap_rows > 0: A1 holds that many rows only, row m reads m % a1_wrap_rows (lin4 only: callers check lin4_takes first)
     bool lin4_takes(int M, int N, int C0, int C1, int a1_wrap_rows, int res_wrap_rows = 0) {
@@ -602,36 +634,14 @@ struct Ops {
                 int act, const bf16_t* res, bf16_t* out, float* out_f32 = nullptr, const float* res_f32 = nullptr, int a1_wrap_rows = 0,
                 const float* rowvec = nullptr, int rowvec_ld = 0, int rv_rows = 1, int res_wrap_rows = 0, float alpha = 1.f) {
         if (plan) return;
-        // one-row-per-sample operands beyond these row counts take the tiled kernels
-        constexpr int SGEMM_MAX_ROWS = 4096;          // (2048 sequences: 716 -> 780 img/s against the tiled kernels, round 5)
-        // (round 5, same box: the GEGLU projection of the RARM decode step through the tiled kernel from ~200 rows on: 397.8 -> 409.5 img/s at 256
-        //  sequences, 487.0 -> 514.8 at 512; the plain projections through it: 221 / 305 -- their N = 768 gives the tiled kernel 16-24 tiles)
-        constexpr int SGEMM_GEGLU_MAX_ROWS = 192;
         if (!A1 && C1 == 0 && !rowvec && alpha == 1.f) {         // N/32 x ceil(M/32) blocks (sgemm.hip), 64 x 64 tiles (mgemm.hip)
             SgemmParams q{}; q.A = A0; q.lda = C0; q.W = W; q.M = M; q.N = N; q.K = C0; q.bias = bias;
             q.act = act; q.res_f32 = res_f32; q.res_bf16 = res; q.out_f32 = out_f32; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-            if (skinny(M, act == ACT_GEGLU ? SGEMM_GEGLU_MAX_ROWS : SGEMM_MAX_ROWS)) {
-                // 1536+ rows: LDS-staged 64 x 64 tiles (mgemm.hip) -- the skinny kernel's per-wave operand fetch is 75 MB through the L2 -> CU
-                // fabric for a [2048 x 768] x [768 x 768] product (33.6 us; 15.5 there).  Not in deterministic mode (the kernel choice would follow the batch).
-                static const int mg_from = rdm_env_int(getenv("RDM_MGEMM_FROM"), 1536);     // (tests move it)
-                if (!c->deterministic && single_row && mg_from > 0 && M >= mg_from && act != ACT_GEGLU && mgemm_supported(q)) {
-                    prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
-                    check(launch_mgemm(q, c->stream), "mid-size linear");
-                    prof_end();
-                    return;
-                }
-                q.fixed_split = c->deterministic ? 1 : 0;
-                if (sgemm_supported(q)) {
-                    prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
-                    check(launch_sgemm(q, c->stream), "skinny linear");
-                    prof_end();
-                    return;
-                }
-            }
-            static const int mg_any = rdm_env_int(getenv("RDM_MGEMM_ANY"), 0);      // tests: operands of >= mg_any rows that are not single_row
-            if (!single_row && mg_any > 0 && M >= mg_any && act != ACT_GEGLU && mgemm_supported(q)) {
+            const int kernel = linear_kernel(q, c->deterministic, single_row);
+            if (kernel != RDM_LINEAR_ROWS_TILED) {
+                const bool mid = kernel == RDM_LINEAR_ROWS_MGEMM;
                 prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
-                check(launch_mgemm(q, c->stream), "mid-size linear");
+                check(mid ? launch_mgemm(q, c->stream) : launch_sgemm(q, c->stream), mid ? "mid-size linear" : "skinny linear");
                 prof_end();
                 return;
             }
@@ -659,13 +669,9 @@ struct Ops {
     // out = act(LayerNorm(x) W^T + bias) with the LayerNorm formed inside the skinny GEMM (sgemm.hip): decode-sized operands only.
     // false = not available for this shape (the caller runs layernorm + linear)
     bool linear_ln(const float* x, const float* g, const float* b, int C, const bf16_t* W, const float* bias, int M, int N, int act, bf16_t* out) {
-        // (from ~200 rows on a separate LayerNorm pass + the 64 x 64-tile GEMM beats the LayerNorm-fused 32-row tiles: sgemm.hip)
-        constexpr int SGEMM_LN_MAX_ROWS = 192;
-        if (!c->deterministic && M > SGEMM_LN_MAX_ROWS) return false;
         SgemmParams q{}; q.ln_x = x; q.ln_g = g; q.ln_b = b; q.ln_eps = 1e-5f; q.W = W; q.M = M; q.N = N; q.K = C;
         q.bias = bias; q.act = act; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-        q.fixed_split = c->deterministic ? 1 : 0;
-        if (!skinny(M, 1024) || !sgemm_supported(q)) return false;
+        if (!linear_ln_takes(q, c->deterministic, single_row)) return false;
         if (plan) return true;
         prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C, M, N, C);
         check(launch_sgemm(q, c->stream), "skinny linear on a LayerNorm");
@@ -2981,6 +2987,97 @@ int rdm_op_causal_attention_d64(rdm_ctx* c, const void* qkv, int ldq, int B, int
     Ops o = op_exec(c);
     o.causal_d64((const bf16_t*)qkv, ldq, (bf16_t*)out, ldo, B, n, heads, scale, (bf16_t*)kcache, (bf16_t*)vcache, L);
     return o.rc;
+}
+// ---- the decode step's kernels one at a time (tests/test_gpu_decode_ops.py): argument checks, then the launch rarm_step makes
+int rdm_linear_rows_select(int M, int N, int K, int act, int ln, int deterministic, rdm_linear_rows_form* out) {
+    if (!out || M < 1 || N < 1 || K < 1 || act < ACT_NONE || act > ACT_SILU) return -1;
+    *out = rdm_linear_rows_form{};
+    static const float some = 0.f;                        // the choice reads which operands are given, never their values
+    SgemmParams q{}; q.M = M; q.N = N; q.K = K; q.lda = K; q.act = act; q.ldo = act == ACT_GEGLU ? N / 2 : N;
+    if (ln) { q.ln_x = &some; q.ln_g = &some; q.ln_b = &some; q.ln_eps = 1e-5f; }
+    out->kernel = ln ? (linear_ln_takes(q, deterministic != 0, true) ? RDM_LINEAR_ROWS_SGEMM : RDM_LINEAR_ROWS_REFUSED) : linear_kernel(q, deterministic != 0, true);
+    if (out->kernel == RDM_LINEAR_ROWS_SGEMM) {
+        const SgemmForm f = sgemm_form(q);
+        if (!sgemm_form_compiled(f)) return -3;
+        out->ma = f.ma; out->nb = f.nb; out->u = f.u; out->nw = f.nw; out->ln = f.ln; out->geglu = f.geglu;
+    }
+    return 0;
+}
+int rdm_op_linear_rows(rdm_ctx* c, const void* a, const float* ln_x, const float* gamma, const float* beta, const void* w, const float* bias,
+                       const float* res_f32, void* out_bf16, float* out_f32, int M, int N, int K, int act) {
+    RDM_ENTER(c);
+    if (!w || (a != nullptr) == (ln_x != nullptr) || (!out_bf16 && !out_f32)) return c->fail(-1, "rdm_op_linear_rows: w, exactly one of a / ln_x and an output required");
+    if (M < 1 || N < 1 || K < 8 || K % 8 || act < ACT_NONE || act > ACT_SILU || (act == ACT_GEGLU && N % 2))
+        return c->fail(-1, "rdm_op_linear_rows: bad shape M=%d N=%d K=%d act=%d (K a multiple of 8; GEGLU: N even)", M, N, K, act);
+    Ops o = op_exec(c);
+    o.single_row = true;
+    if (ln_x) {
+        if (!gamma || !beta || !out_bf16 || out_f32 || res_f32) return c->fail(-1, "rdm_op_linear_rows: the LayerNorm form takes gamma, beta and a bf16 output, no residual");
+        if (!o.linear_ln(ln_x, gamma, beta, K, (const bf16_t*)w, bias, M, N, act, (bf16_t*)out_bf16))
+            return c->fail(-5, "rdm_op_linear_rows: shape not taken by the LayerNorm-in-kernel form (M=%d N=%d K=%d act=%d, %s mode)", M, N, K, act,
+                           c->deterministic ? "deterministic" : "fast");
+        return o.rc;
+    }
+    o.linear((const bf16_t*)a, nullptr, K, 0, (const bf16_t*)w, bias, M, N, act, nullptr, (bf16_t*)out_bf16, out_f32, res_f32);
+    return o.rc;
+}
+static int op_pos_slot(rdm_ctx* c, int pos, int** slot) {      // the device step counter of the decode kernels, set on the stream
+    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, 64));
+    *slot = (int*)c->samp;
+    RDM_CHECK_HIP(c, launch_set_int(*slot, pos, c->stream));
+    return 0;
+}
+int rdm_op_rarm_decode_attention(rdm_ctx* c, const void* q, int ldq, const void* k_new, const void* v_new, void* kcache, void* vcache, long long batch_stride,
+                                 int row_stride, long long head_stride, int nkv, int pos, float scale, void* out, int ldo, int heads, int batch) {
+    RDM_ENTER(c);
+    if (!q || !kcache || !vcache || !out) return c->fail(-1, "rdm_op_rarm_decode_attention: null argument");
+    if ((k_new != nullptr) != (v_new != nullptr)) return c->fail(-1, "rdm_op_rarm_decode_attention: k_new and v_new come together");
+    if (heads < 1 || batch < 1 || batch > 65535 || nkv < 1 || nkv > 1024)
+        return c->fail(-1, "rdm_op_rarm_decode_attention: bad shape heads=%d batch=%d nkv=%d (1 <= nkv <= 1024, batch <= 65535)", heads, batch, nkv);
+    if (k_new ? (pos < 0 || pos >= nkv) : pos < -1)
+        return c->fail(-1, "rdm_op_rarm_decode_attention: pos=%d: 0 <= pos < nkv=%d with k_new / v_new, -1 or more without", pos, nkv);
+    if (ldq % 8 || ldq < heads * 64 || ldo % 8 || ldo < heads * 64 || row_stride % 8 || row_stride < 64 || batch_stride % 8 || head_stride % 8 || head_stride < 0)
+        return c->fail(-1, "rdm_op_rarm_decode_attention: bad stride (ldq=%d, ldo=%d: multiples of 8, at least %d; row_stride=%d, batch_stride=%lld, head_stride=%lld: multiples of 8)",
+                       ldq, ldo, heads * 64, row_stride, batch_stride, head_stride);
+    if (((uintptr_t)q | (uintptr_t)k_new | (uintptr_t)v_new | (uintptr_t)kcache | (uintptr_t)vcache | (uintptr_t)out) % 16)
+        return c->fail(-1, "rdm_op_rarm_decode_attention: pointers must be 16-byte aligned");
+    RarmAttnParams p{}; p.q = (const bf16_t*)q; p.ldq = ldq; p.k_new = (const bf16_t*)k_new; p.v_new = (const bf16_t*)v_new;
+    p.Kc = (bf16_t*)kcache; p.Vc = (bf16_t*)vcache; p.batch_stride = batch_stride; p.row_stride = row_stride; p.head_stride = head_stride;
+    p.nkv = nkv; p.scale = scale; p.out = (bf16_t*)out; p.ldo = ldo;
+    if (pos >= 0) { int* slot = nullptr; RDM_TRY(op_pos_slot(c, pos, &slot)); p.pos = slot; }
+    RDM_CHECK_HIP(c, launch_rarm_decode_attention(p, heads, batch, c->stream));
+    return 0;
+}
+int rdm_op_rarm_xattn_decode(rdm_ctx* c, float* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G, const void* UT, const float* bias,
+                             int B2, int Bc, int C, int NP, int heads, int k, const float* ln3_gamma, const float* ln3_beta, void* ln3_out) {
+    RDM_ENTER(c);
+    if (!x || !ln_gamma || !ln_beta || !bias || (Bc > 0 && (!G || !UT))) return c->fail(-1, "rdm_op_rarm_xattn_decode: null argument");
+    if ((ln3_gamma != nullptr) != (ln3_out != nullptr) || (ln3_beta != nullptr) != (ln3_out != nullptr))
+        return c->fail(-1, "rdm_op_rarm_xattn_decode: ln3_gamma, ln3_beta and ln3_out come together");
+    if (B2 < 1 || Bc < 0 || Bc > B2 || C < 8 || C % 8 || C > 1024 || heads < 1 || k < 1 || heads * k > 128 || heads * k > NP)
+        return c->fail(-1, "rdm_op_rarm_xattn_decode: bad shape B2=%d Bc=%d C=%d NP=%d heads=%d k=%d (Bc <= B2; C a multiple of 8 up to 1024; heads * k <= min(128, NP))",
+                       B2, Bc, C, NP, heads, k);
+    if (((uintptr_t)x | (uintptr_t)G | (uintptr_t)UT | (uintptr_t)bias) % 16) return c->fail(-1, "rdm_op_rarm_xattn_decode: x, G, UT and bias must be 16-byte aligned");
+    RarmXattnParams p{}; p.x = x; p.ln_g = ln_gamma; p.ln_b = ln_beta; p.ln_eps = ln_eps; p.G = (const bf16_t*)G; p.UT = (const bf16_t*)UT; p.bias = bias;
+    p.B2 = B2; p.Bc = Bc; p.C = C; p.NP = NP; p.heads = heads; p.k = k; p.ln3_g = ln3_gamma; p.ln3_b = ln3_beta; p.ln3_out = (bf16_t*)ln3_out;
+    RDM_CHECK_HIP(c, launch_rarm_xattn_decode(p, c->stream));
+    return 0;
+}
+int rdm_op_rarm_embed(rdm_ctx* c, const int64_t* tokens, int tok_ld, int tok_rows, int seq0, const float* emb, const float* pos_t, float* x, long long rows, int t,
+                      int C, int vocab, int L, int pos) {
+    RDM_ENTER(c);
+    if (!tokens || !emb || !pos_t || !x) return c->fail(-1, "rdm_op_rarm_embed: null argument");
+    if (rows < 1 || rows > 0x7fffffffLL || C < 1 || vocab < 1 || L < 1 || t < 1 || t > L || pos < -1 || pos >= L)
+        return c->fail(-1, "rdm_op_rarm_embed: bad shape rows=%lld t=%d C=%d vocab=%d L=%d pos=%d (1 <= t <= L, -1 <= pos < L)", rows, t, C, vocab, L, pos);
+    if (pos >= 0) {
+        if (t != 1) return c->fail(-1, "rdm_op_rarm_embed: the decode-step form (pos >= 0) is one row per sequence: t = 1, got %d", t);
+        int* slot = nullptr; RDM_TRY(op_pos_slot(c, pos, &slot));
+        RDM_CHECK_HIP(c, launch_rarm_embed((const long long*)tokens, emb, pos_t, slot, x, (int)rows, C, vocab, c->stream));
+        return 0;
+    }
+    if (tok_rows < 1 || tok_ld < t || seq0 < 0 || rows % t) return c->fail(-1, "rdm_op_rarm_embed: tok_rows >= 1, tok_ld >= t, seq0 >= 0 and whole sequences required (tok_rows=%d tok_ld=%d seq0=%d)", tok_rows, tok_ld, seq0);
+    RDM_CHECK_HIP(c, launch_rarm_embed_seq((const long long*)tokens, tok_ld, tok_rows, seq0, emb, pos_t, x, rows, t, C, vocab, c->stream));
+    return 0;
 }
 int rdm_op_vq_attention(rdm_ctx* c, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias_v, int B, int n, int C, float scale,
                         void* out, int ldo) {

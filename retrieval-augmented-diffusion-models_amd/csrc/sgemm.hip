@@ -291,8 +291,10 @@ static void pick_tile(const SgemmParams& p, int& ma, int& nb) {
     }
 }
 
+// The ONE statement of which instantiation takes a shape: (MA, NB, U, NW, LN) of sgemm_kernel, from (M, N, K, act, LayerNorm operand,
+// fixed_split) only.  launch_sgemm launches what it returns; rdm_linear_rows_select (model.hip) reports it.
 template <bool GEGLU>
-static hipError_t launch_nf(const SgemmParams& p, hipStream_t st) {
+static SgemmForm form_nf(const SgemmParams& p) {
     const bool deep = ((p.K >> 2) % 192) == 0;            // K quarter is a multiple of 6 k-steps of 32 (K = 768, 1536, 3072 ...)
     constexpr int N1 = GEGLU ? 2 : 1, N2 = GEGLU ? 4 : 2, N3 = GEGLU ? 8 : 4;
     int ma, nb;
@@ -302,47 +304,70 @@ static hipError_t launch_nf(const SgemmParams& p, hipStream_t st) {
         // 64 rows as fp32 (196 KB instead of 98 KB per block) and repeats the statistics; the two LayerNorm launches saved (10.8 us per
         // layer) come back as + 26 us of GEMM.  Removed.)
         pick_tile<GEGLU, true>(p, ma, nb);
-        if (ma == 1) return nb == N1 ? launch_one<1, N1, GEGLU, 6, true>(p, st) : launch_one<1, N2, GEGLU, 6, true>(p, st);
-        return nb == N1 ? launch_one<2, N1, GEGLU, 6, true>(p, st) : launch_one<2, N2, GEGLU, 6, true>(p, st);
+        return SgemmForm{ma == 1 ? 1 : 2, nb == N1 ? N1 : N2, 6, 4, 1, GEGLU};
     }
     if constexpr (!GEGLU) {
         // 64 x 96 outputs for wide projections at 384+ rows (q | k | v, N = 2304, at 512 rows: 8 x 24 = 192 blocks in ONE round of the 256 CUs;
         // as 64 x 64 tiles it is 288 blocks of 128 KB LDS each, one per CU: two rounds)
         if (!p.fixed_split && p.M >= 384 && p.N % 96 == 0 && p.N >= 1536 && p.K == 768) {
             const long long b64 = (long long)((p.M + 63) / 64) * (p.N / 64), b96 = (long long)((p.M + 63) / 64) * (p.N / 96);
-            if ((b64 + 255) / 256 > (b96 + 255) / 256) return launch_one<4, 6, false, 3, false, 8>(p, st);
+            if ((b64 + 255) / 256 > (b96 + 255) / 256) return SgemmForm{4, 6, 3, 8, 0, 0};
         }
     }
     pick_tile<GEGLU, false>(p, ma, nb);
     if (nb == N3) {       // 64 x 64 outputs: two (GEGLU) / three k-steps per batch of loads keep the operand registers under the budget
-        if constexpr (GEGLU) return launch_one<4, N3, true, 2>(p, st);
+        if constexpr (GEGLU) return SgemmForm{4, N3, 2, 4, 0, 1};
         else {
-            if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 96 == 0) return launch_one<4, N3, false, 3, false, 8>(p, st);      // eight waves: K / 8 in batches of three k-steps
-            return ((p.K >> 2) % 96) == 0 ? launch_one<4, N3, false, 3>(p, st) : launch_one<4, N3, false, 2>(p, st);
+            if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 96 == 0) return SgemmForm{4, N3, 3, 8, 0, 0};      // eight waves: K / 8 in batches of three k-steps
+            return SgemmForm{4, N3, ((p.K >> 2) % 96) == 0 ? 3 : 2, 4, 0, 0};
         }
     }
-    if (nb == N1) {
-        switch (ma) {
-            case 1: return deep ? launch_one<1, N1, GEGLU, 6>(p, st) : launch_one<1, N1, GEGLU, 2>(p, st);
-            case 2: return deep ? launch_one<2, N1, GEGLU, 6>(p, st) : launch_one<2, N1, GEGLU, 2>(p, st);
-            default: return deep ? launch_one<4, N1, GEGLU, 6>(p, st) : launch_one<4, N1, GEGLU, 2>(p, st);
-        }
+    const int a = ma == 1 ? 1 : ma == 2 ? 2 : 4, b = nb == N1 ? N1 : N2;
+    if (b == N2 && a == 4) {
+        if constexpr (!GEGLU) {
+            // deep K (3072: a wave's share is 12 k-steps): six per batch of loads = two dependent round trips instead of four
+            if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 192 == 0) return SgemmForm{4, N2, 6, 8, 0, 0};
+            if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 96 == 0) return SgemmForm{4, N2, 3, 8, 0, 0};
+        }      // (same box: 512 rows 511.6 -> 519.5 img/s, 256 rows 407.8 -> 404.3: from 384 rows on)
     }
-    switch (ma) {
-        case 1: return deep ? launch_one<1, N2, GEGLU, 6>(p, st) : launch_one<1, N2, GEGLU, 2>(p, st);
-        case 2: return deep ? launch_one<2, N2, GEGLU, 6>(p, st) : launch_one<2, N2, GEGLU, 2>(p, st);
-        default: {
-            if constexpr (!GEGLU) {
-                // deep K (3072: a wave's share is 12 k-steps): six per batch of loads = two dependent round trips instead of four
-                if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 192 == 0) return launch_one<4, N2, false, 6, false, 8>(p, st);
-                if (!p.fixed_split && p.M >= 384 && (p.K >> 3) % 96 == 0) return launch_one<4, N2, false, 3, false, 8>(p, st);
-            }      // (same box: 512 rows 511.6 -> 519.5 img/s, 256 rows 407.8 -> 404.3: from 384 rows on)
-            return deep ? launch_one<4, N2, GEGLU, 6>(p, st) : launch_one<4, N2, GEGLU, 2>(p, st);
-        }
+    return SgemmForm{a, b, deep ? 6 : 2, 4, 0, GEGLU};
+}
+
+SgemmForm sgemm_form(const SgemmParams& p) { return p.act == ACT_GEGLU ? form_nf<true>(p) : form_nf<false>(p); }
+
+// every compiled instantiation, as (MA, NB, GEGLU, U, LN, NW): a form outside this list is an error, never another kernel
+#define SGEMM_FORMS(X)                                                                                                                  \
+    X(1, 1, false, 6, true, 4) X(1, 2, false, 6, true, 4) X(2, 1, false, 6, true, 4) X(2, 2, false, 6, true, 4)                         \
+    X(1, 2, true, 6, true, 4) X(1, 4, true, 6, true, 4) X(2, 2, true, 6, true, 4) X(2, 4, true, 6, true, 4)                             \
+    X(4, 6, false, 3, false, 8) X(4, 4, false, 3, false, 8) X(4, 4, false, 3, false, 4) X(4, 4, false, 2, false, 4)                     \
+    X(4, 8, true, 2, false, 4) X(4, 2, false, 6, false, 8) X(4, 2, false, 3, false, 8)                                                  \
+    X(1, 1, false, 6, false, 4) X(1, 1, false, 2, false, 4) X(2, 1, false, 6, false, 4) X(2, 1, false, 2, false, 4)                     \
+    X(4, 1, false, 6, false, 4) X(4, 1, false, 2, false, 4) X(1, 2, false, 6, false, 4) X(1, 2, false, 2, false, 4)                     \
+    X(2, 2, false, 6, false, 4) X(2, 2, false, 2, false, 4) X(4, 2, false, 6, false, 4) X(4, 2, false, 2, false, 4)                     \
+    X(1, 2, true, 6, false, 4) X(1, 2, true, 2, false, 4) X(2, 2, true, 6, false, 4) X(2, 2, true, 2, false, 4)                         \
+    X(4, 2, true, 6, false, 4) X(4, 2, true, 2, false, 4) X(1, 4, true, 6, false, 4) X(1, 4, true, 2, false, 4)                         \
+    X(2, 4, true, 6, false, 4) X(2, 4, true, 2, false, 4) X(4, 4, true, 6, false, 4) X(4, 4, true, 2, false, 4)
+
+static constexpr int form_key(int ma, int nb, bool geglu, int u, bool ln, int nw) { return ma | nb << 4 | u << 8 | nw << 12 | (ln ? 1 : 0) << 16 | (geglu ? 1 : 0) << 17; }
+static int form_key(const SgemmForm& f) { return form_key(f.ma, f.nb, f.geglu != 0, f.u, f.ln != 0, f.nw); }
+
+bool sgemm_form_compiled(const SgemmForm& f) {
+    switch (form_key(f)) {
+#define X(MA_, NB_, G_, U_, LN_, NW_) case form_key(MA_, NB_, G_, U_, LN_, NW_):
+        SGEMM_FORMS(X)
+#undef X
+        return true;
     }
+    return false;
 }
 
 hipError_t launch_sgemm(const SgemmParams& p, hipStream_t st) {
     if (!sgemm_supported(p)) return hipErrorInvalidValue;
-    return p.act == ACT_GEGLU ? launch_nf<true>(p, st) : launch_nf<false>(p, st);
+    const SgemmForm f = sgemm_form(p);
+    switch (form_key(f)) {
+#define X(MA_, NB_, G_, U_, LN_, NW_) case form_key(MA_, NB_, G_, U_, LN_, NW_): return launch_one<MA_, NB_, G_, U_, LN_, NW_>(p, st);
+        SGEMM_FORMS(X)
+#undef X
+    }
+    return hipErrorInvalidValue;
 }
