@@ -94,6 +94,20 @@ typedef struct {
     int n_nodes; const int* nodes;      /* [host] strictly decreasing timesteps in [0, T-1]; the UNet runs at nodes[0 .. n_nodes-2] */
 } rdm_dpmpp_args;
 
+/* UniPC arguments (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models"): the
+ * multistep data-prediction predictor-corrector on an explicit list of integer timesteps. */
+typedef struct {
+    int batch, k, channels, height, width;
+    float unconditional_guidance_scale;   /* >= 1; > 1 enables CFG batch doubling */
+    int order;             /* 1 | 2 | 3: the predictor's order; the corrector adds one */
+    int variant;           /* 0 = bh1 (B(h) = -h) | 1 = bh2 (B(h) = expm1(-h)) */
+    int corrector;         /* 0: predictor only (order 2, bh2 is then DPM-Solver++(2M); order 1 is DDIM with eta 0) */
+    int lower_order_final; /* step s of n runs at order min(order, s, n + 1 - s) instead of min(order, s) */
+    int log_every_t;       /* intermediates rule of the DDIM loop over n_nodes - 1 steps */
+    int T; const float* alphas_cumprod; /* [host] the model's fp32 buffer [T] */
+    int n_nodes; const int* nodes;      /* [host] strictly decreasing timesteps in [0, T-1]; the UNet runs at nodes[0 .. n_nodes-2] */
+} rdm_unipc_args;
+
 /* ldm LatentDiffusion.p_sample_loop arguments (reached from rdm/models/diffusion/ddpm.py:1008). */
 typedef struct {
     int timesteps;         /* loop runs reversed(range(timesteps)) */
@@ -182,6 +196,27 @@ int rdm_dpmpp_sample(rdm_ctx* ctx, const rdm_dpmpp_args* args, const float* x_T,
  * collide.  nodes_out holds S + 1 entries (time_uniform with an S that does not divide T: ceil(T / (T / S)) + 1); returns the number of
  * nodes written, or a negative value for bad arguments. */
 int rdm_dpmpp_timesteps(const float* alphas_cumprod, int T, int S, int skip_type, int* nodes_out);
+/* UniPC (Zhao et al. 2023), multistep data prediction on integer timesteps; node quantities alpha_i, sigma_i, lambda_i as in
+ * rdm_dpmpp_sample, n = n_nodes - 1 steps and n forwards at nodes[0 .. n-1].  u_j is the UNet input at node j (u_0 = x_0 = x_T),
+ * m_j = (u_j - sigma_j eps_j) / alpha_j with the guided eps at (u_j, nodes[j]).  Step s (1-based, ending at node s) has order
+ * p = min(order, s), with lower_order_final also at most n + 1 - s.  h = lambda_s - lambda_{s-1}, hh = -h, phi_1 = expm1(hh), B = hh (bh1) or
+ * expm1(hh) (bh2); r_i = (lambda_{s-1-i} - lambda_{s-1}) / h for i < p, r_p = 1; g_1 = phi_1 / hh - 1, g_{i+1} = g_i / hh - 1 / (i+1)!,
+ * b_i = g_i i! / B; R_{i,k} = r_k^{i-1}.  Predictor weights (p - 1 values): none, [1/2], or the solution of R[1..2,1..2] rho = b[1..2];
+ * corrector weights (p values): [1/2] for p = 1, else the solution of R rho = b.  With D_i = (m_{s-1-i} - m_{s-1}) / r_i and
+ * base = (sigma_s / sigma_{s-1}) x_{s-1} - alpha_s phi_1 m_{s-1}:  u_s = base - alpha_s B sum_{i<p} rho^p_i D_i, and, m_s being the forward at u_s,
+ * x_s = base - alpha_s B (sum_{i<p} rho^c_i D_i + rho^c_p (m_s - m_{s-1})).  Corrector off: x_s = u_s.  The last node is not corrected; the
+ * result is u_n.  One forward and one fused kernel pass per step: the pass after forward j corrects x_j and predicts u_{j+1}.
+ * x_inter holds u_{j+1}, pred_x0_inter m_j, by the DDIM rule over n steps (n_inter = rdm_ddim_num_intermediates(n, log_every_t)).
+ * Node lists come from rdm_dpmpp_timesteps.  Other arguments as rdm_plms_sample. */
+int rdm_unipc_sample(rdm_ctx* ctx, const rdm_unipc_args* args, const float* x_T, const float* cond, const float* uncond,
+                     float* z_out, float* x_inter, float* pred_x0_inter);
+/* The scalars of the pass after forward j (0 <= j <= n_nodes - 2) of rdm_unipc_sample, host code only (ctx-free), float64 from the fp32
+ * alphas_cumprod.  out[13] = alpha_j, sigma_j, a_x, a_t, a_1, a_2, a_3, b_x, b_0, b_1, b_2, order_c, order_p with
+ * x_j = a_x x_{j-1} + a_t m_j + a_1 m_{j-1} + a_2 m_{j-2} + a_3 m_{j-3} (order_c = the order of step j, 0 when x_j = u_j: j = 0 or no corrector;
+ * coefficients beyond the order are 0) and u_{j+1} = b_x x_j + b_0 m_j + b_1 m_{j-1} + b_2 m_{j-2} (order_p = the order of step j + 1).
+ * Returns 0, or a negative value for bad arguments (nodes as rdm_unipc_sample requires them). */
+int rdm_unipc_coefficients(const float* alphas_cumprod, int T, const int* nodes, int n_nodes, int j, int order, int variant, int corrector,
+                           int lower_order_final, double* out);
 /* ldm LatentDiffusion.p_sample_loop / p_sample (no CFG on this path).
  * noise [dev] f32 [timesteps,B,C,H,W], consumed in loop order. */
 int rdm_ddpm_sample(rdm_ctx* ctx, const rdm_ddpm_args* args, const float* x_T, const float* cond, const float* noise,
@@ -411,6 +446,14 @@ int rdm_op_add(rdm_ctx* ctx, const void* a_bf16, const void* b_bf16, void* out_b
 int rdm_op_dpmpp_step(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, long long n, int cfg, float scale,
                       float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup_or_null,
                       float* m_store_or_null, float* pred_x0_or_null);
+/* One UniPC pass, the kernel of rdm_unipc_sample alone (fp32, n elements; coefficients [host]: the 13 doubles of rdm_unipc_coefficients,
+ * rounded to fp32 here): e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i]) : eps[i]; m = (u - sigma e) / alpha;
+ * xc = order_c ? a_x xc_prev + a_t m + a_1 h1 (+ a_2 h2) (+ a_3 h3) : u; u_next = b_x xc + b_0 m (+ b_1 h1) (+ b_2 h2), terms up to the
+ * orders; xc_out <- xc, x_dup <- u_next, m_store <- m, pred_x0 <- m.  Operands the orders do not reach may be null.  u_next may be u,
+ * xc_out may be xc_prev, m_store may be any history slot. */
+int rdm_op_unipc_step(rdm_ctx* ctx, const float* u, const float* eps, const float* xc_prev_or_null, const float* h1_or_null,
+                      const float* h2_or_null, const float* h3_or_null, long long n, int cfg, float scale, const double* coefficients,
+                      float* xc_out_or_null, float* u_next, float* x_dup_or_null, float* m_store_or_null, float* pred_x0_or_null);
 /* Elementwise pieces of the UNet's training graph: SiLU of the time-embedding MLP (`nn.SiLU()` in
  * openaimodel.py time_embed / emb_layers) -- dy null: out bf16 = silu(x), else out fp32 = dy * silu'(x) -- and the 2 x 2 sum pooling
  * that is the gradient of Upsample's nearest-neighbour F.interpolate: x bf16 [B, 2H, 2W, C] -> out bf16 [B, H, W, C]. */

@@ -72,6 +72,17 @@ class DpmppArgs(C.Structure):
 DPMPP_SKIP_TYPES = {"time_uniform": 0, "logSNR": 1}
 
 
+class UnipcArgs(C.Structure):
+    _fields_ = [("batch", C.c_int), ("k", C.c_int), ("channels", C.c_int), ("height", C.c_int), ("width", C.c_int),
+                ("unconditional_guidance_scale", C.c_float), ("order", C.c_int), ("variant", C.c_int), ("corrector", C.c_int),
+                ("lower_order_final", C.c_int), ("log_every_t", C.c_int), ("T", C.c_int), ("alphas_cumprod", C.POINTER(C.c_float)),
+                ("n_nodes", C.c_int), ("nodes", C.POINTER(C.c_int))]
+
+
+UNIPC_VARIANTS = {"bh1": 0, "bh2": 1}
+UNIPC_COEFFICIENTS = ("alpha", "sigma", "a_x", "a_t", "a_1", "a_2", "a_3", "b_x", "b_0", "b_1", "b_2", "order_c", "order_p")
+
+
 class DdpmArgs(C.Structure):
     _fields_ = [("timesteps", C.c_int), ("batch", C.c_int), ("k", C.c_int), ("channels", C.c_int), ("height", C.c_int),
                 ("width", C.c_int), ("clip_denoised", C.c_int), ("temperature", C.c_float), ("T", C.c_int),
@@ -109,6 +120,9 @@ SIGNATURES = {
     "rdm_plms_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, _P, _P, _P]),
     "rdm_dpmpp_sample": (C.c_int, [_P, C.POINTER(DpmppArgs), _P, _P, _P, _P, _P, _P]),
     "rdm_dpmpp_timesteps": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
+    "rdm_unipc_sample": (C.c_int, [_P, C.POINTER(UnipcArgs), _P, _P, _P, _P, _P, _P]),
+    "rdm_unipc_coefficients": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                         C.c_int, C.POINTER(C.c_double)]),
     "rdm_ddpm_sample": (C.c_int, [_P, C.POINTER(DdpmArgs), _P, _P, _P, _P]),
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
@@ -167,6 +181,7 @@ SIGNATURES = {
     "rdm_op_add": (C.c_int, [_P, _P, _P, _P, C.c_longlong]),
     "rdm_op_dpmpp_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     _P, _P, _P, _P]),
+    "rdm_op_unipc_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.POINTER(C.c_double), _P, _P, _P, _P, _P]),
     "rdm_op_geglu": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int]),
     "rdm_op_linear_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "rdm_op_linear_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
@@ -381,6 +396,28 @@ def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):
     if n < 2:
         raise RdmError(f"dpmpp_timesteps: bad arguments (S={S}, T={T}, skip_type={skip_type!r})")
     return out[:n].copy()
+
+
+def _unipc_variant(what, variant):
+    if variant not in UNIPC_VARIANTS:
+        raise RdmError(f"{what}: variant must be one of {sorted(UNIPC_VARIANTS)}, got {variant!r}")
+    return UNIPC_VARIANTS[variant]
+
+
+def unipc_coefficients(nodes, alphas_cumprod, j, order=2, variant="bh2", corrector=True, lower_order_final=True):
+    """The float64 scalars of the UniPC pass after forward j over `nodes` (rdm_unipc_coefficients; host code, no context needed):
+    -> float64 numpy array [13] in the order of UNIPC_COEFFICIENTS: alpha_j, sigma_j, the correction x_j = a_x x_{j-1} + a_t m_j +
+    a_1 m_{j-1} + a_2 m_{j-2} + a_3 m_{j-3} (order_c 0: x_j = u_j), the prediction u_{j+1} = b_x x_j + b_0 m_j + b_1 m_{j-1} + b_2 m_{j-2}."""
+    ac = _acp_array(alphas_cumprod)
+    nd = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
+    out = np.zeros((len(UNIPC_COEFFICIENTS),), dtype=np.float64)
+    r = lib.rdm_unipc_coefficients(ac.ctypes.data_as(C.POINTER(C.c_float)), ac.shape[0], nd.ctypes.data_as(C.POINTER(C.c_int)), nd.shape[0],
+                                   int(j), int(order), _unipc_variant("unipc_coefficients", variant), int(bool(corrector)),
+                                   int(bool(lower_order_final)), out.ctypes.data_as(C.POINTER(C.c_double)))
+    if r != 0:
+        raise RdmError(f"unipc_coefficients: bad arguments (j={j}, order={order}, {nd.shape[0]} nodes: strictly decreasing timesteps in "
+                       f"[0, {ac.shape[0] - 1}], 0 <= j <= n_nodes - 2, order 1 | 2 | 3)")
+    return out
 
 
 class Context:
@@ -708,6 +745,55 @@ class Context:
             raise RdmError("op_dpmpp_step: operand sizes do not match x")
         self._check(lib.rdm_op_dpmpp_step(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), n, int(bool(cfg)), float(scale), float(sqrt_a_s),
                                           float(sqrt_one_minus_a_s), float(c_x), float(c_0), float(c_1), _ptr(x_out), _ptr(x_dup),
+                                          _ptr(m_store), _ptr(pred_x0)))
+
+    @staticmethod
+    def unipc_coefficients(nodes, alphas_cumprod, j, order=2, variant="bh2", corrector=True, lower_order_final=True):
+        return unipc_coefficients(nodes, alphas_cumprod, j, order, variant, corrector, lower_order_final)
+
+    def unipc_sample(self, nodes, x_T, cond, uncond, alphas_cumprod, scale=1.0, order=2, variant="bh2", corrector=True,
+                     lower_order_final=True, log_every_t=100, want_intermediates=False):
+        """UniPC (Zhao et al. 2023; multistep data prediction, predictor order 1 | 2 | 3, the corrector adds one) over the strictly
+        decreasing integer timesteps `nodes` (dpmpp_timesteps builds the two grids): len(nodes) - 1 UNet forwards, the result at the noise
+        level of nodes[-1].  Returns (z, x_inter, pred_x0_inter): x_inter[j] the UNet input of node j + 1 (the last one is z),
+        pred_x0_inter[j] = m_j; the intermediates are None unless want_intermediates."""
+        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
+        uncond = None if uncond is None else self._dev(uncond, torch.float32)
+        ac = _acp_array(alphas_cumprod)
+        nd = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
+        n_steps = nd.shape[0] - 1
+        self._check_sampler_shapes("unipc_sample", x_T, cond, uncond)
+        if scale > 1.0 and uncond is None:
+            raise RdmError("unipc_sample: unconditional_conditioning is required when unconditional_guidance_scale > 1")
+        B, Cc, H, W = x_T.shape
+        a = UnipcArgs(batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, unconditional_guidance_scale=scale, order=int(order),
+                      variant=_unipc_variant("unipc_sample", variant), corrector=int(bool(corrector)),
+                      lower_order_final=int(bool(lower_order_final)), log_every_t=log_every_t, T=ac.shape[0],
+                      alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)), n_nodes=nd.shape[0],
+                      nodes=nd.ctypes.data_as(C.POINTER(C.c_int)))
+        z = torch.empty_like(x_T)
+        xi = pi = None
+        if want_intermediates:
+            n = lib.rdm_ddim_num_intermediates(n_steps, log_every_t)
+            xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
+            pi = torch.empty_like(xi)
+        self._check(lib.rdm_unipc_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
+        return z, xi, pi
+
+    def op_unipc_step(self, u, eps, coefficients, cfg, scale, u_next, xc_prev=None, h1=None, h2=None, h3=None, xc_out=None, x_dup=None,
+                      m_store=None, pred_x0=None):
+        """The UniPC predict-and-correct kernel alone on caller-owned fp32 device tensors of u.numel() elements (eps: twice that under
+        cfg, [cond | uncond]); `coefficients` the 13 float64 values of unipc_coefficients.  xc_prev / h1 / h2 / h3 as far as the orders
+        reach; u_next may be u, xc_out may be xc_prev, m_store may be a history slot.  Writes into the given outputs."""
+        n = u.numel()
+        co = np.ascontiguousarray(np.asarray(coefficients, dtype=np.float64).reshape(-1))
+        if co.shape[0] != len(UNIPC_COEFFICIENTS):
+            raise RdmError(f"op_unipc_step: coefficients must hold {len(UNIPC_COEFFICIENTS)} values")
+        if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in (xc_prev, h1, h2, h3, xc_out, u_next, x_dup,
+                                                                                                 m_store, pred_x0)):
+            raise RdmError("op_unipc_step: operand sizes do not match u")
+        self._check(lib.rdm_op_unipc_step(self._h, _ptr(u), _ptr(eps), _ptr(xc_prev), _ptr(h1), _ptr(h2), _ptr(h3), n, int(bool(cfg)),
+                                          float(scale), co.ctypes.data_as(C.POINTER(C.c_double)), _ptr(xc_out), _ptr(u_next), _ptr(x_dup),
                                           _ptr(m_store), _ptr(pred_x0)))
 
     def ddpm_sample(self, timesteps, x_T, cond, noise, sched, clip_denoised=True, temperature=1.0):

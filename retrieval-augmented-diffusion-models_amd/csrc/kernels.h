@@ -123,6 +123,20 @@ struct DpmppStepParams {
     int cfg;
 };
 
+// One UniPC pass (Zhao et al. 2023, data prediction, multistep), run after the forward at node j: e = CFG(eps), m = (u - sigma e) / alpha
+// -> m_store, pred_x0; the correction of the kept iterate xc = a_x xc_prev + a_t m + a_1 h1 + a_2 h2 + a_3 h3 with order_c history terms
+// (order_c == 0: xc = u, xc_prev unused) -> xc_out; the prediction u_next = b_x xc + b_0 m + b_1 h1 + b_2 h2 with order_p - 1 history
+// terms -> u_next, x_dup.  h1, h2, h3 = m_{j-1}, m_{j-2}, m_{j-3}; a slot the pass does not read is null.  Every input element is read
+// before any output element is written, by the same thread: u_next may be u, xc_out may be xc_prev, m_store may be h3 (or any slot).
+struct UnipcStepParams {
+    const float* u; const float* eps;                        // eps: [n] rows (cfg == 0) or [2n] (cond | uncond)
+    const float* xc_prev; const float* h1; const float* h2; const float* h3;
+    float* xc_out; float* u_next; float* x_dup; float* m_store; float* pred_x0;     // all but u_next may be null
+    long long n;                                             // B*C*H*W
+    float alpha, sigma, scale, a_x, a_t, a_1, a_2, a_3, b_x, b_0, b_1, b_2;
+    int cfg, order_c, order_p;                               // order_c 0..3, order_p 1..3
+};
+
 struct DdpmStepParams {
     const float* x; const float* eps; const float* noise; float* x_prev; long long n;
     float sqrt_recip, sqrt_recipm1, coef1, coef2, log_var; int clip, nonzero; float temperature;
@@ -283,6 +297,7 @@ hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st);
 hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
 hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);
+hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st);
 hipError_t launch_vq_quantize(const float* z, const float* codebook, int n_embed, const float* pq_w, const float* pq_b,
                               float* out, int* idx_out, int B, int HW, int quantize, hipStream_t st);
 // nearest-code search of a wide-latent VQ first stage (vqcode.hip): idx[m] = argmin_j |e_j|^2 - 2 z_m . e_j on fp32-input MFMAs, first minimum on ties

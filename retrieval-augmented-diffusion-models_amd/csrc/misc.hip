@@ -636,6 +636,72 @@ hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ UniPC predict-and-correct (fp32)
+// Zhao et al. 2023 (UniPC, data prediction, multistep): after the forward at node j one pass forms m = (u - sigma_j e) / alpha_j from
+// the guided eps, corrects the kept iterate, xc = a_x xc_prev + a_t m + a_1 h1 + a_2 h2 + a_3 h3 (order_c history terms; order_c == 0:
+// xc = u), and predicts the next UNet input, u_next = b_x xc + b_0 m + b_1 h1 + b_2 h2 (order_p - 1 history terms), with the nine
+// coefficients the host computes in float64 (rdm_unipc_coefficients).  True divisions, no FMA contraction, both sums taken left to
+// right.  A thread reads its elements of u, xc_prev and the history before it writes any output and no other thread touches them, so
+// u_next may be u, xc_out may be xc_prev, and m_store may be the oldest history slot (the ring rotates by pointer, as PLMS's does).
+// V = 4: float4 accesses (the launcher checks n % 4 and alignment).
+template <int V>
+__global__ __launch_bounds__(256) void unipc_step_kernel(UnipcStepParams p) {
+#pragma clang fp contract(off)
+    const long long nv = p.n / V;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * V;
+        float e[V], u[V], m[V], xc[V], un[V], h1[V], h2[V], h3[V];
+        plms_ld<V>(p.eps, i, e);
+        if (p.cfg) {
+            float w[V]; plms_ld<V>(p.eps + p.n, i, w);
+#pragma unroll
+            for (int k = 0; k < V; k++) e[k] = w[k] + p.scale * (e[k] - w[k]);
+        }
+        plms_ld<V>(p.u, i, u);
+        const int nh = p.order_c > p.order_p - 1 ? p.order_c : p.order_p - 1;        // history slots this pass reads
+        if (nh >= 1) plms_ld<V>(p.h1, i, h1);
+        if (nh >= 2) plms_ld<V>(p.h2, i, h2);
+        if (nh >= 3) plms_ld<V>(p.h3, i, h3);
+#pragma unroll
+        for (int k = 0; k < V; k++) m[k] = (u[k] - p.sigma * e[k]) / p.alpha;
+        if (p.order_c >= 1) {
+            float xp[V]; plms_ld<V>(p.xc_prev, i, xp);
+#pragma unroll
+            for (int k = 0; k < V; k++) {
+                xc[k] = p.a_x * xp[k] + p.a_t * m[k];
+                xc[k] = xc[k] + p.a_1 * h1[k];
+                if (p.order_c >= 2) xc[k] = xc[k] + p.a_2 * h2[k];
+                if (p.order_c >= 3) xc[k] = xc[k] + p.a_3 * h3[k];
+            }
+        } else {
+#pragma unroll
+            for (int k = 0; k < V; k++) xc[k] = u[k];
+        }
+#pragma unroll
+        for (int k = 0; k < V; k++) {
+            un[k] = p.b_x * xc[k] + p.b_0 * m[k];
+            if (p.order_p >= 2) un[k] = un[k] + p.b_1 * h1[k];
+            if (p.order_p >= 3) un[k] = un[k] + p.b_2 * h2[k];
+        }
+        if (p.m_store) plms_st<V>(p.m_store, i, m);           // after the history reads: m_store may be h3's slot
+        if (p.xc_out) plms_st<V>(p.xc_out, i, xc);            // after the xc_prev read: xc_out may be that slot
+        plms_st<V>(p.u_next, i, un);
+        if (p.x_dup) plms_st<V>(p.x_dup, i, un);
+        if (p.pred_x0) plms_st<V>(p.pred_x0, i, m);
+    }
+}
+hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st) {
+    if (p.n <= 0) return hipSuccess;
+    const void* ptrs[] = {p.u, p.eps, p.eps + (p.cfg ? p.n : 0), p.xc_prev, p.h1, p.h2, p.h3, p.xc_out, p.u_next, p.x_dup, p.m_store, p.pred_x0};
+    bool vec = p.n % 4 == 0;
+    for (const void* q : ptrs) vec = vec && ((uintptr_t)q % 16 == 0);        // (null is aligned)
+    const long long nv = vec ? p.n / 4 : p.n;
+    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
+    if (vec) unipc_step_kernel<4><<<grid, 256, 0, st>>>(p);
+    else unipc_step_kernel<1><<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
+}
+
 // out[r, :] = x[r, :] + bias[:]   (bf16 rows, 8 columns per thread).  Cross-attention of a sample whose neighbours are all-zero
 // vectors -- the unconditional half of a guided batch, rdm/models/diffusion/ddpm.py:673-680 -- is exactly to_out.bias: K = V = 0
 // gives uniform attention over zero values (rdm/modules/attention.py:52-72), so t2 = t1 + b_o without any GEMM.

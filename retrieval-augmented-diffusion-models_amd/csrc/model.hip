@@ -2016,6 +2016,170 @@ int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, cons
     return run.finish(z_out);
 }
 
+// UniPC (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models"), data prediction,
+// multistep, in the notation of rdm_unipc_sample's header comment.  Everything below is float64 host code.
+
+// rho <- R^-1 b for R [n][n], n <= 3: Gaussian elimination with partial pivoting, written out (false: singular)
+static bool unipc_solve(int n, double R[3][3], double* b, double* rho) {
+    for (int col = 0; col < n; col++) {
+        int piv = col;
+        for (int i = col + 1; i < n; i++) if (std::fabs(R[i][col]) > std::fabs(R[piv][col])) piv = i;
+        if (R[piv][col] == 0.0) return false;
+        if (piv != col) { for (int k = 0; k < n; k++) std::swap(R[piv][k], R[col][k]); std::swap(b[piv], b[col]); }
+        for (int i = col + 1; i < n; i++) {
+            const double f = R[i][col] / R[col][col];
+            for (int k = col; k < n; k++) R[i][k] -= f * R[col][k];
+            b[i] -= f * b[col];
+        }
+    }
+    for (int i = n - 1; i >= 0; i--) {
+        double v = b[i];
+        for (int k = i + 1; k < n; k++) v -= R[i][k] * rho[k];
+        rho[i] = v / R[i][i];
+    }
+    return true;
+}
+
+// Step s (1-based: from node s-1 to node s) at order p: phi_1 = expm1(-h), B(h), r_1 .. r_{p-1} (r_p = 1 is the corrector's own) and
+// b_1 .. b_3.  lam[i] is the half logSNR of node i.
+struct UnipcStep { double phi1, B, r[3], b[3]; };
+static UnipcStep unipc_step_scalars(const double* lam, int s, int p, int variant) {
+    UnipcStep u{};
+    const double h = lam[s] - lam[s - 1], hh = -h;
+    u.phi1 = std::expm1(hh);
+    u.B = variant == 0 ? hh : std::expm1(hh);
+    for (int i = 1; i < p; i++) u.r[i - 1] = (lam[s - 1 - i] - lam[s - 1]) / h;
+    u.r[p - 1] = 1.0;
+    double g = u.phi1 / hh - 1.0, fact = 1.0;              // g_i, i!
+    for (int i = 1; i <= 3; i++) {
+        u.b[i - 1] = g * fact / u.B;
+        fact *= (double)(i + 1);
+        g = g / hh - 1.0 / fact;
+    }
+    return u;
+}
+
+static int unipc_order(int s, int n, int order, int lower_order_final) {
+    int p = order < s ? order : s;
+    if (lower_order_final && n + 1 - s < p) p = n + 1 - s;
+    return p;
+}
+
+int rdm_unipc_coefficients(const float* alphas_cumprod, int T, const int* nodes, int n_nodes, int j, int order, int variant, int corrector,
+                           int lower_order_final, double* out) {
+    if (!alphas_cumprod || !nodes || !out || T < 2 || n_nodes < 2 || j < 0 || j >= n_nodes - 1 || order < 1 || order > 3 ||
+        (variant != 0 && variant != 1)) return -1;
+    for (int i = 0; i < n_nodes; i++) {
+        if (nodes[i] < 0 || nodes[i] >= T || (i > 0 && nodes[i] >= nodes[i - 1])) return -1;
+        if (!(alphas_cumprod[nodes[i]] > 0.f && alphas_cumprod[nodes[i]] < 1.f)) return -1;
+    }
+    const int n = n_nodes - 1;
+    auto node = [&](int i) { return dpmpp_node(alphas_cumprod, nodes[i]); };
+    std::vector<double> lamv((size_t)n_nodes);
+    for (int i = 0; i < n_nodes; i++) lamv[(size_t)i] = node(i).lambda;
+    const double* lam = lamv.data();
+    const DpmppNode cur = node(j), nxt = node(j + 1);
+    double a[5] = {0, 0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
+    int pc = 0;
+    if (corrector && j >= 1) {                               // the correction of x_j: step j at its order, r_p = 1 for m_j itself
+        pc = unipc_order(j, n, order, lower_order_final);
+        UnipcStep u = unipc_step_scalars(lam, j, pc, variant);
+        double rho[3] = {0.5, 0, 0};
+        if (pc > 1) {
+            double R[3][3], rhs[3];
+            for (int i = 0; i < pc; i++) { rhs[i] = u.b[i]; for (int k = 0; k < pc; k++) R[i][k] = std::pow(u.r[k], (double)i); }
+            if (!unipc_solve(pc, R, rhs, rho)) return -1;
+        }
+        double sum = rho[pc - 1];
+        for (int i = 0; i < pc - 1; i++) sum += rho[i] / u.r[i];
+        a[0] = cur.sigma / node(j - 1).sigma;
+        a[1] = -cur.alpha * u.B * rho[pc - 1];
+        a[2] = -cur.alpha * u.phi1 + cur.alpha * u.B * sum;
+        for (int i = 0; i < pc - 1; i++) a[3 + i] = -cur.alpha * u.B * rho[i] / u.r[i];
+    }
+    const int pp = unipc_order(j + 1, n, order, lower_order_final);       // the prediction of u_{j+1}: step j + 1 at its order
+    {
+        UnipcStep u = unipc_step_scalars(lam, j + 1, pp, variant);
+        double rho[2] = {0.5, 0};
+        if (pp == 3) {
+            double R[3][3], rhs[3];
+            for (int i = 0; i < 2; i++) { rhs[i] = u.b[i]; for (int k = 0; k < 2; k++) R[i][k] = std::pow(u.r[k], (double)i); }
+            if (!unipc_solve(2, R, rhs, rho)) return -1;
+        }
+        double sum = 0.0;
+        for (int i = 0; i < pp - 1; i++) sum += rho[i] / u.r[i];
+        b[0] = nxt.sigma / cur.sigma;
+        b[1] = -nxt.alpha * u.phi1 + nxt.alpha * u.B * sum;
+        for (int i = 0; i < pp - 1; i++) b[2 + i] = -nxt.alpha * u.B * rho[i] / u.r[i];
+    }
+    out[0] = cur.alpha; out[1] = cur.sigma;
+    for (int i = 0; i < 5; i++) out[2 + i] = a[i];
+    for (int i = 0; i < 4; i++) out[7 + i] = b[i];
+    out[11] = (double)pc; out[12] = (double)pp;
+    return 0;
+}
+
+static void unipc_fill(UnipcStepParams& p, const double* co) {
+    p.alpha = (float)co[0]; p.sigma = (float)co[1];
+    p.a_x = (float)co[2]; p.a_t = (float)co[3]; p.a_1 = (float)co[4]; p.a_2 = (float)co[5]; p.a_3 = (float)co[6];
+    p.b_x = (float)co[7]; p.b_0 = (float)co[8]; p.b_1 = (float)co[9]; p.b_2 = (float)co[10];
+    p.order_c = (int)co[11]; p.order_p = (int)co[12];
+}
+
+// The loop of rdm_unipc_sample's header comment: one forward and one unipc_step_kernel launch per step.  The sampler's own scratch is
+// the kept (corrected) x and a ring of three m slots, rotated by pointer: the newest m takes the oldest slot in the pass that reads it.
+int rdm_unipc_sample(rdm_ctx* c, const rdm_unipc_args* a, const float* x_T, const float* cond, const float* uncond,
+                     float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_T || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
+    if (a->order < 1 || a->order > 3) return c->fail(-1, "unipc order must be 1, 2 or 3, got %d", a->order);
+    if (a->variant != 0 && a->variant != 1) return c->fail(-1, "unipc variant must be 0 (bh1) or 1 (bh2), got %d", a->variant);
+    if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1");
+    const bool cfg = a->unconditional_guidance_scale > 1.0f;
+    if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1");
+    if (a->n_nodes < 2) return c->fail(-1, "unipc needs at least 2 nodes, got %d", a->n_nodes);
+    for (int j = 0; j < a->n_nodes; j++) {
+        if (a->nodes[j] < 0 || a->nodes[j] >= a->T) return c->fail(-1, "unipc node %d = %d outside [0, %d]", j, a->nodes[j], a->T - 1);
+        if (j > 0 && a->nodes[j] >= a->nodes[j - 1]) return c->fail(-1, "unipc nodes must be strictly decreasing (node %d = %d after %d)", j, a->nodes[j], a->nodes[j - 1]);
+        const float ac = a->alphas_cumprod[a->nodes[j]];
+        if (!(ac > 0.f && ac < 1.f)) return c->fail(-1, "alphas_cumprod[%d] = %g outside (0, 1)", a->nodes[j], (double)ac);
+    }
+    const int n_steps = a->n_nodes - 1;
+    std::vector<double> co((size_t)n_steps * 13);
+    for (int j = 0; j < n_steps; j++)
+        if (rdm_unipc_coefficients(a->alphas_cumprod, a->T, a->nodes, a->n_nodes, j, a->order, a->variant, a->corrector, a->lower_order_final,
+                                   &co[(size_t)j * 13]) != 0) return c->fail(-1, "unipc coefficients of step %d are undefined on these nodes", j);
+    const std::vector<int> ts(a->nodes, a->nodes + n_steps);
+    const size_t h_stride = SamplerRun::al((size_t)a->batch * a->channels * a->height * a->width * 4);
+    SamplerRun run;
+    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr, 4 * h_stride));
+    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
+    float* xk = (float*)run.extra;
+    float* slot[3] = {(float*)(run.extra + h_stride), (float*)(run.extra + 2 * h_stride), (float*)(run.extra + 3 * h_stride)};
+    int n_hist = 0;                          // slot[0 .. n_hist) = m_{j-1}, m_{j-2}, m_{j-3}
+    for (int j = 0; j < n_steps; j++) {
+        const int index = n_steps - 1 - j;
+        RDM_TRY(run.forward(j));
+        UnipcStepParams p{};
+        unipc_fill(p, &co[(size_t)j * 13]);
+        const int nh = p.order_c > p.order_p - 1 ? p.order_c : p.order_p - 1;
+        if (nh > n_hist) return c->fail(-1, "unipc step %d needs %d earlier predictions, %d held", j, nh, n_hist);
+        p.u = run.x; p.eps = run.eps; p.n = run.n1; p.cfg = cfg ? 1 : 0; p.scale = a->unconditional_guidance_scale;
+        p.xc_prev = p.order_c >= 1 ? xk : nullptr;
+        p.h1 = nh >= 1 ? slot[0] : nullptr; p.h2 = nh >= 2 ? slot[1] : nullptr; p.h3 = nh >= 3 ? slot[2] : nullptr;
+        float* m_new = slot[n_hist < 3 ? n_hist : 2];          // a free slot, or the oldest m (read before it is overwritten)
+        p.xc_out = a->corrector ? xk : nullptr;                // without the corrector the kept x is the UNet input itself
+        p.u_next = run.x; p.x_dup = run.x_dup; p.m_store = m_new; p.pred_x0 = run.pred_x0_slot(index);
+        RDM_CHECK_HIP(c, launch_unipc_step(p, c->stream));
+        for (int i = n_hist < 3 ? n_hist : 2; i > 0; i--) slot[i] = slot[i - 1];
+        slot[0] = m_new;
+        if (n_hist < 3) n_hist++;
+        RDM_TRY(run.log_x(index));
+    }
+    return run.finish(z_out);
+}
+
 int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const float* noise,
                     float* z_out) {
     RDM_ENTER(c);
@@ -2763,6 +2927,22 @@ int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float*
     p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1;
     p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
     RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
+    return 0;
+}
+int rdm_op_unipc_step(rdm_ctx* c, const float* u, const float* eps, const float* xc_prev, const float* h1, const float* h2, const float* h3,
+                      long long n, int cfg, float scale, const double* coefficients, float* xc_out, float* u_next, float* x_dup,
+                      float* m_store, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!u || !eps || !coefficients || !u_next || n < 1) return c->fail(-1, "rdm_op_unipc_step: bad argument");
+    UnipcStepParams p{};
+    unipc_fill(p, coefficients);
+    if (p.order_c < 0 || p.order_c > 3 || p.order_p < 1 || p.order_p > 3) return c->fail(-1, "rdm_op_unipc_step: orders %d, %d outside 0..3, 1..3", p.order_c, p.order_p);
+    const int nh = p.order_c > p.order_p - 1 ? p.order_c : p.order_p - 1;
+    if ((p.order_c >= 1 && !xc_prev) || (nh >= 1 && !h1) || (nh >= 2 && !h2) || (nh >= 3 && !h3))
+        return c->fail(-1, "rdm_op_unipc_step: orders %d, %d need xc_prev / history operands that are null", p.order_c, p.order_p);
+    p.u = u; p.eps = eps; p.xc_prev = xc_prev; p.h1 = h1; p.h2 = h2; p.h3 = h3; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale;
+    p.xc_out = xc_out; p.u_next = u_next; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
+    RDM_CHECK_HIP(c, launch_unipc_step(p, c->stream));
     return 0;
 }
 int rdm_op_ema(rdm_ctx* c, float* shadow, const float* p, long long n, float one_minus_decay) {

@@ -34,8 +34,8 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
 
 
 class _SamplerBase(object):
-    """What DDIMSampler, PLMSSampler and DPMSolverSampler share: the constructor, DDIM's schedule, and the rules the loops apply around a
-    step."""
+    """What DDIMSampler, PLMSSampler, DPMSolverSampler and UniPCSampler share: the constructor, DDIM's schedule, and the rules the loops
+    apply around a step."""
 
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()

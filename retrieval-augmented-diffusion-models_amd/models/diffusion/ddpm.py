@@ -22,6 +22,7 @@ from ...util import ischannellastimage
 from .ddim import DDIMSampler
 from .dpm_solver import DPMSolverSampler
 from .plms import PLMSSampler
+from .uni_pc import UniPCSampler
 
 
 class MinimalRETRODiffusion(object):
@@ -190,7 +191,7 @@ class MinimalRETRODiffusion(object):
             base = parallel.shared_seed(self.device, getattr(self, "_group", None))
             kwargs["x_T"] = parallel.per_sample_noise(base, range(lo, hi), shape, device=self.device)
             steps = None
-            noiseless = kwargs.get("plms", False) or kwargs.get("dpm_solver", False)      # PLMS and DPM-Solver++ draw no per-step noise
+            noiseless = any(kwargs.get(name, False) for name in ("plms", "dpm_solver", "uni_pc"))      # these draw no per-step noise
             if not noiseless and kwargs.get("ddim", True) and kwargs.get("eta", 0.) != 0.:
                 steps = len(range(0, self.num_timesteps, self.num_timesteps // kwargs.get("S", kwargs.get("ddim_steps"))))
             elif not noiseless and not kwargs.get("ddim", True):
@@ -388,14 +389,19 @@ class MinimalRETRODiffusion(object):
 
     # ---- samplers
     @torch.no_grad()
-    def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, dpm_solver=False, **kwargs):
+    def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, dpm_solver=False,
+                   uni_pc=False, **kwargs):
         """ddpm.py:988-1011.  [native] plms=True samples with PLMSSampler (ldm), dpm_solver=True with DPMSolverSampler (DPM-Solver++ 2M
-        on the logSNR grid) on S = ddim_steps instead of DDIM / DDPM."""
+        on the logSNR grid), uni_pc=True with UniPCSampler (UniPC order 2, bh2, with the corrector, on the logSNR grid) on
+        S = ddim_steps instead of DDIM / DDPM."""
         if plms and dpm_solver:
             raise ValueError("plms and dpm_solver select different samplers: give one of them")
+        if uni_pc and (plms or dpm_solver):
+            raise ValueError(f"{'plms' if plms else 'dpm_solver'} and uni_pc select different samplers: give one of them")
         shape = (self.channels, self.image_size, self.image_size) if custom_shape is None else self._latent_shape(custom_shape)
-        if ddim or plms or dpm_solver:
-            sampler = PLMSSampler(self) if plms else DPMSolverSampler(self) if dpm_solver else DDIMSampler(self)
+        if ddim or plms or dpm_solver or uni_pc:
+            sampler = (PLMSSampler(self) if plms else DPMSolverSampler(self) if dpm_solver else UniPCSampler(self) if uni_pc
+                       else DDIMSampler(self))
             ddim_steps = kwargs.pop('S', ddim_steps)
             verbose = kwargs.pop('verbose', False)
             return sampler.sample(S=ddim_steps, batch_size=batch_size, shape=shape, conditioning=cond, verbose=verbose, **kwargs)

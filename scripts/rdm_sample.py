@@ -20,7 +20,8 @@ network), `--gpus N` (batch-sharded multi-GPU sampling, one process per GPU via 
 the finished images; `--gpu` is then ignored and each rank uses its LOCAL_RANK), `--plms` (sample with ldm's PLMSSampler on
 `--steps` instead of DDIM: same schedule, about half the steps for the same accuracy; works with `--gpus N`), `--dpm_solver`
 (sample with DPM-Solver++(2M), ldm's DPMSolverSampler, on a logSNR grid of at most `--steps` steps: 15-25 steps under guidance;
-works with `--gpus N`; not together with `--plms`), `--height PX` / `--width PX` (image size in pixels, default the model's own: the UNet and
+works with `--gpus N`; not together with `--plms`), `--uni_pc` (sample with UniPC order 2: DPM-Solver++(2M) plus a corrector that costs no
+forward, on the same grid; works with `--gpus N`; not together with `--plms` or `--dpm_solver`), `--height PX` / `--width PX` (image size in pixels, default the model's own: the UNet and
 the first stage are convolutional, so a model samples at other sizes -- the reference reaches this through `sample_log(custom_shape=)`
 only, its script has no flag; multiples of 32 = first-stage factor 4 x UNet down factor 8 of the shipped models; every sampler, and
 `--gpus N`).
@@ -73,6 +74,8 @@ def build_parser() -> argparse.ArgumentParser:
                         help="[native] sample with DPM-Solver++(2M) (ldm DPMSolverSampler) on a logSNR grid instead of DDIM")
     parser.add_argument("--height", type=int, default=None, help="[native] image height in pixels (default: the model's own size); a multiple of 32")
     parser.add_argument("--width", type=int, default=None, help="[native] image width in pixels (default: the model's own size); a multiple of 32")
+    parser.add_argument("--uni_pc", default=False, action="store_true",
+                        help="[native] sample with UniPC (order 2, bh2, with the corrector) on a logSNR grid instead of DDIM")
     return parser
 
 
@@ -193,9 +196,9 @@ def _save_logs(logs, keys, opt, sampling_start, n):
 
 
 def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
-    """--plms / --dpm_solver / --height / --width reach MinimalRETRODiffusion.sample_log (the sizes as its custom_shape, in latent
+    """--plms / --dpm_solver / --uni_pc / --height / --width reach MinimalRETRODiffusion.sample_log (the sizes as its custom_shape, in latent
     pixels); without them the calls are the reference's."""
-    kw = {name: True for name in ("plms", "dpm_solver") if getattr(opt, name, False)}
+    kw = {name: True for name in ("plms", "dpm_solver", "uni_pc") if getattr(opt, name, False)}
     height, width = getattr(opt, "height", None), getattr(opt, "width", None)
     if height is not None or width is not None:
         f = 1 << (model.vq_cfg.n_ch_mult - 1)                       # pixels per latent pixel

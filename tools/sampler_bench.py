@@ -2,7 +2,8 @@
 """DDIM against PLMS and DPM-Solver++, native loops on the shipped synthetic UNet + VQ-f4 decoder at B = 64 (CFG 2.0, k = 4
 neighbours; the UNet batch is the guided B' = 128): ms per image, VQ decode included, for each `name:S` given (default ddim:50 plms:50
 plms:25).  PLMS with S timesteps runs S + 1 forwards; dpmpp:S is DPM-Solver++(2M) on the logSNR grid of S targets, whose real step
-count (reported under "forwards") can come out below S.  Prints one JSON line.
+count (reported under "forwards") can come out below S; unipc:S is UniPC (order 2, bh2, with the corrector) on the same grid, one
+forward per step like dpmpp.  Prints the box's calibration probe and one line per run on stderr, one JSON line on stdout.
 
     python tools/sampler_bench.py [--reps N] [--batch B] [ddim:50 plms:50 plms:25 dpmpp:20 ...]
 """
@@ -47,16 +48,21 @@ def main():
             z, _, _ = ctx.plms_sample(S, x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         elif name == "dpmpp":
             z, _, _ = ctx.dpmpp_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
+        elif name == "unipc":
+            z, _, _ = ctx.unipc_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         else:
-            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp)")
+            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | unipc)")
         return ctx.vq_decode(z)
 
     def forwards(name, S):
-        if name == "dpmpp":
+        if name in ("dpmpp", "unipc"):
             return len(ctx.dpmpp_timesteps(S, model.alphas_cumprod)) - 1
         return S + (1 if name == "plms" else 0)
 
-    out = {"batch": B, "scale": 2.0, "k": 4, "reps": a.reps, "ms_per_image": {}, "forwards": {}}
+    tf, gb = ctx.calib_probe()
+    print(f"calibration: mfma probe {tf:.1f} TFLOP/s, hbm stream {gb:.1f} GB/s", file=sys.stderr, flush=True)
+    out = {"batch": B, "scale": 2.0, "k": 4, "reps": a.reps, "calibration": {"mfma_probe_tflops": round(tf, 1), "hbm_stream_gbps": round(gb, 1)},
+           "ms_per_image": {}, "forwards": {}}
     for run in a.runs:
         name, S = run.split(":")
         S = int(S)
@@ -76,6 +82,8 @@ def main():
         out["speedup_plms25_over_ddim50"] = round(ms["ddim:50"] / ms["plms:25"], 3)
     if "ddim:50" in ms and "dpmpp:20" in ms:
         out["speedup_dpmpp20_over_ddim50"] = round(ms["ddim:50"] / ms["dpmpp:20"], 3)
+    if "dpmpp:20" in ms and "unipc:10" in ms:
+        out["speedup_unipc10_over_dpmpp20"] = round(ms["dpmpp:20"] / ms["unipc:10"], 3)
     print(json.dumps(out))
     ctx.close()
 
