@@ -437,6 +437,18 @@ int rdm_op_layernorm_bwd_add(rdm_ctx* ctx, const void* x_bf16, const void* dy_bf
 /* nn.Linear weight gradient dW [N, K] fp32 = dy^T a for dy [M, N], a [M, K] bf16 (autograd of F.linear in the training step): K-split
  * over the M rows, deterministic fixed-order sum of the fp32 partial planes. */
 int rdm_op_linear_wgrad(rdm_ctx* ctx, const void* dy_bf16, const void* a_bf16, float* dw, long long M, int N, int K);
+/* Which kernel the two weight-gradient ops run for a shape, host only (no device call); the ops dispatch on this same function.
+ *   conv != 0: rdm_op_conv3x3_wgrad at (B, H, W, C, N) (M, K ignored); conv == 0: rdm_op_linear_wgrad at (M, N, K) (B, H, W, C ignored).
+ *   path: CONV9_LW4 / 5 / 6 = the nine-tap kernel at image width 16 / 32 / 64; TN9 / TN1 = the per-tap transpose-free kernel with 9 taps / 1 tap;
+ *   the fallbacks copy both operands transposed and run the implicit GEMM.  Z = fp32 planes summed in plane order (1: straight into dw);
+ *   per_plane = what one plane reduces over: chunks of max(32, W) pixels (CONV9), rows (TN), padded K' positions (fallbacks);
+ *   remap: CONV9 = the number of leading planes dealt whole to the XCDs (Z & ~7; the rest in launch order), TN = 1 when tiles * Z is a
+ *   multiple of 8 and the blocks of a (tile, plane) share an XCD, fallbacks 0.  Returns -1 for a shape the op refuses (the two share one check: B, H, W, N >= 1, C even >= 2 and B H W
+ *   within int for the conv; 1 <= M within int, N and K even >= 2 for the linear op). */
+enum { RDM_WGRAD_CONV9_LW4 = 1, RDM_WGRAD_CONV9_LW5 = 2, RDM_WGRAD_CONV9_LW6 = 3, RDM_WGRAD_TN9 = 4, RDM_WGRAD_TN1 = 5, RDM_WGRAD_CONV_FALLBACK = 6,
+       RDM_WGRAD_LINEAR_FALLBACK = 7 };
+typedef struct rdm_wgrad_form { int path, Z, per_plane, remap; } rdm_wgrad_form;
+int rdm_wgrad_select(int conv, int B, int H, int W, int C, int N, long long M, int K, rdm_wgrad_form* form_out);
 int rdm_op_colsum(rdm_ctx* ctx, const void* x_bf16 /*[M,N]*/, float* out /*[N]*/, long long M, int N);
 int rdm_op_transpose(rdm_ctx* ctx, const void* x_bf16 /*[rows,cols]*/, void* y_bf16 /*[cols,rows]*/, int rows, int cols);
 int rdm_op_add(rdm_ctx* ctx, const void* a_bf16, const void* b_bf16, void* out_bf16, long long n);
@@ -481,13 +493,14 @@ int rdm_op_expand2(rdm_ctx* ctx, const void* x_bf16, void* out_bf16, int B, int 
 int rdm_op_ema(rdm_ctx* ctx, float* shadow, const float* param, long long n, float one_minus_decay);
 /* One AdamW step (torch.optim.AdamW: decoupled weight decay, bias-corrected moments; the reference's configure_optimizers,
  * rdm/models/diffusion/ddpm.py, hands the UNet parameters to it) on fp32 master parameters / moments in place; p_bf16 (optional) receives
- * the bf16 working copy the kernels read.  step counts from 1. */
-int rdm_op_adamw(rdm_ctx* ctx, float* p, const float* grad, float* exp_avg, float* exp_avg_sq, void* p_bf16_or_null, long long n, float lr,
-                 float beta1, float beta2, float eps, float weight_decay, int step);
+ * the bf16 working copy the kernels read.  step counts from 1.  The hyper-parameters are doubles: 1 - beta and the bias corrections 1 - beta^step
+ * are differences of nearly equal numbers (1 - 0.999f is 1.3e-5 short of 1e-3), so they are taken in double here and rounded once for the kernel. */
+int rdm_op_adamw(rdm_ctx* ctx, float* p, const float* grad, float* exp_avg, float* exp_avg_sq, void* p_bf16_or_null, long long n, double lr,
+                 double beta1, double beta2, double eps, double weight_decay, int step);
 /* The same two over LISTS of tensors (host arrays of n device pointers and element counts; p_bf16 may be null, or hold null entries): the
  * UNet has 688 parameter tensors, most of them tiny -- 48 tensors per launch instead of one launch each.  Same arithmetic per element. */
 int rdm_op_adamw_multi(rdm_ctx* ctx, int n, float* const* p, const float* const* grad, float* const* exp_avg, float* const* exp_avg_sq,
-                       void* const* p_bf16_or_null, const long long* numel, float lr, float beta1, float beta2, float eps, float weight_decay, int step);
+                       void* const* p_bf16_or_null, const long long* numel, double lr, double beta1, double beta2, double eps, double weight_decay, int step);
 int rdm_op_ema_multi(rdm_ctx* ctx, int n, float* const* shadow, const float* const* param, const long long* numel, float one_minus_decay);
 /* Attention backward, unfused first version (autograd through ldm CrossAttention.forward, attention.py:52-72:
  * sim = einsum(q, k) * scale; attn = sim.softmax(-1); out = einsum(attn, v)).  The scores are materialised per (sample, head):

@@ -48,6 +48,13 @@ class LinearRowsForm(C.Structure):
 LINEAR_ROWS_REFUSED, LINEAR_ROWS_SGEMM, LINEAR_ROWS_MGEMM, LINEAR_ROWS_TILED = range(4)
 
 
+class WgradForm(C.Structure):
+    _fields_ = [("path", C.c_int), ("Z", C.c_int), ("per_plane", C.c_int), ("remap", C.c_int)]
+
+
+WGRAD_PATHS = (None, "conv9<4>", "conv9<5>", "conv9<6>", "tn9", "tn1", "conv_fallback", "linear_fallback")
+
+
 class ClipCfg(C.Structure):
     _fields_ = [("embed_dim", C.c_int), ("image_resolution", C.c_int), ("vision_layers", C.c_int),
                 ("vision_width", C.c_int), ("vision_patch_size", C.c_int), ("context_length", C.c_int),
@@ -188,7 +195,7 @@ SIGNATURES = {
     "rdm_op_ema": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_float]),
     "rdm_op_silu": (C.c_int, [_P, _P, _P, _P, C.c_longlong]),
     "rdm_op_sumpool2": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
-    "rdm_op_adamw": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "rdm_op_adamw": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_longlong, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]),
     "rdm_op_attention_bwd": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
     "rdm_op_bmm": (C.c_int, [_P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "rdm_op_heads": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -209,6 +216,7 @@ SIGNATURES = {
     "rdm_op_rarm_nll": (C.c_int, [_P, _P, C.c_longlong, C.c_int, _P, _P]),
     "rdm_linear_rows_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.POINTER(LinearRowsForm)]),
     "rdm_op_linear_rows": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
+    "rdm_wgrad_select": (C.c_int, [C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_longlong, C.c_int, C.POINTER(WgradForm)]),
     "rdm_op_rarm_decode_attention": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_longlong, C.c_int, C.c_int, C.c_float, _P,
                                                C.c_int, C.c_int, C.c_int]),
     "rdm_op_rarm_xattn_decode": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, _P]),
@@ -219,7 +227,7 @@ SIGNATURES = {
     "rdm_op_embedding_grad": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_small_attention": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.c_float, _P, C.c_int]),
-    "rdm_op_adamw_multi": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int]),
+    "rdm_op_adamw_multi": (C.c_int, [_P, C.c_int, _P, _P, _P, _P, _P, _P, C.c_double, C.c_double, C.c_double, C.c_double, C.c_double, C.c_int]),
     "rdm_op_ema_multi": (C.c_int, [_P, C.c_int, _P, _P, _P, C.c_float]),
     "rdm_op_small_attention_bwd": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, _P, _P, _P]),
 }
@@ -250,6 +258,24 @@ def linear_rows_select(M, N, K, act=ACT_NONE, ln=False, deterministic=False):
     if f.kernel == LINEAR_ROWS_SGEMM:
         return ("sgemm", f.ma, f.nb, f.u, f.nw, bool(f.ln), bool(f.geglu))
     return (("refused", "sgemm", "mgemm", "tiled")[f.kernel],)
+
+
+def wgrad_select(*shape):
+    """The kernel Context.op_conv3x3_wgrad (shape = (B, H, W, C, N)) or Context.op_linear_wgrad (shape = (M, N, K)) launches (host only, no
+    device): (path, Z, per_plane, remap) with path one of WGRAD_PATHS -- "conv9<4|5|6>" the nine-tap kernel at width 16 / 32 / 64, "tn9" /
+    "tn1" the per-tap kernel, the two transposed-copy fallbacks; Z planes of per_plane chunks / rows / K' positions; remap as in rdm_hip.h."""
+    f = WgradForm()
+    if len(shape) == 5:
+        B, H, W, Cc, N = (int(v) for v in shape)
+        rc = lib.rdm_wgrad_select(1, B, H, W, Cc, N, 0, 0, C.byref(f))
+    elif len(shape) == 3:
+        M, N, K = (int(v) for v in shape)
+        rc = lib.rdm_wgrad_select(0, 0, 0, 0, 0, N, M, K, C.byref(f))
+    else:
+        raise RdmError(f"wgrad_select takes (B, H, W, C, N) or (M, N, K), got {shape}")
+    if rc != 0:
+        raise RdmError(f"rdm_wgrad_select{shape} failed ({rc})")
+    return (WGRAD_PATHS[f.path], f.Z, f.per_plane, f.remap)
 
 
 def _ptr(t):

@@ -223,7 +223,7 @@ hipError_t launch_conv_wgrad(const bf16_t* x, const bf16_t* dy, float* dw, int B
 // ---- Linear weight gradient dW [N][K] = dy^T a: the reduction runs over the M rows, the output is tiny -- as ONE GEMM it is 6 tiles on
 // 256 CUs walking K' = M serially (0.2 ms each, a third of the training step).  Like the conv wgrad: row-major transposes dy^T [N][Mp],
 // a^T [K][Mp] (zero padded), Z K-chunks as a batched launch of fp32 planes, fixed-order sum.
-static void linear_wgrad_geom(long long M, int* pZ, long long* pKc) {
+void linear_wgrad_geom(long long M, int* pZ, long long* pKc) {
     int Z = (int)((M + 1023) / 1024); if (Z < 1) Z = 1; if (Z > 128) Z = 128;
     long long Kc = (M + Z - 1) / Z; Kc = (Kc + 63) & ~63LL;
     *pZ = Z; *pKc = Kc;
@@ -801,27 +801,33 @@ hipError_t launch_softmax_bwd(const bf16_t* P, const float* dP, bf16_t* dS, long
 // ---- AdamW step (torch.optim.AdamW semantics, decoupled weight decay, bias correction; ldm configure_optimizers in
 // rdm/models/diffusion/ddpm.py uses torch.optim.AdamW(params, lr)): fp32 master parameters and moments updated in place, optional
 // bf16 working copy of the new parameters for the next forward.
-__device__ __forceinline__ float adamw_elem(float pi, float gi, float& mi, float& vi, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2) {
-    pi = pi * (1.f - lr * wd);
-    mi = __fmaf_rn(b1, mi, (1.f - b1) * gi);
-    vi = __fmaf_rn(b2, vi, (1.f - b2) * gi * gi);
-    return pi - (lr / bc1) * mi / (sqrtf(vi) / sqrtf(bc2) + eps);
+// The differences 1 - beta and 1 - beta^step cancel (1 - 0.999f is 1.3e-5 short of 1e-3, and so was exp_avg_sq after the first step when they
+// were taken in fp32 from fp32 betas): adamw_consts takes them in double from the caller's doubles and rounds each once.
+struct AdamwConsts { float lr, b1, b2, omb1, omb2, eps, wd, bc1, bc2; };
+static AdamwConsts adamw_consts(double lr, double b1, double b2, double eps, double wd, int step) {
+    return AdamwConsts{(float)lr, (float)b1, (float)b2, (float)(1.0 - b1), (float)(1.0 - b2), (float)eps, (float)wd, (float)(1.0 - pow(b1, (double)step)),
+                       (float)(1.0 - pow(b2, (double)step))};
+}
+__device__ __forceinline__ float adamw_elem(float pi, float gi, float& mi, float& vi, const AdamwConsts& k) {
+    pi = pi * (1.f - k.lr * k.wd);
+    mi = __fmaf_rn(k.b1, mi, k.omb1 * gi);
+    vi = __fmaf_rn(k.b2, vi, k.omb2 * gi * gi);
+    return pi - (k.lr / k.bc1) * mi / (sqrtf(vi) / sqrtf(k.bc2) + k.eps);
 }
 __global__ __launch_bounds__(256) void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
-                                                    bf16_t* __restrict__ pb, long long n, float lr, float b1, float b2, float eps, float wd, float bc1, float bc2) {
+                                                    bf16_t* __restrict__ pb, long long n, AdamwConsts k) {
     for (long long i = (long long)blockIdx.x * 256 + threadIdx.x; i < n; i += (long long)gridDim.x * 256) {
         float mi = m[i], vi = v[i];
-        const float pi = adamw_elem(p[i], g[i], mi, vi, lr, b1, b2, eps, wd, bc1, bc2);
+        const float pi = adamw_elem(p[i], g[i], mi, vi, k);
         m[i] = mi; v[i] = vi; p[i] = pi;
         if (pb) pb[i] = f2bf(pi);
     }
 }
-hipError_t launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* pb, long long n, float lr, float b1, float b2, float eps, float wd, int step,
+hipError_t launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* pb, long long n, double lr, double b1, double b2, double eps, double wd, int step,
                         hipStream_t st) {
     if (step < 1) return hipErrorInvalidValue;
     long long grid = (n + 255) / 256; if (grid > 16384) grid = 16384; if (grid < 1) grid = 1;
-    const float bc1 = 1.f - powf(b1, (float)step), bc2 = 1.f - powf(b2, (float)step);
-    adamw_kernel<<<dim3((unsigned)grid), 256, 0, st>>>(p, g, m, v, pb, n, lr, b1, b2, eps, wd, bc1, bc2);
+    adamw_kernel<<<dim3((unsigned)grid), 256, 0, st>>>(p, g, m, v, pb, n, adamw_consts(lr, b1, b2, eps, wd, step));
     return hipGetLastError();
 }
 
@@ -831,7 +837,7 @@ hipError_t launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* pb
 struct MultiTensorArgs {
     int n, ema; int blk[49];
     float* p[48]; const float* g[48]; float* m[48]; float* v[48]; bf16_t* pb[48]; long long numel[48];
-    float lr, b1, b2, eps, wd, bc1, bc2, omd;
+    AdamwConsts k; float omd;
 };
 __global__ __launch_bounds__(256) void multi_tensor_kernel(MultiTensorArgs a) {
     int t = 0;
@@ -849,7 +855,7 @@ __global__ __launch_bounds__(256) void multi_tensor_kernel(MultiTensorArgs a) {
         const long long i = base + u * 256 + threadIdx.x;
         if (i < n) {
             float mi = m[i], vi = v[i];
-            const float pi = adamw_elem(p[i], g[i], mi, vi, a.lr, a.b1, a.b2, a.eps, a.wd, a.bc1, a.bc2);
+            const float pi = adamw_elem(p[i], g[i], mi, vi, a.k);
             m[i] = mi; v[i] = vi; p[i] = pi;
             if (pb) pb[i] = f2bf(pi);
         }
@@ -857,11 +863,11 @@ __global__ __launch_bounds__(256) void multi_tensor_kernel(MultiTensorArgs a) {
 }
 // host arrays of n pointers / element counts; ema: p = shadows, g = parameters, m / v / pb unused (may be null)
 hipError_t launch_multi_tensor(int n, float* const* p, const float* const* g, float* const* m, float* const* v, void* const* pb, const long long* numel, int ema,
-                               float lr, float b1, float b2, float eps, float wd, int step, float omd, hipStream_t st) {
+                               double lr, double b1, double b2, double eps, double wd, int step, float omd, hipStream_t st) {
     if (!ema && step < 1) return hipErrorInvalidValue;
     MultiTensorArgs a{};
-    a.ema = ema; a.lr = lr; a.b1 = b1; a.b2 = b2; a.eps = eps; a.wd = wd; a.omd = omd;
-    a.bc1 = ema ? 1.f : 1.f - powf(b1, (float)step); a.bc2 = ema ? 1.f : 1.f - powf(b2, (float)step);
+    a.ema = ema; a.omd = omd;
+    if (!ema) a.k = adamw_consts(lr, b1, b2, eps, wd, step);
     int i = 0;
     while (i < n) {
         int k = 0; long long blocks = 0;

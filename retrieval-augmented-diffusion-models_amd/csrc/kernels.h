@@ -1,6 +1,7 @@
 // Internal kernel-launch interface of librdm_hip (host side). All launches are asynchronous on `st`.
 #pragma once
 #include "common.h"
+#include "../../include/rdm_hip.h"
 
 struct GnParams {
     const bf16_t* x0; const bf16_t* x1;   // [B, HW, C0], [B, HW, C1] (x1 may be null)
@@ -238,7 +239,14 @@ bool wgrad_tn_supported(long long M, int N, int K, int lda, int ldb);
 bool conv_wgrad_tn_supported(int B, int H, int W, int C, int N);
 size_t wgrad_tn_scratch_bytes(long long M, int N, int K, int taps);
 size_t conv_wgrad_tn_scratch_bytes(int B, int H, int W, int C, int N);
-hipError_t launch_wgrad_tn(const bf16_t* dy, int lda, const bf16_t* x, int ldb, float* dw, long long M, int N, int K, int taps, int H, int W, char* scratch,
+// which kernel takes a weight gradient and its split (wgrad.hip): the public rdm_wgrad_form of rdm_hip.h (path = RDM_WGRAD_*, Z planes of per_plane
+// chunks / rows / K' positions each, remap); *_args_ok: the shapes rdm_op_conv3x3_wgrad / rdm_op_linear_wgrad and rdm_wgrad_select accept
+bool conv_wgrad_args_ok(int B, int H, int W, int C, int N);
+bool linear_wgrad_args_ok(long long M, int N, int K);
+rdm_wgrad_form conv_wgrad_plan(int B, int H, int W, int C, int N);
+rdm_wgrad_form linear_wgrad_plan(long long M, int N, int K);
+void linear_wgrad_geom(long long M, int* Z, long long* Kc);
+hipError_t launch_wgrad_tn(const bf16_t* dy, const bf16_t* x, float* dw, long long M, int N, int K, int taps, int H, int W, char* scratch,
                            const void* zero_page, hipStream_t st);
 hipError_t launch_linear_wgrad(const bf16_t* dy, const bf16_t* a, float* dw, long long M, int N, int K, char* scratch, const void* zero_page, hipStream_t st);
 size_t groupnorm_bwd_scratch_bytes(int B, int HW, int C, int groups);
@@ -265,8 +273,8 @@ hipError_t launch_timestep_embedding(const long long* t, bf16_t* out, int B, int
 hipError_t launch_cast_f32_bf16(const float* x, bf16_t* y, long long n, hipStream_t st);
 hipError_t launch_transpose_bf16(const bf16_t* x, bf16_t* y, int rows, int cols, hipStream_t st, int batch = 1, int ldy = 0);       // y[c][r] = x[r][c] (batch contiguous matrices)
 hipError_t launch_multi_tensor(int n, float* const* p, const float* const* g, float* const* m, float* const* v, void* const* pb, const long long* numel, int ema,
-                               float lr, float b1, float b2, float eps, float wd, int step, float omd, hipStream_t st);      // AdamW / LitEma over a list of tensors, 48 per launch
-hipError_t launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* pb, long long n, float lr, float b1, float b2, float eps, float wd, int step,
+                               double lr, double b1, double b2, double eps, double wd, int step, float omd, hipStream_t st);      // AdamW / LitEma over a list of tensors, 48 per launch
+hipError_t launch_adamw(float* p, const float* g, float* m, float* v, bf16_t* pb, long long n, double lr, double b1, double b2, double eps, double wd, int step,
                         hipStream_t st);
 hipError_t launch_ema(float* shadow, const float* p, long long n, float one_minus_decay, hipStream_t st);
 hipError_t launch_silu(const float* x, const float* dy, bf16_t* ob, float* of, long long n, hipStream_t st);

@@ -2847,10 +2847,10 @@ int rdm_op_conv3x3_dgrad(rdm_ctx* c, const void* dy, const void* w, void* dx, in
 }
 int rdm_op_conv3x3_wgrad(rdm_ctx* c, const void* x, const void* dy, float* dw, int B, int H, int W, int C, int N) {
     RDM_ENTER(c);
-    if (!x || !dy || !dw || C % 2 || N < 1) return c->fail(-1, "rdm_op_conv3x3_wgrad: bad arguments");
-    if (conv_wgrad_tn_supported(B, H, W, C, N)) {
+    if (!x || !dy || !dw || !conv_wgrad_args_ok(B, H, W, C, N)) return c->fail(-1, "rdm_op_conv3x3_wgrad: bad arguments (B, H, W, N >= 1, C even)");
+    if (conv_wgrad_plan(B, H, W, C, N).path != RDM_WGRAD_CONV_FALLBACK) {
         RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, conv_wgrad_tn_scratch_bytes(B, H, W, C, N) + 256));
-        RDM_CHECK_HIP(c, launch_wgrad_tn((const bf16_t*)dy, N, (const bf16_t*)x, C, dw, (long long)B * H * W, N, C, 9, H, W, c->bwd_tmp, c->zero_page, c->stream));
+        RDM_CHECK_HIP(c, launch_wgrad_tn((const bf16_t*)dy, (const bf16_t*)x, dw, (long long)B * H * W, N, C, 9, H, W, c->bwd_tmp, c->zero_page, c->stream));
         return 0;
     }
     const size_t need = conv_wgrad_scratch_bytes(B, H, W, C, N, nullptr, nullptr, nullptr, nullptr, nullptr);
@@ -2886,14 +2886,22 @@ int rdm_op_layernorm_bwd(rdm_ctx* c, const void* x, const void* dy, const float*
 }
 int rdm_op_linear_wgrad(rdm_ctx* c, const void* dy, const void* a, float* dw, long long M, int N, int K) {
     RDM_ENTER(c);
-    if (!dy || !a || !dw || M < 1 || M > 0x7fffffffLL || N < 2 || K < 2 || N % 2 || K % 2) return c->fail(-1, "rdm_op_linear_wgrad: bad argument (N, K even)");
-    if (wgrad_tn_supported(M, N, K, N, K)) {
+    if (!dy || !a || !dw || !linear_wgrad_args_ok(M, N, K)) return c->fail(-1, "rdm_op_linear_wgrad: bad argument (N, K even)");
+    if (linear_wgrad_plan(M, N, K).path != RDM_WGRAD_LINEAR_FALLBACK) {
         RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, wgrad_tn_scratch_bytes(M, N, K, 1) + 256));
-        RDM_CHECK_HIP(c, launch_wgrad_tn((const bf16_t*)dy, N, (const bf16_t*)a, K, dw, M, N, K, 1, 1, 1, c->bwd_tmp, c->zero_page, c->stream));
+        RDM_CHECK_HIP(c, launch_wgrad_tn((const bf16_t*)dy, (const bf16_t*)a, dw, M, N, K, 1, 1, 1, c->bwd_tmp, c->zero_page, c->stream));
         return 0;
     }
     RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, linear_wgrad_scratch_bytes(M, N, K)));
     RDM_CHECK_HIP(c, launch_linear_wgrad((const bf16_t*)dy, (const bf16_t*)a, dw, M, N, K, c->bwd_tmp, c->zero_page, c->stream));
+    return 0;
+}
+// host only: the plan the two entry points above dispatch on, behind the shape checks they make
+int rdm_wgrad_select(int conv, int B, int H, int W, int C, int N, long long M, int K, rdm_wgrad_form* out) {
+    if (!out) return -1;
+    *out = rdm_wgrad_form{};
+    if (conv ? !conv_wgrad_args_ok(B, H, W, C, N) : !linear_wgrad_args_ok(M, N, K)) return -1;
+    *out = conv ? conv_wgrad_plan(B, H, W, C, N) : linear_wgrad_plan(M, N, K);
     return 0;
 }
 int rdm_op_colsum(rdm_ctx* c, const void* x, float* out, long long M, int N) {
@@ -3001,15 +3009,15 @@ int rdm_op_sumpool2(rdm_ctx* c, const void* x, void* out, int B, int H, int W, i
     RDM_CHECK_HIP(c, launch_sumpool2((const bf16_t*)x, (bf16_t*)out, B, H, W, C, c->stream));
     return 0;
 }
-int rdm_op_adamw(rdm_ctx* c, float* p, const float* g, float* m, float* v, void* p_bf16, long long n, float lr, float beta1, float beta2, float eps,
-                 float weight_decay, int step) {
+int rdm_op_adamw(rdm_ctx* c, float* p, const float* g, float* m, float* v, void* p_bf16, long long n, double lr, double beta1, double beta2, double eps,
+                 double weight_decay, int step) {
     RDM_ENTER(c);
     if (!p || !g || !m || !v || n < 1 || step < 1) return c->fail(-1, "rdm_op_adamw: bad argument");
     RDM_CHECK_HIP(c, launch_adamw(p, g, m, v, (bf16_t*)p_bf16, n, lr, beta1, beta2, eps, weight_decay, step, c->stream));
     return 0;
 }
 int rdm_op_adamw_multi(rdm_ctx* c, int n, float* const* p, const float* const* g, float* const* m, float* const* v, void* const* p_bf16, const long long* numel,
-                       float lr, float beta1, float beta2, float eps, float weight_decay, int step) {
+                       double lr, double beta1, double beta2, double eps, double weight_decay, int step) {
     RDM_ENTER(c);
     if (n < 1 || !p || !g || !m || !v || !numel || step < 1) return c->fail(-1, "rdm_op_adamw_multi: bad argument");
     for (int i = 0; i < n; i++) if (!p[i] || !g[i] || !m[i] || !v[i] || numel[i] < 1) return c->fail(-1, "rdm_op_adamw_multi: null tensor in the list");
@@ -3020,7 +3028,7 @@ int rdm_op_ema_multi(rdm_ctx* c, int n, float* const* shadow, const float* const
     RDM_ENTER(c);
     if (n < 1 || !shadow || !param || !numel) return c->fail(-1, "rdm_op_ema_multi: bad argument");
     for (int i = 0; i < n; i++) if (!shadow[i] || !param[i] || numel[i] < 1) return c->fail(-1, "rdm_op_ema_multi: null tensor in the list");
-    RDM_CHECK_HIP(c, launch_multi_tensor(n, shadow, param, nullptr, nullptr, nullptr, numel, 1, 0.f, 0.f, 0.f, 0.f, 0.f, 1, one_minus_decay, c->stream));
+    RDM_CHECK_HIP(c, launch_multi_tensor(n, shadow, param, nullptr, nullptr, nullptr, numel, 1, 0.0, 0.0, 0.0, 0.0, 0.0, 1, one_minus_decay, c->stream));
     return 0;
 }
 int rdm_op_attention_bwd(rdm_ctx* c, const void* q, const void* k, const void* v, const void* o, const void* dout, int B, int n, int m, int heads,

@@ -277,8 +277,11 @@ template <int LW> constexpr int conv9_lds_bytes() {
 
 namespace {
 
+// 192 x 192 output tiles of the per-tap kernel
+int tn_tiles_n(int N) { return (N + 191) / 192; }
+long long tn_tiles(int N, int K) { return (long long)tn_tiles_n(N) * ((K + 191) / 192); }
 void wgrad_geom(long long M, int N, int K, int taps, int* pZ, int* pmz) {
-    const long long tiles = (long long)((N + 191) / 192) * ((K + 191) / 192);
+    const long long tiles = tn_tiles(N, K);
     long long Z = 512 / (tiles * taps);                    // one round of blocks at two per CU
     if (Z > M / 256) Z = M / 256;
     const long long plane = (long long)N * taps * K * 4;
@@ -342,8 +345,39 @@ static hipError_t launch_conv9(WgradParams& p, int Z, hipStream_t st) {
     wgrad_conv9_kernel<LW><<<dim3((unsigned)(p.tiles * Z)), 256, conv9_lds_bytes<LW>(), st>>>(p);
     return hipGetLastError();
 }
-// dw [N][taps][K] fp32.  taps = 1: a = dY [M][N] (row stride lda), b = X [M][K] (row stride ldb).  taps = 9: M = B H W pixels of [B][H][W] images.
-hipError_t launch_wgrad_tn(const bf16_t* dy, int lda, const bf16_t* x, int ldb, float* dw, long long M, int N, int K, int taps, int H, int W, char* scratch,
+// The one rule of which kernel takes a weight gradient, and with what split: the op entry points (model.hip), launch_wgrad_tn below and
+// rdm_wgrad_select (which reports it) all ask these two.  per_plane: image-row chunks (nine-tap kernel), rows m (per-tap / one-tap kernel) or
+// K' positions (fallbacks) of one Z plane; remap: the nine-tap kernel's count of XCD-dealt planes (Z & ~7), the per-tap kernel's flag.
+bool conv_wgrad_args_ok(int B, int H, int W, int C, int N) {
+    return B >= 1 && H >= 1 && W >= 1 && C >= 2 && C % 2 == 0 && N >= 1 && (long long)B * H * W <= 0x7fffffffLL;
+}
+bool linear_wgrad_args_ok(long long M, int N, int K) { return M >= 1 && M <= 0x7fffffffLL && N >= 2 && K >= 2 && N % 2 == 0 && K % 2 == 0; }
+// the per-tap kernel's plan: the blocks of a (tile, plane) share an XCD when tiles * Z is a multiple of 8
+static rdm_wgrad_form tn_plan(int path, long long M, int N, int K, int taps) {
+    int Z, mz; wgrad_geom(M, N, K, taps, &Z, &mz);
+    return rdm_wgrad_form{path, Z, mz, (tn_tiles(N, K) * Z) % 8 == 0};
+}
+rdm_wgrad_form conv_wgrad_plan(int B, int H, int W, int C, int N) {
+    if (!conv_wgrad_tn_supported(B, H, W, C, N)) {
+        int Kc, Z; conv_wgrad_scratch_bytes(B, H, W, C, N, nullptr, nullptr, &Kc, &Z, nullptr);
+        return rdm_wgrad_form{RDM_WGRAD_CONV_FALLBACK, Z, Kc, 0};
+    }
+    if (conv9_ok(B, H, W, C, N)) {
+        int Z, cz; conv9_geom(B, H, W, C, N, &Z, &cz);
+        return rdm_wgrad_form{W == 64 ? RDM_WGRAD_CONV9_LW6 : W == 32 ? RDM_WGRAD_CONV9_LW5 : RDM_WGRAD_CONV9_LW4, Z, cz, Z & ~7};
+    }
+    return tn_plan(RDM_WGRAD_TN9, (long long)B * H * W, N, C, 9);
+}
+rdm_wgrad_form linear_wgrad_plan(long long M, int N, int K) {
+    if (!wgrad_tn_supported(M, N, K, N, K)) {
+        int Z; long long Kc; linear_wgrad_geom(M, &Z, &Kc);
+        return rdm_wgrad_form{RDM_WGRAD_LINEAR_FALLBACK, Z, (int)Kc, 0};
+    }
+    return tn_plan(RDM_WGRAD_TN1, M, N, K, 1);
+}
+// dw [N][taps][K] fp32 for contiguous operands: taps = 1: a = dY [M][N], b = X [M][K].  taps = 9: M = B H W pixels of [B][H][W] images.  The shape must be one
+// the transpose-free kernels take (conv_wgrad_plan / linear_wgrad_plan name one of them); anything else is refused, never rerouted.
+hipError_t launch_wgrad_tn(const bf16_t* dy, const bf16_t* x, float* dw, long long M, int N, int K, int taps, int H, int W, char* scratch,
                            const void* zero_page, hipStream_t st) {
     static bool attr[RDM_MAX_DEVICES] = {false};
     const int dev = rdm_cur_device();
@@ -352,28 +386,29 @@ hipError_t launch_wgrad_tn(const bf16_t* dy, int lda, const bf16_t* x, int ldb, 
         if (e != hipSuccess) return e;
         attr[dev] = true;
     }
-    int Z, mz; wgrad_geom(M, N, K, taps, &Z, &mz);
+    const rdm_wgrad_form pl = taps == 9 ? conv_wgrad_plan((int)(M / ((long long)H * W)), H, W, K, N) : linear_wgrad_plan(M, N, K);
+    const int Z = pl.Z;
     WgradParams p{};
-    if (taps == 9 && lda == N && ldb == K && conv9_ok((int)(M / ((long long)H * W)), H, W, K, N)) {
-        int cz; conv9_geom((int)(M / ((long long)H * W)), H, W, K, N, &Z, &cz);
-        p.a = dy; p.lda = lda; p.b = x; p.ldb = ldb; p.plane = (long long)N * 9 * K; p.ldo = 9 * K; p.tap_stride = K;
+    if (pl.path == RDM_WGRAD_CONV9_LW4 || pl.path == RDM_WGRAD_CONV9_LW5 || pl.path == RDM_WGRAD_CONV9_LW6) {
+        p.a = dy; p.lda = N; p.b = x; p.ldb = K; p.plane = (long long)N * 9 * K; p.ldo = 9 * K; p.tap_stride = K;
         p.out = Z > 1 ? (float*)scratch : dw;
-        p.M = (int)M; p.N = N; p.K = K; p.mz = cz; p.taps = 9; p.tiles_n = N / 64; p.tiles = p.tiles_n * (K / 64);
+        p.M = (int)M; p.N = N; p.K = K; p.mz = pl.per_plane; p.taps = 9; p.tiles_n = N / 64; p.tiles = p.tiles_n * (K / 64);
         while ((1 << p.lw) < W) p.lw++; while ((1 << p.lh) < H) p.lh++;
-        p.zero_page = zero_page; p.remap = Z & ~7;
-        hipError_t e = W == 64 ? launch_conv9<6>(p, Z, st) : W == 32 ? launch_conv9<5>(p, Z, st) : launch_conv9<4>(p, Z, st);
+        p.zero_page = zero_page; p.remap = pl.remap;
+        hipError_t e = pl.path == RDM_WGRAD_CONV9_LW6 ? launch_conv9<6>(p, Z, st) : pl.path == RDM_WGRAD_CONV9_LW5 ? launch_conv9<5>(p, Z, st) : launch_conv9<4>(p, Z, st);
         if (e != hipSuccess) return e;
         return Z > 1 ? launch_reduce_planes((const float*)scratch, dw, (long long)N * 9 * K, Z, st) : hipSuccess;
     }
-    p.a = dy; p.lda = lda; p.b = x; p.ldb = ldb;
+    if (pl.path != (taps == 9 ? RDM_WGRAD_TN9 : RDM_WGRAD_TN1)) return hipErrorInvalidValue;
+    p.a = dy; p.lda = N; p.b = x; p.ldb = K;
     p.plane = (long long)N * taps * K; p.ldo = taps * K; p.tap_stride = K;
     p.out = Z > 1 ? (float*)scratch : dw;
-    p.M = (int)M; p.N = N; p.K = K; p.mz = mz; p.taps = taps;
-    p.tiles_n = (N + 191) / 192; p.tiles = p.tiles_n * ((K + 191) / 192);
+    p.M = (int)M; p.N = N; p.K = K; p.mz = pl.per_plane; p.taps = taps;
+    p.tiles_n = tn_tiles_n(N); p.tiles = (int)tn_tiles(N, K);
     p.lw = 0; p.lh = 0;
     if (taps == 9) { while ((1 << p.lw) < W) p.lw++; while ((1 << p.lh) < H) p.lh++; }
     p.zero_page = zero_page;
-    p.remap = ((long long)p.tiles * Z) % 8 == 0;
+    p.remap = pl.remap;
     wgrad_tn_kernel<<<dim3((unsigned)(p.tiles * Z * taps)), 256, WG_LDS, st>>>(p);
     hipError_t e = hipGetLastError(); if (e != hipSuccess) return e;
     return Z > 1 ? launch_reduce_planes((const float*)scratch, dw, (long long)N * taps * K, Z, st) : hipSuccess;

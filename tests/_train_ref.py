@@ -820,13 +820,320 @@ class SmallAttentionBwd(_AttnBase):
         return [("scale applied twice", SmallAttentionBwd.ref(inp, F64, inp["scale"])), ("head order reversed", _AttnBase.reverse_heads(r, inp["H"]))]
 
 
+# ============================================================================================================ optimizer, EMA, loss-side glue
+def bc_rel_error(beta, step, fp32):
+    """relative error of the bias correction 1 - beta^step as the kernel receives it.  Taken in double on the host and rounded once to
+    fp32: u.  Taken in fp32 from an fp32 beta (1.f - powf(b, step)): beta itself is off by up to 2^-25 (half an ulp below 1), which
+    beta^step carries as step beta^(step-1) 2^-25; powf adds 2 ulp of beta^step, the subtraction one rounding -- all divided by the small
+    difference 1 - beta^step (the cancellation: 2^-25 / 1e-3 = 3e-5 at beta 0.999, step 1)."""
+    bc = 1.0 - beta ** step
+    if not fp32:
+        return U
+    return (step * beta ** (step - 1) * 2.0 ** -25 + 4 * U * beta ** step) / bc + U
+
+
+class AdamW:
+    """One AdamW step (rdm_op_adamw, rdm_op_adamw_multi): torch.optim.AdamW's update written out in fp64 with the betas, lr, eps and weight
+    decay as the Python doubles the caller wrote:
+        p1 = p (1 - lr wd);  m' = b1 m + (1 - b1) g;  v' = b2 v + (1 - b2) g^2;  p' = p1 - (lr / bc1) m' / (sqrt(v') / sqrt(bc2) + eps),
+    bc_i = 1 - b_i^step.  Outputs p, m, v (fp32) and the bf16 copy pb.  Bounds (u = 2^-24, tiny = 2^-126 for a flushed subnormal):
+      m: a_m = u (|m'| + |b1 m| + 2 |(1 - b1) g|) + tiny: the fma's rounding, b1 and 1 - b1 as fp32 numbers, the product (1 - b1) g;
+      v: a_v = u (|v'| + |b2 v| + 3 |(1 - b2) g^2|) + tiny (two products);
+      p: R = sqrt(v') / sqrt(bc2), D = R + eps, T = (lr / bc1) m' / D:
+         e_D = R (a_v / v' + 3 u + e_bc2 / 2) + u eps + u D      (|sqrt(1 + d) - 1| <= |d|; sqrtf, sqrtf, the division; eps as fp32; the add)
+         e_T = |T| (5 u + e_bc1 + e_D / (D - e_D)) + (lr / bc1) a_m / (D - e_D)    (lr, bc1, lr / bc1, the product, the division)
+         a_p = u (2 |p1| + 3 lr wd |p|) + e_T + u |p'|
+         with e_bc1, e_bc2 = bc_rel_error: THE EXPLICIT TERM of the bias corrections (u when they are taken in double on the host);
+      pb: r = 2^-8, a = a_p.
+    Elements 0..3 have g = 0 and v = 0 (the denominator is eps), 4..7 also carry a moment m != 0 (steps > 1), 8..11 a tiny v = 1e-30 with
+    g = 1e-14 and p = 0 (so are all elements of a tensor shorter than 12).  Near misses: eps inside the square root; no bias correction (steps <= 2); the decay added to the gradient
+    (Adam with L2, not AdamW; wd > 0)."""
+    name = "adamw"
+    exact = False
+    BC_FP32 = False                                       # the library takes both corrections in double on the host
+    LR, EPS = 1e-3, 1e-8
+
+    @staticmethod
+    def _one(n, step, seed):
+        g_ = torch.Generator().manual_seed(seed)
+        p = torch.randn(n, generator=g_); g = torch.randn(n, generator=g_) * 0.3
+        if step == 1:
+            m, v = torch.zeros(n), torch.zeros(n)
+        else:
+            m = torch.randn(n, generator=g_) * 0.1; v = (torch.randn(n, generator=g_) * 0.3) ** 2
+        if n >= 12:
+            g[:8] = 0; v[:8] = 0; m[:4] = 0
+            g[8:12] = 1e-14; p[8:12] = 0
+            if step > 1:
+                v[8:12] = 1e-30; m[8:12] = 1e-15
+        else:                                                # a tensor of a few elements: all of the tiny kind
+            g[:] = 1e-14; p[:] = 0
+            if step > 1:
+                v[:] = 1e-30; m[:] = 1e-15
+        return p, g, m, v
+
+    @staticmethod
+    def make(sizes, step, betas, wd, seed=18):
+        parts = [AdamW._one(n, step, seed + 7 * i) for i, n in enumerate(sizes)]
+        p, g, m, v = (torch.cat([q[j] for q in parts]) for j in range(4))
+        return {"p": p, "g": g, "m": m, "v": v, "sizes": list(sizes), "step": step, "betas": betas, "wd": wd, "lr": AdamW.LR, "eps": AdamW.EPS}
+
+    @staticmethod
+    def ref(inp, dt, eps_inside=False, no_bc=False, l2=False):
+        p, g, m, v = (inp[k].to(dt) for k in "pgmv")
+        (b1, b2), t, lr, eps, wd = inp["betas"], inp["step"], inp["lr"], inp["eps"], inp["wd"]
+        bc1, bc2 = (1.0, 1.0) if no_bc else (1 - b1 ** t, 1 - b2 ** t)
+        if l2:
+            g = g + wd * p; p1 = p
+        else:
+            p1 = p * (1 - lr * wd)
+        if dt == torch.float32:                            # the stand-in: the kernel's fused multiply-add (one rounding), betas as fp32 numbers
+            fma = lambda b, x, y: (float(torch.tensor(b, dtype=dt)) * x.double() + y.double()).to(dt)
+            m1 = fma(b1, m, (1 - b1) * g)
+            v1 = fma(b2, v, (1 - b2) * g * g)
+        else:
+            m1 = b1 * m + (1 - b1) * g
+            v1 = b2 * v + (1 - b2) * g * g
+        den = torch.sqrt(v1 / bc2 + eps) if eps_inside else torch.sqrt(v1) / math.sqrt(bc2) + eps
+        p2 = p1 - (lr / bc1) * m1 / den
+        return {"p": p2, "m": m1, "v": v1, "pb": p2}
+
+    @staticmethod
+    def bound_terms(inp, fp32_bc):
+        """-> (a_m, a_v, a_p, the part of a_p that is the bc2 term)"""
+        p, g, m, v = (inp[k].double() for k in "pgmv")
+        (b1, b2), t, lr, eps, wd = inp["betas"], inp["step"], inp["lr"], inp["eps"], inp["wd"]
+        r = AdamW.ref(inp, F64)
+        tiny = 2.0 ** -126
+        a_m = U * (r["m"].abs() + (b1 * m).abs() + 2 * ((1 - b1) * g).abs()) + tiny
+        a_v = U * (r["v"].abs() + (b2 * v).abs() + 3 * ((1 - b2) * g * g).abs()) + tiny
+        bc1, bc2 = 1 - b1 ** t, 1 - b2 ** t
+        e1, e2 = bc_rel_error(b1, t, fp32_bc), bc_rel_error(b2, t, fp32_bc)
+        R = torch.sqrt(r["v"]) / math.sqrt(bc2); D = R + eps
+        dv = torch.where(r["v"] > 0, a_v / r["v"].clamp_min(1e-300), torch.zeros_like(R)).clamp(max=1.0)
+        e_D0 = R * (dv + 3 * U) + U * eps + U * D
+        e_D = e_D0 + R * e2 / 2
+        T = (lr / bc1) * r["m"] / D
+        e_T = T.abs() * (5 * U + e1 + e_D / (D - e_D)) + (lr / bc1) * a_m / (D - e_D)
+        p1 = p * (1 - lr * wd)
+        a_p = U * (2 * p1.abs() + 3 * lr * wd * p.abs()) + e_T + U * r["p"].abs()
+        return a_m, a_v, a_p, T.abs() * (R * e2 / 2) / (D - e_D)
+
+    @staticmethod
+    def bound(inp, ref):
+        a_m, a_v, a_p, _ = AdamW.bound_terms(inp, AdamW.BC_FP32)
+        return {"m": (0.0, a_m), "v": (0.0, a_v), "p": (0.0, a_p), "pb": (BF, a_p)}
+
+    @staticmethod
+    def misses(inp):
+        out = [("eps inside the square root", AdamW.ref(inp, F64, eps_inside=True))]
+        if inp["step"] <= 2:
+            out.append(("no bias correction", AdamW.ref(inp, F64, no_bc=True)))
+        if inp["wd"] > 0:
+            out.append(("decay added to the gradient", AdamW.ref(inp, F64, l2=True)))
+        return out
+
+
+class Ema:
+    """LitEma update s' = s - omd (s - p) on fp32 (rdm_op_ema, rdm_op_ema_multi): the difference, omd as an fp32 number, the product, the
+    final subtraction: a = u (|s'| + 3 |omd (s - p)|).  Near misses: the sign of the step flipped; decay and 1 - decay swapped."""
+    name = "ema"
+    exact = False
+
+    @staticmethod
+    def make(sizes, omd, seed=19):
+        g = torch.Generator().manual_seed(seed)
+        n = sum(sizes)
+        s = torch.randn(n, generator=g)
+        return {"s": s, "p": s + 0.05 * torch.randn(n, generator=g), "sizes": list(sizes), "omd": omd}
+
+    @staticmethod
+    def ref(inp, dt, omd=None, sign=1.0):
+        s, p = inp["s"].to(dt), inp["p"].to(dt)
+        return {"out": s - sign * (inp["omd"] if omd is None else omd) * (s - p)}
+
+    @staticmethod
+    def bound(inp, ref):
+        s, p = inp["s"].double(), inp["p"].double()
+        return {"out": (0.0, U * (ref["out"].abs() + 3 * (inp["omd"] * (s - p)).abs()))}
+
+    @staticmethod
+    def misses(inp):
+        return [("sign flipped", Ema.ref(inp, F64, sign=-1.0)), ("decay and 1 - decay swapped", Ema.ref(inp, F64, omd=1 - inp["omd"]))]
+
+
+class QSample:
+    """x_t = a[b] x0 + b[b] noise (rdm_op_q_sample), fp32 NCHW in; out fp32 NCHW and / or nhwc bf16 [B, H, W, cpad] whose channels >= C
+    are exactly zero.  Two products and an add: a = 2 u (|a x0| + |b noise|) (r = 2^-8 for nhwc; the zero padding has bound 0).  Near
+    misses: the coefficients of the next sample; the two coefficients swapped."""
+    name = "q_sample"
+    exact = False
+
+    @staticmethod
+    def make(B, C, H, W, cpad, nchw, seed=20):
+        g = torch.Generator().manual_seed(seed)
+        abar = 0.02 + 0.96 * torch.rand(B, generator=g)
+        return {"x0": torch.randn(B, C, H, W, generator=g), "noise": torch.randn(B, C, H, W, generator=g), "a": abar.sqrt(), "b": (1 - abar).sqrt(),
+                "cpad": cpad, "nchw": nchw}
+
+    @staticmethod
+    def _pack(inp, v):
+        out = {}
+        if inp["nchw"]:
+            out["out"] = v
+        if inp["cpad"]:
+            B, C, H, W = v.shape
+            z = torch.zeros(B, H, W, inp["cpad"], dtype=v.dtype)
+            z[..., :C] = v.permute(0, 2, 3, 1)
+            out["nhwc"] = z
+        return out
+
+    @staticmethod
+    def ref(inp, dt, roll=0, swap=False):
+        a, b = inp["a"].to(dt).roll(roll)[:, None, None, None], inp["b"].to(dt).roll(roll)[:, None, None, None]
+        if swap:
+            a, b = b, a
+        return QSample._pack(inp, a * inp["x0"].to(dt) + b * inp["noise"].to(dt))
+
+    @staticmethod
+    def bound(inp, ref):
+        a, b = inp["a"].double()[:, None, None, None], inp["b"].double()[:, None, None, None]
+        t = QSample._pack(inp, 2 * U * ((a * inp["x0"].double()).abs() + (b * inp["noise"].double()).abs()))
+        return {k: (BF if k == "nhwc" else 0.0, v) for k, v in t.items()}
+
+    @staticmethod
+    def misses(inp):
+        return [("coefficients of the next sample", QSample.ref(inp, F64, roll=-1)), ("coefficients swapped", QSample.ref(inp, F64, swap=True))]
+
+
+class MseLoss:
+    """se[b] = mean_{c, h, w} (eps - target)^2 and deps = coef[b] (eps - target) (rdm_op_mse_loss): eps / deps bf16 NHWC with row pitch
+    ldc >= C (the padding channels of eps hold garbage and are ignored, those of deps are exactly zero), target fp32 NCHW.  One block per
+    sample: a lane walks ceil(HW / 256) pixels x C channels, then the 256-lane tree (8 levels), then the division: se: a = (ceil(HW / 256)
+    C + 8 + 4) u se (all terms positive; + 4: the difference twice, the square, the division).  deps: r = 2^-8, a = 2 u |coef d|.
+    Near misses: the mean taken over ldc channels (ldc > C); the last pixel missing from se; the coefficient of the next sample."""
+    name = "mse_loss"
+    exact = False
+
+    @staticmethod
+    def make(B, C, H, W, ldc, deps, seed=21):
+        g = torch.Generator().manual_seed(seed)
+        return {"eps": bfr(torch.randn(B, H, W, ldc, generator=g)), "target": torch.randn(B, C, H, W, generator=g),
+                "coef": (0.5 + torch.rand(B, generator=g)) * 1e-2 if deps else None}
+
+    @staticmethod
+    def ref(inp, dt, div_ldc=False, drop_last=False, roll=0):
+        B, C, H, W = inp["target"].shape
+        ldc = inp["eps"].shape[3]
+        d = inp["eps"].to(dt)[..., :C] - inp["target"].to(dt).permute(0, 2, 3, 1)
+        sq = d * d
+        if drop_last:
+            sq = sq.clone(); sq[:, -1, -1] = 0
+        out = {"se": sq.sum((1, 2, 3)) / ((ldc if div_ldc else C) * H * W)}
+        if inp["coef"] is not None:
+            z = torch.zeros(B, H, W, ldc, dtype=dt)
+            z[..., :C] = inp["coef"].to(dt).roll(roll)[:, None, None, None] * d
+            out["deps"] = z
+        return out
+
+    @staticmethod
+    def bound(inp, ref):
+        B, C, H, W = inp["target"].shape
+        out = {"se": (0.0, (_cdiv(H * W, 256) * C + 12) * U * ref["se"].abs())}
+        if "deps" in ref:
+            out["deps"] = (BF, 2 * U * ref["deps"].abs())
+        return out
+
+    @staticmethod
+    def misses(inp):
+        m = [("last pixel missing from se", MseLoss.ref(inp, F64, drop_last=True))]
+        if inp["eps"].shape[3] > inp["target"].shape[1]:
+            m.append(("mean over ldc channels", MseLoss.ref(inp, F64, div_ldc=True)))
+        if inp["coef"] is not None:
+            m.append(("coefficient of the next sample", MseLoss.ref(inp, F64, roll=-1)))
+        return m
+
+
+class WhereRows:
+    """out[b, :] = mask[b] ? a[b, :] : x[b, :] (rdm_op_where_rows), bitwise.  Near misses: the mask inverted; the mask of the next row."""
+    name = "where_rows"
+    exact = True
+
+    @staticmethod
+    def make(rows, n, seed=22):
+        g = torch.Generator().manual_seed(seed)
+        mask = torch.rand(rows, generator=g) < 0.5
+        mask[0] = True
+        if rows > 1:
+            mask[1] = False
+        return {"mask": mask, "a": torch.randn(rows, n, generator=g), "x": torch.randn(rows, n, generator=g)}
+
+    @staticmethod
+    def ref(inp, dt, mask=None):
+        mk = inp["mask"] if mask is None else mask
+        return {"out": torch.where(mk[:, None], inp["a"].to(dt), inp["x"].to(dt))}
+
+    @staticmethod
+    def misses(inp):
+        return [("mask inverted", WhereRows.ref(inp, F64, ~inp["mask"])), ("mask of the next row", WhereRows.ref(inp, F64, inp["mask"].roll(-1)))]
+
+
+class TimestepEmbedding:
+    """ldm timestep_embedding (rdm_op_timestep_embedding): out bf16 [B, ld] = [cos(t f_j) | sin(t f_j) | zero tail], f_j = exp(-ln(1e4) j /
+    half), against fp64 cos | sin.  The columns dim .. ld - 1 are the documented zero tail (bound 0: exactly zero); `guard` is the row after
+    the last one, which the kernel must leave untouched (the test fills it with 7 beforehand).
+    Device error: the exponent -9.2103 j / half is two fp32 operations on an fp32 constant (3 u of up to 9.21), expf adds 2 ulp: f_j is off
+    by e_f = (3 x 9.21 + 4) u relative; the product t f_j one more u; cosf / sinf take that argument error (t f_j up to 999) at slope <= 1
+    and add 2 ulp of a value <= 1: a = (e_f + u) t f_j + 4 u, r = 2^-8.  Near misses: sin | cos; the exponent over half - 1; t + 1."""
+    name = "timestep_embedding"
+    exact = False
+
+    @staticmethod
+    def make(B, dim, ld, seed=23):
+        t = torch.randint(0, 1000, (B,), generator=torch.Generator().manual_seed(seed))
+        t[0] = 0
+        t[-1] = 999
+        return {"t": t, "dim": dim, "ld": ld}
+
+    @staticmethod
+    def arg(inp, dt=F64, den=None, dt_=0):
+        half = inp["dim"] // 2
+        f = torch.exp(-math.log(10000.0) * torch.arange(half, dtype=dt) / (half if den is None else den))
+        return (inp["t"] + dt_).to(dt)[:, None] * f
+
+    @staticmethod
+    def ref(inp, dt, swap=False, den=None, dt_=0):
+        a = TimestepEmbedding.arg(inp, dt, den, dt_)
+        B, half = a.shape
+        out = torch.zeros(B, inp["ld"], dtype=dt)
+        out[:, :half], out[:, half:2 * half] = (torch.sin(a), torch.cos(a)) if swap else (torch.cos(a), torch.sin(a))
+        return {"out": out, "guard": torch.full((inp["ld"],), 7.0, dtype=dt)}
+
+    @staticmethod
+    def bound(inp, ref):
+        a = TimestepEmbedding.arg(inp)
+        e = ((3 * 9.2104 + 4) * U + U) * a + 4 * U
+        full = torch.zeros_like(ref["out"])
+        full[:, :a.shape[1]] = e; full[:, a.shape[1]:2 * a.shape[1]] = e
+        return {"out": (BF, full), "guard": (0.0, torch.zeros(()))}
+
+    @staticmethod
+    def misses(inp):
+        half = inp["dim"] // 2
+        m = [("sin | cos", TimestepEmbedding.ref(inp, F64, swap=True)), ("t + 1", TimestepEmbedding.ref(inp, F64, dt_=1))]
+        if half > 1:
+            m.append(("exponent over half - 1", TimestepEmbedding.ref(inp, F64, den=half - 1)))
+        return m
+
+
+
 # ============================================================================================================ the check itself
 BF16_OUT = {"add", "sumpool2", "colsum_samples", "softmax", "softmax_bwd", "geglu", "conv3x3_dgrad", "attention_bwd", "small_attention_bwd",
             "transpose", "heads", "expand2"}
 
 
 def _bf16_out(case, inp, k):
-    return (case.name in BF16_OUT) or k == "dx" or (case.name == "silu" and not inp["grad"]) or (case.name == "bmm" and not inp["f32"])
+    return (case.name in BF16_OUT) or k in ("dx", "pb", "nhwc", "deps") or (case.name == "timestep_embedding" and k == "out") or (case.name == "silu" and not inp["grad"]) or (case.name == "bmm" and not inp["f32"])
 
 
 def standin(case, inp, bf16_out=_bf16_out):
@@ -951,9 +1258,40 @@ CASES = [
     (SmallAttentionBwd, dict(B=1, nq=77, nkv=3, H=3), "small_attention_bwd: 3 keys"),
     (SmallAttentionBwd, dict(B=2, nq=64, nkv=5, H=2, pad_q=16, pad_kv=32, pad_o=8), "small_attention_bwd: 5 keys, row pitches > C"),
     (SmallAttentionBwd, dict(B=1, nq=260, nkv=32, H=1, pad_q=8, pad_kv=8, pad_o=24), "small_attention_bwd: 32 keys, pitches > C"),
+    (AdamW, dict(sizes=(2049,), step=1, betas=(0.9, 0.999), wd=1e-2), "adamw: step 1, beta2 0.999 (the bc2 cancellation), 2049 elements"),
+    (AdamW, dict(sizes=(2047,), step=2, betas=(0.9, 0.999), wd=0.0), "adamw: step 2, no decay, 2047 elements"),
+    (AdamW, dict(sizes=(2048,), step=10000, betas=(0.9, 0.999), wd=1e-2), "adamw: step 10000, 2048 elements"),
+    (AdamW, dict(sizes=(1,), step=1, betas=(0.9, 0.95), wd=1e-2), "adamw: one element, beta2 0.95"),
+    (AdamW, dict(sizes=(2049,), step=2, betas=(0.9, 0.95), wd=0.0), "adamw: step 2, beta2 0.95, no decay"),
+    (AdamW, dict(sizes=(5000,), step=10000, betas=(0.9, 0.95), wd=1e-2), "adamw: step 10000, beta2 0.95"),
+    (AdamW, dict(sizes=(1, 2047, 2048, 2049) * 13, step=1, betas=(0.9, 0.999), wd=1e-2), "adamw_multi: 52 tensors (two launches), step 1"),
+    (AdamW, dict(sizes=(2049, 1, 2048, 2047) * 13, step=2, betas=(0.9, 0.95), wd=0.0), "adamw_multi: 52 tensors, step 2, no decay"),
+    (AdamW, dict(sizes=(1, 2047, 2048, 2049) * 13, step=10000, betas=(0.9, 0.999), wd=1e-2), "adamw_multi: 52 tensors, step 10000"),
+    (Ema, dict(sizes=(1,), omd=1e-4), "ema: one element"),
+    (Ema, dict(sizes=(2047,), omd=1e-4), "ema: 2047 elements"),
+    (Ema, dict(sizes=(2048,), omd=0.1), "ema: 2048 elements"),
+    (Ema, dict(sizes=(2049,), omd=1e-4), "ema: 2049 elements"),
+    (Ema, dict(sizes=(1, 2047, 2048, 2049) * 13, omd=1e-4), "ema_multi: 52 tensors (two launches)"),
+    (QSample, dict(B=3, C=3, H=15, W=17, cpad=8, nchw=True), "q_sample: both outputs, HW = 255, cpad 8 > C"),
+    (QSample, dict(B=2, C=4, H=25, W=44, cpad=0, nchw=True), "q_sample: NCHW only, HW = 1100"),
+    (QSample, dict(B=5, C=3, H=1, W=1, cpad=64, nchw=False), "q_sample: NHWC only, HW = 1, cpad 64"),
+    (MseLoss, dict(B=3, C=3, H=1, W=1, ldc=8, deps=True), "mse_loss: HW = 1, ldc > C"),
+    (MseLoss, dict(B=2, C=3, H=15, W=17, ldc=64, deps=True), "mse_loss: HW = 255, ldc 64"),
+    (MseLoss, dict(B=3, C=4, H=25, W=44, ldc=4, deps=True), "mse_loss: HW = 1100, ldc = C"),
+    (MseLoss, dict(B=2, C=3, H=25, W=44, ldc=8, deps=False), "mse_loss: without deps"),
+    (WhereRows, dict(rows=1, n=1), "where_rows: one element"),
+    (WhereRows, dict(rows=7, n=2049), "where_rows: 7 rows of 2049"),
+    (WhereRows, dict(rows=300, n=77), "where_rows: 300 rows"),
+    (TimestepEmbedding, dict(B=4, dim=192, ld=192), "timestep_embedding: ld = dim, t = 0 and 999"),
+    (TimestepEmbedding, dict(B=5, dim=64, ld=72), "timestep_embedding: ld > dim (zero tail, guard row)"),
+    (TimestepEmbedding, dict(B=2, dim=2, ld=8), "timestep_embedding: dim 2"),
 ]
 
 
 def case_id(entry):
     case, kw, _ = entry
-    return case.name + "-" + "-".join(f"{k}{v}" for k, v in kw.items())
+    def short(v):
+        if isinstance(v, tuple) and len(v) > 4:
+            return f"{len(v)}x{max(v)}"
+        return "_".join(str(x) for x in v) if isinstance(v, tuple) else v
+    return case.name + "-" + "-".join(f"{k}{short(v)}" for k, v in kw.items())

@@ -25,12 +25,14 @@ def _rand(shape, seed, scale=1.0):
 
 
 @pytest.mark.parametrize("B,H,W,C,N", [(2, 64, 64, 192, 384), (3, 8, 32, 224, 96), (5, 16, 8, 64, 576), (3, 32, 32, 128, 64), (5, 16, 16, 64, 128),
-                                       (2, 8, 64, 64, 64), (4, 16, 16, 576, 576), (1, 2, 16, 64, 64), (9, 4, 32, 192, 64)])
+                                       (2, 8, 64, 64, 64), (4, 16, 16, 576, 576), (1, 2, 16, 64, 64), (9, 4, 32, 192, 64), (8, 2, 16, 64, 64)])
 def test_conv3x3_wgrad_tn(ctx, B, H, W, C, N):
     """The transpose-free wgrad kernels (csrc/wgrad.hip): the nine-tap kernel at widths 64 / 32 / 16 (row ring across sample boundaries:
-    blocks spanning several samples in the 576-channel case, a two-row image, odd sample counts) and the per-tap kernel (widths that are
-    not multiples of 64 channels, 8-pixel rows, partial 192-wide tiles, ragged row counts) -- against the fp32 autograd of the same bf16
-    operands."""
+    blocks spanning several samples in the 576-channel case, two-row images at (8, 2, 16, 64, 64), odd sample counts) and the per-tap
+    kernel (widths that are not multiples of 64 channels, 8-pixel rows, partial 192-wide tiles, ragged row counts) -- against the fp32
+    autograd of the same bf16 operands.  (1, 2, 16, 64, 64) has 32 pixels: below the kernels' floor of 256 it runs the transposed-copy
+    fallback of csrc/backward.hip, not the nine-tap kernel.  Which path a shape takes, and the per-element checks of every path:
+    tests/_wgrad_ref.py and test_gpu_training_ops.py."""
     d = ctx.device
     x = bf16_round(_rand((B, H, W, C), 11))
     w = torch.zeros((N, C, 3, 3), requires_grad=True)
