@@ -408,6 +408,10 @@ def _acp_array(alphas_cumprod):
                                 dtype=np.float32)
 
 
+def _nodes_array(nodes):
+    return np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
+
+
 def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):
     """Node list for Context.dpmpp_sample (rdm_dpmpp_timesteps; host code, no context needed): "time_uniform" = DDIM's S-step
     timesteps descending, then 0; "logSNR" = uniform in logSNR from T - 1 to 0, rounded to integer timesteps (may come out shorter
@@ -435,7 +439,7 @@ def unipc_coefficients(nodes, alphas_cumprod, j, order=2, variant="bh2", correct
     -> float64 numpy array [13] in the order of UNIPC_COEFFICIENTS: alpha_j, sigma_j, the correction x_j = a_x x_{j-1} + a_t m_j +
     a_1 m_{j-1} + a_2 m_{j-2} + a_3 m_{j-3} (order_c 0: x_j = u_j), the prediction u_{j+1} = b_x x_j + b_0 m_j + b_1 m_{j-1} + b_2 m_{j-2}."""
     ac = _acp_array(alphas_cumprod)
-    nd = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
+    nd = _nodes_array(nodes)
     out = np.zeros((len(UNIPC_COEFFICIENTS),), dtype=np.float64)
     r = lib.rdm_unipc_coefficients(ac.ctypes.data_as(C.POINTER(C.c_float)), ac.shape[0], nd.ctypes.data_as(C.POINTER(C.c_int)), nd.shape[0],
                                    int(j), int(order), _unipc_variant("unipc_coefficients", variant), int(bool(corrector)),
@@ -693,41 +697,48 @@ class Context:
         self._check(lib.rdm_unet_forward(self._h, _ptr(x), _ptr(t), _ptr(context), b, context.shape[1], H, W, _ptr(out)))
         return out
 
-    def _ddim_call(self, what, fn, S, x_T, cond, uncond, alphas_cumprod, eta, scale, noise, log_every_t, temperature, want_intermediates):
-        """The set-up that ddim_sample and plms_sample share (both run on DDIM's schedule through DdimArgs): device casts, checks,
-        the fp32 alphas_cumprod array, the outputs.  fn(handle, args, x_T, cond, uncond, noise, z, x_inter, pred_x0_inter) is the
-        library call."""
-        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
-        uncond = None if uncond is None else self._dev(uncond, torch.float32)
-        noise = None if noise is None else self._dev(noise, torch.float32)
+    def _sampler_call(self, what, fn, Args, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=None, nodes=None,
+                      noise=None, **fields):
+        """What ddim_sample, plms_sample, dpmpp_sample and unipc_sample share: device casts, the fp32 alphas_cumprod array, the step
+        count (of DDIM's S-step schedule, or of the node list), shape and guidance checks, the outputs.  Args(**fields) plus the fields
+        every sampler has is the argument struct, fn(handle, args, x_T, cond, uncond, z, x_inter, pred_x0_inter) the library call;
+        noise: a [steps, B, C, H, W] stack to shape-check.  -> (z, x_inter, pred_x0_inter)."""
+        x_T, cond, uncond = (None if t is None else self._dev(t, torch.float32) for t in (x_T, cond, uncond))
         ac = _acp_array(alphas_cumprod)
-        total = len(range(0, ac.shape[0], max(ac.shape[0] // max(int(S), 1), 1)))
-        self._check_sampler_shapes(what, x_T, cond, uncond, noise if eta != 0.0 else None, total)
+        if nodes is None:
+            steps = len(range(0, ac.shape[0], max(ac.shape[0] // max(int(S), 1), 1)))
+            fields["S"] = S
+        else:
+            nd = _nodes_array(nodes)
+            steps = nd.shape[0] - 1
+            fields.update(n_nodes=nd.shape[0], nodes=nd.ctypes.data_as(C.POINTER(C.c_int)))
+        self._check_sampler_shapes(what, x_T, cond, uncond, noise, steps)
         if scale > 1.0 and uncond is None:
             raise RdmError(f"{what}: unconditional_conditioning is required when unconditional_guidance_scale > 1")
         B, Cc, H, W = x_T.shape
-        a = DdimArgs(S=S, batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, eta=eta, temperature=temperature,
-                     unconditional_guidance_scale=scale, log_every_t=log_every_t, T=ac.shape[0],
-                     alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)))
+        a = Args(batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, unconditional_guidance_scale=scale, log_every_t=log_every_t,
+                 T=ac.shape[0], alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)), **fields)
         z = torch.empty_like(x_T)
         xi = pi = None
         if want_intermediates:
-            n = lib.rdm_ddim_num_intermediates(total, log_every_t)
+            n = lib.rdm_ddim_num_intermediates(steps, log_every_t)
             xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
             pi = torch.empty_like(xi)
-        self._check(fn(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(noise), _ptr(z), _ptr(xi), _ptr(pi)))
+        self._check(fn(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
         return z, xi, pi
 
     def ddim_sample(self, S, x_T, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
                     temperature=1.0, want_intermediates=False):
-        return self._ddim_call("ddim_sample", lib.rdm_ddim_sample, S, x_T, cond, uncond, alphas_cumprod, eta, scale, noise,
-                               log_every_t, temperature, want_intermediates)
+        noise = None if noise is None else self._dev(noise, torch.float32)         # (its shape matters only when it is used)
+        return self._sampler_call("ddim_sample", lambda h, a, x, c, u, *out: lib.rdm_ddim_sample(h, a, x, c, u, _ptr(noise), *out), DdimArgs,
+                                  x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+                                  noise=noise if eta != 0.0 else None, eta=eta, temperature=temperature)
 
     def plms_sample(self, S, x_T, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False):
         """ldm PLMSSampler's loop (eta = 0) on DDIM's schedule: S' + 1 UNet forwards for S' sampler timesteps.  Returns
         (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
-        return self._ddim_call("plms_sample", lambda h, a, x, c, u, noise, *out: lib.rdm_plms_sample(h, a, x, c, u, *out),
-                               S, x_T, cond, uncond, alphas_cumprod, 0.0, scale, None, log_every_t, 1.0, want_intermediates)
+        return self._sampler_call("plms_sample", lib.rdm_plms_sample, DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t,
+                                  want_intermediates, S=S, eta=0.0, temperature=1.0)
 
     @staticmethod
     def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):
@@ -738,29 +749,10 @@ class Context:
         """DPM-Solver++(2M) (order 1: DDIM with eta = 0) over the strictly decreasing integer timesteps `nodes` (dpmpp_timesteps builds
         the two grids): len(nodes) - 1 UNet forwards, the result at the noise level of nodes[-1].  lower_order_final None: on below 15
         steps.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
-        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
-        uncond = None if uncond is None else self._dev(uncond, torch.float32)
-        ac = _acp_array(alphas_cumprod)
-        nd = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
-        n_steps = nd.shape[0] - 1
-        self._check_sampler_shapes("dpmpp_sample", x_T, cond, uncond)
-        if scale > 1.0 and uncond is None:
-            raise RdmError("dpmpp_sample: unconditional_conditioning is required when unconditional_guidance_scale > 1")
         if lower_order_final is None:
-            lower_order_final = n_steps < 15
-        B, Cc, H, W = x_T.shape
-        a = DpmppArgs(batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, unconditional_guidance_scale=scale, order=int(order),
-                      lower_order_final=int(bool(lower_order_final)), log_every_t=log_every_t, T=ac.shape[0],
-                      alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)), n_nodes=nd.shape[0],
-                      nodes=nd.ctypes.data_as(C.POINTER(C.c_int)))
-        z = torch.empty_like(x_T)
-        xi = pi = None
-        if want_intermediates:
-            n = lib.rdm_ddim_num_intermediates(n_steps, log_every_t)
-            xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
-            pi = torch.empty_like(xi)
-        self._check(lib.rdm_dpmpp_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
-        return z, xi, pi
+            lower_order_final = _nodes_array(nodes).shape[0] - 1 < 15
+        return self._sampler_call("dpmpp_sample", lib.rdm_dpmpp_sample, DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t,
+                                  want_intermediates, nodes=nodes, order=int(order), lower_order_final=int(bool(lower_order_final)))
 
     def op_dpmpp_step(self, x, eps, m_prev, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, x_out, x_dup=None, m_store=None,
                       pred_x0=None):
@@ -783,28 +775,9 @@ class Context:
         decreasing integer timesteps `nodes` (dpmpp_timesteps builds the two grids): len(nodes) - 1 UNet forwards, the result at the noise
         level of nodes[-1].  Returns (z, x_inter, pred_x0_inter): x_inter[j] the UNet input of node j + 1 (the last one is z),
         pred_x0_inter[j] = m_j; the intermediates are None unless want_intermediates."""
-        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32)
-        uncond = None if uncond is None else self._dev(uncond, torch.float32)
-        ac = _acp_array(alphas_cumprod)
-        nd = np.ascontiguousarray(np.asarray(nodes).reshape(-1), dtype=np.int32)
-        n_steps = nd.shape[0] - 1
-        self._check_sampler_shapes("unipc_sample", x_T, cond, uncond)
-        if scale > 1.0 and uncond is None:
-            raise RdmError("unipc_sample: unconditional_conditioning is required when unconditional_guidance_scale > 1")
-        B, Cc, H, W = x_T.shape
-        a = UnipcArgs(batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, unconditional_guidance_scale=scale, order=int(order),
-                      variant=_unipc_variant("unipc_sample", variant), corrector=int(bool(corrector)),
-                      lower_order_final=int(bool(lower_order_final)), log_every_t=log_every_t, T=ac.shape[0],
-                      alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)), n_nodes=nd.shape[0],
-                      nodes=nd.ctypes.data_as(C.POINTER(C.c_int)))
-        z = torch.empty_like(x_T)
-        xi = pi = None
-        if want_intermediates:
-            n = lib.rdm_ddim_num_intermediates(n_steps, log_every_t)
-            xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
-            pi = torch.empty_like(xi)
-        self._check(lib.rdm_unipc_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
-        return z, xi, pi
+        return self._sampler_call("unipc_sample", lib.rdm_unipc_sample, UnipcArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t,
+                                  want_intermediates, nodes=nodes, order=int(order), variant=_unipc_variant("unipc_sample", variant),
+                                  corrector=int(bool(corrector)), lower_order_final=int(bool(lower_order_final)))
 
     def op_unipc_step(self, u, eps, coefficients, cfg, scale, u_next, xc_prev=None, h1=None, h2=None, h3=None, xc_out=None, x_dup=None,
                       m_store=None, pred_x0=None):

@@ -518,18 +518,43 @@ hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st) {
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------ what the PLMS, DPM-Solver++ and UniPC step kernels share
+template <int V> __device__ __forceinline__ void step_ld(const float* p, long long i, float (&v)[V]) {
+    if constexpr (V == 4) { const float4 t = *(const float4*)(p + i); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
+    else v[0] = p[i];
+}
+template <int V> __device__ __forceinline__ void step_st(float* p, long long i, const float (&v)[V]) {
+    if constexpr (V == 4) *(float4*)(p + i) = make_float4(v[0], v[1], v[2], v[3]);
+    else p[i] = v[0];
+}
+// The guided eps of the PLMS, DPM-Solver++ and UniPC passes: e of the cond rows, or u + scale (e - u) with u the uncond rows n further on
+// (cfg).  The contraction pragma holds for the function body it is written in, so this helper carries its own.
+template <int V> __device__ __forceinline__ void step_guided_eps(const float* eps, long long n, long long i, int cfg, float scale, float (&e)[V]) {
+#pragma clang fp contract(off)
+    step_ld<V>(eps, i, e);
+    if (cfg) {
+        float u[V]; step_ld<V>(eps + n, i, u);
+#pragma unroll
+        for (int k = 0; k < V; k++) e[k] = u[k] + scale * (e[k] - u[k]);
+    }
+}
+// One launch of a step kernel over n elements: the float4 instantiation k4 when n % 4 == 0 and every operand is 16-byte aligned (null
+// is), else the scalar k1; 256 threads on at most 2048 blocks.
+template <class P>
+static hipError_t launch_step(long long n, std::initializer_list<const void*> ptrs, const P& p, void (*k4)(P), void (*k1)(P), hipStream_t st) {
+    if (n <= 0) return hipSuccess;
+    bool vec = n % 4 == 0;
+    for (const void* q : ptrs) vec = vec && ((uintptr_t)q % 16 == 0);
+    const long long nv = vec ? n / 4 : n;
+    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
+    (vec ? k4 : k1)<<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
+}
+
 // ------------------------------------------------------------------ PLMS update (fp32, eta = 0)
 // ldm PLMSSampler.p_sample_plms: CFG combine, the linear-multistep combination of e_t with up to three earlier e_t, and the DDIM
 // update (get_x_prev_and_pred_x0 with sigma_t = 0), one pass per step.  Same association, true divisions and no FMA contraction as the
 // torch expressions, so a torch restatement agrees to rounding.  V = 4: float4 accesses (the launcher checks n % 4 and alignment).
-template <int V> __device__ __forceinline__ void plms_ld(const float* p, long long i, float (&v)[V]) {
-    if constexpr (V == 4) { const float4 t = *(const float4*)(p + i); v[0] = t.x; v[1] = t.y; v[2] = t.z; v[3] = t.w; }
-    else v[0] = p[i];
-}
-template <int V> __device__ __forceinline__ void plms_st(float* p, long long i, const float (&v)[V]) {
-    if constexpr (V == 4) *(float4*)(p + i) = make_float4(v[0], v[1], v[2], v[3]);
-    else p[i] = v[0];
-}
 template <int V>
 __global__ __launch_bounds__(256) void plms_step_kernel(PlmsStepParams p) {
 #pragma clang fp contract(off)
@@ -538,57 +563,45 @@ __global__ __launch_bounds__(256) void plms_step_kernel(PlmsStepParams p) {
     for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
         const long long i = v * V;
         float e[V], x[V], o[V];
-        plms_ld<V>(p.eps, i, e);
-        if (p.cfg) {
-            float u[V]; plms_ld<V>(p.eps + p.n, i, u);
-#pragma unroll
-            for (int k = 0; k < V; k++) e[k] = u[k] + p.scale * (e[k] - u[k]);
-        }
-        plms_ld<V>(p.x, i, x);
+        step_guided_eps<V>(p.eps, p.n, i, p.cfg, p.scale, e);
+        step_ld<V>(p.x, i, x);
         if (p.mode == PLMS_EULER_B) {
-            float q[V]; plms_ld<V>(p.e_prev, i, q);
+            float q[V]; step_ld<V>(p.e_prev, i, q);
 #pragma unroll
             for (int k = 0; k < V; k++) o[k] = (q[k] + e[k]) / 2.0f;
         } else {
 #pragma unroll
             for (int k = 0; k < V; k++) o[k] = e[k];
             if (p.mode == PLMS_STEP && p.order >= 1) {
-                float a[V]; plms_ld<V>(p.h1, i, a);
+                float a[V]; step_ld<V>(p.h1, i, a);
                 if (p.order == 1) {
 #pragma unroll
                     for (int k = 0; k < V; k++) o[k] = (3.0f * e[k] - a[k]) / 2.0f;
                 } else {
-                    float b[V]; plms_ld<V>(p.h2, i, b);
+                    float b[V]; step_ld<V>(p.h2, i, b);
                     if (p.order == 2) {
 #pragma unroll
                         for (int k = 0; k < V; k++) o[k] = (23.0f * e[k] - 16.0f * a[k] + 5.0f * b[k]) / 12.0f;
                     } else {
-                        float c[V]; plms_ld<V>(p.h3, i, c);
+                        float c[V]; step_ld<V>(p.h3, i, c);
 #pragma unroll
                         for (int k = 0; k < V; k++) o[k] = (55.0f * e[k] - 59.0f * a[k] + 37.0f * b[k] - 9.0f * c[k]) / 24.0f;
                     }
                 }
             }
-            plms_st<V>(p.e_store, i, e);          // after the history reads: e_store may be h3's slot
+            step_st<V>(p.e_store, i, e);          // after the history reads: e_store may be h3's slot
         }
         float xo[V], x0[V];
 #pragma unroll
         for (int k = 0; k < V; k++) { x0[k] = (x[k] - p.sqrt_one_minus_at * o[k]) / sa; xo[k] = sap * x0[k] + s1p * o[k]; }
-        plms_st<V>(p.x_out, i, xo);
-        if (p.x_dup) plms_st<V>(p.x_dup, i, xo);
-        if (p.pred_x0) plms_st<V>(p.pred_x0, i, x0);
+        step_st<V>(p.x_out, i, xo);
+        if (p.x_dup) step_st<V>(p.x_dup, i, xo);
+        if (p.pred_x0) step_st<V>(p.pred_x0, i, x0);
     }
 }
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st) {
-    if (p.n <= 0) return hipSuccess;
-    const void* ptrs[] = {p.x, p.eps, p.e_prev, p.h1, p.h2, p.h3, p.e_store, p.x_out, p.x_dup, p.pred_x0};
-    bool vec = p.n % 4 == 0;
-    for (const void* q : ptrs) vec = vec && ((uintptr_t)q % 16 == 0);        // (null is aligned)
-    const long long nv = vec ? p.n / 4 : p.n;
-    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
-    if (vec) plms_step_kernel<4><<<grid, 256, 0, st>>>(p);
-    else plms_step_kernel<1><<<grid, 256, 0, st>>>(p);
-    return hipGetLastError();
+    return launch_step(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.e_prev, p.h1, p.h2, p.h3, p.e_store, p.x_out, p.x_dup, p.pred_x0}, p,
+                       plms_step_kernel<4>, plms_step_kernel<1>, st);
 }
 
 // ------------------------------------------------------------------ DPM-Solver++ update (fp32)
@@ -604,36 +617,23 @@ __global__ __launch_bounds__(256) void dpmpp_step_kernel(DpmppStepParams p) {
     for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
         const long long i = v * V;
         float e[V], x[V], m0[V], xo[V];
-        plms_ld<V>(p.eps, i, e);
-        if (p.cfg) {
-            float u[V]; plms_ld<V>(p.eps + p.n, i, u);
-#pragma unroll
-            for (int k = 0; k < V; k++) e[k] = u[k] + p.scale * (e[k] - u[k]);
-        }
-        plms_ld<V>(p.x, i, x);
+        step_guided_eps<V>(p.eps, p.n, i, p.cfg, p.scale, e);
+        step_ld<V>(p.x, i, x);
 #pragma unroll
         for (int k = 0; k < V; k++) { m0[k] = (x[k] - p.sqrt_one_minus_a_s * e[k]) / p.sqrt_a_s; xo[k] = p.c_x * x[k] + p.c_0 * m0[k]; }
         if (p.m_prev) {
-            float q[V]; plms_ld<V>(p.m_prev, i, q);
+            float q[V]; step_ld<V>(p.m_prev, i, q);
 #pragma unroll
             for (int k = 0; k < V; k++) xo[k] = xo[k] + p.c_1 * q[k];
         }
-        if (p.m_store) plms_st<V>(p.m_store, i, m0);          // after the m_prev read: m_store may be that slot
-        plms_st<V>(p.x_out, i, xo);
-        if (p.x_dup) plms_st<V>(p.x_dup, i, xo);
-        if (p.pred_x0) plms_st<V>(p.pred_x0, i, m0);
+        if (p.m_store) step_st<V>(p.m_store, i, m0);          // after the m_prev read: m_store may be that slot
+        step_st<V>(p.x_out, i, xo);
+        if (p.x_dup) step_st<V>(p.x_dup, i, xo);
+        if (p.pred_x0) step_st<V>(p.pred_x0, i, m0);
     }
 }
 hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st) {
-    if (p.n <= 0) return hipSuccess;
-    const void* ptrs[] = {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.x_out, p.x_dup, p.m_store, p.pred_x0};
-    bool vec = p.n % 4 == 0;
-    for (const void* q : ptrs) vec = vec && ((uintptr_t)q % 16 == 0);        // (null is aligned)
-    const long long nv = vec ? p.n / 4 : p.n;
-    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
-    if (vec) dpmpp_step_kernel<4><<<grid, 256, 0, st>>>(p);
-    else dpmpp_step_kernel<1><<<grid, 256, 0, st>>>(p);
-    return hipGetLastError();
+    return launch_step(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.x_out, p.x_dup, p.m_store, p.pred_x0}, p, dpmpp_step_kernel<4>, dpmpp_step_kernel<1>, st);
 }
 
 // ------------------------------------------------------------------ UniPC predict-and-correct (fp32)
@@ -651,21 +651,16 @@ __global__ __launch_bounds__(256) void unipc_step_kernel(UnipcStepParams p) {
     for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
         const long long i = v * V;
         float e[V], u[V], m[V], xc[V], un[V], h1[V], h2[V], h3[V];
-        plms_ld<V>(p.eps, i, e);
-        if (p.cfg) {
-            float w[V]; plms_ld<V>(p.eps + p.n, i, w);
-#pragma unroll
-            for (int k = 0; k < V; k++) e[k] = w[k] + p.scale * (e[k] - w[k]);
-        }
-        plms_ld<V>(p.u, i, u);
+        step_guided_eps<V>(p.eps, p.n, i, p.cfg, p.scale, e);
+        step_ld<V>(p.u, i, u);
         const int nh = p.order_c > p.order_p - 1 ? p.order_c : p.order_p - 1;        // history slots this pass reads
-        if (nh >= 1) plms_ld<V>(p.h1, i, h1);
-        if (nh >= 2) plms_ld<V>(p.h2, i, h2);
-        if (nh >= 3) plms_ld<V>(p.h3, i, h3);
+        if (nh >= 1) step_ld<V>(p.h1, i, h1);
+        if (nh >= 2) step_ld<V>(p.h2, i, h2);
+        if (nh >= 3) step_ld<V>(p.h3, i, h3);
 #pragma unroll
         for (int k = 0; k < V; k++) m[k] = (u[k] - p.sigma * e[k]) / p.alpha;
         if (p.order_c >= 1) {
-            float xp[V]; plms_ld<V>(p.xc_prev, i, xp);
+            float xp[V]; step_ld<V>(p.xc_prev, i, xp);
 #pragma unroll
             for (int k = 0; k < V; k++) {
                 xc[k] = p.a_x * xp[k] + p.a_t * m[k];
@@ -683,23 +678,15 @@ __global__ __launch_bounds__(256) void unipc_step_kernel(UnipcStepParams p) {
             if (p.order_p >= 2) un[k] = un[k] + p.b_1 * h1[k];
             if (p.order_p >= 3) un[k] = un[k] + p.b_2 * h2[k];
         }
-        if (p.m_store) plms_st<V>(p.m_store, i, m);           // after the history reads: m_store may be h3's slot
-        if (p.xc_out) plms_st<V>(p.xc_out, i, xc);            // after the xc_prev read: xc_out may be that slot
-        plms_st<V>(p.u_next, i, un);
-        if (p.x_dup) plms_st<V>(p.x_dup, i, un);
-        if (p.pred_x0) plms_st<V>(p.pred_x0, i, m);
+        if (p.m_store) step_st<V>(p.m_store, i, m);           // after the history reads: m_store may be h3's slot
+        if (p.xc_out) step_st<V>(p.xc_out, i, xc);            // after the xc_prev read: xc_out may be that slot
+        step_st<V>(p.u_next, i, un);
+        if (p.x_dup) step_st<V>(p.x_dup, i, un);
+        if (p.pred_x0) step_st<V>(p.pred_x0, i, m);
     }
 }
 hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st) {
-    if (p.n <= 0) return hipSuccess;
-    const void* ptrs[] = {p.u, p.eps, p.eps + (p.cfg ? p.n : 0), p.xc_prev, p.h1, p.h2, p.h3, p.xc_out, p.u_next, p.x_dup, p.m_store, p.pred_x0};
-    bool vec = p.n % 4 == 0;
-    for (const void* q : ptrs) vec = vec && ((uintptr_t)q % 16 == 0);        // (null is aligned)
-    const long long nv = vec ? p.n / 4 : p.n;
-    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
-    if (vec) unipc_step_kernel<4><<<grid, 256, 0, st>>>(p);
-    else unipc_step_kernel<1><<<grid, 256, 0, st>>>(p);
-    return hipGetLastError();
+    return launch_step(p.n, {p.u, p.eps, p.eps + (p.cfg ? p.n : 0), p.xc_prev, p.h1, p.h2, p.h3, p.xc_out, p.u_next, p.x_dup, p.m_store, p.pred_x0}, p, unipc_step_kernel<4>, unipc_step_kernel<1>, st);
 }
 
 // out[r, :] = x[r, :] + bias[:]   (bf16 rows, 8 columns per thread).  Cross-attention of a sample whose neighbours are all-zero

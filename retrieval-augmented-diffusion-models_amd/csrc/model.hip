@@ -1798,26 +1798,31 @@ static int sampler_emb_table(rdm_ctx* c, const std::vector<int>& ts, const float
     return 0;
 }
 
-// One sampling call of the DDIM, PLMS and DDPM loops.  begin() lays out the scratch in c->samp ([cond | uncond] staging, the UNet input
-// x of nb rows, the [steps][nb] int64 timestep table, eps, `extra` bytes of the sampler's own), projects the conditioning's K/V, uploads
-// the timestep table and the time-embedding table of ts, and copies x_T into x (both halves of a guided batch: nb = 2B, [x | x] against
-// [cond | uncond]; later steps' kernels write both halves through x_dup).  forward(idx) is then the UNet at ts[idx] on x into eps.
-struct SamplerRun {
+// One sampling call of the five loops.  begin() lays out the scratch in c->samp ([cond | uncond] staging, the UNet input x of nb rows,
+// the [steps][nb] int64 timestep table, eps, n_extra fp32 buffers of B rows for the sampler's own state: extra[]), projects the
+// conditioning's K/V, uploads the timestep table and the time-embedding table of ts, and copies x_T into x (both halves of a guided
+// batch: nb = 2B, [x | x] against [cond | uncond]; later steps' kernels write both halves through x_dup).  forward(idx) is then the
+// UNet at ts[idx] on x into eps.
+extern "C++" struct SamplerRun {
     rdm_ctx* c; int B, nb, k, H, W, total; long long n1;           // n1: elements of x for B rows; total: ts.size()
-    float *x, *x_dup, *eps; char* extra; long long* tdev; const float* emb_table;
-    int log_every_t = 0, n_logged = 0; float *x_inter = nullptr, *pred_x0_inter = nullptr;     // intermediates: set by DDIM and PLMS
+    float *x, *x_dup, *eps, *extra[4]; long long* tdev; const float* emb_table;
+    int log_every_t = 0, n_logged = 0; float *x_inter = nullptr, *pred_x0_inter = nullptr;     // intermediates (DDPM keeps none)
     static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
-    // batch, k, C, H, W: of the entry's args; uncond: null for an unguided call.  The caller has checked that the UNet is loaded.
-    int begin(rdm_ctx* ctx, int batch, int k_, int C, int H_, int W_, const std::vector<int>& ts, const float* x_T, const float* cond,
-              const float* uncond, size_t extra_bytes) {
-        c = ctx; B = batch; nb = uncond ? 2 * B : B; k = k_; H = H_; W = W_; total = (int)ts.size();
-        n1 = (long long)B * C * H * W;
-        const size_t x_bytes = (size_t)n1 * 4 * (nb / B), t_bytes = (size_t)total * nb * 8;
+    // a: the entry's args (batch, k, channels, height, width); uncond: null for an unguided call; log_every / x_inter_out / pred_x0_out:
+    // the entry's intermediates arguments; n_extra <= 4.  The caller has checked that the UNet is loaded.
+    template <class Args>       // rdm_ddim_args | rdm_dpmpp_args | rdm_unipc_args | rdm_ddpm_args: the five fields have the same names
+    int begin(rdm_ctx* ctx, const Args* a, const std::vector<int>& ts, const float* x_T, const float* cond, const float* uncond,
+              int log_every, float* x_inter_out, float* pred_x0_out, int n_extra) {
+        c = ctx; B = a->batch; nb = uncond ? 2 * B : B; k = a->k; H = a->height; W = a->width; total = (int)ts.size();
+        n1 = (long long)B * a->channels * H * W;
+        log_every_t = log_every; x_inter = x_inter_out; pred_x0_inter = pred_x0_out;
+        const size_t x_bytes = (size_t)n1 * 4 * (nb / B), t_bytes = (size_t)total * nb * 8, h_stride = al((size_t)n1 * 4);
         const size_t off_x = al((size_t)nb * k * c->unet.cfg.context_dim * 4), off_t = al(off_x + x_bytes), off_eps = al(off_t + t_bytes),
                      off_extra = al(off_eps + x_bytes);
-        RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, off_extra + extra_bytes));
+        RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, off_extra + n_extra * h_stride));
         RDM_TRY(prepare_kv(c, (float*)c->samp, cond, uncond, B, k));
-        x = (float*)(c->samp + off_x); x_dup = uncond ? x + n1 : nullptr; eps = (float*)(c->samp + off_eps); extra = c->samp + off_extra;
+        x = (float*)(c->samp + off_x); x_dup = uncond ? x + n1 : nullptr; eps = (float*)(c->samp + off_eps);
+        for (int i = 0; i < n_extra; i++) extra[i] = (float*)(c->samp + off_extra + i * h_stride);
         tdev = (long long*)(c->samp + off_t);
         {
             std::vector<long long> th((size_t)total * nb);
@@ -1834,11 +1839,12 @@ struct SamplerRun {
         return unet_forward_impl(c, x, (const int64_t*)(tdev + (size_t)idx * nb), nullptr, u.kv_cache, nb, k, H, W, eps, u.ctx_rows,
                                  x_dup ? B : 0, emb_table ? emb_table + (size_t)idx * u.emb_total : nullptr);
     }
-    // intermediates of step `index` (counting down from total - 1): where the step kernel writes pred_x0, then the copy of the new x
-    bool logs(int index) const { return (index % log_every_t == 0) || (index == total - 1); }
-    float* pred_x0_slot(int index) const { return (logs(index) && pred_x0_inter) ? pred_x0_inter + (size_t)n_logged * n1 : nullptr; }
-    int log_x(int index) {
-        if (!logs(index)) return 0;
+    // intermediates of loop step `step` (0 .. total - 1; the rule counts the index down from total - 1): where the step kernel writes
+    // pred_x0, then the copy of the new x
+    bool logs(int step) const { const int index = total - 1 - step; return (index % log_every_t == 0) || (index == total - 1); }
+    float* pred_x0_slot(int step) const { return (logs(step) && pred_x0_inter) ? pred_x0_inter + (size_t)n_logged * n1 : nullptr; }
+    int log_x(int step) {
+        if (!logs(step)) return 0;
         if (x_inter) RDM_CHECK_HIP(c, hipMemcpyAsync(x_inter + (size_t)n_logged * n1, x, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
         n_logged++;
         return 0;
@@ -1846,14 +1852,36 @@ struct SamplerRun {
     int finish(float* z_out) { RDM_CHECK_HIP(c, hipMemcpyAsync(z_out, x, n1 * 4, hipMemcpyDeviceToDevice, c->stream)); return 0; }
 };
 
+// The guidance arguments of the four guided entries (ddim.py:223, :231): *cfg = the batch is doubled
+static int sampler_guidance(rdm_ctx* c, const char* who, float scale, const float* uncond, bool* cfg) {
+    if (scale < 1.0f) return c->fail(-1, "%s: unconditional_guidance_scale must be >= 1", who);
+    *cfg = scale > 1.0f;
+    if (*cfg && !uncond) return c->fail(-1, "%s: unconditional_conditioning required when scale > 1", who);
+    return 0;
+}
+
+// The history of the PLMS and UniPC loops: the last (up to) three values, h(0) the newest, in three buffers rotated by pointer.  The
+// step kernel writes the newest value to next() -- a free buffer, or the oldest value's -- in the pass that reads h(0..2): a thread
+// reads its elements of the oldest value before it overwrites them.  push() after that launch makes next() h(0).
+struct HistoryRing {
+    float* slot[3]; int held = 0;
+    float* h(int i) const { return i < held ? slot[i] : nullptr; }
+    float* next() const { return slot[held < 3 ? held : 2]; }
+    void push() {
+        float* newest = next();
+        for (int j = held < 3 ? held : 2; j > 0; j--) slot[j] = slot[j - 1];
+        slot[0] = newest;
+        if (held < 3) held++;
+    }
+};
+
 int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
                     const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
-    if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1 (ddim.py:223)");
-    const bool cfg = a->unconditional_guidance_scale > 1.0f;
-    if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1 (ddim.py:231)");
+    bool cfg;
+    RDM_TRY(sampler_guidance(c, "ddim", a->unconditional_guidance_scale, uncond, &cfg));
     if (a->eta != 0.f && !noise) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
@@ -1865,18 +1893,17 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
         sg[i] = (float)((double)a->eta * std::sqrt((1.0 - apd) / (1.0 - atd) * (1.0 - atd / apd)));
     }
     SamplerRun run;
-    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr, 0));
-    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
+    RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 0));
     for (int i = 0; i < total; i++) {
-        const int index = total - i - 1;
+        const int index = total - i - 1;         // of the ascending schedule
         RDM_TRY(run.forward(index));
         DdimStepParams p{};
         p.x = run.x; p.eps = run.eps; p.noise = (noise && a->eta != 0.f) ? noise + (size_t)i * run.n1 : nullptr;
-        p.x_prev = run.x; p.x_dup = run.x_dup; p.pred_x0 = run.pred_x0_slot(index);
+        p.x_prev = run.x; p.x_dup = run.x_dup; p.pred_x0 = run.pred_x0_slot(i);
         p.n_per_batch = run.n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sigma_t = sg[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.temperature = a->temperature; p.cfg = cfg ? 1 : 0;
         RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
-        RDM_TRY(run.log_x(index));
+        RDM_TRY(run.log_x(i));
     }
     return run.finish(z_out);
 }
@@ -1884,62 +1911,79 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
 // ldm PLMSSampler.plms_sampling / p_sample_plms (eta = 0): DDIM's schedule, timesteps and intermediates, total + 1 forwards.  The
 // first step is the pseudo improved Euler step: phase A stores e_t and writes x_tmp = update(x, e_t) into the UNet input, a forward at
 // t_next (one of the table's rows) follows, phase B updates the kept x with (e_t + e_next) / 2.  Later steps combine e_t with up to
-// three earlier e_t held in a ring of three slots, rotated by pointer (the newest e_t takes the oldest slot in the same pass).
+// three earlier e_t held in a HistoryRing.
 int rdm_plms_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
                     float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->eta != 0.f) return c->fail(-1, "ddim_eta must be 0 for PLMS");
-    if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1");
-    const bool cfg = a->unconditional_guidance_scale > 1.0f;
-    if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1");
+    bool cfg;
+    RDM_TRY(sampler_guidance(c, "plms", a->unconditional_guidance_scale, uncond, &cfg));
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
     const int total = (int)ts.size();
-    // the sampler's own scratch: the kept x [B], 3 history slots [B]
-    const size_t h_stride = SamplerRun::al((size_t)a->batch * a->channels * a->height * a->width * 4);
-    SamplerRun run;
-    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr, 4 * h_stride));
-    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
-    float* xk = (float*)run.extra;
-    float* slot[3] = {(float*)(run.extra + h_stride), (float*)(run.extra + 2 * h_stride), (float*)(run.extra + 3 * h_stride)};
+    SamplerRun run;         // the sampler's own scratch: the kept x, 3 history buffers
+    RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 4));
+    float* xk = run.extra[0];
+    HistoryRing ring{{run.extra[1], run.extra[2], run.extra[3]}};          // h(0..2) = o[-1], o[-2], o[-3]
     RDM_CHECK_HIP(c, hipMemcpyAsync(xk, x_T, run.n1 * 4, hipMemcpyDeviceToDevice, c->stream));             // the first step's x, kept beside x_tmp
-    int n_hist = 0;                          // slot[0 .. n_hist) = o[-1], o[-2], o[-3]
     for (int i = 0; i < total; i++) {
-        const int index = total - i - 1;
+        const int index = total - i - 1;         // of the ascending schedule
         PlmsStepParams p{};
         p.eps = run.eps; p.n = run.n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.cfg = cfg ? 1 : 0;
         p.x_out = run.x; p.x_dup = run.x_dup;
-        float* e_new = slot[n_hist < 3 ? n_hist : 2];         // a free slot, or the oldest e_t (read before it is overwritten)
-        p.e_store = e_new;
+        p.e_store = ring.next();
         RDM_TRY(run.forward(index));
-        if (n_hist == 0) {
+        if (ring.held == 0) {
             p.x = xk; p.mode = PLMS_EULER_A;                   // x_tmp -> run.x (both halves); x stays in xk
             RDM_CHECK_HIP(c, launch_plms_step(p, c->stream));
             RDM_TRY(run.forward(index > 0 ? index - 1 : 0));  // t_next = time_range[min(i + 1, total - 1)]
-            p.mode = PLMS_EULER_B; p.e_prev = e_new; p.e_store = nullptr;
+            p.mode = PLMS_EULER_B; p.e_prev = ring.next(); p.e_store = nullptr;
         } else {
-            p.x = run.x; p.mode = PLMS_STEP; p.order = n_hist;
-            p.h1 = slot[0]; p.h2 = n_hist > 1 ? slot[1] : nullptr; p.h3 = n_hist > 2 ? slot[2] : nullptr;
+            p.x = run.x; p.mode = PLMS_STEP; p.order = ring.held;
+            p.h1 = ring.h(0); p.h2 = ring.h(1); p.h3 = ring.h(2);
         }
-        p.pred_x0 = run.pred_x0_slot(index);
+        p.pred_x0 = run.pred_x0_slot(i);
         RDM_CHECK_HIP(c, launch_plms_step(p, c->stream));
-        for (int j = n_hist < 3 ? n_hist : 2; j > 0; j--) slot[j] = slot[j - 1];
-        slot[0] = e_new;
-        if (n_hist < 3) n_hist++;
-        RDM_TRY(run.log_x(index));
+        ring.push();
+        RDM_TRY(run.log_x(i));
     }
     return run.finish(z_out);
 }
 
-// DPM-Solver++ (Lu et al. 2022; ldm models/diffusion/dpm_solver/sampler.py): alpha, sigma and the half logSNR lambda of a timestep, in
-// float64 from the model's fp32 alphas_cumprod
-struct DpmppNode { double alpha, sigma, lambda; };
-static DpmppNode dpmpp_node(const float* acp, int t) {
+// The node-list solvers (DPM-Solver++: Lu et al. 2022, ldm models/diffusion/dpm_solver/sampler.py; UniPC: Zhao et al. 2023): alpha,
+// sigma and the half logSNR lambda of a timestep, in float64 from the model's fp32 alphas_cumprod
+struct SolverNode { double alpha, sigma, lambda; };
+static SolverNode solver_node(const float* acp, int t) {
     const double a = (double)acp[t];
     return {std::sqrt(a), std::sqrt(1.0 - a), 0.5 * std::log(a / (1.0 - a))};
+}
+
+// A node list as rdm_dpmpp_sample, rdm_unipc_sample and rdm_unipc_coefficients take it: at least 2 timesteps in [0, T - 1], strictly
+// decreasing, alphas_cumprod in (0, 1) at each.  Returns what is wrong with it, *at the node at fault.
+enum NodeFault { NODES_OK, NODES_TOO_FEW, NODE_OUT_OF_RANGE, NODE_NOT_DECREASING, NODE_ALPHA };
+static NodeFault check_nodes(const float* acp, int T, const int* nodes, int n_nodes, int* at) {
+    if (n_nodes < 2) return NODES_TOO_FEW;
+    for (int j = 0; j < n_nodes; j++) {
+        *at = j;
+        if (nodes[j] < 0 || nodes[j] >= T) return NODE_OUT_OF_RANGE;
+        if (j > 0 && nodes[j] >= nodes[j - 1]) return NODE_NOT_DECREASING;
+        if (!(acp[nodes[j]] > 0.f && acp[nodes[j]] < 1.f)) return NODE_ALPHA;
+    }
+    return NODES_OK;
+}
+// ... as the error of a sampler entry (who: the sampler's name)
+static int sampler_nodes(rdm_ctx* c, const char* who, const float* acp, int T, const int* nodes, int n_nodes) {
+    int j = 0;
+    switch (check_nodes(acp, T, nodes, n_nodes, &j)) {
+    case NODES_OK: return 0;
+    case NODES_TOO_FEW: return c->fail(-1, "%s needs at least 2 nodes, got %d", who, n_nodes);
+    case NODE_OUT_OF_RANGE: return c->fail(-1, "%s node %d = %d outside [0, %d]", who, j, nodes[j], T - 1);
+    case NODE_NOT_DECREASING: return c->fail(-1, "%s nodes must be strictly decreasing (node %d = %d after %d)", who, j, nodes[j], nodes[j - 1]);
+    default: return c->fail(-1, "alphas_cumprod[%d] = %g outside (0, 1)", nodes[j], (double)acp[nodes[j]]);
+    }
 }
 
 int rdm_dpmpp_timesteps(const float* alphas_cumprod, int T, int S, int skip_type, int* nodes_out) {
@@ -1955,7 +1999,7 @@ int rdm_dpmpp_timesteps(const float* alphas_cumprod, int T, int S, int skip_type
     std::vector<double> lam(T);
     for (int t = 0; t < T; t++) {
         if (!(alphas_cumprod[t] > 0.f && alphas_cumprod[t] < 1.f)) return -1;
-        lam[t] = dpmpp_node(alphas_cumprod, t).lambda;
+        lam[t] = solver_node(alphas_cumprod, t).lambda;
     }
     for (int i = 0; i <= S; i++) {        // logSNR: S + 1 targets uniform in lambda, each to the timestep of nearest lambda
         const double target = lam[T - 1] + (lam[0] - lam[T - 1]) * ((double)i / (double)S);
@@ -1968,34 +2012,24 @@ int rdm_dpmpp_timesteps(const float* alphas_cumprod, int T, int S, int skip_type
 }
 
 // The loop of rdm_dpmpp_sample's header comment: one forward and one dpmpp_step_kernel launch per step, the solver's coefficients computed
-// here in float64.  The history is ONE slot: the kernel reads m_{j-1} from it and writes m_j to it in the same pass.
+// here in float64.  The history is ONE buffer: the kernel reads m_{j-1} from it and writes m_j to it in the same pass.
 int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond,
                      float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->order != 1 && a->order != 2) return c->fail(-1, "dpm-solver++ order must be 1 or 2, got %d", a->order);
-    if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1");
-    const bool cfg = a->unconditional_guidance_scale > 1.0f;
-    if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1");
-    if (a->n_nodes < 2) return c->fail(-1, "dpm-solver++ needs at least 2 nodes, got %d", a->n_nodes);
-    for (int j = 0; j < a->n_nodes; j++) {
-        if (a->nodes[j] < 0 || a->nodes[j] >= a->T) return c->fail(-1, "dpm-solver++ node %d = %d outside [0, %d]", j, a->nodes[j], a->T - 1);
-        if (j > 0 && a->nodes[j] >= a->nodes[j - 1]) return c->fail(-1, "dpm-solver++ nodes must be strictly decreasing (node %d = %d after %d)", j, a->nodes[j], a->nodes[j - 1]);
-        const float ac = a->alphas_cumprod[a->nodes[j]];
-        if (!(ac > 0.f && ac < 1.f)) return c->fail(-1, "alphas_cumprod[%d] = %g outside (0, 1)", a->nodes[j], (double)ac);
-    }
+    bool cfg;
+    RDM_TRY(sampler_guidance(c, "dpm-solver++", a->unconditional_guidance_scale, uncond, &cfg));
+    RDM_TRY(sampler_nodes(c, "dpm-solver++", a->alphas_cumprod, a->T, a->nodes, a->n_nodes));
     const int n_steps = a->n_nodes - 1;
     const std::vector<int> ts(a->nodes, a->nodes + n_steps);
     SamplerRun run;
-    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr,
-                      SamplerRun::al((size_t)a->batch * a->channels * a->height * a->width * 4)));
-    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
-    float* m_slot = (float*)run.extra;
+    RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 1));
+    float* m_slot = run.extra[0];
     double h_prev = 0.0;
     for (int j = 0; j < n_steps; j++) {
-        const int index = n_steps - 1 - j;
-        const DpmppNode s = dpmpp_node(a->alphas_cumprod, a->nodes[j]), t = dpmpp_node(a->alphas_cumprod, a->nodes[j + 1]);
+        const SolverNode s = solver_node(a->alphas_cumprod, a->nodes[j]), t = solver_node(a->alphas_cumprod, a->nodes[j + 1]);
         const double h = t.lambda - s.lambda, g = -t.alpha * std::expm1(-h);       // x <- (sigma_t / sigma_s) x + g D
         const bool second = a->order == 2 && j >= 1 && !(a->lower_order_final && j == n_steps - 1);
         RDM_TRY(run.forward(j));
@@ -2008,10 +2042,10 @@ int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, cons
         } else {
             p.c_0 = (float)g;
         }
-        p.x_out = run.x; p.x_dup = run.x_dup; p.m_store = m_slot; p.pred_x0 = run.pred_x0_slot(index);
+        p.x_out = run.x; p.x_dup = run.x_dup; p.m_store = m_slot; p.pred_x0 = run.pred_x0_slot(j);
         RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
         h_prev = h;
-        RDM_TRY(run.log_x(index));
+        RDM_TRY(run.log_x(j));
     }
     return run.finish(z_out);
 }
@@ -2065,20 +2099,15 @@ static int unipc_order(int s, int n, int order, int lower_order_final) {
     return p;
 }
 
-int rdm_unipc_coefficients(const float* alphas_cumprod, int T, const int* nodes, int n_nodes, int j, int order, int variant, int corrector,
-                           int lower_order_final, double* out) {
-    if (!alphas_cumprod || !nodes || !out || T < 2 || n_nodes < 2 || j < 0 || j >= n_nodes - 1 || order < 1 || order > 3 ||
-        (variant != 0 && variant != 1)) return -1;
-    for (int i = 0; i < n_nodes; i++) {
-        if (nodes[i] < 0 || nodes[i] >= T || (i > 0 && nodes[i] >= nodes[i - 1])) return -1;
-        if (!(alphas_cumprod[nodes[i]] > 0.f && alphas_cumprod[nodes[i]] < 1.f)) return -1;
-    }
+// rdm_unipc_coefficients on a node list that check_nodes has passed (-1: a singular system)
+static int unipc_coefficients(const float* alphas_cumprod, const int* nodes, int n_nodes, int j, int order, int variant, int corrector,
+                              int lower_order_final, double* out) {
     const int n = n_nodes - 1;
-    auto node = [&](int i) { return dpmpp_node(alphas_cumprod, nodes[i]); };
+    auto node = [&](int i) { return solver_node(alphas_cumprod, nodes[i]); };
     std::vector<double> lamv((size_t)n_nodes);
     for (int i = 0; i < n_nodes; i++) lamv[(size_t)i] = node(i).lambda;
     const double* lam = lamv.data();
-    const DpmppNode cur = node(j), nxt = node(j + 1);
+    const SolverNode cur = node(j), nxt = node(j + 1);
     double a[5] = {0, 0, 0, 0, 0}, b[4] = {0, 0, 0, 0};
     int pc = 0;
     if (corrector && j >= 1) {                               // the correction of x_j: step j at its order, r_p = 1 for m_j itself
@@ -2119,6 +2148,14 @@ int rdm_unipc_coefficients(const float* alphas_cumprod, int T, const int* nodes,
     return 0;
 }
 
+int rdm_unipc_coefficients(const float* alphas_cumprod, int T, const int* nodes, int n_nodes, int j, int order, int variant, int corrector,
+                           int lower_order_final, double* out) {
+    int at;
+    if (!alphas_cumprod || !nodes || !out || T < 2 || n_nodes < 2 || j < 0 || j >= n_nodes - 1 || order < 1 || order > 3 ||
+        (variant != 0 && variant != 1) || check_nodes(alphas_cumprod, T, nodes, n_nodes, &at) != NODES_OK) return -1;
+    return unipc_coefficients(alphas_cumprod, nodes, n_nodes, j, order, variant, corrector, lower_order_final, out);
+}
+
 static void unipc_fill(UnipcStepParams& p, const double* co) {
     p.alpha = (float)co[0]; p.sigma = (float)co[1];
     p.a_x = (float)co[2]; p.a_t = (float)co[3]; p.a_1 = (float)co[4]; p.a_2 = (float)co[5]; p.a_3 = (float)co[6];
@@ -2127,7 +2164,7 @@ static void unipc_fill(UnipcStepParams& p, const double* co) {
 }
 
 // The loop of rdm_unipc_sample's header comment: one forward and one unipc_step_kernel launch per step.  The sampler's own scratch is
-// the kept (corrected) x and a ring of three m slots, rotated by pointer: the newest m takes the oldest slot in the pass that reads it.
+// the kept (corrected) x and a HistoryRing of m.
 int rdm_unipc_sample(rdm_ctx* c, const rdm_unipc_args* a, const float* x_T, const float* cond, const float* uncond,
                      float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
@@ -2135,47 +2172,33 @@ int rdm_unipc_sample(rdm_ctx* c, const rdm_unipc_args* a, const float* x_T, cons
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->order < 1 || a->order > 3) return c->fail(-1, "unipc order must be 1, 2 or 3, got %d", a->order);
     if (a->variant != 0 && a->variant != 1) return c->fail(-1, "unipc variant must be 0 (bh1) or 1 (bh2), got %d", a->variant);
-    if (a->unconditional_guidance_scale < 1.0f) return c->fail(-1, "unconditional_guidance_scale must be >= 1");
-    const bool cfg = a->unconditional_guidance_scale > 1.0f;
-    if (cfg && !uncond) return c->fail(-1, "unconditional_conditioning required when scale > 1");
-    if (a->n_nodes < 2) return c->fail(-1, "unipc needs at least 2 nodes, got %d", a->n_nodes);
-    for (int j = 0; j < a->n_nodes; j++) {
-        if (a->nodes[j] < 0 || a->nodes[j] >= a->T) return c->fail(-1, "unipc node %d = %d outside [0, %d]", j, a->nodes[j], a->T - 1);
-        if (j > 0 && a->nodes[j] >= a->nodes[j - 1]) return c->fail(-1, "unipc nodes must be strictly decreasing (node %d = %d after %d)", j, a->nodes[j], a->nodes[j - 1]);
-        const float ac = a->alphas_cumprod[a->nodes[j]];
-        if (!(ac > 0.f && ac < 1.f)) return c->fail(-1, "alphas_cumprod[%d] = %g outside (0, 1)", a->nodes[j], (double)ac);
-    }
+    bool cfg;
+    RDM_TRY(sampler_guidance(c, "unipc", a->unconditional_guidance_scale, uncond, &cfg));
+    RDM_TRY(sampler_nodes(c, "unipc", a->alphas_cumprod, a->T, a->nodes, a->n_nodes));
     const int n_steps = a->n_nodes - 1;
     std::vector<double> co((size_t)n_steps * 13);
     for (int j = 0; j < n_steps; j++)
-        if (rdm_unipc_coefficients(a->alphas_cumprod, a->T, a->nodes, a->n_nodes, j, a->order, a->variant, a->corrector, a->lower_order_final,
-                                   &co[(size_t)j * 13]) != 0) return c->fail(-1, "unipc coefficients of step %d are undefined on these nodes", j);
+        if (unipc_coefficients(a->alphas_cumprod, a->nodes, a->n_nodes, j, a->order, a->variant, a->corrector, a->lower_order_final,
+                               &co[(size_t)j * 13]) != 0) return c->fail(-1, "unipc coefficients of step %d are undefined on these nodes", j);
     const std::vector<int> ts(a->nodes, a->nodes + n_steps);
-    const size_t h_stride = SamplerRun::al((size_t)a->batch * a->channels * a->height * a->width * 4);
     SamplerRun run;
-    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, cfg ? uncond : nullptr, 4 * h_stride));
-    run.log_every_t = a->log_every_t; run.x_inter = x_inter; run.pred_x0_inter = pred_x0_inter;
-    float* xk = (float*)run.extra;
-    float* slot[3] = {(float*)(run.extra + h_stride), (float*)(run.extra + 2 * h_stride), (float*)(run.extra + 3 * h_stride)};
-    int n_hist = 0;                          // slot[0 .. n_hist) = m_{j-1}, m_{j-2}, m_{j-3}
+    RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 4));
+    float* xk = run.extra[0];
+    HistoryRing ring{{run.extra[1], run.extra[2], run.extra[3]}};          // h(0..2) = m_{j-1}, m_{j-2}, m_{j-3}
     for (int j = 0; j < n_steps; j++) {
-        const int index = n_steps - 1 - j;
         RDM_TRY(run.forward(j));
         UnipcStepParams p{};
         unipc_fill(p, &co[(size_t)j * 13]);
         const int nh = p.order_c > p.order_p - 1 ? p.order_c : p.order_p - 1;
-        if (nh > n_hist) return c->fail(-1, "unipc step %d needs %d earlier predictions, %d held", j, nh, n_hist);
+        if (nh > ring.held) return c->fail(-1, "unipc step %d needs %d earlier predictions, %d held", j, nh, ring.held);
         p.u = run.x; p.eps = run.eps; p.n = run.n1; p.cfg = cfg ? 1 : 0; p.scale = a->unconditional_guidance_scale;
         p.xc_prev = p.order_c >= 1 ? xk : nullptr;
-        p.h1 = nh >= 1 ? slot[0] : nullptr; p.h2 = nh >= 2 ? slot[1] : nullptr; p.h3 = nh >= 3 ? slot[2] : nullptr;
-        float* m_new = slot[n_hist < 3 ? n_hist : 2];          // a free slot, or the oldest m (read before it is overwritten)
+        p.h1 = nh >= 1 ? ring.h(0) : nullptr; p.h2 = nh >= 2 ? ring.h(1) : nullptr; p.h3 = nh >= 3 ? ring.h(2) : nullptr;
         p.xc_out = a->corrector ? xk : nullptr;                // without the corrector the kept x is the UNet input itself
-        p.u_next = run.x; p.x_dup = run.x_dup; p.m_store = m_new; p.pred_x0 = run.pred_x0_slot(index);
+        p.u_next = run.x; p.x_dup = run.x_dup; p.m_store = ring.next(); p.pred_x0 = run.pred_x0_slot(j);
         RDM_CHECK_HIP(c, launch_unipc_step(p, c->stream));
-        for (int i = n_hist < 3 ? n_hist : 2; i > 0; i--) slot[i] = slot[i - 1];
-        slot[0] = m_new;
-        if (n_hist < 3) n_hist++;
-        RDM_TRY(run.log_x(index));
+        ring.push();
+        RDM_TRY(run.log_x(j));
     }
     return run.finish(z_out);
 }
@@ -2190,7 +2213,7 @@ int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const 
     std::vector<int> ts(T);
     for (int i = 0; i < T; i++) ts[i] = i;
     SamplerRun run;
-    RDM_TRY(run.begin(c, a->batch, a->k, a->channels, a->height, a->width, ts, x_T, cond, nullptr, 0));
+    RDM_TRY(run.begin(c, a, ts, x_T, cond, nullptr, 0, nullptr, nullptr, 0));
     for (int n = 0, i = T - 1; i >= 0; i--, n++) {
         RDM_TRY(run.forward(i));
         DdpmStepParams p{};

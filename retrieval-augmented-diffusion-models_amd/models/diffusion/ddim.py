@@ -34,8 +34,8 @@ def make_ddim_sampling_parameters(alphacums, ddim_timesteps, eta, verbose=True):
 
 
 class _SamplerBase(object):
-    """What DDIMSampler, PLMSSampler, DPMSolverSampler and UniPCSampler share: the constructor, DDIM's schedule, and the rules the loops
-    apply around a step."""
+    """What DDIMSampler, PLMSSampler, DPMSolverSampler and UniPCSampler share: the constructor, DDIM's schedule, the guided model output
+    of the per-step paths, and the rules the loops apply around a step."""
 
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
@@ -85,6 +85,34 @@ class _SamplerBase(object):
     def _logs(index, log_every_t, total_steps):
         return index % log_every_t == 0 or index == total_steps - 1
 
+    @staticmethod
+    def _warn_batch(conditioning, batch_size):
+        if conditioning is not None and not isinstance(conditioning, (dict, list)):
+            if conditioning.shape[0] != batch_size:
+                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+
+    @staticmethod
+    def _intermediates(img, x_inter, pred_x0, to_cpu=False):
+        """The start latent, then what a native loop logged."""
+        mv = (lambda t: t.detach().cpu()) if to_cpu else (lambda t: t)
+        return {'x_inter': [img] + [mv(t) for t in x_inter], 'pred_x0': [img] + [mv(t) for t in pred_x0]}
+
+    def _model_output(self, x, t, c, uc, scale, score_corrector=None, corrector_kwargs=None, uncond_first=False):
+        """eps of the per-step paths: one forward, or (uc given and scale != 1) one forward of the doubled batch [c | uc] -- ldm's PLMS
+        order [uc | c] with uncond_first: the library's zero-context shortcut keys on TRAILING all-zero rows -- combined as
+        e_u + scale (e_c - e_u); then the score corrector."""
+        if uc is None or scale == 1.:
+            e_t = self.model.apply_model(x, t, c)
+        else:
+            b = x.shape[0]
+            out = self.model.apply_model(torch.cat([x] * 2), torch.cat([t] * 2), torch.cat([uc, c] if uncond_first else [c, uc]))
+            e_c, e_u = (out[b:], out[:b]) if uncond_first else (out[:b], out[b:])
+            e_t = e_u + scale * (e_c - e_u)
+        if score_corrector is not None:
+            assert getattr(self.model, "parameterization", "eps") == "eps"
+            e_t = score_corrector.modify_score(self.model, e_t, x, t, c, **(corrector_kwargs or {}))
+        return e_t
+
     def _masked_blend(self, img, mask, x0, ts, q_noise):
         """Inpainting: outside the mask keep the sample, inside take x0 noised to the step's timestep."""
         assert x0 is not None
@@ -111,9 +139,7 @@ class DDIMSampler(_SamplerBase):
                unconditional_conditioning=None, random_guiding='none', r_shape=None, retro_cond=None,
                return_neighbors=False, k_nn=None, ignore_noising=False, content_cond=None, style_cond=None,
                intermediates_to_cpu=False, **kwargs):
-        if conditioning is not None and not isinstance(conditioning, (dict, list)):
-            if conditioning.shape[0] != batch_size:
-                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        self._warn_batch(conditioning, batch_size)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         size = (batch_size,) + tuple(shape)
         return self.ddim_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -157,9 +183,7 @@ class DDIMSampler(_SamplerBase):
         z, xi, pi = self.model.ctx.ddim_sample(S, img, cond, unconditional_conditioning if unconditional_guidance_scale > 1. else None,
                                                self.alphas_cumprod, eta=eta, scale=unconditional_guidance_scale, noise=noise,
                                                log_every_t=log_every_t, temperature=temperature, want_intermediates=True)
-        mv = (lambda t: t.detach().cpu()) if intermediates_to_cpu else (lambda t: t)
-        intermediates = {'x_inter': [img] + [mv(t) for t in xi], 'pred_x0': [img] + [mv(t) for t in pi]}
-        return z.detach(), intermediates
+        return z.detach(), self._intermediates(img, xi, pi, intermediates_to_cpu)
 
     def _python_loop(self, cond, img, callback, img_callback, log_every_t, temperature, eta, scale, uc, to_cpu, mask=None,
                      x0=None, noise_dropout=0., score_corrector=None, corrector_kwargs=None, random_guiding='none',
@@ -203,7 +227,6 @@ class DDIMSampler(_SamplerBase):
     def p_sample_ddim(self, x, c, t, index, use_original_steps=False, quantize_denoised=False, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, noise=None, random_guider=None):
-        b = x.shape[0]
         assert unconditional_guidance_scale >= 1.
         if use_original_steps:
             raise NotImplementedError("use_original_steps: dead in the reference (ddim.py:249)")
@@ -211,14 +234,8 @@ class DDIMSampler(_SamplerBase):
             noise = torch.randn(x.shape, device=x.device)
         if unconditional_guidance_scale > 1.:
             assert unconditional_conditioning is not None
-            out = self.model.apply_model(torch.cat([x] * 2), torch.cat([t] * 2), torch.cat([c, unconditional_conditioning]))
-            e_t, e_u = out[:b], out[b:]
-            e_t = e_u + unconditional_guidance_scale * (e_t - e_u)
-        else:
-            e_t = self.model.apply_model(x, t, c)
-        if score_corrector is not None:
-            assert getattr(self.model, "parameterization", "eps") == "eps"
-            e_t = score_corrector.modify_score(self.model, e_t, x, t, c, **(corrector_kwargs or {}))
+        e_t = self._model_output(x, t, c, unconditional_conditioning if unconditional_guidance_scale > 1. else None,
+                                 unconditional_guidance_scale, score_corrector, corrector_kwargs)
         a_t = torch.full_like(e_t, float(self.ddim_alphas[index]))
         a_prev = torch.full_like(e_t, float(self.ddim_alphas_prev[index]))
         sigma_t = torch.full_like(e_t, float(self.ddim_sigmas[index]))

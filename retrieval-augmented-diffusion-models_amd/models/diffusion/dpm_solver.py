@@ -45,7 +45,11 @@ def dpmpp_coefficients(alphas_cumprod, s, t, h_prev=None):
     return math.sqrt(a_s), math.sqrt(1.0 - a_s), c_x, g * (1.0 + 1.0 / (2.0 * r)), -g / (2.0 * r), h
 
 
-class DPMSolverSampler(_SamplerBase):
+class _NodeListSampler(_SamplerBase):
+    """What DPMSolverSampler and UniPCSampler share: solvers over a strictly decreasing list of integer timesteps, one forward per step.
+    A subclass gives NAME (as its messages spell it), its option checks, its native call and its per-step update."""
+    NAME = None
+
     def __init__(self, model, **kwargs):
         super().__init__(model, **kwargs)
         ac = model.alphas_cumprod.detach().float().cpu()
@@ -58,6 +62,47 @@ class DPMSolverSampler(_SamplerBase):
             return np.asarray(timesteps, dtype=np.int64).reshape(-1)
         return _lib.dpmpp_timesteps(S, self.alphas_cumprod, skip_type).astype(np.int64)
 
+    def _prepare(self, S, batch_size, shape, conditioning, eta, x_T, scale, uc, skip_type, timesteps):
+        """The preamble of `sample` -> the node list, the conditioning, the unconditional one (None unless guided), the guidance scale
+        (1.0 unless guided), the start latent."""
+        if eta != 0:
+            raise ValueError(f'eta must be 0 for {self.NAME} (the solver is deterministic)')
+        if scale < 1.:
+            raise ValueError('unconditional_guidance_scale must be >= 1')
+        self._warn_batch(conditioning, batch_size)
+        cond = self._unwrap(conditioning, single=self.NAME)
+        uc = self._unwrap(uc)
+        nodes = self.make_nodes(S, skip_type, timesteps)
+        device = self.model.device
+        img = torch.randn((batch_size,) + tuple(shape), device=device) if x_T is None else x_T.to(device)
+        guided = uc is not None and scale != 1.
+        return nodes, cond, uc if guided else None, scale if guided else 1.0, img
+
+    def _python_loop(self, nodes, cond, img, uc, scale, update, callback, img_callback, log_every_t, score_corrector, corrector_kwargs,
+                     mask=None, x0=None, q_noise=None):
+        """Per-step path of `sample`: native apply_model per forward, then update(j, x, eps) -> (the next UNet input, m_j): the
+        solver's torch fp32 update with the library's coefficients."""
+        n_steps = len(nodes) - 1
+        T = self.alphas_cumprod.shape[0]
+        if n_steps < 1 or np.any(np.diff(nodes) >= 0) or nodes[0] >= T or nodes[-1] < 0:
+            raise ValueError(f"{self.NAME} nodes must be strictly decreasing timesteps in [0, {T - 1}], at least two")
+        intermediates = {'x_inter': [img], 'pred_x0': [img]}
+        for j in range(n_steps):
+            ts = torch.full((img.shape[0],), int(nodes[j]), device=img.device, dtype=torch.long)
+            if mask is not None:
+                img = self._masked_blend(img, mask, x0, ts, None if q_noise is None else q_noise[j])
+            img, m = update(j, img, self._model_output(img, ts, cond, uc, scale, score_corrector, corrector_kwargs))
+            if callback: callback(j)
+            if img_callback: img_callback(m, j)
+            if self._logs(n_steps - 1 - j, log_every_t, n_steps):
+                intermediates['x_inter'].append(img)
+                intermediates['pred_x0'].append(m)
+        return img, intermediates
+
+
+class DPMSolverSampler(_NodeListSampler):
+    NAME = "DPM-Solver++"
+
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
@@ -66,73 +111,38 @@ class DPMSolverSampler(_SamplerBase):
         """`order` (1 | 2), `skip_type` ("logSNR" | "time_uniform"), `lower_order_final` (None: on below 15 steps), `timesteps` (an
         explicit node list, strictly decreasing) and `q_noise` (explicit stack [steps, B, C, H, W] for q_sample of the masked region,
         per-step path) are [native]."""
-        if eta != 0:
-            raise ValueError('eta must be 0 for DPM-Solver++ (the solver is deterministic)')
         if order not in (1, 2):
             raise ValueError(f'DPM-Solver++ order must be 1 or 2, got {order!r}')
-        if unconditional_guidance_scale < 1.:
-            raise ValueError('unconditional_guidance_scale must be >= 1')
-        if conditioning is not None and not isinstance(conditioning, (dict, list)):
-            if conditioning.shape[0] != batch_size:
-                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
-        cond = self._unwrap(conditioning, single="DPM-Solver++")
-        uc = self._unwrap(unconditional_conditioning)
-        nodes = self.make_nodes(S, skip_type, timesteps)
+        nodes, cond, uc, scale, img = self._prepare(S, batch_size, shape, conditioning, eta, x_T, unconditional_guidance_scale,
+                                                    unconditional_conditioning, skip_type, timesteps)
         n_steps = len(nodes) - 1
         if lower_order_final is None:
             lower_order_final = n_steps < 15
-        device = self.model.device
-        size = (batch_size,) + tuple(shape)
-        img = torch.randn(size, device=device) if x_T is None else x_T.to(device)
         print(f"Running DPM-Solver++ Sampling (order {order}) with {n_steps} timesteps")
-        guided = uc is not None and unconditional_guidance_scale != 1.
-        scale = unconditional_guidance_scale if guided else 1.0
-        per_step = (callback is not None or img_callback is not None or quantize_x0 or mask is not None or x0 is not None or
-                    score_corrector is not None)
-        if per_step:
-            return self._python_loop(nodes, cond, img, callback, img_callback, log_every_t, order, lower_order_final, quantize_x0, mask,
-                                     x0, score_corrector, corrector_kwargs, scale, uc if guided else None, kwargs.get("q_noise"))
-        z, xi, pi = self.model.ctx.dpmpp_sample(nodes, img, cond, uc if guided else None, self.alphas_cumprod, scale=scale, order=order,
+        if (callback is not None or img_callback is not None or quantize_x0 or mask is not None or x0 is not None or
+                score_corrector is not None):
+            return self._python_loop(nodes, cond, img, uc, scale, self._update(nodes, order, lower_order_final, quantize_x0), callback,
+                                     img_callback, log_every_t, score_corrector, corrector_kwargs, mask, x0, kwargs.get("q_noise"))
+        z, xi, pi = self.model.ctx.dpmpp_sample(nodes, img, cond, uc, self.alphas_cumprod, scale=scale, order=order,
                                                 lower_order_final=lower_order_final, log_every_t=log_every_t, want_intermediates=True)
-        intermediates = {'x_inter': [img] + list(xi), 'pred_x0': [img] + list(pi)}
-        return z.detach(), intermediates
+        return z.detach(), self._intermediates(img, xi, pi)
 
-    def _python_loop(self, nodes, cond, img, callback, img_callback, log_every_t, order, lower_order_final, quantize_denoised, mask, x0,
-                     score_corrector, corrector_kwargs, scale, uc, q_noise):
-        """Per-step path of sample: native apply_model per forward, torch fp32 update with the library's coefficients."""
+    def _update(self, nodes, order, lower_order_final, quantize_denoised):
+        """The per-step path's update(j, x, eps) -> (x at node j + 1, m_j)."""
         ac = self.alphas_cumprod.numpy()
-        n_steps = len(nodes) - 1
-        if n_steps < 1 or np.any(np.diff(nodes) >= 0) or nodes[0] >= ac.shape[0] or nodes[-1] < 0:
-            raise ValueError(f"DPM-Solver++ nodes must be strictly decreasing timesteps in [0, {ac.shape[0] - 1}], at least two")
-        intermediates = {'x_inter': [img], 'pred_x0': [img]}
-        b = img.shape[0]
         f32 = lambda v: float(np.float32(v))
         m_prev, h_prev = None, None
-        for j in range(n_steps):
-            index = n_steps - 1 - j
-            ts = torch.full((b,), int(nodes[j]), device=img.device, dtype=torch.long)
-            if mask is not None:
-                img = self._masked_blend(img, mask, x0, ts, None if q_noise is None else q_noise[j])
-            if uc is None:
-                e = self.model.apply_model(img, ts, cond)
-            else:
-                out = self.model.apply_model(torch.cat([img] * 2), torch.cat([ts] * 2), torch.cat([cond, uc]))
-                e = out[b:] + scale * (out[:b] - out[b:])
-            if score_corrector is not None:
-                assert getattr(self.model, "parameterization", "eps") == "eps"
-                e = score_corrector.modify_score(self.model, e, img, ts, cond, **(corrector_kwargs or {}))
-            second = order == 2 and j >= 1 and not (lower_order_final and j == n_steps - 1)
+
+        def update(j, x, e):
+            nonlocal m_prev, h_prev
+            second = order == 2 and j >= 1 and not (lower_order_final and j == len(nodes) - 2)
             alpha_s, sigma_s, c_x, c_0, c_1, h_prev = dpmpp_coefficients(ac, int(nodes[j]), int(nodes[j + 1]), h_prev if second else None)
-            m = (img - f32(sigma_s) * e) / f32(alpha_s)
+            m = (x - f32(sigma_s) * e) / f32(alpha_s)
             if quantize_denoised:
                 m = self.model.quantize_first_stage(m)
-            img = f32(c_x) * img + f32(c_0) * m
+            x = f32(c_x) * x + f32(c_0) * m
             if second:
-                img = img + f32(c_1) * m_prev
+                x = x + f32(c_1) * m_prev
             m_prev = m
-            if callback: callback(j)
-            if img_callback: img_callback(m, j)
-            if self._logs(index, log_every_t, n_steps):
-                intermediates['x_inter'].append(img)
-                intermediates['pred_x0'].append(m)
-        return img, intermediates
+            return x, m
+        return update

@@ -29,9 +29,7 @@ class PLMSSampler(_SamplerBase):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, **kwargs):
-        if conditioning is not None and not isinstance(conditioning, (dict, list)):
-            if conditioning.shape[0] != batch_size:
-                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
+        self._warn_batch(conditioning, batch_size)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         size = (batch_size,) + tuple(shape)
         return self.plms_sampling(conditioning, size, callback=callback, img_callback=img_callback,
@@ -64,8 +62,7 @@ class PLMSSampler(_SamplerBase):
                                                unconditional_conditioning if guided else None, self.alphas_cumprod,
                                                scale=unconditional_guidance_scale if guided else 1.0, log_every_t=log_every_t,
                                                want_intermediates=True)
-        intermediates = {'x_inter': [img] + list(xi), 'pred_x0': [img] + list(pi)}
-        return z.detach(), intermediates
+        return z.detach(), self._intermediates(img, xi, pi)
 
     def _python_loop(self, cond, img, callback, img_callback, log_every_t, timesteps, quantize_denoised, mask, x0, score_corrector,
                      corrector_kwargs, scale, uc, q_noise):
@@ -106,18 +103,8 @@ class PLMSSampler(_SamplerBase):
         b = x.shape[0]
 
         def get_model_output(x, t):
-            if unconditional_conditioning is None or unconditional_guidance_scale == 1.:
-                e_t = self.model.apply_model(x, t, c)
-            else:
-                x_in = torch.cat([x] * 2)
-                t_in = torch.cat([t] * 2)
-                c_in = torch.cat([unconditional_conditioning, c])
-                e_t_uncond, e_t = self.model.apply_model(x_in, t_in, c_in).chunk(2)
-                e_t = e_t_uncond + unconditional_guidance_scale * (e_t - e_t_uncond)
-            if score_corrector is not None:
-                assert getattr(self.model, "parameterization", "eps") == "eps"
-                e_t = score_corrector.modify_score(self.model, e_t, x, t, c, **(corrector_kwargs or {}))
-            return e_t
+            return self._model_output(x, t, c, unconditional_conditioning, unconditional_guidance_scale, score_corrector, corrector_kwargs,
+                                      uncond_first=True)
 
         def get_x_prev_and_pred_x0(e_t, index):
             # sigma_t = 0 (eta = 0): dir_xt = (1 - a_prev - sigma_t**2).sqrt() * e_t and a zero noise term, as in ldm

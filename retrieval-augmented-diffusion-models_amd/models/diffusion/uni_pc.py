@@ -29,21 +29,11 @@ import numpy as np
 import torch
 
 from ... import _lib
-from .ddim import _SamplerBase
+from .dpm_solver import _NodeListSampler
 
 
-class UniPCSampler(_SamplerBase):
-    def __init__(self, model, **kwargs):
-        super().__init__(model, **kwargs)
-        ac = model.alphas_cumprod.detach().float().cpu()
-        assert ac.shape[0] == self.ddpm_num_timesteps, 'alphas have to be defined for each timestep'
-        self.register_buffer('alphas_cumprod', ac)
-
-    def make_nodes(self, S, skip_type="logSNR", timesteps=None):
-        """[native] the node list: `timesteps` as given, or the library's grid of S steps (the grids of DPMSolverSampler)."""
-        if timesteps is not None:
-            return np.asarray(timesteps, dtype=np.int64).reshape(-1)
-        return _lib.dpmpp_timesteps(S, self.alphas_cumprod, skip_type).astype(np.int64)
+class UniPCSampler(_NodeListSampler):
+    NAME = "UniPC"
 
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
@@ -53,8 +43,6 @@ class UniPCSampler(_SamplerBase):
                timesteps=None, **kwargs):
         """`order` (1 | 2 | 3: the predictor's), `variant` ("bh1" | "bh2"), `corrector`, `skip_type` ("logSNR" | "time_uniform"),
         `lower_order_final` and `timesteps` (an explicit node list, strictly decreasing) are [native]."""
-        if eta != 0:
-            raise ValueError('eta must be 0 for UniPC (the solver is deterministic)')
         if mask is not None or x0 is not None:
             raise ValueError('UniPC has no inpainting form (the predictor-corrector keeps two iterates; mask / x0 are not supported): '
                              'use DDIMSampler, PLMSSampler or DPMSolverSampler for inpainting')
@@ -62,52 +50,24 @@ class UniPCSampler(_SamplerBase):
             raise ValueError(f'UniPC order must be 1, 2 or 3, got {order!r}')
         if variant not in _lib.UNIPC_VARIANTS:
             raise ValueError(f'UniPC variant must be one of {sorted(_lib.UNIPC_VARIANTS)}, got {variant!r}')
-        if unconditional_guidance_scale < 1.:
-            raise ValueError('unconditional_guidance_scale must be >= 1')
-        if conditioning is not None and not isinstance(conditioning, (dict, list)):
-            if conditioning.shape[0] != batch_size:
-                print(f"Warning: Got {conditioning.shape[0]} conditionings but batch-size is {batch_size}")
-        cond = self._unwrap(conditioning, single="UniPC")
-        uc = self._unwrap(unconditional_conditioning)
-        nodes = self.make_nodes(S, skip_type, timesteps)
-        n_steps = len(nodes) - 1
-        device = self.model.device
-        size = (batch_size,) + tuple(shape)
-        img = torch.randn(size, device=device) if x_T is None else x_T.to(device)
-        print(f"Running UniPC Sampling (order {order}, {variant}, corrector {'on' if corrector else 'off'}) with {n_steps} timesteps")
-        guided = uc is not None and unconditional_guidance_scale != 1.
-        scale = unconditional_guidance_scale if guided else 1.0
+        nodes, cond, uc, scale, img = self._prepare(S, batch_size, shape, conditioning, eta, x_T, unconditional_guidance_scale,
+                                                    unconditional_conditioning, skip_type, timesteps)
+        print(f"Running UniPC Sampling (order {order}, {variant}, corrector {'on' if corrector else 'off'}) with {len(nodes) - 1} timesteps")
         solver = dict(order=order, variant=variant, corrector=bool(corrector), lower_order_final=bool(lower_order_final))
         if callback is not None or img_callback is not None or quantize_x0 or score_corrector is not None:
-            return self._python_loop(nodes, cond, img, callback, img_callback, log_every_t, solver, quantize_x0, score_corrector,
-                                     corrector_kwargs, scale, uc if guided else None)
-        z, xi, pi = self.model.ctx.unipc_sample(nodes, img, cond, uc if guided else None, self.alphas_cumprod, scale=scale,
-                                                log_every_t=log_every_t, want_intermediates=True, **solver)
-        intermediates = {'x_inter': [img] + list(xi), 'pred_x0': [img] + list(pi)}
-        return z.detach(), intermediates
+            return self._python_loop(nodes, cond, img, uc, scale, self._update(nodes, solver, quantize_x0), callback, img_callback,
+                                     log_every_t, score_corrector, corrector_kwargs)
+        z, xi, pi = self.model.ctx.unipc_sample(nodes, img, cond, uc, self.alphas_cumprod, scale=scale, log_every_t=log_every_t,
+                                                want_intermediates=True, **solver)
+        return z.detach(), self._intermediates(img, xi, pi)
 
-    def _python_loop(self, nodes, cond, img, callback, img_callback, log_every_t, solver, quantize_denoised, score_corrector,
-                     corrector_kwargs, scale, uc):
-        """Per-step path of sample: native apply_model per forward, torch fp32 updates with the library's coefficients, in the
-        kernel's association."""
+    def _update(self, nodes, solver, quantize_denoised):
+        """The per-step path's update(j, u_j, eps) -> (u_{j+1}, m_j), in the kernel's association."""
         ac = self.alphas_cumprod.numpy()
-        n_steps = len(nodes) - 1
-        if n_steps < 1 or np.any(np.diff(nodes) >= 0) or nodes[0] >= ac.shape[0] or nodes[-1] < 0:
-            raise ValueError(f"UniPC nodes must be strictly decreasing timesteps in [0, {ac.shape[0] - 1}], at least two")
-        intermediates = {'x_inter': [img], 'pred_x0': [img]}
-        b = img.shape[0]
-        u, xc, hist = img, img, []                   # hist: m_{j-1}, m_{j-2}, m_{j-3}
-        for j in range(n_steps):
-            index = n_steps - 1 - j
-            ts = torch.full((b,), int(nodes[j]), device=u.device, dtype=torch.long)
-            if uc is None:
-                e = self.model.apply_model(u, ts, cond)
-            else:
-                out = self.model.apply_model(torch.cat([u] * 2), torch.cat([ts] * 2), torch.cat([cond, uc]))
-                e = out[b:] + scale * (out[:b] - out[b:])
-            if score_corrector is not None:
-                assert getattr(self.model, "parameterization", "eps") == "eps"
-                e = score_corrector.modify_score(self.model, e, u, ts, cond, **(corrector_kwargs or {}))
+        xc, hist = None, []                          # the kept (corrected) iterate; m_{j-1}, m_{j-2}, m_{j-3}
+
+        def update(j, u, e):
+            nonlocal xc, hist
             co = _lib.unipc_coefficients(nodes, ac, j, **solver)
             alpha, sigma, a_x, a_t, a_1, a_2, a_3, b_x, b_0, b_1, b_2 = (float(np.float32(v)) for v in co[:11])
             order_c, order_p = int(co[11]), int(co[12])
@@ -124,9 +84,5 @@ class UniPCSampler(_SamplerBase):
             for b_i, h in zip((b_1, b_2)[:order_p - 1], hist):
                 u = u + b_i * h
             hist = [m] + hist[:2]
-            if callback: callback(j)
-            if img_callback: img_callback(m, j)
-            if self._logs(index, log_every_t, n_steps):
-                intermediates['x_inter'].append(u)
-                intermediates['pred_x0'].append(m)
-        return u, intermediates
+            return u, m
+        return update

@@ -16,6 +16,12 @@ def rel_l2(a: torch.Tensor, b: torch.Tensor) -> float:
     return float((a - b).norm() / (b.norm() + 1e-30))
 
 
+def within(tag, what, value, bound):
+    """Print the measured figure under `[tag]`, then hold it to the bound (a module binds its tag: partial(within, "plms"))."""
+    print(f"[{tag}] {what}: measured {value:.3e} (bound {bound:.1e})")
+    assert value <= bound, f"{what}: {value} > {bound}"
+
+
 def max_rel(a: torch.Tensor, b: torch.Tensor) -> float:
     a, b = a.double().cpu(), b.double().cpu()
     return float((a - b).abs().max() / (b.abs().max() + 1e-30))

@@ -2,6 +2,7 @@
 step of the loop against the D-form restatement of tests/_dpmpp_ref.py in deterministic mode, order 1 against the DDIM loop,
 DPMSolverSampler against the D-form loop over the CPU oracle UNet, batch independence in deterministic mode, errors, and the end-to-end
 entry."""
+import functools
 import math
 
 import numpy as np
@@ -12,7 +13,7 @@ from oracle import diffusion as odiff
 from oracle import unet as ounet
 
 import _dpmpp_ref as ref
-from _util import rel_l2
+from _util import rel_l2, within
 from test_gpu_plms import model, tiny  # noqa: F401  (fixtures: the tiny UNet on the session context, the tiny model)
 
 pytestmark = pytest.mark.gpu
@@ -23,9 +24,7 @@ UPDATE_TOL = 1e-5            # as the DDIM update in test_gpu_emul.py and the PL
 ACP = odiff.Schedule().alphas_cumprod
 
 
-def _within(what, value, bound):
-    print(f"[dpmpp] {what}: measured {value:.3e} (bound {bound:.1e})")
-    assert value <= bound, f"{what}: {value} > {bound}"
+_within = functools.partial(within, "dpmpp")
 
 
 # ---- the kernel alone

@@ -1,6 +1,7 @@
 """The native PLMS loop (rdm_plms_sample, fused update kernel) on the GPU: step by step against a torch restatement in deterministic mode,
 PLMSSampler against a PLMS loop over the CPU oracle UNet, batch independence in deterministic mode, errors, and the end-to-end entry."""
 import ctypes as C
+import functools
 
 import numpy as np
 import pytest
@@ -10,7 +11,7 @@ from oracle import diffusion as odiff
 from oracle import unet as ounet
 from oracle import vqdecoder as ovq
 
-from _util import rel_l2, spec_to_unet_cfg
+from _util import rel_l2, spec_to_unet_cfg, within
 
 pytestmark = pytest.mark.gpu
 torch.set_grad_enabled(False)
@@ -19,9 +20,7 @@ LATENT_TOL = 2.5e-2          # as test_gpu_surface.py's DDIM latent bound
 UPDATE_TOL = 1e-5            # as the DDIM update in test_gpu_emul.py
 
 
-def _within(what, value, bound):
-    print(f"[plms] {what}: measured {value:.3e} (bound {bound:.1e})")
-    assert value <= bound, f"{what}: {value} > {bound}"
+_within = functools.partial(within, "plms")
 
 
 @pytest.fixture(scope="module")

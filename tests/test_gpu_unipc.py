@@ -1,6 +1,7 @@
 """The native UniPC loop (rdm_unipc_sample, fused predict-and-correct kernel) on the GPU: the kernel alone per element against float64,
 every step of the loop teacher-forced against the D-form restatement of tests/_unipc_ref.py in deterministic mode, UniPCSampler against
 the D-form loop over the CPU oracle UNet, batch independence in deterministic mode, errors, and the end-to-end entry."""
+import functools
 import itertools
 
 import numpy as np
@@ -12,7 +13,7 @@ from oracle import unet as ounet
 
 import _dpmpp_ref as dref
 import _unipc_ref as ref
-from _util import rel_l2
+from _util import rel_l2, within
 from test_gpu_plms import model, tiny  # noqa: F401  (fixtures: the tiny UNet on the session context, the tiny model)
 
 pytestmark = pytest.mark.gpu
@@ -24,9 +25,7 @@ ACP = odiff.Schedule().alphas_cumprod
 NODES10 = dref.timesteps(ACP.numpy(), 10, "logSNR")
 
 
-def _within(what, value, bound):
-    print(f"[unipc] {what}: measured {value:.3e} (bound {bound:.1e})")
-    assert value <= bound, f"{what}: {value} > {bound}"
+_within = functools.partial(within, "unipc")
 
 
 # ---- the kernel alone
