@@ -222,6 +222,36 @@ int rdm_unipc_coefficients(const float* alphas_cumprod, int T, const int* nodes,
 int rdm_ddpm_sample(rdm_ctx* ctx, const rdm_ddpm_args* args, const float* x_T, const float* cond, const float* noise,
                     float* z_out);
 
+/* ---- device noise ------------------------------------------------------------------------------
+ * The library's own definition of "sample i of seed s": Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85, ten rounds) with
+ *     key        = (seed low 32 bits, seed high 32 bits)
+ *     counter[0] = block   = (element index WITHIN the sample row) >> 2
+ *     counter[1] = step    = draw index: the loop step counted from 0 in loop order (the i-th step taken)
+ *     counter[2] = row     = GLOBAL sample index, row0 + b
+ *     counter[3] = stream  = 0: the starting latent x_T (step 0) | 1: per-step update noise | >= 2: reserved, refused by the entries
+ * Element e of a row takes output word e & 3 of block e >> 2: rows never share a block, and a value depends on (seed, stream, step, row, e)
+ * only -- not on the batch size, on how row0 splits a batch, on the grid or on the vector width.  Normals are Box-Muller on the word pairs
+ * (w0, w1) and (w2, w3): u = ((w >> 9) + 0.5) 2^-23 (exact in fp32, strictly inside (0, 1), so |z| <= 5.77), r = sqrtf(-2 logf(u1)),
+ * sincospif(2 u2, &s, &c); element 2h = r c, element 2h + 1 = r s of pair h.  row0 + B must fit 32 bits and per_row must be at most 2^34.
+ *
+ * rdm_rng_words: host code only (ctx-free): the four words of one block, out[4] [host].  Returns 0, -1 for a null out.
+ * rdm_op_rng_words / rdm_op_randn: the word / the normal each element of B rows of per_row elements would consume at (step, stream), rows
+ * row0 .. row0 + B - 1; out [dev] [B, per_row] (uint32 / f32).  Any per_row >= 1 (a row's last block may be partial); an out that is not
+ * 16-byte aligned, or a per_row that is no multiple of 4, takes scalar stores. */
+int rdm_rng_words(uint64_t seed, uint32_t row, uint32_t step, uint32_t stream, uint32_t block, uint32_t* out);
+int rdm_op_rng_words(rdm_ctx* ctx, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, uint32_t* out);
+int rdm_op_randn(rdm_ctx* ctx, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, float* out);
+/* rdm_ddim_sample / rdm_ddpm_sample without a noise stack: loop step i applies the normals of (seed, stream 1, step i, row0 + b), generated
+ * in registers in the pass that applies them -- bit for bit the loop fed with a stack of rdm_op_randn(step = i) outputs.  x_T may be NULL:
+ * the start is then the normals of (seed, stream 0, step 0).  With eta == 0 the DDIM entry draws no step noise and equals rdm_ddim_sample;
+ * the final DDPM step consumes none, as in rdm_ddpm_sample.  channels * height * width must be a multiple of 4.  Other arguments as the
+ * stack entries. */
+int rdm_ddim_sample_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
+                           const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter);
+int rdm_ddpm_sample_seeded(rdm_ctx* ctx, const rdm_ddpm_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
+                           float* z_out);
+
 /* ---- first stage: LatentDiffusion.decode_first_stage -> VQModelInterface.decode
  *      (called at rdm/models/diffusion/ddpm.py:840, 981). z [dev] f32 [b,3,h,w] -> img [dev] f32 [b,3,H,W];
  * indices_out [dev] int32 [b*h*w] or NULL. */

@@ -131,6 +131,11 @@ SIGNATURES = {
     "rdm_unipc_coefficients": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(C.c_double)]),
     "rdm_ddpm_sample": (C.c_int, [_P, C.POINTER(DdpmArgs), _P, _P, _P, _P]),
+    "rdm_rng_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
+    "rdm_op_rng_words": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P]),
+    "rdm_op_randn": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P]),
+    "rdm_ddim_sample_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "rdm_ddpm_sample_seeded": (C.c_int, [_P, C.POINTER(DdpmArgs), C.c_uint64, C.c_int64, _P, _P, _P]),
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
     "rdm_vq_quantize": (C.c_int, [_P, _P, C.c_int, _P, _P]),
@@ -428,6 +433,24 @@ def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):
     return out[:n].copy()
 
 
+def rng_words(seed, row, step, stream, block):
+    """The four Philox4x32-10 words of one block of the library's noise generator (rdm_rng_words; host code, no context needed): key =
+    the 64-bit seed, counter = (block, step, row, stream).  -> uint32 numpy array [4]."""
+    out = np.zeros((4,), dtype=np.uint32)
+    if lib.rdm_rng_words(int(seed) & (2 ** 64 - 1), int(row), int(step), int(stream), int(block), out.ctypes.data_as(C.POINTER(C.c_uint32))) != 0:
+        raise RdmError("rng_words: bad arguments")
+    return out
+
+
+def _noise_seed(what, seed, row0, B):
+    """The (seed, row0) of a device-noise call, checked before any pointer crosses the ABI: the seed modulo 2^64, rows [row0, row0 + B)
+    32-bit counters."""
+    row0 = int(row0)
+    if row0 < 0 or row0 + int(B) >= 2 ** 32:
+        raise RdmError(f"{what}: rows [row0, row0 + B) must be non-negative and row0 + B must fit 32 bits, got row0={row0}, B={int(B)}")
+    return int(seed) & (2 ** 64 - 1), row0
+
+
 def _unipc_variant(what, variant):
     if variant not in UNIPC_VARIANTS:
         raise RdmError(f"{what}: variant must be one of {sorted(UNIPC_VARIANTS)}, got {variant!r}")
@@ -698,12 +721,16 @@ class Context:
         return out
 
     def _sampler_call(self, what, fn, Args, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=None, nodes=None,
-                      noise=None, **fields):
+                      noise=None, x_shape=None, **fields):
         """What ddim_sample, plms_sample, dpmpp_sample and unipc_sample share: device casts, the fp32 alphas_cumprod array, the step
         count (of DDIM's S-step schedule, or of the node list), shape and guidance checks, the outputs.  Args(**fields) plus the fields
         every sampler has is the argument struct, fn(handle, args, x_T, cond, uncond, z, x_inter, pred_x0_inter) the library call;
-        noise: a [steps, B, C, H, W] stack to shape-check.  -> (z, x_inter, pred_x0_inter)."""
+        noise: a [steps, B, C, H, W] stack to shape-check; x_shape: the latent shape of a seeded call without x_T (fn then gets a null
+        x_T and the library draws the start).  -> (z, x_inter, pred_x0_inter)."""
         x_T, cond, uncond = (None if t is None else self._dev(t, torch.float32) for t in (x_T, cond, uncond))
+        x_arg = x_T
+        if x_T is None:
+            x_T = torch.empty(tuple(int(v) for v in x_shape), device="meta", dtype=torch.float32)     # shapes only
         ac = _acp_array(alphas_cumprod)
         if nodes is None:
             steps = len(range(0, ac.shape[0], max(ac.shape[0] // max(int(S), 1), 1)))
@@ -718,21 +745,67 @@ class Context:
         B, Cc, H, W = x_T.shape
         a = Args(batch=B, k=cond.shape[1], channels=Cc, height=H, width=W, unconditional_guidance_scale=scale, log_every_t=log_every_t,
                  T=ac.shape[0], alphas_cumprod=ac.ctypes.data_as(C.POINTER(C.c_float)), **fields)
-        z = torch.empty_like(x_T)
+        z = torch.empty(tuple(x_T.shape), device=self.device, dtype=torch.float32)
         xi = pi = None
         if want_intermediates:
             n = lib.rdm_ddim_num_intermediates(steps, log_every_t)
             xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
             pi = torch.empty_like(xi)
-        self._check(fn(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
+        self._check(fn(self._h, C.byref(a), _ptr(x_arg), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
         return z, xi, pi
 
     def ddim_sample(self, S, x_T, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
-                    temperature=1.0, want_intermediates=False):
-        noise = None if noise is None else self._dev(noise, torch.float32)         # (its shape matters only when it is used)
-        return self._sampler_call("ddim_sample", lambda h, a, x, c, u, *out: lib.rdm_ddim_sample(h, a, x, c, u, _ptr(noise), *out), DdimArgs,
-                                  x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
-                                  noise=noise if eta != 0.0 else None, eta=eta, temperature=temperature)
+                    temperature=1.0, want_intermediates=False, seed=None, row0=0, shape=None):
+        """rdm_ddim_sample; with `seed` rdm_ddim_sample_seeded: step i's noise is the library's own (seed, stream 1, step i, row0 + b),
+        generated in the step kernel (no stack; `noise` must then be None), and x_T may be None -- the start is then drawn from stream 0
+        at the latent `shape` (C, H, W), for cond.shape[0] rows."""
+        if seed is None:
+            if x_T is None:
+                raise RdmError("ddim_sample: x_T is required without a seed")
+            noise = None if noise is None else self._dev(noise, torch.float32)         # (its shape matters only when it is used)
+            return self._sampler_call("ddim_sample", lambda h, a, x, c, u, *out: lib.rdm_ddim_sample(h, a, x, c, u, _ptr(noise), *out), DdimArgs,
+                                      x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+                                      noise=noise if eta != 0.0 else None, eta=eta, temperature=temperature)
+        if noise is not None:
+            raise RdmError("ddim_sample: give a seed or a noise stack, not both")
+        x_shape = self._seeded_shape("ddim_sample", x_T, cond, shape)
+        seed, row0 = _noise_seed("ddim_sample", seed, row0, x_shape[0])
+        return self._sampler_call("ddim_sample", lambda h, a, x, c, u, *out: lib.rdm_ddim_sample_seeded(h, a, seed, row0, x, c, u, *out),
+                                  DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+                                  x_shape=x_shape, eta=eta, temperature=temperature)
+
+    @staticmethod
+    def _seeded_shape(what, x_T, cond, shape):
+        """(B, C, H, W) of a seeded sampling call: x_T's, or cond's rows at the given latent shape (C, H, W)."""
+        if x_T is not None:
+            return tuple(x_T.shape)
+        if shape is None or len(tuple(shape)) != 3:
+            raise RdmError(f"{what}: a seeded call without x_T needs the latent shape (C, H, W)")
+        return (int(cond.shape[0]),) + tuple(int(v) for v in shape)
+
+    def _rng_fill(self, what, fn, dtype, seed, B, per_row, row0, step, stream, out):
+        B, per_row, step, stream = int(B), int(per_row), int(step), int(stream)
+        if B < 1 or per_row < 1:
+            raise RdmError(f"{what}: B and per_row must be >= 1, got B={B}, per_row={per_row}")
+        if not (0 <= step < 2 ** 32 and 0 <= stream < 2 ** 32):
+            raise RdmError(f"{what}: step and stream are 32-bit counters, got step={step}, stream={stream}")
+        seed, row0 = _noise_seed(what, seed, row0, B)
+        if out is None:
+            out = torch.empty((B, per_row), device=self.device, dtype=dtype)
+        elif out.dtype != dtype or out.numel() != B * per_row or not out.is_cuda:
+            raise RdmError(f"{what}: out must be a {dtype} device tensor of B * per_row = {B * per_row} elements")
+        self._check(fn(self._h, seed, row0, B, per_row, step, stream, _ptr(out)))
+        return out
+
+    def op_rng_words(self, seed, B, per_row, row0=0, step=0, stream=0, out=None):
+        """The Philox word each element of rows row0 .. row0 + B - 1 consumes at (step, stream): int32 [B, per_row] holding the uint32 bits
+        (rdm_op_rng_words; include/rdm_hip.h "device noise").  out: an int32 device tensor of B * per_row elements to write into."""
+        return self._rng_fill("op_rng_words", lib.rdm_op_rng_words, torch.int32, seed, B, per_row, row0, step, stream, out)
+
+    def op_randn(self, seed, B, per_row, row0=0, step=0, stream=0, out=None):
+        """The library's normals: f32 [B, per_row], row b element e a function of (seed, stream, step, row0 + b, e) only (rdm_op_randn).
+        stream 0 / step 0 is the starting latent of the seeded samplers, stream 1 / step i the update noise of loop step i."""
+        return self._rng_fill("op_randn", lib.rdm_op_randn, torch.float32, seed, B, per_row, row0, step, stream, out)
 
     def plms_sample(self, S, x_T, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False):
         """ldm PLMSSampler's loop (eta = 0) on DDIM's schedule: S' + 1 UNet forwards for S' sampler timesteps.  Returns
@@ -795,8 +868,23 @@ class Context:
                                           float(scale), co.ctypes.data_as(C.POINTER(C.c_double)), _ptr(xc_out), _ptr(u_next), _ptr(x_dup),
                                           _ptr(m_store), _ptr(pred_x0)))
 
-    def ddpm_sample(self, timesteps, x_T, cond, noise, sched, clip_denoised=True, temperature=1.0):
-        x_T = self._dev(x_T, torch.float32); cond = self._dev(cond, torch.float32); noise = self._dev(noise, torch.float32)
+    def ddpm_sample(self, timesteps, x_T, cond, noise=None, sched=None, clip_denoised=True, temperature=1.0, seed=None, row0=0, shape=None):
+        """rdm_ddpm_sample on a noise stack [timesteps, B, C, H, W]; with `seed` (and no stack) rdm_ddpm_sample_seeded: the library's own
+        noise, generated in the step kernel, and x_T may be None (drawn from stream 0 at the latent `shape` (C, H, W))."""
+        if sched is None:
+            raise RdmError("ddpm_sample: the schedule arrays are required")
+        if seed is not None and noise is not None:
+            raise RdmError("ddpm_sample: give a seed or a noise stack, not both")
+        if seed is None and (noise is None or x_T is None):
+            raise RdmError("ddpm_sample: x_T and a noise stack are required without a seed")
+        cond = self._dev(cond, torch.float32)
+        x_arg = x_T = None if x_T is None else self._dev(x_T, torch.float32)
+        noise = None if noise is None else self._dev(noise, torch.float32)
+        if seed is not None:
+            x_shape = self._seeded_shape("ddpm_sample", x_T, cond, shape)
+            seed, row0 = _noise_seed("ddpm_sample", seed, row0, x_shape[0])
+            if x_T is None:
+                x_T = torch.empty(x_shape, device="meta", dtype=torch.float32)     # shapes only
         arrs = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for k, v in sched.items()}
         fp = lambda k: arrs[k].ctypes.data_as(C.POINTER(C.c_float))
         self._check_sampler_shapes("ddpm_sample", x_T, cond, None, noise, int(timesteps))
@@ -807,8 +895,11 @@ class Context:
                      sqrt_recipm1_alphas_cumprod=fp("sqrt_recipm1_alphas_cumprod"),
                      posterior_mean_coef1=fp("posterior_mean_coef1"), posterior_mean_coef2=fp("posterior_mean_coef2"),
                      posterior_log_variance_clipped=fp("posterior_log_variance_clipped"))
-        z = torch.empty_like(x_T)
-        self._check(lib.rdm_ddpm_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(noise), _ptr(z)))
+        z = torch.empty(tuple(x_T.shape), device=self.device, dtype=torch.float32)
+        if seed is not None:
+            self._check(lib.rdm_ddpm_sample_seeded(self._h, C.byref(a), seed, row0, _ptr(x_arg), _ptr(cond), _ptr(z)))
+        else:
+            self._check(lib.rdm_ddpm_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(noise), _ptr(z)))
         return z
 
     def vq_decode(self, z, force_not_quantize=False, return_indices=False):

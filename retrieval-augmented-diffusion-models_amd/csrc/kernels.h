@@ -143,6 +143,12 @@ struct DdpmStepParams {
     float sqrt_recip, sqrt_recipm1, coef1, coef2, log_var; int clip, nonzero; float temperature;
 };
 
+// Device noise (philox.h).  StepRngParams: what a seeded step kernel adds to the step's own parameters -- the noise of element e of row b
+// is the normal of (seed, stream 1, step, row0 + b, e), per_row = C*H*W elements per sample row.  RngFillParams: rows x per_row words or
+// normals of one (step, stream) into out.
+struct StepRngParams { unsigned long long seed; long long per_row; uint32_t row0, step; };
+struct RngFillParams { unsigned long long seed; long long rows, per_row; uint32_t row0, step, stream; uint32_t* out; };
+
 // RARM decode step (rarm.hip)
 struct RarmAttnParams {
     const bf16_t* q; int ldq;                 // q[b*ldq + h*64 + d]; k_new / v_new share ldq (one fused qkv row per sequence)
@@ -303,6 +309,9 @@ hipError_t launch_add_bias_rows(const bf16_t* x, const float* bias, bf16_t* out,
 hipError_t launch_row_nonzero(const float* x, int rows, long long n, int* flag, hipStream_t st);   // flag[r] = row r has a non-zero element
 hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st);
 hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st);
+hipError_t launch_ddim_step_seeded(const DdimStepParams& p, const StepRngParams& g, hipStream_t st);   // p.noise unused; n, per_row % 4 == 0, operands 16-byte aligned
+hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams& g, hipStream_t st);
+hipError_t launch_rng_fill(const RngFillParams& p, bool normal, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
 hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);
 hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st);

@@ -1,5 +1,6 @@
 // Small / bandwidth-bound kernels around the GEMM core (gfx950).
 #include "kernels.h"
+#include "philox.h"
 
 // ------------------------------------------------------------------ stem conv: few input channels
 typedef float f2_t __attribute__((ext_vector_type(2)));
@@ -747,6 +748,125 @@ __global__ void ddpm_step_kernel(DdpmStepParams p) {
 hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st) {
     int grid = (int)((p.n + 255) / 256); if (grid > 2048) grid = 2048;
     ddpm_step_kernel<<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ device noise (philox.h)
+// One element of the DDIM / DDPM update on a noise value z held in a register: the expressions of ddim_step_kernel / ddpm_step_kernel, term
+// for term.  Those two kernels keep their own text (routed through these functions hipcc vectorises their kernel-argument loads and
+// un-fuses two of ddpm_step_kernel's FMAs: other bits), and add the noise term after a branch, so never fused into the sum; here it is
+// always present, and joins the sum in a block without FMA contraction.  Both forms then round alike.
+struct DdimStepScalars { float sa, sap, dirc; };
+__device__ __forceinline__ DdimStepScalars ddim_step_scalars(const DdimStepParams& p) {
+    return {sqrtf(p.a_t), sqrtf(p.a_prev), sqrtf(1.0f - p.a_prev - p.sigma_t * p.sigma_t)};
+}
+__device__ __forceinline__ float ddim_update(const DdimStepParams& p, const DdimStepScalars& s, float e, float eu, float x, float z, float& x0) {
+    if (p.cfg) e = eu + p.scale * (e - eu);
+    x0 = (x - p.sqrt_one_minus_at * e) / s.sa;
+    const float dir = s.dirc * e;
+    const float nz = p.sigma_t * z * p.temperature;
+    const float det = s.sap * x0 + dir;
+    {
+#pragma clang fp contract(off)
+        return det + nz;
+    }
+}
+__device__ __forceinline__ float ddpm_update(const DdpmStepParams& p, float sd, float x, float eps, float z) {
+    float x0 = p.sqrt_recip * x - p.sqrt_recipm1 * eps;
+    if (p.clip) x0 = fminf(1.f, fmaxf(-1.f, x0));
+    const float mean = p.coef1 * x0 + p.coef2 * x;
+    const float nz = p.nonzero ? sd * z * p.temperature : 0.f;
+    {
+#pragma clang fp contract(off)
+        return mean + nz;
+    }
+}
+// The DDIM / DDPM updates with the step's noise generated in registers, in the pass that applies it: a thread takes ONE Philox block --
+// four consecutive elements of one sample row (per_row % 4 == 0: rows never share a block) -- derives (row, block) from its flat vector
+// index, and applies the update to the four normals.  The loop is bit-identical to a stack loop fed with rdm_op_randn's output
+// (tests/test_gpu_device_noise.py holds it to that).  float4 accesses throughout (the launcher checks alignment).
+__global__ __launch_bounds__(256) void ddim_step_seeded_kernel(DdimStepParams p, StepRngParams g) {
+    const DdimStepScalars s = ddim_step_scalars(p);
+    const long long nv = p.n_per_batch >> 2, bpr = g.per_row >> 2;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * 4, r = v / bpr;
+        float z[4], e[4], u[4] = {}, x[4], xp[4], x0[4];
+        philox_normal4(g.seed, (uint32_t)(v - r * bpr), g.step, g.row0 + (uint32_t)r, RDM_RNG_STREAM_STEP, z);
+        step_ld<4>(p.eps, i, e);
+        if (p.cfg) step_ld<4>(p.eps + p.n_per_batch, i, u);
+        step_ld<4>(p.x, i, x);
+#pragma unroll
+        for (int k = 0; k < 4; k++) xp[k] = ddim_update(p, s, e[k], u[k], x[k], z[k], x0[k]);
+        step_st<4>(p.x_prev, i, xp);
+        if (p.x_dup) step_st<4>(p.x_dup, i, xp);
+        if (p.pred_x0) step_st<4>(p.pred_x0, i, x0);
+    }
+}
+__global__ __launch_bounds__(256) void ddpm_step_seeded_kernel(DdpmStepParams p, StepRngParams g) {
+    const float sd = p.nonzero ? expf(0.5f * p.log_var) : 0.f;
+    const long long nv = p.n >> 2, bpr = g.per_row >> 2;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * 4, r = v / bpr;
+        float z[4], e[4], x[4], xp[4];
+        philox_normal4(g.seed, (uint32_t)(v - r * bpr), g.step, g.row0 + (uint32_t)r, RDM_RNG_STREAM_STEP, z);
+        step_ld<4>(p.eps, i, e);
+        step_ld<4>(p.x, i, x);
+#pragma unroll
+        for (int k = 0; k < 4; k++) xp[k] = ddpm_update(p, sd, x[k], e[k], z[k]);
+        step_st<4>(p.x_prev, i, xp);
+    }
+}
+// The seeded step kernels have no scalar form: n and per_row multiples of 4 (per_row dividing n), every operand 16-byte aligned.
+static bool seeded_step_ok(long long n, long long per_row, std::initializer_list<const void*> ptrs) {
+    bool ok = n > 0 && per_row > 0 && per_row % 4 == 0 && n % per_row == 0;
+    for (const void* q : ptrs) ok = ok && ((uintptr_t)q % 16 == 0);
+    return ok;
+}
+hipError_t launch_ddim_step_seeded(const DdimStepParams& p, const StepRngParams& g, hipStream_t st) {
+    if (!seeded_step_ok(p.n_per_batch, g.per_row, {p.x, p.eps, p.eps + (p.cfg ? p.n_per_batch : 0), p.x_prev, p.x_dup, p.pred_x0})) return hipErrorInvalidValue;
+    const int grid = (int)std::min<long long>((p.n_per_batch / 4 + 255) / 256, 2048);
+    ddim_step_seeded_kernel<<<grid, 256, 0, st>>>(p, g);
+    return hipGetLastError();
+}
+hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams& g, hipStream_t st) {
+    if (!seeded_step_ok(p.n, g.per_row, {p.x, p.eps, p.x_prev})) return hipErrorInvalidValue;
+    const int grid = (int)std::min<long long>((p.n / 4 + 255) / 256, 2048);
+    ddpm_step_seeded_kernel<<<grid, 256, 0, st>>>(p, g);
+    return hipGetLastError();
+}
+
+// What each element of B rows of per_row elements would consume: the Philox word (NORMAL = false) or the normal made of it, one block
+// of four elements per thread.  V = 4: one 16-byte store (per_row % 4 == 0 and out aligned); V = 1: scalar stores, a row's last block cut
+// at the row's end (any per_row >= 1, any 4-byte aligned out).
+template <bool NORMAL, int V>
+__global__ __launch_bounds__(256) void rng_fill_kernel(RngFillParams p) {
+    const long long bpr = (p.per_row + 3) >> 2, nblk = p.rows * bpr;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nblk; v += (long long)gridDim.x * 256) {
+        const long long r = v / bpr, b = v - r * bpr;
+        uint32_t w[4];
+        philox4x32_10(p.seed, (uint32_t)b, p.step, p.row0 + (uint32_t)r, p.stream, w);
+        if constexpr (NORMAL) {
+            float z[4];
+            box_muller(w[0], w[1], z[0], z[1]);
+            box_muller(w[2], w[3], z[2], z[3]);
+#pragma unroll
+            for (int k = 0; k < 4; k++) w[k] = __float_as_uint(z[k]);
+        }
+        uint32_t* dst = p.out + r * p.per_row + b * 4;
+        if constexpr (V == 4) *(uint4*)dst = make_uint4(w[0], w[1], w[2], w[3]);
+        else {
+            const long long left = p.per_row - b * 4;
+#pragma unroll
+            for (int k = 0; k < 4; k++) if (k < left) dst[k] = w[k];
+        }
+    }
+}
+hipError_t launch_rng_fill(const RngFillParams& p, bool normal, hipStream_t st) {
+    if (p.rows <= 0 || p.per_row <= 0) return hipErrorInvalidValue;
+    const bool vec = p.per_row % 4 == 0 && (uintptr_t)p.out % 16 == 0;
+    const long long nblk = p.rows * ((p.per_row + 3) >> 2);
+    const int grid = (int)std::min<long long>((nblk + 255) / 256, 2048);
+    (normal ? (vec ? rng_fill_kernel<true, 4> : rng_fill_kernel<true, 1>) : (vec ? rng_fill_kernel<false, 4> : rng_fill_kernel<false, 1>))<<<grid, 256, 0, st>>>(p);
     return hipGetLastError();
 }
 

@@ -26,6 +26,7 @@
 #include "../../include/rdm_hip.h"
 #include "kernels.h"
 #include "knn.h"
+#include "philox.h"
 
 #define RDM_CHECK_HIP(ctx, expr)                                                            \
     do {                                                                                    \
@@ -1803,6 +1804,17 @@ static int sampler_emb_table(rdm_ctx* c, const std::vector<int>& ts, const float
 // conditioning's K/V, uploads the timestep table and the time-embedding table of ts, and copies x_T into x (both halves of a guided
 // batch: nb = 2B, [x | x] against [cond | uncond]; later steps' kernels write both halves through x_dup).  forward(idx) is then the
 // UNet at ts[idx] on x into eps.
+// Device noise (philox.h): the seed and the global index of the call's first sample row
+struct NoiseSeed { uint64_t seed; int64_t row0; };
+// rows [row0, row0 + B) must be 32-bit row counters and a row's block counter must fit 32 bits (per_row <= 2^34)
+static int check_noise_rows(rdm_ctx* c, const char* who, int64_t row0, int64_t B, int64_t per_row) {
+    if (B < 1 || per_row < 1) return c->fail(-1, "%s: B and per_row must be >= 1 (B=%lld, per_row=%lld)", who, (long long)B, (long long)per_row);
+    if (row0 < 0 || row0 > 0xFFFFFFFFll || B > 0xFFFFFFFFll - row0)
+        return c->fail(-1, "%s: row0 + B must fit 32 bits (row0=%lld, B=%lld)", who, (long long)row0, (long long)B);
+    if (per_row > (1ll << 34)) return c->fail(-1, "%s: per_row must be at most 2^34, got %lld", who, (long long)per_row);
+    return 0;
+}
+
 extern "C++" struct SamplerRun {
     rdm_ctx* c; int B, nb, k, H, W, total; long long n1;           // n1: elements of x for B rows; total: ts.size()
     float *x, *x_dup, *eps, *extra[4]; long long* tdev; const float* emb_table;
@@ -1830,10 +1842,20 @@ extern "C++" struct SamplerRun {
             RDM_CHECK_HIP(c, hipMemcpyAsync(tdev, th.data(), t_bytes, hipMemcpyHostToDevice, c->stream));
             RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));   // th goes out of scope
         }
-        RDM_CHECK_HIP(c, hipMemcpyAsync(x, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
-        if (x_dup) RDM_CHECK_HIP(c, hipMemcpyAsync(x_dup, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+        if (x_T) {              // null: a seeded entry draws the start (draw_start)
+            RDM_CHECK_HIP(c, hipMemcpyAsync(x, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+            if (x_dup) RDM_CHECK_HIP(c, hipMemcpyAsync(x_dup, x_T, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+        }
         return sampler_emb_table(c, ts, &emb_table);
     }
+    // the start of a seeded call without x_T: row b of x = the normals of (seed, stream 0, step 0, row0 + b)
+    int draw_start(const NoiseSeed& ns) {
+        RngFillParams f{ns.seed, B, n1 / B, (uint32_t)ns.row0, 0u, RDM_RNG_STREAM_XT, (uint32_t*)x};
+        RDM_CHECK_HIP(c, launch_rng_fill(f, true, c->stream));
+        if (x_dup) RDM_CHECK_HIP(c, hipMemcpyAsync(x_dup, x, n1 * 4, hipMemcpyDeviceToDevice, c->stream));
+        return 0;
+    }
+    StepRngParams step_rng(const NoiseSeed& ns, int step) const { return {ns.seed, n1 / B, (uint32_t)ns.row0, (uint32_t)step}; }
     int forward(int idx) {        // guided: [x | x] at the same t, so the context-independent prefix runs once (shared half = B)
         UNet& u = c->unet;
         return unet_forward_impl(c, x, (const int64_t*)(tdev + (size_t)idx * nb), nullptr, u.kv_cache, nb, k, H, W, eps, u.ctx_rows,
@@ -1875,14 +1897,17 @@ struct HistoryRing {
     }
 };
 
-int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
-                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
-    RDM_ENTER(c);
-    if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+// The DDIM loop of rdm_ddim_sample (ns null: the step noise is read from the stack `noise`) and rdm_ddim_sample_seeded (ns: it is generated
+// in the step kernel, and a null x_T is drawn).
+static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
+                            const float* noise, const NoiseSeed* ns, float* z_out, float* x_inter, float* pred_x0_inter) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     bool cfg;
     RDM_TRY(sampler_guidance(c, "ddim", a->unconditional_guidance_scale, uncond, &cfg));
-    if (a->eta != 0.f && !noise) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
+    if (ns) {
+        RDM_TRY(check_noise_rows(c, "ddim (seeded)", ns->row0, a->batch, (int64_t)a->channels * a->height * a->width));
+        if (((int64_t)a->channels * a->height * a->width) % 4) return c->fail(-1, "ddim (seeded): channels * height * width must be a multiple of 4");
+    } else if (a->eta != 0.f && !noise) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
     const int total = (int)ts.size();
@@ -1894,6 +1919,7 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
     }
     SamplerRun run;
     RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 0));
+    if (!x_T) RDM_TRY(run.draw_start(*ns));
     for (int i = 0; i < total; i++) {
         const int index = total - i - 1;         // of the ascending schedule
         RDM_TRY(run.forward(index));
@@ -1902,10 +1928,27 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
         p.x_prev = run.x; p.x_dup = run.x_dup; p.pred_x0 = run.pred_x0_slot(i);
         p.n_per_batch = run.n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sigma_t = sg[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.temperature = a->temperature; p.cfg = cfg ? 1 : 0;
-        RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
+        if (ns && a->eta != 0.f) {          // the noise of loop step i, in registers
+            const hipError_t e = launch_ddim_step_seeded(p, run.step_rng(*ns, i), c->stream);
+            if (e == hipErrorInvalidValue) return c->fail(-1, "ddim (seeded): pred_x0_inter must be 16-byte aligned");
+            RDM_CHECK_HIP(c, e);
+        } else RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
         RDM_TRY(run.log_x(i));
     }
     return run.finish(z_out);
+}
+int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
+                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    return ddim_sample_impl(c, a, x_T, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
+}
+int rdm_ddim_sample_seeded(rdm_ctx* c, const rdm_ddim_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
+                           const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    const NoiseSeed ns{seed, row0};
+    return ddim_sample_impl(c, a, x_T, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
 }
 
 // ldm PLMSSampler.plms_sampling / p_sample_plms (eta = 0): DDIM's schedule, timesteps and intermediates, total + 1 forwards.  The
@@ -2203,27 +2246,74 @@ int rdm_unipc_sample(rdm_ctx* c, const rdm_unipc_args* a, const float* x_T, cons
     return run.finish(z_out);
 }
 
-int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const float* noise,
-                    float* z_out) {
-    RDM_ENTER(c);
-    if (!c || !a || !x_T || !cond || !noise || !z_out) return c ? c->fail(-1, "null argument") : -1;
+// The ancestral loop of rdm_ddpm_sample (ns null: noise stack) and rdm_ddpm_sample_seeded (ns: generated in the step kernel; a null x_T
+// is drawn).  The final step (i == 0) consumes no noise either way.
+static int ddpm_sample_impl(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const float* noise, const NoiseSeed* ns,
+                            float* z_out) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->timesteps < 1 || a->timesteps > a->T) return c->fail(-1, "bad timesteps");
+    if (ns) {
+        RDM_TRY(check_noise_rows(c, "ddpm (seeded)", ns->row0, a->batch, (int64_t)a->channels * a->height * a->width));
+        if (((int64_t)a->channels * a->height * a->width) % 4) return c->fail(-1, "ddpm (seeded): channels * height * width must be a multiple of 4");
+    }
     const int T = a->timesteps;
     std::vector<int> ts(T);
     for (int i = 0; i < T; i++) ts[i] = i;
     SamplerRun run;
     RDM_TRY(run.begin(c, a, ts, x_T, cond, nullptr, 0, nullptr, nullptr, 0));
+    if (!x_T) RDM_TRY(run.draw_start(*ns));
     for (int n = 0, i = T - 1; i >= 0; i--, n++) {
         RDM_TRY(run.forward(i));
         DdpmStepParams p{};
-        p.x = run.x; p.eps = run.eps; p.noise = noise + (size_t)n * run.n1; p.x_prev = run.x; p.n = run.n1;
+        p.x = run.x; p.eps = run.eps; p.noise = noise ? noise + (size_t)n * run.n1 : nullptr; p.x_prev = run.x; p.n = run.n1;
         p.sqrt_recip = a->sqrt_recip_alphas_cumprod[i]; p.sqrt_recipm1 = a->sqrt_recipm1_alphas_cumprod[i];
         p.coef1 = a->posterior_mean_coef1[i]; p.coef2 = a->posterior_mean_coef2[i]; p.log_var = a->posterior_log_variance_clipped[i];
         p.clip = a->clip_denoised; p.nonzero = (i != 0); p.temperature = a->temperature;
-        RDM_CHECK_HIP(c, launch_ddpm_step(p, c->stream));
+        if (ns && p.nonzero) RDM_CHECK_HIP(c, launch_ddpm_step_seeded(p, run.step_rng(*ns, n), c->stream));      // the noise of loop step n, in registers
+        else RDM_CHECK_HIP(c, launch_ddpm_step(p, c->stream));
     }
     return run.finish(z_out);
+}
+int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const float* noise,
+                    float* z_out) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_T || !cond || !noise || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    return ddpm_sample_impl(c, a, x_T, cond, noise, nullptr, z_out);
+}
+int rdm_ddpm_sample_seeded(rdm_ctx* c, const rdm_ddpm_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond, float* z_out) {
+    RDM_ENTER(c);
+    if (!c || !a || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    const NoiseSeed ns{seed, row0};
+    return ddpm_sample_impl(c, a, x_T, cond, nullptr, &ns, z_out);
+}
+
+// ---- device noise: the generator alone (philox.h)
+int rdm_rng_words(uint64_t seed, uint32_t row, uint32_t step, uint32_t stream, uint32_t block, uint32_t* out) {
+    if (!out) return -1;
+    uint32_t w[4];
+    philox4x32_10(seed, block, step, row, stream, w);
+    for (int k = 0; k < 4; k++) out[k] = w[k];
+    return 0;
+}
+static int op_rng_fill(rdm_ctx* c, const char* who, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream,
+                       void* out, bool normal) {
+    if (!out) return c->fail(-1, "%s: null argument", who);
+    if (stream >= RDM_RNG_STREAMS) return c->fail(-1, "%s: stream %u is reserved (0 = starting latent, 1 = per-step noise)", who, stream);
+    RDM_TRY(check_noise_rows(c, who, row0, B, per_row));
+    if ((uintptr_t)out % 4) return c->fail(-1, "%s: out must be 4-byte aligned", who);
+    RngFillParams f{seed, B, per_row, (uint32_t)row0, step, stream, (uint32_t*)out};
+    RDM_CHECK_HIP(c, launch_rng_fill(f, normal, c->stream));
+    return 0;
+}
+int rdm_op_rng_words(rdm_ctx* c, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, uint32_t* out) {
+    RDM_ENTER(c);
+    if (!c) return -1;
+    return op_rng_fill(c, "rdm_op_rng_words", seed, row0, B, per_row, step, stream, out, false);
+}
+int rdm_op_randn(rdm_ctx* c, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, float* out) {
+    RDM_ENTER(c);
+    if (!c) return -1;
+    return op_rng_fill(c, "rdm_op_randn", seed, row0, B, per_row, step, stream, out, true);
 }
 
 

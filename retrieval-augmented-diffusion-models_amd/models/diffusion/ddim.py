@@ -97,6 +97,19 @@ class _SamplerBase(object):
         mv = (lambda t: t.detach().cpu()) if to_cpu else (lambda t: t)
         return {'x_inter': [img] + [mv(t) for t in x_inter], 'pred_x0': [img] + [mv(t) for t in pred_x0]}
 
+    def _device_randn(self, size, noise_seed, noise_row0=0, step=0, stream=0):
+        """[native] The library's own normals (Context.op_randn: a function of (seed, stream, step, global row, element) only) at the
+        latent size (B, C, H, W), rows noise_row0 .. noise_row0 + B - 1: stream 0 / step 0 is the starting latent of a seeded sampling
+        call, stream 1 / step i the update noise of loop step i."""
+        size = tuple(int(v) for v in size)
+        return self.model.ctx.op_randn(noise_seed, size[0], int(np.prod(size[1:])), row0=noise_row0, step=step, stream=stream).reshape(size)
+
+    def _seeded_start(self, x_T, size, noise_seed, noise_row0=0):
+        """x_T when given; else, with a noise_seed, the library's starting latent (stream 0); else None (the caller draws with torch)."""
+        if x_T is not None or noise_seed is None:
+            return x_T
+        return self._device_randn(size, noise_seed, noise_row0)
+
     def _model_output(self, x, t, c, uc, scale, score_corrector=None, corrector_kwargs=None, uncond_first=False):
         """eps of the per-step paths: one forward, or (uc given and scale != 1) one forward of the doubled batch [c | uc] -- ldm's PLMS
         order [uc | c] with uncond_first: the library's zero-context shortcut keys on TRAILING all-zero rows -- combined as
@@ -138,7 +151,10 @@ class DDIMSampler(_SamplerBase):
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, random_guiding='none', r_shape=None, retro_cond=None,
                return_neighbors=False, k_nn=None, ignore_noising=False, content_cond=None, style_cond=None,
-               intermediates_to_cpu=False, **kwargs):
+               intermediates_to_cpu=False, noise_seed=None, noise_row0=0, **kwargs):
+        """`noise_seed` / `noise_row0` [native]: take the starting latent (when no x_T is given) and the per-step noise of eta > 0 from
+        the library's counter-based generator, rows noise_row0 .. noise_row0 + batch_size - 1 of that seed: no noise stack exists, and a
+        row's sample does not depend on how a batch is sharded.  Default None: torch's generator, as before."""
         self._warn_batch(conditioning, batch_size)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         size = (batch_size,) + tuple(shape)
@@ -149,15 +165,17 @@ class DDIMSampler(_SamplerBase):
                                   unconditional_conditioning=unconditional_conditioning, random_guiding=random_guiding,
                                   content_cond=content_cond, style_cond=style_cond,
                                   intermediates_to_cpu=intermediates_to_cpu, S=S, eta=eta, noise=kwargs.get("noise"),
-                                  q_noise=kwargs.get("q_noise"))
+                                  q_noise=kwargs.get("q_noise"), noise_seed=noise_seed, noise_row0=noise_row0)
 
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, random_guiding='none', content_cond=None, style_cond=None,
-                      intermediates_to_cpu=False, S=None, eta=0., **kwargs):
+                      intermediates_to_cpu=False, S=None, eta=0., noise_seed=None, noise_row0=0, **kwargs):
         self._refuse_original_steps(ddim_use_original_steps)
+        if noise_seed is not None and kwargs.get("noise") is not None:
+            raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
         # options that change the loop body step by step run through the per-step path (native UNet forward per step)
         per_step = (quantize_denoised or mask is not None or x0 is not None or noise_dropout > 0. or score_corrector is not None or
                     content_cond is not None or style_cond is not None or random_guiding != 'none' or timesteps is not None)
@@ -167,6 +185,7 @@ class DDIMSampler(_SamplerBase):
         if unconditional_guidance_scale > 1.:
             assert unconditional_conditioning is not None
         device = self.model.device
+        x_T = self._seeded_start(x_T, shape, noise_seed, noise_row0)
         img = torch.randn(shape, device=device) if x_T is None else x_T.to(device)
         total_steps = self.ddim_timesteps.shape[0]
         print(f"Running DDIM Sampling with {total_steps} timesteps")
@@ -176,21 +195,25 @@ class DDIMSampler(_SamplerBase):
                                      mask=mask, x0=x0, noise_dropout=noise_dropout, score_corrector=score_corrector,
                                      corrector_kwargs=corrector_kwargs, random_guiding=random_guiding, timesteps=timesteps,
                                      content_cond=self._unwrap(content_cond), style_cond=self._unwrap(style_cond),
-                                     noise=kwargs.get("noise"), q_noise=kwargs.get("q_noise"), quantize_denoised=quantize_denoised)
+                                     noise=kwargs.get("noise"), q_noise=kwargs.get("q_noise"), quantize_denoised=quantize_denoised,
+                                     noise_seed=noise_seed, noise_row0=noise_row0)
         noise = kwargs.get("noise")             # [native] optional explicit per-step noise stack [S, B, C, H, W] (consumed in loop order)
-        if eta != 0. and noise is None:
+        seeded = {} if noise_seed is None else dict(seed=noise_seed, row0=noise_row0)      # [native] the step kernel generates the noise
+        if eta != 0. and noise is None and noise_seed is None:
             noise = torch.randn((total_steps,) + tuple(shape), device=device)
         z, xi, pi = self.model.ctx.ddim_sample(S, img, cond, unconditional_conditioning if unconditional_guidance_scale > 1. else None,
                                                self.alphas_cumprod, eta=eta, scale=unconditional_guidance_scale, noise=noise,
-                                               log_every_t=log_every_t, temperature=temperature, want_intermediates=True)
+                                               log_every_t=log_every_t, temperature=temperature, want_intermediates=True, **seeded)
         return z.detach(), self._intermediates(img, xi, pi, intermediates_to_cpu)
 
     def _python_loop(self, cond, img, callback, img_callback, log_every_t, temperature, eta, scale, uc, to_cpu, mask=None,
                      x0=None, noise_dropout=0., score_corrector=None, corrector_kwargs=None, random_guiding='none',
-                     timesteps=None, content_cond=None, style_cond=None, noise=None, q_noise=None, quantize_denoised=False):
+                     timesteps=None, content_cond=None, style_cond=None, noise=None, q_noise=None, quantize_denoised=False,
+                     noise_seed=None, noise_row0=0):
         """Per-step path of ddim.py:143-209 (callbacks, inpainting mask, style / content conditioning by SNR band, timestep
         subset, noise dropout, score corrector): native UNet forward per step, torch elementwise update.  `noise` / `q_noise`
-        [native]: optional explicit stacks [steps, B, C, H, W] for the update noise and for q_sample of the masked region."""
+        [native]: optional explicit stacks [steps, B, C, H, W] for the update noise and for q_sample of the masked region;
+        `noise_seed` [native]: step i's update noise is the library's (stream 1, step i), what the native seeded loop applies."""
         ts_all = self._timestep_subset(timesteps)
         total_steps = ts_all.shape[0]
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
@@ -214,7 +237,9 @@ class DDIMSampler(_SamplerBase):
             img, pred_x0 = self.p_sample_ddim(img, input_cond, ts, index=index, temperature=temperature, quantize_denoised=quantize_denoised,
                                               noise_dropout=noise_dropout, score_corrector=score_corrector,
                                               corrector_kwargs=corrector_kwargs, unconditional_guidance_scale=scale,
-                                              unconditional_conditioning=uc, noise=None if noise is None else noise[i],
+                                              unconditional_conditioning=uc,
+                                              noise=(noise[i] if noise is not None else None if noise_seed is None or eta == 0. else
+                                                     self._device_randn(img.shape, noise_seed, noise_row0, step=i, stream=1)),
                                               random_guider=random_guider)
             if callback: callback(i)
             if img_callback: img_callback(pred_x0, i)

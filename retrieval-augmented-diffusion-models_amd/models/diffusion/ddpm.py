@@ -181,12 +181,19 @@ class MinimalRETRODiffusion(object):
             raise ValueError(f"custom_shape must be ({self.channels}, H, W) with H and W positive multiples of the UNet's down factor {down}, got {tuple(custom_shape)}")
         return shape
 
-    def _sample_shard(self, c, c_uncond, lo, hi, n_total, scale, kwargs):
+    def _sample_shard(self, c, c_uncond, lo, hi, n_total, scale, kwargs, device_noise=False):
         """sample_log + decode_first_stage on rows [lo, hi) of a global batch of n_total, then the all-gather.  The starting noise and
-        the per-step noise stack are drawn at the latent shape of the call (custom_shape when given)."""
+        the per-step noise stack are drawn at the latent shape of the call (custom_shape when given).  device_noise [native]: nothing
+        is drawn here -- the samplers take the noise of global rows lo .. hi - 1 from the library's counter-based generator
+        (noise_seed = the call's shared seed, noise_row0 = lo): no starting latent, no [steps, b, C, H, W] stack, no transposed copy."""
         shape = self._latent_shape(kwargs.get("custom_shape"))
         if kwargs.get("x_T") is not None:
             kwargs["x_T"] = kwargs["x_T"][lo:hi]
+        elif device_noise:
+            if kwargs.get("noise") is not None:
+                raise ValueError("device_noise and an explicit noise stack select different noise sources: give one of them")
+            kwargs["noise_seed"] = parallel.shared_seed(self.device, getattr(self, "_group", None))
+            kwargs["noise_row0"] = lo
         else:
             base = parallel.shared_seed(self.device, getattr(self, "_group", None))
             kwargs["x_T"] = parallel.per_sample_noise(base, range(lo, hi), shape, device=self.device)
@@ -410,9 +417,11 @@ class MinimalRETRODiffusion(object):
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, timesteps=None, noise=None,
-               temperature=1., shape=None, **kwargs):
+               temperature=1., shape=None, noise_seed=None, noise_row0=0, **kwargs):
         """ldm LatentDiffusion.sample -> p_sample_loop (ancestral DDPM; CFG kwargs are swallowed like in ldm).  shape: ldm's argument,
-        (batch_size, C, H, W) of the latents; default the model's own size."""
+        (batch_size, C, H, W) of the latents; default the model's own size.  noise_seed / noise_row0 [native]: the starting latent (when
+        no x_T is given) and every step's noise come from the library's counter-based generator, rows noise_row0 .. of that seed, inside
+        the step kernel -- no [timesteps, B, C, H, W] stack exists."""
         if shape is None:
             shape = (batch_size, self.channels, self.image_size, self.image_size)
         else:
@@ -425,18 +434,24 @@ class MinimalRETRODiffusion(object):
             cond = cond[0]
         cond = cond[:batch_size]
         return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, timesteps=timesteps,
-                                  noise=noise, temperature=temperature)
+                                  noise=noise, temperature=temperature, noise_seed=noise_seed, noise_row0=noise_row0)
 
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, timesteps=None, noise=None,
-                      temperature=1., **kwargs):
+                      temperature=1., noise_seed=None, noise_row0=0, **kwargs):
         T = int(timesteps) if timesteps is not None else self.num_timesteps
-        img = torch.randn(shape, device=self.device) if x_T is None else x_T
-        if noise is None:
-            noise = torch.randn((T,) + tuple(shape), device=self.device)
         sched = {n: getattr(self, n).numpy() for n in ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod",
                                                         "posterior_mean_coef1", "posterior_mean_coef2",
                                                         "posterior_log_variance_clipped")}
+        if noise_seed is not None:              # [native] the library's own noise, generated in the step kernel; x_T may stay None
+            if noise is not None:
+                raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
+            z = self.ctx.ddpm_sample(T, x_T, cond, None, sched, clip_denoised=self.clip_denoised, temperature=temperature,
+                                     seed=noise_seed, row0=noise_row0, shape=tuple(shape)[1:])
+            return (z, [z]) if return_intermediates else z
+        img = torch.randn(shape, device=self.device) if x_T is None else x_T
+        if noise is None:
+            noise = torch.randn((T,) + tuple(shape), device=self.device)
         z = self.ctx.ddpm_sample(T, img, cond, noise, sched, clip_denoised=self.clip_denoised, temperature=temperature)
         return (z, [z]) if return_intermediates else z
 
@@ -448,8 +463,10 @@ class MinimalRETRODiffusion(object):
     def sample_with_query(self, query, cond=None, bs=None, k_nn=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, return_nns=False,
                           n_reps=None, query_embedded=False, example_maps=None, visualize_nns=True, omit_query=False,
-                          normalize=False, **kwargs):
-        """ddpm.py:689-844 (nn_encoder is None, retrieval_encoder = Identity — every shipped config)."""
+                          normalize=False, device_noise=False, **kwargs):
+        """ddpm.py:689-844 (nn_encoder is None, retrieval_encoder = Identity — every shipped config).  device_noise [native]: the
+        starting latents and the per-step noise (DDIM eta > 0, DDPM) are the library's counter-based generator's, a function of (the
+        call's shared seed, GLOBAL row) generated inside the step kernels (_sample_shard) -- no noise tensor is drawn in Python."""
         if cond is not None or return_nns:
             raise NotImplementedError("cond (a second conditioning) / return_nns (neighbour image grids) are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))      # a bad custom_shape fails here, not after the retrieval
@@ -510,8 +527,8 @@ class MinimalRETRODiffusion(object):
         if n_reps is not None:
             c_uncond = torch.cat([c_uncond] * n_reps, dim=1)
         c_uncond = c_uncond.to(self.device).float().contiguous()
-        if self.distributed:
-            return {"query_samples": self._sample_shard(c, c_uncond, lo, hi, n_total, unconditional_guidance_scale, kwargs)}
+        if self.distributed or device_noise:
+            return {"query_samples": self._sample_shard(c, c_uncond, lo, hi, n_total, unconditional_guidance_scale, kwargs, device_noise)}
         with self.ema_scope("Plotting"):
             samples, _ = self.sample_log(cond=c, batch_size=bs, unconditional_guidance_scale=unconditional_guidance_scale,
                                          unconditional_conditioning=c_uncond, **kwargs)
@@ -546,8 +563,9 @@ class MinimalRETRODiffusion(object):
     def sample_from_rdata(self, N, cond=None, return_nns=False, use_weights=False, qids=None, k_nn=None, memsize=100,
                           verbose=False, pre_loaded_patches=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, nn_embeddings=None,
-                          **kwargs):
-        """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921)."""
+                          device_noise=False, **kwargs):
+        """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921).  device_noise [native]: as in
+        sample_with_query."""
         if cond is not None or return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("cond / return_nns / pre_loaded_patches are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))
@@ -575,8 +593,8 @@ class MinimalRETRODiffusion(object):
         c = self.retrieval_encoder(retro_cond).contiguous()
         c_uncond = self.get_unconditional_conditioning(c.shape, unconditional_guidance_label=unconditional_retro_guidance_label, k_nn=k_nn)
         c_uncond = c_uncond.to(self.device).float().contiguous()
-        if self.distributed:
-            return {"samples_with_sampled_nns": self._sample_shard(c, c_uncond, lo, hi, N, unconditional_guidance_scale, kwargs)}
+        if self.distributed or device_noise:
+            return {"samples_with_sampled_nns": self._sample_shard(c, c_uncond, lo, hi, N, unconditional_guidance_scale, kwargs, device_noise)}
         with self.ema_scope("Plotting"):
             samples, _ = self.sample_log(cond=c, batch_size=N, unconditional_guidance_scale=unconditional_guidance_scale,
                                          unconditional_conditioning=c_uncond, **kwargs)

@@ -107,12 +107,14 @@ class DPMSolverSampler(_NodeListSampler):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, order=2, skip_type="logSNR", lower_order_final=None, timesteps=None, **kwargs):
-        """`order` (1 | 2), `skip_type` ("logSNR" | "time_uniform"), `lower_order_final` (None: on below 15 steps), `timesteps` (an
+               unconditional_conditioning=None, order=2, skip_type="logSNR", lower_order_final=None, timesteps=None, noise_seed=None, noise_row0=0, **kwargs):
+        """`noise_seed` / `noise_row0` [native]: without an x_T the starting latent is the library's own (DDIMSampler.sample); no per-step
+        noise is drawn.  `order` (1 | 2), `skip_type` ("logSNR" | "time_uniform"), `lower_order_final` (None: on below 15 steps), `timesteps` (an
         explicit node list, strictly decreasing) and `q_noise` (explicit stack [steps, B, C, H, W] for q_sample of the masked region,
         per-step path) are [native]."""
         if order not in (1, 2):
             raise ValueError(f'DPM-Solver++ order must be 1 or 2, got {order!r}')
+        x_T = self._seeded_start(x_T, (batch_size,) + tuple(shape), noise_seed, noise_row0)
         nodes, cond, uc, scale, img = self._prepare(S, batch_size, shape, conditioning, eta, x_T, unconditional_guidance_scale,
                                                     unconditional_conditioning, skip_type, timesteps)
         n_steps = len(nodes) - 1

@@ -28,10 +28,13 @@ class PLMSSampler(_SamplerBase):
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
-               unconditional_conditioning=None, **kwargs):
+               unconditional_conditioning=None, noise_seed=None, noise_row0=0, **kwargs):
+        """`noise_seed` / `noise_row0` [native]: without an x_T the starting latent is the library's own (DDIMSampler.sample); PLMS draws
+        no per-step noise."""
         self._warn_batch(conditioning, batch_size)
         self.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=verbose)
         size = (batch_size,) + tuple(shape)
+        x_T = self._seeded_start(x_T, size, noise_seed, noise_row0)
         return self.plms_sampling(conditioning, size, callback=callback, img_callback=img_callback,
                                   quantize_denoised=quantize_x0, mask=mask, x0=x0, ddim_use_original_steps=False,
                                   noise_dropout=noise_dropout, temperature=temperature, score_corrector=score_corrector,

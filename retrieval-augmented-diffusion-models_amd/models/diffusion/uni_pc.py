@@ -40,8 +40,9 @@ class UniPCSampler(_NodeListSampler):
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
                corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, order=2, variant="bh2", corrector=True, skip_type="logSNR", lower_order_final=True,
-               timesteps=None, **kwargs):
-        """`order` (1 | 2 | 3: the predictor's), `variant` ("bh1" | "bh2"), `corrector`, `skip_type` ("logSNR" | "time_uniform"),
+               timesteps=None, noise_seed=None, noise_row0=0, **kwargs):
+        """`noise_seed` / `noise_row0` [native]: without an x_T the starting latent is the library's own (DDIMSampler.sample); no per-step
+        noise is drawn.  `order` (1 | 2 | 3: the predictor's), `variant` ("bh1" | "bh2"), `corrector`, `skip_type` ("logSNR" | "time_uniform"),
         `lower_order_final` and `timesteps` (an explicit node list, strictly decreasing) are [native]."""
         if mask is not None or x0 is not None:
             raise ValueError('UniPC has no inpainting form (the predictor-corrector keeps two iterates; mask / x0 are not supported): '
@@ -50,6 +51,7 @@ class UniPCSampler(_NodeListSampler):
             raise ValueError(f'UniPC order must be 1, 2 or 3, got {order!r}')
         if variant not in _lib.UNIPC_VARIANTS:
             raise ValueError(f'UniPC variant must be one of {sorted(_lib.UNIPC_VARIANTS)}, got {variant!r}')
+        x_T = self._seeded_start(x_T, (batch_size,) + tuple(shape), noise_seed, noise_row0)
         nodes, cond, uc, scale, img = self._prepare(S, batch_size, shape, conditioning, eta, x_T, unconditional_guidance_scale,
                                                     unconditional_conditioning, skip_type, timesteps)
         print(f"Running UniPC Sampling (order {order}, {variant}, corrector {'on' if corrector else 'off'}) with {len(nodes) - 1} timesteps")

@@ -24,7 +24,11 @@ works with `--gpus N`; not together with `--plms`), `--uni_pc` (sample with UniP
 forward, on the same grid; works with `--gpus N`; not together with `--plms` or `--dpm_solver`), `--height PX` / `--width PX` (image size in pixels, default the model's own: the UNet and
 the first stage are convolutional, so a model samples at other sizes -- the reference reaches this through `sample_log(custom_shape=)`
 only, its script has no flag; multiples of 32 = first-stage factor 4 x UNet down factor 8 of the shipped models; every sampler, and
-`--gpus N`).
+`--gpus N`), `--eta FLOAT` (DDIM's eta, default 0.0 = the reference script's deterministic DDIM; above 0 every step adds
+sigma_t-scaled noise; DDIM only, PLMS refuses it and DPM-Solver++ / UniPC ignore it), `--device_noise` (the starting latents and the
+`--eta` noise come from the library's counter-based generator inside the step kernels, keyed by (the run's seed draw, global sample
+index): no noise tensor is drawn or stacked in Python, and the images differ from the default torch-generator streams; works with
+`--gpus N` with the same sharding invariance).
 """
 import argparse
 import datetime
@@ -76,6 +80,10 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--width", type=int, default=None, help="[native] image width in pixels (default: the model's own size); a multiple of 32")
     parser.add_argument("--uni_pc", default=False, action="store_true",
                         help="[native] sample with UniPC (order 2, bh2, with the corrector) on a logSNR grid instead of DDIM")
+    parser.add_argument("--eta", type=float, default=0.0, help="[native] DDIM eta (0.0: deterministic DDIM, as the reference script samples)")
+    parser.add_argument("--device_noise", default=False, action="store_true",
+                        help="[native] starting latents and per-step noise from the library's counter-based generator inside the step kernels "
+                        "(no noise stack)")
     return parser
 
 
@@ -196,9 +204,11 @@ def _save_logs(logs, keys, opt, sampling_start, n):
 
 
 def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
-    """--plms / --dpm_solver / --uni_pc / --height / --width reach MinimalRETRODiffusion.sample_log (the sizes as its custom_shape, in latent
-    pixels); without them the calls are the reference's."""
-    kw = {name: True for name in ("plms", "dpm_solver", "uni_pc") if getattr(opt, name, False)}
+    """--plms / --dpm_solver / --uni_pc / --height / --width / --eta reach MinimalRETRODiffusion.sample_log (the sizes as its custom_shape, in
+    latent pixels), --device_noise sample_with_query / sample_from_rdata; without them the calls are the reference's."""
+    kw = {name: True for name in ("plms", "dpm_solver", "uni_pc", "device_noise") if getattr(opt, name, False)}
+    if getattr(opt, "eta", 0.0) != 0.0:
+        kw["eta"] = opt.eta
     height, width = getattr(opt, "height", None), getattr(opt, "width", None)
     if height is not None or width is not None:
         f = 1 << (model.vq_cfg.n_ch_mult - 1)                       # pixels per latent pixel

@@ -3,9 +3,14 @@
 neighbours; the UNet batch is the guided B' = 128): ms per image, VQ decode included, for each `name:S` given (default ddim:50 plms:50
 plms:25).  PLMS with S timesteps runs S + 1 forwards; dpmpp:S is DPM-Solver++(2M) on the logSNR grid of S targets, whose real step
 count (reported under "forwards") can come out below S; unipc:S is UniPC (order 2, bh2, with the corrector) on the same grid, one
-forward per step like dpmpp.  Prints the box's calibration probe and one line per run on stderr, one JSON line on stdout.
+forward per step like dpmpp.  The stochastic loops come in two forms: ddimeta:S (DDIM, eta = 1) and ddpm:S (ancestral DDPM, unguided)
+draw the starting latents and the [S, B, 3, 64, 64] noise stack per call the way MinimalRETRODiffusion._sample_shard does (one torch
+generator per sample row, then the transposed copy) and time that with the loop; ddimeta_rng:S and ddpm_rng:S are the seeded entries,
+whose step kernels generate the noise (no x_T, no stack).  Every line also carries the peak of torch.cuda.max_memory_allocated() over the
+timed calls.  A spec given twice is timed twice (the second under `name:S#2`): the box's own A/A spread.  Prints the box's calibration
+probe and one line per run on stderr, one JSON line on stdout.
 
-    python tools/sampler_bench.py [--reps N] [--batch B] [ddim:50 plms:50 plms:25 dpmpp:20 ...]
+    python tools/sampler_bench.py [--reps N] [--batch B] [ddim:50 plms:50 plms:25 dpmpp:20 ddpm:250 ddpm:250 ddpm_rng:250 ...]
 """
 import argparse
 import json
@@ -26,7 +31,7 @@ def main():
 
     import torch
     import rdm_amd  # noqa: F401
-    from rdm_amd import _lib, packing, synthetic
+    from rdm_amd import _lib, packing, parallel, synthetic
     from rdm_amd.models.diffusion.ddpm import MinimalRETRODiffusion
 
     torch.set_grad_enabled(False)
@@ -41,8 +46,31 @@ def main():
     cond = torch.randn(B, 4, 512, device=d, generator=g) * 0.45
     uncond = torch.zeros_like(cond)
 
+    sched_ddpm = {n: getattr(model, n).numpy() for n in ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1",
+                                                          "posterior_mean_coef2", "posterior_log_variance_clipped")}
+    calls = [0]
+
+    def stack(steps):
+        """The starting latents and the noise stack of one call, as _sample_shard draws them."""
+        calls[0] += 1
+        x = parallel.per_sample_noise(1000 + calls[0], range(B), (3, 64, 64), device=d)
+        nz = parallel.per_sample_noise(1001 + calls[0], range(B), (steps, 3, 64, 64), device=d)
+        return x, nz.transpose(0, 1).contiguous()
+
     def sample(name, S):
-        if name == "ddim":
+        if name == "ddimeta":
+            x, nz = stack(S)
+            z, _, _ = ctx.ddim_sample(S, x, cond, uncond, model.alphas_cumprod, eta=1.0, scale=2.0, noise=nz)
+        elif name == "ddimeta_rng":
+            calls[0] += 1
+            z, _, _ = ctx.ddim_sample(S, None, cond, uncond, model.alphas_cumprod, eta=1.0, scale=2.0, seed=1000 + calls[0], shape=(3, 64, 64))
+        elif name == "ddpm":
+            x, nz = stack(S)
+            z = ctx.ddpm_sample(S, x, cond, nz, sched_ddpm, clip_denoised=True)
+        elif name == "ddpm_rng":
+            calls[0] += 1
+            z = ctx.ddpm_sample(S, None, cond, None, sched_ddpm, clip_denoised=True, seed=1000 + calls[0], shape=(3, 64, 64))
+        elif name == "ddim":
             z, _, _ = ctx.ddim_sample(S, x_T, cond, uncond, model.alphas_cumprod, eta=0.0, scale=2.0)
         elif name == "plms":
             z, _, _ = ctx.plms_sample(S, x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
@@ -51,7 +79,7 @@ def main():
         elif name == "unipc":
             z, _, _ = ctx.unipc_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         else:
-            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | unipc)")
+            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | unipc | ddimeta | ddimeta_rng | ddpm | ddpm_rng)")
         return ctx.vq_decode(z)
 
     def forwards(name, S):
@@ -62,12 +90,15 @@ def main():
     tf, gb = ctx.calib_probe()
     print(f"calibration: mfma probe {tf:.1f} TFLOP/s, hbm stream {gb:.1f} GB/s", file=sys.stderr, flush=True)
     out = {"batch": B, "scale": 2.0, "k": 4, "reps": a.reps, "calibration": {"mfma_probe_tflops": round(tf, 1), "hbm_stream_gbps": round(gb, 1)},
-           "ms_per_image": {}, "forwards": {}}
-    for run in a.runs:
+           "ms_per_image": {}, "forwards": {}, "peak_torch_mib": {}}
+    for n_run, run in enumerate(a.runs):
         name, S = run.split(":")
         S = int(S)
+        if run in a.runs[:n_run]:
+            run = f"{run}#{a.runs[:n_run].count(run) + 1}"
         sample(name, S)                      # warm-up: scratch, tables, K/V cache
         torch.cuda.synchronize()
+        torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
         for _ in range(a.reps):
             img = sample(name, S)
@@ -76,7 +107,10 @@ def main():
         assert torch.isfinite(img).all()
         out["ms_per_image"][run] = round(dt * 1e3 / B, 3)
         out["forwards"][run] = forwards(name, S)
-        print(f"{run}: {dt * 1e3:.1f} ms per call, {dt * 1e3 / B:.3f} ms per image", file=sys.stderr, flush=True)
+        peak = torch.cuda.max_memory_allocated() / 2 ** 20
+        out["peak_torch_mib"][run] = round(peak, 1)
+        del img
+        print(f"{run}: {dt * 1e3:.1f} ms per call, {dt * 1e3 / B:.3f} ms per image, peak torch memory {peak:.1f} MiB", file=sys.stderr, flush=True)
     ms = out["ms_per_image"]
     if "ddim:50" in ms and "plms:25" in ms:
         out["speedup_plms25_over_ddim50"] = round(ms["ddim:50"] / ms["plms:25"], 3)
