@@ -89,7 +89,7 @@ int conv_halo_ksplit(const IgemmParams& p) {
 hipError_t launch_conv3x3(const IgemmParams& p, hipStream_t st) {
     const ConvKernel k = p.Wfrag ? conv3x3_kernel(p) : CONV_IGEMM;
     // The implicit GEMM and the strip form know nothing of ksplit / ws and must never see ksplit > 1.  They cannot: conv_halo_ksplit
-    // answers 1 unless the conv is CONV_HALO4's, and Ops::conv3 (model.hip) asks it only once it holds the fragment copy.  A caller
+    // answers 1 unless the conv is CONV_HALO4's, and Ops::conv3 (dispatch.hip) asks it only once it holds the fragment copy.  A caller
     // that set ksplit some other way gets an error, not a conv missing its K-split parts
     if (p.ksplit > 1 && k != CONV_HALO4) return hipErrorInvalidValue;
     if (k == CONV_IGEMM) return launch_igemm(p, true, 1, st);

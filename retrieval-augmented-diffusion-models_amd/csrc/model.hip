@@ -1,5 +1,6 @@
-// Host-side executors of librdm_hip: context, weight blob/manifest, UNet / VQ-decoder / CLIP graph
-// walkers, DDIM / DDPM loops, and the C ABI declared in include/rdm_hip.h.
+// Host-side executors of librdm_hip: the UNet, first-stage / CLIP and RARM graph walkers, the five samplers and the
+// operator-level entries (rdm_op_*) of the C ABI declared in include/rdm_hip.h.  What they share is in host.h; model
+// descriptions and loaders are in describe.hip, kernel selection (the Ops methods) in dispatch.hip, the context in context.hip.
 //
 // The executors mirror the reference's module graphs
 //   UNetModel.__init__/forward      rdm/modules/diffusionmodules/openaimodel.py:66-371
@@ -12,843 +13,8 @@
 // SiLU), no materialised skip-concat, cross-attention K/V and all 22 emb_layers projections batched
 // into one GEMM each, K/V of the retrieved neighbours computed once per sample() call instead of
 // once per step per layer.
-#include <dlfcn.h>
-#include <stdarg.h>
-#include <stdio.h>
-#include <stdlib.h>
-#include <string.h>
-
-#include <cmath>
-#include <string>
-#include <unordered_map>
-#include <vector>
-
-#include "../../include/rdm_hip.h"
-#include "kernels.h"
-#include "knn.h"
+#include "host.h"
 #include "philox.h"
-
-#define RDM_CHECK_HIP(ctx, expr)                                                            \
-    do {                                                                                    \
-        hipError_t _e = (expr);                                                             \
-        if (_e != hipSuccess) return (ctx)->fail(-2, "%s failed: %s (%s:%d)", #expr, hipGetErrorString(_e), __FILE__, __LINE__); \
-    } while (0)
-#define RDM_TRY(expr)            \
-    do {                         \
-        int _r = (expr);         \
-        if (_r != 0) return _r;  \
-    } while (0)
-
-// Every C-ABI entry binds the calling thread to the context's device for the duration of the call and restores the
-// caller's current device on exit (a context for device 1 used from a thread whose current device is 0 must neither
-// launch on device 0 nor leave the caller's device changed).
-struct DevGuard {
-    int prev = -1; bool changed = false;
-    explicit DevGuard(int dev) {
-        if (hipGetDevice(&prev) != hipSuccess) prev = -1;
-        if (prev != dev) changed = hipSetDevice(dev) == hipSuccess;
-    }
-    ~DevGuard() { if (changed && prev >= 0) (void)hipSetDevice(prev); }
-    DevGuard(const DevGuard&) = delete; DevGuard& operator=(const DevGuard&) = delete;
-};
-#define RDM_ENTER(c) if (!(c)) return -1; DevGuard _dev_guard((c)->device)
-
-// ------------------------------------------------------------------------------------ manifest
-struct Manifest {
-    std::string text;
-    size_t total = 0;
-    size_t add(const std::string& kind, const std::string& srcs, size_t nbytes) {      // kind may carry a padding recipe ("|R=..|C=..", build_unet)
-        total = (total + 255) & ~(size_t)255;
-        const size_t off = total;
-        text += std::to_string(off) + " " + std::to_string(nbytes) + " " + kind + " "; text += srcs; text += "\n";
-        total += nbytes;
-        return off;
-    }
-    // the unpadded kinds every builder uses, by element count
-    size_t f32(const std::string& n, size_t numel) { return add("f32", n, numel * 4); }
-    size_t bf16(const std::string& n, size_t numel) { return add("bf16", n, numel * 2); }
-    size_t conv3(const std::string& n, size_t cout, size_t cin) { return add("conv3", n, cout * cin * 9 * 2); }      // bf16 [cout][3][3][cin]
-};
-
-// ------------------------------------------------------------------------------------ arena
-struct Arena {
-    char* base = nullptr; size_t cap = 0, off = 0, peak = 0; bool planning = false;
-    void reset() { off = 0; }
-    void* alloc(size_t bytes) {
-        off = (off + 255) & ~(size_t)255;
-        void* p = base ? base + off : (void*)(uintptr_t)(off + 256);
-        off += bytes;
-        if (off > peak) peak = off;
-        return p;
-    }
-};
-
-// ------------------------------------------------------------------------------------ what every model owns
-template <typename T> static void free_dev(T*& p, size_t& bytes) { if (p) (void)hipFree(p); p = nullptr; bytes = 0; }
-// A model is a description (cfg, layer graph, blob offsets: filled by its build_* function, which allocates nothing) plus the
-// device memory behind it.  A description without memory may be copied (load_model builds one aside and assigns it).
-struct ModelBase {
-    char* blob = nullptr; size_t blob_bytes = 0; Arena arena; bool loaded = false;
-    void release() { free_dev(blob, blob_bytes); free_dev(arena.base, arena.cap); loaded = false; }      // (the caller has synchronised)
-};
-
-// ------------------------------------------------------------------------------------ UNet description
-// Channel padding.  Every GEMM / conv K loop advances in 64-channel slices and the skip-concat split points sit on slice boundaries,
-// so an activation with C channels is held with P(C) = C rounded up to 64 of them, the tail zero: models/rdm/ffhq has
-// model_channels 224 (224 / 448 / 672 / 896: multiples of 32 only).  Weights are padded to match by the packer -- the manifest kind
-// carries the recipe, "|R=" row segments and "|C=" channel segments as logical>padded pairs, absent when nothing is padded (the
-// ImageNet models: byte-identical manifests) -- with zero rows / columns / biases / norm affines in the tail, so a padded channel
-// stays exactly zero through every layer.  Only the normalisations must know the LOGICAL counts (group membership and divisor of
-// GroupNorm, mean / variance of LayerNorm); attention simply gains all-zero heads.  cin / cout / c below are PHYSICAL counts.
-static inline int pad64(int c) { return (c + 63) & ~63; }
-struct Seg { int n, p; };
-static std::string seg_spec(const char* tag, std::initializer_list<Seg> segs) {
-    bool any = false; for (const Seg& g : segs) any |= g.n != g.p;
-    if (!any) return "";
-    std::string o = std::string("|") + tag + "=";
-    bool first = true;
-    for (const Seg& g : segs) { char b[48]; snprintf(b, sizeof b, "%s%d>%d", first ? "" : ",", g.n, g.p); o += b; first = false; }
-    return o;
-}
-struct ResW { int cin, cout; size_t gn1g, gn1b, w1, b1, gn2g, gn2b, w2, b2, wsk, bsk; int emb_off; bool skip; int l0, l1, lout, p0, p1; };
-constexpr int XA_NP = 128;        // padded (heads x neighbours) width of the skinny cross-attention operands
-
-struct StW {
-    int c, heads; size_t gng, gnb, win, bin, ln1g, ln1b, wqk, wv, wo1, bo1, ln2g, ln2b, wq2, wo2, bo2, ln3g, ln3b, wff1,
-        bff1, wff2, bff2, wout, bout, wfo, bfo; int kv_off; long long xa_unit;   // xa_unit: per-sample element offset of this layer's (G, U) pair
-    int lc;                           // logical channels (c is padded)
-    bool v_follows;
-};
-struct ConvW { int c; size_t w, b; int lc; };
-struct ULayer { int kind; int idx; };            // 0 conv_in, 1 res, 2 st, 3 down, 4 up
-struct UBlock { int where; std::vector<ULayer> layers; };   // where: 0 input, 1 middle, 2 output
-
-struct UNet : ModelBase {
-    rdm_unet_cfg cfg{};
-    std::vector<UBlock> blocks; std::vector<ResW> res; std::vector<StW> st; std::vector<ConvW> down, up;
-    size_t te0w, te0b, te2w, te2b, embw, embb, kvw, cinw, cinb, outg, outb, outw, outbias;
-    int emb_total = 0, kv_total = 0; long long xa_total = 0;         // xa_total: per-sample elements of all (G, U) pairs
-    bf16_t* xa_cache = nullptr; size_t xa_cache_bytes = 0;
-    // cached cross-attention K/V for the current conditioning
-    bf16_t* kv_cache = nullptr; size_t kv_cache_bytes = 0;
-    float* emb_table = nullptr; size_t emb_table_bytes = 0;      // rdm_ddim_sample: one row of emb_total floats per sampler timestep
-    int ctx_rows = 0;            // samples [ctx_rows, B') of the cached conditioning have ALL-ZERO neighbours (the unconditional half of
-                                 // a guided batch): their cross-attention is the output bias, no GEMM runs for them
-    void release() { free_dev(xa_cache, xa_cache_bytes); free_dev(kv_cache, kv_cache_bytes); free_dev(emb_table, emb_table_bytes); ModelBase::release(); }
-};
-
-static void build_unet(UNet& u, const rdm_unet_cfg& c, Manifest& mf) {
-    u.cfg = c;
-    const int mc = c.model_channels, ted = mc * 4, mcp = pad64(mc);       // ted = 4 mc: a multiple of 64 whenever mc % 32 == 0... (128-aligned)
-    // vec: fp32 vector(s) over channel segments; mat: bf16 [rows][cols]; both padded per segment
-    auto vec = [&](const std::string& n, std::initializer_list<Seg> segs) {
-        size_t tot = 0; for (const Seg& g : segs) tot += g.p;
-        return mf.add("f32" + seg_spec("R", segs), n, tot * 4);
-    };
-    auto mat = [&](const char* kind, const std::string& n, std::initializer_list<Seg> rows, std::initializer_list<Seg> cols, size_t elt = 2, int taps = 1) {
-        size_t r = 0, k = 0; for (const Seg& g : rows) r += g.p; for (const Seg& g : cols) k += g.p;
-        return mf.add((std::string(kind) + seg_spec("R", rows) + seg_spec("C", cols)), n, r * k * taps * elt);
-    };
-    const Seg TED{ted, ted};
-    u.te0w = mat("bf16", "time_embed.0.weight", {TED}, {{mc, mcp}}); u.te0b = vec("time_embed.0.bias", {TED});
-    u.te2w = mat("bf16", "time_embed.2.weight", {TED}, {TED}); u.te2b = vec("time_embed.2.bias", {TED});
-    std::string emb_w_srcs, emb_b_srcs, kv_srcs, emb_rspec, kv_rspec;
-    bool emb_padded = false, kv_padded = false;
-    u.emb_total = 0; u.kv_total = 0; u.xa_total = 0;
-    auto in_attn = [&](int ds) { for (int i = 0; i < c.n_attention_resolutions; i++) if (c.attention_resolutions[i] == ds) return true; return false; };
-    auto add_seg = [](std::string& spec, bool& padded, int n, int p) { char b[48]; snprintf(b, sizeof b, "%s%d>%d", spec.empty() ? "" : ",", n, p); spec += b; padded |= n != p; };
-    auto add_res = [&](const std::string& pre, int l0, int l1, int lout) {       // input = [l0 | l1] logical channels (l1: the skip tensor, or 0)
-        ResW r{}; r.l0 = l0; r.l1 = l1; r.lout = lout; r.p0 = pad64(l0); r.p1 = l1 ? pad64(l1) : 0;
-        r.cin = r.p0 + r.p1; r.cout = pad64(lout); r.skip = (l0 + l1) != lout;
-        const Seg S0{l0, r.p0}, S1{l1, r.p1}, SO{lout, r.cout};
-        if (l1) { r.gn1g = vec(pre + ".in_layers.0.weight", {S0, S1}); r.gn1b = vec(pre + ".in_layers.0.bias", {S0, S1}); }
-        else { r.gn1g = vec(pre + ".in_layers.0.weight", {S0}); r.gn1b = vec(pre + ".in_layers.0.bias", {S0}); }
-        r.w1 = l1 ? mat("conv3", pre + ".in_layers.2.weight", {SO}, {S0, S1}, 2, 9) : mat("conv3", pre + ".in_layers.2.weight", {SO}, {S0}, 2, 9);
-        r.b1 = vec(pre + ".in_layers.2.bias", {SO});
-        r.gn2g = vec(pre + ".out_layers.0.weight", {SO}); r.gn2b = vec(pre + ".out_layers.0.bias", {SO});
-        r.w2 = mat("conv3", pre + ".out_layers.3.weight", {SO}, {SO}, 2, 9); r.b2 = vec(pre + ".out_layers.3.bias", {SO});
-        if (r.skip) {
-            r.wsk = l1 ? mat("bf16", pre + ".skip_connection.weight", {SO}, {S0, S1}) : mat("bf16", pre + ".skip_connection.weight", {SO}, {S0});
-            r.bsk = vec(pre + ".skip_connection.bias", {SO});
-        }
-        r.emb_off = u.emb_total; u.emb_total += r.cout;
-        if (!emb_w_srcs.empty()) { emb_w_srcs += ","; emb_b_srcs += ","; }
-        emb_w_srcs += pre + ".emb_layers.1.weight"; emb_b_srcs += pre + ".emb_layers.1.bias";
-        add_seg(emb_rspec, emb_padded, lout, r.cout);
-        u.res.push_back(r); return (int)u.res.size() - 1;
-    };
-    auto add_st = [&](const std::string& pre, int lch) {
-        StW s{}; s.lc = lch; s.c = pad64(lch); s.heads = s.c / c.num_head_channels;
-        const int ch = s.c;
-        const Seg S{lch, ch}, F{4 * lch, 4 * lch};
-        const std::string tb = pre + ".transformer_blocks.0";
-        s.gng = vec(pre + ".norm.weight", {S}); s.gnb = vec(pre + ".norm.bias", {S});
-        s.win = mat("bf16", pre + ".proj_in.weight", {S}, {S}); s.bin = vec(pre + ".proj_in.bias", {S});
-        s.ln1g = vec(tb + ".norm1.weight", {S}); s.ln1b = vec(tb + ".norm1.bias", {S});
-        s.wqk = mat("bf16", tb + ".attn1.to_q.weight," + tb + ".attn1.to_k.weight", {S, S}, {S});
-        s.wv = mat("bf16", tb + ".attn1.to_v.weight", {S}, {S});
-        s.v_follows = s.wv == s.wqk + (size_t)2 * ch * ch * 2;      // to_v directly behind to_q | to_k in the blob: q | k | v is ONE projection (else the separate V path runs)
-        s.wo1 = mat("bf16", tb + ".attn1.to_out.0.weight", {S}, {S}); s.bo1 = vec(tb + ".attn1.to_out.0.bias", {S});
-        s.ln2g = vec(tb + ".norm2.weight", {S}); s.ln2b = vec(tb + ".norm2.bias", {S});
-        s.wq2 = mat("bf16", tb + ".attn2.to_q.weight", {S}, {S});
-        s.wo2 = mat("bf16", tb + ".attn2.to_out.0.weight", {S}, {S}); s.bo2 = vec(tb + ".attn2.to_out.0.bias", {S});
-        s.ln3g = vec(tb + ".norm3.weight", {S}); s.ln3b = vec(tb + ".norm3.bias", {S});
-        // GEGLU hidden width 4 * lch (a multiple of 128): not padded, only its K side
-        s.wff1 = mat("geglu_w", tb + ".ff.net.0.proj.weight", {{8 * lch, 8 * lch}}, {S});
-        s.bff1 = mf.add("geglu_b", tb + ".ff.net.0.proj.bias", (size_t)8 * lch * 4);
-        s.wff2 = mat("bf16", tb + ".ff.net.2.weight", {S}, {F}); s.bff2 = vec(tb + ".ff.net.2.bias", {S});
-        s.wout = mat("bf16", pre + ".proj_out.weight", {S}, {S}); s.bout = vec(pre + ".proj_out.bias", {S});
-        // ff.net.2 followed by proj_out is one linear map of [ff | t2]:  [W_out W_2 | W_out], bias W_out b_2 + b_out (packed in fp32)
-        s.wfo = mat("fuse_w", tb + ".ff.net.2.weight," + pre + ".proj_out.weight", {S}, {F, S});
-        s.bfo = mf.add("fuse_b" + seg_spec("R", {S}), tb + ".ff.net.2.bias," + pre + ".proj_out.weight," + pre + ".proj_out.bias", (size_t)ch * 4);
-        s.kv_off = u.kv_total; u.kv_total += 2 * ch;
-        s.xa_unit = u.xa_total; u.xa_total += 4LL * XA_NP * ch;      // G, U row-major + their fragment-ordered images (attention.hip: xattn_fused_kernel)
-        if (!kv_srcs.empty()) kv_srcs += ",";
-        kv_srcs += tb + ".attn2.to_k.weight," + tb + ".attn2.to_v.weight";
-        add_seg(kv_rspec, kv_padded, lch, ch); add_seg(kv_rspec, kv_padded, lch, ch);
-        u.st.push_back(s); return (int)u.st.size() - 1;
-    };
-    auto name_of = [](const char* grp, int i, int j) { char b[64]; snprintf(b, sizeof b, "%s.%d.%d", grp, i, j); return std::string(b); };
-
-    // input blocks (openaimodel.py:144-215); all channel bookkeeping below is LOGICAL
-    std::vector<int> chans;
-    {
-        UBlock b; b.where = 0; b.layers.push_back({0, 0});
-        u.cinw = mf.add("f32" + seg_spec("R", {{mc, mcp}}), "input_blocks.0.0.weight", (size_t)mcp * c.in_channels * 9 * 4);     // [mc][in][3][3]: rows padded
-        u.cinb = vec("input_blocks.0.0.bias", {{mc, mcp}});
-        u.blocks.push_back(b); chans.push_back(mc);
-    }
-    int ch = mc, ds = 1, idx = 1;
-    for (int level = 0; level < c.n_channel_mult; level++) {
-        const int mult = c.channel_mult[level];
-        for (int r = 0; r < c.num_res_blocks; r++) {
-            UBlock b; b.where = 0;
-            b.layers.push_back({1, add_res(name_of("input_blocks", idx, 0), ch, 0, mult * mc)});
-            ch = mult * mc;
-            if (in_attn(ds)) b.layers.push_back({2, add_st(name_of("input_blocks", idx, 1), ch)});
-            u.blocks.push_back(b); idx++; chans.push_back(ch);
-        }
-        if (level != c.n_channel_mult - 1) {
-            UBlock b; b.where = 0;
-            ConvW d{}; d.lc = ch; d.c = pad64(ch); const std::string pre = name_of("input_blocks", idx, 0);
-            d.w = mat("conv3", pre + ".op.weight", {{ch, d.c}}, {{ch, d.c}}, 2, 9); d.b = vec(pre + ".op.bias", {{ch, d.c}});
-            u.down.push_back(d); b.layers.push_back({3, (int)u.down.size() - 1});
-            u.blocks.push_back(b); idx++; chans.push_back(ch); ds *= 2;
-        }
-    }
-    {   // middle (openaimodel.py:223-249)
-        UBlock b; b.where = 1;
-        b.layers.push_back({1, add_res("middle_block.0", ch, 0, ch)});
-        b.layers.push_back({2, add_st("middle_block.1", ch)});
-        b.layers.push_back({1, add_res("middle_block.2", ch, 0, ch)});
-        u.blocks.push_back(b);
-    }
-    int oidx = 0;   // output blocks (openaimodel.py:252-305)
-    for (int level = c.n_channel_mult - 1; level >= 0; level--) {
-        const int mult = c.channel_mult[level];
-        for (int i = 0; i <= c.num_res_blocks; i++) {
-            const int ich = chans.back(); chans.pop_back();
-            UBlock b; b.where = 2; int j = 0;
-            b.layers.push_back({1, add_res(name_of("output_blocks", oidx, j++), ch, ich, mc * mult)});
-            ch = mc * mult;
-            if (in_attn(ds)) b.layers.push_back({2, add_st(name_of("output_blocks", oidx, j++), ch)});
-            if (level && i == c.num_res_blocks) {
-                ConvW up{}; up.lc = ch; up.c = pad64(ch); const std::string pre = name_of("output_blocks", oidx, j++);
-                up.w = mat("conv3", pre + ".conv.weight", {{ch, up.c}}, {{ch, up.c}}, 2, 9); up.b = vec(pre + ".conv.bias", {{ch, up.c}});
-                u.up.push_back(up); b.layers.push_back({4, (int)u.up.size() - 1}); ds /= 2;
-            }
-            u.blocks.push_back(b); oidx++;
-        }
-    }
-    u.outg = vec("out.0.weight", {{mc, mcp}}); u.outb = vec("out.0.bias", {{mc, mcp}});
-    // out conv weights stay [Cout][Cin][3][3] fp32 (misc.hip conv_out_kernel): the Cin axis is padded
-    u.outw = mf.add(mc == mcp ? std::string("f32") : "f32_cin" + seg_spec("C", {{mc, mcp}}), "out.2.weight", (size_t)c.out_channels * mcp * 9 * 4);
-    u.outbias = mf.add("f32", "out.2.bias", (size_t)c.out_channels * 4);
-    u.embw = mf.add(std::string("bf16") + (emb_padded ? "|R=" + emb_rspec : ""), emb_w_srcs, (size_t)u.emb_total * ted * 2);
-    u.embb = mf.add(std::string("f32") + (emb_padded ? "|R=" + emb_rspec : ""), emb_b_srcs, (size_t)u.emb_total * 4);
-    u.kvw = mf.add(std::string("bf16") + (kv_padded ? "|R=" + kv_rspec : ""), kv_srcs, (size_t)u.kv_total * c.context_dim * 2);
-}
-
-// ------------------------------------------------------------------------------------ first-stage description (decoder and encoder)
-// ldm / taming Decoder and Encoder are built from the same pieces: ResnetBlocks (+ one AttnBlock per block at attn_resolutions) per
-// level, a resampling conv between levels, and a res - attn - res middle.
-struct VqRes { int cin, cout; size_t n1g, n1b, w1, b1, n2g, n2b, w2, b2, wsk, bsk; bool skip; };
-struct VqAttn { int c; size_t ng, nb, wq, bq, wk, bk, wv, bv, wo, bo; };
-struct VqLevel {
-    std::vector<VqRes> blocks;
-    std::vector<VqAttn> attn;          // one per block, or none
-    ConvW resample{};                  // the level's Upsample / stride-2 Downsample conv (the last level walked has none)
-};
-struct VqMid { VqRes res1, res2; VqAttn attn; bool has_attn; };
-
-static VqRes add_vq_res(Manifest& mf, const std::string& pre, int cin, int cout) {
-    VqRes r{}; r.cin = cin; r.cout = cout; r.skip = cin != cout;
-    r.n1g = mf.f32(pre + ".norm1.weight", cin); r.n1b = mf.f32(pre + ".norm1.bias", cin);
-    r.w1 = mf.conv3(pre + ".conv1.weight", cout, cin); r.b1 = mf.f32(pre + ".conv1.bias", cout);
-    r.n2g = mf.f32(pre + ".norm2.weight", cout); r.n2b = mf.f32(pre + ".norm2.bias", cout);
-    r.w2 = mf.conv3(pre + ".conv2.weight", cout, cout); r.b2 = mf.f32(pre + ".conv2.bias", cout);
-    if (r.skip) { r.wsk = mf.bf16(pre + ".nin_shortcut.weight", (size_t)cout * cin); r.bsk = mf.f32(pre + ".nin_shortcut.bias", cout); }
-    return r;
-}
-static VqAttn add_vq_attn(Manifest& mf, const std::string& p, int ch) {
-    VqAttn a{}; a.c = ch;
-    a.ng = mf.f32(p + ".norm.weight", ch); a.nb = mf.f32(p + ".norm.bias", ch);
-    a.wq = mf.bf16(p + ".q.weight", (size_t)ch * ch); a.bq = mf.f32(p + ".q.bias", ch);
-    a.wk = mf.bf16(p + ".k.weight", (size_t)ch * ch); a.bk = mf.f32(p + ".k.bias", ch);
-    a.wv = mf.bf16(p + ".v.weight", (size_t)ch * ch); a.bv = mf.f32(p + ".v.bias", ch);
-    a.wo = mf.bf16(p + ".proj_out.weight", (size_t)ch * ch); a.bo = mf.f32(p + ".proj_out.bias", ch);
-    return a;
-}
-// pre: "decoder.mid" / "encoder.mid"
-static VqMid add_vq_mid(Manifest& mf, const std::string& pre, int ch, bool attn) {
-    VqMid m{}; m.has_attn = attn;
-    m.res1 = add_vq_res(mf, pre + ".block_1", ch, ch);
-    if (attn) m.attn = add_vq_attn(mf, pre + ".attn_1", ch);
-    m.res2 = add_vq_res(mf, pre + ".block_2", ch, ch);
-    return m;
-}
-// pre: "decoder.up.<lvl>" / "encoder.down.<lvl>"; n_blocks ResnetBlocks ch -> bout (AttnBlocks behind them when the level's resolution
-// `res` is in attn_resolutions), then the conv of `resample` ("upsample" / "downsample"; null: none).  ch leaves as the level's width.
-static VqLevel add_vq_level(Manifest& mf, const rdm_vq_cfg& c, const std::string& pre, int n_blocks, int& ch, int bout, int res, const char* resample) {
-    VqLevel L;
-    bool at = false;
-    for (int i = 0; i < c.n_attn_resolutions; i++) at = at || c.attn_resolutions[i] == res;
-    for (int i = 0; i < n_blocks; i++) {
-        L.blocks.push_back(add_vq_res(mf, pre + ".block." + std::to_string(i), ch, bout)); ch = bout;
-        if (at) L.attn.push_back(add_vq_attn(mf, pre + ".attn." + std::to_string(i), ch));
-    }
-    if (resample) {
-        const std::string p = pre + "." + resample + ".conv";
-        L.resample.c = ch; L.resample.w = mf.conv3(p + ".weight", ch, ch); L.resample.b = mf.f32(p + ".bias", ch);
-    }
-    return L;
-}
-
-struct VqModel : ModelBase {
-    rdm_vq_cfg cfg{};
-    bool wide = false;                             // z_channels > 4 (taming VQGAN-f16: 256): latent handled as bf16 NHWC tokens, GEMM-class
-                                                   // post_quant_conv / conv_in; else the 3-channel VQ-f4 path (tiny fp32 stem kernels)
-    size_t codebook, pqw, pqb, cinw, cinb, noutg, noutb, coutw, coutb;
-    VqMid mid;
-    std::vector<VqLevel> levels;                   // indexed by level (walked high to low; level 0 has no upsample)
-    float* code_norms = nullptr;                   // |e_j|^2 of the codebook (vqcode.hip), made on first use by rdm_vq_encode_indices
-    void release() { if (code_norms) (void)hipFree(code_norms); code_norms = nullptr; ModelBase::release(); }
-};
-
-static void build_vq(VqModel& v, const rdm_vq_cfg& c, Manifest& mf) {
-    v.cfg = c;
-    v.wide = c.z_channels > 4;
-    if (!c.kl) v.codebook = mf.f32("quantize.embedding.weight", (size_t)c.n_embed * c.embed_dim);
-    int bin = c.ch * c.ch_mult[c.n_ch_mult - 1];
-    const size_t pq = (size_t)c.z_channels * c.embed_dim;      // wide: post_quant_conv a bf16 GEMM operand, conv_in a conv3 entry; else fp32 for the stem kernels
-    v.pqw = v.wide ? mf.bf16("post_quant_conv.weight", pq) : mf.f32("post_quant_conv.weight", pq); v.pqb = mf.f32("post_quant_conv.bias", c.z_channels);
-    v.cinw = v.wide ? mf.conv3("decoder.conv_in.weight", bin, c.z_channels) : mf.f32("decoder.conv_in.weight", (size_t)bin * c.z_channels * 9);
-    v.cinb = mf.f32("decoder.conv_in.bias", bin);
-    v.mid = add_vq_mid(mf, "decoder.mid", bin, c.mid_attn);
-    v.levels.assign(c.n_ch_mult, {});
-    int curr_res = c.resolution >> (c.n_ch_mult - 1);
-    for (int lvl = c.n_ch_mult - 1; lvl >= 0; lvl--, curr_res *= 2)
-        v.levels[lvl] = add_vq_level(mf, c, "decoder.up." + std::to_string(lvl), c.num_res_blocks + 1, bin, c.ch * c.ch_mult[lvl], curr_res, lvl ? "upsample" : nullptr);
-    v.noutg = mf.f32("decoder.norm_out.weight", bin); v.noutb = mf.f32("decoder.norm_out.bias", bin);
-    v.coutw = mf.f32("decoder.conv_out.weight", (size_t)c.out_ch * bin * 9); v.coutb = mf.f32("decoder.conv_out.bias", c.out_ch);
-}
-
-// First-stage ENCODER (VQ-f4: training input; VQGAN-f16: image -> codes).
-// ldm Encoder (ldm/modules/diffusionmodules/model.py; un-vendored: restated from the published code, parity unpinned) as reached from
-// MinimalRETRODiffusion.get_input -> encode_first_stage -> VQModelInterface.encode = quant_conv(encoder(x)) under torch.no_grad()
-// (rdm/models/diffusion/ddpm.py:390-391): conv_in, per level num_res_blocks ResnetBlocks (+ AttnBlocks at attn_resolutions) and a
-// stride-2 Downsample conv with (0, 1, 0, 1) zero padding, mid res-attn-res, GroupNorm + swish + conv_out, quant_conv (1x1).
-// The taming VQGAN-f16 encoder (wide latent; un-vendored, parity unpinned) is the same graph: only the tail's weights are stored otherwise
-// (conv_out as conv3 bf16, quant_conv as a bf16 GEMM operand: vqenc_body).
-struct VqEncModel : ModelBase {
-    rdm_vq_cfg cfg{};
-    bool wide = false;                             // z_channels > 4 (taming VQGAN-f16): conv_out is an ordinary 3x3 conv, quant_conv a GEMM with an fp32 token-major output
-    size_t cinw, cinb, noutg, noutb, coutw, coutb, qw, qb;
-    std::vector<VqLevel> levels;                   // indexed by level (walked low to high; the last level has no downsample)
-    VqMid mid;
-};
-static void build_vqenc(VqEncModel& v, const rdm_vq_cfg& c, Manifest& mf) {
-    v.cfg = c;
-    v.cinw = mf.f32("encoder.conv_in.weight", (size_t)c.ch * c.out_ch * 9); v.cinb = mf.f32("encoder.conv_in.bias", c.ch);
-    v.levels.assign(c.n_ch_mult, {});
-    int bin = c.ch, curr_res = c.resolution;
-    for (int lvl = 0; lvl < c.n_ch_mult; lvl++, curr_res /= 2)
-        v.levels[lvl] = add_vq_level(mf, c, "encoder.down." + std::to_string(lvl), c.num_res_blocks, bin, c.ch * c.ch_mult[lvl], curr_res,
-                                     lvl != c.n_ch_mult - 1 ? "downsample" : nullptr);
-    v.mid = add_vq_mid(mf, "encoder.mid", bin, c.mid_attn);
-    v.noutg = mf.f32("encoder.norm_out.weight", bin); v.noutb = mf.f32("encoder.norm_out.bias", bin);
-    v.wide = c.z_channels > 4;
-    const size_t qc = (size_t)c.embed_dim * c.z_channels;      // wide: conv_out a conv3 entry, quant_conv a bf16 GEMM operand; else fp32 for the head / quantiser kernels
-    v.coutw = v.wide ? mf.conv3("encoder.conv_out.weight", c.z_channels, bin) : mf.f32("encoder.conv_out.weight", (size_t)c.z_channels * bin * 9);
-    v.coutb = mf.f32("encoder.conv_out.bias", c.z_channels);
-    v.qw = v.wide ? mf.bf16("quant_conv.weight", qc) : mf.f32("quant_conv.weight", qc); v.qb = mf.f32("quant_conv.bias", c.embed_dim);
-}
-
-// ------------------------------------------------------------------------------------ CLIP description
-struct ClipBlk { size_t ln1g, ln1b, wqkv, bqkv, wo, bo, ln2g, ln2b, wfc, bfc, wpj, bpj; };
-struct ClipModel : ModelBase {
-    rdm_clip_cfg cfg{};
-    std::vector<ClipBlk> text, vis;
-    size_t tok, pos, lnfg, lnfb, tproj;                               // text
-    size_t conv1, cls, vpos, lnpreg, lnpreb, lnpostg, lnpostb, vproj;  // vision
-};
-static void build_clip(ClipModel& m, const rdm_clip_cfg& c, Manifest& mf) {
-    m.cfg = c;
-    auto tower = [&](std::vector<ClipBlk>& out, const std::string& pre, int w, int layers) {
-        for (int i = 0; i < layers; i++) {
-            char b[96]; snprintf(b, sizeof b, "%s.resblocks.%d", pre.c_str(), i); const std::string p = b;
-            ClipBlk k{};
-            k.ln1g = mf.f32(p + ".ln_1.weight", w); k.ln1b = mf.f32(p + ".ln_1.bias", w);
-            k.wqkv = mf.bf16(p + ".attn.in_proj_weight", (size_t)3 * w * w); k.bqkv = mf.f32(p + ".attn.in_proj_bias", 3 * w);
-            k.wo = mf.bf16(p + ".attn.out_proj.weight", (size_t)w * w); k.bo = mf.f32(p + ".attn.out_proj.bias", w);
-            k.ln2g = mf.f32(p + ".ln_2.weight", w); k.ln2b = mf.f32(p + ".ln_2.bias", w);
-            k.wfc = mf.bf16(p + ".mlp.c_fc.weight", (size_t)4 * w * w); k.bfc = mf.f32(p + ".mlp.c_fc.bias", 4 * w);
-            k.wpj = mf.bf16(p + ".mlp.c_proj.weight", (size_t)4 * w * w); k.bpj = mf.f32(p + ".mlp.c_proj.bias", w);
-            out.push_back(k);
-        }
-    };
-    const int vw = c.vision_width, g = c.image_resolution / c.vision_patch_size, tw = c.transformer_width;
-    m.conv1 = mf.bf16("visual.conv1.weight", (size_t)vw * 3 * c.vision_patch_size * c.vision_patch_size);
-    m.cls = mf.f32("visual.class_embedding", vw); m.vpos = mf.f32("visual.positional_embedding", (size_t)(g * g + 1) * vw);
-    m.lnpreg = mf.f32("visual.ln_pre.weight", vw); m.lnpreb = mf.f32("visual.ln_pre.bias", vw);
-    tower(m.vis, "visual.transformer", vw, c.vision_layers);
-    m.lnpostg = mf.f32("visual.ln_post.weight", vw); m.lnpostb = mf.f32("visual.ln_post.bias", vw);
-    m.vproj = mf.add("bf16_t", "visual.proj", (size_t)vw * c.embed_dim * 2);
-    tower(m.text, "transformer", tw, c.transformer_layers);
-    m.tok = mf.f32("token_embedding.weight", (size_t)c.vocab_size * tw);
-    m.pos = mf.f32("positional_embedding", (size_t)c.context_length * tw);
-    m.lnfg = mf.f32("ln_final.weight", tw); m.lnfb = mf.f32("ln_final.bias", tw);
-    m.tproj = mf.add("bf16_t", "text_projection", (size_t)tw * c.embed_dim * 2);
-}
-
-// ------------------------------------------------------------------------------------ RARM transformer description
-struct RarmBlk { size_t ln1g, ln1b, wqkv, wo1, bo1, ln2g, ln2b, wq2, wo2, bo2, ln3g, ln3b, wff1, bff1, wff2, bff2; };
-struct RarmModel : ModelBase {
-    rdm_rarm_cfg cfg{}; int C = 0, kv_total = 0;
-    std::vector<RarmBlk> blk;
-    size_t emb, pos, kvw, wpo, bpo;
-    // sampling state: per-layer self-attention K/V cache [depth][2][B'][L][C], projected neighbours [B'*k][depth*2*C],
-    // device step counter / completion counter / current tokens, logits of the current step
-    char* cache = nullptr; size_t cache_bytes = 0;
-    char* ctxkv = nullptr; size_t ctxkv_bytes = 0;
-    char* state = nullptr; size_t state_bytes = 0;
-    // decode-step cross-attention operands per layer (rarm_prepare): [depth][2][Bc][128][C] bf16 (G, UT), valid for xa_B conditional sequences and xa_k neighbours
-    char* xa = nullptr; size_t xa_bytes = 0; int xa_B = 0, xa_k = 0;
-    void release() { free_dev(cache, cache_bytes); free_dev(ctxkv, ctxkv_bytes); free_dev(state, state_bytes); free_dev(xa, xa_bytes); xa_B = xa_k = 0; ModelBase::release(); }
-};
-static void build_rarm(RarmModel& m, const rdm_rarm_cfg& c, Manifest& mf) {
-    m.cfg = c; m.C = c.n_heads * c.d_head;
-    const int C = m.C;
-    m.emb = mf.f32("proj_in.weight", (size_t)c.vocab_in * C);
-    m.pos = mf.add("f32_t", "positional_encoding", (size_t)C * c.sequence_length * 4);
-    std::string kv_srcs;
-    for (int i = 0; i < c.depth; i++) {
-        char b[64]; snprintf(b, sizeof b, "transformer_blocks.%d", i); const std::string p = b;
-        RarmBlk k{};
-        k.ln1g = mf.f32(p + ".norm1.weight", C); k.ln1b = mf.f32(p + ".norm1.bias", C);
-        k.wqkv = mf.bf16(p + ".attn1.to_q.weight," + p + ".attn1.to_k.weight," + p + ".attn1.to_v.weight", (size_t)3 * C * C);
-        k.wo1 = mf.bf16(p + ".attn1.to_out.0.weight", (size_t)C * C); k.bo1 = mf.f32(p + ".attn1.to_out.0.bias", C);
-        k.ln2g = mf.f32(p + ".norm2.weight", C); k.ln2b = mf.f32(p + ".norm2.bias", C);
-        k.wq2 = mf.bf16(p + ".attn2.to_q.weight", (size_t)C * C);
-        k.wo2 = mf.bf16(p + ".attn2.to_out.0.weight", (size_t)C * C); k.bo2 = mf.f32(p + ".attn2.to_out.0.bias", C);
-        k.ln3g = mf.f32(p + ".norm3.weight", C); k.ln3b = mf.f32(p + ".norm3.bias", C);
-        k.wff1 = mf.add("geglu_w", p + ".ff.net.0.proj.weight", (size_t)8 * C * C * 2);
-        k.bff1 = mf.add("geglu_b", p + ".ff.net.0.proj.bias", (size_t)8 * C * 4);
-        k.wff2 = mf.bf16(p + ".ff.net.2.weight", (size_t)C * 4 * C); k.bff2 = mf.f32(p + ".ff.net.2.bias", C);
-        if (!kv_srcs.empty()) kv_srcs += ",";
-        kv_srcs += p + ".attn2.to_k.weight," + p + ".attn2.to_v.weight";
-        m.blk.push_back(k);
-    }
-    m.kv_total = c.depth * 2 * C;
-    m.kvw = mf.add("bf16", kv_srcs, (size_t)m.kv_total * c.context_dim * 2);      // the neighbours' K/V of ALL layers: one GEMM per sampling call
-    m.wpo = mf.bf16("proj_out.weight", (size_t)c.vocab_out * C); m.bpo = mf.f32("proj_out.bias", c.vocab_out);
-}
-
-// ------------------------------------------------------------------------------------ context
-struct rdm_ctx {
-    int device = 0; hipStream_t stream = nullptr; char err[512] = {0};
-    void* zero_page = nullptr; float* eye3 = nullptr;
-    UNet unet; VqModel vq; VqEncModel vqenc; ClipModel clip; RarmModel rarm; KnnDb db;
-    float* gn_partial = nullptr; size_t gn_partial_bytes = 0;
-    char* splitk_ws = nullptr; size_t splitk_ws_bytes = 0;   // fp32 partial planes of the K-split halo convs
-    char* samp = nullptr; size_t samp_bytes = 0;     // sampler scratch
-    // derived weight layouts, built on first use per weight and dropped when a model is reloaded: fragment-ordered copies of the 3x3 conv
-    // weights (conv_halo4.hip) and of the Linear / 1x1 weights (lin4.hip; optionally scaled by a LayerNorm's gamma, with the (s, b') table
-    // of the folded LayerNorm beside it).  Keyed on everything the copy depends on -- the entry is the copy of exactly that
-    // (weight, shape, kind, gamma): two weights can never alias one entry.
-    struct FragKey {
-        const void* W; int N, K, kind; const void* aux;       // kind: 0 conv3x3, 1 linear, 2 linear GEGLU-ordered, 3 / 4 = 1 / 2 with LayerNorm folded in (aux = gamma)
-        bool operator==(const FragKey& o) const { return W == o.W && N == o.N && K == o.K && kind == o.kind && aux == o.aux; }
-    };
-    struct FragKeyHash {
-        size_t operator()(const FragKey& k) const {
-            size_t h = std::hash<const void*>()(k.W);
-            for (size_t v : {(size_t)k.N, (size_t)k.K, (size_t)k.kind, (size_t)(uintptr_t)k.aux}) h = (h ^ v) * 0x9E3779B97F4A7C15ull + (h >> 29);
-            return h;
-        }
-    };
-    struct FragVal { bf16_t* frag; float* sb; };
-    std::unordered_map<FragKey, FragVal, FragKeyHash> wfrag;
-    char* bwd_tmp = nullptr; size_t bwd_tmp_bytes = 0;          // scratch of the backward ops (backward.hip)
-    char* wfrag_tmp = nullptr; size_t wfrag_tmp_bytes = 0;      // derived copies of caller-owned weights, re-packed per call (Ops::derived)
-    void drop_frags() { for (auto& kv : wfrag) { (void)hipFree(kv.second.frag); if (kv.second.sb) (void)hipFree(kv.second.sb); } wfrag.clear(); }
-    // derived copy of kind `kind` of the weight W [N][K] (conv kinds: K = input channels): 0 = fragment-ordered 3x3 conv weights
-    // (conv_halo4.hip), 1 / 2 = fragment-ordered Linear / 1x1 weights (lin4.hip; 2: GEGLU-ordered), 5 = [4][N][2][2][Cin] phase weights of
-    // a fused-upsample conv (igemm.hip CONV == 3)
-    static size_t derived_bytes(int kind, int N, int K) { return (size_t)N * K * 2 * (kind == 0 ? 9 : kind == 5 ? 16 : 1); }
-    hipError_t pack_derived(int kind, const bf16_t* W, bf16_t* d, int N, int K) {
-        return kind == 0 ? launch_conv_w_fragpack(W, d, N, K, stream)
-             : kind == 5 ? launch_conv_phase_weights(W, d, N, K, stream)
-                         : launch_lin_w_fragpack(W, d, N, K, K, kind == 2, stream);
-    }
-    // (the copies are packed on `stream`; rdm_set_stream synchronises the old stream before it installs another one, so a copy is
-    //  complete before any other stream can launch a kernel that reads it)
-    const bf16_t* cached_derived(const bf16_t* W, int N, int K, int kind) {
-        const FragKey key{W, N, K, kind, nullptr};
-        auto it = wfrag.find(key);
-        if (it != wfrag.end()) return it->second.frag;
-        bf16_t* d = nullptr;
-        if (hipMalloc((void**)&d, derived_bytes(kind, N, K)) != hipSuccess) return nullptr;
-        if (pack_derived(kind, W, d, N, K) != hipSuccess) { (void)hipFree(d); return nullptr; }
-        wfrag[key] = FragVal{d, nullptr};
-        return d;
-    }
-    // [2][C] fp32 = {0, b}: the rowvec of attn1.to_out over a guided batch's [conditional | unconditional] halves (unet_body: the
-    // unconditional rows' cross-attention is exactly attn2.to_out's bias b, which then rides in attn1.to_out's start values)
-    const float* zero_bias_pair(const float* b, int C) {
-        const FragKey key{b, C, 2, 6, nullptr};
-        auto it = wfrag.find(key);
-        if (it != wfrag.end()) return it->second.sb;
-        float* t = nullptr;
-        if (hipMalloc((void**)&t, (size_t)2 * C * sizeof(float)) != hipSuccess) return nullptr;
-        if (hipMemsetAsync(t, 0, (size_t)C * sizeof(float), stream) != hipSuccess ||
-            hipMemcpyAsync(t + C, b, (size_t)C * sizeof(float), hipMemcpyDeviceToDevice, stream) != hipSuccess) { (void)hipFree(t); return nullptr; }
-        wfrag[key] = FragVal{nullptr, t};
-        return t;
-    }
-    // batch-invariant execution (rdm_set_deterministic / env RDM_DETERMINISTIC): every kernel-selection decision (skinny vs tiled GEMM,
-    // halo vs generic conv, conv split-K, the zero-context shortcut) is a function of the PER-SAMPLE layer shape only, so a row's
-    // result is bitwise independent of the batch it sits in and of the number of ranks the batch is sharded over
-    bool deterministic = rdm_env_int(getenv("RDM_DETERMINISTIC"), 0) != 0;
-    // debug tap (rdm_debug_tap): the output activation of top-level UNet block `tap_block` (NHWC bf16) is copied into tap_buf by the next forward
-    void* tap_buf = nullptr; size_t tap_bytes = 0; int tap_block = -1, tap_sub = 0;      // tap_sub: 0 = the block's output, else 16 * layer-in-block + stage (unet_body)
-    // RCCL communicator (rdm_comm_*): library handle from dlopen, function table, communicator
-    void* rccl_lib = nullptr; void* comm = nullptr; int comm_world = 0;
-    // optional per-launch HIP-event profiler for the GEMM-class kernels (bench.py roofline)
-    unsigned prof = 0;           // bit k set: record HIP events around launches of kind k (RDM_PROF_* in rdm_hip.h)
-    struct ProfRec { hipEvent_t a, b; int kind; double flops; const char* tag; int d0, d1, d2; };      // tag: the op's role in the graph (string literal), d*: its shape
-    std::vector<ProfRec> prof_recs; std::vector<hipEvent_t> prof_pool;
-    hipEvent_t prof_event() {
-        if (!prof_pool.empty()) { hipEvent_t e = prof_pool.back(); prof_pool.pop_back(); return e; }
-        hipEvent_t e; hipEventCreate(&e); return e;
-    }
-    int fail(int code, const char* fmt, ...) {
-        va_list ap; va_start(ap, fmt); vsnprintf(err, sizeof err, fmt, ap); va_end(ap); return code;
-    }
-};
-
-static int ensure_bytes(rdm_ctx* c, char** p, size_t* have, size_t need) {
-    if (*have >= need) return 0;
-    if (*p) { RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream)); RDM_CHECK_HIP(c, hipFree(*p)); *p = nullptr; *have = 0; }
-    RDM_CHECK_HIP(c, hipMalloc((void**)p, need));
-    *have = need; return 0;
-}
-
-// ------------------------------------------------------------------------------------ op helpers
-static int gn_chunks(int HW) { const int n = HW / 64; return n < 1 ? 1 : n > 32 ? 32 : n; }      // GroupNorm statistics: pixel chunks per sample
-
-// Which kernel takes a linear op that the skinny kernels may run (one bf16 operand, no row vector, alpha 1), and whether the LayerNorm-in-
-// kernel form takes a LayerNorm + projection: the ONE statement of both choices, shared by Ops::linear / Ops::linear_ln (every executor
-// and op entry) and by rdm_linear_rows_select, which reports it.  Host only: reads q's shape, activation and which pointers are set.
-static bool skinny_rows(bool deterministic, bool single_row, int M, int single_max) {
-    return deterministic ? single_row : (M <= 128 || (single_row && M <= single_max));
-}
-static int linear_kernel(SgemmParams& q, bool deterministic, bool single_row) {
-    // one-row-per-sample operands beyond these row counts take the tiled kernels
-    constexpr int SGEMM_MAX_ROWS = 4096;          // (2048 sequences: 716 -> 780 img/s against the tiled kernels, round 5)
-    // (round 5, same box: the GEGLU projection of the RARM decode step through the tiled kernel from ~200 rows on: 397.8 -> 409.5 img/s at 256
-    //  sequences, 487.0 -> 514.8 at 512; the plain projections through it: 221 / 305 -- their N = 768 gives the tiled kernel 16-24 tiles)
-    constexpr int SGEMM_GEGLU_MAX_ROWS = 192;
-    if (skinny_rows(deterministic, single_row, q.M, q.act == ACT_GEGLU ? SGEMM_GEGLU_MAX_ROWS : SGEMM_MAX_ROWS)) {
-        // 1536+ rows: LDS-staged 64 x 64 tiles (mgemm.hip) -- the skinny kernel's per-wave operand fetch is 75 MB through the L2 -> CU
-        // fabric for a [2048 x 768] x [768 x 768] product (33.6 us; 15.5 there).  Not in deterministic mode (the kernel choice would follow the batch).
-        static const int mg_from = rdm_env_int(getenv("RDM_MGEMM_FROM"), 1536);     // (tests move it)
-        if (!deterministic && single_row && mg_from > 0 && q.M >= mg_from && q.act != ACT_GEGLU && mgemm_supported(q)) return RDM_LINEAR_ROWS_MGEMM;
-        q.fixed_split = deterministic ? 1 : 0;
-        if (sgemm_supported(q)) return RDM_LINEAR_ROWS_SGEMM;
-    }
-    static const int mg_any = rdm_env_int(getenv("RDM_MGEMM_ANY"), 0);      // tests: operands of >= mg_any rows that are not single_row
-    if (!single_row && mg_any > 0 && q.M >= mg_any && q.act != ACT_GEGLU && mgemm_supported(q)) return RDM_LINEAR_ROWS_MGEMM;
-    return RDM_LINEAR_ROWS_TILED;
-}
-static bool linear_ln_takes(SgemmParams& q, bool deterministic, bool single_row) {
-    // (from ~200 rows on a separate LayerNorm pass + the 64 x 64-tile GEMM beats the LayerNorm-fused 32-row tiles: sgemm.hip)
-    constexpr int SGEMM_LN_MAX_ROWS = 192;
-    if (!deterministic && q.M > SGEMM_LN_MAX_ROWS) return false;
-    q.fixed_split = deterministic ? 1 : 0;
-    return skinny_rows(deterministic, single_row, q.M, 1024) && sgemm_supported(q);
-}
-
-// The kernel dispatch of the model executors and of the operator-level entries (rdm_op_*): which kernel runs an op, with which
-// parameters.  Weight and bias arguments are device pointers (executors: o.w<T>(offset) into the model blob).
-struct Ops {
-    rdm_ctx* c; Arena* ar; const char* blob; bool plan; int rc = 0;
-    template <typename T> const T* w(size_t off) const { return (const T*)(blob + off); }
-    bf16_t* abf(size_t n) { return (bf16_t*)ar->alloc(n * 2); }
-    float* af32(size_t n) { return (float*)ar->alloc(n * 4); }
-    void check(hipError_t e, const char* what) {
-        if (e != hipSuccess && rc == 0) rc = c->fail(-3, "%s: %s", what, hipGetErrorString(e));
-    }
-    IgemmParams base(int M, int N, int K) {
-        IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.ldo = N; p.zero_page = c->zero_page;
-        p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1; return p;
-    }
-    // Derived weight copies (rdm_ctx::derived_bytes): with constant weights (the executors' blobs; the op entries when their caller promises
-    // constant weights) built once per weight and cached in the context, otherwise packed per call into wfrag_tmp.
-    // null: the copy could not be made, and the op runs a kernel that reads W itself.
-    bool const_weights = true;
-    const bf16_t* derived(const bf16_t* W, int N, int K, int kind) {
-        if (const_weights) return c->cached_derived(W, N, K, kind);
-        if (ensure_bytes(c, &c->wfrag_tmp, &c->wfrag_tmp_bytes, rdm_ctx::derived_bytes(kind, N, K)) != 0) return nullptr;
-        bf16_t* d = (bf16_t*)c->wfrag_tmp;
-        return c->pack_derived(kind, W, d, N, K) == hipSuccess ? d : nullptr;
-    }
-    bool single_row = false;     // set by callers around ops whose operand has one row per sample (see linear)
-    int rows_hint = 0;           // rows per sample of the operand of the linear ops that follow (0 = unknown); set by the UNet block executors
-    // skinny (weight-streaming) kernel for decode-sized operands.  Fast mode: whenever M <= 128, and for `single_row` operands up to
-    // single_max rows.  Deterministic mode: exactly for the ops with ONE row per sample (`single_row`: time embedding, RARM decode step,
-    // CLIP projection), at any batch (one-row-per-sample operands of bigger batches -- RARM decode at 128+ sequences per GPU -- keep the
-    // skinny kernel: its row blocks scale with M, while the tiled kernels would run a dozen 256-row tiles)
-    bool skinny(int M, int single_max) const { return skinny_rows(c->deterministic, single_row, M, single_max); }
-    // out[M,N] = act(A[M,K] W^T + bias) (+res)
-    // a1_wrap_rows > 0: A1 holds that many rows only, row m reads m % a1_wrap_rows (lin4 only: callers check lin4_takes first)
-    bool lin4_takes(int M, int N, int C0, int C1, int a1_wrap_rows, int res_wrap_rows = 0) {
-        if (c->deterministic) return false;
-        IgemmParams t = base(M, N, C0 + C1);
-        t.C0 = C0; t.C1 = C1; t.W = (const bf16_t*)blob; t.Wfrag = t.W; t.out_bf16 = (bf16_t*)blob; t.a1_wrap_rows = a1_wrap_rows;
-        if (res_wrap_rows > 0) { t.res_bf16 = (const bf16_t*)blob; t.res_wrap_rows = res_wrap_rows; }
-        return lin4_supported(t, 1);
-    }
-    // rowvec / rowvec_ld / rv_rows: a per-row-group per-column add (IgemmParams::rowvec with rows_per_sample = rv_rows)
-    // alpha: scale of the product (the skinny and mid-size kernels take alpha == 1 only)
-    void linear(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int M, int N,
-                int act, const bf16_t* res, bf16_t* out, float* out_f32 = nullptr, const float* res_f32 = nullptr, int a1_wrap_rows = 0,
-                const float* rowvec = nullptr, int rowvec_ld = 0, int rv_rows = 1, int res_wrap_rows = 0, float alpha = 1.f) {
-        if (plan) return;
-        if (!A1 && C1 == 0 && !rowvec && alpha == 1.f) {         // N/32 x ceil(M/32) blocks (sgemm.hip), 64 x 64 tiles (mgemm.hip)
-            SgemmParams q{}; q.A = A0; q.lda = C0; q.W = W; q.M = M; q.N = N; q.K = C0; q.bias = bias;
-            q.act = act; q.res_f32 = res_f32; q.res_bf16 = res; q.out_f32 = out_f32; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-            const int kernel = linear_kernel(q, c->deterministic, single_row);
-            if (kernel != RDM_LINEAR_ROWS_TILED) {
-                const bool mid = kernel == RDM_LINEAR_ROWS_MGEMM;
-                prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
-                check(mid ? launch_mgemm(q, c->stream) : launch_sgemm(q, c->stream), mid ? "mid-size linear" : "skinny linear");
-                prof_end();
-                return;
-            }
-        }
-        IgemmParams p = base(M, N, C0 + C1);
-        p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = W; p.bias = bias; p.alpha = alpha;
-        p.act = act; p.res_bf16 = res; p.res_f32 = res_f32; p.out_bf16 = out; p.out_f32 = out_f32; p.a1_wrap_rows = a1_wrap_rows;
-        p.res_wrap_rows = res_wrap_rows;
-        if (rowvec) { p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = rv_rows; }
-        if (act == ACT_GEGLU) p.ldo = N / 2;
-        // one-wave-per-SIMD kernel for the big-M projections (its tile choice follows M, so not in deterministic mode)
-        // (deterministic mode: its use must not follow the batch -- exactly when the rows of ONE sample fill whole 128 / 256-row tiles,
-        //  at any tile count; a row's sum order is the same in every tile position)
-        {
-            IgemmParams t = p; t.Wfrag = p.W;
-            const int tile_rows = (N % 384 == 0) ? 128 : 256;
-            const bool det_ok = rows_hint > 0 && rows_hint % tile_rows == 0;
-            if (c->deterministic) t.l4_any_tiles = p.l4_any_tiles = 1;
-            if ((!c->deterministic || det_ok) && lin4_supported(t, 1)) p.Wfrag = derived(p.W, N, C0 + C1, act == ACT_GEGLU ? 2 : 1);
-        }
-        prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)(C0 + C1), M, N, C0 + C1);
-        check(launch_igemm(p, false, 1, c->stream), "linear");
-        prof_end();
-    }
-    // out = act(LayerNorm(x) W^T + bias) with the LayerNorm formed inside the skinny GEMM (sgemm.hip): decode-sized operands only.
-    // false = not available for this shape (the caller runs layernorm + linear)
-    bool linear_ln(const float* x, const float* g, const float* b, int C, const bf16_t* W, const float* bias, int M, int N, int act, bf16_t* out) {
-        SgemmParams q{}; q.ln_x = x; q.ln_g = g; q.ln_b = b; q.ln_eps = 1e-5f; q.W = W; q.M = M; q.N = N; q.K = C;
-        q.bias = bias; q.act = act; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-        if (!linear_ln_takes(q, c->deterministic, single_row)) return false;
-        if (plan) return true;
-        prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C, M, N, C);
-        check(launch_sgemm(q, c->stream), "skinny linear on a LayerNorm");
-        prof_end();
-        return true;
-    }
-    void conv3(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int B, int Hin, int Win, int N,
-               int stride, int ups, const float* rowvec, int rowvec_ld, const bf16_t* res, bf16_t* out, int asym = 0) {
-        if (plan) return;
-        const int Hout = ups ? Hin * 2 : (stride == 2 ? Hin / 2 : Hin), Wout = ups ? Win * 2 : (stride == 2 ? Win / 2 : Win);
-        IgemmParams p = base(B * Hout * Wout, N, 9 * (C0 + C1));
-        p.asym = asym;
-        p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = W; p.bias = bias;
-        p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.stride = stride; p.ups = ups;
-        p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = Hout * Wout; p.res_bf16 = res; p.out_bf16 = out;
-        // deterministic mode: the halo kernels need whole 256-pixel tiles, which at < 256 pixels per sample exist only for batches
-        // that are multiples of 256 / HW -- there the generic implicit GEMM (another summation order) runs for EVERY batch; and no
-        // split-K (its factor follows the tile count, i.e. the batch)
-        // Upsample's conv by output phase: four 2 x 2-tap convs at source resolution on pre-summed weights, 2.25 x fewer FLOPs than the
-        // nine taps at output resolution (igemm.hip CONV == 3)
-        if (ups && !A1 && C1 == 0 && C0 % 64 == 0 && N % 8 == 0 && !rowvec && !res && stride == 1) {
-            const bf16_t* wp = derived(W, N, C0, 5);
-            if (wp) {
-                IgemmParams q = base(B * Hin * Win, N, 4 * C0);
-                q.A0 = A0; q.C0 = C0; q.W = wp; q.bias = bias; q.out_bf16 = out; q.phase2 = 1;
-                q.Hin = Hin; q.Win = Win; q.Hout = Hout; q.Wout = Wout; q.stride = 1; q.rows_per_sample = Hin * Win;
-                q.sA = 0; q.sW = (long long)N * 4 * C0; q.sO = 0;
-                prof_begin(RDM_PROF_UPSCONV, 2.0 * 4.0 * q.M * N * (double)q.K, 4 * q.M, N, q.K);
-                check(launch_igemm(q, true, 4, c->stream), "conv3x3 on a 2x upsample, by phase");
-                prof_end();
-                return;
-            }
-        }
-        const bool det_generic = c->deterministic && ((Hout * Wout) % 256 != 0);
-        if (!det_generic && conv3x3_kernel(p) != CONV_IGEMM) p.Wfrag = derived(W, N, C0 + C1, 0);
-        // the K-split is chosen only with the fragment copy in hand: without one the conv runs on the implicit GEMM, which knows nothing of ksplit / ws
-        const int ks = (p.Wfrag && !c->deterministic) ? conv_halo_ksplit(p) : 1;
-        if (ks > 1 && ensure_bytes(c, &c->splitk_ws, &c->splitk_ws_bytes, (size_t)ks * p.M * N * 4) == 0) { p.ksplit = ks; p.ws = (float*)c->splitk_ws; }
-        prof_begin(RDM_PROF_CONV3X3, 2.0 * p.M * N * (double)p.K, p.M, N, p.K);
-        check(launch_conv3x3(p, c->stream), "conv3x3");      // no p.Wfrag (det_generic, no halo geometry, no memory for the copy): the implicit GEMM
-        prof_end();
-    }
-    // (Round 6, wave quantisation: a conv of q full rounds of the CUs plus a partial round -- the 16 x 16 level of a guided batch of 64 is 384
-    //  tiles on 256 CUs -- was run as full rounds + a K-split remainder in three forms: tail rows on a second stream, halves handed out inside
-    //  one launch, two launches on tile sub-ranges.  All parity-exact, all SLOWER (-1.0 .. -1.4 % on the headline), and the launch trace says
-    //  why: under the package power cap a half-empty round is nearly half price -- 256 tiles take 140 us, 384 tiles 213 us: the 128
-    //  remainder tiles cost 73 us on a chip that clocks up when half its CUs idle -- while 256 K halves + their fp32 planes and finisher cost
-    //  118 us.  The code is in the history (commits "conv tail split", "conv_halo4 TAIL variant", "conv remainder split"), the numbers in
-    //  profiles/r06_conv_tail_split_*.log, r06_conv_remainder_split_*.)
-    int cur_block = -1, cur_layer = 0;           // position in the UNet's block table (debug tap)
-    void tap(int stage, const void* ptr, size_t nbytes) {      // rdm_debug_tap: stage `stage` of layer cur_layer of block cur_block
-        if (plan || !c->tap_buf || c->tap_block != cur_block || c->tap_sub != cur_layer * 16 + stage) return;
-        if (nbytes > c->tap_bytes) nbytes = c->tap_bytes;
-        check(hipMemcpyAsync(c->tap_buf, ptr, nbytes, hipMemcpyDeviceToDevice, c->stream), "debug tap");
-    }
-    bool prof_open = false;
-    const char* tag = "";        // role of the ops that follow in the graph ("st.proj_in", "res.conv1", ...): rdm_prof_dump groups by it
-    void prof_begin(int kind, double work, int d0 = 0, int d1 = 0, int d2 = 0) {       // work: FLOPs (GEMM-class kinds) or bytes (bandwidth-class kinds)
-        prof_open = (c->prof >> kind) & 1u;
-        if (!prof_open) return;
-        rdm_ctx::ProfRec r; r.a = c->prof_event(); r.b = c->prof_event(); r.kind = kind; r.flops = work; r.tag = tag; r.d0 = d0; r.d1 = d1; r.d2 = d2;
-        hipEventRecord(r.a, c->stream); c->prof_recs.push_back(r);
-    }
-    void prof_end() { if (prof_open) hipEventRecord(c->prof_recs.back().b, c->stream); prof_open = false; }
-    // (gn_partial must hold B samples' statistics: ensure_gn_partial)
-    void groupnorm(const bf16_t* x0, const bf16_t* x1, int C0, int C1, int B, int HW, const float* g, const float* b, float eps, int silu,
-                   bf16_t* out, int L0 = -1, int L1 = -1, int x1_bmod = 0, int x0_bmod = 0) {      // L0 / L1: logical channels of the (zero-padded) sources, default = all
-        if (plan) return;
-        GnParams p{}; p.x0 = x0; p.x1 = x1; p.C0 = C0; p.C1 = C1; p.HW = HW; p.B = B; p.groups = 32; p.x1_bmod = x1_bmod; p.x0_bmod = x0_bmod;
-        p.L0 = L0 < 0 ? C0 : L0; p.L1 = L1 < 0 ? C1 : L1;
-        p.nchunk = gn_chunks(HW); p.partial = c->gn_partial; p.gamma = g; p.beta = b; p.eps = eps; p.silu = silu;
-        p.out = out;
-        prof_begin(RDM_PROF_GROUPNORM, (double)B * HW * (C0 + C1) * 4.0, B * HW, C0 + C1, silu);       // ALGORITHMIC bytes: one read + one write of the bf16 tensor (round 5: the one-pass kernel moves exactly these; the two-pass form of the 64 x 64 level reads twice)
-        check(launch_groupnorm(p, c->stream), "groupnorm");
-        prof_end();
-    }
-    // GroupNorm + SiLU + 3x3 conv to a few channels (UNet `out`, VQ decoder conv_out): one statistics pass + the fused MFMA head kernel
-    // (misc.hip), or GroupNorm-apply into `tmp` + the VALU head conv where the fused kernel does not apply.  g == null: no GroupNorm
-    // (the fused kernel only)
-    HeadParams head_params(const bf16_t* x, int B, int H, int W, int C, const float* g, const float* b, float eps, const float* wt, const float* bias,
-                           int Cout, float* out, bf16_t* wp) const {
-        HeadParams hp{}; hp.x = x; hp.B = B; hp.H = H; hp.W = W; hp.C = C; hp.groups = 32; hp.gamma = g; hp.beta = b; hp.eps = eps;
-        hp.w = wt; hp.wp = wp; hp.bias = bias; hp.out = out; hp.Cout = Cout;
-        if (g) { hp.partial = c->gn_partial; hp.nchunk = gn_chunks(H * W); }
-        return hp;
-    }
-    void head(const bf16_t* x, int B, int H, int W, int C, int Clog, const float* g, const float* b, float eps, const float* wt, const float* bias, int Cout,
-              float* out, bf16_t* tmp, bf16_t* wp) {
-        if (plan) return;
-        const HeadParams hp = head_params(x, B, H, W, C, g, b, eps, wt, bias, Cout, out, wp);
-        if (Clog == C && head_conv_supported(hp)) {
-            if (g) {
-                GnParams p{}; p.x0 = x; p.C0 = C; p.HW = H * W; p.B = B; p.groups = 32; p.L0 = C; p.nchunk = hp.nchunk; p.partial = c->gn_partial;
-                prof_begin(RDM_PROF_GROUPNORM, (double)B * H * W * C * 2.0, B * H * W, C, 2);
-                check(launch_gn_stats(p, c->stream), "head groupnorm statistics");
-                prof_end();
-            }
-            check(launch_head_conv(hp, c->stream), "head conv");
-            return;
-        }
-        groupnorm(x, nullptr, C, 0, B, H * W, g, b, eps, 1, tmp, Clog, 0);
-        check(launch_conv_out(tmp, wt, bias, out, B, H, W, C, Cout, c->stream), "conv_out");
-    }
-    // nearest codebook row of every token (vqcode.hip): z f32 [M, E], cb f32 [N, E], norms = |e_j|^2 (launch_vq_code_norms), ws of
-    // vq_nearest_ws_bytes(M, N); first minimum on ties, indices as int32 and / or int64
-    void vq_nearest(const float* z, const float* cb, const float* norms, long long M, int N, int E, char* ws, int* idx32, long long* idx64) {
-        if (plan) return;
-        check(launch_vq_nearest(z, cb, norms, M, N, E, ws, idx32, idx64, c->stream), "vq nearest code");
-    }
-    void layernorm(const void* x, int in_f32, const float* g, const float* b, void* out, int out_f32, int M, int C, int Clog = -1, float eps = 1e-5f) {
-        if (plan) return;
-        prof_begin(RDM_PROF_LAYERNORM, (double)M * C * ((in_f32 ? 4.0 : 2.0) + (out_f32 ? 4.0 : 2.0)), M, C, 0);
-        check(launch_layernorm(x, in_f32, g, b, out, out_f32, M, C, eps, c->stream, Clog < 0 ? C : Clog), "layernorm");
-        prof_end();
-    }
-    // d = 32 flash attention over n tokens (attention.hip): q / k (= q + C) token-major at row stride ldq; V either token-major at the
-    // same stride (v: the fused q | k | v projection, n % 64 == 0) or V^T per sample [B][C][n] (vt)
-    void flash_d32(const bf16_t* q, int ldq, const bf16_t* v, const bf16_t* vt, bf16_t* out, int B, int n, int heads) {
-        if (plan) return;
-        const int C = heads * 32;
-        FlashParams f{}; f.q = q; f.ldq = ldq; f.k = q + C; f.ldk = ldq; f.v = v; f.ldv = v ? ldq : 0; f.vt = vt; f.out = out; f.ldo = C;
-        f.n = n; f.C = C; f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
-        prof_begin(RDM_PROF_ATTENTION, 4.0 * B * heads * (double)n * n * 32, B, n, C);
-        check(launch_flash_d32(f, heads, B, c->stream), "flash attention");
-        prof_end();
-    }
-    // causal self-attention at d_head 64 over all n positions of B sequences (attention.hip): qkv = the fused q | k | v projection rows;
-    // kc / vc: optional head-major decode caches [B][heads][L][64] that receive rows 0 .. n-1
-    void causal_d64(const bf16_t* qkv, int ldq, bf16_t* out, int ldo, int B, int n, int heads, float scale, bf16_t* kc, bf16_t* vc, int L) {
-        if (plan) return;
-        CausalD64Params f{}; f.qkv = qkv; f.ldq = ldq; f.out = out; f.ldo = ldo; f.n = n; f.C = heads * 64;
-        f.scale_log2e = scale * 1.4426950408889634f; f.kcache = kc; f.vcache = vc; f.L = L;
-        prof_begin(RDM_PROF_ATTENTION, 2.0 * B * heads * (double)n * n * 64, B, n, f.C);
-        check(launch_causal_d64(f, heads, B, c->stream), "causal attention");
-        prof_end();
-    }
-    // the first stage's AttnBlock without its n x n scores (vq_attn.hip): one head of C channels over n tokens, any n
-    void vq_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, const float* bias_v, bf16_t* out, int ldo, int B, int n, int C,
-                      float scale) {
-        if (plan) return;
-        VqAttnParams f{}; f.q = q; f.ldq = ldq; f.k = k; f.ldk = ldk; f.v = v; f.ldv = ldv; f.bias = bias_v; f.out = out; f.ldo = ldo; f.n = n; f.C = C; f.scale = scale;
-        prof_begin(RDM_PROF_ATTENTION, 6.0 * B * (double)n * n * C, B, n, C);      // the scores twice (vq_attn.hip) and P.V
-        check(launch_vq_attn_stream(f, B, c->stream), "vq attention");
-        prof_end();
-    }
-    // attention over a few keys / short sequences (attention.hip): head dim D, nq queries and nkv keys per sample
-    void small_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, bf16_t* out, int ldo, int B, int nq, int nkv,
-                         int heads, int D, int causal, float scale, const char* what) {
-        if (plan) return;
-        SmallAttnParams p{}; p.q = q; p.ldq = ldq; p.k = k; p.ldk = ldk; p.v = v; p.ldv = ldv; p.out = out;
-        p.ldo = ldo; p.nq = nq; p.nkv = nkv; p.causal = causal; p.scale = scale;
-        check(launch_small_attention(p, D, heads, B, c->stream), what);
-    }
-    // cross-attention over k neighbours in one launch (attention.hip): scores against G, softmax, P U, bias and residual; G / U are the
-    // fragment-ordered images of launch_xattn_pack.  ln_g given: x holds the raw rows, the scores are taken on LayerNorm(x) and the residual
-    // is x itself (res null); ln3_out given: LayerNorm(out rows; ln3_g, ln3_b) leaves with the finished rows
-    static XattnParams xattn_params(int rows, int n, int C, int NP, int ncols, int group) {
-        XattnParams q{}; q.rows = rows; q.n = n; q.C = C; q.NP = NP; q.ncols = ncols; q.group = group; return q;
-    }
-    void xattn_fused(const bf16_t* x, const float* ln_g, const float* ln_b, float ln_eps, const bf16_t* G, const bf16_t* U, const float* bias,
-                     const bf16_t* res, bf16_t* out, int rows, int n, int C, int NP, int ncols, int group,
-                     const float* ln3_g = nullptr, const float* ln3_b = nullptr, bf16_t* ln3_out = nullptr) {
-        if (plan) return;
-        XattnParams q = xattn_params(rows, n, C, NP, ncols, group);
-        q.x = x; q.G = G; q.U = U; q.bias = bias; q.res = res; q.out = out; q.ln_g = ln_g; q.ln_b = ln_b; q.ln_eps = ln_eps;
-        q.ln3_g = ln3_g; q.ln3_b = ln3_b; q.ln3_out = ln3_out;
-        prof_begin(RDM_PROF_LINEAR, 4.0 * rows * NP * (double)C, rows, NP, C);
-        check(launch_xattn_fused(q, c->stream), "fused cross attention");
-        prof_end();
-    }
-};
-
-static int ensure_gn_partial(rdm_ctx* c, int B) {
-    const size_t need = (size_t)B * 32 * 64 * 2 * sizeof(float);
-    return ensure_bytes(c, (char**)&c->gn_partial, &c->gn_partial_bytes, need);
-}
 
 // ------------------------------------------------------------------------------------ UNet forward
 // kv: bf16 [B*k, kv_total] cross-attention keys/values for every SpatialTransformer (rdm_unet_forward: per call; the samplers: prepare_kv)
@@ -1174,88 +340,41 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
     o.head(h.p, B, H, W, mc, mcl, o.w<float>(u.outg), o.w<float>(u.outb), 1e-5f, o.w<float>(u.outw), o.w<float>(u.outbias), c.out_channels, eps_out, no, hwp);
 }
 
-// plan (count bytes) -> ensure arena -> run
-template <typename F>
-static int run_with_arena(rdm_ctx* c, Arena& ar, const char* blob, F&& body) {
-    Ops plan{c, &ar, blob, true};
-    char* keep = ar.base; ar.base = nullptr; ar.reset(); ar.peak = 0;
-    body(plan);
-    const size_t need = ar.peak + 4096;
-    ar.base = keep;
-    RDM_TRY(ensure_bytes(c, &ar.base, &ar.cap, need));
-    ar.reset();
-    Ops run{c, &ar, blob, false};
-    body(run);
-    return run.rc;
+static int unet_forward_impl(rdm_ctx* c, const float* x, const int64_t* t, const float* context, const bf16_t* kv_cached,
+                             int b, int k, int H, int W, float* eps_out, int ctx_rows = -1, int shared_half = 0, const float* emb_row = nullptr) {
+    UNet& u = c->unet;
+    if (!u.loaded) return c->fail(-1, "unet weights not loaded");
+    const int down = 1 << (u.cfg.n_channel_mult - 1);
+    if (b < 1 || k < 1 || H % down || W % down) return c->fail(-1, "bad unet_forward shape b=%d k=%d H=%d W=%d", b, k, H, W);
+    if (k > 256) return c->fail(-1, "k=%d neighbours exceeds the cross-attention kernel limit (256)", k);
+    RDM_TRY(ensure_gn_partial(c, b));
+    return run_with_arena(c, u.arena, u.blob, [&](Ops& o) {
+        const bf16_t* kv = kv_cached;
+        const bf16_t* xa = (kv_cached && xattn_skinny_ok(u, k)) ? u.xa_cache : nullptr;
+        if (!kv) {
+            bf16_t* kvb = o.abf((size_t)b * k * u.kv_total);
+            unet_compute_kv(o, u, context, b, k, kvb);
+            kv = kvb;
+            if (xattn_skinny_ok(u, k)) {
+                bf16_t* xab = o.abf((size_t)b * u.xa_total);
+                unet_compute_xattn(o, u, kv, b, k, xab);
+                xa = xab;
+            }
+        }
+        unet_body(o, u, x, (const long long*)t, kv, xa, b, k, H, W, eps_out, (ctx_rows >= 0 && ctx_rows <= b) ? ctx_rows : b, shared_half, emb_row);
+    });
 }
 
-// One cfg check per model, called by its manifest entry (c null, load false) and by its load entry.  First what the builder walks --
-// array extents, divisors: refused by both entries --, then, for `load`, what the executors and kernels take.
-static int cfg_refuse(rdm_ctx* c, const char* msg) { return c ? c->fail(-1, "%s", msg) : -1; }
-static int cfg_check_unet(rdm_ctx* c, const rdm_unet_cfg* g, bool /*load*/) {
-    if (!g || g->n_channel_mult < 1 || g->n_channel_mult > RDM_MAX_LEVELS || g->n_attention_resolutions > RDM_MAX_LEVELS) return cfg_refuse(c, "bad unet cfg");
-    if (g->model_channels % 32 || g->num_head_channels != 32 || g->context_dim % 64 || g->in_channels > 4 || g->out_channels > 4)
-        return cfg_refuse(c, "unsupported unet cfg: model_channels % 32 == 0 (GroupNorm32; widths that are not multiples of 64 run zero-padded), num_head_channels == 32, context_dim % 64 == 0 required");
-    return 0;
-}
-// first stage, decoder and encoder.  `exec`: also what the executors take (the decoder's manifest entry describes any cfg that can be walked)
-static int cfg_check_first_stage(rdm_ctx* c, const rdm_vq_cfg* g, bool encoder, bool exec) {
-    bool ok = g && g->n_ch_mult >= 1 && g->n_ch_mult <= RDM_MAX_LEVELS && g->n_attn_resolutions >= 0 && g->n_attn_resolutions <= RDM_MAX_LEVELS;
-    if (ok && exec) {
-        const bool narrow = g->embed_dim == 3 && g->z_channels == 3;      // VQ-f4; the decoder also as KL-f4
-        const bool wide = g->embed_dim > 0 && g->z_channels > 0 && g->embed_dim % 64 == 0 && g->z_channels % 64 == 0 && !g->kl;      // VQGAN-f16
-        ok = g->ch % 64 == 0 && g->out_ch <= 4 && (narrow || wide);
-        if (encoder) ok = ok && !g->kl && g->resolution % (1 << (g->n_ch_mult - 1)) == 0;      // the VQ interface only; every Downsample halves exactly
-    }
-    if (ok) return 0;
-    return cfg_refuse(c, encoder ? "unsupported first-stage encoder cfg: n_ch_mult in [1, RDM_MAX_LEVELS], n_attn_resolutions in [0, RDM_MAX_LEVELS], VQ interface (kl = 0), resolution a multiple of 2^(levels - 1), "
-                                   "ch % 64 == 0, out_ch <= 4 and either embed_dim == z_channels == 3 (VQ-f4) or both multiples of 64 (VQGAN-f16)"
-                                 : "unsupported vq cfg: n_ch_mult in [1, RDM_MAX_LEVELS], n_attn_resolutions in [0, RDM_MAX_LEVELS], ch % 64 == 0, out_ch <= 4 and either embed_dim == z_channels == 3 "
-                                   "(VQ-f4 / KL-f4) or both multiples of 64 (VQGAN-f16, kl = 0)");
-}
-static int cfg_check_vq(rdm_ctx* c, const rdm_vq_cfg* g, bool load) { return cfg_check_first_stage(c, g, false, load); }
-static int cfg_check_vqenc(rdm_ctx* c, const rdm_vq_cfg* g, bool /*load*/) { return cfg_check_first_stage(c, g, true, true); }
-static int cfg_check_clip(rdm_ctx* c, const rdm_clip_cfg* g, bool load) {
-    if (!g || g->vision_patch_size < 1) return cfg_refuse(c, "bad clip cfg: vision_patch_size >= 1 required");
-    if (load && (g->transformer_width % 64 || g->vision_width % 64 || g->embed_dim % 8 || g->transformer_heads < 1 || g->transformer_width / g->transformer_heads != 64))
-        return cfg_refuse(c, "unsupported clip cfg: widths % 64 == 0 and 64-d heads required");
-    return 0;
-}
-static int cfg_check_rarm(rdm_ctx* c, const rdm_rarm_cfg* g, bool load) {
-    if (!g || g->depth < 1 || g->n_heads < 1) return cfg_refuse(c, "bad rarm cfg: depth >= 1 and n_heads >= 1 required");
-    if (load && (g->d_head != 64 || g->context_dim % 64 || g->sequence_length > 1024 || g->vocab_out % 2))
-        return cfg_refuse(c, "unsupported rarm cfg: d_head == 64, context_dim % 64 == 0, sequence_length <= 1024, even vocab_out required");
-    return 0;
+int rdm_unet_forward(rdm_ctx* c, const float* x, const int64_t* t, const float* context, int b, int k, int H, int W,
+                     float* eps_out) {
+    RDM_ENTER(c);
+    if (!c || !x || !t || !context || !eps_out) return c ? c->fail(-1, "null argument") : -1;
+    return unet_forward_impl(c, x, t, context, nullptr, b, k, H, W, eps_out);
 }
 
-// rdm_*_manifest: the description is built into a model of its own, nothing is allocated
-template <typename M, typename Cfg>
-static long long model_manifest(int (*check)(rdm_ctx*, const Cfg*, bool), void (*build)(M&, const Cfg&, Manifest&), const Cfg* cfg,
-                                char* buf, size_t buflen, size_t* blob_bytes) {
-    if (check(nullptr, cfg, false)) return -1;
-    M m{}; Manifest mf; build(m, *cfg, mf);
-    if (blob_bytes) *blob_bytes = (mf.total + 255) & ~(size_t)255;
-    if (buf && buflen > mf.text.size()) { memcpy(buf, mf.text.c_str(), mf.text.size() + 1); }
-    return (long long)mf.text.size();
-}
-
-// rdm_load_*: everything that can refuse the load comes before the first change to `live` -- a refused load leaves the model that was
-// loaded before fully usable
-template <typename M, typename Cfg>
-static int load_model(rdm_ctx* c, M& live, int (*check)(rdm_ctx*, const Cfg*, bool), void (*build)(M&, const Cfg&, Manifest&), const Cfg* cfg,
-                      const void* packed, size_t nbytes) {
-    RDM_TRY(check(c, cfg, true));
-    if (!packed) return c->fail(-1, "null blob");
-    M next{}; Manifest mf; build(next, *cfg, mf);
-    const size_t need = (mf.total + 255) & ~(size_t)255;
-    if (nbytes != need) return c->fail(-1, "packed blob is %zu bytes, manifest needs %zu", nbytes, need);
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    c->drop_frags();                                  // derived weight layouts refer to blob addresses that may be reused
-    live.release();                                   // the old weights, and the arena and everything else made for or from them
-    live = next;                                      // (a description only: owns no device memory)
-    RDM_CHECK_HIP(c, hipMalloc((void**)&live.blob, need));
-    RDM_CHECK_HIP(c, hipMemcpy(live.blob, packed, need, hipMemcpyHostToDevice));
-    live.blob_bytes = need; live.loaded = true;
+int rdm_debug_tap(rdm_ctx* c, void* buf, size_t nbytes, int block, int sub) {
+    if (!c) return -1;
+    c->tap_buf = buf; c->tap_bytes = buf ? nbytes : 0; c->tap_block = buf ? block : -1; c->tap_sub = buf ? sub : 0;
     return 0;
 }
 
@@ -1557,79 +676,6 @@ static void clip_image_body(Ops& o, ClipModel& m, const float* img, int B, float
     o.single_row = false;
 }
 
-// ==================================================================================== C ABI
-extern "C" {
-
-const char* rdm_version(void) { return "rdm_hip 0.1 (gfx950)"; }
-
-int rdm_ctx_create(int device_id, rdm_ctx** out) {
-    if (!out) return -1;
-    *out = nullptr;
-    int n = 0;
-    if (hipGetDeviceCount(&n) != hipSuccess || n <= 0) return -4;      // no HIP device: fail loudly, there is no CPU path
-    if (device_id < 0 || device_id >= n) return -1;
-    DevGuard guard(device_id);
-    rdm_ctx* c = new rdm_ctx();
-    c->device = device_id;
-    {   // zero page + identity matrix (the residual-as-K-columns operand of the linear GEMMs, igemm.hip)
-        const size_t bytes = RDM_EYE_OFFSET + (size_t)RDM_EYE_N * RDM_EYE_N * 2;
-        std::vector<uint16_t> host(bytes / 2, 0);
-        for (int i = 0; i < RDM_EYE_N; i++) host[RDM_EYE_OFFSET / 2 + (size_t)i * RDM_EYE_N + i] = 0x3F80;   // bf16 1.0
-        if (hipMalloc(&c->zero_page, bytes) != hipSuccess || hipMemcpy(c->zero_page, host.data(), bytes, hipMemcpyHostToDevice) != hipSuccess) { delete c; return -2; }
-    }
-    *out = c;
-    return 0;
-}
-
-void rdm_ctx_destroy(rdm_ctx* c) {
-    if (!c) return;
-    if (c->comm) rdm_comm_destroy(c);
-    DevGuard guard(c->device);
-    hipDeviceSynchronize();
-    c->unet.release(); c->vq.release(); c->vqenc.release(); c->clip.release(); c->rarm.release();
-    void* ptrs[] = {c->zero_page, c->eye3, c->gn_partial, c->samp, c->splitk_ws, c->wfrag_tmp, c->bwd_tmp};      // the context's own buffers
-    for (void* p : ptrs) if (p) hipFree(p);
-    c->drop_frags();
-    knn_free(c->db);
-    delete c;
-}
-
-const char* rdm_last_error(rdm_ctx* c) { return c ? c->err : "null context"; }
-
-// The grow-only work buffers (backward scratch: K-major operand copies + up to 256 MB of fp32 weight-gradient planes per conv -- over
-// 1 GB for the 576 -> 192 block at 64 x 64 and batch 64 --, split-K planes, per-call weight re-packs, sampler scratch) are kept between
-// calls so that steady-state steps allocate nothing; a caller switching from training back to sampling hands them back here.  They
-// are re-created on demand.
-int rdm_release_scratch(rdm_ctx* c) {
-    RDM_ENTER(c);
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    char** bufs[] = {&c->bwd_tmp, &c->wfrag_tmp, &c->splitk_ws, &c->samp};
-    size_t* sizes[] = {&c->bwd_tmp_bytes, &c->wfrag_tmp_bytes, &c->splitk_ws_bytes, &c->samp_bytes};
-    for (int i = 0; i < 4; i++) { if (*bufs[i]) { (void)hipFree(*bufs[i]); *bufs[i] = nullptr; } *sizes[i] = 0; }
-    return 0;
-}
-int rdm_set_deterministic(rdm_ctx* c, int on) { if (!c) return -1; c->deterministic = on != 0; return 0; }
-int rdm_get_deterministic(rdm_ctx* c) { return c ? (c->deterministic ? 1 : 0) : -1; }
-int rdm_set_stream(rdm_ctx* c, void* s) {
-    RDM_ENTER(c);
-    if ((hipStream_t)s != c->stream) {      // work queued (and derived weight copies packed) on the old stream completes before the new one is used
-        RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-        c->stream = (hipStream_t)s;
-    }
-    return 0;
-}
-
-long long rdm_unet_manifest(const rdm_unet_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_unet, build_unet, cfg, buf, buflen, blob_bytes); }
-long long rdm_vq_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_vq, build_vq, cfg, buf, buflen, blob_bytes); }
-long long rdm_vqenc_manifest(const rdm_vq_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_vqenc, build_vqenc, cfg, buf, buflen, blob_bytes); }
-long long rdm_clip_manifest(const rdm_clip_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_clip, build_clip, cfg, buf, buflen, blob_bytes); }
-long long rdm_rarm_manifest(const rdm_rarm_cfg* cfg, char* buf, size_t buflen, size_t* blob_bytes) { return model_manifest(cfg_check_rarm, build_rarm, cfg, buf, buflen, blob_bytes); }
-
-int rdm_load_unet(rdm_ctx* c, const rdm_unet_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->unet, cfg_check_unet, build_unet, cfg, packed, nbytes); }
-int rdm_load_vq(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->vq, cfg_check_vq, build_vq, cfg, packed, nbytes); }
-int rdm_load_vqenc(rdm_ctx* c, const rdm_vq_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->vqenc, cfg_check_vqenc, build_vqenc, cfg, packed, nbytes); }
-int rdm_load_clip(rdm_ctx* c, const rdm_clip_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->clip, cfg_check_clip, build_clip, cfg, packed, nbytes); }
-int rdm_load_rarm(rdm_ctx* c, const rdm_rarm_cfg* cfg, const void* packed, size_t nbytes) { RDM_ENTER(c); return load_model(c, c->rarm, cfg_check_rarm, build_rarm, cfg, packed, nbytes); }
 // img [b, out_ch, H, W] -> z_out [b, embed_dim, H / f, W / f]; `what`: the entry's name in messages
 static int vq_encode_impl(rdm_ctx* c, const char* what, const float* img, int b, int H, int W, float* z_out) {
     if (!img || !z_out || b < 1) return c->fail(-1, "%s: bad argument", what);
@@ -1683,36 +729,94 @@ int rdm_vq_encode_indices(rdm_ctx* c, const float* img, int b, int64_t* indices_
     });
 }
 
-static int unet_forward_impl(rdm_ctx* c, const float* x, const int64_t* t, const float* context, const bf16_t* kv_cached,
-                             int b, int k, int H, int W, float* eps_out, int ctx_rows = -1, int shared_half = 0, const float* emb_row = nullptr) {
-    UNet& u = c->unet;
-    if (!u.loaded) return c->fail(-1, "unet weights not loaded");
-    const int down = 1 << (u.cfg.n_channel_mult - 1);
-    if (b < 1 || k < 1 || H % down || W % down) return c->fail(-1, "bad unet_forward shape b=%d k=%d H=%d W=%d", b, k, H, W);
-    if (k > 256) return c->fail(-1, "k=%d neighbours exceeds the cross-attention kernel limit (256)", k);
-    RDM_TRY(ensure_gn_partial(c, b));
-    return run_with_arena(c, u.arena, u.blob, [&](Ops& o) {
-        const bf16_t* kv = kv_cached;
-        const bf16_t* xa = (kv_cached && xattn_skinny_ok(u, k)) ? u.xa_cache : nullptr;
-        if (!kv) {
-            bf16_t* kvb = o.abf((size_t)b * k * u.kv_total);
-            unet_compute_kv(o, u, context, b, k, kvb);
-            kv = kvb;
-            if (xattn_skinny_ok(u, k)) {
-                bf16_t* xab = o.abf((size_t)b * u.xa_total);
-                unet_compute_xattn(o, u, kv, b, k, xab);
-                xa = xab;
-            }
-        }
-        unet_body(o, u, x, (const long long*)t, kv, xa, b, k, H, W, eps_out, (ctx_rows >= 0 && ctx_rows <= b) ? ctx_rows : b, shared_half, emb_row);
+// z [b, z_channels, h, w] -> img_out [b, out_ch, f h, f w], indices_out [b, h w] or null
+static int vq_decode_impl(rdm_ctx* c, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out) {
+    if (!z || !img_out) return c->fail(-1, "null argument");
+    if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
+    if (c->vq.wide) return c->fail(-1, "this first stage has a wide latent (VQGAN-f16): decode from code indices with rdm_vq_decode_indices");
+    if (b < 1 || h < 1 || w < 1) return c->fail(-1, "vq decode: bad shape b=%d h=%d w=%d", b, h, w);
+    const rdm_vq_cfg& q = c->vq.cfg;
+    const int f = 1 << (q.n_ch_mult - 1);
+    const size_t zper = (size_t)q.z_channels * h * w, iper = (size_t)q.out_ch * (f * h) * ((size_t)f * w);
+    return vq_walk(c, c->vq, b, h, w, true, [&](Ops& o, int b0, int n) {
+        vq_body(o, c->vq, z + b0 * zper, n, h, w, force_not_quantize, img_out + b0 * iper, indices_out ? indices_out + (size_t)b0 * h * w : nullptr);
+    });
+}
+int rdm_vq_decode(rdm_ctx* c, const float* z, int b, int force_not_quantize, float* img_out, int32_t* indices_out) {
+    RDM_ENTER(c);
+    const int zr = c->vq.loaded ? c->vq.cfg.resolution >> (c->vq.cfg.n_ch_mult - 1) : 1;      // (not loaded: refused before zr is used)
+    return vq_decode_impl(c, z, b, zr, zr, force_not_quantize, img_out, indices_out);
+}
+int rdm_vq_decode_hw(rdm_ctx* c, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out) {
+    RDM_ENTER(c);
+    return vq_decode_impl(c, z, b, h, w, force_not_quantize, img_out, indices_out);
+}
+static int vq_quantize_impl(rdm_ctx* c, const char* what, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out) {
+    if (!z || !zq_out || b < 1 || h < 1 || w < 1 || (long long)h * w > 0x7fffffffLL / b) return c->fail(-1, "%s: bad argument", what);
+    VqModel& v = c->vq;
+    if (!v.loaded) return c->fail(-1, "vq weights not loaded");
+    if (v.wide || v.cfg.kl || v.cfg.embed_dim != 3) return c->fail(-1, "%s: needs a VQ first stage with a 3-channel latent (VQ-f4)", what);
+    if (!c->eye3) {       // the quantiser kernel ends in a 3 x 3 map (post_quant_conv in decode): identity + zero bias here
+        const float e[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
+        RDM_CHECK_HIP(c, hipMalloc((void**)&c->eye3, sizeof e));
+        RDM_CHECK_HIP(c, hipMemcpy(c->eye3, e, sizeof e, hipMemcpyHostToDevice));
+    }
+    RDM_CHECK_HIP(c, launch_vq_quantize(z, (const float*)(v.blob + v.codebook), v.cfg.n_embed, c->eye3, c->eye3 + 9, zq_out, indices_out, b, h * w, 1, c->stream));
+    return 0;
+}
+int rdm_vq_quantize(rdm_ctx* c, const float* z, int b, float* zq_out, int32_t* indices_out) {
+    RDM_ENTER(c);
+    const int zr = c->vq.loaded ? c->vq.cfg.resolution >> (c->vq.cfg.n_ch_mult - 1) : 1;
+    return vq_quantize_impl(c, "rdm_vq_quantize", z, b, zr, zr, zq_out, indices_out);
+}
+int rdm_vq_quantize_hw(rdm_ctx* c, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out) {
+    RDM_ENTER(c);
+    return vq_quantize_impl(c, "rdm_vq_quantize_hw", z, b, h, w, zq_out, indices_out);
+}
+int rdm_vq_decode_indices(rdm_ctx* c, const int64_t* indices, int b, float* img_out) {
+    RDM_ENTER(c);
+    if (!indices || !img_out || b < 1) return c->fail(-1, "bad argument");
+    if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
+    if (!c->vq.wide || c->vq.cfg.kl) return c->fail(-1, "rdm_vq_decode_indices needs a VQGAN first stage with a wide latent (z_channels %% 64 == 0)");
+    const rdm_vq_cfg& q = c->vq.cfg;
+    const int zr = q.resolution >> (q.n_ch_mult - 1);
+    return vq_walk(c, c->vq, b, zr, zr, true, [&](Ops& o, int b0, int n) {
+        vq_wide_body(o, c->vq, (const long long*)indices + (size_t)b0 * zr * zr, n, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution);
     });
 }
 
-int rdm_unet_forward(rdm_ctx* c, const float* x, const int64_t* t, const float* context, int b, int k, int H, int W,
-                     float* eps_out) {
+int rdm_to_uint8(rdm_ctx* c, const float* img, int b, int ch, int h, int w, uint8_t* out) {
     RDM_ENTER(c);
-    if (!c || !x || !t || !context || !eps_out) return c ? c->fail(-1, "null argument") : -1;
-    return unet_forward_impl(c, x, t, context, nullptr, b, k, H, W, eps_out);
+    if (!c || !img || !out) return -1;
+    RDM_CHECK_HIP(c, launch_to_uint8_hwc(img, out, b, ch, h, w, c->stream));
+    return 0;
+}
+
+int rdm_clip_encode_text(rdm_ctx* c, const int64_t* tokens, int b, float* out) {
+    RDM_ENTER(c);
+    if (!c || !tokens || !out) return c ? c->fail(-1, "null argument") : -1;
+    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
+    return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_text_body(o, c->clip, (const long long*)tokens, b, out); });
+}
+int rdm_clip_encode_image(rdm_ctx* c, const float* image, int b, float* out) {
+    RDM_ENTER(c);
+    if (!c || !image || !out) return c ? c->fail(-1, "null argument") : -1;
+    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
+    return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_image_body(o, c->clip, image, b, out); });
+}
+
+int rdm_clip_preprocess(rdm_ctx* c, const float* image, int b, int h, int w, float* out) {
+    RDM_ENTER(c);
+    if (!image || !out || b < 1 || h < 1 || w < 1) return c->fail(-1, "bad argument");
+    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded (the target resolution comes from the clip cfg)");
+    RDM_CHECK_HIP(c, launch_clip_preprocess(image, b, h, w, c->clip.cfg.image_resolution, c->clip.cfg.vision_patch_size, out, nullptr, c->stream));
+    return 0;
+}
+int rdm_clip_encode_image_raw(rdm_ctx* c, const float* image, int b, int h, int w, float* out) {
+    RDM_ENTER(c);
+    if (!image || !out || b < 1 || h < 1 || w < 1) return c->fail(-1, "bad argument");
+    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
+    return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_image_body(o, c->clip, image, b, out, h, w); });
 }
 
 // ---- samplers
@@ -1815,7 +919,7 @@ static int check_noise_rows(rdm_ctx* c, const char* who, int64_t row0, int64_t B
     return 0;
 }
 
-extern "C++" struct SamplerRun {
+struct SamplerRun {
     rdm_ctx* c; int B, nb, k, H, W, total; long long n1;           // n1: elements of x for B rows; total: ts.size()
     float *x, *x_dup, *eps, *extra[4]; long long* tdev; const float* emb_table;
     int log_every_t = 0, n_logged = 0; float *x_inter = nullptr, *pred_x0_inter = nullptr;     // intermediates (DDPM keeps none)
@@ -2316,95 +1420,33 @@ int rdm_op_randn(rdm_ctx* c, uint64_t seed, int64_t row0, int64_t B, int64_t per
     return op_rng_fill(c, "rdm_op_randn", seed, row0, B, per_row, step, stream, out, true);
 }
 
-
-// z [b, z_channels, h, w] -> img_out [b, out_ch, f h, f w], indices_out [b, h w] or null
-static int vq_decode_impl(rdm_ctx* c, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out) {
-    if (!z || !img_out) return c->fail(-1, "null argument");
-    if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
-    if (c->vq.wide) return c->fail(-1, "this first stage has a wide latent (VQGAN-f16): decode from code indices with rdm_vq_decode_indices");
-    if (b < 1 || h < 1 || w < 1) return c->fail(-1, "vq decode: bad shape b=%d h=%d w=%d", b, h, w);
-    const rdm_vq_cfg& q = c->vq.cfg;
-    const int f = 1 << (q.n_ch_mult - 1);
-    const size_t zper = (size_t)q.z_channels * h * w, iper = (size_t)q.out_ch * (f * h) * ((size_t)f * w);
-    return vq_walk(c, c->vq, b, h, w, true, [&](Ops& o, int b0, int n) {
-        vq_body(o, c->vq, z + b0 * zper, n, h, w, force_not_quantize, img_out + b0 * iper, indices_out ? indices_out + (size_t)b0 * h * w : nullptr);
-    });
-}
-int rdm_vq_decode(rdm_ctx* c, const float* z, int b, int force_not_quantize, float* img_out, int32_t* indices_out) {
+// ---- the DPM-Solver++ and UniPC step kernels alone
+int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int cfg, float scale, float sqrt_a_s,
+                      float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup, float* m_store, float* pred_x0) {
     RDM_ENTER(c);
-    const int zr = c->vq.loaded ? c->vq.cfg.resolution >> (c->vq.cfg.n_ch_mult - 1) : 1;      // (not loaded: refused before zr is used)
-    return vq_decode_impl(c, z, b, zr, zr, force_not_quantize, img_out, indices_out);
-}
-int rdm_vq_decode_hw(rdm_ctx* c, const float* z, int b, int h, int w, int force_not_quantize, float* img_out, int32_t* indices_out) {
-    RDM_ENTER(c);
-    return vq_decode_impl(c, z, b, h, w, force_not_quantize, img_out, indices_out);
-}
-static int vq_quantize_impl(rdm_ctx* c, const char* what, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out) {
-    if (!z || !zq_out || b < 1 || h < 1 || w < 1 || (long long)h * w > 0x7fffffffLL / b) return c->fail(-1, "%s: bad argument", what);
-    VqModel& v = c->vq;
-    if (!v.loaded) return c->fail(-1, "vq weights not loaded");
-    if (v.wide || v.cfg.kl || v.cfg.embed_dim != 3) return c->fail(-1, "%s: needs a VQ first stage with a 3-channel latent (VQ-f4)", what);
-    if (!c->eye3) {       // the quantiser kernel ends in a 3 x 3 map (post_quant_conv in decode): identity + zero bias here
-        const float e[12] = {1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f, 1.f, 0.f, 0.f, 0.f};
-        RDM_CHECK_HIP(c, hipMalloc((void**)&c->eye3, sizeof e));
-        RDM_CHECK_HIP(c, hipMemcpy(c->eye3, e, sizeof e, hipMemcpyHostToDevice));
-    }
-    RDM_CHECK_HIP(c, launch_vq_quantize(z, (const float*)(v.blob + v.codebook), v.cfg.n_embed, c->eye3, c->eye3 + 9, zq_out, indices_out, b, h * w, 1, c->stream));
+    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_step: bad argument");
+    DpmppStepParams p{};
+    p.x = x; p.eps = eps; p.m_prev = m_prev; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale; p.sqrt_a_s = sqrt_a_s;
+    p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1;
+    p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
+    RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
     return 0;
 }
-int rdm_vq_quantize(rdm_ctx* c, const float* z, int b, float* zq_out, int32_t* indices_out) {
+int rdm_op_unipc_step(rdm_ctx* c, const float* u, const float* eps, const float* xc_prev, const float* h1, const float* h2, const float* h3,
+                      long long n, int cfg, float scale, const double* coefficients, float* xc_out, float* u_next, float* x_dup,
+                      float* m_store, float* pred_x0) {
     RDM_ENTER(c);
-    const int zr = c->vq.loaded ? c->vq.cfg.resolution >> (c->vq.cfg.n_ch_mult - 1) : 1;
-    return vq_quantize_impl(c, "rdm_vq_quantize", z, b, zr, zr, zq_out, indices_out);
-}
-int rdm_vq_quantize_hw(rdm_ctx* c, const float* z, int b, int h, int w, float* zq_out, int32_t* indices_out) {
-    RDM_ENTER(c);
-    return vq_quantize_impl(c, "rdm_vq_quantize_hw", z, b, h, w, zq_out, indices_out);
-}
-int rdm_vq_decode_indices(rdm_ctx* c, const int64_t* indices, int b, float* img_out) {
-    RDM_ENTER(c);
-    if (!indices || !img_out || b < 1) return c->fail(-1, "bad argument");
-    if (!c->vq.loaded) return c->fail(-1, "vq weights not loaded");
-    if (!c->vq.wide || c->vq.cfg.kl) return c->fail(-1, "rdm_vq_decode_indices needs a VQGAN first stage with a wide latent (z_channels %% 64 == 0)");
-    const rdm_vq_cfg& q = c->vq.cfg;
-    const int zr = q.resolution >> (q.n_ch_mult - 1);
-    return vq_walk(c, c->vq, b, zr, zr, true, [&](Ops& o, int b0, int n) {
-        vq_wide_body(o, c->vq, (const long long*)indices + (size_t)b0 * zr * zr, n, img_out + (size_t)b0 * q.out_ch * q.resolution * q.resolution);
-    });
-}
-
-int rdm_to_uint8(rdm_ctx* c, const float* img, int b, int ch, int h, int w, uint8_t* out) {
-    RDM_ENTER(c);
-    if (!c || !img || !out) return -1;
-    RDM_CHECK_HIP(c, launch_to_uint8_hwc(img, out, b, ch, h, w, c->stream));
+    if (!u || !eps || !coefficients || !u_next || n < 1) return c->fail(-1, "rdm_op_unipc_step: bad argument");
+    UnipcStepParams p{};
+    unipc_fill(p, coefficients);
+    if (p.order_c < 0 || p.order_c > 3 || p.order_p < 1 || p.order_p > 3) return c->fail(-1, "rdm_op_unipc_step: orders %d, %d outside 0..3, 1..3", p.order_c, p.order_p);
+    const int nh = p.order_c > p.order_p - 1 ? p.order_c : p.order_p - 1;
+    if ((p.order_c >= 1 && !xc_prev) || (nh >= 1 && !h1) || (nh >= 2 && !h2) || (nh >= 3 && !h3))
+        return c->fail(-1, "rdm_op_unipc_step: orders %d, %d need xc_prev / history operands that are null", p.order_c, p.order_p);
+    p.u = u; p.eps = eps; p.xc_prev = xc_prev; p.h1 = h1; p.h2 = h2; p.h3 = h3; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale;
+    p.xc_out = xc_out; p.u_next = u_next; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
+    RDM_CHECK_HIP(c, launch_unipc_step(p, c->stream));
     return 0;
-}
-
-int rdm_clip_encode_text(rdm_ctx* c, const int64_t* tokens, int b, float* out) {
-    RDM_ENTER(c);
-    if (!c || !tokens || !out) return c ? c->fail(-1, "null argument") : -1;
-    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
-    return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_text_body(o, c->clip, (const long long*)tokens, b, out); });
-}
-int rdm_clip_encode_image(rdm_ctx* c, const float* image, int b, float* out) {
-    RDM_ENTER(c);
-    if (!c || !image || !out) return c ? c->fail(-1, "null argument") : -1;
-    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
-    return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_image_body(o, c->clip, image, b, out); });
-}
-
-int rdm_clip_preprocess(rdm_ctx* c, const float* image, int b, int h, int w, float* out) {
-    RDM_ENTER(c);
-    if (!image || !out || b < 1 || h < 1 || w < 1) return c->fail(-1, "bad argument");
-    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded (the target resolution comes from the clip cfg)");
-    RDM_CHECK_HIP(c, launch_clip_preprocess(image, b, h, w, c->clip.cfg.image_resolution, c->clip.cfg.vision_patch_size, out, nullptr, c->stream));
-    return 0;
-}
-int rdm_clip_encode_image_raw(rdm_ctx* c, const float* image, int b, int h, int w, float* out) {
-    RDM_ENTER(c);
-    if (!image || !out || b < 1 || h < 1 || w < 1) return c->fail(-1, "bad argument");
-    if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
-    return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_image_body(o, c->clip, image, b, out, h, w); });
 }
 
 // ---- RARM (kernels in rarm.hip)
@@ -2641,26 +1683,7 @@ int rdm_rarm_nll(rdm_ctx* c, const int64_t* tokens, const int64_t* targets, int 
     return rarm_seq_body(c, tokens, t, b, b, t, k, nullptr, targets, nll_out, false);
 }
 static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
-                           const float* uniforms, int64_t* tokens_out, bool prefill = false);
-int rdm_rarm_sample_prefill(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
-                            const float* uniforms, int64_t* tokens_out) {
-    RDM_ENTER(c);
-    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_rarm_sample_prefill: top_p must lie in (0, 1], got %g", (double)top_p);
-    if (a && a->k > 128) return c->fail(-1, "the whole-sequence pass attends at most 128 neighbours per sequence, got k=%d", a->k);
-    return rarm_sample_run(c, a, top_p, cond_tokens, context, uniforms, tokens_out, true);
-}
-int rdm_rarm_sample(rdm_ctx* c, const rdm_rarm_sample_args* a, const int64_t* cond_tokens, const float* context, const float* uniforms,
-                    int64_t* tokens_out) {
-    return rarm_sample_run(c, a, 1.0f, cond_tokens, context, uniforms, tokens_out);
-}
-int rdm_rarm_sample_top_p(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
-                          const float* uniforms, int64_t* tokens_out) {
-    RDM_ENTER(c);
-    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_rarm_sample_top_p: top_p must lie in (0, 1], got %g", (double)top_p);
-    return rarm_sample_run(c, a, top_p, cond_tokens, context, uniforms, tokens_out);
-}
-static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
-                           const float* uniforms, int64_t* tokens_out, bool prefill) {
+                           const float* uniforms, int64_t* tokens_out, bool prefill = false) {
     RDM_ENTER(c);
     if (!a || !cond_tokens || !context || !uniforms || !tokens_out) return c->fail(-1, "null argument");
     if (a->cond_len < 1 || a->steps < 1 || a->temperature <= 0.f) return c->fail(-1, "bad sampling arguments");
@@ -2690,168 +1713,22 @@ static int rarm_sample_run(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_
     }
     return 0;
 }
-
-// ---- retrieval (kernels in knn.hip)
-int rdm_db_load(rdm_ctx* c, const void* emb, long long n, int dim, int dtype, int is_device) {
+int rdm_rarm_sample_prefill(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
+                            const float* uniforms, int64_t* tokens_out) {
     RDM_ENTER(c);
-    if (!c || !emb) return -1;
-    const char* msg = knn_load(c->db, emb, n, dim, dtype, is_device, c->stream);
-    return msg ? c->fail(-5, "rdm_db_load: %s", msg) : 0;
+    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_rarm_sample_prefill: top_p must lie in (0, 1], got %g", (double)top_p);
+    if (a && a->k > 128) return c->fail(-1, "the whole-sequence pass attends at most 128 neighbours per sequence, got k=%d", a->k);
+    return rarm_sample_run(c, a, top_p, cond_tokens, context, uniforms, tokens_out, true);
 }
-long long rdm_db_size(rdm_ctx* c) { return c ? c->db.n : -1; }
-static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out);
-int rdm_knn(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out) { return knn_entry(c, q, b, k, idx_out, score_out, nullptr); }
-int rdm_knn_f64(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, double* score_out) { return knn_entry(c, q, b, k, idx_out, nullptr, score_out); }
-static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out) {
+int rdm_rarm_sample(rdm_ctx* c, const rdm_rarm_sample_args* a, const int64_t* cond_tokens, const float* context, const float* uniforms,
+                    int64_t* tokens_out) {
+    return rarm_sample_run(c, a, 1.0f, cond_tokens, context, uniforms, tokens_out);
+}
+int rdm_rarm_sample_top_p(rdm_ctx* c, const rdm_rarm_sample_args* a, float top_p, const int64_t* cond_tokens, const float* context,
+                          const float* uniforms, int64_t* tokens_out) {
     RDM_ENTER(c);
-    if (!c || !q || !idx_out) return c ? c->fail(-1, "null argument") : -1;
-    const bool prof = (c->prof >> RDM_PROF_KNN) & 1u;
-    if (prof) {     // whole search (query prep + database scan + candidate merge); work = bytes of the database passes
-        rdm_ctx::ProfRec r; r.a = c->prof_event(); r.b = c->prof_event(); r.kind = RDM_PROF_KNN;
-        r.flops = (double)((b + 63) / 64) * (double)c->db.n * c->db.dim * 2.0;
-        r.tag = "knn"; r.d0 = b; r.d1 = k; r.d2 = c->db.dim;
-        hipEventRecord(r.a, c->stream); c->prof_recs.push_back(r);
-    }
-    const char* msg = knn_search(c->db, q, b, k, idx_out, score_out, score64_out, c->stream);
-    if (prof) hipEventRecord(c->prof_recs.back().b, c->stream);
-    return msg ? c->fail(-5, "rdm_knn: %s", msg) : 0;
-}
-int rdm_knn_last_fallback(rdm_ctx* c) { return c ? c->db.last_fallbacks : -1; }
-int rdm_db_gather(rdm_ctx* c, const uint32_t* idx, long long n_idx, float* out) {
-    RDM_ENTER(c);
-    if (!c || !idx || !out) return -1;
-    const char* msg = knn_gather(c->db, idx, n_idx, out, c->stream);
-    return msg ? c->fail(-5, "rdm_db_gather: %s", msg) : 0;
-}
-
-// ---- profiler
-// ------------------------------------------------------------------------------------ RCCL wrappers (include/rdm_hip.h, multi-GPU)
-// RCCL is resolved at run time: the ABI types are spelled out here (ncclUniqueId = 128 bytes, ncclComm_t = pointer, ncclInt8 = 0)
-namespace {
-struct RcclId { char b[128]; };
-typedef int (*fn_get_id)(RcclId*);
-typedef int (*fn_init_rank)(void**, int, RcclId, int);
-typedef int (*fn_all_gather)(const void*, void*, size_t, int, void*, hipStream_t);
-typedef int (*fn_all_reduce)(const void*, void*, size_t, int, int, void*, hipStream_t);
-typedef int (*fn_destroy)(void*);
-typedef const char* (*fn_errstr)(int);
-struct RcclFns { fn_get_id get_id; fn_init_rank init_rank; fn_all_gather all_gather; fn_all_reduce all_reduce; fn_destroy destroy; fn_errstr errstr; };
-int rccl_load(rdm_ctx* c, RcclFns& f) {
-    if (!c->rccl_lib) {
-        c->rccl_lib = dlopen("librccl.so.1", RTLD_NOW | RTLD_GLOBAL);
-        if (!c->rccl_lib) c->rccl_lib = dlopen("librccl.so", RTLD_NOW | RTLD_GLOBAL);
-        if (!c->rccl_lib) return c->fail(-5, "rdm_comm: cannot load librccl.so (%s)", dlerror());
-    }
-    f.get_id = (fn_get_id)dlsym(c->rccl_lib, "ncclGetUniqueId"); f.init_rank = (fn_init_rank)dlsym(c->rccl_lib, "ncclCommInitRank");
-    f.all_gather = (fn_all_gather)dlsym(c->rccl_lib, "ncclAllGather"); f.destroy = (fn_destroy)dlsym(c->rccl_lib, "ncclCommDestroy");
-    f.all_reduce = (fn_all_reduce)dlsym(c->rccl_lib, "ncclAllReduce");
-    f.errstr = (fn_errstr)dlsym(c->rccl_lib, "ncclGetErrorString");
-    if (!f.get_id || !f.init_rank || !f.all_gather || !f.destroy) return c->fail(-5, "rdm_comm: librccl.so lacks the expected entry points");
-    return 0;
-}
-}  // namespace
-int rdm_comm_unique_id(rdm_ctx* c, void* id128) {
-    RDM_ENTER(c);
-    if (!id128) return c->fail(-1, "rdm_comm_unique_id: null id buffer");
-    RcclFns f{}; RDM_TRY(rccl_load(c, f));
-    RcclId id; const int r = f.get_id(&id);
-    if (r != 0) return c->fail(-5, "ncclGetUniqueId failed: %s", f.errstr ? f.errstr(r) : "?");
-    memcpy(id128, id.b, 128);
-    return 0;
-}
-int rdm_comm_init(rdm_ctx* c, const void* id128, int rank, int world) {
-    RDM_ENTER(c);
-    if (!id128 || world < 1 || rank < 0 || rank >= world) return c->fail(-1, "rdm_comm_init: bad arguments (rank %d of %d)", rank, world);
-    if (c->comm) return c->fail(-1, "rdm_comm_init: communicator already initialised (rdm_comm_destroy first)");
-    RcclFns f{}; RDM_TRY(rccl_load(c, f));
-    RcclId id; memcpy(id.b, id128, 128);
-    void* comm = nullptr; const int r = f.init_rank(&comm, world, id, rank);
-    if (r != 0) return c->fail(-5, "ncclCommInitRank failed: %s", f.errstr ? f.errstr(r) : "?");
-    c->comm = comm; c->comm_world = world;
-    return 0;
-}
-int rdm_comm_all_gather(rdm_ctx* c, const void* send, void* recv, size_t nbytes) {
-    RDM_ENTER(c);
-    if (!c->comm) return c->fail(-1, "rdm_comm_all_gather: no communicator (rdm_comm_init)");
-    if (!send || !recv) return c->fail(-1, "rdm_comm_all_gather: null buffer");
-    RcclFns f{}; RDM_TRY(rccl_load(c, f));
-    const int r = f.all_gather(send, recv, nbytes, /*ncclInt8*/ 0, c->comm, c->stream);
-    if (r != 0) return c->fail(-5, "ncclAllGather failed: %s", f.errstr ? f.errstr(r) : "?");
-    return 0;
-}
-int rdm_comm_all_reduce_f32(rdm_ctx* c, float* buf, size_t count, int average) {
-    RDM_ENTER(c);
-    if (!c->comm) return c->fail(-1, "rdm_comm_all_reduce_f32: no communicator (rdm_comm_init)");
-    if (!buf) return c->fail(-1, "rdm_comm_all_reduce_f32: null buffer");
-    RcclFns f{}; RDM_TRY(rccl_load(c, f));
-    if (!f.all_reduce) return c->fail(-5, "rdm_comm: librccl.so lacks ncclAllReduce");
-    const int r = f.all_reduce(buf, buf, count, /*ncclFloat32*/ 7, /*ncclSum*/ 0, c->comm, c->stream);
-    if (r != 0) return c->fail(-5, "ncclAllReduce failed: %s", f.errstr ? f.errstr(r) : "?");
-    if (average && c->comm_world > 1) RDM_CHECK_HIP(c, launch_scale_f32(buf, (long long)count, 1.0f / (float)c->comm_world, c->stream));
-    return 0;
-}
-int rdm_comm_destroy(rdm_ctx* c) {
-    RDM_ENTER(c);
-    if (!c->comm) return 0;
-    RcclFns f{}; RDM_TRY(rccl_load(c, f));
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    f.destroy(c->comm); c->comm = nullptr; c->comm_world = 0;
-    return 0;
-}
-
-int rdm_prof_enable(rdm_ctx* c, int kind_mask) {
-    if (!c) return -1;
-    c->prof = (unsigned)kind_mask;
-    return 0;
-}
-int rdm_prof_collect(rdm_ctx* c, int kind, long long* launches, double* ms, double* flops) {
-    RDM_ENTER(c);
-    if (!c) return -1;
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    long long n = 0; double t = 0, f = 0;
-    for (auto& r : c->prof_recs) {
-        if (r.kind != kind) continue;
-        float e = 0; hipEventElapsedTime(&e, r.a, r.b);
-        n++; t += e; f += r.flops;
-    }
-    if (launches) *launches = n; if (ms) *ms = t; if (flops) *flops = f;
-    return 0;
-}
-int rdm_debug_tap(rdm_ctx* c, void* buf, size_t nbytes, int block, int sub) {
-    if (!c) return -1;
-    c->tap_buf = buf; c->tap_bytes = buf ? nbytes : 0; c->tap_block = buf ? block : -1; c->tap_sub = buf ? sub : 0;
-    return 0;
-}
-int rdm_prof_dump(rdm_ctx* c, const char* path) {
-    RDM_ENTER(c);
-    if (!c || !path) return -1;
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    FILE* f = fopen(path, "w");
-    if (!f) return c->fail(-1, "rdm_prof_dump: cannot open %s", path);
-    fprintf(f, "kind,tag,d0,d1,d2,ms,work\n");
-    for (auto& r : c->prof_recs) {
-        float e = 0; hipEventElapsedTime(&e, r.a, r.b);
-        fprintf(f, "%d,%s,%d,%d,%d,%.6f,%.6e\n", r.kind, r.tag ? r.tag : "", r.d0, r.d1, r.d2, e, r.flops);
-    }
-    fclose(f);
-    return 0;
-}
-// Box calibration (calib.hip): fixed probes, independent of every product kernel.  buf: caller's device scratch.
-int rdm_calib_probe(rdm_ctx* c, void* buf, size_t buf_bytes, double mfma_ms, size_t stream_bytes, int stream_reps, double* mfma_tflops, double* stream_gbps) {
-    RDM_ENTER(c);
-    if (!buf || buf_bytes < (1u << 20) || buf_bytes < 2 * stream_bytes || stream_bytes % 16 || stream_reps < 1 || !(mfma_ms > 0))
-        return c->fail(-2, "rdm_calib_probe: buf must hold max(1 MiB, 2 * stream_bytes), stream_bytes a multiple of 16, stream_reps >= 1, mfma_ms > 0");
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    RDM_CHECK_HIP(c, run_calib_probes(buf, mfma_ms, stream_bytes, stream_reps, mfma_tflops, stream_gbps, c->stream));
-    return 0;
-}
-int rdm_prof_reset(rdm_ctx* c) {
-    RDM_ENTER(c);
-    if (!c) return -1;
-    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
-    for (auto& r : c->prof_recs) { c->prof_pool.push_back(r.a); c->prof_pool.push_back(r.b); }
-    c->prof_recs.clear();
-    return 0;
+    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_rarm_sample_top_p: top_p must lie in (0, 1], got %g", (double)top_p);
+    return rarm_sample_run(c, a, top_p, cond_tokens, context, uniforms, tokens_out);
 }
 
 // ---- operator-level entries (parity tests, op benchmarks, the training path): argument checks, then the executors' dispatch (Ops) on
@@ -2921,33 +1798,6 @@ int rdm_op_vq_nearest_code(rdm_ctx* c, const float* z, const float* codebook, lo
     Ops o = op_exec(c);
     o.vq_nearest(z, codebook, norms, M, N, E, c->samp + nbytes, idx_out, nullptr);
     return o.rc;
-}
-static int op_rarm_sampler_run(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
-                               float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out);
-int rdm_op_rarm_sampler(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
-                        const float* uniforms, int64_t* tokens_out) {
-    return op_rarm_sampler_run(c, logits, b, vocab, cfg, guidance_scale, temperature, top_k, 1.0f, uniforms, tokens_out, nullptr);
-}
-int rdm_op_rarm_sampler_top_p(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
-                              float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out) {
-    RDM_ENTER(c);
-    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_op_rarm_sampler_top_p: top_p must lie in (0, 1], got %g", (double)top_p);
-    return op_rarm_sampler_run(c, logits, b, vocab, cfg, guidance_scale, temperature, top_k, top_p, uniforms, tokens_out, kept_out);
-}
-static int op_rarm_sampler_run(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
-                               float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out) {
-    RDM_ENTER(c);
-    if (!logits || !uniforms || !tokens_out || b < 1 || vocab < 1) return c->fail(-1, "rdm_op_rarm_sampler: bad arguments");
-    if (!(temperature > 0.f)) return c->fail(-1, "rdm_op_rarm_sampler: temperature must be positive");
-    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, (size_t)b * 8 + 64));
-    int* pos = (int*)c->samp; int* done = pos + 1; long long* next = (long long*)(c->samp + 64);
-    RDM_CHECK_HIP(c, launch_set_int(pos, 0, c->stream));
-    RDM_CHECK_HIP(c, launch_set_int(done, 0, c->stream));
-    RarmSampleParams sp{}; sp.logits = logits; sp.vocab = vocab; sp.B = b; sp.cfg = cfg ? 1 : 0; sp.scale = guidance_scale; sp.temperature = temperature;
-    sp.top_k = top_k > 0 ? top_k : vocab; sp.uniforms = uniforms; sp.pos = pos; sp.pos0 = 0; sp.steps = 1; sp.tokens_out = (long long*)tokens_out;
-    sp.next_tokens = next; sp.done = done; sp.top_p = top_p; sp.kept_out = kept_out;
-    RDM_CHECK_HIP(c, launch_rarm_sample(sp, c->stream));
-    return 0;
 }
 // ---- backward ops (kernels in backward.hip)
 int rdm_op_conv3x3_dgrad(rdm_ctx* c, const void* dy, const void* w, void* dx, int B, int H, int W, int C, int N) {
@@ -3037,33 +1887,6 @@ int rdm_op_add(rdm_ctx* c, const void* a, const void* b, void* out, long long n)
     if (!a || !b || !out) return c->fail(-1, "rdm_op_add: null argument");
     if (n < 1) return c->fail(-1, "rdm_op_add: n must be positive");
     RDM_CHECK_HIP(c, launch_add_bf16((const bf16_t*)a, (const bf16_t*)b, (bf16_t*)out, n, c->stream));
-    return 0;
-}
-int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int cfg, float scale, float sqrt_a_s,
-                      float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup, float* m_store, float* pred_x0) {
-    RDM_ENTER(c);
-    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_step: bad argument");
-    DpmppStepParams p{};
-    p.x = x; p.eps = eps; p.m_prev = m_prev; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale; p.sqrt_a_s = sqrt_a_s;
-    p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1;
-    p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
-    RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
-    return 0;
-}
-int rdm_op_unipc_step(rdm_ctx* c, const float* u, const float* eps, const float* xc_prev, const float* h1, const float* h2, const float* h3,
-                      long long n, int cfg, float scale, const double* coefficients, float* xc_out, float* u_next, float* x_dup,
-                      float* m_store, float* pred_x0) {
-    RDM_ENTER(c);
-    if (!u || !eps || !coefficients || !u_next || n < 1) return c->fail(-1, "rdm_op_unipc_step: bad argument");
-    UnipcStepParams p{};
-    unipc_fill(p, coefficients);
-    if (p.order_c < 0 || p.order_c > 3 || p.order_p < 1 || p.order_p > 3) return c->fail(-1, "rdm_op_unipc_step: orders %d, %d outside 0..3, 1..3", p.order_c, p.order_p);
-    const int nh = p.order_c > p.order_p - 1 ? p.order_c : p.order_p - 1;
-    if ((p.order_c >= 1 && !xc_prev) || (nh >= 1 && !h1) || (nh >= 2 && !h2) || (nh >= 3 && !h3))
-        return c->fail(-1, "rdm_op_unipc_step: orders %d, %d need xc_prev / history operands that are null", p.order_c, p.order_p);
-    p.u = u; p.eps = eps; p.xc_prev = xc_prev; p.h1 = h1; p.h2 = h2; p.h3 = h3; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale;
-    p.xc_out = xc_out; p.u_next = u_next; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
-    RDM_CHECK_HIP(c, launch_unipc_step(p, c->stream));
     return 0;
 }
 int rdm_op_ema(rdm_ctx* c, float* shadow, const float* p, long long n, float one_minus_decay) {
@@ -3289,21 +2112,94 @@ int rdm_op_causal_attention_d64(rdm_ctx* c, const void* qkv, int ldq, int B, int
     o.causal_d64((const bf16_t*)qkv, ldq, (bf16_t*)out, ldo, B, n, heads, scale, (bf16_t*)kcache, (bf16_t*)vcache, L);
     return o.rc;
 }
-// ---- the decode step's kernels one at a time (tests/test_gpu_decode_ops.py): argument checks, then the launch rarm_step makes
-int rdm_linear_rows_select(int M, int N, int K, int act, int ln, int deterministic, rdm_linear_rows_form* out) {
-    if (!out || M < 1 || N < 1 || K < 1 || act < ACT_NONE || act > ACT_SILU) return -1;
-    *out = rdm_linear_rows_form{};
-    static const float some = 0.f;                        // the choice reads which operands are given, never their values
-    SgemmParams q{}; q.M = M; q.N = N; q.K = K; q.lda = K; q.act = act; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-    if (ln) { q.ln_x = &some; q.ln_g = &some; q.ln_b = &some; q.ln_eps = 1e-5f; }
-    out->kernel = ln ? (linear_ln_takes(q, deterministic != 0, true) ? RDM_LINEAR_ROWS_SGEMM : RDM_LINEAR_ROWS_REFUSED) : linear_kernel(q, deterministic != 0, true);
-    if (out->kernel == RDM_LINEAR_ROWS_SGEMM) {
-        const SgemmForm f = sgemm_form(q);
-        if (!sgemm_form_compiled(f)) return -3;
-        out->ma = f.ma; out->nb = f.nb; out->u = f.u; out->nw = f.nw; out->ln = f.ln; out->geglu = f.geglu;
-    }
+int rdm_op_vq_attention(rdm_ctx* c, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias_v, int B, int n, int C, float scale,
+                        void* out, int ldo) {
+    RDM_ENTER(c);
+    if (B < 1 || n < 1) return c->fail(-1, "rdm_op_vq_attention: bad shape B=%d n=%d (B >= 1, n >= 1)", B, n);
+    if (!q || !k || !v || !out) return c->fail(-1, "rdm_op_vq_attention: null argument");
+    if (!vq_attn_stream_supported(C)) return c->fail(-1, "rdm_op_vq_attention: C=%d must be a multiple of 128, at most 512", C);
+    if (ldq % 8 || ldq < C || ldk % 8 || ldk < C || ldv % 8 || ldv < C || ldo % 4 || ldo < C)
+        return c->fail(-1, "rdm_op_vq_attention: bad row pitch (ldq=%d, ldk=%d, ldv=%d: multiples of 8; ldo=%d: a multiple of 4; each at least C=%d)", ldq, ldk, ldv, ldo, C);
+    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (uintptr_t)out % 8)
+        return c->fail(-1, "rdm_op_vq_attention: q, k and v must be 16-byte aligned, out 8-byte aligned");
+    if ((long long)B * ((n + 63) / 64) > 0x7fffffffLL) return c->fail(-1, "rdm_op_vq_attention: B=%d x n=%d is more than one launch takes", B, n);
+    Ops o = op_exec(c);
+    o.vq_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, bias_v, (bf16_t*)out, ldo, B, n, C, scale);
+    return o.rc;
+}
+int rdm_op_causal_attention_d64_bwd(rdm_ctx* c, const void* qkv, int ldq, const void* out, int ldo, const void* dout, int lddo, int B, int n, int heads,
+                                    float scale, void* dqkv, int ldd) {
+    RDM_ENTER(c);
+    if (!qkv || !out || !dout || !dqkv) return c->fail(-1, "rdm_op_causal_attention_d64_bwd: null argument");
+    if (B < 1 || n < 1 || n > 1024 || heads < 1) return c->fail(-1, "rdm_op_causal_attention_d64_bwd: bad shape B=%d n=%d heads=%d (1 <= n <= 1024)", B, n, heads);
+    const int C = heads * 64;
+    if (ldq % 8 || ldq < 3 * C || lddo % 8 || lddo < C || ldo % 4 || ldo < C || ldd % 4 || ldd < 3 * C)
+        return c->fail(-1, "rdm_op_causal_attention_d64_bwd: bad row pitch (ldq=%d, lddo=%d: multiples of 8; ldo=%d, ldd=%d: multiples of 4; each at least its %d or %d columns)",
+                       ldq, lddo, ldo, ldd, C, 3 * C);
+    RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, causal_attention_d64_bwd_scratch_bytes(B, heads, n)));
+    RDM_CHECK_HIP(c, launch_causal_attention_d64_bwd((const bf16_t*)qkv, ldq, (const bf16_t*)out, ldo, (const bf16_t*)dout, lddo, B, n, heads, scale, (bf16_t*)dqkv, ldd,
+                                                     c->bwd_tmp, c->stream));
     return 0;
 }
+int rdm_op_embedding_grad(rdm_ctx* c, const int64_t* tokens, const void* dy, int M, int C, int V, float* dw) {
+    RDM_ENTER(c);
+    if (!tokens || !dy || !dw) return c->fail(-1, "rdm_op_embedding_grad: null argument");
+    if (M < 1 || C < 1 || C > 12288 || V < 1) return c->fail(-1, "rdm_op_embedding_grad: bad shape M=%d C=%d V=%d (M, V >= 1; 1 <= C <= 12288)", M, C, V);
+    RDM_CHECK_HIP(c, launch_embedding_grad((const long long*)tokens, (const bf16_t*)dy, M, C, V, dw, c->stream));
+    return 0;
+}
+int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int nq, int nkv,
+                           int heads, int D, int causal, float scale, void* out, int ldo) {
+    RDM_ENTER(c);
+    Ops o = op_exec(c);
+    o.small_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldkv, (const bf16_t*)v, ldkv, (bf16_t*)out, ldo, B, nq, nkv, heads, D, causal, scale,
+                      "small attention");
+    return o.rc;
+}
+int rdm_op_conv_in(rdm_ctx* c, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, void* out) {
+    RDM_ENTER(c);
+    if (!x || !w || !bias || !out) return c->fail(-1, "rdm_op_conv_in: null argument");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W * 5 >= (1ll << 30) || Cin < 1 || Cin > 4 || Cout < 8 || Cout % 8 || ((Cin <= 3 ? 3 : 4) * 9 + 1) * (long long)Cout * 4 > 96 * 1024)
+        return c->fail(-3, "rdm_op_conv_in: unsupported shape (1 <= Cin <= 4, Cout %% 8, weights + bias within 96 KB of LDS): B %d Cin %d H %d W %d Cout %d", B, Cin, H, W, Cout);
+    RDM_CHECK_HIP(c, launch_conv_in(x, w, bias, (bf16_t*)out, B, Cin, H, W, Cout, c->stream));
+    return 0;
+}
+int rdm_op_conv_out(rdm_ctx* c, const void* x, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout, float* out) {
+    RDM_ENTER(c);
+    if (!x || !w || !bias || !out) return c->fail(-1, "rdm_op_conv_out: null argument");
+    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W >= (1ll << 31) || Cin < 64 || Cin % 64 || Cout < 1 || Cout > 4 || (long long)Cout * 9 * Cin * 4 > 64 * 1024)
+        return c->fail(-3, "rdm_op_conv_out: unsupported shape (Cin %% 64, 1 <= Cout <= 4, weights within 64 KB of LDS): B %d H %d W %d Cin %d Cout %d", B, H, W, Cin, Cout);
+    RDM_CHECK_HIP(c, launch_conv_out((const bf16_t*)x, w, bias, (float*)out, B, H, W, Cin, Cout, c->stream));
+    return 0;
+}
+
+// ---- the token sampler alone
+static int op_rarm_sampler_run(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
+                               float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out) {
+    RDM_ENTER(c);
+    if (!logits || !uniforms || !tokens_out || b < 1 || vocab < 1) return c->fail(-1, "rdm_op_rarm_sampler: bad arguments");
+    if (!(temperature > 0.f)) return c->fail(-1, "rdm_op_rarm_sampler: temperature must be positive");
+    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, (size_t)b * 8 + 64));
+    int* pos = (int*)c->samp; int* done = pos + 1; long long* next = (long long*)(c->samp + 64);
+    RDM_CHECK_HIP(c, launch_set_int(pos, 0, c->stream));
+    RDM_CHECK_HIP(c, launch_set_int(done, 0, c->stream));
+    RarmSampleParams sp{}; sp.logits = logits; sp.vocab = vocab; sp.B = b; sp.cfg = cfg ? 1 : 0; sp.scale = guidance_scale; sp.temperature = temperature;
+    sp.top_k = top_k > 0 ? top_k : vocab; sp.uniforms = uniforms; sp.pos = pos; sp.pos0 = 0; sp.steps = 1; sp.tokens_out = (long long*)tokens_out;
+    sp.next_tokens = next; sp.done = done; sp.top_p = top_p; sp.kept_out = kept_out;
+    RDM_CHECK_HIP(c, launch_rarm_sample(sp, c->stream));
+    return 0;
+}
+int rdm_op_rarm_sampler(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
+                        const float* uniforms, int64_t* tokens_out) {
+    return op_rarm_sampler_run(c, logits, b, vocab, cfg, guidance_scale, temperature, top_k, 1.0f, uniforms, tokens_out, nullptr);
+}
+int rdm_op_rarm_sampler_top_p(rdm_ctx* c, const float* logits, int b, int vocab, int cfg, float guidance_scale, float temperature, int top_k,
+                              float top_p, const float* uniforms, int64_t* tokens_out, int32_t* kept_out) {
+    RDM_ENTER(c);
+    if (!(top_p > 0.f && top_p <= 1.f)) return c->fail(-1, "rdm_op_rarm_sampler_top_p: top_p must lie in (0, 1], got %g", (double)top_p);
+    return op_rarm_sampler_run(c, logits, b, vocab, cfg, guidance_scale, temperature, top_k, top_p, uniforms, tokens_out, kept_out);
+}
+// ---- the decode step's kernels one at a time (tests/test_gpu_decode_ops.py): argument checks, then the launch rarm_step makes
 int rdm_op_linear_rows(rdm_ctx* c, const void* a, const float* ln_x, const float* gamma, const float* beta, const void* w, const float* bias,
                        const float* res_f32, void* out_bf16, float* out_f32, int M, int N, int K, int act) {
     RDM_ENTER(c);
@@ -3380,40 +2276,11 @@ int rdm_op_rarm_embed(rdm_ctx* c, const int64_t* tokens, int tok_ld, int tok_row
     RDM_CHECK_HIP(c, launch_rarm_embed_seq((const long long*)tokens, tok_ld, tok_rows, seq0, emb, pos_t, x, rows, t, C, vocab, c->stream));
     return 0;
 }
-int rdm_op_vq_attention(rdm_ctx* c, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias_v, int B, int n, int C, float scale,
-                        void* out, int ldo) {
-    RDM_ENTER(c);
-    if (B < 1 || n < 1) return c->fail(-1, "rdm_op_vq_attention: bad shape B=%d n=%d (B >= 1, n >= 1)", B, n);
-    if (!q || !k || !v || !out) return c->fail(-1, "rdm_op_vq_attention: null argument");
-    if (!vq_attn_stream_supported(C)) return c->fail(-1, "rdm_op_vq_attention: C=%d must be a multiple of 128, at most 512", C);
-    if (ldq % 8 || ldq < C || ldk % 8 || ldk < C || ldv % 8 || ldv < C || ldo % 4 || ldo < C)
-        return c->fail(-1, "rdm_op_vq_attention: bad row pitch (ldq=%d, ldk=%d, ldv=%d: multiples of 8; ldo=%d: a multiple of 4; each at least C=%d)", ldq, ldk, ldv, ldo, C);
-    if (((uintptr_t)q | (uintptr_t)k | (uintptr_t)v) % 16 || (uintptr_t)out % 8)
-        return c->fail(-1, "rdm_op_vq_attention: q, k and v must be 16-byte aligned, out 8-byte aligned");
-    if ((long long)B * ((n + 63) / 64) > 0x7fffffffLL) return c->fail(-1, "rdm_op_vq_attention: B=%d x n=%d is more than one launch takes", B, n);
-    Ops o = op_exec(c);
-    o.vq_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, bias_v, (bf16_t*)out, ldo, B, n, C, scale);
-    return o.rc;
-}
 int rdm_op_rarm_nll(rdm_ctx* c, const float* logits, long long rows, int vocab, const int64_t* targets, float* nll_out) {
     RDM_ENTER(c);
     if (!logits || !targets || !nll_out) return c->fail(-1, "rdm_op_rarm_nll: null argument");
     if (rows < 1 || vocab < 2 || vocab % 2) return c->fail(-1, "rdm_op_rarm_nll: rows >= 1 and an even vocabulary required (rows=%lld, vocab=%d)", rows, vocab);
     RDM_CHECK_HIP(c, launch_rarm_nll(logits, rows, vocab, (const long long*)targets, nll_out, c->stream));
-    return 0;
-}
-int rdm_op_causal_attention_d64_bwd(rdm_ctx* c, const void* qkv, int ldq, const void* out, int ldo, const void* dout, int lddo, int B, int n, int heads,
-                                    float scale, void* dqkv, int ldd) {
-    RDM_ENTER(c);
-    if (!qkv || !out || !dout || !dqkv) return c->fail(-1, "rdm_op_causal_attention_d64_bwd: null argument");
-    if (B < 1 || n < 1 || n > 1024 || heads < 1) return c->fail(-1, "rdm_op_causal_attention_d64_bwd: bad shape B=%d n=%d heads=%d (1 <= n <= 1024)", B, n, heads);
-    const int C = heads * 64;
-    if (ldq % 8 || ldq < 3 * C || lddo % 8 || lddo < C || ldo % 4 || ldo < C || ldd % 4 || ldd < 3 * C)
-        return c->fail(-1, "rdm_op_causal_attention_d64_bwd: bad row pitch (ldq=%d, lddo=%d: multiples of 8; ldo=%d, ldd=%d: multiples of 4; each at least its %d or %d columns)",
-                       ldq, lddo, ldo, ldd, C, 3 * C);
-    RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, causal_attention_d64_bwd_scratch_bytes(B, heads, n)));
-    RDM_CHECK_HIP(c, launch_causal_attention_d64_bwd((const bf16_t*)qkv, ldq, (const bf16_t*)out, ldo, (const bf16_t*)dout, lddo, B, n, heads, scale, (bf16_t*)dqkv, ldd,
-                                                     c->bwd_tmp, c->stream));
     return 0;
 }
 int rdm_op_rarm_nll_bwd(rdm_ctx* c, const float* logits, long long rows, int vocab, const int64_t* targets, float gscale, void* dlogits, float* nll_out) {
@@ -3423,36 +2290,3 @@ int rdm_op_rarm_nll_bwd(rdm_ctx* c, const float* logits, long long rows, int voc
     RDM_CHECK_HIP(c, launch_rarm_nll_bwd(logits, rows, vocab, (const long long*)targets, gscale, (bf16_t*)dlogits, nll_out, c->stream));
     return 0;
 }
-int rdm_op_embedding_grad(rdm_ctx* c, const int64_t* tokens, const void* dy, int M, int C, int V, float* dw) {
-    RDM_ENTER(c);
-    if (!tokens || !dy || !dw) return c->fail(-1, "rdm_op_embedding_grad: null argument");
-    if (M < 1 || C < 1 || C > 12288 || V < 1) return c->fail(-1, "rdm_op_embedding_grad: bad shape M=%d C=%d V=%d (M, V >= 1; 1 <= C <= 12288)", M, C, V);
-    RDM_CHECK_HIP(c, launch_embedding_grad((const long long*)tokens, (const bf16_t*)dy, M, C, V, dw, c->stream));
-    return 0;
-}
-int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int nq, int nkv,
-                           int heads, int D, int causal, float scale, void* out, int ldo) {
-    RDM_ENTER(c);
-    Ops o = op_exec(c);
-    o.small_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldkv, (const bf16_t*)v, ldkv, (bf16_t*)out, ldo, B, nq, nkv, heads, D, causal, scale,
-                      "small attention");
-    return o.rc;
-}
-int rdm_op_conv_in(rdm_ctx* c, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, void* out) {
-    RDM_ENTER(c);
-    if (!x || !w || !bias || !out) return c->fail(-1, "rdm_op_conv_in: null argument");
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W * 5 >= (1ll << 30) || Cin < 1 || Cin > 4 || Cout < 8 || Cout % 8 || ((Cin <= 3 ? 3 : 4) * 9 + 1) * (long long)Cout * 4 > 96 * 1024)
-        return c->fail(-3, "rdm_op_conv_in: unsupported shape (1 <= Cin <= 4, Cout %% 8, weights + bias within 96 KB of LDS): B %d Cin %d H %d W %d Cout %d", B, Cin, H, W, Cout);
-    RDM_CHECK_HIP(c, launch_conv_in(x, w, bias, (bf16_t*)out, B, Cin, H, W, Cout, c->stream));
-    return 0;
-}
-int rdm_op_conv_out(rdm_ctx* c, const void* x, const float* w, const float* bias, int B, int H, int W, int Cin, int Cout, float* out) {
-    RDM_ENTER(c);
-    if (!x || !w || !bias || !out) return c->fail(-1, "rdm_op_conv_out: null argument");
-    if (B < 1 || B > 65535 || H < 1 || W < 1 || (long long)H * W >= (1ll << 31) || Cin < 64 || Cin % 64 || Cout < 1 || Cout > 4 || (long long)Cout * 9 * Cin * 4 > 64 * 1024)
-        return c->fail(-3, "rdm_op_conv_out: unsupported shape (Cin %% 64, 1 <= Cout <= 4, weights within 64 KB of LDS): B %d H %d W %d Cin %d Cout %d", B, H, W, Cin, Cout);
-    RDM_CHECK_HIP(c, launch_conv_out((const bf16_t*)x, w, bias, (float*)out, B, H, W, Cin, Cout, c->stream));
-    return 0;
-}
-
-}  // extern "C"

@@ -15,7 +15,7 @@
 #include "kernels.h"
 
 
-// Zero-padded sources (model.hip build_unet): x0 holds L0 <= C0 real channels, x1 L1 <= C1; groups partition the L0 + L1 logical
+// Zero-padded sources (describe.hip build_unet): x0 holds L0 <= C0 real channels, x1 L1 <= C1; groups partition the L0 + L1 logical
 // channels.  gn_logical: physical concat index -> logical index (or -1 for a padding channel); gn_physical: the inverse.
 __device__ __forceinline__ int gn_logical(const GnParams& p, int c) {
     if (c < p.C0) return c < p.L0 ? c : -1;

@@ -292,7 +292,7 @@ static void pick_tile(const SgemmParams& p, int& ma, int& nb) {
 }
 
 // The ONE statement of which instantiation takes a shape: (MA, NB, U, NW, LN) of sgemm_kernel, from (M, N, K, act, LayerNorm operand,
-// fixed_split) only.  launch_sgemm launches what it returns; rdm_linear_rows_select (model.hip) reports it.
+// fixed_split) only.  launch_sgemm launches what it returns; rdm_linear_rows_select (dispatch.hip) reports it.
 template <bool GEGLU>
 static SgemmForm form_nf(const SgemmParams& p) {
     const bool deep = ((p.K >> 2) % 192) == 0;            // K quarter is a multiple of 6 k-steps of 32 (K = 768, 1536, 3072 ...)

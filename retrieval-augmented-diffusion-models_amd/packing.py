@@ -31,7 +31,7 @@ def _geglu_perm(n8c: int) -> torch.Tensor:
 
 
 def _parse_kind(kd: str):
-    """'kind|R=a>b,c>d|C=e>f' -> (kind, row segments, channel segments): the library's channel-padding recipe (model.hip build_unet):
+    """'kind|R=a>b,c>d|C=e>f' -> (kind, row segments, channel segments): the library's channel-padding recipe (describe.hip build_unet):
     a dimension of sum(logical) entries becomes sum(padded) entries, every segment followed by its zero tail."""
     parts = kd.split("|")
     rows = cols = None

@@ -63,7 +63,7 @@ def lin4_wm(M, N):
 
 
 def linear_path(M, N, K, act=ACT_NONE, alpha=1.0, f32=False, res=False, rows=None, mgemm=False):
-    """the kernel rdm_op_linear / rdm_op_linear_rowvec launches for this call (model.hip Ops::linear, lin4_supported, launch_igemm)"""
+    """the kernel rdm_op_linear / rdm_op_linear_rowvec launches for this call (dispatch.hip Ops::linear, lin4_supported, launch_igemm)"""
     if M <= 128 and alpha == 1.0 and rows is None and K % 256 == 0 and (N % 64 == 0 if act == ACT_GEGLU else N % 32 == 0):
         return "sgemm"
     if mgemm:
@@ -122,7 +122,7 @@ def conv_ksplit(B, H, W, C, N):
 
 
 def conv_path(B, H, W, C, N, stride=1, ups=0, dual=False, rowvec=False, res=False):
-    """(kernel, K-split planes) rdm_op_conv3x3 launches (model.hip Ops::conv3, conv_halo.hip launch_conv3x3); H, W: the input"""
+    """(kernel, K-split planes) rdm_op_conv3x3 launches (dispatch.hip Ops::conv3, conv_halo.hip launch_conv3x3); H, W: the input"""
     Ho, Wo = (2 * H, 2 * W) if ups else ((H // 2, W // 2) if stride == 2 else (H, W))
     if ups and not dual and C % 64 == 0 and N % 8 == 0 and not rowvec and not res and stride == 1:
         return "igemm phase2", 1
@@ -1009,7 +1009,7 @@ def _gn(**kw):
     B, HW, C = kw["B"], kw["HW"], kw["C0"] + kw.get("C1", 0)
     plan = gn_onepass_plan(HW, C)
     path = f"gn_onepass<NV{plan[2]}, {plan[1]}>" if plan else "gn_stats + gn_apply"
-    if plan is None:                                         # model.hip gn_chunks: the pixel chunks of the statistics pass
+    if plan is None:                                         # dispatch.hip gn_chunks: the pixel chunks of the statistics pass
         nchunk = min(32, max(1, HW // 64))
         if HW % nchunk:
             path += f": {nchunk} chunks of {_cdiv(HW, nchunk)} rows, the last one short"
