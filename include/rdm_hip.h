@@ -319,7 +319,7 @@ int rdm_rarm_sample_top_p(rdm_ctx* ctx, const rdm_rarm_sample_args* args, float 
                           const float* uniforms, int64_t* tokens_out);
 /* ---- RARM over whole sequences: one transformer pass over all t positions (causal self-attention at d_head 64 on the MFMA units,
  *      csrc/attention.hip: causal_d64_kernel) instead of t decode steps.  Sequences are walked in ranges of at most 32 768 rows
- *      (RARM_SEQ_ROWS, csrc/model.hip), so the scratch does not grow with b * t.  At most 128 neighbours per sequence (k <= 128).
+ *      (RARM_SEQ_ROWS, csrc/rarm_exec.hip), so the scratch does not grow with b * t.  At most 128 neighbours per sequence (k <= 128).
  * rdm_rarm_forward_seq: RetrievalPatchTransformer.forward(x, context) (rdm/modules/attention.py:252-272): the contract of
  *      rdm_rarm_forward -- tokens [dev] int64 [b,t], context [dev] f32 [b,k,context_dim], logits_out [dev] f32 [b,t,vocab_out]. */
 int rdm_rarm_forward_seq(rdm_ctx* ctx, const int64_t* tokens, int b, int t, const float* context, int k, float* logits_out);

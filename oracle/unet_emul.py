@@ -3,7 +3,7 @@
 Purpose (verdict round 4, item 4 "close the parity window once"): the fp32 oracle (oracle/unet.py, pinned bit-for-bit against the reference's
 own classes) and the library differ by bf16 STORAGE rounding, ~1.2e-2 relative L2 per forward at the shipped size -- a window wide enough
 to hide a mis-wired residual or a tanh-for-erf GELU.  This module walks the SAME graph with the same state dict in fp32 arithmetic and
-rounds to bf16 at exactly the points where the library stores a bf16 tensor (csrc/model.hip: unet_body), with the library's algebraic
+rounds to bf16 at exactly the points where the library stores a bf16 tensor (csrc/unet_exec.hip: unet_body), with the library's algebraic
 re-associations done the library's way (each cites its site):
 
   * weights of every GEMM / 3x3 conv in bf16; biases, norm affine, conv_in and the `out` conv in fp32;

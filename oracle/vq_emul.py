@@ -1,5 +1,5 @@
 """The LIBRARY's arithmetic for the VQ-f4 first-stage decode, restated on the CPU (oracle — test infrastructure only; the companion of
-oracle/unet_emul.py, same purpose and method: fp32 math, one bf16 rounding wherever csrc/model.hip `vq_body` / `vq_trunk` store a bf16 tensor).
+oracle/unet_emul.py, same purpose and method: fp32 math, one bf16 rounding wherever csrc/first_stage.hip `vq_body` / `vq_trunk` store a bf16 tensor).
 
   * quantisation + post_quant_conv and conv_in in fp32 (vq_quantize_kernel, conv_in_kernel), conv_in's output rounded;
   * ResnetBlock: bf16(swish(GroupNorm eps 1e-6)), bf16 3x3 weights, bias / shortcut added in fp32, one rounding per conv;

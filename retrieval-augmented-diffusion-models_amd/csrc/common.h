@@ -77,7 +77,7 @@ inline int rdm_cur_device() { int d = 0; (void)hipGetDevice(&d); return (d >= 0 
 
 // The library's only environment switches are read through this, as rdm_env_int(getenv("RDM_..."), def) (unset: def):
 // RDM_DETERMINISTIC (= rdm_set_deterministic), and the test / tool hooks RDM_MGEMM_ANY, RDM_MGEMM_FROM, RDM_VQ_RANGE and
-// RDM_OP_FRAG_CACHE (host.h, dispatch.hip, model.hip).  tests/test_library_cpu.py keeps the list from growing.
+// RDM_OP_FRAG_CACHE (host.h, dispatch.hip, first_stage.hip, ops.hip).  tests/test_library_cpu.py keeps the list from growing.
 inline int rdm_env_int(const char* value, int def) { return value ? atoi(value) : def; }
 
 struct IgemmParams {

@@ -1,6 +1,7 @@
-// What the host-side files of librdm_hip share (included only by describe.hip, dispatch.hip, context.hip and model.hip): the entry
-// macros, manifest / arena / model base, the description structs of the five models (rdm_ctx holds them by value), the context,
-// the Ops dispatch struct and run_with_arena.  No function but the Ops methods and the rdm_* entries crosses a file boundary.
+// What the host-side files of librdm_hip share (included only by describe.hip, dispatch.hip, context.hip, unet_exec.hip,
+// first_stage.hip, samplers.hip, rarm_exec.hip and ops.hip): the entry macros, manifest / arena / model base, the description structs
+// of the five models (rdm_ctx holds them by value), the context, the Ops dispatch struct and run_with_arena.  No function crosses a
+// file boundary but the Ops methods, the rdm_* entries and the three UNet functions declared at the end, which samplers.hip calls.
 // The C ABI itself is declared in include/rdm_hip.h; every rdm_* definition takes its C linkage from there.
 #pragma once
 #include <stdarg.h>
@@ -347,3 +348,11 @@ static int run_with_arena(rdm_ctx* c, Arena& ar, const char* blob, F&& body) {
     body(run);
     return run.rc;
 }
+
+// ------------------------------------------------------------------------------------ UNet executor, as the samplers use it
+// (unet_exec.hip; once per sampling call: the conditioning's K/V into UNet::kv_cache / xa_cache / ctx_rows, the time-embedding rows
+// of ts into UNet::emb_table; then one forward per step against them)
+int unet_prepare_kv(rdm_ctx* c, float* cat, const float* cond, const float* uncond, int B, int k);
+int unet_emb_table(rdm_ctx* c, const std::vector<int>& ts, const float** table);
+int unet_forward_impl(rdm_ctx* c, const float* x, const int64_t* t, const float* context, const bf16_t* kv_cached,
+                      int b, int k, int H, int W, float* eps_out, int ctx_rows = -1, int shared_half = 0, const float* emb_row = nullptr);

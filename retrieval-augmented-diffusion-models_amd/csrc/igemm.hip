@@ -22,7 +22,7 @@
 #include "kernels.h"
 
 // softmax over groups of g (1, 2, 4) ADJACENT COLUMNS of an accumulator fragment: adjacent columns are adjacent lanes (D layout:
-// col = lane & 31), every r is one row.  Used by the skinny cross-attention scores GEMM (model.hip).
+// col = lane & 31), every r is one row.  Used by the skinny cross-attention scores GEMM (unet_exec.hip).
 __device__ __forceinline__ void softmax_group16(float (&v)[16], int g) {
 #pragma unroll
     for (int r = 0; r < 16; r++) {

@@ -41,7 +41,7 @@ struct FlashParams {
     float scale_log2e;               // d^-0.5 * log2(e)
 };
 
-// cross-attention over k retrieved neighbours in the re-associated form (model.hip: unet_compute_xattn): per sample b
+// cross-attention over k retrieved neighbours in the re-associated form (unet_exec.hip: unet_compute_xattn): per sample b
 //   out = softmax_groups(x G_b^T) U_b^T + bias + res      x [rows][C], G_b [NP][C], U_b [C][NP]  (all bf16, row-major)
 struct XattnParams {
     const bf16_t* x; const bf16_t* G; const bf16_t* U;

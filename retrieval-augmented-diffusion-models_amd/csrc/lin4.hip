@@ -205,7 +205,7 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
     const int L4_STAT = L4_BIAS + p.N * 8;                     // LN: (mean, rstd) of the tile's BM rows
     // rowvec (IgemmParams: a per-sample per-column add) in the restricted form lin4_supported admits: at most TWO row groups of
     // rows_per_sample rows (whole tiles each) -- the guided batch's conditional | unconditional halves, whose attn1.to_out bias differs
-    // by attn2's output bias (model.hip: the unconditional rows' cross-attention is exactly that bias).  Packed (hi | lo << 16) like the
+    // by attn2's output bias (unet_exec.hip: the unconditional rows' cross-attention is exactly that bias).  Packed (hi | lo << 16) like the
     // bias, [group][N] behind the bias table; it rides in k = 2, 3 of the start-value MFMA.
     const int L4_RV = L4_BIAS + p.N * 4;
     const bool has_rv = !LN && p.rowvec != nullptr;

@@ -36,7 +36,7 @@ hipError_t launch_rarm_embed(const long long* tokens, const float* emb, const fl
     return hipGetLastError();
 }
 
-// The same for ALL positions of a range of sequences (the whole-sequence pass, model.hip: rarm_seq_body): row r of x is position r % t
+// The same for ALL positions of a range of sequences (the whole-sequence pass, rarm_exec.hip: rarm_seq_body): row r of x is position r % t
 // of sequence r / t.  Token rows wrap at tok_rows: the unconditional half of a guided batch reads the conditional half's tokens.
 __global__ __launch_bounds__(256) void rarm_embed_seq_kernel(const long long* tokens, int tok_ld, int tok_rows, int seq0, const float* emb,
                                                              const float* pos_t /*[L][C]*/, float* x, int t, int C, int vocab) {
@@ -376,7 +376,7 @@ hipError_t launch_rarm_decode_attention(const RarmAttnParams& p, int heads, int 
 // ---------------------------------------------------------------- decode-step cross-attention, one launch
 // norm2 + to_q + attention over the k neighbours + to_out + residual (RetrievalPatchTransformer block, rdm/modules/attention.py:238)
 // for ONE new token per sequence.  With the neighbours fixed for the whole sampling call, softmax(q K^T / sqrt d) V W_o^T is
-// re-associated per sequence (model.hip: rarm_prepare): scores = LN(x) G_b^T, out = P UT_b -- two matrix-vector products against 2 x
+// re-associated per sequence (rarm_exec.hip: rarm_prepare): scores = LN(x) G_b^T, out = P UT_b -- two matrix-vector products against 2 x
 // heads*k x C bf16 per sequence instead of two C x C projections and an attention launch (3 launches of ~9 us each, all latency).
 // One block per sequence: LayerNorm by block reduction (two-pass, rounded to bf16 as the GEMM operand was), a wave per group of
 // score rows (coalesced 16-byte pieces, wave reduction), per-head softmax, then 4 output channels per thread over the heads*k rows.

@@ -345,7 +345,7 @@ static hipError_t launch_conv9(WgradParams& p, int Z, hipStream_t st) {
     wgrad_conv9_kernel<LW><<<dim3((unsigned)(p.tiles * Z)), 256, conv9_lds_bytes<LW>(), st>>>(p);
     return hipGetLastError();
 }
-// The one rule of which kernel takes a weight gradient, and with what split: the op entry points (model.hip), launch_wgrad_tn below and
+// The one rule of which kernel takes a weight gradient, and with what split: the op entry points (ops.hip), launch_wgrad_tn below and
 // rdm_wgrad_select (which reports it) all ask these two.  per_plane: image-row chunks (nine-tap kernel), rows m (per-tap / one-tap kernel) or
 // K' positions (fallbacks) of one Z plane; remap: the nine-tap kernel's count of XCD-dealt planes (Z & ~7), the per-tap kernel's flag.
 bool conv_wgrad_args_ok(int B, int H, int W, int C, int N) {

@@ -96,7 +96,7 @@ def pack(kind: str, cfg, sd: Dict[str, torch.Tensor]) -> np.ndarray:
             data = _bf16_bytes(_pad_dim(ts[0][_geglu_perm(ts[0].shape[0])], 1, cseg))
         elif kd == "geglu_b":
             data = _f32_bytes(ts[0][_geglu_perm(ts[0].shape[0])])
-        elif kd == "fuse_w":      # [W_out W_2 | W_out]: ff.net.2 then proj_out as ONE linear map of [ff | t2] (model.hip transformer())
+        elif kd == "fuse_w":      # [W_out W_2 | W_out]: ff.net.2 then proj_out as ONE linear map of [ff | t2] (unet_exec.hip transformer())
             w2, wo = ts[0].double(), ts[1].reshape(ts[1].shape[0], -1).double()
             data = _bf16_bytes(_pad_dim(_pad_dim(torch.cat([wo @ w2, wo], dim=1).float(), 0, rseg), 1, cseg))
         elif kd == "fuse_b":      # W_out b_2 + b_out

@@ -298,7 +298,7 @@ def test_vqgan_decode_indices(ctx, which):
 
 
 def test_vq_decode_walked_in_sample_ranges(ctx, tmp_path):
-    """A batch bigger than the decoder's range (model.hip vq_range: the largest activation below 2^30 elements, so that the halo convs'
+    """A batch bigger than the decoder's range (first_stage.hip vq_range: the largest activation below 2^30 elements, so that the halo convs'
     32-bit operand offsets hold) is decoded range by range.  Forced here with RDM_VQ_RANGE=2 in a child process on 5 images of the tiny
     VQGAN (ranges of 2, 2, 1) and on 3 latents of the tiny VQ-f4 decoder: every image must match the one-range decode of this process to 1e-6
     (decoding is per sample; the tiny shapes take the same kernels at B = 1, 2 and 5, so equal bits are expected and reported)."""
