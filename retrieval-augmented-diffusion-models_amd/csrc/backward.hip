@@ -209,9 +209,9 @@ hipError_t launch_conv_wgrad(const bf16_t* x, const bf16_t* dy, float* dw, int B
     e = hipGetLastError(); if (e != hipSuccess) return e;
     for (int tap = 0; tap < 9; tap++) {
         const int ky = tap / 3, kx = tap % 3;
-        IgemmParams p{}; p.M = N; p.N = C; p.K = Kc; p.alpha = 1.f; p.zero_page = zero_page;
-        p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1;
-        p.A0 = dyT + margin; p.C0 = Kc; p.lda = PR; p.sA = Kc;
+        IgemmParams p = igemm_plain(N, C, Kc, zero_page);
+        p.A0 = dyT + margin; p.C0 = Kc;
+        p.lda = PR; p.sA = Kc;
         p.W = xT[kx] + margin + (ky - 1) * WP; p.ldw = PR; p.sW = Kc;       // row offset: a multiple of 8 elements (16-byte aligned)
         p.out_f32 = parts + (size_t)tap * C; p.ldo = 9 * C; p.sO = (long long)N * 9 * C;
         e = launch_igemm(p, false, Z, st);
@@ -241,9 +241,9 @@ hipError_t launch_linear_wgrad(const bf16_t* dy, const bf16_t* a, float* dw, lon
     if (Mp != M) { e = hipMemsetAsync(scratch, 0, (size_t)(N + K) * Mp * 2, st); if (e != hipSuccess) return e; }
     e = launch_transpose_bf16(dy, dyT, (int)M, N, st, 1, (int)Mp); if (e != hipSuccess) return e;
     e = launch_transpose_bf16(a, aT, (int)M, K, st, 1, (int)Mp); if (e != hipSuccess) return e;
-    IgemmParams p{}; p.M = N; p.N = K; p.K = (int)Kc; p.alpha = 1.f; p.zero_page = zero_page;
-    p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1;
-    p.A0 = dyT; p.C0 = (int)Kc; p.lda = (int)Mp; p.sA = Kc;
+    IgemmParams p = igemm_plain(N, K, (int)Kc, zero_page);
+    p.A0 = dyT; p.C0 = (int)Kc;
+    p.lda = (int)Mp; p.sA = Kc;
     p.W = aT; p.ldw = (int)Mp; p.sW = Kc;
     p.out_f32 = parts; p.ldo = K; p.sO = (long long)N * K;
     e = launch_igemm(p, false, Z, st); if (e != hipSuccess) return e;

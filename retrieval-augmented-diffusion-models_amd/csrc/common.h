@@ -119,6 +119,12 @@ struct IgemmParams {
     const float* ln_sb; float ln_inv_c, ln_eps;      // ln_inv_c = 1 / (logical row width): zero padding beyond it adds nothing to the sums
     int dbg;                    // always 0: read only by conv3x3_halo4_kernel's phase-clock code, kept for its code generation (conv_halo4.hip)
 };
+// the start values of a plain GEMM out[M, N] = A[M, K] W^T (host): no scale, 1 x 1 geometry, one row per row-vector group, output rows of N;
+// every caller goes on from these (Ops::base, the op entries, the weight-gradient fallbacks)
+inline IgemmParams igemm_plain(int M, int N, int K, const void* zero_page) {
+    IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.ldo = N; p.zero_page = zero_page;
+    p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1; return p;
+}
 
 // host + device: halo geometry of a conv (output H x W) in the one-wave-per-SIMD kernel.  A tile is 256 consecutive output pixels =
 // NS sample parts of RS whole image rows; its halo is NROW = NS (RS + 2) rows of HPW = W + 2 positions.  LDS image (per 64-channel

@@ -46,79 +46,80 @@ const bf16_t* Ops::derived(const bf16_t* W, int N, int K, int kind) {
     return c->pack_derived(kind, W, d, N, K) == hipSuccess ? d : nullptr;
 }
 
-// skinny (weight-streaming) kernel for decode-sized operands.  Fast mode: whenever M <= 128, and for `single_row` operands up to
-// single_max rows.  Deterministic mode: exactly for the ops with ONE row per sample (`single_row`: time embedding, RARM decode step,
-// CLIP projection), at any batch (one-row-per-sample operands of bigger batches -- RARM decode at 128+ sequences per GPU -- keep the
-// skinny kernel: its row blocks scale with M, while the tiled kernels would run a dozen 256-row tiles)
-bool Ops::skinny(int M, int single_max) const { return skinny_rows(c->deterministic, single_row, M, single_max); }
-// out[M,N] = act(A[M,K] W^T + bias) (+res)
-// a1_wrap_rows > 0: A1 holds that many rows only, row m reads m % a1_wrap_rows (lin4 only: callers check lin4_takes first)
-bool Ops::lin4_takes(int M, int N, int C0, int C1, int a1_wrap_rows, int res_wrap_rows) {
+// The skinny (weight-streaming) kernels take decode-sized operands (skinny_rows).  Fast mode: whenever M <= 128, and for `single_row`
+// operands up to a per-form row count.  Deterministic mode: exactly for the ops with ONE row per sample (`single_row`: time embedding,
+// RARM decode step, CLIP projection), at any batch (one-row-per-sample operands of bigger batches -- RARM decode at 128+ sequences per
+// GPU -- keep the skinny kernel: its row blocks scale with M, while the tiled kernels would run a dozen 256-row tiles)
+static SgemmParams skinny_params(const LinearOp& op) {      // the op as the skinny / mid-size kernels take it (one bf16 operand, or LayerNorm(ln_x))
+    SgemmParams q{}; q.A = op.A0; q.lda = op.C0; q.W = op.W; q.M = op.M; q.N = op.N; q.K = op.C0; q.bias = op.bias;
+    q.act = op.act; q.res_f32 = op.res_f32; q.res_bf16 = op.res_bf16; q.out_f32 = op.out_f32; q.out_bf16 = op.out_bf16;
+    q.ldo = op.act == ACT_GEGLU ? op.N / 2 : op.N;
+    return q;
+}
+bool Ops::lin4_takes(const LinearOp& op) {
     if (c->deterministic) return false;
-    IgemmParams t = base(M, N, C0 + C1);
-    t.C0 = C0; t.C1 = C1; t.W = (const bf16_t*)blob; t.Wfrag = t.W; t.out_bf16 = (bf16_t*)blob; t.a1_wrap_rows = a1_wrap_rows;
-    if (res_wrap_rows > 0) { t.res_bf16 = (const bf16_t*)blob; t.res_wrap_rows = res_wrap_rows; }
+    IgemmParams t = base(op.M, op.N, op.C0 + op.C1);
+    t.C0 = op.C0; t.C1 = op.C1; t.W = (const bf16_t*)blob; t.Wfrag = t.W; t.out_bf16 = (bf16_t*)blob; t.a1_wrap_rows = op.a1_wrap_rows;
+    if (op.res_wrap_rows > 0) { t.res_bf16 = (const bf16_t*)blob; t.res_wrap_rows = op.res_wrap_rows; }
     return lin4_supported(t, 1);
 }
-// rowvec / rowvec_ld / rv_rows: a per-row-group per-column add (IgemmParams::rowvec with rows_per_sample = rv_rows)
-// alpha: scale of the product (the skinny and mid-size kernels take alpha == 1 only)
-void Ops::linear(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int M, int N,
-                 int act, const bf16_t* res, bf16_t* out, float* out_f32, const float* res_f32, int a1_wrap_rows,
-                 const float* rowvec, int rowvec_ld, int rv_rows, int res_wrap_rows, float alpha) {
+void Ops::linear(const LinearOp& op) {
     if (plan) return;
-    if (!A1 && C1 == 0 && !rowvec && alpha == 1.f) {         // N/32 x ceil(M/32) blocks (sgemm.hip), 64 x 64 tiles (mgemm.hip)
-        SgemmParams q{}; q.A = A0; q.lda = C0; q.W = W; q.M = M; q.N = N; q.K = C0; q.bias = bias;
-        q.act = act; q.res_f32 = res_f32; q.res_bf16 = res; q.out_f32 = out_f32; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-        const int kernel = linear_kernel(q, c->deterministic, single_row);
+    const int M = op.M, N = op.N, K = op.C0 + op.C1;
+    if (!op.A1 && op.C1 == 0 && !op.rowvec && op.alpha == 1.f) {         // N/32 x ceil(M/32) blocks (sgemm.hip), 64 x 64 tiles (mgemm.hip)
+        SgemmParams q = skinny_params(op);
+        const int kernel = linear_kernel(q, c->deterministic, op.single_row);
         if (kernel != RDM_LINEAR_ROWS_TILED) {
             const bool mid = kernel == RDM_LINEAR_ROWS_MGEMM;
-            prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C0, M, N, C0);
+            prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)K, M, N, K);
             check(mid ? launch_mgemm(q, c->stream) : launch_sgemm(q, c->stream), mid ? "mid-size linear" : "skinny linear");
             prof_end();
             return;
         }
     }
-    IgemmParams p = base(M, N, C0 + C1);
-    p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = W; p.bias = bias; p.alpha = alpha;
-    p.act = act; p.res_bf16 = res; p.res_f32 = res_f32; p.out_bf16 = out; p.out_f32 = out_f32; p.a1_wrap_rows = a1_wrap_rows;
-    p.res_wrap_rows = res_wrap_rows;
-    if (rowvec) { p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = rv_rows; }
-    if (act == ACT_GEGLU) p.ldo = N / 2;
+    IgemmParams p = base(M, N, K);
+    p.A0 = op.A0; p.A1 = op.A1; p.C0 = op.C0; p.C1 = op.C1; p.W = op.W; p.bias = op.bias; p.alpha = op.alpha;
+    p.act = op.act; p.res_bf16 = op.res_bf16; p.res_f32 = op.res_f32; p.out_bf16 = op.out_bf16; p.out_f32 = op.out_f32;
+    p.a1_wrap_rows = op.a1_wrap_rows; p.res_wrap_rows = op.res_wrap_rows;
+    if (op.rowvec) { p.rowvec = op.rowvec; p.rowvec_ld = op.rowvec_ld; p.rows_per_sample = op.rows_per_sample; }
+    if (op.act == ACT_GEGLU) p.ldo = N / 2;
     // one-wave-per-SIMD kernel for the big-M projections (its tile choice follows M, so not in deterministic mode)
-    // (deterministic mode: its use must not follow the batch -- exactly when the rows of ONE sample fill whole 128 / 256-row tiles,
-    //  at any tile count; a row's sum order is the same in every tile position)
+    // (deterministic mode: its use must not follow the batch -- exactly when the rows of ONE sample (op.sample_rows) fill whole
+    //  128 / 256-row tiles, at any tile count; a row's sum order is the same in every tile position)
     {
         IgemmParams t = p; t.Wfrag = p.W;
         const int tile_rows = (N % 384 == 0) ? 128 : 256;
-        const bool det_ok = rows_hint > 0 && rows_hint % tile_rows == 0;
+        const bool det_ok = op.sample_rows > 0 && op.sample_rows % tile_rows == 0;
         if (c->deterministic) t.l4_any_tiles = p.l4_any_tiles = 1;
-        if ((!c->deterministic || det_ok) && lin4_supported(t, 1)) p.Wfrag = derived(p.W, N, C0 + C1, act == ACT_GEGLU ? 2 : 1);
+        if ((!c->deterministic || det_ok) && lin4_supported(t, 1)) p.Wfrag = derived(p.W, N, K, op.act == ACT_GEGLU ? 2 : 1);
     }
-    prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)(C0 + C1), M, N, C0 + C1);
+    prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)K, M, N, K);
     check(launch_igemm(p, false, 1, c->stream), "linear");
     prof_end();
 }
-// out = act(LayerNorm(x) W^T + bias) with the LayerNorm formed inside the skinny GEMM (sgemm.hip): decode-sized operands only.
-// false = not available for this shape (the caller runs layernorm + linear)
-bool Ops::linear_ln(const float* x, const float* g, const float* b, int C, const bf16_t* W, const float* bias, int M, int N, int act, bf16_t* out) {
-    SgemmParams q{}; q.ln_x = x; q.ln_g = g; q.ln_b = b; q.ln_eps = 1e-5f; q.W = W; q.M = M; q.N = N; q.K = C;
-    q.bias = bias; q.act = act; q.out_bf16 = out; q.ldo = act == ACT_GEGLU ? N / 2 : N;
-    if (!linear_ln_takes(q, c->deterministic, single_row)) return false;
+// out = act(LayerNorm(ln_x; ln_g, ln_b) W^T + bias), bf16, with the LayerNorm formed inside the skinny GEMM (sgemm.hip): decode-sized
+// operands only.  false = not available for this shape (the caller runs layernorm + linear)
+bool Ops::linear_ln(const LinearOp& op) {
+    SgemmParams q = skinny_params(op);
+    q.ln_x = op.ln_x; q.ln_g = op.ln_g; q.ln_b = op.ln_b; q.ln_eps = 1e-5f;
+    if (!linear_ln_takes(q, c->deterministic, op.single_row)) return false;
     if (plan) return true;
-    prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)C, M, N, C);
+    prof_begin(RDM_PROF_LINEAR, 2.0 * op.M * op.N * (double)op.C0, op.M, op.N, op.C0);
     check(launch_sgemm(q, c->stream), "skinny linear on a LayerNorm");
     prof_end();
     return true;
 }
-void Ops::conv3(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int B, int Hin, int Win, int N,
-                int stride, int ups, const float* rowvec, int rowvec_ld, const bf16_t* res, bf16_t* out, int asym) {
+void Ops::conv3(const Conv3Op& op) {
     if (plan) return;
+    const bf16_t* A0 = op.A0; const bf16_t* A1 = op.A1; const bf16_t* W = op.W; const float* bias = op.bias;
+    const int C0 = op.C0, C1 = op.C1, B = op.B, Hin = op.Hin, Win = op.Win, N = op.N, stride = op.stride, ups = op.ups;
+    const float* rowvec = op.rowvec; const bf16_t* res = op.res_bf16; bf16_t* out = op.out_bf16;
     const int Hout = ups ? Hin * 2 : (stride == 2 ? Hin / 2 : Hin), Wout = ups ? Win * 2 : (stride == 2 ? Win / 2 : Win);
     IgemmParams p = base(B * Hout * Wout, N, 9 * (C0 + C1));
-    p.asym = asym;
+    p.asym = op.asym;
     p.A0 = A0; p.A1 = A1; p.C0 = C0; p.C1 = C1; p.W = W; p.bias = bias;
     p.Hin = Hin; p.Win = Win; p.Hout = Hout; p.Wout = Wout; p.stride = stride; p.ups = ups;
-    p.rowvec = rowvec; p.rowvec_ld = rowvec_ld; p.rows_per_sample = Hout * Wout; p.res_bf16 = res; p.out_bf16 = out;
+    p.rowvec = rowvec; p.rowvec_ld = op.rowvec_ld; p.rows_per_sample = Hout * Wout; p.res_bf16 = res; p.out_bf16 = out;
     // deterministic mode: the halo kernels need whole 256-pixel tiles, which at < 256 pixels per sample exist only for batches
     // that are multiples of 256 / HW -- there the generic implicit GEMM (another summation order) runs for EVERY batch; and no
     // split-K (its factor follows the tile count, i.e. the batch)
@@ -166,34 +167,32 @@ void Ops::prof_begin(int kind, double work, int d0, int d1, int d2) {       // w
 }
 void Ops::prof_end() { if (prof_open) hipEventRecord(c->prof_recs.back().b, c->stream); prof_open = false; }
 // (gn_partial must hold B samples' statistics: ensure_gn_partial)
-void Ops::groupnorm(const bf16_t* x0, const bf16_t* x1, int C0, int C1, int B, int HW, const float* g, const float* b, float eps, int silu,
-                    bf16_t* out, int L0, int L1, int x1_bmod, int x0_bmod) {      // L0 / L1: logical channels of the (zero-padded) sources, default = all
+// the caller names x0 (x1), C0 (C1), HW, B, gamma, beta, eps, silu, out, and L0 / L1 (logical channels of zero-padded sources; 0 = all)
+// and x1_bmod / x0_bmod where they apply; the statistics' geometry is the dispatch's
+void Ops::groupnorm(GnParams p) {
     if (plan) return;
-    GnParams p{}; p.x0 = x0; p.x1 = x1; p.C0 = C0; p.C1 = C1; p.HW = HW; p.B = B; p.groups = 32; p.x1_bmod = x1_bmod; p.x0_bmod = x0_bmod;
-    p.L0 = L0 < 0 ? C0 : L0; p.L1 = L1 < 0 ? C1 : L1;
-    p.nchunk = gn_chunks(HW); p.partial = c->gn_partial; p.gamma = g; p.beta = b; p.eps = eps; p.silu = silu;
-    p.out = out;
-    prof_begin(RDM_PROF_GROUPNORM, (double)B * HW * (C0 + C1) * 4.0, B * HW, C0 + C1, silu);       // ALGORITHMIC bytes: one read + one write of the bf16 tensor (round 5: the one-pass kernel moves exactly these; the two-pass form of the 64 x 64 level reads twice)
+    p.groups = 32; p.nchunk = gn_chunks(p.HW); p.partial = c->gn_partial;
+    if (p.L0 <= 0) p.L0 = p.C0;
+    if (p.L1 <= 0) p.L1 = p.C1;
+    prof_begin(RDM_PROF_GROUPNORM, (double)p.B * p.HW * (p.C0 + p.C1) * 4.0, p.B * p.HW, p.C0 + p.C1, p.silu);       // ALGORITHMIC bytes: one read + one write of the bf16 tensor (round 5: the one-pass kernel moves exactly these; the two-pass form of the 64 x 64 level reads twice)
     check(launch_groupnorm(p, c->stream), "groupnorm");
     prof_end();
 }
 // GroupNorm + SiLU + 3x3 conv to a few channels (UNet `out`, VQ decoder conv_out): one statistics pass + the fused MFMA head kernel
-// (misc.hip), or GroupNorm-apply into `tmp` + the VALU head conv where the fused kernel does not apply.  g == null: no GroupNorm
-// (the fused kernel only)
-HeadParams Ops::head_params(const bf16_t* x, int B, int H, int W, int C, const float* g, const float* b, float eps, const float* wt, const float* bias,
-                            int Cout, float* out, bf16_t* wp) const {
-    HeadParams hp{}; hp.x = x; hp.B = B; hp.H = H; hp.W = W; hp.C = C; hp.groups = 32; hp.gamma = g; hp.beta = b; hp.eps = eps;
-    hp.w = wt; hp.wp = wp; hp.bias = bias; hp.out = out; hp.Cout = Cout;
-    if (g) { hp.partial = c->gn_partial; hp.nchunk = gn_chunks(H * W); }
+// (misc.hip), or GroupNorm-apply into `tmp` + the VALU head conv where the fused kernel does not apply.  gamma == null: no GroupNorm
+// (the fused kernel only).  The caller names x, B, H, W, C, gamma, beta, eps, w, wp, bias, out, Cout.
+HeadParams Ops::head_params(HeadParams hp) const {
+    hp.groups = 32;
+    if (hp.gamma) { hp.partial = c->gn_partial; hp.nchunk = gn_chunks(hp.H * hp.W); }
     return hp;
 }
-void Ops::head(const bf16_t* x, int B, int H, int W, int C, int Clog, const float* g, const float* b, float eps, const float* wt, const float* bias, int Cout,
-               float* out, bf16_t* tmp, bf16_t* wp) {
+void Ops::head(HeadParams hp, int Clog, bf16_t* tmp) {
     if (plan) return;
-    const HeadParams hp = head_params(x, B, H, W, C, g, b, eps, wt, bias, Cout, out, wp);
-    if (Clog == C && head_conv_supported(hp)) {
-        if (g) {
-            GnParams p{}; p.x0 = x; p.C0 = C; p.HW = H * W; p.B = B; p.groups = 32; p.L0 = C; p.nchunk = hp.nchunk; p.partial = c->gn_partial;
+    hp = head_params(hp);
+    const int B = hp.B, H = hp.H, W = hp.W, C = hp.C;
+    if ((Clog <= 0 || Clog == C) && head_conv_supported(hp)) {
+        if (hp.gamma) {
+            GnParams p{}; p.x0 = hp.x; p.C0 = C; p.HW = H * W; p.B = B; p.groups = 32; p.L0 = C; p.nchunk = hp.nchunk; p.partial = c->gn_partial;
             prof_begin(RDM_PROF_GROUPNORM, (double)B * H * W * C * 2.0, B * H * W, C, 2);
             check(launch_gn_stats(p, c->stream), "head groupnorm statistics");
             prof_end();
@@ -201,70 +200,60 @@ void Ops::head(const bf16_t* x, int B, int H, int W, int C, int Clog, const floa
         check(launch_head_conv(hp, c->stream), "head conv");
         return;
     }
-    groupnorm(x, nullptr, C, 0, B, H * W, g, b, eps, 1, tmp, Clog, 0);
-    check(launch_conv_out(tmp, wt, bias, out, B, H, W, C, Cout, c->stream), "conv_out");
+    groupnorm({.x0 = hp.x, .C0 = C, .HW = H * W, .B = B, .L0 = Clog, .gamma = hp.gamma, .beta = hp.beta, .eps = hp.eps, .silu = 1, .out = tmp});
+    check(launch_conv_out(tmp, hp.w, hp.bias, hp.out, B, H, W, C, hp.Cout, c->stream), "conv_out");
 }
-// nearest codebook row of every token (vqcode.hip): z f32 [M, E], cb f32 [N, E], norms = |e_j|^2 (launch_vq_code_norms), ws of
-// vq_nearest_ws_bytes(M, N); first minimum on ties, indices as int32 and / or int64
-void Ops::vq_nearest(const float* z, const float* cb, const float* norms, long long M, int N, int E, char* ws, int* idx32, long long* idx64) {
+void Ops::vq_nearest(const VqNearestOp& op) {
     if (plan) return;
-    check(launch_vq_nearest(z, cb, norms, M, N, E, ws, idx32, idx64, c->stream), "vq nearest code");
+    check(launch_vq_nearest(op.z, op.codebook, op.norms, op.M, op.N, op.E, op.ws, op.idx32, op.idx64, c->stream), "vq nearest code");
 }
-void Ops::layernorm(const void* x, int in_f32, const float* g, const float* b, void* out, int out_f32, int M, int C, int Clog, float eps) {
+void Ops::layernorm(const LayerNormOp& op) {
     if (plan) return;
-    prof_begin(RDM_PROF_LAYERNORM, (double)M * C * ((in_f32 ? 4.0 : 2.0) + (out_f32 ? 4.0 : 2.0)), M, C, 0);
-    check(launch_layernorm(x, in_f32, g, b, out, out_f32, M, C, eps, c->stream, Clog < 0 ? C : Clog), "layernorm");
+    const bool in_f32 = op.x_f32 != nullptr, out_f32 = op.out_f32 != nullptr;
+    prof_begin(RDM_PROF_LAYERNORM, (double)op.M * op.C * ((in_f32 ? 4.0 : 2.0) + (out_f32 ? 4.0 : 2.0)), op.M, op.C, 0);
+    check(launch_layernorm(in_f32 ? (const void*)op.x_f32 : op.x_bf16, in_f32, op.gamma, op.beta, out_f32 ? (void*)op.out_f32 : op.out_bf16, out_f32,
+                           op.M, op.C, op.eps, c->stream, op.Clog < 0 ? op.C : op.Clog), "layernorm");
     prof_end();
 }
 // d = 32 flash attention over n tokens (attention.hip): q / k (= q + C) token-major at row stride ldq; V either token-major at the
-// same stride (v: the fused q | k | v projection, n % 64 == 0) or V^T per sample [B][C][n] (vt)
-void Ops::flash_d32(const bf16_t* q, int ldq, const bf16_t* v, const bf16_t* vt, bf16_t* out, int B, int n, int heads) {
+// same stride (v: the fused q | k | v projection, n % 64 == 0) or V^T per sample [B][C][n] (vt).  The caller names q, ldq, v or vt, out, n.
+void Ops::flash_d32(FlashParams f, int heads, int B) {
     if (plan) return;
-    const int C = heads * 32;
-    FlashParams f{}; f.q = q; f.ldq = ldq; f.k = q + C; f.ldk = ldq; f.v = v; f.ldv = v ? ldq : 0; f.vt = vt; f.out = out; f.ldo = C;
-    f.n = n; f.C = C; f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
+    const int C = heads * 32, n = f.n;
+    f.k = f.q + C; f.ldk = f.ldq; f.ldv = f.v ? f.ldq : 0; f.ldo = C; f.C = C;
+    f.scale_log2e = (1.0f / sqrtf(32.f)) * 1.4426950408889634f;
     prof_begin(RDM_PROF_ATTENTION, 4.0 * B * heads * (double)n * n * 32, B, n, C);
     check(launch_flash_d32(f, heads, B, c->stream), "flash attention");
     prof_end();
 }
 // causal self-attention at d_head 64 over all n positions of B sequences (attention.hip): qkv = the fused q | k | v projection rows;
-// kc / vc: optional head-major decode caches [B][heads][L][64] that receive rows 0 .. n-1
-void Ops::causal_d64(const bf16_t* qkv, int ldq, bf16_t* out, int ldo, int B, int n, int heads, float scale, bf16_t* kc, bf16_t* vc, int L) {
+// kcache / vcache: optional head-major decode caches [B][heads][L][64] that receive rows 0 .. n-1.  The caller names all but C and scale_log2e.
+void Ops::causal_d64(CausalD64Params f, int heads, int B, float scale) {
     if (plan) return;
-    CausalD64Params f{}; f.qkv = qkv; f.ldq = ldq; f.out = out; f.ldo = ldo; f.n = n; f.C = heads * 64;
-    f.scale_log2e = scale * 1.4426950408889634f; f.kcache = kc; f.vcache = vc; f.L = L;
+    const int n = f.n;
+    f.C = heads * 64; f.scale_log2e = scale * 1.4426950408889634f;
     prof_begin(RDM_PROF_ATTENTION, 2.0 * B * heads * (double)n * n * 64, B, n, f.C);
     check(launch_causal_d64(f, heads, B, c->stream), "causal attention");
     prof_end();
 }
 // the first stage's AttnBlock without its n x n scores (vq_attn.hip): one head of C channels over n tokens, any n
-void Ops::vq_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, const float* bias_v, bf16_t* out, int ldo, int B, int n, int C,
-                       float scale) {
+void Ops::vq_attention(const VqAttnParams& f, int B) {
     if (plan) return;
-    VqAttnParams f{}; f.q = q; f.ldq = ldq; f.k = k; f.ldk = ldk; f.v = v; f.ldv = ldv; f.bias = bias_v; f.out = out; f.ldo = ldo; f.n = n; f.C = C; f.scale = scale;
-    prof_begin(RDM_PROF_ATTENTION, 6.0 * B * (double)n * n * C, B, n, C);      // the scores twice (vq_attn.hip) and P.V
+    prof_begin(RDM_PROF_ATTENTION, 6.0 * B * (double)f.n * f.n * f.C, B, f.n, f.C);      // the scores twice (vq_attn.hip) and P.V
     check(launch_vq_attn_stream(f, B, c->stream), "vq attention");
     prof_end();
 }
 // attention over a few keys / short sequences (attention.hip): head dim D, nq queries and nkv keys per sample
-void Ops::small_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, bf16_t* out, int ldo, int B, int nq, int nkv,
-                          int heads, int D, int causal, float scale, const char* what) {
+void Ops::small_attention(const SmallAttnParams& p, int D, int heads, int B, const char* what) {
     if (plan) return;
-    SmallAttnParams p{}; p.q = q; p.ldq = ldq; p.k = k; p.ldk = ldk; p.v = v; p.ldv = ldv; p.out = out;
-    p.ldo = ldo; p.nq = nq; p.nkv = nkv; p.causal = causal; p.scale = scale;
     check(launch_small_attention(p, D, heads, B, c->stream), what);
 }
 // cross-attention over k neighbours in one launch (attention.hip): scores against G, softmax, P U, bias and residual; G / U are the
 // fragment-ordered images of launch_xattn_pack.  ln_g given: x holds the raw rows, the scores are taken on LayerNorm(x) and the residual
 // is x itself (res null); ln3_out given: LayerNorm(out rows; ln3_g, ln3_b) leaves with the finished rows
-void Ops::xattn_fused(const bf16_t* x, const float* ln_g, const float* ln_b, float ln_eps, const bf16_t* G, const bf16_t* U, const float* bias,
-                      const bf16_t* res, bf16_t* out, int rows, int n, int C, int NP, int ncols, int group,
-                      const float* ln3_g, const float* ln3_b, bf16_t* ln3_out) {
+void Ops::xattn_fused(const XattnParams& q) {
     if (plan) return;
-    XattnParams q = xattn_params(rows, n, C, NP, ncols, group);
-    q.x = x; q.G = G; q.U = U; q.bias = bias; q.res = res; q.out = out; q.ln_g = ln_g; q.ln_b = ln_b; q.ln_eps = ln_eps;
-    q.ln3_g = ln3_g; q.ln3_b = ln3_b; q.ln3_out = ln3_out;
-    prof_begin(RDM_PROF_LINEAR, 4.0 * rows * NP * (double)C, rows, NP, C);
+    prof_begin(RDM_PROF_LINEAR, 4.0 * q.rows * q.NP * (double)q.C, q.rows, q.NP, q.C);
     check(launch_xattn_fused(q, c->stream), "fused cross attention");
     prof_end();
 }

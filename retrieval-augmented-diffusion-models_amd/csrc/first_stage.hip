@@ -10,15 +10,19 @@
 static bf16_t* vq_res(Ops& o, const VqRes& r, bf16_t* x, int B, int H, int W) {
     const int HW = H * W, M = B * HW;
     bf16_t* n1 = o.abf((size_t)M * r.cin);
-    o.groupnorm(x, nullptr, r.cin, 0, B, HW, o.w<float>(r.n1g), o.w<float>(r.n1b), 1e-6f, 1, n1);
+    o.groupnorm({.x0 = x, .C0 = r.cin, .HW = HW, .B = B, .gamma = o.w<float>(r.n1g), .beta = o.w<float>(r.n1b), .eps = 1e-6f, .silu = 1, .out = n1});
     bf16_t* h1 = o.abf((size_t)M * r.cout);
-    o.conv3(n1, nullptr, r.cin, 0, o.w<bf16_t>(r.w1), o.w<float>(r.b1), B, H, W, r.cout, 1, 0, nullptr, 0, nullptr, h1);
+    o.conv3({.A0 = n1, .C0 = r.cin, .W = o.w<bf16_t>(r.w1), .bias = o.w<float>(r.b1), .B = B, .Hin = H, .Win = W, .N = r.cout, .out_bf16 = h1});
     bf16_t* n2 = o.abf((size_t)M * r.cout);
-    o.groupnorm(h1, nullptr, r.cout, 0, B, HW, o.w<float>(r.n2g), o.w<float>(r.n2b), 1e-6f, 1, n2);
+    o.groupnorm({.x0 = h1, .C0 = r.cout, .HW = HW, .B = B, .gamma = o.w<float>(r.n2g), .beta = o.w<float>(r.n2b), .eps = 1e-6f, .silu = 1, .out = n2});
     const bf16_t* rs = x;
-    if (r.skip) { bf16_t* s = o.abf((size_t)M * r.cout); o.linear(x, nullptr, r.cin, 0, o.w<bf16_t>(r.wsk), o.w<float>(r.bsk), M, r.cout, ACT_NONE, nullptr, s); rs = s; }
+    if (r.skip) {
+        bf16_t* s = o.abf((size_t)M * r.cout);
+        o.linear({.A0 = x, .C0 = r.cin, .W = o.w<bf16_t>(r.wsk), .bias = o.w<float>(r.bsk), .M = M, .N = r.cout, .out_bf16 = s});
+        rs = s;
+    }
     bf16_t* out = o.abf((size_t)M * r.cout);
-    o.conv3(n2, nullptr, r.cout, 0, o.w<bf16_t>(r.w2), o.w<float>(r.b2), B, H, W, r.cout, 1, 0, nullptr, 0, rs, out);
+    o.conv3({.A0 = n2, .C0 = r.cout, .W = o.w<bf16_t>(r.w2), .bias = o.w<float>(r.b2), .B = B, .Hin = H, .Win = W, .N = r.cout, .res_bf16 = rs, .out_bf16 = out});
     return out;
 }
 // An AttnBlock over more than VQ_ATTN_STREAM_N tokens runs on the streaming kernel (vq_attn.hip) when that kernel takes its width; up to there
@@ -32,15 +36,15 @@ static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) 
         // beyond VQ_ATTN_STREAM_N tokens: token-major q, k, v (b_v after P.V, as below) and the two-sweep kernel of vq_attn.hip -- the chain's
         // arithmetic with no scores, no probabilities and no padded copies in memory, at any n
         bf16_t* hn = o.abf((size_t)M * C);
-        o.groupnorm(x, nullptr, C, 0, B, n, o.w<float>(a.ng), o.w<float>(a.nb), 1e-6f, 0, hn);
+        o.groupnorm({.x0 = x, .C0 = C, .HW = n, .B = B, .gamma = o.w<float>(a.ng), .beta = o.w<float>(a.nb), .eps = 1e-6f, .out = hn});
         bf16_t* q = o.abf((size_t)M * C); bf16_t* kk = o.abf((size_t)M * C); bf16_t* v = o.abf((size_t)M * C);
-        o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wq), o.w<float>(a.bq), M, C, ACT_NONE, nullptr, q);
-        o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wk), o.w<float>(a.bk), M, C, ACT_NONE, nullptr, kk);
-        o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wv), nullptr, M, C, ACT_NONE, nullptr, v);
+        o.linear({.A0 = hn, .C0 = C, .W = o.w<bf16_t>(a.wq), .bias = o.w<float>(a.bq), .M = M, .N = C, .out_bf16 = q});
+        o.linear({.A0 = hn, .C0 = C, .W = o.w<bf16_t>(a.wk), .bias = o.w<float>(a.bk), .M = M, .N = C, .out_bf16 = kk});
+        o.linear({.A0 = hn, .C0 = C, .W = o.w<bf16_t>(a.wv), .M = M, .N = C, .out_bf16 = v});
         bf16_t* ao = o.abf((size_t)M * C);
-        o.vq_attention(q, C, kk, C, v, C, o.w<float>(a.bv), ao, C, B, n, C, 1.0f / sqrtf((float)C));
+        o.vq_attention({.q = q, .ldq = C, .k = kk, .ldk = C, .v = v, .ldv = C, .bias = o.w<float>(a.bv), .out = ao, .ldo = C, .n = n, .C = C, .scale = 1.0f / sqrtf((float)C)}, B);
         bf16_t* out = o.abf((size_t)M * C);
-        o.linear(ao, nullptr, C, 0, o.w<bf16_t>(a.wo), o.w<float>(a.bo), M, C, ACT_NONE, x, out);
+        o.linear({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(a.wo), .bias = o.w<float>(a.bo), .M = M, .N = C, .res_bf16 = x, .out_bf16 = out});
         return out;
     }
     // The score and P.V GEMMs contract over tokens in 64-slices and write column pairs: a token count that is no multiple of 64 (a 5 x 7
@@ -52,7 +56,7 @@ static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) 
     const bool padn = np != n;
     const size_t rowb = (size_t)n * C * 2, prowb = (size_t)np * C * 2;
     bf16_t* hn = o.abf((size_t)M * C);
-    o.groupnorm(x, nullptr, C, 0, B, n, o.w<float>(a.ng), o.w<float>(a.nb), 1e-6f, 0, hn);
+    o.groupnorm({.x0 = x, .C0 = C, .HW = n, .B = B, .gamma = o.w<float>(a.ng), .beta = o.w<float>(a.nb), .eps = 1e-6f, .out = hn});
     if (padn) {
         bf16_t* hp = o.abf((size_t)Mp * C);
         if (!o.plan) {
@@ -62,8 +66,8 @@ static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) 
         hn = hp;
     }
     bf16_t* q = o.abf((size_t)Mp * C); bf16_t* kk = o.abf((size_t)Mp * C); bf16_t* vt = o.abf((size_t)Mp * C);
-    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wq), o.w<float>(a.bq), Mp, C, ACT_NONE, nullptr, q);
-    o.linear(hn, nullptr, C, 0, o.w<bf16_t>(a.wk), o.w<float>(a.bk), Mp, C, ACT_NONE, nullptr, kk);
+    o.linear({.A0 = hn, .C0 = C, .W = o.w<bf16_t>(a.wq), .bias = o.w<float>(a.bq), .M = Mp, .N = C, .out_bf16 = q});
+    o.linear({.A0 = hn, .C0 = C, .W = o.w<bf16_t>(a.wk), .bias = o.w<float>(a.bk), .M = Mp, .N = C, .out_bf16 = kk});
     float* S = o.af32((size_t)B * np * np); bf16_t* P = o.abf((size_t)B * np * np); bf16_t* ao = o.abf((size_t)Mp * C);
     if (!o.plan) {
         IgemmParams p = o.base(C, np, C);    // V^T[b] = Wv . hn[b]^T   (bias b_v folded in after P.V: rows of P sum to 1)
@@ -85,7 +89,7 @@ static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) 
         ao = aoc;
     }
     bf16_t* out = o.abf((size_t)M * C);
-    o.linear(ao, nullptr, C, 0, o.w<bf16_t>(a.wo), o.w<float>(a.bo), M, C, ACT_NONE, x, out);
+    o.linear({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(a.wo), .bias = o.w<float>(a.bo), .M = M, .N = C, .res_bf16 = x, .out_bf16 = out});
     return out;
 }
 
@@ -126,14 +130,15 @@ static void vq_trunk(Ops& o, VqModel& v, bf16_t* h, int B, int H, int W, float* 
         if (lvl != 0) {
             const ConvW& u = v.levels[lvl].resample;
             bf16_t* out = o.abf((size_t)B * (H * 2) * (W * 2) * u.c);
-            o.conv3(h, nullptr, u.c, 0, o.w<bf16_t>(u.w), o.w<float>(u.b), B, H, W, u.c, 1, 1, nullptr, 0, nullptr, out);
+            o.conv3({.A0 = h, .C0 = u.c, .W = o.w<bf16_t>(u.w), .bias = o.w<float>(u.b), .B = B, .Hin = H, .Win = W, .N = u.c, .ups = 1, .out_bf16 = out});
             h = out; H *= 2; W *= 2;
             vq_tap(o, &tapi, h, B, H, W, u.c);
         }
     }
     bf16_t* no = o.abf((size_t)B * H * W * bin);
     bf16_t* hwp = o.abf(head_conv_wp_bytes(bin) / 2);
-    o.head(h, B, H, W, bin, bin, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, o.w<float>(v.coutw), o.w<float>(v.coutb), c.out_ch, img, no, hwp);
+    o.head({.x = h, .B = B, .H = H, .W = W, .C = bin, .gamma = o.w<float>(v.noutg), .beta = o.w<float>(v.noutb), .eps = 1e-6f, .w = o.w<float>(v.coutw), .wp = hwp,
+            .bias = o.w<float>(v.coutb), .out = img, .Cout = c.out_ch}, bin, no);
 }
 
 // VQ-f4 (3-channel latent [B, 3, h0, w0]: any size, the decoder is conv-only): quantise (or not) + post_quant_conv + conv_in as tiny fp32 stem
@@ -161,10 +166,10 @@ static void vq_wide_body(Ops& o, VqModel& v, const long long* indices, int B, fl
     bf16_t* zq = o.abf((size_t)M * c.embed_dim);
     if (!o.plan) o.check(launch_codebook_gather(indices, o.w<float>(v.codebook), c.n_embed, c.embed_dim, M, zq, o.c->stream), "codebook gather");
     bf16_t* h0 = o.abf((size_t)M * c.z_channels);
-    o.linear(zq, nullptr, c.embed_dim, 0, o.w<bf16_t>(v.pqw), o.w<float>(v.pqb), M, c.z_channels, ACT_NONE, nullptr, h0);
+    o.linear({.A0 = zq, .C0 = c.embed_dim, .W = o.w<bf16_t>(v.pqw), .bias = o.w<float>(v.pqb), .M = M, .N = c.z_channels, .out_bf16 = h0});
     const int bin = c.ch * c.ch_mult[c.n_ch_mult - 1];
     bf16_t* h = o.abf((size_t)M * bin);
-    o.conv3(h0, nullptr, c.z_channels, 0, o.w<bf16_t>(v.cinw), o.w<float>(v.cinb), B, zr, zr, bin, 1, 0, nullptr, 0, nullptr, h);
+    o.conv3({.A0 = h0, .C0 = c.z_channels, .W = o.w<bf16_t>(v.cinw), .bias = o.w<float>(v.cinb), .B = B, .Hin = zr, .Win = zr, .N = bin, .out_bf16 = h});
     vq_trunk(o, v, h, B, zr, zr, img);
 }
 
@@ -182,7 +187,7 @@ static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, int H, 
         if (lvl != c.n_ch_mult - 1) {      // F.pad(x, (0, 1, 0, 1)) + Conv2d(stride 2, padding 0): window rows 2 oy .. 2 oy + 2, zero beyond the last row / column
             const ConvW& d = v.levels[lvl].resample;
             bf16_t* out = o.abf((size_t)B * (H / 2) * (W / 2) * d.c);
-            o.conv3(h, nullptr, d.c, 0, o.w<bf16_t>(d.w), o.w<float>(d.b), B, H, W, d.c, 2, 0, nullptr, 0, nullptr, out, /*asym=*/1);
+            o.conv3({.A0 = h, .C0 = d.c, .W = o.w<bf16_t>(d.w), .bias = o.w<float>(d.b), .B = B, .Hin = H, .Win = W, .N = d.c, .stride = 2, .out_bf16 = out, .asym = 1});
             h = out; H /= 2; W /= 2;
         }
     }
@@ -190,17 +195,18 @@ static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, int H, 
     bf16_t* no = o.abf((size_t)B * H * W * bin);
     if (v.wide) {
         const int M = B * H * W;
-        o.groupnorm(h, nullptr, bin, 0, B, H * W, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, 1, no);
+        o.groupnorm({.x0 = h, .C0 = bin, .HW = H * W, .B = B, .gamma = o.w<float>(v.noutg), .beta = o.w<float>(v.noutb), .eps = 1e-6f, .silu = 1, .out = no});
         bf16_t* ze = o.abf((size_t)M * c.z_channels);
-        o.conv3(no, nullptr, bin, 0, o.w<bf16_t>(v.coutw), o.w<float>(v.coutb), B, H, W, c.z_channels, 1, 0, nullptr, 0, nullptr, ze);
+        o.conv3({.A0 = no, .C0 = bin, .W = o.w<bf16_t>(v.coutw), .bias = o.w<float>(v.coutb), .B = B, .Hin = H, .Win = W, .N = c.z_channels, .out_bf16 = ze});
         float* zt = o.af32((size_t)M * c.embed_dim);
-        o.linear(ze, nullptr, c.z_channels, 0, o.w<bf16_t>(v.qw), o.w<float>(v.qb), M, c.embed_dim, ACT_NONE, nullptr, nullptr, zt);
+        o.linear({.A0 = ze, .C0 = c.z_channels, .W = o.w<bf16_t>(v.qw), .bias = o.w<float>(v.qb), .M = M, .N = c.embed_dim, .out_f32 = zt});
         if (z && !o.plan) o.check(launch_vq_rows_to_nchw(zt, nullptr, z, B, H * W, c.embed_dim, o.c->stream), "latent to NCHW");
         return zt;
     }
     bf16_t* hwp = o.abf(head_conv_wp_bytes(bin) / 2);
     float* ze = o.af32((size_t)B * c.z_channels * H * W);
-    o.head(h, B, H, W, bin, bin, o.w<float>(v.noutg), o.w<float>(v.noutb), 1e-6f, o.w<float>(v.coutw), o.w<float>(v.coutb), c.z_channels, ze, no, hwp);
+    o.head({.x = h, .B = B, .H = H, .W = W, .C = bin, .gamma = o.w<float>(v.noutg), .beta = o.w<float>(v.noutb), .eps = 1e-6f, .w = o.w<float>(v.coutw), .wp = hwp,
+            .bias = o.w<float>(v.coutb), .out = ze, .Cout = c.z_channels}, bin, no);
     if (!o.plan) o.check(launch_vq_quantize(ze, nullptr, 0, o.w<float>(v.qw), o.w<float>(v.qb), z, nullptr, B, H * W, 0, o.c->stream), "quant_conv");
     return nullptr;
 }
@@ -258,14 +264,14 @@ static void clip_tower(Ops& o, const std::vector<ClipBlk>& blks, float* x, int B
     bf16_t* ln = o.abf((size_t)M * Wd); bf16_t* qkv = o.abf((size_t)M * 3 * Wd); bf16_t* ao = o.abf((size_t)M * Wd);
     bf16_t* hid = o.abf((size_t)M * 4 * Wd);
     for (const ClipBlk& k : blks) {
-        o.layernorm(x, 1, o.w<float>(k.ln1g), o.w<float>(k.ln1b), ln, 0, M, Wd);
-        o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(k.wqkv), o.w<float>(k.bqkv), M, 3 * Wd, ACT_NONE, nullptr, qkv);
-        o.small_attention(qkv, 3 * Wd, qkv + Wd, 3 * Wd, qkv + 2 * Wd, 3 * Wd, ao, Wd, B, L, L, heads, Wd / heads, causal, 1.0f / sqrtf((float)(Wd / heads)),
-                          "clip attention");
-        o.linear(ao, nullptr, Wd, 0, o.w<bf16_t>(k.wo), o.w<float>(k.bo), M, Wd, ACT_NONE, nullptr, nullptr, x, x);        // x += out_proj(attn)
-        o.layernorm(x, 1, o.w<float>(k.ln2g), o.w<float>(k.ln2b), ln, 0, M, Wd);
-        o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(k.wfc), o.w<float>(k.bfc), M, 4 * Wd, ACT_QUICKGELU, nullptr, hid);
-        o.linear(hid, nullptr, 4 * Wd, 0, o.w<bf16_t>(k.wpj), o.w<float>(k.bpj), M, Wd, ACT_NONE, nullptr, nullptr, x, x);  // x += mlp
+        o.layernorm({.x_f32 = x, .gamma = o.w<float>(k.ln1g), .beta = o.w<float>(k.ln1b), .M = M, .C = Wd, .out_bf16 = ln});
+        o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(k.wqkv), .bias = o.w<float>(k.bqkv), .M = M, .N = 3 * Wd, .out_bf16 = qkv});
+        o.small_attention({.q = qkv, .ldq = 3 * Wd, .k = qkv + Wd, .ldk = 3 * Wd, .v = qkv + 2 * Wd, .ldv = 3 * Wd, .out = ao, .ldo = Wd, .nq = L, .nkv = L, .causal = causal,
+                           .scale = 1.0f / sqrtf((float)(Wd / heads))}, Wd / heads, heads, B, "clip attention");
+        o.linear({.A0 = ao, .C0 = Wd, .W = o.w<bf16_t>(k.wo), .bias = o.w<float>(k.bo), .M = M, .N = Wd, .res_f32 = x, .out_f32 = x});        // x += out_proj(attn)
+        o.layernorm({.x_f32 = x, .gamma = o.w<float>(k.ln2g), .beta = o.w<float>(k.ln2b), .M = M, .C = Wd, .out_bf16 = ln});
+        o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(k.wfc), .bias = o.w<float>(k.bfc), .M = M, .N = 4 * Wd, .act = ACT_QUICKGELU, .out_bf16 = hid});
+        o.linear({.A0 = hid, .C0 = 4 * Wd, .W = o.w<bf16_t>(k.wpj), .bias = o.w<float>(k.bpj), .M = M, .N = Wd, .res_f32 = x, .out_f32 = x});  // x += mlp
     }
 }
 static void clip_text_body(Ops& o, ClipModel& m, const long long* tokens, int B, float* out) {
@@ -275,10 +281,8 @@ static void clip_text_body(Ops& o, ClipModel& m, const long long* tokens, int B,
     clip_tower(o, m.text, x, B, L, Wd, c.transformer_heads, 1);
     float* eot = o.af32((size_t)B * Wd); bf16_t* ln = o.abf((size_t)B * Wd);
     if (!o.plan) o.check(launch_clip_gather_eot(tokens, x, eot, B, L, Wd, o.c->stream), "gather eot");
-    o.layernorm(eot, 1, o.w<float>(m.lnfg), o.w<float>(m.lnfb), ln, 0, B, Wd);
-    o.single_row = true;                                  // the pooled token: one row per sample
-    o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(m.tproj), nullptr, B, c.embed_dim, ACT_NONE, nullptr, nullptr, out);
-    o.single_row = false;
+    o.layernorm({.x_f32 = eot, .gamma = o.w<float>(m.lnfg), .beta = o.w<float>(m.lnfb), .M = B, .C = Wd, .out_bf16 = ln});
+    o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(m.tproj), .M = B, .N = c.embed_dim, .out_f32 = out, .single_row = true});      // the pooled token: one row per sample
 }
 // raw_h > 0: `img` is the un-preprocessed [B,3,raw_h,raw_w] image in [-1,1]; the bicubic resize + normalisation of
 // ClipImageRetriever.preprocess (rdm/modules/retrievers.py:83-91) is fused into the patch gather
@@ -290,17 +294,15 @@ static void clip_image_body(Ops& o, ClipModel& m, const float* img, int B, float
         if (raw_h > 0) o.check(launch_clip_preprocess(img, B, raw_h, raw_w, c.image_resolution, P, nullptr, patches, o.c->stream), "preprocess+patchify");
         else o.check(launch_clip_patchify(img, patches, B, c.image_resolution, P, o.c->stream), "patchify");
     }
-    o.linear(patches, nullptr, K, 0, o.w<bf16_t>(m.conv1), nullptr, B * G * G, Wd, ACT_NONE, nullptr, nullptr, pe);
+    o.linear({.A0 = patches, .C0 = K, .W = o.w<bf16_t>(m.conv1), .M = B * G * G, .N = Wd, .out_f32 = pe});
     float* x0 = o.af32((size_t)B * L * Wd); float* x = o.af32((size_t)B * L * Wd);
     if (!o.plan) o.check(launch_clip_vit_assemble(pe, o.w<float>(m.cls), o.w<float>(m.vpos), x0, B, G * G, Wd, o.c->stream), "vit assemble");
-    o.layernorm(x0, 1, o.w<float>(m.lnpreg), o.w<float>(m.lnpreb), x, 1, B * L, Wd);
+    o.layernorm({.x_f32 = x0, .gamma = o.w<float>(m.lnpreg), .beta = o.w<float>(m.lnpreb), .M = B * L, .C = Wd, .out_f32 = x});
     clip_tower(o, m.vis, x, B, L, Wd, Wd / 64, 0);
     float* cls = o.af32((size_t)B * Wd); bf16_t* ln = o.abf((size_t)B * Wd);
     if (!o.plan) o.check(launch_gather_rows_f32(x, cls, B, L, Wd, o.c->stream), "gather cls");
-    o.layernorm(cls, 1, o.w<float>(m.lnpostg), o.w<float>(m.lnpostb), ln, 0, B, Wd);
-    o.single_row = true;                                  // the pooled token: one row per sample
-    o.linear(ln, nullptr, Wd, 0, o.w<bf16_t>(m.vproj), nullptr, B, c.embed_dim, ACT_NONE, nullptr, nullptr, out);
-    o.single_row = false;
+    o.layernorm({.x_f32 = cls, .gamma = o.w<float>(m.lnpostg), .beta = o.w<float>(m.lnpostb), .M = B, .C = Wd, .out_bf16 = ln});
+    o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(m.vproj), .M = B, .N = c.embed_dim, .out_f32 = out, .single_row = true});      // the pooled token: one row per sample
 }
 
 // img [b, out_ch, H, W] -> z_out [b, embed_dim, H / f, W / f]; `what`: the entry's name in messages
@@ -350,7 +352,8 @@ int rdm_vq_encode_indices(rdm_ctx* c, const float* img, int b, int64_t* indices_
         const long long M = (long long)n * HW;
         char* ws = (char*)o.ar->alloc(vq_nearest_ws_bytes(M, d.n_embed));
         int* idx32 = (int*)o.ar->alloc((size_t)M * 4);
-        o.vq_nearest(zt, cb, c->vq.code_norms, M, d.n_embed, d.embed_dim, ws, idx32, (long long*)indices_out + (size_t)b0 * HW);
+        o.vq_nearest({.z = zt, .codebook = cb, .norms = c->vq.code_norms, .M = M, .N = d.n_embed, .E = d.embed_dim, .ws = ws, .idx32 = idx32,
+                      .idx64 = (long long*)indices_out + (size_t)b0 * HW});
         if (quant_out && !o.plan)
             o.check(launch_vq_rows_to_nchw(cb, idx32, quant_out + (size_t)b0 * d.embed_dim * HW, n, HW, d.embed_dim, o.c->stream), "codebook rows to NCHW");
     });

@@ -277,7 +277,52 @@ inline int ensure_gn_partial(rdm_ctx* c, int B) {
 }
 
 // The kernel dispatch of the model executors and of the operator-level entries (rdm_op_*): which kernel runs an op, with which
-// parameters.  Weight and bias arguments are device pointers (executors: o.w<T>(offset) into the model blob).
+// parameters.  Weight and bias operands are device pointers (executors: o.w<T>(offset) into the model blob).  Every op is one struct,
+// filled at the call site by field name; a field a call does not name keeps the default written here (pointers null, counts 0).
+// The fields that IgemmParams also has carry its names and meanings.
+
+// out[M, N] = act(alpha A W^T + bias) (+ rowvec) (+ res), A = [A0 | A1] with K = C0 + C1 columns.  (GEGLU: out has N / 2 columns)
+struct LinearOp {
+    const bf16_t* A0 = nullptr; const bf16_t* A1 = nullptr; int C0 = 0, C1 = 0;
+    const float* ln_x = nullptr; const float* ln_g = nullptr; const float* ln_b = nullptr;      // Ops::linear_ln only: A = LayerNorm(ln_x [M][C0] fp32; ln_g, ln_b), A0 unused
+    const bf16_t* W = nullptr; const float* bias = nullptr;
+    int M = 0, N = 0;
+    int act = ACT_NONE;
+    const bf16_t* res_bf16 = nullptr; const float* res_f32 = nullptr;
+    bf16_t* out_bf16 = nullptr; float* out_f32 = nullptr;
+    const float* rowvec = nullptr; int rowvec_ld = 0, rows_per_sample = 1;      // a per-column add shared by each group of rows_per_sample rows (row stride rowvec_ld)
+    int a1_wrap_rows = 0, res_wrap_rows = 0;                                    // lin4 only (callers ask lin4_takes first): A1 / res_bf16 hold that many rows, row m reads m % rows
+    float alpha = 1.f;                                                          // (the skinny and mid-size kernels take alpha == 1 only)
+    // what the kernel choice reads besides the shape (dispatch.hip: linear_kernel, and the lin4 rule of the deterministic mode):
+    bool single_row = false;     // the operand has ONE row per sample (time embedding, RARM decode step, pooled CLIP token)
+    int sample_rows = 0;         // rows per sample of the operand where the caller knows them (the UNet's blocks), 0 = unknown
+};
+// 3x3 conv over [B, Hin, Win, C0 (+ C1)] NHWC -> [B, Hout, Wout, N]: stride 1 / 2, or ups = 1: on the nearest-2x upsampled input
+struct Conv3Op {
+    const bf16_t* A0 = nullptr; const bf16_t* A1 = nullptr; int C0 = 0, C1 = 0;
+    const bf16_t* W = nullptr; const float* bias = nullptr;
+    int B = 0, Hin = 0, Win = 0, N = 0, stride = 1, ups = 0;
+    const bf16_t* res_bf16 = nullptr; bf16_t* out_bf16 = nullptr;
+    const float* rowvec = nullptr; int rowvec_ld = 0;       // a per-column add per SAMPLE (the time embedding), row stride rowvec_ld
+    int asym = 0;                                           // IgemmParams::asym
+};
+// LayerNorm over rows of C (statistics over the first Clog, the rest zero padding): exactly one x_* and one out_* is given
+struct LayerNormOp {
+    const float* x_f32 = nullptr; const bf16_t* x_bf16 = nullptr;
+    const float* gamma = nullptr; const float* beta = nullptr;
+    int M = 0, C = 0;
+    float* out_f32 = nullptr; bf16_t* out_bf16 = nullptr;
+    int Clog = -1;                                          // -1: = C
+    float eps = 1e-5f;
+};
+// nearest codebook row of every token (vqcode.hip): z f32 [M, E], codebook f32 [N, E], norms = |e_j|^2 (launch_vq_code_norms), ws of
+// vq_nearest_ws_bytes(M, N); first minimum on ties, indices as int32 and / or int64
+struct VqNearestOp {
+    const float* z = nullptr; const float* codebook = nullptr; const float* norms = nullptr;
+    long long M = 0; int N = 0, E = 0;
+    char* ws = nullptr; int* idx32 = nullptr; long long* idx64 = nullptr;
+};
+
 struct Ops {
     rdm_ctx* c; Arena* ar; const char* blob; bool plan; int rc = 0;
     template <typename T> const T* w(size_t off) const { return (const T*)(blob + off); }
@@ -286,52 +331,35 @@ struct Ops {
     void check(hipError_t e, const char* what) {
         if (e != hipSuccess && rc == 0) rc = c->fail(-3, "%s: %s", what, hipGetErrorString(e));
     }
-    IgemmParams base(int M, int N, int K) {
-        IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.ldo = N; p.zero_page = c->zero_page;
-        p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1; return p;
-    }
+    IgemmParams base(int M, int N, int K) const { return igemm_plain(M, N, K, c->zero_page); }
     // Derived weight copies (rdm_ctx::derived_bytes): with constant weights (the executors' blobs; the op entries when their caller promises
     // constant weights) built once per weight and cached in the context, otherwise packed per call into wfrag_tmp.
     // null: the copy could not be made, and the op runs a kernel that reads W itself.
     bool const_weights = true;
     const bf16_t* derived(const bf16_t* W, int N, int K, int kind);
-    bool single_row = false;     // set by callers around ops whose operand has one row per sample (see linear)
-    int rows_hint = 0;           // rows per sample of the operand of the linear ops that follow (0 = unknown); set by the UNet block executors
-    // the dispatch proper (dispatch.hip, documented there)
-    bool skinny(int M, int single_max) const;
-    bool lin4_takes(int M, int N, int C0, int C1, int a1_wrap_rows, int res_wrap_rows = 0);
-    void linear(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int M, int N,
-                int act, const bf16_t* res, bf16_t* out, float* out_f32 = nullptr, const float* res_f32 = nullptr, int a1_wrap_rows = 0,
-                const float* rowvec = nullptr, int rowvec_ld = 0, int rv_rows = 1, int res_wrap_rows = 0, float alpha = 1.f);
-    bool linear_ln(const float* x, const float* g, const float* b, int C, const bf16_t* W, const float* bias, int M, int N, int act, bf16_t* out);
-    void conv3(const bf16_t* A0, const bf16_t* A1, int C0, int C1, const bf16_t* W, const float* bias, int B, int Hin, int Win, int N,
-               int stride, int ups, const float* rowvec, int rowvec_ld, const bf16_t* res, bf16_t* out, int asym = 0);
+    // the dispatch proper (dispatch.hip, documented there).  Nothing that chooses a kernel is state of Ops: it travels in the op.
+    bool lin4_takes(const LinearOp& op);          // reads M, N, C0, C1, a1_wrap_rows, res_wrap_rows
+    void linear(const LinearOp& op);              // (ignores ln_*)
+    bool linear_ln(const LinearOp& op);
+    void conv3(const Conv3Op& op);
     int cur_block = -1, cur_layer = 0;           // position in the UNet's block table (debug tap)
     void tap(int stage, const void* ptr, size_t nbytes);
     bool prof_open = false;
     const char* tag = "";        // role of the ops that follow in the graph ("st.proj_in", "res.conv1", ...): rdm_prof_dump groups by it
     void prof_begin(int kind, double work, int d0 = 0, int d1 = 0, int d2 = 0);
     void prof_end();
-    void groupnorm(const bf16_t* x0, const bf16_t* x1, int C0, int C1, int B, int HW, const float* g, const float* b, float eps, int silu,
-                   bf16_t* out, int L0 = -1, int L1 = -1, int x1_bmod = 0, int x0_bmod = 0);
-    HeadParams head_params(const bf16_t* x, int B, int H, int W, int C, const float* g, const float* b, float eps, const float* wt, const float* bias,
-                           int Cout, float* out, bf16_t* wp) const;
-    void head(const bf16_t* x, int B, int H, int W, int C, int Clog, const float* g, const float* b, float eps, const float* wt, const float* bias, int Cout,
-              float* out, bf16_t* tmp, bf16_t* wp);
-    void vq_nearest(const float* z, const float* cb, const float* norms, long long M, int N, int E, char* ws, int* idx32, long long* idx64);
-    void layernorm(const void* x, int in_f32, const float* g, const float* b, void* out, int out_f32, int M, int C, int Clog = -1, float eps = 1e-5f);
-    void flash_d32(const bf16_t* q, int ldq, const bf16_t* v, const bf16_t* vt, bf16_t* out, int B, int n, int heads);
-    void causal_d64(const bf16_t* qkv, int ldq, bf16_t* out, int ldo, int B, int n, int heads, float scale, bf16_t* kc, bf16_t* vc, int L);
-    void vq_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, const float* bias_v, bf16_t* out, int ldo, int B, int n, int C,
-                      float scale);
-    void small_attention(const bf16_t* q, int ldq, const bf16_t* k, int ldk, const bf16_t* v, int ldv, bf16_t* out, int ldo, int B, int nq, int nkv,
-                         int heads, int D, int causal, float scale, const char* what);
-    static XattnParams xattn_params(int rows, int n, int C, int NP, int ncols, int group) {
-        XattnParams q{}; q.rows = rows; q.n = n; q.C = C; q.NP = NP; q.ncols = ncols; q.group = group; return q;
-    }
-    void xattn_fused(const bf16_t* x, const float* ln_g, const float* ln_b, float ln_eps, const bf16_t* G, const bf16_t* U, const float* bias,
-                     const bf16_t* res, bf16_t* out, int rows, int n, int C, int NP, int ncols, int group,
-                     const float* ln3_g = nullptr, const float* ln3_b = nullptr, bf16_t* ln3_out = nullptr);
+    // The ops below take their kernel's own parameter struct (kernels.h) with the caller's fields named; the dispatch fills in what it
+    // owns: groups, nchunk, partial (GroupNorm, head), k = q + C and the strides that follow from it (flash), scale_log2e.
+    void groupnorm(GnParams p);
+    HeadParams head_params(HeadParams hp) const;
+    void head(HeadParams hp, int Clog = 0, bf16_t* tmp = nullptr);      // Clog: logical channels of x (0: = C); tmp [B, H, W, C]: needed only where the fused kernel does not apply
+    void vq_nearest(const VqNearestOp& op);
+    void layernorm(const LayerNormOp& op);
+    void flash_d32(FlashParams f, int heads, int B);
+    void causal_d64(CausalD64Params f, int heads, int B, float scale);
+    void vq_attention(const VqAttnParams& f, int B);
+    void small_attention(const SmallAttnParams& p, int D, int heads, int B, const char* what);
+    void xattn_fused(const XattnParams& q);
 };
 
 // plan (count bytes) -> ensure arena -> run

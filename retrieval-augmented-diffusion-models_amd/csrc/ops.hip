@@ -11,30 +11,29 @@ static Ops op_exec(rdm_ctx* c) {
     o.const_weights = cache;
     return o;
 }
-static int op_linear(rdm_ctx* c, const void* a, const void* w, const float* bias, const void* res, void* out, float* out_f32,
-                     int M, int N, int K, int act, float alpha, const float* rowvec, int rows_per_group) {
-    Ops o = op_exec(c);
-    o.linear((const bf16_t*)a, nullptr, K, 0, (const bf16_t*)w, bias, M, N, act, (const bf16_t*)res, (bf16_t*)out, out_f32, nullptr, 0,
-             rowvec, N, rows_per_group, 0, alpha);
-    return o.rc;
-}
 int rdm_op_linear(rdm_ctx* c, const void* a, const void* w, const float* bias, const void* res, void* out, float* out_f32,
                   int M, int N, int K, int act, float alpha) {
     RDM_ENTER(c);
-    return op_linear(c, a, w, bias, res, out, out_f32, M, N, K, act, alpha, nullptr, 1);
+    Ops o = op_exec(c);
+    o.linear({.A0 = (const bf16_t*)a, .C0 = K, .W = (const bf16_t*)w, .bias = bias, .M = M, .N = N, .act = act, .res_bf16 = (const bf16_t*)res,
+              .out_bf16 = (bf16_t*)out, .out_f32 = out_f32, .alpha = alpha});
+    return o.rc;
 }
 int rdm_op_linear_rowvec(rdm_ctx* c, const void* a, const void* w, const float* bias, const float* rowvec, int rows_per_group, const void* res,
-                         void* out, int M, int N, int K) {
+                         void* out, int M, int N, int K) {      // rows_per_group: LinearOp's (and IgemmParams') rows_per_sample
     RDM_ENTER(c);
     if (!rowvec || rows_per_group < 1) return c->fail(-1, "rdm_op_linear_rowvec: rowvec and rows_per_group >= 1 required");
-    return op_linear(c, a, w, bias, res, out, nullptr, M, N, K, ACT_NONE, 1.0f, rowvec, rows_per_group);
+    Ops o = op_exec(c);
+    o.linear({.A0 = (const bf16_t*)a, .C0 = K, .W = (const bf16_t*)w, .bias = bias, .M = M, .N = N, .res_bf16 = (const bf16_t*)res, .out_bf16 = (bf16_t*)out,
+              .rowvec = rowvec, .rowvec_ld = N, .rows_per_sample = rows_per_group});
+    return o.rc;
 }
 int rdm_op_linear_ln(rdm_ctx* c, const void* x, const void* w, const float* bias, const float* gamma, const float* beta, void* out,
                      int M, int N, int K, int act, float eps) {
     RDM_ENTER(c);
     if (!x || !w || !gamma || !beta || !out) return c->fail(-1, "rdm_op_linear_ln: null argument");
-    IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = 1.f; p.ldo = (act == ACT_GEGLU) ? N / 2 : N; p.zero_page = c->zero_page;
-    p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1;
+    IgemmParams p = igemm_plain(M, N, K, c->zero_page);
+    if (act == ACT_GEGLU) p.ldo = N / 2;
     p.A0 = (const bf16_t*)x; p.C0 = K; p.W = (const bf16_t*)w; p.out_bf16 = (bf16_t*)out; p.act = act; p.l4_any_tiles = 1;
     p.ln_inv_c = 1.0f / (float)K; p.ln_eps = eps;
     IgemmParams t = p; t.Wfrag = p.W; t.ln_sb = gamma;
@@ -54,8 +53,8 @@ int rdm_op_conv3x3(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, c
                    int ups) {
     RDM_ENTER(c);
     Ops o = op_exec(c);
-    o.conv3((const bf16_t*)x0, (const bf16_t*)x1, C0, C1, (const bf16_t*)w, bias, B, Hin, Win, N, stride, ups, rowvec, rowvec_ld,
-            (const bf16_t*)res, (bf16_t*)out);
+    o.conv3({.A0 = (const bf16_t*)x0, .A1 = (const bf16_t*)x1, .C0 = C0, .C1 = C1, .W = (const bf16_t*)w, .bias = bias, .B = B, .Hin = Hin, .Win = Win, .N = N,
+             .stride = stride, .ups = ups, .res_bf16 = (const bf16_t*)res, .out_bf16 = (bf16_t*)out, .rowvec = rowvec, .rowvec_ld = rowvec_ld});
     return o.rc;
 }
 // the nearest-code kernel alone on caller-given operands (vqcode.hip): |e|^2 and the split planes live in the sampler scratch
@@ -68,7 +67,7 @@ int rdm_op_vq_nearest_code(rdm_ctx* c, const float* z, const float* codebook, lo
     float* norms = (float*)c->samp;
     RDM_CHECK_HIP(c, launch_vq_code_norms(codebook, norms, N, E, c->stream));
     Ops o = op_exec(c);
-    o.vq_nearest(z, codebook, norms, M, N, E, c->samp + nbytes, idx_out, nullptr);
+    o.vq_nearest({.z = z, .codebook = codebook, .norms = norms, .M = M, .N = N, .E = E, .ws = c->samp + nbytes, .idx32 = idx_out});
     return o.rc;
 }
 // ---- backward ops (kernels in backward.hip)
@@ -263,9 +262,8 @@ int rdm_op_bmm(rdm_ctx* c, const void* a, const void* w, void* out_bf16, float* 
     RDM_ENTER(c);
     if (!a || !w || (!out_bf16 && !out_f32) || batch < 1 || M < 1 || N < 2 || K < 64 || K % 64 || N % 2)
         return c->fail(-1, "rdm_op_bmm: bad argument (K must be a multiple of 64, N even)");
-    IgemmParams p{}; p.M = M; p.N = N; p.K = K; p.alpha = alpha; p.ldo = N; p.zero_page = c->zero_page;
-    p.Hin = p.Win = p.Hout = p.Wout = 1; p.stride = 1; p.rows_per_sample = 1;
-    p.A0 = (const bf16_t*)a; p.C0 = K; p.W = (const bf16_t*)w; p.out_bf16 = (bf16_t*)out_bf16; p.out_f32 = out_f32;
+    IgemmParams p = igemm_plain(M, N, K, c->zero_page);
+    p.alpha = alpha; p.A0 = (const bf16_t*)a; p.C0 = K; p.W = (const bf16_t*)w; p.out_bf16 = (bf16_t*)out_bf16; p.out_f32 = out_f32;
     p.sA = (long long)M * K; p.sW = (long long)N * K; p.sO = (long long)M * N;
     RDM_CHECK_HIP(c, launch_igemm(p, false, batch, c->stream));
     return 0;
@@ -311,55 +309,60 @@ int rdm_op_groupnorm(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1,
     RDM_ENTER(c);
     RDM_TRY(ensure_gn_partial(c, B));
     Ops o = op_exec(c);
-    o.groupnorm((const bf16_t*)x0, (const bf16_t*)x1, C0, C1, B, HW, gamma, beta, eps, silu, (bf16_t*)out);
+    o.groupnorm({.x0 = (const bf16_t*)x0, .x1 = (const bf16_t*)x1, .C0 = C0, .C1 = C1, .HW = HW, .B = B, .gamma = gamma, .beta = beta, .eps = eps, .silu = silu,
+                 .out = (bf16_t*)out});
     return o.rc;
 }
 int rdm_op_layernorm(rdm_ctx* c, const void* x, int in_is_f32, const float* gamma, const float* beta, int M, int C, float eps,
                      void* out) {
     RDM_ENTER(c);
     Ops o = op_exec(c);
-    o.layernorm(x, in_is_f32, gamma, beta, out, 0, M, C, -1, eps);
+    o.layernorm({.x_f32 = in_is_f32 ? (const float*)x : nullptr, .x_bf16 = in_is_f32 ? nullptr : (const bf16_t*)x, .gamma = gamma, .beta = beta, .M = M, .C = C,
+                 .out_bf16 = (bf16_t*)out, .eps = eps});
     return o.rc;
 }
 int rdm_op_self_attention(rdm_ctx* c, const void* qk, const void* vt, int B, int n, int heads, void* out) {
     RDM_ENTER(c);
     Ops o = op_exec(c);
-    o.flash_d32((const bf16_t*)qk, 2 * heads * 32, nullptr, (const bf16_t*)vt, (bf16_t*)out, B, n, heads);
+    o.flash_d32({.q = (const bf16_t*)qk, .ldq = 2 * heads * 32, .vt = (const bf16_t*)vt, .out = (bf16_t*)out, .n = n}, heads, B);
     return o.rc;
 }
 int rdm_op_self_attention_qkv(rdm_ctx* c, const void* qkv, int B, int n, int heads, void* out) {
     RDM_ENTER(c);
     if (n % 64 != 0) return c->fail(-3, "rdm_op_self_attention_qkv: n = %d must be a multiple of 64 (token-major V is read by the LDS-shared kernel only)", n);
     Ops o = op_exec(c);
-    o.flash_d32((const bf16_t*)qkv, 3 * heads * 32, (const bf16_t*)qkv + 2 * heads * 32, nullptr, (bf16_t*)out, B, n, heads);
+    o.flash_d32({.q = (const bf16_t*)qkv, .ldq = 3 * heads * 32, .v = (const bf16_t*)qkv + 2 * heads * 32, .out = (bf16_t*)out, .n = n}, heads, B);
     return o.rc;
 }
 // G / U arrive in their natural layout: their fragment-ordered images are packed per call into bwd_tmp
-static int op_xattn_fused(rdm_ctx* c, const void* x, const float* ln_g, const float* ln_b, float ln_eps, const void* G, const void* U,
-                          const float* bias, const void* res, void* out, int B, int n, int C, int NP, int ncols, int group,
-                          const float* ln3_g, const float* ln3_b, void* ln3_out) {
-    const size_t img = (size_t)B * NP * C;
+static int op_xattn_fused(rdm_ctx* c, XattnParams q, int B) {      // q.G / q.U: the natural layout
+    const size_t img = (size_t)B * q.NP * q.C;
     RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, 2 * img * 2));
     bf16_t* Gp = (bf16_t*)c->bwd_tmp; bf16_t* Up = Gp + img;
     Ops o = op_exec(c);
-    o.check(launch_xattn_pack((const bf16_t*)G, (const bf16_t*)U, Gp, Up, B, NP, C, c->stream), "xattn pack");
-    o.xattn_fused((const bf16_t*)x, ln_g, ln_b, ln_eps, Gp, Up, bias, (const bf16_t*)res, (bf16_t*)out, B * n, n, C, NP, ncols, group,
-                  ln3_g, ln3_b, (bf16_t*)ln3_out);
+    o.check(launch_xattn_pack(q.G, q.U, Gp, Up, B, q.NP, q.C, c->stream), "xattn pack");
+    q.G = Gp; q.U = Up;
+    o.xattn_fused(q);
     return o.rc;
 }
 int rdm_op_xattn_fused(rdm_ctx* c, const void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G, const void* U,
                        const float* bias, const void* res, int B, int n, int C, int NP, int ncols, int group, void* out) {
     RDM_ENTER(c);
     if ((ln_gamma != nullptr) != (ln_beta != nullptr) || (ln_gamma && res)) return c->fail(-3, "rdm_op_xattn_fused: LayerNorm needs gamma and beta, and then the residual is x itself (res must be null)");
-    if (!xattn_fused_supported(Ops::xattn_params(B * n, n, C, NP, ncols, group))) return c->fail(-3, "rdm_op_xattn_fused: unsupported shape (n %% 32, C %% 64, NP %% 32, ncols <= min(NP, 128), group 1 / 2 / 4): n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
-    return op_xattn_fused(c, x, ln_gamma, ln_beta, ln_eps, G, U, bias, res, out, B, n, C, NP, ncols, group, nullptr, nullptr, nullptr);
+    const XattnParams q{.x = (const bf16_t*)x, .G = (const bf16_t*)G, .U = (const bf16_t*)U, .bias = bias, .res = (const bf16_t*)res, .out = (bf16_t*)out,
+                        .rows = B * n, .n = n, .C = C, .NP = NP, .ncols = ncols, .group = group, .ln_g = ln_gamma, .ln_b = ln_beta, .ln_eps = ln_eps};
+    if (!xattn_fused_supported(q)) return c->fail(-3, "rdm_op_xattn_fused: unsupported shape (n %% 32, C %% 64, NP %% 32, ncols <= min(NP, 128), group 1 / 2 / 4): n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
+    return op_xattn_fused(c, q, B);
 }
 int rdm_op_xattn_fused_ln3(rdm_ctx* c, void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G, const void* U,
                            const float* bias, int B, int n, int C, int NP, int ncols, int group, const float* ln3_gamma, const float* ln3_beta, void* ln3_out) {
     RDM_ENTER(c);
     if (!x || !ln_gamma || !ln_beta || !ln3_gamma || !ln3_beta || !ln3_out) return c->fail(-1, "rdm_op_xattn_fused_ln3: null argument");
-    if (!xattn_fused_supported(Ops::xattn_params(B * n, n, C, NP, ncols, group))) return c->fail(-3, "rdm_op_xattn_fused_ln3: unsupported shape: n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
-    return op_xattn_fused(c, x, ln_gamma, ln_beta, ln_eps, G, U, bias, nullptr, x, B, n, C, NP, ncols, group, ln3_gamma, ln3_beta, ln3_out);
+    const XattnParams q{.x = (const bf16_t*)x, .G = (const bf16_t*)G, .U = (const bf16_t*)U, .bias = bias, .out = (bf16_t*)x,
+                        .rows = B * n, .n = n, .C = C, .NP = NP, .ncols = ncols, .group = group, .ln_g = ln_gamma, .ln_b = ln_beta, .ln_eps = ln_eps,
+                        .ln3_g = ln3_gamma, .ln3_b = ln3_beta, .ln3_out = (bf16_t*)ln3_out};
+    if (!xattn_fused_supported(q)) return c->fail(-3, "rdm_op_xattn_fused_ln3: unsupported shape: n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
+    return op_xattn_fused(c, q, B);
 }
 int rdm_op_head_conv(rdm_ctx* c, const void* x, const float* gn_gamma, const float* gn_beta, float gn_eps, const float* w, const float* bias,
                      int B, int H, int W, int C, int Cout, float* out) {
@@ -367,10 +370,12 @@ int rdm_op_head_conv(rdm_ctx* c, const void* x, const float* gn_gamma, const flo
     if ((gn_gamma != nullptr) != (gn_beta != nullptr)) return c->fail(-3, "rdm_op_head_conv: GroupNorm needs gamma and beta");
     if (gn_gamma) RDM_TRY(ensure_gn_partial(c, B));
     Ops o = op_exec(c);
-    if (!head_conv_supported(o.head_params((const bf16_t*)x, B, H, W, C, gn_gamma, gn_beta, gn_eps, w, bias, Cout, out, nullptr)))
+    HeadParams hp{.x = (const bf16_t*)x, .B = B, .H = H, .W = W, .C = C, .gamma = gn_gamma, .beta = gn_beta, .eps = gn_eps, .w = w, .bias = bias, .out = out, .Cout = Cout};
+    if (!head_conv_supported(o.head_params(hp)))
         return c->fail(-3, "rdm_op_head_conv: unsupported shape (C %% 32, C <= 240, W %% 32, H %% 2, Cout <= 8, C %% 32 groups): C %d H %d W %d Cout %d", C, H, W, Cout);
     RDM_TRY(ensure_bytes(c, &c->bwd_tmp, &c->bwd_tmp_bytes, head_conv_wp_bytes(C)));
-    o.head((const bf16_t*)x, B, H, W, C, C, gn_gamma, gn_beta, gn_eps, w, bias, Cout, out, nullptr, (bf16_t*)c->bwd_tmp);
+    hp.wp = (bf16_t*)c->bwd_tmp;
+    o.head(hp);             // (the fused kernel takes it: no GroupNorm-apply scratch)
     return o.rc;
 }
 int rdm_op_causal_attention_d64(rdm_ctx* c, const void* qkv, int ldq, int B, int n, int heads, float scale, void* out, int ldo, void* kcache,
@@ -381,7 +386,8 @@ int rdm_op_causal_attention_d64(rdm_ctx* c, const void* qkv, int ldq, int B, int
     if ((kcache != nullptr) != (vcache != nullptr) || (kcache && L < n))
         return c->fail(-1, "rdm_op_causal_attention_d64: kcache and vcache come together, with L >= n (L=%d, n=%d)", L, n);
     Ops o = op_exec(c);
-    o.causal_d64((const bf16_t*)qkv, ldq, (bf16_t*)out, ldo, B, n, heads, scale, (bf16_t*)kcache, (bf16_t*)vcache, L);
+    o.causal_d64({.qkv = (const bf16_t*)qkv, .ldq = ldq, .out = (bf16_t*)out, .ldo = ldo, .n = n, .kcache = (bf16_t*)kcache, .vcache = (bf16_t*)vcache, .L = L},
+                 heads, B, scale);
     return o.rc;
 }
 int rdm_op_vq_attention(rdm_ctx* c, const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, const float* bias_v, int B, int n, int C, float scale,
@@ -396,7 +402,8 @@ int rdm_op_vq_attention(rdm_ctx* c, const void* q, int ldq, const void* k, int l
         return c->fail(-1, "rdm_op_vq_attention: q, k and v must be 16-byte aligned, out 8-byte aligned");
     if ((long long)B * ((n + 63) / 64) > 0x7fffffffLL) return c->fail(-1, "rdm_op_vq_attention: B=%d x n=%d is more than one launch takes", B, n);
     Ops o = op_exec(c);
-    o.vq_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldk, (const bf16_t*)v, ldv, bias_v, (bf16_t*)out, ldo, B, n, C, scale);
+    o.vq_attention({.q = (const bf16_t*)q, .ldq = ldq, .k = (const bf16_t*)k, .ldk = ldk, .v = (const bf16_t*)v, .ldv = ldv, .bias = bias_v, .out = (bf16_t*)out, .ldo = ldo,
+                    .n = n, .C = C, .scale = scale}, B);
     return o.rc;
 }
 int rdm_op_causal_attention_d64_bwd(rdm_ctx* c, const void* qkv, int ldq, const void* out, int ldo, const void* dout, int lddo, int B, int n, int heads,
@@ -424,8 +431,8 @@ int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, co
                            int heads, int D, int causal, float scale, void* out, int ldo) {
     RDM_ENTER(c);
     Ops o = op_exec(c);
-    o.small_attention((const bf16_t*)q, ldq, (const bf16_t*)k, ldkv, (const bf16_t*)v, ldkv, (bf16_t*)out, ldo, B, nq, nkv, heads, D, causal, scale,
-                      "small attention");
+    o.small_attention({.q = (const bf16_t*)q, .ldq = ldq, .k = (const bf16_t*)k, .ldk = ldkv, .v = (const bf16_t*)v, .ldv = ldkv, .out = (bf16_t*)out, .ldo = ldo,
+                       .nq = nq, .nkv = nkv, .causal = causal, .scale = scale}, D, heads, B, "small attention");
     return o.rc;
 }
 int rdm_op_conv_in(rdm_ctx* c, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, void* out) {
@@ -479,15 +486,16 @@ int rdm_op_linear_rows(rdm_ctx* c, const void* a, const float* ln_x, const float
     if (M < 1 || N < 1 || K < 8 || K % 8 || act < ACT_NONE || act > ACT_SILU || (act == ACT_GEGLU && N % 2))
         return c->fail(-1, "rdm_op_linear_rows: bad shape M=%d N=%d K=%d act=%d (K a multiple of 8; GEGLU: N even)", M, N, K, act);
     Ops o = op_exec(c);
-    o.single_row = true;
+    const LinearOp op{.A0 = (const bf16_t*)a, .C0 = K, .ln_x = ln_x, .ln_g = gamma, .ln_b = beta, .W = (const bf16_t*)w, .bias = bias, .M = M, .N = N, .act = act,
+                      .res_f32 = res_f32, .out_bf16 = (bf16_t*)out_bf16, .out_f32 = out_f32, .single_row = true};
     if (ln_x) {
         if (!gamma || !beta || !out_bf16 || out_f32 || res_f32) return c->fail(-1, "rdm_op_linear_rows: the LayerNorm form takes gamma, beta and a bf16 output, no residual");
-        if (!o.linear_ln(ln_x, gamma, beta, K, (const bf16_t*)w, bias, M, N, act, (bf16_t*)out_bf16))
+        if (!o.linear_ln(op))
             return c->fail(-5, "rdm_op_linear_rows: shape not taken by the LayerNorm-in-kernel form (M=%d N=%d K=%d act=%d, %s mode)", M, N, K, act,
                            c->deterministic ? "deterministic" : "fast");
         return o.rc;
     }
-    o.linear((const bf16_t*)a, nullptr, K, 0, (const bf16_t*)w, bias, M, N, act, nullptr, (bf16_t*)out_bf16, out_f32, res_f32);
+    o.linear(op);
     return o.rc;
 }
 static int op_pos_slot(rdm_ctx* c, int pos, int** slot) {      // the device step counter of the decode kernels, set on the stream

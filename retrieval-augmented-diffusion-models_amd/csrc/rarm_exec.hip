@@ -37,7 +37,7 @@ static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,c
     return run_with_arena(c, m.arena, m.blob, [&](Ops& o) {
         bf16_t* cb = o.abf((size_t)B * k * g.context_dim);
         if (!o.plan) o.check(launch_cast_f32_bf16(context, cb, (long long)B * k * g.context_dim, c->stream), "cast ctx");
-        o.linear(cb, nullptr, g.context_dim, 0, o.w<bf16_t>(m.kvw), nullptr, B * k, m.kv_total, ACT_NONE, nullptr, (bf16_t*)m.ctxkv);
+        o.linear({.A0 = cb, .C0 = g.context_dim, .W = o.w<bf16_t>(m.kvw), .M = B * k, .N = m.kv_total, .out_bf16 = (bf16_t*)m.ctxkv});
         // the decode step's cross-attention re-associated per sequence (rarm.hip: rarm_xattn_decode_kernel):
         //   G_l[b][(h,j)][:] = (K_bj restricted to head h) W_q / sqrt(d),   UT_l[b][(h,j)][:] = W_o (V_bj restricted to head h)
         if (fuse) {
@@ -67,19 +67,25 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
     RarmModel& m = c->rarm; const rdm_rarm_cfg& g = m.cfg; const int C = m.C, L = g.sequence_length;
     RarmState st = rarm_state(m, B2);
     return run_with_arena(c, m.arena, m.blob, [&](Ops& o) {
-        o.single_row = true;                              // a decode step is one row per sequence throughout
         float* x = o.af32((size_t)B2 * C);
         bf16_t* ln = o.abf((size_t)B2 * C); bf16_t* qkv = o.abf((size_t)B2 * 3 * C); bf16_t* ao = o.abf((size_t)B2 * C);
         bf16_t* q2 = o.abf((size_t)B2 * C); bf16_t* ff = o.abf((size_t)B2 * 4 * C);
+        // a decode step is one row per sequence throughout: every projection of the step is B2 single_row rows
+        auto lin = [&](LinearOp op) { op.M = B2; op.single_row = true; o.linear(op); };
+        // a projection of LayerNorm(x; g, b): formed inside the skinny GEMM where that takes the shape, else as a pass into `ln` of its own
+        auto ln_lin = [&](const float* g, const float* b, LinearOp op) {
+            op.ln_x = x; op.ln_g = g; op.ln_b = b; op.C0 = C; op.M = B2; op.single_row = true;
+            if (o.linear_ln(op)) return;
+            o.layernorm({.x_f32 = x, .gamma = g, .beta = b, .M = B2, .C = C, .out_bf16 = ln});
+            op.A0 = ln;
+            o.linear(op);
+        };
         if (!o.plan) o.check(launch_rarm_embed(st.tokens, o.w<float>(m.emb), o.w<float>(m.pos), st.pos, x, B2, C, g.vocab_in, c->stream), "rarm embed");
         const float scale = 1.0f / sqrtf((float)g.d_head);
         const bool ln3_fused = m.xa_B > 0 && m.xa_k == k;      // the fused cross-attention kernel also emits norm3 of its output rows
         for (int l = 0; l < g.depth; l++) {
             const RarmBlk& b = m.blk[l];
-            if (!o.linear_ln(x, o.w<float>(b.ln1g), o.w<float>(b.ln1b), C, o.w<bf16_t>(b.wqkv), nullptr, B2, 3 * C, ACT_NONE, qkv)) {
-                o.layernorm(x, 1, o.w<float>(b.ln1g), o.w<float>(b.ln1b), ln, 0, B2, C);
-                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wqkv), nullptr, B2, 3 * C, ACT_NONE, nullptr, qkv);
-            }
+            ln_lin(o.w<float>(b.ln1g), o.w<float>(b.ln1b), {.W = o.w<bf16_t>(b.wqkv), .N = 3 * C, .out_bf16 = qkv});
             if (!o.plan) {
                 RarmAttnParams p{}; p.q = qkv; p.ldq = 3 * C; p.k_new = qkv + C; p.v_new = qkv + 2 * C;
                 p.Kc = (bf16_t*)m.cache + ((size_t)l * 2) * B2 * L * C; p.Vc = (bf16_t*)m.cache + ((size_t)l * 2 + 1) * B2 * L * C;
@@ -93,7 +99,7 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
                 o.check(launch_rarm_decode_attention(p, g.n_heads, B2, c->stream), "rarm self attention");
                 o.prof_end();
             }
-            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo1), o.w<float>(b.bo1), B2, C, ACT_NONE, nullptr, nullptr, x, x);
+            lin({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo1), .bias = o.w<float>(b.bo1), .N = C, .res_f32 = x, .out_f32 = x});
             if (m.xa_B > 0 && m.xa_k == k) {      // norm2 + to_q + attention over the neighbours + to_out + residual in one launch
                 if (!o.plan) {
                     RarmXattnParams xp{}; xp.x = x; xp.ln_g = o.w<float>(b.ln2g); xp.ln_b = o.w<float>(b.ln2b); xp.ln_eps = 1e-5f;
@@ -103,27 +109,23 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
                     o.check(launch_rarm_xattn_decode(xp, c->stream), "rarm fused cross attention");
                 }
             } else {
-            if (!o.linear_ln(x, o.w<float>(b.ln2g), o.w<float>(b.ln2b), C, o.w<bf16_t>(b.wq2), nullptr, B2, C, ACT_NONE, q2)) {
-                o.layernorm(x, 1, o.w<float>(b.ln2g), o.w<float>(b.ln2b), ln, 0, B2, C);
-                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wq2), nullptr, B2, C, ACT_NONE, nullptr, q2);
-            }
+            ln_lin(o.w<float>(b.ln2g), o.w<float>(b.ln2b), {.W = o.w<bf16_t>(b.wq2), .N = C, .out_bf16 = q2});
             if (!o.plan) {
                 RarmAttnParams p{}; p.q = q2; p.ldq = C; p.Kc = (bf16_t*)m.ctxkv + (size_t)l * 2 * C; p.Vc = (bf16_t*)m.ctxkv + (size_t)l * 2 * C + C;
                 p.batch_stride = (long long)k * m.kv_total; p.row_stride = m.kv_total; p.nkv = k; p.scale = scale; p.out = ao; p.ldo = C;
                 o.check(launch_rarm_decode_attention(p, g.n_heads, B2, c->stream), "rarm cross attention");
             }
-            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo2), o.w<float>(b.bo2), B2, C, ACT_NONE, nullptr, nullptr, x, x);
+            lin({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo2), .bias = o.w<float>(b.bo2), .N = C, .res_f32 = x, .out_f32 = x});
             }
+            const LinearOp geglu{.W = o.w<bf16_t>(b.wff1), .bias = o.w<float>(b.bff1), .N = 8 * C, .act = ACT_GEGLU, .out_bf16 = ff};
             if (ln3_fused) {      // norm3 left the cross-attention kernel with the finished rows: a plain GEGLU GEMM on the bf16 operand
-                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), B2, 8 * C, ACT_GEGLU, nullptr, ff);
-            } else if (!o.linear_ln(x, o.w<float>(b.ln3g), o.w<float>(b.ln3b), C, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), B2, 8 * C, ACT_GEGLU, ff)) {
-                o.layernorm(x, 1, o.w<float>(b.ln3g), o.w<float>(b.ln3b), ln, 0, B2, C);
-                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), B2, 8 * C, ACT_GEGLU, nullptr, ff);
-            }
-            o.linear(ff, nullptr, 4 * C, 0, o.w<bf16_t>(b.wff2), o.w<float>(b.bff2), B2, C, ACT_NONE, nullptr, nullptr, x, x);
+                LinearOp op = geglu; op.A0 = ln; op.C0 = C;
+                lin(op);
+            } else ln_lin(o.w<float>(b.ln3g), o.w<float>(b.ln3b), geglu);
+            lin({.A0 = ff, .C0 = 4 * C, .W = o.w<bf16_t>(b.wff2), .bias = o.w<float>(b.bff2), .N = C, .res_f32 = x, .out_f32 = x});
         }
         if (!o.plan) o.check(launch_cast_f32_bf16(x, ln, (long long)B2 * C, c->stream), "cast x");
-        o.linear(ln, nullptr, C, 0, o.w<bf16_t>(m.wpo), o.w<float>(m.bpo), B2, g.vocab_out, ACT_NONE, nullptr, nullptr, st.logits);
+        lin({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(m.wpo), .bias = o.w<float>(m.bpo), .N = g.vocab_out, .out_f32 = st.logits});
     });
 }
 static int rarm_check(rdm_ctx* c, int b, int k, int positions) {
@@ -141,7 +143,7 @@ static int rarm_set_tokens(rdm_ctx* c, RarmState& st, const int64_t* tokens, int
     return 0;
 }
 // ---- the whole-sequence pass: RetrievalPatchTransformer.forward over all t positions of B2 sequences at once (attention.py:252-272),
-// the transformer of rarm_step with t rows per sequence -- tiled GEMMs (single_row stays false: no kernel on this path is chosen by the
+// the transformer of rarm_step with t rows per sequence -- tiled GEMMs (no op here is single_row: no kernel on this path is chosen by the
 // row count in deterministic mode), the causal d_head-64 kernel over the sequence itself, small_attention over its k neighbour rows of
 // ctxkv (rarm_prepare; the zeroed rows of a guided batch's unconditional half give zero attention output, as in the decode step).
 // Sequences are independent, so they are walked in ranges of whole sequences of at most RARM_SEQ_ROWS rows: that bounds the [rows, 4C]
@@ -171,30 +173,31 @@ static int rarm_seq_body(rdm_ctx* c, const int64_t* tokens, int tok_ld, int tok_
                     "rarm embed");
             for (int l = 0; l < g.depth; l++) {
                 const RarmBlk& b = m.blk[l];
-                o.layernorm(x, 1, o.w<float>(b.ln1g), o.w<float>(b.ln1b), ln, 0, M, C);
-                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wqkv), nullptr, M, 3 * C, ACT_NONE, nullptr, qkv);
+                o.layernorm({.x_f32 = x, .gamma = o.w<float>(b.ln1g), .beta = o.w<float>(b.ln1b), .M = M, .C = C, .out_bf16 = ln});
+                o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(b.wqkv), .M = M, .N = 3 * C, .out_bf16 = qkv});
                 bf16_t* kc = fill_cache ? (bf16_t*)m.cache + (((size_t)l * 2) * B2 + s0) * L * C : nullptr;
                 bf16_t* vc = fill_cache ? (bf16_t*)m.cache + (((size_t)l * 2 + 1) * B2 + s0) * L * C : nullptr;
                 o.tag = "rarm.causal_attention";
-                o.causal_d64(qkv, 3 * C, ao, C, nb, t, g.n_heads, scale, kc, vc, L);
-                o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo1), o.w<float>(b.bo1), M, C, ACT_NONE, nullptr, nullptr, x, x);
-                o.layernorm(x, 1, o.w<float>(b.ln2g), o.w<float>(b.ln2b), ln, 0, M, C);
-                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wq2), nullptr, M, C, ACT_NONE, nullptr, q2);
+                o.causal_d64({.qkv = qkv, .ldq = 3 * C, .out = ao, .ldo = C, .n = t, .kcache = kc, .vcache = vc, .L = L}, g.n_heads, nb, scale);
+                o.linear({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo1), .bias = o.w<float>(b.bo1), .M = M, .N = C, .res_f32 = x, .out_f32 = x});
+                o.layernorm({.x_f32 = x, .gamma = o.w<float>(b.ln2g), .beta = o.w<float>(b.ln2b), .M = M, .C = C, .out_bf16 = ln});
+                o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(b.wq2), .M = M, .N = C, .out_bf16 = q2});
                 const bf16_t* kv = (const bf16_t*)m.ctxkv + (size_t)s0 * k * m.kv_total + (size_t)l * 2 * C;
-                o.small_attention(q2, C, kv, m.kv_total, kv + C, m.kv_total, ao, C, nb, t, k, g.n_heads, g.d_head, 0, scale, "rarm cross attention");
-                o.linear(ao, nullptr, C, 0, o.w<bf16_t>(b.wo2), o.w<float>(b.bo2), M, C, ACT_NONE, nullptr, nullptr, x, x);
-                o.layernorm(x, 1, o.w<float>(b.ln3g), o.w<float>(b.ln3b), ln, 0, M, C);
-                o.linear(ln, nullptr, C, 0, o.w<bf16_t>(b.wff1), o.w<float>(b.bff1), M, 8 * C, ACT_GEGLU, nullptr, ff);
-                o.linear(ff, nullptr, 4 * C, 0, o.w<bf16_t>(b.wff2), o.w<float>(b.bff2), M, C, ACT_NONE, nullptr, nullptr, x, x);
+                o.small_attention({.q = q2, .ldq = C, .k = kv, .ldk = m.kv_total, .v = kv + C, .ldv = m.kv_total, .out = ao, .ldo = C, .nq = t, .nkv = k, .scale = scale},
+                                  g.d_head, g.n_heads, nb, "rarm cross attention");
+                o.linear({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo2), .bias = o.w<float>(b.bo2), .M = M, .N = C, .res_f32 = x, .out_f32 = x});
+                o.layernorm({.x_f32 = x, .gamma = o.w<float>(b.ln3g), .beta = o.w<float>(b.ln3b), .M = M, .C = C, .out_bf16 = ln});
+                o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(b.wff1), .bias = o.w<float>(b.bff1), .M = M, .N = 8 * C, .act = ACT_GEGLU, .out_bf16 = ff});
+                o.linear({.A0 = ff, .C0 = 4 * C, .W = o.w<bf16_t>(b.wff2), .bias = o.w<float>(b.bff2), .M = M, .N = C, .res_f32 = x, .out_f32 = x});
             }
             if (!logits_out && !nll_out) continue;
             o.check(launch_cast_f32_bf16(x, ln, (long long)M * C, c->stream), "cast x");
             const size_t row0 = (size_t)s0 * t;
-            if (logits_out) o.linear(ln, nullptr, C, 0, o.w<bf16_t>(m.wpo), o.w<float>(m.bpo), M, V, ACT_NONE, nullptr, nullptr, logits_out + row0 * V);
+            if (logits_out) o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(m.wpo), .bias = o.w<float>(m.bpo), .M = M, .N = V, .out_f32 = logits_out + row0 * V});
             if (nll_out) {
                 for (int r0 = 0; r0 < M && o.rc == 0; r0 += RARM_NLL_ROWS) {
                     const int nr = M - r0 < RARM_NLL_ROWS ? M - r0 : RARM_NLL_ROWS;
-                    o.linear(ln + (size_t)r0 * C, nullptr, C, 0, o.w<bf16_t>(m.wpo), o.w<float>(m.bpo), nr, V, ACT_NONE, nullptr, nullptr, lg);
+                    o.linear({.A0 = ln + (size_t)r0 * C, .C0 = C, .W = o.w<bf16_t>(m.wpo), .bias = o.w<float>(m.bpo), .M = nr, .N = V, .out_f32 = lg});
                     o.check(launch_rarm_nll(lg, nr, V, (const long long*)targets + row0 + r0, nll_out + row0 + r0, c->stream), "rarm nll");
                 }
             }

@@ -19,7 +19,7 @@ static void unet_compute_kv(Ops& o, UNet& u, const float* context, int B, int k,
     const int cd = u.cfg.context_dim;
     bf16_t* cb = o.abf((size_t)B * k * cd);
     if (!o.plan) o.check(launch_cast_f32_bf16(context, cb, (long long)B * k * cd, o.c->stream), "cast ctx");
-    o.linear(cb, nullptr, cd, 0, o.w<bf16_t>(u.kvw), nullptr, B * k, u.kv_total, ACT_NONE, nullptr, kv_out);
+    o.linear({.A0 = cb, .C0 = cd, .W = o.w<bf16_t>(u.kvw), .M = B * k, .N = u.kv_total, .out_bf16 = kv_out});
 }
 
 // ---- cross-attention over k neighbours as two skinny GEMMs.  softmax(q K^T / sqrt d) V W_o^T with q = x W_q^T is re-associated
@@ -69,13 +69,12 @@ static void unet_time_rows(Ops& o, UNet& u, const long long* t, int B, float* em
     bf16_t* temb = o.abf((size_t)B * mc);
     if (!o.plan) o.check(launch_timestep_embedding(t, temb, B, mcl, mc, o.c->stream), "timestep_embedding");
     bf16_t* e1 = o.abf((size_t)B * ted);
-    o.single_row = true;                                  // one row per sample (see Ops::linear)
-    o.tag = "time_embed";
-    o.linear(temb, nullptr, mc, 0, o.w<bf16_t>(u.te0w), o.w<float>(u.te0b), B, ted, ACT_SILU, nullptr, e1);
+    o.tag = "time_embed";             // (single_row: one row per sample, see LinearOp)
+    o.linear({.A0 = temb, .C0 = mc, .W = o.w<bf16_t>(u.te0w), .bias = o.w<float>(u.te0b), .M = B, .N = ted, .act = ACT_SILU, .out_bf16 = e1, .single_row = true});
     bf16_t* semb = o.abf((size_t)B * ted);
-    o.linear(e1, nullptr, ted, 0, o.w<bf16_t>(u.te2w), o.w<float>(u.te2b), B, ted, ACT_SILU, nullptr, semb);
-    o.linear(semb, nullptr, ted, 0, o.w<bf16_t>(u.embw), o.w<float>(u.embb), B, u.emb_total, ACT_NONE, nullptr, nullptr, emb_all);      // all 22 emb_layers in one GEMM
-    o.single_row = false;
+    o.linear({.A0 = e1, .C0 = ted, .W = o.w<bf16_t>(u.te2w), .bias = o.w<float>(u.te2b), .M = B, .N = ted, .act = ACT_SILU, .out_bf16 = semb, .single_row = true});
+    o.linear({.A0 = semb, .C0 = ted, .W = o.w<bf16_t>(u.embw), .bias = o.w<float>(u.embb), .M = B, .N = u.emb_total, .out_f32 = emb_all,
+              .single_row = true});      // all 22 emb_layers in one GEMM
 }
 
 // emb_row: the batch shares ONE timestep whose emb row was computed ahead of the sampling loop (rdm_ddim_sample: a table of the S rows, one
@@ -115,10 +114,9 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
 
     auto resblock = [&](const ResW& r, const Act& a, Act* skip) -> Act {
         const int C0 = a.C, C1 = skip ? skip->C : 0, HW = a.H * a.W, M = B * HW;
-        o.rows_hint = HW;
         int wrap_b = 0;                                    // > 0: the skip tensor holds Bfull/2 samples, read with a batch wrap
         if (skip && skip->half) {
-            if (B == Bfull && r.skip && o.lin4_takes(M, r.cout, C0, C1, (Bfull / 2) * HW)) wrap_b = Bfull / 2;
+            if (B == Bfull && r.skip && o.lin4_takes({.C0 = C0, .C1 = C1, .M = M, .N = r.cout, .a1_wrap_rows = (Bfull / 2) * HW})) wrap_b = Bfull / 2;
             else expand(*skip);
         }
         const bf16_t* x1 = skip ? skip->p : nullptr;
@@ -129,41 +127,43 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         if (r.skip) {
             sk = o.abf((size_t)M * r.cout);
             o.tag = "res.skip";
-            o.linear(a.p, x1, C0, C1, o.w<bf16_t>(r.wsk), o.w<float>(r.bsk), M, r.cout, ACT_NONE, nullptr, sk, nullptr, nullptr, wrap_b * HW);
+            o.linear({.A0 = a.p, .A1 = x1, .C0 = C0, .C1 = C1, .W = o.w<bf16_t>(r.wsk), .bias = o.w<float>(r.bsk), .M = M, .N = r.cout, .out_bf16 = sk,
+                      .a1_wrap_rows = wrap_b * HW, .sample_rows = HW});
             res = sk;
         }
         bf16_t* n1 = o.abf((size_t)M * r.cin);
         o.tag = "res.gn1";
-        o.groupnorm(a.p, x1, C0, C1, B, HW, o.w<float>(r.gn1g), o.w<float>(r.gn1b), 1e-5f, 1, n1, a.L, skip ? skip->L : 0, wrap_b);
+        o.groupnorm({.x0 = a.p, .x1 = x1, .C0 = C0, .C1 = C1, .HW = HW, .B = B, .L0 = a.L, .L1 = skip ? skip->L : 0,
+                     .gamma = o.w<float>(r.gn1g), .beta = o.w<float>(r.gn1b), .eps = 1e-5f, .silu = 1, .out = n1, .x1_bmod = wrap_b});
         o.tap(1, n1, (size_t)M * r.cin * 2);
         bf16_t* h1 = o.abf((size_t)M * r.cout);
         o.tag = "res.conv1";
-        o.conv3(n1, nullptr, r.cin, 0, o.w<bf16_t>(r.w1), o.w<float>(r.b1), B, a.H, a.W, r.cout, 1, 0, emb_all + r.emb_off, emb_ld, nullptr, h1);
+        o.conv3({.A0 = n1, .C0 = r.cin, .W = o.w<bf16_t>(r.w1), .bias = o.w<float>(r.b1), .B = B, .Hin = a.H, .Win = a.W, .N = r.cout, .out_bf16 = h1,
+                 .rowvec = emb_all + r.emb_off, .rowvec_ld = emb_ld});
         o.tap(2, h1, (size_t)M * r.cout * 2);
         bf16_t* n2 = o.abf((size_t)M * r.cout);
         o.tag = "res.gn2";
-        o.groupnorm(h1, nullptr, r.cout, 0, B, HW, o.w<float>(r.gn2g), o.w<float>(r.gn2b), 1e-5f, 1, n2, r.lout, 0);
+        o.groupnorm({.x0 = h1, .C0 = r.cout, .HW = HW, .B = B, .L0 = r.lout, .gamma = o.w<float>(r.gn2g), .beta = o.w<float>(r.gn2b), .eps = 1e-5f, .silu = 1, .out = n2});
         o.tap(3, n2, (size_t)M * r.cout * 2);
         if (r.skip) o.tap(4, sk, (size_t)M * r.cout * 2);
         bf16_t* out = o.abf((size_t)Bfull * HW * r.cout);           // Bfull: see expand()
         o.tag = "res.conv2";
-        o.conv3(n2, nullptr, r.cout, 0, o.w<bf16_t>(r.w2), o.w<float>(r.b2), B, a.H, a.W, r.cout, 1, 0, nullptr, 0, res, out);
+        o.conv3({.A0 = n2, .C0 = r.cout, .W = o.w<bf16_t>(r.w2), .bias = o.w<float>(r.b2), .B = B, .Hin = a.H, .Win = a.W, .N = r.cout, .res_bf16 = res, .out_bf16 = out});
         o.tap(5, out, (size_t)M * r.cout * 2);
         return Act{out, r.cout, a.H, a.W, r.lout};
     };
     auto transformer = [&](const StW& s, const Act& a) -> Act {
         const int C = s.c, n = a.H * a.W, M = B * n;
-        o.rows_hint = n;
         // a.half: the input left the shared guidance prefix and only its first Bfull / 2 samples exist: its two readers -- the entry GroupNorm and
         // the residual of ff.net.2 x proj_out -- wrap the batch index (round 5: no 50 MB duplication pass per forward)
         const int in_wrap = a.half ? Bfull / 2 : 0;
         bf16_t* xn = o.abf((size_t)M * C);
         o.tag = "st.gn";
-        o.groupnorm(a.p, nullptr, C, 0, B, n, o.w<float>(s.gng), o.w<float>(s.gnb), 1e-6f, 0, xn, s.lc, 0, 0, in_wrap);
+        o.groupnorm({.x0 = a.p, .C0 = C, .HW = n, .B = B, .L0 = s.lc, .gamma = o.w<float>(s.gng), .beta = o.w<float>(s.gnb), .eps = 1e-6f, .out = xn, .x0_bmod = in_wrap});
         o.tap(1, xn, (size_t)M * C * 2);
         bf16_t* t0 = o.abf((size_t)M * C);
         o.tag = "st.proj_in";
-        o.linear(xn, nullptr, C, 0, o.w<bf16_t>(s.win), o.w<float>(s.bin), M, C, ACT_NONE, nullptr, t0);
+        o.linear({.A0 = xn, .C0 = C, .W = o.w<bf16_t>(s.win), .bias = o.w<float>(s.bin), .M = M, .N = C, .out_bf16 = t0, .sample_rows = n});
         o.tap(2, t0, (size_t)M * C * 2);
         // --- attn1 (self)
         bf16_t* l1 = o.abf((size_t)M * C);
@@ -174,14 +174,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         const int QW = vrow ? 3 * C : 2 * C;
         bf16_t* qk = o.abf((size_t)M * QW);
         o.tag = "st.norm1+qkv";
-        o.layernorm(t0, 0, o.w<float>(s.ln1g), o.w<float>(s.ln1b), l1, 0, M, C, s.lc);
+        o.layernorm({.x_bf16 = t0, .gamma = o.w<float>(s.ln1g), .beta = o.w<float>(s.ln1b), .M = M, .C = C, .out_bf16 = l1, .Clog = s.lc});
         o.tap(3, l1, (size_t)M * C * 2);
-        o.linear(l1, nullptr, C, 0, o.w<bf16_t>(s.wqk), nullptr, M, QW, ACT_NONE, nullptr, qk);
+        o.linear({.A0 = l1, .C0 = C, .W = o.w<bf16_t>(s.wqk), .M = M, .N = QW, .out_bf16 = qk, .sample_rows = n});
         o.tap(4, qk, (size_t)M * QW * 2);
         bf16_t* ao = o.abf((size_t)M * C);
         o.tag = "st.self_attention";
         if (vrow) {
-            o.flash_d32(qk, QW, qk + 2 * C, nullptr, ao, B, n, s.heads);
+            o.flash_d32({.q = qk, .ldq = QW, .v = qk + 2 * C, .out = ao, .n = n}, s.heads, B);
         } else if (n % 32 == 0) {
             bf16_t* vt = o.abf((size_t)M * C);      // V^T per sample: [B][C][n] via swapped-operand GEMM
             if (!o.plan) {
@@ -190,18 +190,19 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                 p.out_bf16 = vt; p.ldo = n;
                 o.check(launch_igemm(p, false, B, o.c->stream), "v^T gemm");
             }
-            o.flash_d32(qk, 2 * C, nullptr, vt, ao, B, n, s.heads);
+            o.flash_d32({.q = qk, .ldq = 2 * C, .vt = vt, .out = ao, .n = n}, s.heads, B);
         } else {
             bf16_t* v = o.abf((size_t)M * C);
-            o.linear(l1, nullptr, C, 0, o.w<bf16_t>(s.wv), nullptr, M, C, ACT_NONE, nullptr, v);
-            o.small_attention(qk, 2 * C, qk + C, 2 * C, v, C, ao, C, B, n, n, s.heads, 32, 0, 1.0f / sqrtf(32.f), "small self attention");
+            o.linear({.A0 = l1, .C0 = C, .W = o.w<bf16_t>(s.wv), .M = M, .N = C, .out_bf16 = v, .sample_rows = n});
+            o.small_attention({.q = qk, .ldq = 2 * C, .k = qk + C, .ldk = 2 * C, .v = v, .ldv = C, .out = ao, .ldo = C, .nq = n, .nkv = n, .scale = 1.0f / sqrtf(32.f)},
+                              32, s.heads, B, "small self attention");
         }
         o.tap(5, ao, (size_t)M * C * 2);
         bf16_t* t1 = o.abf((size_t)M * C);
         // --- attn2 (cross over the k neighbours); samples >= Bx have all-zero neighbours: t2 = t1 + b_o exactly (see add_bias_rows_kernel)
         const int Mx = Bx * n;
         // norm2 + attn2 + residual in one kernel when the neighbours' operands are cached (xa), norm2 too when no channel is padding
-        const bool xfused = xa && Mx > 0 && xattn_fused_supported(Ops::xattn_params(Mx, n, C, XA_NP, s.heads * k, k));
+        const bool xfused = xa && Mx > 0 && xattn_fused_supported({.rows = Mx, .n = n, .C = C, .NP = XA_NP, .ncols = s.heads * k, .group = k});
         const bool xln = xfused && s.lc == C && C <= 2048;
         // Round 5: in a guided batch [conditional | unconditional] (Bx = B / 2) with the LayerNorm-fused cross-attention kernel,
         //   * the unconditional rows' t2 = attn1.to_out(...) + t0 + b_o2 leaves attn1.to_out's GEMM directly (b_o2 rides in the start
@@ -211,17 +212,17 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         const bool xfold_shape = xln && !o.c->deterministic;
         const bool bias_fold = xfold_shape && Bx * 2 == B;             // the unconditional half exists and is exactly the second half
         o.tag = "st.attn1.to_out";
+        LinearOp to_out{.A0 = ao, .C0 = C, .W = o.w<bf16_t>(s.wo1), .bias = o.w<float>(s.bo1), .M = M, .N = C, .res_bf16 = t0, .out_bf16 = t1, .sample_rows = n};
         if (bias_fold) {
             const float* zb = o.plan ? nullptr : o.c->zero_bias_pair(o.w<float>(s.bo2), C);
             if (!o.plan && !zb && o.rc == 0) o.rc = o.c->fail(-2, "out of memory for a bias table");
-            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(s.wo1), o.w<float>(s.bo1), M, C, ACT_NONE, t0, t1, nullptr, nullptr, 0, zb, C, Mx);
-        } else {
-            o.linear(ao, nullptr, C, 0, o.w<bf16_t>(s.wo1), o.w<float>(s.bo1), M, C, ACT_NONE, t0, t1);
+            to_out.rowvec = zb; to_out.rowvec_ld = C; to_out.rows_per_sample = Mx;      // rows [0, Mx) + 0, rows [Mx, M) + b_o2
         }
+        o.linear(to_out);
         o.tap(6, t1, (size_t)M * C * 2);          // (with the bias fold: the unconditional rows already hold t2)
         o.tag = "st.norm2+attn2";
         bf16_t* l2 = o.abf((size_t)M * C);
-        if (Mx > 0 && !xln) o.layernorm(t1, 0, o.w<float>(s.ln2g), o.w<float>(s.ln2b), l2, 0, Mx, C, s.lc);
+        if (Mx > 0 && !xln) o.layernorm({.x_bf16 = t1, .gamma = o.w<float>(s.ln2g), .beta = o.w<float>(s.ln2b), .M = Mx, .C = C, .out_bf16 = l2, .Clog = s.lc});
         bf16_t* t2 = xfold_shape ? t1 : o.abf((size_t)M * C);
         bf16_t* l3 = o.abf((size_t)M * C);
         if (Bx < B && !bias_fold && !o.plan)
@@ -231,12 +232,15 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
             bf16_t* P = o.abf((size_t)M * XA_NP);
             const bf16_t* G = xa + (size_t)B * s.xa_unit; const bf16_t* U = G + (size_t)B * XA_NP * C;
             const bf16_t* Gp = U + (size_t)B * C * XA_NP; const bf16_t* Up = Gp + (size_t)B * XA_NP * C;     // their packed images
-            if (xln)            // both GEMMs, the softmax, the residual and norm2 (and norm3) in one launch
-                o.xattn_fused(t1, o.w<float>(s.ln2g), o.w<float>(s.ln2b), 1e-5f, Gp, Up, o.w<float>(s.bo2), nullptr, t2, Mx, n, C, XA_NP, s.heads * k, k,
-                              xfold_shape ? o.w<float>(s.ln3g) : nullptr, xfold_shape ? o.w<float>(s.ln3b) : nullptr, xfold_shape ? l3 : nullptr);
-            else if (xfused)    // on the LayerNorm'd rows
-                o.xattn_fused(l2, nullptr, nullptr, 0.f, Gp, Up, o.w<float>(s.bo2), t1, t2, Mx, n, C, XA_NP, s.heads * k, k);
-            else if (!o.plan) {
+            XattnParams xp{.G = Gp, .U = Up, .bias = o.w<float>(s.bo2), .out = t2, .rows = Mx, .n = n, .C = C, .NP = XA_NP, .ncols = s.heads * k, .group = k};
+            if (xln) {          // both GEMMs, the softmax, the residual and norm2 (and norm3) in one launch
+                xp.x = t1; xp.ln_g = o.w<float>(s.ln2g); xp.ln_b = o.w<float>(s.ln2b); xp.ln_eps = 1e-5f;
+                if (xfold_shape) { xp.ln3_g = o.w<float>(s.ln3g); xp.ln3_b = o.w<float>(s.ln3b); xp.ln3_out = l3; }
+                o.xattn_fused(xp);
+            } else if (xfused) {   // on the LayerNorm'd rows
+                xp.x = l2; xp.res = t1;
+                o.xattn_fused(xp);
+            } else if (!o.plan) {
                 IgemmParams p = o.base(n, XA_NP, C);
                 p.A0 = l2; p.C0 = C; p.sA = (long long)n * C; p.W = G; p.sW = (long long)XA_NP * C; p.out_bf16 = P; p.sO = (long long)n * XA_NP;
                 p.act = ACT_SOFTMAXG; p.sm_group = k;
@@ -252,31 +256,30 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
             }
         } else {
             bf16_t* q2 = o.abf((size_t)M * C);
-            o.linear(l2, nullptr, C, 0, o.w<bf16_t>(s.wq2), nullptr, Mx, C, ACT_NONE, nullptr, q2);
+            o.linear({.A0 = l2, .C0 = C, .W = o.w<bf16_t>(s.wq2), .M = Mx, .N = C, .out_bf16 = q2, .sample_rows = n});
             bf16_t* ao2 = o.abf((size_t)M * C);
-            o.small_attention(q2, C, kv + s.kv_off, u.kv_total, kv + s.kv_off + C, u.kv_total, ao2, C, Bx, n, k, s.heads, 32, 0, 1.0f / sqrtf(32.f),
-                              "cross attention");
-            o.linear(ao2, nullptr, C, 0, o.w<bf16_t>(s.wo2), o.w<float>(s.bo2), Mx, C, ACT_NONE, t1, t2);
+            o.small_attention({.q = q2, .ldq = C, .k = kv + s.kv_off, .ldk = u.kv_total, .v = kv + s.kv_off + C, .ldv = u.kv_total, .out = ao2, .ldo = C,
+                               .nq = n, .nkv = k, .scale = 1.0f / sqrtf(32.f)}, 32, s.heads, Bx, "cross attention");
+            o.linear({.A0 = ao2, .C0 = C, .W = o.w<bf16_t>(s.wo2), .bias = o.w<float>(s.bo2), .M = Mx, .N = C, .res_bf16 = t1, .out_bf16 = t2, .sample_rows = n});
         }
         o.tap(7, t2, (size_t)M * C * 2);
         // --- GEGLU feed-forward
         o.tag = "st.norm3+geglu";
         const int FI = 4 * s.lc;                     // GEGLU hidden width: 4 x the LOGICAL channels (a multiple of 128, never padded)
         bf16_t* ff = o.abf((size_t)M * FI);
-        if (xfold_shape) {       // norm3 of the conditional rows left the cross-attention kernel; the unconditional rows' here
-            if (M > Mx) o.layernorm(t2 + (size_t)Mx * C, 0, o.w<float>(s.ln3g), o.w<float>(s.ln3b), l3 + (size_t)Mx * C, 0, M - Mx, C, s.lc);
-            o.linear(l3, nullptr, C, 0, o.w<bf16_t>(s.wff1), o.w<float>(s.bff1), M, 2 * FI, ACT_GEGLU, nullptr, ff);
-        } else {
-            o.layernorm(t2, 0, o.w<float>(s.ln3g), o.w<float>(s.ln3b), l3, 0, M, C, s.lc);
-            o.linear(l3, nullptr, C, 0, o.w<bf16_t>(s.wff1), o.w<float>(s.bff1), M, 2 * FI, ACT_GEGLU, nullptr, ff);
-        }
+        // norm3: with xfold_shape the conditional rows' left the cross-attention kernel, only the unconditional rows' are formed here
+        const int M3 = xfold_shape ? Mx : 0;
+        if (M > M3) o.layernorm({.x_bf16 = t2 + (size_t)M3 * C, .gamma = o.w<float>(s.ln3g), .beta = o.w<float>(s.ln3b), .M = M - M3, .C = C,
+                                 .out_bf16 = l3 + (size_t)M3 * C, .Clog = s.lc});
+        o.linear({.A0 = l3, .C0 = C, .W = o.w<bf16_t>(s.wff1), .bias = o.w<float>(s.bff1), .M = M, .N = 2 * FI, .act = ACT_GEGLU, .out_bf16 = ff, .sample_rows = n});
         o.tap(8, l3, (size_t)M * C * 2);
         o.tap(9, ff, (size_t)M * FI * 2);
         bf16_t* out = o.abf((size_t)M * C);
         o.tag = "st.ff2*proj_out";
         // t3 = ff W_2^T + b_2 + t2 and out = t3 W_out^T + b_out + x are one GEMM over the K-concatenated operand [ff | t2]
         // (dual-source A) with the product weights built by the packer: t3 never exists (2 of 9 tensor passes, one launch)
-        o.linear(ff, t2, FI, C, o.w<bf16_t>(s.wfo), o.w<float>(s.bfo), M, C, ACT_NONE, a.p, out, nullptr, nullptr, 0, nullptr, 0, 1, in_wrap * n);
+        o.linear({.A0 = ff, .A1 = t2, .C0 = FI, .C1 = C, .W = o.w<bf16_t>(s.wfo), .bias = o.w<float>(s.bfo), .M = M, .N = C, .res_bf16 = a.p, .out_bf16 = out,
+                  .res_wrap_rows = in_wrap * n, .sample_rows = n});
         o.tap(10, out, (size_t)M * C * 2);
         return Act{out, C, a.H, a.W, s.lc};
     };
@@ -299,7 +302,7 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                         {   // the activation itself is duplicated only where its readers cannot wrap the batch index instead (transformer())
                             const StW& s0 = u.st[L.idx];
                             const int n0 = h.H * h.W, Mfull = Bfull * n0;
-                            if (!o.c->deterministic && o.lin4_takes(Mfull, s0.c, 4 * s0.lc, s0.c, 0, (Bfull / 2) * n0)) h.half = true;
+                            if (!o.c->deterministic && o.lin4_takes({.C0 = 4 * s0.lc, .C1 = s0.c, .M = Mfull, .N = s0.c, .res_wrap_rows = (Bfull / 2) * n0})) h.half = true;
                             else expand(h);
                         }
                         for (Act& a : hs) { if (o.c->deterministic) expand(a); else a.half = true; }
@@ -310,14 +313,14 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                     const ConvW& d = u.down[L.idx];
                     bf16_t* out = o.abf((size_t)Bfull * (h.H / 2) * (h.W / 2) * d.c);
                     o.tag = "downsample";
-                    o.conv3(h.p, nullptr, d.c, 0, o.w<bf16_t>(d.w), o.w<float>(d.b), B, h.H, h.W, d.c, 2, 0, nullptr, 0, nullptr, out);
+                    o.conv3({.A0 = h.p, .C0 = d.c, .W = o.w<bf16_t>(d.w), .bias = o.w<float>(d.b), .B = B, .Hin = h.H, .Win = h.W, .N = d.c, .stride = 2, .out_bf16 = out});
                     h = Act{out, d.c, h.H / 2, h.W / 2, d.lc};
                 } break;
                 case 4: {
                     const ConvW& d = u.up[L.idx];
                     bf16_t* out = o.abf((size_t)Bfull * (h.H * 2) * (h.W * 2) * d.c);
                     o.tag = "upsample";
-                    o.conv3(h.p, nullptr, d.c, 0, o.w<bf16_t>(d.w), o.w<float>(d.b), B, h.H, h.W, d.c, 1, 1, nullptr, 0, nullptr, out);
+                    o.conv3({.A0 = h.p, .C0 = d.c, .W = o.w<bf16_t>(d.w), .bias = o.w<float>(d.b), .B = B, .Hin = h.H, .Win = h.W, .N = d.c, .ups = 1, .out_bf16 = out});
                     h = Act{out, d.c, h.H * 2, h.W * 2, d.lc};
                 } break;
             }
@@ -334,7 +337,8 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
     bf16_t* no = o.abf((size_t)B * H * W * mc);
     bf16_t* hwp = o.abf(head_conv_wp_bytes(mc) / 2);
     o.tag = "out_head";
-    o.head(h.p, B, H, W, mc, mcl, o.w<float>(u.outg), o.w<float>(u.outb), 1e-5f, o.w<float>(u.outw), o.w<float>(u.outbias), c.out_channels, eps_out, no, hwp);
+    o.head({.x = h.p, .B = B, .H = H, .W = W, .C = mc, .gamma = o.w<float>(u.outg), .beta = o.w<float>(u.outb), .eps = 1e-5f, .w = o.w<float>(u.outw), .wp = hwp,
+            .bias = o.w<float>(u.outbias), .out = eps_out, .Cout = c.out_channels}, mcl, no);
 }
 
 int unet_forward_impl(rdm_ctx* c, const float* x, const int64_t* t, const float* context, const bf16_t* kv_cached,
