@@ -438,6 +438,23 @@ int rdm_op_conv3x3(rdm_ctx* ctx, const void* x0_bf16, const void* x1_bf16, int C
  * E % 64 == 0 and E <= 512, otherwise an argument error and no launch.  Every index lies in [0, N), also for non-finite z. */
 int rdm_op_vq_nearest_code(rdm_ctx* ctx, const float* z /*[dev] [M,E]*/, const float* codebook /*[dev] [N,E]*/, long long M, int N, int E,
                            int32_t* idx_out /*[dev] [M]*/);
+/* ---- quality metrics on feature sets (csrc/metrics.hip): x f32 [dev] [n, d] row-major, d % 32 == 0 and 32 <= d <= 4096 (anything else: an
+ * argument error naming the op and the value, no launch, the context stays usable).
+ * Frechet distance (Heusel et al. 2017, FID = |mu_a - mu_b|^2 + Tr(S_a + S_b - 2 (S_a S_b)^1/2)): its sufficient statistics.
+ * sum [dev] f64 [d] += SUM_i x_i and outer [dev] f64 [d, d] += SUM_i x_i x_i^T, products and sums in fp64 (v_mfma_f64_16x16x4_f64).  In / out:
+ * the caller zeroes both once and folds any number of batches in.  No atomics; a call's reduction order depends on (n, d) alone, so it
+ * is reproducible, and differently chunked calls differ by fp64 rounding only. */
+int rdm_op_moments_f64(rdm_ctx* ctx, const float* x, int n, int d, double* sum, double* outer);
+/* Improved precision and recall (Kynkaanniemi et al. 2019, eq. 3): radius2_out [dev] f32 [n], entry i = the squared Euclidean distance from
+ * row i to its k-th nearest OTHER row, NN_k(x_i, X \ {x_i})^2.  Self is left out by index, so a duplicate row is a neighbour at distance 0.
+ * 1 <= k <= 8 and k < n.  d2(a, b) = max(0, |a|^2 + |b|^2 - 2 a.b) in fp32 on fp32-input MFMAs, norms and dot product by one chain over k
+ * (equal rows: exactly 0); |d2 - exact| <= 5e-7 (|a|^2 + |b|^2) for d <= 1024.  A pair's value does not depend on n or on where the pair
+ * lands; the n x n distances are streamed, never stored. */
+int rdm_op_knn_radius(rdm_ctx* ctx, const float* x, int n, int d, int k, float* radius2_out);
+/* The same paper's f(probe_i, Ref): hit_out [dev] uint8 [m], 1 iff some j has d2(probe_i, ref_j) <= ref_radius2[j] (ref_radius2 [dev] f32 [n],
+ * from rdm_op_knn_radius on ref); precision = mean f(generated, Real), recall = mean f(real, Generated).  d2 as above.  m, n >= 1. */
+int rdm_op_manifold_hits(rdm_ctx* ctx, const float* probe /*[m,d]*/, int m, const float* ref /*[n,d]*/, const float* ref_radius2, int n, int d,
+                         unsigned char* hit_out);
 /* the RARM sampler kernel alone (taming top_k_logits + softmax + multinomial as an inverse CDF in vocabulary order, after the
  * classifier-free combine lu + scale (lc - lu) and the temperature; transformer.py:237-263): logits [dev] f32 [(cfg ? 2 : 1) * b, vocab]
  * (conditional rows first), uniforms [dev] f32 [b], tokens_out [dev] int64 [b].  top_k <= 0: no filter. */

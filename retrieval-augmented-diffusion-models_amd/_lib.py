@@ -180,6 +180,9 @@ SIGNATURES = {
     "rdm_op_conv3x3": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int]),
     "rdm_op_vq_nearest_code": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int, _P]),
+    "rdm_op_moments_f64": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
+    "rdm_op_knn_radius": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
+    "rdm_op_manifold_hits": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
     "rdm_op_rarm_sampler": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "rdm_op_rarm_sampler_top_p": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P]),
     "rdm_op_conv3x3_dgrad": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -574,6 +577,44 @@ class Context:
             raise RdmError(f"vq_nearest_code: z must be [M,E] and codebook [N,E], got {tuple(z.shape)} and {tuple(codebook.shape)}")
         out = torch.empty((z.shape[0],), device=self.device, dtype=torch.int32)
         self._check(lib.rdm_op_vq_nearest_code(self._h, _ptr(z), _ptr(codebook), z.shape[0], codebook.shape[0], z.shape[1], _ptr(out)))
+        return out
+
+    # ---- quality metrics on feature sets (csrc/metrics.hip; rdm_amd.metrics holds the host arithmetic)
+    def _features(self, what, x, name="x"):
+        """A feature set f32 [n, d] on the device.  The row count and d are checked by the library (it names the op and the value)."""
+        if not isinstance(x, torch.Tensor) or x.ndim != 2:
+            raise RdmError(f"{what}: {name} must be a tensor [n, d], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+        return self._dev(x, torch.float32)
+
+    def op_moments_f64(self, x, sum_, outer):
+        """sum_ f64 [d] += SUM_i x_i, outer f64 [d, d] += SUM_i x_i x_i^T in fp64 (rdm_op_moments_f64): in / out, both on this device,
+        zeroed by the caller before the first batch.  x f32 [n, d], d % 32 == 0, 32 <= d <= 4096."""
+        x = self._features("op_moments_f64", x)
+        d = x.shape[1]
+        for name, t, shape in (("sum_", sum_, (d,)), ("outer", outer, (d, d))):
+            if not isinstance(t, torch.Tensor) or t.dtype != torch.float64 or tuple(t.shape) != shape or t.device != self.device or not t.is_contiguous():
+                raise RdmError(f"op_moments_f64: {name} must be a contiguous float64 tensor {shape} on {self.device} (it is accumulated into)")
+        self._check(lib.rdm_op_moments_f64(self._h, _ptr(x), x.shape[0], d, _ptr(sum_), _ptr(outer)))
+
+    def op_knn_radius(self, x, k):
+        """-> f32 [n]: squared Euclidean distance from each row of x f32 [n, d] to its k-th nearest OTHER row (rdm_op_knn_radius; self is
+        left out by index, duplicates are neighbours at 0).  1 <= k <= 8, k < n."""
+        x = self._features("op_knn_radius", x)
+        out = torch.empty((x.shape[0],), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_op_knn_radius(self._h, _ptr(x), x.shape[0], x.shape[1], int(k), _ptr(out)))
+        return out
+
+    def op_manifold_hits(self, probe, ref, ref_radius2):
+        """-> uint8 [m]: 1 iff probe row i lies within ref_radius2[j] (squared) of some row j of ref (rdm_op_manifold_hits).
+        probe f32 [m, d], ref f32 [n, d], ref_radius2 f32 [n]."""
+        probe = self._features("op_manifold_hits", probe, "probe"); ref = self._features("op_manifold_hits", ref, "ref")
+        if probe.shape[1] != ref.shape[1]:
+            raise RdmError(f"op_manifold_hits: probe and ref must share d, got {tuple(probe.shape)} and {tuple(ref.shape)}")
+        if not isinstance(ref_radius2, torch.Tensor) or tuple(ref_radius2.shape) != (ref.shape[0],):
+            raise RdmError(f"op_manifold_hits: ref_radius2 must be a tensor [{ref.shape[0]}], one radius per ref row")
+        ref_radius2 = self._dev(ref_radius2, torch.float32)
+        out = torch.empty((probe.shape[0],), device=self.device, dtype=torch.uint8)
+        self._check(lib.rdm_op_manifold_hits(self._h, _ptr(probe), probe.shape[0], _ptr(ref), _ptr(ref_radius2), ref.shape[0], ref.shape[1], _ptr(out)))
         return out
 
     def load_clip(self, cfg: ClipCfg, blob: np.ndarray):

@@ -324,6 +324,15 @@ hipError_t launch_vq_code_norms(const float* codebook, float* norms, int N, int 
 hipError_t launch_vq_nearest(const float* z, const float* codebook, const float* norms, long long M, int N, int E, char* ws, int* idx32,
                              long long* idx64, hipStream_t st);       // idx32 / idx64: either may be null
 hipError_t launch_vq_rows_to_nchw(const float* src, const int* idx, float* out, int B, int HW, int E, hipStream_t st);      // out [B,E,HW] = rows idx[token] (null: token) of src [.,E]; E % 32 == 0
+// metric arithmetic on feature sets f32 [n, d] (metrics.hip): fp64 moments, and the two streaming searches over d2(a, b) = |a|^2 + |b|^2 - 2 a.b
+// in fp32 (norms from launch_metric_row_norms: the same chain as the MFMA dot product, so equal rows are at distance exactly 0)
+bool metric_dim_supported(int d);                         // d % 32 == 0, 32 <= d <= 4096
+size_t metric_moments_ws_bytes(int n, int d);             // partial planes of the row splits; 0: none needed
+hipError_t launch_metric_moments(const float* x, int n, int d, double* sum, double* outer, char* ws, hipStream_t st);   // sum [d], outer [d, d]: accumulated into
+hipError_t launch_metric_row_norms(const float* x, float* norms, int n, int d, hipStream_t st);
+hipError_t launch_metric_knn_radius(const float* x, const float* norms, int n, int d, int k, float* radius2, hipStream_t st);   // 1 <= k <= 8, k < n
+hipError_t launch_metric_manifold_hits(const float* probe, const float* pnorms, int m, const float* ref, const float* rnorms, const float* ref_radius2,
+                                       int n, int d, unsigned char* hit, hipStream_t st);
 hipError_t launch_softmax_rows(const float* s, bf16_t* p, long long rows, int n, hipStream_t st, int n_valid = 0);   // columns >= n_valid: probability 0
 hipError_t launch_clip_embed(const long long* tokens, const float* tok_emb, const float* pos_emb, float* out, int B, int L,
                              int Wd, hipStream_t st);

@@ -70,6 +70,50 @@ int rdm_op_vq_nearest_code(rdm_ctx* c, const float* z, const float* codebook, lo
     o.vq_nearest({.z = z, .codebook = codebook, .norms = norms, .M = M, .N = N, .E = E, .ws = c->samp + nbytes, .idx32 = idx_out});
     return o.rc;
 }
+// ---- metric arithmetic on feature sets (kernels in metrics.hip); norms and split planes live in the sampler scratch
+static int metric_dim_check(rdm_ctx* c, const char* op, int d) {
+    if (!metric_dim_supported(d)) return c->fail(-1, "%s: d = %d; the kernels take multiples of 32 from 32 to 4096", op, d);
+    return 0;
+}
+// Frechet distance (Heusel et al. 2017): the sufficient statistics of mu = sum / n and Sigma = (outer - n mu mu^T) / (n - 1)
+int rdm_op_moments_f64(rdm_ctx* c, const float* x, int n, int d, double* sum, double* outer) {
+    RDM_ENTER(c);
+    if (n < 1) return c->fail(-1, "rdm_op_moments_f64: n = %d; at least one row", n);
+    if (!x || !sum || !outer) return c->fail(-1, "rdm_op_moments_f64: null argument");
+    RDM_TRY(metric_dim_check(c, "rdm_op_moments_f64", d));
+    const size_t ws = metric_moments_ws_bytes(n, d);
+    if (ws) RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, ws));
+    RDM_CHECK_HIP(c, launch_metric_moments(x, n, d, sum, outer, ws ? c->samp : nullptr, c->stream));
+    return 0;
+}
+// improved precision / recall (Kynkaanniemi et al. 2019, eq. 3): the radius of row i's k-NN ball, NN_k(x_i, X \ {x_i}), squared
+int rdm_op_knn_radius(rdm_ctx* c, const float* x, int n, int d, int k, float* radius2_out) {
+    RDM_ENTER(c);
+    if (n < 1) return c->fail(-1, "rdm_op_knn_radius: n = %d; at least one row", n);
+    if (!x || !radius2_out) return c->fail(-1, "rdm_op_knn_radius: null argument");
+    RDM_TRY(metric_dim_check(c, "rdm_op_knn_radius", d));
+    if (k < 1 || k > 8) return c->fail(-1, "rdm_op_knn_radius: k = %d; the kernel keeps 1 to 8 neighbours", k);
+    if (k >= n) return c->fail(-1, "rdm_op_knn_radius: k = %d needs more than n = %d rows (self is no neighbour)", k, n);
+    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, (size_t)n * 4));
+    float* norms = (float*)c->samp;
+    RDM_CHECK_HIP(c, launch_metric_row_norms(x, norms, n, d, c->stream));
+    RDM_CHECK_HIP(c, launch_metric_knn_radius(x, norms, n, d, k, radius2_out, c->stream));
+    return 0;
+}
+// the same paper's f(probe_i, Ref) (eq. 3): 1 iff probe_i lies in the k-NN ball of some reference row
+int rdm_op_manifold_hits(rdm_ctx* c, const float* probe, int m, const float* ref, const float* ref_radius2, int n, int d, unsigned char* hit_out) {
+    RDM_ENTER(c);
+    if (m < 1 || n < 1) return c->fail(-1, "rdm_op_manifold_hits: m = %d, n = %d; at least one row each", m, n);
+    if (!probe || !ref || !ref_radius2 || !hit_out) return c->fail(-1, "rdm_op_manifold_hits: null argument");
+    RDM_TRY(metric_dim_check(c, "rdm_op_manifold_hits", d));
+    const size_t mb = ((size_t)m * 4 + 255) & ~(size_t)255;
+    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, mb + (size_t)n * 4));
+    float* pn = (float*)c->samp; float* rn = (float*)(c->samp + mb);
+    RDM_CHECK_HIP(c, launch_metric_row_norms(probe, pn, m, d, c->stream));
+    RDM_CHECK_HIP(c, launch_metric_row_norms(ref, rn, n, d, c->stream));
+    RDM_CHECK_HIP(c, launch_metric_manifold_hits(probe, pn, m, ref, rn, ref_radius2, n, d, hit_out, c->stream));
+    return 0;
+}
 // ---- backward ops (kernels in backward.hip)
 int rdm_op_conv3x3_dgrad(rdm_ctx* c, const void* dy, const void* w, void* dx, int B, int H, int W, int C, int N) {
     RDM_ENTER(c);
