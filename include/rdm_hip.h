@@ -412,7 +412,18 @@ int rdm_calib_probe(rdm_ctx* ctx, void* buf /*[dev]*/, size_t buf_bytes, double 
  *   ResBlock stages 1 in_layers norm+SiLU, 2 in_layers conv + emb, 3 out_layers norm+SiLU, 4 skip_connection, 5 output;
  *   SpatialTransformer stages 1 norm, 2 proj_in, 3 norm1, 4 q|k|v, 5 attn1 heads, 6 x + attn1, 7 x + attn2, 8 norm3, 9 GEGLU, 10 output
  *   (rdm/modules/attention.py:92-96, 170-196).  buf null: off.  tests/test_gpu_emul.py compares the library with the CPU restatement of its
- * arithmetic stage by stage, TEACHER-FORCED, through this. */
+ * arithmetic stage by stage, TEACHER-FORCED, through this.
+ * The CLIP towers (rdm_clip_encode_text: block 2000; rdm_clip_encode_image[_raw]: block 3000) show their tensors the same way, each copied
+ * as it is stored (fp32 or bf16, row-major); sub = 16 * layer + stage with layer 0 the tower's own stages and layer i + 1 resblock i
+ * (B sequences of L = context_length tokens / G^2 + 1 patch tokens, width W, patch size P, embedding E):
+ *   text, layer 0:   1 token + positional embedding f32 [B L, W], 2 the EOT rows (first maximum of the ids) f32 [B, W], 3 ln_final of
+ *                    them bf16 [B, W], 4 the projected embedding f32 [B, E];
+ *   image, layer 0:  1 patch matrix bf16 [B G^2, 3 P^2] (columns in (c, py, px) order), 2 patch embeddings f32 [B G^2, W], 3 cls | patches +
+ *                    positional f32 [B (G^2 + 1), W], 4 ln_pre f32, 5 the cls rows after the last resblock f32 [B, W], 6 ln_post bf16
+ *                    [B, W], 7 the projected embedding f32 [B, E];
+ *   resblock:        1 ln_1 bf16 [rows, W], 2 q|k|v bf16 [rows, 3 W], 3 attention heads bf16 [rows, W], 4 x + out_proj f32 [rows, W],
+ *                    5 ln_2 bf16, 6 QuickGELU hidden bf16 [rows, 4 W], 7 x + c_proj f32 (the block's output).
+ * tests/test_gpu_clip.py holds every one of them to an fp64 restatement on the library's own inputs. */
 int rdm_debug_tap(rdm_ctx* ctx, void* buf /*[dev]*/, size_t nbytes, int block, int sub);
 
 /* ---- operator-level entry points (used by the parity tests; thin wrappers over the kernels) ---- */
@@ -574,6 +585,13 @@ int rdm_op_groupnorm(rdm_ctx* ctx, const void* x0_bf16, const void* x1_bf16, int
                      const float* gamma, const float* beta, float eps, int silu, void* out_bf16);
 int rdm_op_layernorm(rdm_ctx* ctx, const void* x, int in_is_f32, const float* gamma, const float* beta, int M, int C,
                      float eps, void* out_bf16);
+/* The two forms only the CLIP towers run (custom_clip/model.py:166-187, 216-224): LayerNorm of fp32 rows [M, C] to fp32 (visual.ln_pre),
+ * and out_f32 [M, N] = act(a w^T + bias) + res_f32 through the tiled GEMM at any M (the towers' `x = x + attn(...)`, `x = x + mlp(...)` on
+ * the fp32 residual stream): a bf16 [M, K], w bf16 [N, K], bias / res_f32 fp32 or null; out_f32 may be the very buffer res_f32 points
+ * to (each element is read once, by the lane that then writes it).  N even, K % 64 == 0; act: none, QuickGELU or SiLU. */
+int rdm_op_layernorm_f32(rdm_ctx* ctx, const float* x, const float* gamma, const float* beta, int M, int C, float eps, float* out_f32);
+int rdm_op_linear_res_f32(rdm_ctx* ctx, const void* a_bf16, const void* w_bf16, const float* bias, const float* res_f32, float* out_f32,
+                          int M, int N, int K, int act);
 int rdm_op_self_attention(rdm_ctx* ctx, const void* qk_bf16, const void* vt_bf16, int B, int n, int heads,
                           void* out_bf16);
 /* the same attention from ONE fused projection qkv [B, n, 3C] = [q | k | v] (the UNet sampling path's form: V stays token-major and is

@@ -212,6 +212,8 @@ SIGNATURES = {
     "rdm_op_softmax_bwd": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int]),
     "rdm_op_groupnorm": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P, _P, C.c_float, C.c_int, _P]),
     "rdm_op_layernorm": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "rdm_op_layernorm_f32": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_float, _P]),
+    "rdm_op_linear_res_f32": (C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_self_attention": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_self_attention_qkv": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_head_conv": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
@@ -980,6 +982,7 @@ class Context:
         cfg = self._need("clip_encode_text", "clip")
         if tokens.ndim != 2 or tokens.shape[1] != cfg.context_length:
             raise RdmError(f"clip_encode_text: tokens must be [b,{cfg.context_length}], got {tuple(tokens.shape)}")
+        self._check_ids("clip_encode_text", tokens, cfg.vocab_size, "tokens")      # (the embedding kernel indexes the table by the id as given)
         out = torch.empty((tokens.shape[0], self.clip_cfg.embed_dim), device=self.device, dtype=torch.float32)
         self._check(lib.rdm_clip_encode_text(self._h, _ptr(tokens), tokens.shape[0], _ptr(out)))
         return out
@@ -1109,8 +1112,10 @@ class Context:
         self._check(lib.rdm_prof_reset(self._h))
 
     def debug_tap(self, buf, block, sub=0):
-        """The next UNet forwards copy one intermediate activation (block `block`, stage `sub`: include/rdm_hip.h) into `buf` (a bf16
-        device tensor); buf None: off."""
+        """The next forwards copy one intermediate activation (block `block`, stage `sub`: include/rdm_hip.h) into `buf`; buf None: off.
+        UNet blocks (0 ..) and first-stage decoder layers (1000 ..) show bf16 tensors; the CLIP text tower (block 2000) and image tower
+        (block 3000) show each stage in the type it is stored in, fp32 or bf16 (the table in rdm_hip.h): `buf` is a device tensor of
+        that type, and at most its numel * element_size bytes are written."""
         self._tap_keepalive = buf
         self._check(lib.rdm_debug_tap(self._h, _ptr(buf) if buf is not None else None, 0 if buf is None else buf.numel() * buf.element_size(), int(block), int(sub)))
 
@@ -1398,6 +1403,24 @@ class Context:
                                          float(eps), _ptr(out)))
         return out
 
+    def op_layernorm_f32(self, x, gamma, beta, eps=1e-5):
+        """LayerNorm of fp32 rows to fp32 (the image tower's ln_pre)."""
+        assert x.dtype == torch.float32
+        M, Cc = x.shape
+        out = torch.empty((M, Cc), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_op_layernorm_f32(self._h, _ptr(x), _ptr(gamma), _ptr(beta), M, Cc, float(eps), _ptr(out)))
+        return out
+
+    def op_linear_res_f32(self, a, w, bias=None, res=None, act=ACT_NONE, inplace=False):
+        """act(a w^T + bias) + res -> fp32 through the tiled GEMM (the CLIP towers' residual adds).  res fp32 [M, N] or None;
+        inplace: the output is written over `res` (the executors' form), which is returned; else into a fresh tensor."""
+        M, K = a.shape; N = w.shape[0]
+        assert res is None or (res.dtype == torch.float32 and tuple(res.shape) == (M, N))
+        assert not inplace or res is not None
+        out = res if inplace else torch.empty((M, N), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_op_linear_res_f32(self._h, _ptr(a), _ptr(w), _ptr(bias), _ptr(res), _ptr(out), M, N, K, int(act)))
+        return out
+
     def op_self_attention(self, qk, vt, heads):
         B, n, C2 = qk.shape
         out = torch.empty((B, n, C2 // 2), device=self.device, dtype=torch.bfloat16)
@@ -1683,9 +1706,18 @@ class Context:
         return out
 
     def op_small_attention(self, q, k, v, heads, D, causal, scale):
-        B, nq, Cc = q.shape
-        assert k.stride(-2) == v.stride(-2)
+        """q [B, nq, >= heads D], k / v [B, nkv, >= heads D] bf16 at their real row strides: each may be a column slice of one fused
+        [B, n, 3 heads D] projection (the CLIP towers' form), as long as a sample's rows follow the previous sample's at the same pitch."""
+        B, nq, _ = q.shape
+
+        def pitch(t):
+            ld = t.stride(1) if t.shape[1] > 1 else (t.stride(0) if B > 1 else t.shape[2])
+            assert t.stride(2) == 1 and (B == 1 or t.stride(0) == t.shape[1] * ld), "rows of one pitch, samples back to back"
+            return ld
+        ldq, ldk, ldv = pitch(q), pitch(k), pitch(v)
+        assert ldk == ldv, "k and v share one row pitch"
         out = torch.empty((B, nq, heads * D), device=self.device, dtype=torch.bfloat16)
-        self._check(lib.rdm_op_small_attention(self._h, _ptr(q), Cc, _ptr(k), _ptr(v), k.shape[2], B, nq, k.shape[1], heads,
+        p = lambda t: C.c_void_p(t.data_ptr())
+        self._check(lib.rdm_op_small_attention(self._h, p(q), ldq, p(k), p(v), ldk, B, nq, k.shape[1], heads,
                                                D, int(causal), float(scale), _ptr(out), heads * D))
         return out

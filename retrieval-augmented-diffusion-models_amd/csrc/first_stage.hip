@@ -259,50 +259,75 @@ static int vq_walk(rdm_ctx* c, M& m, int b, int h, int w, bool in_ranges, F&& bo
 }
 
 // ------------------------------------------------------------------------------------ CLIP
+// debug tap (rdm_debug_tap): the text tower is block 2000, the image tower block 3000; layer 0 = the tower's own stages (numbered in the
+// bodies below), layer i + 1 = resblock i with stages 1 ln_1, 2 q|k|v, 3 attention heads, 4 x + out_proj, 5 ln_2, 6 QuickGELU hidden, 7 x + c_proj
+constexpr int TAP_CLIP_TEXT = 2000, TAP_CLIP_IMAGE = 3000;
 static void clip_tower(Ops& o, const std::vector<ClipBlk>& blks, float* x, int B, int L, int Wd, int heads, int causal) {
     const int M = B * L;
     bf16_t* ln = o.abf((size_t)M * Wd); bf16_t* qkv = o.abf((size_t)M * 3 * Wd); bf16_t* ao = o.abf((size_t)M * Wd);
     bf16_t* hid = o.abf((size_t)M * 4 * Wd);
     for (const ClipBlk& k : blks) {
+        o.cur_layer = (int)(&k - &blks[0]) + 1;
         o.layernorm({.x_f32 = x, .gamma = o.w<float>(k.ln1g), .beta = o.w<float>(k.ln1b), .M = M, .C = Wd, .out_bf16 = ln});
+        o.tap(1, ln, (size_t)M * Wd * 2);
         o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(k.wqkv), .bias = o.w<float>(k.bqkv), .M = M, .N = 3 * Wd, .out_bf16 = qkv});
+        o.tap(2, qkv, (size_t)M * 3 * Wd * 2);
         o.small_attention({.q = qkv, .ldq = 3 * Wd, .k = qkv + Wd, .ldk = 3 * Wd, .v = qkv + 2 * Wd, .ldv = 3 * Wd, .out = ao, .ldo = Wd, .nq = L, .nkv = L, .causal = causal,
                            .scale = 1.0f / sqrtf((float)(Wd / heads))}, Wd / heads, heads, B, "clip attention");
+        o.tap(3, ao, (size_t)M * Wd * 2);
         o.linear({.A0 = ao, .C0 = Wd, .W = o.w<bf16_t>(k.wo), .bias = o.w<float>(k.bo), .M = M, .N = Wd, .res_f32 = x, .out_f32 = x});        // x += out_proj(attn)
+        o.tap(4, x, (size_t)M * Wd * 4);
         o.layernorm({.x_f32 = x, .gamma = o.w<float>(k.ln2g), .beta = o.w<float>(k.ln2b), .M = M, .C = Wd, .out_bf16 = ln});
+        o.tap(5, ln, (size_t)M * Wd * 2);
         o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(k.wfc), .bias = o.w<float>(k.bfc), .M = M, .N = 4 * Wd, .act = ACT_QUICKGELU, .out_bf16 = hid});
+        o.tap(6, hid, (size_t)M * 4 * Wd * 2);
         o.linear({.A0 = hid, .C0 = 4 * Wd, .W = o.w<bf16_t>(k.wpj), .bias = o.w<float>(k.bpj), .M = M, .N = Wd, .res_f32 = x, .out_f32 = x});  // x += mlp
+        o.tap(7, x, (size_t)M * Wd * 4);
     }
+    o.cur_layer = 0;
 }
 static void clip_text_body(Ops& o, ClipModel& m, const long long* tokens, int B, float* out) {
     const rdm_clip_cfg& c = m.cfg; const int L = c.context_length, Wd = c.transformer_width;
+    o.cur_block = TAP_CLIP_TEXT; o.cur_layer = 0;
     float* x = o.af32((size_t)B * L * Wd);
     if (!o.plan) o.check(launch_clip_embed(tokens, o.w<float>(m.tok), o.w<float>(m.pos), x, B, L, Wd, o.c->stream), "clip embed");
+    o.tap(1, x, (size_t)B * L * Wd * 4);
     clip_tower(o, m.text, x, B, L, Wd, c.transformer_heads, 1);
     float* eot = o.af32((size_t)B * Wd); bf16_t* ln = o.abf((size_t)B * Wd);
     if (!o.plan) o.check(launch_clip_gather_eot(tokens, x, eot, B, L, Wd, o.c->stream), "gather eot");
+    o.tap(2, eot, (size_t)B * Wd * 4);
     o.layernorm({.x_f32 = eot, .gamma = o.w<float>(m.lnfg), .beta = o.w<float>(m.lnfb), .M = B, .C = Wd, .out_bf16 = ln});
+    o.tap(3, ln, (size_t)B * Wd * 2);
     o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(m.tproj), .M = B, .N = c.embed_dim, .out_f32 = out, .single_row = true});      // the pooled token: one row per sample
+    o.tap(4, out, (size_t)B * c.embed_dim * 4);
 }
 // raw_h > 0: `img` is the un-preprocessed [B,3,raw_h,raw_w] image in [-1,1]; the bicubic resize + normalisation of
 // ClipImageRetriever.preprocess (rdm/modules/retrievers.py:83-91) is fused into the patch gather
 static void clip_image_body(Ops& o, ClipModel& m, const float* img, int B, float* out, int raw_h = 0, int raw_w = 0) {
     const rdm_clip_cfg& c = m.cfg; const int P = c.vision_patch_size, G = c.image_resolution / P, Wd = c.vision_width;
     const int K = 3 * P * P, L = G * G + 1;
+    o.cur_block = TAP_CLIP_IMAGE; o.cur_layer = 0;
     bf16_t* patches = o.abf((size_t)B * G * G * K); float* pe = o.af32((size_t)B * G * G * Wd);
     if (!o.plan) {
         if (raw_h > 0) o.check(launch_clip_preprocess(img, B, raw_h, raw_w, c.image_resolution, P, nullptr, patches, o.c->stream), "preprocess+patchify");
         else o.check(launch_clip_patchify(img, patches, B, c.image_resolution, P, o.c->stream), "patchify");
     }
+    o.tap(1, patches, (size_t)B * G * G * K * 2);
     o.linear({.A0 = patches, .C0 = K, .W = o.w<bf16_t>(m.conv1), .M = B * G * G, .N = Wd, .out_f32 = pe});
+    o.tap(2, pe, (size_t)B * G * G * Wd * 4);
     float* x0 = o.af32((size_t)B * L * Wd); float* x = o.af32((size_t)B * L * Wd);
     if (!o.plan) o.check(launch_clip_vit_assemble(pe, o.w<float>(m.cls), o.w<float>(m.vpos), x0, B, G * G, Wd, o.c->stream), "vit assemble");
+    o.tap(3, x0, (size_t)B * L * Wd * 4);
     o.layernorm({.x_f32 = x0, .gamma = o.w<float>(m.lnpreg), .beta = o.w<float>(m.lnpreb), .M = B * L, .C = Wd, .out_f32 = x});
+    o.tap(4, x, (size_t)B * L * Wd * 4);
     clip_tower(o, m.vis, x, B, L, Wd, Wd / 64, 0);
     float* cls = o.af32((size_t)B * Wd); bf16_t* ln = o.abf((size_t)B * Wd);
     if (!o.plan) o.check(launch_gather_rows_f32(x, cls, B, L, Wd, o.c->stream), "gather cls");
+    o.tap(5, cls, (size_t)B * Wd * 4);
     o.layernorm({.x_f32 = cls, .gamma = o.w<float>(m.lnpostg), .beta = o.w<float>(m.lnpostb), .M = B, .C = Wd, .out_bf16 = ln});
+    o.tap(6, ln, (size_t)B * Wd * 2);
     o.linear({.A0 = ln, .C0 = Wd, .W = o.w<bf16_t>(m.vproj), .M = B, .N = c.embed_dim, .out_f32 = out, .single_row = true});      // the pooled token: one row per sample
+    o.tap(7, out, (size_t)B * c.embed_dim * 4);
 }
 
 // img [b, out_ch, H, W] -> z_out [b, embed_dim, H / f, W / f]; `what`: the entry's name in messages
@@ -424,13 +449,17 @@ int rdm_to_uint8(rdm_ctx* c, const float* img, int b, int ch, int h, int w, uint
 
 int rdm_clip_encode_text(rdm_ctx* c, const int64_t* tokens, int b, float* out) {
     RDM_ENTER(c);
-    if (!c || !tokens || !out) return c ? c->fail(-1, "null argument") : -1;
+    if (!c) return -1;
+    if (b < 1) return c->fail(-1, "rdm_clip_encode_text: b = %d; at least one sequence", b);      // (before the pointers: an empty tensor has none)
+    if (!tokens || !out) return c->fail(-1, "null argument");
     if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
     return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_text_body(o, c->clip, (const long long*)tokens, b, out); });
 }
 int rdm_clip_encode_image(rdm_ctx* c, const float* image, int b, float* out) {
     RDM_ENTER(c);
-    if (!c || !image || !out) return c ? c->fail(-1, "null argument") : -1;
+    if (!c) return -1;
+    if (b < 1) return c->fail(-1, "rdm_clip_encode_image: b = %d; at least one image", b);
+    if (!image || !out) return c->fail(-1, "null argument");
     if (!c->clip.loaded) return c->fail(-1, "clip weights not loaded");
     return run_with_arena(c, c->clip.arena, c->clip.blob, [&](Ops& o) { clip_image_body(o, c->clip, image, b, out); });
 }

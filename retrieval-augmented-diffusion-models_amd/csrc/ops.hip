@@ -365,6 +365,24 @@ int rdm_op_layernorm(rdm_ctx* c, const void* x, int in_is_f32, const float* gamm
                  .out_bf16 = (bf16_t*)out, .eps = eps});
     return o.rc;
 }
+// the CLIP towers' forms (first_stage.hip clip_tower / clip_image_body): fp32 rows normalised to fp32 (visual.ln_pre), and a projection
+// added into the fp32 residual stream (x += out_proj(attn), x += c_proj(h): out_f32 may be res_f32 itself)
+int rdm_op_layernorm_f32(rdm_ctx* c, const float* x, const float* gamma, const float* beta, int M, int C, float eps, float* out) {
+    RDM_ENTER(c);
+    if (!x || !gamma || !beta || !out || M < 1 || C < 2) return c->fail(-1, "rdm_op_layernorm_f32: null argument or M < 1, C < 2");
+    Ops o = op_exec(c);
+    o.layernorm({.x_f32 = x, .gamma = gamma, .beta = beta, .M = M, .C = C, .out_f32 = out, .eps = eps});
+    return o.rc;
+}
+int rdm_op_linear_res_f32(rdm_ctx* c, const void* a, const void* w, const float* bias, const float* res_f32, float* out_f32, int M, int N, int K, int act) {
+    RDM_ENTER(c);
+    if (!a || !w || !out_f32) return c->fail(-1, "rdm_op_linear_res_f32: a, w and out_f32 required");
+    if (M < 1 || N < 2 || N % 2 || K < 64 || K % 64 || (act != ACT_NONE && act != ACT_QUICKGELU && act != ACT_SILU))
+        return c->fail(-1, "rdm_op_linear_res_f32: bad shape M=%d N=%d K=%d act=%d (N even, K a multiple of 64; no activation, QuickGELU or SiLU)", M, N, K, act);
+    Ops o = op_exec(c);
+    o.linear({.A0 = (const bf16_t*)a, .C0 = K, .W = (const bf16_t*)w, .bias = bias, .M = M, .N = N, .act = act, .res_f32 = res_f32, .out_f32 = out_f32});
+    return o.rc;
+}
 int rdm_op_self_attention(rdm_ctx* c, const void* qk, const void* vt, int B, int n, int heads, void* out) {
     RDM_ENTER(c);
     Ops o = op_exec(c);

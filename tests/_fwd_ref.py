@@ -165,22 +165,28 @@ class Linear:
     |rowvec|) with S = sum_k |alpha a_k w_k| + |b| + |rowvec| + |res| (a K-long chain of product roundings, the epilogue adds; the start
     values' (hi, lo) carriage).  SiLU / QuickGELU / GEGLU: propagated as _act_bound / _geglu_bound.  r = 2^-8 (bf16 out) or 0.  Near
     misses: the last 64-wide K slice (16 k of a one-slice K) dropped; alpha applied twice; a bias-only epilogue where the residual belongs; the row-group split one
-    tile (128 rows) off; tanh GELU; value and gate swapped; SiLU and QuickGELU exchanged."""
+    tile (128 rows) off; tanh GELU; value and gate swapped; SiLU and QuickGELU exchanged.
+    res_f32 (the CLIP towers' x += proj(h), rdm_op_linear_res_f32): the residual is fp32, NOT rounded to bf16, and is added to the finished
+    fp32 y in one rounding: e = e_y (the fp32-output model, the residual not in S) + u (|res| + |y|), r = 0.  Its near misses: the
+    residual dropped; the residual of row m + 1; the bias dropped."""
     name = "linear"
     exact = False
 
     @staticmethod
-    def make(M, N, K, act=ACT_NONE, bias=True, res=False, f32=False, alpha=1.0, rows=None, mgemm=False, seed=31):
+    def make(M, N, K, act=ACT_NONE, bias=True, res=False, f32=False, alpha=1.0, rows=None, mgemm=False, seed=31, res_f32=False):
         g = torch.Generator().manual_seed(seed)
         inp = {"a": bfr(torch.randn(M, K, generator=g)), "w": bfr(torch.randn(N, K, generator=g) * 2 / math.sqrt(K)), "act": act, "f32": f32,
                "alpha": alpha, "rows": rows, "mgemm": mgemm, "b": 0.5 * torch.randn(N, generator=g) if bias else None,
-               "res": bfr(torch.randn(M, N // 2 if act == ACT_GEGLU else N, generator=g)) if res else None}
+               "res": bfr(torch.randn(M, N // 2 if act == ACT_GEGLU else N, generator=g)) if res else None, "res_f32": res_f32}
+        if res_f32:                                          # an fp32 residual stream: full mantissas, a few times the projection's size
+            assert f32 and not res and act != ACT_GEGLU and rows is None and alpha == 1.0
+            inp["res"] = 3.0 * torch.randn(M, N, generator=g)
         if rows is not None:
             inp["rv"] = torch.randn(_cdiv(M, rows), N, generator=g)
         return inp
 
     @staticmethod
-    def pre(inp, dt, kcut=None, alpha=None, rows=None, absval=False):
+    def pre(inp, dt, kcut=None, alpha=None, rows=None, absval=False, no_bias=False):
         a, w = inp["a"].to(dt), inp["w"].to(dt)
         if absval:
             a, w = a.abs(), w.abs()
@@ -188,7 +194,7 @@ class Linear:
             a, w = a[:, :kcut], w[:, :kcut]
         al = inp["alpha"] if alpha is None else alpha
         y = (abs(al) if absval else al) * (a @ w.t())
-        if inp["b"] is not None:
+        if inp["b"] is not None and not no_bias:
             y = y + (inp["b"].to(dt).abs() if absval else inp["b"].to(dt))
         if "rv" in inp:
             rv = inp["rv"].to(dt).abs() if absval else inp["rv"].to(dt)
@@ -196,9 +202,12 @@ class Linear:
         return y
 
     @staticmethod
-    def ref(inp, dt, kcut=None, alpha=None, rows=None, no_res=False, act=None, tanh=False, swap=False):
-        y = Linear.pre(inp, dt, kcut, alpha, rows)
+    def ref(inp, dt, kcut=None, alpha=None, rows=None, no_res=False, act=None, tanh=False, swap=False, no_bias=False, res_shift=False):
+        y = Linear.pre(inp, dt, kcut, alpha, rows, no_bias=no_bias)
         act = inp["act"] if act is None else act
+        if inp.get("res_f32"):                               # added to the finished (activated) fp32 value
+            y = _act(y, act)
+            return {"out": y if no_res else y + (inp["res"].roll(-1, 0) if res_shift else inp["res"]).to(dt)}
         if act == ACT_GEGLU:
             F2 = y.shape[1] // 2
             xv, gt = (y[:, F2:], y[:, :F2]) if swap else (y[:, :F2], y[:, F2:])
@@ -216,11 +225,14 @@ class Linear:
             carried = carried + inp["b"].double().abs()
         if "rv" in inp:
             carried = carried + inp["rv"].double().abs().repeat_interleave(inp["rows"], 0)[: S.shape[0]]
-        if inp["res"] is not None:
+        if inp["res"] is not None and not inp.get("res_f32"):
             S = S + inp["res"].double().abs()
         e = (K + 8) * U * S + HILO * carried
         r = 0.0 if inp["f32"] else BF
         y = Linear.pre(inp, F64)
+        if inp.get("res_f32"):
+            z = _act(y, inp["act"])
+            return {"out": (r, _act_bound(y, e, inp["act"]) + U * (inp["res"].double().abs() + z.abs()))}
         if inp["act"] == ACT_GEGLU:
             F2 = y.shape[1] // 2
             return {"out": (r, _geglu_bound(y[:, :F2], y[:, F2:], e[:, :F2], e[:, F2:]))}
@@ -236,6 +248,10 @@ class Linear:
             m.append(("alpha applied twice", Linear.ref(inp, F64, alpha=inp["alpha"] ** 2)))
         if inp["res"] is not None:
             m.append(("bias-only epilogue (residual dropped)", Linear.ref(inp, F64, no_res=True)))
+        if inp.get("res_f32"):
+            m.append(("residual of row m + 1", Linear.ref(inp, F64, res_shift=True)))
+            if inp["b"] is not None:
+                m.append(("bias dropped", Linear.ref(inp, F64, no_bias=True)))
         if inp["rows"] is not None:
             m.append(("row-group split one tile off", Linear.ref(inp, F64, rows=inp["rows"] + 128)))
         if inp["act"] == ACT_GEGLU:
@@ -535,12 +551,14 @@ class LayerNorm:
     """LayerNorm over C -> bf16 (rdm_op_layernorm: layernorm_bf16x8_kernel for bf16 rows with C % 8 == 0, C <= 1024, else the fp32- /
     bf16-input layernorm_kernel), exact two-pass variance.  e_xh = u (d mean|x| rstd + (d + 8) |xh|), d = ceil(C / 64) + 14 (the chain of
     a row sum: a lane's elements, 6 shuffle levels); a = |gamma| e_xh + 2 u (|gamma xh| + |beta|), r = 2^-8.  Near misses: eps 1e-6
-    (small-variance rows), the statistics of the next row, unbiased variance (C = 16)."""
+    (small-variance rows), the statistics of the next row, unbiased variance (C = 16).
+    out_f32 (rdm_op_layernorm_f32, the image tower's ln_pre: fp32 rows in, fp32 rows out): the same a with r = 0 -- no output rounding
+    term -- and one more near miss, the output rounded to bf16, which a bound this tight tells from the fp32 output."""
     name = "layernorm"
     exact = False
 
     @staticmethod
-    def make(M, C, f32=False, offset=False, small_var=False, seed=71, x=None, gamma=None, beta=None):
+    def make(M, C, f32=False, offset=False, small_var=False, seed=71, x=None, gamma=None, beta=None, out_f32=False):
         g = torch.Generator().manual_seed(seed)
         if x is None:
             spread = 0.004 if small_var else 1.0
@@ -548,7 +566,7 @@ class LayerNorm:
             x = torch.randn(M, C, generator=g) * spread * (0.5 + torch.rand(M, 1, generator=g)) + off[:, None]
             x = x if f32 else bfr(x)
         return {"x": x, "f32": f32, "gamma": 1 + 0.3 * torch.randn(C, generator=g) if gamma is None else gamma,
-                "beta": 0.3 * torch.randn(C, generator=g) if beta is None else beta, "eps": 1e-5, "small_var": small_var}
+                "beta": 0.3 * torch.randn(C, generator=g) if beta is None else beta, "eps": 1e-5, "small_var": small_var, "out_f32": out_f32}
 
     @staticmethod
     def stats(x, eps, unbiased=False):
@@ -572,11 +590,13 @@ class LayerNorm:
         xh = (x - mean) * rstd
         gam, bet = inp["gamma"].double(), inp["beta"].double()
         e_xh = U * (d * x.abs().mean(1, keepdim=True) * rstd + (d + 8) * xh.abs())
-        return {"out": (BF, gam.abs() * e_xh + 2 * U * ((gam * xh).abs() + bet.abs()))}
+        return {"out": (0.0 if inp.get("out_f32") else BF, gam.abs() * e_xh + 2 * U * ((gam * xh).abs() + bet.abs()))}
 
     @staticmethod
     def misses(inp):
         m = [("statistics of the next row", LayerNorm.ref(inp, F64, shift=True))]
+        if inp.get("out_f32"):
+            m.append(("output rounded to bf16", {"out": bfr(LayerNorm.ref(inp, F64)["out"].float()).double()}))
         if inp["small_var"]:
             m.append(("eps 1e-6", LayerNorm.ref(inp, F64, eps=1e-6)))
         if inp["x"].shape[1] <= 16:
@@ -657,15 +677,18 @@ class SmallAttention:
     64 KiB / (8 D) keys (256 at D = 32, 128 at D = 64) pass through LDS in chunks, the running maximum / sum / output carried per query
     from one chunk to the next: the same key-ordered chain as one chunk, so the bound does not change.  Near misses: the scale applied
     twice; the diagonal masked (causal); the head order reversed; k and v swapped; and where more than one chunk runs: the keys beyond
-    the first chunk dropped; the last chunk alone; the per-chunk softmaxes averaged (no rescale from chunk to chunk)."""
+    the first chunk dropped; the last chunk alone; the per-chunk softmaxes averaged (no rescale from chunk to chunk).
+    fused (the CLIP towers' form): q, k, v are the column thirds of ONE [B, n, 3 H D] buffer, each read at the row pitch 3 H D; one more
+    near miss there: the k and v slices exchanged -- which is "k and v swapped", kept under its own name for the fused layout."""
     name = "small_attention"
     exact = False
 
     @staticmethod
-    def make(B, nq, nkv, H, D, causal=0, seed=91):
+    def make(B, nq, nkv, H, D, causal=0, seed=91, fused=False):
         g = torch.Generator().manual_seed(seed)
+        assert not fused or nq == nkv
         return {"q": bfr(torch.randn(B, nq, H * D, generator=g) * 1.5), "k": bfr(torch.randn(B, nkv, H * D, generator=g) * 1.5),
-                "v": bfr(torch.randn(B, nkv, H * D, generator=g)), "H": H, "D": D, "causal": causal, "scale": D ** -0.5}
+                "v": bfr(torch.randn(B, nkv, H * D, generator=g)), "H": H, "D": D, "causal": causal, "scale": D ** -0.5, "fused": fused}
 
     @staticmethod
     def ref(inp, dt, scale=None, swap=False, reverse=False, diag=False, keys=None, per_chunk=False):
@@ -698,6 +721,9 @@ class SmallAttention:
              ("k and v swapped", SmallAttention.ref(inp, F64, swap=True))]
         if inp["causal"]:
             m.append(("diagonal masked", SmallAttention.ref(inp, F64, diag=True)))
+        if inp.get("fused"):
+            m += [("k and v slices of the fused rows exchanged", SmallAttention.ref(inp, F64, swap=True)),
+                  ("the q slice read where k belongs", {"out": _attn_masked(inp, inp["q"], inp["q"], inp["v"])})]
         nkv = inp["k"].shape[1]
         kc = small_attention_chunk(nkv, inp["D"])
         if nkv > kc:
@@ -706,6 +732,11 @@ class SmallAttention:
                   ("the last chunk alone", SmallAttention.ref(inp, F64, keys=(last, nkv))),
                   ("per-chunk softmaxes averaged", SmallAttention.ref(inp, F64, per_chunk=True))]
         return m
+
+
+def _attn_masked(inp, q, k, v):
+    """SmallAttention.ref on other operands (the fused layout's column-offset near misses)"""
+    return SmallAttention.ref(dict(inp, q=q, k=k, v=v), F64)["out"]
 
 
 class XattnFused:
@@ -990,8 +1021,9 @@ _CI, _CO = ConvIn, ConvOut
 
 
 def _lin(**kw):
-    return (_L, kw, linear_path(kw["M"], kw["N"], kw["K"], kw.get("act", 0), kw.get("alpha", 1.0), kw.get("f32", False), kw.get("res", False),
-                                kw.get("rows"), kw.get("mgemm", False)))
+    path = linear_path(kw["M"], kw["N"], kw["K"], kw.get("act", 0), kw.get("alpha", 1.0), kw.get("f32", False), kw.get("res", False),
+                       kw.get("rows"), kw.get("mgemm", False))
+    return (_L, kw, path + (": f32 residual in place" if kw.get("res_f32") else ""))
 
 
 def _lnf(**kw):
@@ -1025,11 +1057,14 @@ def _cin(**kw):
 def _sm(**kw):
     kc = small_attention_chunk(kw["nkv"], kw["D"])
     path = f"small_attention_kernel<{kw['D']}>: " + ("causal, " if kw.get("causal") else "") + f"{_cdiv(kw['nkv'], kc)} key chunks"
-    return (_SM, kw, path)
+    return (_SM, kw, path + (", fused q|k|v rows" if kw.get("fused") else ""))
 
 
 def _ly(**kw):
     bf = not kw.get("f32", False) and kw["C"] % 8 == 0 and kw["C"] <= 1024
+    if kw.get("out_f32"):
+        assert kw.get("f32")
+        return (_LY, kw, "layernorm_kernel<f32>: f32 out")
     return (_LY, kw, f"layernorm_bf16x8<{1 if kw['C'] <= 512 else 2}>" if bf else f"layernorm_kernel<{'f32' if kw.get('f32') else 'bf16'}>")
 
 
@@ -1069,6 +1104,14 @@ CASES = [
     _lin(M=1064, N=256, K=256, res=True, f32=True, mgemm=True),
     _lin(M=1000, N=192, K=512, act=ACT_SILU, mgemm=True),
     _lin(M=130, N=64, K=128, act=ACT_QUICKGELU, mgemm=True),
+    # the CLIP towers' residual adds (rdm_op_linear_res_f32: fp32 residual, fp32 out, in place): the tiled kernel just above the 128-row
+    # skinny rule with one ragged tile (2 x 77 rows), ragged past 256, 192- and 128-wide column tiles, several column tiles, c_proj's
+    # reduction depth; and the fp32-out QuickGELU epilogue without a residual
+    _lin(M=154, N=128, K=128, f32=True, res_f32=True),
+    _lin(M=308, N=192, K=128, f32=True, res_f32=True),
+    _lin(M=385, N=512, K=128, f32=True, res_f32=True),
+    _lin(M=150, N=128, K=3072, f32=True, res_f32=True),
+    _lin(M=231, N=512, K=128, act=ACT_QUICKGELU, f32=True),
     # LayerNorm folded into lin4
     _lnf(M=16384, N=1152, K=384, offset=True),
     _lnf(M=33024, N=192, K=192, bias=False, small_var=True),
@@ -1138,6 +1181,10 @@ CASES = [
     _ly(M=40, C=16),
     _ly(M=40, C=16, f32=True),
     _ly(M=50, C=1280, offset=True),
+    # fp32 rows to fp32 rows (the image tower's ln_pre): the tiny tower's 5 rows of 128, one sample of ViT-B/32's 50 rows of 768
+    _ly(M=5, C=128, f32=True, out_f32=True, offset=True),
+    _ly(M=50, C=768, f32=True, out_f32=True, offset=True),
+    _ly(M=50, C=768, f32=True, out_f32=True, small_var=True),
     # attention
     (_SA, dict(B=2, n=64, H=2, mode="vt"), "flash_d32_lds_kernel<false>"),
     (_SA, dict(B=1, n=256, H=3, mode="qkv"), "flash_d32_lds_kernel<true>"),
@@ -1153,6 +1200,11 @@ CASES = [
     _sm(B=2, nq=70, nkv=257, H=2, D=32),
     _sm(B=1, nq=600, nkv=600, H=1, D=32),
     _sm(B=2, nq=200, nkv=200, H=1, D=64, causal=1),
+    # q, k, v as column slices of one [B, n, 3 H D] buffer (the CLIP towers): the text tower's 77 causal rows, the image tower's 50, and
+    # the tiny image tower's 5 (fewer keys than a chunk holds, fewer queries than a wave)
+    _sm(B=2, nq=77, nkv=77, H=2, D=64, causal=1, fused=True),
+    _sm(B=3, nq=50, nkv=50, H=2, D=64, causal=0, fused=True),
+    _sm(B=3, nq=5, nkv=5, H=2, D=64, causal=0, fused=True),
     (_XA, dict(B=2, n=64, heads=4, k=4), "xattn_fused_kernel: bias + residual"),
     (_XA, dict(B=2, n=32, heads=2, k=1, bias=False, res=False), "xattn_fused_kernel: no bias / residual"),
     (_XA, dict(B=8, n=64, heads=4, k=2), "xattn_fused_kernel: XCD block order"),
@@ -1178,4 +1230,6 @@ def bf16_out(case, inp, key):
     """does the kernel write this output as bf16 (the stand-in rounds it the same way)"""
     if case is Linear:
         return not inp["f32"]
+    if case is LayerNorm:
+        return not inp.get("out_f32")
     return case not in (HeadConv, ConvOut)

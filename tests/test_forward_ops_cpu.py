@@ -39,7 +39,10 @@ def test_case_ids_name_every_launch_path():
                    "lin4<GEGLU, WM2>", "rowvec", "sgemm", "mgemm", "LN>", "gn_onepass<NV", ", 512>", ", 1024>", "gn_stats + gn_apply",
                    "XCD block order", "layernorm_bf16x8<1>", "layernorm_bf16x8<2>", "layernorm_kernel<f32>", "layernorm_kernel<bf16>",
                    "flash_d32_lds_kernel<false>", "flash_d32_lds_kernel<true>", "flash_d32_kernel", "small_attention_kernel<32>",
-                   "small_attention_kernel<64>", "xattn_fused_kernel", "xattn_ln_fused_kernel", "head_conv_kernel"):
+                   "small_attention_kernel<64>", "xattn_fused_kernel", "xattn_ln_fused_kernel", "head_conv_kernel",
+                   # the forms only the CLIP towers run
+                   "igemm<128, 128>: f32 residual in place", "igemm<128, 192>: f32 residual in place", "layernorm_kernel<f32>: f32 out",
+                   "small_attention_kernel<64>: causal, 1 key chunks, fused q|k|v rows", "small_attention_kernel<64>: 1 key chunks, fused q|k|v rows"):
         assert kernel in paths, kernel
 
 

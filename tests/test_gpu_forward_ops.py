@@ -3,7 +3,9 @@ stem conv, GroupNorm, LayerNorm, flash and small attention, the fused cross-atte
 float64 CPU restatement of the same operation, element by element (tests/_fwd_ref.py states each bound and near miss).  Every case
 also shows that its bound discriminates: the kernel output must fall outside the bound against each near-miss reference.  Kernels that
 sum in a fixed order are called twice and must agree bitwise; for the batched tile geometries, changing one sample's input must leave
-every other sample's output bitwise unchanged."""
+every other sample's output bitwise unchanged.  The three forms only the CLIP towers run -- the tiled GEMM adding an fp32 residual into
+its fp32 output (called with the output aliased to the residual and apart: bitwise equal), LayerNorm fp32 -> fp32, small attention on
+the column thirds of one fused q|k|v buffer -- are cases like the others."""
 import os
 import subprocess
 import sys
@@ -34,6 +36,13 @@ def _run(ctx, case, inp):
         if inp["act"] == R.ACT_GEGLU:
             perm = _geglu_perm(w.shape[0])
             w = w[perm]; bias = None if bias is None else bias[perm]
+        if inp.get("res_f32"):      # the towers' x += proj(h): once into a fresh tensor, once over the residual itself -- bitwise the same
+            sep = ctx.op_linear_res_f32(b(inp["a"]), b(w), o(bias), f(inp["res"]), act=inp["act"])
+            x = f(inp["res"]).clone()
+            inplace = ctx.op_linear_res_f32(b(inp["a"]), b(w), o(bias), x, act=inp["act"], inplace=True)
+            assert inplace.data_ptr() == x.data_ptr() and sep.data_ptr() != x.data_ptr()
+            assert torch.equal(sep, inplace), "out aliased to the residual differs from out in a buffer of its own"
+            return {"out": sep}
         res = None if inp["res"] is None else b(inp["res"])
         if inp["rows"] is not None:
             return {"out": ctx.op_linear_rowvec(b(inp["a"]), b(w), o(bias), f(inp["rv"]), inp["rows"], residual=res)}
@@ -54,6 +63,8 @@ def _run(ctx, case, inp):
         x1 = b(x[..., C0:]) if x.shape[2] > C0 else None
         return {"out": ctx.op_groupnorm(b(x[..., :C0]), f(inp["gamma"]), f(inp["beta"]), inp["eps"], inp["silu"], x1)}
     if case is R.LayerNorm:
+        if inp.get("out_f32"):
+            return {"out": ctx.op_layernorm_f32(f(inp["x"]), f(inp["gamma"]), f(inp["beta"]), inp["eps"])}
         return {"out": ctx.op_layernorm(f(inp["x"]) if inp["f32"] else b(inp["x"]), f(inp["gamma"]), f(inp["beta"]), inp["eps"])}
     if case is R.SelfAttention:
         q, k, v = inp["q"], inp["k"], inp["v"]
@@ -61,6 +72,10 @@ def _run(ctx, case, inp):
             return {"out": ctx.op_self_attention_qkv(b(torch.cat([q, k, v], -1)), inp["H"])}
         return {"out": ctx.op_self_attention(b(torch.cat([q, k], -1)), b(v.transpose(1, 2)), inp["H"])}
     if case is R.SmallAttention:
+        if inp.get("fused"):        # one [B, n, 3 H D] buffer; q, k, v its column thirds at the row pitch 3 H D
+            W = inp["H"] * inp["D"]
+            qkv = b(torch.cat([inp["q"], inp["k"], inp["v"]], -1))
+            return {"out": ctx.op_small_attention(qkv[..., :W], qkv[..., W:2 * W], qkv[..., 2 * W:], inp["H"], inp["D"], inp["causal"], inp["scale"])}
         return {"out": ctx.op_small_attention(b(inp["q"]), b(inp["k"]), b(inp["v"]), inp["H"], inp["D"], inp["causal"], inp["scale"])}
     if case is R.XattnFused:
         ln = (f(inp["gamma"]), f(inp["beta"]), inp["eps"]) if inp["ln"] else None
