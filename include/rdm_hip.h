@@ -466,6 +466,27 @@ int rdm_op_knn_radius(rdm_ctx* ctx, const float* x, int n, int d, int k, float* 
  * from rdm_op_knn_radius on ref); precision = mean f(generated, Real), recall = mean f(real, Generated).  d2 as above.  m, n >= 1. */
 int rdm_op_manifold_hits(rdm_ctx* ctx, const float* probe /*[m,d]*/, int m, const float* ref /*[n,d]*/, const float* ref_radius2, int n, int d,
                          unsigned char* hit_out);
+/* Density (Naeem et al. 2020, eq. 7): density = 1 / (k M) SUM_j SUM_i 1[Y_j in B(X_i, NND_k(X_i))] over generated rows Y_j and real rows X_i.
+ * count_out [dev] int32 [m], entry i = #{ j : d2(probe_i, ref_j) <= ref_radius2[j] }: the balls of the reference set that probe i lies in
+ * (probe = generated, ref = real, ref_radius2 from rdm_op_knn_radius on ref); density = SUM count / (k m).  rdm_op_manifold_hits that counts
+ * where it ORs: count > 0 equals that entry's hit, bit for bit.  d2 as for rdm_op_knn_radius: |d2 - exact| <= 5e-7 (|a|^2 + |b|^2) for
+ * d <= 1024.  m, n >= 1. */
+int rdm_op_manifold_counts(rdm_ctx* ctx, const float* probe /*[m,d]*/, int m, const float* ref /*[n,d]*/, const float* ref_radius2 /*[n]*/,
+                           int n, int d, int32_t* count_out /*[m]*/);
+/* Coverage (the same paper, eq. 9): coverage = 1 / N SUM_i 1[exists j: Y_j in B(X_i, NND_k(X_i))] = mean over real rows i of
+ * [min_j d2(X_i, Y_j) <= radius2_i].  d2_out [dev] f32 [m], entry i = min_j d2(probe_i, ref_j), nothing left out (probe = real, ref =
+ * generated).  d2 as for rdm_op_knn_radius: |d2 - exact| <= 5e-7 (|a|^2 + |b|^2) for d <= 1024, the same value the other entries see for
+ * the pair; a probe equal to a reference row gives exactly 0.  m, n >= 1. */
+int rdm_op_nearest_d2(rdm_ctx* ctx, const float* probe /*[m,d]*/, int m, const float* ref /*[n,d]*/, int n, int d, float* d2_out /*[m]*/);
+/* KID (Binkowski et al. 2018): the unbiased MMD^2 = SUM_{i != j} k(x_i, x_j) / (m (m - 1)) + SUM_{i != j} k(y_i, y_j) / (n (n - 1))
+ * - 2 SUM_{i, j} k(x_i, y_j) / (m n) under k(x, y) = (gamma x.y + coef0)^3 (the paper: gamma = 1 / d, coef0 = 1), averaged over subsets.
+ * This entry gives the row sums of one such kernel matrix per group: rowsum_out [dev] f64 [groups, m], entry (g, i) = SUM_j (gamma
+ * probe_gi . ref_gj + coef0)^3 over the n reference rows of the SAME group, without the pair j == i (row index within the group) when
+ * exclude_same_index is non-zero: the diagonal of XX or YY.  Error statement: the dot product in fp32 on the chain of rdm_op_knn_radius,
+ * dot product within 2.5e-7 (|a|^2 + |b|^2), all later arithmetic fp64 (gamma and coef0 widened as given).  No atomics: a row's sum does
+ * not depend on m, on the group count or on where the row lands.  m, n >= 1; 1 <= groups <= 65535 and groups * max(m, n) must fit an int. */
+int rdm_op_poly3_rowsums(rdm_ctx* ctx, const float* probe /*[groups,m,d]*/, int m, const float* ref /*[groups,n,d]*/, int n, int d, int groups,
+                         int exclude_same_index, float gamma, float coef0, double* rowsum_out /*[groups,m]*/);
 /* the RARM sampler kernel alone (taming top_k_logits + softmax + multinomial as an inverse CDF in vocabulary order, after the
  * classifier-free combine lu + scale (lc - lu) and the temperature; transformer.py:237-263): logits [dev] f32 [(cfg ? 2 : 1) * b, vocab]
  * (conditional rows first), uniforms [dev] f32 [b], tokens_out [dev] int64 [b].  top_k <= 0: no filter. */

@@ -183,6 +183,9 @@ SIGNATURES = {
     "rdm_op_moments_f64": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_op_knn_radius": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_op_manifold_hits": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "rdm_op_manifold_counts": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, _P]),
+    "rdm_op_nearest_d2": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, _P]),
+    "rdm_op_poly3_rowsums": (C.c_int, [_P, _P, C.c_int, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P]),
     "rdm_op_rarm_sampler": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, _P, _P]),
     "rdm_op_rarm_sampler_top_p": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_int, C.c_float, _P, _P, _P]),
     "rdm_op_conv3x3_dgrad": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int]),
@@ -617,6 +620,54 @@ class Context:
         ref_radius2 = self._dev(ref_radius2, torch.float32)
         out = torch.empty((probe.shape[0],), device=self.device, dtype=torch.uint8)
         self._check(lib.rdm_op_manifold_hits(self._h, _ptr(probe), probe.shape[0], _ptr(ref), _ptr(ref_radius2), ref.shape[0], ref.shape[1], _ptr(out)))
+        return out
+
+    def op_manifold_counts(self, probe, ref, ref_radius2):
+        """-> int32 [m]: the number of rows j of ref with probe row i within ref_radius2[j] (squared) of them (rdm_op_manifold_counts):
+        op_manifold_hits that counts where it ORs.  probe f32 [m, d], ref f32 [n, d], ref_radius2 f32 [n]."""
+        probe = self._features("op_manifold_counts", probe, "probe"); ref = self._features("op_manifold_counts", ref, "ref")
+        if probe.shape[1] != ref.shape[1]:
+            raise RdmError(f"op_manifold_counts: probe and ref must share d, got {tuple(probe.shape)} and {tuple(ref.shape)}")
+        if not isinstance(ref_radius2, torch.Tensor) or tuple(ref_radius2.shape) != (ref.shape[0],):
+            raise RdmError(f"op_manifold_counts: ref_radius2 must be a tensor [{ref.shape[0]}], one radius per ref row")
+        ref_radius2 = self._dev(ref_radius2, torch.float32)
+        out = torch.empty((probe.shape[0],), device=self.device, dtype=torch.int32)
+        self._check(lib.rdm_op_manifold_counts(self._h, _ptr(probe), probe.shape[0], _ptr(ref), _ptr(ref_radius2), ref.shape[0], ref.shape[1], _ptr(out)))
+        return out
+
+    def op_nearest_d2(self, probe, ref):
+        """-> f32 [m]: the squared Euclidean distance from probe row i to the nearest row of ref, nothing left out (rdm_op_nearest_d2).
+        probe f32 [m, d], ref f32 [n, d]."""
+        probe = self._features("op_nearest_d2", probe, "probe"); ref = self._features("op_nearest_d2", ref, "ref")
+        if probe.shape[1] != ref.shape[1]:
+            raise RdmError(f"op_nearest_d2: probe and ref must share d, got {tuple(probe.shape)} and {tuple(ref.shape)}")
+        out = torch.empty((probe.shape[0],), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_op_nearest_d2(self._h, _ptr(probe), probe.shape[0], _ptr(ref), ref.shape[0], ref.shape[1], _ptr(out)))
+        return out
+
+    def op_poly3_rowsums(self, probe, ref, gamma, coef0=1.0, exclude_same_index=False, out=None):
+        """-> f64 [G, m] (or [m] for 2-D arguments, one group): entry (g, i) = SUM_j (gamma probe[g, i] . ref[g, j] + coef0)^3 over the rows
+        of ref's group g, without j == i when exclude_same_index (rdm_op_poly3_rowsums): dot product in fp32, the rest in fp64.
+        probe f32 [G, m, d] and ref f32 [G, n, d], or [m, d] and [n, d].  out: optional contiguous float64 tensor of the result's shape on
+        this device, written and returned."""
+        for name, x in (("probe", probe), ("ref", ref)):
+            if not isinstance(x, torch.Tensor) or x.ndim not in (2, 3):
+                raise RdmError(f"op_poly3_rowsums: {name} must be a tensor [G, rows, d] or [rows, d], got {tuple(x.shape) if isinstance(x, torch.Tensor) else type(x)}")
+        if probe.ndim != ref.ndim:
+            raise RdmError(f"op_poly3_rowsums: probe and ref must both be 3-D or both 2-D, got {tuple(probe.shape)} and {tuple(ref.shape)}")
+        flat = probe.ndim == 2
+        p3 = self._dev(probe[None] if flat else probe, torch.float32); r3 = self._dev(ref[None] if flat else ref, torch.float32)
+        if p3.shape[0] != r3.shape[0]:
+            raise RdmError(f"op_poly3_rowsums: probe has {p3.shape[0]} groups and ref {r3.shape[0]}; group g's probes see group g's refs")
+        if p3.shape[2] != r3.shape[2]:
+            raise RdmError(f"op_poly3_rowsums: probe and ref must share d, got {tuple(probe.shape)} and {tuple(ref.shape)}")
+        shape = (p3.shape[1],) if flat else (p3.shape[0], p3.shape[1])
+        if out is None:
+            out = torch.empty(shape, device=self.device, dtype=torch.float64)
+        elif not isinstance(out, torch.Tensor) or out.dtype != torch.float64 or tuple(out.shape) != shape or out.device != self.device or not out.is_contiguous():
+            raise RdmError(f"op_poly3_rowsums: out must be a contiguous float64 tensor {shape} on {self.device}")
+        self._check(lib.rdm_op_poly3_rowsums(self._h, _ptr(p3), p3.shape[1], _ptr(r3), r3.shape[1], p3.shape[2], p3.shape[0],
+                                             int(bool(exclude_same_index)), float(gamma), float(coef0), _ptr(out)))
         return out
 
     def load_clip(self, cfg: ClipCfg, blob: np.ndarray):

@@ -333,6 +333,15 @@ hipError_t launch_metric_row_norms(const float* x, float* norms, int n, int d, h
 hipError_t launch_metric_knn_radius(const float* x, const float* norms, int n, int d, int k, float* radius2, hipStream_t st);   // 1 <= k <= 8, k < n
 hipError_t launch_metric_manifold_hits(const float* probe, const float* pnorms, int m, const float* ref, const float* rnorms, const float* ref_radius2,
                                        int n, int d, unsigned char* hit, hipStream_t st);
+// the same kernel's other epilogues: count [m] = # of the balls probe i lies in; d2 [m] = the nearest ref row's d2; and, on the dot products
+// alone (no norms), rowsum f64 [groups, m] = SUM_j (gamma probe_gi . ref_gj + coef0)^3, group g = blockIdx.y, optionally without j == i
+constexpr int METRIC_MAX_GROUPS = 65535;                  // gridDim.y
+hipError_t launch_metric_manifold_counts(const float* probe, const float* pnorms, int m, const float* ref, const float* rnorms, const float* ref_radius2,
+                                         int n, int d, int* count, hipStream_t st);
+hipError_t launch_metric_nearest_d2(const float* probe, const float* pnorms, int m, const float* ref, const float* rnorms, int n, int d, float* d2,
+                                    hipStream_t st);
+hipError_t launch_metric_poly3_rowsums(const float* probe, int m, const float* ref, int n, int d, int groups, int exclude_same_index, float gamma,
+                                       float coef0, double* rowsum, hipStream_t st);
 hipError_t launch_softmax_rows(const float* s, bf16_t* p, long long rows, int n, hipStream_t st, int n_valid = 0);   // columns >= n_valid: probability 0
 hipError_t launch_clip_embed(const long long* tokens, const float* tok_emb, const float* pos_emb, float* out, int B, int L,
                              int Wd, hipStream_t st);

@@ -1,10 +1,14 @@
-// Metric arithmetic on feature sets (f32 [n, d] row-major): the moments behind the Frechet distance and the two streaming distance
-// searches behind improved precision / recall (Kynkaanniemi et al. 2019).  Three launch groups:
+// Metric arithmetic on feature sets (f32 [n, d] row-major): the moments behind the Frechet distance, the streaming distance searches
+// behind improved precision / recall (Kynkaanniemi et al. 2019) and density / coverage (Naeem et al. 2020), and the polynomial-kernel
+// row sums behind KID (Binkowski et al. 2018).  Two launch groups; metric_dist is ONE kernel with five epilogues on the same dot products:
 //   metric_moments   sum += SUM_i x_i,  outer += SUM_i x_i x_i^T            in fp64 (v_mfma_f64_16x16x4_f64)
 //   metric_dist<0>   radius2[i] = k-th smallest d2(x_i, x_j) over j != i    (self left out BY INDEX: a duplicate is a neighbour at 0)
-//   metric_dist<1>   hit[i] = OR_j  d2(probe_i, ref_j) <= radius2[j]
+//   metric_dist<1>   hit[i]     = OR_j   d2(probe_i, ref_j) <= radius2[j]
+//   metric_dist<2>   count[i]   = SUM_j  d2(probe_i, ref_j) <= radius2[j]   (int32; mode 1 with += for |=)
+//   metric_dist<3>   nearest2[i] = MIN_j d2(probe_i, ref_j)                 (nothing left out)
+//   metric_dist<4>   rowsum[g, i] = SUM_j (gamma (probe_gi . ref_gj) + coef0)^3   in fp64, optionally without j == i; no norms
 //
-// Distance arithmetic, shared by both searches:  d2(a, b) = max(0, fma(-2, a.b, |a|^2 + |b|^2)), everything fp32.  The dot product and the
+// Distance arithmetic, shared by the four searches:  d2(a, b) = max(0, fma(-2, a.b, |a|^2 + |b|^2)), everything fp32.  The dot product and the
 // two norms are the SAME two-level chain over k: inside a 32-wide chunk an fp32 fma chain from 0 in the order the fp32-input MFMA
 // (v_mfma_f32_32x32x2_f32) walks it (per 8 k: k, k+4, k+1, k+5, k+2, k+6, k+3, k+7: the lane halves of one MFMA hold k and k + 4),
 // then the chunk sums are added in ascending chunk order.  metric_row_norms_kernel restates that chain on the VALU, so a.a from the
@@ -13,10 +17,20 @@
 // one instruction sequence wherever the pair lands: it does not depend on n, m, on the tile or lane either row sits in, nor on which of
 // the two is the probe.  The reductions only compare.  Nothing here consults the deterministic switch; no atomics exist.
 //
+// The polynomial mode takes the SAME fp32 dot product (|dot - exact| <= 2.5e-7 (|a|^2 + |b|^2), the dot's half of the d2 budget) and does
+// everything after it in fp64, per pair: convert, one fma (gamma dot + coef0), two multiplies (the cube), one add into the lane's running
+// sum.  That is 5 fp64 VALU operations per pair against 2 d MFMA flops, negligible from d = 128 up: per tile a wave issues 2 d MFMAs of 64
+// cycles and 320 fp64 operations of 4 (the vector fp64 rate is half the fp32 one), 8 % of the MFMA time at d = 128 and 2 % at d = 512,
+// where a 50 000 x 50 000 product measures the same 34 ms in this mode as in the hit mode.  A lane's sum takes its
+// reference rows in ascending tile order, then ascending result register; the four lanes of a probe are added in the order (wi, h)
+// ascending.  A row sum therefore depends on the row, its group's reference rows and n alone: not on m, the group count or the block.
+//
 // Structure of metric_dist (the tiling of vqcode.hip, another reduction): a block owns 128 probe rows and walks all 128-row tiles of
 // the reference set; the reference rows are the MFMA's A operand (result rows = registers) and the probes its B operand (columns =
-// lanes), so a probe's running state -- its 8 smallest distances, or its hit flag -- lives in ONE lane; four lanes per probe are merged
-// through LDS at the end.  Nothing of size n x n is stored.
+// lanes), so a probe's running state -- its 8 smallest distances, its hit flag or count, its minimum, or its fp64 sum -- lives in ONE
+// lane; four lanes per probe are merged through LDS at the end.  Nothing of size n x n is stored.  blockIdx.y is a GROUP: probe
+// [G, M, D] and ref [G, N, D], group g's probes see group g's reference rows only (KID's subsets in one launch); all offsets are 64-bit.
+// Only the polynomial mode is launched with G > 1 (the norms and radii of the other modes are not offset).
 //
 // metric_moments: a block owns a 32 x 32 tile of the d x d outer product (tiles on and above the diagonal only, mirrored on store) and
 // a contiguous range of rows; each wave a 16 x 16 quarter in one f64 MFMA accumulator, rows taken four at a time in ascending order.
@@ -65,18 +79,26 @@ __device__ __forceinline__ void mt_insert(float (&top)[MT_K], float v) {
     }
 }
 
-// MODE 0: radius2 of the probes within their own set (probe == ref, M == N); MODE 1: manifold hits of the probes against (ref, rr2)
+enum { MT_RADIUS = 0, MT_HIT = 1, MT_COUNT = 2, MT_NEAREST = 3, MT_POLY = 4 };
+
+// MODE 0: radius2 of the probes within their own set (probe == ref, M == N); 1 / 2: manifold hits / counts of the probes against
+// (ref, rr2); 3: the nearest reference row's d2; 4: cubic-kernel row sums per group (pn, rn, rr2 unused and null).  out: f32 [M] (0, 3),
+// uint8 [M] (1), int32 [M] (2), f64 [G, M] (4)
 template <int MODE>
 __global__ __launch_bounds__(256) void metric_dist_kernel(const float* __restrict__ probe, const float* __restrict__ pn, int M,
                                                           const float* __restrict__ ref, const float* __restrict__ rn,
-                                                          const float* __restrict__ rr2, int N, int D, int kth,
-                                                          float* __restrict__ rad_out, unsigned char* __restrict__ hit_out) {
+                                                          const float* __restrict__ rr2, int N, int D, int kth, int excl, float gamma,
+                                                          float coef0, void* __restrict__ out) {
+    constexpr bool DIST = MODE != MT_POLY;                               // the modes on d2: they need the norms
+    constexpr bool BALL = MODE == MT_HIT || MODE == MT_COUNT;            // the modes that compare with a radius per reference row
     __shared__ __attribute__((aligned(16))) float sA[MT_T * MT_LD];      // reference rows [row][k]
     __shared__ __attribute__((aligned(16))) float sB[MT_T * MT_LD];      // probe rows     [row][k]
     __shared__ float sN[MT_T];                                           // |ref|^2 of the tile, +inf for rows >= N: their distance is +inf
-    __shared__ float sR[MT_T];                                           // MODE 1: radius2 of the tile's rows (-1 for rows >= N)
+    __shared__ float sR[MT_T];                                           // MODE 1, 2: radius2 of the tile's rows (-1 for rows >= N)
     const int t = threadIdx.x, lane = t & 63, wave = t >> 6, wi = wave >> 1, wj = wave & 1, r = lane & 31, h = lane >> 5;
     const long long row0 = (long long)blockIdx.x * MT_T;
+    probe += (long long)blockIdx.y * M * D;               // the group's rows
+    ref += (long long)blockIdx.y * N * D;
     const int ntiles = (N + MT_T - 1) / MT_T;
     const int nkc = D / MT_KC;
     const long long niter = (long long)ntiles * nkc;
@@ -91,10 +113,10 @@ __global__ __launch_bounds__(256) void metric_dist_kernel(const float* __restric
             ga[i] = j < N ? *(const float4*)(ref + j * D + k0 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
             gb[i] = m < M ? *(const float4*)(probe + m * D + k0 + c4) : make_float4(0.f, 0.f, 0.f, 0.f);
         }
-        if (k0 == 0 && t < MT_T) {
+        if (DIST && k0 == 0 && t < MT_T) {
             const long long j = (long long)tile * MT_T + t;
             gn = j < N ? rn[j] : __builtin_inff();
-            if (MODE == 1) gr = j < N ? rr2[j] : -1.f;
+            if (BALL) gr = j < N ? rr2[j] : -1.f;
         }
     };
 
@@ -110,14 +132,16 @@ __global__ __launch_bounds__(256) void metric_dist_kernel(const float* __restric
 #pragma unroll
     for (int tj = 0; tj < 2; tj++) {
         prow[tj] = row0 + wj * 64 + tj * 32 + r;
-        pnorm[tj] = prow[tj] < M ? pn[prow[tj]] : 0.f;
+        pnorm[tj] = DIST && prow[tj] < M ? pn[prow[tj]] : 0.f;
     }
     float top[2][MT_K];
 #pragma unroll
     for (int tj = 0; tj < 2; tj++)
 #pragma unroll
         for (int i = 0; i < MT_K; i++) top[tj][i] = __builtin_inff();
-    int hit[2] = {0, 0};
+    int hit[2] = {0, 0};                                  // MODE 1: flag; MODE 2: count
+    float best[2] = {__builtin_inff(), __builtin_inff()};
+    double psum[2] = {0.0, 0.0};
 
     if (niter > 0) fetch(0);
     for (long long it = 0; it < niter; it++) {
@@ -129,7 +153,7 @@ __global__ __launch_bounds__(256) void metric_dist_kernel(const float* __restric
             *(float4*)(sA + row * MT_LD + c4) = ga[i];
             *(float4*)(sB + row * MT_LD + c4) = gb[i];
         }
-        if (kc == 0 && t < MT_T) { sN[t] = gn; if (MODE == 1) sR[t] = gr; }
+        if (DIST && kc == 0 && t < MT_T) { sN[t] = gn; if (BALL) sR[t] = gr; }
         __syncthreads();
         if (it + 1 < niter) fetch(it + 1);                // in flight under this chunk's MFMAs
 #pragma unroll
@@ -165,17 +189,32 @@ __global__ __launch_bounds__(256) void metric_dist_kernel(const float* __restric
 #pragma unroll
                 for (int q = 0; q < 16; q++) {
                     const int cl = wi * 64 + ti * 32 + (q & 3) + 8 * (q >> 2) + 4 * h;
-                    const float n = sN[cl];
                     const long long j = (long long)tile * MT_T + cl;
+                    if (MODE == MT_POLY) {
+                        // fp64 from here: k = gamma dot + coef0, k^3 into the lane's sum; rows past N and (excl) the pair j == i add nothing
+#pragma unroll
+                        for (int tj = 0; tj < 2; tj++) {
+                            const double v = fma((double)gamma, (double)tot[ti][tj][q], (double)coef0);
+                            tot[ti][tj][q] = 0.f;
+                            const bool keep = j < N && !(excl && j == prow[tj]);
+                            psum[tj] += keep ? (v * v) * v : 0.0;
+                        }
+                        continue;
+                    }
+                    const float n = sN[cl];
 #pragma unroll
                     for (int tj = 0; tj < 2; tj++) {
                         float d2 = fmaxf(fmaf(-2.f, tot[ti][tj][q], pnorm[tj] + n), 0.f);
                         tot[ti][tj][q] = 0.f;
-                        if (MODE == 0) {
+                        if (MODE == MT_RADIUS) {
                             if (j == prow[tj]) d2 = __builtin_inff();          // self, by index
                             mt_insert(top[tj], d2);
-                        } else {
+                        } else if (MODE == MT_HIT) {
                             hit[tj] |= d2 <= sR[cl] ? 1 : 0;
+                        } else if (MODE == MT_COUNT) {
+                            hit[tj] += d2 <= sR[cl] ? 1 : 0;
+                        } else {
+                            best[tj] = fminf(best[tj], d2);
                         }
                     }
                 }
@@ -183,7 +222,7 @@ __global__ __launch_bounds__(256) void metric_dist_kernel(const float* __restric
     }
     // block reduction: probe (wj, tj, r) has four partial states (wi, h)
     __syncthreads();
-    if (MODE == 0) {
+    if (MODE == MT_RADIUS) {
         float* rs = sA;                                   // [128][4][8] floats = 16 KB of sA's 18
 #pragma unroll
         for (int tj = 0; tj < 2; tj++)
@@ -191,21 +230,37 @@ __global__ __launch_bounds__(256) void metric_dist_kernel(const float* __restric
             for (int i = 0; i < MT_K; i++) rs[((wj * 64 + tj * 32 + r) * 4 + wi * 2 + h) * MT_K + i] = top[tj][i];
         __syncthreads();
         if (t < MT_T && row0 + t < M) {
-            float best[MT_K];
+            float best8[MT_K];
 #pragma unroll
-            for (int i = 0; i < MT_K; i++) best[i] = rs[t * 4 * MT_K + i];
-            for (int s = MT_K; s < 4 * MT_K; s++) mt_insert(best, rs[t * 4 * MT_K + s]);
-            float res = best[0];
+            for (int i = 0; i < MT_K; i++) best8[i] = rs[t * 4 * MT_K + i];
+            for (int s = MT_K; s < 4 * MT_K; s++) mt_insert(best8, rs[t * 4 * MT_K + s]);
+            float res = best8[0];
 #pragma unroll
-            for (int i = 1; i < MT_K; i++) res = (i == kth - 1) ? best[i] : res;
-            rad_out[row0 + t] = res;
+            for (int i = 1; i < MT_K; i++) res = (i == kth - 1) ? best8[i] : res;
+            ((float*)out)[row0 + t] = res;
         }
-    } else {
+    } else if (BALL) {
         int* rs = (int*)sA;
 #pragma unroll
         for (int tj = 0; tj < 2; tj++) rs[(wj * 64 + tj * 32 + r) * 4 + wi * 2 + h] = hit[tj];
         __syncthreads();
-        if (t < MT_T && row0 + t < M) hit_out[row0 + t] = (unsigned char)((rs[t * 4] | rs[t * 4 + 1] | rs[t * 4 + 2] | rs[t * 4 + 3]) != 0);
+        if (t < MT_T && row0 + t < M) {
+            if (MODE == MT_HIT) ((unsigned char*)out)[row0 + t] = (unsigned char)((rs[t * 4] | rs[t * 4 + 1] | rs[t * 4 + 2] | rs[t * 4 + 3]) != 0);
+            else ((int*)out)[row0 + t] = rs[t * 4] + rs[t * 4 + 1] + rs[t * 4 + 2] + rs[t * 4 + 3];
+        }
+    } else if (MODE == MT_NEAREST) {
+        float* rs = sA;
+#pragma unroll
+        for (int tj = 0; tj < 2; tj++) rs[(wj * 64 + tj * 32 + r) * 4 + wi * 2 + h] = best[tj];
+        __syncthreads();
+        if (t < MT_T && row0 + t < M) ((float*)out)[row0 + t] = fminf(fminf(rs[t * 4], rs[t * 4 + 1]), fminf(rs[t * 4 + 2], rs[t * 4 + 3]));
+    } else {
+        double* rs = (double*)sA;                         // [128][4] doubles = 4 KB
+#pragma unroll
+        for (int tj = 0; tj < 2; tj++) rs[(wj * 64 + tj * 32 + r) * 4 + wi * 2 + h] = psum[tj];
+        __syncthreads();
+        // the four lanes of a probe in the order (wi, h) ascending
+        if (t < MT_T && row0 + t < M) ((double*)out)[(long long)blockIdx.y * M + row0 + t] = ((rs[t * 4] + rs[t * 4 + 1]) + rs[t * 4 + 2]) + rs[t * 4 + 3];
     }
 }
 
@@ -305,14 +360,36 @@ hipError_t launch_metric_row_norms(const float* x, float* norms, int n, int d, h
 
 hipError_t launch_metric_knn_radius(const float* x, const float* norms, int n, int d, int k, float* radius2, hipStream_t st) {
     if (!metric_dim_supported(d) || k < 1 || k > MT_K || k >= n) return hipErrorInvalidValue;
-    metric_dist_kernel<0><<<(n + MT_T - 1) / MT_T, 256, 0, st>>>(x, norms, n, x, norms, nullptr, n, d, k, radius2, nullptr);
+    metric_dist_kernel<MT_RADIUS><<<(n + MT_T - 1) / MT_T, 256, 0, st>>>(x, norms, n, x, norms, nullptr, n, d, k, 0, 0.f, 0.f, radius2);
     return hipGetLastError();
 }
 
 hipError_t launch_metric_manifold_hits(const float* probe, const float* pnorms, int m, const float* ref, const float* rnorms, const float* ref_radius2,
                                        int n, int d, unsigned char* hit, hipStream_t st) {
     if (!metric_dim_supported(d) || m < 1 || n < 1) return hipErrorInvalidValue;
-    metric_dist_kernel<1><<<(m + MT_T - 1) / MT_T, 256, 0, st>>>(probe, pnorms, m, ref, rnorms, ref_radius2, n, d, 0, nullptr, hit);
+    metric_dist_kernel<MT_HIT><<<(m + MT_T - 1) / MT_T, 256, 0, st>>>(probe, pnorms, m, ref, rnorms, ref_radius2, n, d, 0, 0, 0.f, 0.f, hit);
+    return hipGetLastError();
+}
+
+hipError_t launch_metric_manifold_counts(const float* probe, const float* pnorms, int m, const float* ref, const float* rnorms, const float* ref_radius2,
+                                         int n, int d, int* count, hipStream_t st) {
+    if (!metric_dim_supported(d) || m < 1 || n < 1) return hipErrorInvalidValue;
+    metric_dist_kernel<MT_COUNT><<<(m + MT_T - 1) / MT_T, 256, 0, st>>>(probe, pnorms, m, ref, rnorms, ref_radius2, n, d, 0, 0, 0.f, 0.f, count);
+    return hipGetLastError();
+}
+
+hipError_t launch_metric_nearest_d2(const float* probe, const float* pnorms, int m, const float* ref, const float* rnorms, int n, int d, float* d2,
+                                    hipStream_t st) {
+    if (!metric_dim_supported(d) || m < 1 || n < 1) return hipErrorInvalidValue;
+    metric_dist_kernel<MT_NEAREST><<<(m + MT_T - 1) / MT_T, 256, 0, st>>>(probe, pnorms, m, ref, rnorms, nullptr, n, d, 0, 0, 0.f, 0.f, d2);
+    return hipGetLastError();
+}
+
+hipError_t launch_metric_poly3_rowsums(const float* probe, int m, const float* ref, int n, int d, int groups, int exclude_same_index, float gamma,
+                                       float coef0, double* rowsum, hipStream_t st) {
+    if (!metric_dim_supported(d) || m < 1 || n < 1 || groups < 1 || groups > METRIC_MAX_GROUPS) return hipErrorInvalidValue;
+    metric_dist_kernel<MT_POLY><<<dim3((m + MT_T - 1) / MT_T, groups), 256, 0, st>>>(probe, nullptr, m, ref, nullptr, nullptr, n, d, 0,
+                                                                                     exclude_same_index ? 1 : 0, gamma, coef0, rowsum);
     return hipGetLastError();
 }
 

@@ -75,6 +75,15 @@ static int metric_dim_check(rdm_ctx* c, const char* op, int d) {
     if (!metric_dim_supported(d)) return c->fail(-1, "%s: d = %d; the kernels take multiples of 32 from 32 to 4096", op, d);
     return 0;
 }
+// |probe_i|^2 [m] and |ref_j|^2 [n] into the sampler scratch, for the modes of metric_dist_kernel that work on d2
+static int metric_pair_norms(rdm_ctx* c, const float* probe, int m, const float* ref, int n, int d, float** pn, float** rn) {
+    const size_t mb = ((size_t)m * 4 + 255) & ~(size_t)255;
+    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, mb + (size_t)n * 4));
+    *pn = (float*)c->samp; *rn = (float*)(c->samp + mb);
+    RDM_CHECK_HIP(c, launch_metric_row_norms(probe, *pn, m, d, c->stream));
+    RDM_CHECK_HIP(c, launch_metric_row_norms(ref, *rn, n, d, c->stream));
+    return 0;
+}
 // Frechet distance (Heusel et al. 2017): the sufficient statistics of mu = sum / n and Sigma = (outer - n mu mu^T) / (n - 1)
 int rdm_op_moments_f64(rdm_ctx* c, const float* x, int n, int d, double* sum, double* outer) {
     RDM_ENTER(c);
@@ -106,12 +115,46 @@ int rdm_op_manifold_hits(rdm_ctx* c, const float* probe, int m, const float* ref
     if (m < 1 || n < 1) return c->fail(-1, "rdm_op_manifold_hits: m = %d, n = %d; at least one row each", m, n);
     if (!probe || !ref || !ref_radius2 || !hit_out) return c->fail(-1, "rdm_op_manifold_hits: null argument");
     RDM_TRY(metric_dim_check(c, "rdm_op_manifold_hits", d));
-    const size_t mb = ((size_t)m * 4 + 255) & ~(size_t)255;
-    RDM_TRY(ensure_bytes(c, &c->samp, &c->samp_bytes, mb + (size_t)n * 4));
-    float* pn = (float*)c->samp; float* rn = (float*)(c->samp + mb);
-    RDM_CHECK_HIP(c, launch_metric_row_norms(probe, pn, m, d, c->stream));
-    RDM_CHECK_HIP(c, launch_metric_row_norms(ref, rn, n, d, c->stream));
+    float *pn, *rn;
+    RDM_TRY(metric_pair_norms(c, probe, m, ref, n, d, &pn, &rn));
     RDM_CHECK_HIP(c, launch_metric_manifold_hits(probe, pn, m, ref, rn, ref_radius2, n, d, hit_out, c->stream));
+    return 0;
+}
+// density (Naeem et al. 2020, eq. 7): 1 / (k M) SUM_j SUM_i 1[Y_j in B(X_i, NND_k(X_i))]; the inner sum over the real rows i is count[j]
+int rdm_op_manifold_counts(rdm_ctx* c, const float* probe, int m, const float* ref, const float* ref_radius2, int n, int d, int32_t* count_out) {
+    RDM_ENTER(c);
+    if (m < 1 || n < 1) return c->fail(-1, "rdm_op_manifold_counts: m = %d, n = %d; at least one row each", m, n);
+    if (!probe || !ref || !ref_radius2 || !count_out) return c->fail(-1, "rdm_op_manifold_counts: null argument");
+    RDM_TRY(metric_dim_check(c, "rdm_op_manifold_counts", d));
+    float *pn, *rn;
+    RDM_TRY(metric_pair_norms(c, probe, m, ref, n, d, &pn, &rn));
+    RDM_CHECK_HIP(c, launch_metric_manifold_counts(probe, pn, m, ref, rn, ref_radius2, n, d, count_out, c->stream));
+    return 0;
+}
+// coverage (the same paper, eq. 9): 1 / N SUM_i 1[exists j: Y_j in B(X_i, NND_k(X_i))] = mean_i [min_j d2(X_i, Y_j) <= r2_i]; the minimum
+int rdm_op_nearest_d2(rdm_ctx* c, const float* probe, int m, const float* ref, int n, int d, float* d2_out) {
+    RDM_ENTER(c);
+    if (m < 1 || n < 1) return c->fail(-1, "rdm_op_nearest_d2: m = %d, n = %d; at least one row each", m, n);
+    if (!probe || !ref || !d2_out) return c->fail(-1, "rdm_op_nearest_d2: null argument");
+    RDM_TRY(metric_dim_check(c, "rdm_op_nearest_d2", d));
+    float *pn, *rn;
+    RDM_TRY(metric_pair_norms(c, probe, m, ref, n, d, &pn, &rn));
+    RDM_CHECK_HIP(c, launch_metric_nearest_d2(probe, pn, m, ref, rn, n, d, d2_out, c->stream));
+    return 0;
+}
+// KID (Binkowski et al. 2018, eq. 4 with k(x, y) = (x.y / d + 1)^3): the row sums of the three kernel matrices of the unbiased MMD^2, one
+// group per subset.  No norms, no scratch
+int rdm_op_poly3_rowsums(rdm_ctx* c, const float* probe, int m, const float* ref, int n, int d, int groups, int exclude_same_index, float gamma,
+                         float coef0, double* rowsum_out) {
+    RDM_ENTER(c);
+    if (m < 1 || n < 1) return c->fail(-1, "rdm_op_poly3_rowsums: m = %d, n = %d; at least one row each", m, n);
+    if (groups < 1 || groups > METRIC_MAX_GROUPS)
+        return c->fail(-1, "rdm_op_poly3_rowsums: groups = %d; one launch takes 1 to %d groups", groups, METRIC_MAX_GROUPS);
+    if (!probe || !ref || !rowsum_out) return c->fail(-1, "rdm_op_poly3_rowsums: null argument");
+    RDM_TRY(metric_dim_check(c, "rdm_op_poly3_rowsums", d));
+    if ((long long)groups * (m > n ? m : n) > 2147483647LL)
+        return c->fail(-1, "rdm_op_poly3_rowsums: groups = %d times max(m, n) = %d rows does not fit an int", groups, m > n ? m : n);
+    RDM_CHECK_HIP(c, launch_metric_poly3_rowsums(probe, m, ref, n, d, groups, exclude_same_index, gamma, coef0, rowsum_out, c->stream));
     return 0;
 }
 // ---- backward ops (kernels in backward.hip)

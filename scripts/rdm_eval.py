@@ -6,7 +6,12 @@ no evaluation script; this one has no counterpart there.
     python scripts/rdm_eval.py --real DIR --fake DIR --clip_ckpt ViT-B-32.pt --gpu 0
 
 prints ONE JSON line: {"fid", "precision", "recall", "n_real", "n_gen", "k", "features", "normalized"}.  The features are the tower's un-normalised
-pooled embedding (--normalize divides each by its norm).  --synthetic runs on the seeded synthetic CLIP weights: the numbers then measure
+pooled embedding (--normalize divides each by its norm).  Two more metrics on request, for the sets the first three are weak on:
+
+    --kid [--kid_subsets 100 --kid_subset_size 1000 --kid_seed 0]    adds "kid", "kid_std" (and the three settings): Kernel Inception Distance
+                (Binkowski et al. 2018) on the same features, mean and std over the subsets; unbiased at any set size, where FID is not
+    --density_coverage [--dc_k 5]                                     adds "density", "coverage", "dc_k" (Naeem et al. 2020): density does not
+                saturate at 1 as precision does, coverage is the recall that generated outliers cannot inflate  --synthetic runs on the seeded synthetic CLIP weights: the numbers then measure
 nothing about image quality, the path runs without checkpoint files.
 """
 import argparse
@@ -29,6 +34,12 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--batch_size", type=int, default=64, help="images per CLIP forward")
     parser.add_argument("--normalize", default=False, action="store_true", help="L2-normalise the features (default: un-normalised)")
     parser.add_argument("--synthetic", default=False, action="store_true", help="seeded synthetic CLIP weights instead of --clip_ckpt")
+    parser.add_argument("--kid", default=False, action="store_true", help="also report KID (mean and std over subsets)")
+    parser.add_argument("--kid_subsets", type=int, default=100, help="subsets KID averages over (0: one estimate on the whole sets)")
+    parser.add_argument("--kid_subset_size", type=int, default=1000, help="rows per KID subset (clamped to the smaller set)")
+    parser.add_argument("--kid_seed", type=int, default=0, help="seed of the subset draw")
+    parser.add_argument("--density_coverage", default=False, action="store_true", help="also report density and coverage")
+    parser.add_argument("--dc_k", type=int, default=5, help="neighbour rank of the density / coverage balls (1..8)")
     return parser
 
 
@@ -37,6 +48,12 @@ def parse_args(argv=None) -> argparse.Namespace:
     opt = parser.parse_args(argv)
     if not 1 <= opt.k <= 8:
         parser.error(f"--k must lie in 1..8, got {opt.k}")
+    if not 1 <= opt.dc_k <= 8:
+        parser.error(f"--dc_k must lie in 1..8, got {opt.dc_k}")
+    if opt.kid_subsets < 0:
+        parser.error(f"--kid_subsets must be 0 (the whole sets) or more, got {opt.kid_subsets}")
+    if opt.kid_subset_size < 2:
+        parser.error(f"--kid_subset_size must be at least 2 (the unbiased estimate leaves the diagonal out), got {opt.kid_subset_size}")
     if opt.batch_size < 1:
         parser.error(f"--batch_size must be positive, got {opt.batch_size}")
     if opt.gpu < 0:
@@ -44,6 +61,11 @@ def parse_args(argv=None) -> argparse.Namespace:
     if opt.clip_ckpt is None and not opt.synthetic:
         parser.error("pass --clip_ckpt <ViT-B/32 state_dict>, or --synthetic for the seeded synthetic weights")
     return opt
+
+
+def extras(opt):
+    """The `extra` of rdm_amd.metrics.evaluate that the flags ask for."""
+    return tuple(name for name, on in (("kid", opt.kid), ("density_coverage", opt.density_coverage)) if on)
 
 
 def list_images(folder):
@@ -82,8 +104,13 @@ def main(argv=None):
     sd = synthetic.clip_state_dict(_lib.make_clip_cfg()) if opt.synthetic else torch.load(opt.clip_ckpt, map_location="cpu")
     model = ClipImageRetriever(state_dict=sd, ctx=ctx)
     res = metrics.evaluate(model, image_batches(list_images(opt.real), opt.batch_size), image_batches(list_images(opt.fake), opt.batch_size),
-                           k=opt.k, batch=opt.batch_size, normalize=opt.normalize)
+                           k=opt.k, batch=opt.batch_size, normalize=opt.normalize, extra=extras(opt), kid_subsets=opt.kid_subsets,
+                           kid_subset_size=opt.kid_subset_size, kid_seed=opt.kid_seed, dc_k=opt.dc_k)
     res.update(k=opt.k, features="clip-vit-b32-synthetic" if opt.synthetic else "clip-vit-b32", normalized=bool(opt.normalize))
+    if opt.kid:
+        res.update(kid_subsets=opt.kid_subsets, kid_subset_size=opt.kid_subset_size, kid_seed=opt.kid_seed)
+    if opt.density_coverage:
+        res.update(dc_k=opt.dc_k)
     print(json.dumps(res))
     ctx.close()
     return res

@@ -1,15 +1,18 @@
 #!/usr/bin/env python3
-"""Distances between the samplers of ONE model, in CLIP-feature FID and precision / recall (rdm_amd.metrics): the shipped synthetic UNet
+"""Distances between the samplers of ONE model, in CLIP-feature FID, KID, precision / recall and density / coverage (rdm_amd.metrics): the shipped synthetic UNet
 + VQ-f4 decoder at B = 64 (CFG 2.0, k = 4 neighbours) draws the same seeds -- starting latents and conditioning from the library's
 counter-based generator, rows 0 .. seeds - 1 of `--noise_seed` -- with DDIM-200 as the converged stand-in, then again with each `name:S`
 given (default ddim:50 plms:25 dpmpp:20 unipc:10 unipc:8), and every set is compared with the DDIM-200 set on the features of the
-synthetic CLIP ViT-B/32 image tower.
+synthetic CLIP ViT-B/32 image tower.  At the default 2048 rows of 512 features a covariance has four rows per dimension and the Frechet
+distance is biased; KID (mean +- std over `--kid_subsets` subsets of `--kid_subset_size` rows) is not.  Precision and recall OR over the
+reference balls and saturate; density counts the balls and coverage uses the reference set's balls alone (k = `--dc_k`).
 
 With random weights these numbers are NOT image quality: they say how far a sampler's output distribution lies from the converged
 sampler's of the same model, in the units a trained checkpoint would be reported in.  Prints the box's calibration probe and one line
 per sampler on stderr, one JSON line on stdout.
 
-    python tools/sampler_quality.py [--seeds 2048] [--batch 64] [--reference ddim:200] [ddim:50 plms:25 ...]
+    python tools/sampler_quality.py [--seeds 2048] [--batch 64] [--reference ddim:200] [--kid_subsets 100] [--kid_subset_size 1000] [--dc_k 5]
+                                    [ddim:50 plms:25 ...]
 """
 import argparse
 import json
@@ -29,6 +32,10 @@ def main():
     ap.add_argument("--batch", type=int, default=64)
     ap.add_argument("--noise_seed", type=int, default=2024)
     ap.add_argument("--k", type=int, default=3)
+    ap.add_argument("--kid_subsets", type=int, default=100)
+    ap.add_argument("--kid_subset_size", type=int, default=1000)
+    ap.add_argument("--kid_seed", type=int, default=0)
+    ap.add_argument("--dc_k", type=int, default=5)
     a = ap.parse_args()
     if a.seeds % a.batch:
         raise SystemExit("--seeds must be a multiple of --batch")
@@ -87,14 +94,19 @@ def main():
     ref_stats, ref_f = features(a.reference)
     out = {"seeds": a.seeds, "batch": B, "noise_seed": a.noise_seed, "k": a.k, "reference": a.reference, "features": "clip-vit-b32-synthetic, un-normalised",
            "calibration": {"mfma_probe_tflops": round(tf, 1), "hbm_stream_gbps": round(gb, 1)},
-           "trace_cov_reference": round(float(ref_stats.cov().trace()), 4), "fid": {}, "precision": {}, "recall": {}}
+           "kid_subsets": a.kid_subsets, "kid_subset_size": a.kid_subset_size, "kid_seed": a.kid_seed, "dc_k": a.dc_k,
+           "trace_cov_reference": round(float(ref_stats.cov().trace()), 4), "fid": {}, "kid": {}, "kid_std": {}, "precision": {}, "recall": {},
+           "density": {}, "coverage": {}}
     for run in a.runs:
         stats, f = features(run)
         fid = metrics.frechet_distance(ref_stats, stats)
         p, r = metrics.precision_recall(ctx, ref_f, f, k=a.k)
+        kid, kid_std = metrics.kernel_distance(ctx, ref_f, f, subsets=a.kid_subsets, subset_size=a.kid_subset_size, seed=a.kid_seed)
+        dens, cov = metrics.density_coverage(ctx, ref_f, f, k=a.dc_k)
         out["fid"][run], out["precision"][run], out["recall"][run] = round(fid, 5), round(p, 4), round(r, 4)
-        print(f"{run} against {a.reference}: FID {fid:.5f} (Tr Sigma of the reference {out['trace_cov_reference']}), precision {p:.4f}, recall {r:.4f}",
-              file=sys.stderr, flush=True)
+        out["kid"][run], out["kid_std"][run], out["density"][run], out["coverage"][run] = float(f"{kid:.5e}"), float(f"{kid_std:.3e}"), round(dens, 4), round(cov, 4)
+        print(f"{run} against {a.reference}: FID {fid:.5f} (Tr Sigma of the reference {out['trace_cov_reference']}), KID {kid:.5e} +- {kid_std:.2e}, "
+              f"precision {p:.4f}, recall {r:.4f}, density {dens:.4f}, coverage {cov:.4f}", file=sys.stderr, flush=True)
     print(json.dumps(out))
     ctx.close()
 
