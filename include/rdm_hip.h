@@ -252,6 +252,55 @@ int rdm_ddim_sample_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, uint64_t see
 int rdm_ddpm_sample_seeded(rdm_ctx* ctx, const rdm_ddpm_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
                            float* z_out);
 
+/* ---- image-to-image on the DDIM schedule (ldm DDIMSampler.stochastic_encode / encode / decode; the reference's vendored ddim.py stops
+ * before them) ------------------------------------------------------------------------------------
+ * The schedule of args->S has `total` ascending timesteps ts[0 .. total-1] (total may exceed S, as in rdm_ddim_sample), levels
+ * a_t[i] = alphas_cumprod[ts[i]] and a_prev[i] = alphas_cumprod[0] for i = 0, else alphas_cumprod[ts[i-1]].  "Level index i" is a_t[i].
+ *
+ * rdm_ddim_decode: x_latent [dev] f32 [B,C,H,W] is taken to be at level index t_start - 1; the DDIM step runs at indices
+ * t_start - 1 ... 0 -- t_start forwards -- with the step arithmetic, CFG batch doubling, eta, temperature and intermediates rule of
+ * rdm_ddim_sample over t_start steps (n_inter = rdm_ddim_num_intermediates(t_start, log_every_t)).  1 <= t_start <= total;
+ * t_start == total is rdm_ddim_sample, bit for bit.  noise [dev] f32 [t_start,B,C,H,W] or NULL (required when eta > 0; consumed in
+ * loop order).  rdm_ddim_decode_seeded: step i of THIS call (counted from 0) applies the normals of (seed, stream 1, step i, row0 + b),
+ * as rdm_ddim_sample_seeded; x_latent is required.
+ *
+ * rdm_ddim_encode: deterministic DDIM inversion, t_enc steps up the schedule (1 <= t_enc <= total).  Step i = 0 .. t_enc - 1 moves the
+ * iterate from level a_prev[i] to level a_t[i]:
+ *     e = e_c (scale == 1) | e_u + scale (e_c - e_u);  pred_x0 = (x - sqrt(1 - a_prev[i]) e) / sqrt(a_prev[i]);
+ *     x <- sqrt(a_t[i]) pred_x0 + sqrt(1 - a_t[i]) e
+ * with the UNet evaluated on the current iterate at the TARGET timestep ts[i] (not ldm's loop index, not the current level's timestep:
+ * DESIGN.md section 3 has the measurement).  The result is at level index t_enc - 1: what rdm_ddim_decode(t_start = t_enc) expects.
+ * args->eta must be 0; args->unconditional_guidance_scale is the inversion's own scale (1 unless the caller knows better: guided
+ * inversion diverges).  x_inter [dev] f32 [n_inter,B,C,H,W] or NULL: the iterate after the steps with i % log_every_t == 0 or
+ * i == t_enc - 1 (n_inter = rdm_ddim_num_intermediates(t_enc, log_every_t)).
+ *
+ * All three return -1 with a message, and leave the context usable, for a t_start / t_enc outside [1, total], a null pointer, a missing
+ * uncond at scale > 1, and eta != 0 on encode. */
+int rdm_ddim_decode(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, const float* x_latent, const float* cond, const float* uncond,
+                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter);
+int rdm_ddim_decode_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, uint64_t seed, int64_t row0, const float* x_latent,
+                           const float* cond, const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter);
+int rdm_ddim_encode(rdm_ctx* ctx, const rdm_ddim_args* args, int t_enc, const float* x0, const float* cond, const float* uncond,
+                    float* z_out, float* x_inter);
+/* The inversion step kernel alone on caller-owned [dev] f32 buffers of n elements (eps: 2n under cfg, [cond | uncond]): pred_x0 =
+ * (x - sqrt_one_minus_a_cur e) / sqrt_a_cur, x_out = sqrt_a_next pred_x0 + sqrt_one_minus_a_next e.  x_out may be x; x_dup and pred_x0
+ * may be NULL.  float4 accesses when n % 4 == 0 and every operand is 16-byte aligned, else scalar ones. */
+int rdm_op_ddim_inverse_step(rdm_ctx* ctx, const float* x, const float* eps, long long n, int cfg, float scale, float sqrt_a_cur,
+                             float sqrt_one_minus_a_cur, float sqrt_a_next, float sqrt_one_minus_a_next, float* x_out,
+                             float* x_dup_or_null, float* pred_x0_or_null);
+/* ldm stochastic_encode without a noise tensor: out = sqrt_a x0 + sqrt_1ma z over B rows of per_row elements, z the normals of
+ * (seed, stream 0, step 0, row0 + b) drawn in registers -- the normals a seeded sampling call starts from, so rows [row0, row0 + B) may
+ * be split over calls.  per_row % 4 == 0 and 16-byte aligned x0 / out are required (-1 otherwise).  out may be x0. */
+int rdm_op_q_sample_seeded(rdm_ctx* ctx, const float* x0, int64_t B, int64_t per_row, float sqrt_a, float sqrt_1ma, uint64_t seed,
+                           int64_t row0, float* out);
+/* One guided UNet forward exactly as the sampling loops run it (rdm_unet_forward on [x | x], [cond | uncond] computes the same function
+ * through other kernel configurations: every sample's own prefix, no zero-context shortcut, the time embedding per row): x [dev] f32
+ * [B,Cin,H,W] at the one timestep t; cond, uncond [dev] f32 [B,k,ctx_dim]; eps_out [dev] f32 [2B,Cout,H,W], rows cond | uncond.  What a
+ * caller's own loop uses when its iterates must be the native loop's -- the per-step path of DDIMSampler.encode: a step up the schedule
+ * carries a difference in eps on undamped. */
+int rdm_unet_forward_guided(rdm_ctx* ctx, const float* x, int64_t t, const float* cond, const float* uncond, int B, int k, int H, int W,
+                            float* eps_out);
+
 /* ---- first stage: LatentDiffusion.decode_first_stage -> VQModelInterface.decode
  *      (called at rdm/models/diffusion/ddpm.py:840, 981). z [dev] f32 [b,3,h,w] -> img [dev] f32 [b,3,H,W];
  * indices_out [dev] int32 [b*h*w] or NULL. */

@@ -136,6 +136,12 @@ SIGNATURES = {
     "rdm_op_randn": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P]),
     "rdm_ddim_sample_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "rdm_ddpm_sample_seeded": (C.c_int, [_P, C.POINTER(DdpmArgs), C.c_uint64, C.c_int64, _P, _P, _P]),
+    "rdm_unet_forward_guided": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
+    "rdm_ddim_decode": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "rdm_ddim_decode_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "rdm_ddim_encode": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, _P, _P]),
+    "rdm_op_ddim_inverse_step": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
+    "rdm_op_q_sample_seeded": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_int64, _P]),
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
     "rdm_vq_quantize": (C.c_int, [_P, _P, C.c_int, _P, _P]),
@@ -814,13 +820,26 @@ class Context:
         self._check(lib.rdm_unet_forward(self._h, _ptr(x), _ptr(t), _ptr(context), b, context.shape[1], H, W, _ptr(out)))
         return out
 
+    def unet_forward_guided(self, x, t, cond, uncond):
+        """rdm_unet_forward_guided: the UNet on [x | x] against [cond | uncond] at the one timestep t, through the kernel configurations
+        the sampling loops run it in (shared prefix of the doubled batch, zero-context shortcut, time-embedding table) -> eps
+        [2B, Cout, H, W], rows cond | uncond."""
+        x, cond, uncond = (self._dev(v, torch.float32) for v in (x, cond, uncond))
+        self._check_sampler_shapes("unet_forward_guided", x, cond, uncond)
+        b, _, H, W = x.shape
+        out = torch.empty((2 * b, self.unet_cfg.out_channels, H, W), device=self.device, dtype=torch.float32)
+        self._check(lib.rdm_unet_forward_guided(self._h, _ptr(x), int(t), _ptr(cond), _ptr(uncond), b, cond.shape[1], H, W, _ptr(out)))
+        return out
+
     def _sampler_call(self, what, fn, Args, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=None, nodes=None,
-                      noise=None, x_shape=None, **fields):
+                      noise=None, x_shape=None, run_steps=None, want_pred_x0=True, **fields):
         """What ddim_sample, plms_sample, dpmpp_sample and unipc_sample share: device casts, the fp32 alphas_cumprod array, the step
         count (of DDIM's S-step schedule, or of the node list), shape and guidance checks, the outputs.  Args(**fields) plus the fields
         every sampler has is the argument struct, fn(handle, args, x_T, cond, uncond, z, x_inter, pred_x0_inter) the library call;
         noise: a [steps, B, C, H, W] stack to shape-check; x_shape: the latent shape of a seeded call without x_T (fn then gets a null
-        x_T and the library draws the start).  -> (z, x_inter, pred_x0_inter)."""
+        x_T and the library draws the start); run_steps: the steps a decode / encode call runs of the S-step schedule, in [1, its
+        length] -- what then sizes the noise stack and the intermediates; want_pred_x0 False: no pred_x0_inter is allocated (fn gets null:
+        the inversion logs x only).  -> (z, x_inter, pred_x0_inter)."""
         x_T, cond, uncond = (None if t is None else self._dev(t, torch.float32) for t in (x_T, cond, uncond))
         x_arg = x_T
         if x_T is None:
@@ -833,6 +852,10 @@ class Context:
             nd = _nodes_array(nodes)
             steps = nd.shape[0] - 1
             fields.update(n_nodes=nd.shape[0], nodes=nd.ctypes.data_as(C.POINTER(C.c_int)))
+        if run_steps is not None:
+            if not 1 <= int(run_steps) <= steps:
+                raise RdmError(f"{what}: the step count must lie in [1, {steps}] (the schedule of S={S}), got {run_steps}")
+            steps = int(run_steps)
         self._check_sampler_shapes(what, x_T, cond, uncond, noise, steps)
         if scale > 1.0 and uncond is None:
             raise RdmError(f"{what}: unconditional_conditioning is required when unconditional_guidance_scale > 1")
@@ -844,7 +867,7 @@ class Context:
         if want_intermediates:
             n = lib.rdm_ddim_num_intermediates(steps, log_every_t)
             xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
-            pi = torch.empty_like(xi)
+            pi = torch.empty_like(xi) if want_pred_x0 else None
         self._check(fn(self._h, C.byref(a), _ptr(x_arg), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
         return z, xi, pi
 
@@ -867,6 +890,69 @@ class Context:
         return self._sampler_call("ddim_sample", lambda h, a, x, c, u, *out: lib.rdm_ddim_sample_seeded(h, a, seed, row0, x, c, u, *out),
                                   DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
                                   x_shape=x_shape, eta=eta, temperature=temperature)
+
+    def ddim_decode(self, S, t_start, x_latent, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
+                    temperature=1.0, want_intermediates=False, seed=None, row0=0):
+        """rdm_ddim_decode (ldm DDIMSampler.decode): the DDIM loop of the S-step schedule from x_latent at level index t_start - 1 down
+        to index 0, t_start forwards; t_start = the schedule's length is ddim_sample.  noise: a [t_start, B, C, H, W] stack for
+        eta > 0; with `seed` rdm_ddim_decode_seeded: step i of this call takes the library's (seed, stream 1, step i, row0 + b), and
+        `noise` must be None.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
+        if x_latent is None:
+            raise RdmError("ddim_decode: x_latent is required")
+        t_start = int(t_start)
+        if seed is None:
+            noise = None if noise is None else self._dev(noise, torch.float32)
+            return self._sampler_call("ddim_decode", lambda h, a, x, c, u, *out: lib.rdm_ddim_decode(h, a, t_start, x, c, u, _ptr(noise), *out),
+                                      DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+                                      noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
+        if noise is not None:
+            raise RdmError("ddim_decode: give a seed or a noise stack, not both")
+        seed, row0 = _noise_seed("ddim_decode", seed, row0, x_latent.shape[0])
+        return self._sampler_call("ddim_decode", lambda h, a, x, c, u, *out: lib.rdm_ddim_decode_seeded(h, a, t_start, seed, row0, x, c, u, *out),
+                                  DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+                                  run_steps=t_start, eta=eta, temperature=temperature)
+
+    def ddim_encode(self, S, t_enc, x0, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False, eta=0.0):
+        """rdm_ddim_encode: deterministic DDIM inversion of x0, t_enc steps up the S-step schedule with the UNet at each step's target
+        timestep; the result is at level index t_enc - 1, what ddim_decode(t_start=t_enc) expects.  scale: the inversion's own guidance
+        scale.  eta is there to be refused: it must be 0.  Returns (z, x_inter): the iterate after the steps the rule
+        i % log_every_t == 0 or i == t_enc - 1 logs, None unless want_intermediates."""
+        if x0 is None:
+            raise RdmError("ddim_encode: x0 is required")
+        if eta != 0.0:
+            raise RdmError(f"ddim_encode: eta must be 0 (the inversion is deterministic), got {eta}")
+        t_enc = int(t_enc)
+        z, xi, _ = self._sampler_call("ddim_encode", lambda h, a, x, c, u, z, xi, pi: lib.rdm_ddim_encode(h, a, t_enc, x, c, u, z, xi),
+                                      DdimArgs, x0, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+                                      run_steps=t_enc, want_pred_x0=False, eta=0.0, temperature=1.0)
+        return z, xi
+
+    def op_ddim_inverse_step(self, x, eps, cfg, scale, sqrt_a_cur, sqrt_one_minus_a_cur, sqrt_a_next, sqrt_one_minus_a_next, x_out, x_dup=None,
+                             pred_x0=None):
+        """The DDIM inversion step kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
+        [cond | uncond]): pred_x0 = (x - sqrt_one_minus_a_cur e) / sqrt_a_cur, x_out = sqrt_a_next pred_x0 + sqrt_one_minus_a_next e.
+        x_out may be x; x_dup / pred_x0 may be None.  Writes into the given outputs."""
+        n = x.numel()
+        if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in (x_out, x_dup, pred_x0)):
+            raise RdmError("op_ddim_inverse_step: operand sizes do not match x")
+        self._check(lib.rdm_op_ddim_inverse_step(self._h, _ptr(x), _ptr(eps), n, int(bool(cfg)), float(scale), float(sqrt_a_cur),
+                                                 float(sqrt_one_minus_a_cur), float(sqrt_a_next), float(sqrt_one_minus_a_next), _ptr(x_out),
+                                                 _ptr(x_dup), _ptr(pred_x0)))
+
+    def op_q_sample_seeded(self, x0, sqrt_a, sqrt_1ma, seed, row0=0, out=None):
+        """sqrt_a x0 + sqrt_1ma z on x0 [B, ...] (fp32, device), z the library's starting-latent normals (seed, stream 0, step 0,
+        row0 + b) drawn in the pass that applies them: no noise tensor (rdm_op_q_sample_seeded).  The elements per row must be a
+        multiple of 4 and x0 / out 16-byte aligned.  out: a tensor of x0's size to write into (may be x0)."""
+        if x0.ndim < 2 or x0.dtype != torch.float32 or not x0.is_cuda or not x0.is_contiguous():
+            raise RdmError("op_q_sample_seeded: x0 must be a contiguous fp32 device tensor [B, ...]")
+        B, per_row = int(x0.shape[0]), int(x0[0].numel())
+        seed, row0 = _noise_seed("op_q_sample_seeded", seed, row0, B)
+        if out is None:
+            out = torch.empty_like(x0)
+        elif out.dtype != torch.float32 or out.numel() != x0.numel() or not out.is_cuda or not out.is_contiguous():
+            raise RdmError("op_q_sample_seeded: out must be a contiguous fp32 device tensor of x0's size")
+        self._check(lib.rdm_op_q_sample_seeded(self._h, _ptr(x0), B, per_row, float(sqrt_a), float(sqrt_1ma), seed, row0, _ptr(out)))
+        return out
 
     @staticmethod
     def _seeded_shape(what, x_T, cond, shape):

@@ -138,6 +138,23 @@ struct UnipcStepParams {
     int cfg, order_c, order_p;                               // order_c 0..3, order_p 1..3
 };
 
+// One step of deterministic DDIM inversion (rdm_ddim_encode), from the level whose sqrt(alpha), sqrt(1 - alpha) are sa_c, s1m_c UP to the
+// level of sa_n, s1m_n: e = CFG(eps), pred_x0 = (x - s1m_c e) / sa_c, x_out = sa_n pred_x0 + s1m_n e.  The four scalars are the host's
+// float64 values rounded to fp32.  x_out may be x: a thread reads its elements of x before it writes them.
+struct DdimInverseStepParams {
+    const float* x; const float* eps;                        // eps: [n] rows (cfg == 0) or [2n] (cond | uncond)
+    float* x_out; float* x_dup; float* pred_x0;              // x_dup, pred_x0 may be null
+    long long n;                                             // B*C*H*W
+    float sa_c, s1m_c, sa_n, s1m_n, scale;
+    int cfg;
+};
+
+// The forward process with the noise generated in registers (rdm_op_q_sample_seeded): out = sqrt_a x0 + sqrt_1ma z, z the normals of
+// (seed, stream 0, step 0, row0 + b) -- a seeded sampling call's starting latent.  rows x per_row elements, per_row % 4 == 0.
+struct QSampleSeededParams {
+    const float* x0; float* out; unsigned long long seed; long long rows, per_row; uint32_t row0; float sqrt_a, sqrt_1ma;
+};
+
 struct DdpmStepParams {
     const float* x; const float* eps; const float* noise; float* x_prev; long long n;
     float sqrt_recip, sqrt_recipm1, coef1, coef2, log_var; int clip, nonzero; float temperature;
@@ -315,6 +332,8 @@ hipError_t launch_rng_fill(const RngFillParams& p, bool normal, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
 hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);
 hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st);
+hipError_t launch_ddim_inverse_step(const DdimInverseStepParams& p, hipStream_t st);
+hipError_t launch_q_sample_seeded(const QSampleSeededParams& p, hipStream_t st);     // hipErrorInvalidValue: per_row % 4 or an operand not 16-byte aligned
 hipError_t launch_vq_quantize(const float* z, const float* codebook, int n_embed, const float* pq_w, const float* pq_b,
                               float* out, int* idx_out, int B, int HW, int quantize, hipStream_t st);
 // nearest-code search of a wide-latent VQ first stage (vqcode.hip): idx[m] = argmin_j |e_j|^2 - 2 z_m . e_j on fp32-input MFMAs, first minimum on ties

@@ -690,6 +690,32 @@ hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st) {
     return launch_step(p.n, {p.u, p.eps, p.eps + (p.cfg ? p.n : 0), p.xc_prev, p.h1, p.h2, p.h3, p.xc_out, p.u_next, p.x_dup, p.m_store, p.pred_x0}, p, unipc_step_kernel<4>, unipc_step_kernel<1>, st);
 }
 
+// ------------------------------------------------------------------ DDIM inversion step (fp32, eta = 0)
+// One step UP the schedule (rdm_ddim_encode; Song et al. 2021's ODE run in reverse, the form of ldm DDIMSampler.encode): CFG combine,
+// pred_x0 = (x - s1m_c e) / sa_c at the CURRENT level, x_out = sa_n pred_x0 + s1m_n e at the NEXT one, the four scalars computed by the
+// host in float64.  True division, no FMA contraction, as the other step kernels.  x_out may be x.  V = 4: float4 accesses (the launcher
+// checks n % 4 and alignment).
+template <int V>
+__global__ __launch_bounds__(256) void ddim_inverse_step_kernel(DdimInverseStepParams p) {
+#pragma clang fp contract(off)
+    const long long nv = p.n / V;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * V;
+        float e[V], x[V], x0[V], xo[V];
+        step_guided_eps<V>(p.eps, p.n, i, p.cfg, p.scale, e);
+        step_ld<V>(p.x, i, x);
+#pragma unroll
+        for (int k = 0; k < V; k++) { x0[k] = (x[k] - p.s1m_c * e[k]) / p.sa_c; xo[k] = p.sa_n * x0[k] + p.s1m_n * e[k]; }
+        step_st<V>(p.x_out, i, xo);
+        if (p.x_dup) step_st<V>(p.x_dup, i, xo);
+        if (p.pred_x0) step_st<V>(p.pred_x0, i, x0);
+    }
+}
+hipError_t launch_ddim_inverse_step(const DdimInverseStepParams& p, hipStream_t st) {
+    return launch_step(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.x_out, p.x_dup, p.pred_x0}, p, ddim_inverse_step_kernel<4>,
+                       ddim_inverse_step_kernel<1>, st);
+}
+
 // out[r, :] = x[r, :] + bias[:]   (bf16 rows, 8 columns per thread).  Cross-attention of a sample whose neighbours are all-zero
 // vectors -- the unconditional half of a guided batch, rdm/models/diffusion/ddpm.py:673-680 -- is exactly to_out.bias: K = V = 0
 // gives uniform attention over zero values (rdm/modules/attention.py:52-72), so t2 = t1 + b_o without any GEMM.
@@ -832,6 +858,29 @@ hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams&
     if (!seeded_step_ok(p.n, g.per_row, {p.x, p.eps, p.x_prev})) return hipErrorInvalidValue;
     const int grid = (int)std::min<long long>((p.n / 4 + 255) / 256, 2048);
     ddpm_step_seeded_kernel<<<grid, 256, 0, st>>>(p, g);
+    return hipGetLastError();
+}
+
+// The forward process on a noise value that never reaches memory: out = sqrt_a x0 + sqrt_1ma z with z the starting-latent normals
+// (stream 0, step 0) of the element's (row, block), derived from the flat vector index as in ddim_step_seeded_kernel.  Both products
+// are rounded before the sum (no FMA contraction), so the result is the one of the same expression on rdm_op_randn's output.
+__global__ __launch_bounds__(256) void q_sample_seeded_kernel(QSampleSeededParams p) {
+#pragma clang fp contract(off)
+    const long long bpr = p.per_row >> 2, nv = p.rows * bpr;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * 4, r = v / bpr;
+        float z[4], x[4], o[4];
+        philox_normal4(p.seed, (uint32_t)(v - r * bpr), 0u, p.row0 + (uint32_t)r, RDM_RNG_STREAM_XT, z);
+        step_ld<4>(p.x0, i, x);
+#pragma unroll
+        for (int k = 0; k < 4; k++) { const float a = p.sqrt_a * x[k], b = p.sqrt_1ma * z[k]; o[k] = a + b; }
+        step_st<4>(p.out, i, o);
+    }
+}
+hipError_t launch_q_sample_seeded(const QSampleSeededParams& p, hipStream_t st) {
+    if (p.rows <= 0 || p.per_row <= 0 || p.rows > (1ll << 62) / p.per_row || !seeded_step_ok(p.rows * p.per_row, p.per_row, {p.x0, p.out})) return hipErrorInvalidValue;
+    const int grid = (int)std::min<long long>((p.rows * (p.per_row / 4) + 255) / 256, 2048);
+    q_sample_seeded_kernel<<<grid, 256, 0, st>>>(p);
     return hipGetLastError();
 }
 

@@ -1,5 +1,6 @@
 // The five sampling loops of librdm_hip (DDIM, PLMS, DPM-Solver++(2M), UniPC, DDPM): their schedules, SamplerRun (one sampling
-// call's scratch, tables and UNet forward), the rdm_*_sample entries, the device-noise entries and the two step-kernel op entries.
+// call's scratch, tables and UNet forward), the rdm_*_sample entries, the device-noise entries, DDIM image-to-image (rdm_ddim_decode: the
+// DDIM loop begun part-way down the schedule; rdm_ddim_encode: the loop that runs UP it) and the step-kernel op entries.
 // Calls into unet_exec.hip through the three functions host.h declares (unet_prepare_kv, unet_emb_table, unet_forward_impl) and
 // into the launch_* of kernels.h.  The loops are the reference's
 //   DDIMSampler                     rdm/models/diffusion/ddim.py:27-268
@@ -62,6 +63,7 @@ struct SamplerRun {
     rdm_ctx* c; int B, nb, k, H, W, total; long long n1;           // n1: elements of x for B rows; total: ts.size()
     float *x, *x_dup, *eps, *extra[4]; long long* tdev; const float* emb_table;
     int log_every_t = 0, n_logged = 0; float *x_inter = nullptr, *pred_x0_inter = nullptr;     // intermediates (DDPM keeps none)
+    bool ascending = false;       // the encode loop: the intermediates rule reads the loop step itself as the schedule index
     static size_t al(size_t v) { return (v + 255) & ~(size_t)255; }
     // a: the entry's args (batch, k, channels, height, width); uncond: null for an unguided call; log_every / x_inter_out / pred_x0_out:
     // the entry's intermediates arguments; n_extra <= 4.  The caller has checked that the UNet is loaded.
@@ -106,7 +108,7 @@ struct SamplerRun {
     }
     // intermediates of loop step `step` (0 .. total - 1; the rule counts the index down from total - 1): where the step kernel writes
     // pred_x0, then the copy of the new x
-    bool logs(int step) const { const int index = total - 1 - step; return (index % log_every_t == 0) || (index == total - 1); }
+    bool logs(int step) const { const int index = ascending ? step : total - 1 - step; return (index % log_every_t == 0) || (index == total - 1); }
     float* pred_x0_slot(int step) const { return (logs(step) && pred_x0_inter) ? pred_x0_inter + (size_t)n_logged * n1 : nullptr; }
     int log_x(int step) {
         if (!logs(step)) return 0;
@@ -141,8 +143,9 @@ struct HistoryRing {
 };
 
 // The DDIM loop of rdm_ddim_sample (ns null: the step noise is read from the stack `noise`) and rdm_ddim_sample_seeded (ns: it is generated
-// in the step kernel, and a null x_T is drawn).
-static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
+// in the step kernel, and a null x_T is drawn), and of the two rdm_ddim_decode entries: n_run steps down from level index n_run - 1
+// (n_run < 0: the whole schedule).  The run is the loop over the schedule cut to its first n_run entries.
+static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, int n_run, const float* x_T, const float* cond, const float* uncond,
                             const float* noise, const NoiseSeed* ns, float* z_out, float* x_inter, float* pred_x0_inter) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     bool cfg;
@@ -153,6 +156,10 @@ static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T
     } else if (a->eta != 0.f && !noise) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
+    if (n_run >= 0) {
+        if (n_run < 1 || n_run > (int)ts.size()) return c->fail(-1, "ddim decode: t_start must lie in [1, %d], got %d", (int)ts.size(), n_run);
+        ts.resize((size_t)n_run);
+    }
     const int total = (int)ts.size();
     std::vector<float> sg(total);
     for (int i = 0; i < total; i++) {
@@ -184,14 +191,61 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
                     const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    return ddim_sample_impl(c, a, x_T, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
+    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
 }
 int rdm_ddim_sample_seeded(rdm_ctx* c, const rdm_ddim_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
                            const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
     const NoiseSeed ns{seed, row0};
-    return ddim_sample_impl(c, a, x_T, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
+    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
+}
+
+// ldm DDIMSampler.decode: the DDIM loop from a latent at level index t_start - 1
+int rdm_ddim_decode(rdm_ctx* c, const rdm_ddim_args* a, int t_start, const float* x_latent, const float* cond, const float* uncond,
+                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_latent || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    if (t_start < 1) return c->fail(-1, "ddim decode: t_start must be at least 1, got %d", t_start);
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
+}
+int rdm_ddim_decode_seeded(rdm_ctx* c, const rdm_ddim_args* a, int t_start, uint64_t seed, int64_t row0, const float* x_latent, const float* cond,
+                           const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_latent || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    if (t_start < 1) return c->fail(-1, "ddim decode: t_start must be at least 1, got %d", t_start);
+    const NoiseSeed ns{seed, row0};
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
+}
+
+// Deterministic DDIM inversion (rdm_ddim_encode's header comment): t_enc steps UP the schedule, step i from level a_prev[i] to a_t[i] with
+// the UNet on the current iterate at the TARGET timestep ts[i].  The scalars are float64 square roots of the fp32 alphas, rounded.
+int rdm_ddim_encode(rdm_ctx* c, const rdm_ddim_args* a, int t_enc, const float* x0, const float* cond, const float* uncond, float* z_out,
+                    float* x_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x0 || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
+    if (a->eta != 0.f) return c->fail(-1, "ddim encode: eta must be 0 (the inversion is deterministic)");
+    bool cfg;
+    RDM_TRY(sampler_guidance(c, "ddim encode", a->unconditional_guidance_scale, uncond, &cfg));
+    std::vector<int> ts; std::vector<float> at, ap, s1m;
+    RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
+    if (t_enc < 1 || t_enc > (int)ts.size()) return c->fail(-1, "ddim encode: t_enc must lie in [1, %d], got %d", (int)ts.size(), t_enc);
+    ts.resize((size_t)t_enc);
+    SamplerRun run;
+    run.ascending = true;
+    RDM_TRY(run.begin(c, a, ts, x0, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, nullptr, 0));
+    for (int i = 0; i < t_enc; i++) {
+        RDM_TRY(run.forward(i));
+        const double ac = (double)ap[i], an = (double)at[i];
+        DdimInverseStepParams p{};
+        p.x = run.x; p.eps = run.eps; p.x_out = run.x; p.x_dup = run.x_dup; p.n = run.n1;
+        p.sa_c = (float)std::sqrt(ac); p.s1m_c = (float)std::sqrt(1.0 - ac); p.sa_n = (float)std::sqrt(an); p.s1m_n = (float)std::sqrt(1.0 - an);
+        p.scale = a->unconditional_guidance_scale; p.cfg = cfg ? 1 : 0;
+        RDM_CHECK_HIP(c, launch_ddim_inverse_step(p, c->stream));
+        RDM_TRY(run.log_x(i));
+    }
+    return run.finish(z_out);
 }
 
 // ldm PLMSSampler.plms_sampling / p_sample_plms (eta = 0): DDIM's schedule, timesteps and intermediates, total + 1 forwards.  The
@@ -557,6 +611,49 @@ int rdm_op_randn(rdm_ctx* c, uint64_t seed, int64_t row0, int64_t B, int64_t per
     RDM_ENTER(c);
     if (!c) return -1;
     return op_rng_fill(c, "rdm_op_randn", seed, row0, B, per_row, step, stream, out, true);
+}
+
+// ---- one guided forward the way the sampling loops run it: a one-step SamplerRun without an update (K/V projected once, the trailing
+// zero-context rows and the B-row prefix of the doubled batch shared, the timestep's embedding row from the table).  eps_out: [2B] rows,
+// cond | uncond.
+int rdm_unet_forward_guided(rdm_ctx* c, const float* x, int64_t t, const float* cond, const float* uncond, int B, int k, int H, int W,
+                            float* eps_out) {
+    RDM_ENTER(c);
+    if (!x || !cond || !uncond || !eps_out) return c->fail(-1, "null argument");
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
+    if (B < 1 || k < 1 || H < 1 || W < 1 || t < 0 || t > 0x7fffffffll)
+        return c->fail(-1, "rdm_unet_forward_guided: bad shape B=%d k=%d H=%d W=%d or timestep %lld", B, k, H, W, (long long)t);
+    rdm_ddim_args a{};
+    a.batch = B; a.k = k; a.channels = c->unet.cfg.in_channels; a.height = H; a.width = W;
+    SamplerRun run;
+    RDM_TRY(run.begin(c, &a, std::vector<int>{(int)t}, x, cond, uncond, 1, nullptr, nullptr, 0));
+    RDM_TRY(run.forward(0));
+    RDM_CHECK_HIP(c, hipMemcpyAsync(eps_out, run.eps, (size_t)run.n1 * 2 * 4, hipMemcpyDeviceToDevice, c->stream));
+    return 0;
+}
+
+// ---- the inversion step and the seeded forward process alone
+int rdm_op_ddim_inverse_step(rdm_ctx* c, const float* x, const float* eps, long long n, int cfg, float scale, float sqrt_a_cur,
+                             float sqrt_one_minus_a_cur, float sqrt_a_next, float sqrt_one_minus_a_next, float* x_out, float* x_dup, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_ddim_inverse_step: bad argument");
+    DdimInverseStepParams p{};
+    p.x = x; p.eps = eps; p.x_out = x_out; p.x_dup = x_dup; p.pred_x0 = pred_x0; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale;
+    p.sa_c = sqrt_a_cur; p.s1m_c = sqrt_one_minus_a_cur; p.sa_n = sqrt_a_next; p.s1m_n = sqrt_one_minus_a_next;
+    RDM_CHECK_HIP(c, launch_ddim_inverse_step(p, c->stream));
+    return 0;
+}
+int rdm_op_q_sample_seeded(rdm_ctx* c, const float* x0, int64_t B, int64_t per_row, float sqrt_a, float sqrt_1ma, uint64_t seed, int64_t row0,
+                           float* out) {
+    RDM_ENTER(c);
+    if (!c) return -1;
+    if (!x0 || !out) return c->fail(-1, "rdm_op_q_sample_seeded: null argument");
+    RDM_TRY(check_noise_rows(c, "rdm_op_q_sample_seeded", row0, B, per_row));
+    const QSampleSeededParams p{x0, out, seed, B, per_row, (uint32_t)row0, sqrt_a, sqrt_1ma};
+    const hipError_t e = launch_q_sample_seeded(p, c->stream);
+    if (e == hipErrorInvalidValue) return c->fail(-1, "rdm_op_q_sample_seeded: per_row must be a multiple of 4 and x0, out 16-byte aligned");
+    RDM_CHECK_HIP(c, e);
+    return 0;
 }
 
 // ---- the DPM-Solver++ and UniPC step kernels alone

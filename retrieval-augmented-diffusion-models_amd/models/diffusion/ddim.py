@@ -9,6 +9,10 @@ first stage's codebook by the native quantiser (rdm_vq_quantize).  ddim_use_orig
 reference that branch reads `self.model.ddim_sigmas_for_original_num_steps` (ddim.py:249), a buffer make_schedule registers on the
 SAMPLER (:52), so it ends in AttributeError there -- dead code, not a feature to mirror.  Unlike the reference, nothing is forced
 onto a "cuda" device string (ddim.py:21-25) and `--seed` style RNG comes from the caller's torch generator.
+
+Image-to-image -- `stochastic_encode`, `encode`, `decode`, which ldm's DDIMSampler has and the reference's vendored copy stops before -- is
+added on ldm's surface at the end of the class: the noised start, deterministic DDIM inversion and the partial decode, each a native
+loop or kernel (rdm_op_q_sample_seeded, rdm_ddim_encode, rdm_ddim_decode) with a per-step path behind `callback`.
 """
 import numpy as np
 import torch
@@ -48,6 +52,7 @@ class _SamplerBase(object):
 
     def make_schedule(self, ddim_num_steps, ddim_discretize="uniform", ddim_eta=0., verbose=True):
         self.ddim_timesteps = make_ddim_timesteps(ddim_discretize, ddim_num_steps, self.ddpm_num_timesteps, verbose)
+        self.ddim_num_steps, self.ddim_eta = int(ddim_num_steps), float(ddim_eta)      # what encode / decode hand to the native loops
         ac = self.model.alphas_cumprod.detach().float().cpu()
         assert ac.shape[0] == self.ddpm_num_timesteps, 'alphas have to be defined for each timestep'
         self.register_buffer('alphas_cumprod', ac)
@@ -209,12 +214,14 @@ class DDIMSampler(_SamplerBase):
     def _python_loop(self, cond, img, callback, img_callback, log_every_t, temperature, eta, scale, uc, to_cpu, mask=None,
                      x0=None, noise_dropout=0., score_corrector=None, corrector_kwargs=None, random_guiding='none',
                      timesteps=None, content_cond=None, style_cond=None, noise=None, q_noise=None, quantize_denoised=False,
-                     noise_seed=None, noise_row0=0):
+                     noise_seed=None, noise_row0=0, ts_all=None):
         """Per-step path of ddim.py:143-209 (callbacks, inpainting mask, style / content conditioning by SNR band, timestep
         subset, noise dropout, score corrector): native UNet forward per step, torch elementwise update.  `noise` / `q_noise`
         [native]: optional explicit stacks [steps, B, C, H, W] for the update noise and for q_sample of the masked region;
-        `noise_seed` [native]: step i's update noise is the library's (stream 1, step i), what the native seeded loop applies."""
-        ts_all = self._timestep_subset(timesteps)
+        `noise_seed` [native]: step i's update noise is the library's (stream 1, step i), what the native seeded loop applies.
+        `ts_all` [native]: the ascending timesteps to run down (decode: the schedule's first t_start) instead of `timesteps`' subset."""
+        if ts_all is None:
+            ts_all = self._timestep_subset(timesteps)
         total_steps = ts_all.shape[0]
         intermediates = {'x_inter': [img], 'pred_x0': [img]}
         b = img.shape[0]
@@ -274,3 +281,142 @@ class DDIMSampler(_SamplerBase):
             noise = torch.nn.functional.dropout(noise, p=noise_dropout)
         x_prev = a_prev.sqrt() * pred_x0 + dir_xt + noise
         return x_prev, pred_x0
+
+    # ---- image-to-image (ldm DDIMSampler.stochastic_encode / encode / decode; the reference's vendored ddim.py stops before them).
+    # make_schedule(S) first, as in ldm.  "Level index i" is ddim_alphas[i]; DESIGN.md section 3 "Image-to-image" has the definitions.
+    @staticmethod
+    def img2img_steps(strength, total):
+        """strength in (0, 1] -> the steps n of a `total`-step schedule an image-to-image call runs: min(total, max(1, int(strength *
+        total))).  The start is noised to level index n - 1 and decode(t_start=n) begins there, so strength 1.0 runs the whole schedule."""
+        strength = float(strength)
+        if not 0. < strength <= 1.:
+            raise ValueError(f"strength must lie in (0, 1], got {strength}")
+        return min(int(total), max(1, int(strength * int(total))))
+
+    def _level_index(self, what, name, v, lo):
+        """An integer (or a tensor of equal integers, as ldm passes t) in [lo, total] / [lo, total - 1]."""
+        if isinstance(v, torch.Tensor):
+            flat = v.reshape(-1)
+            if flat.numel() < 1 or not bool((flat == flat[0]).all()):
+                raise ValueError(f"{what}: {name} must be one level for the whole batch")
+            v = flat[0].item()
+        total = self.ddim_timesteps.shape[0]
+        hi = total if lo == 1 else total - 1
+        if int(v) != v or not lo <= int(v) <= hi:
+            raise ValueError(f"{what}: {name} must be an integer in [{lo}, {hi}] for this schedule of {total} timesteps, got {v}")
+        return int(v)
+
+    def _level_scalars(self, a):
+        """sqrt(a), sqrt(1 - a) in float64 from the fp32 alpha, as python floats (the native loops round them to fp32)."""
+        a = float(a)
+        return float(np.sqrt(a)), float(np.sqrt(1. - a))
+
+    @torch.no_grad()
+    def stochastic_encode(self, x0, t, use_original_steps=False, noise=None, noise_seed=None, noise_row0=0):
+        """ldm stochastic_encode: sqrt(a_t[t]) x0 + sqrt(1 - a_t[t]) z for level index t.  noise_seed / noise_row0 [native]: z is the
+        library's starting-latent normals of (seed, stream 0, step 0, noise_row0 + b), drawn in the kernel that applies them -- what a
+        seeded sampling call starts from; no noise tensor exists.  Otherwise `noise`, or torch's generator as ldm does."""
+        self._refuse_original_steps(use_original_steps)
+        if noise is not None and noise_seed is not None:
+            raise ValueError("noise_seed and an explicit noise select different noise sources: give one of them")
+        t = self._level_index("stochastic_encode", "t", t, 0)
+        sa, s1m = self._level_scalars(self.ddim_alphas[t])
+        if noise_seed is not None:
+            return self.model.ctx.op_q_sample_seeded(x0.to(self.model.device).float().contiguous(), sa, s1m, noise_seed, row0=noise_row0)
+        if noise is None:
+            noise = torch.randn_like(x0)
+        return np.float32(sa).item() * x0 + np.float32(s1m).item() * noise.to(x0.device)
+
+    @torch.no_grad()
+    def p_invert_ddim(self, x, c, t, index, unconditional_guidance_scale=1., unconditional_conditioning=None):
+        """One inversion step of the per-step path: from level a_prev[index] up to a_t[index] with the model at `t` (encode passes the
+        TARGET timestep ddim_timesteps[index]).  A guided step takes the model's apply_model_guided where it has one: the forward of the
+        native loops (apply_model on the doubled batch runs other kernel configurations, and a step UP the schedule carries an eps
+        difference on undamped where a sampling step contracts it), so the iterates of the per-step path are the native loop's.
+        -> (x_next, pred_x0)."""
+        if unconditional_guidance_scale > 1. and unconditional_conditioning is not None and hasattr(self.model, "apply_model_guided"):
+            e_c, e_u = self.model.apply_model_guided(x, int(t.reshape(-1)[0]), c, unconditional_conditioning)
+            e_t = e_u + unconditional_guidance_scale * (e_c - e_u)
+        else:
+            e_t = self._model_output(x, t, c, unconditional_conditioning if unconditional_guidance_scale > 1. else None,
+                                     unconditional_guidance_scale)
+        sa_c, s1m_c = self._level_scalars(self.ddim_alphas_prev[index])
+        sa_n, s1m_n = self._level_scalars(self.ddim_alphas[index])
+        full = lambda v: torch.full_like(e_t, float(np.float32(v)))
+        pred_x0 = (x - full(s1m_c) * e_t) / full(sa_c)
+        return full(sa_n) * pred_x0 + full(s1m_n) * e_t, pred_x0
+
+    @torch.no_grad()
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.,
+               unconditional_conditioning=None, callback=None):
+        """Deterministic DDIM inversion, t_enc steps up the schedule: step i moves the iterate from level a_prev[i] to a_t[i] with the
+        UNet on the current iterate at the TARGET timestep ddim_timesteps[i] (ldm passes the loop index i as the timestep; DESIGN.md
+        section 3 has the measurement behind the choice).  The result is at level index t_enc - 1: what decode(t_start=t_enc) expects.
+        -> (x_next, out) as ldm: out['x_encoded'], out['intermediate_steps'], and with return_intermediates = k the iterates after the
+        steps with i % max(t_enc // k, 1) == 0 or i == t_enc - 1 in out['intermediates'].  A callback (called with i) takes the
+        per-step path; otherwise the loop runs in the library (rdm_ddim_encode)."""
+        self._refuse_original_steps(use_original_steps)
+        t_enc = self._level_index("encode", "t_enc", t_enc, 1)
+        if unconditional_guidance_scale < 1.:
+            raise ValueError("encode: unconditional_guidance_scale must be >= 1")
+        c = self._unwrap(c, single="DDIM")
+        uc = self._unwrap(unconditional_conditioning) if unconditional_guidance_scale > 1. else None
+        if unconditional_guidance_scale > 1. and uc is None:
+            raise ValueError("encode: unconditional_conditioning is required when unconditional_guidance_scale > 1")
+        every = max(t_enc // int(return_intermediates), 1) if return_intermediates else None
+        steps = [i for i in range(t_enc) if every is not None and (i % every == 0 or i == t_enc - 1)]
+        print(f"Running DDIM inversion with {t_enc} timesteps")
+        if callback is not None:
+            x, inter = x0.to(self.model.device), []
+            for i in range(t_enc):
+                ts = torch.full((x.shape[0],), int(self.ddim_timesteps[i]), device=x.device, dtype=torch.long)
+                x, _ = self.p_invert_ddim(x, c, ts, i, unconditional_guidance_scale, uc)
+                if i in steps:
+                    inter.append(x)
+                callback(i)
+        else:
+            x, xi = self.model.ctx.ddim_encode(self.ddim_num_steps, t_enc, x0, c, uc, self.alphas_cumprod, scale=unconditional_guidance_scale,
+                                               log_every_t=every or t_enc, want_intermediates=every is not None)
+            inter = [] if xi is None else list(xi)
+        out = {'x_encoded': x, 'intermediate_steps': steps}
+        if return_intermediates:
+            out['intermediates'] = inter
+        return x.detach(), out
+
+    @torch.no_grad()
+    def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None, use_original_steps=False,
+               callback=None, img_callback=None, eta=None, temperature=1., noise=None, noise_seed=None, noise_row0=0, log_every_t=100,
+               return_intermediates=False, intermediates_to_cpu=False):
+        """ldm decode: x_latent is taken to be at level index t_start - 1 and the DDIM step runs at indices t_start - 1 ... 0 --
+        t_start forwards; t_start = the schedule's length is ddim_sampling from x_T = x_latent.  [native] eta (default: make_schedule's),
+        temperature, noise (a [t_start, B, C, H, W] stack), noise_seed / noise_row0 (step i of this call takes the library's (seed,
+        stream 1, step i)), log_every_t and return_intermediates ((x_dec, intermediates) instead of x_dec) as in sample().  A callback
+        takes the per-step path; otherwise the loop runs in the library (rdm_ddim_decode)."""
+        self._refuse_original_steps(use_original_steps)
+        if noise_seed is not None and noise is not None:
+            raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
+        t_start = self._level_index("decode", "t_start", t_start, 1)
+        if unconditional_guidance_scale < 1.:
+            raise ValueError("decode: unconditional_guidance_scale must be >= 1")
+        cond = self._unwrap(cond, single="DDIM")
+        uc = self._unwrap(unconditional_conditioning) if unconditional_guidance_scale > 1. else None
+        if unconditional_guidance_scale > 1. and uc is None:
+            raise ValueError("decode: unconditional_conditioning is required when unconditional_guidance_scale > 1")
+        if eta is None:
+            eta = self.ddim_eta
+        elif float(eta) != self.ddim_eta:
+            self.make_schedule(self.ddim_num_steps, ddim_eta=eta, verbose=False)
+        img = x_latent.to(self.model.device)
+        print(f"Running DDIM Sampling with {t_start} timesteps")
+        if callback is not None or img_callback is not None:
+            z, inter = self._python_loop(cond, img, callback, img_callback, log_every_t, temperature, eta, unconditional_guidance_scale, uc,
+                                         intermediates_to_cpu, noise=noise, noise_seed=noise_seed, noise_row0=noise_row0,
+                                         ts_all=self.ddim_timesteps[:t_start])
+            return (z, inter) if return_intermediates else z
+        seeded = {} if noise_seed is None else dict(seed=noise_seed, row0=noise_row0)
+        if eta != 0. and noise is None and noise_seed is None:
+            noise = torch.randn((t_start,) + tuple(img.shape), device=img.device)
+        z, xi, pi = self.model.ctx.ddim_decode(self.ddim_num_steps, t_start, img, cond, uc, self.alphas_cumprod, eta=eta,
+                                               scale=unconditional_guidance_scale, noise=noise, log_every_t=log_every_t,
+                                               temperature=temperature, want_intermediates=return_intermediates, **seeded)
+        return (z.detach(), self._intermediates(img, xi, pi, intermediates_to_cpu)) if return_intermediates else z.detach()

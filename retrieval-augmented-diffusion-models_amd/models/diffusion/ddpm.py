@@ -196,7 +196,8 @@ class MinimalRETRODiffusion(object):
             kwargs["noise_row0"] = lo
         else:
             base = parallel.shared_seed(self.device, getattr(self, "_group", None))
-            kwargs["x_T"] = parallel.per_sample_noise(base, range(lo, hi), shape, device=self.device)
+            if not kwargs.get("invert"):                    # (an inverted start takes no noise)
+                kwargs["x_T"] = parallel.per_sample_noise(base, range(lo, hi), shape, device=self.device)
             steps = None
             noiseless = any(kwargs.get(name, False) for name in ("plms", "dpm_solver", "uni_pc"))      # these draw no per-step noise
             if not noiseless and kwargs.get("ddim", True) and kwargs.get("eta", 0.) != 0.:
@@ -226,6 +227,14 @@ class MinimalRETRODiffusion(object):
             assert len(cond) == 1, "single cross-attention conditioning"
             cond = cond[0]
         return self.ctx.unet_forward(x_noisy, t, cond)
+
+    @torch.no_grad()
+    def apply_model_guided(self, x, t, cond, uncond):
+        """[native] (e_c, e_u) of x at the one timestep t, through the forward the native sampling loops run (rdm_unet_forward_guided).
+        apply_model on the doubled batch computes the same function through other kernel configurations; DDIMSampler.encode's per-step
+        path takes this one, because a step up the schedule carries the difference on."""
+        out = self.ctx.unet_forward_guided(x, t, cond, uncond)
+        return out[:x.shape[0]], out[x.shape[0]:]
 
     @torch.no_grad()
     def decode_first_stage(self, z, predict_cids=False, force_not_quantize=False):
@@ -397,15 +406,21 @@ class MinimalRETRODiffusion(object):
     # ---- samplers
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, dpm_solver=False,
-                   uni_pc=False, **kwargs):
+                   uni_pc=False, init_latent=None, strength=None, invert=False, invert_scale=1.0, **kwargs):
         """ddpm.py:988-1011.  [native] plms=True samples with PLMSSampler (ldm), dpm_solver=True with DPMSolverSampler (DPM-Solver++ 2M
         on the logSNR grid), uni_pc=True with UniPCSampler (UniPC order 2, bh2, with the corrector, on the logSNR grid) on
-        S = ddim_steps instead of DDIM / DDPM."""
+        S = ddim_steps instead of DDIM / DDPM.  init_latent / strength / invert / invert_scale [native]: image-to-image, DDIM only
+        (_img2img)."""
         if plms and dpm_solver:
             raise ValueError("plms and dpm_solver select different samplers: give one of them")
         if uni_pc and (plms or dpm_solver):
             raise ValueError(f"{'plms' if plms else 'dpm_solver'} and uni_pc select different samplers: give one of them")
         shape = (self.channels, self.image_size, self.image_size) if custom_shape is None else self._latent_shape(custom_shape)
+        if init_latent is not None or strength is not None or invert:
+            if plms or dpm_solver or uni_pc or not ddim:
+                raise ValueError("image-to-image (init_latent / strength / invert) runs on the DDIM sampler only: "
+                                 "drop plms / dpm_solver / uni_pc and keep ddim=True")
+            return self._img2img(cond, batch_size, ddim_steps, shape, init_latent, strength, invert, invert_scale, **kwargs)
         if ddim or plms or dpm_solver or uni_pc:
             sampler = (PLMSSampler(self) if plms else DPMSolverSampler(self) if dpm_solver else UniPCSampler(self) if uni_pc
                        else DDIMSampler(self))
@@ -414,6 +429,89 @@ class MinimalRETRODiffusion(object):
             return sampler.sample(S=ddim_steps, batch_size=batch_size, shape=shape, conditioning=cond, verbose=verbose, **kwargs)
         return self.sample(cond=cond, batch_size=batch_size, return_intermediates=True,
                            shape=None if custom_shape is None else (batch_size,) + shape, **kwargs)
+
+    @staticmethod
+    def _check_img2img(init_latent, strength, batch_size, shape):
+        """The image-to-image arguments of a sampling call, checked before any GPU work: init_latent [batch_size, C, H, W] at the
+        call's latent shape, strength in (0, 1]."""
+        if init_latent is None:
+            raise ValueError("image-to-image needs init_latent (the encoded image) with strength / invert")
+        if strength is None:
+            raise ValueError("image-to-image needs a strength in (0, 1] with init_latent")
+        DDIMSampler.img2img_steps(strength, 1)
+        want = (int(batch_size),) + tuple(int(v) for v in shape)
+        if tuple(init_latent.shape) != want:
+            raise ValueError(f"init_latent must be {want} (the call's batch at its latent shape), got {tuple(init_latent.shape)}")
+
+    @staticmethod
+    def _check_img2img_request(kwargs, init_image, init_latent, strength, invert):
+        """What can be wrong with the image-to-image arguments of sample_with_query / sample_from_rdata, before the retrieval and any
+        GPU work: one of init_image / init_latent, the DDIM sampler, strength in (0, 1], a channel-last image."""
+        if init_image is None and init_latent is None:
+            if invert:
+                raise ValueError("invert needs init_image or init_latent")
+            return
+        if init_image is not None and init_latent is not None:
+            raise ValueError("init_image and init_latent are the same input in two forms: give one of them")
+        if any(kwargs.get(name, False) for name in ("plms", "dpm_solver", "uni_pc")) or not kwargs.get("ddim", True):
+            raise ValueError("image-to-image (init_image / init_latent) runs on the DDIM sampler only: "
+                             "drop plms / dpm_solver / uni_pc and keep ddim=True")
+        DDIMSampler.img2img_steps(strength, 1)
+        if init_image is not None and torch.as_tensor(init_image).ndim not in (3, 4):
+            raise ValueError(f"init_image must be channel-last, [B,H,W,C] or [H,W,C] in [-1, 1], got {tuple(torch.as_tensor(init_image).shape)}")
+
+    @torch.no_grad()
+    def _img2img_kwargs(self, kwargs, n_total, lo, hi, init_image, init_latent, strength, invert):
+        """The image-to-image keywords of sample_log for rows [lo, hi) of a global batch of n_total: init_image [n_total,H,W,C] (or one
+        image, repeated) through encode_first_stage -> get_first_stage_encoding, or init_latent itself, checked against the call's
+        latent shape.  The rows are cut BEFORE the encoder runs, so a rank encodes its own images only."""
+        if init_image is None and init_latent is None:
+            return
+        src = torch.as_tensor(init_image if init_image is not None else init_latent)
+        if src.ndim == 3:
+            src = src[None]
+        if src.ndim != 4 or src.shape[0] not in (1, n_total):
+            raise ValueError(f"init_image / init_latent must hold one row or one per sample of the batch of {n_total}, got {tuple(src.shape)}")
+        src = src[lo:hi] if src.shape[0] == n_total else src
+        if init_image is not None:
+            x = src.permute(0, 3, 1, 2).to(self.device).float().contiguous()          # 'b h w c -> b c h w', as get_input
+            src = self.get_first_stage_encoding(self.encode_first_stage(x))
+        lat = src.to(self.device).float()
+        if lat.shape[0] == 1 and hi - lo > 1:
+            lat = lat.repeat(hi - lo, 1, 1, 1)
+        self._check_img2img(lat, strength, hi - lo, self._latent_shape(kwargs.get("custom_shape")))
+        kwargs.update(init_latent=lat.contiguous(), strength=strength, invert=invert)
+
+    @torch.no_grad()
+    def _img2img(self, cond, batch_size, ddim_steps, shape, init_latent, strength, invert, invert_scale, x_T=None, eta=0., noise=None,
+                 noise_seed=None, noise_row0=0, unconditional_guidance_scale=1., unconditional_conditioning=None, log_every_t=100,
+                 temperature=1., callback=None, img_callback=None, intermediates_to_cpu=False, **kwargs):
+        """[native] DDIM image-to-image: with n = min(total, max(1, int(strength * total))) of the schedule's `total` timesteps, the
+        start is init_latent noised to level index n - 1 (stochastic_encode; the noise is x_T when given, the library's seeded
+        starting-latent normals with noise_seed, else torch's) or inverted n steps (invert: DDIMSampler.encode under the call's
+        conditioning at invert_scale), then decode(t_start=n) at the call's guidance scale.  The noised level and the level the first
+        decode step assumes are the same one, so strength 1.0 runs the whole schedule.  -> (samples, intermediates) like sample()."""
+        self._check_img2img(init_latent, strength, batch_size, shape)
+        S = kwargs.pop('S', ddim_steps)
+        per_step = [name for name in ("mask", "x0", "quantize_x0", "score_corrector", "content_cond", "style_cond", "timesteps", "noise_dropout")
+                    if kwargs.get(name) is not None and not (isinstance(kwargs[name], (bool, int, float)) and not kwargs[name])]
+        if per_step:                            # options of sample()'s per-step path that decode has no counterpart for (DESIGN.md section 7)
+            raise ValueError(f"image-to-image does not take {per_step}")
+        # (anything else is swallowed, as DDIMSampler.sample swallows it)
+        sampler = DDIMSampler(self)
+        sampler.make_schedule(ddim_num_steps=S, ddim_eta=eta, verbose=False)
+        n = sampler.img2img_steps(strength, sampler.ddim_timesteps.shape[0])
+        if invert:
+            start, _ = sampler.encode(init_latent, cond, n, unconditional_guidance_scale=invert_scale,
+                                      unconditional_conditioning=unconditional_conditioning)
+        else:
+            start = sampler.stochastic_encode(init_latent, n - 1, noise=x_T, noise_seed=None if x_T is not None else noise_seed,
+                                              noise_row0=noise_row0)
+        return sampler.decode(start, cond, n, unconditional_guidance_scale=unconditional_guidance_scale,
+                              unconditional_conditioning=unconditional_conditioning, callback=callback, img_callback=img_callback, eta=eta,
+                              temperature=temperature, noise=None if noise is None else noise[:n], noise_seed=noise_seed,
+                              noise_row0=noise_row0, log_every_t=log_every_t, return_intermediates=True,
+                              intermediates_to_cpu=intermediates_to_cpu)
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, timesteps=None, noise=None,
@@ -463,13 +561,18 @@ class MinimalRETRODiffusion(object):
     def sample_with_query(self, query, cond=None, bs=None, k_nn=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, return_nns=False,
                           n_reps=None, query_embedded=False, example_maps=None, visualize_nns=True, omit_query=False,
-                          normalize=False, device_noise=False, **kwargs):
+                          normalize=False, device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False, **kwargs):
         """ddpm.py:689-844 (nn_encoder is None, retrieval_encoder = Identity — every shipped config).  device_noise [native]: the
         starting latents and the per-step noise (DDIM eta > 0, DDPM) are the library's counter-based generator's, a function of (the
-        call's shared seed, GLOBAL row) generated inside the step kernels (_sample_shard) -- no noise tensor is drawn in Python."""
+        call's shared seed, GLOBAL row) generated inside the step kernels (_sample_shard) -- no noise tensor is drawn in Python.
+        init_image / init_latent / strength / invert [native]: image-to-image on the DDIM sampler (sample_log) -- init_image
+        [B,H,W,C] in [-1,1] (or one image [H,W,C], repeated) goes through encode_first_stage -> get_first_stage_encoding, init_latent
+        is that latent itself; the start is the latent noised by `strength` (with device_noise: row r's noise depends on (the shared
+        seed, r) only) or, with invert, its DDIM inversion under the retrieved conditioning."""
         if cond is not None or return_nns:
             raise NotImplementedError("cond (a second conditioning) / return_nns (neighbour image grids) are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))      # a bad custom_shape fails here, not after the retrieval
+        self._check_img2img_request(kwargs, init_image, init_latent, strength, invert)
         # (the reference asserts `query.ndim` first, which makes its own `isinstance(query, str)` branch unreachable: a caption only
         #  works pre-embedded there, scripts/rdm_sample.py:275-277; here str / list-of-str queries take the CLIP text tower)
         if not query_embedded and not isinstance(query, (str, list)):
@@ -495,6 +598,7 @@ class MinimalRETRODiffusion(object):
             k_nn = self.k_nn
         n_total = len(query)
         lo, hi = self._shard(n_total) if self.distributed else (0, n_total)
+        self._img2img_kwargs(kwargs, n_total, lo, hi, init_image, init_latent, strength, invert)
         shard_db = self.distributed and getattr(self, "shard_db", False)
         if self.distributed and not shard_db:
             query = query[lo:hi]            # every rank retrieves for its own rows only (the database is replicated)
@@ -563,12 +667,13 @@ class MinimalRETRODiffusion(object):
     def sample_from_rdata(self, N, cond=None, return_nns=False, use_weights=False, qids=None, k_nn=None, memsize=100,
                           verbose=False, pre_loaded_patches=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, nn_embeddings=None,
-                          device_noise=False, **kwargs):
-        """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921).  device_noise [native]: as in
-        sample_with_query."""
+                          device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False, **kwargs):
+        """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921).  device_noise, init_image /
+        init_latent / strength / invert [native]: as in sample_with_query."""
         if cond is not None or return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("cond / return_nns / pre_loaded_patches are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))
+        self._check_img2img_request(kwargs, init_image, init_latent, strength, invert)
         self._sync_retriever_sharding()
         if self.retriever.searcher is None:
             self.train_searcher()
@@ -576,6 +681,7 @@ class MinimalRETRODiffusion(object):
             k_nn = self.k_nn
         qids = self.get_qids(memsize, N, qids=qids, use_weights=use_weights, verbose=verbose)   # rank 0's draw on every rank (get_qids)
         lo, hi = self._shard(N) if self.distributed else (0, N)
+        self._img2img_kwargs(kwargs, N, lo, hi, init_image, init_latent, strength, invert)
         shard_db = self.distributed and getattr(self, "shard_db", False) and nn_embeddings is None
         if self.distributed:
             if not shard_db:

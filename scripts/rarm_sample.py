@@ -132,21 +132,23 @@ def load_model(opt):
 IMAGE_SUFFIXES = (".png", ".jpg", ".jpeg", ".bmp", ".webp")
 
 
-def load_images(path, resolution):
-    """Image file or directory (sorted) -> f32 [n,3,R,R] in [-1,1]: centre crop to a square, bicubic resize to the first-stage resolution."""
+def load_images(path, resolution, width=None):
+    """Image file or directory (sorted) -> f32 [n,3,R,R] in [-1,1]: centre crop to a square, bicubic resize to the first-stage resolution.
+    width: -> [n,3,resolution,width] instead, the centre crop taken at that aspect (rdm_sample.py --init_img at --height / --width)."""
     import torch
     from PIL import Image
     path = Path(path)
     files = sorted(f for f in path.iterdir() if f.suffix.lower() in IMAGE_SUFFIXES) if path.is_dir() else [path]
     if not files:
         raise SystemExit(f"no image found at {path}")
+    out_h, out_w = resolution, (resolution if width is None else width)
     out = []
     for f in files:
         im = Image.open(f).convert("RGB")
         w, h = im.size
-        side = min(w, h)
-        left, top = (w - side) // 2, (h - side) // 2
-        im = im.crop((left, top, left + side, top + side)).resize((resolution, resolution), Image.BICUBIC)
+        cw, ch = (min(w, h), min(w, h)) if out_h == out_w else (min(w, h * out_w // out_h), min(h, w * out_h // out_w))
+        left, top = (w - cw) // 2, (h - ch) // 2
+        im = im.crop((left, top, left + cw, top + ch)).resize((out_w, out_h), Image.BICUBIC)
         out.append(torch.from_numpy(np.asarray(im, dtype=np.uint8).copy()).permute(2, 0, 1).float() / 127.5 - 1.0)
     return torch.stack(out)
 

@@ -28,7 +28,10 @@ only, its script has no flag; multiples of 32 = first-stage factor 4 x UNet down
 sigma_t-scaled noise; DDIM only, PLMS refuses it and DPM-Solver++ / UniPC ignore it), `--device_noise` (the starting latents and the
 `--eta` noise come from the library's counter-based generator inside the step kernels, keyed by (the run's seed draw, global sample
 index): no noise tensor is drawn or stacked in Python, and the images differ from the default torch-generator streams; works with
-`--gpus N` with the same sharding invariance).
+`--gpus N` with the same sharding invariance), `--init_img PATH_OR_DIR` / `--strength S` / `--invert` (image-to-image on DDIM: the image,
+resized to the model's size or `--height` / `--width`, is encoded by the first stage and either noised to `int(S x steps)` steps up the
+schedule or, with `--invert`, taken there by deterministic DDIM inversion, then decoded under the retrieved neighbours; strength 1.0 runs
+every step; works with `--gpus N` and `--device_noise`; not with `--plms` / `--dpm_solver` / `--uni_pc`).
 """
 import argparse
 import datetime
@@ -84,6 +87,13 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--device_noise", default=False, action="store_true",
                         help="[native] starting latents and per-step noise from the library's counter-based generator inside the step kernels "
                         "(no noise stack)")
+    parser.add_argument("--init_img", type=Path, default=None,
+                        help="[native] image-to-image: start from this image (or the images of this directory: one, or one per sample of the "
+                        "batch) instead of pure noise; DDIM only")
+    parser.add_argument("--strength", type=float, default=0.75,
+                        help="[native] with --init_img: how far up the schedule the image is taken, in (0, 1]; 1.0 runs every step")
+    parser.add_argument("--invert", default=False, action="store_true",
+                        help="[native] with --init_img: start from the image's deterministic DDIM inversion instead of noising it")
     return parser
 
 
@@ -97,6 +107,14 @@ def parse_args(argv=None) -> argparse.Namespace:
         v = getattr(opt, name)
         if v is not None and (v < SIZE_MULTIPLE or v % SIZE_MULTIPLE):
             parser.error(f"--{name} must be a positive multiple of {SIZE_MULTIPLE} (first-stage factor x UNet down factor), got {v}")
+    if opt.init_img is not None:
+        for name in ("plms", "dpm_solver", "uni_pc"):
+            if getattr(opt, name):
+                parser.error(f"--init_img runs on the DDIM sampler only: drop --{name}")
+        if not 0.0 < opt.strength <= 1.0:
+            parser.error(f"--strength must lie in (0, 1], got {opt.strength}")
+    elif opt.invert:
+        parser.error("--invert needs --init_img")
     if opt.top_m > 1.0:
         opt.top_m = int(opt.top_m)          # top_m should be int if a fixed number of images is given (:138-140)
     if opt.seed is not None and (not opt.increase_guidance) and opt.n_runs > 1:
@@ -153,7 +171,10 @@ def load_model(opt: argparse.Namespace):
     if opt.synthetic:
         model = MinimalRETRODiffusion(unet_config={"params": {}}, first_stage_config={"params": {"ddconfig": {}}}, k_nn=4, device=opt.gpu)
         model.load_unet_state_dict(synthetic.unet_state_dict(model.unet_cfg))
-        model.load_first_stage_state_dict(synthetic.vq_state_dict(model.vq_cfg))
+        fsd = synthetic.vq_state_dict(model.vq_cfg)
+        if getattr(opt, "init_img", None) is not None:                  # image-to-image encodes the image: the first stage's other half
+            fsd.update(synthetic.vq_encoder_state_dict(model.vq_cfg))
+        model.load_first_stage_state_dict(fsd)
         n = opt.synthetic_db_rows
         pool = {"embedding": synthetic.clip_like_rows(n), "img_id": np.arange(n), "patch_coords": np.zeros((n, 4), np.int64)}
         retr = ClipImageRetriever(state_dict=synthetic.clip_state_dict(_lib.make_clip_cfg()), ctx=model.ctx)
@@ -217,7 +238,24 @@ def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
         if height % f or width % f:
             raise SystemExit(f"rdm_sample.py (native): --height / --width must be multiples of the first stage's factor {f}")
         kw["custom_shape"] = (model.channels, height // f, width // f)       # checked against the UNet's down factor by the model
+    if getattr(opt, "init_img", None) is not None:
+        kw.update(init_image=load_init_images(opt, model, kw.get("custom_shape")), strength=opt.strength)
+        if opt.invert:
+            kw["invert"] = True
     return kw
+
+
+def load_init_images(opt: argparse.Namespace, model, custom_shape=None):
+    """--init_img: the image file, or a directory's images (one, repeated by the model, or one per sample of the batch), with the loader
+    of rarm_sample.py --complete_from at the call's size in pixels -> f32 [n,H,W,3] in [-1,1], as sample_with_query takes init_image."""
+    sys.path.insert(0, os.path.dirname(os.path.abspath(__file__)))
+    from rarm_sample import load_images
+    f = 1 << (model.vq_cfg.n_ch_mult - 1)
+    _, h, w = custom_shape if custom_shape is not None else (model.channels, model.image_size, model.image_size)
+    images = load_images(opt.init_img, h * f, w * f)
+    if images.shape[0] not in (1, opt.batch_size):
+        raise SystemExit(f"rdm_sample.py (native): --init_img gives {images.shape[0]} images; give one, or one per sample of -bs {opt.batch_size}")
+    return images.permute(0, 2, 3, 1).contiguous()
 
 
 def sample_unconditional(model, opt: argparse.Namespace, is_writer=True):

@@ -7,10 +7,14 @@ forward per step like dpmpp.  The stochastic loops come in two forms: ddimeta:S 
 draw the starting latents and the [S, B, 3, 64, 64] noise stack per call the way MinimalRETRODiffusion._sample_shard does (one torch
 generator per sample row, then the transposed copy) and time that with the loop; ddimeta_rng:S and ddpm_rng:S are the seeded entries,
 whose step kernels generate the noise (no x_T, no stack).  Every line also carries the peak of torch.cuda.max_memory_allocated() over the
-timed calls.  A spec given twice is timed twice (the second under `name:S#2`): the box's own A/A spread.  Prints the box's calibration
+timed calls.  Image-to-image: img2img:S:STRENGTH encodes a [B, 3, 256, 256] image batch with the first-stage encoder, noises the latent to
+n = min(total, max(1, int(STRENGTH * total))) steps up the S-step schedule with the seeded forward process (no noise tensor) and runs
+the native decode from there -- n forwards; invert:S:STRENGTH takes the latent there by n steps of native DDIM inversion (unguided)
+instead -- 2 n forwards.  The encoder's own ms per image is reported under "vq_encode_ms_per_image".  A spec given twice is timed twice (the second under `name:S#2`): the box's own A/A spread.  Prints the box's calibration
 probe and one line per run on stderr, one JSON line on stdout.
 
     python tools/sampler_bench.py [--reps N] [--batch B] [ddim:50 plms:50 plms:25 dpmpp:20 ddpm:250 ddpm:250 ddpm_rng:250 ...]
+    python tools/sampler_bench.py ddim:50 ddim:50 img2img:50:0.6 invert:50:0.6
 """
 import argparse
 import json
@@ -39,12 +43,21 @@ def main():
     d = ctx.device
     model = MinimalRETRODiffusion(unet_config={"params": {}}, first_stage_config={"params": {"ddconfig": {}}}, k_nn=4, ctx=ctx)
     model.load_unet_state_dict(synthetic.unet_state_dict(model.unet_cfg))
-    model.load_first_stage_state_dict(synthetic.vq_state_dict(model.vq_cfg))
+    fsd = synthetic.vq_state_dict(model.vq_cfg)
+    from_image = any(run.split(":")[0] in ("img2img", "invert") for run in a.runs)
+    if from_image:
+        fsd.update(synthetic.vq_encoder_state_dict(model.vq_cfg))
+    model.load_first_stage_state_dict(fsd)
     B = a.batch
     g = torch.Generator(device=d).manual_seed(0)
     x_T = torch.randn(B, 3, 64, 64, device=d, generator=g)
     cond = torch.randn(B, 4, 512, device=d, generator=g) * 0.45
     uncond = torch.zeros_like(cond)
+    image = torch.rand(B, 3, 256, 256, device=d, generator=g) * 2 - 1 if from_image else None
+
+    def steps_of(S, strength):
+        total = len(range(0, model.num_timesteps, model.num_timesteps // S))
+        return min(total, max(1, int(strength * total))), total
 
     sched_ddpm = {n: getattr(model, n).numpy() for n in ("sqrt_recip_alphas_cumprod", "sqrt_recipm1_alphas_cumprod", "posterior_mean_coef1",
                                                           "posterior_mean_coef2", "posterior_log_variance_clipped")}
@@ -57,8 +70,19 @@ def main():
         nz = parallel.per_sample_noise(1001 + calls[0], range(B), (steps, 3, 64, 64), device=d)
         return x, nz.transpose(0, 1).contiguous()
 
-    def sample(name, S):
-        if name == "ddimeta":
+    def sample(name, S, strength=None):
+        if name in ("img2img", "invert"):
+            import numpy as np
+            calls[0] += 1
+            n, total = steps_of(S, strength)
+            lat = ctx.vq_encode(image)
+            if name == "invert":
+                start, _ = ctx.ddim_encode(S, n, lat, cond, None, model.alphas_cumprod)
+            else:
+                a_n = float(model.alphas_cumprod[range(0, model.num_timesteps, model.num_timesteps // S)[n - 1] + 1])
+                start = ctx.op_q_sample_seeded(lat, np.sqrt(a_n), np.sqrt(1.0 - a_n), 1000 + calls[0], out=lat)
+            z, _, _ = ctx.ddim_decode(S, n, start, cond, uncond, model.alphas_cumprod, eta=0.0, scale=2.0)
+        elif name == "ddimeta":
             x, nz = stack(S)
             z, _, _ = ctx.ddim_sample(S, x, cond, uncond, model.alphas_cumprod, eta=1.0, scale=2.0, noise=nz)
         elif name == "ddimeta_rng":
@@ -79,10 +103,13 @@ def main():
         elif name == "unipc":
             z, _, _ = ctx.unipc_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         else:
-            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | unipc | ddimeta | ddimeta_rng | ddpm | ddpm_rng)")
+            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | unipc | ddimeta | ddimeta_rng | ddpm | ddpm_rng | "
+                             "img2img:S:STRENGTH | invert:S:STRENGTH)")
         return ctx.vq_decode(z)
 
-    def forwards(name, S):
+    def forwards(name, S, strength=None):
+        if name in ("img2img", "invert"):
+            return steps_of(S, strength)[0] * (2 if name == "invert" else 1)
         if name in ("dpmpp", "unipc"):
             return len(ctx.dpmpp_timesteps(S, model.alphas_cumprod)) - 1
         return S + (1 if name == "plms" else 0)
@@ -92,25 +119,39 @@ def main():
     out = {"batch": B, "scale": 2.0, "k": 4, "reps": a.reps, "calibration": {"mfma_probe_tflops": round(tf, 1), "hbm_stream_gbps": round(gb, 1)},
            "ms_per_image": {}, "forwards": {}, "peak_torch_mib": {}}
     for n_run, run in enumerate(a.runs):
-        name, S = run.split(":")
+        name, S, *rest = run.split(":")
         S = int(S)
+        if (name in ("img2img", "invert")) != (len(rest) == 1):
+            raise SystemExit(f"{run!r}: img2img and invert take name:S:STRENGTH, the other samplers name:S")
+        strength = float(rest[0]) if rest else None
+        if strength is not None and not 0.0 < strength <= 1.0:
+            raise SystemExit(f"{run!r}: STRENGTH must lie in (0, 1]")
         if run in a.runs[:n_run]:
             run = f"{run}#{a.runs[:n_run].count(run) + 1}"
-        sample(name, S)                      # warm-up: scratch, tables, K/V cache
+        sample(name, S, strength)            # warm-up: scratch, tables, K/V cache
         torch.cuda.synchronize()
         torch.cuda.reset_peak_memory_stats()
         t0 = time.perf_counter()
         for _ in range(a.reps):
-            img = sample(name, S)
+            img = sample(name, S, strength)
         torch.cuda.synchronize()
         dt = (time.perf_counter() - t0) / a.reps
         assert torch.isfinite(img).all()
         out["ms_per_image"][run] = round(dt * 1e3 / B, 3)
-        out["forwards"][run] = forwards(name, S)
+        out["forwards"][run] = forwards(name, S, strength)
         peak = torch.cuda.max_memory_allocated() / 2 ** 20
         out["peak_torch_mib"][run] = round(peak, 1)
         del img
         print(f"{run}: {dt * 1e3:.1f} ms per call, {dt * 1e3 / B:.3f} ms per image, peak torch memory {peak:.1f} MiB", file=sys.stderr, flush=True)
+    if from_image:                           # the first-stage encoder alone: what an image-to-image call adds to its n forwards
+        ctx.vq_encode(image)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        for _ in range(a.reps):
+            ctx.vq_encode(image)
+        torch.cuda.synchronize()
+        out["vq_encode_ms_per_image"] = round((time.perf_counter() - t0) / a.reps * 1e3 / B, 3)
+        print(f"vq_encode: {out['vq_encode_ms_per_image']:.3f} ms per image", file=sys.stderr, flush=True)
     ms = out["ms_per_image"]
     if "ddim:50" in ms and "plms:25" in ms:
         out["speedup_plms25_over_ddim50"] = round(ms["ddim:50"] / ms["plms:25"], 3)
