@@ -580,6 +580,40 @@ int rdm_wgrad_select(int conv, int B, int H, int W, int C, int N, long long M, i
 int rdm_op_colsum(rdm_ctx* ctx, const void* x_bf16 /*[M,N]*/, float* out /*[N]*/, long long M, int N);
 int rdm_op_transpose(rdm_ctx* ctx, const void* x_bf16 /*[rows,cols]*/, void* y_bf16 /*[cols,rows]*/, int rows, int cols);
 int rdm_op_add(rdm_ctx* ctx, const void* a_bf16, const void* b_bf16, void* out_bf16, long long n);
+/* One DDIM update, the kernel of rdm_ddim_sample alone on caller-owned [dev] f32 buffers of n elements (eps: 2n under cfg, [cond | uncond]),
+ * with the kernel's own scalars -- the caller owns the schedule: e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i]) : eps[i];
+ * pred_x0 = (x - sqrt_one_minus_at e) / sqrtf(a_t); x_prev = sqrtf(a_prev) pred_x0 + sqrtf(1 - a_prev - sigma_t^2) e
+ * + sigma_t noise temperature (no noise operand: the last term is absent, whatever sigma_t); x_dup <- x_prev.  x_prev may be x.
+ * rdm_op_ddim_step_seeded: the kernel of rdm_ddim_sample_seeded -- the noise of element i is the normal of (seed, stream 1, step,
+ * row0 + i / per_row, i % per_row), drawn in registers: bit for bit rdm_op_ddim_step on rdm_op_randn(seed, row0, n / per_row, per_row, step,
+ * stream 1).  It has no scalar form: per_row a multiple of 4 that divides n and 16-byte aligned operands are required (-1 otherwise), and
+ * rows [row0, row0 + n / per_row) must pass the device-noise row check. */
+int rdm_op_ddim_step(rdm_ctx* ctx, const float* x, const float* eps, const float* noise_or_null, long long n, int cfg, float scale, float a_t,
+                     float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, float* x_prev, float* x_dup_or_null,
+                     float* pred_x0_or_null);
+int rdm_op_ddim_step_seeded(rdm_ctx* ctx, const float* x, const float* eps, long long n, int64_t per_row, int cfg, float scale, float a_t,
+                            float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, uint64_t seed, int64_t row0,
+                            uint32_t step, float* x_prev, float* x_dup_or_null, float* pred_x0_or_null);
+/* One PLMS update, the kernel of rdm_plms_sample alone (fp32, n elements, eta = 0): e_t = the guided eps as above.
+ *   mode 0 (step):    e' = e_t | (3 e_t - h1) / 2 | (23 e_t - 16 h1 + 5 h2) / 12 | (55 e_t - 59 h1 + 37 h2 - 9 h3) / 24 at order 0 | 1 | 2 | 3;
+ *                     e_store <- e_t (after the history reads: e_store may be h3)
+ *   mode 1 (Euler A): e' = e_t; e_store <- e_t        mode 2 (Euler B): e' = (e_prev + e_t) / 2; e_store is not written
+ * pred_x0 = (x - sqrt_one_minus_at e') / sqrtf(a_t); x_out = sqrtf(a_prev) pred_x0 + sqrtf(1 - a_prev) e'; x_dup <- x_out.  x_out may be x.
+ * Returns -1 with a message, and launches nothing, for a mode outside 0..2, an order outside 0..3, a null e_prev in mode 2, a null history
+ * operand the order reads in mode 0, and a null e_store in modes 0 and 1. */
+int rdm_op_plms_step(rdm_ctx* ctx, const float* x, const float* eps, const float* e_prev_or_null, const float* h1_or_null,
+                     const float* h2_or_null, const float* h3_or_null, long long n, int cfg, float scale, float a_t, float a_prev,
+                     float sqrt_one_minus_at, int mode, int order, float* e_store_or_null, float* x_out, float* x_dup_or_null,
+                     float* pred_x0_or_null);
+/* One ancestral DDPM update, the kernel of rdm_ddpm_sample alone (fp32, n elements): x0 = sqrt_recip x - sqrt_recipm1 eps, clamped to
+ * [-1, 1] when clip; x_prev = coef1 x0 + coef2 x + (nonzero ? expf(0.5 log_var) noise temperature : 0).  x_prev may be x.  nonzero == 0
+ * ignores the noise operand; nonzero != 0 without one is refused (-1).  rdm_op_ddpm_step_seeded: the kernel of rdm_ddpm_sample_seeded, the
+ * noise drawn as in rdm_op_ddim_step_seeded and under the same conditions. */
+int rdm_op_ddpm_step(rdm_ctx* ctx, const float* x, const float* eps, const float* noise_or_null, long long n, float sqrt_recip,
+                     float sqrt_recipm1, float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, float* x_prev);
+int rdm_op_ddpm_step_seeded(rdm_ctx* ctx, const float* x, const float* eps, long long n, int64_t per_row, float sqrt_recip, float sqrt_recipm1,
+                            float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, uint64_t seed, int64_t row0,
+                            uint32_t step, float* x_prev);
 /* One DPM-Solver++ update, the kernel of rdm_dpmpp_sample alone (fp32, n elements): e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i])
  * : eps[i]; m0 = (x - sqrt_one_minus_a_s e) / sqrt_a_s; x_out = c_x x + c_0 m0 + c_1 m_prev (no m_prev: the last term is absent);
  * x_dup <- x_out, m_store <- m0, pred_x0 <- m0.  m_store may be m_prev itself. */

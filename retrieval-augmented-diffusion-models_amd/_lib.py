@@ -88,6 +88,7 @@ class UnipcArgs(C.Structure):
 
 UNIPC_VARIANTS = {"bh1": 0, "bh2": 1}
 UNIPC_COEFFICIENTS = ("alpha", "sigma", "a_x", "a_t", "a_1", "a_2", "a_3", "b_x", "b_0", "b_1", "b_2", "order_c", "order_p")
+PLMS_STEP, PLMS_EULER_A, PLMS_EULER_B = 0, 1, 2          # rdm_op_plms_step's mode
 
 
 class DdpmArgs(C.Structure):
@@ -206,6 +207,16 @@ SIGNATURES = {
     "rdm_op_dpmpp_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     _P, _P, _P, _P]),
     "rdm_op_unipc_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.POINTER(C.c_double), _P, _P, _P, _P, _P]),
+    "rdm_op_ddim_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                   _P, _P, _P]),
+    "rdm_op_ddim_step_seeded": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                          C.c_float, C.c_uint64, C.c_int64, C.c_uint32, _P, _P, _P]),
+    "rdm_op_plms_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                   C.c_int, _P, _P, _P, _P]),
+    "rdm_op_ddpm_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
+                                   C.c_float, _P]),
+    "rdm_op_ddpm_step_seeded": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                          C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_uint32, _P]),
     "rdm_op_geglu": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int]),
     "rdm_op_linear_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "rdm_op_linear_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
@@ -992,6 +1003,69 @@ class Context:
         (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
         return self._sampler_call("plms_sample", lib.rdm_plms_sample, DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t,
                                   want_intermediates, S=S, eta=0.0, temperature=1.0)
+
+    @staticmethod
+    def _step_sizes(what, x, eps, cfg, others):
+        """What the step-kernel bindings check before a pointer crosses the ABI: eps holds x.numel() elements (twice that under cfg) and
+        every other operand given x.numel()."""
+        n = x.numel()
+        if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in others):
+            raise RdmError(f"{what}: operand sizes do not match x")
+        return n
+
+    @staticmethod
+    def _step_rows(what, n, per_row, seed, row0, step):
+        """(seed, row0, per_row, step) of a seeded step-kernel call; the library checks that per_row divides n."""
+        per_row, step = int(per_row), int(step)
+        if per_row < 1 or not 0 <= step < 2 ** 32:
+            raise RdmError(f"{what}: per_row must be >= 1 and step a 32-bit counter, got per_row={per_row}, step={step}")
+        seed, row0 = _noise_seed(what, seed, row0, max(n // per_row, 1))
+        return seed, row0, per_row, step
+
+    def op_ddim_step(self, x, eps, noise, cfg, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature, x_prev, x_dup=None, pred_x0=None,
+                     seed=None, row0=0, per_row=None, step=0):
+        """The DDIM update kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
+        [cond | uncond]) with the kernel's own scalars (rdm_op_ddim_step); noise / x_dup / pred_x0 may be None, x_prev may be x.  With
+        `seed` (and no noise) rdm_op_ddim_step_seeded: the noise of (seed, stream 1, step, row0 + b) for rows of per_row elements, drawn
+        in the kernel.  Writes into the given outputs."""
+        n = self._step_sizes("op_ddim_step", x, eps, cfg, (noise, x_prev, x_dup, pred_x0))
+        sc = [float(v) for v in (scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature)]
+        if seed is None:
+            self._check(lib.rdm_op_ddim_step(self._h, _ptr(x), _ptr(eps), _ptr(noise), n, int(bool(cfg)), *sc, _ptr(x_prev), _ptr(x_dup),
+                                             _ptr(pred_x0)))
+            return
+        if noise is not None or per_row is None:
+            raise RdmError("op_ddim_step: a seeded call takes per_row and no noise operand")
+        seed, row0, per_row, step = self._step_rows("op_ddim_step", n, per_row, seed, row0, step)
+        self._check(lib.rdm_op_ddim_step_seeded(self._h, _ptr(x), _ptr(eps), n, per_row, int(bool(cfg)), *sc, seed, row0, step, _ptr(x_prev),
+                                                _ptr(x_dup), _ptr(pred_x0)))
+
+    def op_plms_step(self, x, eps, cfg, scale, a_t, a_prev, sqrt_one_minus_at, mode, order, x_out, e_prev=None, h1=None, h2=None, h3=None,
+                     e_store=None, x_dup=None, pred_x0=None):
+        """The PLMS update kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
+        [cond | uncond]); mode PLMS_STEP (with `order` history operands h1 .. h3) | PLMS_EULER_A | PLMS_EULER_B (with e_prev); e_store
+        receives the guided e_t in the first two modes and may be h3; x_out may be x.  Writes into the given outputs."""
+        n = self._step_sizes("op_plms_step", x, eps, cfg, (e_prev, h1, h2, h3, e_store, x_out, x_dup, pred_x0))
+        self._check(lib.rdm_op_plms_step(self._h, _ptr(x), _ptr(eps), _ptr(e_prev), _ptr(h1), _ptr(h2), _ptr(h3), n, int(bool(cfg)),
+                                         float(scale), float(a_t), float(a_prev), float(sqrt_one_minus_at), int(mode), int(order),
+                                         _ptr(e_store), _ptr(x_out), _ptr(x_dup), _ptr(pred_x0)))
+
+    def op_ddpm_step(self, x, eps, noise, sqrt_recip, sqrt_recipm1, coef1, coef2, log_var, clip, nonzero, temperature, x_prev, seed=None,
+                     row0=0, per_row=None, step=0):
+        """The ancestral DDPM update kernel alone on caller-owned fp32 device tensors of x.numel() elements (rdm_op_ddpm_step); noise may
+        be None when nonzero is false, x_prev may be x.  With `seed` (and no noise) rdm_op_ddpm_step_seeded, as op_ddim_step.  Writes
+        into x_prev."""
+        n = self._step_sizes("op_ddpm_step", x, eps, False, (noise, x_prev))
+        sc = [float(v) for v in (sqrt_recip, sqrt_recipm1, coef1, coef2, log_var)]
+        if seed is None:
+            self._check(lib.rdm_op_ddpm_step(self._h, _ptr(x), _ptr(eps), _ptr(noise), n, *sc, int(bool(clip)), int(bool(nonzero)),
+                                             float(temperature), _ptr(x_prev)))
+            return
+        if noise is not None or per_row is None:
+            raise RdmError("op_ddpm_step: a seeded call takes per_row and no noise operand")
+        seed, row0, per_row, step = self._step_rows("op_ddpm_step", n, per_row, seed, row0, step)
+        self._check(lib.rdm_op_ddpm_step_seeded(self._h, _ptr(x), _ptr(eps), n, per_row, *sc, int(bool(clip)), int(bool(nonzero)),
+                                                float(temperature), seed, row0, step, _ptr(x_prev)))
 
     @staticmethod
     def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):

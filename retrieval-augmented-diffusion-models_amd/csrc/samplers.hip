@@ -656,6 +656,87 @@ int rdm_op_q_sample_seeded(rdm_ctx* c, const float* x0, int64_t B, int64_t per_r
     return 0;
 }
 
+// ---- the DDIM, PLMS and DDPM step kernels alone: the kernels' own scalars, as the loops above fill them
+static void ddim_step_fill(DdimStepParams& p, const float* x, const float* eps, long long n, int cfg, float scale, float a_t, float a_prev,
+                           float sigma_t, float sqrt_one_minus_at, float temperature, float* x_prev, float* x_dup, float* pred_x0) {
+    p.x = x; p.eps = eps; p.x_prev = x_prev; p.x_dup = x_dup; p.pred_x0 = pred_x0; p.n_per_batch = n; p.cfg = cfg ? 1 : 0; p.scale = scale;
+    p.a_t = a_t; p.a_prev = a_prev; p.sigma_t = sigma_t; p.sqrt_one_minus_at = sqrt_one_minus_at; p.temperature = temperature;
+}
+int rdm_op_ddim_step(rdm_ctx* c, const float* x, const float* eps, const float* noise, long long n, int cfg, float scale, float a_t,
+                     float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, float* x_prev, float* x_dup, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddim_step: bad argument");
+    DdimStepParams p{};
+    ddim_step_fill(p, x, eps, n, cfg, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature, x_prev, x_dup, pred_x0);
+    p.noise = noise;
+    RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
+    return 0;
+}
+int rdm_op_ddim_step_seeded(rdm_ctx* c, const float* x, const float* eps, long long n, int64_t per_row, int cfg, float scale, float a_t,
+                            float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, uint64_t seed, int64_t row0, uint32_t step,
+                            float* x_prev, float* x_dup, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddim_step_seeded: bad argument");
+    RDM_TRY(check_noise_rows(c, "rdm_op_ddim_step_seeded", row0, per_row >= 1 ? n / per_row : 0, per_row));
+    DdimStepParams p{};
+    ddim_step_fill(p, x, eps, n, cfg, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature, x_prev, x_dup, pred_x0);
+    const hipError_t e = launch_ddim_step_seeded(p, StepRngParams{seed, per_row, (uint32_t)row0, step}, c->stream);
+    if (e == hipErrorInvalidValue)
+        return c->fail(-1, "rdm_op_ddim_step_seeded: per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned");
+    RDM_CHECK_HIP(c, e);
+    return 0;
+}
+
+int rdm_op_plms_step(rdm_ctx* c, const float* x, const float* eps, const float* e_prev, const float* h1, const float* h2, const float* h3,
+                     long long n, int cfg, float scale, float a_t, float a_prev, float sqrt_one_minus_at, int mode, int order, float* e_store,
+                     float* x_out, float* x_dup, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_plms_step: bad argument");
+    if (mode != PLMS_STEP && mode != PLMS_EULER_A && mode != PLMS_EULER_B) return c->fail(-1, "rdm_op_plms_step: mode %d is none of 0 (step), 1 (Euler A), 2 (Euler B)", mode);
+    if (order < 0 || order > 3) return c->fail(-1, "rdm_op_plms_step: order %d outside 0..3", order);
+    if (mode == PLMS_EULER_B && !e_prev) return c->fail(-1, "rdm_op_plms_step: Euler B reads e_prev, which is null");
+    if (mode == PLMS_STEP && ((order >= 1 && !h1) || (order >= 2 && !h2) || (order >= 3 && !h3)))
+        return c->fail(-1, "rdm_op_plms_step: order %d needs history operands that are null", order);
+    if (mode != PLMS_EULER_B && !e_store) return c->fail(-1, "rdm_op_plms_step: mode %d writes e_store, which is null", mode);
+    PlmsStepParams p{};
+    p.x = x; p.eps = eps; p.e_prev = e_prev; p.h1 = h1; p.h2 = h2; p.h3 = h3; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale;
+    p.a_t = a_t; p.a_prev = a_prev; p.sqrt_one_minus_at = sqrt_one_minus_at; p.mode = mode; p.order = order;
+    p.e_store = e_store; p.x_out = x_out; p.x_dup = x_dup; p.pred_x0 = pred_x0;
+    RDM_CHECK_HIP(c, launch_plms_step(p, c->stream));
+    return 0;
+}
+
+static void ddpm_step_fill(DdpmStepParams& p, const float* x, const float* eps, long long n, float sqrt_recip, float sqrt_recipm1, float coef1,
+                           float coef2, float log_var, int clip, int nonzero, float temperature, float* x_prev) {
+    p.x = x; p.eps = eps; p.x_prev = x_prev; p.n = n; p.sqrt_recip = sqrt_recip; p.sqrt_recipm1 = sqrt_recipm1; p.coef1 = coef1; p.coef2 = coef2;
+    p.log_var = log_var; p.clip = clip ? 1 : 0; p.nonzero = nonzero ? 1 : 0; p.temperature = temperature;
+}
+int rdm_op_ddpm_step(rdm_ctx* c, const float* x, const float* eps, const float* noise, long long n, float sqrt_recip, float sqrt_recipm1,
+                     float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, float* x_prev) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddpm_step: bad argument");
+    if (nonzero && !noise) return c->fail(-1, "rdm_op_ddpm_step: nonzero needs a noise operand (or the seeded entry)");
+    DdpmStepParams p{};
+    ddpm_step_fill(p, x, eps, n, sqrt_recip, sqrt_recipm1, coef1, coef2, log_var, clip, nonzero, temperature, x_prev);
+    p.noise = noise;
+    RDM_CHECK_HIP(c, launch_ddpm_step(p, c->stream));
+    return 0;
+}
+int rdm_op_ddpm_step_seeded(rdm_ctx* c, const float* x, const float* eps, long long n, int64_t per_row, float sqrt_recip, float sqrt_recipm1,
+                            float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, uint64_t seed, int64_t row0,
+                            uint32_t step, float* x_prev) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddpm_step_seeded: bad argument");
+    RDM_TRY(check_noise_rows(c, "rdm_op_ddpm_step_seeded", row0, per_row >= 1 ? n / per_row : 0, per_row));
+    DdpmStepParams p{};
+    ddpm_step_fill(p, x, eps, n, sqrt_recip, sqrt_recipm1, coef1, coef2, log_var, clip, nonzero, temperature, x_prev);
+    const hipError_t e = launch_ddpm_step_seeded(p, StepRngParams{seed, per_row, (uint32_t)row0, step}, c->stream);
+    if (e == hipErrorInvalidValue)
+        return c->fail(-1, "rdm_op_ddpm_step_seeded: per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned");
+    RDM_CHECK_HIP(c, e);
+    return 0;
+}
+
 // ---- the DPM-Solver++ and UniPC step kernels alone
 int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int cfg, float scale, float sqrt_a_s,
                       float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup, float* m_store, float* pred_x0) {
