@@ -251,6 +251,23 @@ int rdm_ddim_sample_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, uint64_t see
                            const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter);
 int rdm_ddpm_sample_seeded(rdm_ctx* ctx, const rdm_ddpm_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
                            float* z_out);
+/* SDE-DPM-Solver++(2M): the "sde-dpmsolver++" multistep update of Lu et al.'s reference implementation, a stochastic sampler at
+ * DPM-Solver++'s step counts, on rdm_dpmpp_sample's arguments, node quantities and order rule.  Step j from s = nodes[j] to t = nodes[j+1],
+ * h = lambda_t - lambda_s, m_j = (x - sigma_s eps) / alpha_s with the guided eps:
+ *     g   = alpha_t (1 - exp(-2h))                                           (= -alpha_t expm1(-2h))
+ *     x  <- (sigma_t / sigma_s) exp(-h) x + g m_j  [+ (g / (2r)) (m_j - m_{j-1}), r = h_{j-1} / h, on a second-order step]
+ *           + sigma_t sqrt(1 - exp(-2h)) z_j,   z_j ~ N(0, I)
+ * The host flattens this in float64 to x <- c_x x + c_0 m_j + c_1 m_{j-1} + c_n z_j; the kernel sums left to right in fp32.  The noise is
+ * not scaled by an eta.  rdm_dpmpp_sde_sample: z_j = noise[j], noise [dev] f32 [n_nodes - 1, B, C, H, W] (required).
+ * rdm_dpmpp_sde_sample_seeded: z_j is drawn in the step kernel from the device-noise counters above -- stream 1, step = the loop step j,
+ * row = row0 + b, block = (element within the row) >> 2 -- and the loop is bit-identical to the stack loop fed with
+ * rdm_op_randn(seed, row0, B, per_row, step = j, stream = 1) for j = 0 .. n_nodes - 2.  x_T may be NULL there: the start is then the normals
+ * of (seed, stream 0, step 0), as rdm_ddim_sample_seeded; channels * height * width must be a multiple of 4.  pred_x0_inter holds m_j;
+ * intermediates and other arguments as rdm_dpmpp_sample. */
+int rdm_dpmpp_sde_sample(rdm_ctx* ctx, const rdm_dpmpp_args* args, const float* x_T, const float* cond, const float* uncond,
+                         const float* noise, float* z_out, float* x_inter, float* pred_x0_inter);
+int rdm_dpmpp_sde_sample_seeded(rdm_ctx* ctx, const rdm_dpmpp_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
+                                const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter);
 
 /* ---- image-to-image on the DDIM schedule (ldm DDIMSampler.stochastic_encode / encode / decode; the reference's vendored ddim.py stops
  * before them) ------------------------------------------------------------------------------------
@@ -620,6 +637,21 @@ int rdm_op_ddpm_step_seeded(rdm_ctx* ctx, const float* x, const float* eps, long
 int rdm_op_dpmpp_step(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, long long n, int cfg, float scale,
                       float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup_or_null,
                       float* m_store_or_null, float* pred_x0_or_null);
+/* One SDE-DPM-Solver++ update, the kernel of rdm_dpmpp_sde_sample alone (fp32, n elements): e and m0 as rdm_op_dpmpp_step;
+ * x_out = ((c_x x + c_0 m0) + c_1 m_prev) + c_n z (no m_prev: the c_1 term is absent), with the formula's flattened coefficients
+ * c_x = (sigma_t / sigma_s) exp(-h), c_0 + c_1 = alpha_t (1 - exp(-2h)), c_n = sigma_t sqrt(1 - exp(-2h)) -- the caller owns the schedule;
+ * x_dup <- x_out, m_store <- m0, pred_x0 <- m0.  m_store may be m_prev itself.  z = noise[i] (required).
+ * rdm_op_dpmpp_sde_step_seeded: the kernel of rdm_dpmpp_sde_sample_seeded -- z of element i is the normal of the device-noise counters
+ * (seed, stream 1, step, row0 + i / per_row, block (i % per_row) >> 2), drawn in registers: bit-identical to rdm_op_dpmpp_sde_step fed with
+ * rdm_op_randn(seed, row0, n / per_row, per_row, step, stream = 1).  It has no scalar form: per_row a multiple of 4 that divides n and
+ * 16-byte aligned operands are required (-1 otherwise), and rows [row0, row0 + n / per_row) must pass the device-noise row check. */
+int rdm_op_dpmpp_sde_step(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, const float* noise, long long n, int cfg,
+                          float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out,
+                          float* x_dup_or_null, float* m_store_or_null, float* pred_x0_or_null);
+int rdm_op_dpmpp_sde_step_seeded(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, long long n, int64_t per_row,
+                                 int cfg, float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n,
+                                 uint64_t seed, int64_t row0, uint32_t step, float* x_out, float* x_dup_or_null, float* m_store_or_null,
+                                 float* pred_x0_or_null);
 /* One UniPC pass, the kernel of rdm_unipc_sample alone (fp32, n elements; coefficients [host]: the 13 doubles of rdm_unipc_coefficients,
  * rounded to fp32 here): e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i]) : eps[i]; m = (u - sigma e) / alpha;
  * xc = order_c ? a_x xc_prev + a_t m + a_1 h1 (+ a_2 h2) (+ a_3 h3) : u; u_next = b_x xc + b_0 m (+ b_1 h1) (+ b_2 h2), terms up to the

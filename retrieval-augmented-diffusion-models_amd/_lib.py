@@ -137,6 +137,8 @@ SIGNATURES = {
     "rdm_op_randn": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P]),
     "rdm_ddim_sample_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "rdm_ddpm_sample_seeded": (C.c_int, [_P, C.POINTER(DdpmArgs), C.c_uint64, C.c_int64, _P, _P, _P]),
+    "rdm_dpmpp_sde_sample": (C.c_int, [_P, C.POINTER(DpmppArgs), _P, _P, _P, _P, _P, _P, _P]),
+    "rdm_dpmpp_sde_sample_seeded": (C.c_int, [_P, C.POINTER(DpmppArgs), C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
     "rdm_unet_forward_guided": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_ddim_decode": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
     "rdm_ddim_decode_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
@@ -206,6 +208,10 @@ SIGNATURES = {
     "rdm_op_add": (C.c_int, [_P, _P, _P, _P, C.c_longlong]),
     "rdm_op_dpmpp_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     _P, _P, _P, _P]),
+    "rdm_op_dpmpp_sde_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, _P, _P, _P, _P]),
+    "rdm_op_dpmpp_sde_step_seeded": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                               C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_int64, C.c_uint32, _P, _P, _P, _P]),
     "rdm_op_unipc_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.POINTER(C.c_double), _P, _P, _P, _P, _P]),
     "rdm_op_ddim_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                    _P, _P, _P]),
@@ -1091,6 +1097,48 @@ class Context:
         self._check(lib.rdm_op_dpmpp_step(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), n, int(bool(cfg)), float(scale), float(sqrt_a_s),
                                           float(sqrt_one_minus_a_s), float(c_x), float(c_0), float(c_1), _ptr(x_out), _ptr(x_dup),
                                           _ptr(m_store), _ptr(pred_x0)))
+
+    def dpmpp_sde_sample(self, nodes, x_T, cond, uncond, alphas_cumprod, scale=1.0, order=2, lower_order_final=None, noise=None,
+                         log_every_t=100, want_intermediates=False, seed=None, row0=0, shape=None):
+        """SDE-DPM-Solver++(2M) over the node list of dpmpp_sample: rdm_dpmpp_sde_sample with `noise`, the [len(nodes) - 1, B, C, H, W] stack of
+        the steps' z_j; with `seed` rdm_dpmpp_sde_sample_seeded: z_j is the library's own (seed, stream 1, step j, row0 + b), generated in
+        the step kernel (`noise` must then be None), and x_T may be None -- the start is then drawn from stream 0 at the latent `shape`
+        (C, H, W), for cond.shape[0] rows.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
+        if lower_order_final is None:
+            lower_order_final = _nodes_array(nodes).shape[0] - 1 < 15
+        fields = dict(nodes=nodes, order=int(order), lower_order_final=int(bool(lower_order_final)))
+        if seed is None:
+            if x_T is None or noise is None:
+                raise RdmError("dpmpp_sde_sample: x_T and a noise stack are required without a seed")
+            noise = self._dev(noise, torch.float32)
+            return self._sampler_call("dpmpp_sde_sample", lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample(h, a, x, c, u, _ptr(noise), *out),
+                                      DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, noise=noise, **fields)
+        if noise is not None:
+            raise RdmError("dpmpp_sde_sample: give a seed or a noise stack, not both")
+        x_shape = self._seeded_shape("dpmpp_sde_sample", x_T, cond, shape)
+        seed, row0 = _noise_seed("dpmpp_sde_sample", seed, row0, x_shape[0])
+        return self._sampler_call("dpmpp_sde_sample", lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample_seeded(h, a, seed, row0, x, c, u, *out),
+                                  DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, x_shape=x_shape, **fields)
+
+    def op_dpmpp_sde_step(self, x, eps, m_prev, noise, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup=None,
+                          m_store=None, pred_x0=None, seed=None, row0=0, per_row=None, step=0):
+        """The SDE-DPM-Solver++ update kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
+        [cond | uncond]) (rdm_op_dpmpp_sde_step); m_prev / x_dup / m_store / pred_x0 may be None, m_store may be m_prev.  With `seed` (and
+        no noise) rdm_op_dpmpp_sde_step_seeded: the noise of (seed, stream 1, step, row0 + b) for rows of per_row elements, drawn in the
+        kernel.  Writes into the given outputs."""
+        n = self._step_sizes("op_dpmpp_sde_step", x, eps, cfg, (m_prev, noise, x_out, x_dup, m_store, pred_x0))
+        sc = [float(v) for v in (scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n)]
+        outs = (_ptr(x_out), _ptr(x_dup), _ptr(m_store), _ptr(pred_x0))
+        if seed is None:
+            if noise is None:
+                raise RdmError("op_dpmpp_sde_step: a noise operand or a seed is required")
+            self._check(lib.rdm_op_dpmpp_sde_step(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), _ptr(noise), n, int(bool(cfg)), *sc, *outs))
+            return
+        if noise is not None or per_row is None:
+            raise RdmError("op_dpmpp_sde_step: a seeded call takes per_row and no noise operand")
+        seed, row0, per_row, step = self._step_rows("op_dpmpp_sde_step", n, per_row, seed, row0, step)
+        self._check(lib.rdm_op_dpmpp_sde_step_seeded(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), n, per_row, int(bool(cfg)), *sc, seed, row0, step,
+                                                     *outs))
 
     @staticmethod
     def unipc_coefficients(nodes, alphas_cumprod, j, order=2, variant="bh2", corrector=True, lower_order_final=True):

@@ -124,6 +124,19 @@ struct DpmppStepParams {
     int cfg;
 };
 
+// One SDE-DPM-Solver++ step (Lu et al. 2022, the "sde-dpmsolver++" multistep update; rdm_dpmpp_sde_sample): DpmppStepParams' operands and
+// m0, plus the step's noise -- x_out = ((c_x x + c_0 m0) + c_1 m_prev) + c_n z, with z = noise[i] (the stack form) or the normal of
+// StepRngParams drawn in registers (the seeded form: noise unused).  First-order step: m_prev null, c_1 unused.  m_store may be m_prev.
+struct DpmppSdeStepParams {
+    const float* x; const float* eps;                        // eps: [n] rows (cfg == 0) or [2n] (cond | uncond)
+    const float* m_prev;                                     // the previous step's m0, or null
+    const float* noise;                                      // z_j, n elements (stack form)
+    float* x_out; float* x_dup; float* m_store; float* pred_x0;     // x_dup, m_store, pred_x0 may be null
+    long long n;                                             // B*C*H*W
+    float sqrt_a_s, sqrt_one_minus_a_s, scale, c_x, c_0, c_1, c_n;
+    int cfg;
+};
+
 // One UniPC pass (Zhao et al. 2023, data prediction, multistep), run after the forward at node j: e = CFG(eps), m = (u - sigma e) / alpha
 // -> m_store, pred_x0; the correction of the kept iterate xc = a_x xc_prev + a_t m + a_1 h1 + a_2 h2 + a_3 h3 with order_c history terms
 // (order_c == 0: xc = u, xc_prev unused) -> xc_out; the prediction u_next = b_x xc + b_0 m + b_1 h1 + b_2 h2 with order_p - 1 history
@@ -331,6 +344,8 @@ hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams&
 hipError_t launch_rng_fill(const RngFillParams& p, bool normal, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
 hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);
+hipError_t launch_dpmpp_sde_step(const DpmppSdeStepParams& p, hipStream_t st);
+hipError_t launch_dpmpp_sde_step_seeded(const DpmppSdeStepParams& p, const StepRngParams& g, hipStream_t st);   // as launch_ddim_step_seeded
 hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st);
 hipError_t launch_ddim_inverse_step(const DdimInverseStepParams& p, hipStream_t st);
 hipError_t launch_q_sample_seeded(const QSampleSeededParams& p, hipStream_t st);     // hipErrorInvalidValue: per_row % 4 or an operand not 16-byte aligned

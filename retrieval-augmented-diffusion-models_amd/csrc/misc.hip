@@ -637,6 +637,46 @@ hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st) {
     return launch_step(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.x_out, p.x_dup, p.m_store, p.pred_x0}, p, dpmpp_step_kernel<4>, dpmpp_step_kernel<1>, st);
 }
 
+// ------------------------------------------------------------------ SDE-DPM-Solver++ update (fp32)
+// Lu et al.'s "sde-dpmsolver++" multistep update (rdm_dpmpp_sde_sample's header comment): dpmpp_step_kernel's pass with the step's noise
+// as a fourth term, x_out = ((c_x x + c_0 m0) + c_1 m_prev) + c_n z, the four coefficients computed by the host in float64.  True
+// divisions, no FMA contraction, the sum taken left to right.  dpmpp_sde_update is the element arithmetic of both forms: the stack
+// kernel below reads z from memory, dpmpp_sde_step_seeded_kernel (with the device-noise kernels) draws it in registers, and the two then
+// round alike.  m_store may be m_prev's slot, as in dpmpp_step_kernel.
+template <int V>
+__device__ __forceinline__ void dpmpp_sde_update(const DpmppSdeStepParams& p, long long i, const float (&z)[V]) {
+#pragma clang fp contract(off)
+    float e[V], x[V], m0[V], xo[V];
+    step_guided_eps<V>(p.eps, p.n, i, p.cfg, p.scale, e);
+    step_ld<V>(p.x, i, x);
+#pragma unroll
+    for (int k = 0; k < V; k++) { m0[k] = (x[k] - p.sqrt_one_minus_a_s * e[k]) / p.sqrt_a_s; xo[k] = p.c_x * x[k] + p.c_0 * m0[k]; }
+    if (p.m_prev) {
+        float q[V]; step_ld<V>(p.m_prev, i, q);
+#pragma unroll
+        for (int k = 0; k < V; k++) xo[k] = xo[k] + p.c_1 * q[k];
+    }
+#pragma unroll
+    for (int k = 0; k < V; k++) xo[k] = xo[k] + p.c_n * z[k];
+    if (p.m_store) step_st<V>(p.m_store, i, m0);          // after the m_prev read: m_store may be that slot
+    step_st<V>(p.x_out, i, xo);
+    if (p.x_dup) step_st<V>(p.x_dup, i, xo);
+    if (p.pred_x0) step_st<V>(p.pred_x0, i, m0);
+}
+template <int V>
+__global__ __launch_bounds__(256) void dpmpp_sde_step_kernel(DpmppSdeStepParams p) {
+    const long long nv = p.n / V;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * V;
+        float z[V]; step_ld<V>(p.noise, i, z);
+        dpmpp_sde_update<V>(p, i, z);
+    }
+}
+hipError_t launch_dpmpp_sde_step(const DpmppSdeStepParams& p, hipStream_t st) {
+    return launch_step(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.noise, p.x_out, p.x_dup, p.m_store, p.pred_x0}, p,
+                       dpmpp_sde_step_kernel<4>, dpmpp_sde_step_kernel<1>, st);
+}
+
 // ------------------------------------------------------------------ UniPC predict-and-correct (fp32)
 // Zhao et al. 2023 (UniPC, data prediction, multistep): after the forward at node j one pass forms m = (u - sigma_j e) / alpha_j from
 // the guided eps, corrects the kept iterate, xc = a_x xc_prev + a_t m + a_1 h1 + a_2 h2 + a_3 h3 (order_c history terms; order_c == 0:
@@ -858,6 +898,22 @@ hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams&
     if (!seeded_step_ok(p.n, g.per_row, {p.x, p.eps, p.x_prev})) return hipErrorInvalidValue;
     const int grid = (int)std::min<long long>((p.n / 4 + 255) / 256, 2048);
     ddpm_step_seeded_kernel<<<grid, 256, 0, st>>>(p, g);
+    return hipGetLastError();
+}
+// The SDE-DPM-Solver++ update on noise drawn in registers: ddim_step_seeded_kernel's (row, block) derivation, dpmpp_sde_update's arithmetic
+__global__ __launch_bounds__(256) void dpmpp_sde_step_seeded_kernel(DpmppSdeStepParams p, StepRngParams g) {
+    const long long nv = p.n >> 2, bpr = g.per_row >> 2;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long r = v / bpr;
+        float z[4];
+        philox_normal4(g.seed, (uint32_t)(v - r * bpr), g.step, g.row0 + (uint32_t)r, RDM_RNG_STREAM_STEP, z);
+        dpmpp_sde_update<4>(p, v * 4, z);
+    }
+}
+hipError_t launch_dpmpp_sde_step_seeded(const DpmppSdeStepParams& p, const StepRngParams& g, hipStream_t st) {
+    if (!seeded_step_ok(p.n, g.per_row, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.x_out, p.x_dup, p.m_store, p.pred_x0})) return hipErrorInvalidValue;
+    const int grid = (int)std::min<long long>((p.n / 4 + 255) / 256, 2048);
+    dpmpp_sde_step_seeded_kernel<<<grid, 256, 0, st>>>(p, g);
     return hipGetLastError();
 }
 

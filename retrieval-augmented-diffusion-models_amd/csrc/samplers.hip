@@ -1,4 +1,4 @@
-// The five sampling loops of librdm_hip (DDIM, PLMS, DPM-Solver++(2M), UniPC, DDPM): their schedules, SamplerRun (one sampling
+// The sampling loops of librdm_hip (DDIM, PLMS, DPM-Solver++(2M) and its SDE form, UniPC, DDPM): their schedules, SamplerRun (one sampling
 // call's scratch, tables and UNet forward), the rdm_*_sample entries, the device-noise entries, DDIM image-to-image (rdm_ddim_decode: the
 // DDIM loop begun part-way down the schedule; rdm_ddim_encode: the loop that runs UP it) and the step-kernel op entries.
 // Calls into unet_exec.hip through the three functions host.h declares (unet_prepare_kv, unet_emb_table, unet_forward_impl) and
@@ -390,6 +390,70 @@ int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, cons
     return run.finish(z_out);
 }
 
+// The loop of rdm_dpmpp_sde_sample (ns null: z_j is row j of the stack `noise`) and rdm_dpmpp_sde_sample_seeded (ns: z_j is drawn in the step
+// kernel at step counter j, and a null x_T is drawn): rdm_dpmpp_sample's loop -- one forward and one kernel launch per step, ONE history
+// slot -- with the SDE update's four coefficients computed here in float64.
+static int dpmpp_sde_sample_impl(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond, const float* noise,
+                                 const NoiseSeed* ns, float* z_out, float* x_inter, float* pred_x0_inter) {
+    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
+    if (a->order != 1 && a->order != 2) return c->fail(-1, "sde-dpm-solver++ order must be 1 or 2, got %d", a->order);
+    bool cfg;
+    RDM_TRY(sampler_guidance(c, "sde-dpm-solver++", a->unconditional_guidance_scale, uncond, &cfg));
+    RDM_TRY(sampler_nodes(c, "sde-dpm-solver++", a->alphas_cumprod, a->T, a->nodes, a->n_nodes));
+    if (ns) {
+        RDM_TRY(check_noise_rows(c, "sde-dpm-solver++ (seeded)", ns->row0, a->batch, (int64_t)a->channels * a->height * a->width));
+        if (((int64_t)a->channels * a->height * a->width) % 4) return c->fail(-1, "sde-dpm-solver++ (seeded): channels * height * width must be a multiple of 4");
+    }
+    const int n_steps = a->n_nodes - 1;
+    const std::vector<int> ts(a->nodes, a->nodes + n_steps);
+    SamplerRun run;
+    RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 1));
+    if (!x_T) RDM_TRY(run.draw_start(*ns));
+    float* m_slot = run.extra[0];
+    double h_prev = 0.0;
+    for (int j = 0; j < n_steps; j++) {
+        const SolverNode s = solver_node(a->alphas_cumprod, a->nodes[j]), t = solver_node(a->alphas_cumprod, a->nodes[j + 1]);
+        const double h = t.lambda - s.lambda, q = -std::expm1(-2.0 * h), g = t.alpha * q;       // q = 1 - exp(-2h)
+        const bool second = a->order == 2 && j >= 1 && !(a->lower_order_final && j == n_steps - 1);
+        RDM_TRY(run.forward(j));
+        DpmppSdeStepParams p{};
+        p.x = run.x; p.eps = run.eps; p.n = run.n1; p.cfg = cfg ? 1 : 0; p.scale = a->unconditional_guidance_scale;
+        p.sqrt_a_s = (float)s.alpha; p.sqrt_one_minus_a_s = (float)s.sigma;
+        p.c_x = (float)(t.sigma / s.sigma * std::exp(-h)); p.c_n = (float)(t.sigma * std::sqrt(q));
+        if (second) {
+            const double r = h_prev / h;
+            p.m_prev = m_slot; p.c_0 = (float)(g * (1.0 + 1.0 / (2.0 * r))); p.c_1 = (float)(-g / (2.0 * r));
+        } else {
+            p.c_0 = (float)g;
+        }
+        p.x_out = run.x; p.x_dup = run.x_dup; p.m_store = m_slot; p.pred_x0 = run.pred_x0_slot(j);
+        if (ns) {          // the noise of loop step j, in registers
+            const hipError_t e = launch_dpmpp_sde_step_seeded(p, run.step_rng(*ns, j), c->stream);
+            if (e == hipErrorInvalidValue) return c->fail(-1, "sde-dpm-solver++ (seeded): pred_x0_inter must be 16-byte aligned");
+            RDM_CHECK_HIP(c, e);
+        } else {
+            p.noise = noise + (size_t)j * run.n1;
+            RDM_CHECK_HIP(c, launch_dpmpp_sde_step(p, c->stream));
+        }
+        h_prev = h;
+        RDM_TRY(run.log_x(j));
+    }
+    return run.finish(z_out);
+}
+int rdm_dpmpp_sde_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond, const float* noise,
+                         float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_T || !cond || !noise || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
+    return dpmpp_sde_sample_impl(c, a, x_T, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
+}
+int rdm_dpmpp_sde_sample_seeded(rdm_ctx* c, const rdm_dpmpp_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
+                                const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
+    const NoiseSeed ns{seed, row0};
+    return dpmpp_sde_sample_impl(c, a, x_T, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
+}
+
 // UniPC (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models"), data prediction,
 // multistep, in the notation of rdm_unipc_sample's header comment.  Everything below is float64 host code.
 
@@ -747,6 +811,38 @@ int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float*
     p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1;
     p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
     RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
+    return 0;
+}
+static void dpmpp_sde_step_fill(DpmppSdeStepParams& p, const float* x, const float* eps, const float* m_prev, long long n, int cfg, float scale,
+                                float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out, float* x_dup,
+                                float* m_store, float* pred_x0) {
+    p.x = x; p.eps = eps; p.m_prev = m_prev; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale; p.sqrt_a_s = sqrt_a_s;
+    p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1; p.c_n = c_n;
+    p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
+}
+int rdm_op_dpmpp_sde_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, const float* noise, long long n, int cfg, float scale,
+                          float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out, float* x_dup,
+                          float* m_store, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!x || !eps || !noise || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_sde_step: bad argument");
+    DpmppSdeStepParams p{};
+    dpmpp_sde_step_fill(p, x, eps, m_prev, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
+    p.noise = noise;
+    RDM_CHECK_HIP(c, launch_dpmpp_sde_step(p, c->stream));
+    return 0;
+}
+int rdm_op_dpmpp_sde_step_seeded(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int64_t per_row, int cfg,
+                                 float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, uint64_t seed,
+                                 int64_t row0, uint32_t step, float* x_out, float* x_dup, float* m_store, float* pred_x0) {
+    RDM_ENTER(c);
+    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_sde_step_seeded: bad argument");
+    RDM_TRY(check_noise_rows(c, "rdm_op_dpmpp_sde_step_seeded", row0, per_row >= 1 ? n / per_row : 0, per_row));
+    DpmppSdeStepParams p{};
+    dpmpp_sde_step_fill(p, x, eps, m_prev, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
+    const hipError_t e = launch_dpmpp_sde_step_seeded(p, StepRngParams{seed, per_row, (uint32_t)row0, step}, c->stream);
+    if (e == hipErrorInvalidValue)
+        return c->fail(-1, "rdm_op_dpmpp_sde_step_seeded: per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned");
+    RDM_CHECK_HIP(c, e);
     return 0;
 }
 int rdm_op_unipc_step(rdm_ctx* c, const float* u, const float* eps, const float* xc_prev, const float* h1, const float* h2, const float* h3,

@@ -20,7 +20,7 @@ import torch
 from ... import _lib, packing, parallel
 from ...util import ischannellastimage
 from .ddim import DDIMSampler
-from .dpm_solver import DPMSolverSampler
+from .dpm_solver import DPMSolverSampler, DPMSolverSDESampler
 from .plms import PLMSSampler
 from .uni_pc import UniPCSampler
 
@@ -200,7 +200,11 @@ class MinimalRETRODiffusion(object):
                 kwargs["x_T"] = parallel.per_sample_noise(base, range(lo, hi), shape, device=self.device)
             steps = None
             noiseless = any(kwargs.get(name, False) for name in ("plms", "dpm_solver", "uni_pc"))      # these draw no per-step noise
-            if not noiseless and kwargs.get("ddim", True) and kwargs.get("eta", 0.) != 0.:
+            if kwargs.get("dpm_solver_sde", False):          # one z per step of the node list (the logSNR grid may come out shorter than S)
+                nodes = kwargs.get("timesteps")
+                steps = (len(nodes) if nodes is not None else
+                         len(_lib.dpmpp_timesteps(kwargs.get("S", kwargs.get("ddim_steps")), self.alphas_cumprod, kwargs.get("skip_type", "logSNR")))) - 1
+            elif not noiseless and kwargs.get("ddim", True) and kwargs.get("eta", 0.) != 0.:
                 steps = len(range(0, self.num_timesteps, self.num_timesteps // kwargs.get("S", kwargs.get("ddim_steps"))))
             elif not noiseless and not kwargs.get("ddim", True):
                 steps = int(kwargs.get("timesteps") or self.num_timesteps)
@@ -406,24 +410,28 @@ class MinimalRETRODiffusion(object):
     # ---- samplers
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, dpm_solver=False,
-                   uni_pc=False, init_latent=None, strength=None, invert=False, invert_scale=1.0, **kwargs):
+                   uni_pc=False, init_latent=None, strength=None, invert=False, invert_scale=1.0, dpm_solver_sde=False, **kwargs):
         """ddpm.py:988-1011.  [native] plms=True samples with PLMSSampler (ldm), dpm_solver=True with DPMSolverSampler (DPM-Solver++ 2M
-        on the logSNR grid), uni_pc=True with UniPCSampler (UniPC order 2, bh2, with the corrector, on the logSNR grid) on
+        on the logSNR grid), uni_pc=True with UniPCSampler (UniPC order 2, bh2, with the corrector, on the logSNR grid),
+        dpm_solver_sde=True with DPMSolverSDESampler (SDE-DPM-Solver++ 2M on the logSNR grid: fresh noise every step) on
         S = ddim_steps instead of DDIM / DDPM.  init_latent / strength / invert / invert_scale [native]: image-to-image, DDIM only
         (_img2img)."""
         if plms and dpm_solver:
             raise ValueError("plms and dpm_solver select different samplers: give one of them")
         if uni_pc and (plms or dpm_solver):
             raise ValueError(f"{'plms' if plms else 'dpm_solver'} and uni_pc select different samplers: give one of them")
+        if dpm_solver_sde and (plms or dpm_solver or uni_pc):
+            raise ValueError(f"{'plms' if plms else 'dpm_solver' if dpm_solver else 'uni_pc'} and dpm_solver_sde select different samplers: "
+                             "give one of them")
         shape = (self.channels, self.image_size, self.image_size) if custom_shape is None else self._latent_shape(custom_shape)
         if init_latent is not None or strength is not None or invert:
-            if plms or dpm_solver or uni_pc or not ddim:
+            if plms or dpm_solver or uni_pc or dpm_solver_sde or not ddim:
                 raise ValueError("image-to-image (init_latent / strength / invert) runs on the DDIM sampler only: "
-                                 "drop plms / dpm_solver / uni_pc and keep ddim=True")
+                                 "drop plms / dpm_solver / uni_pc" + (" / dpm_solver_sde" if dpm_solver_sde else "") + " and keep ddim=True")
             return self._img2img(cond, batch_size, ddim_steps, shape, init_latent, strength, invert, invert_scale, **kwargs)
-        if ddim or plms or dpm_solver or uni_pc:
+        if ddim or plms or dpm_solver or uni_pc or dpm_solver_sde:
             sampler = (PLMSSampler(self) if plms else DPMSolverSampler(self) if dpm_solver else UniPCSampler(self) if uni_pc
-                       else DDIMSampler(self))
+                       else DPMSolverSDESampler(self) if dpm_solver_sde else DDIMSampler(self))
             ddim_steps = kwargs.pop('S', ddim_steps)
             verbose = kwargs.pop('verbose', False)
             return sampler.sample(S=ddim_steps, batch_size=batch_size, shape=shape, conditioning=cond, verbose=verbose, **kwargs)
@@ -453,9 +461,10 @@ class MinimalRETRODiffusion(object):
             return
         if init_image is not None and init_latent is not None:
             raise ValueError("init_image and init_latent are the same input in two forms: give one of them")
-        if any(kwargs.get(name, False) for name in ("plms", "dpm_solver", "uni_pc")) or not kwargs.get("ddim", True):
+        sde = kwargs.get("dpm_solver_sde", False)
+        if sde or any(kwargs.get(name, False) for name in ("plms", "dpm_solver", "uni_pc")) or not kwargs.get("ddim", True):
             raise ValueError("image-to-image (init_image / init_latent) runs on the DDIM sampler only: "
-                             "drop plms / dpm_solver / uni_pc and keep ddim=True")
+                             "drop plms / dpm_solver / uni_pc" + (" / dpm_solver_sde" if sde else "") + " and keep ddim=True")
         DDIMSampler.img2img_steps(strength, 1)
         if init_image is not None and torch.as_tensor(init_image).ndim not in (3, 4):
             raise ValueError(f"init_image must be channel-last, [B,H,W,C] or [H,W,C] in [-1, 1], got {tuple(torch.as_tensor(init_image).shape)}")

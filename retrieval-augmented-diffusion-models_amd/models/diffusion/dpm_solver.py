@@ -21,6 +21,8 @@ Options that change the loop body per step (callbacks, mask / x0 inpainting, qua
 score_corrector) take the per-step path: native `apply_model`, torch fp32 update; it reads only `model.num_timesteps`,
 `model.alphas_cumprod`, `model.device` and `model.apply_model` (and `model.q_sample` under a mask, when the model has one).  The solver
 is deterministic: eta != 0 raises ValueError; `temperature` and `noise_dropout` have no effect.
+
+DPMSolverSDESampler [native], at the end of the file, is the solver's stochastic form (SDE-DPM-Solver++(2M)) on the same surface.
 """
 import math
 
@@ -43,6 +45,22 @@ def dpmpp_coefficients(alphas_cumprod, s, t, h_prev=None):
         return math.sqrt(a_s), math.sqrt(1.0 - a_s), c_x, g, 0.0, h
     r = h_prev / h
     return math.sqrt(a_s), math.sqrt(1.0 - a_s), c_x, g * (1.0 + 1.0 / (2.0 * r)), -g / (2.0 * r), h
+
+
+def dpmpp_sde_coefficients(alphas_cumprod, s, t, h_prev=None):
+    """Step s -> t of SDE-DPM-Solver++ in float64 from the fp32 alphas_cumprod: (alpha_s, sigma_s, c_x, c_0, c_1, c_n, h) with
+    x_t = c_x x + c_0 m + c_1 m_prev + c_n z (rdm_dpmpp_sde_sample's flattened form).  h_prev None: first-order step (c_1 = 0)."""
+    a_s, a_t = float(alphas_cumprod[s]), float(alphas_cumprod[t])
+    lam = lambda a: 0.5 * math.log(a / (1.0 - a))
+    h = lam(a_t) - lam(a_s)
+    q = -math.expm1(-2.0 * h)                   # 1 - exp(-2h)
+    g = math.sqrt(a_t) * q
+    c_x = math.sqrt(1.0 - a_t) / math.sqrt(1.0 - a_s) * math.exp(-h)
+    c_n = math.sqrt(1.0 - a_t) * math.sqrt(q)
+    if h_prev is None:
+        return math.sqrt(a_s), math.sqrt(1.0 - a_s), c_x, g, 0.0, c_n, h
+    r = h_prev / h
+    return math.sqrt(a_s), math.sqrt(1.0 - a_s), c_x, g * (1.0 + 1.0 / (2.0 * r)), -g / (2.0 * r), c_n, h
 
 
 class _NodeListSampler(_SamplerBase):
@@ -145,6 +163,81 @@ class DPMSolverSampler(_NodeListSampler):
             x = f32(c_x) * x + f32(c_0) * m
             if second:
                 x = x + f32(c_1) * m_prev
+            m_prev = m
+            return x, m
+        return update
+
+
+class DPMSolverSDESampler(_NodeListSampler):
+    """[native] SDE-DPM-Solver++(2M): the `sde-dpmsolver++` multistep update of Lu et al.'s reference implementation -- a stochastic sampler
+    at DPM-Solver++'s step counts, on the same node lists, order rule and options as DPMSolverSampler.  Step j from s to t adds fresh noise:
+
+        g  = alpha_t (1 - exp(-2 h_j))
+        x <- (sigma_t / sigma_s) exp(-h_j) x + g m_j  [+ (g / (2r)) (m_j - m_{j-1}) on a second-order step]  + sigma_t sqrt(1 - exp(-2 h_j)) z_j
+
+    so the sample forgets its start, which the ODE solvers cannot.  The noise is not scaled by an eta: eta != 0 raises.  z_j comes from
+    `noise=` (a [steps, B, C, H, W] stack), from the library's counter-based generator under `noise_seed` / `noise_row0` (stream 1, step j,
+    rows noise_row0 .. -- generated in the step kernel, no stack exists, and a row's sample does not depend on how a batch is sharded; the
+    starting latent, when no x_T is given, is the library's too), or else from torch's generator the way DDIMSampler draws its stack for
+    eta > 0.  The loop runs inside librdm_hip (rdm_dpmpp_sde_sample / rdm_dpmpp_sde_sample_seeded); the per-step options of
+    DPMSolverSampler take the per-step path here too."""
+    NAME = "SDE-DPM-Solver++"
+
+    @torch.no_grad()
+    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
+               quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
+               corrector_kwargs=None, verbose=True, x_T=None, log_every_t=100, unconditional_guidance_scale=1.,
+               unconditional_conditioning=None, order=2, skip_type="logSNR", lower_order_final=None, timesteps=None, noise_seed=None, noise_row0=0,
+               noise=None, **kwargs):
+        """As DPMSolverSampler.sample, plus `noise` [native]: the explicit stack [steps, B, C, H, W] of the steps' z_j (consumed in loop
+        order).  `noise_seed` / `noise_row0` select the library's generator for the starting latent (when no x_T is given) AND for z_j;
+        a stack and a seed together raise."""
+        if eta != 0:
+            raise ValueError(f"eta must be 0 for {self.NAME}: this solver's noise is not scaled by eta (it is the SDE's own)")
+        if order not in (1, 2):
+            raise ValueError(f'{self.NAME} order must be 1 or 2, got {order!r}')
+        if noise is not None and noise_seed is not None:
+            raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
+        x_T = self._seeded_start(x_T, (batch_size,) + tuple(shape), noise_seed, noise_row0)
+        nodes, cond, uc, scale, img = self._prepare(S, batch_size, shape, conditioning, 0., x_T, unconditional_guidance_scale,
+                                                    unconditional_conditioning, skip_type, timesteps)
+        n_steps = len(nodes) - 1
+        if lower_order_final is None:
+            lower_order_final = n_steps < 15
+        if noise is not None and tuple(noise.shape) != (n_steps,) + tuple(img.shape):
+            raise ValueError(f"{self.NAME} noise stack must be {(n_steps,) + tuple(img.shape)} (one z per step), got {tuple(noise.shape)}")
+        if noise is None and noise_seed is None:
+            noise = torch.randn((n_steps,) + tuple(img.shape), device=img.device)
+        print(f"Running SDE-DPM-Solver++ Sampling (order {order}) with {n_steps} timesteps")
+        if (callback is not None or img_callback is not None or quantize_x0 or mask is not None or x0 is not None or
+                score_corrector is not None):
+            draw = ((lambda j: noise[j].to(img.device)) if noise is not None else
+                    (lambda j: self._device_randn(img.shape, noise_seed, noise_row0, step=j, stream=1)))
+            return self._python_loop(nodes, cond, img, uc, scale, self._update(nodes, order, lower_order_final, quantize_x0, draw), callback,
+                                     img_callback, log_every_t, score_corrector, corrector_kwargs, mask, x0, kwargs.get("q_noise"))
+        seeded = {} if noise_seed is None else dict(seed=noise_seed, row0=noise_row0)
+        z, xi, pi = self.model.ctx.dpmpp_sde_sample(nodes, img, cond, uc, self.alphas_cumprod, scale=scale, order=order,
+                                                    lower_order_final=lower_order_final, noise=noise, log_every_t=log_every_t,
+                                                    want_intermediates=True, **seeded)
+        return z.detach(), self._intermediates(img, xi, pi)
+
+    def _update(self, nodes, order, lower_order_final, quantize_denoised, draw):
+        """The per-step path's update(j, x, eps) -> (x at node j + 1, m_j); draw(j) -> z_j."""
+        ac = self.alphas_cumprod.numpy()
+        f32 = lambda v: float(np.float32(v))
+        m_prev, h_prev = None, None
+
+        def update(j, x, e):
+            nonlocal m_prev, h_prev
+            second = order == 2 and j >= 1 and not (lower_order_final and j == len(nodes) - 2)
+            alpha_s, sigma_s, c_x, c_0, c_1, c_n, h_prev = dpmpp_sde_coefficients(ac, int(nodes[j]), int(nodes[j + 1]), h_prev if second else None)
+            m = (x - f32(sigma_s) * e) / f32(alpha_s)
+            if quantize_denoised:
+                m = self.model.quantize_first_stage(m)
+            x = f32(c_x) * x + f32(c_0) * m
+            if second:
+                x = x + f32(c_1) * m_prev
+            x = x + f32(c_n) * draw(j)
             m_prev = m
             return x, m
         return update

@@ -21,7 +21,9 @@ the finished images; `--gpu` is then ignored and each rank uses its LOCAL_RANK),
 `--steps` instead of DDIM: same schedule, about half the steps for the same accuracy; works with `--gpus N`), `--dpm_solver`
 (sample with DPM-Solver++(2M), ldm's DPMSolverSampler, on a logSNR grid of at most `--steps` steps: 15-25 steps under guidance;
 works with `--gpus N`; not together with `--plms`), `--uni_pc` (sample with UniPC order 2: DPM-Solver++(2M) plus a corrector that costs no
-forward, on the same grid; works with `--gpus N`; not together with `--plms` or `--dpm_solver`), `--height PX` / `--width PX` (image size in pixels, default the model's own: the UNet and
+forward, on the same grid; works with `--gpus N`; not together with `--plms` or `--dpm_solver`), `--dpm_solver_sde` (sample with
+SDE-DPM-Solver++(2M): DPM-Solver++'s grid and step counts with fresh noise at every step, so a stochastic sampler in about 20 forwards; works with
+`--device_noise` and `--gpus N`; not together with the other sampler flags), `--height PX` / `--width PX` (image size in pixels, default the model's own: the UNet and
 the first stage are convolutional, so a model samples at other sizes -- the reference reaches this through `sample_log(custom_shape=)`
 only, its script has no flag; multiples of 32 = first-stage factor 4 x UNet down factor 8 of the shipped models; every sampler, and
 `--gpus N`), `--eta FLOAT` (DDIM's eta, default 0.0 = the reference script's deterministic DDIM; above 0 every step adds
@@ -31,7 +33,7 @@ index): no noise tensor is drawn or stacked in Python, and the images differ fro
 `--gpus N` with the same sharding invariance), `--init_img PATH_OR_DIR` / `--strength S` / `--invert` (image-to-image on DDIM: the image,
 resized to the model's size or `--height` / `--width`, is encoded by the first stage and either noised to `int(S x steps)` steps up the
 schedule or, with `--invert`, taken there by deterministic DDIM inversion, then decoded under the retrieved neighbours; strength 1.0 runs
-every step; works with `--gpus N` and `--device_noise`; not with `--plms` / `--dpm_solver` / `--uni_pc`).
+every step; works with `--gpus N` and `--device_noise`; not with `--plms` / `--dpm_solver` / `--uni_pc` / `--dpm_solver_sde`).
 """
 import argparse
 import datetime
@@ -83,6 +85,9 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--width", type=int, default=None, help="[native] image width in pixels (default: the model's own size); a multiple of 32")
     parser.add_argument("--uni_pc", default=False, action="store_true",
                         help="[native] sample with UniPC (order 2, bh2, with the corrector) on a logSNR grid instead of DDIM")
+    parser.add_argument("--dpm_solver_sde", default=False, action="store_true",
+                        help="[native] sample with SDE-DPM-Solver++(2M) on a logSNR grid instead of DDIM: fresh noise every step, at DPM-Solver++'s "
+                        "step counts")
     parser.add_argument("--eta", type=float, default=0.0, help="[native] DDIM eta (0.0: deterministic DDIM, as the reference script samples)")
     parser.add_argument("--device_noise", default=False, action="store_true",
                         help="[native] starting latents and per-step noise from the library's counter-based generator inside the step kernels "
@@ -108,7 +113,7 @@ def parse_args(argv=None) -> argparse.Namespace:
         if v is not None and (v < SIZE_MULTIPLE or v % SIZE_MULTIPLE):
             parser.error(f"--{name} must be a positive multiple of {SIZE_MULTIPLE} (first-stage factor x UNet down factor), got {v}")
     if opt.init_img is not None:
-        for name in ("plms", "dpm_solver", "uni_pc"):
+        for name in ("plms", "dpm_solver", "uni_pc", "dpm_solver_sde"):
             if getattr(opt, name):
                 parser.error(f"--init_img runs on the DDIM sampler only: drop --{name}")
         if not 0.0 < opt.strength <= 1.0:
@@ -225,9 +230,9 @@ def _save_logs(logs, keys, opt, sampling_start, n):
 
 
 def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
-    """--plms / --dpm_solver / --uni_pc / --height / --width / --eta reach MinimalRETRODiffusion.sample_log (the sizes as its custom_shape, in
+    """--plms / --dpm_solver / --uni_pc / --dpm_solver_sde / --height / --width / --eta reach MinimalRETRODiffusion.sample_log (the sizes as its custom_shape, in
     latent pixels), --device_noise sample_with_query / sample_from_rdata; without them the calls are the reference's."""
-    kw = {name: True for name in ("plms", "dpm_solver", "uni_pc", "device_noise") if getattr(opt, name, False)}
+    kw = {name: True for name in ("plms", "dpm_solver", "uni_pc", "dpm_solver_sde", "device_noise") if getattr(opt, name, False)}
     if getattr(opt, "eta", 0.0) != 0.0:
         kw["eta"] = opt.eta
     height, width = getattr(opt, "height", None), getattr(opt, "width", None)

@@ -6,7 +6,8 @@ count (reported under "forwards") can come out below S; unipc:S is UniPC (order 
 forward per step like dpmpp.  The stochastic loops come in two forms: ddimeta:S (DDIM, eta = 1) and ddpm:S (ancestral DDPM, unguided)
 draw the starting latents and the [S, B, 3, 64, 64] noise stack per call the way MinimalRETRODiffusion._sample_shard does (one torch
 generator per sample row, then the transposed copy) and time that with the loop; ddimeta_rng:S and ddpm_rng:S are the seeded entries,
-whose step kernels generate the noise (no x_T, no stack).  Every line also carries the peak of torch.cuda.max_memory_allocated() over the
+whose step kernels generate the noise (no x_T, no stack); dpmpp_sde:S is SDE-DPM-Solver++(2M) on dpmpp's grid through its seeded entry
+(fresh noise every step, generated in the step kernel; no x_T, no stack).  Every line also carries the peak of torch.cuda.max_memory_allocated() over the
 timed calls.  Image-to-image: img2img:S:STRENGTH encodes a [B, 3, 256, 256] image batch with the first-stage encoder, noises the latent to
 n = min(total, max(1, int(STRENGTH * total))) steps up the S-step schedule with the seeded forward process (no noise tensor) and runs
 the native decode from there -- n forwards; invert:S:STRENGTH takes the latent there by n steps of native DDIM inversion (unguided)
@@ -100,17 +101,21 @@ def main():
             z, _, _ = ctx.plms_sample(S, x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         elif name == "dpmpp":
             z, _, _ = ctx.dpmpp_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
+        elif name == "dpmpp_sde":
+            calls[0] += 1
+            z, _, _ = ctx.dpmpp_sde_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), None, cond, uncond, model.alphas_cumprod, scale=2.0,
+                                           seed=1000 + calls[0], shape=(3, 64, 64))
         elif name == "unipc":
             z, _, _ = ctx.unipc_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         else:
-            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | unipc | ddimeta | ddimeta_rng | ddpm | ddpm_rng | "
+            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | dpmpp_sde | unipc | ddimeta | ddimeta_rng | ddpm | ddpm_rng | "
                              "img2img:S:STRENGTH | invert:S:STRENGTH)")
         return ctx.vq_decode(z)
 
     def forwards(name, S, strength=None):
         if name in ("img2img", "invert"):
             return steps_of(S, strength)[0] * (2 if name == "invert" else 1)
-        if name in ("dpmpp", "unipc"):
+        if name in ("dpmpp", "dpmpp_sde", "unipc"):
             return len(ctx.dpmpp_timesteps(S, model.alphas_cumprod)) - 1
         return S + (1 if name == "plms" else 0)
 

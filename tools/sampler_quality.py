@@ -2,7 +2,9 @@
 """Distances between the samplers of ONE model, in CLIP-feature FID, KID, precision / recall and density / coverage (rdm_amd.metrics): the shipped synthetic UNet
 + VQ-f4 decoder at B = 64 (CFG 2.0, k = 4 neighbours) draws the same seeds -- starting latents and conditioning from the library's
 counter-based generator, rows 0 .. seeds - 1 of `--noise_seed` -- with DDIM-200 as the converged stand-in, then again with each `name:S`
-given (default ddim:50 plms:25 dpmpp:20 unipc:10 unipc:8), and every set is compared with the DDIM-200 set on the features of the
+given (default ddim:50 plms:25 dpmpp:20 unipc:10 unipc:8; dpmpp_sde:S is SDE-DPM-Solver++(2M), whose per-step noise is the generator's
+stream 1 under `noise_seed` for the same rows, and ddimeta:S is DDIM with eta = 1 on the same noise: the two stochastic samplers, whose images are
+not paired with the reference's seed by seed), and every set is compared with the DDIM-200 set on the features of the
 synthetic CLIP ViT-B/32 image tower.  At the default 2048 rows of 512 features a covariance has four rows per dimension and the Frechet
 distance is biased; KID (mean +- std over `--kid_subsets` subsets of `--kid_subset_size` rows) is not.  Precision and recall OR over the
 reference balls and saturate; density counts the balls and coverage uses the reference set's balls alone (k = `--dc_k`).
@@ -66,10 +68,14 @@ def main():
             z, _, _ = ctx.plms_sample(S, x_T, cond, uncond, acp, scale=2.0)
         elif name == "dpmpp":
             z, _, _ = ctx.dpmpp_sample(ctx.dpmpp_timesteps(S, acp), x_T, cond, uncond, acp, scale=2.0)
+        elif name == "dpmpp_sde":
+            z, _, _ = ctx.dpmpp_sde_sample(ctx.dpmpp_timesteps(S, acp), x_T, cond, uncond, acp, scale=2.0, seed=a.noise_seed, row0=row0)
+        elif name == "ddimeta":
+            z, _, _ = ctx.ddim_sample(S, x_T, cond, uncond, acp, eta=1.0, scale=2.0, seed=a.noise_seed, row0=row0)
         elif name == "unipc":
             z, _, _ = ctx.unipc_sample(ctx.dpmpp_timesteps(S, acp), x_T, cond, uncond, acp, scale=2.0)
         else:
-            raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | unipc)")
+            raise SystemExit(f"unknown sampler {name!r} (ddim | ddimeta | plms | dpmpp | dpmpp_sde | unipc)")
         return ctx.vq_decode(z).clamp_(-1.0, 1.0)
 
     def features(run):
