@@ -482,6 +482,18 @@ def _noise_seed(what, seed, row0, B):
     return int(seed) & (2 ** 64 - 1), row0
 
 
+def _noise_source(ctx, what, x_T, cond, noise, seed, row0, shape=None):
+    """Where a sampling call's step noise comes from -> (noise, x_shape, seed, row0).  Without a seed: the caller's stack on ctx's device
+    (or None), x_shape None.  With one: no stack may be given (refused before ctx is touched); x_shape is the call's latent shape (x_T's,
+    or cond's rows at `shape` -- what sizes a call without x_T) and (seed, row0) are validated for its rows."""
+    if seed is None:
+        return (None if noise is None else ctx._dev(noise, torch.float32)), None, None, row0
+    if noise is not None:
+        raise RdmError(f"{what}: give a seed or a noise stack, not both")
+    x_shape = Context._seeded_shape(what, x_T, cond, shape)
+    return (None, x_shape) + _noise_seed(what, seed, row0, x_shape[0])
+
+
 def _unipc_variant(what, variant):
     if variant not in UNIPC_VARIANTS:
         raise RdmError(f"{what}: variant must be one of {sorted(UNIPC_VARIANTS)}, got {variant!r}")
@@ -893,19 +905,13 @@ class Context:
         """rdm_ddim_sample; with `seed` rdm_ddim_sample_seeded: step i's noise is the library's own (seed, stream 1, step i, row0 + b),
         generated in the step kernel (no stack; `noise` must then be None), and x_T may be None -- the start is then drawn from stream 0
         at the latent `shape` (C, H, W), for cond.shape[0] rows."""
-        if seed is None:
-            if x_T is None:
-                raise RdmError("ddim_sample: x_T is required without a seed")
-            noise = None if noise is None else self._dev(noise, torch.float32)         # (its shape matters only when it is used)
-            return self._sampler_call("ddim_sample", lambda h, a, x, c, u, *out: lib.rdm_ddim_sample(h, a, x, c, u, _ptr(noise), *out), DdimArgs,
-                                      x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
-                                      noise=noise if eta != 0.0 else None, eta=eta, temperature=temperature)
-        if noise is not None:
-            raise RdmError("ddim_sample: give a seed or a noise stack, not both")
-        x_shape = self._seeded_shape("ddim_sample", x_T, cond, shape)
-        seed, row0 = _noise_seed("ddim_sample", seed, row0, x_shape[0])
-        return self._sampler_call("ddim_sample", lambda h, a, x, c, u, *out: lib.rdm_ddim_sample_seeded(h, a, seed, row0, x, c, u, *out),
-                                  DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+        if seed is None and x_T is None:
+            raise RdmError("ddim_sample: x_T is required without a seed")
+        noise, x_shape, seed, row0 = _noise_source(self, "ddim_sample", x_T, cond, noise, seed, row0, shape)
+        fn = ((lambda h, a, x, c, u, *out: lib.rdm_ddim_sample(h, a, x, c, u, _ptr(noise), *out)) if seed is None else
+              (lambda h, a, x, c, u, *out: lib.rdm_ddim_sample_seeded(h, a, seed, row0, x, c, u, *out)))
+        return self._sampler_call("ddim_sample", fn, DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
+                                  noise=noise if eta != 0.0 else None,         # (its shape matters only when it is used)
                                   x_shape=x_shape, eta=eta, temperature=temperature)
 
     def ddim_decode(self, S, t_start, x_latent, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
@@ -917,17 +923,11 @@ class Context:
         if x_latent is None:
             raise RdmError("ddim_decode: x_latent is required")
         t_start = int(t_start)
-        if seed is None:
-            noise = None if noise is None else self._dev(noise, torch.float32)
-            return self._sampler_call("ddim_decode", lambda h, a, x, c, u, *out: lib.rdm_ddim_decode(h, a, t_start, x, c, u, _ptr(noise), *out),
-                                      DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
-                                      noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
-        if noise is not None:
-            raise RdmError("ddim_decode: give a seed or a noise stack, not both")
-        seed, row0 = _noise_seed("ddim_decode", seed, row0, x_latent.shape[0])
-        return self._sampler_call("ddim_decode", lambda h, a, x, c, u, *out: lib.rdm_ddim_decode_seeded(h, a, t_start, seed, row0, x, c, u, *out),
-                                  DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
-                                  run_steps=t_start, eta=eta, temperature=temperature)
+        noise, _, seed, row0 = _noise_source(self, "ddim_decode", x_latent, cond, noise, seed, row0)
+        fn = ((lambda h, a, x, c, u, *out: lib.rdm_ddim_decode(h, a, t_start, x, c, u, _ptr(noise), *out)) if seed is None else
+              (lambda h, a, x, c, u, *out: lib.rdm_ddim_decode_seeded(h, a, t_start, seed, row0, x, c, u, *out)))
+        return self._sampler_call("ddim_decode", fn, DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates,
+                                  S=S, noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
 
     def ddim_encode(self, S, t_enc, x0, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False, eta=0.0):
         """rdm_ddim_encode: deterministic DDIM inversion of x0, t_enc steps up the S-step schedule with the UNet at each step's target
@@ -949,9 +949,7 @@ class Context:
         """The DDIM inversion step kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
         [cond | uncond]): pred_x0 = (x - sqrt_one_minus_a_cur e) / sqrt_a_cur, x_out = sqrt_a_next pred_x0 + sqrt_one_minus_a_next e.
         x_out may be x; x_dup / pred_x0 may be None.  Writes into the given outputs."""
-        n = x.numel()
-        if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in (x_out, x_dup, pred_x0)):
-            raise RdmError("op_ddim_inverse_step: operand sizes do not match x")
+        n = self._step_sizes("op_ddim_inverse_step", x, eps, cfg, (x_out, x_dup, pred_x0))
         self._check(lib.rdm_op_ddim_inverse_step(self._h, _ptr(x), _ptr(eps), n, int(bool(cfg)), float(scale), float(sqrt_a_cur),
                                                  float(sqrt_one_minus_a_cur), float(sqrt_a_next), float(sqrt_one_minus_a_next), _ptr(x_out),
                                                  _ptr(x_dup), _ptr(pred_x0)))
@@ -1011,12 +1009,12 @@ class Context:
                                   want_intermediates, S=S, eta=0.0, temperature=1.0)
 
     @staticmethod
-    def _step_sizes(what, x, eps, cfg, others):
+    def _step_sizes(what, x, eps, cfg, others, name="x"):
         """What the step-kernel bindings check before a pointer crosses the ABI: eps holds x.numel() elements (twice that under cfg) and
-        every other operand given x.numel()."""
+        every other operand given x.numel().  name: what the binding calls x."""
         n = x.numel()
         if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in others):
-            raise RdmError(f"{what}: operand sizes do not match x")
+            raise RdmError(f"{what}: operand sizes do not match {name}")
         return n
 
     @staticmethod
@@ -1091,9 +1089,7 @@ class Context:
                       pred_x0=None):
         """The DPM-Solver++ update kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
         [cond | uncond]); m_prev / x_dup / m_store / pred_x0 may be None, m_store may be m_prev.  Writes into the given outputs."""
-        n = x.numel()
-        if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in (m_prev, x_out, x_dup, m_store, pred_x0)):
-            raise RdmError("op_dpmpp_step: operand sizes do not match x")
+        n = self._step_sizes("op_dpmpp_step", x, eps, cfg, (m_prev, x_out, x_dup, m_store, pred_x0))
         self._check(lib.rdm_op_dpmpp_step(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), n, int(bool(cfg)), float(scale), float(sqrt_a_s),
                                           float(sqrt_one_minus_a_s), float(c_x), float(c_0), float(c_1), _ptr(x_out), _ptr(x_dup),
                                           _ptr(m_store), _ptr(pred_x0)))
@@ -1106,19 +1102,13 @@ class Context:
         (C, H, W), for cond.shape[0] rows.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
         if lower_order_final is None:
             lower_order_final = _nodes_array(nodes).shape[0] - 1 < 15
-        fields = dict(nodes=nodes, order=int(order), lower_order_final=int(bool(lower_order_final)))
-        if seed is None:
-            if x_T is None or noise is None:
-                raise RdmError("dpmpp_sde_sample: x_T and a noise stack are required without a seed")
-            noise = self._dev(noise, torch.float32)
-            return self._sampler_call("dpmpp_sde_sample", lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample(h, a, x, c, u, _ptr(noise), *out),
-                                      DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, noise=noise, **fields)
-        if noise is not None:
-            raise RdmError("dpmpp_sde_sample: give a seed or a noise stack, not both")
-        x_shape = self._seeded_shape("dpmpp_sde_sample", x_T, cond, shape)
-        seed, row0 = _noise_seed("dpmpp_sde_sample", seed, row0, x_shape[0])
-        return self._sampler_call("dpmpp_sde_sample", lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample_seeded(h, a, seed, row0, x, c, u, *out),
-                                  DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, x_shape=x_shape, **fields)
+        if seed is None and (x_T is None or noise is None):
+            raise RdmError("dpmpp_sde_sample: x_T and a noise stack are required without a seed")
+        noise, x_shape, seed, row0 = _noise_source(self, "dpmpp_sde_sample", x_T, cond, noise, seed, row0, shape)
+        fn = ((lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample(h, a, x, c, u, _ptr(noise), *out)) if seed is None else
+              (lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample_seeded(h, a, seed, row0, x, c, u, *out)))
+        return self._sampler_call("dpmpp_sde_sample", fn, DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates,
+                                  noise=noise, x_shape=x_shape, nodes=nodes, order=int(order), lower_order_final=int(bool(lower_order_final)))
 
     def op_dpmpp_sde_step(self, x, eps, m_prev, noise, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup=None,
                           m_store=None, pred_x0=None, seed=None, row0=0, per_row=None, step=0):
@@ -1159,13 +1149,10 @@ class Context:
         """The UniPC predict-and-correct kernel alone on caller-owned fp32 device tensors of u.numel() elements (eps: twice that under
         cfg, [cond | uncond]); `coefficients` the 13 float64 values of unipc_coefficients.  xc_prev / h1 / h2 / h3 as far as the orders
         reach; u_next may be u, xc_out may be xc_prev, m_store may be a history slot.  Writes into the given outputs."""
-        n = u.numel()
         co = np.ascontiguousarray(np.asarray(coefficients, dtype=np.float64).reshape(-1))
         if co.shape[0] != len(UNIPC_COEFFICIENTS):
             raise RdmError(f"op_unipc_step: coefficients must hold {len(UNIPC_COEFFICIENTS)} values")
-        if eps.numel() != (2 * n if cfg else n) or any(t is not None and t.numel() != n for t in (xc_prev, h1, h2, h3, xc_out, u_next, x_dup,
-                                                                                                 m_store, pred_x0)):
-            raise RdmError("op_unipc_step: operand sizes do not match u")
+        n = self._step_sizes("op_unipc_step", u, eps, cfg, (xc_prev, h1, h2, h3, xc_out, u_next, x_dup, m_store, pred_x0), name="u")
         self._check(lib.rdm_op_unipc_step(self._h, _ptr(u), _ptr(eps), _ptr(xc_prev), _ptr(h1), _ptr(h2), _ptr(h3), n, int(bool(cfg)),
                                           float(scale), co.ctypes.data_as(C.POINTER(C.c_double)), _ptr(xc_out), _ptr(u_next), _ptr(x_dup),
                                           _ptr(m_store), _ptr(pred_x0)))
@@ -1175,18 +1162,13 @@ class Context:
         noise, generated in the step kernel, and x_T may be None (drawn from stream 0 at the latent `shape` (C, H, W))."""
         if sched is None:
             raise RdmError("ddpm_sample: the schedule arrays are required")
-        if seed is not None and noise is not None:
-            raise RdmError("ddpm_sample: give a seed or a noise stack, not both")
         if seed is None and (noise is None or x_T is None):
             raise RdmError("ddpm_sample: x_T and a noise stack are required without a seed")
+        noise, x_shape, seed, row0 = _noise_source(self, "ddpm_sample", x_T, cond, noise, seed, row0, shape)
         cond = self._dev(cond, torch.float32)
         x_arg = x_T = None if x_T is None else self._dev(x_T, torch.float32)
-        noise = None if noise is None else self._dev(noise, torch.float32)
-        if seed is not None:
-            x_shape = self._seeded_shape("ddpm_sample", x_T, cond, shape)
-            seed, row0 = _noise_seed("ddpm_sample", seed, row0, x_shape[0])
-            if x_T is None:
-                x_T = torch.empty(x_shape, device="meta", dtype=torch.float32)     # shapes only
+        if x_T is None:
+            x_T = torch.empty(x_shape, device="meta", dtype=torch.float32)     # shapes only
         arrs = {k: np.ascontiguousarray(np.asarray(v, dtype=np.float32)) for k, v in sched.items()}
         fp = lambda k: arrs[k].ctypes.data_as(C.POINTER(C.c_float))
         self._check_sampler_shapes("ddpm_sample", x_T, cond, None, noise, int(timesteps))

@@ -111,26 +111,16 @@ struct PlmsStepParams {
     int cfg, mode, order;
 };
 
-// One DPM-Solver++ step (Lu et al. 2022, multistep data prediction; ldm models/diffusion/dpm_solver): e = CFG(eps),
-// m0 = (x - sqrt_one_minus_a_s e) / sqrt_a_s -> m_store, pred_x0; x_out = c_x x + c_0 m0 + c_1 m_prev.  The host flattens the solver's
-// D = (1 + 1/(2r)) m0 - (1/(2r)) m_prev into c_0, c_1 (first-order step: m_prev null, c_1 unused).  m_store may be the very slot m_prev
-// points to: each thread reads its elements of m_prev before it writes m_store, so ONE history slot serves the whole loop.
+// One DPM-Solver++ step, ODE or SDE (Lu et al. 2022, multistep data prediction, "dpmsolver++" / "sde-dpmsolver++"; ldm
+// models/diffusion/dpm_solver): e = CFG(eps), m0 = (x - sqrt_one_minus_a_s e) / sqrt_a_s -> m_store, pred_x0;
+// x_out = ((c_x x + c_0 m0) + c_1 m_prev) + c_n z.  The host flattens the solver's D = (1 + 1/(2r)) m0 - (1/(2r)) m_prev into c_0, c_1
+// (first-order step: m_prev null, c_1 unused).  noise null: the ODE step, no fourth term (c_n unused); else z = noise[i] (the stack form),
+// or the normal of StepRngParams drawn in registers (the seeded launch: noise unused).  m_store may be the very slot m_prev points to:
+// each thread reads its elements of m_prev before it writes m_store, so ONE history slot serves the whole loop.
 struct DpmppStepParams {
     const float* x; const float* eps;                        // eps: [n] rows (cfg == 0) or [2n] (cond | uncond)
     const float* m_prev;                                     // the previous step's m0, or null
-    float* x_out; float* x_dup; float* m_store; float* pred_x0;     // x_dup, m_store, pred_x0 may be null
-    long long n;                                             // B*C*H*W
-    float sqrt_a_s, sqrt_one_minus_a_s, scale, c_x, c_0, c_1;
-    int cfg;
-};
-
-// One SDE-DPM-Solver++ step (Lu et al. 2022, the "sde-dpmsolver++" multistep update; rdm_dpmpp_sde_sample): DpmppStepParams' operands and
-// m0, plus the step's noise -- x_out = ((c_x x + c_0 m0) + c_1 m_prev) + c_n z, with z = noise[i] (the stack form) or the normal of
-// StepRngParams drawn in registers (the seeded form: noise unused).  First-order step: m_prev null, c_1 unused.  m_store may be m_prev.
-struct DpmppSdeStepParams {
-    const float* x; const float* eps;                        // eps: [n] rows (cfg == 0) or [2n] (cond | uncond)
-    const float* m_prev;                                     // the previous step's m0, or null
-    const float* noise;                                      // z_j, n elements (stack form)
+    const float* noise;                                      // z_j, n elements (SDE stack form), or null
     float* x_out; float* x_dup; float* m_store; float* pred_x0;     // x_dup, m_store, pred_x0 may be null
     long long n;                                             // B*C*H*W
     float sqrt_a_s, sqrt_one_minus_a_s, scale, c_x, c_0, c_1, c_n;
@@ -343,9 +333,8 @@ hipError_t launch_ddim_step_seeded(const DdimStepParams& p, const StepRngParams&
 hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams& g, hipStream_t st);
 hipError_t launch_rng_fill(const RngFillParams& p, bool normal, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
-hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);
-hipError_t launch_dpmpp_sde_step(const DpmppSdeStepParams& p, hipStream_t st);
-hipError_t launch_dpmpp_sde_step_seeded(const DpmppSdeStepParams& p, const StepRngParams& g, hipStream_t st);   // as launch_ddim_step_seeded
+hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);      // p.noise null: the ODE step; else the SDE step on the stack's z
+hipError_t launch_dpmpp_sde_step_seeded(const DpmppStepParams& p, const StepRngParams& g, hipStream_t st);   // as launch_ddim_step_seeded
 hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st);
 hipError_t launch_ddim_inverse_step(const DdimInverseStepParams& p, hipStream_t st);
 hipError_t launch_q_sample_seeded(const QSampleSeededParams& p, hipStream_t st);     // hipErrorInvalidValue: per_row % 4 or an operand not 16-byte aligned

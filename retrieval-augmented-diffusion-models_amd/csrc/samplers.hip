@@ -1,5 +1,6 @@
-// The sampling loops of librdm_hip (DDIM, PLMS, DPM-Solver++(2M) and its SDE form, UniPC, DDPM): their schedules, SamplerRun (one sampling
-// call's scratch, tables and UNet forward), the rdm_*_sample entries, the device-noise entries, DDIM image-to-image (rdm_ddim_decode: the
+// The sampling loops of librdm_hip (DDIM, PLMS, DPM-Solver++(2M) and its SDE form -- one loop, dpmpp_sample_impl --, UniPC, DDPM): their
+// schedules, SamplerRun (one sampling call's scratch, tables and UNet forward), NoiseSource (where a loop's step noise comes from: a stack,
+// a seed, or nowhere), the rdm_*_sample entries, the device-noise entries, DDIM image-to-image (rdm_ddim_decode: the
 // DDIM loop begun part-way down the schedule; rdm_ddim_encode: the loop that runs UP it) and the step-kernel op entries.
 // Calls into unet_exec.hip through the three functions host.h declares (unet_prepare_kv, unet_emb_table, unet_forward_impl) and
 // into the launch_* of kernels.h.  The loops are the reference's
@@ -56,6 +57,29 @@ static int check_noise_rows(rdm_ctx* c, const char* who, int64_t row0, int64_t B
     if (row0 < 0 || row0 > 0xFFFFFFFFll || B > 0xFFFFFFFFll - row0)
         return c->fail(-1, "%s: row0 + B must fit 32 bits (row0=%lld, B=%lld)", who, (long long)row0, (long long)B);
     if (per_row > (1ll << 34)) return c->fail(-1, "%s: per_row must be at most 2^34, got %lld", who, (long long)per_row);
+    return 0;
+}
+// Where a loop's step noise comes from: a caller's stack, the generator under (seed, row0), or nowhere (a deterministic loop) -- never two
+// of them: the entries build it with one of the two functions.
+struct NoiseSource {
+    const float* stack = nullptr; bool seeded = false; NoiseSeed seed{};
+    static NoiseSource from_stack(const float* noise) { NoiseSource s; s.stack = noise; return s; }
+    static NoiseSource from_seed(uint64_t seed, int64_t row0) { NoiseSource s; s.seeded = true; s.seed = {seed, row0}; return s; }
+};
+// What a seeded loop asks of the call's shape (who: the sampler's name): check_noise_rows, and whole Philox blocks per row
+template <class Args>
+static int check_seeded(rdm_ctx* c, const char* who, const NoiseSource& ns, const Args* a) {
+    if (!ns.seeded) return 0;
+    const std::string w = std::string(who) + " (seeded)";
+    const int64_t per_row = (int64_t)a->channels * a->height * a->width;
+    RDM_TRY(check_noise_rows(c, w.c_str(), ns.seed.row0, a->batch, per_row));
+    if (per_row % 4) return c->fail(-1, "%s: channels * height * width must be a multiple of 4", w.c_str());
+    return 0;
+}
+// ... and of a seeded step launch: after check_seeded the one operand that can still be misaligned is the caller's pred_x0_inter
+static int seeded_launched(rdm_ctx* c, const char* who, hipError_t e) {
+    if (e == hipErrorInvalidValue) return c->fail(-1, "%s (seeded): pred_x0_inter must be 16-byte aligned", who);
+    RDM_CHECK_HIP(c, e);
     return 0;
 }
 
@@ -142,18 +166,16 @@ struct HistoryRing {
     }
 };
 
-// The DDIM loop of rdm_ddim_sample (ns null: the step noise is read from the stack `noise`) and rdm_ddim_sample_seeded (ns: it is generated
-// in the step kernel, and a null x_T is drawn), and of the two rdm_ddim_decode entries: n_run steps down from level index n_run - 1
-// (n_run < 0: the whole schedule).  The run is the loop over the schedule cut to its first n_run entries.
+// The DDIM loop of rdm_ddim_sample (the step noise is read from ns.stack) and rdm_ddim_sample_seeded (it is generated in the step kernel,
+// and a null x_T is drawn), and of the two rdm_ddim_decode entries: n_run steps down from level index n_run - 1 (n_run < 0: the whole
+// schedule).  The run is the loop over the schedule cut to its first n_run entries.
 static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, int n_run, const float* x_T, const float* cond, const float* uncond,
-                            const float* noise, const NoiseSeed* ns, float* z_out, float* x_inter, float* pred_x0_inter) {
+                            const NoiseSource& ns, float* z_out, float* x_inter, float* pred_x0_inter) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     bool cfg;
     RDM_TRY(sampler_guidance(c, "ddim", a->unconditional_guidance_scale, uncond, &cfg));
-    if (ns) {
-        RDM_TRY(check_noise_rows(c, "ddim (seeded)", ns->row0, a->batch, (int64_t)a->channels * a->height * a->width));
-        if (((int64_t)a->channels * a->height * a->width) % 4) return c->fail(-1, "ddim (seeded): channels * height * width must be a multiple of 4");
-    } else if (a->eta != 0.f && !noise) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
+    RDM_TRY(check_seeded(c, "ddim", ns, a));
+    if (!ns.seeded && a->eta != 0.f && !ns.stack) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
     if (n_run >= 0) {
@@ -169,20 +191,17 @@ static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, int n_run, const
     }
     SamplerRun run;
     RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 0));
-    if (!x_T) RDM_TRY(run.draw_start(*ns));
+    if (!x_T) RDM_TRY(run.draw_start(ns.seed));
     for (int i = 0; i < total; i++) {
         const int index = total - i - 1;         // of the ascending schedule
         RDM_TRY(run.forward(index));
         DdimStepParams p{};
-        p.x = run.x; p.eps = run.eps; p.noise = (noise && a->eta != 0.f) ? noise + (size_t)i * run.n1 : nullptr;
+        p.x = run.x; p.eps = run.eps; p.noise = (ns.stack && a->eta != 0.f) ? ns.stack + (size_t)i * run.n1 : nullptr;
         p.x_prev = run.x; p.x_dup = run.x_dup; p.pred_x0 = run.pred_x0_slot(i);
         p.n_per_batch = run.n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sigma_t = sg[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.temperature = a->temperature; p.cfg = cfg ? 1 : 0;
-        if (ns && a->eta != 0.f) {          // the noise of loop step i, in registers
-            const hipError_t e = launch_ddim_step_seeded(p, run.step_rng(*ns, i), c->stream);
-            if (e == hipErrorInvalidValue) return c->fail(-1, "ddim (seeded): pred_x0_inter must be 16-byte aligned");
-            RDM_CHECK_HIP(c, e);
-        } else RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
+        if (ns.seeded && a->eta != 0.f) RDM_TRY(seeded_launched(c, "ddim", launch_ddim_step_seeded(p, run.step_rng(ns.seed, i), c->stream)));   // the noise of loop step i, in registers
+        else RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
         RDM_TRY(run.log_x(i));
     }
     return run.finish(z_out);
@@ -191,14 +210,13 @@ int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const 
                     const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
+    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, NoiseSource::from_stack(noise), z_out, x_inter, pred_x0_inter);
 }
 int rdm_ddim_sample_seeded(rdm_ctx* c, const rdm_ddim_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
                            const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    const NoiseSeed ns{seed, row0};
-    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
+    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, NoiseSource::from_seed(seed, row0), z_out, x_inter, pred_x0_inter);
 }
 
 // ldm DDIMSampler.decode: the DDIM loop from a latent at level index t_start - 1
@@ -207,15 +225,14 @@ int rdm_ddim_decode(rdm_ctx* c, const rdm_ddim_args* a, int t_start, const float
     RDM_ENTER(c);
     if (!c || !a || !x_latent || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
     if (t_start < 1) return c->fail(-1, "ddim decode: t_start must be at least 1, got %d", t_start);
-    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_stack(noise), z_out, x_inter, pred_x0_inter);
 }
 int rdm_ddim_decode_seeded(rdm_ctx* c, const rdm_ddim_args* a, int t_start, uint64_t seed, int64_t row0, const float* x_latent, const float* cond,
                            const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_latent || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
     if (t_start < 1) return c->fail(-1, "ddim decode: t_start must be at least 1, got %d", t_start);
-    const NoiseSeed ns{seed, row0};
-    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_seed(seed, row0), z_out, x_inter, pred_x0_inter);
 }
 
 // Deterministic DDIM inversion (rdm_ddim_encode's header comment): t_enc steps UP the schedule, step i from level a_prev[i] to a_t[i] with
@@ -351,107 +368,81 @@ int rdm_dpmpp_timesteps(const float* alphas_cumprod, int T, int S, int skip_type
     return n;
 }
 
-// The loop of rdm_dpmpp_sample's header comment: one forward and one dpmpp_step_kernel launch per step, the solver's coefficients computed
-// here in float64.  The history is ONE buffer: the kernel reads m_{j-1} from it and writes m_j to it in the same pass.
-int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond,
-                     float* z_out, float* x_inter, float* pred_x0_inter) {
-    RDM_ENTER(c);
-    if (!c || !a || !x_T || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
+// The float64 coefficients of one DPM-Solver++ step from node s to node t (h = lambda_t - lambda_s, h_prev the step before's):
+// x <- c_x x + g D (+ c_n z), D = m0 or, at second order, (1 + 1/(2r)) m0 - (1/(2r)) m_prev with r = h_prev / h.
+struct DpmppCoefficients { double c_x, c_0, c_1, c_n; };
+static DpmppCoefficients dpmpp_coefficients(const SolverNode& s, const SolverNode& t, double h, double h_prev, bool second, bool sde) {
+    DpmppCoefficients k{};
+    double g;
+    if (sde) {
+        const double q = -std::expm1(-2.0 * h);       // q = 1 - exp(-2h)
+        g = t.alpha * q; k.c_x = t.sigma / s.sigma * std::exp(-h); k.c_n = t.sigma * std::sqrt(q);
+    } else {
+        g = -t.alpha * std::expm1(-h); k.c_x = t.sigma / s.sigma;
+    }
+    if (second) {
+        const double r = h_prev / h;
+        k.c_0 = g * (1.0 + 1.0 / (2.0 * r)); k.c_1 = -g / (2.0 * r);
+    } else {
+        k.c_0 = g;
+    }
+    return k;
+}
+
+// The loop of rdm_dpmpp_sample (sde false: the ODE step, no noise) and of the two rdm_dpmpp_sde_sample entries (z_j is row j of ns.stack, or
+// drawn in the step kernel at step counter j, and a null x_T is drawn): one forward and one step-kernel launch per step.  The history is
+// ONE buffer: the kernel reads m_{j-1} from it and writes m_j to it in the same pass.  who: the solver's name in the messages.
+static int dpmpp_sample_impl(rdm_ctx* c, const rdm_dpmpp_args* a, bool sde, const char* who, const NoiseSource& ns, const float* x_T,
+                             const float* cond, const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
-    if (a->order != 1 && a->order != 2) return c->fail(-1, "dpm-solver++ order must be 1 or 2, got %d", a->order);
+    if (a->order != 1 && a->order != 2) return c->fail(-1, "%s order must be 1 or 2, got %d", who, a->order);
     bool cfg;
-    RDM_TRY(sampler_guidance(c, "dpm-solver++", a->unconditional_guidance_scale, uncond, &cfg));
-    RDM_TRY(sampler_nodes(c, "dpm-solver++", a->alphas_cumprod, a->T, a->nodes, a->n_nodes));
+    RDM_TRY(sampler_guidance(c, who, a->unconditional_guidance_scale, uncond, &cfg));
+    RDM_TRY(sampler_nodes(c, who, a->alphas_cumprod, a->T, a->nodes, a->n_nodes));
+    RDM_TRY(check_seeded(c, who, ns, a));
     const int n_steps = a->n_nodes - 1;
     const std::vector<int> ts(a->nodes, a->nodes + n_steps);
     SamplerRun run;
     RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 1));
+    if (!x_T) RDM_TRY(run.draw_start(ns.seed));
     float* m_slot = run.extra[0];
     double h_prev = 0.0;
     for (int j = 0; j < n_steps; j++) {
         const SolverNode s = solver_node(a->alphas_cumprod, a->nodes[j]), t = solver_node(a->alphas_cumprod, a->nodes[j + 1]);
-        const double h = t.lambda - s.lambda, g = -t.alpha * std::expm1(-h);       // x <- (sigma_t / sigma_s) x + g D
+        const double h = t.lambda - s.lambda;
         const bool second = a->order == 2 && j >= 1 && !(a->lower_order_final && j == n_steps - 1);
+        const DpmppCoefficients k = dpmpp_coefficients(s, t, h, h_prev, second, sde);
         RDM_TRY(run.forward(j));
         DpmppStepParams p{};
         p.x = run.x; p.eps = run.eps; p.n = run.n1; p.cfg = cfg ? 1 : 0; p.scale = a->unconditional_guidance_scale;
-        p.sqrt_a_s = (float)s.alpha; p.sqrt_one_minus_a_s = (float)s.sigma; p.c_x = (float)(t.sigma / s.sigma);
-        if (second) {
-            const double r = h_prev / h;
-            p.m_prev = m_slot; p.c_0 = (float)(g * (1.0 + 1.0 / (2.0 * r))); p.c_1 = (float)(-g / (2.0 * r));
-        } else {
-            p.c_0 = (float)g;
-        }
+        p.sqrt_a_s = (float)s.alpha; p.sqrt_one_minus_a_s = (float)s.sigma;
+        p.c_x = (float)k.c_x; p.c_0 = (float)k.c_0; p.c_1 = (float)k.c_1; p.c_n = (float)k.c_n;
+        p.m_prev = second ? m_slot : nullptr; p.noise = ns.stack ? ns.stack + (size_t)j * run.n1 : nullptr;
         p.x_out = run.x; p.x_dup = run.x_dup; p.m_store = m_slot; p.pred_x0 = run.pred_x0_slot(j);
-        RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
+        if (ns.seeded) RDM_TRY(seeded_launched(c, who, launch_dpmpp_sde_step_seeded(p, run.step_rng(ns.seed, j), c->stream)));   // the noise of loop step j, in registers
+        else RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
         h_prev = h;
         RDM_TRY(run.log_x(j));
     }
     return run.finish(z_out);
 }
-
-// The loop of rdm_dpmpp_sde_sample (ns null: z_j is row j of the stack `noise`) and rdm_dpmpp_sde_sample_seeded (ns: z_j is drawn in the step
-// kernel at step counter j, and a null x_T is drawn): rdm_dpmpp_sample's loop -- one forward and one kernel launch per step, ONE history
-// slot -- with the SDE update's four coefficients computed here in float64.
-static int dpmpp_sde_sample_impl(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond, const float* noise,
-                                 const NoiseSeed* ns, float* z_out, float* x_inter, float* pred_x0_inter) {
-    if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
-    if (a->order != 1 && a->order != 2) return c->fail(-1, "sde-dpm-solver++ order must be 1 or 2, got %d", a->order);
-    bool cfg;
-    RDM_TRY(sampler_guidance(c, "sde-dpm-solver++", a->unconditional_guidance_scale, uncond, &cfg));
-    RDM_TRY(sampler_nodes(c, "sde-dpm-solver++", a->alphas_cumprod, a->T, a->nodes, a->n_nodes));
-    if (ns) {
-        RDM_TRY(check_noise_rows(c, "sde-dpm-solver++ (seeded)", ns->row0, a->batch, (int64_t)a->channels * a->height * a->width));
-        if (((int64_t)a->channels * a->height * a->width) % 4) return c->fail(-1, "sde-dpm-solver++ (seeded): channels * height * width must be a multiple of 4");
-    }
-    const int n_steps = a->n_nodes - 1;
-    const std::vector<int> ts(a->nodes, a->nodes + n_steps);
-    SamplerRun run;
-    RDM_TRY(run.begin(c, a, ts, x_T, cond, cfg ? uncond : nullptr, a->log_every_t, x_inter, pred_x0_inter, 1));
-    if (!x_T) RDM_TRY(run.draw_start(*ns));
-    float* m_slot = run.extra[0];
-    double h_prev = 0.0;
-    for (int j = 0; j < n_steps; j++) {
-        const SolverNode s = solver_node(a->alphas_cumprod, a->nodes[j]), t = solver_node(a->alphas_cumprod, a->nodes[j + 1]);
-        const double h = t.lambda - s.lambda, q = -std::expm1(-2.0 * h), g = t.alpha * q;       // q = 1 - exp(-2h)
-        const bool second = a->order == 2 && j >= 1 && !(a->lower_order_final && j == n_steps - 1);
-        RDM_TRY(run.forward(j));
-        DpmppSdeStepParams p{};
-        p.x = run.x; p.eps = run.eps; p.n = run.n1; p.cfg = cfg ? 1 : 0; p.scale = a->unconditional_guidance_scale;
-        p.sqrt_a_s = (float)s.alpha; p.sqrt_one_minus_a_s = (float)s.sigma;
-        p.c_x = (float)(t.sigma / s.sigma * std::exp(-h)); p.c_n = (float)(t.sigma * std::sqrt(q));
-        if (second) {
-            const double r = h_prev / h;
-            p.m_prev = m_slot; p.c_0 = (float)(g * (1.0 + 1.0 / (2.0 * r))); p.c_1 = (float)(-g / (2.0 * r));
-        } else {
-            p.c_0 = (float)g;
-        }
-        p.x_out = run.x; p.x_dup = run.x_dup; p.m_store = m_slot; p.pred_x0 = run.pred_x0_slot(j);
-        if (ns) {          // the noise of loop step j, in registers
-            const hipError_t e = launch_dpmpp_sde_step_seeded(p, run.step_rng(*ns, j), c->stream);
-            if (e == hipErrorInvalidValue) return c->fail(-1, "sde-dpm-solver++ (seeded): pred_x0_inter must be 16-byte aligned");
-            RDM_CHECK_HIP(c, e);
-        } else {
-            p.noise = noise + (size_t)j * run.n1;
-            RDM_CHECK_HIP(c, launch_dpmpp_sde_step(p, c->stream));
-        }
-        h_prev = h;
-        RDM_TRY(run.log_x(j));
-    }
-    return run.finish(z_out);
+int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond,
+                     float* z_out, float* x_inter, float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_T || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
+    return dpmpp_sample_impl(c, a, false, "dpm-solver++", NoiseSource{}, x_T, cond, uncond, z_out, x_inter, pred_x0_inter);
 }
 int rdm_dpmpp_sde_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond, const float* noise,
                          float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !noise || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
-    return dpmpp_sde_sample_impl(c, a, x_T, cond, uncond, noise, nullptr, z_out, x_inter, pred_x0_inter);
+    return dpmpp_sample_impl(c, a, true, "sde-dpm-solver++", NoiseSource::from_stack(noise), x_T, cond, uncond, z_out, x_inter, pred_x0_inter);
 }
 int rdm_dpmpp_sde_sample_seeded(rdm_ctx* c, const rdm_dpmpp_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
                                 const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
     if (!c || !a || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
-    const NoiseSeed ns{seed, row0};
-    return dpmpp_sde_sample_impl(c, a, x_T, cond, uncond, nullptr, &ns, z_out, x_inter, pred_x0_inter);
+    return dpmpp_sample_impl(c, a, true, "sde-dpm-solver++", NoiseSource::from_seed(seed, row0), x_T, cond, uncond, z_out, x_inter, pred_x0_inter);
 }
 
 // UniPC (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models"), data prediction,
@@ -607,30 +598,26 @@ int rdm_unipc_sample(rdm_ctx* c, const rdm_unipc_args* a, const float* x_T, cons
     return run.finish(z_out);
 }
 
-// The ancestral loop of rdm_ddpm_sample (ns null: noise stack) and rdm_ddpm_sample_seeded (ns: generated in the step kernel; a null x_T
-// is drawn).  The final step (i == 0) consumes no noise either way.
-static int ddpm_sample_impl(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const float* noise, const NoiseSeed* ns,
-                            float* z_out) {
+// The ancestral loop of rdm_ddpm_sample (the noise stack ns.stack) and rdm_ddpm_sample_seeded (generated in the step kernel; a null x_T is
+// drawn).  The final step (i == 0) consumes no noise either way.
+static int ddpm_sample_impl(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const NoiseSource& ns, float* z_out) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->timesteps < 1 || a->timesteps > a->T) return c->fail(-1, "bad timesteps");
-    if (ns) {
-        RDM_TRY(check_noise_rows(c, "ddpm (seeded)", ns->row0, a->batch, (int64_t)a->channels * a->height * a->width));
-        if (((int64_t)a->channels * a->height * a->width) % 4) return c->fail(-1, "ddpm (seeded): channels * height * width must be a multiple of 4");
-    }
+    RDM_TRY(check_seeded(c, "ddpm", ns, a));
     const int T = a->timesteps;
     std::vector<int> ts(T);
     for (int i = 0; i < T; i++) ts[i] = i;
     SamplerRun run;
     RDM_TRY(run.begin(c, a, ts, x_T, cond, nullptr, 0, nullptr, nullptr, 0));
-    if (!x_T) RDM_TRY(run.draw_start(*ns));
+    if (!x_T) RDM_TRY(run.draw_start(ns.seed));
     for (int n = 0, i = T - 1; i >= 0; i--, n++) {
         RDM_TRY(run.forward(i));
         DdpmStepParams p{};
-        p.x = run.x; p.eps = run.eps; p.noise = noise ? noise + (size_t)n * run.n1 : nullptr; p.x_prev = run.x; p.n = run.n1;
+        p.x = run.x; p.eps = run.eps; p.noise = ns.stack ? ns.stack + (size_t)n * run.n1 : nullptr; p.x_prev = run.x; p.n = run.n1;
         p.sqrt_recip = a->sqrt_recip_alphas_cumprod[i]; p.sqrt_recipm1 = a->sqrt_recipm1_alphas_cumprod[i];
         p.coef1 = a->posterior_mean_coef1[i]; p.coef2 = a->posterior_mean_coef2[i]; p.log_var = a->posterior_log_variance_clipped[i];
         p.clip = a->clip_denoised; p.nonzero = (i != 0); p.temperature = a->temperature;
-        if (ns && p.nonzero) RDM_CHECK_HIP(c, launch_ddpm_step_seeded(p, run.step_rng(*ns, n), c->stream));      // the noise of loop step n, in registers
+        if (ns.seeded && p.nonzero) RDM_CHECK_HIP(c, launch_ddpm_step_seeded(p, run.step_rng(ns.seed, n), c->stream));      // the noise of loop step n, in registers
         else RDM_CHECK_HIP(c, launch_ddpm_step(p, c->stream));
     }
     return run.finish(z_out);
@@ -639,13 +626,12 @@ int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const 
                     float* z_out) {
     RDM_ENTER(c);
     if (!c || !a || !x_T || !cond || !noise || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    return ddpm_sample_impl(c, a, x_T, cond, noise, nullptr, z_out);
+    return ddpm_sample_impl(c, a, x_T, cond, NoiseSource::from_stack(noise), z_out);
 }
 int rdm_ddpm_sample_seeded(rdm_ctx* c, const rdm_ddpm_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond, float* z_out) {
     RDM_ENTER(c);
     if (!c || !a || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    const NoiseSeed ns{seed, row0};
-    return ddpm_sample_impl(c, a, x_T, cond, nullptr, &ns, z_out);
+    return ddpm_sample_impl(c, a, x_T, cond, NoiseSource::from_seed(seed, row0), z_out);
 }
 
 // ---- device noise: the generator alone (philox.h)
@@ -802,33 +788,30 @@ int rdm_op_ddpm_step_seeded(rdm_ctx* c, const float* x, const float* eps, long l
 }
 
 // ---- the DPM-Solver++ and UniPC step kernels alone
+static void dpmpp_step_fill(DpmppStepParams& p, const float* x, const float* eps, const float* m_prev, const float* noise, long long n, int cfg,
+                            float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out,
+                            float* x_dup, float* m_store, float* pred_x0) {
+    p.x = x; p.eps = eps; p.m_prev = m_prev; p.noise = noise; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale; p.sqrt_a_s = sqrt_a_s;
+    p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1; p.c_n = c_n;
+    p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
+}
 int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int cfg, float scale, float sqrt_a_s,
                       float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float* x_out, float* x_dup, float* m_store, float* pred_x0) {
     RDM_ENTER(c);
     if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_step: bad argument");
     DpmppStepParams p{};
-    p.x = x; p.eps = eps; p.m_prev = m_prev; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale; p.sqrt_a_s = sqrt_a_s;
-    p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1;
-    p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
+    dpmpp_step_fill(p, x, eps, m_prev, nullptr, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, 0.f, x_out, x_dup, m_store, pred_x0);
     RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
     return 0;
-}
-static void dpmpp_sde_step_fill(DpmppSdeStepParams& p, const float* x, const float* eps, const float* m_prev, long long n, int cfg, float scale,
-                                float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out, float* x_dup,
-                                float* m_store, float* pred_x0) {
-    p.x = x; p.eps = eps; p.m_prev = m_prev; p.n = n; p.cfg = cfg ? 1 : 0; p.scale = scale; p.sqrt_a_s = sqrt_a_s;
-    p.sqrt_one_minus_a_s = sqrt_one_minus_a_s; p.c_x = c_x; p.c_0 = c_0; p.c_1 = c_1; p.c_n = c_n;
-    p.x_out = x_out; p.x_dup = x_dup; p.m_store = m_store; p.pred_x0 = pred_x0;
 }
 int rdm_op_dpmpp_sde_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, const float* noise, long long n, int cfg, float scale,
                           float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out, float* x_dup,
                           float* m_store, float* pred_x0) {
     RDM_ENTER(c);
     if (!x || !eps || !noise || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_sde_step: bad argument");
-    DpmppSdeStepParams p{};
-    dpmpp_sde_step_fill(p, x, eps, m_prev, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
-    p.noise = noise;
-    RDM_CHECK_HIP(c, launch_dpmpp_sde_step(p, c->stream));
+    DpmppStepParams p{};
+    dpmpp_step_fill(p, x, eps, m_prev, noise, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
+    RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
     return 0;
 }
 int rdm_op_dpmpp_sde_step_seeded(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int64_t per_row, int cfg,
@@ -837,8 +820,8 @@ int rdm_op_dpmpp_sde_step_seeded(rdm_ctx* c, const float* x, const float* eps, c
     RDM_ENTER(c);
     if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_sde_step_seeded: bad argument");
     RDM_TRY(check_noise_rows(c, "rdm_op_dpmpp_sde_step_seeded", row0, per_row >= 1 ? n / per_row : 0, per_row));
-    DpmppSdeStepParams p{};
-    dpmpp_sde_step_fill(p, x, eps, m_prev, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
+    DpmppStepParams p{};
+    dpmpp_step_fill(p, x, eps, m_prev, nullptr, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
     const hipError_t e = launch_dpmpp_sde_step_seeded(p, StepRngParams{seed, per_row, (uint32_t)row0, step}, c->stream);
     if (e == hipErrorInvalidValue)
         return c->fail(-1, "rdm_op_dpmpp_sde_step_seeded: per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned");

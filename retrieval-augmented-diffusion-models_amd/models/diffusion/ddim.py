@@ -80,6 +80,12 @@ class _SamplerBase(object):
             raise NotImplementedError("ddim_use_original_steps: dead in the reference (ddim.py:249 reads a buffer that lives on the sampler, "
                                       "not on the model: AttributeError)")
 
+    @staticmethod
+    def _one_noise_source(noise_seed, noise, noun="noise stack"):
+        """[native] A noise_seed selects the library's generator, an explicit `noise` the caller's values: never both."""
+        if noise_seed is not None and noise is not None:
+            raise ValueError(f"noise_seed and an explicit {noun} select different noise sources: give one of them")
+
     def _timestep_subset(self, timesteps):
         if timesteps is None:
             return self.ddim_timesteps
@@ -179,8 +185,7 @@ class DDIMSampler(_SamplerBase):
                       unconditional_conditioning=None, random_guiding='none', content_cond=None, style_cond=None,
                       intermediates_to_cpu=False, S=None, eta=0., noise_seed=None, noise_row0=0, **kwargs):
         self._refuse_original_steps(ddim_use_original_steps)
-        if noise_seed is not None and kwargs.get("noise") is not None:
-            raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
+        self._one_noise_source(noise_seed, kwargs.get("noise"))
         # options that change the loop body step by step run through the per-step path (native UNet forward per step)
         per_step = (quantize_denoised or mask is not None or x0 is not None or noise_dropout > 0. or score_corrector is not None or
                     content_cond is not None or style_cond is not None or random_guiding != 'none' or timesteps is not None)
@@ -317,8 +322,7 @@ class DDIMSampler(_SamplerBase):
         library's starting-latent normals of (seed, stream 0, step 0, noise_row0 + b), drawn in the kernel that applies them -- what a
         seeded sampling call starts from; no noise tensor exists.  Otherwise `noise`, or torch's generator as ldm does."""
         self._refuse_original_steps(use_original_steps)
-        if noise is not None and noise_seed is not None:
-            raise ValueError("noise_seed and an explicit noise select different noise sources: give one of them")
+        self._one_noise_source(noise_seed, noise, "noise")
         t = self._level_index("stochastic_encode", "t", t, 0)
         sa, s1m = self._level_scalars(self.ddim_alphas[t])
         if noise_seed is not None:
@@ -393,8 +397,7 @@ class DDIMSampler(_SamplerBase):
         stream 1, step i)), log_every_t and return_intermediates ((x_dec, intermediates) instead of x_dec) as in sample().  A callback
         takes the per-step path; otherwise the loop runs in the library (rdm_ddim_decode)."""
         self._refuse_original_steps(use_original_steps)
-        if noise_seed is not None and noise is not None:
-            raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
+        self._one_noise_source(noise_seed, noise)
         t_start = self._level_index("decode", "t_start", t_start, 1)
         if unconditional_guidance_scale < 1.:
             raise ValueError("decode: unconditional_guidance_scale must be >= 1")

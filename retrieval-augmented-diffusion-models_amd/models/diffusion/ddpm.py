@@ -19,7 +19,7 @@ import torch
 
 from ... import _lib, packing, parallel
 from ...util import ischannellastimage
-from .ddim import DDIMSampler
+from .ddim import DDIMSampler, _SamplerBase
 from .dpm_solver import DPMSolverSampler, DPMSolverSDESampler
 from .plms import PLMSSampler
 from .uni_pc import UniPCSampler
@@ -551,8 +551,7 @@ class MinimalRETRODiffusion(object):
                                                         "posterior_mean_coef1", "posterior_mean_coef2",
                                                         "posterior_log_variance_clipped")}
         if noise_seed is not None:              # [native] the library's own noise, generated in the step kernel; x_T may stay None
-            if noise is not None:
-                raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
+            _SamplerBase._one_noise_source(noise_seed, noise)
             z = self.ctx.ddpm_sample(T, x_T, cond, None, sched, clip_denoised=self.clip_denoised, temperature=temperature,
                                      seed=noise_seed, row0=noise_row0, shape=tuple(shape)[1:])
             return (z, [z]) if return_intermediates else z

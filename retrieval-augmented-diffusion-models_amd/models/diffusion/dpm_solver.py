@@ -196,8 +196,7 @@ class DPMSolverSDESampler(_NodeListSampler):
             raise ValueError(f"eta must be 0 for {self.NAME}: this solver's noise is not scaled by eta (it is the SDE's own)")
         if order not in (1, 2):
             raise ValueError(f'{self.NAME} order must be 1 or 2, got {order!r}')
-        if noise is not None and noise_seed is not None:
-            raise ValueError("noise_seed and an explicit noise stack select different noise sources: give one of them")
+        self._one_noise_source(noise_seed, noise)
         x_T = self._seeded_start(x_T, (batch_size,) + tuple(shape), noise_seed, noise_row0)
         nodes, cond, uc, scale, img = self._prepare(S, batch_size, shape, conditioning, 0., x_T, unconditional_guidance_scale,
                                                     unconditional_conditioning, skip_type, timesteps)

@@ -94,7 +94,7 @@ def gaussian_run(acp, S, n, seed, sde=True, x_T=None):
     return float(x.mean()), float(x.std()), len(nodes) - 1
 
 
-# ---- the step kernel per element (csrc/misc.hip: dpmpp_sde_update), in the vocabulary of _step_ref
+# ---- the step kernel per element (csrc/sampler_steps.hip: dpmpp_update<V, true>), in the vocabulary of _step_ref
 # roundings of the kernel's text, x_out = ((c_x x + c_0 m0) + c_1 m_prev) + c_n z, on the longest path from an operand to the output:
 #     guided eps       e_c - e_u, scale *, e_u +                                  3   (unguided: 0)
 #     m0               guided + s1m *, x -, / sa                                  guided + 3      -> m_store, pred_x0:  tol_m = K(guided + 3) U A_m

@@ -1,4 +1,4 @@
-"""float64 restatements of the DDIM, PLMS and DDPM step kernels (csrc/misc.hip: ddim_step_kernel, plms_step_kernel<4|1>, ddpm_step_kernel and
+"""float64 restatements of the DDIM, PLMS and DDPM step kernels (csrc/sampler_steps.hip: ddim_step_kernel, plms_step_kernel<4|1>, ddpm_step_kernel and
 the two seeded forms), the per-element bounds they are held to, their near misses and numpy fp32 emulations of the kernel text.
 
 Every restatement takes the kernel's fp32 inputs and fp32 scalars and evaluates the expression in float64.  Beside each value it returns

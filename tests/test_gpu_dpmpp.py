@@ -1,5 +1,5 @@
-"""The native DPM-Solver++ loop (rdm_dpmpp_sample, fused update kernel) on the GPU: the kernel alone per element against float64, every
-step of the loop against the D-form restatement of tests/_dpmpp_ref.py in deterministic mode, order 1 against the DDIM loop,
+"""The native DPM-Solver++ loop (rdm_dpmpp_sample, fused update kernel) on the GPU: the kernel alone per element against float64 and
+bit for bit against the SDE step kernel with its noise term switched off, every step of the loop against the D-form restatement of tests/_dpmpp_ref.py in deterministic mode, order 1 against the DDIM loop,
 DPMSolverSampler against the D-form loop over the CPU oracle UNet, batch independence in deterministic mode, errors, and the end-to-end
 entry."""
 import functools
@@ -91,6 +91,38 @@ def test_step_kernel_per_element_against_fp64(ctx, n, offset, config):
     if x_dup is not None:
         assert torch.equal(x_dup, x_out)
         assert torch.equal(pred_x0, m_store)
+
+
+@pytest.mark.parametrize("history", ["m_prev_none", "m_prev_given", "m_store_aliases_m_prev"])
+@pytest.mark.parametrize("cfg", [0, 1])
+@pytest.mark.parametrize("n", [4096, 1027], ids=["n4096_vector", "n1027_scalar"])
+def test_ode_step_is_the_sde_step_without_its_noise_term(ctx, n, cfg, history):
+    """The ODE and SDE step kernels are one element function (csrc/sampler_steps.hip: dpmpp_update) with and without the c_n z term:
+    op_dpmpp_step must be torch.equal to op_dpmpp_sde_step (stack form) with c_n = 0 and finite normal z, in every output.  xo + 0 z
+    can only turn -0 into +0, which torch.equal treats as equal."""
+    d = ctx.device
+    g = torch.Generator(device=d).manual_seed(7 * n + cfg)
+    rnd = lambda m: torch.randn(m, device=d, generator=g)
+    second = history != "m_prev_none"
+    sa, s1m, c_x, c_0, c_1 = _coefficients(second)
+    x, eps, z = rnd(n), rnd(2 * n if cfg else n), rnd(n)
+    m_prev_in = rnd(n) if second else None
+    got = []
+    for sde in (False, True):
+        m_prev = m_prev_in.clone() if second else None
+        x_out, x_dup, pred_x0, m_new = (torch.full((n,), float("nan"), device=d) for _ in range(4))
+        m_store = m_prev if history == "m_store_aliases_m_prev" else m_new
+        if sde:
+            ctx.op_dpmpp_sde_step(x, eps, m_prev, z, cfg, 2.0 if cfg else 1.0, sa, s1m, c_x, c_0, c_1, 0.0, x_out, x_dup=x_dup, m_store=m_store,
+                                  pred_x0=pred_x0)
+        else:
+            ctx.op_dpmpp_step(x, eps, m_prev, cfg, 2.0 if cfg else 1.0, sa, s1m, c_x, c_0, c_1, x_out, x_dup=x_dup, m_store=m_store,
+                              pred_x0=pred_x0)
+        torch.cuda.synchronize()
+        got.append((x_out, x_dup, m_store, pred_x0))
+    assert torch.isfinite(z).all() and all(torch.isfinite(t).all() for t in got[0])
+    for name, ode, sde in zip(("x_out", "x_dup", "m_store", "pred_x0"), *got):
+        assert torch.equal(ode, sde), name
 
 
 # ---- the loop, step by step

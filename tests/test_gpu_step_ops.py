@@ -1,4 +1,4 @@
-"""The DDIM, PLMS and DDPM step kernels (csrc/misc.hip) alone, through rdm_op_ddim_step / rdm_op_plms_step / rdm_op_ddpm_step and the two
+"""The DDIM, PLMS and DDPM step kernels (csrc/sampler_steps.hip) alone, through rdm_op_ddim_step / rdm_op_plms_step / rdm_op_ddpm_step and the two
 seeded entries: every element of every output against the float64 restatements of tests/_step_ref.py within the bounds derived there
 (scalar tail, float4 path, a misaligned operand, the second trip of each kernel's stride loop, aliased outputs, every optional output),
 into sentinel-guarded buffers; the seeded forms bit for bit against the unseeded ones fed rdm_op_randn's output; every refusal; the
