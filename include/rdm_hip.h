@@ -229,7 +229,9 @@ int rdm_ddpm_sample(rdm_ctx* ctx, const rdm_ddpm_args* args, const float* x_T, c
  *     counter[0] = block   = (element index WITHIN the sample row) >> 2
  *     counter[1] = step    = draw index: the loop step counted from 0 in loop order (the i-th step taken)
  *     counter[2] = row     = GLOBAL sample index, row0 + b
- *     counter[3] = stream  = 0: the starting latent x_T (step 0) | 1: per-step update noise | >= 2: reserved, refused by the entries
+ *     counter[3] = stream  = 0: the forward process's noise | 1: per-step update noise | >= 2: reserved, refused by the entries
+ * Stream 0 is the noise of the forward process q(x_t | x_0): step 0 the starting latent x_T (and rdm_op_q_sample_seeded's noise), step i + 1
+ * the noise the inpainting loop gives the known region at loop step i (rdm_ddim_inpaint_seeded).
  * Element e of a row takes output word e & 3 of block e >> 2: rows never share a block, and a value depends on (seed, stream, step, row, e)
  * only -- not on the batch size, on how row0 splits a batch, on the grid or on the vector width.  Normals are Box-Muller on the word pairs
  * (w0, w1) and (w2, w3): u = ((w >> 9) + 0.5) 2^-23 (exact in fp32, strictly inside (0, 1), so |z| <= 5.77), r = sqrtf(-2 logf(u1)),
@@ -310,6 +312,44 @@ int rdm_op_ddim_inverse_step(rdm_ctx* ctx, const float* x, const float* eps, lon
  * be split over calls.  per_row % 4 == 0 and 16-byte aligned x0 / out are required (-1 otherwise).  out may be x0. */
 int rdm_op_q_sample_seeded(rdm_ctx* ctx, const float* x0, int64_t B, int64_t per_row, float sqrt_a, float sqrt_1ma, uint64_t seed,
                            int64_t row0, float* out);
+
+/* ---- inpainting on the DDIM schedule (ldm DDIMSampler.ddim_sampling with mask / x0) ------------------
+ * The blend: out = (sqrt_a x0 + sqrt_1ma z) m + (1 - m) x over [B,C,H,W] in fp32, every operation rounded on its own (no FMA), in
+ * the order written: where m = 1 the result is fp32(sqrt_a x0 + sqrt_1ma z) and where m = 0 it is x, bit for bit.  x0 [dev] f32
+ * [B,C,H,W] is the known latent; mask [dev] f32 [B,mask_channels,H,W] holds m in [0, 1], 1 = KEEP THE KNOWN LATENT (ldm's convention),
+ * with mask_channels = 1 (one plane for every channel) or C.
+ *
+ * rdm_op_masked_blend: the kernel alone on caller-owned buffers; z [dev] f32 [B,C,H,W] or NULL (zeros: the last blend of a
+ * keep-the-known-region call, at sqrt_a = 1, sqrt_1ma = 0).  out may be x; x_dup (or NULL) receives the same values.  float4 accesses
+ * when B*C*H*W % 4 == 0, H*W % 4 == 0 and every operand is 16-byte aligned, else scalar ones.
+ * rdm_op_masked_blend_seeded: z is drawn in registers from the device-noise counters -- stream 0, the given step, row = row0 + b,
+ * block = (element within the row) >> 2 -- and the result is bit-identical to rdm_op_masked_blend fed with
+ * rdm_op_randn(seed, row0, B, C*H*W, step, stream = 0).  The loops use step = i + 1 for loop step i (step 0 is the starting latent).
+ * C*H*W % 4 == 0 and 16-byte aligned x, x0, out, x_dup are required (-1 otherwise); the mask may have any alignment, and when
+ * H*W % 4 != 0 -- a block then straddles channel planes -- it is indexed per element.
+ *
+ * rdm_ddim_inpaint: rdm_ddim_decode's loop (same arguments, scalars, intermediates) with the blend before every forward: loop step
+ * i = 0 .. t_start - 1 works at level index = t_start - 1 - i and first replaces the iterate by the blend at that level,
+ * sqrt_a = sqrt(a_t[index]), sqrt_1ma = sqrt(1 - a_t[index]) in float64 from the fp32 alpha, rounded, z = q_noise[i]; then the UNet
+ * forward, then rdm_ddim_decode's step.  The result of the last step is not blended, as in ldm's loop.  q_noise [dev] f32
+ * [t_start,B,C,H,W], required, consumed in loop order; noise as rdm_ddim_decode's.  rdm_ddim_inpaint_seeded takes neither stack: the
+ * update noise of loop step i is (seed, stream 1, step i) as rdm_ddim_decode_seeded's, the known region's (seed, stream 0, step i + 1),
+ * both for rows row0 + b, and the loop is bit-identical to the stack loop fed with rdm_op_randn's outputs.  It needs
+ * channels * height * width % 4 == 0 and a 16-byte aligned x0.
+ *
+ * All four return -1 with a message, and leave the context usable, for a null x, x0, mask (or q_noise in the stack loop), a
+ * mask_channels that is neither 1 nor C, a t_start outside [1, total], and what rdm_ddim_decode / its seeded form refuse. */
+int rdm_op_masked_blend(rdm_ctx* ctx, const float* x, const float* x0, const float* mask, const float* z_or_null, int64_t B, int C, int H,
+                        int W, int mask_channels, float sqrt_a, float sqrt_1ma, float* out, float* x_dup_or_null);
+int rdm_op_masked_blend_seeded(rdm_ctx* ctx, const float* x, const float* x0, const float* mask, int64_t B, int C, int H, int W,
+                               int mask_channels, float sqrt_a, float sqrt_1ma, uint64_t seed, int64_t row0, uint32_t step, float* out,
+                               float* x_dup_or_null);
+int rdm_ddim_inpaint(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, const float* x_latent, const float* x0, const float* mask,
+                     int mask_channels, const float* cond, const float* uncond, const float* noise, const float* q_noise, float* z_out,
+                     float* x_inter, float* pred_x0_inter);
+int rdm_ddim_inpaint_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, uint64_t seed, int64_t row0, const float* x_latent,
+                            const float* x0, const float* mask, int mask_channels, const float* cond, const float* uncond, float* z_out,
+                            float* x_inter, float* pred_x0_inter);
 /* One guided UNet forward exactly as the sampling loops run it (rdm_unet_forward on [x | x], [cond | uncond] computes the same function
  * through other kernel configurations: every sample's own prefix, no zero-context shortcut, the time embedding per row): x [dev] f32
  * [B,Cin,H,W] at the one timestep t; cond, uncond [dev] f32 [B,k,ctx_dim]; eps_out [dev] f32 [2B,Cout,H,W], rows cond | uncond.  What a

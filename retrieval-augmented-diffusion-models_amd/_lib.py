@@ -145,6 +145,11 @@ SIGNATURES = {
     "rdm_ddim_encode": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, _P, _P]),
     "rdm_op_ddim_inverse_step": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     "rdm_op_q_sample_seeded": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_int64, _P]),
+    "rdm_op_masked_blend": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "rdm_op_masked_blend_seeded": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
+                                             C.c_int64, C.c_uint32, _P, _P]),
+    "rdm_ddim_inpaint": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
+    "rdm_ddim_inpaint_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, C.c_uint64, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
     "rdm_vq_quantize": (C.c_int, [_P, _P, C.c_int, _P, _P]),
@@ -928,6 +933,76 @@ class Context:
               (lambda h, a, x, c, u, *out: lib.rdm_ddim_decode_seeded(h, a, t_start, seed, row0, x, c, u, *out)))
         return self._sampler_call("ddim_decode", fn, DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates,
                                   S=S, noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
+
+    @staticmethod
+    def _blend_mask(what, mask, shape):
+        """The mask of a blend over a latent of `shape` (B, C, H, W): [B, 1, H, W] or [B, C, H, W] -> its channel count."""
+        B, Cc, H, W = (int(v) for v in shape)
+        if mask.ndim != 4 or tuple(mask.shape) not in ((B, 1, H, W), (B, Cc, H, W)):
+            raise RdmError(f"{what}: mask must be [{B},1,{H},{W}] or [{B},{Cc},{H},{W}], got {tuple(mask.shape)}")
+        return int(mask.shape[1])
+
+    def ddim_inpaint(self, S, t_start, x_latent, x0, mask, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, q_noise=None,
+                     log_every_t=100, temperature=1.0, want_intermediates=False, seed=None, row0=0):
+        """rdm_ddim_inpaint: ddim_decode's loop with the inpainting blend before every forward -- at loop step i the iterate becomes
+        (sqrt(a) x0 + sqrt(1 - a) z_i) mask + (1 - mask) x at that step's level a; mask [B, 1 | C, H, W] in [0, 1], 1 = keep the known
+        latent x0.  z_i = q_noise[i], q_noise a [t_start, B, C, H, W] stack (required without a seed); noise: the update noise stack for
+        eta > 0, as ddim_decode's.  With `seed` rdm_ddim_inpaint_seeded: no stack of either kind -- the update noise is the library's
+        (seed, stream 1, step i), the known region's (seed, stream 0, step i + 1), rows row0 + b.  The result of the last step is not
+        blended.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
+        if x_latent is None or x0 is None or mask is None:
+            raise RdmError("ddim_inpaint: x_latent, x0 and mask are required")
+        t_start = int(t_start)
+        if seed is not None and q_noise is not None:
+            raise RdmError("ddim_inpaint: give a seed or a q_noise stack, not both")
+        noise, _, seed, row0 = _noise_source(self, "ddim_inpaint", x_latent, cond, noise, seed, row0)
+        x0, mask = self._dev(x0, torch.float32), self._dev(mask, torch.float32)
+        if tuple(x0.shape) != tuple(x_latent.shape):
+            raise RdmError(f"ddim_inpaint: x0 {tuple(x0.shape)} must have the latent's shape {tuple(x_latent.shape)}")
+        mc = self._blend_mask("ddim_inpaint", mask, x_latent.shape)
+        if seed is None:
+            if q_noise is None:
+                raise RdmError("ddim_inpaint: a q_noise stack [t_start, B, C, H, W] is required without a seed")
+            q_noise = self._dev(q_noise, torch.float32)
+            if tuple(q_noise.shape) != (t_start,) + tuple(x_latent.shape):
+                raise RdmError(f"ddim_inpaint: q_noise must be {(t_start,) + tuple(x_latent.shape)}, got {tuple(q_noise.shape)}")
+        fn = ((lambda h, a, x, c, u, *out: lib.rdm_ddim_inpaint(h, a, t_start, x, _ptr(x0), _ptr(mask), mc, c, u, _ptr(noise), _ptr(q_noise), *out))
+              if seed is None else
+              (lambda h, a, x, c, u, *out: lib.rdm_ddim_inpaint_seeded(h, a, t_start, seed, row0, x, _ptr(x0), _ptr(mask), mc, c, u, *out)))
+        return self._sampler_call("ddim_inpaint", fn, DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates,
+                                  S=S, noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
+
+    def op_masked_blend(self, x, x0, mask, z, sqrt_a, sqrt_1ma, out=None, x_dup=None, seed=None, row0=0, step=1):
+        """The inpainting blend kernel alone on caller-owned contiguous fp32 device tensors: out = (sqrt_a x0 + sqrt_1ma z) mask +
+        (1 - mask) x over x [B, C, H, W], mask [B, 1 | C, H, W] (1 = x0), z of x's size or None (zeros) (rdm_op_masked_blend).  With `seed`
+        (and no z) rdm_op_masked_blend_seeded: z is the library's (seed, stream 0, step, row0 + b), drawn in the kernel -- step i + 1 for
+        loop step i; C * H * W must then be a multiple of 4 and x, x0, out, x_dup 16-byte aligned.  out (default: a new tensor) may be x;
+        x_dup receives the same values.  -> out."""
+        ok = lambda t: t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
+        if x.ndim != 4 or not all(ok(t) for t in (x, x0, mask)):
+            raise RdmError("op_masked_blend: x [B, C, H, W], x0 and mask must be contiguous fp32 device tensors")
+        if tuple(x0.shape) != tuple(x.shape):
+            raise RdmError(f"op_masked_blend: x0 {tuple(x0.shape)} must have x's shape {tuple(x.shape)}")
+        mc = self._blend_mask("op_masked_blend", mask, x.shape)
+        if out is None:
+            out = torch.empty_like(x)
+        for t in (z, out, x_dup):
+            if t is not None and (not ok(t) or t.numel() != x.numel()):
+                raise RdmError("op_masked_blend: z, out and x_dup must be contiguous fp32 device tensors of x's size")
+        B, Cc, H, W = (int(v) for v in x.shape)
+        if seed is None:
+            self._check(lib.rdm_op_masked_blend(self._h, _ptr(x), _ptr(x0), _ptr(mask), _ptr(z), B, Cc, H, W, mc, float(sqrt_a), float(sqrt_1ma),
+                                                _ptr(out), _ptr(x_dup)))
+            return out
+        if z is not None:
+            raise RdmError("op_masked_blend: a seeded call takes no z operand")
+        step = int(step)
+        if not 0 <= step < 2 ** 32:
+            raise RdmError(f"op_masked_blend: step is a 32-bit counter, got {step}")
+        seed, row0 = _noise_seed("op_masked_blend", seed, row0, B)
+        self._check(lib.rdm_op_masked_blend_seeded(self._h, _ptr(x), _ptr(x0), _ptr(mask), B, Cc, H, W, mc, float(sqrt_a), float(sqrt_1ma), seed,
+                                                   row0, step, _ptr(out), _ptr(x_dup)))
+        return out
 
     def ddim_encode(self, S, t_enc, x0, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False, eta=0.0):
         """rdm_ddim_encode: deterministic DDIM inversion of x0, t_enc steps up the S-step schedule with the UNet at each step's target

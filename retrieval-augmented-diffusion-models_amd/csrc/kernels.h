@@ -169,6 +169,20 @@ struct DdpmStepParams {
 struct StepRngParams { unsigned long long seed; long long per_row; uint32_t row0, step; };
 struct RngFillParams { unsigned long long seed; long long rows, per_row; uint32_t row0, step, stream; uint32_t* out; };
 
+// The inpainting blend of the DDIM loop (rdm_op_masked_blend, rdm_ddim_inpaint; ldm's img_orig * mask + (1 - mask) * img with
+// img_orig = q_sample(x0, t)): out = (sqrt_a x0 + sqrt_1ma z) m + (1 - m) x over [B, C, H, W], m = mask [B, mask_channels, H, W] with
+// mask_channels 1 (one plane for every channel) or C; 1 keeps the known latent x0.  The two scalars are the host's float64 square roots
+// rounded to fp32.  z: the known region's noise, read from memory (null: zeros) -- the seeded kernel draws it instead, the normals of
+// (seed, stream 0, StepRngParams::step, row0 + b).  out may be x: a thread reads its elements of x before it writes them.
+struct MaskedBlendParams {
+    const float* x; const float* x0; const float* mask; const float* z;
+    float* out; float* x_dup;                                // x_dup: second copy of out (the CFG-doubled batch) or null
+    long long n, chw, hw;                                    // B*C*H*W, C*H*W, H*W
+    int mask_channels;                                       // 1 | C
+    int mask_vec;                                            // the seeded kernel: hw % 4 == 0 and mask 16-byte aligned, so a block's four elements share one mask quad
+    float sqrt_a, sqrt_1ma;
+};
+
 // RARM decode step (rarm.hip)
 struct RarmAttnParams {
     const bf16_t* q; int ldq;                 // q[b*ldq + h*64 + d]; k_new / v_new share ldq (one fused qkv row per sequence)
@@ -338,6 +352,8 @@ hipError_t launch_dpmpp_sde_step_seeded(const DpmppStepParams& p, const StepRngP
 hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st);
 hipError_t launch_ddim_inverse_step(const DdimInverseStepParams& p, hipStream_t st);
 hipError_t launch_q_sample_seeded(const QSampleSeededParams& p, hipStream_t st);     // hipErrorInvalidValue: per_row % 4 or an operand not 16-byte aligned
+hipError_t launch_masked_blend(const MaskedBlendParams& p, hipStream_t st);          // float4 form when n % 4 == 0, hw % 4 == 0 and every operand is 16-byte aligned, else scalar
+hipError_t launch_masked_blend_seeded(const MaskedBlendParams& p, const StepRngParams& g, hipStream_t st);   // p.z unused; hipErrorInvalidValue: chw % 4 or x / x0 / out / x_dup not 16-byte aligned
 hipError_t launch_vq_quantize(const float* z, const float* codebook, int n_embed, const float* pq_w, const float* pq_b,
                               float* out, int* idx_out, int B, int HW, int quantize, hipStream_t st);
 // nearest-code search of a wide-latent VQ first stage (vqcode.hip): idx[m] = argmin_j |e_j|^2 - 2 z_m . e_j on fp32-input MFMAs, first minimum on ties

@@ -5,7 +5,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
-#define RDM_RNG_STREAM_XT 0u      // the starting latent x_T (step 0)
+#define RDM_RNG_STREAM_XT 0u      // the forward process's noise: step 0 the starting latent x_T, step i + 1 the known region of inpainting loop step i
 #define RDM_RNG_STREAM_STEP 1u    // per-step update noise
 #define RDM_RNG_STREAMS 2u        // streams >= this are reserved: the entries refuse them
 

@@ -1,5 +1,5 @@
-// The sampling update kernels (DDIM, PLMS, DPM-Solver++ and its SDE form, UniPC, DDIM inversion, DDPM), their seeded forms and the
-// device-noise kernels (gfx950).
+// The sampling update kernels (DDIM, PLMS, DPM-Solver++ and its SDE form, UniPC, DDIM inversion, DDPM), their seeded forms, the
+// device-noise kernels and, at the end, the inpainting blend with its seeded form (gfx950).
 #include "kernels.h"
 #include "philox.h"
 
@@ -424,5 +424,87 @@ hipError_t launch_rng_fill(const RngFillParams& p, bool normal, hipStream_t st) 
     const long long nblk = p.rows * ((p.per_row + 3) >> 2);
     const int grid = (int)std::min<long long>((nblk + 255) / 256, 2048);
     (normal ? (vec ? rng_fill_kernel<true, 4> : rng_fill_kernel<true, 1>) : (vec ? rng_fill_kernel<false, 4> : rng_fill_kernel<false, 1>))<<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------ the inpainting blend (fp32)
+// ldm DDIMSampler.ddim_sampling with a mask: before a step's forward, img = q_sample(x0, t) * mask + (1 - mask) * img.  The expression of the
+// per-step path (models/diffusion/ddim.py _masked_blend over _q_sample), term for term: both products of the forward process rounded,
+// their sum rounded, the product with m, 1 - m, its product with x, the last sum -- true operations, no FMA contraction.  With m = 1 the
+// result is fp32(sqrt_a x0 + sqrt_1ma z) and with m = 0 it is x, bit for bit.  A pass of its own beside the step kernels, which it leaves
+// as they are: B*C*H*W floats once per step, next to a UNet forward.
+__device__ __forceinline__ float masked_blend_value(float sa, float s1m, float x0, float z, float m, float x) {
+#pragma clang fp contract(off)
+    const float a = sa * x0, b = s1m * z;
+    const float q = a + b;
+    const float known = q * m, om = 1.0f - m;
+    const float kept = om * x;
+    return known + kept;
+}
+// element i = b chw + rem of [B, C, H, W] -> its element of the mask [B, mask_channels, H, W]
+__device__ __forceinline__ long long masked_blend_mask_index(const MaskedBlendParams& p, long long i, long long b, long long rem) {
+    return p.mask_channels != 1 ? i : b * p.hw + rem % p.hw;
+}
+__device__ __forceinline__ long long masked_blend_mask_index(const MaskedBlendParams& p, long long i) {
+    if (p.mask_channels != 1) return i;
+    const long long b = i / p.chw;
+    return masked_blend_mask_index(p, i, b, i - b * p.chw);
+}
+// V = 4: float4 accesses; hw % 4 == 0, so the four elements lie in one channel plane and share one aligned mask quad (the launcher checks).
+template <int V>
+__global__ __launch_bounds__(256) void masked_blend_kernel(MaskedBlendParams p) {
+    const long long nv = p.n / V;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * V;
+        float x[V], x0[V], m[V], z[V] = {}, o[V];
+        step_ld<V>(p.x, i, x);
+        step_ld<V>(p.x0, i, x0);
+        step_ld<V>(p.mask, masked_blend_mask_index(p, i), m);
+        if (p.z) step_ld<V>(p.z, i, z);
+#pragma unroll
+        for (int k = 0; k < V; k++) o[k] = masked_blend_value(p.sqrt_a, p.sqrt_1ma, x0[k], z[k], m[k], x[k]);
+        step_st<V>(p.out, i, o);
+        if (p.x_dup) step_st<V>(p.x_dup, i, o);
+    }
+}
+hipError_t launch_masked_blend(const MaskedBlendParams& p, hipStream_t st) {
+    if (p.n <= 0) return hipSuccess;
+    bool vec = p.n % 4 == 0 && p.hw % 4 == 0;               // launch_step's rule, and whole mask quads
+    for (const void* q : {(const void*)p.x, (const void*)p.x0, (const void*)p.mask, (const void*)p.z, (const void*)p.out, (const void*)p.x_dup})
+        vec = vec && ((uintptr_t)q % 16 == 0);
+    const long long nv = vec ? p.n / 4 : p.n;
+    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
+    (vec ? masked_blend_kernel<4> : masked_blend_kernel<1>)<<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
+}
+// The same arithmetic on noise drawn in registers: one Philox block per thread, four consecutive elements of one sample row, (row, block)
+// derived from the flat vector index as in ddim_step_seeded_kernel -- stream 0 (RDM_RNG_STREAM_XT) at step g.step >= 1, the forward
+// process's noise of the known region (philox.h).  chw % 4 == 0: rows never share a block.  When hw % 4 != 0 a block straddles channel
+// planes and the mask is indexed per element (p.mask_vec == 0).  Bit-identical to masked_blend_kernel fed with rdm_op_randn's output.
+__global__ __launch_bounds__(256) void masked_blend_seeded_kernel(MaskedBlendParams p, StepRngParams g) {
+    const long long nv = p.n >> 2, bpr = g.per_row >> 2;
+    for (long long v = (long long)blockIdx.x * 256 + threadIdx.x; v < nv; v += (long long)gridDim.x * 256) {
+        const long long i = v * 4, r = v / bpr, rem = (v - r * bpr) * 4;         // element i is element rem of row r
+        float z[4], x[4], x0[4], m[4], o[4];
+        philox_normal4(g.seed, (uint32_t)(v - r * bpr), g.step, g.row0 + (uint32_t)r, RDM_RNG_STREAM_XT, z);
+        step_ld<4>(p.x, i, x);
+        step_ld<4>(p.x0, i, x0);
+        if (p.mask_vec) step_ld<4>(p.mask, masked_blend_mask_index(p, i, r, rem), m);
+        else {
+#pragma unroll
+            for (int k = 0; k < 4; k++) m[k] = p.mask[masked_blend_mask_index(p, i + k, r, rem + k)];
+        }
+#pragma unroll
+        for (int k = 0; k < 4; k++) o[k] = masked_blend_value(p.sqrt_a, p.sqrt_1ma, x0[k], z[k], m[k], x[k]);
+        step_st<4>(p.out, i, o);
+        if (p.x_dup) step_st<4>(p.x_dup, i, o);
+    }
+}
+hipError_t launch_masked_blend_seeded(const MaskedBlendParams& p, const StepRngParams& g, hipStream_t st) {
+    if (g.per_row != p.chw || !seeded_step_ok(p.n, g.per_row, {p.x, p.x0, p.out, p.x_dup})) return hipErrorInvalidValue;
+    MaskedBlendParams q = p;
+    q.z = nullptr; q.mask_vec = (p.hw % 4 == 0 && (uintptr_t)p.mask % 16 == 0) ? 1 : 0;
+    const int grid = (int)std::min<long long>((p.n / 4 + 255) / 256, 2048);
+    masked_blend_seeded_kernel<<<grid, 256, 0, st>>>(q, g);
     return hipGetLastError();
 }

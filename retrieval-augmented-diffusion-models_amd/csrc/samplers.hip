@@ -1,7 +1,8 @@
 // The sampling loops of librdm_hip (DDIM, PLMS, DPM-Solver++(2M) and its SDE form -- one loop, dpmpp_sample_impl --, UniPC, DDPM): their
 // schedules, SamplerRun (one sampling call's scratch, tables and UNet forward), NoiseSource (where a loop's step noise comes from: a stack,
 // a seed, or nowhere), the rdm_*_sample entries, the device-noise entries, DDIM image-to-image (rdm_ddim_decode: the
-// DDIM loop begun part-way down the schedule; rdm_ddim_encode: the loop that runs UP it) and the step-kernel op entries.
+// DDIM loop begun part-way down the schedule; rdm_ddim_encode: the loop that runs UP it; rdm_ddim_inpaint: decode with the known latent
+// blended in before every forward) and the step-kernel op entries.
 // Calls into unet_exec.hip through the three functions host.h declares (unet_prepare_kv, unet_emb_table, unet_forward_impl) and
 // into the launch_* of kernels.h.  The loops are the reference's
 //   DDIMSampler                     rdm/models/diffusion/ddim.py:27-268
@@ -169,12 +170,19 @@ struct HistoryRing {
 // The DDIM loop of rdm_ddim_sample (the step noise is read from ns.stack) and rdm_ddim_sample_seeded (it is generated in the step kernel,
 // and a null x_T is drawn), and of the two rdm_ddim_decode entries: n_run steps down from level index n_run - 1 (n_run < 0: the whole
 // schedule).  The run is the loop over the schedule cut to its first n_run entries.
+// Inpainting (the two rdm_ddim_inpaint entries): before the forward of loop step i the iterate is blended with the known latent x0 noised
+// to that step's level, x <- (sqrt(a) x0 + sqrt(1 - a) z_i) m + (1 - m) x with a = a_t[index] (masked_blend_kernel; the scalars are float64
+// square roots of the fp32 alpha, rounded, as rdm_ddim_encode's).  z_i is row i of q_noise, or -- a seeded loop, q_noise null -- drawn in
+// the blend kernel from (seed, stream 0, step i + 1).  The result of the last step is not blended, as in ldm's loop.
+struct InpaintSource { const float* x0; const float* mask; int mask_channels; const float* q_noise; };
 static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, int n_run, const float* x_T, const float* cond, const float* uncond,
-                            const NoiseSource& ns, float* z_out, float* x_inter, float* pred_x0_inter) {
+                            const NoiseSource& ns, float* z_out, float* x_inter, float* pred_x0_inter, const InpaintSource* ip = nullptr) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     bool cfg;
     RDM_TRY(sampler_guidance(c, "ddim", a->unconditional_guidance_scale, uncond, &cfg));
     RDM_TRY(check_seeded(c, "ddim", ns, a));
+    if (ip && ip->mask_channels != 1 && ip->mask_channels != a->channels)
+        return c->fail(-1, "ddim inpaint: mask_channels must be 1 or channels = %d, got %d", a->channels, ip->mask_channels);
     if (!ns.seeded && a->eta != 0.f && !ns.stack) return c->fail(-1, "eta > 0 needs an explicit noise stack [S,B,C,H,W] (device RNG parity is not defined)");
     std::vector<int> ts; std::vector<float> at, ap, s1m;
     RDM_TRY(ddim_schedule(c, a, ts, at, ap, s1m));
@@ -194,6 +202,21 @@ static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, int n_run, const
     if (!x_T) RDM_TRY(run.draw_start(ns.seed));
     for (int i = 0; i < total; i++) {
         const int index = total - i - 1;         // of the ascending schedule
+        if (ip) {
+            const double ad = (double)at[index];
+            MaskedBlendParams m{};
+            m.x = run.x; m.x0 = ip->x0; m.mask = ip->mask; m.out = run.x; m.x_dup = run.x_dup;
+            m.n = run.n1; m.chw = run.n1 / run.B; m.hw = (long long)run.H * run.W; m.mask_channels = ip->mask_channels;
+            m.sqrt_a = (float)std::sqrt(ad); m.sqrt_1ma = (float)std::sqrt(1.0 - ad);
+            if (ns.seeded) {                     // the known region's noise of loop step i, in registers
+                const hipError_t e = launch_masked_blend_seeded(m, run.step_rng(ns.seed, i + 1), c->stream);
+                if (e == hipErrorInvalidValue) return c->fail(-1, "ddim inpaint (seeded): x0 must be 16-byte aligned");
+                RDM_CHECK_HIP(c, e);
+            } else {
+                m.z = ip->q_noise + (size_t)i * run.n1;
+                RDM_CHECK_HIP(c, launch_masked_blend(m, c->stream));
+            }
+        }
         RDM_TRY(run.forward(index));
         DdimStepParams p{};
         p.x = run.x; p.eps = run.eps; p.noise = (ns.stack && a->eta != 0.f) ? ns.stack + (size_t)i * run.n1 : nullptr;
@@ -233,6 +256,26 @@ int rdm_ddim_decode_seeded(rdm_ctx* c, const rdm_ddim_args* a, int t_start, uint
     if (!c || !a || !x_latent || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
     if (t_start < 1) return c->fail(-1, "ddim decode: t_start must be at least 1, got %d", t_start);
     return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_seed(seed, row0), z_out, x_inter, pred_x0_inter);
+}
+
+// DDIM inpainting: rdm_ddim_decode's loop with the blend above before every forward
+int rdm_ddim_inpaint(rdm_ctx* c, const rdm_ddim_args* a, int t_start, const float* x_latent, const float* x0, const float* mask, int mask_channels,
+                     const float* cond, const float* uncond, const float* noise, const float* q_noise, float* z_out, float* x_inter,
+                     float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_latent || !x0 || !mask || !q_noise || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    if (t_start < 1) return c->fail(-1, "ddim inpaint: t_start must be at least 1, got %d", t_start);
+    const InpaintSource ip{x0, mask, mask_channels, q_noise};
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_stack(noise), z_out, x_inter, pred_x0_inter, &ip);
+}
+int rdm_ddim_inpaint_seeded(rdm_ctx* c, const rdm_ddim_args* a, int t_start, uint64_t seed, int64_t row0, const float* x_latent, const float* x0,
+                            const float* mask, int mask_channels, const float* cond, const float* uncond, float* z_out, float* x_inter,
+                            float* pred_x0_inter) {
+    RDM_ENTER(c);
+    if (!c || !a || !x_latent || !x0 || !mask || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    if (t_start < 1) return c->fail(-1, "ddim inpaint: t_start must be at least 1, got %d", t_start);
+    const InpaintSource ip{x0, mask, mask_channels, nullptr};
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_seed(seed, row0), z_out, x_inter, pred_x0_inter, &ip);
 }
 
 // Deterministic DDIM inversion (rdm_ddim_encode's header comment): t_enc steps UP the schedule, step i from level a_prev[i] to a_t[i] with
@@ -702,6 +745,41 @@ int rdm_op_q_sample_seeded(rdm_ctx* c, const float* x0, int64_t B, int64_t per_r
     const QSampleSeededParams p{x0, out, seed, B, per_row, (uint32_t)row0, sqrt_a, sqrt_1ma};
     const hipError_t e = launch_q_sample_seeded(p, c->stream);
     if (e == hipErrorInvalidValue) return c->fail(-1, "rdm_op_q_sample_seeded: per_row must be a multiple of 4 and x0, out 16-byte aligned");
+    RDM_CHECK_HIP(c, e);
+    return 0;
+}
+
+// ---- the inpainting blend alone
+static int masked_blend_fill(rdm_ctx* c, const char* who, MaskedBlendParams& p, const float* x, const float* x0, const float* mask, int64_t B,
+                             int C, int H, int W, int mask_channels, float sqrt_a, float sqrt_1ma, float* out, float* x_dup) {
+    if (!x || !x0 || !mask || !out) return c->fail(-1, "%s: null argument", who);
+    if (B < 1 || C < 1 || H < 1 || W < 1 || B > (1ll << 40) / ((long long)C * H * W))
+        return c->fail(-1, "%s: bad shape B=%lld C=%d H=%d W=%d", who, (long long)B, C, H, W);
+    if (mask_channels != 1 && mask_channels != C) return c->fail(-1, "%s: mask_channels must be 1 or C = %d, got %d", who, C, mask_channels);
+    p.x = x; p.x0 = x0; p.mask = mask; p.out = out; p.x_dup = x_dup;
+    p.hw = (long long)H * W; p.chw = p.hw * C; p.n = p.chw * B; p.mask_channels = mask_channels; p.sqrt_a = sqrt_a; p.sqrt_1ma = sqrt_1ma;
+    return 0;
+}
+int rdm_op_masked_blend(rdm_ctx* c, const float* x, const float* x0, const float* mask, const float* z, int64_t B, int C, int H, int W,
+                        int mask_channels, float sqrt_a, float sqrt_1ma, float* out, float* x_dup) {
+    RDM_ENTER(c);
+    if (!c) return -1;
+    MaskedBlendParams p{};
+    RDM_TRY(masked_blend_fill(c, "rdm_op_masked_blend", p, x, x0, mask, B, C, H, W, mask_channels, sqrt_a, sqrt_1ma, out, x_dup));
+    p.z = z;
+    RDM_CHECK_HIP(c, launch_masked_blend(p, c->stream));
+    return 0;
+}
+int rdm_op_masked_blend_seeded(rdm_ctx* c, const float* x, const float* x0, const float* mask, int64_t B, int C, int H, int W, int mask_channels,
+                               float sqrt_a, float sqrt_1ma, uint64_t seed, int64_t row0, uint32_t step, float* out, float* x_dup) {
+    RDM_ENTER(c);
+    if (!c) return -1;
+    MaskedBlendParams p{};
+    RDM_TRY(masked_blend_fill(c, "rdm_op_masked_blend_seeded", p, x, x0, mask, B, C, H, W, mask_channels, sqrt_a, sqrt_1ma, out, x_dup));
+    RDM_TRY(check_noise_rows(c, "rdm_op_masked_blend_seeded", row0, B, p.chw));
+    const hipError_t e = launch_masked_blend_seeded(p, StepRngParams{seed, p.chw, (uint32_t)row0, step}, c->stream);
+    if (e == hipErrorInvalidValue)
+        return c->fail(-1, "rdm_op_masked_blend_seeded: C * H * W must be a multiple of 4, and x, x0, out, x_dup 16-byte aligned");
     RDM_CHECK_HIP(c, e);
     return 0;
 }

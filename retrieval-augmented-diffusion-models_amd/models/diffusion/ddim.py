@@ -219,12 +219,15 @@ class DDIMSampler(_SamplerBase):
     def _python_loop(self, cond, img, callback, img_callback, log_every_t, temperature, eta, scale, uc, to_cpu, mask=None,
                      x0=None, noise_dropout=0., score_corrector=None, corrector_kwargs=None, random_guiding='none',
                      timesteps=None, content_cond=None, style_cond=None, noise=None, q_noise=None, quantize_denoised=False,
-                     noise_seed=None, noise_row0=0, ts_all=None):
+                     noise_seed=None, noise_row0=0, ts_all=None, q_noise_seed=None):
         """Per-step path of ddim.py:143-209 (callbacks, inpainting mask, style / content conditioning by SNR band, timestep
         subset, noise dropout, score corrector): native UNet forward per step, torch elementwise update.  `noise` / `q_noise`
         [native]: optional explicit stacks [steps, B, C, H, W] for the update noise and for q_sample of the masked region;
         `noise_seed` [native]: step i's update noise is the library's (stream 1, step i), what the native seeded loop applies.
-        `ts_all` [native]: the ascending timesteps to run down (decode: the schedule's first t_start) instead of `timesteps`' subset."""
+        `ts_all` [native]: the ascending timesteps to run down (decode: the schedule's first t_start) instead of `timesteps`' subset.
+        `q_noise_seed` [native]: without a q_noise stack, step i's q_sample noise is the library's (stream 0, step i + 1) of that seed, rows
+        noise_row0 .. -- what the native seeded inpainting loop applies (decode passes its noise_seed); None: torch's generator, which is
+        what sample(mask=, noise_seed=) keeps drawing it from."""
         if ts_all is None:
             ts_all = self._timestep_subset(timesteps)
         total_steps = ts_all.shape[0]
@@ -243,7 +246,9 @@ class DDIMSampler(_SamplerBase):
             if content_cond is not None and snr >= 5.e-2 and snr < 1.:
                 input_cond = content_cond
             if mask is not None:
-                img = self._masked_blend(img, mask, x0, ts, None if q_noise is None else q_noise[i])
+                qn = (q_noise[i] if q_noise is not None else None if q_noise_seed is None else
+                      self._device_randn(img.shape, q_noise_seed, noise_row0, step=i + 1, stream=0))
+                img = self._masked_blend(img, mask, x0, ts, qn)
             if random_guiding == 'sampled':
                 random_guider = torch.clamp(torch.randn(img.shape, device=img.device), -1., 1.)
             img, pred_x0 = self.p_sample_ddim(img, input_cond, ts, index=index, temperature=temperature, quantize_denoised=quantize_denoised,
@@ -310,6 +315,23 @@ class DDIMSampler(_SamplerBase):
         if int(v) != v or not lo <= int(v) <= hi:
             raise ValueError(f"{what}: {name} must be an integer in [{lo}, {hi}] for this schedule of {total} timesteps, got {v}")
         return int(v)
+
+    @staticmethod
+    def _inpaint_mask(mask, shape):
+        """A decode mask on the latent's device as the blend kernel reads it: fp32 [B, 1 | C, H, W] (a [1, ...] mask repeated over the batch)."""
+        B, C, H, W = (int(v) for v in shape)
+        m = torch.as_tensor(mask)
+        if m.ndim != 4 or m.shape[0] not in (1, B) or m.shape[1] not in (1, C) or tuple(m.shape[2:]) != (H, W):
+            raise ValueError(f"decode: mask must be [{B} | 1, 1 | {C}, {H}, {W}], got {tuple(m.shape)}")
+        return m.float().expand(B, -1, -1, -1).contiguous()
+
+    @torch.no_grad()
+    def keep_known(self, x, x0, mask):
+        """[native] x0 * mask + (1 - mask) * x on the blend kernel (sqrt_a = 1, sqrt_1ma = 0, no noise): what an inpainting call ends
+        with, so that the known region of its result is x0 itself wherever the mask is 1."""
+        x = x.to(self.model.device).float().contiguous()
+        return self.model.ctx.op_masked_blend(x, x0.to(x.device).float().contiguous(), self._inpaint_mask(mask, x.shape).to(x.device), None,
+                                              1.0, 0.0)
 
     def _level_scalars(self, a):
         """sqrt(a), sqrt(1 - a) in float64 from the fp32 alpha, as python floats (the native loops round them to fp32)."""
@@ -390,14 +412,25 @@ class DDIMSampler(_SamplerBase):
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None, use_original_steps=False,
                callback=None, img_callback=None, eta=None, temperature=1., noise=None, noise_seed=None, noise_row0=0, log_every_t=100,
-               return_intermediates=False, intermediates_to_cpu=False):
+               return_intermediates=False, intermediates_to_cpu=False, mask=None, x0=None, q_noise=None):
         """ldm decode: x_latent is taken to be at level index t_start - 1 and the DDIM step runs at indices t_start - 1 ... 0 --
         t_start forwards; t_start = the schedule's length is ddim_sampling from x_T = x_latent.  [native] eta (default: make_schedule's),
         temperature, noise (a [t_start, B, C, H, W] stack), noise_seed / noise_row0 (step i of this call takes the library's (seed,
         stream 1, step i)), log_every_t and return_intermediates ((x_dec, intermediates) instead of x_dec) as in sample().  A callback
-        takes the per-step path; otherwise the loop runs in the library (rdm_ddim_decode)."""
+        takes the per-step path; otherwise the loop runs in the library (rdm_ddim_decode).
+        mask / x0 / q_noise [native]: inpainting, as in sample() -- before every step the iterate becomes q_sample(x0, t) * mask +
+        (1 - mask) * img (mask [B | 1, 1 | C, H, W] in [0, 1], 1 = keep the known latent x0); the loop is the library's rdm_ddim_inpaint.
+        The known region's noise of step i is q_noise[i] (a [t_start, B, C, H, W] stack), with noise_seed the library's (seed, stream 0,
+        step i + 1) drawn in the blend kernel, else torch's.  The result of the last step is not blended (DESIGN.md section 3
+        "Inpainting")."""
         self._refuse_original_steps(use_original_steps)
         self._one_noise_source(noise_seed, noise)
+        if mask is None and (x0 is not None or q_noise is not None):
+            raise ValueError("decode: x0 / q_noise belong to an inpainting call: give a mask")
+        if mask is not None:
+            if x0 is None:
+                raise ValueError("decode: a mask needs x0, the known latent")
+            self._one_noise_source(noise_seed, q_noise, "q_noise stack")
         t_start = self._level_index("decode", "t_start", t_start, 1)
         if unconditional_guidance_scale < 1.:
             raise ValueError("decode: unconditional_guidance_scale must be >= 1")
@@ -411,14 +444,29 @@ class DDIMSampler(_SamplerBase):
             self.make_schedule(self.ddim_num_steps, ddim_eta=eta, verbose=False)
         img = x_latent.to(self.model.device)
         print(f"Running DDIM Sampling with {t_start} timesteps")
+        inpaint = {}
+        if mask is not None:
+            inpaint = dict(mask=self._inpaint_mask(mask, img.shape).to(img.device), x0=x0.to(img.device).float().contiguous(), q_noise=q_noise)
+            if tuple(inpaint["x0"].shape) != tuple(img.shape):
+                raise ValueError(f"decode: x0 must have the latent's shape {tuple(img.shape)}, got {tuple(x0.shape)}")
         if callback is not None or img_callback is not None:
+            if mask is not None:
+                inpaint["q_noise_seed"] = noise_seed
             z, inter = self._python_loop(cond, img, callback, img_callback, log_every_t, temperature, eta, unconditional_guidance_scale, uc,
                                          intermediates_to_cpu, noise=noise, noise_seed=noise_seed, noise_row0=noise_row0,
-                                         ts_all=self.ddim_timesteps[:t_start])
+                                         ts_all=self.ddim_timesteps[:t_start], **inpaint)
             return (z, inter) if return_intermediates else z
         seeded = {} if noise_seed is None else dict(seed=noise_seed, row0=noise_row0)
         if eta != 0. and noise is None and noise_seed is None:
             noise = torch.randn((t_start,) + tuple(img.shape), device=img.device)
+        if mask is not None:
+            if q_noise is None and noise_seed is None:
+                inpaint["q_noise"] = torch.randn((t_start,) + tuple(img.shape), device=img.device)
+            z, xi, pi = self.model.ctx.ddim_inpaint(self.ddim_num_steps, t_start, img, inpaint["x0"], inpaint["mask"], cond, uc,
+                                                    self.alphas_cumprod, eta=eta, scale=unconditional_guidance_scale, noise=noise,
+                                                    q_noise=inpaint["q_noise"], log_every_t=log_every_t, temperature=temperature,
+                                                    want_intermediates=return_intermediates, **seeded)
+            return (z.detach(), self._intermediates(img, xi, pi, intermediates_to_cpu)) if return_intermediates else z.detach()
         z, xi, pi = self.model.ctx.ddim_decode(self.ddim_num_steps, t_start, img, cond, uc, self.alphas_cumprod, eta=eta,
                                                scale=unconditional_guidance_scale, noise=noise, log_every_t=log_every_t,
                                                temperature=temperature, want_intermediates=return_intermediates, **seeded)

@@ -25,6 +25,53 @@ from .plms import PLMSSampler
 from .uni_pc import UniPCSampler
 
 
+# ---- [native] inpainting: the mask of sample_log / sample_with_query / sample_from_rdata, handled on the host before any GPU work
+def first_stage_factor(model):
+    """Image pixels per latent pixel along one axis: every level of the first stage but the last halves once."""
+    return 1 << (model.vq_cfg.n_ch_mult - 1)
+
+
+def check_inpaint_request(inpaint_mask, has_init, invert, other_sampler):
+    """What can be wrong with an inpainting request whatever the mask's shape: no init image to keep, inversion, a sampler whose
+    loop has no blend, values outside [0, 1]."""
+    if not has_init:
+        raise ValueError("inpaint_mask needs the image to keep: give init_image or init_latent (and a strength)")
+    if invert:
+        raise ValueError("inpainting starts from the noised init latent: invert does not combine with inpaint_mask")
+    if other_sampler:
+        raise ValueError("inpainting (inpaint_mask) runs on the DDIM sampler only: drop plms / dpm_solver / uni_pc / dpm_solver_sde "
+                         "and keep ddim=True")
+    m = torch.as_tensor(inpaint_mask)
+    if m.ndim not in (2, 3, 4) or m.numel() < 1:
+        raise ValueError(f"inpaint_mask must be [h, w] or [B | 1, 1, h, w] at latent resolution or [B | 1, H, W] at image resolution, "
+                         f"got {tuple(m.shape)}")
+    if not bool(((m >= 0) & (m <= 1)).all()):
+        raise ValueError("inpaint_mask must hold values in [0, 1] (1 = keep the init image, 0 = repaint)")
+
+
+def inpaint_mask_to_latent(inpaint_mask, latent_hw, factor, rows=None):
+    """An inpaint_mask in either form -> fp32 [B | 1, 1, h, w] on the host, (h, w) = latent_hw.  At latent resolution: [h, w] or
+    [B | 1, 1, h, w], taken as it is.  At image resolution: [B | 1, H, W] with (H, W) = (f h, f w), f = factor() the first stage's
+    (asked for only here), averaged over every f x f block in float64 -- the share of a latent pixel's image area that is kept.
+    rows: the batch the mask must hold one row, or one row per sample, of."""
+    h, w = (int(v) for v in latent_hw)
+    m = torch.as_tensor(inpaint_mask).detach().cpu().double()
+    if m.ndim == 2:
+        m = m[None, None]
+    elif m.ndim == 3:
+        f = int(factor())
+        if tuple(m.shape[1:]) != (f * h, f * w):
+            raise ValueError(f"inpaint_mask at image resolution must be [B | 1, {f * h}, {f * w}] ({f} x the latent's {h} x {w}), got {tuple(m.shape)}")
+        m = m.reshape(m.shape[0], h, f, w, f).mean(dim=(2, 4))[:, None]
+    if m.ndim != 4 or m.shape[1] != 1 or tuple(m.shape[2:]) != (h, w):
+        raise ValueError(f"inpaint_mask at latent resolution must be [{h}, {w}] or [B | 1, 1, {h}, {w}], got {tuple(torch.as_tensor(inpaint_mask).shape)}")
+    if rows is not None and m.shape[0] not in (1, int(rows)):
+        raise ValueError(f"inpaint_mask must hold one row or one per sample of the batch of {int(rows)}, got {m.shape[0]}")
+    if not bool(((m >= 0) & (m <= 1)).all()):
+        raise ValueError("inpaint_mask must hold values in [0, 1] (1 = keep the init image, 0 = repaint)")
+    return m.float().contiguous()
+
+
 class MinimalRETRODiffusion(object):
     def __init__(self, unet_config, first_stage_config=None, k_nn=4, timesteps=1000, linear_start=0.0015,
                  linear_end=0.0195, image_size=64, channels=3, scale_factor=1.0, clip_denoised=True, log_every_t=200,
@@ -211,6 +258,11 @@ class MinimalRETRODiffusion(object):
             if steps is not None and kwargs.get("noise") is None:      # per-step noise: [steps, b, C, H, W], row streams as above
                 nz = parallel.per_sample_noise(base + 1, range(lo, hi), (steps,) + shape, device=self.device)
                 kwargs["noise"] = nz.transpose(0, 1).contiguous()
+            if kwargs.get("inpaint_mask") is not None and kwargs.get("q_noise") is None:      # the known region's noise, one z per decode step
+                total = len(range(0, self.num_timesteps, self.num_timesteps // kwargs.get("S", kwargs.get("ddim_steps"))))
+                n = DDIMSampler.img2img_steps(kwargs["strength"], total)
+                qz = parallel.per_sample_noise(base + 2, range(lo, hi), (n,) + shape, device=self.device)
+                kwargs["q_noise"] = qz.transpose(0, 1).contiguous()
         with self.ema_scope("Plotting"):
             samples, _ = self.sample_log(cond=c, batch_size=hi - lo, unconditional_guidance_scale=scale,
                                          unconditional_conditioning=c_uncond, **kwargs)
@@ -410,12 +462,15 @@ class MinimalRETRODiffusion(object):
     # ---- samplers
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, dpm_solver=False,
-                   uni_pc=False, init_latent=None, strength=None, invert=False, invert_scale=1.0, dpm_solver_sde=False, **kwargs):
+                   uni_pc=False, init_latent=None, strength=None, invert=False, invert_scale=1.0, dpm_solver_sde=False, inpaint_mask=None,
+                   keep_known=True, **kwargs):
         """ddpm.py:988-1011.  [native] plms=True samples with PLMSSampler (ldm), dpm_solver=True with DPMSolverSampler (DPM-Solver++ 2M
         on the logSNR grid), uni_pc=True with UniPCSampler (UniPC order 2, bh2, with the corrector, on the logSNR grid),
         dpm_solver_sde=True with DPMSolverSDESampler (SDE-DPM-Solver++ 2M on the logSNR grid: fresh noise every step) on
         S = ddim_steps instead of DDIM / DDPM.  init_latent / strength / invert / invert_scale [native]: image-to-image, DDIM only
-        (_img2img)."""
+        (_img2img).  inpaint_mask / keep_known [native]: inpainting on top of image-to-image -- the mask (inpaint_mask_to_latent's
+        forms; 1 = keep init_latent, 0 = repaint) goes to DDIMSampler.decode with x0 = init_latent, and keep_known ends with one more
+        blend so that the returned latent IS init_latent where the mask is 1."""
         if plms and dpm_solver:
             raise ValueError("plms and dpm_solver select different samplers: give one of them")
         if uni_pc and (plms or dpm_solver):
@@ -424,11 +479,16 @@ class MinimalRETRODiffusion(object):
             raise ValueError(f"{'plms' if plms else 'dpm_solver' if dpm_solver else 'uni_pc'} and dpm_solver_sde select different samplers: "
                              "give one of them")
         shape = (self.channels, self.image_size, self.image_size) if custom_shape is None else self._latent_shape(custom_shape)
+        inpaint = {}
+        if inpaint_mask is not None:
+            check_inpaint_request(inpaint_mask, init_latent is not None, invert, plms or dpm_solver or uni_pc or dpm_solver_sde or not ddim)
+            inpaint = dict(inpaint_mask=inpaint_mask_to_latent(inpaint_mask, shape[1:], lambda: first_stage_factor(self), rows=batch_size),
+                           keep_known=keep_known)
         if init_latent is not None or strength is not None or invert:
             if plms or dpm_solver or uni_pc or dpm_solver_sde or not ddim:
                 raise ValueError("image-to-image (init_latent / strength / invert) runs on the DDIM sampler only: "
                                  "drop plms / dpm_solver / uni_pc" + (" / dpm_solver_sde" if dpm_solver_sde else "") + " and keep ddim=True")
-            return self._img2img(cond, batch_size, ddim_steps, shape, init_latent, strength, invert, invert_scale, **kwargs)
+            return self._img2img(cond, batch_size, ddim_steps, shape, init_latent, strength, invert, invert_scale, **inpaint, **kwargs)
         if ddim or plms or dpm_solver or uni_pc or dpm_solver_sde:
             sampler = (PLMSSampler(self) if plms else DPMSolverSampler(self) if dpm_solver else UniPCSampler(self) if uni_pc
                        else DPMSolverSDESampler(self) if dpm_solver_sde else DDIMSampler(self))
@@ -452,9 +512,14 @@ class MinimalRETRODiffusion(object):
             raise ValueError(f"init_latent must be {want} (the call's batch at its latent shape), got {tuple(init_latent.shape)}")
 
     @staticmethod
-    def _check_img2img_request(kwargs, init_image, init_latent, strength, invert):
+    def _check_img2img_request(kwargs, init_image, init_latent, strength, invert, inpaint_mask=None):
         """What can be wrong with the image-to-image arguments of sample_with_query / sample_from_rdata, before the retrieval and any
-        GPU work: one of init_image / init_latent, the DDIM sampler, strength in (0, 1], a channel-last image."""
+        GPU work: one of init_image / init_latent, the DDIM sampler, strength in (0, 1], a channel-last image; and an inpaint_mask
+        without an init image, with invert, or with another sampler."""
+        if inpaint_mask is not None:
+            check_inpaint_request(inpaint_mask, init_image is not None or init_latent is not None, invert,
+                                  kwargs.get("dpm_solver_sde", False) or any(kwargs.get(name, False) for name in ("plms", "dpm_solver", "uni_pc"))
+                                  or not kwargs.get("ddim", True))
         if init_image is None and init_latent is None:
             if invert:
                 raise ValueError("invert needs init_image or init_latent")
@@ -470,12 +535,17 @@ class MinimalRETRODiffusion(object):
             raise ValueError(f"init_image must be channel-last, [B,H,W,C] or [H,W,C] in [-1, 1], got {tuple(torch.as_tensor(init_image).shape)}")
 
     @torch.no_grad()
-    def _img2img_kwargs(self, kwargs, n_total, lo, hi, init_image, init_latent, strength, invert):
+    def _img2img_kwargs(self, kwargs, n_total, lo, hi, init_image, init_latent, strength, invert, inpaint_mask=None, keep_known=True):
         """The image-to-image keywords of sample_log for rows [lo, hi) of a global batch of n_total: init_image [n_total,H,W,C] (or one
         image, repeated) through encode_first_stage -> get_first_stage_encoding, or init_latent itself, checked against the call's
-        latent shape.  The rows are cut BEFORE the encoder runs, so a rank encodes its own images only."""
+        latent shape.  The rows are cut BEFORE the encoder runs, so a rank encodes its own images only.  inpaint_mask: brought to
+        latent resolution on the host (inpaint_mask_to_latent) and cut to the same rows, before the encoder runs too."""
         if init_image is None and init_latent is None:
             return
+        if inpaint_mask is not None:
+            m = inpaint_mask_to_latent(inpaint_mask, self._latent_shape(kwargs.get("custom_shape"))[1:], lambda: first_stage_factor(self),
+                                       rows=n_total)
+            kwargs.update(inpaint_mask=(m[lo:hi] if m.shape[0] == n_total else m).contiguous(), keep_known=keep_known)
         src = torch.as_tensor(init_image if init_image is not None else init_latent)
         if src.ndim == 3:
             src = src[None]
@@ -494,13 +564,19 @@ class MinimalRETRODiffusion(object):
     @torch.no_grad()
     def _img2img(self, cond, batch_size, ddim_steps, shape, init_latent, strength, invert, invert_scale, x_T=None, eta=0., noise=None,
                  noise_seed=None, noise_row0=0, unconditional_guidance_scale=1., unconditional_conditioning=None, log_every_t=100,
-                 temperature=1., callback=None, img_callback=None, intermediates_to_cpu=False, **kwargs):
+                 temperature=1., callback=None, img_callback=None, intermediates_to_cpu=False, inpaint_mask=None, keep_known=True,
+                 q_noise=None, **kwargs):
         """[native] DDIM image-to-image: with n = min(total, max(1, int(strength * total))) of the schedule's `total` timesteps, the
         start is init_latent noised to level index n - 1 (stochastic_encode; the noise is x_T when given, the library's seeded
         starting-latent normals with noise_seed, else torch's) or inverted n steps (invert: DDIMSampler.encode under the call's
         conditioning at invert_scale), then decode(t_start=n) at the call's guidance scale.  The noised level and the level the first
-        decode step assumes are the same one, so strength 1.0 runs the whole schedule.  -> (samples, intermediates) like sample()."""
+        decode step assumes are the same one, so strength 1.0 runs the whole schedule.  -> (samples, intermediates) like sample().
+        inpaint_mask (at latent resolution, [batch_size | 1, 1, h, w], 1 = keep): decode blends init_latent, noised to every step's
+        level, back in where the mask says so (q_noise: an explicit [n, B, C, H, W] stack for that noise; with noise_seed it is the
+        library's); keep_known: one more blend at sqrt_a = 1, sqrt_1ma = 0 puts init_latent itself there at the end."""
         self._check_img2img(init_latent, strength, batch_size, shape)
+        if inpaint_mask is not None and invert:
+            raise ValueError("inpainting starts from the noised init latent: invert does not combine with inpaint_mask")
         S = kwargs.pop('S', ddim_steps)
         per_step = [name for name in ("mask", "x0", "quantize_x0", "score_corrector", "content_cond", "style_cond", "timesteps", "noise_dropout")
                     if kwargs.get(name) is not None and not (isinstance(kwargs[name], (bool, int, float)) and not kwargs[name])]
@@ -516,11 +592,15 @@ class MinimalRETRODiffusion(object):
         else:
             start = sampler.stochastic_encode(init_latent, n - 1, noise=x_T, noise_seed=None if x_T is not None else noise_seed,
                                               noise_row0=noise_row0)
-        return sampler.decode(start, cond, n, unconditional_guidance_scale=unconditional_guidance_scale,
-                              unconditional_conditioning=unconditional_conditioning, callback=callback, img_callback=img_callback, eta=eta,
-                              temperature=temperature, noise=None if noise is None else noise[:n], noise_seed=noise_seed,
-                              noise_row0=noise_row0, log_every_t=log_every_t, return_intermediates=True,
-                              intermediates_to_cpu=intermediates_to_cpu)
+        inpaint = {} if inpaint_mask is None else dict(mask=inpaint_mask, x0=init_latent, q_noise=None if q_noise is None else q_noise[:n])
+        z, inter = sampler.decode(start, cond, n, unconditional_guidance_scale=unconditional_guidance_scale,
+                                  unconditional_conditioning=unconditional_conditioning, callback=callback, img_callback=img_callback, eta=eta,
+                                  temperature=temperature, noise=None if noise is None else noise[:n], noise_seed=noise_seed,
+                                  noise_row0=noise_row0, log_every_t=log_every_t, return_intermediates=True,
+                                  intermediates_to_cpu=intermediates_to_cpu, **inpaint)
+        if inpaint_mask is not None and keep_known:
+            z = sampler.keep_known(z, init_latent, inpaint_mask)
+        return z, inter
 
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, timesteps=None, noise=None,
@@ -569,18 +649,23 @@ class MinimalRETRODiffusion(object):
     def sample_with_query(self, query, cond=None, bs=None, k_nn=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, return_nns=False,
                           n_reps=None, query_embedded=False, example_maps=None, visualize_nns=True, omit_query=False,
-                          normalize=False, device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False, **kwargs):
+                          normalize=False, device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False,
+                          inpaint_mask=None, keep_known=True, **kwargs):
         """ddpm.py:689-844 (nn_encoder is None, retrieval_encoder = Identity — every shipped config).  device_noise [native]: the
         starting latents and the per-step noise (DDIM eta > 0, DDPM) are the library's counter-based generator's, a function of (the
         call's shared seed, GLOBAL row) generated inside the step kernels (_sample_shard) -- no noise tensor is drawn in Python.
         init_image / init_latent / strength / invert [native]: image-to-image on the DDIM sampler (sample_log) -- init_image
         [B,H,W,C] in [-1,1] (or one image [H,W,C], repeated) goes through encode_first_stage -> get_first_stage_encoding, init_latent
         is that latent itself; the start is the latent noised by `strength` (with device_noise: row r's noise depends on (the shared
-        seed, r) only) or, with invert, its DDIM inversion under the retrieved conditioning."""
+        seed, r) only) or, with invert, its DDIM inversion under the retrieved conditioning.
+        inpaint_mask / keep_known [native]: repaint a region of the init image under the retrieved neighbours and keep the rest --
+        inpaint_mask at latent resolution ([B | 1, 1, h, w] or [h, w]) or at image resolution ([B | 1, H, W], area-averaged down by the
+        first stage's factor on the host), float in [0, 1], 1 = KEEP the init image (ldm's convention), 0 = repaint; it is cut to a
+        rank's rows like the init image.  keep_known: the known region of the result is the encoded init image exactly."""
         if cond is not None or return_nns:
             raise NotImplementedError("cond (a second conditioning) / return_nns (neighbour image grids) are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))      # a bad custom_shape fails here, not after the retrieval
-        self._check_img2img_request(kwargs, init_image, init_latent, strength, invert)
+        self._check_img2img_request(kwargs, init_image, init_latent, strength, invert, *(() if inpaint_mask is None else (inpaint_mask,)))
         # (the reference asserts `query.ndim` first, which makes its own `isinstance(query, str)` branch unreachable: a caption only
         #  works pre-embedded there, scripts/rdm_sample.py:275-277; here str / list-of-str queries take the CLIP text tower)
         if not query_embedded and not isinstance(query, (str, list)):
@@ -606,7 +691,8 @@ class MinimalRETRODiffusion(object):
             k_nn = self.k_nn
         n_total = len(query)
         lo, hi = self._shard(n_total) if self.distributed else (0, n_total)
-        self._img2img_kwargs(kwargs, n_total, lo, hi, init_image, init_latent, strength, invert)
+        self._img2img_kwargs(kwargs, n_total, lo, hi, init_image, init_latent, strength, invert,
+                             *(() if inpaint_mask is None else (inpaint_mask, keep_known)))
         shard_db = self.distributed and getattr(self, "shard_db", False)
         if self.distributed and not shard_db:
             query = query[lo:hi]            # every rank retrieves for its own rows only (the database is replicated)
@@ -675,13 +761,14 @@ class MinimalRETRODiffusion(object):
     def sample_from_rdata(self, N, cond=None, return_nns=False, use_weights=False, qids=None, k_nn=None, memsize=100,
                           verbose=False, pre_loaded_patches=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, nn_embeddings=None,
-                          device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False, **kwargs):
+                          device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False, inpaint_mask=None,
+                          keep_known=True, **kwargs):
         """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921).  device_noise, init_image /
-        init_latent / strength / invert [native]: as in sample_with_query."""
+        init_latent / strength / invert, inpaint_mask / keep_known [native]: as in sample_with_query."""
         if cond is not None or return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("cond / return_nns / pre_loaded_patches are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))
-        self._check_img2img_request(kwargs, init_image, init_latent, strength, invert)
+        self._check_img2img_request(kwargs, init_image, init_latent, strength, invert, *(() if inpaint_mask is None else (inpaint_mask,)))
         self._sync_retriever_sharding()
         if self.retriever.searcher is None:
             self.train_searcher()
@@ -689,7 +776,8 @@ class MinimalRETRODiffusion(object):
             k_nn = self.k_nn
         qids = self.get_qids(memsize, N, qids=qids, use_weights=use_weights, verbose=verbose)   # rank 0's draw on every rank (get_qids)
         lo, hi = self._shard(N) if self.distributed else (0, N)
-        self._img2img_kwargs(kwargs, N, lo, hi, init_image, init_latent, strength, invert)
+        self._img2img_kwargs(kwargs, N, lo, hi, init_image, init_latent, strength, invert,
+                             *(() if inpaint_mask is None else (inpaint_mask, keep_known)))
         shard_db = self.distributed and getattr(self, "shard_db", False) and nn_embeddings is None
         if self.distributed:
             if not shard_db:

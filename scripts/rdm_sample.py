@@ -33,7 +33,10 @@ index): no noise tensor is drawn or stacked in Python, and the images differ fro
 `--gpus N` with the same sharding invariance), `--init_img PATH_OR_DIR` / `--strength S` / `--invert` (image-to-image on DDIM: the image,
 resized to the model's size or `--height` / `--width`, is encoded by the first stage and either noised to `int(S x steps)` steps up the
 schedule or, with `--invert`, taken there by deterministic DDIM inversion, then decoded under the retrieved neighbours; strength 1.0 runs
-every step; works with `--gpus N` and `--device_noise`; not with `--plms` / `--dpm_solver` / `--uni_pc` / `--dpm_solver_sde`).
+every step; works with `--gpus N` and `--device_noise`; not with `--plms` / `--dpm_solver` / `--uni_pc` / `--dpm_solver_sde`),
+`--mask PNG` (inpainting, with `--init_img`: a grey image, WHITE = REPAINT, resized to the call's size; the white region is sampled
+anew under the retrieved neighbours and the black region keeps the init image -- in the native DDIM loop, so it works with `--strength`,
+`--eta`, `--device_noise` and `--gpus N`; not with `--invert` or the multistep samplers).
 """
 import argparse
 import datetime
@@ -99,6 +102,9 @@ def build_parser() -> argparse.ArgumentParser:
                         help="[native] with --init_img: how far up the schedule the image is taken, in (0, 1]; 1.0 runs every step")
     parser.add_argument("--invert", default=False, action="store_true",
                         help="[native] with --init_img: start from the image's deterministic DDIM inversion instead of noising it")
+    parser.add_argument("--mask", type=Path, default=None,
+                        help="[native] with --init_img: inpainting -- a grey PNG, white = repaint, black = keep the init image; DDIM only, "
+                        "not with --invert")
     return parser
 
 
@@ -120,6 +126,11 @@ def parse_args(argv=None) -> argparse.Namespace:
             parser.error(f"--strength must lie in (0, 1], got {opt.strength}")
     elif opt.invert:
         parser.error("--invert needs --init_img")
+    if opt.mask is not None:
+        if opt.init_img is None:
+            parser.error("--mask needs --init_img (the image whose black-masked region is kept)")
+        if opt.invert:
+            parser.error("--mask starts from the noised image: drop --invert")
     if opt.top_m > 1.0:
         opt.top_m = int(opt.top_m)          # top_m should be int if a fixed number of images is given (:138-140)
     if opt.seed is not None and (not opt.increase_guidance) and opt.n_runs > 1:
@@ -247,7 +258,20 @@ def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
         kw.update(init_image=load_init_images(opt, model, kw.get("custom_shape")), strength=opt.strength)
         if opt.invert:
             kw["invert"] = True
+    if getattr(opt, "mask", None) is not None:
+        kw["inpaint_mask"] = load_inpaint_mask(opt, model, kw.get("custom_shape"))
     return kw
+
+
+def load_inpaint_mask(opt: argparse.Namespace, model, custom_shape=None):
+    """--mask: the grey PNG at the call's size in pixels (resized like the init image), WHITE = REPAINT -> f32 [1, H, W] in [0, 1] with
+    1 = keep, the convention of sample_with_query's inpaint_mask: 1 - mask / 255.  The model averages it down to latent pixels."""
+    import torch
+    from PIL import Image
+    f = 1 << (model.vq_cfg.n_ch_mult - 1)
+    _, h, w = custom_shape if custom_shape is not None else (model.channels, model.image_size, model.image_size)
+    grey = Image.open(opt.mask).convert("L").resize((w * f, h * f), Image.BILINEAR)
+    return (1.0 - torch.from_numpy(np.asarray(grey, dtype=np.float32)) / 255.0)[None].contiguous()
 
 
 def load_init_images(opt: argparse.Namespace, model, custom_shape=None):

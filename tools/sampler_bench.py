@@ -11,11 +11,15 @@ whose step kernels generate the noise (no x_T, no stack); dpmpp_sde:S is SDE-DPM
 timed calls.  Image-to-image: img2img:S:STRENGTH encodes a [B, 3, 256, 256] image batch with the first-stage encoder, noises the latent to
 n = min(total, max(1, int(STRENGTH * total))) steps up the S-step schedule with the seeded forward process (no noise tensor) and runs
 the native decode from there -- n forwards; invert:S:STRENGTH takes the latent there by n steps of native DDIM inversion (unguided)
-instead -- 2 n forwards.  The encoder's own ms per image is reported under "vq_encode_ms_per_image".  A spec given twice is timed twice (the second under `name:S#2`): the box's own A/A spread.  Prints the box's calibration
+instead -- 2 n forwards; inpaint:S:STRENGTH is img2img with a centred square mask (the middle quarter of the latent is repainted, the
+rest kept): the native inpainting loop through its seeded entry -- n forwards and n blend passes whose known-region noise is generated
+in the blend kernel, then the keep-known blend; inpaint_stack:S:STRENGTH is the same loop fed with an [n, B, 3, 64, 64] torch.randn
+stack for that noise, drawn per call as DDIMSampler.decode draws it without a seed.  The encoder's own ms per image is reported under "vq_encode_ms_per_image".  A spec given twice is timed twice (the second under `name:S#2`): the box's own A/A spread.  Prints the box's calibration
 probe and one line per run on stderr, one JSON line on stdout.
 
     python tools/sampler_bench.py [--reps N] [--batch B] [ddim:50 plms:50 plms:25 dpmpp:20 ddpm:250 ddpm:250 ddpm_rng:250 ...]
     python tools/sampler_bench.py ddim:50 ddim:50 img2img:50:0.6 invert:50:0.6
+    python tools/sampler_bench.py ddim:50 img2img:50:0.6 img2img:50:0.6 inpaint:50:0.6 inpaint_stack:50:0.6
 """
 import argparse
 import json
@@ -45,7 +49,8 @@ def main():
     model = MinimalRETRODiffusion(unet_config={"params": {}}, first_stage_config={"params": {"ddconfig": {}}}, k_nn=4, ctx=ctx)
     model.load_unet_state_dict(synthetic.unet_state_dict(model.unet_cfg))
     fsd = synthetic.vq_state_dict(model.vq_cfg)
-    from_image = any(run.split(":")[0] in ("img2img", "invert") for run in a.runs)
+    FROM_IMAGE = ("img2img", "invert", "inpaint", "inpaint_stack")
+    from_image = any(run.split(":")[0] in FROM_IMAGE for run in a.runs)
     if from_image:
         fsd.update(synthetic.vq_encoder_state_dict(model.vq_cfg))
     model.load_first_stage_state_dict(fsd)
@@ -55,6 +60,8 @@ def main():
     cond = torch.randn(B, 4, 512, device=d, generator=g) * 0.45
     uncond = torch.zeros_like(cond)
     image = torch.rand(B, 3, 256, 256, device=d, generator=g) * 2 - 1 if from_image else None
+    keep = torch.ones(B, 1, 64, 64, device=d)               # 1 = keep the init latent; the centred 32 x 32 square is repainted
+    keep[:, :, 16:48, 16:48] = 0.0
 
     def steps_of(S, strength):
         total = len(range(0, model.num_timesteps, model.num_timesteps // S))
@@ -72,7 +79,7 @@ def main():
         return x, nz.transpose(0, 1).contiguous()
 
     def sample(name, S, strength=None):
-        if name in ("img2img", "invert"):
+        if name in FROM_IMAGE:
             import numpy as np
             calls[0] += 1
             n, total = steps_of(S, strength)
@@ -81,8 +88,16 @@ def main():
                 start, _ = ctx.ddim_encode(S, n, lat, cond, None, model.alphas_cumprod)
             else:
                 a_n = float(model.alphas_cumprod[range(0, model.num_timesteps, model.num_timesteps // S)[n - 1] + 1])
-                start = ctx.op_q_sample_seeded(lat, np.sqrt(a_n), np.sqrt(1.0 - a_n), 1000 + calls[0], out=lat)
-            z, _, _ = ctx.ddim_decode(S, n, start, cond, uncond, model.alphas_cumprod, eta=0.0, scale=2.0)
+                start = ctx.op_q_sample_seeded(lat, np.sqrt(a_n), np.sqrt(1.0 - a_n), 1000 + calls[0], out=None if "inpaint" in name else lat)
+            if name == "inpaint":
+                z, _, _ = ctx.ddim_inpaint(S, n, start, lat, keep, cond, uncond, model.alphas_cumprod, eta=0.0, scale=2.0, seed=1000 + calls[0])
+            elif name == "inpaint_stack":
+                z, _, _ = ctx.ddim_inpaint(S, n, start, lat, keep, cond, uncond, model.alphas_cumprod, eta=0.0, scale=2.0,
+                                           q_noise=torch.randn((n,) + tuple(lat.shape), device=d))
+            else:
+                z, _, _ = ctx.ddim_decode(S, n, start, cond, uncond, model.alphas_cumprod, eta=0.0, scale=2.0)
+            if "inpaint" in name:
+                ctx.op_masked_blend(z, lat, keep, None, 1.0, 0.0, out=z)
         elif name == "ddimeta":
             x, nz = stack(S)
             z, _, _ = ctx.ddim_sample(S, x, cond, uncond, model.alphas_cumprod, eta=1.0, scale=2.0, noise=nz)
@@ -109,11 +124,11 @@ def main():
             z, _, _ = ctx.unipc_sample(ctx.dpmpp_timesteps(S, model.alphas_cumprod), x_T, cond, uncond, model.alphas_cumprod, scale=2.0)
         else:
             raise SystemExit(f"unknown sampler {name!r} (ddim | plms | dpmpp | dpmpp_sde | unipc | ddimeta | ddimeta_rng | ddpm | ddpm_rng | "
-                             "img2img:S:STRENGTH | invert:S:STRENGTH)")
+                             "img2img:S:STRENGTH | invert:S:STRENGTH | inpaint:S:STRENGTH | inpaint_stack:S:STRENGTH)")
         return ctx.vq_decode(z)
 
     def forwards(name, S, strength=None):
-        if name in ("img2img", "invert"):
+        if name in FROM_IMAGE:
             return steps_of(S, strength)[0] * (2 if name == "invert" else 1)
         if name in ("dpmpp", "dpmpp_sde", "unipc"):
             return len(ctx.dpmpp_timesteps(S, model.alphas_cumprod)) - 1
@@ -126,8 +141,8 @@ def main():
     for n_run, run in enumerate(a.runs):
         name, S, *rest = run.split(":")
         S = int(S)
-        if (name in ("img2img", "invert")) != (len(rest) == 1):
-            raise SystemExit(f"{run!r}: img2img and invert take name:S:STRENGTH, the other samplers name:S")
+        if (name in FROM_IMAGE) != (len(rest) == 1):
+            raise SystemExit(f"{run!r}: img2img, invert, inpaint and inpaint_stack take name:S:STRENGTH, the other samplers name:S")
         strength = float(rest[0]) if rest else None
         if strength is not None and not 0.0 < strength <= 1.0:
             raise SystemExit(f"{run!r}: STRENGTH must lie in (0, 1]")
