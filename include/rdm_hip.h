@@ -473,6 +473,32 @@ int rdm_knn_last_fallback(rdm_ctx* ctx);
 /* data_pool['embedding'][nns] gather (dsetbuilder.py:493): idx [dev] uint32 [n_idx] -> out [dev] f32 [n_idx,dim]
  * of the RAW (un-normalised) embeddings (rdm_db_load keeps a raw copy in HBM next to the normalised one). */
 int rdm_db_gather(rdm_ctx* ctx, const uint32_t* idx, long long n_idx, float* out);
+/* Read-outs of the search for the tests (tests/test_knn_cpu.py, tests/test_gpu_knn_stages.py).
+ * rdm_knn_select: what rdm_knn does for a database of n rows x dim, b queries and k neighbours; host only, no device.  path: which scan
+ *   scores the database -- GENERIC (any dim, both fp16 words of the query), D512 (dim 512, hi word only) or BULK (b >= 128 and at
+ *   least 16 tiles of 256 rows: 128-query walkers, hi word only).  ksel: entries per lane list; rescored: merged candidates re-scored
+ *   exactly (>= k); lists_per_block: lists per query a scan block (BULK: a walker) writes; queries_per_launch: 64, BULK 512;
+ *   eps: the bound on |approximate - exact| score the certificate runs with, a function of path and dim (csrc/knn.hip).
+ *   Returns -1 for arguments rdm_db_load / rdm_knn refuse.  The search takes path and eps from this very function.
+ * rdm_op_knn_stages: rdm_knn for ONE query group (b <= 64, or a BULK launch of 128 <= b <= 512) through the same launches, copying
+ *   out every stage.  The caller sets the capacities and the [dev] pointers (any may be NULL); rows = query rows prepared (64, BULK
+ *   128 per group), nlists = lists per query.  qn f32 / qh, ql fp16 [rows, dim] (rows b.. are padding); cand_s f32 / cand_i uint32
+ *   [rows, nlists, ksel], each list by (score desc, index asc), empty slots (-inf, 0xffffffff); per query [b] the merge's verdict
+ *   BEFORE the exact fallback: flag (1 = not certified), tau / tau_idx (k-th exact score and its row among the re-scored
+ *   candidates), theta (largest approximate score of anything dropped); certified iff theta + eps < tau.
+ * rdm_db_rows: the normalised database rows [row0, row0 + rows) as fp16 [rows, dim] into out [dev]. */
+enum { RDM_KNN_SCAN_GENERIC = 1, RDM_KNN_SCAN_D512 = 2, RDM_KNN_SCAN_BULK = 3 };
+typedef struct rdm_knn_form { int path, ksel, rescored, lists_per_block, queries_per_launch; float eps; } rdm_knn_form;
+typedef struct rdm_knn_stages {
+    int rows_cap, nlists_cap;                       /* in: query rows / lists per query the arrays below hold */
+    float* qn; void* qh; void* ql;
+    float* cand_s; uint32_t* cand_i;
+    int* flag; double* tau; uint32_t* tau_idx; float* theta;
+    int rows, nlists; rdm_knn_form form;            /* out */
+} rdm_knn_stages;
+int rdm_knn_select(long long n, int dim, int b, int k, rdm_knn_form* form_out);
+int rdm_op_knn_stages(rdm_ctx* ctx, const float* q, int b, int k, uint32_t* idx_out, float* score_out, rdm_knn_stages* stages);
+int rdm_db_rows(rdm_ctx* ctx, long long row0, long long rows, void* out_f16);
 
 /* ---- multi-GPU: one process and one context per device; the path has ONE exchange, an all-gather -- of the
  * decoded images (replicated database) or of the per-shard (index, score) top-k pairs (row-sharded database).  Thin wrappers

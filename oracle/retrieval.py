@@ -19,6 +19,9 @@ dsetbuilder.py:590-592).  Definition used by oracle and HIP path alike:
   * query          q^  = q / fp32( sqrt( sum_j q_j^2 in fp64 ) )   (division in fp32)
   * score          s_i = sum_j q^_j * d_ij       (exact products, fp64 accumulation)
   * result         top-k by (score descending, index ascending)
+  * zero norm      a database row of norm zero is stored as zeros (it scores 0 against every query; normalize_db itself divides
+                   0 by 0).  A QUERY of norm zero has no direction and no cosine: normalize_queries gives NaN, and the HIP path
+                   refuses the search with an RdmError that names the query ("query 3 has zero norm") instead of ranking NaNs.
 """
 import numpy as np
 

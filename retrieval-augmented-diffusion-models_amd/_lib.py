@@ -99,6 +99,20 @@ class DdpmArgs(C.Structure):
                 ("posterior_log_variance_clipped", C.POINTER(C.c_float))]
 
 
+KNN_SCAN_PATHS = (None, "generic", "d512", "bulk")      # rdm_knn_form.path (RDM_KNN_SCAN_*)
+
+
+class KnnForm(C.Structure):
+    _fields_ = [("path", C.c_int), ("ksel", C.c_int), ("rescored", C.c_int), ("lists_per_block", C.c_int), ("queries_per_launch", C.c_int),
+                ("eps", C.c_float)]
+
+
+class KnnStages(C.Structure):
+    _fields_ = [("rows_cap", C.c_int), ("nlists_cap", C.c_int), ("qn", C.c_void_p), ("qh", C.c_void_p), ("ql", C.c_void_p),
+                ("cand_s", C.c_void_p), ("cand_i", C.c_void_p), ("flag", C.c_void_p), ("tau", C.c_void_p), ("tau_idx", C.c_void_p),
+                ("theta", C.c_void_p), ("rows", C.c_int), ("nlists", C.c_int), ("form", KnnForm)]
+
+
 _P = C.c_void_p
 # name -> (restype, argtypes); exactly the symbols include/rdm_hip.h declares
 SIGNATURES = {
@@ -166,6 +180,9 @@ SIGNATURES = {
     "rdm_knn_f64": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_knn_last_fallback": (C.c_int, [_P]),
     "rdm_db_gather": (C.c_int, [_P, _P, C.c_longlong, _P]),
+    "rdm_knn_select": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(KnnForm)]),
+    "rdm_op_knn_stages": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(KnnStages)]),
+    "rdm_db_rows": (C.c_int, [_P, C.c_longlong, C.c_longlong, _P]),
     "rdm_set_deterministic": (C.c_int, [_P, C.c_int]),
     "rdm_get_deterministic": (C.c_int, [_P]),
     "rdm_prof_enable": (C.c_int, [_P, C.c_int]),
@@ -317,6 +334,16 @@ def wgrad_select(*shape):
     if rc != 0:
         raise RdmError(f"rdm_wgrad_select{shape} failed ({rc})")
     return (WGRAD_PATHS[f.path], f.Z, f.per_plane, f.remap)
+
+
+def knn_select(n, dim, b, k):
+    """What Context.knn does for a database of n rows x dim, b queries, k neighbours (host only, no device): a dict with path (one of
+    KNN_SCAN_PATHS), ksel, rescored, lists_per_block, queries_per_launch and eps, the score-error bound of the certificate."""
+    f = KnnForm()
+    if lib.rdm_knn_select(int(n), int(dim), int(b), int(k), C.byref(f)) != 0:
+        raise RdmError(f"rdm_knn_select(n={n}, dim={dim}, b={b}, k={k}): arguments the search refuses")
+    return {"path": KNN_SCAN_PATHS[f.path], "ksel": f.ksel, "rescored": f.rescored, "lists_per_block": f.lists_per_block,
+            "queries_per_launch": f.queries_per_launch, "eps": float(f.eps)}
 
 
 def _ptr(t):
@@ -1339,10 +1366,12 @@ class Context:
             emb = emb.contiguous()
             dt = {torch.float16: 0, torch.float32: 1}[emb.dtype]
             self._check(lib.rdm_db_load(self._h, _ptr(emb), emb.shape[0], emb.shape[1], dt, 1))
+            self._db_dim = int(emb.shape[1])
         else:
             emb = np.ascontiguousarray(emb.numpy() if isinstance(emb, torch.Tensor) else emb)
             dt = {np.dtype(np.float16): 0, np.dtype(np.float32): 1}[emb.dtype]
             self._check(lib.rdm_db_load(self._h, emb.ctypes.data_as(_P), emb.shape[0], emb.shape[1], dt, 0))
+            self._db_dim = int(emb.shape[1])
 
     def db_size(self):
         return int(lib.rdm_db_size(self._h))
@@ -1360,6 +1389,47 @@ class Context:
 
     def knn_last_fallback(self):
         return int(lib.rdm_knn_last_fallback(self._h))
+
+    def knn_stages(self, q, k):
+        """Context.knn for ONE query group (b <= 64, or 128 <= b <= 512 on the bulk path) with every stage copied out (rdm_op_knn_stages):
+        a dict with idx, score (the final answer), qn f32 / qh, ql fp16 [rows, dim] (rows b.. are padding), cand_s f32 / cand_i int32
+        holding uint32 bits [rows, nlists, ksel], and per query the merge's flag, tau, tau_idx, theta BEFORE the exact fallback, plus the
+        fields of knn_select."""
+        q = self._dev(q, torch.float32)
+        if q.ndim != 2:
+            raise RdmError(f"knn_stages: queries must be [b,dim], got {tuple(q.shape)}")
+        b, dim = q.shape
+        n = self.db_size()
+        form = knn_select(n, dim, b, k)
+        rows = form["queries_per_launch"]
+        ntiles = (n + 255) // 256
+        cap = 8 * min(ntiles, torch.cuda.get_device_properties(self.device).multi_processor_count)
+        dv = self.device
+        t = {"idx": torch.empty((b, k), device=dv, dtype=torch.int32), "score": torch.empty((b, k), device=dv, dtype=torch.float32),
+             "qn": torch.zeros((rows, dim), device=dv, dtype=torch.float32), "qh": torch.zeros((rows, dim), device=dv, dtype=torch.float16),
+             "ql": torch.zeros((rows, dim), device=dv, dtype=torch.float16),
+             "cand_s": torch.zeros(rows * cap * form["ksel"], device=dv, dtype=torch.float32),
+             "cand_i": torch.zeros(rows * cap * form["ksel"], device=dv, dtype=torch.int32),
+             "flag": torch.zeros(b, device=dv, dtype=torch.int32), "tau": torch.zeros(b, device=dv, dtype=torch.float64),
+             "tau_idx": torch.zeros(b, device=dv, dtype=torch.int32), "theta": torch.zeros(b, device=dv, dtype=torch.float32)}
+        st = KnnStages(rows_cap=rows, nlists_cap=cap)
+        for name in ("qn", "qh", "ql", "cand_s", "cand_i", "flag", "tau", "tau_idx", "theta"):
+            setattr(st, name, t[name].data_ptr())
+        self._check(lib.rdm_op_knn_stages(self._h, _ptr(q), b, k, _ptr(t["idx"]), _ptr(t["score"]), C.byref(st)))
+        used = st.rows * st.nlists * st.form.ksel
+        for name in ("qn", "qh", "ql"):
+            t[name] = t[name][:st.rows]
+        for name in ("cand_s", "cand_i"):
+            t[name] = t[name][:used].reshape(st.rows, st.nlists, st.form.ksel)
+        t.update(form)
+        return t
+
+    def db_rows(self, row0, rows):
+        """-> fp16 [rows, dim]: the normalised database rows [row0, row0 + rows) the search scores (rdm_db_rows)."""
+        dim = self._db_dim
+        out = torch.empty((rows, dim), device=self.device, dtype=torch.float16)
+        self._check(lib.rdm_db_rows(self._h, int(row0), int(rows), _ptr(out)))
+        return out
 
     def db_gather(self, idx, dim):
         idx = idx.contiguous()

@@ -72,7 +72,7 @@ int rdm_db_load(rdm_ctx* c, const void* emb, long long n, int dim, int dtype, in
     return msg ? c->fail(-5, "rdm_db_load: %s", msg) : 0;
 }
 long long rdm_db_size(rdm_ctx* c) { return c ? c->db.n : -1; }
-static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out) {
+static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out, rdm_knn_stages* stages = nullptr) {
     RDM_ENTER(c);
     if (!c || !q || !idx_out) return c ? c->fail(-1, "null argument") : -1;
     const bool prof = (c->prof >> RDM_PROF_KNN) & 1u;
@@ -82,13 +82,28 @@ static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out
         r.tag = "knn"; r.d0 = b; r.d1 = k; r.d2 = c->db.dim;
         hipEventRecord(r.a, c->stream); c->prof_recs.push_back(r);
     }
-    const char* msg = knn_search(c->db, q, b, k, idx_out, score_out, score64_out, c->stream);
+    const char* msg = knn_search(c->db, q, b, k, idx_out, score_out, score64_out, c->stream, stages);
     if (prof) hipEventRecord(c->prof_recs.back().b, c->stream);
     return msg ? c->fail(-5, "rdm_knn: %s", msg) : 0;
 }
 int rdm_knn(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out) { return knn_entry(c, q, b, k, idx_out, score_out, nullptr); }
 int rdm_knn_f64(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, double* score_out) { return knn_entry(c, q, b, k, idx_out, nullptr, score_out); }
 int rdm_knn_last_fallback(rdm_ctx* c) { return c ? c->db.last_fallbacks : -1; }
+int rdm_knn_select(long long n, int dim, int b, int k, rdm_knn_form* out) {
+    if (!out) return -1;
+    *out = rdm_knn_form{};
+    return knn_select(n, dim, b, k, out) ? -1 : 0;
+}
+int rdm_op_knn_stages(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, rdm_knn_stages* stages) {
+    if (c && !stages) return c->fail(-1, "rdm_op_knn_stages: null argument");
+    return knn_entry(c, q, b, k, idx_out, score_out, nullptr, stages);
+}
+int rdm_db_rows(rdm_ctx* c, long long row0, long long rows, void* out_f16) {
+    RDM_ENTER(c);
+    if (!out_f16) return c->fail(-1, "rdm_db_rows: null argument");
+    const char* msg = knn_rows(c->db, row0, rows, out_f16, c->stream);
+    return msg ? c->fail(-5, "rdm_db_rows: %s", msg) : 0;
+}
 int rdm_db_gather(rdm_ctx* c, const uint32_t* idx, long long n_idx, float* out) {
     RDM_ENTER(c);
     if (!c || !idx || !out) return -1;

@@ -13,12 +13,22 @@
 //   merge kernel  per query: thread-local top-KSEL over all lane lists -> LDS bitonic sort ->
 //                 the best 2*KSEL candidates are re-scored EXACTLY (fp64 accumulation of exact
 //                 products, the oracle's definition) and sorted by (score desc, index asc).
-// Exactness is a GUARANTEE, not a likelihood.  The approximate score differs from the exact one by at most KNN_EPS
-// (fp32 accumulation of 1024 exact f16 x f16 products with partial sums <= 1: <= 1024 * 2^-24 = 6.1e-5 when each step rounds
-// to nearest, doubled for an unknown rounding mode inside the MFMA, plus <= 7e-7 for the subnormal tail of the lo word).  Every
-// row that is dropped anywhere (lane list, merge-thread list, the cut after the best 2*KSEL) has an approximate score <= theta,
+// Exactness is a GUARANTEE, not a likelihood.  The approximate score differs from the exact one by at most eps = knn_eps(path, dim)
+// (below; tests/_knn_ref.py eps_bound restates it term by term and the CPU suite holds eps >= eps_bound for every path and dim):
+//   accumulation   fp32 accumulation of P exact f16 x f16 products with partial sums <= 1 (unit vectors): <= P * 2^-24 when each
+//                  step rounds to nearest, doubled for an unknown rounding mode and order inside the MFMA.  P = 2 dim for the
+//                  hi + lo scan, dim for the hi-word scans: dim * 2^-22 resp. dim * 2^-23 (512: 1.22e-4 / 6.1e-5; 4096: 9.8e-4 / 4.9e-4).
+//   hi-word scans  fp16 has unit roundoff 2^-11: |q^_j - hi_j| <= 2^-11 |q^_j| moves a score by <= 2^-11 sum |q^_j d_j| <= 2^-11
+//                  = 4.88e-4 (a 512-d query with 247 equal entries against the row fp16(q^) reaches 4.69e-4).
+//   hi + lo scan   what hi + lo leaves of q^: <= 2^-25 per element where the lo word is an fp16 subnormal (absolute spacing 2^-24),
+//                  sum_j 2^-25 |d_j| <= sqrt(dim) 2^-25; <= 2^-11 |lo_j| <= 2^-22 |q^_j| where it is normal, in sum <= 2^-22.
+//                  This holds only if the f16 MFMA honours subnormal INPUTS (lo words of the 247-entry query are all subnormal):
+//                  it does -- tests/test_gpu_knn_stages.py holds that case to the accumulation term on the device (4.2e-7 measured
+//                  at dim 256 where a flush would show 4.7e-4; tests/_knn_ref.py MEASURED).
+//   both           the same sqrt(dim) 2^-25 for hi words below 2^-14 (kept in the library's eps for the hi-word scans too).
+// Every row that is dropped anywhere (lane list, merge-thread list, the cut after the re-scored prefix) has an approximate score <= theta,
 // the maximum of the full lane lists' tails, the scores the merge threads rejected and the first score after the cut.  If
-// theta + KNN_EPS < tau (the k-th EXACT score among the re-scored candidates) no dropped row can belong to the top k and the result
+// theta + eps < tau (the k-th EXACT score among the re-scored candidates) no dropped row can belong to the top k and the result
 // is certified.  Otherwise (a cluster of near-duplicates around the k-th score -- real in OpenImages patches) the query is
 // flagged and an exact pass streams the database once more in fp64, collecting every row that beats the current k-th candidate
 // under the total order (score desc, index asc); the top k of those is the answer.  Unflagged batches pay three empty launches.
@@ -34,8 +44,6 @@
 #define KNN_QMAX 512           // queries per launch of the bulk scan (4 groups of 128): size of the per-query scratch arrays
 #define KNN_BK 64              // K slice per stage
 
-constexpr float KNN_EPS = 2.0e-4f;   // bound on |approximate - exact| score (derivation above)
-constexpr float KNN_EPS_BULK = 5.0e-4f;   // bulk scan: hi word of the query only (+ 2^-12 sum |q_j d_j| <= 2.4e-4)
 constexpr int KNN_FB_CAP = 8192;      // exact-fallback candidates kept per query
 struct Cand { float s; uint32_t i; };
 __device__ __forceinline__ bool better(float s, uint32_t i, float ts, uint32_t ti) { return s > ts || (s == ts && i < ti); }
@@ -83,8 +91,10 @@ __global__ __launch_bounds__(256) void knn_normalize_rows_kernel(const TIN* x, _
     }
 }
 
-// q f32 [b, dim] -> qn f32 [64, dim] (normalised, zero padded), qh / ql fp16 [64, dim]
-__global__ void knn_prep_queries_kernel(const float* q, int b, int dim, float* qn, _Float16* qh, _Float16* ql) {
+// q f32 [b, dim] -> qn f32 [64, dim] (normalised, zero padded), qh / ql fp16 [64, dim].  A query of norm zero has no direction (the
+// oracle's definition divides by the norm): its rows are written as zeros and zero_query gets 1 + its index in the batch (the
+// largest such); the host refuses the search.
+__global__ void knn_prep_queries_kernel(const float* q, int b, int dim, float* qn, _Float16* qh, _Float16* ql, int qbase, int* zero_query) {
     const int row = blockIdx.x, lane = threadIdx.x;
     double acc = 0.0;
     if (row < b) for (int c = lane; c < dim; c += 64) { const double v = (double)q[(long long)row * dim + c]; acc += v * v; }
@@ -93,12 +103,13 @@ __global__ void knn_prep_queries_kernel(const float* q, int b, int dim, float* q
     const float nrm = (float)sqrt(acc);
     for (int c = lane; c < dim; c += 64) {
         float v = 0.f;
-        if (row < b) v = q[(long long)row * dim + c] / nrm;
+        if (row < b && nrm > 0.f) v = q[(long long)row * dim + c] / nrm;
         const _Float16 h = (_Float16)v;
         qn[(long long)row * dim + c] = v;
         qh[(long long)row * dim + c] = h;
         ql[(long long)row * dim + c] = (_Float16)(v - (float)h);
     }
+    if (row < b && lane == 0 && !(nrm > 0.f)) atomicMax(zero_query, qbase + row + 1);
 }
 
 // ---------------------------------------------------------------- scan
@@ -216,114 +227,17 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(ScanParams p) {
 }
 
 // ---------------------------------------------------------------- scan, dim == 512 (CLIP ViT-B/32: the reference's only database)
-// The queries never touch LDS: wave w owns 32 queries (w & 1) and keeps their hi / lo fp16 words for ALL 512 dimensions as
-// MFMA B fragments in registers (2 x 32 fragments = 256 registers; one wave per SIMD has 512), against 128 of the tile's 256
-// rows (w >> 1).  LDS holds only the database ring (3 stages of 256 rows x 64 dims, requested two stages ahead with counted
-// vmcnt across raw barriers), so a stage costs 32 LDS-DMA pieces instead of 48 and 4 instead of 6 LDS reads per k-step; the
-// K loop of a tile is fully unrolled (the register-resident fragments need compile-time indices).
-// Measured (20.9 M x 512, 64 queries): 5.2 ms = 4.1 TB/s of database streamed, vs 6.6 ms for the LDS-staged-query kernel; the
-// bare LDS-DMA stream of the same walk runs at 6.3 TB/s (tools/ubench/hbm_pattern.hip), the gap is LDS-DMA issue time that a
-// single wave per SIMD cannot overlap with its own MFMAs.
-template <int KSEL>
-__global__ __launch_bounds__(256, 1) void knn_scan512_kernel(ScanParams p) {
-    constexpr int DB_BYTES = KNN_ROWS * 128, NKC = 8, DIM = 512;
-    extern __shared__ __attribute__((aligned(16))) char smem[];
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int lrow = tid >> 3, pchunk = tid & 7;
-    const int frow = lane & 31, fhalf = lane >> 5;
-    const int rh = wave >> 1, qt = wave & 1;
-    const char* zero = (const char*)p.zero_page;
-
-    f16x8 qh[32], ql[32];
-    {
-        const _Float16* qhp = p.qh + (long long)(qt * 32 + frow) * DIM + fhalf * 8;
-        const _Float16* qlp = p.ql + (long long)(qt * 32 + frow) * DIM + fhalf * 8;
-#pragma unroll
-        for (int kk = 0; kk < 32; kk++) { qh[kk] = *(const f16x8*)(qhp + kk * 16); ql[kk] = *(const f16x8*)(qlp + kk * 16); }
-    }
-    float ls[KSEL]; uint32_t li[KSEL];
-#pragma unroll
-    for (int j = 0; j < KSEL; j++) { ls[j] = -INFINITY; li[j] = 0xffffffffu; }
-
-    const long long my_tiles = (p.ntiles - blockIdx.x + gridDim.x - 1) / gridDim.x;
-    const long long iters = my_tiles * NKC;
-    // Address arithmetic is the cost of an LDS-DMA request here (the 64-bit row * dim products of a naive loader took ~900 cycles
-    // per stage, more than the 32 requests' time on the memory path): one 64-bit lane pointer per TILE, pieces and K chunks are
-    // constant byte offsets from it; the swizzle term does not depend on the piece (32 | piece stride).
-    const int csw = (pchunk ^ ((lrow >> 1) & 7)) * 16;    // byte offset of my (swizzled) source chunk inside a 128-byte segment
-    auto tile_ptr = [&](long long tile) { return (const char*)p.dbn + (tile * KNN_ROWS + lrow) * (long long)(DIM * 2) + csw; };
-    auto tile_rows = [&](long long tile) { const long long left = p.n - tile * KNN_ROWS; return (int)(left > KNN_ROWS ? KNN_ROWS : left); };
-    // stage st_kc of the tile whose lane pointer is st_ptr (st_rows valid rows) -> ring slot st_slot; then advance the stream
-    const char* st_ptr = tile_ptr(blockIdx.x); int st_rows = tile_rows(blockIdx.x); int st_kc = 0, st_slot = 0; long long st_tile = blockIdx.x;
-    auto stage_next = [&]() {
-        char* Ds = smem + st_slot * DB_BYTES;
-        const char* src = st_ptr + st_kc * (KNN_BK * 2);
-#pragma unroll
-        for (int i = 0; i < KNN_ROWS / 32; i++) {
-            const void* g = (i * 32 + lrow < st_rows) ? (const void*)(src + (long long)i * 32 * DIM * 2) : (const void*)zero;
-            glds16(g, Ds + (i * 32 + wave * 8) * 128);
-        }
-        st_slot = st_slot == 2 ? 0 : st_slot + 1;
-        if (++st_kc == NKC) { st_kc = 0; st_tile += gridDim.x; st_ptr = tile_ptr(st_tile); st_rows = tile_rows(st_tile); }
-    };
-    f32x16 acc[4];
-#pragma unroll
-    for (int a = 0; a < 4; a++)
-#pragma unroll
-        for (int r = 0; r < 16; r++) acc[a][r] = 0.f;
-
-    if (iters > 0) stage_next();
-    if (iters > 1) stage_next();
-    long long it = 0;
-    for (long long tl = 0; tl < my_tiles; tl++) {
-#pragma unroll
-        for (int kc = 0; kc < NKC; kc++, it++) {
-            // needed now: stage `it`; the 8 pieces of stage it+1 (requested after it) may stay in flight
-            if (it + 1 < iters) asm volatile("s_waitcnt vmcnt(8)" ::: "memory");
-            else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-            __builtin_amdgcn_s_barrier();                 // raw barrier (a __syncthreads would drain vmcnt): stage landed for all
-            if (it + 2 < iters) stage_next();             // waves; the slot of stage it-1 is free (its reads fed MFMAs already)
-            const char* Ds = smem + (int)(it % 3) * DB_BYTES;
-#pragma unroll
-            for (int k = 0; k < 4; k++) {
-                const int chunk = k * 2 + fhalf, kk = kc * 4 + k;
-                f16x8 a[4];
-#pragma unroll
-                for (int rf = 0; rf < 4; rf++) {
-                    const int row = rh * 128 + rf * 32 + frow;
-                    a[rf] = *(const f16x8*)(Ds + row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4));
-                }
-#pragma unroll
-                for (int rf = 0; rf < 4; rf++) {
-                    acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rf], ql[kk], acc[rf], 0, 0, 0);
-                    acc[rf] = __builtin_amdgcn_mfma_f32_32x32x16_f16(a[rf], qh[kk], acc[rf], 0, 0, 0);
-                }
-            }
-        }
-        const long long tile = blockIdx.x + tl * gridDim.x;
-        const long long rbase = tile * KNN_ROWS + rh * 128 + 4 * fhalf;
-#pragma unroll
-        for (int rf = 0; rf < 4; rf++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                const long long row = rbase + rf * 32 + (r & 3) + 8 * (r >> 2);
-                if (row < p.n) list_insert<KSEL>(ls, li, acc[rf][r], (uint32_t)row);
-                acc[rf][r] = 0.f;
-            }
-    }
-    const int list_id = blockIdx.x * 4 + rh * 2 + fhalf;
-    const long long base = ((long long)(qt * 32 + frow) * p.nlists + list_id) * KSEL;
-#pragma unroll
-    for (int j = 0; j < KSEL; j++) { p.cand_s[base + j] = ls[j]; p.cand_i[base + j] = li[j]; }
-}
-
-// ---------------------------------------------------------------- scan, dim == 512, 8 waves (two per SIMD), KSEL == 8
-// Same idea as knn_scan512_kernel (queries resident in registers, database-only LDS ring) with 16x16x32 MFMAs: a wave owns 16
-// queries (128 registers of hi / lo fragments) x 128 rows, so 8 waves = 2 row halves x 4 query groups fit two per SIMD (256
-// registers each) and one wave's LDS-DMA issue, LDS latency and list insertion hide behind its SIMD partner's MFMAs.
-// D layout 16x16: col (query) = lane & 15, row = (lane >> 4) * 4 + reg -> still one query, one private top-k list per lane.
-// Scores with the hi fp16 word of the query only (certificate bound KNN_EPS_BULK): that halves the MFMA work, and the lighter loop
-// holds a higher clock: 4.99 -> 4.48 ms per 64 queries over 20.9 M rows.
+// 8 waves (two per SIMD), KSEL == 8.  The queries never touch LDS: a wave keeps the hi fp16 words of its 16 queries for ALL 512
+// dimensions as 16x16x32 MFMA B fragments in registers (16 fragments = 64 registers), against 128 of the tile's 256 rows, so
+// 8 waves = 2 row halves x 4 query groups fit two per SIMD and one wave's LDS-DMA issue, LDS latency and list insertion hide behind
+// its SIMD partner's MFMAs.  LDS holds only the database ring (3 stages of 256 rows x 64 dims, requested two stages ahead with
+// counted vmcnt across raw barriers); the K loop of a tile is fully unrolled (the register-resident fragments need compile-time
+// indices).  Address arithmetic is the cost of an LDS-DMA request here (the 64-bit row * dim products of a naive loader took ~900
+// cycles per stage): one 64-bit lane pointer per TILE, pieces and K chunks are constant byte offsets from it; the swizzle term
+// does not depend on the piece.
+// D layout 16x16: col (query) = lane & 15, row = (lane >> 4) * 4 + reg -> one query, one private top-k list per lane.
+// Scores with the hi fp16 word of the query only (certificate bound knn_eps(hi-word path)): half the MFMA work of a hi + lo scan,
+// and the lighter loop holds a higher clock: 4.99 -> 4.48 ms per 64 queries over 20.9 M rows (4 waves, 32x32x16, hi + lo, retired).
 template <int KSEL>
 __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
     constexpr int DB_BYTES = KNN_ROWS * 128, NKC = 8, DIM = 512;
@@ -420,8 +334,9 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
 // the same top-k at dataset scale.  One database pass per 64 queries (above) is HBM-bound there; this kernel scores 128 queries per
 // block against each 256-row tile, and a launch carries up to FOUR query groups whose walkers sit on the same XCD and walk the same
 // tiles, so three of them read the tile from that XCD's L2: HBM streams the database once per 512 queries.  Scores come from the hi
-// word of the query only: |q - fp16(q)| <= 2^-12 |q| per element moves a score by at most 2^-12 sum |q_j d_j| <= 2.4e-4 (unit
-// vectors) -- the certificate in the merge runs with KNN_EPS_BULK and the exact fallback absorbs the (rare) failures.  A stage is 256
+// word of the query only: |q - fp16(q)| <= 2^-11 |q| per element (fp16's unit roundoff) moves a score by at most 2^-11 sum |q_j d_j|
+// <= 4.88e-4 (unit vectors) -- the certificate in the merge runs with knn_eps(bulk, dim), derived at the top of the file, and the
+// exact fallback absorbs the (rare) failures.  A stage is 256
 // database rows + 128 query rows x 64 dims = 48 KB, three stages in an LDS ring requested two ahead.
 //
 // The block is cut into producer and consumer waves.  The first version (eight waves of 128 rows x 32 queries that also issued the
@@ -609,9 +524,11 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
 struct Certify {
     int* flag;                          // [64] 1 = candidate set not provably sufficient -> exact fallback for this query
     double* tau; uint32_t* tau_idx;     // [64] the current k-th (exact score, index)
+    float* theta;                       // [64] the merge's bound on the approximate score of every dropped row (read-out only)
     int* fb_count;                      // [64] rows collected by the fallback
     double* fb_s; uint32_t* fb_i;       // [64][KNN_FB_CAP]
-    int* status;                        // sticky bits for the host: 1 = a fallback ran, 2 = a fallback overflowed KNN_FB_CAP
+    int* status;                        // [0] sticky bits for the host: 1 = a fallback ran, 2 = a fallback overflowed KNN_FB_CAP
+                                        // [1] 1 + index of a zero-norm query, 0 = none
 };
 struct MergeParams {
     const float* cand_s; const uint32_t* cand_i; int nlists;
@@ -693,7 +610,7 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(MergeParams p) {
         const double tau = ex[p.k - 1];
         const bool certified = (double)th + (double)p.eps < tau;
         p.cert.flag[q] = certified ? 0 : 1;
-        p.cert.tau[q] = tau; p.cert.tau_idx[q] = exi[p.k - 1]; p.cert.fb_count[q] = 0;
+        p.cert.tau[q] = tau; p.cert.tau_idx[q] = exi[p.k - 1]; p.cert.fb_count[q] = 0; p.cert.theta[q] = th;
         if (!certified) atomicOr(p.cert.status, 1);
     }
 }
@@ -808,22 +725,66 @@ const char* knn_load(KnnDb& db, const void* emb, long long n, int dim, int dtype
     return msg;
 }
 
+// The bound on |approximate - exact| score of a scan path at a dimension (derivation at the top of the file), rounded UP to fp32.
+static float knn_eps(int path, int dim) {
+    const double tail = sqrt((double)dim) * 0x1p-25;                       // fp16 words below 2^-14: absolute spacing 2^-24
+    const double e = path == RDM_KNN_SCAN_GENERIC ? dim * 0x1p-22 + tail + 0x1p-22         // 2 dim products, doubled; lo word's residuals
+                                                  : dim * 0x1p-23 + tail + 0x1p-11;        // dim products, doubled; hi word's roundoff
+    float f = (float)e;
+    if ((double)f < e) f = nextafterf(f, INFINITY);
+    return f;
+}
+
+const char* knn_select(long long n, int dim, int b, int k, rdm_knn_form* out) {
+    if (n <= 0 || dim <= 0 || dim % KNN_BK != 0 || dim > 4096) return "dim must be a positive multiple of 64";
+    if (n >= 0xffffffffLL) return "database too large for uint32 indices";
+    if (b < 1 || k < 1) return "b and k must be positive";
+    if (k > n) return "k exceeds database size";
+    if (k > 28) return "k > 28 is not supported (the merge re-scores the best 64 candidates)";
+    const long long ntiles = (n + KNN_ROWS - 1) / KNN_ROWS;
+    // List length per lane: 8 for every k; the merge re-scores the best 16 (k <= 4) or 64 (k <= 28) of the merged candidates.  The
+    // length is a SPEED choice, not a correctness margin: whatever a list drops is covered by the certificate (and the exact
+    // fallback) in the merge.  A lane sees 1/2048 of the rows (1/256 in the bulk scan), so a list overflows only when more than 8
+    // of a query's best ~64 rows fall into one lane's rows.  (The insertion chain runs for a candidate when ANY of the wave's 64
+    // lanes accepts it, so its cost grows with the list length times the acceptance rate: 16-entry lists made k = 16 take 8.8 ms
+    // per 64 queries against 4.4 ms for k = 4, 32-entry lists 8x and the 8-wave bulk kernel spilled.)
+    out->ksel = 8;
+    out->rescored = k <= 4 ? 16 : 64;
+    // dataset-scale query batches: 128-query walkers, up to 4 groups per database pass; dim 512 online: register-resident hi words
+    out->path = (b >= 128 && ntiles >= 16) ? RDM_KNN_SCAN_BULK : dim == 512 ? RDM_KNN_SCAN_D512 : RDM_KNN_SCAN_GENERIC;
+    out->lists_per_block = out->path == RDM_KNN_SCAN_BULK ? 4 : 8;
+    out->queries_per_launch = out->path == RDM_KNN_SCAN_BULK ? KNN_QMAX : KNN_Q;
+    out->eps = knn_eps(out->path, dim);
+    return nullptr;
+}
+
+// copy of one stage's result into the caller's array, if it asked for that one
+static const char* stage_out(void* dst, const void* src, size_t bytes, hipStream_t st) {
+    return dst ? hiperr(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToDevice, st)) : nullptr;
+}
+
 template <int KSEL, int R>
-static const char* search_impl(KnnDb& db, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out, hipStream_t st) {
+static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float* q, int b, int k, uint32_t* idx_out, float* score_out,
+                               double* score64_out, hipStream_t st, rdm_knn_stages* so) {
     int dev = 0, ncu = 256;
     hipGetDevice(&dev);
     hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
     const long long ntiles = (db.n + KNN_ROWS - 1) / KNN_ROWS;
     int grid = (int)(ntiles < ncu ? ntiles : ncu);
-    const bool d512 = db.dim == 512;                 // register-resident queries (4 lists per block and query instead of 8)
-    const int nlists = grid * (d512 ? 4 : 8);
     const int nlists_cap = grid * 8;
-    const bool bulk = b >= 128 && db.dim % KNN_BK == 0 && ntiles >= 16;       // dataset-scale query batches: 128-query walkers, up to 4 groups per database pass
-    const int QS = bulk ? KNN_QMAX : KNN_Q;                    // queries the scratch is sized for
+    const bool bulk = form.path == RDM_KNN_SCAN_BULK;
+    const int QS = form.queries_per_launch;                    // queries the scratch is sized for
+    if (so) {
+        if (b > QS || (bulk && b < 128)) return "stages are read out for one query group: b <= 64, or 128 <= b <= 512 on the bulk path";
+        so->rows = bulk ? (b + 127) / 128 * 128 : KNN_Q;
+        so->nlists = bulk ? 0 : grid * form.lists_per_block;       // bulk: set at the launch below
+        so->form = form;
+        if (so->rows_cap < so->rows) return "stages: rows_cap is too small";
+    }
     const size_t qn_b = (size_t)QS * db.dim * 4, qh_b = (size_t)QS * db.dim * 2;
     const size_t cand_b = (size_t)QS * nlists_cap * KSEL * 4;
     const size_t cert_off = (qn_b + 2 * qh_b + 2 * cand_b + 255) & ~(size_t)255;
-    const size_t cert_b = 256 /*status*/ + KNN_QMAX * (4 + 8 + 4 + 4) + 256 + (size_t)KNN_QMAX * KNN_FB_CAP * 12;
+    const size_t cert_b = 256 /*status*/ + KNN_QMAX * (4 + 8 + 4 + 4 + 4) + 256 + (size_t)KNN_QMAX * KNN_FB_CAP * 12;
     const size_t need = cert_off + cert_b + 1024;
     if (db.scratch_bytes < need) {
         if (db.scratch) { KNN_TRY(hipStreamSynchronize(st)); KNN_TRY(hipFree(db.scratch)); db.scratch = nullptr; db.scratch_bytes = 0; }
@@ -841,102 +802,112 @@ static const char* search_impl(KnnDb& db, const float* q, int b, int k, uint32_t
         cert.fb_i = (uint32_t*)cb; cb += (size_t)KNN_QMAX * KNN_FB_CAP * 4;
         cert.tau_idx = (uint32_t*)cb; cb += KNN_QMAX * 4;
         cert.flag = (int*)cb; cb += KNN_QMAX * 4;
-        cert.fb_count = (int*)cb;
+        cert.fb_count = (int*)cb; cb += KNN_QMAX * 4;
+        cert.theta = (float*)cb;
     }
-    KNN_TRY(hipMemsetAsync(cert.status, 0, 4, st));
+    KNN_TRY(hipMemsetAsync(cert.status, 0, 8, st));
     if (!db.zero_page) { KNN_TRY(hipMalloc(&db.zero_page, 256)); KNN_TRY(hipMemset(db.zero_page, 0, 256)); }
     void* zero_page = db.zero_page;
     constexpr int scan_smem = 2 * (KNN_ROWS * 128 + 2 * KNN_Q * 128);
     constexpr int scan512_smem = 3 * KNN_ROWS * 128;
+    constexpr int bulk_smem = 3 * (KNN_ROWS * 128 + 128 * 128);
     constexpr int merge_smem = 256 * KSEL * 8;
     static bool attr_dev[RDM_MAX_DEVICES] = {false};
     bool& attr = attr_dev[rdm_cur_device()];
     if (!attr) {
         KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, scan_smem));
-        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_bulk_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bulk_smem));
         KNN_TRY(hipFuncSetAttribute((const void*)knn_merge_kernel<KSEL, R>, hipFuncAttributeMaxDynamicSharedMemorySize, merge_smem));
         attr = true;
     }
+    // one query group (online: <= 64 queries, bulk: <= 512) from the scored lists on: merge + exact re-score, then the exact fallback
+    // for the flagged queries (both kernels return at once when nothing is flagged)
+    auto merge_group = [&](int q0, int bq, int nlists) -> const char* {
+        if (so) {
+            so->nlists = nlists;
+            if (so->nlists_cap < nlists) return "stages: nlists_cap is too small";
+            const size_t rows = (size_t)so->rows;
+            KNN_TRY(hipGetLastError());
+            if (const char* m = stage_out(so->qn, qn, rows * db.dim * 4, st)) return m;
+            if (const char* m = stage_out(so->qh, qh, rows * db.dim * 2, st)) return m;
+            if (const char* m = stage_out(so->ql, ql, rows * db.dim * 2, st)) return m;
+            if (const char* m = stage_out(so->cand_s, cs, rows * nlists * KSEL * 4, st)) return m;
+            if (const char* m = stage_out(so->cand_i, ci, rows * nlists * KSEL * 4, st)) return m;
+        }
+        MergeParams mp{}; mp.cand_s = cs; mp.cand_i = ci; mp.nlists = nlists; mp.dbn = (const _Float16*)db.dbn; mp.qn = qn;
+        mp.dim = db.dim; mp.n = db.n; mp.k = k; mp.idx_out = idx_out; mp.score_out = score_out; mp.score64_out = score64_out; mp.qbase = q0;
+        mp.cert = cert; mp.eps = form.eps;
+        knn_merge_kernel<KSEL, R><<<bq, 256, merge_smem, st>>>(mp);
+        KNN_TRY(hipGetLastError());
+        if (so) {       // the merge's verdict, before the fallback answers the flagged queries
+            if (const char* m = stage_out(so->flag, cert.flag, (size_t)bq * 4, st)) return m;
+            if (const char* m = stage_out(so->tau, cert.tau, (size_t)bq * 8, st)) return m;
+            if (const char* m = stage_out(so->tau_idx, cert.tau_idx, (size_t)bq * 4, st)) return m;
+            if (const char* m = stage_out(so->theta, cert.theta, (size_t)bq * 4, st)) return m;
+        }
+        knn_exact_collect_kernel<<<ncu * 4, 256, 0, st>>>(cert, (const _Float16*)db.dbn, qn, db.n, db.dim, bq);
+        KNN_TRY(hipGetLastError());
+        knn_exact_finish_kernel<<<bq, 256, 0, st>>>(cert, k, idx_out, score_out, score64_out, q0);
+        return hiperr(hipGetLastError());
+    };
+    ScanParams sp{}; sp.dbn = (const _Float16*)db.dbn; sp.n = db.n; sp.dim = db.dim; sp.ntiles = ntiles; sp.qh = qh; sp.ql = ql;
+    sp.cand_s = cs; sp.cand_i = ci; sp.zero_page = zero_page;
     if (bulk) {
-        constexpr int bulk_smem = 3 * (KNN_ROWS * 128 + 128 * 128);
-        static bool battr_dev[RDM_MAX_DEVICES] = {false};
-        bool& battr = battr_dev[rdm_cur_device()];
-        if (!battr) { KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_bulk_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bulk_smem)); battr = true; }
         const int bgrid = (ncu / 32) * 32;                                  // a multiple of 8 XCDs x 4 groups
         for (int q0 = 0; q0 < b; q0 += KNN_QMAX) {
             const int bq = (b - q0 < KNN_QMAX) ? b - q0 : KNN_QMAX;
             const int groups = (bq + 127) / 128;                        // 1 .. 4 query groups share every database pass
-            knn_prep_queries_kernel<<<groups * 128, 64, 0, st>>>(q + (size_t)q0 * db.dim, bq, db.dim, qn, qh, ql);
+            knn_prep_queries_kernel<<<groups * 128, 64, 0, st>>>(q + (size_t)q0 * db.dim, bq, db.dim, qn, qh, ql, q0, cert.status + 1);
             KNN_TRY(hipGetLastError());
-            BulkParams bp{}; bp.groups = groups;
-            bp.s.dbn = (const _Float16*)db.dbn; bp.s.n = db.n; bp.s.dim = db.dim; bp.s.ntiles = ntiles; bp.s.qh = qh; bp.s.ql = ql;
-            bp.s.cand_s = cs; bp.s.cand_i = ci; bp.s.zero_page = zero_page;
+            BulkParams bp{}; bp.groups = groups; bp.s = sp;
             int walkers = bgrid / groups; if ((long long)walkers > ntiles) walkers = (int)ntiles;
             walkers = (walkers / 8) * 8;                                    // >= 8 (ntiles >= 16): every walker owns a tile and writes its lists
-            const int g2 = walkers * groups;
-            bp.s.nlists = walkers * 4;
-            knn_scan_bulk_kernel<KSEL><<<g2, 512, bulk_smem, st>>>(bp);
+            bp.s.nlists = walkers * form.lists_per_block;
+            knn_scan_bulk_kernel<KSEL><<<walkers * groups, 512, bulk_smem, st>>>(bp);
             KNN_TRY(hipGetLastError());
-            MergeParams mp{}; mp.cand_s = cs; mp.cand_i = ci; mp.nlists = bp.s.nlists; mp.dbn = (const _Float16*)db.dbn; mp.qn = qn;
-            mp.dim = db.dim; mp.n = db.n; mp.k = k; mp.idx_out = idx_out; mp.score_out = score_out; mp.score64_out = score64_out; mp.qbase = q0; mp.cert = cert; mp.eps = KNN_EPS_BULK;
-            knn_merge_kernel<KSEL, R><<<bq, 256, merge_smem, st>>>(mp);
-            KNN_TRY(hipGetLastError());
-            knn_exact_collect_kernel<<<ncu * 4, 256, 0, st>>>(cert, (const _Float16*)db.dbn, qn, db.n, db.dim, bq);
-            KNN_TRY(hipGetLastError());
-            knn_exact_finish_kernel<<<bq, 256, 0, st>>>(cert, k, idx_out, score_out, score64_out, q0);
-            KNN_TRY(hipGetLastError());
+            if (const char* m = merge_group(q0, bq, bp.s.nlists)) return m;
         }
     } else
     for (int q0 = 0; q0 < b; q0 += KNN_Q) {
         const int bq = (b - q0 < KNN_Q) ? b - q0 : KNN_Q;
-        knn_prep_queries_kernel<<<KNN_Q, 64, 0, st>>>(q + (size_t)q0 * db.dim, bq, db.dim, qn, qh, ql);
+        knn_prep_queries_kernel<<<KNN_Q, 64, 0, st>>>(q + (size_t)q0 * db.dim, bq, db.dim, qn, qh, ql, q0, cert.status + 1);
         KNN_TRY(hipGetLastError());
-        ScanParams sp{}; sp.dbn = (const _Float16*)db.dbn; sp.n = db.n; sp.dim = db.dim; sp.ntiles = ntiles; sp.qh = qh; sp.ql = ql;
-        sp.cand_s = cs; sp.cand_i = ci; sp.nlists = nlists; sp.zero_page = zero_page;
-        const bool w8 = d512 && KSEL == 8;                               // hi-word scoring: certificate bound KNN_EPS_BULK
-        if (w8) {
-            static bool attr8_dev[RDM_MAX_DEVICES] = {false};
-            bool& attr8 = attr8_dev[rdm_cur_device()];
-            if (!attr8) {
-                KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<8>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
-                attr8 = true;
-            }
-            sp.nlists = grid * 8;
-            knn_scan512w8_kernel<8><<<grid, 512, scan512_smem, st>>>(sp);
-        } else if (d512) knn_scan512_kernel<KSEL><<<grid, 256, scan512_smem, st>>>(sp);
+        sp.nlists = grid * form.lists_per_block;
+        if (form.path == RDM_KNN_SCAN_D512) knn_scan512w8_kernel<KSEL><<<grid, 512, scan512_smem, st>>>(sp);
         else knn_scan_kernel<KSEL><<<grid, 256, scan_smem, st>>>(sp);
         KNN_TRY(hipGetLastError());
-        MergeParams mp{}; mp.cand_s = cs; mp.cand_i = ci; mp.nlists = sp.nlists; mp.dbn = (const _Float16*)db.dbn; mp.qn = qn;
-        mp.dim = db.dim; mp.n = db.n; mp.k = k; mp.idx_out = idx_out; mp.score_out = score_out; mp.score64_out = score64_out; mp.qbase = q0; mp.cert = cert; mp.eps = w8 ? KNN_EPS_BULK : KNN_EPS;
-        knn_merge_kernel<KSEL, R><<<bq, 256, merge_smem, st>>>(mp);
-        KNN_TRY(hipGetLastError());
-        // exact fallback for the flagged queries of this group (both kernels return at once when nothing is flagged)
-        knn_exact_collect_kernel<<<ncu * 4, 256, 0, st>>>(cert, (const _Float16*)db.dbn, qn, db.n, db.dim, bq);
-        KNN_TRY(hipGetLastError());
-        knn_exact_finish_kernel<<<bq, 256, 0, st>>>(cert, k, idx_out, score_out, score64_out, q0);
-        KNN_TRY(hipGetLastError());
+        if (const char* m = merge_group(q0, bq, sp.nlists)) return m;
     }
-    int status = 0;
-    KNN_TRY(hipMemcpyAsync(&status, cert.status, 4, hipMemcpyDeviceToHost, st));
+    int status[2] = {0, 0};
+    KNN_TRY(hipMemcpyAsync(status, cert.status, 8, hipMemcpyDeviceToHost, st));
     KNN_TRY(hipStreamSynchronize(st));
-    db.last_fallbacks = status & 1;
-    if (status & 2) return "exact fallback overflow: more than 8192 rows tie with the k-th neighbour within the score error bound";
+    db.last_fallbacks = status[0] & 1;
+    if (status[1]) {
+        static thread_local char msg[96];
+        snprintf(msg, sizeof msg, "query %d has zero norm: cosine similarity to it is undefined", status[1] - 1);
+        return msg;
+    }
+    if (status[0] & 2) return "exact fallback overflow: more than 8192 rows tie with the k-th neighbour within the score error bound";
     return nullptr;
 }
 
-const char* knn_search(KnnDb& db, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out, hipStream_t st) {
+const char* knn_search(KnnDb& db, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out, hipStream_t st,
+                       rdm_knn_stages* stages) {
     if (!db.dbn) return "no database loaded (rdm_db_load)";
-    if (b < 1 || k < 1) return "b and k must be positive";
-    if (k > db.n) return "k exceeds database size";
-    // List length per lane: 8 for every k; the merge re-scores the best 16 (k <= 4) or 64 (k <= 28) of the merged candidates.  The
-    // length is a SPEED choice, not a correctness margin: whatever a list drops is covered by the certificate (and the exact
-    // fallback) in the merge.  A lane sees 1/2048 of the rows (1/256 in the bulk scan), so a list overflows only when more than 8
-    // of a query's best ~64 rows fall into one lane's rows.  (The insertion chain runs for a candidate when ANY of the wave's 64
-    // lanes accepts it, so its cost grows with the list length times the acceptance rate: 16-entry lists made k = 16 take 8.8 ms
-    // per 64 queries against 4.4 ms for k = 4, 32-entry lists 8x and the 8-wave bulk kernel spilled.)
-    if (k <= 4) return search_impl<8, 16>(db, q, b, k, idx_out, score_out, score64_out, st);
-    if (k <= 28) return search_impl<8, 64>(db, q, b, k, idx_out, score_out, score64_out, st);
-    return "k > 28 is not supported (the merge re-scores the best 64 candidates)";
+    rdm_knn_form form{};
+    if (const char* m = knn_select(db.n, db.dim, b, k, &form)) return m;
+    static_assert(KNN_Q == 64 && KNN_QMAX == 512, "rdm_hip.h documents these group sizes");
+    if (form.ksel == 8 && form.rescored == 16) return search_impl<8, 16>(db, form, q, b, k, idx_out, score_out, score64_out, st, stages);
+    if (form.ksel == 8 && form.rescored == 64) return search_impl<8, 64>(db, form, q, b, k, idx_out, score_out, score64_out, st, stages);
+    return "no scan kernel is compiled for this list length and re-scored prefix";
+}
+
+const char* knn_rows(KnnDb& db, long long row0, long long rows, void* out_f16, hipStream_t st) {
+    if (!db.dbn) return "no database loaded (rdm_db_load)";
+    if (row0 < 0 || rows < 0 || row0 + rows > db.n) return "rows outside the database";
+    if (rows == 0) return nullptr;
+    return hiperr(hipMemcpyAsync(out_f16, (const char*)db.dbn + (size_t)row0 * db.dim * 2, (size_t)rows * db.dim * 2, hipMemcpyDeviceToDevice, st));
 }
 
 const char* knn_gather(KnnDb& db, const uint32_t* idx, long long n_idx, float* out, hipStream_t st) {

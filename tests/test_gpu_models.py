@@ -262,6 +262,7 @@ def test_knn_bit_exact(ctx, N, B, k):
     ref_i, ref_s = oret.exact_topk(oret.normalize_db(db), oret.normalize_queries(q), k)
     assert np.array_equal(idx, ref_i), f"top-k indices differ in {(idx != ref_i).sum()} places"
     assert np.abs(sc.cpu().numpy() - ref_s).max() <= 1e-6
+    assert ctx.knn_last_fallback() == 0                           # certified from the scan's lists: the exact pass repaired nothing
     # gather of raw embeddings (dsetbuilder.py:493)
     emb = ctx.db_gather(torch.from_numpy(ref_i.astype(np.int64).astype(np.int32)).to(ctx.device), 512).cpu().numpy()
     assert np.array_equal(emb, db[ref_i].astype(np.float32))
@@ -282,6 +283,7 @@ def test_knn_other_dims_bit_exact(ctx, dim):
     ref_i, ref_s = oret.exact_topk(oret.normalize_db(db), oret.normalize_queries(q), k)
     assert np.array_equal(idx.cpu().numpy().view(np.uint32), ref_i)
     assert np.abs(sc.cpu().numpy() - ref_s).max() <= 1e-6
+    assert ctx.knn_last_fallback() == 0
 
 
 def test_knn_planted_neighbours_large(ctx):
