@@ -557,6 +557,16 @@ int rdm_calib_probe(rdm_ctx* ctx, void* buf /*[dev]*/, size_t buf_bytes, double 
  *                    5 ln_2 bf16, 6 QuickGELU hidden bf16 [rows, 4 W], 7 x + c_proj f32 (the block's output).
  * tests/test_gpu_clip.py holds every one of them to an fp64 restatement on the library's own inputs. */
 int rdm_debug_tap(rdm_ctx* ctx, void* buf /*[dev]*/, size_t nbytes, int block, int sub);
+/* test hook: where the SHARED GUIDANCE PREFIX of a guided sampler forward ends.  With classifier-free guidance the UNet batch is
+ * [x | x] with contexts [cond | uncond] (ddim.py:229-234), and everything in front of the first cross-attention computes the same values
+ * for both halves, so it runs once on the first half.  through_attn1 = 1 (the default): the prefix covers the layers in front of the
+ * first SpatialTransformer AND that transformer's norm, proj_in, norm1, q|k|v projection and self-attention; it ends at attn1.to_out,
+ * which reads its operand and residual with a row wrap (or from duplicated copies where the wrapped GEMM form does not take the shape).
+ * 0: the prefix ends in front of that transformer.  Both give bit-identical results (every row's arithmetic is the same; the shared
+ * stages choose their kernels as for the whole batch): tests/test_gpu_guided_prefix.py compares them inside one process.  rdm_debug_tap
+ * shows a stage that ran on the first half as the logical tensor, the second half a copy of the first.  Deterministic mode always ends
+ * the prefix in front of the transformer.  Not an environment switch, and not meant for production use. */
+int rdm_debug_guidance_prefix(rdm_ctx* ctx, int through_attn1);
 
 /* ---- operator-level entry points (used by the parity tests; thin wrappers over the kernels) ---- */
 int rdm_op_linear(rdm_ctx* ctx, const void* a_bf16, const void* w_bf16, const float* bias, const void* residual_bf16,

@@ -190,6 +190,7 @@ SIGNATURES = {
     "rdm_prof_reset": (C.c_int, [_P]),
     "rdm_prof_dump": (C.c_int, [_P, C.c_char_p]),
     "rdm_debug_tap": (C.c_int, [_P, _P, C.c_size_t, C.c_int, C.c_int]),
+    "rdm_debug_guidance_prefix": (C.c_int, [_P, C.c_int]),
     "rdm_calib_probe": (C.c_int, [_P, _P, C.c_size_t, C.c_double, C.c_size_t, C.c_int, C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rdm_comm_unique_id": (C.c_int, [_P, _P]),
     "rdm_comm_init": (C.c_int, [_P, _P, C.c_int, C.c_int]),
@@ -1504,6 +1505,11 @@ class Context:
         that type, and at most its numel * element_size bytes are written."""
         self._tap_keepalive = buf
         self._check(lib.rdm_debug_tap(self._h, _ptr(buf) if buf is not None else None, 0 if buf is None else buf.numel() * buf.element_size(), int(block), int(sub)))
+
+    def debug_guidance_prefix(self, through_attn1=1):
+        """Where the shared guidance prefix of a guided forward ends (rdm_debug_guidance_prefix): 1 (default) at the first transformer's
+        attn1.to_out, 0 in front of that transformer.  Both give the same bits; the hook exists to compare them in one process."""
+        self._check(lib.rdm_debug_guidance_prefix(self._h, int(through_attn1)))
 
     def calib_probe(self, mfma_ms=800.0, stream_bytes=1 << 30, stream_reps=6):
         """Box calibration (rdm_calib_probe): (sustained dense-bf16 MFMA TFLOP/s on random operands, HBM copy GB/s read + write)."""

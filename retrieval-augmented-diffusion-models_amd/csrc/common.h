@@ -118,6 +118,9 @@ struct IgemmParams {
     // stored weight row (launch_lin_ln_sb); the kernel takes the row statistics itself: out = rstd (A Wg^T - mean s) + b'
     const float* ln_sb; float ln_inv_c, ln_eps;      // ln_inv_c = 1 / (logical row width): zero padding beyond it adds nothing to the sums
     int dbg;                    // always 0: read only by conv3x3_halo4_kernel's phase-clock code, kept for its code generation (conv_halo4.hip)
+    int a0_wrap_rows;           // lin4 only, a1_wrap_rows' sibling: > 0: A0 holds only that many rows and row m reads m % a0_wrap_rows (whole tiles, at most
+                                // two copies).  (Last, so that no other field's offset in the kernel argument moved when it was added.)
+    int choice_rows;            // host only (LinearOp::choice_rows): > M: the tile form and lin4's tile-count rule are chosen as for that many rows
 };
 // the start values of a plain GEMM out[M, N] = A[M, K] W^T (host): no scale, 1 x 1 geometry, one row per row-vector group, output rows of N;
 // every caller goes on from these (Ops::base, the op entries, the weight-gradient fallbacks)

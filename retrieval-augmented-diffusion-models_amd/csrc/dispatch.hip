@@ -59,16 +59,20 @@ static SgemmParams skinny_params(const LinearOp& op) {      // the op as the ski
 bool Ops::lin4_takes(const LinearOp& op) {
     if (c->deterministic) return false;
     IgemmParams t = base(op.M, op.N, op.C0 + op.C1);
-    t.C0 = op.C0; t.C1 = op.C1; t.W = (const bf16_t*)blob; t.Wfrag = t.W; t.out_bf16 = (bf16_t*)blob; t.a1_wrap_rows = op.a1_wrap_rows;
+    t.C0 = op.C0; t.C1 = op.C1; t.W = (const bf16_t*)blob; t.Wfrag = t.W; t.out_bf16 = (bf16_t*)blob;
+    t.a0_wrap_rows = op.a0_wrap_rows; t.a1_wrap_rows = op.a1_wrap_rows;
+    if (op.rowvec) { t.rowvec = op.rowvec; t.rowvec_ld = op.rowvec_ld; t.rows_per_sample = op.rows_per_sample; }
     if (op.res_wrap_rows > 0) { t.res_bf16 = (const bf16_t*)blob; t.res_wrap_rows = op.res_wrap_rows; }
     return lin4_supported(t, 1);
 }
 void Ops::linear(const LinearOp& op) {
     if (plan) return;
     const int M = op.M, N = op.N, K = op.C0 + op.C1;
-    if (!op.A1 && op.C1 == 0 && !op.rowvec && op.alpha == 1.f) {         // N/32 x ceil(M/32) blocks (sgemm.hip), 64 x 64 tiles (mgemm.hip)
+    if (!op.A1 && op.C1 == 0 && !op.rowvec && op.alpha == 1.f && op.a0_wrap_rows == 0 && op.res_wrap_rows == 0) {         // N/32 x ceil(M/32) blocks (sgemm.hip), 64 x 64 tiles (mgemm.hip)
         SgemmParams q = skinny_params(op);
+        if (op.choice_rows > M) q.M = op.choice_rows;
         const int kernel = linear_kernel(q, c->deterministic, op.single_row);
+        q.M = M;
         if (kernel != RDM_LINEAR_ROWS_TILED) {
             const bool mid = kernel == RDM_LINEAR_ROWS_MGEMM;
             prof_begin(RDM_PROF_LINEAR, 2.0 * M * N * (double)K, M, N, K);
@@ -80,7 +84,7 @@ void Ops::linear(const LinearOp& op) {
     IgemmParams p = base(M, N, K);
     p.A0 = op.A0; p.A1 = op.A1; p.C0 = op.C0; p.C1 = op.C1; p.W = op.W; p.bias = op.bias; p.alpha = op.alpha;
     p.act = op.act; p.res_bf16 = op.res_bf16; p.res_f32 = op.res_f32; p.out_bf16 = op.out_bf16; p.out_f32 = op.out_f32;
-    p.a1_wrap_rows = op.a1_wrap_rows; p.res_wrap_rows = op.res_wrap_rows;
+    p.a0_wrap_rows = op.a0_wrap_rows; p.a1_wrap_rows = op.a1_wrap_rows; p.res_wrap_rows = op.res_wrap_rows; p.choice_rows = op.choice_rows;
     if (op.rowvec) { p.rowvec = op.rowvec; p.rowvec_ld = op.rowvec_ld; p.rows_per_sample = op.rows_per_sample; }
     if (op.act == ACT_GEGLU) p.ldo = N / 2;
     // one-wave-per-SIMD kernel for the big-M projections (its tile choice follows M, so not in deterministic mode)
@@ -154,10 +158,15 @@ void Ops::conv3(const Conv3Op& op) {
 //  remainder tiles cost 73 us on a chip that clocks up when half its CUs idle -- while 256 K halves + their fp32 planes and finisher cost
 //  118 us.  The code is in the history (commits "conv tail split", "conv_halo4 TAIL variant", "conv remainder split"), the numbers in
 //  profiles/r06_conv_tail_split_*.log, r06_conv_remainder_split_*.)
-void Ops::tap(int stage, const void* ptr, size_t nbytes) {      // rdm_debug_tap: stage `stage` of layer cur_layer of block cur_block
+// twice: the stage ran on the first half of a guided batch only (unet_body's shared prefix inside the first transformer) and ptr holds
+// those nbytes; the tap shows the LOGICAL tensor, both halves, the second a copy of the first
+void Ops::tap(int stage, const void* ptr, size_t nbytes, bool twice) {      // rdm_debug_tap: stage `stage` of layer cur_layer of block cur_block
     if (plan || !c->tap_buf || c->tap_block != cur_block || c->tap_sub != cur_layer * 16 + stage) return;
-    if (nbytes > c->tap_bytes) nbytes = c->tap_bytes;
-    check(hipMemcpyAsync(c->tap_buf, ptr, nbytes, hipMemcpyDeviceToDevice, c->stream), "debug tap");
+    const size_t n0 = nbytes > c->tap_bytes ? c->tap_bytes : nbytes;
+    check(hipMemcpyAsync(c->tap_buf, ptr, n0, hipMemcpyDeviceToDevice, c->stream), "debug tap");
+    if (!twice || c->tap_bytes <= nbytes) return;
+    const size_t n1 = c->tap_bytes - nbytes < nbytes ? c->tap_bytes - nbytes : nbytes;
+    check(hipMemcpyAsync((char*)c->tap_buf + nbytes, ptr, n1, hipMemcpyDeviceToDevice, c->stream), "debug tap");
 }
 void Ops::prof_begin(int kind, double work, int d0, int d1, int d2) {       // work: FLOPs (GEMM-class kinds) or bytes (bandwidth-class kinds)
     prof_open = (c->prof >> kind) & 1u;

@@ -249,6 +249,9 @@ struct rdm_ctx {
     bool deterministic = rdm_env_int(getenv("RDM_DETERMINISTIC"), 0) != 0;
     // debug tap (rdm_debug_tap): the output activation of top-level UNet block `tap_block` (NHWC bf16) is copied into tap_buf by the next forward
     void* tap_buf = nullptr; size_t tap_bytes = 0; int tap_block = -1, tap_sub = 0;      // tap_sub: 0 = the block's output, else 16 * layer-in-block + stage (unet_body)
+    // rdm_debug_guidance_prefix: 1 = the shared guidance prefix of a guided forward runs through the first transformer's self-attention,
+    // 0 = it ends in front of that transformer (unet_body)
+    int prefix_through_attn1 = 1;
     // RCCL communicator (rdm_comm_*): library handle from dlopen, function table, communicator
     void* rccl_lib = nullptr; void* comm = nullptr; int comm_world = 0;
     // optional per-launch HIP-event profiler for the GEMM-class kernels (bench.py roofline)
@@ -291,11 +294,13 @@ struct LinearOp {
     const bf16_t* res_bf16 = nullptr; const float* res_f32 = nullptr;
     bf16_t* out_bf16 = nullptr; float* out_f32 = nullptr;
     const float* rowvec = nullptr; int rowvec_ld = 0, rows_per_sample = 1;      // a per-column add shared by each group of rows_per_sample rows (row stride rowvec_ld)
-    int a1_wrap_rows = 0, res_wrap_rows = 0;                                    // lin4 only (callers ask lin4_takes first): A1 / res_bf16 hold that many rows, row m reads m % rows
+    int a0_wrap_rows = 0, a1_wrap_rows = 0, res_wrap_rows = 0;                  // lin4 only (callers ask lin4_takes first): A0 / A1 / res_bf16 hold that many rows, row m reads m % rows
     float alpha = 1.f;                                                          // (the skinny and mid-size kernels take alpha == 1 only)
     // what the kernel choice reads besides the shape (dispatch.hip: linear_kernel, and the lin4 rule of the deterministic mode):
     bool single_row = false;     // the operand has ONE row per sample (time embedding, RARM decode step, pooled CLIP token)
     int sample_rows = 0;         // rows per sample of the operand where the caller knows them (the UNet's blocks), 0 = unknown
+    int choice_rows = 0;         // > M: the op is a shared stage of a guided batch, run once on M of choice_rows logical rows (unet_body's prefix inside the
+                                 // first transformer): its kernel is chosen as for choice_rows rows, so a row's value does not depend on where the prefix ends
 };
 // 3x3 conv over [B, Hin, Win, C0 (+ C1)] NHWC -> [B, Hout, Wout, N]: stride 1 / 2, or ups = 1: on the nearest-2x upsampled input
 struct Conv3Op {
@@ -338,12 +343,12 @@ struct Ops {
     bool const_weights = true;
     const bf16_t* derived(const bf16_t* W, int N, int K, int kind);
     // the dispatch proper (dispatch.hip, documented there).  Nothing that chooses a kernel is state of Ops: it travels in the op.
-    bool lin4_takes(const LinearOp& op);          // reads M, N, C0, C1, a1_wrap_rows, res_wrap_rows
+    bool lin4_takes(const LinearOp& op);          // reads M, N, C0, C1, a0_wrap_rows, a1_wrap_rows, res_wrap_rows, rowvec (set or not), rowvec_ld, rows_per_sample
     void linear(const LinearOp& op);              // (ignores ln_*)
     bool linear_ln(const LinearOp& op);
     void conv3(const Conv3Op& op);
     int cur_block = -1, cur_layer = 0;           // position in the UNet's block table (debug tap)
-    void tap(int stage, const void* ptr, size_t nbytes);
+    void tap(int stage, const void* ptr, size_t nbytes, bool twice = false);      // twice: ptr holds the first half of the logical tensor, whose second half equals it
     bool prof_open = false;
     const char* tag = "";        // role of the ops that follow in the graph ("st.proj_in", "res.conv1", ...): rdm_prof_dump groups by it
     void prof_begin(int kind, double work, int d0 = 0, int d1 = 0, int d2 = 0);

@@ -614,11 +614,12 @@ hipError_t launch_igemm(const IgemmParams& p_in, bool conv, int batch, hipStream
     // tall 256-row tiles (8 waves, 1 block/CU) cut the L2->LDS operand traffic per FLOP by 1.44x; use them
     // whenever there are enough row tiles to fill the chip, else the 128-row tile (4 waves, 2 blocks/CU).
     const bool wide = (p.N % 192 == 0);
-    const long long tiles256 = (long long)((p.M + 255) / 256) * ((p.N + (wide ? 191 : 127)) / (wide ? 192 : 128)) * batch;
+    const int Mc = p.choice_rows > p.M ? p.choice_rows : p.M;
+    const long long tiles256 = (long long)((Mc + 255) / 256) * ((p.N + (wide ? 191 : 127)) / (wide ? 192 : 128)) * batch;
     const bool tall = tiles256 >= 256 && p.M > 128;      // 8 waves, 3-deep A ring: the HBM latency of the activation stream is covered
                                                    // (M <= 128 rows per batch item: a 256-row tile would be mostly padding)
     if (!conv && p.Wfrag && lin4_supported(p, batch)) return launch_lin4(p, st);       // lin4.hip
-    if (p.a1_wrap_rows > 0 || p.res_wrap_rows > 0) return hipErrorInvalidValue;                               // a wrapped second source is read by lin4 only
+    if (p.a0_wrap_rows > 0 || p.a1_wrap_rows > 0 || p.res_wrap_rows > 0) return hipErrorInvalidValue;         // a wrapped source or residual is read by lin4 only
     if (p.act == ACT_GEGLU) {
         if (conv) return hipErrorInvalidValue;
         // 256-wide tile (x and gate interleaved: 128 outputs): the A tile is re-read once per column tile, and the

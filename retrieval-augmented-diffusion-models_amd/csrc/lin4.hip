@@ -85,11 +85,12 @@ __device__ __forceinline__ unsigned long long l4_uni64(unsigned long long v) {  
     return ((unsigned long long)hi << 32) | lo;
 }
 __device__ __forceinline__ ASrc l4_asrc(bool dead, int row0, int kc, int C0, const char* A0p, const char* A1p, unsigned ld0, unsigned ld1,
-                                        const char* zero, unsigned voffA0, unsigned voffA1, unsigned lane16, int wrap1) {
+                                        const char* zero, unsigned voffA0, unsigned voffA1, unsigned lane16, int wrap0, int wrap1) {
     ASrc s;
     const bool second = kc >= C0;
     const unsigned ld = second ? ld1 : ld0;
     if (second && row0 >= wrap1) row0 -= wrap1;             // second source holds wrap1 rows only (IgemmParams::a1_wrap_rows; at most two copies)
+    if (!second && row0 >= wrap0) row0 -= wrap0;            // and the first wrap0 (IgemmParams::a0_wrap_rows)
     const char* b = (second ? A1p : A0p) + (unsigned long long)row0 * ld + (unsigned)((second ? kc - C0 : kc) * 2);
     s.base = (const char*)l4_uni64((unsigned long long)(dead ? zero : b));
     s.pstride = (unsigned)__builtin_amdgcn_readfirstlane((int)(dead ? 0u : 32u * ld));
@@ -137,6 +138,7 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
     const char* const zero = (const char*)p.zero_page;
     const char* const Wf = (const char*)p.Wfrag;
     const unsigned ld0 = (unsigned)(p.lda > 0 ? p.lda : p.C0) * 2u, ld1 = (unsigned)p.C1 * 2u;     // row strides in bytes
+    const int wrap0 = p.a0_wrap_rows > 0 ? p.a0_wrap_rows : 0x7fffffff;
     const int wrap1 = p.a1_wrap_rows > 0 ? p.a1_wrap_rows : 0x7fffffff;
 
     // ---- per-lane constants
@@ -169,7 +171,7 @@ __global__ __launch_bounds__(256, 1) void lin4_kernel(IgemmParams p) {
         return (const char*)l4_uni64((unsigned long long)(Wf + off));
     };
     auto a_src = [&](const Cur& c) __attribute__((always_inline)) {
-        return l4_asrc(c.tile >= t_end, c.bm * BM, c.sl * BK, C0, A0p, A1p, ld0, ld1, zero, voffA0, voffA1, lane16, wrap1);
+        return l4_asrc(c.tile >= t_end, c.bm * BM, c.sl * BK, C0, A0p, A1p, ld0, ld1, zero, voffA0, voffA1, lane16, wrap0, wrap1);
     };
 
     asm volatile("" ::: H4_ACC_CLOBBERS);                    // the kernel descriptor must allocate the accumulator AGPRs
@@ -580,11 +582,13 @@ bool lin4_supported(const IgemmParams& p, int batch) {
     if (p.C1 > 0 && p.lda > 0) return false;
     if (p.res_wrap_rows > 0 && (!p.res_bf16 || p.res_wrap_rows % (128 * wm) != 0 || 2LL * p.res_wrap_rows < p.M)) return false;
     if (p.a1_wrap_rows > 0 && (p.C1 == 0 || p.a1_wrap_rows % (128 * wm) != 0 || 2LL * p.a1_wrap_rows < p.M)) return false;     // whole tiles, at most two copies
+    if (p.a0_wrap_rows > 0 && (p.a0_wrap_rows % (128 * wm) != 0 || 2LL * p.a0_wrap_rows < p.M)) return false;      // the same for the first source
     // LayerNorm folded in: one source of >= 2 slices, no residual (the bias rides in ln_sb), everything in 160 KiB of LDS
     if (p.ln_sb && (p.C1 > 0 || p.K < 128 || p.res_bf16 || p.bias || lin4_smem_bytes(p, wm) > 160 * 1024 || !(p.ln_inv_c > 0.f))) return false;
     // far fewer tiles than CUs: the 128-row tiles of igemm.hip (160 tiles -- the 8x8-level projections -- still win here: 28 vs 32 us)
     constexpr int L4_MIN_TILES = 128;
-    if (!p.l4_any_tiles && (long long)(p.M / (128 * wm)) * (p.N / (wm == 1 ? 384 : 192)) < L4_MIN_TILES) return false;
+    const int Mc = p.choice_rows > p.M ? p.choice_rows : p.M;       // (a shared stage of a guided batch counts the tiles of the whole batch)
+    if (!p.l4_any_tiles && (long long)(Mc / (128 * wm)) * (p.N / (wm == 1 ? 384 : 192)) < L4_MIN_TILES) return false;
     return true;
 }
 

@@ -99,8 +99,12 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
     // Shared guidance prefix: with classifier-free guidance the batch is [x | x] with the SAME x and t in both halves and different
     // contexts (ddim.py:229-234), so every layer before the first SpatialTransformer (conv_in, the 64x64 ResBlocks, the first
     // Downsample, the first 32x32 ResBlock: 12 % of the conv FLOPs, 17 % of the GroupNorm bytes) computes identical values for the two
-    // halves.  They run once on Bfull/2 samples; the activations (and the skip tensors already pushed) are duplicated right before the
-    // first context-dependent layer.  B below is the batch the CURRENT layer runs on.
+    // halves -- and so does that transformer up to its cross-attention, the first op that reads the context: its GroupNorm, proj_in,
+    // norm1, the q | k | v projection and the self-attention (at 32 x 32: one of the model's three most expensive attention layers).
+    // All of these run once on Bfull/2 samples.  The prefix ends at attn1.to_out, which runs on all Bfull samples (its start values
+    // differ between the halves: the bias fold below) and reads its operand and its residual with a row wrap; the block's input and
+    // the skip tensors already pushed are wrapped by their readers or duplicated there (leave_prefix).  Deterministic mode, and
+    // rdm_debug_guidance_prefix(ctx, 0), end the prefix in front of the transformer.  B below is the batch the CURRENT layer runs on.
     B = (Bshared > 0 && Bshared * 2 == Bfull) ? Bshared : Bfull;
     // (block outputs produced inside the prefix are allocated for Bfull samples and written into the first half, so leaving the
     //  prefix costs one copy of B samples per tensor: first half -> second half)
@@ -111,6 +115,16 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
     };
     // Skip tensors pushed inside the prefix are NOT duplicated when their readers can wrap the batch index instead (GroupNorm's and the
     // skip_connection GEMM's second source: 4 of the 5 copies, 0.24 ms of a 34.5 ms forward); resblock() materialises one on demand.
+    // Leaving the prefix at transformer s0, whose input is `in`: from here on B = Bfull.
+    auto leave_prefix = [&](const StW& s0, Act& in) {
+        // the activation itself is duplicated only where its readers cannot wrap the batch index instead (transformer())
+        const int n0 = in.H * in.W, Mfull = Bfull * n0;
+        if (!o.c->deterministic && o.lin4_takes({.C0 = 4 * s0.lc, .C1 = s0.c, .M = Mfull, .N = s0.c, .res_wrap_rows = (Bfull / 2) * n0})) in.half = true;
+        else expand(in);
+        for (Act& a : hs) { if (o.c->deterministic) expand(a); else a.half = true; }
+        B = Bfull;
+    };
+    const bool through_attn1 = o.c->prefix_through_attn1 && !o.c->deterministic;
 
     auto resblock = [&](const ResW& r, const Act& a, Act* skip) -> Act {
         const int C0 = a.C, C1 = skip ? skip->C : 0, HW = a.H * a.W, M = B * HW;
@@ -152,67 +166,83 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         o.tap(5, out, (size_t)M * r.cout * 2);
         return Act{out, r.cout, a.H, a.W, r.lout};
     };
-    auto transformer = [&](const StW& s, const Act& a) -> Act {
-        const int C = s.c, n = a.H * a.W, M = B * n;
-        // a.half: the input left the shared guidance prefix and only its first Bfull / 2 samples exist: its two readers -- the entry GroupNorm and
-        // the residual of ff.net.2 x proj_out -- wrap the batch index (round 5: no 50 MB duplication pass per forward)
-        const int in_wrap = a.half ? Bfull / 2 : 0;
-        bf16_t* xn = o.abf((size_t)M * C);
-        o.tag = "st.gn";
-        o.groupnorm({.x0 = a.p, .C0 = C, .HW = n, .B = B, .L0 = s.lc, .gamma = o.w<float>(s.gng), .beta = o.w<float>(s.gnb), .eps = 1e-6f, .out = xn, .x0_bmod = in_wrap});
-        o.tap(1, xn, (size_t)M * C * 2);
-        bf16_t* t0 = o.abf((size_t)M * C);
-        o.tag = "st.proj_in";
-        o.linear({.A0 = xn, .C0 = C, .W = o.w<bf16_t>(s.win), .bias = o.w<float>(s.bin), .M = M, .N = C, .out_bf16 = t0, .sample_rows = n});
-        o.tap(2, t0, (size_t)M * C * 2);
-        // --- attn1 (self)
-        bf16_t* l1 = o.abf((size_t)M * C);
-        // n % 64 == 0: q | k | v in ONE projection (to_v's rows follow to_q | to_k in the blob, asserted in build_unet); the flash kernel
-        // reads the token-major V block through transpose reads, so no per-layer V^T GEMM (6.8 % of the forward as a batched
-        // weights-as-A GEMM at 380 TFLOP/s)
-        const bool vrow = (n % 64 == 0) && s.v_follows;
-        const int QW = vrow ? 3 * C : 2 * C;
-        bf16_t* qk = o.abf((size_t)M * QW);
-        o.tag = "st.norm1+qkv";
-        o.layernorm({.x_bf16 = t0, .gamma = o.w<float>(s.ln1g), .beta = o.w<float>(s.ln1b), .M = M, .C = C, .out_bf16 = l1, .Clog = s.lc});
-        o.tap(3, l1, (size_t)M * C * 2);
-        o.linear({.A0 = l1, .C0 = C, .W = o.w<bf16_t>(s.wqk), .M = M, .N = QW, .out_bf16 = qk, .sample_rows = n});
-        o.tap(4, qk, (size_t)M * QW * 2);
-        bf16_t* ao = o.abf((size_t)M * C);
-        o.tag = "st.self_attention";
-        if (vrow) {
-            o.flash_d32({.q = qk, .ldq = QW, .v = qk + 2 * C, .out = ao, .n = n}, s.heads, B);
-        } else if (n % 32 == 0) {
-            bf16_t* vt = o.abf((size_t)M * C);      // V^T per sample: [B][C][n] via swapped-operand GEMM
-            if (!o.plan) {
-                IgemmParams p = o.base(C, n, C);
-                p.A0 = o.w<bf16_t>(s.wv); p.C0 = C; p.W = l1; p.sA = 0; p.sW = (long long)n * C; p.sO = (long long)C * n;
-                p.out_bf16 = vt; p.ldo = n;
-                o.check(launch_igemm(p, false, B, o.c->stream), "v^T gemm");
-            }
-            o.flash_d32({.q = qk, .ldq = 2 * C, .vt = vt, .out = ao, .n = n}, s.heads, B);
-        } else {
-            bf16_t* v = o.abf((size_t)M * C);
-            o.linear({.A0 = l1, .C0 = C, .W = o.w<bf16_t>(s.wv), .M = M, .N = C, .out_bf16 = v, .sample_rows = n});
-            o.small_attention({.q = qk, .ldq = 2 * C, .k = qk + C, .ldk = 2 * C, .v = v, .ldv = C, .out = ao, .ldo = C, .nq = n, .nkv = n, .scale = 1.0f / sqrtf(32.f)},
-                              32, s.heads, B, "small self attention");
-        }
-        o.tap(5, ao, (size_t)M * C * 2);
-        bf16_t* t1 = o.abf((size_t)M * C);
-        // --- attn2 (cross over the k neighbours); samples >= Bx have all-zero neighbours: t2 = t1 + b_o exactly (see add_bias_rows_kernel)
+    auto transformer = [&](const StW& s, Act& a) -> Act {
+        const int C = s.c, n = a.H * a.W;
+        // pre: still inside the shared guidance prefix (the first transformer of a guided forward).  The stages up to the self-attention
+        // run on the Bs = Bfull / 2 samples that exist (Ms rows); everything from attn1.to_out on runs on Bfull samples (M rows).
+        const bool pre = B < Bfull;
+        const int Bs = B, Ms = Bs * n, M = Bfull * n;
+        // attn2 (cross over the k neighbours); samples >= Bx have all-zero neighbours: t2 = t1 + b_o exactly (see add_bias_rows_kernel)
         const int Mx = Bx * n;
         // norm2 + attn2 + residual in one kernel when the neighbours' operands are cached (xa), norm2 too when no channel is padding
         const bool xfused = xa && Mx > 0 && xattn_fused_supported({.rows = Mx, .n = n, .C = C, .NP = XA_NP, .ncols = s.heads * k, .group = k});
         const bool xln = xfused && s.lc == C && C <= 2048;
-        // Round 5: in a guided batch [conditional | unconditional] (Bx = B / 2) with the LayerNorm-fused cross-attention kernel,
+        // Round 5: in a guided batch [conditional | unconditional] (Bx = Bfull / 2) with the LayerNorm-fused cross-attention kernel,
         //   * the unconditional rows' t2 = attn1.to_out(...) + t0 + b_o2 leaves attn1.to_out's GEMM directly (b_o2 rides in the start
         //     values of those rows: Ops::linear's rowvec; one rounding less than t1 -> + b_o2), no add_bias_rows pass;
         //   * the cross-attention kernel runs IN PLACE on the conditional rows (t2 aliases t1) and emits norm3 of its finished rows, so
         //     the separate LayerNorm-3 pass only covers the unconditional rows.
         const bool xfold_shape = xln && !o.c->deterministic;
-        const bool bias_fold = xfold_shape && Bx * 2 == B;             // the unconditional half exists and is exactly the second half
+        const bool bias_fold = xfold_shape && Bx * 2 == Bfull;          // the unconditional half exists and is exactly the second half
+        // attn1.to_out then reads its operand ao and its residual t0, which hold Ms rows, with a row wrap where lin4 takes the op in that
+        // form (pre_wrap); elsewhere (few tiles, other widths) both are duplicated into buffers of M rows first
+        const bool pre_wrap = pre && o.lin4_takes({.C0 = C, .M = M, .N = C, .rowvec = bias_fold ? o.w<float>(s.bo2) : nullptr /* set or not is all that is read */,
+                                                   .rowvec_ld = C, .rows_per_sample = Mx, .a0_wrap_rows = Ms, .res_wrap_rows = Ms});
+        const size_t Mh = pre_wrap ? Ms : M;         // rows allocated for t0 and ao
+        // a.half: the input left the shared guidance prefix and only its first Bfull / 2 samples exist: its two readers -- the entry GroupNorm and
+        // the residual of ff.net.2 x proj_out -- wrap the batch index (round 5: no 50 MB duplication pass per forward).  (pre: the GroupNorm
+        // runs on those samples alone, and a.half is decided where the prefix is left, below)
+        bf16_t* xn = o.abf((size_t)Ms * C);
+        o.tag = "st.gn";
+        o.groupnorm({.x0 = a.p, .C0 = C, .HW = n, .B = Bs, .L0 = s.lc, .gamma = o.w<float>(s.gng), .beta = o.w<float>(s.gnb), .eps = 1e-6f, .out = xn,
+                     .x0_bmod = a.half ? Bfull / 2 : 0});
+        o.tap(1, xn, (size_t)Ms * C * 2, pre);
+        bf16_t* t0 = o.abf(Mh * C);
+        o.tag = "st.proj_in";
+        o.linear({.A0 = xn, .C0 = C, .W = o.w<bf16_t>(s.win), .bias = o.w<float>(s.bin), .M = Ms, .N = C, .out_bf16 = t0, .sample_rows = n, .choice_rows = M});
+        o.tap(2, t0, (size_t)Ms * C * 2, pre);
+        // --- attn1 (self)
+        bf16_t* l1 = o.abf((size_t)Ms * C);
+        // n % 64 == 0: q | k | v in ONE projection (to_v's rows follow to_q | to_k in the blob, asserted in build_unet); the flash kernel
+        // reads the token-major V block through transpose reads, so no per-layer V^T GEMM (6.8 % of the forward as a batched
+        // weights-as-A GEMM at 380 TFLOP/s)
+        const bool vrow = (n % 64 == 0) && s.v_follows;
+        const int QW = vrow ? 3 * C : 2 * C;
+        bf16_t* qk = o.abf((size_t)Ms * QW);
+        o.tag = "st.norm1+qkv";
+        o.layernorm({.x_bf16 = t0, .gamma = o.w<float>(s.ln1g), .beta = o.w<float>(s.ln1b), .M = Ms, .C = C, .out_bf16 = l1, .Clog = s.lc});
+        o.tap(3, l1, (size_t)Ms * C * 2, pre);
+        o.linear({.A0 = l1, .C0 = C, .W = o.w<bf16_t>(s.wqk), .M = Ms, .N = QW, .out_bf16 = qk, .sample_rows = n, .choice_rows = M});
+        o.tap(4, qk, (size_t)Ms * QW * 2, pre);
+        bf16_t* ao = o.abf(Mh * C);
+        o.tag = "st.self_attention";
+        if (vrow) {
+            o.flash_d32({.q = qk, .ldq = QW, .v = qk + 2 * C, .out = ao, .n = n}, s.heads, Bs);
+        } else if (n % 32 == 0) {
+            bf16_t* vt = o.abf((size_t)Ms * C);      // V^T per sample: [B][C][n] via swapped-operand GEMM
+            if (!o.plan) {
+                IgemmParams p = o.base(C, n, C);
+                p.A0 = o.w<bf16_t>(s.wv); p.C0 = C; p.W = l1; p.sA = 0; p.sW = (long long)n * C; p.sO = (long long)C * n;
+                p.out_bf16 = vt; p.ldo = n;
+                o.check(launch_igemm(p, false, Bs, o.c->stream), "v^T gemm");
+            }
+            o.flash_d32({.q = qk, .ldq = 2 * C, .vt = vt, .out = ao, .n = n}, s.heads, Bs);
+        } else {
+            bf16_t* v = o.abf((size_t)Ms * C);
+            o.linear({.A0 = l1, .C0 = C, .W = o.w<bf16_t>(s.wv), .M = Ms, .N = C, .out_bf16 = v, .sample_rows = n, .choice_rows = M});
+            o.small_attention({.q = qk, .ldq = 2 * C, .k = qk + C, .ldk = 2 * C, .v = v, .ldv = C, .out = ao, .ldo = C, .nq = n, .nkv = n, .scale = 1.0f / sqrtf(32.f)},
+                              32, s.heads, Bs, "small self attention");
+        }
+        o.tap(5, ao, (size_t)Ms * C * 2, pre);
+        if (pre) {             // the first context-dependent op follows: leave the shared prefix (B = Bfull from here on)
+            leave_prefix(s, a);
+            if (!pre_wrap) { Act t0a{t0, C, a.H, a.W, s.lc}, aoa{ao, C, a.H, a.W, s.lc}; expand(t0a); expand(aoa); }
+        }
+        bf16_t* t1 = o.abf((size_t)M * C);
+        // --- attn2 (the forms chosen at the top)
         o.tag = "st.attn1.to_out";
         LinearOp to_out{.A0 = ao, .C0 = C, .W = o.w<bf16_t>(s.wo1), .bias = o.w<float>(s.bo1), .M = M, .N = C, .res_bf16 = t0, .out_bf16 = t1, .sample_rows = n};
+        if (pre_wrap) to_out.a0_wrap_rows = to_out.res_wrap_rows = Ms;
         if (bias_fold) {
             const float* zb = o.plan ? nullptr : o.c->zero_bias_pair(o.w<float>(s.bo2), C);
             if (!o.plan && !zb && o.rc == 0) o.rc = o.c->fail(-2, "out of memory for a bias table");
@@ -279,7 +309,7 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         // t3 = ff W_2^T + b_2 + t2 and out = t3 W_out^T + b_out + x are one GEMM over the K-concatenated operand [ff | t2]
         // (dual-source A) with the product weights built by the packer: t3 never exists (2 of 9 tensor passes, one launch)
         o.linear({.A0 = ff, .A1 = t2, .C0 = FI, .C1 = C, .W = o.w<bf16_t>(s.wfo), .bias = o.w<float>(s.bfo), .M = M, .N = C, .res_bf16 = a.p, .out_bf16 = out,
-                  .res_wrap_rows = in_wrap * n, .sample_rows = n});
+                  .res_wrap_rows = a.half ? (Bfull / 2) * n : 0, .sample_rows = n});
         o.tap(10, out, (size_t)M * C * 2);
         return Act{out, C, a.H, a.W, s.lc};
     };
@@ -298,16 +328,8 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
                 } break;
                 case 1: h = resblock(u.res[L.idx], h, (first && skip) ? skip : nullptr); break;
                 case 2:
-                    if (B < Bfull) {       // first context-dependent layer: leave the shared prefix
-                        {   // the activation itself is duplicated only where its readers cannot wrap the batch index instead (transformer())
-                            const StW& s0 = u.st[L.idx];
-                            const int n0 = h.H * h.W, Mfull = Bfull * n0;
-                            if (!o.c->deterministic && o.lin4_takes({.C0 = 4 * s0.lc, .C1 = s0.c, .M = Mfull, .N = s0.c, .res_wrap_rows = (Bfull / 2) * n0})) h.half = true;
-                            else expand(h);
-                        }
-                        for (Act& a : hs) { if (o.c->deterministic) expand(a); else a.half = true; }
-                        B = Bfull;
-                    }
+                    // the first context-dependent layer: the shared prefix ends inside it, at attn1.to_out (transformer()), or in front of it
+                    if (B < Bfull && !through_attn1) leave_prefix(u.st[L.idx], h);
                     h = transformer(u.st[L.idx], h); break;
                 case 3: {
                     const ConvW& d = u.down[L.idx];
@@ -376,6 +398,12 @@ int rdm_unet_forward(rdm_ctx* c, const float* x, const int64_t* t, const float* 
 int rdm_debug_tap(rdm_ctx* c, void* buf, size_t nbytes, int block, int sub) {
     if (!c) return -1;
     c->tap_buf = buf; c->tap_bytes = buf ? nbytes : 0; c->tap_block = buf ? block : -1; c->tap_sub = buf ? sub : 0;
+    return 0;
+}
+
+int rdm_debug_guidance_prefix(rdm_ctx* c, int through_attn1) {
+    if (!c) return -1;
+    c->prefix_through_attn1 = through_attn1 != 0;
     return 0;
 }
 
