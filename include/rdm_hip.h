@@ -499,6 +499,30 @@ typedef struct rdm_knn_stages {
 int rdm_knn_select(long long n, int dim, int b, int k, rdm_knn_form* form_out);
 int rdm_op_knn_stages(rdm_ctx* ctx, const float* q, int b, int k, uint32_t* idx_out, float* score_out, rdm_knn_stages* stages);
 int rdm_db_rows(rdm_ctx* ctx, long long row0, long long rows, void* out_f16);
+/* ---- filtered retrieval: the exact top-k over the rows a per-query bitmap allows (conditioning on a class, a style subset, a held-out
+ *      split, a deny list) in ONE pass over the resident database, whatever the number of different masks in the batch.
+ * A mask is rdm_knn_mask_words(n) 64-bit words (n rounded up to the scans' 256-row tile, / 64; host only): bit r % 64 of word r / 64 set
+ *   = row r may be returned.  Bits at or beyond n are ignored (all-ones words are fine).
+ * rdm_knn_filtered: rdm_knn with allow [dev] uint64 [n_masks, words] and mask_of_query [host] int32 [b] (NULL: every query uses mask
+ *   0).  Same order and scores as rdm_knn, over the allowed rows only: disallowed rows enter no candidate list and are skipped by the
+ *   exact fallback, so the exactness certificate holds unchanged for the subset.  A query whose mask allows fewer than k rows gets
+ *   those rows followed by (0xffffffff, -inf) entries, and the call succeeds.  Refused: allow == NULL, n_masks < 1, a mask_of_query
+ *   entry outside [0, n_masks) (the message names the query), zero-norm queries as in rdm_knn.  rdm_knn_last_fallback reports on it.
+ *   The filter is an argument of the call: nothing of it stays on the context.
+ * rdm_knn_filtered_f64: the same with the fp64 scores (rdm_knn_f64; shard merges).
+ * rdm_op_knn_stages_filtered: rdm_op_knn_stages through the launches of rdm_knn_filtered.
+ * rdm_op_row_mask: one mask from rows [dev] int64 [n_rows] (duplicates allowed; invert = 1: the complement within [0, n)) into
+ *   bits_out [dev] uint64 [words]; an index outside [0, n) is an error (found by the kernel, reported after it).
+ * rdm_op_row_mask_count: counts_out [host] [n_masks] = allowed rows below n of each mask of allow [dev] [n_masks, words]. */
+int rdm_knn_mask_words(long long n);
+int rdm_knn_filtered(rdm_ctx* ctx, const float* q, int b, int k, const uint64_t* allow, int n_masks, const int32_t* mask_of_query,
+                     uint32_t* idx_out, float* score_out);
+int rdm_knn_filtered_f64(rdm_ctx* ctx, const float* q, int b, int k, const uint64_t* allow, int n_masks, const int32_t* mask_of_query,
+                         uint32_t* idx_out, double* score_out);
+int rdm_op_knn_stages_filtered(rdm_ctx* ctx, const float* q, int b, int k, const uint64_t* allow, int n_masks, const int32_t* mask_of_query,
+                               uint32_t* idx_out, float* score_out, rdm_knn_stages* stages);
+int rdm_op_row_mask(rdm_ctx* ctx, const int64_t* rows, long long n_rows, long long n, int invert, uint64_t* bits_out);
+int rdm_op_row_mask_count(rdm_ctx* ctx, const uint64_t* allow, int n_masks, long long n, long long* counts_out);
 
 /* ---- multi-GPU: one process and one context per device; the path has ONE exchange, an all-gather -- of the
  * decoded images (replicated database) or of the per-shard (index, score) top-k pairs (row-sharded database).  Thin wrappers

@@ -183,6 +183,12 @@ SIGNATURES = {
     "rdm_knn_select": (C.c_int, [C.c_longlong, C.c_int, C.c_int, C.c_int, C.POINTER(KnnForm)]),
     "rdm_op_knn_stages": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P, C.POINTER(KnnStages)]),
     "rdm_db_rows": (C.c_int, [_P, C.c_longlong, C.c_longlong, _P]),
+    "rdm_knn_mask_words": (C.c_int, [C.c_longlong]),
+    "rdm_knn_filtered": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "rdm_knn_filtered_f64": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P]),
+    "rdm_op_knn_stages_filtered": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, C.c_int, _P, _P, _P, C.POINTER(KnnStages)]),
+    "rdm_op_row_mask": (C.c_int, [_P, _P, C.c_longlong, C.c_longlong, C.c_int, _P]),
+    "rdm_op_row_mask_count": (C.c_int, [_P, _P, C.c_int, C.c_longlong, _P]),
     "rdm_set_deterministic": (C.c_int, [_P, C.c_int]),
     "rdm_get_deterministic": (C.c_int, [_P]),
     "rdm_prof_enable": (C.c_int, [_P, C.c_int]),
@@ -345,6 +351,64 @@ def knn_select(n, dim, b, k):
         raise RdmError(f"rdm_knn_select(n={n}, dim={dim}, b={b}, k={k}): arguments the search refuses")
     return {"path": KNN_SCAN_PATHS[f.path], "ksel": f.ksel, "rescored": f.rescored, "lists_per_block": f.lists_per_block,
             "queries_per_launch": f.queries_per_launch, "eps": float(f.eps)}
+
+
+NO_ROW = 0xffffffff          # the index a filtered search returns where a mask allows fewer than k rows (its score is -inf)
+
+
+def knn_mask_words(n):
+    """64-bit words of one row mask for a database of n rows: n rounded up to the scans' 256-row tile, / 64 (rdm_knn_mask_words)."""
+    return int(lib.rdm_knn_mask_words(int(n)))
+
+
+def pack_row_mask(allowed):
+    """Host packer: bool [n] -> int64 [knn_mask_words(n)] holding the uint64 words of the mask, bit r % 64 of word r / 64 = allowed[r]."""
+    a = np.asarray(allowed)
+    if a.dtype != np.bool_ or a.ndim != 1 or a.shape[0] < 1:
+        raise RdmError(f"pack_row_mask: a boolean array of length n >= 1, got {a.dtype} {a.shape}")
+    bits = np.zeros(knn_mask_words(a.shape[0]) * 64, dtype=np.bool_)
+    bits[:a.shape[0]] = a
+    return np.packbits(bits, bitorder="little").view(np.uint64).view(np.int64).copy()
+
+
+def shard_row_mask(rows, row0, n_local):
+    """The local index list of the shard holding the global rows [row0, row0 + n_local): rows (int array, or bool array over the whole
+    database) -> sorted int64 local indices.  row0 need not be a multiple of 64: every shard builds its own mask from local indices."""
+    r = np.asarray(rows)
+    if r.dtype == np.bool_:
+        r = np.flatnonzero(r)
+    if r.ndim != 1 or (r.size and not np.issubdtype(r.dtype, np.integer)):
+        raise RdmError(f"shard_row_mask: rows must be a 1-d integer or boolean array, got {r.dtype} {r.shape}")
+    r = r.astype(np.int64)
+    if (r < 0).any():
+        raise RdmError("shard_row_mask: negative row index")
+    r = r[(r >= row0) & (r < row0 + n_local)] - int(row0)
+    return np.unique(r)
+
+
+def row_filter_args(allow, mask_of_query, b, words):
+    """Checks of Context.knn's filter arguments that need no device -> (allow as [n_masks, words], n_masks, int32 ids or None)."""
+    if allow is None:
+        if mask_of_query is not None:
+            raise RdmError("knn: mask_of_query needs allow")
+        return None, 0, None
+    if not isinstance(allow, torch.Tensor) or allow.dtype != torch.int64:
+        raise RdmError("knn: allow must be an int64 tensor holding the masks' 64-bit words (Context.row_mask / pack_row_mask)")
+    if allow.ndim == 1:
+        allow = allow[None]
+    if allow.ndim != 2 or allow.shape[1] != words or allow.shape[0] < 1:
+        raise RdmError(f"knn: allow must be [n_masks, {words}] for this database, got {tuple(allow.shape)}")
+    n_masks = int(allow.shape[0])
+    ids = None
+    if mask_of_query is not None:
+        ids = np.ascontiguousarray(mask_of_query.cpu().numpy() if isinstance(mask_of_query, torch.Tensor) else mask_of_query)
+        if ids.shape != (b,) or not np.issubdtype(ids.dtype, np.integer):
+            raise RdmError(f"knn: mask_of_query must hold one integer per query ([{b}]), got {ids.dtype} {ids.shape}")
+        bad = np.flatnonzero((ids < 0) | (ids >= n_masks))
+        if bad.size:
+            raise RdmError(f"knn: query {int(bad[0])} names mask {int(ids[bad[0]])}: mask_of_query must lie in [0, {n_masks})")
+        ids = ids.astype(np.int32)
+    return allow, n_masks, ids
 
 
 def _ptr(t):
@@ -1377,30 +1441,77 @@ class Context:
     def db_size(self):
         return int(lib.rdm_db_size(self._h))
 
-    def knn(self, q, k, f64=False):
-        """-> (idx int32 holding uint32 bits [b,k], score f32 [b,k]); f64=True: the fp64 scores the ranking was made on (shard merges)."""
+    def knn(self, q, k, f64=False, allow=None, mask_of_query=None):
+        """-> (idx int32 holding uint32 bits [b,k], score f32 [b,k]); f64=True: the fp64 scores the ranking was made on (shard merges).
+        allow: int64 [n_masks, words] (or [words]) row masks on the device (row_mask), mask_of_query: one mask index per query (None:
+        mask 0 for all) -- the exact top-k over the rows each query's mask allows (rdm_knn_filtered); a query with fewer than k allowed
+        rows gets them followed by (NO_ROW, -inf).  allow=None: the unfiltered search."""
         q = self._dev(q, torch.float32)
         if q.ndim != 2:
             raise RdmError(f"knn: queries must be [b,dim], got {tuple(q.shape)}")
+        allow, n_masks, ids = row_filter_args(allow, mask_of_query, q.shape[0], knn_mask_words(self.db_size()))
         idx = torch.empty((q.shape[0], k), device=self.device, dtype=torch.int32)   # uint32 bits
         sc = torch.empty((q.shape[0], k), device=self.device, dtype=torch.float64 if f64 else torch.float32)
-        fn = lib.rdm_knn_f64 if f64 else lib.rdm_knn
-        self._check(fn(self._h, _ptr(q), q.shape[0], k, _ptr(idx), _ptr(sc)))
+        if allow is None:
+            fn = lib.rdm_knn_f64 if f64 else lib.rdm_knn
+            self._check(fn(self._h, _ptr(q), q.shape[0], k, _ptr(idx), _ptr(sc)))
+        else:
+            allow = self._dev(allow, torch.int64)
+            fn = lib.rdm_knn_filtered_f64 if f64 else lib.rdm_knn_filtered
+            self._check(fn(self._h, _ptr(q), q.shape[0], k, _ptr(allow), n_masks, None if ids is None else ids.ctypes.data_as(_P),
+                           _ptr(idx), _ptr(sc)))
         return idx, sc
+
+    def row_mask(self, rows_or_bool, invert=False):
+        """-> int64 [words] on the device: the mask that allows the listed rows of the loaded database (rdm_op_row_mask).  Takes an index
+        array or tensor (duplicates allowed), or a boolean array of length n; invert: the complement within [0, n)."""
+        n = self.db_size()
+        if n <= 0:
+            raise RdmError("row_mask: no database loaded")
+        r = rows_or_bool
+        if isinstance(r, torch.Tensor):
+            if r.dtype == torch.bool:
+                if r.shape != (n,):
+                    raise RdmError(f"row_mask: a boolean mask must have length {n}, got {tuple(r.shape)}")
+                r = torch.nonzero(r.reshape(-1)).reshape(-1)
+            r = r.reshape(-1).to(device=self.device, dtype=torch.int64).contiguous()
+        else:
+            r = np.asarray(r)
+            if r.dtype == np.bool_:
+                if r.shape != (n,):
+                    raise RdmError(f"row_mask: a boolean mask must have length {n}, got {r.shape}")
+                r = np.flatnonzero(r)
+            if r.size and not np.issubdtype(r.dtype, np.integer):
+                raise RdmError(f"row_mask: row indices must be integers, got {r.dtype}")
+            r = torch.from_numpy(np.ascontiguousarray(r.reshape(-1).astype(np.int64))).to(self.device)
+        bits = torch.empty(knn_mask_words(n), device=self.device, dtype=torch.int64)
+        self._check(lib.rdm_op_row_mask(self._h, _ptr(r) if r.numel() else None, r.numel(), n, int(bool(invert)), _ptr(bits)))
+        return bits
+
+    def row_mask_count(self, allow):
+        """-> int64 numpy [n_masks]: allowed rows (below n) of each mask of allow int64 [n_masks, words] or [words]."""
+        allow, n_masks, _ = row_filter_args(allow, None, 0, knn_mask_words(self.db_size()))
+        if allow is None:
+            raise RdmError("row_mask_count: allow is None")
+        allow = self._dev(allow, torch.int64)
+        out = np.zeros(n_masks, dtype=np.int64)
+        self._check(lib.rdm_op_row_mask_count(self._h, _ptr(allow), n_masks, self.db_size(), out.ctypes.data_as(_P)))
+        return out
 
     def knn_last_fallback(self):
         return int(lib.rdm_knn_last_fallback(self._h))
 
-    def knn_stages(self, q, k):
+    def knn_stages(self, q, k, allow=None, mask_of_query=None):
         """Context.knn for ONE query group (b <= 64, or 128 <= b <= 512 on the bulk path) with every stage copied out (rdm_op_knn_stages):
         a dict with idx, score (the final answer), qn f32 / qh, ql fp16 [rows, dim] (rows b.. are padding), cand_s f32 / cand_i int32
         holding uint32 bits [rows, nlists, ksel], and per query the merge's flag, tau, tau_idx, theta BEFORE the exact fallback, plus the
-        fields of knn_select."""
+        fields of knn_select.  allow / mask_of_query as in knn: the same read-out of the filtered search (rdm_op_knn_stages_filtered)."""
         q = self._dev(q, torch.float32)
         if q.ndim != 2:
             raise RdmError(f"knn_stages: queries must be [b,dim], got {tuple(q.shape)}")
         b, dim = q.shape
         n = self.db_size()
+        allow, n_masks, ids = row_filter_args(allow, mask_of_query, b, knn_mask_words(n))
         form = knn_select(n, dim, b, k)
         rows = form["queries_per_launch"]
         ntiles = (n + 255) // 256
@@ -1416,7 +1527,12 @@ class Context:
         st = KnnStages(rows_cap=rows, nlists_cap=cap)
         for name in ("qn", "qh", "ql", "cand_s", "cand_i", "flag", "tau", "tau_idx", "theta"):
             setattr(st, name, t[name].data_ptr())
-        self._check(lib.rdm_op_knn_stages(self._h, _ptr(q), b, k, _ptr(t["idx"]), _ptr(t["score"]), C.byref(st)))
+        if allow is None:
+            self._check(lib.rdm_op_knn_stages(self._h, _ptr(q), b, k, _ptr(t["idx"]), _ptr(t["score"]), C.byref(st)))
+        else:
+            allow = self._dev(allow, torch.int64)
+            self._check(lib.rdm_op_knn_stages_filtered(self._h, _ptr(q), b, k, _ptr(allow), n_masks,
+                                                       None if ids is None else ids.ctypes.data_as(_P), _ptr(t["idx"]), _ptr(t["score"]), C.byref(st)))
         used = st.rows * st.nlists * st.form.ksel
         for name in ("qn", "qh", "ql"):
             t[name] = t[name][:st.rows]

@@ -72,7 +72,8 @@ int rdm_db_load(rdm_ctx* c, const void* emb, long long n, int dim, int dtype, in
     return msg ? c->fail(-5, "rdm_db_load: %s", msg) : 0;
 }
 long long rdm_db_size(rdm_ctx* c) { return c ? c->db.n : -1; }
-static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out, rdm_knn_stages* stages = nullptr) {
+static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out, rdm_knn_stages* stages = nullptr,
+                     const KnnFilter* filt = nullptr) {
     RDM_ENTER(c);
     if (!c || !q || !idx_out) return c ? c->fail(-1, "null argument") : -1;
     const bool prof = (c->prof >> RDM_PROF_KNN) & 1u;
@@ -82,9 +83,9 @@ static int knn_entry(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out
         r.tag = "knn"; r.d0 = b; r.d1 = k; r.d2 = c->db.dim;
         hipEventRecord(r.a, c->stream); c->prof_recs.push_back(r);
     }
-    const char* msg = knn_search(c->db, q, b, k, idx_out, score_out, score64_out, c->stream, stages);
+    const char* msg = knn_search(c->db, q, b, k, idx_out, score_out, score64_out, c->stream, stages, filt);
     if (prof) hipEventRecord(c->prof_recs.back().b, c->stream);
-    return msg ? c->fail(-5, "rdm_knn: %s", msg) : 0;
+    return msg ? c->fail(-5, filt ? "rdm_knn_filtered: %s" : "rdm_knn: %s", msg) : 0;
 }
 int rdm_knn(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out) { return knn_entry(c, q, b, k, idx_out, score_out, nullptr); }
 int rdm_knn_f64(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, double* score_out) { return knn_entry(c, q, b, k, idx_out, nullptr, score_out); }
@@ -97,6 +98,36 @@ int rdm_knn_select(long long n, int dim, int b, int k, rdm_knn_form* out) {
 int rdm_op_knn_stages(rdm_ctx* c, const float* q, int b, int k, uint32_t* idx_out, float* score_out, rdm_knn_stages* stages) {
     if (c && !stages) return c->fail(-1, "rdm_op_knn_stages: null argument");
     return knn_entry(c, q, b, k, idx_out, score_out, nullptr, stages);
+}
+// ---- filtered retrieval: the filter is an argument of the call, nothing of it stays on the context
+int rdm_knn_mask_words(long long n) { return (int)knn_mask_words(n); }
+int rdm_knn_filtered(rdm_ctx* c, const float* q, int b, int k, const uint64_t* allow, int n_masks, const int32_t* mask_of_query, uint32_t* idx_out,
+                     float* score_out) {
+    const KnnFilter f{allow, n_masks, mask_of_query};
+    return knn_entry(c, q, b, k, idx_out, score_out, nullptr, nullptr, &f);
+}
+int rdm_knn_filtered_f64(rdm_ctx* c, const float* q, int b, int k, const uint64_t* allow, int n_masks, const int32_t* mask_of_query, uint32_t* idx_out,
+                         double* score_out) {
+    const KnnFilter f{allow, n_masks, mask_of_query};
+    return knn_entry(c, q, b, k, idx_out, nullptr, score_out, nullptr, &f);
+}
+int rdm_op_knn_stages_filtered(rdm_ctx* c, const float* q, int b, int k, const uint64_t* allow, int n_masks, const int32_t* mask_of_query,
+                               uint32_t* idx_out, float* score_out, rdm_knn_stages* stages) {
+    if (c && !stages) return c->fail(-1, "rdm_op_knn_stages_filtered: null argument");
+    const KnnFilter f{allow, n_masks, mask_of_query};
+    return knn_entry(c, q, b, k, idx_out, score_out, nullptr, stages, &f);
+}
+int rdm_op_row_mask(rdm_ctx* c, const int64_t* rows, long long n_rows, long long n, int invert, uint64_t* bits_out) {
+    RDM_ENTER(c);
+    if (!bits_out || (!rows && n_rows > 0)) return c->fail(-1, "rdm_op_row_mask: null argument");
+    const char* msg = knn_row_mask(rows, n_rows, n, invert, bits_out, c->stream);
+    return msg ? c->fail(-5, "rdm_op_row_mask: %s", msg) : 0;
+}
+int rdm_op_row_mask_count(rdm_ctx* c, const uint64_t* allow, int n_masks, long long n, long long* counts_out) {
+    RDM_ENTER(c);
+    if (!allow || !counts_out) return c->fail(-1, "rdm_op_row_mask_count: null argument");
+    const char* msg = knn_row_mask_count(allow, n_masks, n, counts_out, c->stream);
+    return msg ? c->fail(-5, "rdm_op_row_mask_count: %s", msg) : 0;
 }
 int rdm_db_rows(rdm_ctx* c, long long row0, long long rows, void* out_f16) {
     RDM_ENTER(c);

@@ -36,6 +36,7 @@
 #include <string.h>
 
 #include <type_traits>
+#include <vector>
 #include "kernels.h"
 #include "knn.h"
 
@@ -120,8 +121,25 @@ struct ScanParams {
     int nlists; const void* zero_page;
 };
 
-template <int KSEL>
-__global__ __launch_bounds__(256) void knn_scan_kernel(ScanParams p) {
+// Filtered search (rdm_knn_filtered): one bitmap of `words` 64-bit words per mask, bit r % 64 of word r / 64 = row r may be returned;
+// words = n rounded up to the 256-row tile / 64, so a lane may fetch the word(s) of any row span of any tile.  mask_id[q] names the
+// mask of prepared query q (padding queries: 0).  The filtered instantiations take these after the fields the unfiltered ones take.
+struct ScanParamsF : ScanParams { const uint64_t* allow; const int* mask_id; long long words; };
+template <bool FILT> using ScanArg = std::conditional_t<FILT, ScanParamsF, ScanParams>;
+// The online scans keep LDS-DMA requests in flight across their read-outs under hand-counted vmcnt waits, and beside such a request
+// the compiler waits vmcnt(0) for any load of its own: the mask words are loaded by inline asm and waited for by the count of the
+// requests issued AFTER them.  Nothing may read the registers before that wait, not even a copy: the counted wait is a bare
+// instruction and mask_words_landed, straight after it, is the first statement that names them -- whatever move the compiler needs
+// for its tied operands lands between the two.
+__device__ __forceinline__ uint64_t mask_word_load(const uint64_t* ptr) {
+    uint64_t v;
+    asm volatile("global_load_dwordx2 %0, %1, off" : "=v"(v) : "v"(ptr) : "memory");
+    return v;
+}
+__device__ __forceinline__ void mask_words_landed(uint64_t& a, uint64_t& b) { asm volatile("" : "+v"(a), "+v"(b) :: "memory"); }
+
+template <int KSEL, bool FILT>
+__global__ __launch_bounds__(256) void knn_scan_kernel(ScanArg<FILT> p) {
     constexpr int DB_BYTES = KNN_ROWS * 128, Q_BYTES = KNN_Q * 128, STAGE = DB_BYTES + 2 * Q_BYTES;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -169,11 +187,26 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(ScanParams p) {
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[a][b][r] = 0.f;
 
+    // filtered: the words of my two queries' masks for my wave's 64-row span of the tile, requested at the tile's last K slice
+    // BEFORE the next stage's 12 LDS-DMA requests and waited for by that count at the read-out
+    const uint64_t* mrow[2] = {nullptr, nullptr}; uint64_t mw[2] = {0, 0};
+    if constexpr (FILT) {
+#pragma unroll
+        for (int qt = 0; qt < 2; qt++) mrow[qt] = p.allow + (long long)p.mask_id[qt * 32 + frow] * p.words + wave;
+    }
+    static_assert(KNN_ROWS / 32 + 2 * (KNN_Q / 32) == 12, "counted vmcnt at the filtered read-out");
+
     if (iters > 0) stage(0, 0);
     for (long long it = 0; it < iters; it++) {
         const int cur = (int)(it & 1);
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
         __syncthreads();
+        if constexpr (FILT) {
+            if ((it + 1) % nkc == 0) {
+                const long long tile = blockIdx.x + (it / nkc) * gridDim.x;
+                mw[0] = mask_word_load(mrow[0] + tile * (KNN_ROWS / 64)); mw[1] = mask_word_load(mrow[1] + tile * (KNN_ROWS / 64));
+            }
+        }
         if (it + 1 < iters) stage(it + 1, cur ^ 1);
         const char* Ds = smem + cur * STAGE; const char* Qh = Ds + DB_BYTES; const char* Ql = Qh + Q_BYTES;
 #pragma unroll
@@ -204,11 +237,23 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(ScanParams p) {
         if (kc == nkc - 1) {
             const long long tile = blockIdx.x + tl * gridDim.x;
             const long long rbase = tile * KNN_ROWS + wave * 64 + 4 * fhalf;
+            if constexpr (FILT) {
+                if (it + 1 < iters) asm volatile("s_waitcnt vmcnt(12)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                mask_words_landed(mw[0], mw[1]);
+                mw[0] >>= 4 * fhalf; mw[1] >>= 4 * fhalf;           // bit (rf * 32 + (r & 3) + 8 * (r >> 2)) = my row (rf, r)
+            }
 #pragma unroll
             for (int rf = 0; rf < 2; rf++)
 #pragma unroll
                 for (int r = 0; r < 16; r++) {
                     const long long row = rbase + rf * 32 + (r & 3) + 8 * (r >> 2);
+                    if constexpr (FILT) {               // a disallowed row is a row past the end: never inserted
+                        const int sh = rf * 32 + (r & 3) + 8 * (r >> 2);
+                        if (row < p.n) {
+                            if ((mw[0] >> sh) & 1) list_insert<KSEL>(ls[0], li[0], acc[rf][0][r], (uint32_t)row);
+                            if ((mw[1] >> sh) & 1) list_insert<KSEL>(ls[1], li[1], acc[rf][1][r], (uint32_t)row);
+                        }
+                    } else
                     if (row < p.n) {
                         list_insert<KSEL>(ls[0], li[0], acc[rf][0][r], (uint32_t)row);
                         list_insert<KSEL>(ls[1], li[1], acc[rf][1][r], (uint32_t)row);
@@ -238,8 +283,8 @@ __global__ __launch_bounds__(256) void knn_scan_kernel(ScanParams p) {
 // D layout 16x16: col (query) = lane & 15, row = (lane >> 4) * 4 + reg -> one query, one private top-k list per lane.
 // Scores with the hi fp16 word of the query only (certificate bound knn_eps(hi-word path)): half the MFMA work of a hi + lo scan,
 // and the lighter loop holds a higher clock: 4.99 -> 4.48 ms per 64 queries over 20.9 M rows (4 waves, 32x32x16, hi + lo, retired).
-template <int KSEL>
-__global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
+template <int KSEL, bool FILT>
+__global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanArg<FILT> p) {
     constexpr int DB_BYTES = KNN_ROWS * 128, NKC = 8, DIM = 512;
     extern __shared__ __attribute__((aligned(16))) char smem[];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
@@ -279,6 +324,13 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
 #pragma unroll
     for (int a = 0; a < 8; a++) acc[a] = f32x4{0.f, 0.f, 0.f, 0.f};
 
+    // filtered: the two words of my query's mask for my 128-row half of the tile.  Requested in the tile's LAST K slice, after that
+    // slice's stage wait and BEFORE the 4 requests of stage it+2, so every counted wait of the ring stays true (nothing of mine is
+    // outstanding at a stage wait: the read-out below waits for the words by the count of the requests issued after them -- 4, or
+    // none behind the block's last tile -- which retires no more than the next stage wait would).
+    const uint64_t* mrow = nullptr; uint64_t mw0 = 0, mw1 = 0;
+    if constexpr (FILT) mrow = p.allow + (long long)p.mask_id[qg * 16 + l15] * p.words + rh * 2;
+
     if (iters > 0) stage_next();
     if (iters > 1) stage_next();
     long long it = 0;
@@ -288,6 +340,12 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
             if (it + 1 < iters) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");     // stage it landed; stage it+1 (4 pieces) may fly
             else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
             __builtin_amdgcn_s_barrier();
+            if constexpr (FILT) {
+                if (kc == NKC - 1) {
+                    const uint64_t* mp = mrow + (blockIdx.x + tl * gridDim.x) * (KNN_ROWS / 64);
+                    mw0 = mask_word_load(mp); mw1 = mask_word_load(mp + 1);
+                }
+            }
             if (it + 2 < iters) stage_next();
             const char* Ds = smem + (int)(it % 3) * DB_BYTES;
 #pragma unroll
@@ -305,19 +363,30 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
         }
         const long long tile = blockIdx.x + tl * gridDim.x;
         const long long rbase = tile * KNN_ROWS + rh * 128 + kq * 4;
+        if constexpr (FILT) {
+            if (it + 1 < iters) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // it: first slice of the next tile
+            mask_words_landed(mw0, mw1);
+            mw0 >>= kq * 4; mw1 >>= kq * 4;                   // bit ((rf & 3) * 16 + r) of word rf >> 2 = my row (rf, r)
+        }
         if ((tile + 1) * KNN_ROWS <= p.n) {                   // full tile (all but the last): no per-row bound check
             const uint32_t rb = (uint32_t)rbase;
 #pragma unroll
             for (int rf = 0; rf < 8; rf++)
 #pragma unroll
-                for (int r = 0; r < 4; r++) { list_insert_ascending<KSEL>(ls, li, acc[rf][r], rb + rf * 16 + r); acc[rf][r] = 0.f; }
+                for (int r = 0; r < 4; r++) {
+                    if constexpr (FILT) { if (((rf < 4 ? mw0 : mw1) >> ((rf & 3) * 16 + r)) & 1) list_insert_ascending<KSEL>(ls, li, acc[rf][r], rb + rf * 16 + r); }
+                    else list_insert_ascending<KSEL>(ls, li, acc[rf][r], rb + rf * 16 + r);
+                    acc[rf][r] = 0.f;
+                }
         } else {
 #pragma unroll
             for (int rf = 0; rf < 8; rf++)
 #pragma unroll
                 for (int r = 0; r < 4; r++) {
                     const long long row = rbase + rf * 16 + r;
-                    if (row < p.n) list_insert_ascending<KSEL>(ls, li, acc[rf][r], (uint32_t)row);
+                    bool live = row < p.n;
+                    if constexpr (FILT) live = live && (((rf < 4 ? mw0 : mw1) >> ((rf & 3) * 16 + r)) & 1);
+                    if (live) list_insert_ascending<KSEL>(ls, li, acc[rf][r], (uint32_t)row);
                     acc[rf][r] = 0.f;
                 }
         }
@@ -351,11 +420,12 @@ __global__ __launch_bounds__(512, 2) void knn_scan512w8_kernel(ScanParams p) {
 // 8-entry lists, the ascending insertion and the 16-candidate pre-compare below); an idle sleep in place of the MFMAs hides completely
 // behind the requests (62 ms), the real MFMA + LDS-read stream does not (96 ms without insertion): what is left is contention between
 // the LDS-DMA stream (48 KB per stage and block at ~26 B/clk) and the scoring waves, not the ring depth.
-struct BulkParams { ScanParams s; int groups; };      // s.qh: [groups*128][dim]; s.cand_*: [groups*128][nlists][KSEL]
+template <bool FILT> struct BulkArg { ScanArg<FILT> s; int groups; };      // s.qh: [groups*128][dim]; s.cand_*: [groups*128][nlists][KSEL]
+using BulkParams = BulkArg<false>;
 
-template <int KSEL>
-__global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
-    const ScanParams& p = bp.s;
+template <int KSEL, bool FILT>
+__global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkArg<FILT> bp) {
+    const ScanArg<FILT>& p = bp.s;
     constexpr int QB = 128, DB_BYTES = KNN_ROWS * 128, Q_BYTES = QB * 128, STAGE = DB_BYTES + Q_BYTES, NSLOT = 3;
     constexpr int NP = KNN_ROWS / 64 + QB / 64;               // 64-row pieces per stage (4 database + 2 query)
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -432,6 +502,14 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
 #pragma unroll
             for (int r = 0; r < 16; r++) acc[a][f][r] = 0.f;
     int cslot = 0, ckc = 0; long long ctile = wk;
+    // filtered: the two words of each of my two queries' masks for my 128-row half of the tile.  The scoring waves issue no other
+    // vector-memory request and count none by hand, so these are ordinary loads, issued ahead of the tile's last K slice.
+    const GLOBAL_AS uint64_t* mrow[2] = {nullptr, nullptr}; uint64_t mw[2][2] = {{0, 0}, {0, 0}};
+    if constexpr (FILT) {
+#pragma unroll
+        for (int f = 0; f < 2; f++)
+            mrow[f] = (const GLOBAL_AS uint64_t*)(p.allow + (long long)p.mask_id[grp * QB + qh2 * 64 + f * 32 + frow] * p.words + rg * 2);
+    }
     // LDS byte addresses of my fragment rows for the four k-steps of a stage (slot base added per stage).  (row >> 1) & 7 of every
     // fragment row equals (frow >> 1) & 7: the row / query offsets are multiples of 32 rows, applied as immediates.
     const unsigned lds0 = (unsigned)(uintptr_t)(LDS_AS char*)smem;
@@ -446,6 +524,12 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
     for (long long it = 0; it < iters; it++) {
         __builtin_amdgcn_s_barrier();                     // stage `it` landed (the loader waves waited for it before arriving here)
         __builtin_amdgcn_sched_barrier(0);
+        if constexpr (FILT) {
+            if (ckc + 1 == nkc) {
+#pragma unroll
+                for (int f = 0; f < 2; f++) { mw[f][0] = mrow[f][ctile * (KNN_ROWS / 64)]; mw[f][1] = mrow[f][ctile * (KNN_ROWS / 64) + 1]; }
+            }
+        }
         const unsigned sb = (unsigned)(cslot * STAGE);
         cslot = cslot == NSLOT - 1 ? 0 : cslot + 1;
         {
@@ -488,6 +572,16 @@ __global__ __launch_bounds__(512, 1) void knn_scan_bulk_kernel(BulkParams bp) {
                         const bool dead = rbase + rf * 32 + (r & 3) + 8 * (r >> 2) >= p.n;
                         acc[rf][0][r] = dead ? -INFINITY : acc[rf][0][r];
                         acc[rf][1][r] = dead ? -INFINITY : acc[rf][1][r];
+                    }
+            }
+            if constexpr (FILT) {                          // a disallowed row loses like a row past the end, before the pre-compare
+#pragma unroll
+                for (int f = 0; f < 2; f++)
+#pragma unroll
+                    for (int rf = 0; rf < 4; rf++) {
+                        const uint32_t m = (uint32_t)(mw[f][rf >> 1] >> ((rf & 1) * 32 + 4 * fhalf));    // bit ((r & 3) + 8 * (r >> 2)) = row (rf, r)
+#pragma unroll
+                        for (int r = 0; r < 16; r++) acc[rf][f][r] = ((m >> ((r & 3) + 8 * (r >> 2))) & 1u) ? acc[rf][f][r] : -INFINITY;
                     }
             }
             const uint32_t rb = (uint32_t)rbase;
@@ -608,7 +702,10 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(MergeParams p) {
         float th = (si[R] != 0xffffffffu) ? ss[R] : -INFINITY;          // first candidate after the re-scored prefix
         for (int t = 0; t < 256; t++) th = fmaxf(th, s_theta[t]);
         const double tau = ex[p.k - 1];
-        const bool certified = (double)th + (double)p.eps < tau;
+        // Short subset (filtered search): fewer than k candidates, so tau = -inf.  If nothing was dropped anywhere (theta = -inf) every
+        // allowed row is among the re-scored ones and the answer -- those rows, then (0xffffffff, -inf) -- is complete; if a list did
+        // drop rows, the exact pass collects every allowed row.  Unfiltered, k <= n rows makes tau finite whenever theta = -inf.
+        const bool certified = (double)th + (double)p.eps < tau || (tau == -INFINITY && th == -INFINITY);
         p.cert.flag[q] = certified ? 0 : 1;
         p.cert.tau[q] = tau; p.cert.tau_idx[q] = exi[p.k - 1]; p.cert.fb_count[q] = 0; p.cert.theta[q] = th;
         if (!certified) atomicOr(p.cert.status, 1);
@@ -618,7 +715,9 @@ __global__ __launch_bounds__(256) void knn_merge_kernel(MergeParams p) {
 // ---------------------------------------------------------------- exact fallback (flagged queries only; normally none)
 // One wave per row: exact fp64 score against every flagged query; rows that beat-or-tie the query's current k-th candidate
 // under (score desc, index asc) are appended.  The true top k all do (the current k-th is the k-th best of a SUBSET).
-__global__ __launch_bounds__(256) void knn_exact_collect_kernel(Certify c, const _Float16* dbn, const float* qn, long long n, int dim, int nq) {
+// allow != nullptr (filtered search): a row the query's mask disallows is skipped BEFORE it is scored -- it must not be collected.
+__global__ __launch_bounds__(256) void knn_exact_collect_kernel(Certify c, const _Float16* dbn, const float* qn, long long n, int dim, int nq,
+                                                                const uint64_t* allow, const int* mask_id, long long words) {
     __shared__ int fq[KNN_QMAX]; __shared__ int nf;
     const int tid = threadIdx.x, lane = tid & 63;
     if (tid == 0) { int m = 0; for (int q = 0; q < nq; q++) if (c.flag[q]) fq[m++] = q; nf = m; }
@@ -628,6 +727,7 @@ __global__ __launch_bounds__(256) void knn_exact_collect_kernel(Certify c, const
     for (long long row = wave0; row < n; row += nwaves) {
         for (int f = 0; f < nf; f++) {
             const int q = fq[f];
+            if (allow && !((allow[(long long)mask_id[q] * words + (row >> 6)] >> (row & 63)) & 1)) continue;
             const double s = exact_score(qn + (long long)q * dim, dbn + row * dim, dim, lane);
             if (lane == 0) {
                 const double tau = c.tau[q]; const uint32_t ti = c.tau_idx[q];
@@ -659,11 +759,11 @@ __global__ __launch_bounds__(256) void knn_exact_finish_kernel(Certify c, int k,
             if (tid < o && (bs[tid + o] > bs[tid] || (bs[tid + o] == bs[tid] && bi[tid + o] < bi[tid]))) { bs[tid] = bs[tid + o]; bi[tid] = bi[tid + o]; bp[tid] = bp[tid + o]; }
             __syncthreads();
         }
-        if (tid == 0 && bp[0] >= 0) {
+        if (tid == 0) {                                   // nothing left (a filtered query with fewer than k allowed rows): (0xffffffff, -inf)
             idx_out[(long long)(qbase + q) * k + j] = bi[0];
             if (score_out) score_out[(long long)(qbase + q) * k + j] = (float)bs[0];
             if (score64_out) score64_out[(long long)(qbase + q) * k + j] = bs[0];
-            fi[bp[0]] = 0xffffffffu;                      // taken
+            if (bp[0] >= 0) fi[bp[0]] = 0xffffffffu;      // taken
         }
         __syncthreads();
     }
@@ -677,6 +777,41 @@ __global__ void knn_gather_kernel(const TIN* raw, const uint32_t* idx, long long
         const long long r = i / dim; const int c = (int)(i - r * dim);
         out[i] = (float)raw[(long long)idx[r] * dim + c];
     }
+}
+
+// ---------------------------------------------------------------- row masks (rdm_op_row_mask, rdm_op_row_mask_count)
+// every word of the mask: nothing allowed, or (invert) every row below n
+__global__ void knn_mask_fill_kernel(uint64_t* bits, long long words, long long n, int invert) {
+    const long long w = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (w >= words) return;
+    uint64_t v = 0;
+    if (invert) { const long long left = n - w * 64; v = left >= 64 ? ~0ull : left > 0 ? (1ull << left) - 1 : 0; }
+    bits[w] = v;
+}
+// one listed row per thread (duplicates allowed): set its bit, or (invert) clear it; a row outside [0, n) raises *bad
+__global__ void knn_mask_rows_kernel(const int64_t* rows, long long n_rows, long long n, int invert, uint64_t* bits, int* bad) {
+    const long long i = (long long)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n_rows) return;
+    const int64_t r = rows[i];
+    if (r < 0 || r >= n) { atomicOr(bad, 1); return; }
+    const unsigned long long bit = 1ull << (r & 63);
+    if (invert) atomicAnd((unsigned long long*)bits + (r >> 6), ~bit);
+    else atomicOr((unsigned long long*)bits + (r >> 6), bit);
+}
+// one block per mask: allowed rows below n
+__global__ __launch_bounds__(256) void knn_mask_count_kernel(const uint64_t* allow, long long words, long long n, unsigned long long* counts) {
+    const uint64_t* m = allow + (long long)blockIdx.x * words;
+    unsigned long long c = 0;
+    for (long long w = threadIdx.x; w * 64 < n; w += 256) {
+        const long long left = n - w * 64;
+        c += __popcll(left >= 64 ? m[w] : m[w] & ((1ull << left) - 1));
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o);
+    __shared__ unsigned long long part[4];
+    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
+    __syncthreads();
+    if (threadIdx.x == 0) counts[blockIdx.x] = part[0] + part[1] + part[2] + part[3];
 }
 
 // ---------------------------------------------------------------- host
@@ -765,7 +900,7 @@ static const char* stage_out(void* dst, const void* src, size_t bytes, hipStream
 
 template <int KSEL, int R>
 static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float* q, int b, int k, uint32_t* idx_out, float* score_out,
-                               double* score64_out, hipStream_t st, rdm_knn_stages* so) {
+                               double* score64_out, hipStream_t st, rdm_knn_stages* so, const KnnFilter* filt) {
     int dev = 0, ncu = 256;
     hipGetDevice(&dev);
     hipDeviceGetAttribute(&ncu, hipDeviceAttributeMultiprocessorCount, dev);
@@ -784,7 +919,7 @@ static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float*
     const size_t qn_b = (size_t)QS * db.dim * 4, qh_b = (size_t)QS * db.dim * 2;
     const size_t cand_b = (size_t)QS * nlists_cap * KSEL * 4;
     const size_t cert_off = (qn_b + 2 * qh_b + 2 * cand_b + 255) & ~(size_t)255;
-    const size_t cert_b = 256 /*status*/ + KNN_QMAX * (4 + 8 + 4 + 4 + 4) + 256 + (size_t)KNN_QMAX * KNN_FB_CAP * 12;
+    const size_t cert_b = 256 /*status*/ + KNN_QMAX * (4 + 8 + 4 + 4 + 4) + KNN_QMAX * 4 /*mask ids*/ + 256 + (size_t)KNN_QMAX * KNN_FB_CAP * 12;
     const size_t need = cert_off + cert_b + 1024;
     if (db.scratch_bytes < need) {
         if (db.scratch) { KNN_TRY(hipStreamSynchronize(st)); KNN_TRY(hipFree(db.scratch)); db.scratch = nullptr; db.scratch_bytes = 0; }
@@ -793,7 +928,7 @@ static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float*
     char* s = (char*)db.scratch;
     float* qn = (float*)s; _Float16* qh = (_Float16*)(s + qn_b); _Float16* ql = (_Float16*)(s + qn_b + qh_b);
     float* cs = (float*)(s + qn_b + 2 * qh_b); uint32_t* ci = (uint32_t*)(s + qn_b + 2 * qh_b + cand_b);
-    Certify cert{};
+    Certify cert{}; int* mask_id = nullptr;
     {
         char* cb = s + cert_off;
         cert.status = (int*)cb; cb += 256;
@@ -803,8 +938,20 @@ static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float*
         cert.tau_idx = (uint32_t*)cb; cb += KNN_QMAX * 4;
         cert.flag = (int*)cb; cb += KNN_QMAX * 4;
         cert.fb_count = (int*)cb; cb += KNN_QMAX * 4;
-        cert.theta = (float*)cb;
+        cert.theta = (float*)cb; cb += KNN_QMAX * 4;
+        mask_id = (int*)cb;
     }
+    // filtered: the mask of every query of every launch, padded with mask 0 to whole launches; each launch stages its QS ids to the
+    // device with its prepared queries (the host copy lives until the stream is synchronised below)
+    const long long words = knn_mask_words(db.n);
+    std::vector<int32_t> mids;
+    if (filt) {
+        mids.assign(((size_t)b + QS - 1) / QS * QS, 0);
+        if (filt->mask_of_query) for (int i = 0; i < b; i++) mids[i] = filt->mask_of_query[i];
+    }
+    auto stage_mask_ids = [&](int q0) -> const char* {
+        return filt ? hiperr(hipMemcpyAsync(mask_id, mids.data() + q0, (size_t)QS * 4, hipMemcpyHostToDevice, st)) : nullptr;
+    };
     KNN_TRY(hipMemsetAsync(cert.status, 0, 8, st));
     if (!db.zero_page) { KNN_TRY(hipMalloc(&db.zero_page, 256)); KNN_TRY(hipMemset(db.zero_page, 0, 256)); }
     void* zero_page = db.zero_page;
@@ -815,9 +962,12 @@ static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float*
     static bool attr_dev[RDM_MAX_DEVICES] = {false};
     bool& attr = attr_dev[rdm_cur_device()];
     if (!attr) {
-        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, scan_smem));
-        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
-        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_bulk_kernel<KSEL>, hipFuncAttributeMaxDynamicSharedMemorySize, bulk_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_kernel<KSEL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, scan_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<KSEL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_bulk_kernel<KSEL, false>, hipFuncAttributeMaxDynamicSharedMemorySize, bulk_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_kernel<KSEL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, scan_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan512w8_kernel<KSEL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, scan512_smem));
+        KNN_TRY(hipFuncSetAttribute((const void*)knn_scan_bulk_kernel<KSEL, true>, hipFuncAttributeMaxDynamicSharedMemorySize, bulk_smem));
         KNN_TRY(hipFuncSetAttribute((const void*)knn_merge_kernel<KSEL, R>, hipFuncAttributeMaxDynamicSharedMemorySize, merge_smem));
         attr = true;
     }
@@ -846,13 +996,15 @@ static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float*
             if (const char* m = stage_out(so->tau_idx, cert.tau_idx, (size_t)bq * 4, st)) return m;
             if (const char* m = stage_out(so->theta, cert.theta, (size_t)bq * 4, st)) return m;
         }
-        knn_exact_collect_kernel<<<ncu * 4, 256, 0, st>>>(cert, (const _Float16*)db.dbn, qn, db.n, db.dim, bq);
+        knn_exact_collect_kernel<<<ncu * 4, 256, 0, st>>>(cert, (const _Float16*)db.dbn, qn, db.n, db.dim, bq,
+                                                          filt ? filt->allow : nullptr, mask_id, words);
         KNN_TRY(hipGetLastError());
         knn_exact_finish_kernel<<<bq, 256, 0, st>>>(cert, k, idx_out, score_out, score64_out, q0);
         return hiperr(hipGetLastError());
     };
-    ScanParams sp{}; sp.dbn = (const _Float16*)db.dbn; sp.n = db.n; sp.dim = db.dim; sp.ntiles = ntiles; sp.qh = qh; sp.ql = ql;
+    ScanParamsF sp{}; sp.dbn = (const _Float16*)db.dbn; sp.n = db.n; sp.dim = db.dim; sp.ntiles = ntiles; sp.qh = qh; sp.ql = ql;
     sp.cand_s = cs; sp.cand_i = ci; sp.zero_page = zero_page;
+    sp.allow = filt ? filt->allow : nullptr; sp.mask_id = mask_id; sp.words = words;       // the unfiltered kernels take the ScanParams base
     if (bulk) {
         const int bgrid = (ncu / 32) * 32;                                  // a multiple of 8 XCDs x 4 groups
         for (int q0 = 0; q0 < b; q0 += KNN_QMAX) {
@@ -860,22 +1012,30 @@ static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float*
             const int groups = (bq + 127) / 128;                        // 1 .. 4 query groups share every database pass
             knn_prep_queries_kernel<<<groups * 128, 64, 0, st>>>(q + (size_t)q0 * db.dim, bq, db.dim, qn, qh, ql, q0, cert.status + 1);
             KNN_TRY(hipGetLastError());
-            BulkParams bp{}; bp.groups = groups; bp.s = sp;
+            if (const char* m = stage_mask_ids(q0)) return m;
             int walkers = bgrid / groups; if ((long long)walkers > ntiles) walkers = (int)ntiles;
             walkers = (walkers / 8) * 8;                                    // >= 8 (ntiles >= 16): every walker owns a tile and writes its lists
-            bp.s.nlists = walkers * form.lists_per_block;
-            knn_scan_bulk_kernel<KSEL><<<walkers * groups, 512, bulk_smem, st>>>(bp);
+            sp.nlists = walkers * form.lists_per_block;
+            if (filt) { BulkArg<true> bp{}; bp.groups = groups; bp.s = sp; knn_scan_bulk_kernel<KSEL, true><<<walkers * groups, 512, bulk_smem, st>>>(bp); }
+            else { BulkParams bp{}; bp.groups = groups; bp.s = sp; knn_scan_bulk_kernel<KSEL, false><<<walkers * groups, 512, bulk_smem, st>>>(bp); }
             KNN_TRY(hipGetLastError());
-            if (const char* m = merge_group(q0, bq, bp.s.nlists)) return m;
+            if (const char* m = merge_group(q0, bq, sp.nlists)) return m;
         }
     } else
     for (int q0 = 0; q0 < b; q0 += KNN_Q) {
         const int bq = (b - q0 < KNN_Q) ? b - q0 : KNN_Q;
         knn_prep_queries_kernel<<<KNN_Q, 64, 0, st>>>(q + (size_t)q0 * db.dim, bq, db.dim, qn, qh, ql, q0, cert.status + 1);
         KNN_TRY(hipGetLastError());
+        if (const char* m = stage_mask_ids(q0)) return m;
         sp.nlists = grid * form.lists_per_block;
-        if (form.path == RDM_KNN_SCAN_D512) knn_scan512w8_kernel<KSEL><<<grid, 512, scan512_smem, st>>>(sp);
-        else knn_scan_kernel<KSEL><<<grid, 256, scan_smem, st>>>(sp);
+        const ScanParams& su = sp;
+        if (form.path == RDM_KNN_SCAN_D512) {
+            if (filt) knn_scan512w8_kernel<KSEL, true><<<grid, 512, scan512_smem, st>>>(sp);
+            else knn_scan512w8_kernel<KSEL, false><<<grid, 512, scan512_smem, st>>>(su);
+        } else {
+            if (filt) knn_scan_kernel<KSEL, true><<<grid, 256, scan_smem, st>>>(sp);
+            else knn_scan_kernel<KSEL, false><<<grid, 256, scan_smem, st>>>(su);
+        }
         KNN_TRY(hipGetLastError());
         if (const char* m = merge_group(q0, bq, sp.nlists)) return m;
     }
@@ -892,15 +1052,57 @@ static const char* search_impl(KnnDb& db, const rdm_knn_form& form, const float*
     return nullptr;
 }
 
+long long knn_mask_words(long long n) { return n <= 0 ? 0 : (n + KNN_ROWS - 1) / KNN_ROWS * (KNN_ROWS / 64); }
+
 const char* knn_search(KnnDb& db, const float* q, int b, int k, uint32_t* idx_out, float* score_out, double* score64_out, hipStream_t st,
-                       rdm_knn_stages* stages) {
+                       rdm_knn_stages* stages, const KnnFilter* filt) {
     if (!db.dbn) return "no database loaded (rdm_db_load)";
     rdm_knn_form form{};
     if (const char* m = knn_select(db.n, db.dim, b, k, &form)) return m;
+    if (filt) {
+        if (!filt->allow) return "null mask";
+        if (filt->n_masks < 1) return "n_masks must be at least 1";
+        if (filt->mask_of_query) for (int i = 0; i < b; i++) if (filt->mask_of_query[i] < 0 || filt->mask_of_query[i] >= filt->n_masks) {
+            static thread_local char msg[128];
+            snprintf(msg, sizeof msg, "query %d names mask %d: mask_of_query must lie in [0, %d)", i, (int)filt->mask_of_query[i], filt->n_masks);
+            return msg;
+        }
+    }
     static_assert(KNN_Q == 64 && KNN_QMAX == 512, "rdm_hip.h documents these group sizes");
-    if (form.ksel == 8 && form.rescored == 16) return search_impl<8, 16>(db, form, q, b, k, idx_out, score_out, score64_out, st, stages);
-    if (form.ksel == 8 && form.rescored == 64) return search_impl<8, 64>(db, form, q, b, k, idx_out, score_out, score64_out, st, stages);
+    if (form.ksel == 8 && form.rescored == 16) return search_impl<8, 16>(db, form, q, b, k, idx_out, score_out, score64_out, st, stages, filt);
+    if (form.ksel == 8 && form.rescored == 64) return search_impl<8, 64>(db, form, q, b, k, idx_out, score_out, score64_out, st, stages, filt);
     return "no scan kernel is compiled for this list length and re-scored prefix";
+}
+
+const char* knn_row_mask(const int64_t* rows, long long n_rows, long long n, int invert, uint64_t* bits_out, hipStream_t st) {
+    if (n <= 0 || n_rows < 0) return "n must be positive and n_rows non-negative";
+    const long long words = knn_mask_words(n);
+    int* bad = nullptr;
+    KNN_TRY(hipMalloc(&bad, 4));
+    int host_bad = 0;
+    hipError_t e = hipMemsetAsync(bad, 0, 4, st);
+    if (e == hipSuccess) { knn_mask_fill_kernel<<<(int)((words + 255) / 256), 256, 0, st>>>(bits_out, words, n, invert); e = hipGetLastError(); }
+    if (e == hipSuccess && n_rows > 0) {
+        knn_mask_rows_kernel<<<(unsigned)((n_rows + 255) / 256), 256, 0, st>>>(rows, n_rows, n, invert, bits_out, bad);
+        e = hipGetLastError();
+    }
+    if (e == hipSuccess) e = hipMemcpyAsync(&host_bad, bad, 4, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(bad);
+    if (e != hipSuccess) return hipGetErrorString(e);
+    return host_bad ? "a row index lies outside [0, n)" : nullptr;
+}
+
+const char* knn_row_mask_count(const uint64_t* allow, int n_masks, long long n, long long* counts_out, hipStream_t st) {
+    if (n <= 0 || n_masks < 1) return "n and n_masks must be positive";
+    unsigned long long* dev = nullptr;
+    KNN_TRY(hipMalloc(&dev, (size_t)n_masks * 8));
+    knn_mask_count_kernel<<<n_masks, 256, 0, st>>>(allow, knn_mask_words(n), n, dev);
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(counts_out, dev, (size_t)n_masks * 8, hipMemcpyDeviceToHost, st);
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
+    (void)hipFree(dev);
+    return hiperr(e);
 }
 
 const char* knn_rows(KnnDb& db, long long row0, long long rows, void* out_f16, hipStream_t st) {

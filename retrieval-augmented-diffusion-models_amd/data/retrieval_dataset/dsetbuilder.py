@@ -26,28 +26,33 @@ class HipSearcher(object):
     def __init__(self, ctx, dim, row0=0, group=None, sharded=False, n_local=None):
         self.ctx, self.dim, self.row0, self.group, self.sharded, self.n_local = ctx, dim, int(row0), group, bool(sharded), n_local
 
-    def _search(self, q: torch.Tensor, k: int):
+    def _search(self, q: torch.Tensor, k: int, allow=None, mask_of_query=None):
+        """allow / mask_of_query: the row filter of Context.knn over THIS context's rows (sharded: every rank passes its local masks).  A
+        query whose masks allow fewer than k rows over all shards gets (NO_ROW, -inf) in the places beyond them."""
+        filt = {} if allow is None else {"allow": allow, "mask_of_query": mask_of_query}        # none given: today's call, unchanged
         if not self.sharded:
-            return self.ctx.knn(q, k)
+            return self.ctx.knn(q, k, **filt)
         from ... import parallel
         kl = min(k, self.n_local)
-        idx, sc = self.ctx.knn(q, kl, f64=True)
-        gid = (idx.to(torch.int64) & 0xffffffff) + self.row0
+        idx, sc = self.ctx.knn(q, kl, f64=True, **filt)
+        gid = idx.to(torch.int64) & 0xffffffff
+        gid = torch.where(gid == _lib.NO_ROW, torch.full_like(gid, 2 ** 62), gid + self.row0)      # the library's "no row" is the merge's
         if kl < k:                                                  # a shard shorter than k: pad with "no row"
             pad = k - kl
             gid = torch.cat([gid, torch.full((gid.shape[0], pad), 2 ** 62, dtype=torch.int64, device=gid.device)], dim=1)
             sc = torch.cat([sc, torch.full((sc.shape[0], pad), float("-inf"), dtype=torch.float64, device=sc.device)], dim=1)
         gi, gs = parallel.merge_sharded_topk(gid, sc, k, self.group)
+        gi = torch.where(gi >= 2 ** 62, torch.full_like(gi, _lib.NO_ROW), gi)
         return gi.to(torch.int32), gs.to(torch.float32)             # uint32 bits, like the unsharded call
 
-    def search_batched(self, queries, final_num_neighbors=None, **kw):
+    def search_batched(self, queries, final_num_neighbors=None, allow=None, mask_of_query=None, **kw):
         q = torch.as_tensor(np.ascontiguousarray(queries, dtype=np.float32))
-        idx, dist = self._search(q, int(final_num_neighbors))
+        idx, dist = self._search(q, int(final_num_neighbors), allow, mask_of_query)
         return idx.cpu().numpy().view(np.uint32), dist.cpu().numpy()
 
-    def search_batched_device(self, queries: torch.Tensor, k: int):
+    def search_batched_device(self, queries: torch.Tensor, k: int, allow=None, mask_of_query=None):
         """Device-resident variant (no host round trip): -> (idx int32-bits-of-uint32 [B,k], score f32 [B,k])."""
-        return self._search(queries, k)
+        return self._search(queries, k, allow, mask_of_query)
 
     def search(self, query, final_num_neighbors=None, **kw):
         i, d = self.search_batched(np.asarray(query)[None], final_num_neighbors)
@@ -66,6 +71,7 @@ class DatasetBuilder(object):
         self.visualize = False
         self.retriever = retriever
         self.searcher = None
+        self._subsets = {}                                  # name -> {"rows": sorted global row indices, "mask": device mask or None}
         self._dev_index = device if isinstance(device, int) else (torch.device(device).index or 0)
         self._ctx = ctx if ctx is not None else (retriever.model.ctx if retriever is not None else None)
         self.data_pool = {'embedding': [], 'img_id': [], 'patch_coords': []}
@@ -131,7 +137,65 @@ class DatasetBuilder(object):
             emb = emb.astype(np.float32)
         self.ctx.db_load(emb)
         self.searcher = HipSearcher(self.ctx, emb.shape[1], row0=row0, group=group, sharded=sharded, n_local=emb.shape[0])
+        for s in self._subsets.values():                    # the masks belong to the database just loaded (and to this rank's rows)
+            s["mask"] = self._build_mask(s["rows"])
         return self.searcher
+
+    # ---- [native] filtered retrieval: named row subsets of the resident database (a class, a style, a held-out split, a deny list)
+    def _build_mask(self, rows):
+        local = _lib.shard_row_mask(rows, self.searcher.row0, self.searcher.n_local) if self.searcher.sharded else rows
+        return self.ctx.row_mask(local)
+
+    def define_subset(self, name, rows_or_bool):
+        """Name a subset of the database rows: an index array (duplicates allowed) or a boolean array over all rows.  The mask is built
+        once and kept on the device (per shard when the rows are sharded) and rebuilt at train_searcher(); search_k_nearest(subset=name)
+        and the models' db_subset= then search those rows only."""
+        n = len(self.data_pool['embedding'])
+        r = np.asarray(rows_or_bool.cpu().numpy() if isinstance(rows_or_bool, torch.Tensor) else rows_or_bool)
+        if r.dtype == np.bool_:
+            if r.shape != (n,):
+                raise ValueError(f"define_subset({name!r}): a boolean subset must have one entry per database row ({n}), got {r.shape}")
+            r = np.flatnonzero(r)
+        if r.ndim != 1 or (r.size and not np.issubdtype(r.dtype, np.integer)):
+            raise ValueError(f"define_subset({name!r}): row indices must be a 1-d integer array, got {r.dtype} {r.shape}")
+        r = np.unique(r.astype(np.int64))
+        if r.size and (r[0] < 0 or r[-1] >= n):
+            raise ValueError(f"define_subset({name!r}): row indices must lie in [0, {n})")
+        self._subsets[name] = {"rows": r, "mask": self._build_mask(r) if self.searcher is not None else None}
+        return self
+
+    def subsets(self):
+        """-> {name: number of rows} of the defined subsets."""
+        return {name: int(len(s["rows"])) for name, s in self._subsets.items()}
+
+    def _subset_filter(self, subset, b):
+        """subset: a name, or a list of b names / None (None: the whole database for that query) -> (allow, mask_of_query, names)."""
+        names = [subset] * b if subset is None or isinstance(subset, str) else list(subset)
+        if len(names) != b:
+            raise ValueError(f"subset: one name per query ({b}), got {len(names)}")
+        distinct = []
+        for nm in names:
+            if nm is not None and nm not in self._subsets:
+                raise KeyError(f"subset {nm!r} is not defined (define_subset); defined: {sorted(self._subsets)}")
+            if nm not in distinct:
+                distinct.append(nm)
+        words = _lib.knn_mask_words(self.ctx.db_size())
+        masks = [torch.full((words,), -1, dtype=torch.int64, device=self.ctx.device) if nm is None else self._subsets[nm]["mask"] for nm in distinct]
+        ids = np.array([distinct.index(nm) for nm in names], dtype=np.int32)
+        return torch.stack(masks), ids, names
+
+    def search_subset(self, query_embeddings, k, subset=None):
+        """searcher.search_batched over the rows of `subset` (_subset_filter) -> (nns uint32 [b,k], distances); a ValueError where a
+        subset holds fewer than k rows -- before anything indexes the data pool with the "no row" id."""
+        if subset is None:
+            return self.searcher.search_batched(query_embeddings, final_num_neighbors=k)
+        allow, ids, names = self._subset_filter(subset, len(query_embeddings))
+        nns, distances = self.searcher.search_batched(query_embeddings, final_num_neighbors=k, allow=allow, mask_of_query=ids)
+        short = np.flatnonzero((nns == _lib.NO_ROW).any(axis=1))
+        if short.size:
+            nm = names[int(short[0])]
+            raise ValueError(f"subset {nm!r} allows {len(self._subsets[nm]['rows'])} rows, fewer than k = {k} neighbours (query {int(short[0])})")
+        return nns, distances
 
     # ---- dsetbuilder.py:461-473
     @torch.no_grad()
@@ -211,7 +275,9 @@ class DatasetBuilder(object):
         return files
 
     # ---- dsetbuilder.py:478-518
-    def search_k_nearest(self, queries, k=None, is_caption=False, visualize=None, query_embedded=False):
+    def search_k_nearest(self, queries, k=None, is_caption=False, visualize=None, query_embedded=False, subset=None):
+        """subset [native]: a name given to define_subset, or a list of one name (or None = the whole database) per query: the exact
+        k nearest among that subset's rows.  A subset of fewer than k rows is a ValueError."""
         assert self.searcher is not None, 'Cannot search with uninitialized searcher'
         if k is None:
             k = self.k
@@ -220,7 +286,7 @@ class DatasetBuilder(object):
         else:
             query_embeddings_ = queries.cpu().numpy() if isinstance(queries, torch.Tensor) else np.asarray(queries)
         start = time.time()
-        nns, distances = self.searcher.search_batched(query_embeddings_, final_num_neighbors=k)   # normalises on device (:487)
+        nns, distances = self.search_subset(query_embeddings_, k, subset)                          # normalises on device (:487)
         end = time.time()
         out = {'embeddings': self.data_pool['embedding'][nns],
                'img_ids': self.data_pool['img_id'][nns] if len(self.data_pool.get('img_id', [])) else None,

@@ -258,7 +258,9 @@ class LatentImageRETRO(object):
     @torch.no_grad()
     def sample_from_rdata(self, N, cond=None, return_nns=False, use_weights=False, qids=None, k_nn=None, memsize=100, verbose=False,
                           top_k=256, temperature=1.0, code_side_len=16, z_dimensionality=256, pre_loaded_patches=None,
-                          nn_embeddings=None, query_embeddings=None, top_p=None, **kwargs):
+                          nn_embeddings=None, query_embeddings=None, top_p=None, db_subset=None, **kwargs):
+        """db_subset [native]: the neighbours come from a named subset of the database (retriever.define_subset), a name or one name (or
+        None) per sample; the pseudo-queries are drawn as before."""
         if return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("return_nns / pre_loaded_patches need the raw OpenImages patches (out of scope, SURVEY.md §2 #8)")
         if cond is not None:
@@ -275,7 +277,7 @@ class LatentImageRETRO(object):
                 query_embeddings = self.retriever.data_pool['embedding'][qids]
             qe = query_embeddings.cpu().numpy() if isinstance(query_embeddings, torch.Tensor) else np.asarray(query_embeddings)
             qe = qe.astype(np.float32)
-            nns, _ = self.retriever.searcher.search_batched(qe / np.linalg.norm(qe, axis=1)[:, np.newaxis], final_num_neighbors=k_nn)
+            nns, _ = self.retriever.search_subset(qe / np.linalg.norm(qe, axis=1)[:, np.newaxis], k_nn, db_subset)
             retro_cond = torch.from_numpy(np.asarray(self.retriever.data_pool['embedding'][nns])).to(self.device).to(torch.float)
         else:
             retro_cond = nn_embeddings

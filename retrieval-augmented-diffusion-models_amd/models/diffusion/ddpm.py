@@ -650,7 +650,7 @@ class MinimalRETRODiffusion(object):
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, return_nns=False,
                           n_reps=None, query_embedded=False, example_maps=None, visualize_nns=True, omit_query=False,
                           normalize=False, device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False,
-                          inpaint_mask=None, keep_known=True, **kwargs):
+                          inpaint_mask=None, keep_known=True, db_subset=None, **kwargs):
         """ddpm.py:689-844 (nn_encoder is None, retrieval_encoder = Identity — every shipped config).  device_noise [native]: the
         starting latents and the per-step noise (DDIM eta > 0, DDPM) are the library's counter-based generator's, a function of (the
         call's shared seed, GLOBAL row) generated inside the step kernels (_sample_shard) -- no noise tensor is drawn in Python.
@@ -661,7 +661,9 @@ class MinimalRETRODiffusion(object):
         inpaint_mask / keep_known [native]: repaint a region of the init image under the retrieved neighbours and keep the rest --
         inpaint_mask at latent resolution ([B | 1, 1, h, w] or [h, w]) or at image resolution ([B | 1, H, W], area-averaged down by the
         first stage's factor on the host), float in [0, 1], 1 = KEEP the init image (ldm's convention), 0 = repaint; it is cut to a
-        rank's rows like the init image.  keep_known: the known region of the result is the encoded init image exactly."""
+        rank's rows like the init image.  keep_known: the known region of the result is the encoded init image exactly.
+        db_subset [native]: retrieve from a named subset of the database (retriever.define_subset) -- a name, or one name (or None = the
+        whole database) per sample; the search is the exact top-k of the subset's rows, in the same single pass over the database."""
         if cond is not None or return_nns:
             raise NotImplementedError("cond (a second conditioning) / return_nns (neighbour image grids) are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))      # a bad custom_shape fails here, not after the retrieval
@@ -696,8 +698,10 @@ class MinimalRETRODiffusion(object):
         shard_db = self.distributed and getattr(self, "shard_db", False)
         if self.distributed and not shard_db:
             query = query[lo:hi]            # every rank retrieves for its own rows only (the database is replicated)
+            if db_subset is not None and not isinstance(db_subset, str):
+                db_subset = list(db_subset)[lo:hi]
         nn_dict = self.retriever.search_k_nearest(query, visualize=False, k=k_nn, is_caption=is_caption,
-                                                  query_embedded=query_embedded)
+                                                  query_embedded=query_embedded, subset=db_subset)
         q_emb = torch.as_tensor(nn_dict['q_embeddings']).float()
         r_emb = torch.as_tensor(nn_dict['embeddings']).float()
         if shard_db:                        # row-sharded database: every rank searched ALL queries on its rows; keep this rank's samples
@@ -762,9 +766,10 @@ class MinimalRETRODiffusion(object):
                           verbose=False, pre_loaded_patches=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, nn_embeddings=None,
                           device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False, inpaint_mask=None,
-                          keep_known=True, **kwargs):
+                          keep_known=True, db_subset=None, **kwargs):
         """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921).  device_noise, init_image /
-        init_latent / strength / invert, inpaint_mask / keep_known [native]: as in sample_with_query."""
+        init_latent / strength / invert, inpaint_mask / keep_known [native]: as in sample_with_query.  db_subset [native]: the
+        pseudo-queries are drawn as before, from the whole database; only their neighbours come from the subset."""
         if cond is not None or return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("cond / return_nns / pre_loaded_patches are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))
@@ -782,11 +787,13 @@ class MinimalRETRODiffusion(object):
         if self.distributed:
             if not shard_db:
                 qids = np.asarray(qids)[lo:hi]
+                if db_subset is not None and not isinstance(db_subset, str):
+                    db_subset = list(db_subset)[lo:hi]
             if nn_embeddings is not None:
                 nn_embeddings = nn_embeddings[lo:hi]
         query_embeddings = self.retriever.data_pool['embedding'][qids]
         if nn_embeddings is None:
-            nns, _ = self.retriever.searcher.search_batched(query_embeddings, final_num_neighbors=k_nn)   # normalises internally
+            nns, _ = self.retriever.search_subset(query_embeddings, k_nn, db_subset)                      # normalises internally
             if shard_db:                    # row-sharded database: all pseudo-queries were searched on this rank's rows and merged
                 nns = nns[lo:hi]
             retro_cond = torch.from_numpy(np.asarray(self.retriever.data_pool['embedding'][nns])).to(self.device).to(torch.float)

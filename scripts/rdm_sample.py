@@ -105,6 +105,12 @@ def build_parser() -> argparse.ArgumentParser:
     parser.add_argument("--mask", type=Path, default=None,
                         help="[native] with --init_img: inpainting -- a grey PNG, white = repaint, black = keep the init image; DDIM only, "
                         "not with --invert")
+    parser.add_argument("--db_subset", type=Path, default=None,
+                        help="[native] retrieve neighbours from a subset of the database only: a .npy file holding an integer array of row "
+                        "indices or a boolean array over all rows (a class, a style, a held-out split, a deny list); works with --gpus N "
+                        "and --shard_db")
+    parser.add_argument("--db_subset_invert", default=False, action="store_true",
+                        help="[native] with --db_subset: retrieve from every row NOT in the file")
     return parser
 
 
@@ -131,6 +137,8 @@ def parse_args(argv=None) -> argparse.Namespace:
             parser.error("--mask needs --init_img (the image whose black-masked region is kept)")
         if opt.invert:
             parser.error("--mask starts from the noised image: drop --invert")
+    if opt.db_subset_invert and opt.db_subset is None:
+        parser.error("--db_subset_invert needs --db_subset")
     if opt.top_m > 1.0:
         opt.top_m = int(opt.top_m)          # top_m should be int if a fixed number of images is given (:138-140)
     if opt.seed is not None and (not opt.increase_guidance) and opt.n_runs > 1:
@@ -260,7 +268,32 @@ def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
             kw["invert"] = True
     if getattr(opt, "mask", None) is not None:
         kw["inpaint_mask"] = load_inpaint_mask(opt, model, kw.get("custom_shape"))
+    if getattr(opt, "db_subset", None) is not None:
+        kw["db_subset"] = define_db_subset(opt, model)
     return kw
+
+
+DB_SUBSET_NAME = "--db_subset"
+
+
+def define_db_subset(opt: argparse.Namespace, model) -> str:
+    """--db_subset / --db_subset_invert: the .npy index or boolean array becomes a named subset of the model's retriever (built once,
+    per shard under --shard_db) -> the name sample_with_query / sample_from_rdata take as db_subset."""
+    if DB_SUBSET_NAME not in model.retriever.subsets():
+        n = len(model.retriever.data_pool["embedding"])
+        rows = np.load(opt.db_subset, allow_pickle=False)
+        if rows.dtype != np.bool_ and not np.issubdtype(rows.dtype, np.integer):
+            raise SystemExit(f"rdm_sample.py (native): --db_subset must hold an integer index array or a boolean array, got {rows.dtype}")
+        if rows.dtype != np.bool_:
+            if rows.size and (rows.min() < 0 or rows.max() >= n):
+                raise SystemExit(f"rdm_sample.py (native): --db_subset holds row indices outside the database's [0, {n})")
+            member = np.zeros(n, dtype=np.bool_)
+            member[rows.reshape(-1)] = True
+            rows = member
+        elif rows.shape != (n,):
+            raise SystemExit(f"rdm_sample.py (native): a boolean --db_subset must have one entry per database row ({n}), got {rows.shape}")
+        model.retriever.define_subset(DB_SUBSET_NAME, ~rows if opt.db_subset_invert else rows)
+    return DB_SUBSET_NAME
 
 
 def load_inpaint_mask(opt: argparse.Namespace, model, custom_shape=None):
