@@ -165,6 +165,24 @@ int rdm_load_rarm(rdm_ctx* ctx, const rdm_rarm_cfg* cfg, const void* packed, siz
 int rdm_unet_forward(rdm_ctx* ctx, const float* x, const int64_t* t, const float* context, int b, int k, int H, int W,
                      float* eps_out);
 
+/* ---- neighbour bias: one additive term per (sample, neighbour) on the UNet's cross-attention scores (the `mask` argument of ldm's
+ * CrossAttention.forward, rdm/modules/attention.py:42-58, as an additive term).
+ *   bias[b][j], fp32, is added to EVERY head's score of neighbour j of sample b, after the 1/sqrt(d) scale and before the softmax over the
+ *   k neighbours.  0 is the unbiased model; log w makes the neighbour count w times; -inf removes it: its probability is exactly 0 and
+ *   its (finite) embedding has no influence on the result at all.  Refused with -1 and a message (the context stays usable, the bias
+ *   that was in force stays in force): +inf, NaN, and a row without a finite entry.  The neighbour embeddings themselves must be
+ *   finite; masked places conventionally hold zeros.
+ *   The bias belongs to the conditional rows: the unconditional half of a guided batch is never biased (it is skipped through the
+ *   to_out.bias shortcut when its neighbours are all zero, and attends its caller-given neighbours unbiased otherwise).
+ * bias_host: HOST fp32 [rows][k]; the library validates it and keeps a device copy, in force until cleared (bias_host NULL; rows and k are
+ * then ignored) or replaced.  Honoured by rdm_unet_forward (rows == b) and by rdm_unet_forward_guided and every sampler entry (DDIM, PLMS,
+ * DPM-Solver++, UniPC, DDPM, their seeded forms, the SDE solver, rdm_ddim_decode / _encode / _inpaint; rows == batch), in deterministic
+ * mode too.  A bias whose (rows, k) does not match such a call makes the call fail with -1 and a message: it is never silently
+ * ignored.  The RARM, CLIP, first-stage and training entries do not read it.
+ * rdm_get_neighbour_bias: 1 = a bias is set (*rows, *k filled), 0 = none (*rows = *k = 0); either pointer may be NULL. */
+int rdm_set_neighbour_bias(rdm_ctx* ctx, const float* bias_host, int rows, int k);
+int rdm_get_neighbour_bias(rdm_ctx* ctx, int* rows, int* k);
+
 /* ---- samplers -------------------------------------------------------------------------------
  * DDIMSampler.sample / ddim_sampling / p_sample_ddim (rdm/models/diffusion/ddim.py:58-268).
  * x_T [dev] f32 [B,C,H,W]; cond, uncond [dev] f32 [B,k,ctx_dim] (uncond may be NULL when scale == 1);
@@ -850,6 +868,14 @@ int rdm_op_xattn_fused(rdm_ctx* ctx, const void* x_bf16, const float* ln_gamma, 
 int rdm_op_xattn_fused_ln3(rdm_ctx* ctx, void* x_bf16_inout, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G_bf16,
                            const void* U_bf16, const float* bias, int B, int n, int C, int NP, int ncols, int group,
                            const float* ln3_gamma, const float* ln3_beta, void* ln3_out_bf16);
+/* Both of the above under a neighbour bias (see rdm_set_neighbour_bias for the semantics): key_bias [dev] fp32 [B, group], entry
+ * [b][j] added to the score columns h * group + j of sample b before the group softmax; -inf entries allowed, every row needs one finite
+ * entry (the caller's duty here: the device values are not read back).  ln3_out given: the in-place LN + norm3 form (x is written,
+ * out must be x or null, res null, ln_gamma / ln_beta / ln3_gamma / ln3_beta required); else rdm_op_xattn_fused's plain or LN form.
+ * With group 1 a finite bias cannot change the result: it is bitwise the unbiased one. */
+int rdm_op_xattn_fused_biased(rdm_ctx* ctx, void* x_bf16, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G_bf16,
+                              const void* U_bf16, const float* bias, const void* res_bf16, int B, int n, int C, int NP, int ncols, int group,
+                              void* out_bf16, const float* ln3_gamma, const float* ln3_beta, void* ln3_out_bf16, const float* key_bias);
 /* Causal self-attention at d_head 64 over all n positions (CrossAttention.forward with RetrievalPatchTransformer's causal mask,
  * rdm/modules/attention.py:42-74, 199-272): qkv bf16 [B*n rows at stride ldq] = q | k | v thirds of heads*64 columns each, head h in columns
  * h*64..h*64+63 of its third; out bf16 [B*n, heads*64] at stride ldo; 1 <= n <= 1024.  kcache / vcache (both or neither) [B][heads][L][64]
@@ -932,6 +958,12 @@ int rdm_op_head_conv(rdm_ctx* ctx, const void* x_bf16, const float* gn_gamma, co
                      const float* bias, int B, int H, int W, int C, int Cout, float* out_f32);
 int rdm_op_small_attention(rdm_ctx* ctx, const void* q_bf16, int ldq, const void* k_bf16, const void* v_bf16, int ldkv,
                            int B, int nq, int nkv, int heads, int D, int causal, float scale, void* out_bf16, int ldo);
+/* The same with key_bias [dev] fp32 [B, nkv] added to every head's scaled score of key j of sample b (the UNet's cross-attention at
+ * k = 3, 8, 16 and at odd token counts under a neighbour bias).  -inf keys are skipped: they contribute exactly nothing, whatever their
+ * k / v rows hold; every row needs one finite entry.  Not with causal (-1). */
+int rdm_op_small_attention_biased(rdm_ctx* ctx, const void* q_bf16, int ldq, const void* k_bf16, const void* v_bf16, int ldkv,
+                                  int B, int nq, int nkv, int heads, int D, int causal, float scale, void* out_bf16, int ldo,
+                                  const float* key_bias);
 /* Gradient of rdm_op_small_attention for the UNet's cross-attention (ldm CrossAttention, rdm/modules/attention.py:52-72, with the few
  * retrieved-neighbour embeddings as keys): d_head = 32, 1..32 keys, not causal.  q [B, nq, ldq], k / v [B, nkv, ldkv], dout [B, nq, ldo]
  * (head h = columns [32 h, 32 h + 32)) -> dq [B, nq, 32 heads], dk / dv [B, nkv, 32 heads], all bf16; sums in a fixed order. */

@@ -3,6 +3,7 @@
 There is deliberately NO fallback: if the shared library is missing this module raises at import,
 and `Context()` raises when no HIP device is present.
 """
+import contextlib
 import ctypes as C
 import os
 
@@ -191,6 +192,12 @@ SIGNATURES = {
     "rdm_op_row_mask_count": (C.c_int, [_P, _P, C.c_int, C.c_longlong, _P]),
     "rdm_set_deterministic": (C.c_int, [_P, C.c_int]),
     "rdm_get_deterministic": (C.c_int, [_P]),
+    "rdm_set_neighbour_bias": (C.c_int, [_P, _P, C.c_int, C.c_int]),
+    "rdm_get_neighbour_bias": (C.c_int, [_P, C.POINTER(C.c_int), C.POINTER(C.c_int)]),
+    "rdm_op_xattn_fused_biased": (C.c_int, [_P, _P, _P, _P, C.c_float, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, _P,
+                                            _P, _P, _P, _P]),
+    "rdm_op_small_attention_biased": (C.c_int, [_P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
+                                                C.c_int, C.c_float, _P, C.c_int, _P]),
     "rdm_prof_enable": (C.c_int, [_P, C.c_int]),
     "rdm_prof_collect": (C.c_int, [_P, C.c_int, C.POINTER(C.c_longlong), C.POINTER(C.c_double), C.POINTER(C.c_double)]),
     "rdm_prof_reset": (C.c_int, [_P]),
@@ -1572,6 +1579,53 @@ class Context:
     def deterministic(self) -> bool:
         return lib.rdm_get_deterministic(self._h) == 1
 
+    def set_neighbour_bias(self, bias):
+        """The additive per-(sample, neighbour) term on the UNet's cross-attention scores (include/rdm_hip.h rdm_set_neighbour_bias):
+        bias [B, k] (0 = unbiased, log w = counts w times, -inf = absent), in force for every UNet forward and sampler call of B
+        conditional samples x k neighbours until replaced or cleared (None).  Refused: NaN, +inf, a row without a finite entry."""
+        if bias is None:
+            self._check(lib.rdm_set_neighbour_bias(self._h, None, 0, 0))
+            self._nn_bias = None
+            return
+        b = torch.as_tensor(bias).detach().to("cpu", torch.float32).contiguous()
+        if b.ndim != 2 or b.shape[0] < 1 or b.shape[1] < 1:
+            raise RdmError(f"set_neighbour_bias: the bias must be [B, k], got {tuple(b.shape)}")
+        self._check(lib.rdm_set_neighbour_bias(self._h, C.c_void_p(b.data_ptr()), b.shape[0], b.shape[1]))
+        self._nn_bias = b.clone()            # (the host copy: what neighbour_bias_doubled restores)
+
+    def get_neighbour_bias(self):
+        """(rows, k) of the bias in force, or None."""
+        r, k = C.c_int(0), C.c_int(0)
+        return (r.value, k.value) if lib.rdm_get_neighbour_bias(self._h, C.byref(r), C.byref(k)) == 1 else None
+
+    @contextlib.contextmanager
+    def neighbour_bias_doubled(self, uncond_first=False):
+        """For a per-step path's guided forward, which runs unet_forward on the doubled batch [c | uc] ([uc | c] with uncond_first): the
+        bias in force, [B, k], becomes [bias | zeros] ([zeros | bias]) for the block -- the unconditional half is never biased -- and is put
+        back afterwards.  Without a bias in force nothing happens."""
+        b = getattr(self, "_nn_bias", None)
+        if b is None:
+            yield
+            return
+        z = torch.zeros_like(b)
+        self.set_neighbour_bias(torch.cat([z, b] if uncond_first else [b, z]))
+        try:
+            yield
+        finally:
+            self.set_neighbour_bias(b)
+
+    @contextlib.contextmanager
+    def neighbour_bias(self, bias):
+        """`with ctx.neighbour_bias(bias): ...`: set for the block (None: nothing is set), cleared on the way out whatever happens."""
+        if bias is None:
+            yield
+            return
+        self.set_neighbour_bias(bias)
+        try:
+            yield
+        finally:
+            self.set_neighbour_bias(None)
+
     # ---- RCCL through the C ABI (include/rdm_hip.h "multi-GPU"); the package's own multi-GPU path uses torch.distributed
     def comm_unique_id(self) -> bytes:
         buf = C.create_string_buffer(128)
@@ -1970,24 +2024,42 @@ class Context:
         self._check(lib.rdm_op_conv_out(self._h, _ptr(x), _ptr(w), _ptr(bias), B, H, W, Cin, Cout, _ptr(out)))
         return out
 
-    def op_xattn_fused(self, x, G, U, bias, res, ncols, group, ln=None):
+    def _key_bias(self, what, key_bias, B, m):
+        kb = self._dev(key_bias, torch.float32).contiguous()
+        if tuple(kb.shape) != (B, m):
+            raise RdmError(f"{what}: key_bias must be [{B}, {m}], got {tuple(kb.shape)}")
+        return kb
+
+    def op_xattn_fused(self, x, G, U, bias, res, ncols, group, ln=None, key_bias=None):
         """out = softmax_groups(x G^T) U^T + bias + res per sample: x / res bf16 [B, n, C], G bf16 [B, NP, C], U bf16 [B, C, NP].
-        ln = (gamma, beta, eps): scores on LayerNorm(x), residual = x (res must be None)."""
+        ln = (gamma, beta, eps): scores on LayerNorm(x), residual = x (res must be None).  key_bias fp32 [B, group]: the neighbour
+        bias, added to the score columns h * group + j before the softmax (-inf: neighbour j is absent)."""
         B, n, Cc = x.shape
         NP = G.shape[1]
         out = torch.empty((B, n, Cc), device=self.device, dtype=torch.bfloat16)
         g, b_, eps = ln if ln is not None else (None, None, 0.0)
         opt = lambda t: _ptr(t) if t is not None else None
+        if key_bias is not None:
+            kb = self._key_bias("op_xattn_fused", key_bias, B, group)
+            self._check(lib.rdm_op_xattn_fused_biased(self._h, _ptr(x), opt(g), opt(b_), float(eps), _ptr(G), _ptr(U), opt(bias), opt(res),
+                                                      B, n, Cc, NP, ncols, group, _ptr(out), None, None, None, _ptr(kb)))
+            return out
         self._check(lib.rdm_op_xattn_fused(self._h, _ptr(x), opt(g), opt(b_), float(eps), _ptr(G), _ptr(U), opt(bias), opt(res),
                                            B, n, Cc, NP, ncols, group, _ptr(out)))
         return out
 
-    def op_xattn_fused_ln3(self, x, G, U, bias, ncols, group, ln, ln3):
-        """IN PLACE x <- softmax_groups(LayerNorm(x; ln) G^T) U^T + bias + x, and -> LayerNorm(new x; ln3) (bf16).  ln / ln3 = (gamma, beta[, eps])."""
+    def op_xattn_fused_ln3(self, x, G, U, bias, ncols, group, ln, ln3, key_bias=None):
+        """IN PLACE x <- softmax_groups(LayerNorm(x; ln) G^T) U^T + bias + x, and -> LayerNorm(new x; ln3) (bf16).  ln / ln3 = (gamma, beta[, eps]).
+        key_bias: as in op_xattn_fused."""
         B, n, Cc = x.shape
         assert x.is_contiguous() and x.dtype == torch.bfloat16
         out3 = torch.empty_like(x)
         opt = lambda t: _ptr(t) if t is not None else None
+        if key_bias is not None:
+            kb = self._key_bias("op_xattn_fused_ln3", key_bias, B, group)
+            self._check(lib.rdm_op_xattn_fused_biased(self._h, _ptr(x), _ptr(ln[0]), _ptr(ln[1]), float(ln[2] if len(ln) > 2 else 1e-5), _ptr(G), _ptr(U),
+                                                      opt(bias), None, B, n, Cc, G.shape[1], ncols, group, None, _ptr(ln3[0]), _ptr(ln3[1]), _ptr(out3), _ptr(kb)))
+            return out3
         self._check(lib.rdm_op_xattn_fused_ln3(self._h, _ptr(x), _ptr(ln[0]), _ptr(ln[1]), float(ln[2] if len(ln) > 2 else 1e-5), _ptr(G), _ptr(U), opt(bias),
                                                B, n, Cc, G.shape[1], ncols, group, _ptr(ln3[0]), _ptr(ln3[1]), _ptr(out3)))
         return out3
@@ -2213,7 +2285,7 @@ class Context:
         self._check(lib.rdm_op_embedding_grad(self._h, _ptr(tokens), _ptr(dy), M, Cc, V, _ptr(out)))
         return out
 
-    def op_small_attention(self, q, k, v, heads, D, causal, scale):
+    def op_small_attention(self, q, k, v, heads, D, causal, scale, key_bias=None):
         """q [B, nq, >= heads D], k / v [B, nkv, >= heads D] bf16 at their real row strides: each may be a column slice of one fused
         [B, n, 3 heads D] projection (the CLIP towers' form), as long as a sample's rows follow the previous sample's at the same pitch."""
         B, nq, _ = q.shape
@@ -2226,6 +2298,11 @@ class Context:
         assert ldk == ldv, "k and v share one row pitch"
         out = torch.empty((B, nq, heads * D), device=self.device, dtype=torch.bfloat16)
         p = lambda t: C.c_void_p(t.data_ptr())
+        if key_bias is not None:      # fp32 [B, nkv], added to every head's scaled score of key j; -inf keys are skipped
+            kb = self._key_bias("op_small_attention", key_bias, B, k.shape[1])
+            self._check(lib.rdm_op_small_attention_biased(self._h, p(q), ldq, p(k), p(v), ldk, B, nq, k.shape[1], heads,
+                                                          D, int(causal), float(scale), _ptr(out), heads * D, _ptr(kb)))
+            return out
         self._check(lib.rdm_op_small_attention(self._h, p(q), ldq, p(k), p(v), ldk, B, nq, k.shape[1], heads,
                                                D, int(causal), float(scale), _ptr(out), heads * D))
         return out

@@ -338,7 +338,16 @@ __device__ __forceinline__ void xattn_group_softmax(float* s, int group) {
     }
 }
 
-template <int NB>        // 32-column score blocks in use: ceil(ncols / 32)
+// BIAS (both kernels): the neighbour bias p.key_bias[b][j] joins the score of column h * group + j, i.e. register r of a lane's 16 takes
+// entry r & (group - 1): `group` wave-uniform floats per block, added to the summed fp32 score in front of the softmax.  A -inf entry makes
+// the score -inf whatever the (finite) G rows hold, its probability exp(-inf - m) = 0 exactly, and the U columns meet a zero operand.
+// Validation (rdm_set_neighbour_bias) leaves every row one finite entry, so the group maximum is finite.
+__device__ __forceinline__ void xattn_load_bias(const XattnParams& p, int b, float* kb) {
+#pragma unroll
+    for (int j = 0; j < 4; j++) kb[j] = p.key_bias[(long long)b * p.group + (j & (p.group - 1))];
+}
+
+template <int NB, bool BIAS>        // NB: 32-column score blocks in use: ceil(ncols / 32)
 __global__ __launch_bounds__(256) void xattn_fused_kernel(XattnParams p) {
     __shared__ __attribute__((aligned(16))) float part[4 * NB * 4 * 64 * 4];       // [wave][jb*4 + q][lane][4]
     constexpr int SB = NB == 4 ? 5 : 3;                                             // k-steps requested together
@@ -402,6 +411,8 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(XattnParams p) {
         }
     __syncthreads();
     // ---- sum of the four partials, group softmax, probabilities as the B operand of phase 2
+    float kb[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BIAS) xattn_load_bias(p, b, kb);
     bf16x8 pf[2 * NB];
 #pragma unroll
     for (int jb = 0; jb < NB; jb++) {
@@ -412,6 +423,10 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(XattnParams p) {
 #pragma unroll
             for (int ww = 1; ww < 4; ww++) t += *(const f32x4*)(part + (((ww * NB + jb) * 4 + q) * 64 + lane) * 4);
             s[4 * q] = t[0]; s[4 * q + 1] = t[1]; s[4 * q + 2] = t[2]; s[4 * q + 3] = t[3];
+        }
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) s[r] += kb[r & 3];
         }
         xattn_group_softmax(s, p.group);
 #pragma unroll
@@ -461,7 +476,7 @@ __global__ __launch_bounds__(256) void xattn_fused_kernel(XattnParams p) {
 // residual is read from the tile, the result written back into it, and the tile leaves coalesced.  Every global access of the
 // activations is now whole rows (the MFMA-layout accesses above touch 32 - 64 cache lines per instruction).  The score exchange goes
 // block by block through one 16 KiB buffer.
-template <int NB>
+template <int NB, bool BIAS>
 __global__ __launch_bounds__(256) void xattn_ln_fused_kernel(XattnParams p) {
     extern __shared__ __attribute__((aligned(16))) char xsm[];
     constexpr int SB = 3;
@@ -586,6 +601,8 @@ __global__ __launch_bounds__(256) void xattn_ln_fused_kernel(XattnParams p) {
     Blk k0, k1;
     if (w < ncb) request(k0, w);
     // ---- exchange + softmax, one 32-column block at a time
+    float kb[4] = {0.f, 0.f, 0.f, 0.f};
+    if constexpr (BIAS) xattn_load_bias(p, b, kb);
     bf16x8 pf[2 * NB];
 #pragma unroll
     for (int jb = 0; jb < NB; jb++) {
@@ -604,6 +621,10 @@ __global__ __launch_bounds__(256) void xattn_ln_fused_kernel(XattnParams p) {
             s[4 * q] = t[0]; s[4 * q + 1] = t[1]; s[4 * q + 2] = t[2]; s[4 * q + 3] = t[3];
         }
         __syncthreads();
+        if constexpr (BIAS) {
+#pragma unroll
+            for (int r = 0; r < 16; r++) s[r] += kb[r & 3];
+        }
         xattn_group_softmax(s, p.group);
 #pragma unroll
         for (int half = 0; half < 2; half++) {
@@ -705,44 +726,51 @@ bool xattn_fused_supported(const XattnParams& p) {
 }
 // p.G / p.U: the fragment-ordered images written by launch_xattn_pack
 static size_t xattn_ln_smem(int C) { return (size_t)32 * (2 * C + 16) + 4 * 4 * 64 * 4 * 4 + 4 * 32 * 4; }
-hipError_t launch_xattn_fused(const XattnParams& p, hipStream_t st) {
-    if (!xattn_fused_supported(p) || !p.x || !p.G || !p.U || !p.out) return hipErrorInvalidValue;
-    const int nb = (p.ncols + 31) / 32;
-    dim3 grid((unsigned)(p.rows / 32));
+template <bool BIAS>
+static hipError_t xattn_fused_launch(const XattnParams& p, int nb, dim3 grid, hipStream_t st) {
     if (p.ln_g) {
-        if (!p.ln_b || xattn_ln_smem(p.C) > 160 * 1024) return hipErrorInvalidValue;
         static bool attr[RDM_MAX_DEVICES] = {};
         const int dev = rdm_cur_device();
         if (!attr[dev]) {
             hipError_t e = hipSuccess;
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<1>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<2>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<3>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
-            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<4>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<1, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<2, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<3, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
+            if (e == hipSuccess) e = hipFuncSetAttribute((const void*)xattn_ln_fused_kernel<4, BIAS>, hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024);
             if (e != hipSuccess) return e;
             attr[dev] = true;
         }
         const size_t smem = xattn_ln_smem(p.C);
         switch (nb) {
-            case 1: xattn_ln_fused_kernel<1><<<grid, 256, smem, st>>>(p); break;
-            case 2: xattn_ln_fused_kernel<2><<<grid, 256, smem, st>>>(p); break;
-            case 3: xattn_ln_fused_kernel<3><<<grid, 256, smem, st>>>(p); break;
-            default: xattn_ln_fused_kernel<4><<<grid, 256, smem, st>>>(p); break;
+            case 1: xattn_ln_fused_kernel<1, BIAS><<<grid, 256, smem, st>>>(p); break;
+            case 2: xattn_ln_fused_kernel<2, BIAS><<<grid, 256, smem, st>>>(p); break;
+            case 3: xattn_ln_fused_kernel<3, BIAS><<<grid, 256, smem, st>>>(p); break;
+            default: xattn_ln_fused_kernel<4, BIAS><<<grid, 256, smem, st>>>(p); break;
         }
         return hipGetLastError();
     }
     switch (nb) {
-        case 1: xattn_fused_kernel<1><<<grid, 256, 0, st>>>(p); break;
-        case 2: xattn_fused_kernel<2><<<grid, 256, 0, st>>>(p); break;
-        case 3: xattn_fused_kernel<3><<<grid, 256, 0, st>>>(p); break;
-        default: xattn_fused_kernel<4><<<grid, 256, 0, st>>>(p); break;
+        case 1: xattn_fused_kernel<1, BIAS><<<grid, 256, 0, st>>>(p); break;
+        case 2: xattn_fused_kernel<2, BIAS><<<grid, 256, 0, st>>>(p); break;
+        case 3: xattn_fused_kernel<3, BIAS><<<grid, 256, 0, st>>>(p); break;
+        default: xattn_fused_kernel<4, BIAS><<<grid, 256, 0, st>>>(p); break;
     }
     return hipGetLastError();
+}
+hipError_t launch_xattn_fused(const XattnParams& p, hipStream_t st) {
+    if (!xattn_fused_supported(p) || !p.x || !p.G || !p.U || !p.out) return hipErrorInvalidValue;
+    if (p.ln_g && (!p.ln_b || xattn_ln_smem(p.C) > 160 * 1024)) return hipErrorInvalidValue;
+    const int nb = (p.ncols + 31) / 32;
+    dim3 grid((unsigned)(p.rows / 32));
+    return p.key_bias ? xattn_fused_launch<true>(p, nb, grid, st) : xattn_fused_launch<false>(p, nb, grid, st);
 }
 
 // ------------------------------------------------------------------------------ small attention
 
-template <int D>
+// BIAS: p.key_bias[b][j] joins the scaled score of key j (every head, every query).  A key whose biased score is -inf is SKIPPED: with the
+// running maximum still at -inf it would give exp(m - mn) = exp(-inf + inf) = NaN and poison the row (a masked first key), and skipped
+// it contributes exactly nothing, whatever its k / v rows hold.  The caller leaves every row one finite entry.
+template <int D, bool BIAS>
 __global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p, int kc) {
     extern __shared__ float kv[];            // K [kc][D] then V [kc][D]  (f32): the keys pass through LDS in chunks of kc (>= nkv: one chunk)
     const int h = blockIdx.y, b = blockIdx.z;
@@ -779,6 +807,10 @@ __global__ __launch_bounds__(256) void small_attention_kernel(SmallAttnParams p,
             float s = 0.f;
 #pragma unroll
             for (int d = 0; d < D; d++) s += qr[d] * Ks[j * D + d];
+            if constexpr (BIAS) {
+                s += p.key_bias[(long long)b * p.nkv + j0 + j];
+                if (s == -INFINITY) continue;
+            }
             const float mn = fmaxf(m, s);
             const float a = __expf(m - mn), pj = __expf(s - mn);
             l = l * a + pj; m = mn;
@@ -808,8 +840,12 @@ hipError_t launch_small_attention(const SmallAttnParams& p, int D, int heads, in
     int threads = p.nq >= 256 ? 256 : ((p.nq + 63) / 64) * 64;
     int gx = (p.nq + threads - 1) / threads;
     dim3 grid(gx, heads, batch);
-    if (D == 32) small_attention_kernel<32><<<grid, threads, sm, st>>>(p, kc);
-    else small_attention_kernel<64><<<grid, threads, sm, st>>>(p, kc);
+    if (p.key_bias) {
+        if (p.causal) return hipErrorInvalidValue;          // (a causal row may then hold masked keys only)
+        if (D == 32) small_attention_kernel<32, true><<<grid, threads, sm, st>>>(p, kc);
+        else small_attention_kernel<64, true><<<grid, threads, sm, st>>>(p, kc);
+    } else if (D == 32) small_attention_kernel<32, false><<<grid, threads, sm, st>>>(p, kc);
+    else small_attention_kernel<64, false><<<grid, threads, sm, st>>>(p, kc);
     return hipGetLastError();
 }
 

@@ -32,7 +32,7 @@ void rdm_ctx_destroy(rdm_ctx* c) {
     DevGuard guard(c->device);
     hipDeviceSynchronize();
     c->unet.release(); c->vq.release(); c->vqenc.release(); c->clip.release(); c->rarm.release();
-    void* ptrs[] = {c->zero_page, c->eye3, c->gn_partial, c->samp, c->splitk_ws, c->wfrag_tmp, c->bwd_tmp};      // the context's own buffers
+    void* ptrs[] = {c->zero_page, c->eye3, c->gn_partial, c->samp, c->splitk_ws, c->wfrag_tmp, c->bwd_tmp, c->nn_bias};      // the context's own buffers
     for (void* p : ptrs) if (p) hipFree(p);
     c->drop_frags();
     knn_free(c->db);
@@ -55,6 +55,41 @@ int rdm_release_scratch(rdm_ctx* c) {
 }
 int rdm_set_deterministic(rdm_ctx* c, int on) { if (!c) return -1; c->deterministic = on != 0; return 0; }
 int rdm_get_deterministic(rdm_ctx* c) { return c ? (c->deterministic ? 1 : 0) : -1; }
+// The neighbour bias (rdm_hip.h): validated on the host, kept as [rows | rows zero rows][k] on the device (host.h: nn_bias).  A refused
+// bias changes nothing.
+int rdm_set_neighbour_bias(rdm_ctx* c, const float* bias, int rows, int k) {
+    RDM_ENTER(c);
+    if (!bias) { c->nn_bias_rows = c->nn_bias_k = 0; return 0; }       // (the buffer stays for the next bias)
+    if (rows < 1 || k < 1 || k > 256 || (long long)rows * k > (1ll << 24)) return c->fail(-1, "rdm_set_neighbour_bias: bad shape rows=%d k=%d (rows >= 1, 1 <= k <= 256)", rows, k);
+    for (int b = 0; b < rows; b++) {
+        bool any = false;
+        for (int j = 0; j < k; j++) {
+            const float v = bias[(size_t)b * k + j];
+            if (v != v) return c->fail(-1, "rdm_set_neighbour_bias: bias[%d][%d] is NaN", b, j);
+            if (v == INFINITY) return c->fail(-1, "rdm_set_neighbour_bias: bias[%d][%d] is +inf (finite values and -inf only)", b, j);
+            any = any || v != -INFINITY;
+        }
+        if (!any) return c->fail(-1, "rdm_set_neighbour_bias: row %d has no finite entry (a sample must keep at least one neighbour)", b);
+    }
+    const size_t n = (size_t)rows * k;
+    std::vector<float> host(2 * n, 0.f);
+    std::copy(bias, bias + n, host.begin());
+    // a forward already queued on the stream may still read the previous copy
+    RDM_CHECK_HIP(c, hipStreamSynchronize(c->stream));
+    c->nn_bias_rows = c->nn_bias_k = 0;              // (nothing is in force if the copy below fails half-way)
+    RDM_TRY(ensure_bytes(c, (char**)&c->nn_bias, &c->nn_bias_bytes, 2 * n * sizeof(float)));
+    hipError_t e = hipMemcpyAsync(c->nn_bias, host.data(), 2 * n * sizeof(float), hipMemcpyHostToDevice, c->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(c->stream);       // host goes out of scope
+    RDM_CHECK_HIP(c, e);
+    c->nn_bias_rows = rows; c->nn_bias_k = k;
+    return 0;
+}
+int rdm_get_neighbour_bias(rdm_ctx* c, int* rows, int* k) {
+    if (!c) return -1;
+    if (rows) *rows = c->nn_bias_rows;
+    if (k) *k = c->nn_bias_k;
+    return c->nn_bias_rows ? 1 : 0;
+}
 int rdm_set_stream(rdm_ctx* c, void* s) {
     RDM_ENTER(c);
     if ((hipStream_t)s != c->stream) {      // work queued (and derived weight copies packed) on the old stream completes before the new one is used

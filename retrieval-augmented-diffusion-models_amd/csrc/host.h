@@ -252,6 +252,16 @@ struct rdm_ctx {
     // rdm_debug_guidance_prefix: 1 = the shared guidance prefix of a guided forward runs through the first transformer's self-attention,
     // 0 = it ends in front of that transformer (unet_body)
     int prefix_through_attn1 = 1;
+    // neighbour bias (rdm_set_neighbour_bias): device fp32 [2 * nn_bias_rows][nn_bias_k], the caller's validated rows followed by as many
+    // all-zero rows -- the unconditional half of a guided batch, which is never biased -- so that a kernel over [cond | uncond] samples
+    // indexes it by the sample; null: none set.  neighbour_bias_for: the pointer a UNet call over `rows` conditional samples runs under
+    // (null without a bias), or -1 with a message when the bias that is set has another shape.
+    float* nn_bias = nullptr; size_t nn_bias_bytes = 0; int nn_bias_rows = 0, nn_bias_k = 0;
+    int neighbour_bias_for(const char* who, int rows, int k) {
+        if (!nn_bias_rows || (rows == nn_bias_rows && k == nn_bias_k)) return 0;
+        return fail(-1, "%s: a neighbour bias of %d rows x %d neighbours is set, the call has %d conditional samples x %d neighbours (set a matching bias, or clear it with a null pointer)",
+                    who, nn_bias_rows, nn_bias_k, rows, k);
+    }
     // RCCL communicator (rdm_comm_*): library handle from dlopen, function table, communicator
     void* rccl_lib = nullptr; void* comm = nullptr; int comm_world = 0;
     // optional per-launch HIP-event profiler for the GEMM-class kernels (bench.py roofline)

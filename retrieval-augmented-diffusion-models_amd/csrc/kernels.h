@@ -52,6 +52,9 @@ struct XattnParams {
     // LN-fused form only: out may alias x (a block reads its 32 rows before it writes them); ln3_out given: LayerNorm(out rows; ln3_g,
     // ln3_b, ln_eps) -- norm3 of BasicTransformerBlock (attention.py:239) -- leaves with the finished tile as the next GEMM's operand
     const float* ln3_g; const float* ln3_b; bf16_t* ln3_out;
+    // neighbour bias (rdm_hip.h: rdm_set_neighbour_bias): fp32 [samples][group], added to every head's score of neighbour j of the block's
+    // sample before the group softmax; -inf removes the neighbour.  Null: the unbiased instantiations run (the bias is a template parameter)
+    const float* key_bias;
 };
 bool xattn_fused_supported(const XattnParams& p);
 hipError_t launch_xattn_fused(const XattnParams& p, hipStream_t st);        // G / U: FRAGMENT-ORDERED images, written by:
@@ -63,6 +66,7 @@ struct SmallAttnParams {
     bf16_t* out; int ldo;
     int nq, nkv, causal;
     float scale;
+    const float* key_bias;           // optional fp32 [B][nkv], added to every head's scaled score of key j; -inf keys are skipped (not with causal)
 };
 
 // causal self-attention over all query positions, d_head = 64 (attention.hip: causal_d64_kernel); q | k | v are the thirds of the fused

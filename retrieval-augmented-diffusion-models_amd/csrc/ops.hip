@@ -469,6 +469,22 @@ int rdm_op_xattn_fused_ln3(rdm_ctx* c, void* x, const float* ln_gamma, const flo
     if (!xattn_fused_supported(q)) return c->fail(-3, "rdm_op_xattn_fused_ln3: unsupported shape: n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
     return op_xattn_fused(c, q, B);
 }
+int rdm_op_xattn_fused_biased(rdm_ctx* c, void* x, const float* ln_gamma, const float* ln_beta, float ln_eps, const void* G, const void* U,
+                              const float* bias, const void* res, int B, int n, int C, int NP, int ncols, int group, void* out,
+                              const float* ln3_gamma, const float* ln3_beta, void* ln3_out, const float* key_bias) {
+    RDM_ENTER(c);
+    if (!key_bias) return c->fail(-1, "rdm_op_xattn_fused_biased: key_bias is null (the unbiased entries are rdm_op_xattn_fused / _ln3)");
+    if ((ln_gamma != nullptr) != (ln_beta != nullptr) || (ln_gamma && res)) return c->fail(-3, "rdm_op_xattn_fused_biased: LayerNorm needs gamma and beta, and then the residual is x itself (res must be null)");
+    if (ln3_out && (!x || !ln_gamma || !ln3_gamma || !ln3_beta || (out && out != x)))
+        return c->fail(-1, "rdm_op_xattn_fused_biased: the norm3 form runs in place on x with ln_gamma, ln_beta, ln3_gamma and ln3_beta given (out: x or null)");
+    if (!ln3_out && !out) return c->fail(-1, "rdm_op_xattn_fused_biased: out is null");
+    const XattnParams q{.x = (const bf16_t*)x, .G = (const bf16_t*)G, .U = (const bf16_t*)U, .bias = bias, .res = (const bf16_t*)res,
+                        .out = ln3_out ? (bf16_t*)x : (bf16_t*)out, .rows = B * n, .n = n, .C = C, .NP = NP, .ncols = ncols, .group = group,
+                        .ln_g = ln_gamma, .ln_b = ln_beta, .ln_eps = ln_eps, .ln3_g = ln3_out ? ln3_gamma : nullptr, .ln3_b = ln3_out ? ln3_beta : nullptr,
+                        .ln3_out = (bf16_t*)ln3_out, .key_bias = key_bias};
+    if (!xattn_fused_supported(q)) return c->fail(-3, "rdm_op_xattn_fused_biased: unsupported shape (n %% 32, C %% 64, NP %% 32, ncols <= min(NP, 128), group 1 / 2 / 4): n %d C %d NP %d ncols %d group %d", n, C, NP, ncols, group);
+    return op_xattn_fused(c, q, B);
+}
 int rdm_op_head_conv(rdm_ctx* c, const void* x, const float* gn_gamma, const float* gn_beta, float gn_eps, const float* w, const float* bias,
                      int B, int H, int W, int C, int Cout, float* out) {
     RDM_ENTER(c);
@@ -538,6 +554,16 @@ int rdm_op_small_attention(rdm_ctx* c, const void* q, int ldq, const void* k, co
     Ops o = op_exec(c);
     o.small_attention({.q = (const bf16_t*)q, .ldq = ldq, .k = (const bf16_t*)k, .ldk = ldkv, .v = (const bf16_t*)v, .ldv = ldkv, .out = (bf16_t*)out, .ldo = ldo,
                        .nq = nq, .nkv = nkv, .causal = causal, .scale = scale}, D, heads, B, "small attention");
+    return o.rc;
+}
+int rdm_op_small_attention_biased(rdm_ctx* c, const void* q, int ldq, const void* k, const void* v, int ldkv, int B, int nq, int nkv,
+                                  int heads, int D, int causal, float scale, void* out, int ldo, const float* key_bias) {
+    RDM_ENTER(c);
+    if (!key_bias) return c->fail(-1, "rdm_op_small_attention_biased: key_bias is null (the unbiased entry is rdm_op_small_attention)");
+    if (causal) return c->fail(-1, "rdm_op_small_attention_biased: a key bias does not combine with the causal mask");
+    Ops o = op_exec(c);
+    o.small_attention({.q = (const bf16_t*)q, .ldq = ldq, .k = (const bf16_t*)k, .ldk = ldkv, .v = (const bf16_t*)v, .ldv = ldkv, .out = (bf16_t*)out, .ldo = ldo,
+                       .nq = nq, .nkv = nkv, .causal = 0, .scale = scale, .key_bias = key_bias}, D, heads, B, "small attention (biased)");
     return o.rc;
 }
 int rdm_op_conv_in(rdm_ctx* c, const float* x, const float* w, const float* bias, int B, int Cin, int H, int W, int Cout, void* out) {

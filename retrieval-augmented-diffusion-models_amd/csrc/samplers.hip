@@ -96,6 +96,7 @@ struct SamplerRun {
     int begin(rdm_ctx* ctx, const Args* a, const std::vector<int>& ts, const float* x_T, const float* cond, const float* uncond,
               int log_every, float* x_inter_out, float* pred_x0_out, int n_extra) {
         c = ctx; B = a->batch; nb = uncond ? 2 * B : B; k = a->k; H = a->height; W = a->width; total = (int)ts.size();
+        RDM_TRY(c->neighbour_bias_for("sampler", B, k));       // a neighbour bias in force belongs to exactly these B conditional samples
         n1 = (long long)B * a->channels * H * W;
         log_every_t = log_every; x_inter = x_inter_out; pred_x0_inter = pred_x0_out;
         const size_t x_bytes = (size_t)n1 * 4 * (nb / B), t_bytes = (size_t)total * nb * 8, h_stride = al((size_t)n1 * 4);

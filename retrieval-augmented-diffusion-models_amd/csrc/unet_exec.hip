@@ -177,6 +177,10 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         // norm2 + attn2 + residual in one kernel when the neighbours' operands are cached (xa), norm2 too when no channel is padding
         const bool xfused = xa && Mx > 0 && xattn_fused_supported({.rows = Mx, .n = n, .C = C, .NP = XA_NP, .ncols = s.heads * k, .group = k});
         const bool xln = xfused && s.lc == C && C <= 2048;
+        // the neighbour bias (host.h: nn_bias, [conditional rows | as many zero rows][k]; DESIGN 3 "Neighbour bias"): the fused kernels and
+        // the generic branch take it as an operand; the two-GEMM middle form has no place for it, so under a bias the conditional samples of
+        // a shape the fused kernel refuses go through the generic branch, and only the never-biased samples behind them keep the two GEMMs
+        const float* nbias = o.c->nn_bias_rows ? o.c->nn_bias : nullptr;
         // Round 5: in a guided batch [conditional | unconditional] (Bx = Bfull / 2) with the LayerNorm-fused cross-attention kernel,
         //   * the unconditional rows' t2 = attn1.to_out(...) + t0 + b_o2 leaves attn1.to_out's GEMM directly (b_o2 rides in the start
         //     values of those rows: Ops::linear's rowvec; one rounding less than t1 -> + b_o2), no add_bias_rows pass;
@@ -257,12 +261,27 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
         bf16_t* l3 = o.abf((size_t)M * C);
         if (Bx < B && !bias_fold && !o.plan)
             o.check(launch_add_bias_rows(t1 + (size_t)Mx * C, o.w<float>(s.bo2), t2 + (size_t)Mx * C, (long long)(M - Mx), C, o.c->stream), "zero-context cross attention");
+        // the generic branch over samples [b0, b0 + nbat): q projection -> small_attention over the k neighbours -> out projection
+        auto xattn_generic = [&](int b0, int nbat, const float* kb) {
+            const size_t r0 = (size_t)b0 * n * C;
+            bf16_t* q2 = o.abf((size_t)M * C);
+            o.linear({.A0 = l2 + r0, .C0 = C, .W = o.w<bf16_t>(s.wq2), .M = nbat * n, .N = C, .out_bf16 = q2, .sample_rows = n});
+            bf16_t* ao2 = o.abf((size_t)M * C);
+            const bf16_t* kv0 = kv + (size_t)b0 * k * u.kv_total + s.kv_off;
+            o.small_attention({.q = q2, .ldq = C, .k = kv0, .ldk = u.kv_total, .v = kv0 + C, .ldv = u.kv_total, .out = ao2, .ldo = C,
+                               .nq = n, .nkv = k, .scale = 1.0f / sqrtf(32.f), .key_bias = kb ? kb + (size_t)b0 * k : nullptr}, 32, s.heads, nbat, "cross attention");
+            o.linear({.A0 = ao2, .C0 = C, .W = o.w<bf16_t>(s.wo2), .bias = o.w<float>(s.bo2), .M = nbat * n, .N = C, .res_bf16 = t1 + r0, .out_bf16 = t2 + r0, .sample_rows = n});
+        };
+        // samples [0, Bg) of the middle form's go through the generic branch instead: the biased ones
+        const int Bg = (nbias && xa && !xfused) ? (Bx < o.c->nn_bias_rows ? Bx : o.c->nn_bias_rows) : 0;
+        if (Bg > 0) xattn_generic(0, Bg, nbias);
         if (Mx == 0) {
         } else if (xa) {       // two skinny per-sample GEMMs (see unet_compute_xattn)
             bf16_t* P = o.abf((size_t)M * XA_NP);
             const bf16_t* G = xa + (size_t)B * s.xa_unit; const bf16_t* U = G + (size_t)B * XA_NP * C;
             const bf16_t* Gp = U + (size_t)B * C * XA_NP; const bf16_t* Up = Gp + (size_t)B * XA_NP * C;     // their packed images
-            XattnParams xp{.G = Gp, .U = Up, .bias = o.w<float>(s.bo2), .out = t2, .rows = Mx, .n = n, .C = C, .NP = XA_NP, .ncols = s.heads * k, .group = k};
+            XattnParams xp{.G = Gp, .U = Up, .bias = o.w<float>(s.bo2), .out = t2, .rows = Mx, .n = n, .C = C, .NP = XA_NP, .ncols = s.heads * k, .group = k,
+                           .key_bias = nbias};
             if (xln) {          // both GEMMs, the softmax, the residual and norm2 (and norm3) in one launch
                 xp.x = t1; xp.ln_g = o.w<float>(s.ln2g); xp.ln_b = o.w<float>(s.ln2b); xp.ln_eps = 1e-5f;
                 if (xfold_shape) { xp.ln3_g = o.w<float>(s.ln3g); xp.ln3_b = o.w<float>(s.ln3b); xp.ln3_out = l3; }
@@ -270,27 +289,24 @@ static void unet_body(Ops& o, UNet& u, const float* x, const long long* t, const
             } else if (xfused) {   // on the LayerNorm'd rows
                 xp.x = l2; xp.res = t1;
                 o.xattn_fused(xp);
-            } else if (!o.plan) {
+            } else if (!o.plan && Bx > Bg) {
+                const size_t r0 = (size_t)Bg * n * C, g0 = (size_t)Bg * XA_NP * C;         // (Bg = 0 without a bias)
+                const int Br = Bx - Bg; const double Mr = (double)Br * n;
                 IgemmParams p = o.base(n, XA_NP, C);
-                p.A0 = l2; p.C0 = C; p.sA = (long long)n * C; p.W = G; p.sW = (long long)XA_NP * C; p.out_bf16 = P; p.sO = (long long)n * XA_NP;
+                p.A0 = l2 + r0; p.C0 = C; p.sA = (long long)n * C; p.W = G + g0; p.sW = (long long)XA_NP * C; p.out_bf16 = P; p.sO = (long long)n * XA_NP;
                 p.act = ACT_SOFTMAXG; p.sm_group = k;
-                o.prof_begin(RDM_PROF_LINEAR, 2.0 * Mx * XA_NP * (double)C);
-                o.check(launch_igemm(p, false, Bx, o.c->stream), "xattn scores");
+                o.prof_begin(RDM_PROF_LINEAR, 2.0 * Mr * XA_NP * (double)C);
+                o.check(launch_igemm(p, false, Br, o.c->stream), "xattn scores");
                 o.prof_end();
                 IgemmParams q = o.base(n, C, XA_NP);
-                q.A0 = P; q.C0 = XA_NP; q.sA = (long long)n * XA_NP; q.W = U; q.sW = (long long)C * XA_NP; q.bias = o.w<float>(s.bo2);
-                q.res_bf16 = t1; q.out_bf16 = t2; q.sO = (long long)n * C;
-                o.prof_begin(RDM_PROF_LINEAR, 2.0 * Mx * C * (double)XA_NP);
-                o.check(launch_igemm(q, false, Bx, o.c->stream), "xattn out");
+                q.A0 = P; q.C0 = XA_NP; q.sA = (long long)n * XA_NP; q.W = U + g0; q.sW = (long long)C * XA_NP; q.bias = o.w<float>(s.bo2);
+                q.res_bf16 = t1 + r0; q.out_bf16 = t2 + r0; q.sO = (long long)n * C;
+                o.prof_begin(RDM_PROF_LINEAR, 2.0 * Mr * C * (double)XA_NP);
+                o.check(launch_igemm(q, false, Br, o.c->stream), "xattn out");
                 o.prof_end();
             }
         } else {
-            bf16_t* q2 = o.abf((size_t)M * C);
-            o.linear({.A0 = l2, .C0 = C, .W = o.w<bf16_t>(s.wq2), .M = Mx, .N = C, .out_bf16 = q2, .sample_rows = n});
-            bf16_t* ao2 = o.abf((size_t)M * C);
-            o.small_attention({.q = q2, .ldq = C, .k = kv + s.kv_off, .ldk = u.kv_total, .v = kv + s.kv_off + C, .ldv = u.kv_total, .out = ao2, .ldo = C,
-                               .nq = n, .nkv = k, .scale = 1.0f / sqrtf(32.f)}, 32, s.heads, Bx, "cross attention");
-            o.linear({.A0 = ao2, .C0 = C, .W = o.w<bf16_t>(s.wo2), .bias = o.w<float>(s.bo2), .M = Mx, .N = C, .res_bf16 = t1, .out_bf16 = t2, .sample_rows = n});
+            xattn_generic(0, Bx, nbias);
         }
         o.tap(7, t2, (size_t)M * C * 2);
         // --- GEGLU feed-forward
@@ -370,6 +386,8 @@ int unet_forward_impl(rdm_ctx* c, const float* x, const int64_t* t, const float*
     const int down = 1 << (u.cfg.n_channel_mult - 1);
     if (b < 1 || k < 1 || H % down || W % down) return c->fail(-1, "bad unet_forward shape b=%d k=%d H=%d W=%d", b, k, H, W);
     if (k > 256) return c->fail(-1, "k=%d neighbours exceeds the cross-attention kernel limit (256)", k);
+    // (the entries have matched the bias against their conditional rows: neighbour_bias_for; this is what the kernels' indexing needs)
+    if (c->nn_bias_rows && (k != c->nn_bias_k || b > 2 * c->nn_bias_rows)) return c->fail(-1, "unet forward: the neighbour bias in force (%d x %d) does not cover b=%d k=%d", c->nn_bias_rows, c->nn_bias_k, b, k);
     RDM_TRY(ensure_gn_partial(c, b));
     return run_with_arena(c, u.arena, u.blob, [&](Ops& o) {
         const bf16_t* kv = kv_cached;
@@ -392,6 +410,7 @@ int rdm_unet_forward(rdm_ctx* c, const float* x, const int64_t* t, const float* 
                      float* eps_out) {
     RDM_ENTER(c);
     if (!c || !x || !t || !context || !eps_out) return c ? c->fail(-1, "null argument") : -1;
+    RDM_TRY(c->neighbour_bias_for("rdm_unet_forward", b, k));
     return unet_forward_impl(c, x, t, context, nullptr, b, k, H, W, eps_out);
 }
 

@@ -184,18 +184,32 @@ class DatasetBuilder(object):
         ids = np.array([distinct.index(nm) for nm in names], dtype=np.int32)
         return torch.stack(masks), ids, names
 
-    def search_subset(self, query_embeddings, k, subset=None):
+    def search_subset(self, query_embeddings, k, subset=None, short_ok=False):
         """searcher.search_batched over the rows of `subset` (_subset_filter) -> (nns uint32 [b,k], distances); a ValueError where a
-        subset holds fewer than k rows -- before anything indexes the data pool with the "no row" id."""
+        subset holds fewer than k rows -- before anything indexes the data pool with the "no row" id.
+        short_ok [native]: a subset of 1 .. k - 1 rows does not raise; its queries come back with their rows followed by _lib.NO_ROW
+        places (real_neighbours() counts and fills them), for a caller that masks the missing neighbours (the UNet's neighbour bias).  A
+        subset without any row still raises."""
         if subset is None:
             return self.searcher.search_batched(query_embeddings, final_num_neighbors=k)
         allow, ids, names = self._subset_filter(subset, len(query_embeddings))
         nns, distances = self.searcher.search_batched(query_embeddings, final_num_neighbors=k, allow=allow, mask_of_query=ids)
-        short = np.flatnonzero((nns == _lib.NO_ROW).any(axis=1))
+        real = (np.asarray(nns) != _lib.NO_ROW).sum(axis=1)
+        short = np.flatnonzero(real < (1 if short_ok else k))
         if short.size:
             nm = names[int(short[0])]
-            raise ValueError(f"subset {nm!r} allows {len(self._subsets[nm]['rows'])} rows, fewer than k = {k} neighbours (query {int(short[0])})")
+            raise ValueError(f"subset {nm!r} allows {len(self._subsets[nm]['rows'])} rows, fewer than k = {k} neighbours (query {int(short[0])})"
+                             if not short_ok else f"subset {nm!r} allows no row at all (query {int(short[0])}): nothing to attend")
         return nns, distances
+
+    @staticmethod
+    def real_neighbours(nns):
+        """[native] A search result with _lib.NO_ROW places (search_subset(short_ok=True)) -> (counts [b] of real neighbours, which
+        lead each row; the index array with row 0 in the NO_ROW places, safe to index the data pool with; the boolean [b, k] of the
+        real places)."""
+        nns = np.asarray(nns)
+        real = nns != _lib.NO_ROW
+        return real.sum(axis=1).astype(np.int64), np.where(real, nns, 0), real
 
     # ---- dsetbuilder.py:461-473
     @torch.no_grad()
@@ -275,9 +289,11 @@ class DatasetBuilder(object):
         return files
 
     # ---- dsetbuilder.py:478-518
-    def search_k_nearest(self, queries, k=None, is_caption=False, visualize=None, query_embedded=False, subset=None):
+    def search_k_nearest(self, queries, k=None, is_caption=False, visualize=None, query_embedded=False, subset=None, short_ok=False):
         """subset [native]: a name given to define_subset, or a list of one name (or None = the whole database) per query: the exact
-        k nearest among that subset's rows.  A subset of fewer than k rows is a ValueError."""
+        k nearest among that subset's rows.  A subset of fewer than k rows is a ValueError -- unless short_ok [native]: then the
+        missing places hold zero embeddings (img_ids / patch_coords: row 0's, meaningless there; nns keeps _lib.NO_ROW) and
+        out['counts'] holds the number of real neighbours per query (k for everyone without a short subset)."""
         assert self.searcher is not None, 'Cannot search with uninitialized searcher'
         if k is None:
             k = self.k
@@ -286,13 +302,19 @@ class DatasetBuilder(object):
         else:
             query_embeddings_ = queries.cpu().numpy() if isinstance(queries, torch.Tensor) else np.asarray(queries)
         start = time.time()
-        nns, distances = self.search_subset(query_embeddings_, k, subset)                          # normalises on device (:487)
+        nns, distances = self.search_subset(query_embeddings_, k, subset, short_ok=short_ok)       # normalises on device (:487)
         end = time.time()
-        out = {'embeddings': self.data_pool['embedding'][nns],
-               'img_ids': self.data_pool['img_id'][nns] if len(self.data_pool.get('img_id', [])) else None,
-               'patch_coords': self.data_pool['patch_coords'][nns] if len(self.data_pool.get('patch_coords', [])) else None,
+        counts, rows, real = self.real_neighbours(nns)
+        emb = self.data_pool['embedding'][rows]
+        if not real.all():
+            emb = np.where(real[..., None], emb, np.zeros((), dtype=emb.dtype))
+        out = {'embeddings': emb,
+               'img_ids': self.data_pool['img_id'][rows] if len(self.data_pool.get('img_id', [])) else None,
+               'patch_coords': self.data_pool['patch_coords'][rows] if len(self.data_pool.get('patch_coords', [])) else None,
                'queries': queries, 'exec_time': end - start, 'nns': nns, 'distances': distances,
                'q_embeddings': query_embeddings_}
+        if short_ok:
+            out['counts'] = counts
         if visualize if visualize is not None else self.visualize:
             raise NotImplementedError("nn_patches visualisation needs the raw OpenImages JPEGs (out of scope, SURVEY.md §2 #8)")
         return out

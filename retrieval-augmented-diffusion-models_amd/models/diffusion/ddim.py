@@ -14,8 +14,14 @@ Image-to-image -- `stochastic_encode`, `encode`, `decode`, which ldm's DDIMSampl
 added on ldm's surface at the end of the class: the noised start, deterministic DDIM inversion and the partial decode, each a native
 loop or kernel (rdm_op_q_sample_seeded, rdm_ddim_encode, rdm_ddim_decode) with a per-step path behind `callback`.
 """
+import contextlib
+
 import numpy as np
 import torch
+
+from ...util import takes_neighbour_bias
+
+_biased = takes_neighbour_bias(lambda sampler: sampler.model.ctx)      # sample / decode / encode(..., neighbour_bias=[B, k])
 
 
 def make_ddim_timesteps(ddim_discr_method, num_ddim_timesteps, num_ddpm_timesteps, verbose=True):
@@ -129,7 +135,9 @@ class _SamplerBase(object):
             e_t = self.model.apply_model(x, t, c)
         else:
             b = x.shape[0]
-            out = self.model.apply_model(torch.cat([x] * 2), torch.cat([t] * 2), torch.cat([uc, c] if uncond_first else [c, uc]))
+            ctx = getattr(self.model, "ctx", None)      # a neighbour bias in force belongs to the b conditional rows of the doubled batch
+            with (ctx.neighbour_bias_doubled(uncond_first) if hasattr(ctx, "neighbour_bias_doubled") else contextlib.nullcontext()):
+                out = self.model.apply_model(torch.cat([x] * 2), torch.cat([t] * 2), torch.cat([uc, c] if uncond_first else [c, uc]))
             e_c, e_u = (out[b:], out[:b]) if uncond_first else (out[:b], out[b:])
             e_t = e_u + scale * (e_c - e_u)
         if score_corrector is not None:
@@ -156,6 +164,7 @@ class _SamplerBase(object):
 
 class DDIMSampler(_SamplerBase):
 
+    @_biased
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
@@ -372,6 +381,7 @@ class DDIMSampler(_SamplerBase):
         pred_x0 = (x - full(s1m_c) * e_t) / full(sa_c)
         return full(sa_n) * pred_x0 + full(s1m_n) * e_t, pred_x0
 
+    @_biased
     @torch.no_grad()
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None, unconditional_guidance_scale=1.,
                unconditional_conditioning=None, callback=None):
@@ -409,6 +419,7 @@ class DDIMSampler(_SamplerBase):
             out['intermediates'] = inter
         return x.detach(), out
 
+    @_biased
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1., unconditional_conditioning=None, use_original_steps=False,
                callback=None, img_callback=None, eta=None, temperature=1., noise=None, noise_seed=None, noise_row0=0, log_every_t=100,

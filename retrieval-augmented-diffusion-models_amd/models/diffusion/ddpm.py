@@ -18,11 +18,13 @@ import numpy as np
 import torch
 
 from ... import _lib, packing, parallel
-from ...util import ischannellastimage
+from ...util import ischannellastimage, neighbour_bias_from, takes_neighbour_bias
 from .ddim import DDIMSampler, _SamplerBase
 from .dpm_solver import DPMSolverSampler, DPMSolverSDESampler
 from .plms import PLMSSampler
 from .uni_pc import UniPCSampler
+
+_biased = takes_neighbour_bias(lambda model: model.ctx)      # sample_log / sample / p_sample_loop(..., neighbour_bias=[B, k])
 
 
 # ---- [native] inpainting: the mask of sample_log / sample_with_query / sample_from_rdata, handled on the host before any GPU work
@@ -460,6 +462,7 @@ class MinimalRETRODiffusion(object):
         return sig
 
     # ---- samplers
+    @_biased
     @torch.no_grad()
     def sample_log(self, cond, batch_size, ddim, ddim_steps, custom_shape=None, del_sampler=False, plms=False, dpm_solver=False,
                    uni_pc=False, init_latent=None, strength=None, invert=False, invert_scale=1.0, dpm_solver_sde=False, inpaint_mask=None,
@@ -602,6 +605,7 @@ class MinimalRETRODiffusion(object):
             z = sampler.keep_known(z, init_latent, inpaint_mask)
         return z, inter
 
+    @_biased
     @torch.no_grad()
     def sample(self, cond, batch_size=16, return_intermediates=False, x_T=None, timesteps=None, noise=None,
                temperature=1., shape=None, noise_seed=None, noise_row0=0, **kwargs):
@@ -623,6 +627,7 @@ class MinimalRETRODiffusion(object):
         return self.p_sample_loop(cond, shape, return_intermediates=return_intermediates, x_T=x_T, timesteps=timesteps,
                                   noise=noise, temperature=temperature, noise_seed=noise_seed, noise_row0=noise_row0)
 
+    @_biased
     @torch.no_grad()
     def p_sample_loop(self, cond, shape, return_intermediates=False, x_T=None, timesteps=None, noise=None,
                       temperature=1., noise_seed=None, noise_row0=0, **kwargs):
@@ -642,6 +647,13 @@ class MinimalRETRODiffusion(object):
         return (z, [z]) if return_intermediates else z
 
     # ---- retrieval-conditioned entry points
+    @staticmethod
+    def _merge_bias(a, b):
+        """The sum of two neighbour biases (a caller's and the one that masks a short subset's missing places), refused where a row is
+        left without a neighbour."""
+        from ...util import check_neighbour_bias
+        return check_neighbour_bias(a + b)
+
     def train_searcher(self):
         self.retriever.train_searcher()
 
@@ -650,7 +662,8 @@ class MinimalRETRODiffusion(object):
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, return_nns=False,
                           n_reps=None, query_embedded=False, example_maps=None, visualize_nns=True, omit_query=False,
                           normalize=False, device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False,
-                          inpaint_mask=None, keep_known=True, db_subset=None, **kwargs):
+                          inpaint_mask=None, keep_known=True, db_subset=None, nn_counts=None, nn_weights=None,
+                          short_subsets="error", **kwargs):
         """ddpm.py:689-844 (nn_encoder is None, retrieval_encoder = Identity — every shipped config).  device_noise [native]: the
         starting latents and the per-step noise (DDIM eta > 0, DDPM) are the library's counter-based generator's, a function of (the
         call's shared seed, GLOBAL row) generated inside the step kernels (_sample_shard) -- no noise tensor is drawn in Python.
@@ -663,7 +676,18 @@ class MinimalRETRODiffusion(object):
         first stage's factor on the host), float in [0, 1], 1 = KEEP the init image (ldm's convention), 0 = repaint; it is cut to a
         rank's rows like the init image.  keep_known: the known region of the result is the encoded init image exactly.
         db_subset [native]: retrieve from a named subset of the database (retriever.define_subset) -- a name, or one name (or None = the
-        whole database) per sample; the search is the exact top-k of the subset's rows, in the same single pass over the database."""
+        whole database) per sample; the search is the exact top-k of the subset's rows, in the same single pass over the database.
+        nn_counts / nn_weights [native]: the neighbour bias of the UNet's cross-attention (util.neighbour_bias_from) -- nn_counts, an int
+        or one per sample in [1, k_nn]: sample b attends the first nn_counts[b] entries of its conditioning (the query first unless
+        omit_query), so one batch can mix neighbour counts; nn_weights [B, k_nn] >= 0: entry j counts w times (0 = absent).  Tiled like
+        the conditioning under n_reps, cut to a rank's rows like every per-sample argument; not with example_maps.
+        short_subsets [native]: "error" (default) -- a db_subset of fewer rows than the search asks for is a ValueError; "mask" -- its
+        samples attend the neighbours that exist (the missing places hold zero embeddings and are masked).  A subset without any row
+        raises either way."""
+        if short_subsets not in ("error", "mask"):
+            raise ValueError(f'short_subsets must be "error" or "mask", got {short_subsets!r}')
+        if example_maps is not None and (nn_counts is not None or nn_weights is not None or short_subsets == "mask"):
+            raise ValueError("nn_counts / nn_weights / short_subsets='mask' do not combine with example_maps (its conditioning is not the retrieved neighbour list)")
         if cond is not None or return_nns:
             raise NotImplementedError("cond (a second conditioning) / return_nns (neighbour image grids) are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))      # a bad custom_shape fails here, not after the retrieval
@@ -693,6 +717,7 @@ class MinimalRETRODiffusion(object):
             k_nn = self.k_nn
         n_total = len(query)
         lo, hi = self._shard(n_total) if self.distributed else (0, n_total)
+        nn_bias = neighbour_bias_from(n_total, k_nn, nn_counts, nn_weights)         # (refused before the retrieval and any GPU work)
         self._img2img_kwargs(kwargs, n_total, lo, hi, init_image, init_latent, strength, invert,
                              *(() if inpaint_mask is None else (inpaint_mask, keep_known)))
         shard_db = self.distributed and getattr(self, "shard_db", False)
@@ -700,12 +725,24 @@ class MinimalRETRODiffusion(object):
             query = query[lo:hi]            # every rank retrieves for its own rows only (the database is replicated)
             if db_subset is not None and not isinstance(db_subset, str):
                 db_subset = list(db_subset)[lo:hi]
+        short = {"short_ok": True} if short_subsets == "mask" and db_subset is not None else {}
         nn_dict = self.retriever.search_k_nearest(query, visualize=False, k=k_nn, is_caption=is_caption,
-                                                  query_embedded=query_embedded, subset=db_subset)
+                                                  query_embedded=query_embedded, subset=db_subset, **short)
         q_emb = torch.as_tensor(nn_dict['q_embeddings']).float()
         r_emb = torch.as_tensor(nn_dict['embeddings']).float()
+        found = torch.as_tensor(nn_dict['counts']) if short else None
         if shard_db:                        # row-sharded database: every rank searched ALL queries on its rows; keep this rank's samples
             q_emb, r_emb = q_emb[lo:hi], r_emb[lo:hi]
+            found = None if found is None else found[lo:hi]
+        if nn_bias is not None:
+            nn_bias = nn_bias[lo:hi]
+        if found is not None:               # the conditioning's entries that exist: the query (unless omitted), then the found neighbours
+            have = found.clamp(max=k_nn) if omit_query else 1 + found.clamp(max=k_nn - 1)
+            if bool((have < k_nn).any()):
+                gone = neighbour_bias_from(hi - lo, k_nn, nn_counts=have.numpy())
+                nn_bias = gone if nn_bias is None else self._merge_bias(nn_bias, gone)
+        if nn_bias is not None:
+            kwargs["neighbour_bias"] = torch.cat([nn_bias] * n_reps, dim=1) if n_reps is not None else nn_bias
         if normalize:
             q_emb = q_emb / q_emb.norm(dim=-1, keepdim=True)
             r_emb = r_emb / r_emb.norm(dim=-1, keepdim=True)
@@ -766,10 +803,13 @@ class MinimalRETRODiffusion(object):
                           verbose=False, pre_loaded_patches=None, unconditional_guidance_scale=1.,
                           unconditional_guidance_label=None, unconditional_retro_guidance_label=None, nn_embeddings=None,
                           device_noise=False, init_image=None, init_latent=None, strength=0.75, invert=False, inpaint_mask=None,
-                          keep_known=True, db_subset=None, **kwargs):
+                          keep_known=True, db_subset=None, nn_counts=None, nn_weights=None, short_subsets="error", **kwargs):
         """ddpm.py:878-984: pseudo-queries drawn from the DB; the query itself is NOT prepended (:921).  device_noise, init_image /
         init_latent / strength / invert, inpaint_mask / keep_known [native]: as in sample_with_query.  db_subset [native]: the
-        pseudo-queries are drawn as before, from the whole database; only their neighbours come from the subset."""
+        pseudo-queries are drawn as before, from the whole database; only their neighbours come from the subset.  nn_counts /
+        nn_weights / short_subsets [native]: as in sample_with_query, over the k_nn retrieved neighbours (there is no query entry)."""
+        if short_subsets not in ("error", "mask"):
+            raise ValueError(f'short_subsets must be "error" or "mask", got {short_subsets!r}')
         if cond is not None or return_nns or pre_loaded_patches is not None:
             raise NotImplementedError("cond / return_nns / pre_loaded_patches are not part of the native sampling path")
         self._latent_shape(kwargs.get("custom_shape"))
@@ -781,6 +821,7 @@ class MinimalRETRODiffusion(object):
             k_nn = self.k_nn
         qids = self.get_qids(memsize, N, qids=qids, use_weights=use_weights, verbose=verbose)   # rank 0's draw on every rank (get_qids)
         lo, hi = self._shard(N) if self.distributed else (0, N)
+        nn_bias = neighbour_bias_from(N, k_nn, nn_counts, nn_weights)
         self._img2img_kwargs(kwargs, N, lo, hi, init_image, init_latent, strength, invert,
                              *(() if inpaint_mask is None else (inpaint_mask, keep_known)))
         shard_db = self.distributed and getattr(self, "shard_db", False) and nn_embeddings is None
@@ -793,12 +834,25 @@ class MinimalRETRODiffusion(object):
                 nn_embeddings = nn_embeddings[lo:hi]
         query_embeddings = self.retriever.data_pool['embedding'][qids]
         if nn_embeddings is None:
-            nns, _ = self.retriever.search_subset(query_embeddings, k_nn, db_subset)                      # normalises internally
+            mask_short = short_subsets == "mask" and db_subset is not None
+            nns, _ = self.retriever.search_subset(query_embeddings, k_nn, db_subset, short_ok=mask_short)  # normalises internally
             if shard_db:                    # row-sharded database: all pseudo-queries were searched on this rank's rows and merged
                 nns = nns[lo:hi]
-            retro_cond = torch.from_numpy(np.asarray(self.retriever.data_pool['embedding'][nns])).to(self.device).to(torch.float)
+            found, rows, real = self.retriever.real_neighbours(nns)
+            emb = np.asarray(self.retriever.data_pool['embedding'][rows])
+            if not real.all():              # (short_subsets="mask" only: search_subset raised otherwise) zero embeddings, masked below
+                emb = np.where(real[..., None], emb, np.zeros((), dtype=emb.dtype))
+            retro_cond = torch.from_numpy(emb).to(self.device).to(torch.float)
         else:
             retro_cond = nn_embeddings
+            real = None
+        if nn_bias is not None:
+            nn_bias = nn_bias[lo:hi]
+        if real is not None and not real.all():
+            gone = neighbour_bias_from(hi - lo, k_nn, nn_counts=found)
+            nn_bias = gone if nn_bias is None else self._merge_bias(nn_bias, gone)
+        if nn_bias is not None:
+            kwargs["neighbour_bias"] = nn_bias
         c = self.retrieval_encoder(retro_cond).contiguous()
         c_uncond = self.get_unconditional_conditioning(c.shape, unconditional_guidance_label=unconditional_retro_guidance_label, k_nn=k_nn)
         c_uncond = c_uncond.to(self.device).float().contiguous()

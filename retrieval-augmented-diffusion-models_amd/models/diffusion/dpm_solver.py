@@ -31,6 +31,7 @@ import torch
 
 from ... import _lib
 from .ddim import _SamplerBase
+from .ddim import _biased
 
 
 def dpmpp_coefficients(alphas_cumprod, s, t, h_prev=None):
@@ -121,6 +122,7 @@ class _NodeListSampler(_SamplerBase):
 class DPMSolverSampler(_NodeListSampler):
     NAME = "DPM-Solver++"
 
+    @_biased
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
@@ -183,6 +185,7 @@ class DPMSolverSDESampler(_NodeListSampler):
     DPMSolverSampler take the per-step path here too."""
     NAME = "SDE-DPM-Solver++"
 
+    @_biased
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,

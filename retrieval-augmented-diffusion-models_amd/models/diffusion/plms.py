@@ -15,6 +15,7 @@ import numpy as np
 import torch
 
 from .ddim import _SamplerBase
+from .ddim import _biased
 
 
 class PLMSSampler(_SamplerBase):
@@ -24,6 +25,7 @@ class PLMSSampler(_SamplerBase):
         self.ddim_num_steps = ddim_num_steps            # [native] the S the library rebuilds this schedule from
         super().make_schedule(ddim_num_steps, ddim_discretize, ddim_eta, verbose)
 
+    @_biased
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,

@@ -29,12 +29,14 @@ import numpy as np
 import torch
 
 from ... import _lib
+from .ddim import _biased
 from .dpm_solver import _NodeListSampler
 
 
 class UniPCSampler(_NodeListSampler):
     NAME = "UniPC"
 
+    @_biased
     @torch.no_grad()
     def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
                quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,

@@ -111,7 +111,24 @@ def build_parser() -> argparse.ArgumentParser:
                         "and --shard_db")
     parser.add_argument("--db_subset_invert", default=False, action="store_true",
                         help="[native] with --db_subset: retrieve from every row NOT in the file")
+    parser.add_argument("--nn_counts", type=nn_counts_arg, default=None,
+                        help="[native] how many entries of its conditioning a sample attends, in [1, k_nn]: one value, or one per sample of "
+                        "the batch, e.g. 4,2,1,1 (the rest are masked in the UNet's cross-attention)")
+    parser.add_argument("--short_subsets", type=str, default="error", choices=("error", "mask"),
+                        help="[native] with --db_subset: a subset of fewer rows than --k_nn asks for is an error (default), or its missing "
+                        "neighbours are masked")
     return parser
+
+
+def nn_counts_arg(text: str):
+    """--nn_counts: '3' -> 3, '4,2,1' -> [4, 2, 1]"""
+    try:
+        vals = [int(v) for v in text.split(",")]
+    except ValueError:
+        raise argparse.ArgumentTypeError(f"expected an integer or a comma-separated list of integers, got {text!r}")
+    if not vals or min(vals) < 1:
+        raise argparse.ArgumentTypeError(f"neighbour counts are at least 1, got {text!r}")
+    return vals[0] if len(vals) == 1 else vals
 
 
 SIZE_MULTIPLE = 32          # first-stage factor (VQ-f4: 4) x UNet down factor (8) of the shipped models
@@ -139,6 +156,13 @@ def parse_args(argv=None) -> argparse.Namespace:
             parser.error("--mask starts from the noised image: drop --invert")
     if opt.db_subset_invert and opt.db_subset is None:
         parser.error("--db_subset_invert needs --db_subset")
+    if opt.short_subsets != "error" and opt.db_subset is None:
+        parser.error("--short_subsets needs --db_subset")
+    if isinstance(opt.nn_counts, list) and len(opt.nn_counts) != opt.batch_size:
+        parser.error(f"--nn_counts takes one value or one per sample of the batch ({opt.batch_size}), got {len(opt.nn_counts)}")
+    k_eff = 1 if opt.only_caption else opt.k_nn
+    if opt.nn_counts is not None and max(opt.nn_counts if isinstance(opt.nn_counts, list) else [opt.nn_counts]) > k_eff:
+        parser.error(f"--nn_counts must lie in [1, {k_eff}] (the neighbours the call retrieves)")
     if opt.top_m > 1.0:
         opt.top_m = int(opt.top_m)          # top_m should be int if a fixed number of images is given (:138-140)
     if opt.seed is not None and (not opt.increase_guidance) and opt.n_runs > 1:
@@ -270,6 +294,10 @@ def _sampler_kwargs(opt: argparse.Namespace, model=None) -> dict:
         kw["inpaint_mask"] = load_inpaint_mask(opt, model, kw.get("custom_shape"))
     if getattr(opt, "db_subset", None) is not None:
         kw["db_subset"] = define_db_subset(opt, model)
+    if getattr(opt, "nn_counts", None) is not None:
+        kw["nn_counts"] = opt.nn_counts
+    if getattr(opt, "short_subsets", "error") != "error":
+        kw["short_subsets"] = opt.short_subsets
     return kw
 
 
