@@ -597,7 +597,14 @@ int rdm_calib_probe(rdm_ctx* ctx, void* buf /*[dev]*/, size_t buf_bytes, double 
  *                    [B, W], 7 the projected embedding f32 [B, E];
  *   resblock:        1 ln_1 bf16 [rows, W], 2 q|k|v bf16 [rows, 3 W], 3 attention heads bf16 [rows, W], 4 x + out_proj f32 [rows, W],
  *                    5 ln_2 bf16, 6 QuickGELU hidden bf16 [rows, 4 W], 7 x + c_proj f32 (the block's output).
- * tests/test_gpu_clip.py holds every one of them to an fp64 restatement on the library's own inputs. */
+ * tests/test_gpu_clip.py holds every one of them to an fp64 restatement on the library's own inputs.
+ * The first stage shows its layer outputs as bf16 NHWC tokens [B, H W, C], copied as stored and clipped to nbytes, sub = 0, numbered in
+ * execution order.  Decoder (rdm_vq_decode*): block 1000 = conv_in's output, then mid.block_1, mid.attn_1, mid.block_2, then per level
+ * (coarse to fine) each ResnetBlock, each AttnBlock where the level has one, and the Upsample conv's output.  Encoder (rdm_vq_encode*):
+ * block 1500 = conv_in's output, then per level (fine to coarse) each ResnetBlock, each AttnBlock where the level has one, and the
+ * Downsample conv's output, then mid.block_1, mid.attn_1, mid.block_2; a wide latent (VQGAN-f16) adds norm_out + swish and conv_out.
+ * A decoder number never fires during an encode, nor an encoder number during a decode.  tests/test_gpu_emul.py and
+ * tests/test_gpu_vq_encoder.py compare each layer teacher-forced with oracle/vq_emul.py. */
 int rdm_debug_tap(rdm_ctx* ctx, void* buf /*[dev]*/, size_t nbytes, int block, int sub);
 /* test hook: where the SHARED GUIDANCE PREFIX of a guided sampler forward ends.  With classifier-free guidance the UNet batch is
  * [x | x] with contexts [cond | uncond] (ddim.py:229-234), and everything in front of the first cross-attention computes the same values
@@ -628,6 +635,12 @@ int rdm_op_linear_ln(rdm_ctx* ctx, const void* x_bf16, const void* w_bf16, const
 int rdm_op_conv3x3(rdm_ctx* ctx, const void* x0_bf16, const void* x1_bf16, int C0, int C1, const void* w_bf16,
                    const float* bias, const float* rowvec, int rowvec_ld, const void* residual_bf16, void* out_bf16,
                    int B, int Hin, int Win, int N, int stride, int ups);
+/* The first-stage encoder's Downsample conv alone ([ldm] Downsample(with_conv): F.pad(x, (0, 1, 0, 1)) then Conv2d(kernel 3, stride 2,
+ * padding 0)), exactly the call the encoder makes: the 3x3 window of output (oy, ox) starts AT input (2 oy, 2 ox), zero beyond the last
+ * row and column.  x bf16 NHWC [B, Hin, Win, C], w bf16 [N][3][3][C], bias f32 [N] or null, out bf16 [B, Hin / 2, Win / 2, N].  C % 64 == 0
+ * and N even; odd Hin or Win are an argument error and no launch (the context stays usable). */
+int rdm_op_conv3x3_down(rdm_ctx* ctx, const void* x_bf16, int C, const void* w_bf16, const float* bias, void* out_bf16, int B, int Hin, int Win,
+                        int N);
 /* the nearest-code kernel of rdm_vq_encode_indices alone, on caller-given operands: idx_out[m] = argmin_j |e_j|^2 - 2 z_m . e_j, evaluated
  * in fp32 on fp32-input MFMAs, first minimum on ties (taming VectorQuantizer2: torch.argmin); bitwise independent of M.  Any M, N >= 1;
  * E % 64 == 0 and E <= 512, otherwise an argument error and no launch.  Every index lies in [0, N), also for non-finite z. */

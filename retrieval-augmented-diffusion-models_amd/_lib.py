@@ -224,6 +224,7 @@ SIGNATURES = {
     "rdm_op_linear": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "rdm_op_conv3x3": (C.c_int, [_P, _P, _P, C.c_int, C.c_int, _P, _P, _P, C.c_int, _P, _P, C.c_int, C.c_int, C.c_int,
                                  C.c_int, C.c_int, C.c_int]),
+    "rdm_op_conv3x3_down": (C.c_int, [_P, _P, C.c_int, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int]),
     "rdm_op_vq_nearest_code": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_int, _P]),
     "rdm_op_moments_f64": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_op_knn_radius": (C.c_int, [_P, _P, C.c_int, C.c_int, C.c_int, _P]),
@@ -1670,7 +1671,7 @@ class Context:
 
     def debug_tap(self, buf, block, sub=0):
         """The next forwards copy one intermediate activation (block `block`, stage `sub`: include/rdm_hip.h) into `buf`; buf None: off.
-        UNet blocks (0 ..) and first-stage decoder layers (1000 ..) show bf16 tensors; the CLIP text tower (block 2000) and image tower
+        UNet blocks (0 ..), first-stage decoder layers (1000 ..) and encoder layers (1500 ..) show bf16 tensors; the CLIP text tower (block 2000) and image tower
         (block 3000) show each stage in the type it is stored in, fp32 or bf16 (the table in rdm_hip.h): `buf` is a device tensor of
         that type, and at most its numel * element_size bytes are written."""
         self._tap_keepalive = buf
@@ -1733,6 +1734,15 @@ class Context:
         self._check(lib.rdm_op_conv3x3(self._h, _ptr(x0), _ptr(x1), C0, C1, _ptr(w), _ptr(bias), _ptr(rowvec),
                                        0 if rowvec is None else rowvec.shape[1], _ptr(residual), _ptr(out), B, Hin, Win, N,
                                        stride, ups))
+        return out
+
+    def op_conv3x3_down(self, x, w, bias):
+        """The first-stage encoder's Downsample conv (rdm_op_conv3x3_down): F.pad(x, (0, 1, 0, 1)) + a 3x3 conv of stride 2 without padding.
+        x bf16 [B, Hin, Win, C], w bf16 [N, 3, 3, C], bias f32 [N] or None -> bf16 [B, Hin / 2, Win / 2, N]; odd Hin or Win raise RdmError."""
+        B, Hin, Win, Cc = x.shape
+        N = w.shape[0]
+        out = torch.empty((B, Hin // 2, Win // 2, N), device=self.device, dtype=torch.bfloat16)
+        self._check(lib.rdm_op_conv3x3_down(self._h, _ptr(x), Cc, _ptr(w), _ptr(bias), _ptr(out), B, Hin, Win, N))
         return out
 
     def op_rarm_sampler(self, logits, uniforms, guidance_scale=1.0, temperature=1.0, top_k=None, top_p=None, return_kept=False):

@@ -93,10 +93,11 @@ static bf16_t* vq_attn(Ops& o, const VqAttn& a, bf16_t* x, int B, int H, int W) 
     return out;
 }
 
-// debug tap (rdm_debug_tap): first-stage decoder layers are blocks 1000, 1001, ... in execution order (conv_in's output = 1000).
-// tapi: the decoder's running block number; null (the encoder): no taps
+// debug tap (rdm_debug_tap): first-stage decoder layers are blocks 1000, 1001, ... in execution order (conv_in's output = 1000), encoder
+// layers blocks 1500, 1501, ... (conv_in's output = 1500): the ranges are apart, so a decoder number never fires in an encode nor the reverse.
+// tapi: the walker's running block number.  With the tap off this launches and allocates nothing.
+constexpr int TAP_VQ_DECODER = 1000, TAP_VQ_ENCODER = 1500;
 static void vq_tap(Ops& o, int* tapi, const bf16_t* t, int B, int H, int W, int ch) {
-    if (!tapi) return;
     o.cur_block = (*tapi)++; o.cur_layer = 0;
     if (!o.plan && o.c->tap_buf && o.c->tap_sub == 0 && o.c->tap_block == o.cur_block) {
         size_t nb = (size_t)B * H * W * ch * 2; if (nb > o.c->tap_bytes) nb = o.c->tap_bytes;
@@ -122,7 +123,7 @@ static bf16_t* vq_mid(Ops& o, const VqMid& m, bf16_t* h, int B, int H, int W, in
 // decoder trunk shared by the VQ-f4 (ldm) and VQGAN-f16 (taming) first stages: ResnetBlocks, AttnBlocks, nearest-2x upsample convs
 static void vq_trunk(Ops& o, VqModel& v, bf16_t* h, int B, int H, int W, float* img) {
     const rdm_vq_cfg& c = v.cfg;
-    int bin = c.ch * c.ch_mult[c.n_ch_mult - 1], tapi = 1000;
+    int bin = c.ch * c.ch_mult[c.n_ch_mult - 1], tapi = TAP_VQ_DECODER;
     vq_tap(o, &tapi, h, B, H, W, bin);
     h = vq_mid(o, v.mid, h, B, H, W, &tapi);
     for (int lvl = c.n_ch_mult - 1; lvl >= 0; lvl--) {
@@ -181,23 +182,27 @@ static float* vqenc_body(Ops& o, VqEncModel& v, const float* img, int B, int H, 
     const rdm_vq_cfg& c = v.cfg;
     bf16_t* h = o.abf((size_t)B * H * W * c.ch);
     if (!o.plan) o.check(launch_conv_in(img, o.w<float>(v.cinw), o.w<float>(v.cinb), h, B, c.out_ch, H, W, c.ch, o.c->stream), "encoder conv_in");
-    int bin = c.ch;
+    int bin = c.ch, tapi = TAP_VQ_ENCODER;
+    vq_tap(o, &tapi, h, B, H, W, bin);
     for (int lvl = 0; lvl < c.n_ch_mult; lvl++) {
-        h = vq_blocks(o, v.levels[lvl], h, B, H, W, bin, nullptr);
+        h = vq_blocks(o, v.levels[lvl], h, B, H, W, bin, &tapi);
         if (lvl != c.n_ch_mult - 1) {      // F.pad(x, (0, 1, 0, 1)) + Conv2d(stride 2, padding 0): window rows 2 oy .. 2 oy + 2, zero beyond the last row / column
             const ConvW& d = v.levels[lvl].resample;
             bf16_t* out = o.abf((size_t)B * (H / 2) * (W / 2) * d.c);
             o.conv3({.A0 = h, .C0 = d.c, .W = o.w<bf16_t>(d.w), .bias = o.w<float>(d.b), .B = B, .Hin = H, .Win = W, .N = d.c, .stride = 2, .out_bf16 = out, .asym = 1});
             h = out; H /= 2; W /= 2;
+            vq_tap(o, &tapi, h, B, H, W, d.c);
         }
     }
-    h = vq_mid(o, v.mid, h, B, H, W, nullptr);
+    h = vq_mid(o, v.mid, h, B, H, W, &tapi);
     bf16_t* no = o.abf((size_t)B * H * W * bin);
     if (v.wide) {
         const int M = B * H * W;
         o.groupnorm({.x0 = h, .C0 = bin, .HW = H * W, .B = B, .gamma = o.w<float>(v.noutg), .beta = o.w<float>(v.noutb), .eps = 1e-6f, .silu = 1, .out = no});
+        vq_tap(o, &tapi, no, B, H, W, bin);
         bf16_t* ze = o.abf((size_t)M * c.z_channels);
         o.conv3({.A0 = no, .C0 = bin, .W = o.w<bf16_t>(v.coutw), .bias = o.w<float>(v.coutb), .B = B, .Hin = H, .Win = W, .N = c.z_channels, .out_bf16 = ze});
+        vq_tap(o, &tapi, ze, B, H, W, c.z_channels);
         float* zt = o.af32((size_t)M * c.embed_dim);
         o.linear({.A0 = ze, .C0 = c.z_channels, .W = o.w<bf16_t>(v.qw), .bias = o.w<float>(v.qb), .M = M, .N = c.embed_dim, .out_f32 = zt});
         if (z && !o.plan) o.check(launch_vq_rows_to_nchw(zt, nullptr, z, B, H * W, c.embed_dim, o.c->stream), "latent to NCHW");

@@ -57,6 +57,16 @@ int rdm_op_conv3x3(rdm_ctx* c, const void* x0, const void* x1, int C0, int C1, c
              .stride = stride, .ups = ups, .res_bf16 = (const bf16_t*)res, .out_bf16 = (bf16_t*)out, .rowvec = rowvec, .rowvec_ld = rowvec_ld});
     return o.rc;
 }
+// the first-stage encoder's Downsample conv (vqenc_body's call): F.pad(x, (0, 1, 0, 1)) + Conv2d(3, stride 2, padding 0) on the generic implicit GEMM
+int rdm_op_conv3x3_down(rdm_ctx* c, const void* x, int C, const void* w, const float* bias, void* out, int B, int Hin, int Win, int N) {
+    RDM_ENTER(c);
+    if (!x || !w || !out || B < 1 || Hin < 2 || Win < 2 || C < 64 || C % 64 || N < 2 || N % 2 || (long long)B * Hin * Win > 0x7fffffffLL)
+        return c->fail(-1, "rdm_op_conv3x3_down: bad argument (null pointer, or B %d Hin %d Win %d C %d N %d: C %% 64 == 0, N even)", B, Hin, Win, C, N);
+    if (Hin % 2 || Win % 2) return c->fail(-1, "rdm_op_conv3x3_down: Hin and Win must be even (a Downsample halves exactly), got %d x %d", Hin, Win);
+    Ops o = op_exec(c);
+    o.conv3({.A0 = (const bf16_t*)x, .C0 = C, .W = (const bf16_t*)w, .bias = bias, .B = B, .Hin = Hin, .Win = Win, .N = N, .stride = 2, .out_bf16 = (bf16_t*)out, .asym = 1});
+    return o.rc;
+}
 // the nearest-code kernel alone on caller-given operands (vqcode.hip): |e|^2 and the split planes live in the sampler scratch
 int rdm_op_vq_nearest_code(rdm_ctx* c, const float* z, const float* codebook, long long M, int N, int E, int32_t* idx_out) {
     RDM_ENTER(c);

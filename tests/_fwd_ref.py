@@ -352,14 +352,19 @@ class Conv3x3:
     small (a plane rounded to bf16 is seen) and every 64-channel slice carries weight.  Near misses: the K-split planes rounded to bf16;
     the last 64-channel slice of tap (2, 2) dropped; the taps flipped; the neighbouring sample's rows instead of the zero padding (and, on
     strips, zero padding at the 64-column strip edges instead of the neighbouring strip's pixels); the time-embedding row of sample b + 1;
-    the bias missing on the last 8 channels; bilinear instead of nearest upsample; the residual dropped."""
+    the bias missing on the last 8 channels; bilinear instead of nearest upsample; the residual dropped.
+    asym = 1 (rdm_op_conv3x3_down, IgemmParams::asym): the first-stage encoder's Downsample, conv2d(pad(x, (0, 1, 0, 1)), w, stride 2) without
+    further padding -- the window of output (oy, ox) starts AT input (2 oy, 2 ox), zero beyond the last row and column; bound and launch
+    geometry are those of the stride-2 generic conv.  Its near misses: the symmetric padding-1 stride-2 conv (window origin one up and
+    left); the zero row / column on the other side, pad (1, 0, 1, 0); the conv without its bias."""
     name = "conv3x3"
     exact = False
 
     @staticmethod
-    def make(B, H, W, C0, N, C1=0, stride=1, ups=0, rowvec=False, ld_pad=0, res=False, seed=51):
+    def make(B, H, W, C0, N, C1=0, stride=1, ups=0, rowvec=False, ld_pad=0, res=False, seed=51, asym=0):
         g = torch.Generator().manual_seed(seed)
         C = C0 + C1
+        assert not asym or (stride == 2 and not (ups or C1 or rowvec or res) and H % 2 == 0 and W % 2 == 0)
         kind, S = conv_path(B, H, W, C, N, stride, ups, C1 > 0, rowvec, res)
         x = bfr(torch.randn(B, H, W, C, generator=g) + 1.5)
         mean = torch.zeros(C)
@@ -372,7 +377,7 @@ class Conv3x3:
             mean[lo:hi] = -(bounds[-1][0]) / (hi - lo)
         w = bfr((torch.randn(N, C, 3, 3, generator=g) + 0.5 * mean[None, :, None, None]) / math.sqrt(9 * C))
         Ho, Wo = (2 * H, 2 * W) if ups else ((H // 2, W // 2) if stride == 2 else (H, W))
-        inp = {"x": x, "C0": C0, "w": w, "b": 0.5 * torch.randn(N, generator=g), "stride": stride, "ups": ups, "S": S, "kind": kind}
+        inp = {"x": x, "C0": C0, "w": w, "b": 0.5 * torch.randn(N, generator=g), "stride": stride, "ups": ups, "S": S, "kind": kind, "asym": asym}
         if rowvec:
             inp["t"] = torch.randn(B, N + ld_pad, generator=g)
         if res:
@@ -380,9 +385,11 @@ class Conv3x3:
         return inp
 
     @staticmethod
-    def conv(inp, dt, x=None, w=None, mode="nearest", stack=False, strips=False):
+    def conv(inp, dt, x=None, w=None, mode="nearest", stack=False, strips=False, pad=(0, 1, 0, 1)):
         x = (inp["x"] if x is None else x).to(dt).permute(0, 3, 1, 2)
         w = (inp["w"] if w is None else w).to(dt)
+        if inp.get("asym") and pad is not None:                 # pad None: the symmetric conv below
+            return F.conv2d(F.pad(x, pad), w, stride=2).permute(0, 2, 3, 1)
         if inp["ups"]:
             x = F.interpolate(x, scale_factor=2, mode=mode, **({} if mode == "nearest" else {"align_corners": False}))
         if stack:                                            # the samples stacked vertically: each one's top / bottom pad row is its neighbour
@@ -394,10 +401,12 @@ class Conv3x3:
         return F.conv2d(x, w, stride=inp["stride"], padding=1).permute(0, 2, 3, 1)
 
     @staticmethod
-    def epilogue(inp, dt, y, shift_t=False, bias_cut=False, no_res=False):
+    def epilogue(inp, dt, y, shift_t=False, bias_cut=False, no_res=False, no_bias=False):
         b = inp["b"].to(dt).clone()
         if bias_cut:
             b[-8:] = 0
+        if no_bias:
+            b[:] = 0
         y = y + b
         if "t" in inp:
             t = inp["t"].to(dt)[:, : y.shape[3]]
@@ -441,6 +450,10 @@ class Conv3x3:
         m = [("last 64-channel slice of tap (2, 2) dropped", {"out": Conv3x3.epilogue(inp, F64, Conv3x3.conv(inp, F64, w=w))}),
              ("taps flipped", {"out": Conv3x3.epilogue(inp, F64, Conv3x3.conv(inp, F64, w=inp["w"].flip(2, 3)))}),
              ("bias missing on the last 8 channels", Conv3x3.ref(inp, F64, bias_cut=True))]
+        if inp.get("asym"):
+            m += [("symmetric padding 1 (window origin one up and left)", {"out": Conv3x3.epilogue(inp, F64, Conv3x3.conv(inp, F64, pad=None))}),
+                  ("zero row and column on the wrong side: pad (1, 0, 1, 0)", {"out": Conv3x3.epilogue(inp, F64, Conv3x3.conv(inp, F64, pad=(1, 0, 1, 0)))}),
+                  ("bias dropped", Conv3x3.ref(inp, F64, no_bias=True))]
         if inp["stride"] == 1 and inp["x"].shape[0] > 1:
             m.append(("neighbouring sample instead of zero padding", {"out": Conv3x3.epilogue(inp, F64, Conv3x3.conv(inp, F64, stack=True))}))
         Wo = inp["x"].shape[2] * (2 if inp["ups"] else 1)
@@ -1034,7 +1047,7 @@ def _lnf(**kw):
 def _conv(**kw):
     kind, S = conv_path(kw["B"], kw["H"], kw["W"], kw["C0"] + kw.get("C1", 0), kw["N"], kw.get("stride", 1), kw.get("ups", 0), kw.get("C1", 0) > 0,
                         kw.get("rowvec", False), kw.get("res", False))
-    return (_CV, kw, kind + (f" + K-split {S} + splitk_finish" if S > 1 else ""))
+    return (_CV, kw, kind + (f" + K-split {S} + splitk_finish" if S > 1 else "") + (": asym (Downsample)" if kw.get("asym") else ""))
 
 
 def _gn(**kw):
@@ -1148,6 +1161,12 @@ CASES = [
     _conv(B=3, H=6, W=10, C0=64, N=64, stride=2),
     _conv(B=2, H=5, W=7, C0=64, N=64, ups=1),
     _conv(B=1, H=5, W=7, C0=64, C1=64, N=72, ups=1),
+    # the first-stage encoder's Downsample (rdm_op_conv3x3_down): a square and a non-square batch, ONE output pixel whose every border tap is
+    # masked (2 x 2 input: the window's last row and column are all padding), and a 128-channel non-square input
+    _conv(B=2, H=16, W=16, C0=64, N=64, stride=2, asym=1),
+    _conv(B=3, H=6, W=10, C0=64, N=64, stride=2, asym=1),
+    _conv(B=1, H=2, W=2, C0=64, N=128, stride=2, asym=1),
+    _conv(B=1, H=10, W=14, C0=128, N=128, stride=2, asym=1),
     # stem conv, all four instantiations: one partial wave; direct stores, four input channels; a short second block; one pixel; a ragged
     # second grid-stride trip
     _cin(B=2, Cin=3, H=5, W=7, Cout=64),

@@ -33,7 +33,7 @@ def test_case_ids_name_every_launch_path():
     for kernel in ("halo4<2>", "halo4<3>", "halo4<2, STRIP>", "halo4<3, STRIP>", "conv_in_kernel<4, 3>", "conv_in_kernel<4, 4>", "conv_in_kernel<0, 3>", "conv_in_kernel<0, 4>",
                    "conv_out_kernel", "small_attention_kernel<32>: 2 key chunks", "small_attention_kernel<32>: 3 key chunks",
                    "small_attention_kernel<64>: causal, 2 key chunks", "gn_stats + gn_apply: 17 chunks of 65 rows, the last one short",
-                   "blocks x 2 trips", "K-split 2", "K-split 3", "igemm phase2", "igemm conv",
+                   "blocks x 2 trips", "K-split 2", "K-split 3", "igemm phase2", "igemm conv", "igemm conv: asym (Downsample)",
                    "igemm ups", "igemm<128, 128", "igemm<256, 192", "igemm<128, 192", "igemm<256, 128", "res_k", "igemm<256, 256, GEGLU>",
                    "igemm<128, 128, GEGLU>", "igemm<256, 128, GEGLU>", "lin4<plain, WM1>", "lin4<plain, WM2>", "lin4<GEGLU, WM1>",
                    "lin4<GEGLU, WM2>", "rowvec", "sgemm", "mgemm", "LN>", "gn_onepass<NV", ", 512>", ", 1024>", "gn_stats + gn_apply",
@@ -44,6 +44,25 @@ def test_case_ids_name_every_launch_path():
                    "igemm<128, 128>: f32 residual in place", "igemm<128, 192>: f32 residual in place", "layernorm_kernel<f32>: f32 out",
                    "small_attention_kernel<64>: causal, 1 key chunks, fused q|k|v rows", "small_attention_kernel<64>: 1 key chunks, fused q|k|v rows"):
         assert kernel in paths, kernel
+
+
+def test_downsample_cases_are_the_encoders_and_each_has_its_three_misses():
+    """The asym (Downsample) form of the conv3x3 case: the four shapes rdm_op_conv3x3_down is run at, the fp64 reference is
+    conv2d(pad(x, (0, 1, 0, 1)), w, stride 2) + bias, each shape carries the symmetric-padding, wrong-side-padding and dropped-bias near
+    misses (check() above has shown the fp32 stand-in outside the bound against each), and odd sizes are not a case."""
+    import torch.nn.functional as F
+    down = [e[1] for e in R.CASES if e[0] is R.Conv3x3 and e[1].get("asym")]
+    assert [(k["B"], k["H"], k["W"], k["C0"], k["N"]) for k in down] == [(2, 16, 16, 64, 64), (3, 6, 10, 64, 64), (1, 2, 2, 64, 128), (1, 10, 14, 128, 128)]
+    for kw in down:
+        inp = R.Conv3x3.make(**kw)
+        x, w = inp["x"].double().permute(0, 3, 1, 2), inp["w"].double()
+        want = (F.conv2d(F.pad(x, (0, 1, 0, 1)), w, stride=2) + inp["b"].double()[None, :, None, None]).permute(0, 2, 3, 1)
+        ref = R.Conv3x3.ref(inp, torch.float64)["out"]
+        assert ref.shape == (kw["B"], kw["H"] // 2, kw["W"] // 2, kw["N"]) and torch.equal(ref, want)
+        labels = [m[0] for m in R.Conv3x3.misses(inp)]
+        assert sum(("symmetric padding" in s) + ("wrong side" in s) + (s == "bias dropped") for s in labels) == 3, labels
+    with pytest.raises(AssertionError):
+        R.Conv3x3.make(B=1, H=5, W=6, C0=64, N=64, stride=2, asym=1)
 
 
 def test_bf16_ksplit_planes_fall_outside_the_bound():

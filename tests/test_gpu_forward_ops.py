@@ -56,6 +56,8 @@ def _run(ctx, case, inp):
     if case is R.Conv3x3:
         x, C0 = inp["x"], inp["C0"]
         x1 = b(x[..., C0:]) if x.shape[3] > C0 else None
+        if inp["asym"]:             # the first-stage encoder's Downsample: its own entry point, exactly vqenc_body's call
+            return {"out": ctx.op_conv3x3_down(b(x), b(inp["w"].permute(0, 2, 3, 1)), f(inp["b"]))}
         return {"out": ctx.op_conv3x3(b(x[..., :C0]), b(inp["w"].permute(0, 2, 3, 1)), f(inp["b"]), x1=x1, rowvec=o(inp.get("t")),
                                       residual=b(inp["res"]) if "res" in inp else None, stride=inp["stride"], ups=inp["ups"])}
     if case is R.GroupNorm:
@@ -125,6 +127,27 @@ def test_linear_mgemm_matches_fp64_restatement(ctx):
     r = subprocess.run([sys.executable, "-c", code], env=dict(os.environ, RDM_MGEMM_ANY="64"), capture_output=True, text=True, timeout=600)
     print(r.stdout[-2000:])
     assert r.returncode == 0 and "OK" in r.stdout, r.stdout[-2000:] + r.stderr[-3000:]
+
+
+def test_conv3x3_down_refuses_odd_sizes_and_the_context_stays_usable(ctx):
+    """rdm_op_conv3x3_down: an odd Hin or Win is an argument error and no launch (the output keeps its sentinel); the next call on the same
+    context runs and is held to the bound."""
+    from rdm_amd import _lib
+    d = ctx.device
+    g = torch.Generator().manual_seed(9)
+    w, bias = torch.randn(64, 3, 3, 64, generator=g).to(d, BF), torch.randn(64, generator=g).to(d)
+    for H, W in ((5, 6), (6, 5), (1, 1)):
+        x = torch.randn(1, H, W, 64, generator=g).to(d, BF)
+        out = torch.full((1, max(H // 2, 1), max(W // 2, 1), 64), 7.0, device=d, dtype=BF)
+        rc = _lib.lib.rdm_op_conv3x3_down(ctx._h, x.data_ptr(), 64, w.data_ptr(), bias.data_ptr(), out.data_ptr(), 1, H, W, 64)
+        torch.cuda.synchronize()
+        assert rc != 0 and bool((out == 7.0).all()), (H, W, rc)
+        with pytest.raises(_lib.RdmError, match="rdm_op_conv3x3_down"):
+            ctx.op_conv3x3_down(x, w, bias)
+    inp = R.Conv3x3.make(B=3, H=6, W=10, C0=64, N=64, stride=2, asym=1)
+    out = _run(ctx, R.Conv3x3, inp)
+    torch.cuda.synchronize()
+    check(R.Conv3x3, inp, {k: v.float().cpu() for k, v in out.items()})
 
 
 def test_xattn_ln3_matches_layernorm_of_its_own_rows(ctx):
