@@ -604,7 +604,30 @@ int rdm_calib_probe(rdm_ctx* ctx, void* buf /*[dev]*/, size_t buf_bytes, double 
  * block 1500 = conv_in's output, then per level (fine to coarse) each ResnetBlock, each AttnBlock where the level has one, and the
  * Downsample conv's output, then mid.block_1, mid.attn_1, mid.block_2; a wide latent (VQGAN-f16) adds norm_out + swish and conv_out.
  * A decoder number never fires during an encode, nor an encoder number during a decode.  tests/test_gpu_emul.py and
- * tests/test_gpu_vq_encoder.py compare each layer teacher-forced with oracle/vq_emul.py. */
+ * tests/test_gpu_vq_encoder.py compare each layer teacher-forced with oracle/vq_emul.py.
+ * The RARM transformer shows its executors the same way (each tensor copied as it is stored, row-major; sub = 16 * layer + stage, layer 0
+ * the executor's own stages, layer i + 1 transformer block i; B sequences with k neighbours, B2 = 2 B rows in a guided sampling call,
+ * else B; C = n_heads * d_head, V = vocab_out):
+ *   block 4000, the per-call preparation (every rdm_rarm_* entry):
+ *     layer 0:       1 the neighbours cast to bf16 [B k, context_dim], 2 the neighbours' keys | values of all layers, bf16
+ *                    [B2 k, depth * 2 C] (layer l's keys at column 2 l C, its values at 2 l C + C; the unconditional rows zero);
+ *     layer l + 1:   1 G_l = expand_heads(K_l) / sqrt(d_head) . W_q, 2 UT_l = W_o . expand_heads(V_l), each bf16 [B, 128, C] -- only in a
+ *                    call whose decode steps take the one-launch cross-attention (n_heads * k <= 128, and B2 < 384 or deterministic mode);
+ *   block 4100, the decode step (rdm_rarm_forward, the rdm_rarm_sample* loops), rows = B2:
+ *     layer 0:       1 token + positional embedding f32 [rows, C], 2 the final x cast to bf16 [rows, C], 3 the logits f32 [rows, V];
+ *     block:         1 norm1 bf16 [rows, C], 2 q|k|v bf16 [rows, 3 C], 3 self-attention heads bf16 [rows, C], 4 x + attn1.to_out f32,
+ *                    5 norm2 bf16, 6 attn2.to_q bf16, 7 cross-attention heads bf16, 8 x + attn2 f32, 9 norm3 bf16, 10 GEGLU hidden bf16
+ *                    [rows, 4 C], 11 x + ff.net.2 f32 (the block's output).
+ *     A stage the chosen form does not hold in memory does not fire: 1, 5 and 9 exist only where the LayerNorm runs as a pass of its own
+ *     (not formed inside the skinny GEMM: more than 192 rows outside deterministic mode, or a shape the in-kernel form declines); in the
+ *     one-launch cross-attention 5, 6 and 7 do not exist and 9 is the norm3 the kernel emits.  One entry runs many steps: step s, counted
+ *     over the decode steps of that entry, lands at byte offset s * (stage bytes), clipped to nbytes, so that one rdm_rarm_forward over t
+ *     positions (or one sampling call) shows a stage at every position: [steps, rows, width].
+ *   block 4200, the whole-sequence pass (rdm_rarm_forward_seq, rdm_rarm_nll, the prefix of rdm_rarm_sample_prefill), rows = B2 t, sequence
+ *     major: the decode step's layer and stage numbers, all eleven block stages always; layer 0 stages 2 and 3 where the call has a head
+ *     (3: rdm_rarm_forward_seq only).  Each range of sequences the pass walks lands at its own row offset, clipped.
+ * A 4100 number never fires in the whole-sequence pass, nor a 4200 number in a decode step.  tests/test_gpu_rarm_stages.py holds every
+ * stage to a float64 restatement of that stage on the library's own tapped inputs (tests/_rarm_stage_ref.py). */
 int rdm_debug_tap(rdm_ctx* ctx, void* buf /*[dev]*/, size_t nbytes, int block, int sub);
 /* test hook: where the SHARED GUIDANCE PREFIX of a guided sampler forward ends.  With classifier-free guidance the UNet batch is
  * [x | x] with contexts [cond | uncond] (ddim.py:229-234), and everything in front of the first cross-attention computes the same values

@@ -160,13 +160,14 @@ void Ops::conv3(const Conv3Op& op) {
 //  profiles/r06_conv_tail_split_*.log, r06_conv_remainder_split_*.)
 // twice: the stage ran on the first half of a guided batch only (unet_body's shared prefix inside the first transformer) and ptr holds
 // those nbytes; the tap shows the LOGICAL tensor, both halves, the second a copy of the first
-void Ops::tap(int stage, const void* ptr, size_t nbytes, bool twice) {      // rdm_debug_tap: stage `stage` of layer cur_layer of block cur_block
-    if (plan || !c->tap_buf || c->tap_block != cur_block || c->tap_sub != cur_layer * 16 + stage) return;
-    const size_t n0 = nbytes > c->tap_bytes ? c->tap_bytes : nbytes;
-    check(hipMemcpyAsync(c->tap_buf, ptr, n0, hipMemcpyDeviceToDevice, c->stream), "debug tap");
-    if (!twice || c->tap_bytes <= nbytes) return;
-    const size_t n1 = c->tap_bytes - nbytes < nbytes ? c->tap_bytes - nbytes : nbytes;
-    check(hipMemcpyAsync((char*)c->tap_buf + nbytes, ptr, n1, hipMemcpyDeviceToDevice, c->stream), "debug tap");
+void Ops::tap(int stage, const void* ptr, size_t nbytes, bool twice, size_t offset) {      // rdm_debug_tap: stage `stage` of layer cur_layer of block cur_block
+    if (plan || !c->tap_buf || c->tap_block != cur_block || c->tap_sub != cur_layer * 16 + stage || offset >= c->tap_bytes) return;
+    char* dst = (char*)c->tap_buf + offset; const size_t room = c->tap_bytes - offset;
+    const size_t n0 = nbytes > room ? room : nbytes;
+    check(hipMemcpyAsync(dst, ptr, n0, hipMemcpyDeviceToDevice, c->stream), "debug tap");
+    if (!twice || room <= nbytes) return;
+    const size_t n1 = room - nbytes < nbytes ? room - nbytes : nbytes;
+    check(hipMemcpyAsync(dst + nbytes, ptr, n1, hipMemcpyDeviceToDevice, c->stream), "debug tap");
 }
 void Ops::prof_begin(int kind, double work, int d0, int d1, int d2) {       // work: FLOPs (GEMM-class kinds) or bytes (bandwidth-class kinds)
     prof_open = (c->prof >> kind) & 1u;

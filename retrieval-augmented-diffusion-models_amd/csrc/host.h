@@ -249,6 +249,7 @@ struct rdm_ctx {
     bool deterministic = rdm_env_int(getenv("RDM_DETERMINISTIC"), 0) != 0;
     // debug tap (rdm_debug_tap): the output activation of top-level UNet block `tap_block` (NHWC bf16) is copied into tap_buf by the next forward
     void* tap_buf = nullptr; size_t tap_bytes = 0; int tap_block = -1, tap_sub = 0;      // tap_sub: 0 = the block's output, else 16 * layer-in-block + stage (unet_body)
+    int tap_step = 0;      // decode steps (rarm_step) run so far by the current RARM entry: step s shows its stage at byte offset s * (stage bytes)
     // rdm_debug_guidance_prefix: 1 = the shared guidance prefix of a guided forward runs through the first transformer's self-attention,
     // 0 = it ends in front of that transformer (unet_body)
     int prefix_through_attn1 = 1;
@@ -358,7 +359,8 @@ struct Ops {
     bool linear_ln(const LinearOp& op);
     void conv3(const Conv3Op& op);
     int cur_block = -1, cur_layer = 0;           // position in the UNet's block table (debug tap)
-    void tap(int stage, const void* ptr, size_t nbytes, bool twice = false);      // twice: ptr holds the first half of the logical tensor, whose second half equals it
+    // twice: ptr holds the first half of the logical tensor, whose second half equals it; offset: where in the buffer the copy lands (clipped)
+    void tap(int stage, const void* ptr, size_t nbytes, bool twice = false, size_t offset = 0);
     bool prof_open = false;
     const char* tag = "";        // role of the ops that follow in the graph ("st.proj_in", "res.conv1", ...): rdm_prof_dump groups by it
     void prof_begin(int kind, double work, int d0 = 0, int d1 = 0, int d2 = 0);

@@ -4,6 +4,9 @@
 #include "host.h"
 
 // ---- RARM (kernels in rarm.hip)
+// rdm_debug_tap blocks of the three executors (include/rdm_hip.h): sub = 16 * layer + stage, layer 0 the executor's own stages, layer
+// i + 1 transformer block i
+constexpr int TAP_RARM_PREPARE = 4000, TAP_RARM_STEP = 4100, TAP_RARM_SEQ = 4200;
 struct RarmState { int* pos; int* done; long long* tokens; float* logits; };
 static RarmState rarm_state(RarmModel& m, int B2) {
     RarmState st{};
@@ -30,14 +33,18 @@ static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,c
     constexpr int RARM_XGEMM_FROM = 384;
     const bool fuse = decode && g.n_heads * k <= 128 && C <= 1024 && C % 64 == 0 && (c->deterministic || B2 < RARM_XGEMM_FROM);
     m.xa_B = 0; m.xa_k = 0;
+    c->tap_step = 0;
     if (fuse) {
         RDM_TRY(ensure_bytes(c, &m.xa, &m.xa_bytes, (size_t)g.depth * 2 * B * 128 * C * 2));
         m.xa_B = B; m.xa_k = k;
     }
     return run_with_arena(c, m.arena, m.blob, [&](Ops& o) {
+        o.cur_block = TAP_RARM_PREPARE; o.cur_layer = 0;
         bf16_t* cb = o.abf((size_t)B * k * g.context_dim);
         if (!o.plan) o.check(launch_cast_f32_bf16(context, cb, (long long)B * k * g.context_dim, c->stream), "cast ctx");
+        o.tap(1, cb, (size_t)B * k * g.context_dim * 2);
         o.linear({.A0 = cb, .C0 = g.context_dim, .W = o.w<bf16_t>(m.kvw), .M = B * k, .N = m.kv_total, .out_bf16 = (bf16_t*)m.ctxkv});
+        o.tap(2, m.ctxkv, (size_t)B2 * k * m.kv_total * 2);
         // the decode step's cross-attention re-associated per sequence (rarm.hip: rarm_xattn_decode_kernel):
         //   G_l[b][(h,j)][:] = (K_bj restricted to head h) W_q / sqrt(d),   UT_l[b][(h,j)][:] = W_o (V_bj restricted to head h)
         if (fuse) {
@@ -57,6 +64,9 @@ static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,c
                     IgemmParams q = o.base(B * NP, C, C);
                     q.A0 = vexp; q.C0 = C; q.W = o.w<bf16_t>(bk.wo2); q.out_bf16 = UT;
                     o.check(launch_igemm(q, false, 1, c->stream), "rarm xattn UT");
+                    o.cur_layer = l + 1;
+                    o.tap(1, G, (size_t)B * NP * C * 2);
+                    o.tap(2, UT, (size_t)B * NP * C * 2);
                 }
             }
         }
@@ -66,26 +76,34 @@ static int rarm_prepare(rdm_ctx* c, int B2, int k, const float* context /*[B,k,c
 static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy of the position processed (profiling only: the kernels read the device counter) */) {
     RarmModel& m = c->rarm; const rdm_rarm_cfg& g = m.cfg; const int C = m.C, L = g.sequence_length;
     RarmState st = rarm_state(m, B2);
+    const size_t step = (size_t)c->tap_step++;      // this step's place in a tap buffer: stage bytes * step
     return run_with_arena(c, m.arena, m.blob, [&](Ops& o) {
+        o.cur_block = TAP_RARM_STEP; o.cur_layer = 0;
+        auto tap = [&](int stage, const void* p, size_t width_bytes) { o.tap(stage, p, (size_t)B2 * width_bytes, false, step * B2 * width_bytes); };
         float* x = o.af32((size_t)B2 * C);
         bf16_t* ln = o.abf((size_t)B2 * C); bf16_t* qkv = o.abf((size_t)B2 * 3 * C); bf16_t* ao = o.abf((size_t)B2 * C);
         bf16_t* q2 = o.abf((size_t)B2 * C); bf16_t* ff = o.abf((size_t)B2 * 4 * C);
         // a decode step is one row per sequence throughout: every projection of the step is B2 single_row rows
         auto lin = [&](LinearOp op) { op.M = B2; op.single_row = true; o.linear(op); };
         // a projection of LayerNorm(x; g, b): formed inside the skinny GEMM where that takes the shape, else as a pass into `ln` of its own
-        auto ln_lin = [&](const float* g, const float* b, LinearOp op) {
+        // (ln_stage: the tap stage of the LayerNorm's rows, which exist only in the second form)
+        auto ln_lin = [&](const float* g, const float* b, LinearOp op, int ln_stage) {
             op.ln_x = x; op.ln_g = g; op.ln_b = b; op.C0 = C; op.M = B2; op.single_row = true;
             if (o.linear_ln(op)) return;
             o.layernorm({.x_f32 = x, .gamma = g, .beta = b, .M = B2, .C = C, .out_bf16 = ln});
+            tap(ln_stage, ln, (size_t)C * 2);
             op.A0 = ln;
             o.linear(op);
         };
         if (!o.plan) o.check(launch_rarm_embed(st.tokens, o.w<float>(m.emb), o.w<float>(m.pos), st.pos, x, B2, C, g.vocab_in, c->stream), "rarm embed");
+        tap(1, x, (size_t)C * 4);
         const float scale = 1.0f / sqrtf((float)g.d_head);
         const bool ln3_fused = m.xa_B > 0 && m.xa_k == k;      // the fused cross-attention kernel also emits norm3 of its output rows
         for (int l = 0; l < g.depth; l++) {
             const RarmBlk& b = m.blk[l];
-            ln_lin(o.w<float>(b.ln1g), o.w<float>(b.ln1b), {.W = o.w<bf16_t>(b.wqkv), .N = 3 * C, .out_bf16 = qkv});
+            o.cur_layer = l + 1;
+            ln_lin(o.w<float>(b.ln1g), o.w<float>(b.ln1b), {.W = o.w<bf16_t>(b.wqkv), .N = 3 * C, .out_bf16 = qkv}, 1);
+            tap(2, qkv, (size_t)3 * C * 2);
             if (!o.plan) {
                 RarmAttnParams p{}; p.q = qkv; p.ldq = 3 * C; p.k_new = qkv + C; p.v_new = qkv + 2 * C;
                 p.Kc = (bf16_t*)m.cache + ((size_t)l * 2) * B2 * L * C; p.Vc = (bf16_t*)m.cache + ((size_t)l * 2 + 1) * B2 * L * C;
@@ -99,7 +117,9 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
                 o.check(launch_rarm_decode_attention(p, g.n_heads, B2, c->stream), "rarm self attention");
                 o.prof_end();
             }
+            tap(3, ao, (size_t)C * 2);
             lin({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo1), .bias = o.w<float>(b.bo1), .N = C, .res_f32 = x, .out_f32 = x});
+            tap(4, x, (size_t)C * 4);
             if (m.xa_B > 0 && m.xa_k == k) {      // norm2 + to_q + attention over the neighbours + to_out + residual in one launch
                 if (!o.plan) {
                     RarmXattnParams xp{}; xp.x = x; xp.ln_g = o.w<float>(b.ln2g); xp.ln_b = o.w<float>(b.ln2b); xp.ln_eps = 1e-5f;
@@ -109,23 +129,32 @@ static int rarm_step(rdm_ctx* c, int B2, int k, int pos_hint = -1 /* host's copy
                     o.check(launch_rarm_xattn_decode(xp, c->stream), "rarm fused cross attention");
                 }
             } else {
-            ln_lin(o.w<float>(b.ln2g), o.w<float>(b.ln2b), {.W = o.w<bf16_t>(b.wq2), .N = C, .out_bf16 = q2});
+            ln_lin(o.w<float>(b.ln2g), o.w<float>(b.ln2b), {.W = o.w<bf16_t>(b.wq2), .N = C, .out_bf16 = q2}, 5);
+            tap(6, q2, (size_t)C * 2);
             if (!o.plan) {
                 RarmAttnParams p{}; p.q = q2; p.ldq = C; p.Kc = (bf16_t*)m.ctxkv + (size_t)l * 2 * C; p.Vc = (bf16_t*)m.ctxkv + (size_t)l * 2 * C + C;
                 p.batch_stride = (long long)k * m.kv_total; p.row_stride = m.kv_total; p.nkv = k; p.scale = scale; p.out = ao; p.ldo = C;
                 o.check(launch_rarm_decode_attention(p, g.n_heads, B2, c->stream), "rarm cross attention");
             }
+            tap(7, ao, (size_t)C * 2);
             lin({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo2), .bias = o.w<float>(b.bo2), .N = C, .res_f32 = x, .out_f32 = x});
             }
+            tap(8, x, (size_t)C * 4);
+            if (ln3_fused) tap(9, ln, (size_t)C * 2);
             const LinearOp geglu{.W = o.w<bf16_t>(b.wff1), .bias = o.w<float>(b.bff1), .N = 8 * C, .act = ACT_GEGLU, .out_bf16 = ff};
             if (ln3_fused) {      // norm3 left the cross-attention kernel with the finished rows: a plain GEGLU GEMM on the bf16 operand
                 LinearOp op = geglu; op.A0 = ln; op.C0 = C;
                 lin(op);
-            } else ln_lin(o.w<float>(b.ln3g), o.w<float>(b.ln3b), geglu);
+            } else ln_lin(o.w<float>(b.ln3g), o.w<float>(b.ln3b), geglu, 9);
+            tap(10, ff, (size_t)4 * C * 2);
             lin({.A0 = ff, .C0 = 4 * C, .W = o.w<bf16_t>(b.wff2), .bias = o.w<float>(b.bff2), .N = C, .res_f32 = x, .out_f32 = x});
+            tap(11, x, (size_t)C * 4);
         }
+        o.cur_layer = 0;
         if (!o.plan) o.check(launch_cast_f32_bf16(x, ln, (long long)B2 * C, c->stream), "cast x");
+        tap(2, ln, (size_t)C * 2);
         lin({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(m.wpo), .bias = o.w<float>(m.bpo), .N = g.vocab_out, .out_f32 = st.logits});
+        tap(3, st.logits, (size_t)g.vocab_out * 4);
     });
 }
 static int rarm_check(rdm_ctx* c, int b, int k, int positions) {
@@ -166,34 +195,56 @@ static int rarm_seq_body(rdm_ctx* c, const int64_t* tokens, int tok_ld, int tok_
         bf16_t* q2 = o.abf(Mmax * C); bf16_t* ff = o.abf(Mmax * 4 * C);
         float* lg = nll_out ? o.af32((size_t)(Mmax < (size_t)RARM_NLL_ROWS ? Mmax : (size_t)RARM_NLL_ROWS) * V) : nullptr;
         if (o.plan) return;
+        o.cur_block = TAP_RARM_SEQ;
         const float scale = 1.0f / sqrtf((float)g.d_head);
         for (int s0 = 0; s0 < B2 && o.rc == 0; s0 += per) {
             const int nb = B2 - s0 < per ? B2 - s0 : per, M = nb * t;
+            // a range shows its rows at its own row offset of the [B2 * t, width] stage
+            auto tap = [&](int stage, const void* p, size_t width_bytes) { o.tap(stage, p, (size_t)M * width_bytes, false, (size_t)s0 * t * width_bytes); };
+            o.cur_layer = 0;
             o.check(launch_rarm_embed_seq((const long long*)tokens, tok_ld, tok_rows, s0, o.w<float>(m.emb), o.w<float>(m.pos), x, M, t, C, g.vocab_in, c->stream),
                     "rarm embed");
+            tap(1, x, (size_t)C * 4);
             for (int l = 0; l < g.depth; l++) {
                 const RarmBlk& b = m.blk[l];
+                o.cur_layer = l + 1;
                 o.layernorm({.x_f32 = x, .gamma = o.w<float>(b.ln1g), .beta = o.w<float>(b.ln1b), .M = M, .C = C, .out_bf16 = ln});
+                tap(1, ln, (size_t)C * 2);
                 o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(b.wqkv), .M = M, .N = 3 * C, .out_bf16 = qkv});
+                tap(2, qkv, (size_t)3 * C * 2);
                 bf16_t* kc = fill_cache ? (bf16_t*)m.cache + (((size_t)l * 2) * B2 + s0) * L * C : nullptr;
                 bf16_t* vc = fill_cache ? (bf16_t*)m.cache + (((size_t)l * 2 + 1) * B2 + s0) * L * C : nullptr;
                 o.tag = "rarm.causal_attention";
                 o.causal_d64({.qkv = qkv, .ldq = 3 * C, .out = ao, .ldo = C, .n = t, .kcache = kc, .vcache = vc, .L = L}, g.n_heads, nb, scale);
+                tap(3, ao, (size_t)C * 2);
                 o.linear({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo1), .bias = o.w<float>(b.bo1), .M = M, .N = C, .res_f32 = x, .out_f32 = x});
+                tap(4, x, (size_t)C * 4);
                 o.layernorm({.x_f32 = x, .gamma = o.w<float>(b.ln2g), .beta = o.w<float>(b.ln2b), .M = M, .C = C, .out_bf16 = ln});
+                tap(5, ln, (size_t)C * 2);
                 o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(b.wq2), .M = M, .N = C, .out_bf16 = q2});
+                tap(6, q2, (size_t)C * 2);
                 const bf16_t* kv = (const bf16_t*)m.ctxkv + (size_t)s0 * k * m.kv_total + (size_t)l * 2 * C;
                 o.small_attention({.q = q2, .ldq = C, .k = kv, .ldk = m.kv_total, .v = kv + C, .ldv = m.kv_total, .out = ao, .ldo = C, .nq = t, .nkv = k, .scale = scale},
                                   g.d_head, g.n_heads, nb, "rarm cross attention");
+                tap(7, ao, (size_t)C * 2);
                 o.linear({.A0 = ao, .C0 = C, .W = o.w<bf16_t>(b.wo2), .bias = o.w<float>(b.bo2), .M = M, .N = C, .res_f32 = x, .out_f32 = x});
+                tap(8, x, (size_t)C * 4);
                 o.layernorm({.x_f32 = x, .gamma = o.w<float>(b.ln3g), .beta = o.w<float>(b.ln3b), .M = M, .C = C, .out_bf16 = ln});
+                tap(9, ln, (size_t)C * 2);
                 o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(b.wff1), .bias = o.w<float>(b.bff1), .M = M, .N = 8 * C, .act = ACT_GEGLU, .out_bf16 = ff});
+                tap(10, ff, (size_t)4 * C * 2);
                 o.linear({.A0 = ff, .C0 = 4 * C, .W = o.w<bf16_t>(b.wff2), .bias = o.w<float>(b.bff2), .M = M, .N = C, .res_f32 = x, .out_f32 = x});
+                tap(11, x, (size_t)C * 4);
             }
             if (!logits_out && !nll_out) continue;
+            o.cur_layer = 0;
             o.check(launch_cast_f32_bf16(x, ln, (long long)M * C, c->stream), "cast x");
+            tap(2, ln, (size_t)C * 2);
             const size_t row0 = (size_t)s0 * t;
-            if (logits_out) o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(m.wpo), .bias = o.w<float>(m.bpo), .M = M, .N = V, .out_f32 = logits_out + row0 * V});
+            if (logits_out) {
+                o.linear({.A0 = ln, .C0 = C, .W = o.w<bf16_t>(m.wpo), .bias = o.w<float>(m.bpo), .M = M, .N = V, .out_f32 = logits_out + row0 * V});
+                tap(3, logits_out + row0 * V, (size_t)V * 4);
+            }
             if (nll_out) {
                 for (int r0 = 0; r0 < M && o.rc == 0; r0 += RARM_NLL_ROWS) {
                     const int nr = M - r0 < RARM_NLL_ROWS ? M - r0 : RARM_NLL_ROWS;
