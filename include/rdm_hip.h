@@ -176,22 +176,62 @@ int rdm_unet_forward(rdm_ctx* ctx, const float* x, const int64_t* t, const float
  *   to_out.bias shortcut when its neighbours are all zero, and attends its caller-given neighbours unbiased otherwise).
  * bias_host: HOST fp32 [rows][k]; the library validates it and keeps a device copy, in force until cleared (bias_host NULL; rows and k are
  * then ignored) or replaced.  Honoured by rdm_unet_forward (rows == b) and by rdm_unet_forward_guided and every sampler entry (DDIM, PLMS,
- * DPM-Solver++, UniPC, DDPM, their seeded forms, the SDE solver, rdm_ddim_decode / _encode / _inpaint; rows == batch), in deterministic
+ * DPM-Solver++, UniPC, DDPM, seeded or not, the SDE solver, rdm_ddim_decode / _encode / _inpaint; rows == batch), in deterministic
  * mode too.  A bias whose (rows, k) does not match such a call makes the call fail with -1 and a message: it is never silently
  * ignored.  The RARM, CLIP, first-stage and training entries do not read it.
  * rdm_get_neighbour_bias: 1 = a bias is set (*rows, *k filled), 0 = none (*rows = *k = 0); either pointer may be NULL. */
 int rdm_set_neighbour_bias(rdm_ctx* ctx, const float* bias_host, int rows, int k);
 int rdm_get_neighbour_bias(rdm_ctx* ctx, int* rows, int* k);
 
+/* ---- device noise ------------------------------------------------------------------------------
+ * The library's own definition of "sample i of seed s": Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key
+ * increments 0x9E3779B9 / 0xBB67AE85, ten rounds) with
+ *     key        = (seed low 32 bits, seed high 32 bits)
+ *     counter[0] = block   = (element index WITHIN the sample row) >> 2
+ *     counter[1] = step    = draw index: the loop step counted from 0 in loop order (the i-th step taken)
+ *     counter[2] = row     = GLOBAL sample index, row0 + b
+ *     counter[3] = stream  = 0: the forward process's noise | 1: per-step update noise | >= 2: reserved, refused by the entries
+ * Stream 0 is the noise of the forward process q(x_t | x_0): step 0 the starting latent x_T (and rdm_op_q_sample_seeded's noise), step i + 1
+ * the noise the inpainting loop gives the known region at loop step i (a seeded rdm_ddim_inpaint).
+ * Element e of a row takes output word e & 3 of block e >> 2: rows never share a block, and a value depends on (seed, stream, step, row, e)
+ * only -- not on the batch size, on how row0 splits a batch, on the grid or on the vector width.  Normals are Box-Muller on the word pairs
+ * (w0, w1) and (w2, w3): u = ((w >> 9) + 0.5) 2^-23 (exact in fp32, strictly inside (0, 1), so |z| <= 5.77), r = sqrtf(-2 logf(u1)),
+ * sincospif(2 u2, &s, &c); element 2h = r c, element 2h + 1 = r s of pair h.  row0 + B must fit 32 bits and per_row must be at most 2^34.
+ *
+ * rdm_rng_words: host code only (ctx-free): the four words of one block, out[4] [host].  Returns 0, -1 for a null out.
+ * rdm_op_rng_words / rdm_op_randn: the word / the normal each element of B rows of per_row elements would consume at (step, stream), rows
+ * row0 .. row0 + B - 1; out [dev] [B, per_row] (uint32 / f32).  Any per_row >= 1 (a row's last block may be partial); an out that is not
+ * 16-byte aligned, or a per_row that is no multiple of 4, takes scalar stores.
+ *
+ * rdm_noise: where a sampler loop or a step op takes its noise from -- the one `noise` argument of every entry that consumes some.  A NULL
+ * pointer, or seeded == 0 with a NULL stack, is no noise source, and each entry says what it then does.  seeded != 0: loop step i applies
+ * the normals of (seed, stream 1, step i, row0 + b), generated in registers in the pass that applies them -- bit for bit the stack form fed
+ * with rdm_op_randn(seed, row0, B, per_row, step = i, stream = 1).  A seeded call has no scalar form: C*H*W (the ops: per_row, which must
+ * divide n) must be a multiple of 4, every operand 16-byte aligned, and rows [row0, row0 + B) must pass the row check above (-1 with a
+ * message otherwise).  A seeded loop that takes x_T may be given a NULL one: the start is then the normals of (seed, stream 0, step 0).
+ * seeded != 0 together with a stack is refused (-1, "give a seed or a stack, not both"); the context stays usable. */
+typedef struct rdm_noise {
+    const float* stack;    /* [dev] caller's noise tensor, or NULL */
+    int          seeded;   /* != 0: the library's generator under (seed, row0); stack must be NULL */
+    uint64_t     seed;
+    int64_t      row0;
+    int64_t      per_row;  /* read by the rdm_op_* entries only (the loops derive it from args) */
+    uint32_t     step;     /* read by the rdm_op_* entries only (the loops count it) */
+} rdm_noise;
+int rdm_rng_words(uint64_t seed, uint32_t row, uint32_t step, uint32_t stream, uint32_t block, uint32_t* out);
+int rdm_op_rng_words(rdm_ctx* ctx, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, uint32_t* out);
+int rdm_op_randn(rdm_ctx* ctx, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, float* out);
+
 /* ---- samplers -------------------------------------------------------------------------------
  * DDIMSampler.sample / ddim_sampling / p_sample_ddim (rdm/models/diffusion/ddim.py:58-268).
  * x_T [dev] f32 [B,C,H,W]; cond, uncond [dev] f32 [B,k,ctx_dim] (uncond may be NULL when scale == 1);
- * noise [dev] f32 [S,B,C,H,W] or NULL (required when eta > 0; consumed in loop order);
+ * noise (rdm_noise above): the stack is [dev] f32 [S,B,C,H,W], consumed in loop order; a source is required when eta > 0, and with eta == 0
+ * no step noise is drawn from either kind.  x_T may be NULL only when seeded;
  * z_out [dev] f32 [B,C,H,W]; x_inter / pred_x0_inter [dev] f32 [n_inter,B,C,H,W] or NULL, filled for the
  * steps ddim.py:207 logs (n_inter = rdm_ddim_num_intermediates). */
 int rdm_ddim_num_intermediates(int S, int log_every_t);
 int rdm_ddim_sample(rdm_ctx* ctx, const rdm_ddim_args* args, const float* x_T, const float* cond, const float* uncond,
-                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter);
+                    const rdm_noise* noise, float* z_out, float* x_inter, float* pred_x0_inter);
 /* ldm PLMSSampler.sample / plms_sampling / p_sample_plms (ldm/models/diffusion/plms.py): pseudo linear multistep sampling on DDIM's
  * schedule with eta = 0 (args->eta != 0 is an error, as make_schedule's ValueError; temperature has no effect there).  The first step is
  * the pseudo improved Euler step (two forwards), later steps combine the guided eps with up to three earlier ones: S' + 1 forwards for
@@ -236,41 +276,11 @@ int rdm_unipc_sample(rdm_ctx* ctx, const rdm_unipc_args* args, const float* x_T,
 int rdm_unipc_coefficients(const float* alphas_cumprod, int T, const int* nodes, int n_nodes, int j, int order, int variant, int corrector,
                            int lower_order_final, double* out);
 /* ldm LatentDiffusion.p_sample_loop / p_sample (no CFG on this path).
- * noise [dev] f32 [timesteps,B,C,H,W], consumed in loop order. */
-int rdm_ddpm_sample(rdm_ctx* ctx, const rdm_ddpm_args* args, const float* x_T, const float* cond, const float* noise,
+ * noise (rdm_noise, required): the stack is [dev] f32 [timesteps,B,C,H,W], consumed in loop order; the final step consumes none from
+ * either kind.  x_T may be NULL only when seeded. */
+int rdm_ddpm_sample(rdm_ctx* ctx, const rdm_ddpm_args* args, const float* x_T, const float* cond, const rdm_noise* noise,
                     float* z_out);
 
-/* ---- device noise ------------------------------------------------------------------------------
- * The library's own definition of "sample i of seed s": Philox4x32-10 (Salmon et al., SC'11; multipliers 0xD2511F53 / 0xCD9E8D57, key
- * increments 0x9E3779B9 / 0xBB67AE85, ten rounds) with
- *     key        = (seed low 32 bits, seed high 32 bits)
- *     counter[0] = block   = (element index WITHIN the sample row) >> 2
- *     counter[1] = step    = draw index: the loop step counted from 0 in loop order (the i-th step taken)
- *     counter[2] = row     = GLOBAL sample index, row0 + b
- *     counter[3] = stream  = 0: the forward process's noise | 1: per-step update noise | >= 2: reserved, refused by the entries
- * Stream 0 is the noise of the forward process q(x_t | x_0): step 0 the starting latent x_T (and rdm_op_q_sample_seeded's noise), step i + 1
- * the noise the inpainting loop gives the known region at loop step i (rdm_ddim_inpaint_seeded).
- * Element e of a row takes output word e & 3 of block e >> 2: rows never share a block, and a value depends on (seed, stream, step, row, e)
- * only -- not on the batch size, on how row0 splits a batch, on the grid or on the vector width.  Normals are Box-Muller on the word pairs
- * (w0, w1) and (w2, w3): u = ((w >> 9) + 0.5) 2^-23 (exact in fp32, strictly inside (0, 1), so |z| <= 5.77), r = sqrtf(-2 logf(u1)),
- * sincospif(2 u2, &s, &c); element 2h = r c, element 2h + 1 = r s of pair h.  row0 + B must fit 32 bits and per_row must be at most 2^34.
- *
- * rdm_rng_words: host code only (ctx-free): the four words of one block, out[4] [host].  Returns 0, -1 for a null out.
- * rdm_op_rng_words / rdm_op_randn: the word / the normal each element of B rows of per_row elements would consume at (step, stream), rows
- * row0 .. row0 + B - 1; out [dev] [B, per_row] (uint32 / f32).  Any per_row >= 1 (a row's last block may be partial); an out that is not
- * 16-byte aligned, or a per_row that is no multiple of 4, takes scalar stores. */
-int rdm_rng_words(uint64_t seed, uint32_t row, uint32_t step, uint32_t stream, uint32_t block, uint32_t* out);
-int rdm_op_rng_words(rdm_ctx* ctx, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, uint32_t* out);
-int rdm_op_randn(rdm_ctx* ctx, uint64_t seed, int64_t row0, int64_t B, int64_t per_row, uint32_t step, uint32_t stream, float* out);
-/* rdm_ddim_sample / rdm_ddpm_sample without a noise stack: loop step i applies the normals of (seed, stream 1, step i, row0 + b), generated
- * in registers in the pass that applies them -- bit for bit the loop fed with a stack of rdm_op_randn(step = i) outputs.  x_T may be NULL:
- * the start is then the normals of (seed, stream 0, step 0).  With eta == 0 the DDIM entry draws no step noise and equals rdm_ddim_sample;
- * the final DDPM step consumes none, as in rdm_ddpm_sample.  channels * height * width must be a multiple of 4.  Other arguments as the
- * stack entries. */
-int rdm_ddim_sample_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
-                           const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter);
-int rdm_ddpm_sample_seeded(rdm_ctx* ctx, const rdm_ddpm_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
-                           float* z_out);
 /* SDE-DPM-Solver++(2M): the "sde-dpmsolver++" multistep update of Lu et al.'s reference implementation, a stochastic sampler at
  * DPM-Solver++'s step counts, on rdm_dpmpp_sample's arguments, node quantities and order rule.  Step j from s = nodes[j] to t = nodes[j+1],
  * h = lambda_t - lambda_s, m_j = (x - sigma_s eps) / alpha_s with the guided eps:
@@ -278,16 +288,10 @@ int rdm_ddpm_sample_seeded(rdm_ctx* ctx, const rdm_ddpm_args* args, uint64_t see
  *     x  <- (sigma_t / sigma_s) exp(-h) x + g m_j  [+ (g / (2r)) (m_j - m_{j-1}), r = h_{j-1} / h, on a second-order step]
  *           + sigma_t sqrt(1 - exp(-2h)) z_j,   z_j ~ N(0, I)
  * The host flattens this in float64 to x <- c_x x + c_0 m_j + c_1 m_{j-1} + c_n z_j; the kernel sums left to right in fp32.  The noise is
- * not scaled by an eta.  rdm_dpmpp_sde_sample: z_j = noise[j], noise [dev] f32 [n_nodes - 1, B, C, H, W] (required).
- * rdm_dpmpp_sde_sample_seeded: z_j is drawn in the step kernel from the device-noise counters above -- stream 1, step = the loop step j,
- * row = row0 + b, block = (element within the row) >> 2 -- and the loop is bit-identical to the stack loop fed with
- * rdm_op_randn(seed, row0, B, per_row, step = j, stream = 1) for j = 0 .. n_nodes - 2.  x_T may be NULL there: the start is then the normals
- * of (seed, stream 0, step 0), as rdm_ddim_sample_seeded; channels * height * width must be a multiple of 4.  pred_x0_inter holds m_j;
- * intermediates and other arguments as rdm_dpmpp_sample. */
+ * not scaled by an eta.  noise (rdm_noise, required): z_j = stack[j], [dev] f32 [n_nodes - 1, B, C, H, W], or drawn at step j when seeded;
+ * x_T may be NULL only when seeded.  pred_x0_inter holds m_j; intermediates and other arguments as rdm_dpmpp_sample. */
 int rdm_dpmpp_sde_sample(rdm_ctx* ctx, const rdm_dpmpp_args* args, const float* x_T, const float* cond, const float* uncond,
-                         const float* noise, float* z_out, float* x_inter, float* pred_x0_inter);
-int rdm_dpmpp_sde_sample_seeded(rdm_ctx* ctx, const rdm_dpmpp_args* args, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
-                                const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter);
+                         const rdm_noise* noise, float* z_out, float* x_inter, float* pred_x0_inter);
 
 /* ---- image-to-image on the DDIM schedule (ldm DDIMSampler.stochastic_encode / encode / decode; the reference's vendored ddim.py stops
  * before them) ------------------------------------------------------------------------------------
@@ -297,9 +301,8 @@ int rdm_dpmpp_sde_sample_seeded(rdm_ctx* ctx, const rdm_dpmpp_args* args, uint64
  * rdm_ddim_decode: x_latent [dev] f32 [B,C,H,W] is taken to be at level index t_start - 1; the DDIM step runs at indices
  * t_start - 1 ... 0 -- t_start forwards -- with the step arithmetic, CFG batch doubling, eta, temperature and intermediates rule of
  * rdm_ddim_sample over t_start steps (n_inter = rdm_ddim_num_intermediates(t_start, log_every_t)).  1 <= t_start <= total;
- * t_start == total is rdm_ddim_sample, bit for bit.  noise [dev] f32 [t_start,B,C,H,W] or NULL (required when eta > 0; consumed in
- * loop order).  rdm_ddim_decode_seeded: step i of THIS call (counted from 0) applies the normals of (seed, stream 1, step i, row0 + b),
- * as rdm_ddim_sample_seeded; x_latent is required.
+ * t_start == total is rdm_ddim_sample, bit for bit.  noise as rdm_ddim_sample's, the stack [dev] f32 [t_start,B,C,H,W]; seeded, step i of
+ * THIS call (counted from 0) draws at step i.  x_latent is required either way.
  *
  * rdm_ddim_encode: deterministic DDIM inversion, t_enc steps up the schedule (1 <= t_enc <= total).  Step i = 0 .. t_enc - 1 moves the
  * iterate from level a_prev[i] to level a_t[i]:
@@ -314,9 +317,7 @@ int rdm_dpmpp_sde_sample_seeded(rdm_ctx* ctx, const rdm_dpmpp_args* args, uint64
  * All three return -1 with a message, and leave the context usable, for a t_start / t_enc outside [1, total], a null pointer, a missing
  * uncond at scale > 1, and eta != 0 on encode. */
 int rdm_ddim_decode(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, const float* x_latent, const float* cond, const float* uncond,
-                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter);
-int rdm_ddim_decode_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, uint64_t seed, int64_t row0, const float* x_latent,
-                           const float* cond, const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter);
+                    const rdm_noise* noise, float* z_out, float* x_inter, float* pred_x0_inter);
 int rdm_ddim_encode(rdm_ctx* ctx, const rdm_ddim_args* args, int t_enc, const float* x0, const float* cond, const float* uncond,
                     float* z_out, float* x_inter);
 /* The inversion step kernel alone on caller-owned [dev] f32 buffers of n elements (eps: 2n under cfg, [cond | uncond]): pred_x0 =
@@ -337,37 +338,30 @@ int rdm_op_q_sample_seeded(rdm_ctx* ctx, const float* x0, int64_t B, int64_t per
  * [B,C,H,W] is the known latent; mask [dev] f32 [B,mask_channels,H,W] holds m in [0, 1], 1 = KEEP THE KNOWN LATENT (ldm's convention),
  * with mask_channels = 1 (one plane for every channel) or C.
  *
- * rdm_op_masked_blend: the kernel alone on caller-owned buffers; z [dev] f32 [B,C,H,W] or NULL (zeros: the last blend of a
- * keep-the-known-region call, at sqrt_a = 1, sqrt_1ma = 0).  out may be x; x_dup (or NULL) receives the same values.  float4 accesses
- * when B*C*H*W % 4 == 0, H*W % 4 == 0 and every operand is 16-byte aligned, else scalar ones.
- * rdm_op_masked_blend_seeded: z is drawn in registers from the device-noise counters -- stream 0, the given step, row = row0 + b,
- * block = (element within the row) >> 2 -- and the result is bit-identical to rdm_op_masked_blend fed with
+ * rdm_op_masked_blend: the kernel alone on caller-owned buffers; z (rdm_noise): the stack is [dev] f32 [B,C,H,W]; no noise source reads z
+ * as zeros (the last blend of a keep-the-known-region call, at sqrt_a = 1, sqrt_1ma = 0).  out may be x; x_dup (or NULL) receives the same
+ * values.  float4 accesses when B*C*H*W % 4 == 0, H*W % 4 == 0 and every operand is 16-byte aligned, else scalar ones.
+ * Seeded, z is drawn on STREAM 0 at z->step (per_row is C*H*W, the field is not read) -- bit-identical to the stack form fed with
  * rdm_op_randn(seed, row0, B, C*H*W, step, stream = 0).  The loops use step = i + 1 for loop step i (step 0 is the starting latent).
- * C*H*W % 4 == 0 and 16-byte aligned x, x0, out, x_dup are required (-1 otherwise); the mask may have any alignment, and when
+ * C*H*W % 4 == 0 and 16-byte aligned x, x0, out, x_dup are then required (-1 otherwise); the mask may have any alignment, and when
  * H*W % 4 != 0 -- a block then straddles channel planes -- it is indexed per element.
  *
  * rdm_ddim_inpaint: rdm_ddim_decode's loop (same arguments, scalars, intermediates) with the blend before every forward: loop step
  * i = 0 .. t_start - 1 works at level index = t_start - 1 - i and first replaces the iterate by the blend at that level,
  * sqrt_a = sqrt(a_t[index]), sqrt_1ma = sqrt(1 - a_t[index]) in float64 from the fp32 alpha, rounded, z = q_noise[i]; then the UNet
  * forward, then rdm_ddim_decode's step.  The result of the last step is not blended, as in ldm's loop.  q_noise [dev] f32
- * [t_start,B,C,H,W], required, consumed in loop order; noise as rdm_ddim_decode's.  rdm_ddim_inpaint_seeded takes neither stack: the
- * update noise of loop step i is (seed, stream 1, step i) as rdm_ddim_decode_seeded's, the known region's (seed, stream 0, step i + 1),
- * both for rows row0 + b, and the loop is bit-identical to the stack loop fed with rdm_op_randn's outputs.  It needs
+ * [t_start,B,C,H,W], consumed in loop order: required unless noise is seeded, and then it must be NULL; noise as rdm_ddim_decode's.  A
+ * seeded call takes neither stack: the update noise of loop step i is (seed, stream 1, step i), the known region's (seed, stream 0,
+ * step i + 1), both for rows row0 + b, and the loop is bit-identical to the stack loop fed with rdm_op_randn's outputs.  It needs
  * channels * height * width % 4 == 0 and a 16-byte aligned x0.
  *
- * All four return -1 with a message, and leave the context usable, for a null x, x0, mask (or q_noise in the stack loop), a
- * mask_channels that is neither 1 nor C, a t_start outside [1, total], and what rdm_ddim_decode / its seeded form refuse. */
-int rdm_op_masked_blend(rdm_ctx* ctx, const float* x, const float* x0, const float* mask, const float* z_or_null, int64_t B, int C, int H,
+ * Both return -1 with a message, and leave the context usable, for a null x, x0, mask (or q_noise in the stack loop), a q_noise beside a
+ * seed, a mask_channels that is neither 1 nor C, a t_start outside [1, total], and what rdm_ddim_decode refuses. */
+int rdm_op_masked_blend(rdm_ctx* ctx, const float* x, const float* x0, const float* mask, const rdm_noise* z, int64_t B, int C, int H,
                         int W, int mask_channels, float sqrt_a, float sqrt_1ma, float* out, float* x_dup_or_null);
-int rdm_op_masked_blend_seeded(rdm_ctx* ctx, const float* x, const float* x0, const float* mask, int64_t B, int C, int H, int W,
-                               int mask_channels, float sqrt_a, float sqrt_1ma, uint64_t seed, int64_t row0, uint32_t step, float* out,
-                               float* x_dup_or_null);
 int rdm_ddim_inpaint(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, const float* x_latent, const float* x0, const float* mask,
-                     int mask_channels, const float* cond, const float* uncond, const float* noise, const float* q_noise, float* z_out,
+                     int mask_channels, const float* cond, const float* uncond, const rdm_noise* noise, const float* q_noise, float* z_out,
                      float* x_inter, float* pred_x0_inter);
-int rdm_ddim_inpaint_seeded(rdm_ctx* ctx, const rdm_ddim_args* args, int t_start, uint64_t seed, int64_t row0, const float* x_latent,
-                            const float* x0, const float* mask, int mask_channels, const float* cond, const float* uncond, float* z_out,
-                            float* x_inter, float* pred_x0_inter);
 /* One guided UNet forward exactly as the sampling loops run it (rdm_unet_forward on [x | x], [cond | uncond] computes the same function
  * through other kernel configurations: every sample's own prefix, no zero-context shortcut, the time embedding per row): x [dev] f32
  * [B,Cin,H,W] at the one timestep t; cond, uncond [dev] f32 [B,k,ctx_dim]; eps_out [dev] f32 [2B,Cout,H,W], rows cond | uncond.  What a
@@ -754,17 +748,12 @@ int rdm_op_add(rdm_ctx* ctx, const void* a_bf16, const void* b_bf16, void* out_b
 /* One DDIM update, the kernel of rdm_ddim_sample alone on caller-owned [dev] f32 buffers of n elements (eps: 2n under cfg, [cond | uncond]),
  * with the kernel's own scalars -- the caller owns the schedule: e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i]) : eps[i];
  * pred_x0 = (x - sqrt_one_minus_at e) / sqrtf(a_t); x_prev = sqrtf(a_prev) pred_x0 + sqrtf(1 - a_prev - sigma_t^2) e
- * + sigma_t noise temperature (no noise operand: the last term is absent, whatever sigma_t); x_dup <- x_prev.  x_prev may be x.
- * rdm_op_ddim_step_seeded: the kernel of rdm_ddim_sample_seeded -- the noise of element i is the normal of (seed, stream 1, step,
- * row0 + i / per_row, i % per_row), drawn in registers: bit for bit rdm_op_ddim_step on rdm_op_randn(seed, row0, n / per_row, per_row, step,
- * stream 1).  It has no scalar form: per_row a multiple of 4 that divides n and 16-byte aligned operands are required (-1 otherwise), and
- * rows [row0, row0 + n / per_row) must pass the device-noise row check. */
-int rdm_op_ddim_step(rdm_ctx* ctx, const float* x, const float* eps, const float* noise_or_null, long long n, int cfg, float scale, float a_t,
+ * + sigma_t noise temperature (no noise source: the last term is absent, whatever sigma_t); x_dup <- x_prev.  x_prev may be x.
+ * noise (rdm_noise): the stack holds n elements; seeded, the noise of element i is the normal of (seed, stream 1, noise->step,
+ * row0 + i / per_row, i % per_row) with noise->per_row, and rows [row0, row0 + n / per_row) must pass the device-noise row check. */
+int rdm_op_ddim_step(rdm_ctx* ctx, const float* x, const float* eps, const rdm_noise* noise, long long n, int cfg, float scale, float a_t,
                      float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, float* x_prev, float* x_dup_or_null,
                      float* pred_x0_or_null);
-int rdm_op_ddim_step_seeded(rdm_ctx* ctx, const float* x, const float* eps, long long n, int64_t per_row, int cfg, float scale, float a_t,
-                            float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, uint64_t seed, int64_t row0,
-                            uint32_t step, float* x_prev, float* x_dup_or_null, float* pred_x0_or_null);
 /* One PLMS update, the kernel of rdm_plms_sample alone (fp32, n elements, eta = 0): e_t = the guided eps as above.
  *   mode 0 (step):    e' = e_t | (3 e_t - h1) / 2 | (23 e_t - 16 h1 + 5 h2) / 12 | (55 e_t - 59 h1 + 37 h2 - 9 h3) / 24 at order 0 | 1 | 2 | 3;
  *                     e_store <- e_t (after the history reads: e_store may be h3)
@@ -778,13 +767,9 @@ int rdm_op_plms_step(rdm_ctx* ctx, const float* x, const float* eps, const float
                      float* pred_x0_or_null);
 /* One ancestral DDPM update, the kernel of rdm_ddpm_sample alone (fp32, n elements): x0 = sqrt_recip x - sqrt_recipm1 eps, clamped to
  * [-1, 1] when clip; x_prev = coef1 x0 + coef2 x + (nonzero ? expf(0.5 log_var) noise temperature : 0).  x_prev may be x.  nonzero == 0
- * ignores the noise operand; nonzero != 0 without one is refused (-1).  rdm_op_ddpm_step_seeded: the kernel of rdm_ddpm_sample_seeded, the
- * noise drawn as in rdm_op_ddim_step_seeded and under the same conditions. */
-int rdm_op_ddpm_step(rdm_ctx* ctx, const float* x, const float* eps, const float* noise_or_null, long long n, float sqrt_recip,
+ * ignores a noise stack; nonzero != 0 without a noise source is refused (-1).  noise as rdm_op_ddim_step's. */
+int rdm_op_ddpm_step(rdm_ctx* ctx, const float* x, const float* eps, const rdm_noise* noise, long long n, float sqrt_recip,
                      float sqrt_recipm1, float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, float* x_prev);
-int rdm_op_ddpm_step_seeded(rdm_ctx* ctx, const float* x, const float* eps, long long n, int64_t per_row, float sqrt_recip, float sqrt_recipm1,
-                            float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, uint64_t seed, int64_t row0,
-                            uint32_t step, float* x_prev);
 /* One DPM-Solver++ update, the kernel of rdm_dpmpp_sample alone (fp32, n elements): e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i])
  * : eps[i]; m0 = (x - sqrt_one_minus_a_s e) / sqrt_a_s; x_out = c_x x + c_0 m0 + c_1 m_prev (no m_prev: the last term is absent);
  * x_dup <- x_out, m_store <- m0, pred_x0 <- m0.  m_store may be m_prev itself. */
@@ -794,18 +779,10 @@ int rdm_op_dpmpp_step(rdm_ctx* ctx, const float* x, const float* eps, const floa
 /* One SDE-DPM-Solver++ update, the kernel of rdm_dpmpp_sde_sample alone (fp32, n elements): e and m0 as rdm_op_dpmpp_step;
  * x_out = ((c_x x + c_0 m0) + c_1 m_prev) + c_n z (no m_prev: the c_1 term is absent), with the formula's flattened coefficients
  * c_x = (sigma_t / sigma_s) exp(-h), c_0 + c_1 = alpha_t (1 - exp(-2h)), c_n = sigma_t sqrt(1 - exp(-2h)) -- the caller owns the schedule;
- * x_dup <- x_out, m_store <- m0, pred_x0 <- m0.  m_store may be m_prev itself.  z = noise[i] (required).
- * rdm_op_dpmpp_sde_step_seeded: the kernel of rdm_dpmpp_sde_sample_seeded -- z of element i is the normal of the device-noise counters
- * (seed, stream 1, step, row0 + i / per_row, block (i % per_row) >> 2), drawn in registers: bit-identical to rdm_op_dpmpp_sde_step fed with
- * rdm_op_randn(seed, row0, n / per_row, per_row, step, stream = 1).  It has no scalar form: per_row a multiple of 4 that divides n and
- * 16-byte aligned operands are required (-1 otherwise), and rows [row0, row0 + n / per_row) must pass the device-noise row check. */
-int rdm_op_dpmpp_sde_step(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, const float* noise, long long n, int cfg,
-                          float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out,
-                          float* x_dup_or_null, float* m_store_or_null, float* pred_x0_or_null);
-int rdm_op_dpmpp_sde_step_seeded(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, long long n, int64_t per_row,
-                                 int cfg, float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n,
-                                 uint64_t seed, int64_t row0, uint32_t step, float* x_out, float* x_dup_or_null, float* m_store_or_null,
-                                 float* pred_x0_or_null);
+ * x_dup <- x_out, m_store <- m0, pred_x0 <- m0.  m_store may be m_prev itself.  z: noise (rdm_noise, required), as rdm_op_ddim_step's. */
+int rdm_op_dpmpp_sde_step(rdm_ctx* ctx, const float* x, const float* eps, const float* m_prev_or_null, const rdm_noise* noise, long long n,
+                          int cfg, float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n,
+                          float* x_out, float* x_dup_or_null, float* m_store_or_null, float* pred_x0_or_null);
 /* One UniPC pass, the kernel of rdm_unipc_sample alone (fp32, n elements; coefficients [host]: the 13 doubles of rdm_unipc_coefficients,
  * rounded to fp32 here): e = cfg ? eps[n + i] + scale (eps[i] - eps[n + i]) : eps[i]; m = (u - sigma e) / alpha;
  * xc = order_c ? a_x xc_prev + a_t m + a_1 h1 (+ a_2 h2) (+ a_3 h3) : u; u_next = b_x xc + b_0 m (+ b_1 h1) (+ b_2 h2), terms up to the

@@ -100,6 +100,12 @@ class DdpmArgs(C.Structure):
                 ("posterior_log_variance_clipped", C.POINTER(C.c_float))]
 
 
+class Noise(C.Structure):
+    """rdm_noise: a caller's stack, or the library's generator under (seed, row0); per_row and step are the step ops'."""
+    _fields_ = [("stack", C.c_void_p), ("seeded", C.c_int), ("seed", C.c_uint64), ("row0", C.c_int64), ("per_row", C.c_int64),
+                ("step", C.c_uint32)]
+
+
 KNN_SCAN_PATHS = (None, "generic", "d512", "bulk")      # rdm_knn_form.path (RDM_KNN_SCAN_*)
 
 
@@ -139,32 +145,25 @@ SIGNATURES = {
     "rdm_vq_decode_indices": (C.c_int, [_P, _P, C.c_int, _P]),
     "rdm_unet_forward": (C.c_int, [_P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
     "rdm_ddim_num_intermediates": (C.c_int, [C.c_int, C.c_int]),
-    "rdm_ddim_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, _P, _P, _P, _P]),
+    "rdm_ddim_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, C.POINTER(Noise), _P, _P, _P]),
     "rdm_plms_sample": (C.c_int, [_P, C.POINTER(DdimArgs), _P, _P, _P, _P, _P, _P]),
     "rdm_dpmpp_sample": (C.c_int, [_P, C.POINTER(DpmppArgs), _P, _P, _P, _P, _P, _P]),
     "rdm_dpmpp_timesteps": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.c_int, C.c_int, C.POINTER(C.c_int)]),
     "rdm_unipc_sample": (C.c_int, [_P, C.POINTER(UnipcArgs), _P, _P, _P, _P, _P, _P]),
     "rdm_unipc_coefficients": (C.c_int, [C.POINTER(C.c_float), C.c_int, C.POINTER(C.c_int), C.c_int, C.c_int, C.c_int, C.c_int, C.c_int,
                                          C.c_int, C.POINTER(C.c_double)]),
-    "rdm_ddpm_sample": (C.c_int, [_P, C.POINTER(DdpmArgs), _P, _P, _P, _P]),
+    "rdm_ddpm_sample": (C.c_int, [_P, C.POINTER(DdpmArgs), _P, _P, C.POINTER(Noise), _P]),
     "rdm_rng_words": (C.c_int, [C.c_uint64, C.c_uint32, C.c_uint32, C.c_uint32, C.c_uint32, C.POINTER(C.c_uint32)]),
     "rdm_op_rng_words": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P]),
     "rdm_op_randn": (C.c_int, [_P, C.c_uint64, C.c_int64, C.c_int64, C.c_int64, C.c_uint32, C.c_uint32, _P]),
-    "rdm_ddim_sample_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
-    "rdm_ddpm_sample_seeded": (C.c_int, [_P, C.POINTER(DdpmArgs), C.c_uint64, C.c_int64, _P, _P, _P]),
-    "rdm_dpmpp_sde_sample": (C.c_int, [_P, C.POINTER(DpmppArgs), _P, _P, _P, _P, _P, _P, _P]),
-    "rdm_dpmpp_sde_sample_seeded": (C.c_int, [_P, C.POINTER(DpmppArgs), C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "rdm_dpmpp_sde_sample": (C.c_int, [_P, C.POINTER(DpmppArgs), _P, _P, _P, C.POINTER(Noise), _P, _P, _P]),
     "rdm_unet_forward_guided": (C.c_int, [_P, _P, C.c_int64, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, _P]),
-    "rdm_ddim_decode": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "rdm_ddim_decode_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, C.c_uint64, C.c_int64, _P, _P, _P, _P, _P, _P]),
+    "rdm_ddim_decode": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, C.POINTER(Noise), _P, _P, _P]),
     "rdm_ddim_encode": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, _P, _P]),
     "rdm_op_ddim_inverse_step": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, _P, _P, _P]),
     "rdm_op_q_sample_seeded": (C.c_int, [_P, _P, C.c_int64, C.c_int64, C.c_float, C.c_float, C.c_uint64, C.c_int64, _P]),
-    "rdm_op_masked_blend": (C.c_int, [_P, _P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
-    "rdm_op_masked_blend_seeded": (C.c_int, [_P, _P, _P, _P, C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, C.c_uint64,
-                                             C.c_int64, C.c_uint32, _P, _P]),
-    "rdm_ddim_inpaint": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P, _P, _P]),
-    "rdm_ddim_inpaint_seeded": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, C.c_uint64, C.c_int64, _P, _P, _P, C.c_int, _P, _P, _P, _P, _P]),
+    "rdm_op_masked_blend": (C.c_int, [_P, _P, _P, _P, C.POINTER(Noise), C.c_int64, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float, C.c_float, _P, _P]),
+    "rdm_ddim_inpaint": (C.c_int, [_P, C.POINTER(DdimArgs), C.c_int, _P, _P, _P, C.c_int, _P, _P, C.POINTER(Noise), _P, _P, _P, _P]),
     "rdm_vq_decode": (C.c_int, [_P, _P, C.c_int, C.c_int, _P, _P]),
     "rdm_release_scratch": (C.c_int, [_P]),
     "rdm_vq_quantize": (C.c_int, [_P, _P, C.c_int, _P, _P]),
@@ -245,21 +244,15 @@ SIGNATURES = {
     "rdm_op_add": (C.c_int, [_P, _P, _P, _P, C.c_longlong]),
     "rdm_op_dpmpp_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
                                     _P, _P, _P, _P]),
-    "rdm_op_dpmpp_sde_step": (C.c_int, [_P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                        C.c_float, C.c_float, _P, _P, _P, _P]),
-    "rdm_op_dpmpp_sde_step_seeded": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
-                                               C.c_float, C.c_float, C.c_float, C.c_uint64, C.c_int64, C.c_uint32, _P, _P, _P, _P]),
+    "rdm_op_dpmpp_sde_step": (C.c_int, [_P, _P, _P, _P, C.POINTER(Noise), C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float,
+                                        C.c_float, C.c_float, C.c_float, _P, _P, _P, _P]),
     "rdm_op_unipc_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.POINTER(C.c_double), _P, _P, _P, _P, _P]),
-    "rdm_op_ddim_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                   _P, _P, _P]),
-    "rdm_op_ddim_step_seeded": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int64, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
-                                          C.c_float, C.c_uint64, C.c_int64, C.c_uint32, _P, _P, _P]),
+    "rdm_op_ddim_step": (C.c_int, [_P, _P, _P, C.POINTER(Noise), C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float,
+                                   C.c_float, _P, _P, _P]),
     "rdm_op_plms_step": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_longlong, C.c_int, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
                                    C.c_int, _P, _P, _P, _P]),
-    "rdm_op_ddpm_step": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int, C.c_int,
-                                   C.c_float, _P]),
-    "rdm_op_ddpm_step_seeded": (C.c_int, [_P, _P, _P, C.c_longlong, C.c_int64, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
-                                          C.c_int, C.c_float, C.c_uint64, C.c_int64, C.c_uint32, _P]),
+    "rdm_op_ddpm_step": (C.c_int, [_P, _P, _P, C.POINTER(Noise), C.c_longlong, C.c_float, C.c_float, C.c_float, C.c_float, C.c_float, C.c_int,
+                                   C.c_int, C.c_float, _P]),
     "rdm_op_geglu": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int]),
     "rdm_op_linear_ln": (C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int, C.c_int, C.c_int, C.c_int, C.c_float]),
     "rdm_op_linear_wgrad": (C.c_int, [_P, _P, _P, _P, C.c_longlong, C.c_int, C.c_int]),
@@ -588,15 +581,17 @@ def _noise_seed(what, seed, row0, B):
 
 
 def _noise_source(ctx, what, x_T, cond, noise, seed, row0, shape=None):
-    """Where a sampling call's step noise comes from -> (noise, x_shape, seed, row0).  Without a seed: the caller's stack on ctx's device
-    (or None), x_shape None.  With one: no stack may be given (refused before ctx is touched); x_shape is the call's latent shape (x_T's,
-    or cond's rows at `shape` -- what sizes a call without x_T) and (seed, row0) are validated for its rows."""
+    """Where a sampling call's step noise comes from -> (Noise, stack, x_shape).  Without a seed: the caller's stack on ctx's device (or
+    None; the struct points into it), x_shape None.  With one: no stack may be given (refused before ctx is touched); x_shape is the call's
+    latent shape (x_T's, or cond's rows at `shape` -- what sizes a call without x_T) and (seed, row0) are validated for its rows."""
     if seed is None:
-        return (None if noise is None else ctx._dev(noise, torch.float32)), None, None, row0
+        stack = None if noise is None else ctx._dev(noise, torch.float32)
+        return Noise(stack=_ptr(stack)), stack, None
     if noise is not None:
         raise RdmError(f"{what}: give a seed or a noise stack, not both")
     x_shape = Context._seeded_shape(what, x_T, cond, shape)
-    return (None, x_shape) + _noise_seed(what, seed, row0, x_shape[0])
+    seed, row0 = _noise_seed(what, seed, row0, x_shape[0])
+    return Noise(seeded=1, seed=seed, row0=row0), None, x_shape
 
 
 def _unipc_variant(what, variant):
@@ -966,14 +961,14 @@ class Context:
         return out
 
     def _sampler_call(self, what, fn, Args, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=None, nodes=None,
-                      noise=None, x_shape=None, run_steps=None, want_pred_x0=True, **fields):
+                      noise=None, nz=None, x_shape=None, run_steps=None, want_pred_x0=True, **fields):
         """What ddim_sample, plms_sample, dpmpp_sample and unipc_sample share: device casts, the fp32 alphas_cumprod array, the step
         count (of DDIM's S-step schedule, or of the node list), shape and guidance checks, the outputs.  Args(**fields) plus the fields
-        every sampler has is the argument struct, fn(handle, args, x_T, cond, uncond, z, x_inter, pred_x0_inter) the library call;
-        noise: a [steps, B, C, H, W] stack to shape-check; x_shape: the latent shape of a seeded call without x_T (fn then gets a null
-        x_T and the library draws the start); run_steps: the steps a decode / encode call runs of the S-step schedule, in [1, its
-        length] -- what then sizes the noise stack and the intermediates; want_pred_x0 False: no pred_x0_inter is allocated (fn gets null:
-        the inversion logs x only).  -> (z, x_inter, pred_x0_inter)."""
+        every sampler has is the argument struct, fn(handle, args, x_T, cond, uncond, [nz,] z, x_inter, pred_x0_inter) the library call;
+        nz: the Noise of a sampler that takes one; noise: a [steps, B, C, H, W] stack to shape-check; x_shape: the latent shape of a
+        seeded call without x_T (fn then gets a null x_T and the library draws the start); run_steps: the steps a decode / encode call
+        runs of the S-step schedule, in [1, its length] -- what then sizes the noise stack and the intermediates; want_pred_x0 False: no
+        pred_x0_inter is allocated (fn gets null: the inversion logs x only).  -> (z, x_inter, pred_x0_inter)."""
         x_T, cond, uncond = (None if t is None else self._dev(t, torch.float32) for t in (x_T, cond, uncond))
         x_arg = x_T
         if x_T is None:
@@ -1002,37 +997,35 @@ class Context:
             n = lib.rdm_ddim_num_intermediates(steps, log_every_t)
             xi = torch.empty((n,) + tuple(x_T.shape), device=self.device, dtype=torch.float32)
             pi = torch.empty_like(xi) if want_pred_x0 else None
-        self._check(fn(self._h, C.byref(a), _ptr(x_arg), _ptr(cond), _ptr(uncond), _ptr(z), _ptr(xi), _ptr(pi)))
+        self._check(fn(self._h, C.byref(a), _ptr(x_arg), _ptr(cond), _ptr(uncond), *([] if nz is None else [C.byref(nz)]), _ptr(z), _ptr(xi),
+                       _ptr(pi)))
         return z, xi, pi
 
     def ddim_sample(self, S, x_T, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
                     temperature=1.0, want_intermediates=False, seed=None, row0=0, shape=None):
-        """rdm_ddim_sample; with `seed` rdm_ddim_sample_seeded: step i's noise is the library's own (seed, stream 1, step i, row0 + b),
+        """rdm_ddim_sample; with `seed` step i's noise is the library's own (seed, stream 1, step i, row0 + b),
         generated in the step kernel (no stack; `noise` must then be None), and x_T may be None -- the start is then drawn from stream 0
         at the latent `shape` (C, H, W), for cond.shape[0] rows."""
         if seed is None and x_T is None:
             raise RdmError("ddim_sample: x_T is required without a seed")
-        noise, x_shape, seed, row0 = _noise_source(self, "ddim_sample", x_T, cond, noise, seed, row0, shape)
-        fn = ((lambda h, a, x, c, u, *out: lib.rdm_ddim_sample(h, a, x, c, u, _ptr(noise), *out)) if seed is None else
-              (lambda h, a, x, c, u, *out: lib.rdm_ddim_sample_seeded(h, a, seed, row0, x, c, u, *out)))
-        return self._sampler_call("ddim_sample", fn, DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates, S=S,
-                                  noise=noise if eta != 0.0 else None,         # (its shape matters only when it is used)
+        nz, noise, x_shape = _noise_source(self, "ddim_sample", x_T, cond, noise, seed, row0, shape)
+        return self._sampler_call("ddim_sample", lib.rdm_ddim_sample, DdimArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t,
+                                  want_intermediates, S=S, nz=nz, noise=noise if eta != 0.0 else None,   # (its shape matters only when it is used)
                                   x_shape=x_shape, eta=eta, temperature=temperature)
 
     def ddim_decode(self, S, t_start, x_latent, cond, uncond, alphas_cumprod, eta=0.0, scale=1.0, noise=None, log_every_t=100,
                     temperature=1.0, want_intermediates=False, seed=None, row0=0):
         """rdm_ddim_decode (ldm DDIMSampler.decode): the DDIM loop of the S-step schedule from x_latent at level index t_start - 1 down
         to index 0, t_start forwards; t_start = the schedule's length is ddim_sample.  noise: a [t_start, B, C, H, W] stack for
-        eta > 0; with `seed` rdm_ddim_decode_seeded: step i of this call takes the library's (seed, stream 1, step i, row0 + b), and
+        eta > 0; with `seed` step i of this call takes the library's (seed, stream 1, step i, row0 + b), and
         `noise` must be None.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
         if x_latent is None:
             raise RdmError("ddim_decode: x_latent is required")
         t_start = int(t_start)
-        noise, _, seed, row0 = _noise_source(self, "ddim_decode", x_latent, cond, noise, seed, row0)
-        fn = ((lambda h, a, x, c, u, *out: lib.rdm_ddim_decode(h, a, t_start, x, c, u, _ptr(noise), *out)) if seed is None else
-              (lambda h, a, x, c, u, *out: lib.rdm_ddim_decode_seeded(h, a, t_start, seed, row0, x, c, u, *out)))
-        return self._sampler_call("ddim_decode", fn, DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates,
-                                  S=S, noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
+        nz, noise, _ = _noise_source(self, "ddim_decode", x_latent, cond, noise, seed, row0)
+        return self._sampler_call("ddim_decode", lambda h, a, *rest: lib.rdm_ddim_decode(h, a, t_start, *rest), DdimArgs, x_latent, cond, uncond,
+                                  alphas_cumprod, scale, log_every_t, want_intermediates, S=S, nz=nz, noise=noise if eta != 0.0 else None,
+                                  run_steps=t_start, eta=eta, temperature=temperature)
 
     @staticmethod
     def _blend_mask(what, mask, shape):
@@ -1047,7 +1040,7 @@ class Context:
         """rdm_ddim_inpaint: ddim_decode's loop with the inpainting blend before every forward -- at loop step i the iterate becomes
         (sqrt(a) x0 + sqrt(1 - a) z_i) mask + (1 - mask) x at that step's level a; mask [B, 1 | C, H, W] in [0, 1], 1 = keep the known
         latent x0.  z_i = q_noise[i], q_noise a [t_start, B, C, H, W] stack (required without a seed); noise: the update noise stack for
-        eta > 0, as ddim_decode's.  With `seed` rdm_ddim_inpaint_seeded: no stack of either kind -- the update noise is the library's
+        eta > 0, as ddim_decode's.  With `seed` no stack of either kind -- the update noise is the library's
         (seed, stream 1, step i), the known region's (seed, stream 0, step i + 1), rows row0 + b.  The result of the last step is not
         blended.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
         if x_latent is None or x0 is None or mask is None:
@@ -1055,7 +1048,7 @@ class Context:
         t_start = int(t_start)
         if seed is not None and q_noise is not None:
             raise RdmError("ddim_inpaint: give a seed or a q_noise stack, not both")
-        noise, _, seed, row0 = _noise_source(self, "ddim_inpaint", x_latent, cond, noise, seed, row0)
+        nz, noise, _ = _noise_source(self, "ddim_inpaint", x_latent, cond, noise, seed, row0)
         x0, mask = self._dev(x0, torch.float32), self._dev(mask, torch.float32)
         if tuple(x0.shape) != tuple(x_latent.shape):
             raise RdmError(f"ddim_inpaint: x0 {tuple(x0.shape)} must have the latent's shape {tuple(x_latent.shape)}")
@@ -1066,16 +1059,14 @@ class Context:
             q_noise = self._dev(q_noise, torch.float32)
             if tuple(q_noise.shape) != (t_start,) + tuple(x_latent.shape):
                 raise RdmError(f"ddim_inpaint: q_noise must be {(t_start,) + tuple(x_latent.shape)}, got {tuple(q_noise.shape)}")
-        fn = ((lambda h, a, x, c, u, *out: lib.rdm_ddim_inpaint(h, a, t_start, x, _ptr(x0), _ptr(mask), mc, c, u, _ptr(noise), _ptr(q_noise), *out))
-              if seed is None else
-              (lambda h, a, x, c, u, *out: lib.rdm_ddim_inpaint_seeded(h, a, t_start, seed, row0, x, _ptr(x0), _ptr(mask), mc, c, u, *out)))
+        fn = lambda h, a, x, c, u, n, *out: lib.rdm_ddim_inpaint(h, a, t_start, x, _ptr(x0), _ptr(mask), mc, c, u, n, _ptr(q_noise), *out)
         return self._sampler_call("ddim_inpaint", fn, DdimArgs, x_latent, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates,
-                                  S=S, noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
+                                  S=S, nz=nz, noise=noise if eta != 0.0 else None, run_steps=t_start, eta=eta, temperature=temperature)
 
     def op_masked_blend(self, x, x0, mask, z, sqrt_a, sqrt_1ma, out=None, x_dup=None, seed=None, row0=0, step=1):
         """The inpainting blend kernel alone on caller-owned contiguous fp32 device tensors: out = (sqrt_a x0 + sqrt_1ma z) mask +
         (1 - mask) x over x [B, C, H, W], mask [B, 1 | C, H, W] (1 = x0), z of x's size or None (zeros) (rdm_op_masked_blend).  With `seed`
-        (and no z) rdm_op_masked_blend_seeded: z is the library's (seed, stream 0, step, row0 + b), drawn in the kernel -- step i + 1 for
+        (and no z) z is the library's (seed, stream 0, step, row0 + b), drawn in the kernel -- step i + 1 for
         loop step i; C * H * W must then be a multiple of 4 and x, x0, out, x_dup 16-byte aligned.  out (default: a new tensor) may be x;
         x_dup receives the same values.  -> out."""
         ok = lambda t: t.dtype == torch.float32 and t.is_cuda and t.is_contiguous()
@@ -1090,18 +1081,17 @@ class Context:
             if t is not None and (not ok(t) or t.numel() != x.numel()):
                 raise RdmError("op_masked_blend: z, out and x_dup must be contiguous fp32 device tensors of x's size")
         B, Cc, H, W = (int(v) for v in x.shape)
-        if seed is None:
-            self._check(lib.rdm_op_masked_blend(self._h, _ptr(x), _ptr(x0), _ptr(mask), _ptr(z), B, Cc, H, W, mc, float(sqrt_a), float(sqrt_1ma),
-                                                _ptr(out), _ptr(x_dup)))
-            return out
-        if z is not None:
-            raise RdmError("op_masked_blend: a seeded call takes no z operand")
-        step = int(step)
-        if not 0 <= step < 2 ** 32:
-            raise RdmError(f"op_masked_blend: step is a 32-bit counter, got {step}")
-        seed, row0 = _noise_seed("op_masked_blend", seed, row0, B)
-        self._check(lib.rdm_op_masked_blend_seeded(self._h, _ptr(x), _ptr(x0), _ptr(mask), B, Cc, H, W, mc, float(sqrt_a), float(sqrt_1ma), seed,
-                                                   row0, step, _ptr(out), _ptr(x_dup)))
+        nz = Noise(stack=_ptr(z))
+        if seed is not None:
+            if z is not None:
+                raise RdmError("op_masked_blend: a seeded call takes no z operand")
+            step = int(step)
+            if not 0 <= step < 2 ** 32:
+                raise RdmError(f"op_masked_blend: step is a 32-bit counter, got {step}")
+            seed, row0 = _noise_seed("op_masked_blend", seed, row0, B)
+            nz = Noise(seeded=1, seed=seed, row0=row0, step=step)
+        self._check(lib.rdm_op_masked_blend(self._h, _ptr(x), _ptr(x0), _ptr(mask), C.byref(nz), B, Cc, H, W, mc, float(sqrt_a), float(sqrt_1ma),
+                                            _ptr(out), _ptr(x_dup)))
         return out
 
     def ddim_encode(self, S, t_enc, x0, cond, uncond, alphas_cumprod, scale=1.0, log_every_t=100, want_intermediates=False, eta=0.0):
@@ -1193,31 +1183,30 @@ class Context:
         return n
 
     @staticmethod
-    def _step_rows(what, n, per_row, seed, row0, step):
-        """(seed, row0, per_row, step) of a seeded step-kernel call; the library checks that per_row divides n."""
+    def _step_noise(what, noise, n, seed, row0, per_row, step):
+        """The Noise of a step-kernel call: the noise operand (or None), or, with a seed, (seed, row0, per_row, step); the library checks
+        that per_row divides n."""
+        if seed is None:
+            return Noise(stack=_ptr(noise))
+        if noise is not None or per_row is None:
+            raise RdmError(f"{what}: a seeded call takes per_row and no noise operand")
         per_row, step = int(per_row), int(step)
         if per_row < 1 or not 0 <= step < 2 ** 32:
             raise RdmError(f"{what}: per_row must be >= 1 and step a 32-bit counter, got per_row={per_row}, step={step}")
         seed, row0 = _noise_seed(what, seed, row0, max(n // per_row, 1))
-        return seed, row0, per_row, step
+        return Noise(seeded=1, seed=seed, row0=row0, per_row=per_row, step=step)
 
     def op_ddim_step(self, x, eps, noise, cfg, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature, x_prev, x_dup=None, pred_x0=None,
                      seed=None, row0=0, per_row=None, step=0):
         """The DDIM update kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
         [cond | uncond]) with the kernel's own scalars (rdm_op_ddim_step); noise / x_dup / pred_x0 may be None, x_prev may be x.  With
-        `seed` (and no noise) rdm_op_ddim_step_seeded: the noise of (seed, stream 1, step, row0 + b) for rows of per_row elements, drawn
+        `seed` (and no noise) the noise of (seed, stream 1, step, row0 + b) for rows of per_row elements, drawn
         in the kernel.  Writes into the given outputs."""
         n = self._step_sizes("op_ddim_step", x, eps, cfg, (noise, x_prev, x_dup, pred_x0))
         sc = [float(v) for v in (scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature)]
-        if seed is None:
-            self._check(lib.rdm_op_ddim_step(self._h, _ptr(x), _ptr(eps), _ptr(noise), n, int(bool(cfg)), *sc, _ptr(x_prev), _ptr(x_dup),
-                                             _ptr(pred_x0)))
-            return
-        if noise is not None or per_row is None:
-            raise RdmError("op_ddim_step: a seeded call takes per_row and no noise operand")
-        seed, row0, per_row, step = self._step_rows("op_ddim_step", n, per_row, seed, row0, step)
-        self._check(lib.rdm_op_ddim_step_seeded(self._h, _ptr(x), _ptr(eps), n, per_row, int(bool(cfg)), *sc, seed, row0, step, _ptr(x_prev),
-                                                _ptr(x_dup), _ptr(pred_x0)))
+        nz = self._step_noise("op_ddim_step", noise, n, seed, row0, per_row, step)
+        self._check(lib.rdm_op_ddim_step(self._h, _ptr(x), _ptr(eps), C.byref(nz), n, int(bool(cfg)), *sc, _ptr(x_prev), _ptr(x_dup),
+                                         _ptr(pred_x0)))
 
     def op_plms_step(self, x, eps, cfg, scale, a_t, a_prev, sqrt_one_minus_at, mode, order, x_out, e_prev=None, h1=None, h2=None, h3=None,
                      e_store=None, x_dup=None, pred_x0=None):
@@ -1232,19 +1221,13 @@ class Context:
     def op_ddpm_step(self, x, eps, noise, sqrt_recip, sqrt_recipm1, coef1, coef2, log_var, clip, nonzero, temperature, x_prev, seed=None,
                      row0=0, per_row=None, step=0):
         """The ancestral DDPM update kernel alone on caller-owned fp32 device tensors of x.numel() elements (rdm_op_ddpm_step); noise may
-        be None when nonzero is false, x_prev may be x.  With `seed` (and no noise) rdm_op_ddpm_step_seeded, as op_ddim_step.  Writes
+        be None when nonzero is false, x_prev may be x.  With `seed` (and no noise) the library's noise, as op_ddim_step.  Writes
         into x_prev."""
         n = self._step_sizes("op_ddpm_step", x, eps, False, (noise, x_prev))
         sc = [float(v) for v in (sqrt_recip, sqrt_recipm1, coef1, coef2, log_var)]
-        if seed is None:
-            self._check(lib.rdm_op_ddpm_step(self._h, _ptr(x), _ptr(eps), _ptr(noise), n, *sc, int(bool(clip)), int(bool(nonzero)),
-                                             float(temperature), _ptr(x_prev)))
-            return
-        if noise is not None or per_row is None:
-            raise RdmError("op_ddpm_step: a seeded call takes per_row and no noise operand")
-        seed, row0, per_row, step = self._step_rows("op_ddpm_step", n, per_row, seed, row0, step)
-        self._check(lib.rdm_op_ddpm_step_seeded(self._h, _ptr(x), _ptr(eps), n, per_row, *sc, int(bool(clip)), int(bool(nonzero)),
-                                                float(temperature), seed, row0, step, _ptr(x_prev)))
+        nz = self._step_noise("op_ddpm_step", noise, n, seed, row0, per_row, step)
+        self._check(lib.rdm_op_ddpm_step(self._h, _ptr(x), _ptr(eps), C.byref(nz), n, *sc, int(bool(clip)), int(bool(nonzero)),
+                                         float(temperature), _ptr(x_prev)))
 
     @staticmethod
     def dpmpp_timesteps(S, alphas_cumprod, skip_type="logSNR"):
@@ -1272,38 +1255,31 @@ class Context:
     def dpmpp_sde_sample(self, nodes, x_T, cond, uncond, alphas_cumprod, scale=1.0, order=2, lower_order_final=None, noise=None,
                          log_every_t=100, want_intermediates=False, seed=None, row0=0, shape=None):
         """SDE-DPM-Solver++(2M) over the node list of dpmpp_sample: rdm_dpmpp_sde_sample with `noise`, the [len(nodes) - 1, B, C, H, W] stack of
-        the steps' z_j; with `seed` rdm_dpmpp_sde_sample_seeded: z_j is the library's own (seed, stream 1, step j, row0 + b), generated in
+        the steps' z_j; with `seed` z_j is the library's own (seed, stream 1, step j, row0 + b), generated in
         the step kernel (`noise` must then be None), and x_T may be None -- the start is then drawn from stream 0 at the latent `shape`
         (C, H, W), for cond.shape[0] rows.  Returns (z, x_inter, pred_x0_inter); the intermediates are None unless want_intermediates."""
         if lower_order_final is None:
             lower_order_final = _nodes_array(nodes).shape[0] - 1 < 15
         if seed is None and (x_T is None or noise is None):
             raise RdmError("dpmpp_sde_sample: x_T and a noise stack are required without a seed")
-        noise, x_shape, seed, row0 = _noise_source(self, "dpmpp_sde_sample", x_T, cond, noise, seed, row0, shape)
-        fn = ((lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample(h, a, x, c, u, _ptr(noise), *out)) if seed is None else
-              (lambda h, a, x, c, u, *out: lib.rdm_dpmpp_sde_sample_seeded(h, a, seed, row0, x, c, u, *out)))
-        return self._sampler_call("dpmpp_sde_sample", fn, DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t, want_intermediates,
-                                  noise=noise, x_shape=x_shape, nodes=nodes, order=int(order), lower_order_final=int(bool(lower_order_final)))
+        nz, noise, x_shape = _noise_source(self, "dpmpp_sde_sample", x_T, cond, noise, seed, row0, shape)
+        return self._sampler_call("dpmpp_sde_sample", lib.rdm_dpmpp_sde_sample, DpmppArgs, x_T, cond, uncond, alphas_cumprod, scale, log_every_t,
+                                  want_intermediates, nz=nz, noise=noise, x_shape=x_shape, nodes=nodes, order=int(order),
+                                  lower_order_final=int(bool(lower_order_final)))
 
     def op_dpmpp_sde_step(self, x, eps, m_prev, noise, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup=None,
                           m_store=None, pred_x0=None, seed=None, row0=0, per_row=None, step=0):
         """The SDE-DPM-Solver++ update kernel alone on caller-owned fp32 device tensors of x.numel() elements (eps: twice that under cfg,
         [cond | uncond]) (rdm_op_dpmpp_sde_step); m_prev / x_dup / m_store / pred_x0 may be None, m_store may be m_prev.  With `seed` (and
-        no noise) rdm_op_dpmpp_sde_step_seeded: the noise of (seed, stream 1, step, row0 + b) for rows of per_row elements, drawn in the
+        no noise) the noise of (seed, stream 1, step, row0 + b) for rows of per_row elements, drawn in the
         kernel.  Writes into the given outputs."""
         n = self._step_sizes("op_dpmpp_sde_step", x, eps, cfg, (m_prev, noise, x_out, x_dup, m_store, pred_x0))
         sc = [float(v) for v in (scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n)]
         outs = (_ptr(x_out), _ptr(x_dup), _ptr(m_store), _ptr(pred_x0))
-        if seed is None:
-            if noise is None:
-                raise RdmError("op_dpmpp_sde_step: a noise operand or a seed is required")
-            self._check(lib.rdm_op_dpmpp_sde_step(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), _ptr(noise), n, int(bool(cfg)), *sc, *outs))
-            return
-        if noise is not None or per_row is None:
-            raise RdmError("op_dpmpp_sde_step: a seeded call takes per_row and no noise operand")
-        seed, row0, per_row, step = self._step_rows("op_dpmpp_sde_step", n, per_row, seed, row0, step)
-        self._check(lib.rdm_op_dpmpp_sde_step_seeded(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), n, per_row, int(bool(cfg)), *sc, seed, row0, step,
-                                                     *outs))
+        if seed is None and noise is None:
+            raise RdmError("op_dpmpp_sde_step: a noise operand or a seed is required")
+        nz = self._step_noise("op_dpmpp_sde_step", noise, n, seed, row0, per_row, step)
+        self._check(lib.rdm_op_dpmpp_sde_step(self._h, _ptr(x), _ptr(eps), _ptr(m_prev), C.byref(nz), n, int(bool(cfg)), *sc, *outs))
 
     @staticmethod
     def unipc_coefficients(nodes, alphas_cumprod, j, order=2, variant="bh2", corrector=True, lower_order_final=True):
@@ -1333,13 +1309,13 @@ class Context:
                                           _ptr(m_store), _ptr(pred_x0)))
 
     def ddpm_sample(self, timesteps, x_T, cond, noise=None, sched=None, clip_denoised=True, temperature=1.0, seed=None, row0=0, shape=None):
-        """rdm_ddpm_sample on a noise stack [timesteps, B, C, H, W]; with `seed` (and no stack) rdm_ddpm_sample_seeded: the library's own
+        """rdm_ddpm_sample on a noise stack [timesteps, B, C, H, W]; with `seed` (and no stack) the library's own
         noise, generated in the step kernel, and x_T may be None (drawn from stream 0 at the latent `shape` (C, H, W))."""
         if sched is None:
             raise RdmError("ddpm_sample: the schedule arrays are required")
         if seed is None and (noise is None or x_T is None):
             raise RdmError("ddpm_sample: x_T and a noise stack are required without a seed")
-        noise, x_shape, seed, row0 = _noise_source(self, "ddpm_sample", x_T, cond, noise, seed, row0, shape)
+        nz, noise, x_shape = _noise_source(self, "ddpm_sample", x_T, cond, noise, seed, row0, shape)
         cond = self._dev(cond, torch.float32)
         x_arg = x_T = None if x_T is None else self._dev(x_T, torch.float32)
         if x_T is None:
@@ -1355,10 +1331,7 @@ class Context:
                      posterior_mean_coef1=fp("posterior_mean_coef1"), posterior_mean_coef2=fp("posterior_mean_coef2"),
                      posterior_log_variance_clipped=fp("posterior_log_variance_clipped"))
         z = torch.empty(tuple(x_T.shape), device=self.device, dtype=torch.float32)
-        if seed is not None:
-            self._check(lib.rdm_ddpm_sample_seeded(self._h, C.byref(a), seed, row0, _ptr(x_arg), _ptr(cond), _ptr(z)))
-        else:
-            self._check(lib.rdm_ddpm_sample(self._h, C.byref(a), _ptr(x_T), _ptr(cond), _ptr(noise), _ptr(z)))
+        self._check(lib.rdm_ddpm_sample(self._h, C.byref(a), _ptr(x_arg), _ptr(cond), C.byref(nz), _ptr(z)))
         return z
 
     def vq_decode(self, z, force_not_quantize=False, return_indices=False):

@@ -345,19 +345,18 @@ hipError_t launch_softmax_bwd(const bf16_t* P, const float* dP, bf16_t* dS, long
 hipError_t launch_expand_heads(const bf16_t* kv, int ld, int B, int k, int heads, int hd, int NP, float scale, bf16_t* out, hipStream_t st);
 hipError_t launch_add_bias_rows(const bf16_t* x, const float* bias, bf16_t* out, long long rows, int C, hipStream_t st);
 hipError_t launch_row_nonzero(const float* x, int rows, long long n, int* flag, hipStream_t st);   // flag[r] = row r has a non-zero element
-hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st);
-hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st);
-hipError_t launch_ddim_step_seeded(const DdimStepParams& p, const StepRngParams& g, hipStream_t st);   // p.noise unused; n, per_row % 4 == 0, operands 16-byte aligned
-hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams& g, hipStream_t st);
+// rng null: the kernel reads p.noise / p.z from memory; else the seeded kernel draws it (p.noise / p.z unused), which has no scalar form --
+// hipErrorInvalidValue unless n and per_row are multiples of 4, per_row divides n and every operand is 16-byte aligned
+hipError_t launch_ddim_step(const DdimStepParams& p, const StepRngParams* rng, hipStream_t st);
+hipError_t launch_ddpm_step(const DdpmStepParams& p, const StepRngParams* rng, hipStream_t st);
 hipError_t launch_rng_fill(const RngFillParams& p, bool normal, hipStream_t st);
 hipError_t launch_plms_step(const PlmsStepParams& p, hipStream_t st);
-hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st);      // p.noise null: the ODE step; else the SDE step on the stack's z
-hipError_t launch_dpmpp_sde_step_seeded(const DpmppStepParams& p, const StepRngParams& g, hipStream_t st);   // as launch_ddim_step_seeded
+hipError_t launch_dpmpp_step(const DpmppStepParams& p, const StepRngParams* rng, hipStream_t st);      // rng and p.noise null: the ODE step; else the SDE step
 hipError_t launch_unipc_step(const UnipcStepParams& p, hipStream_t st);
 hipError_t launch_ddim_inverse_step(const DdimInverseStepParams& p, hipStream_t st);
 hipError_t launch_q_sample_seeded(const QSampleSeededParams& p, hipStream_t st);     // hipErrorInvalidValue: per_row % 4 or an operand not 16-byte aligned
-hipError_t launch_masked_blend(const MaskedBlendParams& p, hipStream_t st);          // float4 form when n % 4 == 0, hw % 4 == 0 and every operand is 16-byte aligned, else scalar
-hipError_t launch_masked_blend_seeded(const MaskedBlendParams& p, const StepRngParams& g, hipStream_t st);   // p.z unused; hipErrorInvalidValue: chw % 4 or x / x0 / out / x_dup not 16-byte aligned
+// rng null: float4 form when n % 4 == 0, hw % 4 == 0 and every operand is 16-byte aligned, else scalar; rng: hipErrorInvalidValue for chw % 4 or x / x0 / out / x_dup not 16-byte aligned
+hipError_t launch_masked_blend(const MaskedBlendParams& p, const StepRngParams* rng, hipStream_t st);
 hipError_t launch_vq_quantize(const float* z, const float* codebook, int n_embed, const float* pq_w, const float* pq_b,
                               float* out, int* idx_out, int B, int HW, int quantize, hipStream_t st);
 // nearest-code search of a wide-latent VQ first stage (vqcode.hip): idx[m] = argmin_j |e_j|^2 - 2 z_m . e_j on fp32-input MFMAs, first minimum on ties

@@ -24,11 +24,6 @@ __global__ void ddim_step_kernel(DdimStepParams p) {
         if (p.pred_x0) p.pred_x0[i] = x0;
     }
 }
-hipError_t launch_ddim_step(const DdimStepParams& p, hipStream_t st) {
-    int grid = (int)((p.n_per_batch + 255) / 256); if (grid > 2048) grid = 2048;
-    ddim_step_kernel<<<grid, 256, 0, st>>>(p);
-    return hipGetLastError();
-}
 
 // ------------------------------------------------------------------ what the PLMS, DPM-Solver++ and UniPC step kernels share
 template <int V> __device__ __forceinline__ void step_ld(const float* p, long long i, float (&v)[V]) {
@@ -164,12 +159,6 @@ __global__ __launch_bounds__(256) void dpmpp_sde_step_kernel(DpmppStepParams p) 
         dpmpp_update<V, true>(p, i, z);
     }
 }
-// p.noise null: the ODE step
-hipError_t launch_dpmpp_step(const DpmppStepParams& p, hipStream_t st) {
-    const bool sde = p.noise != nullptr;
-    return launch_step(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.noise, p.x_out, p.x_dup, p.m_store, p.pred_x0}, p,
-                       sde ? dpmpp_sde_step_kernel<4> : dpmpp_step_kernel<4>, sde ? dpmpp_sde_step_kernel<1> : dpmpp_step_kernel<1>, st);
-}
 
 // ------------------------------------------------------------------ UniPC predict-and-correct (fp32)
 // Zhao et al. 2023 (UniPC, data prediction, multistep): after the forward at node j one pass forms m = (u - sigma_j e) / alpha_j from
@@ -260,11 +249,6 @@ __global__ void ddpm_step_kernel(DdpmStepParams p) {
         const float mean = p.coef1 * x0 + p.coef2 * x;
         p.x_prev[i] = mean + (p.nonzero ? sd * p.noise[i] * p.temperature : 0.f);
     }
-}
-hipError_t launch_ddpm_step(const DdpmStepParams& p, hipStream_t st) {
-    int grid = (int)((p.n + 255) / 256); if (grid > 2048) grid = 2048;
-    ddpm_step_kernel<<<grid, 256, 0, st>>>(p);
-    return hipGetLastError();
 }
 
 // ------------------------------------------------------------------ device noise (philox.h)
@@ -359,14 +343,24 @@ static hipError_t launch_step_seeded(long long n, std::initializer_list<const vo
     k<<<grid, 256, 0, st>>>(p, g);
     return hipGetLastError();
 }
-hipError_t launch_ddim_step_seeded(const DdimStepParams& p, const StepRngParams& g, hipStream_t st) {
-    return launch_step_seeded(p.n_per_batch, {p.x, p.eps, p.eps + (p.cfg ? p.n_per_batch : 0), p.x_prev, p.x_dup, p.pred_x0}, p, g, ddim_step_seeded_kernel, st);
+// The launchers of the three updates: rng null -> the kernel that reads p.noise (the ODE step when that is null too), else the seeded one
+hipError_t launch_ddim_step(const DdimStepParams& p, const StepRngParams* rng, hipStream_t st) {
+    if (rng) return launch_step_seeded(p.n_per_batch, {p.x, p.eps, p.eps + (p.cfg ? p.n_per_batch : 0), p.x_prev, p.x_dup, p.pred_x0}, p, *rng, ddim_step_seeded_kernel, st);
+    int grid = (int)((p.n_per_batch + 255) / 256); if (grid > 2048) grid = 2048;
+    ddim_step_kernel<<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
 }
-hipError_t launch_ddpm_step_seeded(const DdpmStepParams& p, const StepRngParams& g, hipStream_t st) {
-    return launch_step_seeded(p.n, {p.x, p.eps, p.x_prev}, p, g, ddpm_step_seeded_kernel, st);
+hipError_t launch_ddpm_step(const DdpmStepParams& p, const StepRngParams* rng, hipStream_t st) {
+    if (rng) return launch_step_seeded(p.n, {p.x, p.eps, p.x_prev}, p, *rng, ddpm_step_seeded_kernel, st);
+    int grid = (int)((p.n + 255) / 256); if (grid > 2048) grid = 2048;
+    ddpm_step_kernel<<<grid, 256, 0, st>>>(p);
+    return hipGetLastError();
 }
-hipError_t launch_dpmpp_sde_step_seeded(const DpmppStepParams& p, const StepRngParams& g, hipStream_t st) {
-    return launch_step_seeded(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.x_out, p.x_dup, p.m_store, p.pred_x0}, p, g, dpmpp_sde_step_seeded_kernel, st);
+hipError_t launch_dpmpp_step(const DpmppStepParams& p, const StepRngParams* rng, hipStream_t st) {
+    if (rng) return launch_step_seeded(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.x_out, p.x_dup, p.m_store, p.pred_x0}, p, *rng, dpmpp_sde_step_seeded_kernel, st);
+    const bool sde = p.noise != nullptr;
+    return launch_step(p.n, {p.x, p.eps, p.eps + (p.cfg ? p.n : 0), p.m_prev, p.noise, p.x_out, p.x_dup, p.m_store, p.pred_x0}, p,
+                       sde ? dpmpp_sde_step_kernel<4> : dpmpp_step_kernel<4>, sde ? dpmpp_sde_step_kernel<1> : dpmpp_step_kernel<1>, st);
 }
 
 // The forward process on a noise value that never reaches memory: out = sqrt_a x0 + sqrt_1ma z with z the starting-latent normals
@@ -467,16 +461,6 @@ __global__ __launch_bounds__(256) void masked_blend_kernel(MaskedBlendParams p) 
         if (p.x_dup) step_st<V>(p.x_dup, i, o);
     }
 }
-hipError_t launch_masked_blend(const MaskedBlendParams& p, hipStream_t st) {
-    if (p.n <= 0) return hipSuccess;
-    bool vec = p.n % 4 == 0 && p.hw % 4 == 0;               // launch_step's rule, and whole mask quads
-    for (const void* q : {(const void*)p.x, (const void*)p.x0, (const void*)p.mask, (const void*)p.z, (const void*)p.out, (const void*)p.x_dup})
-        vec = vec && ((uintptr_t)q % 16 == 0);
-    const long long nv = vec ? p.n / 4 : p.n;
-    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
-    (vec ? masked_blend_kernel<4> : masked_blend_kernel<1>)<<<grid, 256, 0, st>>>(p);
-    return hipGetLastError();
-}
 // The same arithmetic on noise drawn in registers: one Philox block per thread, four consecutive elements of one sample row, (row, block)
 // derived from the flat vector index as in ddim_step_seeded_kernel -- stream 0 (RDM_RNG_STREAM_XT) at step g.step >= 1, the forward
 // process's noise of the known region (philox.h).  chw % 4 == 0: rows never share a block.  When hw % 4 != 0 a block straddles channel
@@ -500,11 +484,21 @@ __global__ __launch_bounds__(256) void masked_blend_seeded_kernel(MaskedBlendPar
         if (p.x_dup) step_st<4>(p.x_dup, i, o);
     }
 }
-hipError_t launch_masked_blend_seeded(const MaskedBlendParams& p, const StepRngParams& g, hipStream_t st) {
-    if (g.per_row != p.chw || !seeded_step_ok(p.n, g.per_row, {p.x, p.x0, p.out, p.x_dup})) return hipErrorInvalidValue;
-    MaskedBlendParams q = p;
-    q.z = nullptr; q.mask_vec = (p.hw % 4 == 0 && (uintptr_t)p.mask % 16 == 0) ? 1 : 0;
-    const int grid = (int)std::min<long long>((p.n / 4 + 255) / 256, 2048);
-    masked_blend_seeded_kernel<<<grid, 256, 0, st>>>(q, g);
+hipError_t launch_masked_blend(const MaskedBlendParams& p, const StepRngParams* rng, hipStream_t st) {
+    if (rng) {
+        if (rng->per_row != p.chw || !seeded_step_ok(p.n, rng->per_row, {p.x, p.x0, p.out, p.x_dup})) return hipErrorInvalidValue;
+        MaskedBlendParams q = p;
+        q.z = nullptr; q.mask_vec = (p.hw % 4 == 0 && (uintptr_t)p.mask % 16 == 0) ? 1 : 0;
+        const int grid = (int)std::min<long long>((p.n / 4 + 255) / 256, 2048);
+        masked_blend_seeded_kernel<<<grid, 256, 0, st>>>(q, *rng);
+        return hipGetLastError();
+    }
+    if (p.n <= 0) return hipSuccess;
+    bool vec = p.n % 4 == 0 && p.hw % 4 == 0;               // launch_step's rule, and whole mask quads
+    for (const void* q : {(const void*)p.x, (const void*)p.x0, (const void*)p.mask, (const void*)p.z, (const void*)p.out, (const void*)p.x_dup})
+        vec = vec && ((uintptr_t)q % 16 == 0);
+    const long long nv = vec ? p.n / 4 : p.n;
+    const int grid = (int)std::min<long long>((nv + 255) / 256, 2048);
+    (vec ? masked_blend_kernel<4> : masked_blend_kernel<1>)<<<grid, 256, 0, st>>>(p);
     return hipGetLastError();
 }

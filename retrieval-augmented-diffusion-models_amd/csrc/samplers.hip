@@ -1,6 +1,6 @@
 // The sampling loops of librdm_hip (DDIM, PLMS, DPM-Solver++(2M) and its SDE form -- one loop, dpmpp_sample_impl --, UniPC, DDPM): their
 // schedules, SamplerRun (one sampling call's scratch, tables and UNet forward), NoiseSource (where a loop's step noise comes from: a stack,
-// a seed, or nowhere), the rdm_*_sample entries, the device-noise entries, DDIM image-to-image (rdm_ddim_decode: the
+// a seed, or nowhere: the entries' one rdm_noise argument), the rdm_*_sample entries, the device-noise entries, DDIM image-to-image (rdm_ddim_decode: the
 // DDIM loop begun part-way down the schedule; rdm_ddim_encode: the loop that runs UP it; rdm_ddim_inpaint: decode with the known latent
 // blended in before every forward) and the step-kernel op entries.
 // Calls into unet_exec.hip through the three functions host.h declares (unet_prepare_kv, unet_emb_table, unet_forward_impl) and
@@ -61,12 +61,18 @@ static int check_noise_rows(rdm_ctx* c, const char* who, int64_t row0, int64_t B
     return 0;
 }
 // Where a loop's step noise comes from: a caller's stack, the generator under (seed, row0), or nowhere (a deterministic loop) -- never two
-// of them: the entries build it with one of the two functions.
+// of them: noise_source builds it from an entry's rdm_noise argument (who: the entry's name) and refuses one that names both.
 struct NoiseSource {
     const float* stack = nullptr; bool seeded = false; NoiseSeed seed{};
-    static NoiseSource from_stack(const float* noise) { NoiseSource s; s.stack = noise; return s; }
-    static NoiseSource from_seed(uint64_t seed, int64_t row0) { NoiseSource s; s.seeded = true; s.seed = {seed, row0}; return s; }
+    bool none() const { return !seeded && !stack; }
 };
+static int noise_source(rdm_ctx* c, const char* who, const rdm_noise* n, NoiseSource* ns) {
+    *ns = NoiseSource{};
+    if (n && n->seeded && n->stack) return c->fail(-1, "%s: give a seed or a stack, not both", who);
+    if (n && n->seeded) { ns->seeded = true; ns->seed = {n->seed, n->row0}; }
+    else if (n) ns->stack = n->stack;
+    return 0;
+}
 // What a seeded loop asks of the call's shape (who: the sampler's name): check_noise_rows, and whole Philox blocks per row
 template <class Args>
 static int check_seeded(rdm_ctx* c, const char* who, const NoiseSource& ns, const Args* a) {
@@ -168,10 +174,10 @@ struct HistoryRing {
     }
 };
 
-// The DDIM loop of rdm_ddim_sample (the step noise is read from ns.stack) and rdm_ddim_sample_seeded (it is generated in the step kernel,
-// and a null x_T is drawn), and of the two rdm_ddim_decode entries: n_run steps down from level index n_run - 1 (n_run < 0: the whole
-// schedule).  The run is the loop over the schedule cut to its first n_run entries.
-// Inpainting (the two rdm_ddim_inpaint entries): before the forward of loop step i the iterate is blended with the known latent x0 noised
+// The DDIM loop of rdm_ddim_sample (the step noise is read from ns.stack, or, seeded, generated in the step kernel, and a null x_T is
+// drawn) and of rdm_ddim_decode: n_run steps down from level index n_run - 1 (n_run < 0: the whole schedule).  The run is the loop over
+// the schedule cut to its first n_run entries.
+// Inpainting (rdm_ddim_inpaint): before the forward of loop step i the iterate is blended with the known latent x0 noised
 // to that step's level, x <- (sqrt(a) x0 + sqrt(1 - a) z_i) m + (1 - m) x with a = a_t[index] (masked_blend_kernel; the scalars are float64
 // square roots of the fp32 alpha, rounded, as rdm_ddim_encode's).  z_i is row i of q_noise, or -- a seeded loop, q_noise null -- drawn in
 // the blend kernel from (seed, stream 0, step i + 1).  The result of the last step is not blended, as in ldm's loop.
@@ -209,14 +215,11 @@ static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, int n_run, const
             m.x = run.x; m.x0 = ip->x0; m.mask = ip->mask; m.out = run.x; m.x_dup = run.x_dup;
             m.n = run.n1; m.chw = run.n1 / run.B; m.hw = (long long)run.H * run.W; m.mask_channels = ip->mask_channels;
             m.sqrt_a = (float)std::sqrt(ad); m.sqrt_1ma = (float)std::sqrt(1.0 - ad);
-            if (ns.seeded) {                     // the known region's noise of loop step i, in registers
-                const hipError_t e = launch_masked_blend_seeded(m, run.step_rng(ns.seed, i + 1), c->stream);
-                if (e == hipErrorInvalidValue) return c->fail(-1, "ddim inpaint (seeded): x0 must be 16-byte aligned");
-                RDM_CHECK_HIP(c, e);
-            } else {
-                m.z = ip->q_noise + (size_t)i * run.n1;
-                RDM_CHECK_HIP(c, launch_masked_blend(m, c->stream));
-            }
+            const StepRngParams g = run.step_rng(ns.seed, i + 1);         // seeded: the known region's noise of loop step i, in registers
+            if (!ns.seeded) m.z = ip->q_noise + (size_t)i * run.n1;
+            const hipError_t e = launch_masked_blend(m, ns.seeded ? &g : nullptr, c->stream);
+            if (ns.seeded && e == hipErrorInvalidValue) return c->fail(-1, "ddim inpaint (seeded): x0 must be 16-byte aligned");
+            RDM_CHECK_HIP(c, e);
         }
         RDM_TRY(run.forward(index));
         DdimStepParams p{};
@@ -224,59 +227,45 @@ static int ddim_sample_impl(rdm_ctx* c, const rdm_ddim_args* a, int n_run, const
         p.x_prev = run.x; p.x_dup = run.x_dup; p.pred_x0 = run.pred_x0_slot(i);
         p.n_per_batch = run.n1; p.a_t = at[index]; p.a_prev = ap[index]; p.sigma_t = sg[index]; p.sqrt_one_minus_at = s1m[index];
         p.scale = a->unconditional_guidance_scale; p.temperature = a->temperature; p.cfg = cfg ? 1 : 0;
-        if (ns.seeded && a->eta != 0.f) RDM_TRY(seeded_launched(c, "ddim", launch_ddim_step_seeded(p, run.step_rng(ns.seed, i), c->stream)));   // the noise of loop step i, in registers
-        else RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
+        const StepRngParams g = run.step_rng(ns.seed, i), *rng = (ns.seeded && a->eta != 0.f) ? &g : nullptr;   // the noise of loop step i, in registers
+        if (rng) RDM_TRY(seeded_launched(c, "ddim", launch_ddim_step(p, rng, c->stream)));
+        else RDM_CHECK_HIP(c, launch_ddim_step(p, nullptr, c->stream));
         RDM_TRY(run.log_x(i));
     }
     return run.finish(z_out);
 }
 int rdm_ddim_sample(rdm_ctx* c, const rdm_ddim_args* a, const float* x_T, const float* cond, const float* uncond,
-                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
+                    const rdm_noise* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
-    if (!c || !a || !x_T || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, NoiseSource::from_stack(noise), z_out, x_inter, pred_x0_inter);
-}
-int rdm_ddim_sample_seeded(rdm_ctx* c, const rdm_ddim_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
-                           const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
-    RDM_ENTER(c);
-    if (!c || !a || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, NoiseSource::from_seed(seed, row0), z_out, x_inter, pred_x0_inter);
+    NoiseSource ns;
+    RDM_TRY(noise_source(c, "rdm_ddim_sample", noise, &ns));
+    if (!a || (!x_T && !ns.seeded) || !cond || !z_out) return c->fail(-1, "null argument");
+    return ddim_sample_impl(c, a, -1, x_T, cond, uncond, ns, z_out, x_inter, pred_x0_inter);
 }
 
 // ldm DDIMSampler.decode: the DDIM loop from a latent at level index t_start - 1
 int rdm_ddim_decode(rdm_ctx* c, const rdm_ddim_args* a, int t_start, const float* x_latent, const float* cond, const float* uncond,
-                    const float* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
+                    const rdm_noise* noise, float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
-    if (!c || !a || !x_latent || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    NoiseSource ns;
+    RDM_TRY(noise_source(c, "rdm_ddim_decode", noise, &ns));
+    if (!a || !x_latent || !cond || !z_out) return c->fail(-1, "null argument");
     if (t_start < 1) return c->fail(-1, "ddim decode: t_start must be at least 1, got %d", t_start);
-    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_stack(noise), z_out, x_inter, pred_x0_inter);
-}
-int rdm_ddim_decode_seeded(rdm_ctx* c, const rdm_ddim_args* a, int t_start, uint64_t seed, int64_t row0, const float* x_latent, const float* cond,
-                           const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
-    RDM_ENTER(c);
-    if (!c || !a || !x_latent || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    if (t_start < 1) return c->fail(-1, "ddim decode: t_start must be at least 1, got %d", t_start);
-    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_seed(seed, row0), z_out, x_inter, pred_x0_inter);
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, ns, z_out, x_inter, pred_x0_inter);
 }
 
 // DDIM inpainting: rdm_ddim_decode's loop with the blend above before every forward
 int rdm_ddim_inpaint(rdm_ctx* c, const rdm_ddim_args* a, int t_start, const float* x_latent, const float* x0, const float* mask, int mask_channels,
-                     const float* cond, const float* uncond, const float* noise, const float* q_noise, float* z_out, float* x_inter,
+                     const float* cond, const float* uncond, const rdm_noise* noise, const float* q_noise, float* z_out, float* x_inter,
                      float* pred_x0_inter) {
     RDM_ENTER(c);
-    if (!c || !a || !x_latent || !x0 || !mask || !q_noise || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
+    NoiseSource ns;
+    RDM_TRY(noise_source(c, "rdm_ddim_inpaint", noise, &ns));
+    if (ns.seeded && q_noise) return c->fail(-1, "rdm_ddim_inpaint: give a seed or a q_noise stack, not both");
+    if (!a || !x_latent || !x0 || !mask || (!q_noise && !ns.seeded) || !cond || !z_out) return c->fail(-1, "null argument");
     if (t_start < 1) return c->fail(-1, "ddim inpaint: t_start must be at least 1, got %d", t_start);
     const InpaintSource ip{x0, mask, mask_channels, q_noise};
-    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_stack(noise), z_out, x_inter, pred_x0_inter, &ip);
-}
-int rdm_ddim_inpaint_seeded(rdm_ctx* c, const rdm_ddim_args* a, int t_start, uint64_t seed, int64_t row0, const float* x_latent, const float* x0,
-                            const float* mask, int mask_channels, const float* cond, const float* uncond, float* z_out, float* x_inter,
-                            float* pred_x0_inter) {
-    RDM_ENTER(c);
-    if (!c || !a || !x_latent || !x0 || !mask || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    if (t_start < 1) return c->fail(-1, "ddim inpaint: t_start must be at least 1, got %d", t_start);
-    const InpaintSource ip{x0, mask, mask_channels, nullptr};
-    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, NoiseSource::from_seed(seed, row0), z_out, x_inter, pred_x0_inter, &ip);
+    return ddim_sample_impl(c, a, t_start, x_latent, cond, uncond, ns, z_out, x_inter, pred_x0_inter, &ip);
 }
 
 // Deterministic DDIM inversion (rdm_ddim_encode's header comment): t_enc steps UP the schedule, step i from level a_prev[i] to a_t[i] with
@@ -433,7 +422,7 @@ static DpmppCoefficients dpmpp_coefficients(const SolverNode& s, const SolverNod
     return k;
 }
 
-// The loop of rdm_dpmpp_sample (sde false: the ODE step, no noise) and of the two rdm_dpmpp_sde_sample entries (z_j is row j of ns.stack, or
+// The loop of rdm_dpmpp_sample (sde false: the ODE step, no noise) and of rdm_dpmpp_sde_sample (z_j is row j of ns.stack, or
 // drawn in the step kernel at step counter j, and a null x_T is drawn): one forward and one step-kernel launch per step.  The history is
 // ONE buffer: the kernel reads m_{j-1} from it and writes m_j to it in the same pass.  who: the solver's name in the messages.
 static int dpmpp_sample_impl(rdm_ctx* c, const rdm_dpmpp_args* a, bool sde, const char* who, const NoiseSource& ns, const float* x_T,
@@ -463,8 +452,9 @@ static int dpmpp_sample_impl(rdm_ctx* c, const rdm_dpmpp_args* a, bool sde, cons
         p.c_x = (float)k.c_x; p.c_0 = (float)k.c_0; p.c_1 = (float)k.c_1; p.c_n = (float)k.c_n;
         p.m_prev = second ? m_slot : nullptr; p.noise = ns.stack ? ns.stack + (size_t)j * run.n1 : nullptr;
         p.x_out = run.x; p.x_dup = run.x_dup; p.m_store = m_slot; p.pred_x0 = run.pred_x0_slot(j);
-        if (ns.seeded) RDM_TRY(seeded_launched(c, who, launch_dpmpp_sde_step_seeded(p, run.step_rng(ns.seed, j), c->stream)));   // the noise of loop step j, in registers
-        else RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
+        const StepRngParams g = run.step_rng(ns.seed, j);         // seeded: the noise of loop step j, in registers
+        if (ns.seeded) RDM_TRY(seeded_launched(c, who, launch_dpmpp_step(p, &g, c->stream)));
+        else RDM_CHECK_HIP(c, launch_dpmpp_step(p, nullptr, c->stream));
         h_prev = h;
         RDM_TRY(run.log_x(j));
     }
@@ -476,17 +466,13 @@ int rdm_dpmpp_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, cons
     if (!c || !a || !x_T || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
     return dpmpp_sample_impl(c, a, false, "dpm-solver++", NoiseSource{}, x_T, cond, uncond, z_out, x_inter, pred_x0_inter);
 }
-int rdm_dpmpp_sde_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond, const float* noise,
+int rdm_dpmpp_sde_sample(rdm_ctx* c, const rdm_dpmpp_args* a, const float* x_T, const float* cond, const float* uncond, const rdm_noise* noise,
                          float* z_out, float* x_inter, float* pred_x0_inter) {
     RDM_ENTER(c);
-    if (!c || !a || !x_T || !cond || !noise || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
-    return dpmpp_sample_impl(c, a, true, "sde-dpm-solver++", NoiseSource::from_stack(noise), x_T, cond, uncond, z_out, x_inter, pred_x0_inter);
-}
-int rdm_dpmpp_sde_sample_seeded(rdm_ctx* c, const rdm_dpmpp_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond,
-                                const float* uncond, float* z_out, float* x_inter, float* pred_x0_inter) {
-    RDM_ENTER(c);
-    if (!c || !a || !cond || !z_out || !a->alphas_cumprod || !a->nodes) return c ? c->fail(-1, "null argument") : -1;
-    return dpmpp_sample_impl(c, a, true, "sde-dpm-solver++", NoiseSource::from_seed(seed, row0), x_T, cond, uncond, z_out, x_inter, pred_x0_inter);
+    NoiseSource ns;
+    RDM_TRY(noise_source(c, "rdm_dpmpp_sde_sample", noise, &ns));
+    if (!a || (!x_T && !ns.seeded) || !cond || ns.none() || !z_out || !a->alphas_cumprod || !a->nodes) return c->fail(-1, "null argument");
+    return dpmpp_sample_impl(c, a, true, "sde-dpm-solver++", ns, x_T, cond, uncond, z_out, x_inter, pred_x0_inter);
 }
 
 // UniPC (Zhao et al. 2023, "UniPC: A Unified Predictor-Corrector Framework for Fast Sampling of Diffusion Models"), data prediction,
@@ -642,8 +628,8 @@ int rdm_unipc_sample(rdm_ctx* c, const rdm_unipc_args* a, const float* x_T, cons
     return run.finish(z_out);
 }
 
-// The ancestral loop of rdm_ddpm_sample (the noise stack ns.stack) and rdm_ddpm_sample_seeded (generated in the step kernel; a null x_T is
-// drawn).  The final step (i == 0) consumes no noise either way.
+// The ancestral loop of rdm_ddpm_sample (the noise stack ns.stack, or, seeded, generated in the step kernel; a null x_T is drawn).  The
+// final step (i == 0) consumes no noise either way.
 static int ddpm_sample_impl(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const NoiseSource& ns, float* z_out) {
     if (!c->unet.loaded) return c->fail(-1, "unet weights not loaded");
     if (a->timesteps < 1 || a->timesteps > a->T) return c->fail(-1, "bad timesteps");
@@ -661,21 +647,18 @@ static int ddpm_sample_impl(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T
         p.sqrt_recip = a->sqrt_recip_alphas_cumprod[i]; p.sqrt_recipm1 = a->sqrt_recipm1_alphas_cumprod[i];
         p.coef1 = a->posterior_mean_coef1[i]; p.coef2 = a->posterior_mean_coef2[i]; p.log_var = a->posterior_log_variance_clipped[i];
         p.clip = a->clip_denoised; p.nonzero = (i != 0); p.temperature = a->temperature;
-        if (ns.seeded && p.nonzero) RDM_CHECK_HIP(c, launch_ddpm_step_seeded(p, run.step_rng(ns.seed, n), c->stream));      // the noise of loop step n, in registers
-        else RDM_CHECK_HIP(c, launch_ddpm_step(p, c->stream));
+        const StepRngParams g = run.step_rng(ns.seed, n);         // seeded: the noise of loop step n, in registers
+        RDM_CHECK_HIP(c, launch_ddpm_step(p, ns.seeded && p.nonzero ? &g : nullptr, c->stream));
     }
     return run.finish(z_out);
 }
-int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const float* noise,
+int rdm_ddpm_sample(rdm_ctx* c, const rdm_ddpm_args* a, const float* x_T, const float* cond, const rdm_noise* noise,
                     float* z_out) {
     RDM_ENTER(c);
-    if (!c || !a || !x_T || !cond || !noise || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    return ddpm_sample_impl(c, a, x_T, cond, NoiseSource::from_stack(noise), z_out);
-}
-int rdm_ddpm_sample_seeded(rdm_ctx* c, const rdm_ddpm_args* a, uint64_t seed, int64_t row0, const float* x_T, const float* cond, float* z_out) {
-    RDM_ENTER(c);
-    if (!c || !a || !cond || !z_out) return c ? c->fail(-1, "null argument") : -1;
-    return ddpm_sample_impl(c, a, x_T, cond, NoiseSource::from_seed(seed, row0), z_out);
+    NoiseSource ns;
+    RDM_TRY(noise_source(c, "rdm_ddpm_sample", noise, &ns));
+    if (!a || (!x_T && !ns.seeded) || !cond || ns.none() || !z_out) return c->fail(-1, "null argument");
+    return ddpm_sample_impl(c, a, x_T, cond, ns, z_out);
 }
 
 // ---- device noise: the generator alone (philox.h)
@@ -761,59 +744,58 @@ static int masked_blend_fill(rdm_ctx* c, const char* who, MaskedBlendParams& p, 
     p.hw = (long long)H * W; p.chw = p.hw * C; p.n = p.chw * B; p.mask_channels = mask_channels; p.sqrt_a = sqrt_a; p.sqrt_1ma = sqrt_1ma;
     return 0;
 }
-int rdm_op_masked_blend(rdm_ctx* c, const float* x, const float* x0, const float* mask, const float* z, int64_t B, int C, int H, int W,
+int rdm_op_masked_blend(rdm_ctx* c, const float* x, const float* x0, const float* mask, const rdm_noise* z, int64_t B, int C, int H, int W,
                         int mask_channels, float sqrt_a, float sqrt_1ma, float* out, float* x_dup) {
     RDM_ENTER(c);
-    if (!c) return -1;
+    NoiseSource ns;
+    RDM_TRY(noise_source(c, "rdm_op_masked_blend", z, &ns));
     MaskedBlendParams p{};
     RDM_TRY(masked_blend_fill(c, "rdm_op_masked_blend", p, x, x0, mask, B, C, H, W, mask_channels, sqrt_a, sqrt_1ma, out, x_dup));
-    p.z = z;
-    RDM_CHECK_HIP(c, launch_masked_blend(p, c->stream));
-    return 0;
-}
-int rdm_op_masked_blend_seeded(rdm_ctx* c, const float* x, const float* x0, const float* mask, int64_t B, int C, int H, int W, int mask_channels,
-                               float sqrt_a, float sqrt_1ma, uint64_t seed, int64_t row0, uint32_t step, float* out, float* x_dup) {
-    RDM_ENTER(c);
-    if (!c) return -1;
-    MaskedBlendParams p{};
-    RDM_TRY(masked_blend_fill(c, "rdm_op_masked_blend_seeded", p, x, x0, mask, B, C, H, W, mask_channels, sqrt_a, sqrt_1ma, out, x_dup));
-    RDM_TRY(check_noise_rows(c, "rdm_op_masked_blend_seeded", row0, B, p.chw));
-    const hipError_t e = launch_masked_blend_seeded(p, StepRngParams{seed, p.chw, (uint32_t)row0, step}, c->stream);
-    if (e == hipErrorInvalidValue)
-        return c->fail(-1, "rdm_op_masked_blend_seeded: C * H * W must be a multiple of 4, and x, x0, out, x_dup 16-byte aligned");
+    p.z = ns.stack;
+    StepRngParams g{};
+    if (ns.seeded) {
+        RDM_TRY(check_noise_rows(c, "rdm_op_masked_blend (seeded)", z->row0, B, p.chw));
+        g = {z->seed, p.chw, (uint32_t)z->row0, z->step};
+    }
+    const hipError_t e = launch_masked_blend(p, ns.seeded ? &g : nullptr, c->stream);
+    if (ns.seeded && e == hipErrorInvalidValue)
+        return c->fail(-1, "rdm_op_masked_blend (seeded): C * H * W must be a multiple of 4, and x, x0, out, x_dup 16-byte aligned");
     RDM_CHECK_HIP(c, e);
     return 0;
 }
 
 // ---- the DDIM, PLMS and DDPM step kernels alone: the kernels' own scalars, as the loops above fill them
+// The noise of a step op entry `who`: ns from its rdm_noise argument and, seeded, the row check of n / per_row rows and the kernel's counters in *g
+static int op_step_noise(rdm_ctx* c, const char* who, const rdm_noise* noise, long long n, NoiseSource* ns, StepRngParams* g) {
+    RDM_TRY(noise_source(c, who, noise, ns));
+    if (!ns->seeded) return 0;
+    const std::string w = std::string(who) + " (seeded)";
+    RDM_TRY(check_noise_rows(c, w.c_str(), noise->row0, noise->per_row >= 1 ? n / noise->per_row : 0, noise->per_row));
+    *g = {noise->seed, noise->per_row, (uint32_t)noise->row0, noise->step};
+    return 0;
+}
+// ... and its launch: what a seeded step kernel, which has no scalar form, asks of the call's shape
+static int op_step_launched(rdm_ctx* c, const char* who, const NoiseSource& ns, hipError_t e) {
+    if (ns.seeded && e == hipErrorInvalidValue)
+        return c->fail(-1, "%s (seeded): per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned", who);
+    RDM_CHECK_HIP(c, e);
+    return 0;
+}
 static void ddim_step_fill(DdimStepParams& p, const float* x, const float* eps, long long n, int cfg, float scale, float a_t, float a_prev,
                            float sigma_t, float sqrt_one_minus_at, float temperature, float* x_prev, float* x_dup, float* pred_x0) {
     p.x = x; p.eps = eps; p.x_prev = x_prev; p.x_dup = x_dup; p.pred_x0 = pred_x0; p.n_per_batch = n; p.cfg = cfg ? 1 : 0; p.scale = scale;
     p.a_t = a_t; p.a_prev = a_prev; p.sigma_t = sigma_t; p.sqrt_one_minus_at = sqrt_one_minus_at; p.temperature = temperature;
 }
-int rdm_op_ddim_step(rdm_ctx* c, const float* x, const float* eps, const float* noise, long long n, int cfg, float scale, float a_t,
+int rdm_op_ddim_step(rdm_ctx* c, const float* x, const float* eps, const rdm_noise* noise, long long n, int cfg, float scale, float a_t,
                      float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, float* x_prev, float* x_dup, float* pred_x0) {
     RDM_ENTER(c);
     if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddim_step: bad argument");
+    NoiseSource ns; StepRngParams g{};
+    RDM_TRY(op_step_noise(c, "rdm_op_ddim_step", noise, n, &ns, &g));
     DdimStepParams p{};
     ddim_step_fill(p, x, eps, n, cfg, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature, x_prev, x_dup, pred_x0);
-    p.noise = noise;
-    RDM_CHECK_HIP(c, launch_ddim_step(p, c->stream));
-    return 0;
-}
-int rdm_op_ddim_step_seeded(rdm_ctx* c, const float* x, const float* eps, long long n, int64_t per_row, int cfg, float scale, float a_t,
-                            float a_prev, float sigma_t, float sqrt_one_minus_at, float temperature, uint64_t seed, int64_t row0, uint32_t step,
-                            float* x_prev, float* x_dup, float* pred_x0) {
-    RDM_ENTER(c);
-    if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddim_step_seeded: bad argument");
-    RDM_TRY(check_noise_rows(c, "rdm_op_ddim_step_seeded", row0, per_row >= 1 ? n / per_row : 0, per_row));
-    DdimStepParams p{};
-    ddim_step_fill(p, x, eps, n, cfg, scale, a_t, a_prev, sigma_t, sqrt_one_minus_at, temperature, x_prev, x_dup, pred_x0);
-    const hipError_t e = launch_ddim_step_seeded(p, StepRngParams{seed, per_row, (uint32_t)row0, step}, c->stream);
-    if (e == hipErrorInvalidValue)
-        return c->fail(-1, "rdm_op_ddim_step_seeded: per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned");
-    RDM_CHECK_HIP(c, e);
-    return 0;
+    p.noise = ns.stack;
+    return op_step_launched(c, "rdm_op_ddim_step", ns, launch_ddim_step(p, ns.seeded ? &g : nullptr, c->stream));
 }
 
 int rdm_op_plms_step(rdm_ctx* c, const float* x, const float* eps, const float* e_prev, const float* h1, const float* h2, const float* h3,
@@ -840,30 +822,17 @@ static void ddpm_step_fill(DdpmStepParams& p, const float* x, const float* eps, 
     p.x = x; p.eps = eps; p.x_prev = x_prev; p.n = n; p.sqrt_recip = sqrt_recip; p.sqrt_recipm1 = sqrt_recipm1; p.coef1 = coef1; p.coef2 = coef2;
     p.log_var = log_var; p.clip = clip ? 1 : 0; p.nonzero = nonzero ? 1 : 0; p.temperature = temperature;
 }
-int rdm_op_ddpm_step(rdm_ctx* c, const float* x, const float* eps, const float* noise, long long n, float sqrt_recip, float sqrt_recipm1,
+int rdm_op_ddpm_step(rdm_ctx* c, const float* x, const float* eps, const rdm_noise* noise, long long n, float sqrt_recip, float sqrt_recipm1,
                      float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, float* x_prev) {
     RDM_ENTER(c);
     if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddpm_step: bad argument");
-    if (nonzero && !noise) return c->fail(-1, "rdm_op_ddpm_step: nonzero needs a noise operand (or the seeded entry)");
+    NoiseSource ns; StepRngParams g{};
+    RDM_TRY(op_step_noise(c, "rdm_op_ddpm_step", noise, n, &ns, &g));
+    if (nonzero && ns.none()) return c->fail(-1, "rdm_op_ddpm_step: nonzero needs a noise operand (a stack or a seed)");
     DdpmStepParams p{};
     ddpm_step_fill(p, x, eps, n, sqrt_recip, sqrt_recipm1, coef1, coef2, log_var, clip, nonzero, temperature, x_prev);
-    p.noise = noise;
-    RDM_CHECK_HIP(c, launch_ddpm_step(p, c->stream));
-    return 0;
-}
-int rdm_op_ddpm_step_seeded(rdm_ctx* c, const float* x, const float* eps, long long n, int64_t per_row, float sqrt_recip, float sqrt_recipm1,
-                            float coef1, float coef2, float log_var, int clip, int nonzero, float temperature, uint64_t seed, int64_t row0,
-                            uint32_t step, float* x_prev) {
-    RDM_ENTER(c);
-    if (!x || !eps || !x_prev || n < 1) return c->fail(-1, "rdm_op_ddpm_step_seeded: bad argument");
-    RDM_TRY(check_noise_rows(c, "rdm_op_ddpm_step_seeded", row0, per_row >= 1 ? n / per_row : 0, per_row));
-    DdpmStepParams p{};
-    ddpm_step_fill(p, x, eps, n, sqrt_recip, sqrt_recipm1, coef1, coef2, log_var, clip, nonzero, temperature, x_prev);
-    const hipError_t e = launch_ddpm_step_seeded(p, StepRngParams{seed, per_row, (uint32_t)row0, step}, c->stream);
-    if (e == hipErrorInvalidValue)
-        return c->fail(-1, "rdm_op_ddpm_step_seeded: per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned");
-    RDM_CHECK_HIP(c, e);
-    return 0;
+    p.noise = ns.stack;
+    return op_step_launched(c, "rdm_op_ddpm_step", ns, launch_ddpm_step(p, ns.seeded ? &g : nullptr, c->stream));
 }
 
 // ---- the DPM-Solver++ and UniPC step kernels alone
@@ -880,32 +849,20 @@ int rdm_op_dpmpp_step(rdm_ctx* c, const float* x, const float* eps, const float*
     if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_step: bad argument");
     DpmppStepParams p{};
     dpmpp_step_fill(p, x, eps, m_prev, nullptr, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, 0.f, x_out, x_dup, m_store, pred_x0);
-    RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
+    RDM_CHECK_HIP(c, launch_dpmpp_step(p, nullptr, c->stream));
     return 0;
 }
-int rdm_op_dpmpp_sde_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, const float* noise, long long n, int cfg, float scale,
-                          float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out, float* x_dup,
+int rdm_op_dpmpp_sde_step(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, const rdm_noise* noise, long long n, int cfg,
+                          float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, float* x_out, float* x_dup,
                           float* m_store, float* pred_x0) {
     RDM_ENTER(c);
-    if (!x || !eps || !noise || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_sde_step: bad argument");
+    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_sde_step: bad argument");
+    NoiseSource ns; StepRngParams g{};
+    RDM_TRY(op_step_noise(c, "rdm_op_dpmpp_sde_step", noise, n, &ns, &g));
+    if (ns.none()) return c->fail(-1, "rdm_op_dpmpp_sde_step: bad argument");
     DpmppStepParams p{};
-    dpmpp_step_fill(p, x, eps, m_prev, noise, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
-    RDM_CHECK_HIP(c, launch_dpmpp_step(p, c->stream));
-    return 0;
-}
-int rdm_op_dpmpp_sde_step_seeded(rdm_ctx* c, const float* x, const float* eps, const float* m_prev, long long n, int64_t per_row, int cfg,
-                                 float scale, float sqrt_a_s, float sqrt_one_minus_a_s, float c_x, float c_0, float c_1, float c_n, uint64_t seed,
-                                 int64_t row0, uint32_t step, float* x_out, float* x_dup, float* m_store, float* pred_x0) {
-    RDM_ENTER(c);
-    if (!x || !eps || !x_out || n < 1) return c->fail(-1, "rdm_op_dpmpp_sde_step_seeded: bad argument");
-    RDM_TRY(check_noise_rows(c, "rdm_op_dpmpp_sde_step_seeded", row0, per_row >= 1 ? n / per_row : 0, per_row));
-    DpmppStepParams p{};
-    dpmpp_step_fill(p, x, eps, m_prev, nullptr, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
-    const hipError_t e = launch_dpmpp_sde_step_seeded(p, StepRngParams{seed, per_row, (uint32_t)row0, step}, c->stream);
-    if (e == hipErrorInvalidValue)
-        return c->fail(-1, "rdm_op_dpmpp_sde_step_seeded: per_row must be a multiple of 4 that divides n, and every operand 16-byte aligned");
-    RDM_CHECK_HIP(c, e);
-    return 0;
+    dpmpp_step_fill(p, x, eps, m_prev, ns.stack, n, cfg, scale, sqrt_a_s, sqrt_one_minus_a_s, c_x, c_0, c_1, c_n, x_out, x_dup, m_store, pred_x0);
+    return op_step_launched(c, "rdm_op_dpmpp_sde_step", ns, launch_dpmpp_step(p, ns.seeded ? &g : nullptr, c->stream));
 }
 int rdm_op_unipc_step(rdm_ctx* c, const float* u, const float* eps, const float* xc_prev, const float* h1, const float* h2, const float* h3,
                       long long n, int cfg, float scale, const double* coefficients, float* xc_out, float* u_next, float* x_dup,

@@ -181,7 +181,7 @@ class DPMSolverSDESampler(_NodeListSampler):
     `noise=` (a [steps, B, C, H, W] stack), from the library's counter-based generator under `noise_seed` / `noise_row0` (stream 1, step j,
     rows noise_row0 .. -- generated in the step kernel, no stack exists, and a row's sample does not depend on how a batch is sharded; the
     starting latent, when no x_T is given, is the library's too), or else from torch's generator the way DDIMSampler draws its stack for
-    eta > 0.  The loop runs inside librdm_hip (rdm_dpmpp_sde_sample / rdm_dpmpp_sde_sample_seeded); the per-step options of
+    eta > 0.  The loop runs inside librdm_hip (rdm_dpmpp_sde_sample); the per-step options of
     DPMSolverSampler take the per-step path here too."""
     NAME = "SDE-DPM-Solver++"
 

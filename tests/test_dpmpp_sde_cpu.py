@@ -317,14 +317,15 @@ def test_dpmpp_sde_symbols_in_header_and_library():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rdm_hip.h")).read(), flags=re.S)
     import rdm_amd  # noqa: F401
     from rdm_amd import _lib
-    n_args = {"rdm_dpmpp_sde_sample": 9, "rdm_dpmpp_sde_sample_seeded": 10, "rdm_op_dpmpp_sde_step": 18, "rdm_op_dpmpp_sde_step_seeded": 21}
+    n_args = {"rdm_dpmpp_sde_sample": 9, "rdm_op_dpmpp_sde_step": 18}
     for name, n in n_args.items():
         decl = re.search(r"int\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
         assert decl is not None, name
         assert len(decl.group(1).split(",")) == n == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(_lib.lib, name)
-    for name in ("rdm_dpmpp_sde_sample", "rdm_dpmpp_sde_sample_seeded"):
-        assert re.search(r"int\s+" + name + r"\s*\(\s*rdm_ctx\*\s*\w+,\s*const rdm_dpmpp_args\*", src)
+    for name in ("rdm_dpmpp_sde_sample_seeded", "rdm_op_dpmpp_sde_step_seeded"):      # the twins the one rdm_noise argument replaced
+        assert not re.search(r"\b" + name + r"\b", src) and name not in _lib.SIGNATURES, name
+    assert re.search(r"int\s+rdm_dpmpp_sde_sample\s*\(\s*rdm_ctx\*\s*\w+,\s*const rdm_dpmpp_args\*", src)
     assert hasattr(_lib.Context, "dpmpp_sde_sample") and hasattr(_lib.Context, "op_dpmpp_sde_step")
     # rdm_dpmpp_args is the ODE solver's, field for field
     assert [f[0] for f in _lib.DpmppArgs._fields_] == ["batch", "k", "channels", "height", "width", "unconditional_guidance_scale", "order",

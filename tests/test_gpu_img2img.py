@@ -1,4 +1,4 @@
-"""Native DDIM image-to-image on the GPU (rdm_ddim_decode / rdm_ddim_decode_seeded / rdm_ddim_encode, the inversion step kernel, the
+"""Native DDIM image-to-image on the GPU (rdm_ddim_decode, stack and seeded, / rdm_ddim_encode, the inversion step kernel, the
 seeded forward process): the two kernels per element against float64, decode against the DDIM loop bit for bit, the tail property,
 every inversion step rebuilt on the GPU, DDIMSampler.encode / decode against the per-step path and the CPU oracle UNet, the end-to-end
 entry, errors, and one script run.  tests/_img2img_ref.py is the restatement."""
@@ -455,12 +455,13 @@ def _errors_leave_the_context_usable(ctx, x, c, uc, noise):
         ctx._check(fn(ctx._h, C.byref(a), *args, _lib._ptr(z), None, *([None] if fn is not _lib.lib.rdm_ddim_encode else [])))
 
     P = _lib._ptr
+    seeded = lambda seed, row0: C.byref(_lib.Noise(seeded=1, seed=seed, row0=row0))       # a filled rdm_noise
     bad_calls = {
         "t_start = 0": lambda: ctx.ddim_decode(4, 0, x, c, None, ACP),
         "t_start = total + 1": lambda: ctx.ddim_decode(4, total + 1, x, c, None, ACP),
         "t_start = 0 at the C ABI": lambda: raw(_lib.lib.rdm_ddim_decode, 0, P(x), P(c), None, None),
         "t_start = total + 1 at the C ABI": lambda: raw(_lib.lib.rdm_ddim_decode, total + 1, P(x), P(c), None, None),
-        "seeded t_start = total + 1 at the C ABI": lambda: raw(_lib.lib.rdm_ddim_decode_seeded, total + 1, 5, 0, P(x), P(c), None),
+        "seeded t_start = total + 1 at the C ABI": lambda: raw(_lib.lib.rdm_ddim_decode, total + 1, P(x), P(c), None, seeded(5, 0)),
         "t_enc = 0": lambda: ctx.ddim_encode(4, 0, x, c, None, ACP),
         "t_enc = total + 1": lambda: ctx.ddim_encode(4, total + 1, x, c, None, ACP),
         "t_enc = total + 1 at the C ABI": lambda: raw(_lib.lib.rdm_ddim_encode, total + 1, P(x), P(c), None),

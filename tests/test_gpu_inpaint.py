@@ -1,4 +1,4 @@
-"""Native DDIM inpainting on the GPU (masked_blend_kernel / masked_blend_seeded_kernel, rdm_ddim_inpaint / rdm_ddim_inpaint_seeded,
+"""Native DDIM inpainting on the GPU (masked_blend_kernel / masked_blend_seeded_kernel, rdm_ddim_inpaint with stacks and seeded,
 DDIMSampler.decode(mask=), sample_log(inpaint_mask=), rdm_sample.py --mask): the blend per element against float64 and bit for bit
 against its six fp32 operations, the seeded blend against the stack blend, the loop against the same loop rebuilt from op entries, the
 identities (an all-zero mask is decode; the oracle's loop; the per-step path), the seeded loop against the stack loop and its
@@ -263,7 +263,7 @@ def _stacks(ctx, seed, B, steps, per_row, shape, row0=0):
 
 @pytest.mark.parametrize("scale", [2.0, 1.0], ids=["cfg2", "unguided"])
 def test_seeded_inpaint_loop_equals_the_stack_loop_and_does_not_depend_on_the_sharding(tiny, scale):
-    """eta 1, deterministic mode (batch-invariant, as test_gpu_device_noise.py compares shards): rdm_ddim_inpaint_seeded against the stack
+    """eta 1, deterministic mode (batch-invariant, as test_gpu_device_noise.py compares shards): the seeded rdm_ddim_inpaint against the stack
     loop fed with op_randn's outputs -- stream 1 / step i for the update, stream 0 / step i + 1 for the known region; B = 4 in one call
     against two shards of 2 with row0."""
     ctx, _, _ = tiny
@@ -361,8 +361,8 @@ def test_errors_leave_the_context_usable(tiny, model):
         z = torch.empty_like(x)
         ctx._check(fn(ctx._h, C.byref(a), *args, P(z), None, None))
 
-    inp, inp_s, blend, blend_s = (_lib.lib.rdm_ddim_inpaint, _lib.lib.rdm_ddim_inpaint_seeded, _lib.lib.rdm_op_masked_blend,
-                                  _lib.lib.rdm_op_masked_blend_seeded)
+    inp, blend = _lib.lib.rdm_ddim_inpaint, _lib.lib.rdm_op_masked_blend
+    seeded = lambda seed, row0, stack=None, step=0: C.byref(_lib.Noise(stack=P(stack), seeded=1, seed=seed, row0=row0, step=step))     # a filled rdm_noise
     o = torch.empty_like(x)
     odd = torch.zeros(2, 3, 5, 7, device=ctx.device)
     buf = torch.zeros(x.numel() + 4, device=ctx.device)
@@ -371,14 +371,16 @@ def test_errors_leave_the_context_usable(tiny, model):
         "a null x0 at the C ABI": lambda: raw(inp, 2, P(x), None, P(mask), 1, P(c), None, None, P(qn)),
         "a null mask at the C ABI": lambda: raw(inp, 2, P(x), P(x0), None, 1, P(c), None, None, P(qn)),
         "a null q_noise at the C ABI": lambda: raw(inp, 2, P(x), P(x0), P(mask), 1, P(c), None, None, None),
-        "a null x0 at the seeded C ABI": lambda: raw(inp_s, 2, 5, 0, P(x), None, P(mask), 1, P(c), None),
+        "a null x0 at the seeded C ABI": lambda: raw(inp, 2, P(x), None, P(mask), 1, P(c), None, seeded(5, 0), None),
         "mask_channels = 2 at the C ABI": lambda: raw(inp, 2, P(x), P(x0), P(mask), 2, P(c), None, None, P(qn)),
-        "mask_channels = 0 at the seeded C ABI": lambda: raw(inp_s, 2, 5, 0, P(x), P(x0), P(mask), 0, P(c), None),
+        "mask_channels = 0 at the seeded C ABI": lambda: raw(inp, 2, P(x), P(x0), P(mask), 0, P(c), None, seeded(5, 0), None),
         "t_start = 0 at the C ABI": lambda: raw(inp, 0, P(x), P(x0), P(mask), 1, P(c), None, None, P(qn)),
         "t_start = total + 1 at the C ABI": lambda: raw(inp, total + 1, P(x), P(x0), P(mask), 1, P(c), None, None, P(qn)),
-        "seeded t_start = total + 1 at the C ABI": lambda: raw(inp_s, total + 1, 5, 0, P(x), P(x0), P(mask), 1, P(c), None),
-        "a misaligned x0 in the seeded loop": lambda: raw(inp_s, 2, 5, 0, P(x), P(off), P(mask), 1, P(c), None),
-        "row0 beyond 32 bits in the seeded loop": lambda: raw(inp_s, 2, 5, 2 ** 32 - 1, P(x), P(x0), P(mask), 1, P(c), None),
+        "seeded t_start = total + 1 at the C ABI": lambda: raw(inp, total + 1, P(x), P(x0), P(mask), 1, P(c), None, seeded(5, 0), None),
+        "a misaligned x0 in the seeded loop": lambda: raw(inp, 2, P(x), P(off), P(mask), 1, P(c), None, seeded(5, 0), None),
+        "row0 beyond 32 bits in the seeded loop": lambda: raw(inp, 2, P(x), P(x0), P(mask), 1, P(c), None, seeded(5, 2 ** 32 - 1), None),
+        "a seed with a noise stack at the C ABI": lambda: raw(inp, 2, P(x), P(x0), P(mask), 1, P(c), None, seeded(5, 0, stack=qn), None),
+        "a seed with a q_noise stack at the C ABI": lambda: raw(inp, 2, P(x), P(x0), P(mask), 1, P(c), None, seeded(5, 0), P(qn)),
         "t_start = 0": lambda: ctx.ddim_inpaint(4, 0, x, x0, mask, c, None, ACP, q_noise=qn),
         "t_start = total + 1": lambda: ctx.ddim_inpaint(4, total + 1, x, x0, mask, c, None, ACP, q_noise=qn),
         "no q_noise and no seed": lambda: ctx.ddim_inpaint(4, 2, x, x0, mask, c, None, ACP),
@@ -393,8 +395,8 @@ def test_errors_leave_the_context_usable(tiny, model):
         "blend: B = 0 at the C ABI": lambda: ctx._check(blend(ctx._h, P(x), P(x0), P(mask), None, 0, 3, 16, 16, 1, 1.0, 0.0, P(o), None)),
         "seeded blend: per_row % 4": lambda: ctx.op_masked_blend(odd, odd, odd[:, :1].contiguous(), None, SA, S1M, seed=1),
         "seeded blend: a misaligned out": lambda: ctx.op_masked_blend(x, x0, mask, None, SA, S1M, out=off, seed=1),
-        "seeded blend: row0 beyond 32 bits at the C ABI": lambda: ctx._check(blend_s(ctx._h, P(x), P(x0), P(mask), 2, 3, 16, 16, 1, 1.0, 0.0, 1,
-                                                                                   2 ** 32 - 1, 1, P(o), None)),
+        "seeded blend: row0 beyond 32 bits at the C ABI": lambda: ctx._check(blend(ctx._h, P(x), P(x0), P(mask), seeded(1, 2 ** 32 - 1, step=1),
+                                                                                 2, 3, 16, 16, 1, 1.0, 0.0, P(o), None)),
         "seeded blend with a z operand": lambda: ctx.op_masked_blend(x, x0, mask, x0, SA, S1M, seed=1),
         "blend: a mask of another plane": lambda: ctx.op_masked_blend(x, x0, mask[:, :, :8].contiguous(), None, SA, S1M),
     }

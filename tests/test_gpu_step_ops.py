@@ -1,9 +1,10 @@
-"""The DDIM, PLMS and DDPM step kernels (csrc/sampler_steps.hip) alone, through rdm_op_ddim_step / rdm_op_plms_step / rdm_op_ddpm_step and the two
-seeded entries: every element of every output against the float64 restatements of tests/_step_ref.py within the bounds derived there
+"""The DDIM, PLMS and DDPM step kernels (csrc/sampler_steps.hip) alone, through rdm_op_ddim_step / rdm_op_plms_step / rdm_op_ddpm_step, stack
+and seeded: every element of every output against the float64 restatements of tests/_step_ref.py within the bounds derived there
 (scalar tail, float4 path, a misaligned operand, the second trip of each kernel's stride loop, aliased outputs, every optional output),
 into sentinel-guarded buffers; the seeded forms bit for bit against the unseeded ones fed rdm_op_randn's output; every refusal; the
 device expf behind DDPM's sd; and the host wiring of the three loops: each logged step of the DDIM and PLMS loops, and a DDPM chain,
 rebuilt with the op entries from scalars the test computes itself, bit for bit in deterministic mode."""
+import ctypes as C
 import re
 
 import numpy as np
@@ -216,7 +217,7 @@ def test_step_op_refusals_leave_the_context_usable(ctx):
     """every refusal raises RdmError with its own message, leaves the output it was given as it was, and a following good call returns
     the bits it returned before"""
     from rdm_amd import _lib
-    from rdm_amd._lib import RdmError
+    from rdm_amd._lib import Noise, RdmError
     lib, P = _lib.lib, _lib._ptr
     d = ctx.device
     n, per_row = 48, 12
@@ -242,30 +243,35 @@ def test_step_op_refusals_leave_the_context_usable(ctx):
     o = torch.full((n,), SENTINEL, dtype=torch.int32, device=d).view(torch.float32)       # the output of every refused call: must stay as it is
     odd_before = odd.clone()
     ddim_raw = lambda x_, e_, o_, n_: ctx._check(lib.rdm_op_ddim_step(ctx._h, P(x_), P(e_), None, n_, 0, 1.0, a_t, a_prev, 0.0, s1m, 1.0, P(o_), None, None))
-    ddim_seeded_raw = lambda x_, e_, o_, n_, pr, row0: ctx._check(lib.rdm_op_ddim_step_seeded(ctx._h, P(x_), P(e_), n_, pr, 0, 1.0, a_t, a_prev, sigma_t, s1m,
-                                                                                          1.0, 1, row0, 0, P(o_), None, None))
+    seeded = lambda pr, row0, stack=None: C.byref(Noise(stack=P(stack), seeded=1, seed=1, row0=row0, per_row=pr, step=0))      # a filled rdm_noise
+    ddim_seeded_raw = lambda x_, e_, o_, n_, pr, row0, stack=None: ctx._check(lib.rdm_op_ddim_step(ctx._h, P(x_), P(e_), seeded(pr, row0, stack), n_, 0, 1.0, a_t,
+                                                                                                   a_prev, sigma_t, s1m, 1.0, P(o_), None, None))
     plms_raw = lambda x_, e_, o_, n_: ctx._check(lib.rdm_op_plms_step(ctx._h, P(x_), P(e_), None, None, None, None, n_, 0, 1.0, a_t, a_prev, s1m, 1, 0,
                                                                       P(o), P(o_), None, None))
-    ddpm_raw = lambda x_, e_, z_, o_, n_, nonzero=1: ctx._check(lib.rdm_op_ddpm_step(ctx._h, P(x_), P(e_), P(z_), n_, *dp, 1, nonzero, 1.0, P(o_)))
-    ddpm_seeded_raw = lambda x_, e_, o_, n_, pr, row0: ctx._check(lib.rdm_op_ddpm_step_seeded(ctx._h, P(x_), P(e_), n_, pr, *dp, 1, 1, 1.0, 1, row0, 0, P(o_)))
+    ddpm_raw = lambda x_, e_, z_, o_, n_, nonzero=1: ctx._check(lib.rdm_op_ddpm_step(ctx._h, P(x_), P(e_), C.byref(Noise(stack=P(z_))), n_, *dp, 1, nonzero, 1.0,
+                                                                                     P(o_)))
+    ddpm_seeded_raw = lambda x_, e_, o_, n_, pr, row0, stack=None: ctx._check(lib.rdm_op_ddpm_step(ctx._h, P(x_), P(e_), seeded(pr, row0, stack), n_, *dp, 1, 1,
+                                                                                                   1.0, P(o_)))
     plms = lambda mode, order, **kw: ctx.op_plms_step(x, eps2, True, 2.0, a_t, a_prev, s1m, mode, order, o, **kw)
     e = eps2[:n]
     # each case has one fault, and the message says which refusal fired
     ARG, SHAPE, ROWS, COUNT = "bad argument", "multiple of 4 that divides n, and every operand 16-byte aligned", "row0 + B must fit 32 bits", "B and per_row must be >= 1"
+    BOTH = "give a seed or a stack, not both"
     bad = [
         ("ddim: n = 0", "rdm_op_ddim_step: " + ARG, lambda: ddim_raw(x, e, o, 0)),
         ("ddim: null x", "rdm_op_ddim_step: " + ARG, lambda: ddim_raw(None, e, o, n)),
         ("ddim: null eps", "rdm_op_ddim_step: " + ARG, lambda: ddim_raw(x, None, o, n)),
         ("ddim: null x_prev", "rdm_op_ddim_step: " + ARG, lambda: ddim_raw(x, e, None, n)),
-        ("ddim seeded: n = -4", "rdm_op_ddim_step_seeded: " + ARG, lambda: ddim_seeded_raw(x, e, o, -4, per_row, 0)),
-        ("ddim seeded: null x_prev", "rdm_op_ddim_step_seeded: " + ARG, lambda: ddim_seeded_raw(x, e, None, n, per_row, 0)),
-        ("ddim seeded: per_row % 4", "rdm_op_ddim_step_seeded: per_row must be a " + SHAPE, lambda: ddim_seeded_raw(x, e, o, n, 6, 0)),
-        ("ddim seeded: n % per_row", "rdm_op_ddim_step_seeded: per_row must be a " + SHAPE, lambda: ddim_seeded_raw(x, e, o, 40, per_row, 0)),
-        ("ddim seeded: misaligned x", "rdm_op_ddim_step_seeded: per_row must be a " + SHAPE, lambda: ddim_seeded_raw(odd, e, o, n, per_row, 0)),
-        ("ddim seeded: misaligned x_prev", "rdm_op_ddim_step_seeded: per_row must be a " + SHAPE, lambda: ddim_seeded_raw(x, e, odd, n, per_row, 0)),
-        ("ddim seeded: per_row 0", "rdm_op_ddim_step_seeded: " + COUNT, lambda: ddim_seeded_raw(x, e, o, n, 0, 0)),
-        ("ddim seeded: row0 + B past 32 bits", "rdm_op_ddim_step_seeded: " + ROWS, lambda: ddim_seeded_raw(x, e, o, n, per_row, 2 ** 32 - n // per_row)),
-        ("ddim seeded: negative row0", "rdm_op_ddim_step_seeded: " + ROWS, lambda: ddim_seeded_raw(x, e, o, n, per_row, -1)),
+        ("ddim seeded: n = -4", "rdm_op_ddim_step: " + ARG, lambda: ddim_seeded_raw(x, e, o, -4, per_row, 0)),
+        ("ddim seeded: null x_prev", "rdm_op_ddim_step: " + ARG, lambda: ddim_seeded_raw(x, e, None, n, per_row, 0)),
+        ("ddim seeded: per_row % 4", "rdm_op_ddim_step (seeded): per_row must be a " + SHAPE, lambda: ddim_seeded_raw(x, e, o, n, 6, 0)),
+        ("ddim seeded: n % per_row", "rdm_op_ddim_step (seeded): per_row must be a " + SHAPE, lambda: ddim_seeded_raw(x, e, o, 40, per_row, 0)),
+        ("ddim seeded: misaligned x", "rdm_op_ddim_step (seeded): per_row must be a " + SHAPE, lambda: ddim_seeded_raw(odd, e, o, n, per_row, 0)),
+        ("ddim seeded: misaligned x_prev", "rdm_op_ddim_step (seeded): per_row must be a " + SHAPE, lambda: ddim_seeded_raw(x, e, odd, n, per_row, 0)),
+        ("ddim seeded: per_row 0", "rdm_op_ddim_step (seeded): " + COUNT, lambda: ddim_seeded_raw(x, e, o, n, 0, 0)),
+        ("ddim seeded: row0 + B past 32 bits", "rdm_op_ddim_step (seeded): " + ROWS, lambda: ddim_seeded_raw(x, e, o, n, per_row, 2 ** 32 - n // per_row)),
+        ("ddim seeded: negative row0", "rdm_op_ddim_step (seeded): " + ROWS, lambda: ddim_seeded_raw(x, e, o, n, per_row, -1)),
+        ("ddim seeded: with a stack", "rdm_op_ddim_step: " + BOTH, lambda: ddim_seeded_raw(x, e, o, n, per_row, 0, stack=nz)),
         ("plms: n = 0", "rdm_op_plms_step: " + ARG, lambda: plms_raw(x, e, o, 0)),
         ("plms: null x", "rdm_op_plms_step: " + ARG, lambda: plms_raw(None, e, o, n)),
         ("plms: null eps", "rdm_op_plms_step: " + ARG, lambda: plms_raw(x, None, o, n)),
@@ -286,12 +292,13 @@ def test_step_op_refusals_leave_the_context_usable(ctx):
         ("ddpm: null eps", "rdm_op_ddpm_step: " + ARG, lambda: ddpm_raw(x, None, nz, o, n)),
         ("ddpm: null x_prev", "rdm_op_ddpm_step: " + ARG, lambda: ddpm_raw(x, e, nz, None, n)),
         ("ddpm: nonzero with neither noise nor seed", "nonzero needs a noise operand", lambda: ctx.op_ddpm_step(x, e, None, *dp, True, True, 1.0, o)),
-        ("ddpm seeded: null x", "rdm_op_ddpm_step_seeded: " + ARG, lambda: ddpm_seeded_raw(None, e, o, n, per_row, 0)),
-        ("ddpm seeded: per_row % 4", "rdm_op_ddpm_step_seeded: per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, e, o, n, 6, 0)),
-        ("ddpm seeded: n % per_row", "rdm_op_ddpm_step_seeded: per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, e, o, 40, per_row, 0)),
-        ("ddpm seeded: misaligned eps", "rdm_op_ddpm_step_seeded: per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, odd, o, n, per_row, 0)),
-        ("ddpm seeded: misaligned x_prev", "rdm_op_ddpm_step_seeded: per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, e, odd, n, per_row, 0)),
-        ("ddpm seeded: row0 + B past 32 bits", "rdm_op_ddpm_step_seeded: " + ROWS, lambda: ddpm_seeded_raw(x, e, o, n, per_row, 2 ** 32 - n // per_row)),
+        ("ddpm seeded: null x", "rdm_op_ddpm_step: " + ARG, lambda: ddpm_seeded_raw(None, e, o, n, per_row, 0)),
+        ("ddpm seeded: per_row % 4", "rdm_op_ddpm_step (seeded): per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, e, o, n, 6, 0)),
+        ("ddpm seeded: n % per_row", "rdm_op_ddpm_step (seeded): per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, e, o, 40, per_row, 0)),
+        ("ddpm seeded: misaligned eps", "rdm_op_ddpm_step (seeded): per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, odd, o, n, per_row, 0)),
+        ("ddpm seeded: misaligned x_prev", "rdm_op_ddpm_step (seeded): per_row must be a " + SHAPE, lambda: ddpm_seeded_raw(x, e, odd, n, per_row, 0)),
+        ("ddpm seeded: row0 + B past 32 bits", "rdm_op_ddpm_step (seeded): " + ROWS, lambda: ddpm_seeded_raw(x, e, o, n, per_row, 2 ** 32 - n // per_row)),
+        ("ddpm seeded: with a stack", "rdm_op_ddpm_step: " + BOTH, lambda: ddpm_seeded_raw(x, e, o, n, per_row, 0, stack=nz)),
     ]
     for what, message, call in bad:
         with pytest.raises(RdmError, match=re.escape(message)):

@@ -487,17 +487,23 @@ def test_img2img_symbols_in_header_and_library():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rdm_hip.h")).read(), flags=re.S)
     import rdm_amd  # noqa: F401
     from rdm_amd import _lib
-    n_args = {"rdm_ddim_decode": 10, "rdm_ddim_decode_seeded": 11, "rdm_ddim_encode": 8, "rdm_op_ddim_inverse_step": 13, "rdm_op_q_sample_seeded": 9}
+    n_args = {"rdm_ddim_decode": 10, "rdm_ddim_encode": 8, "rdm_op_ddim_inverse_step": 13, "rdm_op_q_sample_seeded": 9}
     for name, n in n_args.items():
         decl = re.search(r"int\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
         assert decl is not None, name
         assert len(decl.group(1).split(",")) == n == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(_lib.lib, name)
         assert re.search(r"int\s+" + name + r"\s*\(\s*rdm_ctx\*", src)
-    for name in ("rdm_ddim_decode", "rdm_ddim_decode_seeded", "rdm_ddim_encode"):
+    for name in ("rdm_ddim_decode_seeded", "rdm_ddim_sample_seeded", "rdm_ddpm_sample_seeded"):      # the twins the one rdm_noise argument replaced
+        assert not re.search(r"\b" + name + r"\b", src) and name not in _lib.SIGNATURES, name
+    for name in ("rdm_ddim_decode", "rdm_ddim_encode"):
         assert re.search(r"int\s+" + name + r"\s*\(\s*rdm_ctx\*\s*\w+,\s*const rdm_ddim_args\*\s*\w+,\s*int\s+t_", src), name
     # rdm_ddim_args keeps its layout
     assert [f[0] for f in _lib.DdimArgs._fields_] == ["S", "batch", "k", "channels", "height", "width", "eta", "temperature",
                                                       "unconditional_guidance_scale", "log_every_t", "T", "alphas_cumprod"]
+    # rdm_noise: the binding's struct and the header's list the same fields in the same order
+    noise_fields = ["stack", "seeded", "seed", "row0", "per_row", "step"]
+    assert [f[0] for f in _lib.Noise._fields_] == noise_fields
+    assert re.findall(r"(\w+)\s*;", re.search(r"typedef struct rdm_noise\s*\{(.*?)\}\s*rdm_noise;", src, flags=re.S).group(1)) == noise_fields
     for m in ("ddim_decode", "ddim_encode", "op_ddim_inverse_step", "op_q_sample_seeded"):
         assert callable(getattr(_lib.Context, m))

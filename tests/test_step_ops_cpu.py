@@ -89,12 +89,14 @@ def test_step_op_symbols_in_header_and_library():
     src = re.sub(r"/\*.*?\*/", "", open(os.path.join(ROOT, "include", "rdm_hip.h")).read(), flags=re.S)
     import rdm_amd  # noqa: F401
     from rdm_amd import _lib
-    n_args = {"rdm_op_ddim_step": 15, "rdm_op_ddim_step_seeded": 18, "rdm_op_plms_step": 19, "rdm_op_ddpm_step": 14, "rdm_op_ddpm_step_seeded": 17}
+    n_args = {"rdm_op_ddim_step": 15, "rdm_op_plms_step": 19, "rdm_op_ddpm_step": 14}
     for name, n in n_args.items():
         decl = re.search(r"int\s+" + name + r"\s*\(([^)]*)\)\s*;", src)
         assert decl is not None, name
         assert len(decl.group(1).split(",")) == n == len(_lib.SIGNATURES[name][1]), name
         assert hasattr(_lib.lib, name)
+    for name in ("rdm_op_ddim_step_seeded", "rdm_op_ddpm_step_seeded"):      # the twins the one rdm_noise argument replaced
+        assert not re.search(r"\b" + name + r"\b", src) and name not in _lib.SIGNATURES, name
     assert (_lib.PLMS_STEP, _lib.PLMS_EULER_A, _lib.PLMS_EULER_B) == (R.PLMS_STEP, R.PLMS_EULER_A, R.PLMS_EULER_B) == (0, 1, 2)
 
 
